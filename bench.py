@@ -16,9 +16,14 @@ kernel sums every 32 x 32 tile on the XCD that traced it and stores the pixels a
 frame (no resolve launch, no copy).  Several frames are in flight (one stream + context + host buffer each),
 and the timed region ends when every frame has landed.
 The frame is fixed (BASELINE: large scene, 1200x800x10 spp), so scaling is STRONG.  Inputs (sphere tables, camera)
-are resident in HBM before the timed region.  `value_device_resident` is the same run with the frames left in HBM
-(round 2's headline); `value_dispatch_to_host` is ONE synchronous frame at a time through r1_render() — what the
-drop-in's benchmark() prints.  Data is synthetic by construction: the scenes are code, not files.
+are resident in HBM before the timed region.  Data is synthetic by construction: the scenes are code, not files.
+
+A plain run sets up, warms up, times --steps frames and prints the line; nothing else runs.  `--full` adds what the
+benchmark measures and checks beside the headline: `check` (the timed frame against one synchronous r1_render),
+`value_device_resident` (the same run with the frames left in HBM, round 2's headline), `value_dispatch_to_host` (ONE
+synchronous frame at a time through r1_render() — what the drop-in's benchmark() prints), `exhaustive_sweep`,
+`value_long_run` (N > 1), the executed work of the roofline (`roofline.work`) and `cpu_baseline`.
+`--dump-outputs DIR` writes what the last timed step delivered — the frame's pixels and ray count — as DIR/*.npy.
 """
 import argparse
 import json
@@ -239,25 +244,63 @@ def parse_args(argv=None):
                     help="with --emulate-shards K on one GPU: also run the rank path's RCCL all-gather per frame through a ONE-rank "
                          "communicator (the collective's launch cost next to a 1/K frame; the data does not leave the GPU)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only for rehearsals)")
-    ap.add_argument("--check", action="store_true", default=True,
-                    help="(default) after the timed region compare the image and ray count that landed on the host with ONE synchronous, "
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: check, secondary measurements, the roofline's executed work and the CPU baseline "
+                         "(a plain run times the steps and prints the line, nothing else)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last one delivered (pixels, ray count) as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--check", action="store_true", default=None,
+                    help="(default with --full) after the timed region compare the image and ray count that landed on the host with ONE synchronous, "
                          "unsharded r1_render of the same frame — another build of the kernel (latency mode), so `check: true` in the line "
                          "says the timed frames' pixels and count are the frame's")
     ap.add_argument("--no-check", dest="check", action="store_false")
     ap.add_argument("--pixel-mode", action="store_true",
                     help="r1_set_pixel_mode: lanes own pixels, 3 B/pixel written, no per-sample workspace, no resolve launch (~10 %% slower)")
     ap.add_argument("--no-host-copy", action="store_true", help="`value` = frames left in HBM (round 2's headline mode), no copies to the host")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary measurements (device-resident run, exhaustive sweep, r1_render span)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the secondary measurements (device-resident run, exhaustive sweep, r1_render span)")
     ap.add_argument("--lib", default="", help="another build of librays1.so (e.g. rays1bench_amd/lib/librays1_tuning.so, `make tuning`: "
                                               "the build that reads the R1_* tuning knobs); default: the shipped library")
     ap.add_argument("--cpu-table", action="store_true",
                     help="also time the reference's step13 (all threads / 1 thread) on the three scenes and the step1 port "
-                         "on the host cores (cpu_baseline.table; adds ~30 s)")
+                         "on the host cores (cpu_baseline.table; adds ~30 s; needs --full)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.cpu_table and not args.full:
+        ap.error("--cpu-table extends the CPU baseline of --full")
+    if args.check is None:
+        args.check = args.full
+    if not args.full:
+        args.no_extras = args.no_cpu_baseline = True  # a plain run: the timed steps and the line
     if args.lib:
         args.lib = os.path.abspath(args.lib)  # (resolved where the command was given)
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
     return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, image, rays):
+    """Writes one frame as the caller received it: `image` (H x W x 3 pixel values) and `rays` (the frame's ray count),
+    float32 / float64.  An image over the size limit is written as a fixed, seeded sample of its pixels plus their indices."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    img = np.asarray(image, np.float32)
+    out = {"rays": np.array([rays], np.float64)}
+    if img.nbytes <= DUMP_LIMIT_BYTES // 2:
+        out["image"] = img
+    else:
+        px = img.reshape(img.shape[0] * img.shape[1], -1) if img.ndim == 3 else img.reshape(-1, 1)
+        keep = (DUMP_LIMIT_BYTES // 2) // (px.shape[1] * 4 + 8)
+        idx = np.sort(np.random.default_rng(0).choice(px.shape[0], keep, replace=False))
+        out["image_sample"] = px[idx]
+        out["image_sample_index"] = idx.astype(np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def self_launch(args):
@@ -327,6 +370,7 @@ def run_inproc(args):
     img = np.zeros((h, w, 3), np.uint8)
     counter = [0]
     dev_s = [0.0]
+    last_rays = [0]
 
     def step():
         k = (counter[0] // B) % lanes
@@ -334,6 +378,7 @@ def run_inproc(args):
         if lanes == 1:
             rays, s = multis[0].render_into(p, img)
             dev_s[0] += s
+            last_rays[0] = rays
             return rays
         pending[k] += 1
         if pending[k] == B:
@@ -366,6 +411,13 @@ def run_inproc(args):
     submit = time.perf_counter() - t0
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        last = args.steps - 1  # its frame: record last % B of the batch of r1_multi object (last // B) % lanes
+        if lanes > 1:
+            hf = hosts[(last // B) % lanes]
+            dump_outputs(args.dump_outputs, hf.image(last % B), hf.rays(last % B))
+        else:
+            dump_outputs(args.dump_outputs, img, last_rays[0])
     if lanes > 1:
         rays_per_step = hosts[0].rays(0)
         img = hosts[0].image(0).copy()
@@ -646,6 +698,21 @@ def run_ranks(args):
     for k_ in submit_max:
         submit_max[k_] = 0.0
     elapsed, submit, (trace_ms_sum, total_ms_sum, launches) = timed(args.steps, with_events=True)
+    if args.dump_outputs and rank == 0:
+        # the last timed step's frame: record last % B of the last launch of slot (last // B) % len(slots)
+        last = args.steps - 1
+        sl, j = slots[(last // B) % len(slots)], last % B
+        if sharded and n == 1:  # emulated rank: its own record (tile block + its rays) is what the step delivered
+            rec = sl.records[j * record_bytes:(j + 1) * record_bytes].cpu().numpy()
+            dump_outputs(args.dump_outputs, rec[:block_bytes], int(rec[trailer:record_bytes].view(np.int64)[0]))
+        elif host_copy[0]:
+            dump_outputs(args.dump_outputs, sl.host.image(j), sl.host.rays(j))
+        elif sharded or args.pixel_mode:  # frames left in HBM: the assembled frame record
+            rec = sl.frames[j * frec:(j + 1) * frec].cpu().numpy()
+            dump_outputs(args.dump_outputs, rec[:img_bytes].reshape(h, w, 3), int(rec[frec - 8:frec].view(np.uint64)[0]))
+        else:  # whole frames left in the context's device buffers: the same frame brought home by the same kernel
+            rays_ = sl.frame_rays()
+            dump_outputs(args.dump_outputs, sl.host.image(0), rays_)
     submit_max_timed = dict(submit_max)
     frames = args.steps
     value = rays_per_step * args.steps / elapsed / 1e6
@@ -716,7 +783,7 @@ def run_ranks(args):
     # ---- what the timed kernel executes (measured, outside the timed region): one synchronous frame
     # through the diagnostic build of the same kernel (R1_VARIANT_*_STATS: same samples, plus counters)
     work = None
-    if rank == 0 and (info["kernel"] == 4 or (info["kernel"] == 2 and info["spheres_active"] <= 1023)):
+    if args.full and rank == 0 and (info["kernel"] == 4 or (info["kernel"] == 2 and info["spheres_active"] <= 1023)):
         try:
             work = measure_work(rend, p, info, binding)
         except Exception as e:  # diagnostics never fail the bench

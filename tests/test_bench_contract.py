@@ -1,5 +1,5 @@
 """The bench line contract (no GPU): the committed line of the round (profiles/rNN/bench_line.json,
-written by `python bench.py` on the GPU box) carries every field the driver and the judge read, no
+written by `python bench.py --full` on the GPU box) carries every field the driver and the judge read, no
 field named `frac` exceeds 1, every roofline number can be recomputed from the other fields of the
 line, and bench.py's defaults are the contract's (N = 1, a K/W that finishes in minutes)."""
 import glob
@@ -147,3 +147,43 @@ def test_hardware_queue_budget_is_explicit_and_below_the_cliff():
     sys.path.insert(0, ROOT)
     bench = importlib.import_module("bench")
     assert bench.INFLIGHT_SINGLE <= bench.QUEUES_SINGLE < bench.QUEUES_CLIFF and bench.INFLIGHT_RANK < bench.QUEUES_RANK < bench.QUEUES_CLIFF
+
+
+def test_plain_run_is_lean_and_full_keeps_the_secondary_measurements():
+    """A plain `bench.py --gpus 1 --steps N --warmup W` times the steps and prints the line; the check, the secondary
+    measurements and the CPU baseline run with --full only (and --check alone still asks for the check)."""
+    import importlib
+    import sys
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    plain = bench.parse_args(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert not plain.full and plain.check is False and plain.no_extras and plain.no_cpu_baseline and plain.steps == 5
+    full = bench.parse_args(["--full"])
+    assert full.full and full.check is True and not full.no_extras and not full.no_cpu_baseline
+    assert bench.parse_args(["--full", "--no-check"]).check is False and bench.parse_args(["--check"]).check is True
+
+
+def test_dump_outputs_writes_float_arrays_within_the_limit(tmp_path):
+    import importlib
+    import sys
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    img = np.random.default_rng(3).integers(0, 256, (80, 120, 3), dtype=np.uint8)
+    bench.dump_outputs(str(tmp_path / "a"), img, 12345)
+    got = np.load(tmp_path / "a" / "image.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, img.astype(np.float32))
+    rays = np.load(tmp_path / "a" / "rays.npy")
+    assert rays.dtype == np.float64 and rays.tolist() == [12345.0]
+    # an image over the limit: a fixed, seeded sample of its pixels and their indices, the same every time
+    big = np.zeros((4000, 3000, 3), np.uint8)
+    big[:, :, 1] = np.arange(3000, dtype=np.uint32) % 251
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big, 7)
+    total = sum(os.path.getsize(os.path.join(tmp_path, "b", f)) for f in os.listdir(tmp_path / "b"))
+    assert total <= bench.DUMP_LIMIT_BYTES and not os.path.exists(tmp_path / "b" / "image.npy")
+    idx = np.load(tmp_path / "b" / "image_sample_index.npy")
+    px = np.load(tmp_path / "b" / "image_sample.npy")
+    assert idx.dtype == np.float64 and px.dtype == np.float32 and len(idx) == len(px) > 0
+    assert np.array_equal(px, big.reshape(-1, 3)[idx.astype(np.int64)].astype(np.float32))
+    assert np.array_equal(idx, np.load(tmp_path / "c" / "image_sample_index.npy"))

@@ -637,3 +637,33 @@ def test_throughput_entry_point_equals_the_synchronous_one(case):
             assert out.cpu().numpy().tobytes() == ref.tobytes()
     finally:
         rend.close()
+
+
+def test_plain_bench_run_dumps_the_last_timed_frame(tmp_path):
+    """`bench.py --dump-outputs DIR` (a plain run: no check, no secondary measurements): the pixels and ray count of the last
+    timed frame, as float32 / float64 .npy files, equal ONE synchronous r1_render of the same frame."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    w, h, spp, seed = 300, 200, 4, 10001
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--width", str(w),
+                          "--height", str(h), "--spp", str(spp), "--dump-outputs", str(tmp_path / "out")],
+                         capture_output=True, timeout=600, cwd=root, env={k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK")})
+    assert out.returncode == 0, out.stderr.decode()[-2000:]
+    line = json.loads(out.stdout.decode().strip().splitlines()[-1])
+    assert line["steps"] == 7 and line["ms_per_step"] > 0 and line["value"] > 0
+    for k in ("check", "cpu_baseline", "value_device_resident", "value_dispatch_to_host", "exhaustive_sweep"):
+        assert k not in line, k
+    img = np.load(tmp_path / "out" / "image.npy")
+    rays = np.load(tmp_path / "out" / "rays.npy")
+    assert img.dtype == np.float32 and img.shape == (h, w, 3) and rays.dtype == np.float64 and rays.shape == (1,)
+    rend = r1.Renderer(0)
+    try:
+        rend.set_scene(r1.create_large_scene(w, h))
+        ref, ref_rays, _ = rend.render(r1.make_params(w, h, spp, seed))
+    finally:
+        rend.close()
+    assert int(rays[0]) == ref_rays == line["config"]["rays_per_step"]
+    assert np.array_equal(img, ref.astype(np.float32))

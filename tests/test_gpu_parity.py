@@ -549,7 +549,7 @@ def test_bench_two_ranks_rehearsal_gathers_the_unsharded_frame():
     env = dict(os.environ, R1_BENCH_DEVICE="0")
     # the BARE entry: bench.py starts its two ranks itself (fresh processes, before it touches HIP) and relays their line
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo",
-                          "--steps", "6", "--warmup", "2", "--inflight", "4", "--check", "--width", "300", "--height", "200", "--spp", "4"],
+                          "--steps", "6", "--warmup", "2", "--inflight", "4", "--full", "--check", "--width", "300", "--height", "200", "--spp", "4"],
                          capture_output=True, timeout=600, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr.decode()[-2000:]
     line = json.loads(out.stdout.decode().strip().splitlines()[-1])

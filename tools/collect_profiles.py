@@ -25,7 +25,7 @@ def means(c, match):
 
 tp, lat, pix, sw = ("r1_trace_kernel<4, false, false, 0>", "r1_trace_kernel<4, false, false, 1>", "r1_trace_kernel<4, false, false, 2>",
                     "r1_trace_kernel<2, false, false, 0>")
-cmd = "rocprofv3 --pmc <counters> --kernel-trace -- python3 bench.py --no-cpu-baseline --steps 3 --warmup 1 --inflight 1 (tools/profile_round.sh); mean per dispatch"
+cmd = "rocprofv3 --pmc <counters> --kernel-trace -- python3 bench.py --full --no-cpu-baseline --steps 3 --warmup 1 --inflight 1 (tools/profile_round.sh); mean per dispatch"
 counters = {"command": cmd, "workload": "large 1200x800x10",
             "tree kernel, frames in flight (MODE 0)": {k: v[0] for k, v in {**means("pmc_sq1", tp), **means("pmc_sq2", tp)}.items()},
             "tree kernel, synchronous frame (MODE 1, 1536 workgroups)": {k: v[0] for k, v in {**means("pmc_sq1", lat), **means("pmc_sq2", lat)}.items()},
@@ -65,7 +65,7 @@ if c20:
     if "SQ_ACTIVE_INST_VALU" in v and "SQ_BUSY_CYCLES" in v:
         # a SIMD issues one VALU instruction of one wave at a time: busy VALU quad-cycles summed over waves / (SQ busy cycles x 4 SIMDs per CU ... per SE)
         derived["valu_quadcycles_per_sq_busy_cycle"] = v["SQ_ACTIVE_INST_VALU"] / v["SQ_BUSY_CYCLES"]
-    json.dump({"command": "rocprofv3 --pmc <counters> --kernel-trace -- python3 bench.py --no-cpu-baseline --no-extras --steps 40 --warmup 20 "
+    json.dump({"command": "rocprofv3 --pmc <counters> --kernel-trace -- python3 bench.py --full --no-cpu-baseline --no-extras --steps 40 --warmup 20 "
                           "(20 frames in flight: the timed configuration); mean per dispatch of r1_trace_kernel<4,false,false,0>",
                "workload": "large 1200x800x10", "counters": v, "dispatch_overlap_under_collection": ov, "derived": derived,
                "note": "rocprofv3 reads the counters per dispatch; `dispatch_overlap_under_collection` says whether the 20 frames in flight still "
@@ -81,7 +81,7 @@ traffic = {"workload": "large 1200x800x10", "kernel": "r1_trace_kernel<4,false,f
            # the build the counters belong to: bench.py quotes them only while it runs the same library.  The
            # profile run writes the hash next to its outputs (tools/profile_round.sh: lib_sha16.txt)
            "lib_sha16": (open(f"{out}/lib_sha16.txt").read().strip() if os.path.exists(f"{out}/lib_sha16.txt") else None),
-           "source": f"profiles/{tag}/pmc_hbm_traffic.json (rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE, separate passes, bench.py --no-cpu-baseline "
+           "source": f"profiles/{tag}/pmc_hbm_traffic.json (rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE, separate passes, bench.py --full --no-cpu-baseline "
                      f"--steps 3 --warmup 1 --inflight 1; mean over {f['FETCH_SIZE'][1]} dispatches)",
            "FETCH_SIZE_KB": f["FETCH_SIZE"][0], "WRITE_SIZE_KB": w["WRITE_SIZE"][0],
            "correction": "MI355X_MICROARCH.md §HBM: on gfx950 FETCH_SIZE reports 1/2 of the bytes of a wide coalesced read -> x2; WRITE_SIZE taken as is",
@@ -108,7 +108,7 @@ try:
     short["1"] = json.loads(open(f"{out}/bench_line_driver_command.json").read().strip().splitlines()[-1])["ms_per_step"]
 except Exception:
     pass
-em = {"command": "python bench.py --steps 320 --warmup 32 --no-cpu-baseline --no-extras --emulate-shards N --rccl-selftest (one GPU carries rank 0's tiles of an N-GPU run through "
+em = {"command": "python bench.py --full --steps 320 --warmup 32 --no-cpu-baseline --no-extras --emulate-shards N --rccl-selftest (one GPU carries rank 0's tiles of an N-GPU run through "
                  "the rank path: frame batches, one RCCL all-gather per launch through a one-rank communicator, copies to the host); N = 1: the bench line",
       "ms_per_frame_steps20": short,
       "ms_per_frame": ms, "fraction_of_ideal": {k: one / int(k) / v for k, v in ms.items() if k != "1"},

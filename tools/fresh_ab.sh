@@ -6,7 +6,7 @@ L=rays1bench_amd/lib
 timeout -k 10 900 python -m pytest tests -x -q -m gpu > gpurun_out/fresh_tests.log 2>&1 || { tail -30 gpurun_out/fresh_tests.log; exit 1; }
 tail -2 gpurun_out/fresh_tests.log
 get='import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(sys.argv[1], round(d["value"]), "%.4f" % d["ms_per_step"], "sync", (d.get("value_dispatch_to_host") or {}).get("value"))'
-run() { local label=$1 so=$2; shift 2; python bench.py --lib $so --no-cpu-baseline "$@" 2>/dev/null | python -c "$get" "$label"; }
+run() { local label=$1 so=$2; shift 2; python bench.py --full --lib $so --no-cpu-baseline "$@" 2>/dev/null | python -c "$get" "$label"; }
 for i in 1 2 3; do
   for so in librays1.so librays1_nofresh.so; do
     run "$so 300" $L/$so --steps 300 --warmup 20 --no-extras
