@@ -126,9 +126,16 @@ enum
     R1_VARIANT_BVH_STATS = 5, /* BVH plus traversal counters (diagnostic; r1_last_stats slots [2] node-loop trips,
                                  [3] leaf-loop trips, [5] sphere-pair tests, [9] node visits, [14] leaf trips x lanes, [15] root steps: the root's leaf and
                                  the box of its other child tested outside the walk's loops) */
-    R1_VARIANT_WAVEFRONT = 6  /* the same tracer as separate generate / intersect / shade kernels with the paths
+    R1_VARIANT_WAVEFRONT = 6, /* the same tracer as separate generate / intersect / shade kernels with the paths
                                  and per-level queues in HBM; a comparison build: same pixels,
                                  slower than the megakernel; frames of <= 2^24 sample slots       */
+    R1_VARIANT_GRID = 7,      /* optional uniform grid: outliers tested by every ray, then
+                                 a cell walk presents the registered spheres to the reference's per-sphere test; rays
+                                 whose origin is too far for the grid's pad take the tree walk (fallback).  Built on the
+                                 first render that asks for it after r1_set_scene; bit-identical to the exhaustive sweeps */
+    R1_VARIANT_GRID_STATS = 8 /* GRID plus walk counters (diagnostic; r1_last_stats slots [2] wave trips of the cell-walk
+                                 loop, [5] sphere tests summed over lanes (outliers and cells), [9] cell steps summed over
+                                 lanes, [14] lanes that took the fallback, [15] outlier tests summed over lanes) */
 };
 
 typedef struct r1_context r1_context; /* opaque: device, stream, events, workspace */
@@ -375,6 +382,36 @@ typedef struct r1_bvh_info
 } r1_bvh_info;
 int r1_bvh_describe(const r1_scene *scene, int32_t leaf_max, r1_bvh_info *info, float *nodes_out, size_t nodes_cap, uint32_t *ids_out,
                     size_t ids_cap);
+
+/* Shape of the uniform grid R1_VARIANT_GRID uses (r1_grid.cpp), built on the host exactly as the render path builds it.  Optional
+ * outputs: `start_out` the cells' CSR offsets (cells[0] * cells[1] * cells[2] + 1 entries; cell (jx, jy, jz) is
+ * (jz * cells[1] + jy) * cells[0] + jx), `ids_out` the registered spheres of each cell (`registrations` entries, scene indices, ascending
+ * within a cell), `outliers_out` the spheres every ray tests before the walk (`outliers` entries, scene indices). */
+typedef struct r1_grid_info
+{
+    float lo[3], hi[3];     /* the grid's box: cell j of axis a spans [lo + j cell, lo + (j + 1) cell] */
+    int32_t cells[3];       /* cells per axis (a flat axis has one) */
+    float cell[3];          /* cell size per axis */
+    float pad;              /* registration pad: the largest rho_i - r_i of a registered sphere (its ball of radius rho_i is registered) */
+    float v_safe;           /* V: the grid is exact for rays whose origin lies within V of every registered centre; the others take the
+                               tree walk (plays the part of a t_safe, see r1_grid.cpp) */
+    float centre_lo[3], centre_hi[3]; /* box of the registered centres (the fallback test: farthest point of it from the origin > V) */
+    int32_t spheres;        /* active spheres */
+    int32_t outliers;       /* spheres tested by every ray */
+    int32_t registrations;  /* entries of all cells together */
+    int32_t max_occupancy;  /* most spheres in one cell */
+    float build_ms;         /* host time of the build */
+} r1_grid_info;
+int r1_grid_describe(const r1_scene *scene, r1_grid_info *info, uint32_t *start_out, size_t start_cap, uint32_t *ids_out, size_t ids_cap,
+                     uint32_t *outliers_out, size_t outliers_cap);
+
+/* One ray through the grid on the host, in the kernel's own arithmetic (r1_grid_dda.h) and with its stopping rule: `presented`
+ * receives (up to `cap`) the scene indices of the spheres given to the per-sphere test, in order — the outliers, then the walked
+ * cells' lists — and *n_presented their number; *hit_index / *hit_t the final hit (minimum offer, ties to the lowest index; -1 and
+ * FLT_MAX for none); *fallback = 1 if the ray takes the tree walk instead (its hit is then the exhaustive minimum, which that walk
+ * returns).  Builds the grid on every call.  No GPU needed. */
+int r1_grid_visit(const r1_scene *scene, const float o[3], const float d[3], uint32_t *presented, size_t cap, size_t *n_presented,
+                  int32_t *hit_index, float *hit_t, int32_t *fallback);
 
 enum
 {

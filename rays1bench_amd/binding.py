@@ -18,6 +18,7 @@ LIBDIR = os.path.join(HERE, "lib")
 R1_OK, R1_EINVAL, R1_ENODEVICE, R1_EHIP, R1_ENOMEM, R1_ELIMIT = 0, -1, -2, -3, -4, -5
 SCENE_SMALL, SCENE_MEDIUM, SCENE_LARGE, SCENE_GRID = 0, 1, 2, 3
 VARIANT_DEFAULT, VARIANT_REFERENCE, VARIANT_PREFILTER, VARIANT_STATS, VARIANT_BVH, VARIANT_BVH_STATS, VARIANT_WAVEFRONT = 0, 1, 2, 3, 4, 5, 6
+VARIANT_GRID, VARIANT_GRID_STATS = 7, 8
 
 
 
@@ -105,6 +106,12 @@ def build(verbose=False):
     subprocess.check_call(["make", "-j4", "-C", CSRC] + ([] if verbose else ["-s"]))
 
 
+class GridInfo(C.Structure):
+    _fields_ = [("lo", C.c_float * 3), ("hi", C.c_float * 3), ("cells", C.c_int32 * 3), ("cell", C.c_float * 3), ("pad", C.c_float),
+                ("v_safe", C.c_float), ("centre_lo", C.c_float * 3), ("centre_hi", C.c_float * 3), ("spheres", C.c_int32),
+                ("outliers", C.c_int32), ("registrations", C.c_int32), ("max_occupancy", C.c_int32), ("build_ms", C.c_float)]
+
+
 # every symbol include/rays1.h declares: (name, restype, argtypes)
 _u8p, _f32p, _u64p, _i32p, _dblp = (C.POINTER(t) for t in (C.c_uint8, C.c_float, C.c_uint64, C.c_int32, C.c_double))
 _ctx = C.c_void_p
@@ -154,6 +161,9 @@ SYMBOLS = [
     ("r1_host_scene_spheres", C.POINTER(CScene), [C.c_void_p]),
     ("r1_host_scene_camera", C.POINTER(CCamera), [C.c_void_p]),
     ("r1_bvh_describe", C.c_int, [C.POINTER(CScene), C.c_int32, C.POINTER(BvhInfo), _f32p, C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t]),
+    ("r1_grid_describe", C.c_int, [C.POINTER(CScene), C.POINTER(GridInfo), C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t,
+                                   C.POINTER(C.c_uint32), C.c_size_t]),
+    ("r1_grid_visit", C.c_int, [C.POINTER(CScene), _f32p, _f32p, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_size_t), _i32p, _f32p, _i32p]),
     ("r1_tga_write_rgb24", C.c_int, [C.c_char_p, C.c_int32, C.c_int32, _u8p]),
     ("r1_log_results", C.c_int, [C.c_char_p, C.c_char_p, _dblp, _u64p, C.c_int32]),
 ]
@@ -346,6 +356,7 @@ class Renderer:
         d["span_cycles"] = int(out[12]) - (m - int(out[13]))
         d["leaf_lane_trips"] = int(out[14])  # tree diagnostic build: leaf trips summed over lanes
         d["root_steps"] = int(out[15])       # tree diagnostic build: root steps (one box test + the root's leaf, outside the walk's loops)
+        d["raw"] = [int(x) for x in out]     # (the grid's diagnostic build: include/rays1.h R1_VARIANT_GRID_STATS names its slots)
         return d
 
     def wave_log(self):
@@ -526,6 +537,39 @@ def bvh_describe(cscene, leaf_max=0):
     d = {k: int(getattr(info, k)) for k, _ in BvhInfo._fields_ if k != "centre"}
     d["centre"] = np.array(list(info.centre), np.float32)
     return d, nodes, ids[:2 * info.pairs]
+
+
+def grid_describe(cscene):
+    """Host-side build of the R1_VARIANT_GRID index: (info dict, start uint32[cells + 1], ids uint32[registrations], outliers uint32[n]);
+    ids and outliers are scene indices."""
+    info = GridInfo()
+    _check(lib().r1_grid_describe(C.byref(cscene), C.byref(info), None, 0, None, 0, None, 0))
+    ncells = int(info.cells[0]) * int(info.cells[1]) * int(info.cells[2])
+    start = np.zeros(ncells + 1, np.uint32)
+    ids = np.zeros(max(info.registrations, 1), np.uint32)
+    outl = np.zeros(max(info.outliers, 1), np.uint32)
+    u32p = C.POINTER(C.c_uint32)
+    _check(lib().r1_grid_describe(C.byref(cscene), C.byref(info), start.ctypes.data_as(u32p), start.size, ids.ctypes.data_as(u32p), ids.size,
+                                  outl.ctypes.data_as(u32p), outl.size))
+    d = {}
+    for k, t in GridInfo._fields_:
+        v = getattr(info, k)
+        d[k] = np.array(list(v), np.float32 if k != "cells" else np.int64) if hasattr(v, "__len__") else v
+    return d, start, ids[:info.registrations], outl[:info.outliers]
+
+
+def grid_visit(cscene, o, d, cap=1 << 16):
+    """One ray through the grid on the host, in the kernel's arithmetic: (presented scene indices in order, hit index or -1, hit t,
+    fallback flag)."""
+    o = np.ascontiguousarray(o, np.float32)
+    d = np.ascontiguousarray(d, np.float32)
+    pres = np.zeros(cap, np.uint32)
+    n, hi, ht, fb = C.c_size_t(), C.c_int32(), C.c_float(), C.c_int32()
+    _check(lib().r1_grid_visit(C.byref(cscene), o.ctypes.data_as(_f32p), d.ctypes.data_as(_f32p), pres.ctypes.data_as(C.POINTER(C.c_uint32)), cap,
+                               C.byref(n), C.byref(hi), C.byref(ht), C.byref(fb)))
+    if n.value > cap:
+        return grid_visit(cscene, o, d, int(n.value))
+    return pres[:n.value], int(hi.value), float(ht.value), bool(fb.value)
 
 
 class RESULT:

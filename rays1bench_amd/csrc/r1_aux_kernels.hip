@@ -277,7 +277,7 @@ extern "C" hipError_t r1_launch_put6(void *dst, const uint32_t *w, hipStream_t s
     return hipGetLastError();
 }
 
-// The trace kernel's instantiations live in four translation units (tree / exhaustive sweep x small / big scenes); each exports one
+// The trace kernel's instantiations live in six translation units (tree / exhaustive sweep / uniform grid x small / big scenes); each exports one
 // launch and one occupancy function for its family.
 #define R1_TU_DECL(NAME)                                                                                                               \
     extern "C" hipError_t r1_tu_##NAME##_launch(const R1TraceArgs *args, int variant, int mode, int batch, int blocks, size_t dyn_lds, \
@@ -287,6 +287,8 @@ R1_TU_DECL(tree_small)
 R1_TU_DECL(tree_big)
 R1_TU_DECL(sweep_small)
 R1_TU_DECL(sweep_big)
+R1_TU_DECL(grid_small)
+R1_TU_DECL(grid_big)
 #undef R1_TU_DECL
 
 // The kernel mode that is built for (variant, big) given what the caller would like (0 samples + one guided queue,
@@ -296,23 +298,27 @@ extern "C" int r1_trace_mode(int variant, int big, int wanted)
 {
     if (variant == 1)
         return 0;
-    if (variant == 3 || variant == 5)
+    if (variant == 3 || variant == 5 || variant == 8)
         return big ? 0 : 1;
     if (wanted == 1)
         return big ? 0 : 1;
     return wanted == 2 ? 2 : 0;
 }
 
-extern "C" hipError_t r1_launch_trace(const R1TraceArgs *args, int variant, int big_in, int mode, int blocks, hipStream_t stream)
+// grid_lds: the grid kernels' 16-bit tables in LDS (small scenes; R1GridArgs::lds_bytes, which lives in device memory)
+extern "C" hipError_t r1_launch_trace(const R1TraceArgs *args, int variant, int big_in, int mode, int blocks, size_t grid_lds, hipStream_t stream)
 {
     // dynamic LDS of the tree kernels: the traversal stack, one entry per inner node on a path, and (small scenes) the node table
     const bool big = big_in != 0; // 32-bit hit indices, attenuation stack in the global workspace
     const bool tree = variant == 4 || variant == 5;
     const size_t trav = tree ? (size_t)args->bvh_depth * R1_BLOCK * (big ? sizeof(uint32_t) : sizeof(uint16_t)) + (size_t)args->bvh_lds_f4 * 16 + R1_ENTRY_LDS_BYTES(args->entry_lds) : 0;
+    // uniform grid: the fallback's traversal stack (32-bit entries) and (small scenes) the grid's 16-bit tables
+    const bool grid = variant == 7 || variant == 8;
+    const size_t gtrav = grid ? (size_t)args->bvh_depth * R1_BLOCK * sizeof(uint32_t) + (big ? 0 : (size_t)grid_lds) : 0;
     if (mode != r1_trace_mode(variant, big_in, mode))
         return hipErrorInvalidValue; // the caller sizes its arguments by the mode: it must be the one that is built
-    const int batch = args->batch != nullptr; // frame batches: the MODE 3 build of the throughput kernels (variants 2 and 4 only)
-    if (batch && (mode != 0 || (variant != 2 && variant != 4)))
+    const int batch = args->batch != nullptr; // frame batches: the MODE 3 build of the throughput kernels (variants 2, 4 and 7 only)
+    if (batch && (mode != 0 || (variant != 2 && variant != 4 && variant != 7)))
         return hipErrorInvalidValue;
     if (variant == 3 && big)
         variant = 2; // (no diagnostic build of the LDS-tiled sweep)
@@ -325,6 +331,12 @@ extern "C" hipError_t r1_launch_trace(const R1TraceArgs *args, int variant, int 
         return hipErrorInvalidValue;
     if (tree)
         return big ? r1_tu_tree_big_launch(args, variant, mode, batch, blocks, trav, stream) : r1_tu_tree_small_launch(args, variant, mode, batch, blocks, trav, stream);
+    if (grid && args->grid == nullptr)
+        return hipErrorInvalidValue; // (the grid kernels read their tables through this pointer)
+    if (grid && mode == 2 && !big)
+        return hipErrorInvalidValue; // (the grid's PIXEL mode runs through its big-scene kernel)
+    if (grid)
+        return big ? r1_tu_grid_big_launch(args, variant, mode, batch, blocks, gtrav, stream) : r1_tu_grid_small_launch(args, variant, mode, batch, blocks, gtrav, stream);
     return big ? r1_tu_sweep_big_launch(args, variant, mode, batch, blocks, 0, stream) : r1_tu_sweep_small_launch(args, variant, mode, batch, blocks, 0, stream);
 }
 
@@ -335,6 +347,8 @@ extern "C" hipError_t r1_trace_occupancy(int variant, int big, int mode, size_t 
         variant = 2;
     if (tree)
         return big ? r1_tu_tree_big_occupancy(variant, mode, dyn_lds, blocks_per_cu) : r1_tu_tree_small_occupancy(variant, mode, dyn_lds, blocks_per_cu);
+    if (variant == 7 || variant == 8)
+        return big ? r1_tu_grid_big_occupancy(variant, mode, dyn_lds, blocks_per_cu) : r1_tu_grid_small_occupancy(variant, mode, dyn_lds, blocks_per_cu);
     return big ? r1_tu_sweep_big_occupancy(variant, mode, 0, blocks_per_cu) : r1_tu_sweep_small_occupancy(variant, mode, 0, blocks_per_cu);
 }
 

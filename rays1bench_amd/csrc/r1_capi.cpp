@@ -21,8 +21,9 @@
 
 #include "../../include/rays1.h"
 #include "r1_device.h"
+#include "r1_grid.h"
 
-extern "C" hipError_t r1_launch_trace(const R1TraceArgs *args, int variant, int big, int mode, int blocks, hipStream_t stream);
+extern "C" hipError_t r1_launch_trace(const R1TraceArgs *args, int variant, int big, int mode, int blocks, size_t grid_lds, hipStream_t stream);
 extern "C" int r1_trace_mode(int variant, int big, int wanted); // 0 samples + one queue, 1 latency, 2 pixel: what is built for (variant, big)
 extern "C" hipError_t r1_launch_resolve(const R1ResolveArgs *args, int max_rows, hipStream_t stream);
 extern "C" hipError_t r1_launch_wavefront(R1WaveArgs *w, int blocks, hipStream_t stream);
@@ -103,6 +104,12 @@ struct r1_context
     // scene
     DevBuf sweep, exact, exact_g, shade, mat, members;
     DevBuf bvh_nodes, bvh_prims, bvh_ids; // R1_VARIANT_BVH (r1_bvh.cpp)
+    // R1_VARIANT_GRID (r1_grid.cpp): built on the first render that asks for it after r1_set_scene (ensure_grid)
+    DevBuf grid_tab, grid_out, grid_dev;  // cell table + ids, outliers, the R1GridArgs the kernels read
+    DevBuf grid_tab32, grid_dev32;        // the same in the big-scene kernel's 32-bit form (small scenes: for PIXEL mode, see enqueue_frame)
+    bool grid_valid = false;
+    bool grid_small = false;  // 16-bit tables that the small-scene kernel keeps in LDS
+    R1GridArgs grid_args;     // (pointers into grid_tab / grid_out; a copy of it in grid_dev)
     DevBuf wf_paths, wf_hits, wf_queue, wf_counts; // R1_VARIANT_WAVEFRONT workspace
     DevBuf wave_log;                               // STATS builds: per-wave {start, queue empty, end, iterations}
     unsigned long long wave_log_ptr = 0;
@@ -148,7 +155,7 @@ struct r1_context
     unsigned long long *host_word = nullptr, *host_word_dev = nullptr;
     int default_variant = 4;    // what R1_VARIANT_DEFAULT resolves to for the scene in the context (r1_set_scene): synchronous frames
     int default_variant_tp = 4; // ... and frames in flight (the throughput kernels: measured apart, the two kernel families do not rank alike)
-    int occupancy[48] = {0}; // [variant + 8 * big + 16 * mode]
+    int occupancy[96] = {0}; // [variant + 16 * big + 32 * mode]
     bool pixel_mode = false; // r1_set_pixel_mode
     DevBuf gstack; // blocks per CU of the trace kernel, by variant
     // per-tile entry nodes for primary rays (R1_ENTRY): the tree's nodes on the host, the device table, what it was computed for
@@ -270,7 +277,7 @@ extern "C" void r1_destroy(r1_context *c)
     if (c->stream)
         (void)hipStreamSynchronize(c->stream);
     release(c->sweep), release(c->exact), release(c->exact_g), release(c->shade), release(c->mat), release(c->members);
-    release(c->bvh_nodes), release(c->bvh_prims), release(c->bvh_ids);
+    release(c->bvh_nodes), release(c->bvh_prims), release(c->bvh_ids), release(c->grid_tab), release(c->grid_out), release(c->grid_dev), release(c->grid_tab32), release(c->grid_dev32);
     release(c->wf_paths), release(c->wf_hits), release(c->wf_queue), release(c->wf_counts);
     release(c->bvh_wide), release(c->bvh_entry), release(c->land_spill), release(c->gstack), release(c->counters), release(c->samples), release(c->image), release(c->batch_rays);
     release(c->wave_log);
@@ -575,6 +582,7 @@ extern "C" int r1_set_scene(r1_context *c, const r1_scene *s, const r1_camera *c
             return R1_OK; // bit-identical scene and camera: everything on the device is current
     }
     c->have_scene = false;
+    c->grid_valid = false;
 
     // active spheres: inv_radius != 0 (rayweek1.cpp:291); order preserved so that ties keep
     // the earlier index as in the reference's in-order resolve loop
@@ -1024,6 +1032,73 @@ static void *mapped_host(const void *ptr)
     return at.type == hipMemoryTypeHost ? at.devicePointer : nullptr;
 }
 
+// R1_VARIANT_GRID: builds the uniform grid of the context's scene (from the arrays r1_set_scene received, so that r1_grid_describe and
+// r1_grid_visit see the same grid) and uploads it, once per scene.  Contexts that never ask for the grid pay nothing for it.
+static int ensure_grid(r1_context *c)
+{
+    if (c->grid_valid)
+        return R1_OK;
+    r1_scene s;
+    s.count = (uint32_t)c->src_mat.size();
+    s.center_x = c->src_f32[0].data(), s.center_y = c->src_f32[1].data(), s.center_z = c->src_f32[2].data();
+    s.radius_sq = c->src_f32[3].data(), s.inv_radius = c->src_f32[4].data(), s.mat_type = c->src_mat.data();
+    s.albedo_r = c->src_f32[5].data(), s.albedo_g = c->src_f32[6].data(), s.albedo_b = c->src_f32[7].data(), s.mat_param = c->src_f32[8].data();
+    R1Grid g;
+    if (r1_grid_from_scene(&s, g) != R1_OK)
+    {
+        r1_set_error("grid: the scene's spheres could not be read");
+        return R1_EINVAL;
+    }
+    // small-scene kernel: 16-bit cell starts and ids, all of it copied into every workgroup's LDS
+    const size_t halves = g.start.size() + g.ids.size();
+    c->grid_small = c->n_active <= R1_MAX_ACTIVE_10BIT && halves <= R1_GRID_LDS_HALVES && g.ids.size() < 65536u;
+    std::vector<uint32_t> tab32;
+    std::vector<uint16_t> tab16;
+    size_t tab_bytes;
+    if (c->grid_small)
+    {
+        tab16.assign((halves + 7) & ~(size_t)7, 0); // (whole 16-byte rows: the kernel copies float4)
+        for (size_t q = 0; q < g.start.size(); ++q)
+            tab16[q] = (uint16_t)g.start[q];
+        for (size_t q = 0; q < g.ids.size(); ++q)
+            tab16[g.start.size() + q] = (uint16_t)g.ids[q];
+        tab_bytes = tab16.size() * 2;
+    }
+    tab32 = g.start;
+    tab32.insert(tab32.end(), g.ids.begin(), g.ids.end());
+    if (!c->grid_small)
+        tab_bytes = tab32.size() * 4;
+    std::vector<uint32_t> outl = g.outliers;
+    if (outl.empty())
+        outl.push_back(0u);
+    int rc;
+    R1_HIP(hipSetDevice(c->device));
+    R1_HIP(hipDeviceSynchronize()); // (launches of an earlier grid may still read the buffers that are about to be replaced)
+    if ((rc = ensure(c->grid_tab, tab_bytes)) || (rc = ensure(c->grid_out, outl.size() * 4)) || (rc = ensure(c->grid_tab32, tab32.size() * 4)))
+        return rc;
+    R1_HIP(hipMemcpyAsync(c->grid_tab32.p, tab32.data(), tab32.size() * 4, hipMemcpyHostToDevice, c->stream));
+    R1_HIP(hipMemcpyAsync(c->grid_tab.p, c->grid_small ? (const void *)tab16.data() : (const void *)tab32.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));
+    R1_HIP(hipMemcpyAsync(c->grid_out.p, outl.data(), outl.size() * 4, hipMemcpyHostToDevice, c->stream));
+    R1_HIP(hipStreamSynchronize(c->stream));
+    R1GridArgs &G = c->grid_args;
+    memset(&G, 0, sizeof(G));
+    G.geom = g.geom;
+    G.outliers = (const uint32_t *)c->grid_out.p;
+    G.n_out = (uint32_t)g.outliers.size();
+    G.n_start = (uint32_t)g.start.size();
+    G.tab = (const uint32_t *)c->grid_tab.p;
+    G.lds_bytes = c->grid_small ? (uint32_t)tab_bytes : 0u;
+    R1GridArgs G32 = G;
+    G32.tab = (const uint32_t *)c->grid_tab32.p, G32.lds_bytes = 0;
+    if ((rc = ensure(c->grid_dev, sizeof(G))) || (rc = ensure(c->grid_dev32, sizeof(G))))
+        return rc;
+    R1_HIP(hipMemcpyAsync(c->grid_dev.p, c->grid_small ? &G : &G32, sizeof(G), hipMemcpyHostToDevice, c->stream));
+    R1_HIP(hipMemcpyAsync(c->grid_dev32.p, &G32, sizeof(G), hipMemcpyHostToDevice, c->stream));
+    R1_HIP(hipStreamSynchronize(c->stream));
+    c->grid_valid = true;
+    return R1_OK;
+}
+
 // Enqueues the frame (trace + resolve) on `st`.  d_out / d_rays are device addresses; d_rays == NULL stands for the context's own
 // count word (counters + R1_COUNTER_BYTES; the allocation may move in here, so callers take that address afterwards).
 static int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int block_layout, void *d_rays, hipStream_t st,
@@ -1048,10 +1123,15 @@ static int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int blo
     case R1_VARIANT_BVH: variant = 4; break;
     case R1_VARIANT_BVH_STATS: variant = 5; break;
     case R1_VARIANT_WAVEFRONT: variant = 6; break;
+    case R1_VARIANT_GRID: variant = 7; break;
+    case R1_VARIANT_GRID_STATS: variant = 8; break;
     case R1_VARIANT_DEFAULT: variant = throughput_mode ? c->default_variant_tp : c->default_variant; break;
     default: variant = 2; break;
     }
     R1_HIP(hipSetDevice(c->device));
+    const bool grid = variant == 7 || variant == 8;
+    if (grid && (rc = ensure_grid(c)))
+        return rc;
     if ((rc = ensure_counters(c, p, n_frames)))
         return rc;
     if (!d_rays)
@@ -1061,12 +1141,15 @@ static int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int blo
     // for the throughput entry point (a lane owns a pixel: no sample records, no resolve launch, ~10 % slower)
     // big-scene kernels: > 1023 hittable spheres (10-bit hit indices), or — tree kernels — a node table too large for LDS, or a tree whose
     // pad is measured per node (small spheres: only the kernels that walk the table in global memory carry that arm, bvh_advance)
-    const int big_scene_ = (c->n_active > R1_MAX_ACTIVE_10BIT || ((variant == 4 || variant == 5) && (c->n_bvh_nodes > R1_NODES_LDS_MAX || c->bvh_pad_local))) ? 1 : 0;
+    // (grid kernels: tables too large for LDS — the small-scene grid kernel's fallback reads the tree from global memory, any tree will do —
+    // and PIXEL mode, which the grid runs through its big-scene kernel only: the small one's PIXEL build would spill)
+    const int big_scene_ = (c->n_active > R1_MAX_ACTIVE_10BIT || ((variant == 4 || variant == 5) && (c->n_bvh_nodes > R1_NODES_LDS_MAX || c->bvh_pad_local)) ||
+                            (grid && (!c->grid_small || (throughput_mode && c->pixel_mode)))) ? 1 : 0;
     static const int tp_mode_env = (int)r1_knob("R1_TP_MODE", -1); // tuning experiments
     const int tp_mode = c->pixel_mode ? 2 : (tp_mode_env >= 0 && tp_mode_env <= 2 ? tp_mode_env : 0);
     const int mode = variant == 6 ? 0 : r1_trace_mode(variant, big_scene_, throughput_mode ? tp_mode : 1);
     const bool pixel_mode = mode == 2;
-    if (batch && (mode != 0 || variant == 6 || variant == 3 || variant == 5 || variant == 1))
+    if (batch && (mode != 0 || variant == 6 || variant == 3 || variant == 5 || variant == 8 || variant == 1))
     {
         r1_set_error("frame batches run through the throughput kernels only (no PIXEL mode, no diagnostic / reference-form / wavefront variant)");
         return R1_EINVAL;
@@ -1172,9 +1255,11 @@ static int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int blo
     // saves the two memset launches in front of every frame (they cost nothing to execute and ~10 us each to dispatch:
     // a rank of an 8-GPU run renders its share of a frame in 140 us).  Frames without a resolve launch, and the diagnostic
     // builds, whose counters are read back afterwards, count into the caller's word and clear with memsets.
-    const bool fused_clear = !land && !pixel_mode && c->n_local_tiles && c->total_samples && variant != 3 && variant != 5;
+    const bool fused_clear = !land && !pixel_mode && c->n_local_tiles && c->total_samples && variant != 3 && variant != 5 && variant != 8;
     a.num_rays = fused_clear ? (unsigned long long *)((char *)c->counters.p + 32) : (unsigned long long *)d_rays;
-    a.stats = (variant == 3 || variant == 5) ? (unsigned long long *)((char *)c->counters.p + 128) : nullptr;
+    a.stats = (variant == 3 || variant == 5 || variant == 8) ? (unsigned long long *)((char *)c->counters.p + 128) : nullptr;
+    if (grid)
+        a.grid = (const R1GridArgs *)(big_scene_ ? c->grid_dev32.p : c->grid_dev.p), a.scene.bvh_root_leaf = 0u; // (the grid kernels' fallback walks the tree from its root: no root step, r1_trace.hpp)
 
     // BIG kernels: 32-bit hit indices, the attenuation stack in a global workspace (the packed
     // LDS stack holds 10-bit indices) and the tree's node table through the vector L1.  Tried for the
@@ -1186,7 +1271,8 @@ static int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int blo
     static const int big_top_env = (int)r1_knob("R1_BIG_TOP", R1_BVH_TOP_NODES); // tuning experiments
     // (big scenes: at least node 0 — the walk's root step reads it from the LDS copy, whatever the tuning knob says)
     a.bvh_lds_f4 = !(variant == 4 || variant == 5) ? 0u : (!big ? 4u * c->n_bvh_nodes : 4u * std::min<uint32_t>(c->n_bvh_nodes, (uint32_t)std::max(1, big_top_env)));
-    a.bvh_wide = nullptr;
+    if (!grid)
+        a.bvh_wide = nullptr; // (shares its word with a.grid)
     if (R1_BVH4 && (variant == 4 || variant == 5) && !big)
     {
         if (!c->bvh_wide_f4)
@@ -1196,10 +1282,11 @@ static int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int blo
         }
         a.bvh_wide = (const float4 *)c->bvh_wide.p, a.bvh_lds_f4 = c->bvh_wide_f4, a.bvh_depth = c->bvh_wide_stack;
     }
-    const int occ_slot = variant + 8 * big + 16 * mode;
+    const int occ_slot = variant + 16 * big + 32 * mode;
     if (c->occupancy[occ_slot] == 0)
         R1_HIP(r1_trace_occupancy(variant, big, mode,
-                                  (variant == 4 || variant == 5) ? (size_t)a.bvh_depth * R1_BLOCK * (big ? 4 : 2) + (size_t)a.bvh_lds_f4 * 16 + R1_ENTRY_LDS_BYTES(a.entry_lds) : 0,
+                                  (variant == 4 || variant == 5) ? (size_t)a.bvh_depth * R1_BLOCK * (big ? 4 : 2) + (size_t)a.bvh_lds_f4 * 16 + R1_ENTRY_LDS_BYTES(a.entry_lds)
+                                  : grid ? (size_t)a.bvh_depth * R1_BLOCK * 4 + (big ? 0 : (size_t)c->grid_args.lds_bytes) : 0,
                                   &c->occupancy[occ_slot]));
     int per_cu = c->occupancy[occ_slot];
     if (per_cu < 1)
@@ -1362,7 +1449,7 @@ static int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int blo
         if (c->ring_used < c->ring_frames)
             ++c->ring_used;
     }
-    if (big || (R1_STACK_LDS_WORDS < R1_STACK_WORDS && (variant == 4 || variant == 5)))
+    if (big || (R1_STACK_LDS_WORDS < R1_STACK_WORDS && (variant == 4 || variant == 5 || grid)))
     {
         // sized for the largest grid of this kernel (not this frame's): a frame with a bigger grid must not reallocate
         // (sized for the build that keeps the fewest words in LDS: the latency / diagnostic builds keep R1_STACK_LDS_WORDS, the throughput builds R1_STACK_LDS_WORDS_TP)
@@ -1375,7 +1462,7 @@ static int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int blo
     if (!land && !c->counters_clean)
         R1_HIP(hipMemsetAsync(c->counters.p, 0, R1_COUNTER_BYTES, st));
     c->counters_clean = false;
-    if (variant == 3 || variant == 5)
+    if (variant == 3 || variant == 5 || variant == 8)
     {
         c->wave_log_waves = (uint32_t)blocks * (R1_BLOCK / 64);
         if ((rc = ensure(c->wave_log, (size_t)c->wave_log_waves * 32)))
@@ -1388,7 +1475,7 @@ static int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int blo
         R1_HIP(hipMemsetAsync(d_rays, 0, 8, st));
     R1_HIP(hipEventRecord(e0, st));
     if (c->total_samples && variant != 6)
-        R1_HIP(r1_launch_trace(&a, variant, big, mode, (int)blocks, st));
+        R1_HIP(r1_launch_trace(&a, variant, big, mode, (int)blocks, grid && !big ? c->grid_args.lds_bytes : 0u, st));
     if (c->total_samples && variant == 6)
     {
         // wavefront variant: path state, per-level queues and the attenuation stack live in HBM
@@ -1509,7 +1596,7 @@ static int render_host(r1_context *c, const r1_params *p, uint8_t *rgb_out, uint
         return rc;
     // the ray count: stored by the frame's last launch straight into the context's page-locked word (no second copy to
     // enqueue and wait for); the diagnostic builds count with atomics and keep a device word + copy
-    const bool stats = p->variant == R1_VARIANT_STATS || p->variant == R1_VARIANT_BVH_STATS;
+    const bool stats = p->variant == R1_VARIANT_STATS || p->variant == R1_VARIANT_BVH_STATS || p->variant == R1_VARIANT_GRID_STATS;
     const bool direct = !stats && c->host_word_dev;
     // a page-locked pixel buffer (r1_host_alloc) receives the tiles straight from the trace kernel's resolvers: no copy either
     Landing land_to;

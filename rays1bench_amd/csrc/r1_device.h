@@ -4,6 +4,8 @@
 
 #include <stdint.h>
 
+#include "r1_grid_dda.h"
+
 // Launch geometry of the trace kernel.
 #define R1_BLOCK 256        // threads per workgroup = 4 wave64
 #define R1_BIT_WORDS 8      // small scenes: per-lane flag words in LDS, 32 groups each, worked off 256 groups at a time
@@ -190,6 +192,18 @@ struct R1DeviceScene
     uint32_t bvh_root_leaf; // 1 / 2: child 0 / 1 of the root is a leaf of <= 2 pairs that every ray tests: the root step of bvh_advance; 0: none
 };
 
+// R1_VARIANT_GRID (r1_grid.cpp): the uniform grid's walk geometry and tables (device memory, R1TraceArgs::grid).  `tab` = [cells + 1] CSR offsets, then the registered
+// active sphere indices; 16-bit entries for the small-scene kernel (which copies all of it into LDS), 32-bit for the big one.
+struct R1GridArgs
+{
+    R1GridGeom geom;
+    const uint32_t *outliers; // active indices every ray tests before the walk
+    uint32_t n_out;
+    uint32_t n_start;         // cells + 1: where the sphere ids begin in tab
+    const uint32_t *tab;
+    uint32_t lds_bytes;       // small-scene kernel: bytes of tab in LDS behind the fallback's traversal stack (multiple of 16)
+};
+
 struct R1DeviceCamera
 {
     float origin[3], lower_left[3], horizontal[3], vertical[3], u[3], v[3];
@@ -242,7 +256,11 @@ struct R1TraceArgs
     uint32_t *land_cnt;           // [n_frames * n_local_tiles] x R1_LAND_CNT_STRIDE words: samples each tile still lacks; the tracing waves subtract, the wave that
                                   // owes the tile re-arms
     R1LandArgs land;
-    const float4 *bvh_wide;       // R1_BVH4: the 4-wide table the small-scene kernels copy into LDS instead of scene.bvh_nodes (bvh_lds_f4 float4)
+    union
+    {
+        const float4 *bvh_wide;   // R1_BVH4: the 4-wide table the small-scene kernels copy into LDS instead of scene.bvh_nodes (bvh_lds_f4 float4)
+        const R1GridArgs *grid;   // R1_VARIANT_GRID: the grid's arguments, in device memory (one word here: the other kernels' argument block
+    };                            // keeps its size and layout, and so their code)
     uint32_t entry_lds;           // R1_ENTRY, small-scene kernels, single frames: the workgroups keep the table as 16-bit words in LDS behind their node table (0: read from bvh_entry)
     const uint32_t *bvh_entry;    // R1_ENTRY: [n_frames * n_local_tiles] child reference (the kernel's form) a primary ray of that tile starts at after the root step
     uint32_t coop_lanes;          // small scenes: once the queue is empty, a wave with <= coop_lanes live paths tests each of them

@@ -1,0 +1,31 @@
+// r1_grid.h — the uniform grid of R1_VARIANT_GRID on the host (built by r1_grid.cpp, uploaded by r1_capi.cpp).
+#ifndef R1_GRID_H
+#define R1_GRID_H
+
+#include <stdint.h>
+#include <vector>
+
+#include "r1_grid_dda.h"
+
+#define R1_GRID_SPAN_MAX 64    // a sphere whose padded ball overlaps more cells is an outlier (tested by every ray before the walk)
+#define R1_GRID_AXIS_MAX 4096  // cells per axis at most
+#define R1_GRID_LDS_HALVES 8192 // small-scene kernel: cell starts + sphere ids (16 bits each) it keeps in LDS (16 KB); larger grids run the big kernel
+
+struct r1_scene;
+
+struct R1Grid
+{
+    R1GridGeom geom;
+    std::vector<uint32_t> start;    // [cells + 1] CSR offsets into ids; cell (jx, jy, jz) = (jz ny + jy) nx + jx
+    std::vector<uint32_t> ids;      // active sphere indices, ascending within a cell
+    std::vector<uint32_t> outliers; // active indices every ray tests before the walk (ascending)
+    uint32_t max_occupancy = 0;
+    double pad = 0;    // largest registration pad: rho_i - r_i over the registered spheres
+    double v_safe = 0; // V: origins within V of every registered centre walk the grid, the others take the tree
+    double build_ms = 0;
+};
+
+void r1_build_grid(uint32_t na, const float *cx, const float *cy, const float *cz, const float *rsq, const double *rbound, R1Grid &g);
+int r1_grid_from_scene(const r1_scene *s, R1Grid &g); // the active spheres of s, filtered as r1_set_scene does
+
+#endif

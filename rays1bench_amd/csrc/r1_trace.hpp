@@ -48,6 +48,7 @@
 #include <stdint.h>
 
 #include "r1_device.h"
+#include "r1_grid_dda.h"
 #include "../../include/rays1_seed.h"
 
 #pragma clang fp contract(off)
@@ -67,7 +68,9 @@ typedef const f4 __attribute__((address_space(4))) *cf4_ptr;
 typedef float v2f __attribute__((ext_vector_type(2)));
 typedef float f16 __attribute__((ext_vector_type(16)));
 typedef const f16 __attribute__((address_space(4))) *cf16_ptr;
-typedef uint32_t __attribute__((address_space(1))) r1_gu32; // a word of global memory (explicit: keeps rarely used stores / loads from becoming generic ones)
+typedef uint32_t __attribute__((address_space(1))) r1_gu32;
+typedef const R1GridArgs __attribute__((address_space(4))) R1GridCArgs; // the grid's arguments (device memory, read with scalar loads)
+// a word of global memory (explicit: keeps rarely used stores / loads from becoming generic ones)
 
 // The kernel's arguments read again from the kernarg segment (scalar loads, constant cache) at the place of use, through a pointer the
 // optimiser cannot trace back to the prologue's loads.  hipcc keeps every argument field the loop uses in an SGPR from the prologue on;
@@ -1045,6 +1048,66 @@ __device__ __forceinline__ void sweep_bvh(const R1DeviceScene &S, const bool ali
     }
 }
 
+// ---- walk of the optional uniform grid (R1_VARIANT_GRID) ---------------------------------
+// Per lane: the outliers (every ray, wave-uniform loop: scalar loads), then — unless the origin is too far for the grid's pad
+// (r1g_far: the lane takes the fallback, the tree walk the caller runs) — the cells along the ray in order of entry t, every
+// registered sphere of a cell through exact_offer, until the next cell is entered beyond the closest offer or the ray leaves the box
+// (r1_grid_dda.h; why that presents every sphere that matters: r1_grid.cpp).  Result = minimum offer, ties to the lowest index.
+// SMALL: the cell table and the ids are the workgroup's 16-bit copy in LDS (`ltab`); else 32-bit, through the vector L1.
+// STATS: wstat[2] wave trips of the walk loop, [5] sphere tests summed over lanes, [9] cell steps summed over lanes, [17] outlier
+// tests summed over lanes (published in stats slot 15); the caller counts the fallback lanes.
+// Returns true if this lane takes the fallback.
+template <bool STATS, bool SMALL>
+__device__ __forceinline__ bool grid_trace(const R1TraceArgs &GA, R1GridCArgs *G, const bool alive, const V3 o, const V3 d,
+                                           float &best, uint32_t &best_id, const uint16_t *ltab, const int tid, unsigned long long *wstat)
+{
+    R1GridCArgs &geom_args = *G;
+    auto &geom = geom_args.geom; // (read in place: scalar loads where the walk uses a field)
+    best = FLT_MAX, best_id = 0xFFFFFFFFu;
+    if (!alive)
+        return false;
+    for (uint32_t k = 0; k < G->n_out; ++k) // (uniform index: scalar loads)
+    {
+        const uint32_t id = ((const __attribute__((address_space(4))) uint32_t *)G->outliers)[k];
+        const float t = exact_offer(((cf4_ptr)GA.scene.exact)[id], o, d);
+        const bool upd = (t < FLT_MAX) & ((t < best) | ((t == best) & (id < best_id)));
+        best = upd ? t : best;
+        best_id = upd ? id : best_id;
+    }
+    if (STATS)
+        wstat[17] += G->n_out, wstat[5] += G->n_out;
+    if (r1g_far(geom, o.x, o.y, o.z))
+        return true;
+    R1GridRay r;
+    bool walking = r1g_setup(geom, o.x, o.y, o.z, d.x, d.y, d.z, best, r);
+    const f4 *__restrict__ tab = (const f4 *)GA.scene.exact;
+    while (walking)
+    {
+        if (STATS)
+        {
+            wstat[9] += 1;
+            if ((tid & 63) == __ffsll((long long)__ballot(1)) - 1)
+                wstat[2] += 1;
+        }
+        const uint32_t c = r1g_cell(geom, r);
+        const r1_gu32 *gtab = (const r1_gu32 *)G->tab;
+        uint32_t k = SMALL ? (uint32_t)ltab[c] : gtab[c];
+        const uint32_t e = SMALL ? (uint32_t)ltab[c + 1u] : gtab[c + 1u];
+        if (STATS)
+            wstat[5] += e - k;
+        for (; k < e; ++k)
+        {
+            const uint32_t id = SMALL ? (uint32_t)ltab[G->n_start + k] : gtab[G->n_start + k];
+            const float t = exact_offer(tab[id], o, d);
+            const bool upd = (t < FLT_MAX) & ((t < best) | ((t == best) & (id < best_id)));
+            best = upd ? t : best;
+            best_id = upd ? id : best_id;
+        }
+        walking = r1g_step(geom, r, best);
+    }
+    return false;
+}
+
 // ---- the tail of a frame: a few live paths per wave ------------------------------------------------
 // Every live ray of the wave in turn against ALL active spheres, lane l testing spheres l, l + 64, ...
 // with the reference's per-sphere arithmetic (exact_offer), then the minimum offer, ties to the lowest
@@ -1673,7 +1736,8 @@ struct TraceWaves
 #define R1_TREE_WAVES_LAT 6 // (the synchronous build: 67 VGPRs, seven workgroups per CU at run time; built for eight — 64 VGPRs, two words of the
                             //  LDS stack less — it spills and is no faster: profiles/r04/retune_after_fresh_args.txt)
 #endif
-    static constexpr int value = STATS ? 1 : (VARIANT == 4 ? (BIG ? 8 : ((MODE == 0 || MODE == 3) ? R1_TREE_WAVES_TP : R1_TREE_WAVES_LAT)) : (VARIANT == 2 && !BIG ? 5 : 1));
+    // (the grid's PIXEL-mode build — big-scene kernel only — is built for four waves: at eight it keeps a scratch slot for its SGPR spills)
+    static constexpr int value = STATS ? 1 : (VARIANT == 7 && MODE == 2) ? 4 : ((VARIANT == 4 || VARIANT == 7) ? (BIG ? 8 : ((MODE == 0 || MODE == 3) ? R1_TREE_WAVES_TP : R1_TREE_WAVES_LAT)) : (VARIANT == 2 && !BIG ? 5 : 1));
 };
 
 // MODE 1 = LAT = latency-mode build (the synchronous entry points: one frame, full grid): sub-queues and
@@ -1681,8 +1745,9 @@ struct TraceWaves
 // long-lived waves per frame) leaves them out: they cost it registers and bring it nothing.
 // MODE 0 = frames in flight (the throughput entry point): samples in one guided queue, few long-lived waves per frame.
 // MODE 2 = PIXEL mode (the throughput entry point after r1_set_pixel_mode; see struct Pixel): the queue holds pixels.
+// (the body of the kernel; r1_trace_kernel and, for the uniform grid, r1_grid_kernel below are its __global__ instances)
 template <int VARIANT, bool STATS, bool BIG, int MODE>
-__global__ void __launch_bounds__(R1_BLOCK, (TraceWaves<VARIANT, STATS, BIG, MODE>::value)) r1_trace_kernel(const R1TraceArgs A)
+__device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
 {
     constexpr bool LAT = MODE == 1, PIX = MODE == 2, BATCH = MODE == 3; // MODE 3 = MODE 0 whose queue spans the frames of a batch
     // tiles resolved inside the kernel: the throughput builds of the tree kernels (frames in flight, MODE 0 / 3); a
@@ -1718,7 +1783,7 @@ __global__ void __launch_bounds__(R1_BLOCK, (TraceWaves<VARIANT, STATS, BIG, MOD
         log_start = __builtin_amdgcn_s_memrealtime();
     }
     // words of the attenuation stack in LDS (the rest of a deep path's entries live in the global workspace)
-    constexpr int LW = VARIANT == 4 ? (((MODE == 0 || MODE == 3) && !STATS) ? R1_STACK_LDS_WORDS_TP : R1_STACK_LDS_WORDS) : R1_STACK_WORDS;
+    constexpr int LW = (VARIANT == 4 || VARIANT == 7) ? (((MODE == 0 || MODE == 3) && !STATS) ? R1_STACK_LDS_WORDS_TP : R1_STACK_LDS_WORDS) : R1_STACK_WORDS;
     __shared__ uint32_t s_stack[BIG ? 1 : LW * R1_BLOCK];
     __shared__ uint32_t s_cand[VARIANT == 2 ? (BIG ? R1_CAND_CAP : R1_BIT_WORDS) * R1_BLOCK : 1];
     __shared__ IDX s_pairs[VARIANT == 2 ? (R1_BLOCK / 64) * PairBits<IDX>::cap : 1];
@@ -1738,6 +1803,20 @@ __global__ void __launch_bounds__(R1_BLOCK, (TraceWaves<VARIANT, STATS, BIG, MOD
     constexpr bool LN = VARIANT == 4 && !BIG;
     typedef typename IdxType<!LN>::type TS; // traversal-stack entry: uint16_t for the small-scene tree kernels, else uint32_t
     const size_t trav_words = VARIANT == 4 ? (size_t)A.bvh_depth * R1_BLOCK * sizeof(TS) / 4 : 0; // (bvh_depth x 256 entries: a multiple of 16 bytes either way)
+    // R1_VARIANT_GRID: the fallback's traversal stack (32-bit entries: the tree walk of bvh_advance from the table in global memory), then
+    // (small scenes) the workgroup's copy of the grid's 16-bit cell table and ids
+    const size_t gtrav_words = VARIANT == 7 ? (size_t)A.bvh_depth * R1_BLOCK : 0;
+    const uint16_t *ltab = (const uint16_t *)(s_trav + gtrav_words);
+    if (VARIANT == 7 && !BIG)
+    {
+        float4 *dst = (float4 *)(s_trav + gtrav_words);
+        const R1GridCArgs *ga = (const R1GridCArgs *)(uintptr_t)A.grid;
+        const float4 *src = (const float4 *)(const r1_gu32 *)ga->tab;
+        const uint32_t n16 = ga->lds_bytes / 16u;
+        for (uint32_t i = (uint32_t)tid; i < n16; i += R1_BLOCK)
+            dst[i] = src[i];
+        __syncthreads();
+    }
     const float4 *lnodes = (const float4 *)(s_trav + trav_words);
     // (big scenes: A.bvh_lds_f4 covers the first nodes of the breadth-first top of the tree only)
     const uint32_t top = LN ? 0u : A.bvh_lds_f4 >> 2;
@@ -1786,7 +1865,7 @@ __global__ void __launch_bounds__(R1_BLOCK, (TraceWaves<VARIANT, STATS, BIG, MOD
 #ifndef R1_SPARE_MIN
 #define R1_SPARE_MIN 40u
 #endif
-    constexpr bool SPARE = R1_SPARE && !BIG && (VARIANT == 4 || VARIANT == 2) && (MODE == 0 || MODE == 3); // (big scenes: the registers buy an eighth wave instead)
+    constexpr bool SPARE = R1_SPARE && !BIG && (VARIANT == 4 || VARIANT == 2 || VARIANT == 7) && (MODE == 0 || MODE == 3); // (big scenes: the registers buy an eighth wave instead)
     Path spare = p;
     bool has_spare = false;
 
@@ -2035,6 +2114,34 @@ __global__ void __launch_bounds__(R1_BLOCK, (TraceWaves<VARIANT, STATS, BIG, MOD
             if (tv.best_id != 0xFFFFFFFFu)
                 t_hit = tv.best, hit = (int)tv.best_id;
         }
+        else if (VARIANT == 7)
+        {
+#if R1_FRESH
+            R1_FRESH_ARGS(HA) // (table pointers and the grid's geometry: fetched for the walk, free again after it)
+#else
+            const R1TraceArgs &HA = A;
+#endif
+            float best;
+            uint32_t best_id;
+            const bool fb = grid_trace<STATS, !BIG>(HA, (R1GridCArgs *)(uintptr_t)HA.grid, alive, p.o, p.d, best, best_id, ltab, tid, wstat);
+            if (STATS)
+                wstat[16] += fb ? 1ull : 0ull;
+            if (__ballot(fb) != 0ull)
+            {
+                // fallback: the tree walk from scratch (from the root, table in global memory), exact for any origin; the
+                // outliers' offer is kept (the tree presents them again: same offers, the index tie goes to the same sphere)
+                Trav fv;
+                trav_start(fv);
+                fv.best = best, fv.best_id = best_id;
+                if (!fb)
+                    fv.cur = R1_BVH_DONE;
+                // (grid launches carry scene.bvh_root_leaf = 0: the walk starts at the root, which it reads from global memory)
+                bvh_advance<false, false, false, uint32_t>(HA.scene, p.o, p.d, fv, s_trav, tid, 64u, wstat, nullptr);
+                best = fv.best, best_id = fv.best_id;
+            }
+            if (best_id != 0xFFFFFFFFu)
+                t_hit = best, hit = (int)best_id;
+        }
         else
         {
 #if R1_FRESH
@@ -2101,9 +2208,9 @@ __global__ void __launch_bounds__(R1_BLOCK, (TraceWaves<VARIANT, STATS, BIG, MOD
         for (int off = 32; off > 0; off >>= 1)
             c9 += __shfl_down(c9, off, 64);
         wstat[9] = c9;
-        if (VARIANT == 4)
+        if (VARIANT == 4 || VARIANT == 7)
         {
-            // per-lane counters of sweep_bvh
+            // per-lane counters of sweep_bvh / grid_trace
             const int slots[5] = {2, 3, 5, 16, 17};
             for (int q = 0; q < 5; ++q)
             {
@@ -2116,7 +2223,14 @@ __global__ void __launch_bounds__(R1_BLOCK, (TraceWaves<VARIANT, STATS, BIG, MOD
         if (lane == 0 && wave_log)
         {
             unsigned long long *rec = wave_log + 4 * (size_t)(blockIdx.x * (R1_BLOCK / 64) + (threadIdx.x >> 6));
-            rec[0] = log_start, rec[1] = log_exhausted, rec[2] = __builtin_amdgcn_s_memrealtime(), rec[3] = wstat[0];
+            if (VARIANT == 7) // (the log lives in global memory: say so, no generic stores)
+            {
+                typedef unsigned long long __attribute__((address_space(1))) gu64;
+                gu64 *grec = (gu64 *)(uintptr_t)rec;
+                grec[0] = log_start, grec[1] = log_exhausted, grec[2] = __builtin_amdgcn_s_memrealtime(), grec[3] = wstat[0];
+            }
+            else
+                rec[0] = log_start, rec[1] = log_exhausted, rec[2] = __builtin_amdgcn_s_memrealtime(), rec[3] = wstat[0];
         }
         if (lane == 0 && A.stats)
         {
@@ -2126,9 +2240,9 @@ __global__ void __launch_bounds__(R1_BLOCK, (TraceWaves<VARIANT, STATS, BIG, MOD
             atomicMax(&A.stats[11], ~wstat[8]);                     // ~shortest wave
             atomicMax(&A.stats[12], (unsigned long long)__builtin_readcyclecounter());  // last wave end (this XCD's counter)
             atomicMax(&A.stats[13], ~wstat[14]);                    // ~first wave start
-            if (VARIANT == 4)
+            if (VARIANT == 4 || VARIANT == 7)
             {
-                atomicAdd(&A.stats[14], wstat[16]);                 // tree: leaf trips summed over lanes
+                atomicAdd(&A.stats[14], wstat[16]);                 // tree: leaf trips summed over lanes (grid: fallback lanes)
                 atomicAdd(&A.stats[15], wstat[17]);                 // tree: root steps (bvh_advance) summed over lanes
             }
         }
@@ -2145,6 +2259,19 @@ __global__ void __launch_bounds__(R1_BLOCK, (TraceWaves<VARIANT, STATS, BIG, MOD
         if (lane == 0 && lane_rays)
             atomicAdd(A.num_rays, lane_rays);
     }
+}
+
+template <int VARIANT, bool STATS, bool BIG, int MODE>
+__global__ void __launch_bounds__(R1_BLOCK, (TraceWaves<VARIANT, STATS, BIG, MODE>::value)) r1_trace_kernel(const R1TraceArgs A)
+{
+    r1_trace_body<VARIANT, STATS, BIG, MODE>(A);
+}
+
+// R1_VARIANT_GRID: the same body under a name of its own (VARIANT 7)
+template <bool STATS, bool BIG, int MODE>
+__global__ void __launch_bounds__(R1_BLOCK, (TraceWaves<7, STATS, BIG, MODE>::value)) r1_grid_kernel(const R1TraceArgs A)
+{
+    r1_trace_body<7, STATS, BIG, MODE>(A);
 }
 
 #endif // R1_TRACE_HPP

@@ -2,13 +2,30 @@
 //   R1_TU_NAME   tree_small | tree_big | sweep_small | sweep_big
 //   R1_TU_BIG    true / false
 //   R1_TU_TREE   1: variants 4 (product) and 5 (diagnostic build); 0: variants 2 (grouped sweep), 3 (its diagnostic build, small scenes), 1 (reference form)
+//   R1_TU_GRID   1: variants 7 (uniform grid) and 8 (its diagnostic build); R1_TU_TREE is 0 then
+#ifndef R1_TU_GRID
+#define R1_TU_GRID 0
+#endif
 #include "r1_trace.hpp"
 
 #define R1_CAT2(a, b, c) a##b##c
 #define R1_CAT(a, b, c) R1_CAT2(a, b, c)
 
 // S = diagnostic build, M = mode (0 frames in flight, 1 latency, 2 pixel, 3 frame batches); calls X(V, S, M) for the instance that is built
-#if R1_TU_TREE
+#if R1_TU_GRID
+// (PIXEL mode: the big-scene build only, r1_capi.cpp; r1_launch_trace refuses the small one)
+#define R1_TU_DISPATCH(X)                                                                                              \
+    if (variant == 8)                                                                                                  \
+        X(7, true, (R1_TU_BIG ? 0 : 1));                                                                               \
+    else if (mode == 2 && R1_TU_BIG)                                                                                   \
+        X(7, false, (R1_TU_BIG ? 2 : 0));                                                                              \
+    else if (mode == 1 && !R1_TU_BIG)                                                                                  \
+        X(7, false, 1);                                                                                                \
+    else if (batch)                                                                                                    \
+        X(7, false, 3);                                                                                                \
+    else                                                                                                               \
+        X(7, false, 0);
+#elif R1_TU_TREE
 #define R1_TU_DISPATCH(X)                                                                                              \
     if (variant == 5)                                                                                                  \
         X(4, true, (R1_TU_BIG ? 0 : 1));                                                                               \
@@ -46,9 +63,15 @@
         X(2, false, 0);
 #endif
 
+#if R1_TU_GRID
+#define R1_TU_KERNEL(V, S, M) r1_grid_kernel<S, R1_TU_BIG, M>
+#else
+#define R1_TU_KERNEL(V, S, M) r1_trace_kernel<V, S, R1_TU_BIG, M>
+#endif
+
 extern "C" hipError_t R1_CAT(r1_tu_, R1_TU_NAME, _launch)(const R1TraceArgs *args, int variant, int mode, int batch, int blocks, size_t dyn_lds, hipStream_t stream)
 {
-#define R1_GO(V, S, M) hipLaunchKernelGGL((r1_trace_kernel<V, S, R1_TU_BIG, M>), dim3(blocks), dim3(R1_BLOCK), dyn_lds, stream, *args)
+#define R1_GO(V, S, M) hipLaunchKernelGGL((R1_TU_KERNEL(V, S, M)), dim3(blocks), dim3(R1_BLOCK), dyn_lds, stream, *args)
     R1_TU_DISPATCH(R1_GO)
 #undef R1_GO
     return hipGetLastError();
@@ -57,7 +80,7 @@ extern "C" hipError_t R1_CAT(r1_tu_, R1_TU_NAME, _launch)(const R1TraceArgs *arg
 extern "C" hipError_t R1_CAT(r1_tu_, R1_TU_NAME, _occupancy)(int variant, int mode, size_t dyn_lds, int *blocks_per_cu)
 {
     const int batch = 0; // (the batch build of a kernel has the occupancy of its single-frame build)
-#define R1_OCC(V, S, M) return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, r1_trace_kernel<V, S, R1_TU_BIG, M>, R1_BLOCK, dyn_lds)
+#define R1_OCC(V, S, M) return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, R1_TU_KERNEL(V, S, M), R1_BLOCK, dyn_lds)
     R1_TU_DISPATCH(R1_OCC)
 #undef R1_OCC
 }

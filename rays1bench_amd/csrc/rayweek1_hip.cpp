@@ -10,7 +10,7 @@
 //
 // What the reference fixes at compile time (common.h:19-28) is a run-time option here:
 //     --width W --height H --spp S --seed N --device D --devices N --variant V
-//       (V = R1_VARIANT_*: 0 default, 1 reference-form sweep, 2 exhaustive sweep, 4 box tree, 6 wavefront)
+//       (V = R1_VARIANT_*: 0 default, 1 reference-form sweep, 2 exhaustive sweep, 4 box tree, 6 wavefront, 7 uniform grid)
 // Defaults are the reference's multi-threaded defaults: 1280x720, 250 spp.
 // --devices N splits the frame over N HIP devices inside this one process, tile t -> device
 // t % N (the in-process twin of the reference's thread pool, rayweek1.cpp:785-842):
@@ -247,8 +247,8 @@ RESULT benchmark(Scene *scene, Pix *pixels, bool write_tga, const char *scene_na
     printf("devices:        %d (first hip:%d, %d CUs, %d workgroups x %d threads)\n", nd, g_device, li.compute_units, li.blocks,
            li.threads_per_block);
     static const char *const kernel_names[] = {"default", "reference-form sweep", "grouped exhaustive sweep", "grouped exhaustive sweep + counters",
-                                               "box tree", "box tree + counters", "wavefront"};
-    printf("kernel:         %s (%d hittable spheres, %d inner nodes)\n", li.kernel >= 0 && li.kernel <= 6 ? kernel_names[li.kernel] : "?",
+                                               "box tree", "box tree + counters", "wavefront", "uniform grid", "uniform grid + counters"};
+    printf("kernel:         %s (%d hittable spheres, %d inner nodes)\n", li.kernel >= 0 && li.kernel <= 8 ? kernel_names[li.kernel] : "?",
            li.spheres_active, li.bvh_nodes);
     printf("device time:    %.3fms (%0.2f mrays/s)\n", device_seconds * 1e3, device_seconds ? result.num_rays / device_seconds / 1e6 : 0.0);
     printf("\n");
