@@ -252,7 +252,7 @@ def _same_bits_or_both_nan(a, b):
 def _check_all_kernels(renderer, sa, w, h, spp, seed):
     renderer.set_scene_raw(_cscene(sa), _ccamera(sa))
     ref = renderer.render_samples(r1.make_params(w, h, spp, seed, variant=binding.VARIANT_REFERENCE))
-    for variant in (binding.VARIANT_BVH, binding.VARIANT_PREFILTER, binding.VARIANT_WAVEFRONT):
+    for variant in (binding.VARIANT_BVH, binding.VARIANT_PREFILTER, binding.VARIANT_WAVEFRONT, binding.VARIANT_GRID):
         got = renderer.render_samples(r1.make_params(w, h, spp, seed, variant=variant))
         assert got[1] == ref[1], variant
         assert got[2].tobytes() == ref[2].tobytes(), variant     # same device arithmetic: bits, NaN payloads included
@@ -422,7 +422,7 @@ def test_rayweek1_hip_gather_rccl_one_device(tmp_path):
         assert re.fullmatch(r"hip\|\d+\.\d{3}s\|\d+\|\d+\.\d{3} mrays/s\|", open(tmp_path / "b" / f"out_{n}.txt").read())
 
 
-@pytest.mark.parametrize("case", ["sweep_small", "tree_big", "sweep_big", "medium_default", "empty_shards"])
+@pytest.mark.parametrize("case", ["sweep_small", "tree_big", "sweep_big", "medium_default", "empty_shards", "grid_small", "grid_big"])
 def test_frame_batches_through_every_throughput_kernel(case):
     """Frame batches (MODE 3 builds of the throughput kernels) for the kernels tests/test_gpu_parity.py does not reach: the
     exhaustive sweep, the big-scene tree and sweep kernels (> 1023 spheres), a scene in DEFAULT's measured band, and shards
@@ -437,6 +437,10 @@ def test_frame_batches_through_every_throughput_kernel(case):
         sc, w, h, spp, variant = r1.create_grid_scene(96, 64, 40, 30), 96, 64, 2, binding.VARIANT_PREFILTER
     elif case == "medium_default":
         sc, w, h, spp = r1.create_medium_scene(150, 90), 150, 90, 3
+    elif case == "grid_small":  # the uniform grid's small-scene kernel (table in LDS)
+        sc, w, h, spp, variant = r1.create_large_scene(150, 90), 150, 90, 3, binding.VARIANT_GRID
+    elif case == "grid_big":
+        sc, w, h, spp, variant = r1.create_grid_scene(96, 64, 40, 30), 96, 64, 2, binding.VARIANT_GRID
     else:  # one 32x32 tile, three shards: shards 1 and 2 own nothing
         sc, w, h, spp, shards = r1.create_small_scene(30, 20), 30, 20, 4, 3
     rend = r1.Renderer(0)
@@ -501,7 +505,8 @@ def test_rayweek1_hip_pipeline_mode_counts_the_same_rays(tmp_path):
 # ---- PIXEL mode of the throughput entry point (r1_set_pixel_mode) --------------------------------------
 
 
-@pytest.mark.parametrize("case", ["large_1200x800x10_8shards", "medium_ragged_tiles", "large_96x64x250", "grid_1600_spheres", "sweep_kernel"])
+@pytest.mark.parametrize("case", ["large_1200x800x10_8shards", "medium_ragged_tiles", "large_96x64x250", "grid_1600_spheres", "sweep_kernel",
+                                  "uniform_grid_small_scene"])
 def test_pixel_mode_writes_the_same_pixels_and_counts(case):
     """r1_set_pixel_mode: lanes own pixels and resolve in-kernel (3 B/pixel, no per-sample records, no resolve
     launch).  The device-resident shard blocks must equal, byte for byte, what the per-sample path renders."""
@@ -516,8 +521,10 @@ def test_pixel_mode_writes_the_same_pixels_and_counts(case):
         sc, w, h, spp, shards, tw, th = r1.create_large_scene(96, 64), 96, 64, 250, 2, 32, 32
     elif case == "grid_1600_spheres":
         sc, w, h, spp, shards, tw, th = r1.create_grid_scene(160, 120, 50, 32), 160, 120, 4, 2, 32, 32
-    else:
+    elif case == "sweep_kernel":
         sc, w, h, spp, shards, tw, th, variant = r1.create_large_scene(320, 200), 320, 200, 6, 1, 32, 32, binding.VARIANT_PREFILTER
+    else:  # R1_VARIANT_GRID on a small scene: PIXEL mode runs the grid's big-scene kernel (r1_capi.cpp)
+        sc, w, h, spp, shards, tw, th, variant = r1.create_large_scene(150, 90), 150, 90, 3, 2, 24, 40, binding.VARIANT_GRID
     rend = r1.Renderer(0)
     try:
         rend.set_scene(sc)

@@ -101,7 +101,7 @@ def test_grid_sphere_count_edges(renderer, n_active):
     assert same(got, ref)
 
 
-CASES = ["mixed_radii", "far_camera", "tiny_spheres", "coincident", "noise_dominated", "collinear"]
+CASES = ["mixed_radii", "far_camera", "tiny_spheres", "coincident", "noise_dominated", "collinear", "dense_cluster", "nested"]
 
 
 @pytest.mark.parametrize("case", CASES)
@@ -121,6 +121,11 @@ def test_grid_is_exact_on_adversarial_scenes(renderer, case):
         c, rad = rng.uniform(-3, 3, (n, 3)), np.exp(rng.uniform(np.log(1e-3), np.log(0.05), n))
     elif case == "coincident":
         c, rad = np.repeat(rng.uniform(-3, 3, (n // 6, 3)), 6, axis=0), np.repeat(rng.uniform(0.1, 0.6, n // 6), 6)
+    elif case == "dense_cluster":
+        c, rad = rng.normal(0, 1.2, (n, 3)), rng.uniform(0.05, 0.35, n)
+    elif case == "nested":
+        centres = rng.uniform(-4, 4, (12, 3))
+        c, rad = centres[rng.integers(0, 12, n)], rng.uniform(0.05, 2.5, n)
     elif case == "noise_dominated":
         shift = np.array([-420.0, 380.0, 210.0], np.float32)
         c, rad = rng.uniform(-1.5, 1.5, (n, 3)) + shift, np.full(n, 2e-3)
@@ -137,6 +142,8 @@ def test_grid_is_exact_on_adversarial_scenes(renderer, case):
     got = renderer.render_samples(r1.make_params(w, h, spp, 1234, variant=GRID))
     ref = renderer.render_samples(r1.make_params(w, h, spp, 1234, variant=binding.VARIANT_REFERENCE))
     assert same(got, ref)
+    oimg, orays, osamples = r1o.render_frame(sa, oparams(r1.make_params(w, h, spp, 1234)), want_samples=True)
+    assert got[1] == orays and got[2].tobytes() == osamples.tobytes()
 
 
 @pytest.mark.parametrize("bounces", [1, 3, 50, 51])

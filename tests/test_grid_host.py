@@ -304,3 +304,114 @@ def test_pad_constants_against_a_monte_carlo_worst_case():
         bound = r_t + (23 * U * v * v + 2 * U * r_t * r_t) / (2 * r_t) + 5 * U * v
         worst = max(worst, (dist - r_t) / (bound - r_t))
     assert 0 < worst < 1.0, worst
+
+
+# ---- preconditions of tests/test_gpu_grid_edges.py: each fixture still reaches the path its GPU test is about --------------------------
+
+
+def _edges():
+    import test_gpu_grid_edges as e  # (its GPU tests are marked gpu; the scene builders run anywhere)
+    return e
+
+
+def _cs(sa):
+    from test_gpu_bvh import _as_cscene
+    return _as_cscene(sa)
+
+
+@pytest.mark.parametrize("kind", ["large", "lattice"])
+def test_telephoto_rays_take_the_fallback_and_hit(kind):
+    e = _edges()
+    w, h = 96, 64
+    sc = r1.create_large_scene(w, h) if kind == "large" else r1.create_grid_scene(w, h, 48, 36)
+    sa = e.telephoto(r1o_scene(sc), w, h)
+    cs, rng = _cs(sa), np.random.default_rng(21)
+    hits = 0
+    rays = camera_rays(sa.camera_array, 63, rng)
+    for o, d in rays:
+        check_ray(cs, sa.arrays, o.astype(F), d.astype(F), expect_fallback=True)
+        hits += brute(sa.arrays, o.astype(F), d.astype(F))[0] >= 0
+    assert hits > len(rays) // 2, hits
+
+
+def test_straddling_lens_and_tie_scene_preconditions():
+    e = _edges()
+    w, h = 96, 64
+    sa = e.straddling_lens(r1o_scene(r1.create_large_scene(w, h)), w, h)
+    cam, cs = sa.camera_array, _cs(sa)
+    d = unit(cam[3:6] + 0.5 * cam[6:9] + 0.5 * cam[9:12] - cam[0:3])
+    near, far = cam[0:3] - cam[21] * 0.9 * cam[12:15], cam[0:3] + cam[21] * 0.9 * cam[12:15]
+    flags = {check_ray(cs, sa.arrays, o.astype(F), d.astype(F)) for o in (near, far)}
+    assert flags == {True, False}  # the lens crosses V: one rim walks the grid, the other takes the fallback
+    sa, big = e.tie_scene(w, h)
+    cs = _cs(sa)
+    info, start, ids, outl = binding.grid_describe(cs)
+    assert outl.tolist() == [big] and set(ids.tolist()) == set(range(big))
+    hit_groups, hit_outlier = 0, 0
+    for o, d in camera_rays(sa.camera_array, 120, np.random.default_rng(22)):
+        check_ray(cs, sa.arrays, o.astype(F), d.astype(F), expect_fallback=True)
+        hit = brute(sa.arrays, o.astype(F), d.astype(F))[0]
+        hit_groups += 0 <= hit < big
+        hit_outlier += hit == big
+        assert hit < 0 or hit == big or hit % 4 == 0  # of four coincident spheres, the first
+    assert hit_groups >= 10 and hit_outlier >= 5, (hit_groups, hit_outlier)
+
+
+def test_limit_scenes_sit_at_the_lds_limit():
+    e = _edges()
+    for kind in e.LIMIT_SCENES:
+        sa = e.limit_scene(kind, 80, 60)
+        cs = _cs(sa)
+        info = binding.grid_describe(cs)[0]
+        hv = e.halves(cs)
+        assert info["spheres"] <= 1023 and info["registrations"] > 4096, kind
+        assert (8000 <= hv <= binding_lds_halves()) if kind != "over" else (binding_lds_halves() < hv <= 8400), (kind, hv)
+        if kind == "deep":
+            assert binding.bvh_describe(cs)[0]["depth"] >= 15
+        for o_, d in camera_rays(sa.camera_array, 6, np.random.default_rng(23)):
+            check_ray(cs, sa.arrays, o_.astype(F), d.astype(F), expect_fallback=False)
+
+
+def binding_lds_halves():
+    import re
+    src = open(binding.os.path.join(binding.HERE, "csrc", "r1_grid.h")).read()
+    return int(re.search(r"#define R1_GRID_LDS_HALVES (\d+)", src).group(1))
+
+
+def test_outlier_and_cell_shapes():
+    e = _edges()
+    rng = np.random.default_rng(24)
+    for shape in e.SHAPES:
+        sa, want = e.shape_scene(shape, 72, 48)
+        cs = _cs(sa)
+        info = e.check_shape(cs, want)
+        check_structure(cs, sa.arrays)
+        hits = 0
+        for o, d in camera_rays(sa.camera_array, 40, rng):
+            check_ray(cs, sa.arrays, o.astype(F), d.astype(F))
+            hits += brute(sa.arrays, o.astype(F), d.astype(F))[0] >= 0
+        assert hits >= 4, (shape, hits)
+        if shape == "all_outliers":
+            assert float(info["v_safe"]) >= 16 and info["max_occupancy"] == 0
+
+
+def test_boundary_plane_rays_against_brute_force():
+    e = _edges()
+    sa, x = e.boundary_plane_scene(64, 48)
+    cs = _cs(sa)
+    info = binding.grid_describe(cs)[0]
+    k = (np.float64(x) - np.float64(info["lo"][0])) / np.float64(info["cell"][0])
+    assert k == int(k) and 0 < k < info["cells"][0]  # exactly on an inner boundary
+    cam = sa.camera_array
+    hits = 0
+    for o, d in camera_rays(cam, 80, np.random.default_rng(25)):
+        o, d = o.astype(F), d.astype(F)
+        assert o[0] == x and d[0] == 0
+        assert not check_ray(cs, sa.arrays, o, d)
+        hits += brute(sa.arrays, o, d)[0] >= 0
+    assert hits > 20, hits
+
+
+def r1o_scene(sc):
+    import r1o
+    return r1o.SceneArrays.from_c(sc.spheres, sc.camera)
