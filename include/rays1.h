@@ -183,6 +183,30 @@ int r1_render(r1_context *ctx, const r1_params *params, uint8_t *rgb_out, uint64
 int r1_render_samples(r1_context *ctx, const r1_params *params, uint8_t *rgb_out, uint64_t *num_rays_out,
                       float *samples_out);
 
+/* Progressive rendering: traces samples [first_sample, first_sample + params->spp) of every pixel and adds them,
+ * in sample order, to the context's per-pixel fp32 accumulator.  A sample's streams depend on (seed, pixel, sample
+ * index) only (rays1_seed.h), and the resolve sums a pixel's samples in sample order with plain fp32 adds, so the
+ * accumulator then holds exactly what r1_render sums for spp = first_sample + params->spp.
+ *   first_sample == 0  starts a new accumulation (any earlier one is discarded).
+ *   first_sample > 0   continues the context's accumulation: first_sample must equal the samples accumulated so far,
+ *                      every field of *params but spp must equal the call that started it (size, seed, max_bounces,
+ *                      tile size, shard fields, variant), and no r1_set_scene may have happened since.  Otherwise
+ *                      the call returns R1_EINVAL and leaves the accumulation untouched.  A call that fails after it
+ *                      has enqueued work invalidates it: only first_sample == 0 is accepted next.
+ *   params->spp        this pass's samples, bounded per pass by the limits of r1_render (2^31 samples and 2^31
+ *                      padded sample slots); first_sample + spp <= INT32_MAX; nothing else bounds the total.
+ *   rgb_out            (may be NULL: accumulate only) the row-major image of samples [0, first_sample + spp),
+ *                      byte-identical to r1_render with that spp and the same other fields wherever that call is
+ *                      within its limits.
+ *   num_rays_out       (may be NULL) the cumulative color() count, equal to that r1_render's.
+ * Whole frames only (num_shards == 1).  Variants DEFAULT, REFERENCE, PREFILTER, BVH and GRID, small and big scenes;
+ * the diagnostic variants and WAVEFRONT return R1_EINVAL.  PIXEL mode (r1_set_pixel_mode) does not apply.
+ * Synchronous, like r1_render; r1_last_launch_info and r1_last_timing describe the last pass.  r1_render,
+ * r1_render_async and r1_render_batch_async may be called on the context between passes without disturbing the
+ * accumulation.  Each pass keeps 16 bytes per sample of that pass on the device (as r1_render does per frame) and
+ * the accumulator 16 bytes per pixel. */
+int r1_render_pass(r1_context *ctx, const r1_params *params, int32_t first_sample, uint8_t *rgb_out, uint64_t *num_rays_out);
+
 /* Pipelined form of r1_render — frames in flight whose results land on the HOST.  The reference times
  * dispatch -> pixels + ray count on the host (rayweek1.cpp:848 -> :891) for ONE frame and waits; a caller that
  * renders frame after frame (main's `-n` runs, rayweek1.cpp:969-984) can keep several in flight instead: the call
@@ -198,7 +222,8 @@ int r1_render_samples(r1_context *ctx, const r1_params *params, uint8_t *rgb_out
 int r1_render_async(r1_context *ctx, const r1_params *params, uint8_t *rgb_out, uint64_t *num_rays_out, void *hip_stream);
 
 /* Frame BATCHES: n_frames frames of the same scene, camera and size in ONE launch; frame f is seeded
- * params->seed + f * seed_stride (0: identical frames; 1: the passes of a progressive render).  The trace kernel is
+ * params->seed + f * seed_stride (0: identical frames; 1: independent frames of consecutive seeds — the passes of a
+ * progressive render that ADD UP are r1_render_pass's).  The trace kernel is
  * persistent — a wave keeps refilling its lanes from a queue of samples — and what a launch costs beyond its samples is
  * its ramp and, above all, its drain: the last ~40 iterations of every wave run with few live lanes.  In a batch the
  * queue is frame-major and the waves flow from one frame into the next, so that cost is paid once per batch instead of

@@ -124,6 +124,7 @@ SYMBOLS = [
     ("r1_set_scene", C.c_int, [_ctx, C.POINTER(CScene), C.POINTER(CCamera)]),
     ("r1_render", C.c_int, [_ctx, C.POINTER(Params), _u8p, _u64p, _dblp]),
     ("r1_render_samples", C.c_int, [_ctx, C.POINTER(Params), _u8p, _u64p, _f32p]),
+    ("r1_render_pass", C.c_int, [_ctx, C.POINTER(Params), C.c_int32, _u8p, _u64p]),
     ("r1_tile_count", C.c_int, [C.POINTER(Params), _i32p, _i32p]),
     ("r1_shard_block_bytes", C.c_size_t, [C.POINTER(Params)]),
     ("r1_shard_record_bytes", C.c_size_t, [C.POINTER(Params)]),
@@ -284,6 +285,14 @@ class Renderer:
         rays = C.c_uint64()
         _check(lib().r1_render_samples(self._c, C.byref(params), img.ctypes.data_as(_u8p), C.byref(rays), samples.ctypes.data_as(_f32p)))
         return img, int(rays.value), samples
+
+    def render_pass(self, params, first_sample, image=True):
+        """r1_render_pass: samples [first_sample, first_sample + params.spp) added to the context's accumulator.  Returns
+        (preview of samples [0, first_sample + params.spp) or None, cumulative ray count)."""
+        img = np.zeros((params.height, params.width, 3), np.uint8) if image else None
+        rays = C.c_uint64()
+        _check(lib().r1_render_pass(self._c, C.byref(params), first_sample, img.ctypes.data_as(_u8p) if image else None, C.byref(rays)))
+        return img, int(rays.value)
 
     def render_async(self, params, host_frame, stream_ptr=None):
         """r1_render_async: enqueue one frame (throughput kernels) whose pixels + ray count land in `host_frame`

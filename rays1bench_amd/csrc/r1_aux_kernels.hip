@@ -1,4 +1,4 @@
-// r1_aux_kernels.hip — the kernels around the trace kernel (wavefront variant, resolve, batch counts, assemble) and the launch
+// r1_aux_kernels.hip — the kernels around the trace kernel (wavefront variant, resolve, progressive accumulate, batch counts, assemble) and the launch
 // dispatch called from r1_capi.cpp.  The trace kernel template and its device functions: r1_trace.hpp.
 #include "r1_trace.hpp"
 
@@ -151,11 +151,8 @@ __global__ void __launch_bounds__(256) r1_resolve_kernel(const R1ResolveArgs A)
                 cr += v.x, cg += v.y, cb += v.z; // col += color(...) rayweek1.cpp:762
                 rays += __float_as_uint(v.w);
             }
-            cr *= A.inv_spp, cg *= A.inv_spp, cb *= A.inv_spp;
-            cr = ieee_sqrt(cr), cg = ieee_sqrt(cg), cb = ieee_sqrt(cb);
-            const uint8_t r = (uint8_t)(int)(cr * 255.99f);
-            const uint8_t g = (uint8_t)(int)(cg * 255.99f);
-            const uint8_t b = (uint8_t)(int)(cb * 255.99f);
+            uint8_t r, g, b;
+            quantise_pixel(cr, cg, cb, A.inv_spp, r, g, b);
             size_t o;
             if (A.block_layout)
                 o = ((size_t)lt * A.tile_h * A.tile_w + (size_t)ly * A.tile_w + lx) * 3;
@@ -179,6 +176,60 @@ __global__ void __launch_bounds__(256) r1_resolve_kernel(const R1ResolveArgs A)
             if (threadIdx.x == 0)
                 A.frame_rays[(size_t)lt_all * gridDim.x + blockIdx.x] = s_part[0] + s_part[1] + s_part[2] + s_part[3];
             __syncthreads();
+        }
+    }
+}
+
+// ============================================================================================
+// Progressive passes (r1_render_pass): in place of the resolve launch.  One thread per pixel of a padded tile, as the resolve: the
+// accumulator (or 0.0f on the pass that starts the frame) plus the pass's records in sample order — the same sequence of fp32 adds the
+// resolve of the whole frame makes — stored back, then quantised as the resolve does with n = first_sample + spp samples summed.
+// ============================================================================================
+__global__ void __launch_bounds__(256) r1_accum_kernel(const R1AccumArgs A)
+{
+    if (blockIdx.x == 0 && blockIdx.y == 0 && A.rays_src)
+    {
+        // the pass's ray count (the trace kernel's), then the counter block zeroed for the next launch: as r1_resolve_kernel
+        if (threadIdx.x == 0)
+            *A.rays_dst = *A.rays_src;
+        __syncthreads();
+        if (A.reset)
+            ((uint4 *)A.reset)[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
+    }
+    const uint32_t tile_px = (uint32_t)(A.tile_w * A.tile_h);
+    for (uint32_t lt = blockIdx.y; lt < A.n_local_tiles; lt += gridDim.y)
+    {
+        const int x0 = (int)(lt % (uint32_t)A.tiles_x) * A.tile_w;
+        const int y0 = (int)(lt / (uint32_t)A.tiles_x) * A.tile_h;
+        const int tw = min(A.tile_w, A.width - x0);
+        const int th = min(A.tile_h, A.height - y0);
+        for (uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x; pix < tile_px; pix += gridDim.x * blockDim.x)
+        {
+            const int ly = (int)(pix / (uint32_t)A.tile_w);
+            const int lx = (int)(pix - (uint32_t)ly * (uint32_t)A.tile_w);
+            if (lx >= tw || ly >= th)
+                continue; // void slots of an edge tile
+            float4 *const acc = A.accum + (size_t)lt * tile_px + pix;
+            float cr = 0, cg = 0, cb = 0;
+            if (!A.fresh)
+            {
+                const float4 a = *acc;
+                cr = a.x, cg = a.y, cb = a.z;
+            }
+            const float4 *s = A.samples + (size_t)lt * A.full + pix; // [tile][sample][pixel]
+            for (int i = 0; i < A.spp; ++i)
+            {
+                const float4 v = s[(size_t)i * tile_px];
+                cr += v.x, cg += v.y, cb += v.z; // col += color(...) rayweek1.cpp:762
+            }
+            *acc = make_float4(cr, cg, cb, 0.0f);
+            if (A.out)
+            {
+                uint8_t r, g, b;
+                quantise_pixel(cr, cg, cb, A.inv_n, r, g, b);
+                uint8_t *const o = A.out + ((size_t)(y0 + ly) * A.width + (x0 + lx)) * 3;
+                o[0] = r, o[1] = g, o[2] = b;
+            }
         }
     }
 }
@@ -296,6 +347,8 @@ R1_TU_DECL(grid_big)
 // mode, big scenes have no latency mode.
 extern "C" int r1_trace_mode(int variant, int big, int wanted)
 {
+    if (wanted == 4) // progressive passes: the product variants' MODE 4 builds (r1_pass_kernel); none of the diagnostic builds
+        return variant == 1 || variant == 2 || variant == 4 || variant == 7 ? 4 : -1;
     if (variant == 1)
         return 0;
     if (variant == 3 || variant == 5 || variant == 8)
@@ -318,8 +371,10 @@ extern "C" hipError_t r1_launch_trace(const R1TraceArgs *args, int variant, int 
     if (mode != r1_trace_mode(variant, big_in, mode))
         return hipErrorInvalidValue; // the caller sizes its arguments by the mode: it must be the one that is built
     const int batch = args->batch != nullptr; // frame batches: the MODE 3 build of the throughput kernels (variants 2, 4 and 7 only)
-    if (batch && (mode != 0 || (variant != 2 && variant != 4 && variant != 7)))
+    if (batch && mode != 4 && (mode != 0 || (variant != 2 && variant != 4 && variant != 7)))
         return hipErrorInvalidValue;
+    if (mode == 4 && !batch)
+        return hipErrorInvalidValue; // (a pass reads its first sample through args->batch)
     if (variant == 3 && big)
         variant = 2; // (no diagnostic build of the LDS-tiled sweep)
     // the throughput builds of the product kernels sum their tiles themselves (R1_LAND): a launch through them says on how many XCDs
@@ -381,6 +436,15 @@ extern "C" hipError_t r1_launch_resolve(const R1ResolveArgs *args, int max_rows,
     if (args->frame_rays) // frame batches: per-frame ray counts from the launch's partial sums ([tile of the batch][bx])
         hipLaunchKernelGGL(r1_batch_counts_kernel, dim3(args->n_frames), dim3(256), 0, stream, args->frame_rays, args->n_local_tiles * (uint32_t)bx,
                            args->out, args->out_stride, args->rays_offset);
+    return hipGetLastError();
+}
+
+// one row of workgroups per tile (at most 65535 rows), as the synchronous frame's resolve launch
+extern "C" hipError_t r1_launch_accum(const R1AccumArgs *args, hipStream_t stream)
+{
+    const int bx = (args->tile_w * args->tile_h + 255) / 256;
+    const int by = (int)(args->n_local_tiles < 65535u ? args->n_local_tiles : 65535u);
+    hipLaunchKernelGGL(r1_accum_kernel, dim3(bx, by), dim3(256), 0, stream, *args);
     return hipGetLastError();
 }
 

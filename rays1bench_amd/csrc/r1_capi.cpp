@@ -24,8 +24,9 @@
 #include "r1_grid.h"
 
 extern "C" hipError_t r1_launch_trace(const R1TraceArgs *args, int variant, int big, int mode, int blocks, size_t grid_lds, hipStream_t stream);
-extern "C" int r1_trace_mode(int variant, int big, int wanted); // 0 samples + one queue, 1 latency, 2 pixel: what is built for (variant, big)
+extern "C" int r1_trace_mode(int variant, int big, int wanted); // 0 samples + one queue, 1 latency, 2 pixel, 4 pass: what is built for (variant, big)
 extern "C" hipError_t r1_launch_resolve(const R1ResolveArgs *args, int max_rows, hipStream_t stream);
+extern "C" hipError_t r1_launch_accum(const R1AccumArgs *args, hipStream_t stream);
 extern "C" hipError_t r1_launch_wavefront(R1WaveArgs *w, int blocks, hipStream_t stream);
 extern "C" hipError_t r1_launch_land_arm(uint32_t *tile_cnt, unsigned long long *frame_rays, uint32_t *frame_left, uint32_t n_frames, uint32_t n_local_tiles,
                                          int width, int height, int spp, int tile_w, int tile_h, int tiles_x, int shard, int num_shards, hipStream_t stream);
@@ -155,7 +156,7 @@ struct r1_context
     unsigned long long *host_word = nullptr, *host_word_dev = nullptr;
     int default_variant = 4;    // what R1_VARIANT_DEFAULT resolves to for the scene in the context (r1_set_scene): synchronous frames
     int default_variant_tp = 4; // ... and frames in flight (the throughput kernels: measured apart, the two kernel families do not rank alike)
-    int occupancy[96] = {0}; // [variant + 16 * big + 32 * mode]
+    int occupancy[160] = {0}; // [variant + 16 * big + 32 * mode]
     bool pixel_mode = false; // r1_set_pixel_mode
     DevBuf gstack; // blocks per CU of the trace kernel, by variant
     // per-tile entry nodes for primary rays (R1_ENTRY): the tree's nodes on the host, the device table, what it was computed for
@@ -168,6 +169,12 @@ struct r1_context
     int entry_frames = 0;
     bool entry_valid = false;
     DevBuf land_spill; // R1_LAND: [waves of the grid][tiles of the launch] every wave's list of the tiles it took chunks from
+    // progressive passes (r1_render_pass): the frame being accumulated
+    DevBuf accum;              // [local tile][pixel of the padded tile] fp32 {r, g, b, 0}
+    bool pass_valid = false;   // accum holds samples [0, pass_samples) of pass_key's frame (false after r1_set_scene or a failed pass)
+    r1_params pass_key;        // the params that started it (spp: that pass's)
+    int32_t pass_samples = 0;
+    uint64_t pass_rays = 0;    // color() calls of those samples
 
     r1_launch_info info;
 };
@@ -280,7 +287,7 @@ extern "C" void r1_destroy(r1_context *c)
     release(c->bvh_nodes), release(c->bvh_prims), release(c->bvh_ids), release(c->grid_tab), release(c->grid_out), release(c->grid_dev), release(c->grid_tab32), release(c->grid_dev32);
     release(c->wf_paths), release(c->wf_hits), release(c->wf_queue), release(c->wf_counts);
     release(c->bvh_wide), release(c->bvh_entry), release(c->land_spill), release(c->gstack), release(c->counters), release(c->samples), release(c->image), release(c->batch_rays);
-    release(c->wave_log);
+    release(c->wave_log), release(c->accum);
     if (c->host_word)
         (void)hipHostFree(c->host_word);
     for (hipEvent_t e : c->ring)
@@ -447,8 +454,9 @@ static std::vector<R1Group> build_groups(uint32_t na, const std::vector<double> 
 // timed benchmark() call, the kernel choice of each rank and a 62 MB workspace depend on a wall-clock race: VERDICT r03 / ADVICE r03.)
 struct Batch;
 struct Landing;
+struct Pass;
 static int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int block_layout, void *d_rays, hipStream_t st, bool throughput_mode,
-                         const Batch *batch = nullptr, Landing *landing = nullptr);
+                         const Batch *batch = nullptr, Landing *landing = nullptr, const Pass *pass = nullptr);
 
 // ---- 4-wide nodes (R1_BVH4) -------------------------------------------------------------------------------------
 // The binary tree of a small scene collapsed: a wide node starts as a binary node's two children and replaces its inner child with the
@@ -569,6 +577,7 @@ extern "C" int r1_set_scene(r1_context *c, const r1_scene *s, const r1_camera *c
         r1_set_error("r1_set_scene: null argument");
         return R1_EINVAL;
     }
+    c->pass_valid = false; // (a progressive frame does not continue across a scene upload, even of the same arrays)
     R1_HIP(hipSetDevice(c->device));
 
     const float *const src[9] = {s->center_x, s->center_y, s->center_z, s->radius_sq, s->inv_radius, s->albedo_r, s->albedo_g, s->albedo_b, s->mat_param};
@@ -1017,6 +1026,14 @@ struct Landing
     bool used = false;
 };
 
+// A progressive pass (r1_render_pass): samples [first_sample, first_sample + spp) traced by the MODE 4 kernels, then r1_accum_kernel instead of
+// the resolve launch.  d_out of enqueue_frame receives the preview unless `image` is false.
+struct Pass
+{
+    int32_t first_sample = 0;
+    bool image = true;
+};
+
 // device address of page-locked host memory (r1_host_alloc, hipHostMalloc, hipHostRegister), or null for anything else
 static void *mapped_host(const void *ptr)
 {
@@ -1102,7 +1119,7 @@ static int ensure_grid(r1_context *c)
 // Enqueues the frame (trace + resolve) on `st`.  d_out / d_rays are device addresses; d_rays == NULL stands for the context's own
 // count word (counters + R1_COUNTER_BYTES; the allocation may move in here, so callers take that address afterwards).
 static int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int block_layout, void *d_rays, hipStream_t st,
-                         bool throughput_mode, const Batch *batch, Landing *landing)
+                         bool throughput_mode, const Batch *batch, Landing *landing, const Pass *pass)
 {
     const int n_frames = batch ? batch->n_frames : 1;
     if (!c->have_scene)
@@ -1134,6 +1151,8 @@ static int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int blo
         return rc;
     if ((rc = ensure_counters(c, p, n_frames)))
         return rc;
+    if (pass && (rc = ensure(c->accum, (size_t)c->n_local_tiles * p->tile_w * p->tile_h * 16)))
+        return rc;
     if (!d_rays)
         d_rays = (char *)c->counters.p + R1_COUNTER_BYTES;
     // kernel mode: the host-returning entry points run in latency mode, the throughput entry point with few long-lived
@@ -1147,7 +1166,12 @@ static int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int blo
                             (grid && (!c->grid_small || (throughput_mode && c->pixel_mode)))) ? 1 : 0;
     static const int tp_mode_env = (int)r1_knob("R1_TP_MODE", -1); // tuning experiments
     const int tp_mode = c->pixel_mode ? 2 : (tp_mode_env >= 0 && tp_mode_env <= 2 ? tp_mode_env : 0);
-    const int mode = variant == 6 ? 0 : r1_trace_mode(variant, big_scene_, throughput_mode ? tp_mode : 1);
+    const int mode = variant == 6 ? 0 : r1_trace_mode(variant, big_scene_, pass ? 4 : (throughput_mode ? tp_mode : 1));
+    if (mode < 0)
+    {
+        r1_set_error("variant %d has no progressive-pass build", p->variant);
+        return R1_EINVAL;
+    }
     const bool pixel_mode = mode == 2;
     if (batch && (mode != 0 || variant == 6 || variant == 3 || variant == 5 || variant == 8 || variant == 1))
     {
@@ -1217,6 +1241,20 @@ static int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int blo
             c->batch_args_last = ba, c->batch_args_stream = st;
             R1_HIP(r1_launch_put6((char *)c->counters.p + R1_COUNTER_BYTES + 64 + 32 * c->batch_args_slot, (const uint32_t *)&ba, st));
         }
+        a.batch = (const R1BatchArgs *)((char *)c->counters.p + R1_COUNTER_BYTES + 64 + 32 * c->batch_args_slot);
+    }
+    if (pass)
+    {
+        // the pass's first sample, in a batch-argument slot of its own (the MODE 4 kernels read it where a sample is seeded); a batch that
+        // follows takes a new slot (its numbers never equal the cleared ones: n_frames >= 2)
+        R1PassArgs pa;
+        memset(&pa, 0, sizeof(pa));
+        pa.first_sample = (uint32_t)pass->first_sample;
+        static_assert(sizeof(R1PassArgs) == 24, "r1_launch_put6 writes the six words of R1PassArgs");
+        c->batch_args_slot = (c->batch_args_slot + 1) & 7;
+        memset(&c->batch_args_last, 0, sizeof(c->batch_args_last));
+        c->batch_args_stream = st;
+        R1_HIP(r1_launch_put6((char *)c->counters.p + R1_COUNTER_BYTES + 64 + 32 * c->batch_args_slot, (const uint32_t *)&pa, st));
         a.batch = (const R1BatchArgs *)((char *)c->counters.p + R1_COUNTER_BYTES + 64 + 32 * c->batch_args_slot);
     }
     a.full = c->full;
@@ -1354,7 +1392,7 @@ static int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int blo
     }
     if (mode == 1 && land)
         a.chunk_max = a.chunk_min = 64u; // (the XCDs' cursors hand out the wave-fulls: eight lines instead of one, no sub-queues)
-    else if (mode == 1)
+    else if (mode == 1 || (mode == 4 && !big_scene_))
     {
         static const int nq_env = (int)r1_knob("R1_NQ", 0), ch_env = (int)r1_knob("R1_CHUNK", 0);
         long long nq = nq_env > 0 ? nq_env : R1_SUBQUEUES;
@@ -1531,7 +1569,24 @@ static int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int blo
         r.reset = (uint32_t *)c->counters.p;
     }
     static const int resolve_rows = (int)r1_knob("R1_RESOLVE_ROWS", R1_RESOLVE_ROWS_TP); // tuning experiments
-    if (land)
+    if (pass && c->n_local_tiles)
+    {
+        // progressive pass: the records go into the accumulator, and the preview of samples [0, first_sample + spp) into d_out
+        R1AccumArgs ac;
+        memset(&ac, 0, sizeof(ac));
+        ac.samples = (const float4 *)c->samples.p;
+        ac.accum = (float4 *)c->accum.p;
+        ac.out = pass->image ? (uint8_t *)d_out : nullptr;
+        ac.full = c->full;
+        ac.width = p->width, ac.height = p->height, ac.spp = p->spp;
+        ac.tile_w = p->tile_w, ac.tile_h = p->tile_h, ac.tiles_x = a.tiles_x;
+        ac.n_local_tiles = c->n_local_tiles;
+        ac.fresh = pass->first_sample == 0 ? 1u : 0u;
+        ac.inv_n = (float)(1.0f / (pass->first_sample + p->spp)); // rayweek1.cpp:765 at the accumulated spp
+        ac.rays_src = r.rays_src, ac.rays_dst = r.rays_dst, ac.reset = r.reset;
+        R1_HIP(r1_launch_accum(&ac, st));
+    }
+    else if (land)
         ; // the trace launch resolved its tiles itself
     else if (c->n_local_tiles && !pixel_mode)
         R1_HIP(r1_launch_resolve(&r, throughput_mode ? resolve_rows : 0, st));
@@ -1693,6 +1748,92 @@ extern "C" int r1_render_samples(r1_context *c, const r1_params *p, uint8_t *rgb
         return R1_EINVAL;
     }
     return render_host(c, p, rgb_out, num_rays_out, nullptr, samples_out);
+}
+
+// Progressive rendering: samples [first_sample, first_sample + spp) of every pixel, added in sample order to the context's fp32 accumulator.  The
+// accumulator then holds exactly the sums the resolve of a frame of first_sample + spp samples computes (a sample's streams depend on (seed,
+// pixel, sample index) only, include/rays1_seed.h), so every preview is that frame's image, bit for bit.
+static bool same_pass_frame(const r1_params &a, const r1_params &b) // every field but spp
+{
+    return a.width == b.width && a.height == b.height && a.max_bounces == b.max_bounces && a.seed == b.seed && a.tile_w == b.tile_w &&
+           a.tile_h == b.tile_h && a.shard == b.shard && a.num_shards == b.num_shards && a.variant == b.variant;
+}
+
+extern "C" int r1_render_pass(r1_context *c, const r1_params *p, int32_t first_sample, uint8_t *rgb_out, uint64_t *num_rays_out)
+{
+    if (!c || !p)
+    {
+        r1_set_error("r1_render_pass: null argument");
+        return R1_EINVAL;
+    }
+    int rc = r1_params_check(p);
+    if (rc)
+        return rc;
+    if (p->num_shards != 1)
+    {
+        r1_set_error("r1_render_pass renders whole frames (num_shards == 1)");
+        return R1_EINVAL;
+    }
+    if (p->variant == R1_VARIANT_STATS || p->variant == R1_VARIANT_BVH_STATS || p->variant == R1_VARIANT_GRID_STATS || p->variant == R1_VARIANT_WAVEFRONT)
+    {
+        r1_set_error("r1_render_pass: variant %d (a diagnostic build or the wavefront variant) has no progressive-pass build", p->variant);
+        return R1_EINVAL;
+    }
+    if (first_sample < 0 || (int64_t)first_sample + p->spp > (int64_t)INT32_MAX)
+    {
+        r1_set_error("r1_render_pass: first_sample %d + spp %d is not within [0, INT32_MAX]", first_sample, p->spp);
+        return R1_EINVAL;
+    }
+    if (first_sample > 0 && !(c->pass_valid && c->pass_samples == first_sample && same_pass_frame(c->pass_key, *p)))
+    {
+        if (!c->pass_valid)
+            r1_set_error("r1_render_pass: no accumulation to continue (start one with first_sample 0)");
+        else if (c->pass_samples != first_sample)
+            r1_set_error("r1_render_pass: first_sample %d, but %d samples are accumulated", first_sample, c->pass_samples);
+        else
+            r1_set_error("r1_render_pass: the parameters differ from those that started the accumulation (only spp may change)");
+        return R1_EINVAL;
+    }
+    if (!c->have_scene)
+    {
+        r1_set_error("no scene set (call r1_set_scene first)");
+        return R1_EINVAL;
+    }
+    int32_t tiles = 0;
+    if ((rc = r1_tile_count(p, &tiles, nullptr)))
+        return rc;
+    if ((uint64_t)p->tile_w * p->tile_h * p->spp * (uint64_t)tiles >= ((uint64_t)1 << 31))
+    {
+        r1_set_error("a pass of %dx%dx%d with %dx%d tiles exceeds 2^31 sample slots per launch", p->width, p->height, p->spp, p->tile_w, p->tile_h);
+        return R1_ELIMIT;
+    }
+    R1_HIP(hipSetDevice(c->device));
+    const size_t img_bytes = (size_t)p->width * p->height * 3;
+    if (rgb_out && (rc = ensure(c->image, img_bytes + 64)))
+        return rc;
+    // from here on a failure leaves the accumulator in an unknown state: only first_sample == 0 is accepted next
+    c->pass_valid = false;
+    const bool direct = c->host_word_dev != nullptr; // the pass's ray count straight into the page-locked word, as r1_render
+    Pass ps;
+    ps.first_sample = first_sample;
+    ps.image = rgb_out != nullptr;
+    if ((rc = enqueue_frame(c, p, c->image.p, 0, direct ? (void *)c->host_word_dev : nullptr, c->stream, false, nullptr, nullptr, &ps)))
+        return rc;
+    uint64_t rays = 0;
+    if (rgb_out)
+        R1_HIP(hipMemcpyAsync(rgb_out, c->image.p, img_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (!direct)
+        R1_HIP(hipMemcpyAsync(&rays, (char *)c->counters.p + R1_COUNTER_BYTES, 8, hipMemcpyDeviceToHost, c->stream));
+    R1_HIP(hipStreamSynchronize(c->stream));
+    if (direct)
+        rays = *(volatile unsigned long long *)c->host_word;
+    c->pass_rays = (first_sample == 0 ? 0u : c->pass_rays) + rays;
+    c->pass_samples = first_sample + p->spp;
+    c->pass_key = *p;
+    c->pass_valid = true;
+    if (num_rays_out)
+        *num_rays_out = c->pass_rays;
+    return R1_OK;
 }
 
 // Pipelined form of r1_render (frames in flight, results on the HOST): the frame is enqueued with the throughput

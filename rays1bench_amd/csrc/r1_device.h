@@ -140,6 +140,14 @@ struct R1BatchArgs
     uint32_t n_local_tiles;
 };
 
+// Progressive passes (r1_render_pass, the MODE 4 builds): the pass's first global sample index, device memory behind R1TraceArgs::batch
+// (null in every single-frame launch).  Six words: written by r1_launch_put6 into a batch-argument slot.
+struct R1PassArgs
+{
+    uint32_t first_sample;
+    uint32_t unused[5];
+};
+
 // What the waves that sum finished tiles need (R1_LAND); by value in the kernel arguments, read when a wave has run out of samples.
 struct R1LandArgs
 {
@@ -305,6 +313,25 @@ struct R1ResolveArgs
     const unsigned long long *rays_src; // null: the trace kernel counted into the caller's word itself
     unsigned long long *rays_dst;
     uint32_t *reset;             // R1_COUNTER_BYTES to zero, or null
+};
+
+// Progressive passes (r1_accum_kernel, in place of the resolve launch): adds the pass's records, in sample order, to the context's per-pixel
+// fp32 accumulator and (optionally) quantises the sum of samples [0, first_sample + spp) into the row-major image.
+struct R1AccumArgs
+{
+    const float4 *samples;       // the pass's records, [local tile][pass-local sample][pixel of the padded tile]
+    float4 *accum;               // [local tile][pixel of the padded tile] {r, g, b, 0}
+    uint8_t *out;                // row-major width*height*3 preview, or null: accumulate only
+    uint32_t full;               // tile_w * tile_h * spp
+    int32_t width, height, spp;  // spp: the pass's samples
+    int32_t tile_w, tile_h, tiles_x;
+    uint32_t n_local_tiles;
+    uint32_t fresh;              // 1: the pass starts the accumulation (first_sample == 0): start from 0.0f
+    float inv_n;                 // (float)(1.0f / n), n = first_sample + spp
+    // as R1ResolveArgs: publish the pass's ray count, zero the counter block for the next launch
+    const unsigned long long *rays_src;
+    unsigned long long *rays_dst;
+    uint32_t *reset;
 };
 
 #endif

@@ -1244,7 +1244,9 @@ __device__ __forceinline__ bool tile_pixel(const R1TraceArgs &A, const uint32_t 
 
 // sample slot k -> (tile, pixel, sample); then seeds + primary ray.
 // Returns false for a void slot (pixel of an edge tile that lies outside the image).
-template <bool BATCH = false>
+// PASS (progressive passes, MODE 4): s is the pass-local sample index — the record's place — and the sample is seeded with its global
+// index s + first_sample, which the pass's R1PassArgs hold behind A.batch.
+template <bool BATCH = false, bool PASS = false>
 __device__ __forceinline__ bool start_sample(const R1TraceArgs &A, Path &p, uint32_t k)
 {
     const uint32_t j = fastdiv(k, A.div_full); // padded tile, frame-major over the frames of the launch
@@ -1268,8 +1270,25 @@ __device__ __forceinline__ bool start_sample(const R1TraceArgs &A, Path &p, uint
     // output slot: samples are stored [tile][sample][pixel] so that the resolve pass reads
     // coalesced (consecutive pixels of one sample index)
     p.k = (j * (uint32_t)A.spp + s) * (uint32_t)(A.tile_w * A.tile_h) + pix;
-    start_ray(A, p, x, y, s, seed);
+    uint32_t s_global = s;
+    if (PASS)
+    {
+        typedef const uint32_t __attribute__((address_space(4))) *cu32_ptr;
+        s_global += ((cu32_ptr)A.batch)[0]; // R1PassArgs::first_sample
+    }
+    start_ray(A, p, x, y, s_global, seed);
     return true;
+}
+
+// rayweek1.cpp:765-775: col *= 1 / spp; sqrtf per channel; (uint8)(int)(c * 255.99f) — the resolve launch and the progressive passes'
+// accumulate launch (inv = (float)(1.0f / samples summed))
+__device__ __forceinline__ void quantise_pixel(float cr, float cg, float cb, const float inv, uint8_t &r, uint8_t &g, uint8_t &b)
+{
+    cr *= inv, cg *= inv, cb *= inv;
+    cr = ieee_sqrt(cr), cg = ieee_sqrt(cg), cb = ieee_sqrt(cb);
+    r = (uint8_t)(int)(cr * 255.99f);
+    g = (uint8_t)(int)(cg * 255.99f);
+    b = (uint8_t)(int)(cb * 255.99f);
 }
 
 // PIXEL mode (frames in flight): a lane owns a PIXEL and runs its spp samples one after the other, so
@@ -1745,11 +1764,14 @@ struct TraceWaves
 // long-lived waves per frame) leaves them out: they cost it registers and bring it nothing.
 // MODE 0 = frames in flight (the throughput entry point): samples in one guided queue, few long-lived waves per frame.
 // MODE 2 = PIXEL mode (the throughput entry point after r1_set_pixel_mode; see struct Pixel): the queue holds pixels.
-// (the body of the kernel; r1_trace_kernel and, for the uniform grid, r1_grid_kernel below are its __global__ instances)
+// MODE 4 = a progressive pass (r1_render_pass): small scenes as MODE 1, big scenes as MODE 0 without landing; the records take the pass-local
+// sample index, the seeds the global one (start_sample), and r1_accum_kernel sums them into the frame's accumulator.
+// (the body of the kernel; r1_trace_kernel and, for the uniform grid, r1_grid_kernel below are its __global__ instances; r1_pass_kernel the MODE 4 ones)
 template <int VARIANT, bool STATS, bool BIG, int MODE>
 __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
 {
-    constexpr bool LAT = MODE == 1, PIX = MODE == 2, BATCH = MODE == 3; // MODE 3 = MODE 0 whose queue spans the frames of a batch
+    constexpr bool PASS = MODE == 4;
+    constexpr bool LAT = MODE == 1 || (PASS && !BIG), PIX = MODE == 2, BATCH = MODE == 3; // MODE 3 = MODE 0 whose queue spans the frames of a batch
     // tiles resolved inside the kernel: the throughput builds of the tree kernels (frames in flight, MODE 0 / 3); a
     // launch through them is a landing launch (r1_launch_trace checks).  The synchronous frame keeps the resolve launch (measured
     // slower with its tiles summed at wave exit, R1_LAND_SYNC), and so do the exhaustive sweep's kernels.
@@ -2027,7 +2049,7 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
             if (SPARE)
             {
                 if (!has_spare && rank < avail)
-                    has_spare = start_sample<BATCH>(FA, spare, q_next + rank); // false: void slot, ask again
+                    has_spare = start_sample<BATCH, PASS>(FA, spare, q_next + rank); // false: void slot, ask again
             }
             else if (!alive && rank < avail)
             {
@@ -2038,7 +2060,7 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
                         start_ray(A, p, (int)(px.xy & 0xFFFFu), (int)(px.xy >> 16), 0u, A.seed);
                 }
                 else
-                    alive = start_sample<BATCH>(FA, p, q_next + rank); // false: void slot, ask again
+                    alive = start_sample<BATCH, PASS>(FA, p, q_next + rank); // false: void slot, ask again
                 if (VARIANT == 4 && alive)
                     trav_start(tv);
             }
@@ -2272,6 +2294,13 @@ template <bool STATS, bool BIG, int MODE>
 __global__ void __launch_bounds__(R1_BLOCK, (TraceWaves<7, STATS, BIG, MODE>::value)) r1_grid_kernel(const R1TraceArgs A)
 {
     r1_trace_body<7, STATS, BIG, MODE>(A);
+}
+
+// Progressive passes (MODE 4): the same body under a name of its own, for the tree (4), the exhaustive sweeps (2, 1) and the grid (7)
+template <int VARIANT, bool BIG>
+__global__ void __launch_bounds__(R1_BLOCK, (TraceWaves<VARIANT, false, BIG, 4>::value)) r1_pass_kernel(const R1TraceArgs A)
+{
+    r1_trace_body<VARIANT, false, BIG, 4>(A);
 }
 
 #endif // R1_TRACE_HPP

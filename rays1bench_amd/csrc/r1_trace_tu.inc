@@ -11,7 +11,8 @@
 #define R1_CAT2(a, b, c) a##b##c
 #define R1_CAT(a, b, c) R1_CAT2(a, b, c)
 
-// S = diagnostic build, M = mode (0 frames in flight, 1 latency, 2 pixel, 3 frame batches); calls X(V, S, M) for the instance that is built
+// S = diagnostic build, M = mode (0 frames in flight, 1 latency, 2 pixel, 3 frame batches; 4 progressive passes: R1_TU_PASS below); calls X(V, S, M)
+// for the instance that is built
 #if R1_TU_GRID
 // (PIXEL mode: the big-scene build only, r1_capi.cpp; r1_launch_trace refuses the small one)
 #define R1_TU_DISPATCH(X)                                                                                              \
@@ -69,10 +70,32 @@
 #define R1_TU_KERNEL(V, S, M) r1_trace_kernel<V, S, R1_TU_BIG, M>
 #endif
 
+// progressive passes (MODE 4, r1_render_pass): r1_pass_kernel<V, big> for the family's product variants; calls X(V) for the instance that is built
+#if R1_TU_GRID
+#define R1_TU_PASS(X) X(7)
+#elif R1_TU_TREE
+#define R1_TU_PASS(X) X(4)
+#else
+#define R1_TU_PASS(X)                                                                                                  \
+    if (variant == 1)                                                                                                  \
+        X(1)                                                                                                           \
+    else                                                                                                               \
+        X(2)
+#endif
+
 extern "C" hipError_t R1_CAT(r1_tu_, R1_TU_NAME, _launch)(const R1TraceArgs *args, int variant, int mode, int batch, int blocks, size_t dyn_lds, hipStream_t stream)
 {
 #define R1_GO(V, S, M) hipLaunchKernelGGL((R1_TU_KERNEL(V, S, M)), dim3(blocks), dim3(R1_BLOCK), dyn_lds, stream, *args)
-    R1_TU_DISPATCH(R1_GO)
+#define R1_GO_PASS(V) hipLaunchKernelGGL((r1_pass_kernel<V, R1_TU_BIG>), dim3(blocks), dim3(R1_BLOCK), dyn_lds, stream, *args);
+    if (mode == 4)
+    {
+        R1_TU_PASS(R1_GO_PASS)
+    }
+    else
+    {
+        R1_TU_DISPATCH(R1_GO)
+    }
+#undef R1_GO_PASS
 #undef R1_GO
     return hipGetLastError();
 }
@@ -81,6 +104,12 @@ extern "C" hipError_t R1_CAT(r1_tu_, R1_TU_NAME, _occupancy)(int variant, int mo
 {
     const int batch = 0; // (the batch build of a kernel has the occupancy of its single-frame build)
 #define R1_OCC(V, S, M) return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, R1_TU_KERNEL(V, S, M), R1_BLOCK, dyn_lds)
+#define R1_OCC_PASS(V) return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, r1_pass_kernel<V, R1_TU_BIG>, R1_BLOCK, dyn_lds);
+    if (mode == 4)
+    {
+        R1_TU_PASS(R1_OCC_PASS)
+    }
     R1_TU_DISPATCH(R1_OCC)
+#undef R1_OCC_PASS
 #undef R1_OCC
 }

@@ -20,6 +20,8 @@
 //     --gather host: one host thread + r1_context per device, each device copies its own tiles
 //         into the caller's pixel buffer (also works oversubscribed: N contexts on fewer GPUs)
 // bench.py's one-process-per-GPU form (torch.distributed) gathers the same records.
+// --passes K renders each frame progressively (r1_render_pass): K contiguous passes whose sample counts differ by at most one, pixels
+// asked for on the last pass only; the timed span covers all of them, and the image and ray count are those of the one-launch frame.
 // --backend hip (default) | cpu-step1 | cpu-step12: the reference's two single-thread CPU stages
 // (r1_cpu_backends.cpp) behind the same benchmark(), for the README-style table
 // (README.md:38-84).  Named backends of this program only — never a fallback: with --backend hip and no
@@ -64,6 +66,7 @@ static int g_devices = 1;
 static int g_backend = 0; // 0 hip, 1 cpu-step1, 12 cpu-step12
 static int g_pipeline = 0; // --pipeline FRAMES: after the benchmark() runs, FRAMES frames per scene with several in flight (r1_render_async)
 static int g_inflight = 20;
+static int g_passes = 0;   // --passes K: every frame in K progressive passes (r1_render_pass); 0 = one r1_render
 int r1cpu_step12_render(const r1_scene *scene, const r1_camera *cam, int width, int height, int spp, int max_bounces, uint8_t *rgb,
                         uint64_t *num_rays); // r1_cpu_backends.cpp
 int r1cpu_step1_render(int scene_kind, const r1_scene *scene, const r1_camera *cam, int width, int height, int spp, uint8_t *rgb,
@@ -197,7 +200,22 @@ RESULT benchmark(Scene *scene, Pix *pixels, bool write_tga, const char *scene_na
         r1_params q = p;
         q.shard = i, q.num_shards = nd;
         int rc = r1_set_scene(g_ctx[i], scene->hitables, scene->camera);
-        if (rc == R1_OK)
+        if (rc == R1_OK && g_passes > 0)
+        {
+            // --passes K (one device): K contiguous passes, sizes differing by at most one; pixels on the last pass only
+            int32_t first = 0;
+            for (int k = 0; k < g_passes && rc == R1_OK; ++k)
+            {
+                q.spp = g_spp / g_passes + (k < g_spp % g_passes ? 1 : 0);
+                const bool last = k == g_passes - 1;
+                rc = r1_render_pass(g_ctx[i], &q, first, last ? &pixels[0].r : nullptr, &rays[i]);
+                double trace_ms = 0, total_ms = 0;
+                if (rc == R1_OK && r1_last_timing(g_ctx[i], &trace_ms, &total_ms) == R1_OK)
+                    dev_s[i] += total_ms * 1e-3;
+                first += q.spp;
+            }
+        }
+        else if (rc == R1_OK)
             rc = r1_render(g_ctx[i], &q, &pixels[0].r, &rays[i], &dev_s[i]);
         rcs[i] = rc;
         if (rc != R1_OK)
@@ -250,6 +268,8 @@ RESULT benchmark(Scene *scene, Pix *pixels, bool write_tga, const char *scene_na
                                                "box tree", "box tree + counters", "wavefront", "uniform grid", "uniform grid + counters"};
     printf("kernel:         %s (%d hittable spheres, %d inner nodes)\n", li.kernel >= 0 && li.kernel <= 8 ? kernel_names[li.kernel] : "?",
            li.spheres_active, li.bvh_nodes);
+    if (g_passes > 0)
+        printf("passes:         %d\n", g_passes);
     printf("device time:    %.3fms (%0.2f mrays/s)\n", device_seconds * 1e3, device_seconds ? result.num_rays / device_seconds / 1e6 : 0.0);
     printf("\n");
 
@@ -394,6 +414,7 @@ static int pipelined(const char *scene_name, int kind, int frames)
 int main(int argc, const char *argv[])
 {
     bool write_tga = false;
+    bool passes_given = false;
     int num_runs = 1;
     const static int MAX_NUMS = 32;
     RESULT results[MAX_NUMS];
@@ -428,6 +449,11 @@ int main(int argc, const char *argv[])
             g_pipeline = atoi(argv[++i]);
         else if (strcmp(argv[i], "--inflight") == 0 && i + 1 < argc)
             g_inflight = atoi(argv[++i]);
+        else if (strcmp(argv[i], "--passes") == 0 && i + 1 < argc)
+        {
+            g_passes = atoi(argv[++i]);
+            passes_given = true;
+        }
         else if (strcmp(argv[i], "--backend") == 0 && i + 1 < argc)
         {
             const char *b = argv[++i];
@@ -442,6 +468,11 @@ int main(int argc, const char *argv[])
     if (g_screen_w <= 0 || g_screen_h <= 0 || g_spp <= 0 || g_devices < 1 || g_devices > 64 || g_gather == -2 || g_backend < 0)
     {
         fprintf(stderr, "bad --width/--height/--spp/--devices/--gather/--backend\n");
+        return 1;
+    }
+    if (passes_given && (g_passes < 1 || g_passes > g_spp || g_backend != 0 || g_devices > 1 || g_gather == 1 || g_pipeline > 0))
+    {
+        fprintf(stderr, "bad --passes %d: needs 1 <= K <= spp (%d), the hip backend, one device (no --gather rccl) and no --pipeline\n", g_passes, g_spp);
         return 1;
     }
 
