@@ -256,6 +256,7 @@ extern "C" int r1_create(int device, r1_context **out)
     }
     if (hipHostMalloc((void **)&c->host_word, 64, hipHostMallocMapped) == hipSuccess)
     {
+        memset(c->host_word, 0, 64); // (the runtime may hand back a recycled block: word 2 is land_check's "a resolver gave up" flag)
         if (hipHostGetDevicePointer((void **)&c->host_word_dev, c->host_word, 0) != hipSuccess)
         {
             (void)hipHostFree(c->host_word);
@@ -1408,24 +1409,30 @@ static int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int blo
             a.chunk_max = a.chunk_min = ch_env > 0 ? (uint32_t)ch_env : 64u;
         }
     }
+    int land_parity = 0;
     if (land)
     {
         // Launches alternate between two sets of queue heads and wave counts; workgroup 0 zeroes the set the launch before used, which
         // nobody touches any more (a workgroup that starts late still asks its own queue for work after the frame's last tile has been
         // summed, so a launch cannot clear its own).  After anything else has run through this context both sets (and the round-3 block) are cleared here.
-        if (!c->land_prev)
+        // The parity and the armed countdowns are committed only once the trace launch is enqueued: until then the context counts as
+        // neither, so a call refused from here on (tile lists too long, an allocation, the launch) sends the next one through both memsets
+        // and the arming launch — it would otherwise take the set the last launch that ran left exhausted, and no tile would be summed.
+        const bool prev = c->land_prev, armed = c->land_armed;
+        c->land_prev = false, c->land_armed = false;
+        land_parity = prev ? c->land_parity ^ 1 : 0;
+        if (!prev)
         {
             R1_HIP(hipMemsetAsync(c->counters.p, 0, R1_COUNTER_BYTES, st));
             R1_HIP(hipMemsetAsync((char *)c->counters.p + R1_COUNTER_BYTES + 1024, 0, R1_COUNTER_BYTES - 1024, st)); // (not the batch-argument slots in front of it)
-            c->land_parity = 1;
         }
-        c->land_parity ^= 1;
         char *const set0 = (char *)c->counters.p + 1024, *const set1 = (char *)c->counters.p + R1_COUNTER_BYTES + 1024;
-        a.queue = (uint32_t *)(c->land_parity ? set1 : set0);
-        a.land.clear_heads = (uint32_t *)(c->land_parity ? set0 : set1);
+        a.queue = (uint32_t *)(land_parity ? set1 : set0);
+        a.land.clear_heads = (uint32_t *)(land_parity ? set0 : set1);
         a.land.clear_count = (R1_COUNTER_BYTES - 1024) / 128;
         static_assert((R1_COUNTER_BYTES - 1024) / 128 <= R1_BLOCK && R1_COUNTER_TAIL >= 1024 + (R1_COUNTER_BYTES - 1024), "the second set of queue heads fits the tail");
-        // the launch's generation tags its sample records (1 .. 2^24 - 1; on wrap-around the records are wiped)
+        // the launch's generation tags its sample records (1 .. 2^24 - 1; on wrap-around the records are wiped).  Advanced at once, even by
+        // a call that is refused later: a tag no launch used costs nothing, one used again could let stale records pass for new ones
         c->land_gen = (c->land_gen + 1) & 0xFFFFFFu;
         if (c->land_gen == 0)
         {
@@ -1437,11 +1444,11 @@ static int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int blo
         unsigned long long *frame_rays = (unsigned long long *)((char *)c->counters.p + land_frames_off());
         uint32_t *frame_left = (uint32_t *)(frame_rays + n_frames);
         a.land_cnt = (uint32_t *)((char *)frame_rays + (((size_t)n_frames * 16 + 127) & ~(size_t)127)); // (every countdown on a 128-byte line of its own)
-        if (!c->land_armed || c->land_frames != n_frames || !same_tiling(c->land_key, *p))
+        if (!armed || c->land_frames != n_frames || !same_tiling(c->land_key, *p))
         {
             R1_HIP(r1_launch_land_arm(a.land_cnt, frame_rays, frame_left, (uint32_t)n_frames, c->n_local_tiles, p->width, p->height, p->spp, p->tile_w, p->tile_h,
                                       a.tiles_x, p->shard, p->num_shards, st));
-            c->land_armed = true, c->land_frames = n_frames, c->land_key = *p;
+            c->land_frames = n_frames, c->land_key = *p; // (land_armed: committed with the launch)
         }
         if (landing && landing->out && (batch || landing->rays))
         {
@@ -1595,6 +1602,8 @@ static int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int blo
             R1_HIP(hipMemsetAsync((char *)d_out + (size_t)f * batch->out_stride + batch->rays_offset, 0, 8, st));
     c->counters_clean = fused_clear;
     c->land_prev = land;
+    if (land)
+        c->land_parity = land_parity, c->land_armed = true;
     R1_HIP(hipEventRecord(e2, st));
     c->last0 = e0, c->last1 = e1, c->last2 = e2;
     c->timing_valid = true;

@@ -225,13 +225,19 @@ def test_shards_tile_the_frame_exactly(renderer, shards):
     w, h, spp = 300, 170, 4
     renderer.set_scene(r1.create_large_scene(w, h))
     full, full_rays, _ = renderer.render(mp(w, h, spp, 11))
-    acc = np.zeros_like(full)
+    tw = th = 32  # (make_params' default tiles) global tile t belongs to shard t % shards
+    ys, xs = np.mgrid[0:h, 0:w]
+    owner = ((ys // th) * ((w + tw - 1) // tw) + xs // tw) % shards
+    sentinel = 0xCD
+    acc = np.full_like(full, sentinel)
     total = 0
     for s in range(shards):
-        part = np.zeros_like(full)
+        part = np.full_like(full, sentinel)
         rays, _ = renderer.render_into(mp(w, h, spp, 11, shard=s, num_shards=shards), part)
-        assert not ((acc != 0) & (part != 0)).any() or True
-        acc = np.maximum(acc, part)
+        mine = owner == s
+        assert part[mine].tobytes() == full[mine].tobytes(), s  # the shard's own tiles: the full frame's pixels
+        assert (part[~mine] == sentinel).all(), s  # every other pixel untouched
+        acc[mine] = part[mine]
         total += rays
     assert total == full_rays
     assert acc.tobytes() == full.tobytes()
