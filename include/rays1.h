@@ -94,7 +94,10 @@ typedef struct r1_camera
 
 /* Runtime replacements for the reference's compile-time configuration
  * (src/common/common.h:19-28: SCREEN_W, SCREEN_H, NUM_SAMPLES_PER_PIXEL, MAX_BOUNCES)
- * plus the build-defined seeding contract (include/rays1_seed.h) and sharding. */
+ * plus the build-defined seeding contract (include/rays1_seed.h) and sharding.
+ * Limits (R1_ELIMIT): width, height <= 65535 and width * height * spp < 2^31; per launch, the padded sample slots
+ * (tiles of the launch * tile_w * tile_h * spp, times the frames of a batch) < 2^31.  Any tile size within them is
+ * rendered, a tile whose sample records span more than 4 GiB included. */
 typedef struct r1_params
 {
     int32_t width;       /* SCREEN_W                                              */

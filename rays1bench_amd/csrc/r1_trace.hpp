@@ -1604,28 +1604,36 @@ __device__ __forceinline__ bool land_resolve_tile(const R1TraceArgs &A, const ui
     const int tw = min(A.tile_w, A.width - x0), th = min(A.tile_h, A.height - y0);
     const uint32_t tile_px = (uint32_t)(A.tile_w * A.tile_h);
     // the tile's records [s][pixel], read with sc0 loads (buffer form: 16 bytes at once): they must come from the L2, not from this CU's
-    // vector L1 — a pass that meets a record whose store is still on its way would otherwise find the same stale line again
-    const __amdgpu_buffer_rsrc_t rec = __builtin_amdgcn_make_buffer_rsrc((void *)(A.samples + (size_t)t * A.full), 0, (int)(A.full * 16u), 0x00020000);
+    // vector L1 — a pass that meets a record whose store is still on its way would otherwise find the same stale line again.
+    // A tile's records can span 4 GiB and more (tile_px * spp < 2^31 records of 16 bytes), beyond what a buffer's 32-bit range and offset
+    // reach: every load gets a descriptor of its own, based (64-bit address) at the wave's 64 pixels of that sample, and an offset < 1 KiB
+    const float4 *const recs = A.samples + (size_t)t * A.full;
     constexpr int SC0 = 1;
     typedef uint32_t land_u4 __attribute__((ext_vector_type(4)));
     uint8_t *const out = L.out + (size_t)f * L.out_stride;
     const uint32_t spp = (uint32_t)A.spp;
     uint32_t bad = 0;
     unsigned long long rays = 0;
-    for (uint32_t pix = (uint32_t)lane; pix < tile_px; pix += 64u)
+    for (uint32_t p0 = 0; p0 < tile_px; p0 += 64u) // (wave-uniform: the descriptors below stay in SGPRs)
     {
+        const uint32_t pix = p0 + (uint32_t)lane;
         const int ly = (int)(pix / (uint32_t)A.tile_w), lx = (int)(pix - (uint32_t)ly * (uint32_t)A.tile_w);
-        if (lx >= tw || ly >= th)
+        if (pix >= tile_px || lx >= tw || ly >= th)
             continue; // void slots of an edge tile
+        const int range = (int)(min(64u, tile_px - p0) * 16u); // (a load outside the tile reads zeros, never a neighbour's records)
         float cr = 0, cg = 0, cb = 0;
         for (uint32_t s0 = 0; s0 < spp; s0 += LOADS)
         {
             const uint32_t n = min((uint32_t)LOADS, spp - s0); // (wave-uniform)
+            const float4 *const row = recs + (size_t)s0 * tile_px + p0;
             land_u4 v[LOADS];
 #pragma unroll
             for (uint32_t u = 0; u < LOADS; ++u)
                 if (u < n)
-                    v[u] = __builtin_amdgcn_raw_buffer_load_b128(rec, (int)(((s0 + u) * tile_px + pix) * 16u), 0, SC0);
+                {
+                    const __amdgpu_buffer_rsrc_t rec = __builtin_amdgcn_make_buffer_rsrc((void *)(row + (size_t)u * tile_px), 0, range, 0x00020000);
+                    v[u] = __builtin_amdgcn_raw_buffer_load_b128(rec, lane * 16, 0, SC0);
+                }
 #pragma unroll
             for (uint32_t u = 0; u < LOADS; ++u)
                 if (u < n)
