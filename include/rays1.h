@@ -167,6 +167,13 @@ int r1_device_count(void);
  * (rayweek1.cpp:845, :851). */
 int r1_set_scene(r1_context *ctx, const r1_scene *scene, const r1_camera *camera);
 
+/* Replaces the context's camera and nothing else: no table is built or uploaded and nothing is waited for (r1_set_scene with a
+ * camera that differs in one bit rebuilds the sphere groups and the box tree and drops the uniform grid).  The camera travels by
+ * value in every launch's arguments, so launches already enqueued keep the camera they were enqueued with.  Needs a scene
+ * (R1_EINVAL before the first r1_set_scene).  Ends a progressive accumulation as r1_set_scene does (the next r1_render_pass with
+ * first_sample > 0 returns R1_EINVAL).  r1_set_scene(the same arrays, this camera) afterwards still finds everything current. */
+int r1_set_camera(r1_context *ctx, const r1_camera *camera);
+
 /* Renders the frame (or this shard's tiles of it) and returns everything on the host.
  * Replaces TileRenderScheduler::run + render_tile (rayweek1.cpp:785-842, :722-782).
  *   rgb_out      width*height*3 bytes, row-major, row 0 = bottom row, Pix{r,g,b}
@@ -238,6 +245,17 @@ int r1_render_async(r1_context *ctx, const r1_params *params, uint8_t *rgb_out, 
  * frames only.  Each frame's pixels and count equal what r1_render returns for its seed. */
 size_t r1_frame_record_bytes(const r1_params *params);
 int r1_render_batch_async(r1_context *ctx, const r1_params *params, int32_t n_frames, uint32_t seed_stride, void *host_frames, void *hip_stream);
+
+/* Camera PATHS: r1_render_batch_async with cameras[f] in place of the context's camera for frame f — a turntable or a
+ * fly-through in one launch, the waves flowing from frame to frame (the MODE 5 kernels: where a sample starts, its lane loads the
+ * camera of the sample's frame from a device table).  Same frame records, same page-locked / pageable / NULL host_frames
+ * behaviour, same limits (R1_ELIMIT) and the same variants accepted and refused as r1_render_batch_async; whole frames only,
+ * n_frames >= 1.  `cameras` is host memory, n_frames entries, read during the call only.  The context's own camera is not
+ * changed.  Frame f's pixels and count equal r1_render with seed params->seed + f * seed_stride after
+ * r1_set_camera(ctx, &cameras[f]).  There is no sharded device form (r1_render_shard_device_batch with cameras) and no
+ * r1_multi form of it: more than one device has never run on hardware here, and camera paths add nothing to that debt. */
+int r1_render_path_async(r1_context *ctx, const r1_params *params, int32_t n_frames, uint32_t seed_stride, const r1_camera *cameras, void *host_frames,
+                         void *hip_stream);
 
 /* Page-locked, device-visible host memory for the render entry points' outputs (hipHostMalloc / hipHostFree). */
 int r1_host_alloc(size_t bytes, void **out);
@@ -358,6 +376,8 @@ typedef struct r1_multi r1_multi;
 int r1_multi_create(int32_t n_devices, const int32_t *devices, r1_multi **out);
 void r1_multi_destroy(r1_multi *m);
 int r1_multi_set_scene(r1_multi *m, const r1_scene *scene, const r1_camera *camera);
+/* r1_set_camera on every device's context. */
+int r1_multi_set_camera(r1_multi *m, const r1_camera *camera);
 /* rgb_out / num_rays_out as r1_render (whole frame); device_seconds_out (optional): render + gather
  * on the slowest device, from HIP events. */
 int r1_multi_render(r1_multi *m, const r1_params *params, uint8_t *rgb_out, uint64_t *num_rays_out, double *device_seconds_out);
@@ -458,6 +478,16 @@ int r1_host_scene_create(int kind, int32_t width, int32_t height, int32_t grid_w
 void r1_host_scene_destroy(r1_host_scene *hs);
 const r1_scene *r1_host_scene_spheres(const r1_host_scene *hs);
 const r1_camera *r1_host_scene_camera(const r1_host_scene *hs);
+/* The arguments the scene builder gave Camera::init (rayweek1.cpp:564, :595, :666), so that a caller can move the reference's
+ * own camera; the aspect is the width / height the scene was created for. */
+int r1_host_scene_view(const r1_host_scene *hs, float lookfrom[3], float lookat[3], float vup[3], float *vfov_degrees, float *aperture,
+                       float *focus_dist);
+
+/* Camera::init (rayweek1.cpp:366-379) in the reference's arithmetic — tan evaluated in double and rounded once, which is what the
+ * reference's optimised builds contain.  Host only.  R1_EINVAL for NULL pointers; otherwise it computes
+ * what that arithmetic computes, NaNs included (lookfrom == lookat, vup parallel to the view direction). */
+int r1_camera_look_at(const float lookfrom[3], const float lookat[3], const float vup[3], float vfov_degrees, float aspect, float aperture,
+                      float focus_dist, r1_camera *out);
 
 /* tga_write_rgb24 (common.h:86-122): writes a 24-bit TGA and, like the reference,
  * leaves `pixels` with R and B swapped.  Returns R1_OK or R1_EINVAL if the file

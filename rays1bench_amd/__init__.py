@@ -10,5 +10,5 @@ There is no CPU fallback: if librays1.so or a HIP device is missing, calls raise
 """
 from .binding import (  # noqa: F401
     R1Error, Renderer, Scene, Params, RESULT, benchmark, build, create_grid_scene, create_large_scene,
-    create_medium_scene, create_small_scene, device_count, lib, lib_path, log_results, make_params, tga_write_rgb24,
+    camera_look_at, camera_to_array, orbit_cameras, create_medium_scene, create_small_scene, device_count, lib, lib_path, log_results, make_params, tga_write_rgb24,
 )

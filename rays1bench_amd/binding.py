@@ -122,6 +122,7 @@ SYMBOLS = [
     ("r1_last_error", C.c_char_p, []),
     ("r1_device_count", C.c_int, []),
     ("r1_set_scene", C.c_int, [_ctx, C.POINTER(CScene), C.POINTER(CCamera)]),
+    ("r1_set_camera", C.c_int, [_ctx, C.POINTER(CCamera)]),
     ("r1_render", C.c_int, [_ctx, C.POINTER(Params), _u8p, _u64p, _dblp]),
     ("r1_render_samples", C.c_int, [_ctx, C.POINTER(Params), _u8p, _u64p, _f32p]),
     ("r1_render_pass", C.c_int, [_ctx, C.POINTER(Params), C.c_int32, _u8p, _u64p]),
@@ -131,6 +132,7 @@ SYMBOLS = [
     ("r1_render_async", C.c_int, [_ctx, C.POINTER(Params), _u8p, _u64p, C.c_void_p]),
     ("r1_frame_record_bytes", C.c_size_t, [C.POINTER(Params)]),
     ("r1_render_batch_async", C.c_int, [_ctx, C.POINTER(Params), C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    ("r1_render_path_async", C.c_int, [_ctx, C.POINTER(Params), C.c_int32, C.c_uint32, C.POINTER(CCamera), C.c_void_p, C.c_void_p]),
     ("r1_render_shard_device_batch", C.c_int, [_ctx, C.POINTER(Params), C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]),
     ("r1_assemble_device_records_batch", C.c_int, [_ctx, C.POINTER(Params), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("r1_host_alloc", C.c_int, [C.c_size_t, C.POINTER(C.c_void_p)]),
@@ -141,6 +143,7 @@ SYMBOLS = [
     ("r1_multi_create", C.c_int, [C.c_int32, _i32p, C.POINTER(C.c_void_p)]),
     ("r1_multi_destroy", None, [C.c_void_p]),
     ("r1_multi_set_scene", C.c_int, [C.c_void_p, C.POINTER(CScene), C.POINTER(CCamera)]),
+    ("r1_multi_set_camera", C.c_int, [C.c_void_p, C.POINTER(CCamera)]),
     ("r1_multi_render", C.c_int, [C.c_void_p, C.POINTER(Params), _u8p, _u64p, _dblp]),
     ("r1_multi_render_async", C.c_int, [C.c_void_p, C.POINTER(Params), C.c_void_p]),
     ("r1_multi_render_batch_async", C.c_int, [C.c_void_p, C.POINTER(Params), C.c_int32, C.c_uint32, C.c_void_p]),
@@ -161,6 +164,8 @@ SYMBOLS = [
     ("r1_host_scene_destroy", None, [C.c_void_p]),
     ("r1_host_scene_spheres", C.POINTER(CScene), [C.c_void_p]),
     ("r1_host_scene_camera", C.POINTER(CCamera), [C.c_void_p]),
+    ("r1_host_scene_view", C.c_int, [C.c_void_p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p]),
+    ("r1_camera_look_at", C.c_int, [_f32p, _f32p, _f32p, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(CCamera)]),
     ("r1_bvh_describe", C.c_int, [C.POINTER(CScene), C.c_int32, C.POINTER(BvhInfo), _f32p, C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t]),
     ("r1_grid_describe", C.c_int, [C.POINTER(CScene), C.POINTER(GridInfo), C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t,
                                    C.POINTER(C.c_uint32), C.c_size_t]),
@@ -226,6 +231,16 @@ class Scene:
         return np.array(sum([list(getattr(c, f)) for f in ("origin", "lower_left", "horizontal", "vertical", "u", "v", "w")], [])
                         + [c.lens_radius], dtype=np.float32)
 
+    def view(self):
+        """r1_host_scene_view: the arguments the builder gave Camera::init, as a dict ready for camera_look_at (aspect: this
+        scene's width / height in fp32, rayweek1.cpp:564)."""
+        v = [(C.c_float * 3)() for _ in range(3)]
+        s = [C.c_float() for _ in range(3)]
+        _check(lib().r1_host_scene_view(self._h, v[0], v[1], v[2], C.byref(s[0]), C.byref(s[1]), C.byref(s[2])))
+        return {"lookfrom": np.array(list(v[0]), np.float32), "lookat": np.array(list(v[1]), np.float32), "vup": np.array(list(v[2]), np.float32),
+                "vfov": np.float32(s[0].value), "aspect": np.float32(self.width) / np.float32(self.height), "aperture": np.float32(s[1].value),
+                "focus_dist": np.float32(s[2].value)}
+
     def close(self):
         if self._h:
             lib().r1_host_scene_destroy(self._h)
@@ -236,6 +251,39 @@ class Scene:
             self.close()
         except Exception:
             pass
+
+
+def camera_look_at(lookfrom, lookat, vup, vfov, aspect, aperture, focus_dist):
+    """r1_camera_look_at: Camera::init (rayweek1.cpp:366-379) in the reference's arithmetic; returns a CCamera."""
+    a = [np.ascontiguousarray(x, np.float32) for x in (lookfrom, lookat, vup)]
+    if any(x.shape != (3,) for x in a):
+        raise R1Error(R1_EINVAL, "camera_look_at: lookfrom, lookat and vup are 3-vectors")
+    out = CCamera()
+    _check(lib().r1_camera_look_at(a[0].ctypes.data_as(_f32p), a[1].ctypes.data_as(_f32p), a[2].ctypes.data_as(_f32p), float(vfov), float(aspect),
+                                   float(aperture), float(focus_dist), C.byref(out)))
+    return out
+
+
+def orbit_cameras(scene, n, view=None):
+    """n cameras of `scene` turned about the vertical axis through lookat, camera f at angle 2 pi f / n — rayweek1_hip --orbit's
+    arithmetic (fp32; camera 0 is the scene's own camera bit for bit: cos 0 = 1, sin 0 = 0).  `view` overrides entries of scene.view()."""
+    v = scene.view()
+    v.update(view or {})
+    f32 = np.float32
+    out = []
+    for f in range(n):
+        a = 2.0 * np.pi * f / n
+        cs, sn = f32(np.cos(a)), f32(np.sin(a))
+        dx, dz = f32(v["lookfrom"][0] - v["lookat"][0]), f32(v["lookfrom"][2] - v["lookat"][2])
+        eye = np.array([v["lookat"][0] + f32(f32(dx * cs) + f32(dz * sn)), v["lookfrom"][1], v["lookat"][2] + f32(f32(dz * cs) - f32(dx * sn))], f32)
+        out.append(camera_look_at(eye, v["lookat"], v["vup"], v["vfov"], v["aspect"], v["aperture"], v["focus_dist"]))
+    return out
+
+
+def camera_to_array(cam):
+    """The 22 floats of a CCamera, in the order of Scene.camera_array()."""
+    return np.array(sum([list(getattr(cam, f)) for f in ("origin", "lower_left", "horizontal", "vertical", "u", "v", "w")], []) + [cam.lens_radius],
+                    dtype=np.float32)
 
 
 def create_small_scene(width=1280, height=720):
@@ -267,6 +315,10 @@ class Renderer:
 
     def set_scene_raw(self, cscene, ccamera):
         _check(lib().r1_set_scene(self._c, C.byref(cscene), C.byref(ccamera)))
+
+    def set_camera(self, ccamera):
+        """r1_set_camera: the camera alone (nothing is built, uploaded or waited for)."""
+        _check(lib().r1_set_camera(self._c, C.byref(ccamera)))
 
     def render(self, params):
         img = np.zeros((params.height, params.width, 3), np.uint8)
@@ -305,6 +357,13 @@ class Renderer:
         to leave them on the device) once the stream is idle."""
         _check(lib().r1_render_batch_async(self._c, C.byref(params), n_frames, seed_stride, C.c_void_p(host_frames.ptr) if host_frames else None,
                                            _stream_arg(stream_ptr)))
+
+    def render_path_async(self, params, cameras, host_frames, seed_stride=0, stream_ptr=None):
+        """r1_render_path_async: one frame per camera of `cameras` (a sequence of CCamera) in one launch; the records land in
+        `host_frames` (a HostFrames, or None to leave them on the device) once the stream is idle."""
+        arr = (CCamera * len(cameras))(*cameras)
+        _check(lib().r1_render_path_async(self._c, C.byref(params), len(cameras), seed_stride, arr, C.c_void_p(host_frames.ptr) if host_frames else None,
+                                          _stream_arg(stream_ptr)))
 
     def render_shard_device_batch(self, params, n_frames, d_records_ptr, seed_stride=0, stream_ptr=None):
         _check(lib().r1_render_shard_device_batch(self._c, C.byref(params), n_frames, seed_stride, C.c_void_p(d_records_ptr),
@@ -471,6 +530,9 @@ class MultiRenderer:
 
     def set_scene(self, scene):
         _check(lib().r1_multi_set_scene(self._m, scene.spheres, scene.camera))
+
+    def set_camera(self, ccamera):
+        _check(lib().r1_multi_set_camera(self._m, C.byref(ccamera)))
 
     def render(self, params):
         img = np.zeros((params.height, params.width, 3), np.uint8)

@@ -311,6 +311,24 @@ __global__ void r1_put6_kernel(uint32_t *dst, uint32_t a, uint32_t b, uint32_t c
     dst[0] = a, dst[1] = b, dst[2] = c, dst[3] = d, dst[4] = e, dst[5] = f;
 }
 
+// eight words: a camera path's R1PathArgs (the batch's numbers and the address of its camera table)
+__global__ void r1_put8_kernel(uint32_t *dst, uint32_t a, uint32_t b, uint32_t c, uint32_t d, uint32_t e, uint32_t f, uint32_t g, uint32_t h)
+{
+    dst[0] = a, dst[1] = b, dst[2] = c, dst[3] = d, dst[4] = e, dst[5] = f, dst[6] = g, dst[7] = h;
+}
+
+// a camera path's table (R1PathArgs::cameras), R1_PUT_CAMS cameras per launch, the values in the kernel arguments as above: thread t stores float4 t
+#define R1_PUT_CAMS 32
+struct R1CameraRows
+{
+    float4 row[R1_PUT_CAMS * R1_PATH_CAM_F4];
+};
+__global__ void r1_put_cameras_kernel(float4 *dst, const R1CameraRows rows, uint32_t n_f4)
+{
+    if (threadIdx.x < n_f4)
+        dst[threadIdx.x] = rows.row[threadIdx.x];
+}
+
 // ---- launchers (called from r1_capi.cpp) -----------------------------------------------------
 
 extern "C" hipError_t r1_launch_land_arm(uint32_t *tile_cnt, unsigned long long *frame_rays, uint32_t *frame_left, uint32_t n_frames, uint32_t n_local_tiles,
@@ -326,6 +344,32 @@ extern "C" hipError_t r1_launch_put6(void *dst, const uint32_t *w, hipStream_t s
 {
     hipLaunchKernelGGL(r1_put6_kernel, dim3(1), dim3(1), 0, stream, (uint32_t *)dst, w[0], w[1], w[2], w[3], w[4], w[5]);
     return hipGetLastError();
+}
+
+extern "C" hipError_t r1_launch_put8(void *dst, const uint32_t *w, hipStream_t stream)
+{
+    hipLaunchKernelGGL(r1_put8_kernel, dim3(1), dim3(1), 0, stream, (uint32_t *)dst, w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7]);
+    return hipGetLastError();
+}
+
+// cameras20: n rows of R1_PATH_CAM_F4 float4 (host memory, read here)
+extern "C" hipError_t r1_launch_put_cameras(void *dst, const float *cameras20, int n, hipStream_t stream)
+{
+    static_assert(sizeof(R1CameraRows) <= 3072, "the rows travel in the kernel arguments (4 KB at most)");
+    for (int f0 = 0; f0 < n; f0 += R1_PUT_CAMS)
+    {
+        const int m = n - f0 < R1_PUT_CAMS ? n - f0 : R1_PUT_CAMS;
+        R1CameraRows rows;
+        const float *src = cameras20 + (size_t)f0 * R1_PATH_CAM_F4 * 4;
+        for (int i = 0; i < R1_PUT_CAMS * R1_PATH_CAM_F4; ++i)
+            rows.row[i] = i < m * R1_PATH_CAM_F4 ? make_float4(src[4 * i], src[4 * i + 1], src[4 * i + 2], src[4 * i + 3]) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        hipLaunchKernelGGL(r1_put_cameras_kernel, dim3(1), dim3(R1_PUT_CAMS * R1_PATH_CAM_F4), 0, stream, (float4 *)dst + (size_t)f0 * R1_PATH_CAM_F4, rows,
+                           (uint32_t)(m * R1_PATH_CAM_F4));
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess)
+            return e;
+    }
+    return hipSuccess;
 }
 
 // The trace kernel's instantiations live in six translation units (tree / exhaustive sweep / uniform grid x small / big scenes); each exports one
@@ -359,7 +403,8 @@ extern "C" int r1_trace_mode(int variant, int big, int wanted)
 }
 
 // grid_lds: the grid kernels' 16-bit tables in LDS (small scenes; R1GridArgs::lds_bytes, which lives in device memory)
-extern "C" hipError_t r1_launch_trace(const R1TraceArgs *args, int variant, int big_in, int mode, int blocks, size_t grid_lds, hipStream_t stream)
+// path: a camera path (the MODE 5 builds: mode 0 with a batch block that ends in the camera table, R1PathArgs)
+extern "C" hipError_t r1_launch_trace(const R1TraceArgs *args, int variant, int big_in, int mode, int path, int blocks, size_t grid_lds, hipStream_t stream)
 {
     // dynamic LDS of the tree kernels: the traversal stack, one entry per inner node on a path, and (small scenes) the node table
     const bool big = big_in != 0; // 32-bit hit indices, attenuation stack in the global workspace
@@ -375,6 +420,8 @@ extern "C" hipError_t r1_launch_trace(const R1TraceArgs *args, int variant, int 
         return hipErrorInvalidValue;
     if (mode == 4 && !batch)
         return hipErrorInvalidValue; // (a pass reads its first sample through args->batch)
+    if (path && (!batch || mode != 0))
+        return hipErrorInvalidValue; // (batches only, and so variants 2, 4 and 7 only)
     if (variant == 3 && big)
         variant = 2; // (no diagnostic build of the LDS-tiled sweep)
     // the throughput builds of the product kernels sum their tiles themselves (R1_LAND): a launch through them says on how many XCDs
@@ -384,6 +431,8 @@ extern "C" hipError_t r1_launch_trace(const R1TraceArgs *args, int variant, int 
     // (the tree kernels look a primary ray's entry node up in args->bvh_entry whenever the tree has a root step: never launch them without)
     if (tree && R1_ENTRY_MODE(mode) && args->scene.bvh_root_leaf != 0u && args->bvh_entry == nullptr)
         return hipErrorInvalidValue;
+    if (path)
+        mode = 5; // (lands its tiles as mode 0 / 3 does; looks no entry node up)
     if (tree)
         return big ? r1_tu_tree_big_launch(args, variant, mode, batch, blocks, trav, stream) : r1_tu_tree_small_launch(args, variant, mode, batch, blocks, trav, stream);
     if (grid && args->grid == nullptr)

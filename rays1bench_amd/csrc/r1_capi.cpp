@@ -23,7 +23,7 @@
 #include "r1_device.h"
 #include "r1_grid.h"
 
-extern "C" hipError_t r1_launch_trace(const R1TraceArgs *args, int variant, int big, int mode, int blocks, size_t grid_lds, hipStream_t stream);
+extern "C" hipError_t r1_launch_trace(const R1TraceArgs *args, int variant, int big, int mode, int path, int blocks, size_t grid_lds, hipStream_t stream);
 extern "C" int r1_trace_mode(int variant, int big, int wanted); // 0 samples + one queue, 1 latency, 2 pixel, 4 pass: what is built for (variant, big)
 extern "C" hipError_t r1_launch_resolve(const R1ResolveArgs *args, int max_rows, hipStream_t stream);
 extern "C" hipError_t r1_launch_accum(const R1AccumArgs *args, hipStream_t stream);
@@ -31,6 +31,8 @@ extern "C" hipError_t r1_launch_wavefront(R1WaveArgs *w, int blocks, hipStream_t
 extern "C" hipError_t r1_launch_land_arm(uint32_t *tile_cnt, unsigned long long *frame_rays, uint32_t *frame_left, uint32_t n_frames, uint32_t n_local_tiles,
                                          int width, int height, int spp, int tile_w, int tile_h, int tiles_x, int shard, int num_shards, hipStream_t stream);
 extern "C" hipError_t r1_launch_put6(void *dst, const uint32_t *words, hipStream_t stream);
+extern "C" hipError_t r1_launch_put8(void *dst, const uint32_t *words, hipStream_t stream);
+extern "C" hipError_t r1_launch_put_cameras(void *dst, const float *cameras20, int n, hipStream_t stream); // n cameras of 20 floats each, host memory read during the call
 extern "C" hipError_t r1_launch_assemble(const void *blocks, void *rgb, int width, int height, int tile_w, int tile_h, int tiles_x, int num_shards,
                                          size_t shard_stride, int n_frames, size_t frame_in, size_t frame_out, size_t total_offset, long long total_out,
                                          int want_total, hipStream_t stream);
@@ -137,6 +139,10 @@ struct r1_context
     R1BatchArgs batch_args_last = {0, 0, {0, 0, 0}, 0};
     hipStream_t batch_args_stream = nullptr;
     int batch_args_slot = -1;
+    // camera paths: the launch's table of cameras (R1PathArgs::cameras), two halves taken in turn so that a launch still reading the
+    // previous table is not disturbed; written in stream order by launches whose values travel in their kernel arguments
+    DevBuf path_cams;
+    int path_cams_half = 0;
     // R1_LAND (tiles resolved inside the trace kernel): per-context state
     bool land_prev = false;      // the last launch through this context was a LAND launch
     int land_parity = 0;         // the set of queue heads that launch used
@@ -288,7 +294,7 @@ extern "C" void r1_destroy(r1_context *c)
     release(c->bvh_nodes), release(c->bvh_prims), release(c->bvh_ids), release(c->grid_tab), release(c->grid_out), release(c->grid_dev), release(c->grid_tab32), release(c->grid_dev32);
     release(c->wf_paths), release(c->wf_hits), release(c->wf_queue), release(c->wf_counts);
     release(c->bvh_wide), release(c->bvh_entry), release(c->land_spill), release(c->gstack), release(c->counters), release(c->samples), release(c->image), release(c->batch_rays);
-    release(c->wave_log), release(c->accum);
+    release(c->wave_log), release(c->accum), release(c->path_cams);
     if (c->host_word)
         (void)hipHostFree(c->host_word);
     for (hipEvent_t e : c->ring)
@@ -570,6 +576,20 @@ static int build_wide(const std::vector<float> &bin, int root_leaf, std::vector<
     return std::max(need, 1);
 }
 
+// what the kernels read of a camera (Camera::getRay, rayweek1.cpp:381-386, does not use w)
+static R1DeviceCamera device_camera(const r1_camera &cam)
+{
+    R1DeviceCamera d;
+    memcpy(d.origin, cam.origin, 12);
+    memcpy(d.lower_left, cam.lower_left, 12);
+    memcpy(d.horizontal, cam.horizontal, 12);
+    memcpy(d.vertical, cam.vertical, 12);
+    memcpy(d.u, cam.u, 12);
+    memcpy(d.v, cam.v, 12);
+    d.lens_radius = cam.lens_radius;
+    return d;
+}
+
 extern "C" int r1_set_scene(r1_context *c, const r1_scene *s, const r1_camera *cam)
 {
     if (!c || !s || !cam || !s->center_x || !s->center_y || !s->center_z || !s->radius_sq || !s->inv_radius || !s->mat_type ||
@@ -773,19 +793,34 @@ extern "C" int r1_set_scene(r1_context *c, const r1_scene *s, const r1_camera *c
     c->n_active = na;
     c->n_sweep = ns;
     c->n_padded_scene = s->count;
-    memcpy(c->cam.origin, cam->origin, 12);
-    memcpy(c->cam.lower_left, cam->lower_left, 12);
-    memcpy(c->cam.horizontal, cam->horizontal, 12);
-    memcpy(c->cam.vertical, cam->vertical, 12);
-    memcpy(c->cam.u, cam->u, 12);
-    memcpy(c->cam.v, cam->v, 12);
-    c->cam.lens_radius = cam->lens_radius;
+    c->cam = device_camera(*cam);
     for (int k = 0; k < 9; ++k)
         c->src_f32[k].assign(src[k], src[k] + s->count);
     c->src_mat.assign(s->mat_type, s->mat_type + s->count);
     c->src_cam = *cam;
     c->have_scene = true;
     c->default_variant = c->default_variant_tp = 4;
+    return R1_OK;
+}
+
+// The camera alone: it travels by value in every launch's arguments, so nothing is built, uploaded or waited for, and launches already
+// enqueued keep the camera they were enqueued with.
+extern "C" int r1_set_camera(r1_context *c, const r1_camera *cam)
+{
+    if (!c || !cam)
+    {
+        r1_set_error("r1_set_camera: %s is NULL", !c ? "ctx" : "camera");
+        return R1_EINVAL;
+    }
+    if (!c->have_scene)
+    {
+        r1_set_error("r1_set_camera: no scene set (call r1_set_scene first)");
+        return R1_EINVAL;
+    }
+    c->pass_valid = false; // (a progressive frame does not continue across a change of view, as across r1_set_scene)
+    c->cam = device_camera(*cam);
+    c->src_cam = *cam;       // r1_set_scene(same arrays, this camera) is still the shortcut
+    c->entry_valid = false;  // R1_ENTRY: the per-tile entry nodes belong to a camera
     return R1_OK;
 }
 
@@ -872,6 +907,7 @@ struct Batch
     int n_frames = 1;
     uint32_t seed_stride = 0;
     size_t out_stride = 0, rays_offset = 0;
+    const r1_camera *cameras = nullptr; // a camera path: [n_frames], host memory; null: every frame through the context's camera
 };
 
 // ---- per-tile entry nodes for primary rays (R1_ENTRY) ---------------------------------------------------------
@@ -1227,7 +1263,39 @@ static int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int blo
     a.shard = p->shard, a.num_shards = p->num_shards;
     a.n_local_tiles = c->n_local_tiles;
     a.batch = nullptr;
-    if (batch && n_frames > 1)
+    const bool path = batch && batch->cameras && n_frames > 1; // (a path of one frame: the single-frame kernel with that camera by value)
+    if (batch && batch->cameras && n_frames == 1)
+        a.cam = device_camera(batch->cameras[0]);
+    if (path)
+    {
+        // the frames' cameras: a table in device memory, written in stream order; then the batch's numbers and the table's address in a
+        // slot of their own (a batch that follows takes a new slot: its numbers may equal these, its block has no table)
+        const size_t half = ((size_t)n_frames * R1_PATH_CAM_F4 * 16 + 255) & ~(size_t)255;
+        if ((rc = ensure(c->path_cams, 2 * half))) // (growing frees the old table: hipFree waits for the launches that read it)
+            return rc;
+        c->path_cams_half ^= 1;
+        char *const table = (char *)c->path_cams.p + (c->path_cams_half ? c->path_cams.cap / 2 : 0);
+        std::vector<float> rows((size_t)n_frames * R1_PATH_CAM_F4 * 4, 0.0f);
+        for (int f = 0; f < n_frames; ++f)
+        {
+            const R1DeviceCamera d = device_camera(batch->cameras[f]);
+            static_assert(sizeof(R1DeviceCamera) == 19 * 4 && R1_PATH_CAM_F4 * 4 >= 19, "a table row holds an R1DeviceCamera");
+            memcpy(&rows[(size_t)f * R1_PATH_CAM_F4 * 4], &d, sizeof(d));
+        }
+        R1_HIP(r1_launch_put_cameras(table, rows.data(), n_frames, st));
+        R1PathArgs pa;
+        memset(&pa, 0, sizeof(pa));
+        pa.batch.n_frames = (uint32_t)n_frames, pa.batch.seed_stride = batch->seed_stride;
+        pa.batch.div_tiles = make_div(c->n_local_tiles ? c->n_local_tiles : 1u), pa.batch.n_local_tiles = c->n_local_tiles;
+        pa.cameras = (const float *)table;
+        static_assert(sizeof(R1PathArgs) == 32 && __builtin_offsetof(R1PathArgs, cameras) == 24, "r1_launch_put8 writes the eight words of R1PathArgs into a 32-byte slot");
+        c->batch_args_slot = (c->batch_args_slot + 1) & 7;
+        memset(&c->batch_args_last, 0, sizeof(c->batch_args_last));
+        c->batch_args_stream = st;
+        R1_HIP(r1_launch_put8((char *)c->counters.p + R1_COUNTER_BYTES + 64 + 32 * c->batch_args_slot, (const uint32_t *)&pa, st));
+        a.batch = (const R1BatchArgs *)((char *)c->counters.p + R1_COUNTER_BYTES + 64 + 32 * c->batch_args_slot);
+    }
+    else if (batch && n_frames > 1)
     {
         // the batch's numbers, in the context's counter allocation behind the published ray count (stream-ordered upload:
         // the previous launch through this context has finished reading its copy by the time this one is written)
@@ -1275,15 +1343,21 @@ static int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int blo
     {
         // per-tile entry nodes of the primary rays (compute_entries): once per (scene, camera, tiling, frames of the launch, reference form)
         const int form = big_scene_ ? 2 : 1;
+        const bool own_cam = batch && batch->cameras; // a camera path: the one-frame form's table is made for its camera and for this launch only
+        if (own_cam)                                   // (the MODE 5 kernels look no entry up: their frames have a camera each)
+            c->entry_valid = false;
         if (!c->entry_valid || c->entry_frames != n_frames * 4 + form || !same_tiling(c->entry_key, *p))
         {
             std::vector<uint32_t> tab;
+            const R1DeviceCamera keep = c->cam;
+            c->cam = a.cam;
             compute_entries(c, p, n_frames, !big_scene_, tab);
+            c->cam = keep;
             R1_HIP(hipDeviceSynchronize()); // (launches still reading the previous table: a change of tiling is rare)
             if ((rc = ensure(c->bvh_entry, tab.size() * 4)))
                 return rc;
             R1_HIP(hipMemcpy(c->bvh_entry.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
-            c->entry_valid = true, c->entry_frames = n_frames * 4 + form, c->entry_key = *p;
+            c->entry_valid = !own_cam, c->entry_frames = n_frames * 4 + form, c->entry_key = *p;
         }
         a.bvh_entry = (const uint32_t *)c->bvh_entry.p;
         static const int entry_lds_env = (int)r1_knob("R1_ENTRY_LDS", 1); // tuning: 0 = the table stays in global memory
@@ -1520,7 +1594,7 @@ static int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int blo
         R1_HIP(hipMemsetAsync(d_rays, 0, 8, st));
     R1_HIP(hipEventRecord(e0, st));
     if (c->total_samples && variant != 6)
-        R1_HIP(r1_launch_trace(&a, variant, big, mode, (int)blocks, grid && !big ? c->grid_args.lds_bytes : 0u, st));
+        R1_HIP(r1_launch_trace(&a, variant, big, mode, path ? 1 : 0, (int)blocks, grid && !big ? c->grid_args.lds_bytes : 0u, st));
     if (c->total_samples && variant == 6)
     {
         // wavefront variant: path state, per-level queues and the attenuation stack live in HBM
@@ -1910,6 +1984,42 @@ extern "C" int r1_render_batch_async(r1_context *c, const r1_params *p, int32_t 
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
     Batch b;
     b.n_frames = n_frames, b.seed_stride = seed_stride, b.out_stride = frame, b.rays_offset = frame - 8;
+    Landing land_to;
+    if (host_frames && ((uintptr_t)host_frames & 7u) == 0)
+        land_to.out = mapped_host(host_frames);
+    if ((rc = enqueue_frame(c, p, c->image.p, 0, nullptr, st, true, &b, &land_to)))
+        return rc;
+    if (host_frames && !land_to.used) // (NULL: the frames stay in the context's device buffer — a measurement aid)
+        R1_HIP(hipMemcpyAsync(host_frames, c->image.p, frame * (size_t)n_frames, hipMemcpyDeviceToHost, st));
+    return R1_OK;
+}
+
+// A camera path: r1_render_batch_async with cameras[f] in place of the context's camera for frame f (the MODE 5 kernels; one frame: the
+// single-frame kernel with cameras[0] by value).  The context's own camera is not touched.
+extern "C" int r1_render_path_async(r1_context *c, const r1_params *p, int32_t n_frames, uint32_t seed_stride, const r1_camera *cameras, void *host_frames,
+                                    void *hip_stream)
+{
+    if (!c || !p || !cameras || n_frames < 1)
+    {
+        r1_set_error("r1_render_path_async: bad argument (%s)", !c ? "ctx is NULL" : !p ? "params is NULL" : !cameras ? "cameras is NULL" : "n_frames < 1");
+        return R1_EINVAL;
+    }
+    int rc = r1_params_check(p);
+    if (rc)
+        return rc;
+    if (p->num_shards != 1)
+    {
+        r1_set_error("r1_render_path_async renders whole frames (num_shards == 1)");
+        return R1_EINVAL;
+    }
+    R1_HIP(hipSetDevice(c->device));
+    const size_t frame = r1_frame_record_bytes(p);
+    if ((rc = ensure(c->image, frame * (size_t)n_frames)))
+        return rc;
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    Batch b;
+    b.n_frames = n_frames, b.seed_stride = seed_stride, b.out_stride = frame, b.rays_offset = frame - 8;
+    b.cameras = cameras;
     Landing land_to;
     if (host_frames && ((uintptr_t)host_frames & 7u) == 0)
         land_to.out = mapped_host(host_frames);

@@ -48,6 +48,31 @@ inline void store(float *dst, V3 v)
     dst[2] = v.z;
 }
 
+// Camera::init, rayweek1.cpp:366-379 (r1_camera_look_at and the scene builders)
+inline void look_at(V3 lookfrom, V3 lookat, V3 vup, float vfov, float aspect, float aperture, float focus_dist, r1_camera &cam)
+{
+    cam.lens_radius = aperture / 2;
+    // The reference calls tanf(theta / 2).  Its value for vfov = 60 depends on who evaluates
+    // it: g++ folds the call at compile time (MPFR, correctly rounded: 0x1.279a74p-1, which
+    // is what the fixture binary and any -O2/-O3 build of the reference contain) while
+    // glibc's run-time tanf returns 0x1.279a76p-1.  Evaluating in double and rounding once
+    // gives the correctly rounded value on every toolchain.
+    float theta = vfov * (float)M_PI / 180;
+    float half_height = (float)tan((double)(theta / 2));
+    float half_width = aspect * half_height;
+    V3 w = unit(sub(lookfrom, lookat));
+    V3 u = unit(cross(vup, w));
+    V3 v = cross(w, u);
+    V3 ll = sub(sub(sub(lookfrom, scale(u, half_width * focus_dist)), scale(v, half_height * focus_dist)), scale(w, focus_dist));
+    store(cam.origin, lookfrom);
+    store(cam.lower_left, ll);
+    store(cam.horizontal, scale(u, 2 * half_width * focus_dist));
+    store(cam.vertical, scale(v, 2 * half_height * focus_dist));
+    store(cam.u, u);
+    store(cam.v, v);
+    store(cam.w, w);
+}
+
 } // namespace
 
 struct r1_host_scene
@@ -84,29 +109,15 @@ struct r1_host_scene
             add({999999999.f, 999999999.f, 999999999.f}, 0, R1_MAT_NONE, {0, 0, 0}, 0);
     }
 
-    // Camera::init, rayweek1.cpp:366-379
+    // the arguments the builder gave Camera::init (r1_host_scene_view)
+    V3 view_from = {0, 0, 0}, view_at = {0, 0, 0}, view_up = {0, 1, 0};
+    float view_vfov = 0, view_aperture = 0, view_focus = 0;
+
     void camera_init(V3 lookfrom, V3 lookat, V3 vup, float vfov, float aspect, float aperture, float focus_dist)
     {
-        cam.lens_radius = aperture / 2;
-        // The reference calls tanf(theta / 2).  Its value for vfov = 60 depends on who evaluates
-        // it: g++ folds the call at compile time (MPFR, correctly rounded: 0x1.279a74p-1, which
-        // is what the fixture binary and any -O2/-O3 build of the reference contain) while
-        // glibc's run-time tanf returns 0x1.279a76p-1.  Evaluating in double and rounding once
-        // gives the correctly rounded value on every toolchain.
-        float theta = vfov * (float)M_PI / 180;
-        float half_height = (float)tan((double)(theta / 2));
-        float half_width = aspect * half_height;
-        V3 w = unit(sub(lookfrom, lookat));
-        V3 u = unit(cross(vup, w));
-        V3 v = cross(w, u);
-        V3 ll = sub(sub(sub(lookfrom, scale(u, half_width * focus_dist)), scale(v, half_height * focus_dist)), scale(w, focus_dist));
-        store(cam.origin, lookfrom);
-        store(cam.lower_left, ll);
-        store(cam.horizontal, scale(u, 2 * half_width * focus_dist));
-        store(cam.vertical, scale(v, 2 * half_height * focus_dist));
-        store(cam.u, u);
-        store(cam.v, v);
-        store(cam.w, w);
+        view_from = lookfrom, view_at = lookat, view_up = vup;
+        view_vfov = vfov, view_aperture = aperture, view_focus = focus_dist;
+        look_at(lookfrom, lookat, vup, vfov, aspect, aperture, focus_dist, cam);
     }
 
     void finish()
@@ -252,6 +263,35 @@ extern "C" int r1_host_scene_create(int kind, int32_t width, int32_t height, int
 extern "C" void r1_host_scene_destroy(r1_host_scene *hs) { delete hs; }
 extern "C" const r1_scene *r1_host_scene_spheres(const r1_host_scene *hs) { return hs ? &hs->view : nullptr; }
 extern "C" const r1_camera *r1_host_scene_camera(const r1_host_scene *hs) { return hs ? &hs->cam : nullptr; }
+
+
+extern "C" int r1_camera_look_at(const float lookfrom[3], const float lookat[3], const float vup[3], float vfov_degrees, float aspect, float aperture,
+                                 float focus_dist, r1_camera *out)
+{
+    const char *bad = !lookfrom ? "lookfrom" : !lookat ? "lookat" : !vup ? "vup" : !out ? "out" : nullptr;
+    if (bad)
+    {
+        r1_set_error("r1_camera_look_at: %s is NULL", bad);
+        return R1_EINVAL;
+    }
+    look_at({lookfrom[0], lookfrom[1], lookfrom[2]}, {lookat[0], lookat[1], lookat[2]}, {vup[0], vup[1], vup[2]}, vfov_degrees, aspect, aperture, focus_dist, *out);
+    return R1_OK;
+}
+
+extern "C" int r1_host_scene_view(const r1_host_scene *hs, float lookfrom[3], float lookat[3], float vup[3], float *vfov_degrees, float *aperture, float *focus_dist)
+{
+    const char *bad = !hs ? "scene" : !lookfrom ? "lookfrom" : !lookat ? "lookat" : !vup ? "vup" : !vfov_degrees ? "vfov_degrees" : !aperture ? "aperture" : !focus_dist ? "focus_dist" : nullptr;
+    if (bad)
+    {
+        r1_set_error("r1_host_scene_view: %s is NULL", bad);
+        return R1_EINVAL;
+    }
+    store(lookfrom, hs->view_from);
+    store(lookat, hs->view_at);
+    store(vup, hs->view_up);
+    *vfov_degrees = hs->view_vfov, *aperture = hs->view_aperture, *focus_dist = hs->view_focus;
+    return R1_OK;
+}
 
 // ---- tiles and shards -----------------------------------------------------------------
 

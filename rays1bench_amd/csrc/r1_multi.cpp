@@ -235,6 +235,23 @@ extern "C" int r1_multi_set_scene(r1_multi *m, const r1_scene *scene, const r1_c
     return R1_OK;
 }
 
+// r1_set_camera over the object's contexts (a context without a scene refuses; the contexts before it keep the new camera)
+extern "C" int r1_multi_set_camera(r1_multi *m, const r1_camera *camera)
+{
+    if (!m || !camera)
+    {
+        r1_set_error("r1_multi_set_camera: %s is NULL", !m ? "multi" : "camera");
+        return R1_EINVAL;
+    }
+    for (int i = 0; i < m->n; ++i)
+    {
+        const int rc = r1_set_camera(m->ctx[i], camera);
+        if (rc != R1_OK)
+            return rc;
+    }
+    return R1_OK;
+}
+
 // device buffers of one r1_multi: every device's record + gathered records, device 0's image (or frame record)
 static int multi_buffers(r1_multi *m, const size_t record, const size_t rgb_bytes)
 {

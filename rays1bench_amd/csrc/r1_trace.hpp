@@ -1194,7 +1194,8 @@ __device__ __forceinline__ uint32_t fastdiv(uint32_t n, const R1FastDiv dv)
 }
 
 // seeds + primary ray of sample s of pixel (x, y) (rayweek1.cpp:759-760)
-__device__ __forceinline__ void start_ray(const R1TraceArgs &A, Path &p, const int x, const int y, const uint32_t s, const uint32_t seed)
+// C: the camera — the launch's own (A.cam), or the frame's of a camera path (start_sample)
+__device__ __forceinline__ void start_ray(const R1TraceArgs &A, const R1DeviceCamera &C, Path &p, const int x, const int y, const uint32_t s, const uint32_t seed)
 {
     const r1_sample_seed sd = r1_seed_sample(seed, (uint32_t)(y * A.width + x), s);
     p.s_scalar = sd.scalar;
@@ -1220,12 +1221,12 @@ __device__ __forceinline__ void start_ray(const R1TraceArgs &A, Path &p, const i
     } while (vdot(dk, dk) >= 1.0f);
 
     // Camera::getRay (rayweek1.cpp:381-386)
-    const V3 rd = vscale(dk, A.cam.lens_radius);
-    const V3 offset = vadd(vscale(ld3(A.cam.u), rd.x), vscale(ld3(A.cam.v), rd.y));
-    const V3 org = ld3(A.cam.origin);
+    const V3 rd = vscale(dk, C.lens_radius);
+    const V3 offset = vadd(vscale(ld3(C.u), rd.x), vscale(ld3(C.v), rd.y));
+    const V3 org = ld3(C.origin);
     p.o = vadd(org, offset);
     const V3 dir =
-        vsub(vsub(vadd(vadd(ld3(A.cam.lower_left), vscale(ld3(A.cam.horizontal), u)), vscale(ld3(A.cam.vertical), v)), org), offset);
+        vsub(vsub(vadd(vadd(ld3(C.lower_left), vscale(ld3(C.horizontal), u)), vscale(ld3(C.vertical), v)), org), offset);
     p.d = vunit(dir);
 }
 
@@ -1246,14 +1247,21 @@ __device__ __forceinline__ bool tile_pixel(const R1TraceArgs &A, const uint32_t 
 // Returns false for a void slot (pixel of an edge tile that lies outside the image).
 // PASS (progressive passes, MODE 4): s is the pass-local sample index — the record's place — and the sample is seeded with its global
 // index s + first_sample, which the pass's R1PassArgs hold behind A.batch.
-template <bool BATCH = false, bool PASS = false>
+// PATH (camera paths, MODE 5): a batch whose frame f is seen through camera f of the table behind the batch's numbers (R1PathArgs).  The
+// queue is frame-major and a wave's chunk may straddle frames, so f is a per-lane value and every lane loads its frame's camera itself:
+// five vector loads where start_ray needs them, dead before the walk — the builds keep the VGPR count of their MODE 3 siblings
+// (tools/kernel_meta.py).  The other form — a loop over the wave's distinct f, the camera through scalar loads, the lanes of that frame
+// masked in — is not kept: hipcc proves `frame == f0` inside the masked arm, addresses the camera by the lane's own f again and hoists
+// start_ray out of the loop, i.e. emits these very loads behind a loop that only builds the address.
+template <bool BATCH = false, bool PASS = false, bool PATH = false>
 __device__ __forceinline__ bool start_sample(const R1TraceArgs &A, Path &p, uint32_t k)
 {
+    static_assert(!PATH || BATCH, "a camera path is a batch");
     const uint32_t j = fastdiv(k, A.div_full); // padded tile, frame-major over the frames of the launch
     const uint32_t r = k - j * A.full;
     const uint32_t pix = fastdiv(r, A.div_spp);
     const uint32_t s = r - pix * (uint32_t)A.spp;
-    uint32_t jl = j, seed = A.seed;
+    uint32_t jl = j, seed = A.seed, frame = 0;
     if (BATCH) // (its own build of the kernel, MODE 3: the single-frame kernels stay as they were, to the register)
     {
         typedef const uint32_t __attribute__((address_space(4))) *cu32_ptr;
@@ -1263,6 +1271,7 @@ __device__ __forceinline__ bool start_sample(const R1TraceArgs &A, Path &p, uint
         const uint32_t f = fastdiv(j, dv);
         jl = j - f * b[5];
         seed += f * b[1];
+        frame = f;
     }
     int x, y;
     if (!tile_pixel(A, jl, pix, x, y))
@@ -1276,7 +1285,21 @@ __device__ __forceinline__ bool start_sample(const R1TraceArgs &A, Path &p, uint
         typedef const uint32_t __attribute__((address_space(4))) *cu32_ptr;
         s_global += ((cu32_ptr)A.batch)[0]; // R1PassArgs::first_sample
     }
-    start_ray(A, p, x, y, s_global, seed);
+    if (PATH)
+    {
+        // R1PathArgs::cameras: [n_frames] cameras of R1_PATH_CAM_F4 float4 each, in R1DeviceCamera's order
+        typedef const f4 __attribute__((address_space(1))) *gf4_ptr;
+        const gf4_ptr tab = *(const __attribute__((address_space(4))) gf4_ptr *)((const __attribute__((address_space(4))) char *)A.batch + __builtin_offsetof(R1PathArgs, cameras));
+        const gf4_ptr t = tab + (size_t)frame * R1_PATH_CAM_F4;
+        typedef float f3 __attribute__((ext_vector_type(3)));
+        typedef const f3 __attribute__((address_space(1))) *gf3_ptr;
+        const f4 c0 = t[0], c1 = t[1], c2 = t[2], c3 = t[3];
+        const f3 c4 = *(gf3_ptr)(t + 4); // (the row's 20th word is padding: a loaded register nobody reads is the first one hipcc reuses, and it waits for all five loads to do so)
+        const R1DeviceCamera C = {{c0.x, c0.y, c0.z}, {c0.w, c1.x, c1.y}, {c1.z, c1.w, c2.x}, {c2.y, c2.z, c2.w}, {c3.x, c3.y, c3.z}, {c3.w, c4.x, c4.y}, c4.z};
+        start_ray(A, C, p, x, y, s_global, seed);
+        return true;
+    }
+    start_ray(A, A.cam, p, x, y, s_global, seed);
     return true;
 }
 
@@ -1764,7 +1787,7 @@ struct TraceWaves
                             //  LDS stack less — it spills and is no faster: profiles/r04/retune_after_fresh_args.txt)
 #endif
     // (the grid's PIXEL-mode build — big-scene kernel only — is built for four waves: at eight it keeps a scratch slot for its SGPR spills)
-    static constexpr int value = STATS ? 1 : (VARIANT == 7 && MODE == 2) ? 4 : ((VARIANT == 4 || VARIANT == 7) ? (BIG ? 8 : ((MODE == 0 || MODE == 3) ? R1_TREE_WAVES_TP : R1_TREE_WAVES_LAT)) : (VARIANT == 2 && !BIG ? 5 : 1));
+    static constexpr int value = STATS ? 1 : (VARIANT == 7 && MODE == 2) ? 4 : ((VARIANT == 4 || VARIANT == 7) ? (BIG ? 8 : ((MODE == 0 || MODE == 3 || MODE == 5) ? R1_TREE_WAVES_TP : R1_TREE_WAVES_LAT)) : (VARIANT == 2 && !BIG ? 5 : 1));
 };
 
 // MODE 1 = LAT = latency-mode build (the synchronous entry points: one frame, full grid): sub-queues and
@@ -1772,6 +1795,7 @@ struct TraceWaves
 // long-lived waves per frame) leaves them out: they cost it registers and bring it nothing.
 // MODE 0 = frames in flight (the throughput entry point): samples in one guided queue, few long-lived waves per frame.
 // MODE 2 = PIXEL mode (the throughput entry point after r1_set_pixel_mode; see struct Pixel): the queue holds pixels.
+// MODE 5 = a camera path (r1_render_path_async): MODE 3 with one camera per frame, read from a device table where a sample starts.
 // MODE 4 = a progressive pass (r1_render_pass): small scenes as MODE 1, big scenes as MODE 0 without landing; the records take the pass-local
 // sample index, the seeds the global one (start_sample), and r1_accum_kernel sums them into the frame's accumulator.
 // (the body of the kernel; r1_trace_kernel and, for the uniform grid, r1_grid_kernel below are its __global__ instances; r1_pass_kernel the MODE 4 ones)
@@ -1779,7 +1803,8 @@ template <int VARIANT, bool STATS, bool BIG, int MODE>
 __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
 {
     constexpr bool PASS = MODE == 4;
-    constexpr bool LAT = MODE == 1 || (PASS && !BIG), PIX = MODE == 2, BATCH = MODE == 3; // MODE 3 = MODE 0 whose queue spans the frames of a batch
+    constexpr bool CPATH = MODE == 5; // MODE 5 = MODE 3 whose frames each have a camera of their own (start_sample)
+    constexpr bool LAT = MODE == 1 || (PASS && !BIG), PIX = MODE == 2, BATCH = MODE == 3 || CPATH; // MODE 3 = MODE 0 whose queue spans the frames of a batch
     // tiles resolved inside the kernel: the throughput builds of the tree kernels (frames in flight, MODE 0 / 3); a
     // launch through them is a landing launch (r1_launch_trace checks).  The synchronous frame keeps the resolve launch (measured
     // slower with its tiles summed at wave exit, R1_LAND_SYNC), and so do the exhaustive sweep's kernels.
@@ -1813,7 +1838,7 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
         log_start = __builtin_amdgcn_s_memrealtime();
     }
     // words of the attenuation stack in LDS (the rest of a deep path's entries live in the global workspace)
-    constexpr int LW = (VARIANT == 4 || VARIANT == 7) ? (((MODE == 0 || MODE == 3) && !STATS) ? R1_STACK_LDS_WORDS_TP : R1_STACK_LDS_WORDS) : R1_STACK_WORDS;
+    constexpr int LW = (VARIANT == 4 || VARIANT == 7) ? (((MODE == 0 || MODE == 3 || MODE == 5) && !STATS) ? R1_STACK_LDS_WORDS_TP : R1_STACK_LDS_WORDS) : R1_STACK_WORDS;
     __shared__ uint32_t s_stack[BIG ? 1 : LW * R1_BLOCK];
     __shared__ uint32_t s_cand[VARIANT == 2 ? (BIG ? R1_CAND_CAP : R1_BIT_WORDS) * R1_BLOCK : 1];
     __shared__ IDX s_pairs[VARIANT == 2 ? (R1_BLOCK / 64) * PairBits<IDX>::cap : 1];
@@ -1895,7 +1920,7 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
 #ifndef R1_SPARE_MIN
 #define R1_SPARE_MIN 40u
 #endif
-    constexpr bool SPARE = R1_SPARE && !BIG && (VARIANT == 4 || VARIANT == 2 || VARIANT == 7) && (MODE == 0 || MODE == 3); // (big scenes: the registers buy an eighth wave instead)
+    constexpr bool SPARE = R1_SPARE && !BIG && (VARIANT == 4 || VARIANT == 2 || VARIANT == 7) && (MODE == 0 || MODE == 3 || MODE == 5); // (big scenes: the registers buy an eighth wave instead)
     Path spare = p;
     bool has_spare = false;
 
@@ -1929,7 +1954,7 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
         if (PIX && !alive && px.s < (uint32_t)A.spp)
         {
             // the next sample of the pixel in hand: no queue, no index arithmetic
-            start_ray(A, p, (int)(px.xy & 0xFFFFu), (int)(px.xy >> 16), px.s, A.seed);
+            start_ray(A, A.cam, p, (int)(px.xy & 0xFFFFu), (int)(px.xy >> 16), px.s, A.seed);
             alive = true;
             if (VARIANT == 4)
                 trav_start(tv);
@@ -2057,7 +2082,7 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
             if (SPARE)
             {
                 if (!has_spare && rank < avail)
-                    has_spare = start_sample<BATCH, PASS>(FA, spare, q_next + rank); // false: void slot, ask again
+                    has_spare = start_sample<BATCH, PASS, CPATH>(FA, spare, q_next + rank); // false: void slot, ask again
             }
             else if (!alive && rank < avail)
             {
@@ -2065,10 +2090,10 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
                 {
                     alive = pixel_take(A, px, q_next + rank); // false: void slot, ask again
                     if (alive)
-                        start_ray(A, p, (int)(px.xy & 0xFFFFu), (int)(px.xy >> 16), 0u, A.seed);
+                        start_ray(A, A.cam, p, (int)(px.xy & 0xFFFFu), (int)(px.xy >> 16), 0u, A.seed);
                 }
                 else
-                    alive = start_sample<BATCH, PASS>(FA, p, q_next + rank); // false: void slot, ask again
+                    alive = start_sample<BATCH, PASS, CPATH>(FA, p, q_next + rank); // false: void slot, ask again
                 if (VARIANT == 4 && alive)
                     trav_start(tv);
             }
@@ -2309,6 +2334,13 @@ template <int VARIANT, bool BIG>
 __global__ void __launch_bounds__(R1_BLOCK, (TraceWaves<VARIANT, false, BIG, 4>::value)) r1_pass_kernel(const R1TraceArgs A)
 {
     r1_trace_body<VARIANT, false, BIG, 4>(A);
+}
+
+// Camera paths (MODE 5): the same body under a name of its own, for the families that have a batch build: tree (4), grouped sweep (2), grid (7)
+template <int VARIANT, bool BIG>
+__global__ void __launch_bounds__(R1_BLOCK, (TraceWaves<VARIANT, false, BIG, 5>::value)) r1_path_kernel(const R1TraceArgs A)
+{
+    r1_trace_body<VARIANT, false, BIG, 5>(A);
 }
 
 #endif // R1_TRACE_HPP

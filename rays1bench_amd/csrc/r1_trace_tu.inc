@@ -11,7 +11,7 @@
 #define R1_CAT2(a, b, c) a##b##c
 #define R1_CAT(a, b, c) R1_CAT2(a, b, c)
 
-// S = diagnostic build, M = mode (0 frames in flight, 1 latency, 2 pixel, 3 frame batches; 4 progressive passes: R1_TU_PASS below); calls X(V, S, M)
+// S = diagnostic build, M = mode (0 frames in flight, 1 latency, 2 pixel, 3 frame batches; 4 progressive passes: R1_TU_PASS below; 5 camera paths: R1_TU_PATH_VARIANT); calls X(V, S, M)
 // for the instance that is built
 #if R1_TU_GRID
 // (PIXEL mode: the big-scene build only, r1_capi.cpp; r1_launch_trace refuses the small one)
@@ -83,11 +83,26 @@
         X(2)
 #endif
 
+// camera paths (MODE 5, r1_render_path_async): r1_path_kernel<V, big> for the family's batch variant
+#if R1_TU_GRID
+#define R1_TU_PATH_VARIANT 7
+#elif R1_TU_TREE
+#define R1_TU_PATH_VARIANT 4
+#else
+#define R1_TU_PATH_VARIANT 2
+#endif
+
 extern "C" hipError_t R1_CAT(r1_tu_, R1_TU_NAME, _launch)(const R1TraceArgs *args, int variant, int mode, int batch, int blocks, size_t dyn_lds, hipStream_t stream)
 {
 #define R1_GO(V, S, M) hipLaunchKernelGGL((R1_TU_KERNEL(V, S, M)), dim3(blocks), dim3(R1_BLOCK), dyn_lds, stream, *args)
 #define R1_GO_PASS(V) hipLaunchKernelGGL((r1_pass_kernel<V, R1_TU_BIG>), dim3(blocks), dim3(R1_BLOCK), dyn_lds, stream, *args);
-    if (mode == 4)
+    if (mode == 5)
+    {
+        if (variant != R1_TU_PATH_VARIANT || !batch)
+            return hipErrorInvalidValue;
+        hipLaunchKernelGGL((r1_path_kernel<R1_TU_PATH_VARIANT, R1_TU_BIG>), dim3(blocks), dim3(R1_BLOCK), dyn_lds, stream, *args);
+    }
+    else if (mode == 4)
     {
         R1_TU_PASS(R1_GO_PASS)
     }

@@ -27,6 +27,7 @@
 // (README.md:38-84).  Named backends of this program only — never a fallback: with --backend hip and no
 // usable device the program exits with an error.
 
+#include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -66,6 +67,7 @@ static int g_devices = 1;
 static int g_backend = 0; // 0 hip, 1 cpu-step1, 12 cpu-step12
 static int g_pipeline = 0; // --pipeline FRAMES: after the benchmark() runs, FRAMES frames per scene with several in flight (r1_render_async)
 static int g_inflight = 20;
+static int g_orbit = 0;    // --orbit FRAMES: after the benchmark() runs, FRAMES frames per scene with the camera turned about the vertical axis through lookat (r1_render_path_async)
 static int g_passes = 0;   // --passes K: every frame in K progressive passes (r1_render_pass); 0 = one r1_render
 int r1cpu_step12_render(const r1_scene *scene, const r1_camera *cam, int width, int height, int spp, int max_bounces, uint8_t *rgb,
                         uint64_t *num_rays); // r1_cpu_backends.cpp
@@ -411,10 +413,118 @@ static int pipelined(const char *scene_name, int kind, int frames)
     return rc == R1_OK ? 0 : 1;
 }
 
+// ---- a moving camera (no reference counterpart: its camera is fixed when the scene is built) -------------------------
+// --orbit FRAMES: the scene's own camera (r1_host_scene_view) turned about the vertical axis through lookat, frame f at angle 2 pi f / FRAMES
+// (frame 0 is the scene's camera bit for bit: cos 0 = 1, sin 0 = 0), every frame with benchmark()'s seed.  The frames are rendered as camera-path
+// batches — consecutive frames of the orbit in ONE launch, each through its own camera (r1_render_path_async) — over --inflight contexts, the
+// records landing in page-locked memory.  Prints one line per scene; with -w writes frame 0 and the middle frame.
+static int orbit(const char *scene_name, int kind, int frames, bool write_tga)
+{
+    r1_host_scene *hs = nullptr;
+    if (r1_host_scene_create(kind, g_screen_w, g_screen_h, 0, 0, &hs) != R1_OK)
+        return 1;
+    r1_params p;
+    memset(&p, 0, sizeof(p));
+    p.width = g_screen_w, p.height = g_screen_h, p.spp = g_spp, p.max_bounces = g_max_bounces, p.seed = g_seed;
+    p.tile_w = 32, p.tile_h = 32, p.shard = 0, p.num_shards = 1, p.variant = g_variant;
+    float from[3], at[3], up[3], vfov = 0, aperture = 0, focus = 0;
+    int rc = r1_host_scene_view(hs, from, at, up, &vfov, &aperture, &focus);
+    std::vector<r1_camera> cams((size_t)frames);
+    for (int f = 0; f < frames && rc == R1_OK; ++f)
+    {
+        const double a = 2.0 * M_PI * (double)f / (double)frames;
+        const float cs = (float)cos(a), sn = (float)sin(a);
+        const float dx = from[0] - at[0], dz = from[2] - at[2];
+        const float eye[3] = {at[0] + (dx * cs + dz * sn), from[1], at[2] + (dz * cs - dx * sn)};
+        rc = r1_camera_look_at(eye, at, up, vfov, (float)g_screen_w / (float)g_screen_h, aperture, focus, &cams[(size_t)f]);
+    }
+    // frames per launch: the orbit dealt evenly to the contexts, at most 16 (all frames of a launch are delivered together) and within the
+    // 2^31 padded sample slots of a launch
+    const int k = g_inflight < frames ? g_inflight : frames;
+    const uint64_t slots = (uint64_t)((g_screen_w + 31) / 32) * (uint64_t)((g_screen_h + 31) / 32) * 1024u * (uint64_t)g_spp;
+    int per = (frames + k - 1) / k;
+    per = per > 16 ? 16 : per;
+    if (slots && (uint64_t)per * slots >= ((uint64_t)1 << 31))
+        per = (int)((((uint64_t)1 << 31) - 1) / slots);
+    per = per < 1 ? 1 : per;
+    const int launches = (frames + per - 1) / per;
+    const size_t rec = r1_frame_record_bytes(&p); // image, padded to 8 bytes, + uint64 ray count
+    const size_t img_bytes = (size_t)g_screen_w * g_screen_h * 3;
+    std::vector<r1_context *> ctx((size_t)k, nullptr);
+    std::vector<uint8_t *> host((size_t)k, nullptr);
+    const int visible = r1_device_count();
+    for (int i = 0; i < k && rc == R1_OK; ++i) // every context first, the scenes afterwards: the streams get their own hardware queues
+        rc = r1_create(g_device % (visible > 0 ? visible : 1), &ctx[(size_t)i]);
+    for (int i = 0; i < k && rc == R1_OK; ++i)
+    {
+        rc = r1_set_scene(ctx[(size_t)i], r1_host_scene_spheres(hs), r1_host_scene_camera(hs));
+        if (rc == R1_OK)
+            rc = r1_host_alloc(rec * (size_t)per, (void **)&host[(size_t)i]);
+    }
+    const int keep_frame[2] = {0, frames / 2}; // -w: the frames written afterwards
+    std::vector<uint8_t> keep[2];
+    uint64_t rays = 0;
+    double secs = 0;
+    auto landed = [&](int launch) { // the launch's records are on the host: count its rays, keep the frames that are written
+        const size_t s = (size_t)(launch % k);
+        const int f0 = launch * per, n = frames - f0 < per ? frames - f0 : per;
+        for (int i = 0; i < n; ++i)
+        {
+            rays += *(const uint64_t *)(host[s] + (size_t)(i + 1) * rec - 8);
+            for (int w = 0; w < 2; ++w)
+                if (write_tga && f0 + i == keep_frame[w])
+                    keep[w].assign(host[s] + (size_t)i * rec, host[s] + (size_t)i * rec + img_bytes);
+        }
+    };
+    for (int pass = 0; pass < 2 && rc == R1_OK; ++pass) // pass 0: workspaces and queues (not timed)
+    {
+        rays = 0;
+        const int n = pass ? launches : (k < launches ? k : launches);
+        auto t0 = std::chrono::high_resolution_clock::now();
+        for (int l = 0; l < n && rc == R1_OK; ++l)
+        {
+            const size_t s = (size_t)(l % k);
+            if (l >= k) // the slot's previous launch has to have landed before its buffer is reused
+            {
+                rc = r1_sync(ctx[s]);
+                landed(l - k);
+            }
+            const int f0 = l * per;
+            if (rc == R1_OK)
+                rc = r1_render_path_async(ctx[s], &p, frames - f0 < per ? frames - f0 : per, 0u, &cams[(size_t)f0], host[s], nullptr);
+        }
+        for (int l = n > k ? n - k : 0; l < n && rc == R1_OK; ++l)
+        {
+            rc = r1_sync(ctx[(size_t)(l % k)]);
+            landed(l);
+        }
+        secs = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
+    }
+    if (rc == R1_OK)
+        printf("%s orbit:  %d frames, %d per launch, %d in flight, %.3f ms per frame, %llu rays, %0.2f mrays/s (one camera per frame, pixels + count on the host)\n",
+               scene_name, frames, per, k, secs / frames * 1e3, (unsigned long long)rays, rays / secs / 1e6);
+    else
+        fprintf(stderr, "orbit %s: %s\n", scene_name, r1_last_error());
+    for (int w = 0; w < 2 && rc == R1_OK && write_tga; ++w)
+        if (!keep[w].empty() && (w == 0 || keep_frame[1] != keep_frame[0]))
+        {
+            char filename[128];
+            snprintf(filename, sizeof(filename), "orbit_%s_%03d.tga", scene_name, keep_frame[w]);
+            r1_tga_write_rgb24(filename, g_screen_w, g_screen_h, keep[w].data());
+        }
+    for (int i = 0; i < k; ++i)
+    {
+        r1_host_free(host[(size_t)i]);
+        r1_destroy(ctx[(size_t)i]);
+    }
+    r1_host_scene_destroy(hs);
+    return rc == R1_OK ? 0 : 1;
+}
+
 int main(int argc, const char *argv[])
 {
     bool write_tga = false;
-    bool passes_given = false;
+    bool passes_given = false, orbit_given = false;
     int num_runs = 1;
     const static int MAX_NUMS = 32;
     RESULT results[MAX_NUMS];
@@ -449,6 +559,11 @@ int main(int argc, const char *argv[])
             g_pipeline = atoi(argv[++i]);
         else if (strcmp(argv[i], "--inflight") == 0 && i + 1 < argc)
             g_inflight = atoi(argv[++i]);
+        else if (strcmp(argv[i], "--orbit") == 0 && i + 1 < argc)
+        {
+            g_orbit = atoi(argv[++i]);
+            orbit_given = true;
+        }
         else if (strcmp(argv[i], "--passes") == 0 && i + 1 < argc)
         {
             g_passes = atoi(argv[++i]);
@@ -470,13 +585,18 @@ int main(int argc, const char *argv[])
         fprintf(stderr, "bad --width/--height/--spp/--devices/--gather/--backend\n");
         return 1;
     }
+    if (orbit_given && (g_orbit < 1 || g_backend != 0 || g_devices > 1 || g_gather == 1 || passes_given || g_inflight < 1 || g_inflight > 64))
+    {
+        fprintf(stderr, "bad --orbit %d: needs FRAMES >= 1, the hip backend, one device (no --gather rccl), no --passes and 1 <= --inflight <= 64\n", g_orbit);
+        return 1;
+    }
     if (passes_given && (g_passes < 1 || g_passes > g_spp || g_backend != 0 || g_devices > 1 || g_gather == 1 || g_pipeline > 0))
     {
         fprintf(stderr, "bad --passes %d: needs 1 <= K <= spp (%d), the hip backend, one device (no --gather rccl) and no --pipeline\n", g_passes, g_spp);
         return 1;
     }
 
-    if (g_pipeline > 0 && g_backend == 0)
+    if ((g_pipeline > 0 || g_orbit > 0) && g_backend == 0)
     {
         // Frames in flight only overlap when their streams sit on different hardware queues; the ROCm default is 4.  One queue
         // per frame in flight + one for the context benchmark() renders through (two streams that share a queue run their frames
@@ -552,6 +672,13 @@ int main(int argc, const char *argv[])
         rc_pipe |= pipelined("small", R1_SCENE_SMALL, g_pipeline);
         rc_pipe |= pipelined("medium", R1_SCENE_MEDIUM, g_pipeline);
         rc_pipe |= pipelined("large", R1_SCENE_LARGE, g_pipeline);
+    }
+
+    if (g_orbit > 0)
+    {
+        rc_pipe |= orbit("small", R1_SCENE_SMALL, g_orbit, write_tga);
+        rc_pipe |= orbit("medium", R1_SCENE_MEDIUM, g_orbit, write_tga);
+        rc_pipe |= orbit("large", R1_SCENE_LARGE, g_orbit, write_tga);
     }
 
     if (pixels_pinned)

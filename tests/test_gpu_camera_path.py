@@ -1,0 +1,463 @@
+"""GPU tests of camera paths: r1_set_camera replaces the camera alone, r1_render_path_async renders one frame per
+camera in one launch (the MODE 5 kernels: where a sample starts, its lane loads the camera of the sample's frame).  Frame f of a path
+must be, byte for byte and ray for ray, what r1_render returns after r1_set_camera(cameras[f]) — and that is what r1_set_scene(scene,
+cameras[f]) gives, and what the oracle renders with that camera.  Nothing here has a tolerance."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import rays1bench_amd as r1
+from rays1bench_amd import binding
+import r1o
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAMES = {binding.VARIANT_DEFAULT: "default", binding.VARIANT_REFERENCE: "reference", binding.VARIANT_PREFILTER: "prefilter", binding.VARIANT_GRID: "grid"}
+VARIANT_KERNEL = {binding.VARIANT_DEFAULT: binding.VARIANT_BVH, binding.VARIANT_REFERENCE: binding.VARIANT_REFERENCE,
+                  binding.VARIANT_PREFILTER: binding.VARIANT_PREFILTER, binding.VARIANT_GRID: binding.VARIANT_GRID}
+PATH_VARIANTS = (binding.VARIANT_DEFAULT, binding.VARIANT_PREFILTER, binding.VARIANT_GRID)  # the variants batches accept: tree, sweep and grid families
+BATCH_RULE = "frame batches run through the throughput kernels only"
+
+
+@pytest.fixture(scope="module")
+def renderer():
+    assert r1.device_count() >= 1, "no HIP device: the product has no CPU fallback"
+    r = r1.Renderer(0)
+    yield r
+    r.close()
+
+
+def expect_refusal(fn, rule, code=binding.R1_EINVAL):
+    """The call fails with `code`, and r1_last_error names `rule`: the refusal comes from that check, not from another one the call also
+    breaks."""
+    with pytest.raises(binding.R1Error) as e:
+        fn()
+    assert e.value.code == code, e.value
+    assert rule in str(e.value), e.value
+
+
+def params(w, h, spp, seed, variant=0, tile=(32, 32)):
+    return r1.make_params(w, h, spp, seed, tile_w=tile[0], tile_h=tile[1], variant=variant)
+
+
+def with_seed(p, seed):
+    return r1.make_params(p.width, p.height, p.spp, seed, p.max_bounces, p.tile_w, p.tile_h, variant=p.variant)
+
+
+class Pageable:
+    """Ordinary host memory laid out as binding.HostFrames: n frame records."""
+
+    def __init__(self, w, h, n):
+        self.nbytes = w * h * 3
+        self.record = ((self.nbytes + 7) & ~7) + 8
+        self._all = np.zeros(self.record * n + 8, np.uint8)
+        off = (-self._all.ctypes.data) % 8
+        self._all = self._all[off:off + self.record * n]
+        self.ptr = self._all.ctypes.data
+        self._shape = (h, w, 3)
+
+    def image(self, i):
+        return self._all[i * self.record:i * self.record + self.nbytes].reshape(self._shape)
+
+    def rays(self, i):
+        return int(self._all[(i + 1) * self.record - 8:(i + 1) * self.record].view(np.uint64)[0])
+
+    def close(self):
+        pass
+
+
+def singles(renderer, p, cams, stride):
+    """[(image bytes, rays)]: r1_render with seed + f * stride after r1_set_camera(cams[f])."""
+    out = []
+    for f, cam in enumerate(cams):
+        renderer.set_camera(cam)
+        img, rays, _ = renderer.render(with_seed(p, (p.seed + f * stride) & 0xFFFFFFFF))
+        out.append((img.tobytes(), rays))
+    return out
+
+
+def path(renderer, p, cams, stride, memory="pinned"):
+    """The frames of r1_render_path_async as [(image bytes, rays)]; memory: pinned | pageable | device (host_frames NULL: nothing to read)."""
+    if memory == "device":
+        renderer.render_path_async(p, cams, None, seed_stride=stride)
+        renderer.sync()
+        return None
+    hf = (binding.HostFrames if memory == "pinned" else Pageable)(p.width, p.height, len(cams))
+    try:
+        renderer.render_path_async(p, cams, hf, seed_stride=stride)
+        renderer.sync()
+        return [(hf.image(f).tobytes(), hf.rays(f)) for f in range(len(cams))]
+    finally:
+        hf.close()
+
+
+def family_scene(case, big_size=(256, 160)):
+    if case == "big":
+        return r1.create_grid_scene(big_size[0], big_size[1], 400, 250), big_size[0], big_size[1]
+    if case == "ragged":
+        return r1.create_medium_scene(77, 45), 77, 45
+    w, h = 96, 64
+    return {"small": r1.create_small_scene, "medium": r1.create_medium_scene, "large": r1.create_large_scene}[case](w, h), w, h
+
+
+# ---- r1_set_camera = r1_set_scene ---------------------------------------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("case", ["small", "medium", "ragged", "large", "big"])
+def test_set_camera_equals_set_scene_with_that_camera(renderer, case):
+    sc, w, h = family_scene(case)
+    cam = binding.orbit_cameras(sc, 7)[3]
+    assert r1.camera_to_array(cam).tobytes() != sc.camera_array().tobytes()
+    other = r1.Renderer(0)
+    ha, hb = binding.HostFrames(w, h, 1), binding.HostFrames(w, h, 1)
+    try:
+        renderer.set_scene(sc)
+        renderer.set_camera(cam)
+        other.set_scene_raw(sc.spheres.contents, cam)
+        for variant in sorted(VARIANT_KERNEL):
+            p = params(w, h, 3, 501, variant)
+            a, b = renderer.render(p), other.render(p)
+            assert renderer.launch_info()["kernel"] == VARIANT_KERNEL[variant]
+            assert a[1] == b[1] and a[0].tobytes() == b[0].tobytes(), (case, NAMES[variant], "render")
+            renderer.render_async(p, ha)
+            other.render_async(p, hb)
+            renderer.sync(), other.sync()
+            assert ha.rays(0) == hb.rays(0) == a[1] and ha.image(0).tobytes() == hb.image(0).tobytes() == a[0].tobytes(), (case, NAMES[variant], "async")
+            sa, sb = renderer.render_samples(p), other.render_samples(p)
+            assert sa[1] == sb[1] == a[1] and sa[0].tobytes() == sb[0].tobytes() == a[0].tobytes(), (case, NAMES[variant], "samples image")
+            assert sa[2].tobytes() == sb[2].tobytes(), (case, NAMES[variant], "samples")
+        # r1_set_scene(same arrays, that camera) afterwards is the "identical scene" shortcut: nothing changes
+        renderer.set_scene_raw(sc.spheres.contents, cam)
+        again = renderer.render(params(w, h, 3, 501))
+        want = other.render(params(w, h, 3, 501))
+        assert again[1] == want[1] and again[0].tobytes() == want[0].tobytes()
+    finally:
+        ha.close(), hb.close()
+        other.close()
+
+
+@pytest.mark.parametrize("case", ["small", "medium", "large"])
+def test_set_camera_equals_the_oracle_80x60x4(renderer, case):
+    w, h, spp, seed = 80, 60, 4, 10001
+    sc = {"small": r1.create_small_scene, "medium": r1.create_medium_scene, "large": r1.create_large_scene}[case](w, h)
+    cam = binding.orbit_cameras(sc, 5)[2]
+    renderer.set_scene(sc)
+    renderer.set_camera(cam)
+    oimg, orays, osamples = r1o.render_frame(r1o.SceneArrays(sc.arrays(), r1.camera_to_array(cam)), r1o.make_params(w, h, spp, seed), want_samples=True)
+    for variant in sorted(VARIANT_KERNEL):
+        img, rays, samples = renderer.render_samples(params(w, h, spp, seed, variant))
+        assert rays == orays and img.tobytes() == oimg.tobytes() and samples.tobytes() == osamples.tobytes(), (case, NAMES[variant])
+
+
+# ---- a path = its single frames -----------------------------------------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("variant", PATH_VARIANTS, ids=lambda v: NAMES[v])
+@pytest.mark.parametrize("case", ["small", "big"])
+def test_path_frames_equal_single_frames(renderer, case, variant):
+    sc, w, h = family_scene(case, big_size=(64, 40))
+    renderer.set_scene(sc)
+    own = sc.camera.contents
+    cams = binding.orbit_cameras(sc, 9)[1:8]  # seven cameras, none of them the scene's own
+    p = params(w, h, 2, 900, variant)
+    want = {stride: singles(renderer, p, cams, stride) for stride in (0, 1)}
+    assert len({x[0] for x in want[0]}) == 7  # the frames differ from one another: a kernel that ignored the table could not pass
+    renderer.set_camera(own)
+    own_frame = renderer.render(p)
+    for n in (1, 2, 7):
+        for stride in (0, 1):
+            for memory in ("pinned", "pageable"):
+                got = path(renderer, p, cams[:n], stride, memory)
+                info = renderer.launch_info()
+                assert info["kernel"] == VARIANT_KERNEL[variant]
+                for f in range(n):
+                    assert got[f][1] == want[stride][f][1], (case, NAMES[variant], n, stride, memory, f)
+                    assert got[f][0] == want[stride][f][0], (case, NAMES[variant], n, stride, memory, f)
+            path(renderer, p, cams[:n], stride, "device")
+            # the frames stayed on the device; the context's camera is what it was, and a synchronous render is unaffected
+            after = renderer.render(p)
+            assert after[1] == own_frame[1] and after[0].tobytes() == own_frame[0].tobytes(), (case, NAMES[variant], n, stride)
+
+
+@pytest.mark.parametrize("variant", PATH_VARIANTS, ids=lambda v: NAMES[v])
+@pytest.mark.parametrize("shape", [(8, 4, 1, (4, 4)), (4, 2, 1, (2, 2)), (40, 24, 3, (32, 32))], ids=["8x4x1-tiles4", "4x2x1-tiles2", "40x24x3-ragged"])
+def test_chunks_that_span_frames(renderer, shape, variant):
+    """8 x 4 x 1 with 4 x 4 tiles: a frame is 32 sample slots (R1_CHUNK_MIN), so the 64 lanes of a wave hold two or three frames;
+    4 x 2 x 1 with 2 x 2 tiles: 16 slots, one chunk of the queue spans two frames; 40 x 24 x 3 with 32 x 32 tiles: ragged on both edges."""
+    w, h, spp, tile = shape
+    sc = r1.create_small_scene(w, h)
+    renderer.set_scene(sc)
+    cams = binding.orbit_cameras(sc, 7)
+    p = params(w, h, spp, 77, variant, tile)
+    for stride in (0, 1):
+        want = singles(renderer, p, cams, stride)
+        got = path(renderer, p, cams, stride)
+        assert got == want, (shape, NAMES[variant], stride)
+        if stride == 0:
+            assert len({x[0] for x in want}) >= (7 if w >= 8 else 2), shape
+    renderer.set_camera(sc.camera.contents)
+
+
+def test_full_size_large_1200x800x10_four_cameras(renderer):
+    w, h = 1200, 800
+    sc = r1.create_large_scene(w, h)
+    renderer.set_scene(sc)
+    cams = binding.orbit_cameras(sc, 4)
+    p = params(w, h, 10, 10001)
+    want = singles(renderer, p, cams, 1)
+    got = path(renderer, p, cams, 1)
+    assert renderer.launch_info()["kernel"] == binding.VARIANT_BVH and renderer.launch_info()["tiles_in_kernel"] == 1
+    for f in range(4):
+        assert got[f][1] == want[f][1] and got[f][0] == want[f][0], f
+    assert len({x[0] for x in got}) == 4
+
+
+@pytest.mark.parametrize("variant", [binding.VARIANT_DEFAULT, binding.VARIANT_GRID], ids=lambda v: NAMES[v])
+def test_config5_scene_at_a_reduced_frame(renderer, variant):
+    """The 100 004-sphere lattice of BASELINE config 5 (the big-scene kernels) at 320 x 200 x 4, three cameras."""
+    w, h = 320, 200
+    sc = r1.create_grid_scene(w, h, 400, 250)
+    renderer.set_scene(sc)
+    cams = binding.orbit_cameras(sc, 3)
+    p = params(w, h, 4, 10001, variant)
+    want = singles(renderer, p, cams, 0)
+    got = path(renderer, p, cams, 0)
+    assert got == want and len({x[0] for x in got}) == 3
+
+
+# ---- the same camera everywhere = the batch -----------------------------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("variant", PATH_VARIANTS, ids=lambda v: NAMES[v])
+@pytest.mark.parametrize("case", ["small", "big"])
+def test_one_camera_everywhere_is_the_batch(renderer, case, variant):
+    sc, w, h = family_scene(case, big_size=(64, 40))
+    renderer.set_scene(sc)
+    p = params(w, h, 3, 333, variant)
+    n = 3
+    hb, hp = binding.HostFrames(w, h, n), binding.HostFrames(w, h, n)
+    try:
+        renderer.render_batch_async(p, n, hb, seed_stride=1)
+        renderer.sync()
+        batch_info = renderer.launch_info()
+        renderer.render_path_async(p, [sc.camera.contents] * n, hp, seed_stride=1)
+        renderer.sync()
+        path_info = renderer.launch_info()
+        assert hp._all.tobytes() == hb._all.tobytes(), (case, NAMES[variant])
+        assert path_info["kernel"] == batch_info["kernel"] == VARIANT_KERNEL[variant]
+        assert path_info["tiles_in_kernel"] == batch_info["tiles_in_kernel"] == (1 if variant == binding.VARIANT_DEFAULT else 0)
+        assert path_info["blocks"] == batch_info["blocks"] and path_info["samples"] == batch_info["samples"]
+    finally:
+        hb.close(), hp.close()
+
+
+# ---- hard cameras -------------------------------------------------------------------------------------------------------------------
+
+
+def test_cameras_inside_a_sphere_and_without_a_lens(renderer):
+    """A lookfrom below the surface of the r = 100 ground sphere of the small scene (centre (0, -100.5, -1)), and lens_radius 0."""
+    w, h, spp, seed = 40, 24, 2, 55
+    sc = r1.create_small_scene(w, h)
+    v = sc.view()
+    inside = r1.camera_look_at((0.5, -0.7, 0.2), (0, 0, -1), v["vup"], 60, v["aspect"], 0.1, 1.5)
+    o = np.array([0.5, -0.7, 0.2]) - np.array([0, -100.5, -1])
+    assert np.sqrt((o * o).sum()) < 100.0
+    pinhole = r1.camera_look_at(v["lookfrom"], v["lookat"], v["vup"], v["vfov"], v["aspect"], 0.0, v["focus_dist"])
+    assert pinhole.lens_radius == 0.0
+    cams = [inside, pinhole, sc.camera.contents, inside]
+    renderer.set_scene(sc)
+    oracle = []
+    for cam in cams:
+        img, rays, _ = r1o.render_frame(r1o.SceneArrays(sc.arrays(), r1.camera_to_array(cam)), r1o.make_params(w, h, spp, seed))
+        oracle.append((img.tobytes(), rays))
+    assert oracle[0] != oracle[1] != oracle[2]
+    for variant in PATH_VARIANTS:
+        p = params(w, h, spp, seed, variant)
+        want = singles(renderer, p, cams, 0)
+        assert want == oracle, NAMES[variant]
+        assert path(renderer, p, cams, 0) == want, NAMES[variant]
+
+
+def test_grid_camera_beyond_v_takes_the_fallback_in_a_path(renderer):
+    """A camera whose origin lies farther than v_safe from the registered centres' box: every primary ray takes the grid kernel's tree
+    walk (GRID_STATS slot 14 after set_camera shows it); as frames of a path, between frames that walk the grid, it equals PREFILTER's."""
+    w, h, spp, seed = 96, 64, 2, 41
+    sc = r1.create_large_scene(w, h)
+    info = binding.grid_describe(sc.spheres.contents)[0]
+    frm = np.array([80.0, 14.0, 18.0])
+    clo, chi = info["centre_lo"].astype(np.float64), info["centre_hi"].astype(np.float64)
+    nearest = np.sqrt((np.maximum(np.maximum(clo - frm, frm - chi), 0.0) ** 2).sum())
+    assert nearest > float(info["v_safe"]), (nearest, info["v_safe"])
+    far = r1.camera_look_at(frm, (0.0, 0.5, 0.0), (0, 1, 0), 12.0, np.float32(w) / np.float32(h), 0.0, 10.0)
+    renderer.set_scene(sc)
+    renderer.set_camera(far)
+    renderer.render(params(w, h, spp, seed, binding.VARIANT_GRID_STATS))
+    assert renderer.last_stats()["raw"][14] >= 0.9 * w * h * spp
+    cams = [sc.camera.contents, far, binding.orbit_cameras(sc, 4)[1], far]
+    frames = {}
+    for variant in (binding.VARIANT_GRID, binding.VARIANT_PREFILTER):
+        p = params(w, h, spp, seed, variant)
+        frames[variant] = path(renderer, p, cams, 1)
+        assert renderer.launch_info()["kernel"] == variant
+        assert frames[variant] == singles(renderer, p, cams, 1), NAMES[variant]
+    assert frames[binding.VARIANT_GRID] == frames[binding.VARIANT_PREFILTER]
+    assert frames[binding.VARIANT_GRID][1][1] > 1.5 * w * h * spp  # (the far camera looks at the scene: most of its rays hit)
+
+
+# ---- frames in flight ---------------------------------------------------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("case", ["small", "big"])
+def test_launches_keep_the_camera_they_were_enqueued_with(renderer, case):
+    sc, w, h = family_scene(case, big_size=(128, 80))
+    renderer.set_scene(sc)
+    cam_a, cam_b = binding.orbit_cameras(sc, 5)[1:3]
+    p = params(w, h, 6, 2024)
+    want_a, want_b = singles(renderer, p, [cam_a, cam_b], 0)
+    assert want_a != want_b
+    ha, hb, hp = binding.HostFrames(w, h, 1), binding.HostFrames(w, h, 1), binding.HostFrames(w, h, 2)
+    try:
+        renderer.set_camera(cam_a)
+        renderer.render_async(p, ha)
+        renderer.set_camera(cam_b)  # at once: the first frame is still in flight
+        renderer.render_async(p, hb)
+        renderer.render_path_async(p, [cam_a, cam_a], hp)  # ... and so is the second
+        renderer.sync()
+        assert (ha.image(0).tobytes(), ha.rays(0)) == want_a
+        assert (hb.image(0).tobytes(), hb.rays(0)) == want_b
+        assert (hp.image(0).tobytes(), hp.rays(0)) == want_a and (hp.image(1).tobytes(), hp.rays(1)) == want_a
+        # after r1_render_path_async the context's camera is what it was: B
+        img, rays, _ = renderer.render(p)
+        assert (img.tobytes(), rays) == want_b
+    finally:
+        ha.close(), hb.close(), hp.close()
+
+
+# ---- state and refusals -------------------------------------------------------------------------------------------------------------
+
+
+def test_state_and_refusals(renderer):
+    w, h = 96, 64
+    sc = r1.create_medium_scene(w, h)
+    cams = binding.orbit_cameras(sc, 4)
+    fresh = r1.Renderer(0)
+    try:
+        expect_refusal(lambda: fresh.set_camera(cams[1]), "r1_set_camera: no scene set")
+        expect_refusal(lambda: fresh.render_path_async(params(w, h, 2, 1), cams[:2], None), "no scene set")
+        fresh.set_scene(sc)
+        fresh.set_camera(cams[1])
+    finally:
+        fresh.close()
+    renderer.set_scene(sc)
+    renderer.set_camera(cams[1])
+    p = params(w, h, 3, 91)
+    want = renderer.render(p)
+
+    def still_renders():
+        got = renderer.render(p)
+        assert got[1] == want[1] and got[0].tobytes() == want[0].tobytes()
+        assert path(renderer, p, [cams[1], cams[1]], 0) == [(want[0].tobytes(), want[1])] * 2
+
+    # a progressive pass does not continue across r1_set_camera (even with the same camera), as across r1_set_scene
+    renderer.render_pass(params(w, h, 2, 91), 0)
+    renderer.set_camera(cams[1])
+    expect_refusal(lambda: renderer.render_pass(params(w, h, 1, 91), 2), "no accumulation to continue")
+    img, rays = renderer.render_pass(params(w, h, 2, 91), 0)
+    img, rays = renderer.render_pass(params(w, h, 1, 91), 2)
+    assert rays == want[1] and img.tobytes() == want[0].tobytes()
+    still_renders()
+    # the variants and modes batches refuse
+    for v in (binding.VARIANT_STATS, binding.VARIANT_BVH_STATS, binding.VARIANT_GRID_STATS, binding.VARIANT_REFERENCE, binding.VARIANT_WAVEFRONT):
+        for n in (1, 3):
+            expect_refusal(lambda: renderer.render_path_async(params(w, h, 3, 91, v), cams[:n], None), BATCH_RULE)
+    still_renders()
+    renderer.set_pixel_mode(True)
+    try:
+        expect_refusal(lambda: renderer.render_path_async(p, cams[:3], None), BATCH_RULE)
+        expect_refusal(lambda: renderer.render_path_async(p, cams[:1], None), BATCH_RULE)
+    finally:
+        renderer.set_pixel_mode(False)
+    still_renders()
+    shard = r1.make_params(w, h, 3, 91, shard=0, num_shards=2)
+    expect_refusal(lambda: renderer.render_path_async(shard, cams[:2], None), "whole frames")
+    L, arr = r1.lib(), (binding.CCamera * 2)(*cams[:2])
+    assert L.r1_render_path_async(renderer._c, C.byref(p), 2, 0, None, None, None) == binding.R1_EINVAL
+    assert "cameras is NULL" in L.r1_last_error().decode()
+    assert L.r1_render_path_async(renderer._c, C.byref(p), 0, 0, arr, None, None) == binding.R1_EINVAL
+    assert "n_frames < 1" in L.r1_last_error().decode()
+    assert L.r1_render_path_async(renderer._c, None, 2, 0, arr, None, None) == binding.R1_EINVAL
+    assert "params is NULL" in L.r1_last_error().decode()
+    assert L.r1_set_camera(renderer._c, None) == binding.R1_EINVAL
+    assert "camera is NULL" in L.r1_last_error().decode()
+    still_renders()
+
+
+def test_a_path_one_frame_too_long_for_a_launch(renderer):
+    """The 2^31 padded-slot rule of a launch, by the same rule and text as batches: a 1 x 1 image in 2048 x 2048 tiles is 2^22 slots per
+    frame — 512 frames are refused (R1_ELIMIT), 511 are rendered: each frame is the one pixel r1_render returns for its camera."""
+    w, h = 1, 1
+    sc = r1.create_small_scene(w, h)
+    renderer.set_scene(sc)
+    seven = binding.orbit_cameras(sc, 7)
+    p = params(w, h, 1, 606, tile=(2048, 2048))
+    want = singles(renderer, p, seven, 0)
+    renderer.set_camera(sc.camera.contents)
+    cams = [seven[f % 7] for f in range(512)]
+    expect_refusal(lambda: renderer.render_path_async(p, cams, None), "exceed 2^31 sample slots per launch", code=binding.R1_ELIMIT)
+    expect_refusal(lambda: renderer.render_batch_async(p, 512, None), "exceed 2^31 sample slots per launch", code=binding.R1_ELIMIT)
+    got = path(renderer, p, cams[:511], 0, "pageable")
+    for f in range(511):
+        assert got[f] == want[f % 7], f
+    after = renderer.render(p)
+    assert (after[0].tobytes(), after[1]) == want[0]
+
+
+def test_one_device_multi_renderer_set_camera(renderer):
+    w, h = 120, 80
+    sc = r1.create_large_scene(w, h)
+    cam = binding.orbit_cameras(sc, 6)[2]
+    renderer.set_scene(sc)
+    renderer.set_camera(cam)
+    p = params(w, h, 4, 808)
+    want = renderer.render(p)
+    m = binding.MultiRenderer([0])
+    try:
+        expect_refusal(lambda: m.set_camera(cam), "no scene set")
+        m.set_scene(sc)
+        own = m.render(p)
+        m.set_camera(cam)
+        img, rays, _ = m.render(p)
+        assert rays == want[1] and img.tobytes() == want[0].tobytes()
+        assert own[0].tobytes() != img.tobytes()
+    finally:
+        m.close()
+
+
+# ---- the drop-in program --------------------------------------------------------------------------------------------------------------
+
+
+def test_program_orbit_option(tmp_path):
+    exe = os.path.join(ROOT, "rays1bench_amd", "lib", "rayweek1_hip")
+    w, h, spp = 160, 96, 3
+    out = subprocess.run([exe, "--orbit", "6", "--inflight", "2", "-n", "1", "-w", "--width", str(w), "--height", str(h), "--spp", str(spp)],
+                         cwd=tmp_path, capture_output=True, timeout=300)
+    assert out.returncode == 0, out.stderr.decode()
+    text = out.stdout.decode()
+    for name in ("small", "medium", "large"):
+        lines = re.findall(rf"^{name} orbit:  6 frames, 3 per launch, 2 in flight, \d+\.\d{{3}} ms per frame, (\d+) rays, \d+\.\d\d mrays/s", text, flags=re.M)
+        assert len(lines) == 1, (name, text)
+        assert int(lines[0]) >= 6 * w * h * spp
+        first = (tmp_path / f"orbit_{name}_000.tga").read_bytes()
+        assert first == (tmp_path / f"out_{name}.tga").read_bytes(), name  # angle 0 is the scene's own camera, bit for bit
+        middle = (tmp_path / f"orbit_{name}_003.tga").read_bytes()
+        assert len(middle) == len(first) and middle != first, name
+    assert sorted(f.name for f in tmp_path.iterdir() if f.name.startswith("orbit_")) == sorted(
+        f"orbit_{n}_{k}.tga" for n in ("small", "medium", "large") for k in ("000", "003"))
+    # without the flag the program prints no such line
+    plain = subprocess.run([exe, "--width", "64", "--height", "32", "--spp", "1"], cwd=tmp_path, capture_output=True, timeout=300)
+    assert plain.returncode == 0 and b"orbit" not in plain.stdout
