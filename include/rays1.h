@@ -427,6 +427,11 @@ typedef struct r1_bvh_info
     int32_t pad_local; /* 1: the tree uses pad = A |m0 + m1 - 2 o|^2 + K instead (scenes of small spheres) */
     int32_t root_leaf; /* 1 / 2: child 0 / 1 of the root is a leaf of <= 2 sphere pairs and the other child an inner node — the kernels test
                           that leaf and the other child's box once per ray outside the walk's loops; 0: the root has no such shape */
+    int32_t flat_axis; /* 0 / 1 / 2: along this axis every box the walk's node loop tests (the child boxes of every inner node but a root of the
+                          root-step shape) lies in the slab [flat_m - flat_e, flat_m + flat_e], which is at most 1.25 x as wide as the
+                          narrowest of them; the small-scene tree kernels test that slab once per ray instead of each box's own (axis 1: y).
+                          -1: no such axis (and always for pad_local trees and trees beyond the small-scene kernels' limits) */
+    float flat_m, flat_e;
 } r1_bvh_info;
 int r1_bvh_describe(const r1_scene *scene, int32_t leaf_max, r1_bvh_info *info, float *nodes_out, size_t nodes_cap, uint32_t *ids_out,
                     size_t ids_cap);

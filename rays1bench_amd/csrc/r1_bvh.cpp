@@ -25,9 +25,13 @@
 // What the kernel evaluates (r1_trace.hpp::bvh_box) is ONE fused multiply-add per node,
 //      pad = A * R2 + K,      R2 = |o - C|^2 computed once per ray,
 // C a fixed point of the scene (the per-axis median of the sphere centres, R1Bvh::centre), and
-// A = 2 w2 + u, K = k + 2 w2 g^2 + u (1 + |C|_1), g = the larger |m - C| of the node's two children:
-// |m - o|^2 <= 2 |o - C|^2 + 2 |m - C|^2, so pad >= pad_min for both children, at the price of boxes
-// a few 1e-2 units wider than necessary (large scene: pad ~0.03 next to r = 0.45).  The u terms pay for
+// A = 2 w2 + u, K = k + 2 w2 g^2 + u (1 + |C|_1), g = |m - C|, w2, k and g each CHILD's own (these trees fold K
+// into the half extents child by child, below, so nothing forces both children to carry the larger one; A is
+// the tree's maximum, >= 2 w2 + u of every child):
+// |m - o|^2 <= 2 |o - C|^2 + 2 |m - C|^2, so pad >= pad_min for each child, at the price of boxes
+// a few 1e-2 units wider than necessary (large scene: pad ~0.03 next to r = 0.45).  (One K per NODE, the worse
+// child's, made the sibling of the ground sphere — m_y = -1000.5, g = 1000 — 17.5 units too wide on every side:
+// the box of the root step, which 30.6 % of all rays passed only to fail both boxes of the node below.)  The u terms pay for
 // the slab test's own form a = m * (1/d) - o * (1/d) (fused, o * (1/d) rounded once per ray): next to
 // the errors budgeted above it adds u |o| (1 + u) in position units, and |o| <= |o - C| + |C| <=
 // (1 + R2) / 2 + |C|.  A and K are rounded up with 2^-18 relative headroom for the fp32 evaluation
@@ -66,6 +70,8 @@ struct R1Bvh
     float centre[3] = {0, 0, 0}; // C of the pad formula (see above)
     int pad_local = 0;           // 1: pad measured per node (scenes of small spheres), 0: from `centre`
     int root_leaf = 0;           // 1 / 2: child 0 / 1 of the root is a leaf of <= 2 sphere pairs and the other child an inner node (the root step), 0: no
+    int flat_axis = -1;          // 0 / 1 / 2: every box the node loop tests has nearly the same slab along this axis (see "flat axis" below), -1: none
+    float flat_m = 0, flat_e = 0; // that axis: centre and half extent of the union of those slabs, rounded outward
 };
 
 namespace
@@ -309,16 +315,29 @@ struct Builder
         float A, K;
         if (!pad_local)
         {
-            double g2 = 0;
+            static const int child_k = (int)r1_knob("R1_BVH_CHILD_K", 1); // tuning experiments: 0 = both children carry the worse child's K
+            const double c1n = std::fabs(centre[0]) + std::fabs(centre[1]) + std::fabs(centre[2]);
+            double g2c[2], kc[2] = {k0, k1}, wc[2] = {w0, w1};
+            int j = 0;
             for (const float *m : {m0, m1})
             {
                 double q = 0;
                 for (int a = 0; a < 3; ++a)
                     q += ((double)m[a] - centre[a]) * ((double)m[a] - centre[a]);
-                g2 = std::max(g2, q);
+                g2c[j++] = q;
             }
-            const double c1n = std::fabs(centre[0]) + std::fabs(centre[1]) + std::fabs(centre[2]);
-            A = round_up((2.0 * w2 + u) * head), K = round_up((k + 2.0 * w2 * g2 + u * (1.0 + c1n)) * head);
+            if (!child_k)
+                g2c[0] = g2c[1] = std::max(g2c[0], g2c[1]), kc[0] = kc[1] = k, wc[0] = wc[1] = w2;
+            A = round_up((2.0 * w2 + u) * head), K = 0.0f;
+            // K folded into the half extents here, e' = e + K rounded up, each child its own (see r1_build_bvh: "ONE A for the whole tree")
+            j = 0;
+            for (float *e : {e0, e1})
+            {
+                const float Kc = round_up((kc[j] + 2.0 * wc[j] * g2c[j] + u * (1.0 + c1n)) * head);
+                for (int a = 0; a < 3; ++a)
+                    e[a] = round_up((double)e[a] + (double)Kc);
+                ++j;
+            }
         }
         else
         {
@@ -537,7 +556,7 @@ void r1_build_bvh(uint32_t na, const float *cx, const float *cy, const float *cz
         }
     }
     // Trees whose pad is measured from the scene's centre: ONE A for the whole tree (the largest of the nodes': pad only grows) and
-    // every node's K folded into its half extents, e' = e + K rounded up — b = e |1/d| + (A R2 + K) |1/d| = e' |1/d| + (A R2) |1/d| —
+    // every child's K folded into its half extents (fill()), e' = e + K rounded up — b = e |1/d| + (A R2 + K) |1/d| = e' |1/d| + (A R2) |1/d| —
     // so that the kernels which keep the table in LDS evaluate A R2 |1/d| once per RAY instead of a fused multiply-add and three
     // products per node visit (bvh_advance; 51 -> 47 VALU instructions per visit).  The same number of fp32 roundings as before on the
     // way to b (product, product, fused multiply-add), covered by the same 2^-18 headroom on A and K.  Nodes keep {A, 0} in the pad
@@ -549,14 +568,7 @@ void r1_build_bvh(uint32_t na, const float *cx, const float *cy, const float *cz
         for (size_t n = 0; n < nn; ++n)
             a_max = std::max(a_max, out.nodes[16 * n + 12]);
         for (size_t n = 0; n < nn; ++n)
-        {
-            float *q = &out.nodes[16 * n];
-            const double K = q[13];
-            for (int j = 6; j < 12; ++j)
-                if (std::isfinite(q[j])) // (-inf: a child that never passes)
-                    q[j] = round_up((double)q[j] + K);
-            q[12] = a_max, q[13] = 0.0f;
-        }
+            out.nodes[16 * n + 12] = a_max;
     }
     // The root of the reference's scenes is [one leaf of outliers: the ground + the three big balls | the lattice] (the peeling above),
     // and EVERY ray tests that leaf.  The tree kernels take this step out of the walk's divergent loops: a ray that starts its walk tests
@@ -573,6 +585,48 @@ void r1_build_bvh(uint32_t na, const float *cx, const float *cy, const float *cz
             const uint32_t pairs = (c[k] >> 28) & 7u;
             if ((c[k] & Builder::LEAF) && !(c[1 - k] & Builder::LEAF) && pairs >= 1 && pairs <= 2)
                 out.root_leaf = k + 1;
+        }
+    }
+    // Flat axis.  The reference's scenes are lattices of equal spheres on a plane: every box the node loop tests (the child boxes of
+    // every inner node, but for a root that has the root-step shape: its boxes are tested outside the loop) has, within a few per cent,
+    // the same slab along the plane's normal, and a third of the loop's box arithmetic recomputes it.  For the trees the `LN` walks
+    // take (pad from the scene's centre, table in LDS) the builder names the axis — at most one — along which the UNION of those slabs
+    // is at most R1_BVH_FLAT_RATIO x the narrowest of them, and stores the union as (m_u, e_u) rounded outward: m_u - e_u <= m - e and
+    // m_u + e_u >= m + e in real arithmetic for every such box, K included.  bvh_advance tests that ONE slab once per call instead of
+    // each box's own: a wider box is a conservative box, and the slab test has the form and the operand sizes the pad budgets for.
+    // Among several such axes the one with the smallest ratio; equal ratios: y, then x, then z.  The decision depends on the scene alone.
+    // 1.25: the large scene has 1.12, the medium one (spheres at y = 0, 1 and 1.5) 2.30 — forcing the union there costs +15 % node
+    // visits.  1.0 / 1.25 / 1.5 on the large scene: DESIGN.md 4.17.  0 = never flat.
+    out.flat_axis = -1, out.flat_m = out.flat_e = 0.0f;
+    {
+        static const double ratio_env = r1_knob_f("R1_BVH_FLAT_RATIO", 1.25);
+        const size_t nn = out.nodes.size() / 16;
+        // (a tree of one node has no walk to shorten — its one or two boxes would pass for flat along every axis — and the kernels keep
+        //  the slab in node 1's pad slots)
+        if (ratio_env > 0 && !B.pad_local && nn >= 2 && nn <= R1_NODES_LDS_MAX && na <= R1_MAX_ACTIVE_10BIT)
+        {
+            double best_ratio = 1e300;
+            for (int a : {1, 0, 2})
+            {
+                double L = 1e300, H = -1e300, narrow = 1e300;
+                for (size_t n = out.root_leaf ? 1 : 0; n < nn; ++n)
+                    for (int c = 0; c < 2; ++c)
+                    {
+                        const double m = out.nodes[16 * n + 2 * a + c], e = out.nodes[16 * n + 6 + 2 * a + c];
+                        if (!(e >= 0)) // (-inf: a child that never passes)
+                            continue;
+                        L = std::min(L, m - e), H = std::max(H, m + e), narrow = std::min(narrow, 2.0 * e);
+                    }
+                if (!(H >= L) || !(narrow > 0) || !std::isfinite(H - L))
+                    continue;
+                const double ratio = (H - L) / narrow;
+                if (ratio <= ratio_env && ratio < best_ratio)
+                {
+                    best_ratio = ratio;
+                    const float mu = (float)(0.5 * (L + H));
+                    out.flat_axis = a, out.flat_m = mu, out.flat_e = round_up(std::max(H - (double)mu, (double)mu - L));
+                }
+            }
         }
     }
     // keep the tables non-empty for the uploader
@@ -649,6 +703,7 @@ extern "C" int r1_bvh_describe(const r1_scene *s, int32_t leaf_max, r1_bvh_info 
         info->centre[k] = b.centre[k];
     info->pad_local = b.pad_local;
     info->root_leaf = b.root_leaf;
+    info->flat_axis = b.flat_axis, info->flat_m = b.flat_m, info->flat_e = b.flat_e;
     if (nodes_out)
     {
         if (nodes_cap < b.nodes.size())

@@ -51,6 +51,8 @@ struct R1Bvh
     float centre[3] = {0, 0, 0};
     int pad_local = 0;
     int root_leaf = 0;
+    int flat_axis = -1;
+    float flat_m = 0, flat_e = 0;
 };
 void r1_build_bvh(uint32_t na, const float *cx, const float *cy, const float *cz, const float *rsq, const double *rbound, int leaf_max,
                   R1Bvh &out);
@@ -122,6 +124,7 @@ struct r1_context
     float bvh_centre[3] = {0, 0, 0};
     int bvh_pad_local = 0;
     int bvh_root_leaf = 0;
+    float bvh_flat_m = 0.0f, bvh_flat_e = -1.0f; // the tree's flat y slab (r1_bvh.cpp), e < 0: none
     uint32_t n_active = 0, n_sweep = 0, n_padded_scene = 0, n_groups = 0, n_multi = 0;
     std::vector<uint32_t> active_to_scene;
     R1DeviceCamera cam;
@@ -785,6 +788,8 @@ extern "C" int r1_set_scene(r1_context *c, const r1_scene *s, const r1_camera *c
         c->bvh_centre[k] = bvh.centre[k];
     c->bvh_pad_local = bvh.pad_local;
     c->bvh_root_leaf = bvh.root_leaf;
+    // (the kernels' flat walk is written for y, the up axis of the reference's scenes; a tree flat along x or z walks the generic loop)
+    c->bvh_flat_m = bvh.flat_axis == 1 ? bvh.flat_m : 0.0f, c->bvh_flat_e = bvh.flat_axis == 1 ? bvh.flat_e : -1.0f;
     for (int &o : c->occupancy)
         o = 0; // the tree kernels' LDS footprint follows the tree (depth of the traversal stack, size of the node table)
     c->n_groups = ng;
@@ -1253,6 +1258,7 @@ static int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int blo
         a.scene.bvh_centre[k] = c->bvh_centre[k];
     a.scene.bvh_pad_local = (uint32_t)c->bvh_pad_local;
     a.scene.bvh_root_leaf = (uint32_t)c->bvh_root_leaf;
+    a.scene.bvh_flat_m = c->bvh_flat_m, a.scene.bvh_flat_e = c->bvh_flat_e;
     a.cam = c->cam;
     a.width = p->width, a.height = p->height, a.spp = p->spp, a.max_bounces = p->max_bounces;
     a.seed = p->seed;

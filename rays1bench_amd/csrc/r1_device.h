@@ -208,6 +208,8 @@ struct R1DeviceScene
     float bvh_centre[3];
     uint32_t bvh_pad_local; // 1: pad = A |m0 + m1 - 2 o|^2 + K (scenes of small spheres, r1_bvh.cpp)
     uint32_t bvh_root_leaf; // 1 / 2: child 0 / 1 of the root is a leaf of <= 2 pairs that every ray tests: the root step of bvh_advance; 0: none
+    float bvh_flat_m, bvh_flat_e; // flat trees (r1_bvh.cpp "flat axis", y only): the y slab every box of the node loop lies in; bvh_flat_e < 0: not flat.
+                                  // Read once, where the small-scene tree kernels copy the node table into LDS (bvh_advance finds it there)
 };
 
 // R1_VARIANT_GRID (r1_grid.cpp): the uniform grid's walk geometry and tables (device memory, R1TraceArgs::grid).  `tab` = [cells + 1] CSR offsets, then the registered

@@ -829,7 +829,7 @@ __device__ __forceinline__ void bvh_advance(const R1DeviceScene &S, const V3 o, 
     // pad budgets for its own rounding (r1_bvh.cpp)
     const V3 inv = mk(__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y), __builtin_amdgcn_rcpf(d.z));
     const V3 ainv = mk(fabsf(inv.x), fabsf(inv.y), fabsf(inv.z));
-    const V3 oi = mk(o.x * inv.x, o.y * inv.y, o.z * inv.z);
+    V3 oi = mk(o.x * inv.x, o.y * inv.y, o.z * inv.z); // (flat trees: oi.y becomes N once the root step is over, see visit_flat)
     const float rx = o.x - S.bvh_centre[0], ry = o.y - S.bvh_centre[1], rz = o.z - S.bvh_centre[2];
     const float r2 = __fmaf_rn(rz, rz, __fmaf_rn(ry, ry, rx * rx)); // |o - C|^2 of pad = A r2 + K
     V3 pa_ray = mk(0.0f, 0.0f, 0.0f);
@@ -944,13 +944,60 @@ __device__ __forceinline__ void bvh_advance(const R1DeviceScene &S, const V3 o, 
         else
             cur = R1_BVH_DONE;
     };
+    // Flat trees (r1_bvh.cpp "flat axis"; the small-scene kernels, y): every box the node loop tests lies in ONE y slab (m_u, e_u), wider
+    // than the narrowest of them by a few per cent.  The slab is tested once per call,
+    //      a_u = m_u / d.y - o.y / d.y   b_u = e_u |1 / d.y| + pa.y   N = max(a_u - b_u, 0)   F = min(a_u + b_u, best)   (F again after a leaf)
+    // and a child box costs its two other axes and ONE compare: max(tn, 0) <= min(tf, best) holds iff tn <= tf && tn <= best && tf >= 0,
+    // because best > 0 always (>= 0.001 or FLT_MAX).  11 VALU instructions per box instead of 17, 40 bytes of the node instead of 56, and
+    // the m_y / e_y words are not fetched.  A box tested with the union's slab instead of its own is a
+    // wider box: every sphere that matters is still presented, and the result is the minimum offer with ties to the lowest index in any
+    // order — so two children that both contain the origin (entry distances clamped to N alike) are no longer swapped, to no effect.  NaN
+    // axes drop out of max3 / min3 as in bvh_box; a ray without any finite axis passes where bvh_box failed it: the conservative side.
+    // N and F live where the generic loop keeps oi.y and pa.y (`oi.y`, `pa_ray.y` below), and ONE outer loop serves both walks, picking its
+    // node loop by the tree's flag (a scalar: the compiler keeps it in one SGPR).  Two copies of the outer loop, or N / F in registers of
+    // their own, spilled 5-22 VGPRs to scratch in the 72-register builds; this form leaves every tree kernel the VGPR count it had.
+    // F = min(a_u + b_u, best) follows `best` where it moves — after a leaf: recomputed before each run of the node loop instead, the
+    // synchronous-frame and PIXEL kernels took 1-6 VGPRs more and the rate was 0.1 % lower.
+    constexpr bool FLAT_OK = LN && !ENTRY && !R1_BVH4;
+    auto visit_flat = [&]() {
+        if (STATS)
+        {
+            wstat[9] += 1;
+            if ((tid & 63) == __ffsll((long long)__ballot(1)) - 1)
+                wstat[2] += 1;
+        }
+        const float4 q0 = lnodes[4 * cur + 0], q1 = lnodes[4 * cur + 1], q2 = lnodes[4 * cur + 2], q3 = lnodes[4 * cur + 3];
+        const float ax0 = __fmaf_rn(q0.x, inv.x, -oi.x), az0 = __fmaf_rn(q1.x, inv.z, -oi.z);
+        const float bx0 = __fmaf_rn(q1.z, ainv.x, pa_ray.x), bz0 = __fmaf_rn(q2.z, ainv.z, pa_ray.z);
+        const float ax1 = __fmaf_rn(q0.y, inv.x, -oi.x), az1 = __fmaf_rn(q1.y, inv.z, -oi.z);
+        const float bx1 = __fmaf_rn(q1.w, ainv.x, pa_ray.x), bz1 = __fmaf_rn(q2.w, ainv.z, pa_ray.z);
+        const float tn0 = fmaxf(fmaxf(ax0 - bx0, az0 - bz0), oi.y), tf0 = fminf(fminf(ax0 + bx0, az0 + bz0), pa_ray.y);
+        const float tn1 = fmaxf(fmaxf(ax1 - bx1, az1 - bz1), oi.y), tf1 = fminf(fminf(ax1 + bx1, az1 + bz1), pa_ray.y);
+        const bool h0 = tn0 <= tf0, h1 = tn1 <= tf1;
+        const uint32_t c0 = __float_as_uint(q3.z), c1 = __float_as_uint(q3.w);
+        if (h0 && h1)
+        {
+            const bool swap = tn1 < tn0;
+            trav_put(trav, sp * R1_BLOCK + tid, swap ? c0 : c1);
+            ++sp;
+            cur = swap ? c1 : c0;
+        }
+        else if (h0)
+            cur = c0;
+        else if (h1)
+            cur = c1;
+        else if (sp > 0)
+            cur = trav_get(trav, --sp * R1_BLOCK + tid);
+        else
+            cur = R1_BVH_DONE;
+    };
     // The root step outside the loops (r1_bvh.cpp: the root of the reference's scenes is [a leaf of <= 2 pairs that every ray tests | the
     // rest], S.bvh_root_leaf): the lanes that start a walk in this call (cur == 0: no child reference points at the root) test that leaf
     // and then the box of the other child, all of them together and in straight-line code, and go on at the other child.  Same offers, same
     // pruning rule as a visit of node 0 followed by the leaf; one node trip and one leaf trip fewer per ray in the divergent loops below.
     // (the small-scene kernels find the code in the K slot of their LDS copy of node 0 — the trace kernel puts it there, K itself is folded
     //  into the half extents for their trees — instead of holding a scalar register for it through the whole kernel)
-    const uint32_t root_leaf = LN ? __float_as_uint(lnodes[3].y) : S.bvh_root_leaf;
+    const uint32_t root_leaf = LN ? __float_as_uint(lnodes[3].y) & 3u : S.bvh_root_leaf; // (bit 2 of the LDS copy's code: a flat tree, see r1_trace_kernel)
     if (root_leaf != 0u && cur == 0u) // (the first condition is wave-uniform)
     {
         const int k = root_leaf == 1u ? 1 : 0; // column of the OTHER child in the node's rows
@@ -998,6 +1045,21 @@ __device__ __forceinline__ void bvh_advance(const R1DeviceScene &S, const V3 o, 
     if (LN && cur == 0u)
         cur = 1u; // a tree without the root step: slot 0 of the 4-wide table is the binary root for the root step's use, the collapsed root is node 1
 #endif
+    // Flat trees: the slab, once per call and after the root step (its leaf has moved `best`, and it tests node 0's box with all three
+    // axes).  A ray whose slab interval is empty, N > F, is done — whatever its walk still holds lies in the slab (every leaf box below
+    // the boxes of the loop does), so every test it could still make would fail: the root step's "N <= F", which holds as well for a walk
+    // carried over from an earlier call.
+    // (the flag is made a scalar: the compiler cannot know that a value from LDS is wave-uniform, and a branch it takes for divergent runs
+    //  both node loops one after the other)
+    if (FLAT_OK && (__builtin_amdgcn_readfirstlane((int)__float_as_uint(lnodes[3].y)) & 4) != 0)
+    {
+        const float a_u = __fmaf_rn(lnodes[7].x, inv.y, -oi.y), b_u = __fmaf_rn(lnodes[7].y, ainv.y, pa_ray.y);
+        const float tyf = a_u + b_u;
+        oi.y = fmaxf(a_u - b_u, 0.0f);
+        // (a compare instead of fminf: the compiler canonicalises both operands of an fminf; a NaN sum — a ray that does not move along y — leaves `best`)
+        pa_ray.y = tyf < best ? tyf : best;
+        cur = oi.y <= pa_ray.y ? cur : R1_BVH_DONE;
+    }
     for (;;)
     {
         const unsigned long long walking = __ballot(cur != R1_BVH_DONE);
@@ -1006,8 +1068,12 @@ __device__ __forceinline__ void bvh_advance(const R1DeviceScene &S, const V3 o, 
         if (CARRY && R1_CARRY_DIV * (uint32_t)__popcll(walking) <= n_alive)
             break; // (n_alive <= 3: never true while a lane walks, so the last walks of a wave run to their end)
         // inner nodes: descend to the nearer child, remember the farther one
-        while (cur < LEAF_BIT) // (R1_BVH_DONE has the leaf bit set in either form: one compare)
-            visit_node();
+        if (FLAT_OK && (__builtin_amdgcn_readfirstlane((int)__float_as_uint(lnodes[3].y)) & 4) != 0)
+            while (cur < LEAF_BIT)
+                visit_flat();
+        else
+            while (cur < LEAF_BIT) // (R1_BVH_DONE has the leaf bit set in either form: one compare)
+                visit_node();
         if (cur != R1_BVH_DONE)
         {
             // leaf: `cnt` PAIRS of spheres {cx_a cx_b cy_a cy_b} {cz_a cz_b rsq_a rsq_b}; an odd
@@ -1026,6 +1092,8 @@ __device__ __forceinline__ void bvh_advance(const R1DeviceScene &S, const V3 o, 
                 leaf_quad(prims, ids, first + j, take, o, d, best, best_id);
             }
             cur = sp > 0 ? trav_get(trav, --sp * R1_BLOCK + tid) : R1_BVH_DONE;
+            if (FLAT_OK && (__builtin_amdgcn_readfirstlane((int)__float_as_uint(lnodes[3].y)) & 4) != 0)
+                pa_ray.y = best < pa_ray.y ? best : pa_ray.y; // F = min(a_u + b_u, best): best has moved in the leaf, and only down
         }
     }
     tv.cur = cur, tv.sp = sp, tv.best = best, tv.best_id = best_id;
@@ -1887,8 +1955,12 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
         }
         // node 0's K slot (0 for these trees: K is part of the half extents) carries the root step's code, see bvh_advance (written by
         // the thread that copied that row: program order; outside the loop, where the test made the compiler peel and unroll the copy)
+        // (bit 2 of the code: a flat tree, whose y slab sits in node 1's pad slots — A again and a zero in the table, and the node loop fetches
+        //  neither from LDS; r1_bvh.cpp "flat axis", a flat tree has at least two nodes)
         if (LN && tid == 3)
-            ((float *)dst)[13] = __uint_as_float(A.scene.bvh_root_leaf);
+            ((float *)dst)[13] = __uint_as_float(A.scene.bvh_root_leaf | ((!R1_BVH4 && A.scene.bvh_flat_e >= 0.0f) ? 4u : 0u));
+        if (LN && !R1_BVH4 && tid == 7 && A.scene.bvh_flat_e >= 0.0f)
+            ((float *)dst)[28] = A.scene.bvh_flat_m, ((float *)dst)[29] = A.scene.bvh_flat_e;
         if (LN && !BATCH && R1_ENTRY_MODE(MODE) && A.entry_lds) // the primary rays' entry nodes, 16 bits each (all ones: the walk is over after the root step)
             for (uint32_t i = (uint32_t)tid; i < A.entry_lds; i += R1_BLOCK)
                 ((uint16_t *)(dst + A.bvh_lds_f4))[i] = (uint16_t)A.bvh_entry[i];
