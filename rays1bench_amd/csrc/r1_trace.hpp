@@ -49,6 +49,7 @@
 
 #include "r1_device.h"
 #include "r1_grid_dda.h"
+#include "r1_exact_math.h"
 #include "../../include/rays1_seed.h"
 
 #pragma clang fp contract(off)
@@ -117,6 +118,8 @@ __device__ __forceinline__ void fresh_args(R1ArgWords &u)
 // Correctly rounded sqrt / division.  NOT __fsqrt_rn/__fdiv_rn: without
 // OCML_BASIC_ROUNDED_OPERATIONS hipcc maps __fsqrt_rn to the approximate v_sqrt_f32.  Plain
 // sqrtf() and `/` are IEEE under -fhip-fp32-correctly-rounded-divide-sqrt (set in the Makefile).
+// The hit tests take their roots through r1_sqrt_exact (r1_exact_math.h): the same bits from half the instructions wherever no
+// lane of the wave holds a tiny, zero, negative, infinite or NaN input, the compiler's function for the wave otherwise.
 __device__ __forceinline__ float ieee_sqrt(float x) { return __builtin_sqrtf(x); }
 __device__ __forceinline__ float ieee_div(float a, float b) { return a / b; }
 
@@ -211,7 +214,7 @@ __device__ __forceinline__ void exact_test(const f4 e, uint32_t idx, const V3 o,
     const float discr = nb * nb - c;
     if (!(__float_as_uint(discr) >> 31))
     {
-        const float discr_sq = ieee_sqrt(discr);
+        const float discr_sq = r1_sqrt_exact(discr, true); // (the lanes inside this branch vote: the ballot runs under its exec mask)
         float temp = nb - discr_sq;
         if (temp < t_max && temp > 0.001f)
         {
@@ -269,7 +272,7 @@ __device__ __forceinline__ float exact_offer(const f4 e, const V3 o, const V3 d)
     float offer = FLT_MAX;
     if (!(__float_as_uint(discr) >> 31))
     {
-        const float discr_sq = ieee_sqrt(discr);
+        const float discr_sq = r1_sqrt_exact(discr, true); // (the lanes inside this branch vote: the ballot runs under its exec mask)
         const float t1 = nb - discr_sq;
         const float t = (t1 > 0.001f) ? t1 : nb + discr_sq;
         if (t > 0.001f && t < FLT_MAX)
@@ -756,7 +759,8 @@ __device__ __forceinline__ void leaf_quad(const float4 *__restrict__ prims, cons
     // computes on slot 3's numbers and is kept from the update by `have`), and the sphere's index is fetched before its offer is
     // known to count.  The branched form (only lanes with a flagged sphere, the index only for an offer in range) cost seven register
     // moves per trip for the loop-carried best / best_id and two exec-mask regions.
-    while (__ballot(mask != 0u)) // wave-uniform
+    unsigned long long flagged;
+    while ((flagged = __builtin_amdgcn_ballot_w64(mask != 0u)) != 0ull) // wave-uniform
     {
         const bool have = mask != 0u;
         const uint32_t q = (uint32_t)__builtin_ctz(mask | 8u); // the lowest flagged slot; 3 for a lane that has none left
@@ -764,7 +768,7 @@ __device__ __forceinline__ void leaf_quad(const float4 *__restrict__ prims, cons
         const float n_ = q == 0u ? nb[0] : (q == 1u ? nb[1] : (q == 2u ? nb[2] : nb[3]));
         const float d_ = q == 0u ? ds[0] : (q == 1u ? ds[1] : (q == 2u ? ds[2] : ds[3]));
         const uint32_t id = ids[2 * (size_t)first + q];
-        const float root = ieee_sqrt(d_);
+        const float root = r1_sqrt_exact_lanes(d_, flagged); // (a lane without a flagged sphere holds slot 3's discriminant, of any sign: it does not vote)
         const float t1 = n_ - root;
         const float t = (t1 > 0.001f) ? t1 : n_ + root;
         // (bitwise on purpose: && / || become nested exec-mask regions)
