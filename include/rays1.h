@@ -217,6 +217,63 @@ int r1_render_samples(r1_context *ctx, const r1_params *params, uint8_t *rgb_out
  * the accumulator 16 bytes per pixel. */
 int r1_render_pass(r1_context *ctx, const r1_params *params, int32_t first_sample, uint8_t *rgb_out, uint64_t *num_rays_out);
 
+/* Adaptive sampling: the frame is rendered in passes, and a tile stops sampling once its pixels have settled.
+ *
+ * The rule (integer, exact).  Per pixel two fp32 sums, both taken in sample order with plain adds: `all` over the samples
+ * [0, n) and `even` over those of even index in [0, n) — (n + 1) / 2 of them.  Both are quantised as r1_render quantises a
+ * pixel (times (float)(1.0f / count), correctly rounded square root, (uint8)(int)(c * 255.99f)).  Over a tile's pixels inside
+ * the image and the three channels:
+ *     err_max = max |byte_all - byte_even|        err_sum = sum |byte_all - byte_even|
+ *     settled = err_max <= max_delta  and  err_sum * 256 <= mean_delta_q8 * 3 * (pixels of the tile inside the image)
+ * (64-bit products).  max_delta = -1 can never hold: every tile runs to the cap.  max_delta = 255 with mean_delta_q8 = 65280
+ * always holds: every tile stops after the first pass.
+ *
+ * The schedule.  params->spp is the cap (a frame of that spp must be within the limits of r1_render's params).  n_0 = min(min_spp, spp), n_{k+1} = min(n_k + pass_spp, spp).  Pass k traces the
+ * samples [n_{k-1}, n_k) of every tile still active; then every active tile is tested at n_k, and one that is settled or has
+ * reached the cap leaves.  The test is made at the cap too. */
+typedef struct r1_adaptive
+{
+    int32_t min_spp;        /* >= 1: samples every tile gets before its first test              */
+    int32_t pass_spp;       /* >= 1: samples per further pass                                   */
+    int32_t max_delta;      /* -1 .. 255                                                        */
+    int32_t mean_delta_q8;  /* 0 .. 65280: mean |byte_all - byte_even| allowed, in 1/256 bytes  */
+} r1_adaptive;
+
+typedef struct r1_tile_report /* one per tile, tile t = ty * tiles_x + tx */
+{
+    int32_t spp;            /* samples of each of its pixels in the image                        */
+    int32_t settled;        /* 1: the rule held at `spp` (tested at the cap too); 0: it ran into the cap unsettled */
+    uint32_t err_max, err_sum; /* at its last test                                              */
+} r1_tile_report;
+
+typedef struct r1_adaptive_result
+{
+    uint64_t samples;       /* pixel-samples traced: sum over tiles of spp * pixels inside the image */
+    int32_t passes, tiles, tiles_settled, reserved;
+} r1_adaptive_result;
+
+/* Pure arithmetic, no device: validates *opt against *params exactly as r1_render_adaptive does and writes the cumulative
+ * sample counts n_0 < n_1 < ... = params->spp to n_out[0, *count).  R1_EINVAL, with the offending field's name in
+ * r1_last_error, for options out of range, num_shards != 1, a variant r1_render_adaptive refuses, or cap < the number of
+ * passes (*count is set then too); R1_ELIMIT where a pass would exceed the per-launch limits of r1_render_pass, or a tile has
+ * more than 2^22 pixels.  n_out may be NULL (count only), count may be NULL. */
+int r1_adaptive_schedule(const r1_params *params, const r1_adaptive *opt, int32_t *n_out, size_t cap, size_t *count);
+
+/* Renders the frame by that rule and schedule.  Synchronous.  The contract:
+ *   1. every tile's pixels in rgb_out (row-major, width*height*3) equal r1_render with spp = tiles_out[t].spp and otherwise
+ *      equal params, cropped to the tile, byte for byte (a sample's streams depend on (seed, pixel, sample index) only);
+ *   2. *num_rays_out (may be NULL) is the number of color() calls of exactly those samples;
+ *   3. tiles_out (may be NULL; one entry per tile of the frame) is what the rule gives on those samples: it does not depend
+ *      on the kernel variant, the order of the tiles in a launch or the machine.
+ * result_out may be NULL.  Whole frames only (num_shards == 1).  Variants DEFAULT, PREFILTER, BVH and GRID, small and big
+ * scenes; REFERENCE, the diagnostic variants and WAVEFRONT return R1_EINVAL.  Per pass the limits of r1_render_pass apply
+ * (R1_ELIMIT).  The call discards a progressive accumulation of the context as r1_render_pass(first_sample = 0) does and
+ * leaves none behind (r1_render_pass with first_sample > 0 returns R1_EINVAL afterwards); r1_render, r1_render_async,
+ * batches and paths on the same context are undisturbed before and after.  r1_last_launch_info and r1_last_timing describe
+ * the last pass.  Device memory: 16 bytes per sample of the longest pass, 32 bytes per pixel of the padded tiles. */
+int r1_render_adaptive(r1_context *ctx, const r1_params *params, const r1_adaptive *opt, uint8_t *rgb_out, uint64_t *num_rays_out,
+                       r1_tile_report *tiles_out, r1_adaptive_result *result_out);
+
 /* Pipelined form of r1_render — frames in flight whose results land on the HOST.  The reference times
  * dispatch -> pixels + ray count on the host (rayweek1.cpp:848 -> :891) for ONE frame and waits; a caller that
  * renders frame after frame (main's `-n` runs, rayweek1.cpp:969-984) can keep several in flight instead: the call

@@ -9,6 +9,6 @@ reference's interface for the path — `create_small_scene()`, `create_medium_sc
 There is no CPU fallback: if librays1.so or a HIP device is missing, calls raise.
 """
 from .binding import (  # noqa: F401
-    R1Error, Renderer, Scene, Params, RESULT, benchmark, build, create_grid_scene, create_large_scene,
+    R1Error, Renderer, adaptive_schedule, Scene, Params, RESULT, benchmark, build, create_grid_scene, create_large_scene,
     camera_look_at, camera_to_array, orbit_cameras, create_medium_scene, create_small_scene, device_count, lib, lib_path, log_results, make_params, tga_write_rgb24,
 )

@@ -81,6 +81,22 @@ class BvhInfo(C.Structure):
                 ("flat_axis", C.c_int32), ("flat_m", C.c_float), ("flat_e", C.c_float)]
 
 
+class Adaptive(C.Structure):
+    """r1_adaptive: the schedule (min_spp, then pass_spp per pass, up to params.spp) and the stopping rule of r1_render_adaptive."""
+    _fields_ = [("min_spp", C.c_int32), ("pass_spp", C.c_int32), ("max_delta", C.c_int32), ("mean_delta_q8", C.c_int32)]
+
+
+class TileReport(C.Structure):
+    _fields_ = [("spp", C.c_int32), ("settled", C.c_int32), ("err_max", C.c_uint32), ("err_sum", C.c_uint32)]
+
+
+class AdaptiveResult(C.Structure):
+    _fields_ = [("samples", C.c_uint64), ("passes", C.c_int32), ("tiles", C.c_int32), ("tiles_settled", C.c_int32), ("reserved", C.c_int32)]
+
+
+TILE_REPORT_DTYPE = np.dtype([("spp", np.int32), ("settled", np.int32), ("err_max", np.uint32), ("err_sum", np.uint32)])
+
+
 def make_params(width, height, spp, seed=10001, max_bounces=50, tile_w=32, tile_h=32, shard=0, num_shards=1, variant=0):
     return Params(width, height, spp, max_bounces, seed, tile_w, tile_h, shard, num_shards, variant)
 
@@ -127,6 +143,8 @@ SYMBOLS = [
     ("r1_render", C.c_int, [_ctx, C.POINTER(Params), _u8p, _u64p, _dblp]),
     ("r1_render_samples", C.c_int, [_ctx, C.POINTER(Params), _u8p, _u64p, _f32p]),
     ("r1_render_pass", C.c_int, [_ctx, C.POINTER(Params), C.c_int32, _u8p, _u64p]),
+    ("r1_adaptive_schedule", C.c_int, [C.POINTER(Params), C.POINTER(Adaptive), _i32p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("r1_render_adaptive", C.c_int, [_ctx, C.POINTER(Params), C.POINTER(Adaptive), _u8p, _u64p, C.POINTER(TileReport), C.POINTER(AdaptiveResult)]),
     ("r1_tile_count", C.c_int, [C.POINTER(Params), _i32p, _i32p]),
     ("r1_shard_block_bytes", C.c_size_t, [C.POINTER(Params)]),
     ("r1_shard_record_bytes", C.c_size_t, [C.POINTER(Params)]),
@@ -299,6 +317,16 @@ def create_large_scene(width=1280, height=720):
     return Scene(SCENE_LARGE, width, height)
 
 
+def adaptive_schedule(params, min_spp, pass_spp, max_delta=-1, mean_delta_q8=0):
+    """r1_adaptive_schedule: the cumulative sample counts after every pass of r1_render_adaptive (raises R1Error as that call would)."""
+    opt = Adaptive(min_spp, pass_spp, max_delta, mean_delta_q8)
+    n = C.c_size_t()
+    _check(lib().r1_adaptive_schedule(C.byref(params), C.byref(opt), None, 0, C.byref(n)))
+    out = (C.c_int32 * n.value)()
+    _check(lib().r1_adaptive_schedule(C.byref(params), C.byref(opt), out, n.value, C.byref(n)))
+    return list(out)
+
+
 def create_grid_scene(width, height, grid_w, grid_h):
     return Scene(SCENE_GRID, width, height, grid_w, grid_h)
 
@@ -346,6 +374,21 @@ class Renderer:
         rays = C.c_uint64()
         _check(lib().r1_render_pass(self._c, C.byref(params), first_sample, img.ctypes.data_as(_u8p) if image else None, C.byref(rays)))
         return img, int(rays.value)
+
+    def render_adaptive(self, params, min_spp, pass_spp, max_delta, mean_delta_q8, out=None):
+        """r1_render_adaptive (params.spp is the cap).  Returns (image, ray count, the tiles' reports as a structured array — fields spp,
+        settled, err_max, err_sum; tile t = ty * tiles_x + tx —, {"samples", "passes", "tiles", "tiles_settled"}).  `out`: a uint8 array
+        of height x width x 3 to render into (page-locked memory, for instance)."""
+        img = np.zeros((params.height, params.width, 3), np.uint8) if out is None else out
+        opt = Adaptive(min_spp, pass_spp, max_delta, mean_delta_q8)
+        total = C.c_int32()
+        _check(lib().r1_tile_count(C.byref(params), C.byref(total), None))
+        tiles = np.zeros(total.value, TILE_REPORT_DTYPE)
+        rays, res = C.c_uint64(), AdaptiveResult()
+        _check(lib().r1_render_adaptive(self._c, C.byref(params), C.byref(opt), img.ctypes.data_as(_u8p), C.byref(rays),
+                                        tiles.ctypes.data_as(C.POINTER(TileReport)), C.byref(res)))
+        return img, int(rays.value), tiles, {"samples": int(res.samples), "passes": int(res.passes), "tiles": int(res.tiles),
+                                            "tiles_settled": int(res.tiles_settled)}
 
     def render_async(self, params, host_frame, stream_ptr=None):
         """r1_render_async: enqueue one frame (throughput kernels) whose pixels + ray count land in `host_frame`

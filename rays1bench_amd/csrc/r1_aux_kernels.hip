@@ -234,6 +234,124 @@ __global__ void __launch_bounds__(256) r1_accum_kernel(const R1AccumArgs A)
     }
 }
 
+// ============================================================================================
+// Adaptive sampling (r1_render_adaptive): in place of r1_accum_kernel after a pass over listed tiles.  Workgroup j serves list position j,
+// i.e. tile list[j]: per pixel the `all` accumulator plus the pass's records in sample order, the `even` accumulator plus those of even
+// GLOBAL sample index, both stored back (indexed by tile, so that they survive the list shrinking) and quantised as the resolve does; the
+// `all` bytes go into the image; |byte_all - byte_even| over the tile's pixels inside the image and the three channels is reduced to its
+// maximum and its sum — integers, so the order of the reduction cannot matter — and one lane tests the rule and writes the tile's report.
+// ============================================================================================
+__global__ void __launch_bounds__(256) r1_adapt_accum_kernel(const R1AdaptArgs A)
+{
+    if (blockIdx.x == 0 && A.rays_src)
+    {
+        // the pass's ray count (the trace kernel's), then the counter block zeroed for the next launch: as r1_resolve_kernel
+        if (threadIdx.x == 0)
+            *A.rays_dst = *A.rays_src;
+        __syncthreads();
+        if (A.reset)
+            ((uint4 *)A.reset)[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
+    }
+    __shared__ uint32_t s_max[4], s_sum[4];
+    const uint32_t tile_px = (uint32_t)(A.tile_w * A.tile_h);
+    for (uint32_t j = blockIdx.x; j < A.n_listed; j += gridDim.x)
+    {
+        const uint32_t tile = A.list[j];
+        const int x0 = (int)(tile % (uint32_t)A.tiles_x) * A.tile_w;
+        const int y0 = (int)(tile / (uint32_t)A.tiles_x) * A.tile_h;
+        const int tw = min(A.tile_w, A.width - x0);
+        const int th = min(A.tile_h, A.height - y0);
+        uint32_t emax = 0, esum = 0;
+        for (uint32_t pix = threadIdx.x; pix < tile_px; pix += blockDim.x)
+        {
+            const int ly = (int)(pix / (uint32_t)A.tile_w);
+            const int lx = (int)(pix - (uint32_t)ly * (uint32_t)A.tile_w);
+            if (lx >= tw || ly >= th)
+                continue; // void slots of an edge tile
+            float4 *const pa = A.all + (size_t)tile * tile_px + pix, *const pe = A.even + (size_t)tile * tile_px + pix;
+            float ar = 0, ag = 0, ab = 0, er = 0, eg = 0, eb = 0;
+            if (A.first_sample)
+            {
+                const float4 a = *pa, e = *pe;
+                ar = a.x, ag = a.y, ab = a.z, er = e.x, eg = e.y, eb = e.z;
+            }
+            const float4 *s = A.samples + ((size_t)j * (uint32_t)A.spp) * tile_px + pix; // [list position][sample][pixel]
+            for (int i = 0; i < A.spp; ++i)
+            {
+                const float4 v = s[(size_t)i * tile_px];
+                ar += v.x, ag += v.y, ab += v.z; // col += color(...) rayweek1.cpp:762
+                if (((A.first_sample + (uint32_t)i) & 1u) == 0u)
+                    er += v.x, eg += v.y, eb += v.z;
+            }
+            *pa = make_float4(ar, ag, ab, 0.0f);
+            *pe = make_float4(er, eg, eb, 0.0f);
+            uint8_t r, g, b, r2, g2, b2;
+            quantise_pixel(ar, ag, ab, A.inv_all, r, g, b);
+            quantise_pixel(er, eg, eb, A.inv_even, r2, g2, b2);
+            uint8_t *const o = A.out + ((size_t)(y0 + ly) * A.width + (x0 + lx)) * 3;
+            o[0] = r, o[1] = g, o[2] = b;
+            const uint32_t dr = (uint32_t)abs((int)r - (int)r2), dg = (uint32_t)abs((int)g - (int)g2), db = (uint32_t)abs((int)b - (int)b2);
+            emax = max(emax, max(dr, max(dg, db)));
+            esum += dr + dg + db;
+        }
+        for (int off = 32; off > 0; off >>= 1)
+        {
+            emax = max(emax, (uint32_t)__shfl_down(emax, off, 64));
+            esum += __shfl_down(esum, off, 64);
+        }
+        if ((threadIdx.x & 63u) == 0)
+            s_max[threadIdx.x >> 6] = emax, s_sum[threadIdx.x >> 6] = esum;
+        __syncthreads();
+        if (threadIdx.x == 0)
+        {
+            emax = max(max(s_max[0], s_max[1]), max(s_max[2], s_max[3]));
+            esum = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
+            const bool settled = (int32_t)emax <= A.max_delta &&
+                                 (unsigned long long)esum * 256ull <= (unsigned long long)A.mean_delta_q8 * 3ull * (unsigned long long)(tw * th);
+            R1TileReport rp;
+            rp.spp = (int32_t)A.first_sample + A.spp, rp.settled = settled ? 1 : 0, rp.err_max = emax, rp.err_sum = esum;
+            A.report[tile] = rp;
+        }
+        __syncthreads();
+    }
+}
+
+// The next pass's list: the tiles of this pass's list that are still active — not settled, and (`at_cap` == 0) not at the cap — in the
+// order they had, which is ascending; their number goes to *count_out (a page-locked host word, or device memory).  One workgroup: a wave
+// places its tiles by ballot + prefix popcount, the four waves through LDS.  cur == null: every tile of the frame, in order (the first pass).
+__global__ void __launch_bounds__(256) r1_adapt_compact_kernel(const uint32_t *cur, uint32_t n_cur, const R1TileReport *report, uint32_t at_cap,
+                                                               uint32_t *next, uint32_t *count_out)
+{
+    __shared__ uint32_t s_cnt[4];
+    uint32_t base = 0;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    for (uint32_t i0 = 0; i0 < n_cur; i0 += 256u)
+    {
+        const uint32_t i = i0 + threadIdx.x;
+        uint32_t tile = 0;
+        bool keep = false;
+        if (i < n_cur)
+        {
+            tile = cur ? cur[i] : i;
+            keep = cur ? (!at_cap && report[tile].settled == 0) : true;
+        }
+        const unsigned long long m = __ballot(keep);
+        if (lane == 0)
+            s_cnt[wave] = (uint32_t)__popcll(m);
+        __syncthreads();
+        uint32_t before = 0;
+        for (uint32_t w = 0; w < wave; ++w)
+            before += s_cnt[w];
+        const uint32_t total = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+        if (keep)
+            next[base + before + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = tile;
+        base += total;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0)
+        *count_out = base;
+}
+
 // Frame batches: frame f's ray count = the sum of the partial sums the resolve launch left per (tile, workgroup column);
 // one workgroup per frame; the count goes next to the frame's pixels (out + f * out_stride + rays_offset).
 __global__ void __launch_bounds__(256)
@@ -393,6 +511,8 @@ extern "C" int r1_trace_mode(int variant, int big, int wanted)
 {
     if (wanted == 4) // progressive passes: the product variants' MODE 4 builds (r1_pass_kernel); none of the diagnostic builds
         return variant == 1 || variant == 2 || variant == 4 || variant == 7 ? 4 : -1;
+    if (wanted == 6) // adaptive sampling: the MODE 6 builds (r1_adaptive_kernel) of the tree, the grouped sweep and the grid
+        return variant == 2 || variant == 4 || variant == 7 ? 6 : -1;
     if (variant == 1)
         return 0;
     if (variant == 3 || variant == 5 || variant == 8)
@@ -416,10 +536,10 @@ extern "C" hipError_t r1_launch_trace(const R1TraceArgs *args, int variant, int 
     if (mode != r1_trace_mode(variant, big_in, mode))
         return hipErrorInvalidValue; // the caller sizes its arguments by the mode: it must be the one that is built
     const int batch = args->batch != nullptr; // frame batches: the MODE 3 build of the throughput kernels (variants 2, 4 and 7 only)
-    if (batch && mode != 4 && (mode != 0 || (variant != 2 && variant != 4 && variant != 7)))
+    if (batch && mode != 4 && mode != 6 && (mode != 0 || (variant != 2 && variant != 4 && variant != 7)))
         return hipErrorInvalidValue;
-    if (mode == 4 && !batch)
-        return hipErrorInvalidValue; // (a pass reads its first sample through args->batch)
+    if ((mode == 4 || mode == 6) && !batch)
+        return hipErrorInvalidValue; // (a pass reads its first sample, a listed pass its tile list too, through args->batch)
     if (path && (!batch || mode != 0))
         return hipErrorInvalidValue; // (batches only, and so variants 2, 4 and 7 only)
     if (variant == 3 && big)
@@ -494,6 +614,21 @@ extern "C" hipError_t r1_launch_accum(const R1AccumArgs *args, hipStream_t strea
     const int bx = (args->tile_w * args->tile_h + 255) / 256;
     const int by = (int)(args->n_local_tiles < 65535u ? args->n_local_tiles : 65535u);
     hipLaunchKernelGGL(r1_accum_kernel, dim3(bx, by), dim3(256), 0, stream, *args);
+    return hipGetLastError();
+}
+
+// one workgroup per listed tile (at most 65535, each walking list positions a grid apart), then the next pass's list
+extern "C" hipError_t r1_launch_adapt_accum(const R1AdaptArgs *args, hipStream_t stream)
+{
+    const int bx = (int)(args->n_listed < 65535u ? args->n_listed : 65535u);
+    hipLaunchKernelGGL(r1_adapt_accum_kernel, dim3(bx), dim3(256), 0, stream, *args);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t r1_launch_adapt_compact(const uint32_t *cur, uint32_t n_cur, const R1TileReport *report, uint32_t at_cap, uint32_t *next,
+                                              uint32_t *count_out, hipStream_t stream)
+{
+    hipLaunchKernelGGL(r1_adapt_compact_kernel, dim3(1), dim3(256), 0, stream, cur, n_cur, report, at_cap, next, count_out);
     return hipGetLastError();
 }
 

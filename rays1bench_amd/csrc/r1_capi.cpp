@@ -24,9 +24,12 @@
 #include "r1_grid.h"
 
 extern "C" hipError_t r1_launch_trace(const R1TraceArgs *args, int variant, int big, int mode, int path, int blocks, size_t grid_lds, hipStream_t stream);
-extern "C" int r1_trace_mode(int variant, int big, int wanted); // 0 samples + one queue, 1 latency, 2 pixel, 4 pass: what is built for (variant, big)
+extern "C" int r1_trace_mode(int variant, int big, int wanted); // 0 samples + one queue, 1 latency, 2 pixel, 4 pass, 6 listed pass: what is built for (variant, big)
 extern "C" hipError_t r1_launch_resolve(const R1ResolveArgs *args, int max_rows, hipStream_t stream);
 extern "C" hipError_t r1_launch_accum(const R1AccumArgs *args, hipStream_t stream);
+extern "C" hipError_t r1_launch_adapt_accum(const R1AdaptArgs *args, hipStream_t stream);
+extern "C" hipError_t r1_launch_adapt_compact(const uint32_t *cur, uint32_t n_cur, const R1TileReport *report, uint32_t at_cap, uint32_t *next, uint32_t *count_out,
+                                              hipStream_t stream);
 extern "C" hipError_t r1_launch_wavefront(R1WaveArgs *w, int blocks, hipStream_t stream);
 extern "C" hipError_t r1_launch_land_arm(uint32_t *tile_cnt, unsigned long long *frame_rays, uint32_t *frame_left, uint32_t n_frames, uint32_t n_local_tiles,
                                          int width, int height, int spp, int tile_w, int tile_h, int tiles_x, int shard, int num_shards, hipStream_t stream);
@@ -165,7 +168,7 @@ struct r1_context
     unsigned long long *host_word = nullptr, *host_word_dev = nullptr;
     int default_variant = 4;    // what R1_VARIANT_DEFAULT resolves to for the scene in the context (r1_set_scene): synchronous frames
     int default_variant_tp = 4; // ... and frames in flight (the throughput kernels: measured apart, the two kernel families do not rank alike)
-    int occupancy[160] = {0}; // [variant + 16 * big + 32 * mode]
+    int occupancy[224] = {0}; // [variant + 16 * big + 32 * mode]
     bool pixel_mode = false; // r1_set_pixel_mode
     DevBuf gstack; // blocks per CU of the trace kernel, by variant
     // per-tile entry nodes for primary rays (R1_ENTRY): the tree's nodes on the host, the device table, what it was computed for
@@ -184,6 +187,10 @@ struct r1_context
     r1_params pass_key;        // the params that started it (spp: that pass's)
     int32_t pass_samples = 0;
     uint64_t pass_rays = 0;    // color() calls of those samples
+    // adaptive sampling (r1_render_adaptive): `accum` is its `all` accumulator, indexed by tile of the frame as accum_even is
+    DevBuf accum_even;         // [tile][pixel of the padded tile] the sums over the samples of even global index
+    DevBuf adapt_list;         // two tile lists of a frame's tiles each (this pass's, the next one's), then the next one's length
+    DevBuf adapt_report;       // [tile] R1TileReport
 
     r1_launch_info info;
 };
@@ -297,7 +304,7 @@ extern "C" void r1_destroy(r1_context *c)
     release(c->bvh_nodes), release(c->bvh_prims), release(c->bvh_ids), release(c->grid_tab), release(c->grid_out), release(c->grid_dev), release(c->grid_tab32), release(c->grid_dev32);
     release(c->wf_paths), release(c->wf_hits), release(c->wf_queue), release(c->wf_counts);
     release(c->bvh_wide), release(c->bvh_entry), release(c->land_spill), release(c->gstack), release(c->counters), release(c->samples), release(c->image), release(c->batch_rays);
-    release(c->wave_log), release(c->accum), release(c->path_cams);
+    release(c->wave_log), release(c->accum), release(c->path_cams), release(c->accum_even), release(c->adapt_list), release(c->adapt_report);
     if (c->host_word)
         (void)hipHostFree(c->host_word);
     for (hipEvent_t e : c->ring)
@@ -1070,10 +1077,15 @@ struct Landing
 
 // A progressive pass (r1_render_pass): samples [first_sample, first_sample + spp) traced by the MODE 4 kernels, then r1_accum_kernel instead of
 // the resolve launch.  d_out of enqueue_frame receives the preview unless `image` is false.
+// A pass of r1_render_adaptive has a tile list: the launch's tiles are list[0, n_listed) of the frame's, traced by the MODE 6 kernels and summed
+// and tested by r1_adapt_accum_kernel (accumulators and reports: the context's, indexed by tile of the frame).
 struct Pass
 {
     int32_t first_sample = 0;
     bool image = true;
+    const uint32_t *list = nullptr; // device memory
+    uint32_t n_listed = 0;
+    const r1_adaptive *rule = nullptr;
 };
 
 // device address of page-locked host memory (r1_host_alloc, hipHostMalloc, hipHostRegister), or null for anything else
@@ -1193,7 +1205,16 @@ static int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int blo
         return rc;
     if ((rc = ensure_counters(c, p, n_frames)))
         return rc;
-    if (pass && (rc = ensure(c->accum, (size_t)c->n_local_tiles * p->tile_w * p->tile_h * 16)))
+    const bool listed = pass && pass->list;
+    if (listed)
+    {
+        // a listed pass has the list's length as its tile count (grid size, queue length and record buffer follow from it below); the
+        // cached tiling no longer describes the params it is kept under, so the next call derives its own
+        c->n_local_tiles = pass->n_listed;
+        c->total_samples = c->full * pass->n_listed;
+        c->tile_key_valid = false;
+    }
+    if (pass && !listed && (rc = ensure(c->accum, (size_t)c->n_local_tiles * p->tile_w * p->tile_h * 16)))
         return rc;
     if (!d_rays)
         d_rays = (char *)c->counters.p + R1_COUNTER_BYTES;
@@ -1208,7 +1229,7 @@ static int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int blo
                             (grid && (!c->grid_small || (throughput_mode && c->pixel_mode)))) ? 1 : 0;
     static const int tp_mode_env = (int)r1_knob("R1_TP_MODE", -1); // tuning experiments
     const int tp_mode = c->pixel_mode ? 2 : (tp_mode_env >= 0 && tp_mode_env <= 2 ? tp_mode_env : 0);
-    const int mode = variant == 6 ? 0 : r1_trace_mode(variant, big_scene_, pass ? 4 : (throughput_mode ? tp_mode : 1));
+    const int mode = variant == 6 ? 0 : r1_trace_mode(variant, big_scene_, pass ? (listed ? 6 : 4) : (throughput_mode ? tp_mode : 1));
     if (mode < 0)
     {
         r1_set_error("variant %d has no progressive-pass build", p->variant);
@@ -1325,6 +1346,7 @@ static int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int blo
         R1PassArgs pa;
         memset(&pa, 0, sizeof(pa));
         pa.first_sample = (uint32_t)pass->first_sample;
+        pa.list = pass->list;
         static_assert(sizeof(R1PassArgs) == 24, "r1_launch_put6 writes the six words of R1PassArgs");
         c->batch_args_slot = (c->batch_args_slot + 1) & 7;
         memset(&c->batch_args_last, 0, sizeof(c->batch_args_last));
@@ -1345,7 +1367,7 @@ static int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int blo
         a.coop_lanes = coop_env >= 0 ? (uint32_t)coop_env : R1_COOP_LANES;
     }
     a.bvh_entry = nullptr, a.entry_lds = 0;
-    if (R1_ENTRY && (variant == 4 || variant == 5) && c->bvh_root_leaf && c->n_local_tiles)
+    if (R1_ENTRY && (variant == 4 || variant == 5) && c->bvh_root_leaf && c->n_local_tiles && !listed) // (a listed pass: MODE 6 looks no entry up, and its tiles are not the table's)
     {
         // per-tile entry nodes of the primary rays (compute_entries): once per (scene, camera, tiling, frames of the launch, reference form)
         const int form = big_scene_ ? 2 : 1;
@@ -1473,7 +1495,7 @@ static int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int blo
     }
     if (mode == 1 && land)
         a.chunk_max = a.chunk_min = 64u; // (the XCDs' cursors hand out the wave-fulls: eight lines instead of one, no sub-queues)
-    else if (mode == 1 || (mode == 4 && !big_scene_))
+    else if (mode == 1 || ((mode == 4 || mode == 6) && !big_scene_))
     {
         static const int nq_env = (int)r1_knob("R1_NQ", 0), ch_env = (int)r1_knob("R1_CHUNK", 0);
         long long nq = nq_env > 0 ? nq_env : R1_SUBQUEUES;
@@ -1656,7 +1678,27 @@ static int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int blo
         r.reset = (uint32_t *)c->counters.p;
     }
     static const int resolve_rows = (int)r1_knob("R1_RESOLVE_ROWS", R1_RESOLVE_ROWS_TP); // tuning experiments
-    if (pass && c->n_local_tiles)
+    if (listed && c->n_local_tiles)
+    {
+        // adaptive sampling: the records go into the listed tiles' two accumulators, their `all` bytes into d_out, and every listed tile is tested
+        const int32_t n = pass->first_sample + p->spp;
+        R1AdaptArgs ad;
+        memset(&ad, 0, sizeof(ad));
+        ad.samples = (const float4 *)c->samples.p;
+        ad.list = pass->list;
+        ad.all = (float4 *)c->accum.p, ad.even = (float4 *)c->accum_even.p;
+        ad.out = (uint8_t *)d_out;
+        ad.report = (R1TileReport *)c->adapt_report.p;
+        ad.width = p->width, ad.height = p->height, ad.spp = p->spp;
+        ad.tile_w = p->tile_w, ad.tile_h = p->tile_h, ad.tiles_x = a.tiles_x;
+        ad.n_listed = pass->n_listed;
+        ad.first_sample = (uint32_t)pass->first_sample;
+        ad.inv_all = (float)(1.0f / n), ad.inv_even = (float)(1.0f / ((n + 1) / 2)); // rayweek1.cpp:765 at the samples each accumulator holds
+        ad.max_delta = pass->rule->max_delta, ad.mean_delta_q8 = (uint32_t)pass->rule->mean_delta_q8;
+        ad.rays_src = r.rays_src, ad.rays_dst = r.rays_dst, ad.reset = r.reset;
+        R1_HIP(r1_launch_adapt_accum(&ad, st));
+    }
+    else if (pass && c->n_local_tiles)
     {
         // progressive pass: the records go into the accumulator, and the preview of samples [0, first_sample + spp) into d_out
         R1AccumArgs ac;
@@ -1922,6 +1964,181 @@ extern "C" int r1_render_pass(r1_context *c, const r1_params *p, int32_t first_s
     c->pass_valid = true;
     if (num_rays_out)
         *num_rays_out = c->pass_rays;
+    return R1_OK;
+}
+
+// ---- adaptive sampling --------------------------------------------------------------
+static bool adaptive_variant(int v) { return v == R1_VARIANT_DEFAULT || v == R1_VARIANT_PREFILTER || v == R1_VARIANT_BVH || v == R1_VARIANT_GRID; }
+
+// The one place the options of r1_render_adaptive are validated: the cumulative sample counts after every pass.
+extern "C" int r1_adaptive_schedule(const r1_params *p, const r1_adaptive *o, int32_t *n_out, size_t cap, size_t *count)
+{
+    if (!p || !o || (!n_out && !count))
+    {
+        r1_set_error("r1_adaptive_schedule: null argument");
+        return R1_EINVAL;
+    }
+    int rc = r1_params_check(p);
+    if (rc)
+        return rc;
+    if (p->num_shards != 1)
+    {
+        r1_set_error("adaptive sampling renders whole frames (num_shards == 1, not %d)", p->num_shards);
+        return R1_EINVAL;
+    }
+    if (!adaptive_variant(p->variant))
+    {
+        r1_set_error("adaptive sampling: variant %d (the reference form, a diagnostic build or the wavefront variant) has no listed-tile build", p->variant);
+        return R1_EINVAL;
+    }
+    if (o->min_spp < 1)
+    {
+        r1_set_error("adaptive sampling: min_spp %d is not >= 1", o->min_spp);
+        return R1_EINVAL;
+    }
+    if (o->pass_spp < 1)
+    {
+        r1_set_error("adaptive sampling: pass_spp %d is not >= 1", o->pass_spp);
+        return R1_EINVAL;
+    }
+    if (o->max_delta < -1 || o->max_delta > 255)
+    {
+        r1_set_error("adaptive sampling: max_delta %d is not within [-1, 255]", o->max_delta);
+        return R1_EINVAL;
+    }
+    if (o->mean_delta_q8 < 0 || o->mean_delta_q8 > 65280)
+    {
+        r1_set_error("adaptive sampling: mean_delta_q8 %d is not within [0, 65280]", o->mean_delta_q8);
+        return R1_EINVAL;
+    }
+    int32_t tiles = 0;
+    if ((rc = r1_tile_count(p, &tiles, nullptr)))
+        return rc;
+    const int32_t n0 = o->min_spp < p->spp ? o->min_spp : p->spp;
+    const int32_t longest = std::max(n0, std::min(o->pass_spp, p->spp - n0)); // samples of the longest pass
+    if ((uint64_t)p->tile_w * p->tile_h * (uint64_t)longest * (uint64_t)tiles >= ((uint64_t)1 << 31))
+    {
+        r1_set_error("a pass of %dx%dx%d with %dx%d tiles exceeds 2^31 sample slots per launch", p->width, p->height, longest, p->tile_w, p->tile_h);
+        return R1_ELIMIT;
+    }
+    if ((uint64_t)p->tile_w * p->tile_h > ((uint64_t)1 << 22))
+    {
+        r1_set_error("adaptive sampling: tiles of %dx%d pixels exceed 2^22 (a tile's err_sum is a 32-bit sum of byte differences)", p->tile_w, p->tile_h);
+        return R1_ELIMIT;
+    }
+    const size_t n_pass = 1 + ((size_t)(p->spp - n0) + (size_t)o->pass_spp - 1) / (size_t)o->pass_spp;
+    if (count)
+        *count = n_pass;
+    if (!n_out)
+        return R1_OK;
+    if (cap < n_pass)
+    {
+        r1_set_error("r1_adaptive_schedule: cap %zu, the schedule has %zu passes", cap, n_pass);
+        return R1_EINVAL;
+    }
+    int64_t n = n0;
+    for (size_t k = 0; k < n_pass; ++k, n += o->pass_spp)
+        n_out[k] = (int32_t)std::min<int64_t>(n, p->spp);
+    return R1_OK;
+}
+
+static_assert(sizeof(r1_tile_report) == sizeof(R1TileReport) && sizeof(r1_tile_report) == 16 && sizeof(r1_adaptive_result) == 24, "public structs without padding; the device writes r1_tile_report's layout");
+
+extern "C" int r1_render_adaptive(r1_context *c, const r1_params *p, const r1_adaptive *opt, uint8_t *rgb_out, uint64_t *num_rays_out, r1_tile_report *tiles_out,
+                                  r1_adaptive_result *result_out)
+{
+    if (!c || !p || !opt || !rgb_out)
+    {
+        r1_set_error("r1_render_adaptive: null argument");
+        return R1_EINVAL;
+    }
+    size_t n_pass = 0;
+    int rc = r1_adaptive_schedule(p, opt, nullptr, 0, &n_pass);
+    if (rc)
+        return rc;
+    std::vector<int32_t> sched(n_pass);
+    if ((rc = r1_adaptive_schedule(p, opt, sched.data(), n_pass, nullptr)))
+        return rc;
+    if (!c->have_scene)
+    {
+        r1_set_error("no scene set (call r1_set_scene first)");
+        return R1_EINVAL;
+    }
+    int32_t tiles = 0;
+    if ((rc = r1_tile_count(p, &tiles, nullptr)))
+        return rc;
+    R1_HIP(hipSetDevice(c->device));
+    const size_t img_bytes = (size_t)p->width * p->height * 3;
+    const size_t tile_px = (size_t)p->tile_w * p->tile_h;
+    if ((rc = ensure(c->image, img_bytes + 64)) || (rc = ensure(c->accum, (size_t)tiles * tile_px * 16)) || (rc = ensure(c->accum_even, (size_t)tiles * tile_px * 16)) ||
+        (rc = ensure(c->adapt_list, ((size_t)2 * tiles + 1) * 4)) || (rc = ensure(c->adapt_report, (size_t)tiles * sizeof(R1TileReport))))
+        return rc;
+    c->pass_valid = false; // (the `all` accumulator is r1_render_pass's: an accumulation of the context ends here, as at first_sample 0)
+    const bool direct = c->host_word_dev != nullptr; // ray count and list length straight into the context's page-locked words, as r1_render_pass
+    uint32_t *const lists[2] = {(uint32_t *)c->adapt_list.p, (uint32_t *)c->adapt_list.p + tiles};
+    uint32_t *const d_count = direct ? (uint32_t *)c->host_word_dev + 4 : (uint32_t *)c->adapt_list.p + 2 * (size_t)tiles;
+    R1_HIP(r1_launch_adapt_compact(nullptr, (uint32_t)tiles, (const R1TileReport *)c->adapt_report.p, 0u, lists[0], d_count, c->stream)); // every tile, in order
+    uint32_t m = (uint32_t)tiles;
+    uint64_t rays_sum = 0;
+    int32_t passes = 0;
+    for (size_t k = 0; k < n_pass && m; ++k)
+    {
+        const int32_t first = k ? sched[k - 1] : 0;
+        r1_params pp = *p;
+        pp.spp = sched[k] - first;
+        Pass ps;
+        ps.first_sample = first;
+        ps.list = lists[k & 1], ps.n_listed = m, ps.rule = opt;
+        if ((rc = enqueue_frame(c, &pp, c->image.p, 0, direct ? (void *)c->host_word_dev : nullptr, c->stream, false, nullptr, nullptr, &ps)))
+            return rc;
+        R1_HIP(r1_launch_adapt_compact(lists[k & 1], m, (const R1TileReport *)c->adapt_report.p, sched[k] == p->spp ? 1u : 0u, lists[(k & 1) ^ 1], d_count, c->stream));
+        uint64_t rays = 0;
+        uint32_t next = 0;
+        if (!direct)
+        {
+            R1_HIP(hipMemcpyAsync(&rays, (char *)c->counters.p + R1_COUNTER_BYTES, 8, hipMemcpyDeviceToHost, c->stream));
+            R1_HIP(hipMemcpyAsync(&next, d_count, 4, hipMemcpyDeviceToHost, c->stream));
+        }
+        R1_HIP(hipStreamSynchronize(c->stream));
+        if (direct)
+            rays = *(volatile unsigned long long *)c->host_word, next = ((volatile uint32_t *)c->host_word)[4];
+        rays_sum += rays; // (summed on the host, pass by pass, as r1_render_pass does)
+        ++passes;
+        if (next > m)
+        {
+            r1_set_error("r1_render_adaptive: a pass left %u active tiles of %u", next, m);
+            return R1_EHIP;
+        }
+        m = next;
+    }
+    std::vector<r1_tile_report> local;
+    r1_tile_report *rep = tiles_out;
+    if (!rep)
+    {
+        local.resize((size_t)tiles);
+        rep = local.data();
+    }
+    R1_HIP(hipMemcpyAsync(rep, c->adapt_report.p, (size_t)tiles * sizeof(R1TileReport), hipMemcpyDeviceToHost, c->stream));
+    R1_HIP(hipMemcpyAsync(rgb_out, c->image.p, img_bytes, hipMemcpyDeviceToHost, c->stream));
+    R1_HIP(hipStreamSynchronize(c->stream));
+    if (num_rays_out)
+        *num_rays_out = rays_sum;
+    if (result_out)
+    {
+        const int tiles_x = (p->width + p->tile_w - 1) / p->tile_w;
+        uint64_t samples = 0;
+        int32_t settled = 0;
+        for (int32_t t = 0; t < tiles; ++t)
+        {
+            const int x0 = (t % tiles_x) * p->tile_w, y0 = (t / tiles_x) * p->tile_h;
+            const int tw = p->tile_w < p->width - x0 ? p->tile_w : p->width - x0;
+            const int th = p->tile_h < p->height - y0 ? p->tile_h : p->height - y0;
+            samples += (uint64_t)rep[t].spp * (uint64_t)(tw * th);
+            settled += rep[t].settled ? 1 : 0;
+        }
+        result_out->samples = samples;
+        result_out->passes = passes, result_out->tiles = tiles, result_out->tiles_settled = settled, result_out->reserved = 0;
+    }
     return R1_OK;
 }
 

@@ -152,10 +152,14 @@ struct R1PathArgs
 
 // Progressive passes (r1_render_pass, the MODE 4 builds): the pass's first global sample index, device memory behind R1TraceArgs::batch
 // (null in every single-frame launch).  Six words: written by r1_launch_put6 into a batch-argument slot.
+// Adaptive sampling (r1_render_adaptive, the MODE 6 builds): behind it the pass's tile list — the launch's local tile j is tile list[j] of
+// the frame — device memory; null in a pass of r1_render_pass, whose kernels never read it.
 struct R1PassArgs
 {
     uint32_t first_sample;
-    uint32_t unused[5];
+    uint32_t unused0;
+    const uint32_t *list;
+    uint32_t unused[2];
 };
 
 // What the waves that sum finished tiles need (R1_LAND); by value in the kernel arguments, read when a wave has run out of samples.
@@ -340,6 +344,36 @@ struct R1AccumArgs
     uint32_t n_local_tiles;
     uint32_t fresh;              // 1: the pass starts the accumulation (first_sample == 0): start from 0.0f
     float inv_n;                 // (float)(1.0f / n), n = first_sample + spp
+    // as R1ResolveArgs: publish the pass's ray count, zero the counter block for the next launch
+    const unsigned long long *rays_src;
+    unsigned long long *rays_dst;
+    uint32_t *reset;
+};
+
+// Adaptive sampling (r1_render_adaptive): a tile's report on the device, in the layout of the public r1_tile_report
+struct R1TileReport
+{
+    int32_t spp, settled;
+    uint32_t err_max, err_sum;
+};
+
+// r1_adapt_accum_kernel, in place of r1_accum_kernel after a pass over listed tiles: workgroup j adds the records of list position j to tile
+// list[j]'s two accumulators (every sample; the samples of even global index), quantises both as the resolve does, stores the bytes of the
+// first into the image and tests the tile: err_max / err_sum over |byte_all - byte_even|, all integer.
+struct R1AdaptArgs
+{
+    const float4 *samples;       // the pass's records, [list position][pass-local sample][pixel of the padded tile]
+    const uint32_t *list;        // [n_listed] tiles of the frame
+    float4 *all, *even;          // [tile of the frame][pixel of the padded tile] {r, g, b, 0}
+    uint8_t *out;                // row-major width*height*3
+    R1TileReport *report;        // [tile of the frame]
+    int32_t width, height, spp;  // spp: the pass's samples
+    int32_t tile_w, tile_h, tiles_x;
+    uint32_t n_listed;
+    uint32_t first_sample;       // global index of the pass's first sample (0: the accumulators start from 0.0f)
+    float inv_all, inv_even;     // (float)(1.0f / n), (float)(1.0f / ((n + 1) / 2)), n = first_sample + spp
+    int32_t max_delta;           // the rule: err_max <= max_delta (-1: never) ...
+    uint32_t mean_delta_q8;      // ... and err_sum * 256 <= mean_delta_q8 * 3 * (pixels of the tile inside the image)
     // as R1ResolveArgs: publish the pass's ray count, zero the counter block for the next launch
     const unsigned long long *rays_src;
     unsigned long long *rays_dst;

@@ -1325,10 +1325,13 @@ __device__ __forceinline__ bool tile_pixel(const R1TraceArgs &A, const uint32_t 
 // (tools/kernel_meta.py).  The other form — a loop over the wave's distinct f, the camera through scalar loads, the lanes of that frame
 // masked in — is not kept: hipcc proves `frame == f0` inside the masked arm, addresses the camera by the lane's own f again and hoists
 // start_ray out of the loop, i.e. emits these very loads behind a loop that only builds the address.
-template <bool BATCH = false, bool PASS = false, bool PATH = false>
+// LIST (adaptive sampling, MODE 6): a PASS whose local tile j is tile list[j] of the frame (R1PassArgs::list); the record keeps the list
+// position.  j is a per-lane value (a wave's chunk may straddle tiles), so every lane loads its own entry, as a camera path's lanes do.
+template <bool BATCH = false, bool PASS = false, bool PATH = false, bool LIST = false>
 __device__ __forceinline__ bool start_sample(const R1TraceArgs &A, Path &p, uint32_t k)
 {
     static_assert(!PATH || BATCH, "a camera path is a batch");
+    static_assert(!LIST || (PASS && !BATCH), "a listed pass is a pass");
     const uint32_t j = fastdiv(k, A.div_full); // padded tile, frame-major over the frames of the launch
     const uint32_t r = k - j * A.full;
     const uint32_t pix = fastdiv(r, A.div_spp);
@@ -1344,6 +1347,12 @@ __device__ __forceinline__ bool start_sample(const R1TraceArgs &A, Path &p, uint
         jl = j - f * b[5];
         seed += f * b[1];
         frame = f;
+    }
+    if (LIST)
+    {
+        typedef const uint32_t __attribute__((address_space(1))) *gu32_ptr;
+        const gu32_ptr list = *(const __attribute__((address_space(4))) gu32_ptr *)((const __attribute__((address_space(4))) char *)A.batch + __builtin_offsetof(R1PassArgs, list));
+        jl = list[j];
     }
     int x, y;
     if (!tile_pixel(A, jl, pix, x, y))
@@ -1870,11 +1879,13 @@ struct TraceWaves
 // MODE 5 = a camera path (r1_render_path_async): MODE 3 with one camera per frame, read from a device table where a sample starts.
 // MODE 4 = a progressive pass (r1_render_pass): small scenes as MODE 1, big scenes as MODE 0 without landing; the records take the pass-local
 // sample index, the seeds the global one (start_sample), and r1_accum_kernel sums them into the frame's accumulator.
+// MODE 6 = a pass over listed tiles (r1_render_adaptive): MODE 4 whose local tile j is tile list[j] (start_sample); r1_adapt_accum_kernel sums.
 // (the body of the kernel; r1_trace_kernel and, for the uniform grid, r1_grid_kernel below are its __global__ instances; r1_pass_kernel the MODE 4 ones)
 template <int VARIANT, bool STATS, bool BIG, int MODE>
 __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
 {
-    constexpr bool PASS = MODE == 4;
+    constexpr bool LISTED = MODE == 6;
+    constexpr bool PASS = MODE == 4 || LISTED;
     constexpr bool CPATH = MODE == 5; // MODE 5 = MODE 3 whose frames each have a camera of their own (start_sample)
     constexpr bool LAT = MODE == 1 || (PASS && !BIG), PIX = MODE == 2, BATCH = MODE == 3 || CPATH; // MODE 3 = MODE 0 whose queue spans the frames of a batch
     // tiles resolved inside the kernel: the throughput builds of the tree kernels (frames in flight, MODE 0 / 3); a
@@ -2158,7 +2169,7 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
             if (SPARE)
             {
                 if (!has_spare && rank < avail)
-                    has_spare = start_sample<BATCH, PASS, CPATH>(FA, spare, q_next + rank); // false: void slot, ask again
+                    has_spare = start_sample<BATCH, PASS, CPATH, LISTED>(FA, spare, q_next + rank); // false: void slot, ask again
             }
             else if (!alive && rank < avail)
             {
@@ -2169,7 +2180,7 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
                         start_ray(A, A.cam, p, (int)(px.xy & 0xFFFFu), (int)(px.xy >> 16), 0u, A.seed);
                 }
                 else
-                    alive = start_sample<BATCH, PASS, CPATH>(FA, p, q_next + rank); // false: void slot, ask again
+                    alive = start_sample<BATCH, PASS, CPATH, LISTED>(FA, p, q_next + rank); // false: void slot, ask again
                 if (VARIANT == 4 && alive)
                     trav_start(tv);
             }
@@ -2410,6 +2421,14 @@ template <int VARIANT, bool BIG>
 __global__ void __launch_bounds__(R1_BLOCK, (TraceWaves<VARIANT, false, BIG, 4>::value)) r1_pass_kernel(const R1TraceArgs A)
 {
     r1_trace_body<VARIANT, false, BIG, 4>(A);
+}
+
+// Adaptive sampling (MODE 6): the same body under a name of its own, for the tree (4), the grouped sweep (2) and the grid (7); built for the
+// waves of its r1_pass_kernel sibling
+template <int VARIANT, bool BIG>
+__global__ void __launch_bounds__(R1_BLOCK, (TraceWaves<VARIANT, false, BIG, 4>::value)) r1_adaptive_kernel(const R1TraceArgs A)
+{
+    r1_trace_body<VARIANT, false, BIG, 6>(A);
 }
 
 // Camera paths (MODE 5): the same body under a name of its own, for the families that have a batch build: tree (4), grouped sweep (2), grid (7)

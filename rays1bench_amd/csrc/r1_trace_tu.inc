@@ -83,7 +83,8 @@
         X(2)
 #endif
 
-// camera paths (MODE 5, r1_render_path_async): r1_path_kernel<V, big> for the family's batch variant
+// camera paths (MODE 5, r1_render_path_async): r1_path_kernel<V, big> for the family's batch variant; adaptive sampling (MODE 6,
+// r1_render_adaptive): r1_adaptive_kernel<V, big> for the same variant
 #if R1_TU_GRID
 #define R1_TU_PATH_VARIANT 7
 #elif R1_TU_TREE
@@ -101,6 +102,12 @@ extern "C" hipError_t R1_CAT(r1_tu_, R1_TU_NAME, _launch)(const R1TraceArgs *arg
         if (variant != R1_TU_PATH_VARIANT || !batch)
             return hipErrorInvalidValue;
         hipLaunchKernelGGL((r1_path_kernel<R1_TU_PATH_VARIANT, R1_TU_BIG>), dim3(blocks), dim3(R1_BLOCK), dyn_lds, stream, *args);
+    }
+    else if (mode == 6)
+    {
+        if (variant != R1_TU_PATH_VARIANT || !batch)
+            return hipErrorInvalidValue;
+        hipLaunchKernelGGL((r1_adaptive_kernel<R1_TU_PATH_VARIANT, R1_TU_BIG>), dim3(blocks), dim3(R1_BLOCK), dyn_lds, stream, *args);
     }
     else if (mode == 4)
     {
@@ -124,6 +131,8 @@ extern "C" hipError_t R1_CAT(r1_tu_, R1_TU_NAME, _occupancy)(int variant, int mo
     {
         R1_TU_PASS(R1_OCC_PASS)
     }
+    if (mode == 6)
+        return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, r1_adaptive_kernel<R1_TU_PATH_VARIANT, R1_TU_BIG>, R1_BLOCK, dyn_lds);
     R1_TU_DISPATCH(R1_OCC)
 #undef R1_OCC_PASS
 #undef R1_OCC

@@ -22,6 +22,9 @@
 // bench.py's one-process-per-GPU form (torch.distributed) gathers the same records.
 // --passes K renders each frame progressively (r1_render_pass): K contiguous passes whose sample counts differ by at most one, pixels
 // asked for on the last pass only; the timed span covers all of them, and the image and ray count are those of the one-launch frame.
+// --adaptive MAXDELTA[,MEANQ8] [--min-spp N] [--pass-spp N] renders each frame through r1_render_adaptive: --spp is the cap, a tile stops
+// sampling once its pixels have settled (include/rays1.h); the report gains one "<scene> adaptive:" line.  MEANQ8 defaults to 65280 (no bound
+// on the mean), --min-spp and --pass-spp to 16.
 // --backend hip (default) | cpu-step1 | cpu-step12: the reference's two single-thread CPU stages
 // (r1_cpu_backends.cpp) behind the same benchmark(), for the README-style table
 // (README.md:38-84).  Named backends of this program only — never a fallback: with --backend hip and no
@@ -69,6 +72,8 @@ static int g_pipeline = 0; // --pipeline FRAMES: after the benchmark() runs, FRA
 static int g_inflight = 20;
 static int g_orbit = 0;    // --orbit FRAMES: after the benchmark() runs, FRAMES frames per scene with the camera turned about the vertical axis through lookat (r1_render_path_async)
 static int g_passes = 0;   // --passes K: every frame in K progressive passes (r1_render_pass); 0 = one r1_render
+static bool g_adaptive = false; // --adaptive: every frame through r1_render_adaptive
+static r1_adaptive g_adapt = {16, 16, 0, 65280};
 int r1cpu_step12_render(const r1_scene *scene, const r1_camera *cam, int width, int height, int spp, int max_bounces, uint8_t *rgb,
                         uint64_t *num_rays); // r1_cpu_backends.cpp
 int r1cpu_step1_render(int scene_kind, const r1_scene *scene, const r1_camera *cam, int width, int height, int spp, uint8_t *rgb,
@@ -198,6 +203,8 @@ RESULT benchmark(Scene *scene, Pix *pixels, bool write_tga, const char *scene_na
     std::vector<uint64_t> rays(nd, 0);
     std::vector<double> dev_s(nd, 0.0);
     std::vector<std::string> errs(nd);
+    r1_adaptive_result adapt_res;
+    memset(&adapt_res, 0, sizeof(adapt_res));
     auto worker = [&](int i) {
         r1_params q = p;
         q.shard = i, q.num_shards = nd;
@@ -215,6 +222,22 @@ RESULT benchmark(Scene *scene, Pix *pixels, bool write_tga, const char *scene_na
                 if (rc == R1_OK && r1_last_timing(g_ctx[i], &trace_ms, &total_ms) == R1_OK)
                     dev_s[i] += total_ms * 1e-3;
                 first += q.spp;
+            }
+        }
+        else if (rc == R1_OK && g_adaptive)
+        {
+            // --adaptive (one device): the device time is the sum over the passes
+            size_t n_pass = 0;
+            rc = r1_adaptive_schedule(&q, &g_adapt, nullptr, 0, &n_pass);
+            if (rc == R1_OK)
+                rc = r1_timing_begin(g_ctx[i], (int32_t)n_pass);
+            if (rc == R1_OK)
+            {
+                rc = r1_render_adaptive(g_ctx[i], &q, &g_adapt, &pixels[0].r, &rays[i], nullptr, &adapt_res);
+                double trace_ms = 0, total_ms = 0;
+                const int rc2 = r1_timing_end(g_ctx[i], &trace_ms, &total_ms, nullptr);
+                dev_s[i] = total_ms * 1e-3;
+                rc = rc != R1_OK ? rc : rc2;
             }
         }
         else if (rc == R1_OK)
@@ -273,6 +296,10 @@ RESULT benchmark(Scene *scene, Pix *pixels, bool write_tga, const char *scene_na
     if (g_passes > 0)
         printf("passes:         %d\n", g_passes);
     printf("device time:    %.3fms (%0.2f mrays/s)\n", device_seconds * 1e3, device_seconds ? result.num_rays / device_seconds / 1e6 : 0.0);
+    if (g_adaptive)
+        printf("%s adaptive: passes %d, tiles settled %d / %d, samples %llu (%.4f of cap x pixels), rays %llu (%.4f of cap x pixels)\n", scene_name,
+               adapt_res.passes, adapt_res.tiles_settled, adapt_res.tiles, (unsigned long long)adapt_res.samples, (double)adapt_res.samples / (double)total_samples,
+               (unsigned long long)result.num_rays, (double)result.num_rays / (double)total_samples);
     printf("\n");
 
     delete scene; // rayweek1.cpp:905
@@ -524,7 +551,7 @@ static int orbit(const char *scene_name, int kind, int frames, bool write_tga)
 int main(int argc, const char *argv[])
 {
     bool write_tga = false;
-    bool passes_given = false, orbit_given = false;
+    bool passes_given = false, orbit_given = false, adapt_fields_ok = true, adapt_sub_given = false;
     int num_runs = 1;
     const static int MAX_NUMS = 32;
     RESULT results[MAX_NUMS];
@@ -569,6 +596,26 @@ int main(int argc, const char *argv[])
             g_passes = atoi(argv[++i]);
             passes_given = true;
         }
+        else if (strcmp(argv[i], "--adaptive") == 0 && i + 1 < argc)
+        {
+            // MAXDELTA[,MEANQ8]
+            g_adaptive = true;
+            const char *v = argv[++i];
+            char *end = nullptr;
+            g_adapt.max_delta = (int32_t)strtol(v, &end, 10);
+            adapt_fields_ok = end != v;
+            if (adapt_fields_ok && *end == ',')
+            {
+                const char *w = end + 1;
+                g_adapt.mean_delta_q8 = (int32_t)strtol(w, &end, 10);
+                adapt_fields_ok = end != w;
+            }
+            adapt_fields_ok = adapt_fields_ok && *end == 0;
+        }
+        else if (strcmp(argv[i], "--min-spp") == 0 && i + 1 < argc)
+            g_adapt.min_spp = atoi(argv[++i]), adapt_sub_given = true;
+        else if (strcmp(argv[i], "--pass-spp") == 0 && i + 1 < argc)
+            g_adapt.pass_spp = atoi(argv[++i]), adapt_sub_given = true;
         else if (strcmp(argv[i], "--backend") == 0 && i + 1 < argc)
         {
             const char *b = argv[++i];
@@ -593,6 +640,15 @@ int main(int argc, const char *argv[])
     if (passes_given && (g_passes < 1 || g_passes > g_spp || g_backend != 0 || g_devices > 1 || g_gather == 1 || g_pipeline > 0))
     {
         fprintf(stderr, "bad --passes %d: needs 1 <= K <= spp (%d), the hip backend, one device (no --gather rccl) and no --pipeline\n", g_passes, g_spp);
+        return 1;
+    }
+    if ((g_adaptive || adapt_sub_given) && (!g_adaptive || !adapt_fields_ok || g_adapt.min_spp < 1 || g_adapt.pass_spp < 1 || g_adapt.max_delta < -1 || g_adapt.max_delta > 255 ||
+                                            g_adapt.mean_delta_q8 < 0 || g_adapt.mean_delta_q8 > 65280 || g_backend != 0 || g_devices > 1 || g_gather == 1 || passes_given ||
+                                            g_pipeline > 0 || orbit_given ||
+                                            !(g_variant == R1_VARIANT_DEFAULT || g_variant == R1_VARIANT_PREFILTER || g_variant == R1_VARIANT_BVH || g_variant == R1_VARIANT_GRID)))
+    {
+        fprintf(stderr, "bad --adaptive MAXDELTA[,MEANQ8] / --min-spp / --pass-spp: needs -1 <= MAXDELTA <= 255, 0 <= MEANQ8 <= 65280, --min-spp and --pass-spp >= 1 "
+                        "(both only with --adaptive), the hip backend, one device (no --gather rccl), --variant 0, 2, 4 or 7, and no --passes, --pipeline or --orbit\n");
         return 1;
     }
 
