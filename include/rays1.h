@@ -466,6 +466,64 @@ int r1_multi_layout(const r1_params *params, int32_t n_devices, int32_t n_frames
 /* Facts for reports: device count, RCCL version code (ncclGetVersion), launch info of the first device. */
 int r1_multi_info(r1_multi *m, int32_t *n_devices, int32_t *rccl_version, r1_launch_info *first_device);
 
+/* ---- ray queries: Hitable::hit for caller-supplied rays --------------------------------- */
+
+/* The contract of all three entry points is the reference's `Hitable::hit(Ray(o, d), 0.001f, t_max, &rec)` (rayweek1.cpp:104-108,
+ * :152-339), bit for bit:
+ *   direction  d is normalised as the Ray constructor does it, d * (1 / sqrt(dot(d, d))), in fp32.
+ *   t_min      color()'s 0.001f, not a parameter (the per-sphere test hard-codes it and the box tree's proof is written for t > 0).
+ *   t_max      strict: a root is accepted only if it is < t_max.  +inf is taken as FLT_MAX; NaN or a value <= 0.001f gives a miss.
+ *   non-finite a ray with a non-finite component in o, or in d after normalisation (a zero direction normalises to NaN), is a miss,
+ *              decided before any walk and identically in all three entry points.
+ * R1_CAST_CLOSEST: `out` is n r1_hit records in ray order: t, the SCENE index of the hit sphere (an index into the r1_scene arrays,
+ * placeholders counted), p = o + t * d_unit (multiply, then add) and n = (p - centre) * inv_radius, as rayweek1.cpp:316-322; a miss is
+ * index = -1, t = FLT_MAX, p = n = 0.  Spheres with inv_radius == 0 are never returned (rayweek1.cpp:291).
+ * R1_CAST_ANY: `out` is n bytes, 1 where R1_CAST_CLOSEST would report a hit, else 0 — the same walk, storing one byte (33 instead of
+ * 64 bytes of memory traffic per ray).  There is no early exit. */
+typedef struct r1_ray
+{
+    float o[3];
+    float t_max;
+    float d[3];
+    uint32_t pad; /* ignored */
+} r1_ray; /* 32 bytes */
+
+typedef struct r1_hit
+{
+    float t;
+    int32_t index;
+    float p[3];
+    float n[3];
+} r1_hit; /* 32 bytes */
+
+enum
+{
+    R1_CAST_CLOSEST = 0,
+    R1_CAST_ANY = 1
+};
+
+/* Rays a single launch of r1_cast_rays covers: that call copies in, casts and copies out R1_CAST_CHUNK rays at a time through a
+ * workspace cached in the context (64 bytes per ray of a chunk: 64 MiB), so device memory stays bounded for any n. */
+#define R1_CAST_CHUNK (1u << 20)
+
+/* Casts n rays from host memory against the scene cached in the context (r1_set_scene) and returns the results on the host.
+ * Synchronous.  variant: R1_VARIANT_DEFAULT / R1_VARIANT_BVH (box tree), R1_VARIANT_GRID (uniform grid, built on first use as a
+ * render builds it; rays whose origin is too far for the grid take the tree walk) or R1_VARIANT_REFERENCE (every active sphere in
+ * index order, the reference's own loop: the on-device cross-check); every other variant returns R1_EINVAL.  All of them return the
+ * same bytes.  Small and big scenes.  R1_EINVAL for a NULL ctx, a mode that is not R1_CAST_*, a variant that casts no rays
+ * (r1_last_error names it) and before the first r1_set_scene; then n == 0 is R1_OK and touches nothing; then R1_EINVAL for NULL
+ * pointers.  A cast changes no state another entry point sees: a progressive
+ * accumulation survives it, r1_last_launch_info / r1_last_timing keep describing the last render, the camera plays no part. */
+int r1_cast_rays(r1_context *ctx, int32_t variant, int32_t mode, const r1_ray *rays, size_t n, void *out);
+
+/* The same over DEVICE memory: enqueues the cast on `hip_stream` (a hipStream_t; NULL = the context's stream) and waits for
+ * nothing.  d_rays (n r1_ray) and d_out (n r1_hit, or n bytes) are device memory, both 16-byte aligned (R1_EINVAL otherwise). */
+int r1_cast_rays_device(r1_context *ctx, int32_t variant, int32_t mode, const void *d_rays, size_t n, void *d_out, void *hip_stream);
+
+/* The same without a device: every ray against every sphere in the reference's arithmetic, on host threads.  For callers without
+ * a GPU at hand, and the checker of the two entry points above (tests/golden/cast_*.bin pin it to the reference's own output). */
+int r1_cast_rays_host(const r1_scene *scene, int32_t mode, const r1_ray *rays, size_t n, void *out);
+
 /* ---- host-side helpers of the drop-in (no GPU needed) ------------------------------ */
 
 /* Shape of the spatial index R1_VARIANT_BVH uses (r1_bvh.cpp; the reference has no such

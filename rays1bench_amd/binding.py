@@ -95,6 +95,11 @@ class AdaptiveResult(C.Structure):
 
 
 TILE_REPORT_DTYPE = np.dtype([("spp", np.int32), ("settled", np.int32), ("err_max", np.uint32), ("err_sum", np.uint32)])
+# r1_ray / r1_hit (32 bytes each) and the modes of the ray queries
+RAY_DTYPE = np.dtype([("o", np.float32, 3), ("t_max", np.float32), ("d", np.float32, 3), ("pad", np.uint32)])
+HIT_DTYPE = np.dtype([("t", np.float32), ("index", np.int32), ("p", np.float32, 3), ("n", np.float32, 3)])
+CAST_CLOSEST, CAST_ANY = 0, 1
+CAST_CHUNK = 1 << 20  # R1_CAST_CHUNK: rays per launch of r1_cast_rays
 
 
 def make_params(width, height, spp, seed=10001, max_bounces=50, tile_w=32, tile_h=32, shard=0, num_shards=1, variant=0):
@@ -189,6 +194,9 @@ SYMBOLS = [
     ("r1_grid_describe", C.c_int, [C.POINTER(CScene), C.POINTER(GridInfo), C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t,
                                    C.POINTER(C.c_uint32), C.c_size_t]),
     ("r1_grid_visit", C.c_int, [C.POINTER(CScene), _f32p, _f32p, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_size_t), _i32p, _f32p, _i32p]),
+    ("r1_cast_rays", C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("r1_cast_rays_device", C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    ("r1_cast_rays_host", C.c_int, [C.POINTER(CScene), C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("r1_tga_write_rgb24", C.c_int, [C.c_char_p, C.c_int32, C.c_int32, _u8p]),
     ("r1_log_results", C.c_int, [C.c_char_p, C.c_char_p, _dblp, _u64p, C.c_int32]),
 ]
@@ -436,6 +444,19 @@ class Renderer:
     def assemble_device_records(self, params, d_records_ptr, d_rgb_ptr, d_total_rays_ptr, stream_ptr=None):
         _check(lib().r1_assemble_device_records(self._c, C.byref(params), C.c_void_p(d_records_ptr), C.c_void_p(d_rgb_ptr),
                                                 C.c_void_p(d_total_rays_ptr), _stream_arg(stream_ptr)))
+
+    def cast_rays(self, rays, mode=CAST_CLOSEST, variant=0):
+        """r1_cast_rays: Hitable::hit for caller-supplied rays, host memory in and out.  `rays`: float32 (n, 8) rows {ox oy oz t_max dx
+        dy dz -} or a RAY_DTYPE array.  Returns a HIT_DTYPE array (CAST_CLOSEST) or a uint8 array (CAST_ANY), in ray order."""
+        rays = _as_rays(rays)
+        out = _cast_out(rays.shape[0], mode)
+        _check(lib().r1_cast_rays(self._c, variant, mode, rays.ctypes.data, rays.shape[0], out.ctypes.data))
+        return out
+
+    def cast_rays_device(self, d_rays_ptr, n, d_out_ptr, mode=CAST_CLOSEST, variant=0, stream=None):
+        """r1_cast_rays_device: the same over device memory (16-byte aligned: n r1_ray in, n r1_hit or n bytes out); enqueues on
+        `stream` and waits for nothing."""
+        _check(lib().r1_cast_rays_device(self._c, variant, mode, C.c_void_p(d_rays_ptr), n, C.c_void_p(d_out_ptr), _stream_arg(stream)))
 
     def set_pixel_mode(self, on):
         _check(lib().r1_set_pixel_mode(self._c, 1 if on else 0))
@@ -686,6 +707,29 @@ def grid_visit(cscene, o, d, cap=1 << 16):
     if n.value > cap:
         return grid_visit(cscene, o, d, int(n.value))
     return pres[:n.value], int(hi.value), float(ht.value), bool(fb.value)
+
+
+def _as_rays(rays):
+    rays = np.asarray(rays)
+    if rays.dtype == RAY_DTYPE and rays.ndim == 1:
+        return np.ascontiguousarray(rays)
+    if rays.dtype == np.float32 and rays.ndim == 2 and rays.shape[1] == 8:
+        return np.ascontiguousarray(rays)
+    raise R1Error(R1_EINVAL, "rays: a float32 (n, 8) array or a RAY_DTYPE array")
+
+
+def _cast_out(n, mode):
+    # (a mode the library refuses still gets a buffer that is large enough for either form: the call reports the error)
+    return np.zeros(n, np.uint8) if mode == CAST_ANY else np.zeros(n, HIT_DTYPE)
+
+
+def cast_rays_host(cscene, rays, mode=CAST_CLOSEST):
+    """r1_cast_rays_host: every ray against every sphere in the reference's arithmetic, on host threads (no device).  Same input and
+    output forms as Renderer.cast_rays."""
+    rays = _as_rays(rays)
+    out = _cast_out(rays.shape[0], mode)
+    _check(lib().r1_cast_rays_host(C.byref(cscene), mode, rays.ctypes.data, rays.shape[0], out.ctypes.data))
+    return out
 
 
 class RESULT:

@@ -41,6 +41,8 @@ extern "C" hipError_t r1_launch_assemble(const void *blocks, void *rgb, int widt
                                          int want_total, hipStream_t stream);
 extern "C" size_t r1_frame_record_bytes(const r1_params *p); // r1_host.cpp
 extern "C" hipError_t r1_trace_occupancy(int variant, int big, int mode, size_t dyn_lds, int *blocks_per_cu);
+extern "C" hipError_t r1_launch_cast(const R1CastArgs *args, int structure, int big, int plain, int blocks, size_t dyn_lds, hipStream_t stream); // r1_cast.hip
+extern "C" hipError_t r1_cast_occupancy(int structure, int big, int plain, size_t dyn_lds, int *blocks_per_cu);
 extern "C" int r1_params_check(const r1_params *p); // r1_host.cpp
 
 // r1_bvh.cpp
@@ -191,6 +193,12 @@ struct r1_context
     DevBuf accum_even;         // [tile][pixel of the padded tile] the sums over the samples of even global index
     DevBuf adapt_list;         // two tile lists of a frame's tiles each (this pass's, the next one's), then the next one's length
     DevBuf adapt_report;       // [tile] R1TileReport
+    // ray queries (r1_cast_rays*): nothing here is read or written by a render
+    DevBuf active_dev;         // active_to_scene on the device, uploaded once per r1_set_scene
+    DevBuf cast_cursors;       // R1_CAST_CURSORS ray cursors, 128 bytes apart, taken in turn
+    uint32_t cast_cursor_next = 0;
+    DevBuf cast_ws;            // r1_cast_rays: one chunk's rays and results (R1_CAST_CHUNK x 64 bytes)
+    int cast_occupancy[8] = {0}; // blocks per CU of the cast kernels, [structure slot * 2 + big]
 
     r1_launch_info info;
 };
@@ -305,6 +313,7 @@ extern "C" void r1_destroy(r1_context *c)
     release(c->wf_paths), release(c->wf_hits), release(c->wf_queue), release(c->wf_counts);
     release(c->bvh_wide), release(c->bvh_entry), release(c->land_spill), release(c->gstack), release(c->counters), release(c->samples), release(c->image), release(c->batch_rays);
     release(c->wave_log), release(c->accum), release(c->path_cams), release(c->accum_even), release(c->adapt_list), release(c->adapt_report);
+    release(c->active_dev), release(c->cast_cursors), release(c->cast_ws);
     if (c->host_word)
         (void)hipHostFree(c->host_word);
     for (hipEvent_t e : c->ring)
@@ -768,6 +777,11 @@ extern "C" int r1_set_scene(r1_context *c, const r1_scene *s, const r1_camera *c
     R1_HIP(hipMemcpyAsync(c->bvh_nodes.p, bvh.nodes.data(), bvh.nodes.size() * 4, hipMemcpyHostToDevice, c->stream));
     R1_HIP(hipMemcpyAsync(c->bvh_prims.p, bvh.prims.data(), bvh.prims.size() * 4, hipMemcpyHostToDevice, c->stream));
     R1_HIP(hipMemcpyAsync(c->bvh_ids.p, bvh.ids.data(), bvh.ids.size() * 4, hipMemcpyHostToDevice, c->stream));
+    // ray queries report SCENE indices: the active spheres' scene indices, once per scene
+    if ((rc = ensure(c->active_dev, (size_t)(na ? na : 1) * 4)))
+        return rc;
+    if (na)
+        R1_HIP(hipMemcpyAsync(c->active_dev.p, c->active_to_scene.data(), (size_t)na * 4, hipMemcpyHostToDevice, c->stream));
     R1_HIP(hipStreamSynchronize(c->stream)); // the host vectors go out of scope
     c->bvh_nodes_host = bvh.nodes;
     c->entry_valid = false;
@@ -799,6 +813,8 @@ extern "C" int r1_set_scene(r1_context *c, const r1_scene *s, const r1_camera *c
     c->bvh_flat_m = bvh.flat_axis == 1 ? bvh.flat_m : 0.0f, c->bvh_flat_e = bvh.flat_axis == 1 ? bvh.flat_e : -1.0f;
     for (int &o : c->occupancy)
         o = 0; // the tree kernels' LDS footprint follows the tree (depth of the traversal stack, size of the node table)
+    for (int &o : c->cast_occupancy)
+        o = 0;
     c->n_groups = ng;
     c->n_multi = n_multi;
 
@@ -2270,6 +2286,153 @@ extern "C" int r1_render_shard_device_batch(r1_context *c, const r1_params *p, i
     Batch b;
     b.n_frames = n_frames, b.seed_stride = seed_stride, b.out_stride = record, b.rays_offset = record - 8;
     return enqueue_frame(c, p, d_records, 1, nullptr, st, true, &b);
+}
+
+// ---- ray queries (include/rays1.h "ray queries", r1_cast.hip) ------------------------------------------------------------
+
+static_assert(sizeof(r1_ray) == 32 && sizeof(r1_hit) == 32, "the cast kernels read and write these layouts as two float4");
+
+// the checks every cast entry point makes before it touches anything; *structure: 4 box tree, 7 uniform grid, 1 reference form
+static int cast_check(const char *who, r1_context *c, int32_t variant, int32_t mode, int *structure)
+{
+    if (!c)
+    {
+        r1_set_error("%s: ctx is NULL", who);
+        return R1_EINVAL;
+    }
+    if (mode != R1_CAST_CLOSEST && mode != R1_CAST_ANY)
+    {
+        r1_set_error("%s: mode %d is neither R1_CAST_CLOSEST nor R1_CAST_ANY", who, mode);
+        return R1_EINVAL;
+    }
+    switch (variant)
+    {
+    case R1_VARIANT_DEFAULT:
+    case R1_VARIANT_BVH: *structure = 4; break;
+    case R1_VARIANT_GRID: *structure = 7; break;
+    case R1_VARIANT_REFERENCE: *structure = 1; break;
+    default:
+        r1_set_error("%s: variant %d casts no rays (DEFAULT, BVH, GRID and REFERENCE do)", who, variant);
+        return R1_EINVAL;
+    }
+    if (!c->have_scene)
+    {
+        r1_set_error("%s: no scene set (call r1_set_scene first)", who);
+        return R1_EINVAL;
+    }
+    return R1_OK;
+}
+
+// Enqueues the cast of n rays (device memory) on `st`; waits for nothing (the first grid cast after r1_set_scene builds the grid, as the
+// first grid render does).  Touches none of the state a render reads: no counter block, no sample records, no launch info, no events.
+static int cast_enqueue(r1_context *c, int structure, int32_t mode, const void *d_rays, size_t n, void *d_out, hipStream_t st)
+{
+    int rc;
+    R1_HIP(hipSetDevice(c->device));
+    if (c->n_active == 0)
+        structure = 1; // (no sphere can be hit: the reference form's loop of zero trips writes the misses; there is no tree to stage)
+    if (structure == 7 && (rc = ensure_grid(c)))
+        return rc;
+    // big-scene kernels: as enqueue_frame chooses them (hit indices beyond 10 bits, a node table too large for LDS or a per-node pad; a grid too large for LDS)
+    const bool big = c->n_active > R1_MAX_ACTIVE_10BIT || (structure == 4 && (c->n_bvh_nodes > R1_NODES_LDS_MAX || c->bvh_pad_local)) ||
+                     (structure == 7 && !c->grid_small);
+    static const int plain_env = (int)r1_knob("R1_CAST_PLAIN", 0); // tuning library only: the plain form of the tree cast (r1_cast.hip), for measuring
+    const int plain = structure == 4 && plain_env ? 1 : 0;
+
+    R1CastArgs a;
+    memset(&a, 0, sizeof(a));
+    a.t.scene.exact = (const float4 *)c->exact.p;
+    a.t.scene.shade = (const float4 *)c->shade.p;
+    a.t.scene.n_active = c->n_active;
+    a.t.scene.bvh_nodes = (const float4 *)c->bvh_nodes.p;
+    a.t.scene.bvh_prims = (const float4 *)c->bvh_prims.p;
+    a.t.scene.bvh_ids = (const uint32_t *)c->bvh_ids.p;
+    for (int k = 0; k < 3; ++k)
+        a.t.scene.bvh_centre[k] = c->bvh_centre[k];
+    a.t.scene.bvh_pad_local = (uint32_t)c->bvh_pad_local;
+    // (the grid's fallback and the plain form walk the tree from its root, read from global memory: no root step)
+    a.t.scene.bvh_root_leaf = (structure == 7 || plain) ? 0u : (uint32_t)c->bvh_root_leaf;
+    a.t.scene.bvh_flat_m = c->bvh_flat_m, a.t.scene.bvh_flat_e = c->bvh_flat_e;
+    a.t.bvh_depth = c->bvh_depth > 0 ? c->bvh_depth : 1;
+    // the workgroups' LDS copy of the node table: all of it for small scenes, the breadth-first top (at least node 0) for big ones
+    a.t.bvh_lds_f4 = (structure != 4 || plain) ? 0u : (!big ? 4u * c->n_bvh_nodes : 4u * std::min<uint32_t>(c->n_bvh_nodes, R1_BVH_TOP_NODES));
+    if (structure == 7)
+        a.t.grid = (const R1GridArgs *)(big ? c->grid_dev32.p : c->grid_dev.p);
+    a.active_to_scene = (const uint32_t *)c->active_dev.p;
+    a.mode = (uint32_t)mode;
+    const size_t dyn_lds = structure == 4 ? (plain ? (size_t)a.t.bvh_depth * R1_BLOCK * 4 : (size_t)a.t.bvh_depth * R1_BLOCK * (big ? 4 : 2) + (size_t)a.t.bvh_lds_f4 * 16)
+                           : structure == 7 ? (size_t)a.t.bvh_depth * R1_BLOCK * 4 + (big ? 0 : (size_t)c->grid_args.lds_bytes)
+                                            : 0;
+    int &occ = c->cast_occupancy[(structure == 4 ? 0 : structure == 7 ? 2 : 4) + (big ? 1 : 0)];
+    if (occ == 0)
+        R1_HIP(r1_cast_occupancy(structure, big ? 1 : 0, plain, dyn_lds, &occ));
+    const int per_cu = occ < 1 ? 1 : (occ > 8 ? 8 : occ);
+    if ((rc = ensure(c->cast_cursors, (size_t)R1_CAST_CURSORS * 128)))
+        return rc;
+    for (size_t at = 0; at < n; at += R1_CAST_LAUNCH_MAX)
+    {
+        const uint32_t m = (uint32_t)std::min<size_t>(n - at, R1_CAST_LAUNCH_MAX);
+        a.rays = (const float4 *)((const char *)d_rays + at * sizeof(r1_ray));
+        a.out = (char *)d_out + at * (mode == R1_CAST_ANY ? 1 : sizeof(r1_hit));
+        a.n = m;
+        // persistent: as many workgroups as the chip holds, fewer where the rays run out; a wave claims 64 .. 256 rays at a time,
+        // about an eighth of its share (the waves that finish first take the rest)
+        const uint32_t blocks = (uint32_t)std::min<size_t>((size_t)c->cus * per_cu, ((size_t)m + R1_BLOCK - 1) / R1_BLOCK);
+        const uint32_t share = m / (blocks * (R1_BLOCK / 64) * 8u);
+        a.claim = std::min(256u, std::max(64u, (share + 63u) & ~63u));
+        a.cursor = (uint32_t *)((char *)c->cast_cursors.p + 128 * (c->cast_cursor_next++ % R1_CAST_CURSORS));
+        R1_HIP(hipMemsetAsync(a.cursor, 0, 4, st));
+        R1_HIP(r1_launch_cast(&a, structure, big ? 1 : 0, plain, (int)blocks, dyn_lds, st));
+    }
+    return R1_OK;
+}
+
+extern "C" int r1_cast_rays_device(r1_context *c, int32_t variant, int32_t mode, const void *d_rays, size_t n, void *d_out, void *hip_stream)
+{
+    int structure = 0;
+    int rc = cast_check("r1_cast_rays_device", c, variant, mode, &structure);
+    if (rc)
+        return rc;
+    if (n == 0)
+        return R1_OK;
+    if (!d_rays || !d_out || ((uintptr_t)d_rays & 15u) || ((uintptr_t)d_out & 15u))
+    {
+        r1_set_error("r1_cast_rays_device: d_rays and d_out must be non-NULL device memory, 16-byte aligned");
+        return R1_EINVAL;
+    }
+    return cast_enqueue(c, structure, mode, d_rays, n, d_out, hip_stream ? (hipStream_t)hip_stream : c->stream);
+}
+
+extern "C" int r1_cast_rays(r1_context *c, int32_t variant, int32_t mode, const r1_ray *rays, size_t n, void *out)
+{
+    int structure = 0;
+    int rc = cast_check("r1_cast_rays", c, variant, mode, &structure);
+    if (rc)
+        return rc;
+    if (n == 0)
+        return R1_OK;
+    if (!rays || !out)
+    {
+        r1_set_error("r1_cast_rays: rays and out must not be NULL with n > 0");
+        return R1_EINVAL;
+    }
+    R1_HIP(hipSetDevice(c->device));
+    // one chunk's rays, then its results (32 bytes per ray each): device memory stays bounded for any n
+    const size_t chunk = std::min<size_t>(n, R1_CAST_CHUNK);
+    if ((rc = ensure(c->cast_ws, chunk * 64)))
+        return rc;
+    char *const d_rays = (char *)c->cast_ws.p, *const d_out = d_rays + chunk * 32;
+    const size_t out_each = mode == R1_CAST_ANY ? 1 : sizeof(r1_hit);
+    for (size_t at = 0; at < n; at += chunk)
+    {
+        const size_t m = std::min(chunk, n - at);
+        R1_HIP(hipMemcpyAsync(d_rays, rays + at, m * sizeof(r1_ray), hipMemcpyHostToDevice, c->stream));
+        if ((rc = cast_enqueue(c, structure, mode, d_rays, m, d_out, c->stream)))
+            return rc;
+        R1_HIP(hipMemcpyAsync((char *)out + at * out_each, d_out, m * out_each, hipMemcpyDeviceToHost, c->stream));
+        R1_HIP(hipStreamSynchronize(c->stream)); // (the next chunk reuses the workspace)
+    }
+    return R1_OK;
 }
 
 extern "C" int r1_host_alloc(size_t bytes, void **out)

@@ -306,6 +306,21 @@ struct R1WaveArgs
     int32_t level;        // color() depth this launch works on
 };
 
+// Ray queries (r1_cast_rays / r1_cast_rays_device, r1_cast.hip): caller-supplied rays through the trace kernels' walks.
+struct R1CastArgs
+{
+    R1TraceArgs t;          // what the walks read: scene tables, bvh_lds_f4, bvh_depth, grid (everything else zero)
+    const float4 *rays;     // [n][2] {ox oy oz t_max} {dx dy dz -}: the public r1_ray
+    void *out;              // mode 0: [n][2] float4 {t, bit_cast<float>(scene index), px, py} {pz, nx, ny, nz}: the public r1_hit; mode 1: [n] bytes
+    const uint32_t *active_to_scene; // [n_active] scene index of an active sphere
+    uint32_t *cursor;       // the launch's ray cursor (zero before the launch): the waves claim `claim` rays at a time
+    uint32_t n;             // <= R1_CAST_LAUNCH_MAX
+    uint32_t mode;          // R1_CAST_CLOSEST 0 / R1_CAST_ANY 1
+    uint32_t claim;         // rays per claim (a multiple of 64)
+};
+#define R1_CAST_LAUNCH_MAX (1u << 30) // rays per launch (32-bit ray indices with room for a claim beyond the end); longer arrays take several launches
+#define R1_CAST_CURSORS 64u           // cursors of a context, 128 bytes apart, taken in turn: launches in flight on different streams each have their own
+
 struct R1ResolveArgs
 {
     const float4 *samples;

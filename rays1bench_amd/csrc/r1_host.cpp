@@ -412,3 +412,150 @@ extern "C" int r1_log_results(const char *version, const char *scene, const doub
     fclose(f);
     return R1_OK;
 }
+
+// ---- ray queries on the host: r1_cast_rays_host -------------------------------------------------------------------------------
+// Hitable::hit(Ray(o, d), 0.001f, t_max, &rec) (rayweek1.cpp:104-108, :152-339) for caller-supplied rays: every ray against every
+// active sphere in index order, in the reference's arithmetic — its two FMA chains written with fmaf, everything else operation by
+// operation (this file is compiled with -ffp-contract=off).  A sphere's offer is fixed before the compare with t_max (the comment
+// above exact_offer in r1_trace.hpp derives it), so the result is the minimum offer, ties to the lowest index, accepted only if it
+// is < t_max: the compare is strict, as rayweek1.cpp:298 / :307.
+
+#include <float.h>
+
+#include <functional>
+#include <thread>
+
+int r1_active_spheres(const r1_scene *s, std::vector<uint32_t> &active_to_scene); // inv_radius != 0, finite (r1_bvh.cpp)
+
+namespace
+{
+
+inline bool finite_f(float v)
+{
+    uint32_t b;
+    memcpy(&b, &v, 4);
+    return (b & 0x7F800000u) != 0x7F800000u;
+}
+
+// what one sphere offers a ray (exact_offer of r1_trace.hpp, host_offer of r1_grid.cpp)
+inline float cast_offer(const float *e, const float o[3], const float d[3])
+{
+    const float cox = e[0] - o[0], coy = e[1] - o[1], coz = e[2] - o[2];
+    const float nb = fmaf(coz, d[2], fmaf(coy, d[1], cox * d[0]));
+    const float c = fmaf(coz, coz, fmaf(coy, coy, cox * cox)) - e[3];
+    const float discr = nb * nb - c;
+    uint32_t bits;
+    memcpy(&bits, &discr, 4);
+    float offer = FLT_MAX;
+    if (!(bits >> 31))
+    {
+        const float root = sqrtf(discr);
+        const float t1 = nb - root;
+        const float t = (t1 > 0.001f) ? t1 : nb + root;
+        if (t > 0.001f && t < FLT_MAX)
+            offer = t;
+    }
+    return offer;
+}
+
+void cast_range(const std::vector<float> &ex, const std::vector<uint32_t> &scene_index, const r1_scene *s, int32_t mode, const r1_ray *rays,
+                size_t i0, size_t i1, void *out)
+{
+    const size_t na = scene_index.size();
+    for (size_t i = i0; i < i1; ++i)
+    {
+        const r1_ray &r = rays[i];
+        const float scale = 1.0f / sqrtf((r.d[0] * r.d[0] + r.d[1] * r.d[1]) + r.d[2] * r.d[2]); // unit_vector, mymath.h:211
+        const float d[3] = {r.d[0] * scale, r.d[1] * scale, r.d[2] * scale};
+        float t_max = r.t_max;
+        if (t_max > FLT_MAX) // +inf
+            t_max = FLT_MAX;
+        const bool valid = finite_f(r.o[0]) && finite_f(r.o[1]) && finite_f(r.o[2]) && finite_f(d[0]) && finite_f(d[1]) && finite_f(d[2]) &&
+                           t_max > 0.001f; // (false for NaN)
+        float best = FLT_MAX;
+        size_t best_a = na;
+        if (valid)
+            for (size_t a = 0; a < na; ++a)
+            {
+                const float t = cast_offer(&ex[4 * a], r.o, d);
+                if (t < best) // (ascending index: a tie keeps the earlier sphere)
+                    best = t, best_a = a;
+            }
+        const bool hit = best_a != na && best < t_max;
+        if (mode == R1_CAST_ANY)
+        {
+            ((uint8_t *)out)[i] = hit ? 1 : 0;
+            continue;
+        }
+        r1_hit h;
+        memset(&h, 0, sizeof(h));
+        h.t = FLT_MAX, h.index = -1;
+        if (hit)
+        {
+            const uint32_t k = scene_index[best_a];
+            h.t = best, h.index = (int32_t)k;
+            const float td[3] = {best * d[0], best * d[1], best * d[2]}; // point_at_parameter: _origin + t * _dir
+            for (int q = 0; q < 3; ++q)
+                h.p[q] = r.o[q] + td[q];
+            h.n[0] = (h.p[0] - s->center_x[k]) * s->inv_radius[k];
+            h.n[1] = (h.p[1] - s->center_y[k]) * s->inv_radius[k];
+            h.n[2] = (h.p[2] - s->center_z[k]) * s->inv_radius[k];
+        }
+        ((r1_hit *)out)[i] = h;
+    }
+}
+
+} // namespace
+
+static_assert(sizeof(r1_ray) == 32 && sizeof(r1_hit) == 32, "the device reads and writes these layouts");
+
+extern "C" int r1_cast_rays_host(const r1_scene *s, int32_t mode, const r1_ray *rays, size_t n, void *out)
+{
+    if (mode != R1_CAST_CLOSEST && mode != R1_CAST_ANY)
+    {
+        r1_set_error("r1_cast_rays_host: mode %d is neither R1_CAST_CLOSEST nor R1_CAST_ANY", mode);
+        return R1_EINVAL;
+    }
+    if (!s || (s->count && (!s->center_x || !s->center_y || !s->center_z || !s->radius_sq || !s->inv_radius)))
+    {
+        r1_set_error("r1_cast_rays_host: null scene");
+        return R1_EINVAL;
+    }
+    if (n == 0)
+        return R1_OK;
+    if (!rays || !out)
+    {
+        r1_set_error("r1_cast_rays_host: null rays or out with n > 0");
+        return R1_EINVAL;
+    }
+    std::vector<uint32_t> scene_index;
+    if (r1_active_spheres(s, scene_index) != R1_OK)
+        return R1_EINVAL;
+    std::vector<float> ex(4 * scene_index.size() + 4);
+    for (size_t a = 0; a < scene_index.size(); ++a)
+    {
+        const uint32_t i = scene_index[a];
+        ex[4 * a + 0] = s->center_x[i], ex[4 * a + 1] = s->center_y[i], ex[4 * a + 2] = s->center_z[i], ex[4 * a + 3] = s->radius_sq[i];
+    }
+    // host threads: pieces of at least 256 rays, at most 16 threads (results do not depend on the split: rays are independent)
+    unsigned hw = std::thread::hardware_concurrency();
+    size_t nt = hw ? (hw > 16u ? 16u : hw) : 1u;
+    if (nt > (n + 255) / 256)
+        nt = (n + 255) / 256;
+    if (nt <= 1)
+    {
+        cast_range(ex, scene_index, s, mode, rays, 0, n, out);
+        return R1_OK;
+    }
+    std::vector<std::thread> pool;
+    const size_t per = (n + nt - 1) / nt;
+    for (size_t t = 0; t < nt; ++t)
+    {
+        const size_t i0 = t * per, i1 = i0 + per < n ? i0 + per : n;
+        if (i0 < i1)
+            pool.emplace_back(cast_range, std::cref(ex), std::cref(scene_index), s, mode, rays, i0, i1, out);
+    }
+    for (std::thread &th : pool)
+        th.join();
+    return R1_OK;
+}
