@@ -526,13 +526,10 @@ extern "C" int r1_trace_mode(int variant, int big, int wanted)
 // path: a camera path (the MODE 5 builds: mode 0 with a batch block that ends in the camera table, R1PathArgs)
 extern "C" hipError_t r1_launch_trace(const R1TraceArgs *args, int variant, int big_in, int mode, int path, int blocks, size_t grid_lds, hipStream_t stream)
 {
-    // dynamic LDS of the tree kernels: the traversal stack, one entry per inner node on a path, and (small scenes) the node table
     const bool big = big_in != 0; // 32-bit hit indices, attenuation stack in the global workspace
     const bool tree = variant == 4 || variant == 5;
-    const size_t trav = tree ? (size_t)args->bvh_depth * R1_BLOCK * (big ? sizeof(uint32_t) : sizeof(uint16_t)) + (size_t)args->bvh_lds_f4 * 16 + R1_ENTRY_LDS_BYTES(args->entry_lds) : 0;
-    // uniform grid: the fallback's traversal stack (32-bit entries) and (small scenes) the grid's 16-bit tables
     const bool grid = variant == 7 || variant == 8;
-    const size_t gtrav = grid ? (size_t)args->bvh_depth * R1_BLOCK * sizeof(uint32_t) + (big ? 0 : (size_t)grid_lds) : 0;
+    const size_t walk_lds = r1_walk_lds(tree ? 4 : grid ? 7 : 0, big, args->bvh_depth, args->bvh_lds_f4, grid_lds);
     if (mode != r1_trace_mode(variant, big_in, mode))
         return hipErrorInvalidValue; // the caller sizes its arguments by the mode: it must be the one that is built
     const int batch = args->batch != nullptr; // frame batches: the MODE 3 build of the throughput kernels (variants 2, 4 and 7 only)
@@ -548,19 +545,16 @@ extern "C" hipError_t r1_launch_trace(const R1TraceArgs *args, int variant, int 
     const bool land_kernel = variant == 4 && R1_LAND_MODE(mode);
     if (land_kernel != (args->land_res > 0u))
         return hipErrorInvalidValue;
-    // (the tree kernels look a primary ray's entry node up in args->bvh_entry whenever the tree has a root step: never launch them without)
-    if (tree && R1_ENTRY_MODE(mode) && args->scene.bvh_root_leaf != 0u && args->bvh_entry == nullptr)
-        return hipErrorInvalidValue;
     if (path)
-        mode = 5; // (lands its tiles as mode 0 / 3 does; looks no entry node up)
+        mode = 5; // (lands its tiles as mode 0 / 3 does)
     if (tree)
-        return big ? r1_tu_tree_big_launch(args, variant, mode, batch, blocks, trav, stream) : r1_tu_tree_small_launch(args, variant, mode, batch, blocks, trav, stream);
+        return big ? r1_tu_tree_big_launch(args, variant, mode, batch, blocks, walk_lds, stream) : r1_tu_tree_small_launch(args, variant, mode, batch, blocks, walk_lds, stream);
     if (grid && args->grid == nullptr)
         return hipErrorInvalidValue; // (the grid kernels read their tables through this pointer)
     if (grid && mode == 2 && !big)
         return hipErrorInvalidValue; // (the grid's PIXEL mode runs through its big-scene kernel)
     if (grid)
-        return big ? r1_tu_grid_big_launch(args, variant, mode, batch, blocks, gtrav, stream) : r1_tu_grid_small_launch(args, variant, mode, batch, blocks, gtrav, stream);
+        return big ? r1_tu_grid_big_launch(args, variant, mode, batch, blocks, walk_lds, stream) : r1_tu_grid_small_launch(args, variant, mode, batch, blocks, walk_lds, stream);
     return big ? r1_tu_sweep_big_launch(args, variant, mode, batch, blocks, 0, stream) : r1_tu_sweep_small_launch(args, variant, mode, batch, blocks, 0, stream);
 }
 

@@ -16,7 +16,6 @@
 #include <algorithm>
 #include <new>
 #include <utility>
-#include <functional>
 #include <vector>
 
 #include "../../include/rays1.h"
@@ -116,7 +115,7 @@ struct r1_context
     DevBuf bvh_nodes, bvh_prims, bvh_ids; // R1_VARIANT_BVH (r1_bvh.cpp)
     // R1_VARIANT_GRID (r1_grid.cpp): built on the first render that asks for it after r1_set_scene (ensure_grid)
     DevBuf grid_tab, grid_out, grid_dev;  // cell table + ids, outliers, the R1GridArgs the kernels read
-    DevBuf grid_tab32, grid_dev32;        // the same in the big-scene kernel's 32-bit form (small scenes: for PIXEL mode, see enqueue_frame)
+    DevBuf grid_tab32, grid_dev32;        // the same in the big-scene kernel's 32-bit form (small scenes: for PIXEL mode, see big_scene)
     bool grid_valid = false;
     bool grid_small = false;  // 16-bit tables that the small-scene kernel keeps in LDS
     R1GridArgs grid_args;     // (pointers into grid_tab / grid_out; a copy of it in grid_dev)
@@ -173,15 +172,6 @@ struct r1_context
     int occupancy[224] = {0}; // [variant + 16 * big + 32 * mode]
     bool pixel_mode = false; // r1_set_pixel_mode
     DevBuf gstack; // blocks per CU of the trace kernel, by variant
-    // per-tile entry nodes for primary rays (R1_ENTRY): the tree's nodes on the host, the device table, what it was computed for
-    std::vector<float> bvh_nodes_host;
-    DevBuf bvh_entry;
-    DevBuf bvh_wide; // R1_BVH4: the collapsed table (small scenes)
-    uint32_t bvh_wide_f4 = 0;
-    int bvh_wide_stack = 0;
-    r1_params entry_key;
-    int entry_frames = 0;
-    bool entry_valid = false;
     DevBuf land_spill; // R1_LAND: [waves of the grid][tiles of the launch] every wave's list of the tiles it took chunks from
     // progressive passes (r1_render_pass): the frame being accumulated
     DevBuf accum;              // [local tile][pixel of the padded tile] fp32 {r, g, b, 0}
@@ -311,7 +301,7 @@ extern "C" void r1_destroy(r1_context *c)
     release(c->sweep), release(c->exact), release(c->exact_g), release(c->shade), release(c->mat), release(c->members);
     release(c->bvh_nodes), release(c->bvh_prims), release(c->bvh_ids), release(c->grid_tab), release(c->grid_out), release(c->grid_dev), release(c->grid_tab32), release(c->grid_dev32);
     release(c->wf_paths), release(c->wf_hits), release(c->wf_queue), release(c->wf_counts);
-    release(c->bvh_wide), release(c->bvh_entry), release(c->land_spill), release(c->gstack), release(c->counters), release(c->samples), release(c->image), release(c->batch_rays);
+    release(c->land_spill), release(c->gstack), release(c->counters), release(c->samples), release(c->image), release(c->batch_rays);
     release(c->wave_log), release(c->accum), release(c->path_cams), release(c->accum_even), release(c->adapt_list), release(c->adapt_report);
     release(c->active_dev), release(c->cast_cursors), release(c->cast_ws);
     if (c->host_word)
@@ -483,117 +473,6 @@ struct Landing;
 struct Pass;
 static int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int block_layout, void *d_rays, hipStream_t st, bool throughput_mode,
                          const Batch *batch = nullptr, Landing *landing = nullptr, const Pass *pass = nullptr);
-
-// ---- 4-wide nodes (R1_BVH4) -------------------------------------------------------------------------------------
-// The binary tree of a small scene collapsed: a wide node starts as a binary node's two children and replaces its inner child with the
-// largest box by that child's own two children until it holds four (or only leaves).  Boxes and leaves are the binary tree's, so the
-// spheres offered to a ray — and with them every pixel — stay the same; only the number of dependent trips of the walk changes.
-// Table: slot 0 = the binary root (4 float4 as r1_bvh.cpp writes them, child references in the 16-bit form, + 3 float4 of padding: the
-// root step of bvh_advance reads it), then wide node i >= 1 at float4 7 i: children 0, 1 and children 2, 3 as two row triples of the binary
-// form ({m0x m1x m0y m1y} {m0z m1z e0x e1x} {e0y e1y e0z e1z}), then {ref[4]};
-// an empty slot has e = -inf (never passes) and the reference of a leaf without pairs.  Returns the most entries a lane's stack can hold.
-static int build_wide(const std::vector<float> &bin, int root_leaf, std::vector<float> &out)
-{
-    auto ref_of = [&](uint32_t node, int k) { uint32_t v; memcpy(&v, &bin[16 * (size_t)node + 14 + k], 4); return v; };
-    auto ref16 = [](uint32_t ref) { return ((ref >> 16) & 0xF000u) | (ref & 0x0FFFu); };
-    struct Slot { float m[3], e[3]; uint32_t ref; };
-    auto slot_of = [&](uint32_t node, int k) {
-        Slot s;
-        const float *q = &bin[16 * (size_t)node];
-        for (int a = 0; a < 3; ++a)
-            s.m[a] = q[2 * a + k], s.e[a] = q[6 + 2 * a + k];
-        s.ref = ref_of(node, k);
-        return s;
-    };
-    const size_t n_bin = bin.size() / 16;
-    // Which grandchildren a wide node takes: the cut of <= 4 slots through the binary subtree that minimises the summed surface area of the
-    // wide nodes below it — the expected number of wide visits of a random ray, the measure the binary tree was built by.  (Taking the
-    // largest child first, top-down, leaves the bottom level of a balanced tree of odd height as two-slot nodes: 85 wide nodes for the
-    // large scene's 128 binary ones instead of 43.)  <= 8 cuts per node, memoised over <= 256 nodes.
-    std::vector<double> cost(n_bin, -1.0);
-    std::vector<std::vector<Slot>> cut_of(n_bin);
-    auto area_of = [](const Slot &q) { return std::isfinite(q.e[0] + q.e[1] + q.e[2]) ? (double)q.e[0] * q.e[1] + (double)q.e[1] * q.e[2] + (double)q.e[2] * q.e[0] : 0.0; };
-    std::function<double(uint32_t)> solve = [&](uint32_t b) -> double {
-        if (cost[b] >= 0.0)
-            return cost[b];
-        std::vector<std::vector<Slot>> cuts = {{slot_of(b, 0), slot_of(b, 1)}};
-        for (size_t i = 0; i < cuts.size(); ++i)
-            if (cuts[i].size() < 4)
-                for (size_t k = 0; k < cuts[i].size(); ++k)
-                    if (!(cuts[i][k].ref & 0x80000000u))
-                    {
-                        std::vector<Slot> c = cuts[i];
-                        const uint32_t x = c[k].ref;
-                        c[k] = slot_of(x, 0);
-                        c.push_back(slot_of(x, 1));
-                        cuts.push_back(c);
-                    }
-        double best = 1e300;
-        size_t pick = 0;
-        for (size_t i = 0; i < cuts.size(); ++i)
-        {
-            double sum = 0;
-            for (const Slot &q : cuts[i])
-                if (!(q.ref & 0x80000000u))
-                    sum += area_of(q) + solve(q.ref);
-            if (sum < best)
-                best = sum, pick = i;
-        }
-        cut_of[b] = cuts[pick];
-        return cost[b] = best;
-    };
-    std::vector<uint32_t> wide_of(n_bin, 0u), order; // binary inner node -> wide index (0: none yet)
-    auto wide_index = [&](uint32_t b) {
-        if (!wide_of[b])
-            order.push_back(b), wide_of[b] = (uint32_t)order.size();
-        return wide_of[b];
-    };
-    out.assign(28, 0.0f);
-    memcpy(out.data(), bin.data(), 64);
-    // the walk starts at the root's inner child (root step) — or, a tree without that shape, at the root itself
-    const uint32_t start = root_leaf ? ref_of(0, root_leaf == 1 ? 1 : 0) : 0u;
-    std::vector<int> above; // stack entries the ancestors of wide node i can leave
-    int need = 0;
-    if (!(start & 0x80000000u))
-        wide_index(start), above.push_back(0);
-    for (size_t i = 0; i < order.size(); ++i)
-    {
-        solve(order[i]);
-        const std::vector<Slot> slots = cut_of[order[i]];
-        const int here = above[i] + (int)slots.size() - 1;
-        need = std::max(need, here);
-        float w[28];
-        for (int k = 0; k < 4; ++k)
-        {
-            const bool used = k < (int)slots.size();
-            const int base = 12 * (k >> 1), j = k & 1; // children 0, 1 / 2, 3: one binary-form row triple each
-            for (int a = 0; a < 3; ++a)
-                w[base + 2 * a + j] = used ? slots[k].m[a] : 0.0f, w[base + 6 + 2 * a + j] = used ? slots[k].e[a] : -INFINITY;
-            uint32_t r = 0x8000u; // (an empty slot never passes — e = -inf — and if it did, it is a leaf of no pairs)
-            if (used)
-            {
-                if (slots[k].ref & 0x80000000u)
-                    r = ref16(slots[k].ref);
-                else
-                {
-                    const size_t before = order.size();
-                    r = wide_index(slots[k].ref);
-                    if (order.size() != before)
-                        above.push_back(here);
-                }
-            }
-            memcpy(&w[24 + k], &r, 4);
-        }
-        out.insert(out.end(), w, w + 28);
-    }
-    // slot 0's child references in the kernel's form: leaves as r1_ref16, the inner child as its wide index
-    for (int k = 0; k < 2; ++k)
-    {
-        const uint32_t r = ref_of(0, k), r16 = (r & 0x80000000u) ? ref16(r) : wide_of[r];
-        memcpy(&out[14 + k], &r16, 4);
-    }
-    return std::max(need, 1);
-}
 
 // what the kernels read of a camera (Camera::getRay, rayweek1.cpp:381-386, does not use w)
 static R1DeviceCamera device_camera(const r1_camera &cam)
@@ -783,25 +662,6 @@ extern "C" int r1_set_scene(r1_context *c, const r1_scene *s, const r1_camera *c
     if (na)
         R1_HIP(hipMemcpyAsync(c->active_dev.p, c->active_to_scene.data(), (size_t)na * 4, hipMemcpyHostToDevice, c->stream));
     R1_HIP(hipStreamSynchronize(c->stream)); // the host vectors go out of scope
-    c->bvh_nodes_host = bvh.nodes;
-    c->entry_valid = false;
-    c->bvh_wide_f4 = 0;
-    if (R1_BVH4 && bvh.nodes.size() >= 16 && bvh.nodes.size() / 16 <= R1_NODES_LDS_MAX && !bvh.pad_local)
-    {
-        std::vector<float> wide;
-        c->bvh_wide_stack = build_wide(bvh.nodes, bvh.root_leaf, wide);
-        if (c->bvh_wide_stack <= R1_BVH_STACK && wide.size() / 4 < 7u * 4096u)
-        {
-            if ((rc = ensure(c->bvh_wide, wide.size() * 4)))
-                return rc;
-            R1_HIP(hipMemcpy(c->bvh_wide.p, wide.data(), wide.size() * 4, hipMemcpyHostToDevice));
-            c->bvh_wide_f4 = (uint32_t)(wide.size() / 4);
-        }
-        static const int print = (int)r1_knob("R1_BVH4_PRINT", 0);
-        if (print)
-            fprintf(stderr, "rays1: 4-wide table: %zu binary nodes -> %zu wide nodes, stack %d entries (binary: %d)\n", bvh.nodes.size() / 16, wide.size() / 28 - 1,
-                    c->bvh_wide_stack, bvh.max_depth);
-    }
     c->n_bvh_nodes = (uint32_t)(bvh.nodes.size() / 16);
     c->n_bvh_leaves = bvh.n_leaves;
     c->bvh_depth = bvh.max_depth;
@@ -848,7 +708,6 @@ extern "C" int r1_set_camera(r1_context *c, const r1_camera *cam)
     c->pass_valid = false; // (a progressive frame does not continue across a change of view, as across r1_set_scene)
     c->cam = device_camera(*cam);
     c->src_cam = *cam;       // r1_set_scene(same arrays, this camera) is still the shortcut
-    c->entry_valid = false;  // R1_ENTRY: the per-tile entry nodes belong to a camera
     return R1_OK;
 }
 
@@ -937,150 +796,6 @@ struct Batch
     size_t out_stride = 0, rays_offset = 0;
     const r1_camera *cameras = nullptr; // a camera path: [n_frames], host memory; null: every frame through the context's camera
 };
-
-// ---- per-tile entry nodes for primary rays (R1_ENTRY) ---------------------------------------------------------
-// All primary rays of a 32 x 32 tile leave a small lens disk through a small rectangle of the focal plane: a narrow beam.  For every
-// tile of the launch the deepest node is found below which ALL of them stay, and a primary ray starts its walk there instead of at the
-// root's inner child (bvh_advance's root step still tests the root's leaf — the ground and the big balls — and the inner child's box).
-// Exactness: a subtree is left out only if no ray of the beam can pass the kernel's box test of its root, judged CONSERVATIVELY — the
-// box inflated by the largest pad any of these rays gets (the pad makes the boxes conservative with respect to the reference's fp32
-// sphere test, r1_bvh.cpp) plus a margin for the test's own rounding, against the four side planes of the beam pushed outwards by the
-// lens radius — so the walk from the root would not have entered it either: same offers, same minimum, same pixels.
-static void beam_planes(const R1DeviceCamera &cam, double s0, double s1, double t0, double t1, double n[4][3], double &d_plane)
-{
-    double q[4][3];
-    const double ss[4] = {s0, s1, s1, s0}, tt[4] = {t0, t0, t1, t1};
-    for (int k = 0; k < 4; ++k)
-        for (int a = 0; a < 3; ++a)
-            q[k][a] = (double)cam.lower_left[a] + ss[k] * cam.horizontal[a] + tt[k] * cam.vertical[a] - cam.origin[a]; // corner directions from the lens centre
-    // side plane k contains the lens centre and corners k, k + 1; its normal points away from the opposite corner
-    for (int k = 0; k < 4; ++k)
-    {
-        const double *a = q[k], *b = q[(k + 1) & 3], *c = q[(k + 2) & 3];
-        double m[3] = {a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]};
-        const double len = sqrt(m[0] * m[0] + m[1] * m[1] + m[2] * m[2]);
-        double sgn = (m[0] * c[0] + m[1] * c[1] + m[2] * c[2]) > 0 ? -1.0 : 1.0;
-        for (int i = 0; i < 3; ++i)
-            n[k][i] = len > 0 ? sgn * m[i] / len : 0.0;
-    }
-    // distance of the focal plane from the lens centre (along its normal): every target point is at least that far away
-    double w[3] = {cam.horizontal[1] * (double)cam.vertical[2] - cam.horizontal[2] * (double)cam.vertical[1],
-                   cam.horizontal[2] * (double)cam.vertical[0] - cam.horizontal[0] * (double)cam.vertical[2],
-                   cam.horizontal[0] * (double)cam.vertical[1] - cam.horizontal[1] * (double)cam.vertical[0]};
-    const double wl = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
-    d_plane = wl > 0 ? fabs((w[0] * q[0][0] + w[1] * q[0][1] + w[2] * q[0][2]) / wl) : 0.0;
-}
-
-// may any ray of the beam pass the (inflated) box {m, e}?  false only when one side plane has the whole box outside
-static bool beam_may_hit(const R1DeviceCamera &cam, const double n[4][3], double d_plane, const double m[3], const double e[3])
-{
-    const double r = fabs((double)cam.lens_radius);
-    double rel[3], far2 = 0;
-    for (int a = 0; a < 3; ++a)
-    {
-        rel[a] = m[a] - cam.origin[a];
-        const double f = fabs(rel[a]) + e[a];
-        far2 += f * f;
-    }
-    // a point of a beam ray at parameter L (1 = the focal plane) lies within |1 - L| r of the cone from the lens CENTRE; inside the box
-    // L <= (farthest corner + r) / (focal distance - r)
-    const double lmax = d_plane > 2 * r ? (sqrt(far2) + r) / (d_plane - r) : 1e30;
-    const double rho = r * std::max(1.0, lmax - 1.0);
-    if (!(rho < 1e20))
-        return true;
-    for (int k = 0; k < 4; ++k)
-    {
-        double lo = 0;
-        for (int a = 0; a < 3; ++a)
-            lo += n[k][a] * rel[a] - fabs(n[k][a]) * e[a];
-        if (lo > rho)
-            return false;
-    }
-    return true;
-}
-
-// entry[j] for every tile j of the launch (frame-major as the queue; the frames of a batch share the camera): a child reference in the
-// kernel's form (16-bit for the small-scene kernels); R1_BVH_DONE (all ones) where the beam misses the inner child altogether
-static void compute_entries(const r1_context *c, const r1_params *p, int n_frames, bool ref16, std::vector<uint32_t> &out)
-{
-    const uint32_t nlt = c->n_local_tiles;
-    out.assign((size_t)nlt * n_frames, 0xFFFFFFFFu);
-    const size_t n_nodes = c->bvh_nodes_host.size() / 16;
-    if (!c->bvh_root_leaf || n_nodes < 1 || nlt == 0)
-        return;
-    const float *N = c->bvh_nodes_host.data();
-    auto child = [&](uint32_t node, int k) { uint32_t v; memcpy(&v, N + 16 * (size_t)node + 14 + k, 4); return v; };
-    auto form = [&](uint32_t ref) { return ref16 && ref != 0xFFFFFFFFu ? (((ref >> 16) & 0xF000u) | (ref & 0x0FFFu)) : ref; }; // r1_ref16 (r1_trace.hpp)
-    const uint32_t other = child(0, c->bvh_root_leaf == 1 ? 1 : 0);
-    static const int entry_off = (int)r1_knob("R1_ENTRY_OFF", 0); // tuning: every tile starts at the root's inner child
-    if ((other & 0x80000000u) || entry_off)
-    {
-        out.assign((size_t)nlt * n_frames, form(other));
-        return;
-    }
-    const int tiles_x = (p->width + p->tile_w - 1) / p->tile_w;
-    const double r = fabs((double)c->cam.lens_radius);
-    double oc2 = 0, o1 = 0;
-    for (int a = 0; a < 3; ++a)
-        oc2 += ((double)c->cam.origin[a] - c->bvh_centre[a]) * ((double)c->cam.origin[a] - c->bvh_centre[a]), o1 += fabs((double)c->cam.origin[a]);
-    const double r2max = (sqrt(oc2) + r) * (sqrt(oc2) + r); // largest |o - C|^2 of a primary ray's origin
-    long depth_sum = 0, missed = 0;
-    for (uint32_t lt = 0; lt < nlt; ++lt)
-    {
-        const int tile = p->shard + (int)lt * p->num_shards;
-        const int x0 = (tile % tiles_x) * p->tile_w, y0 = (tile / tiles_x) * p->tile_h;
-        const int tw = std::min(p->tile_w, p->width - x0), th = std::min(p->tile_h, p->height - y0);
-        double n[4][3], d_plane;
-        // (x + jitter) / W with jitter in [0, 1); a hair of slack for the fp32 products of Camera::getRay
-        beam_planes(c->cam, (x0 - 1e-3) / p->width, (x0 + tw + 1e-3) / p->width, (y0 - 1e-3) / p->height, (y0 + th + 1e-3) / p->height, n, d_plane);
-        uint32_t x = other; // descend while exactly one child can be met and it is an inner node
-        int levels = 0;
-        for (;; ++levels)
-        {
-            const float *q = N + 16 * (size_t)x;
-            const double A = q[12], K = q[13];
-            int hits = 0, which = -1;
-            for (int k = 0; k < 2; ++k)
-            {
-                const double m[3] = {q[0 + k], q[2 + k], q[4 + k]};
-                double pad;
-                if (c->bvh_pad_local)
-                {
-                    double s2 = 0; // |m0 + m1 - 2 o|^2 at its largest over the lens disk
-                    const double sv[3] = {(double)q[0] + q[1] - 2.0 * c->cam.origin[0], (double)q[2] + q[3] - 2.0 * c->cam.origin[1], (double)q[4] + q[5] - 2.0 * c->cam.origin[2]};
-                    for (int a = 0; a < 3; ++a)
-                        s2 += sv[a] * sv[a];
-                    pad = A * (sqrt(s2) + 2 * r) * (sqrt(s2) + 2 * r) + K;
-                }
-                else
-                    pad = A * r2max + K;
-                // margin: the slab test's rounding (relative 2^-20 of the coordinates involved is generous) and v_rcp_f32's 1 ulp
-                const double margin = 1e-5 * (fabs(m[0]) + fabs(m[1]) + fabs(m[2]) + o1 + 1.0) + 1e-4;
-                const double e[3] = {q[6 + k] * 1.0001 + pad * 1.001 + margin, q[8 + k] * 1.0001 + pad * 1.001 + margin, q[10 + k] * 1.0001 + pad * 1.001 + margin};
-                if (beam_may_hit(c->cam, n, d_plane, m, e))
-                    ++hits, which = k;
-            }
-            if (hits == 0)
-            {
-                x = 0xFFFFFFFFu; // nothing of the lattice can be met: the walk is over after the root step
-                break;
-            }
-            if (hits == 2)
-                break;
-            const uint32_t cref = child(x, which);
-            x = cref;
-            if (cref & 0x80000000u)
-                break; // a leaf: tested directly
-        }
-        depth_sum += levels + (x == 0xFFFFFFFFu ? 1 : 0), missed += x == 0xFFFFFFFFu;
-        for (int f = 0; f < n_frames; ++f)
-            out[(size_t)f * nlt + lt] = form(x);
-    }
-    static const int print = (int)r1_knob("R1_ENTRY_PRINT", 0);
-    if (print)
-        fprintf(stderr, "rays1: entry nodes: %u tiles, %.2f levels below the root's inner child on average, %ld tiles whose beam misses it\n", nlt,
-                (double)depth_sum / nlt, missed);
-}
 
 // Where the caller finally wants the frame, if the device can write there (page-locked host memory): launches that resolve their own
 // tiles (R1_LAND) store the pixels and the count there directly and set `used`; the entry point then enqueues no copy.
@@ -1186,446 +901,429 @@ static int ensure_grid(r1_context *c)
     return R1_OK;
 }
 
-// Enqueues the frame (trace + resolve) on `st`.  d_out / d_rays are device addresses; d_rays == NULL stands for the context's own
-// count word (counters + R1_COUNTER_BYTES; the allocation may move in here, so callers take that address afterwards).
-static int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int block_layout, void *d_rays, hipStream_t st,
-                         bool throughput_mode, const Batch *batch, Landing *landing, const Pass *pass)
+// ---- one frame, step by step (enqueue_frame at the end) ------------------------------------------------------------------------------
+
+// What a frame launches (internal variant numbering = the public enum, DEFAULT resolved): decided once by choose_kernel, read by every step.
+struct Choice
 {
-    const int n_frames = batch ? batch->n_frames : 1;
-    if (!c->have_scene)
-    {
-        r1_set_error("no scene set (call r1_set_scene first)");
-        return R1_EINVAL;
-    }
-    int rc = r1_params_check(p);
-    if (rc)
-        return rc;
-    // kernel selection.  DEFAULT = the box tree (a property of the build, see above); PREFILTER always forces the exhaustive
-    // sweep, BVH always the tree; all of them produce the same pixels.
-    int variant = 2;
-    switch (p->variant)
-    {
-    case R1_VARIANT_REFERENCE: variant = 1; break;
-    case R1_VARIANT_STATS: variant = 3; break;
-    case R1_VARIANT_BVH: variant = 4; break;
-    case R1_VARIANT_BVH_STATS: variant = 5; break;
-    case R1_VARIANT_WAVEFRONT: variant = 6; break;
-    case R1_VARIANT_GRID: variant = 7; break;
-    case R1_VARIANT_GRID_STATS: variant = 8; break;
-    case R1_VARIANT_DEFAULT: variant = throughput_mode ? c->default_variant_tp : c->default_variant; break;
-    default: variant = 2; break;
-    }
-    R1_HIP(hipSetDevice(c->device));
-    const bool grid = variant == 7 || variant == 8;
-    if (grid && (rc = ensure_grid(c)))
-        return rc;
-    if ((rc = ensure_counters(c, p, n_frames)))
-        return rc;
-    const bool listed = pass && pass->list;
-    if (listed)
-    {
-        // a listed pass has the list's length as its tile count (grid size, queue length and record buffer follow from it below); the
-        // cached tiling no longer describes the params it is kept under, so the next call derives its own
-        c->n_local_tiles = pass->n_listed;
-        c->total_samples = c->full * pass->n_listed;
-        c->tile_key_valid = false;
-    }
-    if (pass && !listed && (rc = ensure(c->accum, (size_t)c->n_local_tiles * p->tile_w * p->tile_h * 16)))
-        return rc;
-    if (!d_rays)
-        d_rays = (char *)c->counters.p + R1_COUNTER_BYTES;
-    // kernel mode: the host-returning entry points run in latency mode, the throughput entry point with few long-lived
-    // waves per frame — per-sample records + r1_resolve_kernel either way, unless r1_set_pixel_mode chose PIXEL mode
-    // for the throughput entry point (a lane owns a pixel: no sample records, no resolve launch, ~10 % slower)
-    // big-scene kernels: > 1023 hittable spheres (10-bit hit indices), or — tree kernels — a node table too large for LDS, or a tree whose
-    // pad is measured per node (small spheres: only the kernels that walk the table in global memory carry that arm, bvh_advance)
-    // (grid kernels: tables too large for LDS — the small-scene grid kernel's fallback reads the tree from global memory, any tree will do —
-    // and PIXEL mode, which the grid runs through its big-scene kernel only: the small one's PIXEL build would spill)
-    const int big_scene_ = (c->n_active > R1_MAX_ACTIVE_10BIT || ((variant == 4 || variant == 5) && (c->n_bvh_nodes > R1_NODES_LDS_MAX || c->bvh_pad_local)) ||
-                            (grid && (!c->grid_small || (throughput_mode && c->pixel_mode)))) ? 1 : 0;
+    int variant, big, mode;
+    bool tree, grid, stats, wavefront; // box tree (4, 5), uniform grid (7, 8), a diagnostic build (3, 5, 8), variant 6
+    bool pixel, path, listed;          // PIXEL mode; a camera path of >= 2 frames; a pass over listed tiles
+    bool land;        // tiles resolved inside the trace kernel: the product kernels' launches; the diagnostic builds, the reference-form
+                      // sweep, the wavefront variant and PIXEL mode keep the round-3 form (records + r1_resolve_kernel, or no records at all)
+    bool fused_clear; // the frame's last launch publishes the ray count and zeroes the counter block (close_frame)
+};
+
+// Big-scene kernels — 32-bit hit indices, the attenuation stack in a global workspace (the packed LDS stack holds 10-bit indices) and the
+// tree's node table through the vector L1: > 1023 hittable spheres, or — tree kernels — a node table too large for LDS, or a tree whose pad
+// is measured per node (small spheres: only the kernels that walk the table in global memory carry that arm, bvh_advance); grid kernels:
+// tables too large for LDS — the small-scene grid kernel's fallback reads the tree from global memory, any tree will do — and PIXEL mode
+// (`grid_pixel`), which the grid runs through its big-scene kernel only: the small one's PIXEL build would spill.  Tried for the tree kernel
+// on small scenes too (more workgroups per CU): 15 % slower.  A grid's answer holds after ensure_grid.
+static bool big_scene(const r1_context *c, bool tree, bool grid, bool grid_pixel)
+{
+    return c->n_active > R1_MAX_ACTIVE_10BIT || (tree && (c->n_bvh_nodes > R1_NODES_LDS_MAX || c->bvh_pad_local)) || (grid && (!c->grid_small || grid_pixel));
+}
+
+// The public enum's numbers are the internal ones.  DEFAULT = the box tree (a property of the build, see above); PREFILTER always forces
+// the exhaustive sweep, BVH always the tree; all of them produce the same pixels.
+static int resolve_variant(const r1_context *c, int32_t wanted, bool throughput_mode)
+{
+    static_assert(R1_VARIANT_REFERENCE == 1 && R1_VARIANT_STATS == 3 && R1_VARIANT_BVH == 4 && R1_VARIANT_BVH_STATS == 5 && R1_VARIANT_WAVEFRONT == 6 &&
+                  R1_VARIANT_GRID == 7 && R1_VARIANT_GRID_STATS == 8, "the kernels' variant numbers");
+    if (wanted == R1_VARIANT_DEFAULT)
+        return throughput_mode ? c->default_variant_tp : c->default_variant;
+    return wanted >= R1_VARIANT_REFERENCE && wanted <= R1_VARIANT_GRID_STATS ? wanted : 2;
+}
+
+// Kernel choice, after the launch's tiles are known (size_tiles) and the grid is built.  Kernel mode: the host-returning entry points run
+// in latency mode, the throughput entry point with few long-lived waves per frame — per-sample records + r1_resolve_kernel either way,
+// unless r1_set_pixel_mode chose PIXEL mode for the throughput entry point (a lane owns a pixel: no sample records, no resolve launch,
+// ~10 % slower).  Refuses what is not built; changes nothing.
+static int choose_kernel(const r1_context *c, const r1_params *p, int variant, bool throughput_mode, const Batch *batch, const Pass *pass, Choice &k)
+{
+    k.variant = variant;
+    k.tree = variant == 4 || variant == 5, k.grid = variant == 7 || variant == 8, k.stats = variant == 3 || variant == 5 || variant == 8, k.wavefront = variant == 6;
+    k.listed = pass && pass->list;
+    k.path = batch && batch->cameras && batch->n_frames > 1; // (a path of one frame: the single-frame kernel with that camera by value)
+    k.big = big_scene(c, k.tree, k.grid, throughput_mode && c->pixel_mode) ? 1 : 0;
     static const int tp_mode_env = (int)r1_knob("R1_TP_MODE", -1); // tuning experiments
     const int tp_mode = c->pixel_mode ? 2 : (tp_mode_env >= 0 && tp_mode_env <= 2 ? tp_mode_env : 0);
-    const int mode = variant == 6 ? 0 : r1_trace_mode(variant, big_scene_, pass ? (listed ? 6 : 4) : (throughput_mode ? tp_mode : 1));
-    if (mode < 0)
+    k.mode = k.wavefront ? 0 : r1_trace_mode(variant, k.big, pass ? (k.listed ? 6 : 4) : (throughput_mode ? tp_mode : 1));
+    if (k.mode < 0)
     {
         r1_set_error("variant %d has no progressive-pass build", p->variant);
         return R1_EINVAL;
     }
-    const bool pixel_mode = mode == 2;
-    if (batch && (mode != 0 || variant == 6 || variant == 3 || variant == 5 || variant == 8 || variant == 1))
+    k.pixel = k.mode == 2;
+    if (batch && (k.mode != 0 || k.wavefront || k.stats || variant == 1))
     {
         r1_set_error("frame batches run through the throughput kernels only (no PIXEL mode, no diagnostic / reference-form / wavefront variant)");
         return R1_EINVAL;
     }
-    if (batch && !(R1_LAND && variant == 4))
+    k.land = variant == 4 && R1_LAND_MODE(k.mode) && c->total_samples > 0;
+    // Frames without a resolve launch, and the diagnostic builds, whose counters are read back afterwards, count into the caller's word
+    // and clear with memsets.
+    k.fused_clear = !k.land && !k.pixel && c->n_local_tiles && c->total_samples && !k.stats;
+    return R1_OK;
+}
+
+// The launch's tiles: the counter allocation (which may move: addresses inside it are taken after this) and the context's tile numbers.
+// A listed pass has the list's length as its tile count — grid size, queue length and record buffer follow from it — so n_local_tiles and
+// total_samples are rewritten BEFORE anything is sized, and the cached tiling, which no longer describes the params it is kept under, is
+// dropped: the next call derives its own.  A pass of r1_render_pass gets its accumulator.
+static int size_tiles(r1_context *c, const r1_params *p, int n_frames, const Pass *pass)
+{
+    int rc = ensure_counters(c, p, n_frames);
+    if (rc)
+        return rc;
+    if (pass && pass->list)
+    {
+        c->n_local_tiles = pass->n_listed;
+        c->total_samples = c->full * pass->n_listed;
+        c->tile_key_valid = false;
+    }
+    else if (pass)
+        return ensure(c->accum, (size_t)c->n_local_tiles * p->tile_w * p->tile_h * 16);
+    return R1_OK;
+}
+
+// The launch's sample records (none in PIXEL mode), and a batch's partial ray counts where a resolve launch will follow
+static int ensure_records(r1_context *c, const r1_params *p, const Choice &k, const Batch *batch, hipStream_t st)
+{
+    int rc;
+    if (batch && !(R1_LAND && k.variant == 4))
     {
         // partial ray counts of the resolve launch: one uint64 per (tile of the batch, workgroup column)
         const size_t cols = ((size_t)p->tile_w * p->tile_h + 255) / 256;
-        if ((rc = ensure(c->batch_rays, (size_t)n_frames * (c->n_local_tiles ? c->n_local_tiles : 1) * cols * 8)))
+        if ((rc = ensure(c->batch_rays, (size_t)batch->n_frames * (c->n_local_tiles ? c->n_local_tiles : 1) * cols * 8)))
             return rc;
     }
-    // tiles resolved inside the trace kernel: the product kernels' launches; the diagnostic builds, the reference-form
-    // sweep, the wavefront variant and PIXEL mode keep the round-3 form (records + r1_resolve_kernel, or no records at all)
-    const bool land = variant == 4 && R1_LAND_MODE(mode) && c->total_samples > 0;
-    if (!pixel_mode)
-    {
-        const size_t want = (size_t)(c->total_samples ? c->total_samples : 1) * 16;
-        const bool fresh = !c->samples.p || c->samples.cap < want;
-        if ((rc = ensure(c->samples, want)))
-            return rc;
-        if (fresh) // a record is recognised by its launch's tag: fresh memory must not carry one by accident
-            R1_HIP(hipMemsetAsync(c->samples.p, 0, c->samples.cap, st));
-    }
+    if (k.pixel)
+        return R1_OK;
+    const size_t want = (size_t)(c->total_samples ? c->total_samples : 1) * 16;
+    const bool fresh = !c->samples.p || c->samples.cap < want;
+    if ((rc = ensure(c->samples, want)))
+        return rc;
+    if (fresh) // a record is recognised by its launch's tag: fresh memory must not carry one by accident
+        R1_HIP(hipMemsetAsync(c->samples.p, 0, c->samples.cap, st));
+    return R1_OK;
+}
 
-    R1TraceArgs a;
-    memset(&a, 0, sizeof(a));
-    a.scene.sweep = (const float4 *)c->sweep.p;
-    a.scene.exact = (const float4 *)c->exact.p;
-    a.scene.shade = (const float4 *)c->shade.p;
-    a.scene.mat = (const float4 *)c->mat.p;
-    a.scene.members = (const uint32_t *)c->members.p;
-    a.scene.exact_g = (const float4 *)c->exact_g.p;
-    a.scene.n_active = c->n_active;
-    a.scene.n_sweep = c->n_sweep;
-    a.scene.n_multi = c->n_multi;
-    a.scene.bvh_nodes = (const float4 *)c->bvh_nodes.p;
-    a.scene.bvh_prims = (const float4 *)c->bvh_prims.p;
-    a.scene.bvh_ids = (const uint32_t *)c->bvh_ids.p;
+// The context's scene as the kernels read it: every table and number of R1DeviceScene (renders and ray queries alike)
+static void fill_scene(const r1_context *c, R1DeviceScene &s)
+{
+    s.sweep = (const float4 *)c->sweep.p, s.exact = (const float4 *)c->exact.p, s.exact_g = (const float4 *)c->exact_g.p;
+    s.shade = (const float4 *)c->shade.p, s.mat = (const float4 *)c->mat.p, s.members = (const uint32_t *)c->members.p;
+    s.n_active = c->n_active, s.n_sweep = c->n_sweep, s.n_multi = c->n_multi;
+    s.bvh_nodes = (const float4 *)c->bvh_nodes.p, s.bvh_prims = (const float4 *)c->bvh_prims.p, s.bvh_ids = (const uint32_t *)c->bvh_ids.p;
     for (int k = 0; k < 3; ++k)
-        a.scene.bvh_centre[k] = c->bvh_centre[k];
-    a.scene.bvh_pad_local = (uint32_t)c->bvh_pad_local;
-    a.scene.bvh_root_leaf = (uint32_t)c->bvh_root_leaf;
-    a.scene.bvh_flat_m = c->bvh_flat_m, a.scene.bvh_flat_e = c->bvh_flat_e;
-    a.cam = c->cam;
+        s.bvh_centre[k] = c->bvh_centre[k];
+    s.bvh_pad_local = (uint32_t)c->bvh_pad_local, s.bvh_root_leaf = (uint32_t)c->bvh_root_leaf;
+    s.bvh_flat_m = c->bvh_flat_m, s.bvh_flat_e = c->bvh_flat_e;
+}
+
+// The walk's share of the arguments, trace and cast kernels alike: the traversal stack's depth and the workgroups' LDS copy of the node
+// table — all of it for small scenes, the first `top_nodes` >= 1 in breadth-first order for big ones (the walk's root step reads node 0
+// from the LDS copy); none where the tree is walked from global memory (!tree_lds: a fallback, the plain cast).
+static void fill_walk(const r1_context *c, bool tree_lds, bool big, uint32_t top_nodes, R1TraceArgs &a)
+{
+    a.bvh_depth = c->bvh_depth > 0 ? c->bvh_depth : 1;
+    a.bvh_lds_f4 = !tree_lds ? 0u : (!big ? 4u * c->n_bvh_nodes : 4u * std::min(c->n_bvh_nodes, top_nodes));
+}
+
+// Everything of R1TraceArgs that follows from the context, the params and the kernel choice; the batch block, the grid size and the
+// landing are the later steps'.  Takes addresses inside the counter allocation: after size_tiles.
+static void frame_args(const r1_context *c, const r1_params *p, const Choice &k, const Batch *batch, void *d_out, int block_layout, void *d_rays, R1TraceArgs &a)
+{
+    memset(&a, 0, sizeof(a));
+    fill_scene(c, a.scene);
+    a.cam = batch && batch->cameras && batch->n_frames == 1 ? device_camera(batch->cameras[0]) : c->cam;
     a.width = p->width, a.height = p->height, a.spp = p->spp, a.max_bounces = p->max_bounces;
     a.seed = p->seed;
-    a.inv_w = 1.0f / p->width;  // Vec3 inv_image_size(1.0f / td.image_w, 1.0f / td.image_h, 0) rayweek1.cpp:746
-    a.inv_h = 1.0f / p->height;
-    a.tile_w = p->tile_w, a.tile_h = p->tile_h;
-    a.tiles_x = (p->width + p->tile_w - 1) / p->tile_w;
+    a.inv_w = 1.0f / p->width, a.inv_h = 1.0f / p->height; // Vec3 inv_image_size(1.0f / td.image_w, 1.0f / td.image_h, 0) rayweek1.cpp:746
+    a.tile_w = p->tile_w, a.tile_h = p->tile_h, a.tiles_x = (p->width + p->tile_w - 1) / p->tile_w;
     a.shard = p->shard, a.num_shards = p->num_shards;
-    a.n_local_tiles = c->n_local_tiles;
-    a.batch = nullptr;
-    const bool path = batch && batch->cameras && n_frames > 1; // (a path of one frame: the single-frame kernel with that camera by value)
-    if (batch && batch->cameras && n_frames == 1)
-        a.cam = device_camera(batch->cameras[0]);
-    if (path)
+    a.n_local_tiles = c->n_local_tiles, a.full = c->full, a.total_samples = c->total_samples;
+    a.div_full = make_div(c->full), a.div_spp = make_div((uint32_t)p->spp), a.div_tw = make_div((uint32_t)p->tile_w), a.div_tx = make_div((uint32_t)a.tiles_x);
+    a.queue = (uint32_t *)((char *)c->counters.p + 1024);
+    static const int coop_env = (int)r1_knob("R1_COOP_LANES", -1);
+    a.coop_lanes = coop_env >= 0 ? (uint32_t)coop_env : R1_COOP_LANES;
+    a.samples = (float4 *)c->samples.p;
+    a.num_rays = k.fused_clear ? (unsigned long long *)((char *)c->counters.p + 32) : (unsigned long long *)d_rays;
+    a.stats = k.stats ? (unsigned long long *)((char *)c->counters.p + 128) : nullptr;
+    if (k.grid)
+        a.grid = (const R1GridArgs *)(k.big ? c->grid_dev32.p : c->grid_dev.p), a.scene.bvh_root_leaf = 0u; // (the grid kernels' fallback walks the tree from its root: no root step, r1_trace.hpp)
+    static const int big_top_env = (int)r1_knob("R1_BIG_TOP", R1_BVH_TOP_NODES); // tuning experiments
+    fill_walk(c, k.tree, k.big, (uint32_t)std::max(1, big_top_env), a);
+    if (k.pixel)
     {
-        // the frames' cameras: a table in device memory, written in stream order; then the batch's numbers and the table's address in a
-        // slot of their own (a batch that follows takes a new slot: its numbers may equal these, its block has no table)
-        const size_t half = ((size_t)n_frames * R1_PATH_CAM_F4 * 16 + 255) & ~(size_t)255;
-        if ((rc = ensure(c->path_cams, 2 * half))) // (growing frees the old table: hipFree waits for the launches that read it)
-            return rc;
-        c->path_cams_half ^= 1;
-        char *const table = (char *)c->path_cams.p + (c->path_cams_half ? c->path_cams.cap / 2 : 0);
-        std::vector<float> rows((size_t)n_frames * R1_PATH_CAM_F4 * 4, 0.0f);
-        for (int f = 0; f < n_frames; ++f)
-        {
-            const R1DeviceCamera d = device_camera(batch->cameras[f]);
-            static_assert(sizeof(R1DeviceCamera) == 19 * 4 && R1_PATH_CAM_F4 * 4 >= 19, "a table row holds an R1DeviceCamera");
-            memcpy(&rows[(size_t)f * R1_PATH_CAM_F4 * 4], &d, sizeof(d));
-        }
-        R1_HIP(r1_launch_put_cameras(table, rows.data(), n_frames, st));
+        // the queue holds the padded pixels of the shard's tiles, and `samples` is the output the kernel resolves into
+        const uint32_t tp = (uint32_t)(p->tile_w * p->tile_h);
+        a.full = tp, a.div_full = make_div(tp), a.total_samples = c->n_local_tiles * tp;
+        a.samples = (float4 *)d_out, a.block_layout = block_layout;
+        a.inv_spp = (float)(1.0f / p->spp); // rayweek1.cpp:765
+    }
+}
+
+// Takes a batch-argument slot (eight 32-byte slots in the counter allocation behind the published ray count) and writes `words` into it by a
+// launch of its own, in stream order: the previous launch through this context has finished reading its copy by the time this one is
+// written, and a NEW slot leaves a launch still reading the previous numbers undisturbed.  `cache` (a batch's numbers): an unchanged batch
+// on the same stream reuses its slot and writes nothing.  cache == null (a path, whose block ends in a table address, and a pass): always a
+// new slot, and batch_args_last is cleared, so that a batch that follows takes a new slot too (its numbers never equal the cleared ones:
+// n_frames >= 2).  Returns the slot.
+static int put_batch_args(r1_context *c, const void *words, int n_words, const R1BatchArgs *cache, hipStream_t st, const R1BatchArgs **slot)
+{
+    char *const slots = (char *)c->counters.p + R1_COUNTER_BYTES + 64;
+    if (!cache || c->batch_args_slot < 0 || c->batch_args_stream != st || memcmp(cache, &c->batch_args_last, sizeof(*cache)) != 0)
+    {
+        c->batch_args_slot = (c->batch_args_slot + 1) & 7;
+        if (cache)
+            c->batch_args_last = *cache;
+        else
+            memset(&c->batch_args_last, 0, sizeof(c->batch_args_last));
+        c->batch_args_stream = st;
+        R1_HIP((n_words == 8 ? r1_launch_put8 : r1_launch_put6)(slots + 32 * c->batch_args_slot, (const uint32_t *)words, st));
+    }
+    *slot = (const R1BatchArgs *)(slots + 32 * c->batch_args_slot);
+    return R1_OK;
+}
+
+// A camera path's table of cameras in device memory, written in stream order into the half of path_cams the previous path did not use.
+// The one step of a frame that allocates on the heap (the rows travel in the arguments of the launches that write them).
+static int put_path_cameras(r1_context *c, const Batch *batch, hipStream_t st, const float **table_out)
+{
+    const int n_frames = batch->n_frames;
+    const size_t half = ((size_t)n_frames * R1_PATH_CAM_F4 * 16 + 255) & ~(size_t)255;
+    int rc = ensure(c->path_cams, 2 * half); // (growing frees the old table: hipFree waits for the launches that read it)
+    if (rc)
+        return rc;
+    c->path_cams_half ^= 1;
+    char *const table = (char *)c->path_cams.p + (c->path_cams_half ? c->path_cams.cap / 2 : 0);
+    std::vector<float> rows((size_t)n_frames * R1_PATH_CAM_F4 * 4, 0.0f);
+    for (int f = 0; f < n_frames; ++f)
+    {
+        const R1DeviceCamera d = device_camera(batch->cameras[f]);
+        static_assert(sizeof(R1DeviceCamera) == 19 * 4 && R1_PATH_CAM_F4 * 4 >= 19, "a table row holds an R1DeviceCamera");
+        memcpy(&rows[(size_t)f * R1_PATH_CAM_F4 * 4], &d, sizeof(d));
+    }
+    R1_HIP(r1_launch_put_cameras(table, rows.data(), n_frames, st));
+    *table_out = (const float *)table;
+    return R1_OK;
+}
+
+// R1TraceArgs::batch (null in a single frame): a batch's numbers, behind them a path's camera table; or a pass's first sample and tile
+// list, which the MODE 4 / 6 kernels read where a sample is seeded.
+static int put_batch_block(r1_context *c, const Choice &k, const Batch *batch, const Pass *pass, hipStream_t st, R1TraceArgs &a)
+{
+    static_assert(sizeof(R1BatchArgs) == 24 && sizeof(R1PassArgs) == 24, "r1_launch_put6 writes the six words of R1BatchArgs / R1PassArgs");
+    static_assert(sizeof(R1PathArgs) == 32 && __builtin_offsetof(R1PathArgs, cameras) == 24, "r1_launch_put8 writes the eight words of R1PathArgs into a 32-byte slot");
+    int rc;
+    if (batch && batch->n_frames > 1)
+    {
         R1PathArgs pa;
         memset(&pa, 0, sizeof(pa));
-        pa.batch.n_frames = (uint32_t)n_frames, pa.batch.seed_stride = batch->seed_stride;
+        pa.batch.n_frames = (uint32_t)batch->n_frames, pa.batch.seed_stride = batch->seed_stride;
         pa.batch.div_tiles = make_div(c->n_local_tiles ? c->n_local_tiles : 1u), pa.batch.n_local_tiles = c->n_local_tiles;
-        pa.cameras = (const float *)table;
-        static_assert(sizeof(R1PathArgs) == 32 && __builtin_offsetof(R1PathArgs, cameras) == 24, "r1_launch_put8 writes the eight words of R1PathArgs into a 32-byte slot");
-        c->batch_args_slot = (c->batch_args_slot + 1) & 7;
-        memset(&c->batch_args_last, 0, sizeof(c->batch_args_last));
-        c->batch_args_stream = st;
-        R1_HIP(r1_launch_put8((char *)c->counters.p + R1_COUNTER_BYTES + 64 + 32 * c->batch_args_slot, (const uint32_t *)&pa, st));
-        a.batch = (const R1BatchArgs *)((char *)c->counters.p + R1_COUNTER_BYTES + 64 + 32 * c->batch_args_slot);
-    }
-    else if (batch && n_frames > 1)
-    {
-        // the batch's numbers, in the context's counter allocation behind the published ray count (stream-ordered upload:
-        // the previous launch through this context has finished reading its copy by the time this one is written)
-        R1BatchArgs ba;
-        ba.n_frames = (uint32_t)n_frames, ba.seed_stride = batch->seed_stride;
-        ba.div_tiles = make_div(c->n_local_tiles ? c->n_local_tiles : 1u), ba.n_local_tiles = c->n_local_tiles;
-        static_assert(sizeof(R1BatchArgs) == 24, "r1_launch_put6 writes the six words of R1BatchArgs");
-        if (c->batch_args_slot < 0 || c->batch_args_stream != st || memcmp(&ba, &c->batch_args_last, sizeof(ba)) != 0)
-        {
-            // a new slot, so that a launch still reading the previous numbers is not disturbed; written in stream order by a launch of its own
-            c->batch_args_slot = (c->batch_args_slot + 1) & 7;
-            c->batch_args_last = ba, c->batch_args_stream = st;
-            R1_HIP(r1_launch_put6((char *)c->counters.p + R1_COUNTER_BYTES + 64 + 32 * c->batch_args_slot, (const uint32_t *)&ba, st));
-        }
-        a.batch = (const R1BatchArgs *)((char *)c->counters.p + R1_COUNTER_BYTES + 64 + 32 * c->batch_args_slot);
+        if (k.path && (rc = put_path_cameras(c, batch, st, &pa.cameras)))
+            return rc;
+        if ((rc = put_batch_args(c, &pa, k.path ? 8 : 6, k.path ? nullptr : &pa.batch, st, &a.batch)))
+            return rc;
     }
     if (pass)
     {
-        // the pass's first sample, in a batch-argument slot of its own (the MODE 4 kernels read it where a sample is seeded); a batch that
-        // follows takes a new slot (its numbers never equal the cleared ones: n_frames >= 2)
         R1PassArgs pa;
         memset(&pa, 0, sizeof(pa));
         pa.first_sample = (uint32_t)pass->first_sample;
         pa.list = pass->list;
-        static_assert(sizeof(R1PassArgs) == 24, "r1_launch_put6 writes the six words of R1PassArgs");
-        c->batch_args_slot = (c->batch_args_slot + 1) & 7;
-        memset(&c->batch_args_last, 0, sizeof(c->batch_args_last));
-        c->batch_args_stream = st;
-        R1_HIP(r1_launch_put6((char *)c->counters.p + R1_COUNTER_BYTES + 64 + 32 * c->batch_args_slot, (const uint32_t *)&pa, st));
-        a.batch = (const R1BatchArgs *)((char *)c->counters.p + R1_COUNTER_BYTES + 64 + 32 * c->batch_args_slot);
+        return put_batch_args(c, &pa, 6, nullptr, st, &a.batch);
     }
-    a.full = c->full;
-    a.div_full = make_div(c->full);
-    a.div_spp = make_div((uint32_t)p->spp);
-    a.div_tw = make_div((uint32_t)p->tile_w);
-    a.div_tx = make_div((uint32_t)a.tiles_x);
-    a.total_samples = c->total_samples;
-    a.queue = (uint32_t *)((char *)c->counters.p + 1024);
-    a.nq = 1;
-    {
-        static const int coop_env = (int)r1_knob("R1_COOP_LANES", -1);
-        a.coop_lanes = coop_env >= 0 ? (uint32_t)coop_env : R1_COOP_LANES;
-    }
-    a.bvh_entry = nullptr, a.entry_lds = 0;
-    if (R1_ENTRY && (variant == 4 || variant == 5) && c->bvh_root_leaf && c->n_local_tiles && !listed) // (a listed pass: MODE 6 looks no entry up, and its tiles are not the table's)
-    {
-        // per-tile entry nodes of the primary rays (compute_entries): once per (scene, camera, tiling, frames of the launch, reference form)
-        const int form = big_scene_ ? 2 : 1;
-        const bool own_cam = batch && batch->cameras; // a camera path: the one-frame form's table is made for its camera and for this launch only
-        if (own_cam)                                   // (the MODE 5 kernels look no entry up: their frames have a camera each)
-            c->entry_valid = false;
-        if (!c->entry_valid || c->entry_frames != n_frames * 4 + form || !same_tiling(c->entry_key, *p))
-        {
-            std::vector<uint32_t> tab;
-            const R1DeviceCamera keep = c->cam;
-            c->cam = a.cam;
-            compute_entries(c, p, n_frames, !big_scene_, tab);
-            c->cam = keep;
-            R1_HIP(hipDeviceSynchronize()); // (launches still reading the previous table: a change of tiling is rare)
-            if ((rc = ensure(c->bvh_entry, tab.size() * 4)))
-                return rc;
-            R1_HIP(hipMemcpy(c->bvh_entry.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
-            c->entry_valid = !own_cam, c->entry_frames = n_frames * 4 + form, c->entry_key = *p;
-        }
-        a.bvh_entry = (const uint32_t *)c->bvh_entry.p;
-        static const int entry_lds_env = (int)r1_knob("R1_ENTRY_LDS", 1); // tuning: 0 = the table stays in global memory
-        a.entry_lds = (!big_scene_ && !batch && entry_lds_env && c->n_local_tiles <= R1_ENTRY_LDS_MAX) ? c->n_local_tiles : 0u;
-    }
-    a.samples = (float4 *)c->samples.p;
-    // The frame's last launch (resolve) publishes the ray count and zeroes the counter block for the next frame, which
-    // saves the two memset launches in front of every frame (they cost nothing to execute and ~10 us each to dispatch:
-    // a rank of an 8-GPU run renders its share of a frame in 140 us).  Frames without a resolve launch, and the diagnostic
-    // builds, whose counters are read back afterwards, count into the caller's word and clear with memsets.
-    const bool fused_clear = !land && !pixel_mode && c->n_local_tiles && c->total_samples && variant != 3 && variant != 5 && variant != 8;
-    a.num_rays = fused_clear ? (unsigned long long *)((char *)c->counters.p + 32) : (unsigned long long *)d_rays;
-    a.stats = (variant == 3 || variant == 5 || variant == 8) ? (unsigned long long *)((char *)c->counters.p + 128) : nullptr;
-    if (grid)
-        a.grid = (const R1GridArgs *)(big_scene_ ? c->grid_dev32.p : c->grid_dev.p), a.scene.bvh_root_leaf = 0u; // (the grid kernels' fallback walks the tree from its root: no root step, r1_trace.hpp)
+    return R1_OK;
+}
 
-    // BIG kernels: 32-bit hit indices, the attenuation stack in a global workspace (the packed
-    // LDS stack holds 10-bit indices) and the tree's node table through the vector L1.  Tried for the
-    // tree kernel on small scenes too (more workgroups per CU): 15 % slower.  The small-scene tree
-    // kernels keep the first 3 * R1_STACK_LDS_WORDS stack entries in LDS and use the workspace beyond.
-    const int big = big_scene_;
-    a.bvh_depth = c->bvh_depth > 0 ? c->bvh_depth : 1;
-    // the workgroups' LDS copy of the node table: all of it for small scenes, the breadth-first top for big ones
-    static const int big_top_env = (int)r1_knob("R1_BIG_TOP", R1_BVH_TOP_NODES); // tuning experiments
-    // (big scenes: at least node 0 — the walk's root step reads it from the LDS copy, whatever the tuning knob says)
-    a.bvh_lds_f4 = !(variant == 4 || variant == 5) ? 0u : (!big ? 4u * c->n_bvh_nodes : 4u * std::min<uint32_t>(c->n_bvh_nodes, (uint32_t)std::max(1, big_top_env)));
-    if (!grid)
-        a.bvh_wide = nullptr; // (shares its word with a.grid)
-    if (R1_BVH4 && (variant == 4 || variant == 5) && !big)
-    {
-        if (!c->bvh_wide_f4)
-        {
-            r1_set_error("this build walks 4-wide nodes (R1_BVH4) and the scene's tree has no such table");
-            return R1_EINVAL;
-        }
-        a.bvh_wide = (const float4 *)c->bvh_wide.p, a.bvh_lds_f4 = c->bvh_wide_f4, a.bvh_depth = c->bvh_wide_stack;
-    }
-    const int occ_slot = variant + 16 * big + 32 * mode;
-    if (c->occupancy[occ_slot] == 0)
-        R1_HIP(r1_trace_occupancy(variant, big, mode,
-                                  (variant == 4 || variant == 5) ? (size_t)a.bvh_depth * R1_BLOCK * (big ? 4 : 2) + (size_t)a.bvh_lds_f4 * 16 + R1_ENTRY_LDS_BYTES(a.entry_lds)
-                                  : grid ? (size_t)a.bvh_depth * R1_BLOCK * 4 + (big ? 0 : (size_t)c->grid_args.lds_bytes) : 0,
-                                  &c->occupancy[occ_slot]));
-    int per_cu = c->occupancy[occ_slot];
-    if (per_cu < 1)
-        per_cu = 1;
-    if (per_cu > 8)
-        per_cu = 8;
+// Workgroups per CU of the chosen kernel with the dynamic LDS its launch will have (r1_walk_lds: the size r1_launch_trace launches with),
+// 1 .. 8.  Asked once per (variant, big, mode) of a scene: the tree kernels' LDS footprint follows the tree, r1_set_scene clears the cache.
+static int blocks_per_cu(r1_context *c, const Choice &k, const R1TraceArgs &a, int *per_cu)
+{
+    int &occ = c->occupancy[k.variant + 16 * k.big + 32 * k.mode];
+    if (occ == 0)
+        R1_HIP(r1_trace_occupancy(k.variant, k.big, k.mode, r1_walk_lds(k.tree ? 4 : k.grid ? 7 : 0, k.big, a.bvh_depth, a.bvh_lds_f4, c->grid_args.lds_bytes), &occ));
     static const int per_cu_env = (int)r1_knob("R1_BLOCKS_PER_CU", 0); // tuning experiments
-    if (per_cu_env > 0 && per_cu_env < per_cu)
-        per_cu = per_cu_env;
-    // Persistent grid.  Latency mode (the synchronous host entry points: one frame, the caller
-    // waits): as many waves as fit, every lane at least one sample.  Throughput mode (the
-    // device-resident entry point, frames in flight on several streams): a wave's lanes run dry
-    // one by one at the end of its share (the longest bounce chain of 64 lanes is ~20 sweeps), so
-    // a wave needs many times that much work to stay full — give every lane
-    // >= R1_SAMPLES_PER_LANE samples and let the other frames fill the CUs a small frame leaves.
-    long long blocks = (long long)c->cus * per_cu;
+    *per_cu = std::min(std::max(occ, 1), 8);
+    if (per_cu_env > 0 && per_cu_env < *per_cu)
+        *per_cu = per_cu_env;
+    return R1_OK;
+}
+
+// The persistent grid and how its waves take work from the queue.  Changes nothing but its result.
+struct GridSize { long long blocks; uint32_t chunk_min, chunk_max, nq; };
+// total: sample slots of the launch; pixels: PIXEL mode — the padded pixels the queue holds instead — else 0
+static GridSize size_grid(int cus, int per_cu, uint32_t total, uint32_t pixels, int mode, bool throughput_mode, int num_shards, bool big)
+{
+    GridSize g;
+    // Latency mode (the synchronous host entry points: one frame, the caller waits): as many waves as fit, every lane at least one
+    // sample.  Throughput mode (the device-resident entry point, frames in flight on several streams): a wave's lanes run dry one by one
+    // at the end of its share (the longest bounce chain of 64 lanes is ~20 sweeps), so a wave needs many times that much work to stay
+    // full — give every lane >= R1_SAMPLES_PER_LANE samples and let the other frames fill the CUs a small frame leaves.
     static const long long spl_env = r1_knob("R1_SAMPLES_PER_LANE", R1_SAMPLES_PER_LANE);
     static const long long minb_env = r1_knob("R1_MIN_BLOCKS", R1_MIN_BLOCKS);
-    long long needed = ((long long)c->total_samples + R1_BLOCK - 1) / R1_BLOCK;
+    long long needed = ((long long)total + R1_BLOCK - 1) / R1_BLOCK;
     if (throughput_mode)
     {
         // few, long-lived workgroups per frame (>= R1_SAMPLES_PER_LANE samples per lane), but not fewer
         // than R1_MIN_BLOCKS while that still leaves R1_SAMPLES_PER_LANE_MIN samples per lane
-        const long long spl = p->num_shards > 1 ? R1_SAMPLES_PER_LANE_SHARD : (spl_env > 0 ? spl_env : 1);
-        const long long hi = ((long long)c->total_samples + R1_BLOCK * spl - 1) / (R1_BLOCK * spl);
-        const long long lo = ((long long)c->total_samples + R1_BLOCK * R1_SAMPLES_PER_LANE_MIN - 1) / (R1_BLOCK * R1_SAMPLES_PER_LANE_MIN);
+        const long long spl = num_shards > 1 ? R1_SAMPLES_PER_LANE_SHARD : (spl_env > 0 ? spl_env : 1);
+        const long long hi = ((long long)total + R1_BLOCK * spl - 1) / (R1_BLOCK * spl);
+        const long long lo = ((long long)total + R1_BLOCK * R1_SAMPLES_PER_LANE_MIN - 1) / (R1_BLOCK * R1_SAMPLES_PER_LANE_MIN);
         needed = std::max(hi, std::min(minb_env, lo));
     }
-    if (blocks > needed)
-        blocks = needed;
-    if (blocks < 1)
-        blocks = 1;
+    g.blocks = std::max(1LL, std::min((long long)cus * per_cu, needed));
     // Queue chunk per atomic: guided (remaining / (2 waves)) between chunk_min and chunk_max.  Large
     // chunks keep a wave on consecutive samples (coherent primary rays, whole sample-record lines)
     // and save atomics — measured at N = 1: 256 -> 1.227 ms, 1024 -> 1.197, 4096 -> 1.231 —
     // but they must stay small against a wave's share of the frame (8 shards: 1024 costs 12 %).
+    static const int chunk_max_env = (int)r1_knob("R1_CHUNK", 0), chunk_min_env = (int)r1_knob("R1_CHUNK_MIN", 0), nq_env = (int)r1_knob("R1_NQ", 0);
+    const long long waves = g.blocks * (R1_BLOCK / 64);
+    if (mode == 2) // chunks in pixels (a wave holds 64 pixels at a time)
     {
-        static const int chunk_max_env = (int)r1_knob("R1_CHUNK", 0), chunk_min_env = (int)r1_knob("R1_CHUNK_MIN", 0);
-        const long long waves = blocks * (R1_BLOCK / 64);
-        long long cm = (long long)c->total_samples / (waves * 12);
-        cm = cm < R1_CHUNK ? R1_CHUNK : (cm > R1_CHUNK_BIG ? R1_CHUNK_BIG : cm);
-        a.chunk_max = chunk_max_env > 0 ? (uint32_t)chunk_max_env : (uint32_t)cm;
-        a.chunk_min = chunk_min_env > 0 ? (uint32_t)chunk_min_env : R1_CHUNK_MIN;
-        if (a.chunk_min > a.chunk_max)
-            a.chunk_min = a.chunk_max;
+        g.chunk_max = (uint32_t)std::min(128LL, std::max(16LL, (long long)pixels / (waves * 12)));
+        g.chunk_min = 8;
     }
-    // Latency mode: every wave of the full grid takes one wave-full of samples per atomic (what a wave
-    // still holds when the queue runs dry is the frame's tail: with 256-sample chunks the waves found
-    // the queue empty over a span of 0.7 ms), which one counter cannot serve: sub-queues.
-    if (pixel_mode)
+    else
     {
-        // the queue holds the padded pixels of the shard's tiles; chunks in pixels (a wave holds 64 pixels at a time)
-        const uint32_t tp = (uint32_t)(p->tile_w * p->tile_h);
-        a.full = tp;
-        a.div_full = make_div(tp);
-        a.total_samples = c->n_local_tiles * tp;
-        a.samples = (float4 *)d_out;
-        a.block_layout = block_layout;
-        a.inv_spp = (float)(1.0f / p->spp); // rayweek1.cpp:765
-        const long long waves = blocks * (R1_BLOCK / 64);
-        long long cm = (long long)a.total_samples / (waves * 12);
-        cm = cm < 16 ? 16 : (cm > 128 ? 128 : cm);
-        a.chunk_max = (uint32_t)cm;
-        a.chunk_min = 8;
+        const long long cm = std::min<long long>(R1_CHUNK_BIG, std::max<long long>(R1_CHUNK, (long long)total / (waves * 12)));
+        g.chunk_max = chunk_max_env > 0 ? (uint32_t)chunk_max_env : (uint32_t)cm;
+        g.chunk_min = std::min(chunk_min_env > 0 ? (uint32_t)chunk_min_env : R1_CHUNK_MIN, g.chunk_max);
     }
-    if (mode == 1 && land)
-        a.chunk_max = a.chunk_min = 64u; // (the XCDs' cursors hand out the wave-fulls: eight lines instead of one, no sub-queues)
-    else if (mode == 1 || ((mode == 4 || mode == 6) && !big_scene_))
+    // Latency mode: every wave of the full grid takes one wave-full of samples per atomic (what a wave still holds when the queue runs
+    // dry is the frame's tail: with 256-sample chunks the waves found the queue empty over a span of 0.7 ms), which one counter cannot
+    // serve: sub-queues.
+    g.nq = 1;
+    if (mode == 1 || ((mode == 4 || mode == 6) && !big))
     {
-        static const int nq_env = (int)r1_knob("R1_NQ", 0), ch_env = (int)r1_knob("R1_CHUNK", 0);
-        long long nq = nq_env > 0 ? nq_env : R1_SUBQUEUES;
         // a wave only ever pulls from its home sub-queue (r1_trace.hpp: home = (4 (block / 8) + wave) % nq), so every
         // sub-queue needs home waves: the full groups of 8 workgroups must cover all nq residues
-        if (nq > 4 * (blocks / 8))
-            nq = 4 * (blocks / 8);
-        if (nq > (R1_COUNTER_BYTES - 1024) / 128)
-            nq = (R1_COUNTER_BYTES - 1024) / 128;
+        const long long nq = std::min<long long>({nq_env > 0 ? nq_env : R1_SUBQUEUES, 4 * (g.blocks / 8), (R1_COUNTER_BYTES - 1024) / 128});
         if (nq > 1)
         {
-            a.nq = (uint32_t)nq;
-            a.chunk_max = a.chunk_min = ch_env > 0 ? (uint32_t)ch_env : 64u;
+            g.nq = (uint32_t)nq;
+            g.chunk_max = g.chunk_min = chunk_max_env > 0 ? (uint32_t)chunk_max_env : 64u;
         }
     }
-    int land_parity = 0;
-    if (land)
+    return g;
+}
+
+// Landing set-up (tiles resolved inside the trace kernel): the launch's set of queue heads, its record tag, the armed countdowns, where the
+// tiles land and the waves' tile lists.
+// Launches alternate between two sets of queue heads and wave counts; workgroup 0 zeroes the set the launch before used, which nobody
+// touches any more (a workgroup that starts late still asks its own queue for work after the frame's last tile has been summed, so a
+// launch cannot clear its own).  After anything else has run through this context both sets (and the round-3 block) are cleared here.
+// land_prev and land_armed are cleared BEFORE anything here can fail, and they and land_parity are committed by enqueue_frame only once
+// the trace launch is enqueued: until then the context counts as neither, so a call refused from here on (tile lists too long, an
+// allocation, the launch) sends the next one through both memsets and the arming launch — it would otherwise take the set the last
+// launch that ran left exhausted, and no tile would be summed.
+static int land_setup(r1_context *c, const r1_params *p, const Batch *batch, Landing *landing, long long blocks, int block_layout, hipStream_t st,
+                      R1TraceArgs &a, void *&d_out, void *&d_rays, int &land_parity)
+{
+    const int n_frames = batch ? batch->n_frames : 1;
+    const bool prev = c->land_prev, armed = c->land_armed;
+    c->land_prev = false, c->land_armed = false;
+    land_parity = prev ? c->land_parity ^ 1 : 0;
+    if (!prev)
     {
-        // Launches alternate between two sets of queue heads and wave counts; workgroup 0 zeroes the set the launch before used, which
-        // nobody touches any more (a workgroup that starts late still asks its own queue for work after the frame's last tile has been
-        // summed, so a launch cannot clear its own).  After anything else has run through this context both sets (and the round-3 block) are cleared here.
-        // The parity and the armed countdowns are committed only once the trace launch is enqueued: until then the context counts as
-        // neither, so a call refused from here on (tile lists too long, an allocation, the launch) sends the next one through both memsets
-        // and the arming launch — it would otherwise take the set the last launch that ran left exhausted, and no tile would be summed.
-        const bool prev = c->land_prev, armed = c->land_armed;
-        c->land_prev = false, c->land_armed = false;
-        land_parity = prev ? c->land_parity ^ 1 : 0;
-        if (!prev)
-        {
-            R1_HIP(hipMemsetAsync(c->counters.p, 0, R1_COUNTER_BYTES, st));
-            R1_HIP(hipMemsetAsync((char *)c->counters.p + R1_COUNTER_BYTES + 1024, 0, R1_COUNTER_BYTES - 1024, st)); // (not the batch-argument slots in front of it)
-        }
-        char *const set0 = (char *)c->counters.p + 1024, *const set1 = (char *)c->counters.p + R1_COUNTER_BYTES + 1024;
-        a.queue = (uint32_t *)(land_parity ? set1 : set0);
-        a.land.clear_heads = (uint32_t *)(land_parity ? set0 : set1);
-        a.land.clear_count = (R1_COUNTER_BYTES - 1024) / 128;
-        static_assert((R1_COUNTER_BYTES - 1024) / 128 <= R1_BLOCK && R1_COUNTER_TAIL >= 1024 + (R1_COUNTER_BYTES - 1024), "the second set of queue heads fits the tail");
-        // the launch's generation tags its sample records (1 .. 2^24 - 1; on wrap-around the records are wiped).  Advanced at once, even by
-        // a call that is refused later: a tag no launch used costs nothing, one used again could let stale records pass for new ones
-        c->land_gen = (c->land_gen + 1) & 0xFFFFFFu;
-        if (c->land_gen == 0)
-        {
-            R1_HIP(hipMemsetAsync(c->samples.p, 0, c->samples.cap, st));
-            c->land_gen = 1;
-        }
-        a.land_tag = c->land_gen << 8;
-        a.land_res = 1; // (a landing launch: r1_launch_trace checks that the kernel and the launch agree)
-        unsigned long long *frame_rays = (unsigned long long *)((char *)c->counters.p + land_frames_off());
-        uint32_t *frame_left = (uint32_t *)(frame_rays + n_frames);
-        a.land_cnt = (uint32_t *)((char *)frame_rays + (((size_t)n_frames * 16 + 127) & ~(size_t)127)); // (every countdown on a 128-byte line of its own)
-        if (!armed || c->land_frames != n_frames || !same_tiling(c->land_key, *p))
-        {
-            R1_HIP(r1_launch_land_arm(a.land_cnt, frame_rays, frame_left, (uint32_t)n_frames, c->n_local_tiles, p->width, p->height, p->spp, p->tile_w, p->tile_h,
-                                      a.tiles_x, p->shard, p->num_shards, st));
-            c->land_frames = n_frames, c->land_key = *p; // (land_armed: committed with the launch)
-        }
-        if (landing && landing->out && (batch || landing->rays))
-        {
-            d_out = landing->out;
-            if (!batch)
-                d_rays = landing->rays;
-            landing->used = true;
-        }
-        a.land.out = (uint8_t *)d_out;
-        a.land.rays_dst = (unsigned long long *)d_rays;
-        a.land.out_stride = batch ? batch->out_stride : 0;
-        a.land.rays_offset = batch ? batch->rays_offset : 0;
-        a.land.rays_in_out = batch ? 1u : 0u;
-        a.land.frame_rays = frame_rays, a.land.frame_left = frame_left;
-        a.land.n_frames = (uint32_t)n_frames;
-        a.land.block_layout = (uint32_t)block_layout;
-        a.land.inv_spp = (float)(1.0f / p->spp); // rayweek1.cpp:765
-        a.land.error = c->host_word_dev ? (uint32_t *)(c->host_word_dev + 1) : nullptr;
-        {
-            // every wave's list of tiles: a row as long as the launch has tiles (the cursors only move forward: a wave meets a tile at
-            // most once; with uneven residency — twenty frames in flight, a frame's first workgroups do most of its work — a
-            // shorter list overflowed at 250 spp)
-            const size_t tiles_all = (size_t)c->n_local_tiles * n_frames;
-            const size_t bytes = (size_t)blocks * (R1_BLOCK / 64) * tiles_all * 4;
-            if (bytes > ((size_t)2 << 30))
-            {
-                r1_set_error("frames in flight: %zu tiles x %lld waves need %zu MB of tile lists; render this frame synchronously or in shards", tiles_all,
-                             (long long)blocks * (R1_BLOCK / 64), bytes >> 20);
-                return R1_ELIMIT;
-            }
-            if ((rc = ensure(c->land_spill, bytes)))
-                return rc;
-            a.land.owed_spill = (uint32_t *)c->land_spill.p;
-            a.land.spill_stride = (uint32_t)tiles_all;
-        }
-        a.num_rays = nullptr;
+        R1_HIP(hipMemsetAsync(c->counters.p, 0, R1_COUNTER_BYTES, st));
+        R1_HIP(hipMemsetAsync((char *)c->counters.p + R1_COUNTER_BYTES + 1024, 0, R1_COUNTER_BYTES - 1024, st)); // (not the batch-argument slots in front of it)
     }
-    hipEvent_t e0 = c->ev0, e1 = c->ev1, e2 = c->ev2;
+    char *const set0 = (char *)c->counters.p + 1024, *const set1 = (char *)c->counters.p + R1_COUNTER_BYTES + 1024;
+    a.queue = (uint32_t *)(land_parity ? set1 : set0);
+    a.land.clear_heads = (uint32_t *)(land_parity ? set0 : set1);
+    a.land.clear_count = (R1_COUNTER_BYTES - 1024) / 128;
+    static_assert((R1_COUNTER_BYTES - 1024) / 128 <= R1_BLOCK && R1_COUNTER_TAIL >= 1024 + (R1_COUNTER_BYTES - 1024), "the second set of queue heads fits the tail");
+    // the launch's generation tags its sample records (1 .. 2^24 - 1; on wrap-around the records are wiped).  Advanced at once, even by
+    // a call that is refused later: a tag no launch used costs nothing, one used again could let stale records pass for new ones
+    c->land_gen = (c->land_gen + 1) & 0xFFFFFFu;
+    if (c->land_gen == 0)
+    {
+        R1_HIP(hipMemsetAsync(c->samples.p, 0, c->samples.cap, st));
+        c->land_gen = 1;
+    }
+    a.land_tag = c->land_gen << 8;
+    a.land_res = 1; // (a landing launch: r1_launch_trace checks that the kernel and the launch agree)
+    unsigned long long *frame_rays = (unsigned long long *)((char *)c->counters.p + land_frames_off());
+    uint32_t *frame_left = (uint32_t *)(frame_rays + n_frames);
+    a.land_cnt = (uint32_t *)((char *)frame_rays + (((size_t)n_frames * 16 + 127) & ~(size_t)127)); // (every countdown on a 128-byte line of its own)
+    if (!armed || c->land_frames != n_frames || !same_tiling(c->land_key, *p))
+    {
+        R1_HIP(r1_launch_land_arm(a.land_cnt, frame_rays, frame_left, (uint32_t)n_frames, c->n_local_tiles, p->width, p->height, p->spp, p->tile_w, p->tile_h,
+                                  a.tiles_x, p->shard, p->num_shards, st));
+        c->land_frames = n_frames, c->land_key = *p; // (land_armed: committed with the launch)
+    }
+    if (landing && landing->out && (batch || landing->rays))
+    {
+        d_out = landing->out;
+        if (!batch)
+            d_rays = landing->rays;
+        landing->used = true;
+    }
+    a.land.out = (uint8_t *)d_out, a.land.rays_dst = (unsigned long long *)d_rays;
+    a.land.out_stride = batch ? batch->out_stride : 0, a.land.rays_offset = batch ? batch->rays_offset : 0, a.land.rays_in_out = batch ? 1u : 0u;
+    a.land.frame_rays = frame_rays, a.land.frame_left = frame_left;
+    a.land.n_frames = (uint32_t)n_frames, a.land.block_layout = (uint32_t)block_layout;
+    a.land.inv_spp = (float)(1.0f / p->spp); // rayweek1.cpp:765
+    a.land.error = c->host_word_dev ? (uint32_t *)(c->host_word_dev + 1) : nullptr;
+    // every wave's list of tiles: a row as long as the launch has tiles (the cursors only move forward: a wave meets a tile at
+    // most once; with uneven residency — twenty frames in flight, a frame's first workgroups do most of its work — a
+    // shorter list overflowed at 250 spp)
+    const size_t tiles_all = (size_t)c->n_local_tiles * n_frames;
+    const size_t bytes = (size_t)blocks * (R1_BLOCK / 64) * tiles_all * 4;
+    if (bytes > ((size_t)2 << 30))
+    {
+        r1_set_error("frames in flight: %zu tiles x %lld waves need %zu MB of tile lists; render this frame synchronously or in shards", tiles_all,
+                     (long long)blocks * (R1_BLOCK / 64), bytes >> 20);
+        return R1_ELIMIT;
+    }
+    int rc = ensure(c->land_spill, bytes);
+    if (rc)
+        return rc;
+    a.land.owed_spill = (uint32_t *)c->land_spill.p;
+    a.land.spill_stride = (uint32_t)tiles_all;
+    a.num_rays = nullptr;
+    return R1_OK;
+}
+
+// The frame's three events: the context's own, or the next slot of the timing ring (r1_timing_begin)
+static void take_events(r1_context *c, hipEvent_t e[3])
+{
+    e[0] = c->ev0, e[1] = c->ev1, e[2] = c->ev2;
     if (c->ring_on && c->ring_frames > 0)
     {
         const int slot = c->ring_used < c->ring_frames ? c->ring_used : c->ring_frames - 1;
-        e0 = c->ring[3 * slot], e1 = c->ring[3 * slot + 1], e2 = c->ring[3 * slot + 2];
+        e[0] = c->ring[3 * slot], e[1] = c->ring[3 * slot + 1], e[2] = c->ring[3 * slot + 2];
         if (c->ring_used < c->ring_frames)
             ++c->ring_used;
     }
-    if (big || (R1_STACK_LDS_WORDS < R1_STACK_WORDS && (variant == 4 || variant == 5 || grid)))
+}
+
+// What the trace launch finds in memory: the attenuation stack's global workspace, a clean counter block (the last frame's closing launch
+// left it so, or a memset does), the diagnostic builds' wave log, and a zero in the caller's count word where the kernel counts into it.
+static int prepare_memory(r1_context *c, const Choice &k, long long blocks, int per_cu, void *d_rays, hipStream_t st, R1TraceArgs &a)
+{
+    int rc;
+    // (the small-scene tree kernels keep the first 3 * R1_STACK_LDS_WORDS stack entries in LDS and use the workspace beyond)
+    if (k.big || (R1_STACK_LDS_WORDS < R1_STACK_WORDS && (k.tree || k.grid)))
     {
         // sized for the largest grid of this kernel (not this frame's): a frame with a bigger grid must not reallocate
         // (sized for the build that keeps the fewest words in LDS: the latency / diagnostic builds keep R1_STACK_LDS_WORDS, the throughput builds R1_STACK_LDS_WORDS_TP)
-        const size_t entries = big ? R1_STACK_ENTRIES : R1_STACK_ENTRIES - 3 * (R1_STACK_LDS_WORDS < R1_STACK_LDS_WORDS_TP ? R1_STACK_LDS_WORDS : R1_STACK_LDS_WORDS_TP);
+        const size_t entries = k.big ? R1_STACK_ENTRIES : R1_STACK_ENTRIES - 3 * (R1_STACK_LDS_WORDS < R1_STACK_LDS_WORDS_TP ? R1_STACK_LDS_WORDS : R1_STACK_LDS_WORDS_TP);
         const size_t max_blocks = std::max((size_t)blocks, (size_t)c->cus * (size_t)per_cu);
         if ((rc = ensure(c->gstack, entries * max_blocks * R1_BLOCK * 4)))
             return rc;
         a.gstack = (uint32_t *)c->gstack.p;
     }
-    if (!land && !c->counters_clean)
+    if (!k.land && !c->counters_clean)
         R1_HIP(hipMemsetAsync(c->counters.p, 0, R1_COUNTER_BYTES, st));
     c->counters_clean = false;
-    if (variant == 3 || variant == 5 || variant == 8)
+    if (k.stats)
     {
         c->wave_log_waves = (uint32_t)blocks * (R1_BLOCK / 64);
         if ((rc = ensure(c->wave_log, (size_t)c->wave_log_waves * 32)))
@@ -1634,84 +1332,64 @@ static int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int blo
         c->wave_log_ptr = (unsigned long long)c->wave_log.p;
         R1_HIP(hipMemcpyAsync((char *)c->counters.p + 128 + 16 * 8, &c->wave_log_ptr, 8, hipMemcpyHostToDevice, st));
     }
-    if (!fused_clear && !land)
+    if (!k.fused_clear && !k.land)
         R1_HIP(hipMemsetAsync(d_rays, 0, 8, st));
-    R1_HIP(hipEventRecord(e0, st));
-    if (c->total_samples && variant != 6)
-        R1_HIP(r1_launch_trace(&a, variant, big, mode, path ? 1 : 0, (int)blocks, grid && !big ? c->grid_args.lds_bytes : 0u, st));
-    if (c->total_samples && variant == 6)
-    {
-        // wavefront variant: path state, per-level queues and the attenuation stack live in HBM
-        const size_t n = c->total_samples;
-        if (n > ((size_t)1 << 24))
-        {
-            r1_set_error("R1_VARIANT_WAVEFRONT keeps every path of the frame in memory: %zu sample slots > 2^24", n);
-            return R1_ELIMIT;
-        }
-        if ((rc = ensure(c->wf_paths, 3 * n * 16)) || (rc = ensure(c->wf_hits, n * 8)) || (rc = ensure(c->wf_queue, 2 * n * 4)) ||
-            (rc = ensure(c->wf_counts, (R1_STACK_ENTRIES + 2) * 4)) || (rc = ensure(c->gstack, (size_t)R1_STACK_ENTRIES * n * 4)))
-            return rc;
-        R1WaveArgs w;
-        memset(&w, 0, sizeof(w));
-        w.t = a;
-        w.t.gstack = (uint32_t *)c->gstack.p;
-        w.paths = (float4 *)c->wf_paths.p;
-        w.hits = (float2 *)c->wf_hits.p;
-        w.queue[0] = (uint32_t *)c->wf_queue.p;
-        w.queue[1] = (uint32_t *)c->wf_queue.p + n;
-        w.counts = (uint32_t *)c->wf_counts.p;
-        w.n_paths = (uint32_t)n;
-        long long wb = (long long)((n + R1_BLOCK - 1) / R1_BLOCK);
-        if (wb > (long long)c->cus * 8)
-            wb = (long long)c->cus * 8;
-        R1_HIP(hipMemsetAsync(c->wf_counts.p, 0, (R1_STACK_ENTRIES + 2) * 4, st));
-        R1_HIP(r1_launch_wavefront(&w, (int)wb, st));
-        blocks = wb;
-    }
-    R1_HIP(hipEventRecord(e1, st));
+    return R1_OK;
+}
 
-    R1ResolveArgs r;
-    memset(&r, 0, sizeof(r));
-    r.samples = (const float4 *)c->samples.p;
-    r.full = c->full;
-    r.width = p->width, r.height = p->height, r.spp = p->spp;
-    r.tile_w = p->tile_w, r.tile_h = p->tile_h, r.tiles_x = a.tiles_x;
-    r.shard = p->shard, r.num_shards = p->num_shards;
-    r.n_local_tiles = c->n_local_tiles;
-    r.inv_spp = (float)(1.0f / p->spp); // rayweek1.cpp:765
-    r.out = (uint8_t *)d_out;
-    r.block_layout = block_layout;
-    r.n_frames = (uint32_t)n_frames;
-    if (batch)
+// The wavefront variant's launches: path state, per-level queues and the attenuation stack live in HBM.  *blocks: the grid it ran with.
+static int launch_wavefront(r1_context *c, const R1TraceArgs &a, hipStream_t st, long long *blocks)
+{
+    int rc;
+    const size_t n = c->total_samples;
+    if (n > ((size_t)1 << 24))
     {
-        r.out_stride = batch->out_stride, r.rays_offset = batch->rays_offset;
-        r.frame_rays = (unsigned long long *)c->batch_rays.p;
+        r1_set_error("R1_VARIANT_WAVEFRONT keeps every path of the frame in memory: %zu sample slots > 2^24", n);
+        return R1_ELIMIT;
     }
-    if (fused_clear)
-    {
-        r.rays_src = (const unsigned long long *)((char *)c->counters.p + 32);
-        r.rays_dst = (unsigned long long *)d_rays;
-        r.reset = (uint32_t *)c->counters.p;
-    }
+    if ((rc = ensure(c->wf_paths, 3 * n * 16)) || (rc = ensure(c->wf_hits, n * 8)) || (rc = ensure(c->wf_queue, 2 * n * 4)) ||
+        (rc = ensure(c->wf_counts, (R1_STACK_ENTRIES + 2) * 4)) || (rc = ensure(c->gstack, (size_t)R1_STACK_ENTRIES * n * 4)))
+        return rc;
+    R1WaveArgs w;
+    memset(&w, 0, sizeof(w));
+    w.t = a;
+    w.t.gstack = (uint32_t *)c->gstack.p;
+    w.paths = (float4 *)c->wf_paths.p, w.hits = (float2 *)c->wf_hits.p, w.counts = (uint32_t *)c->wf_counts.p;
+    w.queue[0] = (uint32_t *)c->wf_queue.p, w.queue[1] = (uint32_t *)c->wf_queue.p + n;
+    w.n_paths = (uint32_t)n;
+    *blocks = std::min((long long)((n + R1_BLOCK - 1) / R1_BLOCK), (long long)c->cus * 8);
+    R1_HIP(hipMemsetAsync(c->wf_counts.p, 0, (R1_STACK_ENTRIES + 2) * 4, st));
+    R1_HIP(r1_launch_wavefront(&w, (int)*blocks, st));
+    return R1_OK;
+}
+
+// The frame's closing launch: the accumulation and test of a listed pass, the accumulation of a pass, nothing (a landing launch resolved its
+// tiles itself; PIXEL mode wrote pixels), the resolve launch, or — a batch's shard without tiles — its frames' zero counts.
+// fused_clear: that launch publishes the ray count and zeroes the counter block for the next frame, which saves the two memset launches
+// in front of every frame (they cost nothing to execute and ~10 us each to dispatch: a rank of an 8-GPU run renders its share of a frame
+// in 140 us).
+static int close_frame(r1_context *c, const r1_params *p, const Choice &k, const Batch *batch, const Pass *pass, int tiles_x, void *d_out, int block_layout,
+                       void *d_rays, bool throughput_mode, hipStream_t st)
+{
+    const unsigned long long *rays_src = k.fused_clear ? (const unsigned long long *)((char *)c->counters.p + 32) : nullptr;
+    unsigned long long *rays_dst = k.fused_clear ? (unsigned long long *)d_rays : nullptr;
+    uint32_t *reset = k.fused_clear ? (uint32_t *)c->counters.p : nullptr;
     static const int resolve_rows = (int)r1_knob("R1_RESOLVE_ROWS", R1_RESOLVE_ROWS_TP); // tuning experiments
-    if (listed && c->n_local_tiles)
+    if (k.listed && c->n_local_tiles)
     {
         // adaptive sampling: the records go into the listed tiles' two accumulators, their `all` bytes into d_out, and every listed tile is tested
         const int32_t n = pass->first_sample + p->spp;
         R1AdaptArgs ad;
         memset(&ad, 0, sizeof(ad));
-        ad.samples = (const float4 *)c->samples.p;
-        ad.list = pass->list;
+        ad.samples = (const float4 *)c->samples.p, ad.list = pass->list;
         ad.all = (float4 *)c->accum.p, ad.even = (float4 *)c->accum_even.p;
-        ad.out = (uint8_t *)d_out;
-        ad.report = (R1TileReport *)c->adapt_report.p;
+        ad.out = (uint8_t *)d_out, ad.report = (R1TileReport *)c->adapt_report.p;
         ad.width = p->width, ad.height = p->height, ad.spp = p->spp;
-        ad.tile_w = p->tile_w, ad.tile_h = p->tile_h, ad.tiles_x = a.tiles_x;
-        ad.n_listed = pass->n_listed;
-        ad.first_sample = (uint32_t)pass->first_sample;
+        ad.tile_w = p->tile_w, ad.tile_h = p->tile_h, ad.tiles_x = tiles_x;
+        ad.n_listed = pass->n_listed, ad.first_sample = (uint32_t)pass->first_sample;
         ad.inv_all = (float)(1.0f / n), ad.inv_even = (float)(1.0f / ((n + 1) / 2)); // rayweek1.cpp:765 at the samples each accumulator holds
         ad.max_delta = pass->rule->max_delta, ad.mean_delta_q8 = (uint32_t)pass->rule->mean_delta_q8;
-        ad.rays_src = r.rays_src, ad.rays_dst = r.rays_dst, ad.reset = r.reset;
+        ad.rays_src = rays_src, ad.rays_dst = rays_dst, ad.reset = reset;
         R1_HIP(r1_launch_adapt_accum(&ad, st));
     }
     else if (pass && c->n_local_tiles)
@@ -1719,44 +1397,107 @@ static int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int blo
         // progressive pass: the records go into the accumulator, and the preview of samples [0, first_sample + spp) into d_out
         R1AccumArgs ac;
         memset(&ac, 0, sizeof(ac));
-        ac.samples = (const float4 *)c->samples.p;
-        ac.accum = (float4 *)c->accum.p;
+        ac.samples = (const float4 *)c->samples.p, ac.accum = (float4 *)c->accum.p;
         ac.out = pass->image ? (uint8_t *)d_out : nullptr;
-        ac.full = c->full;
+        ac.full = c->full, ac.n_local_tiles = c->n_local_tiles;
         ac.width = p->width, ac.height = p->height, ac.spp = p->spp;
-        ac.tile_w = p->tile_w, ac.tile_h = p->tile_h, ac.tiles_x = a.tiles_x;
-        ac.n_local_tiles = c->n_local_tiles;
+        ac.tile_w = p->tile_w, ac.tile_h = p->tile_h, ac.tiles_x = tiles_x;
         ac.fresh = pass->first_sample == 0 ? 1u : 0u;
         ac.inv_n = (float)(1.0f / (pass->first_sample + p->spp)); // rayweek1.cpp:765 at the accumulated spp
-        ac.rays_src = r.rays_src, ac.rays_dst = r.rays_dst, ac.reset = r.reset;
+        ac.rays_src = rays_src, ac.rays_dst = rays_dst, ac.reset = reset;
         R1_HIP(r1_launch_accum(&ac, st));
     }
-    else if (land)
+    else if (k.land)
         ; // the trace launch resolved its tiles itself
-    else if (c->n_local_tiles && !pixel_mode)
+    else if (c->n_local_tiles && !k.pixel)
+    {
+        R1ResolveArgs r;
+        memset(&r, 0, sizeof(r));
+        r.samples = (const float4 *)c->samples.p;
+        r.full = c->full, r.n_local_tiles = c->n_local_tiles;
+        r.width = p->width, r.height = p->height, r.spp = p->spp;
+        r.tile_w = p->tile_w, r.tile_h = p->tile_h, r.tiles_x = tiles_x;
+        r.shard = p->shard, r.num_shards = p->num_shards;
+        r.inv_spp = (float)(1.0f / p->spp); // rayweek1.cpp:765
+        r.out = (uint8_t *)d_out, r.block_layout = block_layout;
+        r.n_frames = (uint32_t)(batch ? batch->n_frames : 1);
+        if (batch)
+        {
+            r.out_stride = batch->out_stride, r.rays_offset = batch->rays_offset;
+            r.frame_rays = (unsigned long long *)c->batch_rays.p;
+        }
+        r.rays_src = rays_src, r.rays_dst = rays_dst, r.reset = reset;
         R1_HIP(r1_launch_resolve(&r, throughput_mode ? resolve_rows : 0, st));
+    }
     else if (batch) // a shard without tiles: its frames' counts are zero
-        for (int f = 0; f < n_frames; ++f)
+        for (int f = 0; f < batch->n_frames; ++f)
             R1_HIP(hipMemsetAsync((char *)d_out + (size_t)f * batch->out_stride + batch->rays_offset, 0, 8, st));
-    c->counters_clean = fused_clear;
-    c->land_prev = land;
-    if (land)
+    return R1_OK;
+}
+
+// Enqueues the frame (trace + resolve) on `st`.  d_out / d_rays are device addresses; d_rays == NULL stands for the context's own
+// count word (counters + R1_COUNTER_BYTES; the allocation may move in here, so callers take that address afterwards).
+static int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int block_layout, void *d_rays, hipStream_t st,
+                         bool throughput_mode, const Batch *batch, Landing *landing, const Pass *pass)
+{
+    if (!c->have_scene)
+    {
+        r1_set_error("no scene set (call r1_set_scene first)");
+        return R1_EINVAL;
+    }
+    int rc = r1_params_check(p);
+    if (rc)
+        return rc;
+    const int variant = resolve_variant(c, p->variant, throughput_mode);
+    R1_HIP(hipSetDevice(c->device));
+    if ((variant == 7 || variant == 8) && (rc = ensure_grid(c)))
+        return rc;
+    if ((rc = size_tiles(c, p, batch ? batch->n_frames : 1, pass)))
+        return rc;
+    if (!d_rays) // (only now: the counter allocation may have moved)
+        d_rays = (char *)c->counters.p + R1_COUNTER_BYTES;
+    Choice k;
+    if ((rc = choose_kernel(c, p, variant, throughput_mode, batch, pass, k)) || (rc = ensure_records(c, p, k, batch, st)))
+        return rc;
+
+    R1TraceArgs a;
+    frame_args(c, p, k, batch, d_out, block_layout, d_rays, a);
+    if ((rc = put_batch_block(c, k, batch, pass, st, a)))
+        return rc;
+    int per_cu = 1, land_parity = 0;
+    if ((rc = blocks_per_cu(c, k, a, &per_cu)))
+        return rc;
+    const GridSize g = size_grid(c->cus, per_cu, c->total_samples, k.pixel ? a.total_samples : 0u, k.mode, throughput_mode, p->num_shards, k.big != 0);
+    a.chunk_min = g.chunk_min, a.chunk_max = g.chunk_max, a.nq = g.nq;
+    long long blocks = g.blocks;
+    if (k.land && (rc = land_setup(c, p, batch, landing, blocks, block_layout, st, a, d_out, d_rays, land_parity)))
+        return rc;
+    hipEvent_t e[3];
+    take_events(c, e);
+    if ((rc = prepare_memory(c, k, blocks, per_cu, d_rays, st, a)))
+        return rc;
+
+    R1_HIP(hipEventRecord(e[0], st));
+    if (c->total_samples && !k.wavefront)
+        R1_HIP(r1_launch_trace(&a, variant, k.big, k.mode, k.path ? 1 : 0, (int)blocks, k.grid && !k.big ? c->grid_args.lds_bytes : 0u, st));
+    if (c->total_samples && k.wavefront && (rc = launch_wavefront(c, a, st, &blocks)))
+        return rc;
+    R1_HIP(hipEventRecord(e[1], st));
+    if ((rc = close_frame(c, p, k, batch, pass, a.tiles_x, d_out, block_layout, d_rays, throughput_mode, st)))
+        return rc;
+    c->counters_clean = k.fused_clear;
+    c->land_prev = k.land;
+    if (k.land)
         c->land_parity = land_parity, c->land_armed = true;
-    R1_HIP(hipEventRecord(e2, st));
-    c->last0 = e0, c->last1 = e1, c->last2 = e2;
+    R1_HIP(hipEventRecord(e[2], st));
+    c->last0 = e[0], c->last1 = e[1], c->last2 = e[2];
     c->timing_valid = true;
 
-    c->info.blocks = (int32_t)blocks;
-    c->info.tiles_in_kernel = land ? 1 : 0;
-    c->info.threads_per_block = R1_BLOCK;
-    c->info.spheres_active = (int32_t)c->n_active;
-    c->info.spheres_padded = (int32_t)c->n_padded_scene;
-    c->info.groups = (int32_t)c->n_groups;
-    c->info.samples = c->total_samples;
+    c->info.blocks = (int32_t)blocks, c->info.threads_per_block = R1_BLOCK, c->info.samples = c->total_samples;
+    c->info.tiles_in_kernel = k.land ? 1 : 0;
     c->info.kernel = variant; // internal numbering = the public enum (DEFAULT resolved)
-    c->info.bvh_nodes = (int32_t)c->n_bvh_nodes;
-    c->info.bvh_leaves = (int32_t)c->n_bvh_leaves;
-    c->info.bvh_depth = c->bvh_depth;
+    c->info.spheres_active = (int32_t)c->n_active, c->info.spheres_padded = (int32_t)c->n_padded_scene, c->info.groups = (int32_t)c->n_groups;
+    c->info.bvh_nodes = (int32_t)c->n_bvh_nodes, c->info.bvh_leaves = (int32_t)c->n_bvh_leaves, c->info.bvh_depth = c->bvh_depth;
     return R1_OK;
 }
 
@@ -2333,36 +2074,23 @@ static int cast_enqueue(r1_context *c, int structure, int32_t mode, const void *
         structure = 1; // (no sphere can be hit: the reference form's loop of zero trips writes the misses; there is no tree to stage)
     if (structure == 7 && (rc = ensure_grid(c)))
         return rc;
-    // big-scene kernels: as enqueue_frame chooses them (hit indices beyond 10 bits, a node table too large for LDS or a per-node pad; a grid too large for LDS)
-    const bool big = c->n_active > R1_MAX_ACTIVE_10BIT || (structure == 4 && (c->n_bvh_nodes > R1_NODES_LDS_MAX || c->bvh_pad_local)) ||
-                     (structure == 7 && !c->grid_small);
+    const bool big = big_scene(c, structure == 4, structure == 7, false);
     static const int plain_env = (int)r1_knob("R1_CAST_PLAIN", 0); // tuning library only: the plain form of the tree cast (r1_cast.hip), for measuring
     const int plain = structure == 4 && plain_env ? 1 : 0;
 
     R1CastArgs a;
     memset(&a, 0, sizeof(a));
-    a.t.scene.exact = (const float4 *)c->exact.p;
-    a.t.scene.shade = (const float4 *)c->shade.p;
-    a.t.scene.n_active = c->n_active;
-    a.t.scene.bvh_nodes = (const float4 *)c->bvh_nodes.p;
-    a.t.scene.bvh_prims = (const float4 *)c->bvh_prims.p;
-    a.t.scene.bvh_ids = (const uint32_t *)c->bvh_ids.p;
-    for (int k = 0; k < 3; ++k)
-        a.t.scene.bvh_centre[k] = c->bvh_centre[k];
-    a.t.scene.bvh_pad_local = (uint32_t)c->bvh_pad_local;
+    fill_scene(c, a.t.scene); // (the sweep's tables ride along: the cast kernels read none of them)
     // (the grid's fallback and the plain form walk the tree from its root, read from global memory: no root step)
-    a.t.scene.bvh_root_leaf = (structure == 7 || plain) ? 0u : (uint32_t)c->bvh_root_leaf;
-    a.t.scene.bvh_flat_m = c->bvh_flat_m, a.t.scene.bvh_flat_e = c->bvh_flat_e;
-    a.t.bvh_depth = c->bvh_depth > 0 ? c->bvh_depth : 1;
-    // the workgroups' LDS copy of the node table: all of it for small scenes, the breadth-first top (at least node 0) for big ones
-    a.t.bvh_lds_f4 = (structure != 4 || plain) ? 0u : (!big ? 4u * c->n_bvh_nodes : 4u * std::min<uint32_t>(c->n_bvh_nodes, R1_BVH_TOP_NODES));
+    if (structure == 7 || plain)
+        a.t.scene.bvh_root_leaf = 0u;
+    fill_walk(c, structure == 4 && !plain, big, R1_BVH_TOP_NODES, a.t);
     if (structure == 7)
         a.t.grid = (const R1GridArgs *)(big ? c->grid_dev32.p : c->grid_dev.p);
     a.active_to_scene = (const uint32_t *)c->active_dev.p;
     a.mode = (uint32_t)mode;
-    const size_t dyn_lds = structure == 4 ? (plain ? (size_t)a.t.bvh_depth * R1_BLOCK * 4 : (size_t)a.t.bvh_depth * R1_BLOCK * (big ? 4 : 2) + (size_t)a.t.bvh_lds_f4 * 16)
-                           : structure == 7 ? (size_t)a.t.bvh_depth * R1_BLOCK * 4 + (big ? 0 : (size_t)c->grid_args.lds_bytes)
-                                            : 0;
+    // (the plain form: a 32-bit traversal stack and no node table)
+    const size_t dyn_lds = plain ? (size_t)a.t.bvh_depth * R1_BLOCK * 4 : r1_walk_lds(structure, big, a.t.bvh_depth, a.t.bvh_lds_f4, c->grid_args.lds_bytes);
     int &occ = c->cast_occupancy[(structure == 4 ? 0 : structure == 7 ? 2 : 4) + (big ? 1 : 0)];
     if (occ == 0)
         R1_HIP(r1_cast_occupancy(structure, big ? 1 : 0, plain, dyn_lds, &occ));

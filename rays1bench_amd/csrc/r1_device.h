@@ -25,12 +25,12 @@
 #define R1_NODES_LDS_MAX 256  // tree kernel: scenes whose tree has at most this many nodes (16 KB) run the small-scene kernels, which keep
                               // the node table in LDS; bigger trees run the big-scene kernels (node table through the vector L1)
 #define R1_CHUNK 256        // most samples a wave takes from the global queue per atomic (small frames) ...
-#define R1_CHUNK_BIG 1024   // ... growing with a wave's share of the frame up to this (enqueue_frame)
+#define R1_CHUNK_BIG 1024   // ... growing with a wave's share of the frame up to this (r1_capi.cpp size_grid)
 #define R1_CHUNK_MIN 32      // fewest (end of the queue: guided self-scheduling)
 #define R1_GROUP_MAX 4         // spheres per group (level 1 of the sweep tests group bounds)
 #define R1_GROUP_MIN_SPHERES 128 // scenes with fewer active spheres are swept ungrouped
 #define R1_GROUP_RATIO 3.5     // a group's bounding radius stays within this factor of its smallest member radius
-#define R1_SAMPLES_PER_LANE 125    // throughput mode grid sizing: samples each lane should get (see enqueue_frame): 1200x800x10 -> 300
+#define R1_SAMPLES_PER_LANE 125    // throughput mode grid sizing: samples each lane should get (r1_capi.cpp size_grid): 1200x800x10 -> 300
                                    // workgroups per frame.  Re-tuned after DESIGN §4.13 (a cheaper refill shifts the balance towards fewer,
                                    // longer-lived workgroups; tools/spl_sweep2.sh, three alternating rounds): 100 / 115 / 125 / 135 / 150 samples
                                    // -> 36.46 / 36.75 / 36.90 / 37.00 / 37.3 Grays/s over 300 steps and 32.7 / 33.3 / 33.4 / 32.7 / 32.0 over the
@@ -58,43 +58,17 @@
 #ifndef R1_LAND
 #define R1_LAND 1
 #endif
-// per-tile entry nodes: a PRIMARY ray starts its walk below the root's inner child at the deepest node all primary rays of
-// its 32 x 32 tile stay under (computed on the host per camera and tiling, r1_capi.cpp compute_entries); 0: every walk starts at that child.
-// Built, bit-identical, measured and NOT adopted (round 4): 9 % fewer node visits per ray (5.41 -> 4.91 on large 1200x800x10; 42 % of the
-// tiles' primary rays are done after the root step) but 5 % more wave iterations — the primary rays' shorter walks do not shorten the LONGEST
-// walk of a wave, which sets the trips of the divergent loops — and 8 % (table in global memory: a vector-memory wait in the root step) to 12 %
-// (table in LDS: six workgroups per CU instead of seven) FEWER Grays/s (profiles/r04/entry_nodes_ab.txt).
-// `make tuning EXTRA=-DR1_ENTRY=1` builds it; tools/entry_ab.sh runs the parity tests, tools/walk_ab*.sh the A/B.
-#ifndef R1_ENTRY
-#define R1_ENTRY 0
-#endif
-#define R1_ENTRY_LDS_MAX 2048u // tiles per launch up to which the small-scene kernels keep the entry table in LDS (4 KB)
-#define R1_ENTRY_LDS_BYTES(n) ((((size_t)(n) * 2u) + 15u) & ~(size_t)15u)
-#define R1_ENTRY_MODE(mode) (R1_ENTRY && ((mode) == 0 || (mode) == 3 || (mode) == 1))
-// 4-wide nodes for the small-scene tree kernels: the binary tree collapsed on the host (a node takes
-// its grandchildren until it holds four children), seven float4 per node in the workgroup's LDS table, four box tests per trip, the hits
-// pushed far-to-near.  An A/B build: make tuning EXTRA=-DR1_BVH4=1.
 // exhaustive sweep, exact phase (exact_trips): member spheres from a table in group order (one global fetch in the dependent chain instead
-// of two), and the wave's rays as two 16-byte LDS reads per slot instead of six 4-byte ones
+// of two)
 #ifndef R1_EXACT_G
 #define R1_EXACT_G 1
-#endif
-#ifndef R1_RAYS_AOS
-#define R1_RAYS_AOS 0
 #endif
 #ifndef R1_SWEEP_PAIRS2
 #define R1_SWEEP_PAIRS2 1 // exhaustive sweep, group test: two pairs of groups interleaved (sweep_prefilter)
 #endif
-#ifndef R1_BVH4
-#define R1_BVH4 0
-#endif
-#if R1_BVH4 && R1_ENTRY
-#error "R1_ENTRY's table holds references into the binary tree: not with R1_BVH4"
-#endif
-#ifndef R1_LAND_SYNC
-#define R1_LAND_SYNC 0 // 1: the synchronous frame's kernels (MODE 1) too — measured and not adopted: 1.276 against 1.077 ms on the device (the tiles a wave owes are summed at ITS exit, i.e. at the end of the frame's critical path; the resolve launch sums all 950 in 26 us with the whole chip), profiles/r04/land_sync_frame.txt
-#endif
-#define R1_LAND_MODE(mode) (R1_LAND && ((mode) == 0 || (mode) == 3 || (mode) == 5 || (R1_LAND_SYNC && (mode) == 1)))
+// (the synchronous frame's kernels, MODE 1, keep the resolve launch: 1.276 against 1.077 ms on the device with their tiles summed at wave
+// exit, i.e. at the end of the frame's critical path; profiles/r04/land_sync_frame.txt)
+#define R1_LAND_MODE(mode) (R1_LAND && ((mode) == 0 || (mode) == 3 || (mode) == 5))
 #define R1_LAND_CNT_STRIDE 32u  // words between two tiles' countdowns: every countdown on its own 128-byte line (an atomic on ONE line sustains ~88 M/s on this chip,
                                // tools/ubench_atomic.hip; the ~40 tiles a synchronous frame's waves work on at a time shared two lines at first: 3.8 ms per frame instead of 1.1)
 #define R1_LAND_MAX_WAIT (1u << 16) // passes over a claimed tile that still find a record of an earlier launch before the wave gives up and flags the launch
@@ -280,18 +254,26 @@ struct R1TraceArgs
     uint32_t *land_cnt;           // [n_frames * n_local_tiles] x R1_LAND_CNT_STRIDE words: samples each tile still lacks; the tracing waves subtract, the wave that
                                   // owes the tile re-arms
     R1LandArgs land;
-    union
-    {
-        const float4 *bvh_wide;   // R1_BVH4: the 4-wide table the small-scene kernels copy into LDS instead of scene.bvh_nodes (bvh_lds_f4 float4)
-        const R1GridArgs *grid;   // R1_VARIANT_GRID: the grid's arguments, in device memory (one word here: the other kernels' argument block
-    };                            // keeps its size and layout, and so their code)
-    uint32_t entry_lds;           // R1_ENTRY, small-scene kernels, single frames: the workgroups keep the table as 16-bit words in LDS behind their node table (0: read from bvh_entry)
-    const uint32_t *bvh_entry;    // R1_ENTRY: [n_frames * n_local_tiles] child reference (the kernel's form) a primary ray of that tile starts at after the root step
+    const R1GridArgs *grid;       // R1_VARIANT_GRID: the grid's arguments, in device memory (one pointer here: the other kernels' argument block
+                                  // keeps its size and layout, and so their code)
     uint32_t coop_lanes;          // small scenes: once the queue is empty, a wave with <= coop_lanes live paths tests each of them
                                   // against ALL spheres, 64 at a time across the wave (cooperative_sweep), instead of walking the tree
                                   // with 60 lanes masked off: the frame's tail is a few 51-bounce chains, and this shortens a step
                                   // of such a chain from ~16 k cycles of dependent node fetches to ~4 k
 };
+
+// Dynamic LDS of a workgroup that walks the box tree (structure 4) or the uniform grid (7), trace and cast kernels alike; 0 for anything else.
+// Tree: the traversal stack — bvh_depth entries per thread, 16-bit for small scenes and 32-bit for big ones — then bvh_lds_f4 float4 of the
+// node table.  Grid: the tree fallback's stack (32-bit entries), then (small scenes) grid_lds bytes of cell table and ids.  The occupancy
+// query and the launch both size by this one function: the grid of a frame is sized for the occupancy its launch has.
+static inline size_t r1_walk_lds(int structure, bool big, int32_t bvh_depth, uint32_t bvh_lds_f4, size_t grid_lds)
+{
+    if (structure == 4)
+        return (size_t)bvh_depth * R1_BLOCK * (big ? 4 : 2) + (size_t)bvh_lds_f4 * 16;
+    if (structure == 7)
+        return (size_t)bvh_depth * R1_BLOCK * 4 + (big ? 0 : grid_lds);
+    return 0;
+}
 
 // Wavefront variant (R1_VARIANT_WAVEFRONT): the same path tracer split into
 // generate / intersect / shade kernels with the paths and per-level queues in HBM.

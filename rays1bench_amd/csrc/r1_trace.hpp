@@ -107,7 +107,7 @@ __device__ __forceinline__ void fresh_args(R1ArgWords &u)
 #define R1_G(f) u.a.f = global_ptr_at<__typeof__(*u.a.f)>(k, __builtin_offsetof(R1TraceArgs, f));
     R1_G(scene.sweep) R1_G(scene.exact) R1_G(scene.shade) R1_G(scene.exact_g) R1_G(scene.members) R1_G(scene.mat) R1_G(scene.bvh_nodes) R1_G(scene.bvh_prims)
     R1_G(scene.bvh_ids) R1_G(queue) R1_G(samples) R1_G(num_rays) R1_G(gstack) R1_G(stats) R1_G(land_cnt) R1_G(land.out) R1_G(land.rays_dst)
-    R1_G(land.frame_rays) R1_G(land.frame_left) R1_G(land.clear_heads) R1_G(land.owed_spill) R1_G(land.error) R1_G(bvh_wide) R1_G(bvh_entry)
+    R1_G(land.frame_rays) R1_G(land.frame_left) R1_G(land.clear_heads) R1_G(land.owed_spill) R1_G(land.error) R1_G(grid)
 #undef R1_G
 }
 #define R1_FRESH_ARGS(L)                                                                                                                  \
@@ -342,14 +342,8 @@ __device__ __forceinline__ void exact_trips(const R1DeviceScene &S, const V3 o, 
         V3 ro, rd;
         if (rays)
         {
-#if R1_RAYS_AOS
-            const float *w = rays + (owner >> 3) * R1_BLOCK + (owner & 7) * 8;
-            const f4 r0 = *(const f4 *)w, r1 = *(const f4 *)(w + 4);
-            ro = mk(r0.x, r0.y, r0.z), rd = mk(r0.w, r1.x, r1.y);
-#else
             ro = mk(rays[0 * R1_BLOCK + owner], rays[1 * R1_BLOCK + owner], rays[2 * R1_BLOCK + owner]);
             rd = mk(rays[3 * R1_BLOCK + owner], rays[4 * R1_BLOCK + owner], rays[5 * R1_BLOCK + owner]);
-#endif
         }
         else
         {
@@ -375,15 +369,8 @@ __device__ __forceinline__ const float *publish_rays(uint32_t *scratch /* [>= 6]
 {
     float *t = (float *)scratch;
     __builtin_amdgcn_wave_barrier(); // every lane has read what it needed from the scratch rows
-#if R1_RAYS_AOS
-    // eight words per ray, side by side: the wave's 64 columns of rows 0..7 hold rays 8 r .. 8 r + 7 in row r (ray_at)
-    float *w = t + (tid & ~63) + ((tid & 63) >> 3) * R1_BLOCK + (tid & 7) * 8;
-    *(f4 *)w = f4{o.x, o.y, o.z, d.x};
-    *(f4 *)(w + 4) = f4{d.y, d.z, 0.0f, 0.0f};
-#else
     t[0 * R1_BLOCK + tid] = o.x, t[1 * R1_BLOCK + tid] = o.y, t[2 * R1_BLOCK + tid] = o.z;
     t[3 * R1_BLOCK + tid] = d.x, t[4 * R1_BLOCK + tid] = d.y, t[5 * R1_BLOCK + tid] = d.z;
-#endif
     __builtin_amdgcn_wave_barrier();
     return t + (tid & ~63);
 }
@@ -454,7 +441,7 @@ __device__ __forceinline__ void cooperative_bits(const R1DeviceScene &S, const V
                     pairs[pos_s--] = v;
             }
         }
-        static_assert(R1_BIT_WORDS >= (R1_RAYS_AOS ? 8 : 6) && R1_CAND_CAP >= 8, "the ray table needs six (eight: side-by-side form) rows of the flag words");
+        static_assert(R1_BIT_WORDS >= 6 && R1_CAND_CAP >= 8, "the ray table needs six rows of the flag words");
         const float *rays = publish_rays(const_cast<uint32_t *>(words), o, d, tid); // the words of this batch are consumed
         exact_trips<STATS, IDX, R1_GROUP_MAX>(S, o, d, total_m, pairs, best, lane, wstat, rays);
         exact_trips<STATS, IDX, 1>(S, o, d, total_s, pairs + (CAP - total_s), best, lane, wstat, rays);
@@ -819,12 +806,9 @@ __device__ __forceinline__ void trav_start(Trav &t)
 // utilisation of the node / leaf steps 0.53 / 0.69 -> 0.74 / 0.75, and 5 % SLOWER once the node table sat in LDS, because
 // the vote costs ~20 VALU instructions per trip; removed in round 3)
 // LN: the node table is read from `lnodes`, the workgroup's copy in LDS (the trace kernel on small scenes), instead of S.bvh_nodes.
-// ENTRY: `entry_at` (null for every ray but a primary one) points at the reference the walk goes on at after the root step instead of
-// the root's inner child: the deepest node every primary ray of the tile stays under (r1_capi.cpp compute_entries).
-template <bool STATS, bool CARRY, bool LN, typename TS, bool ENTRY = false>
+template <bool STATS, bool CARRY, bool LN, typename TS>
 __device__ __forceinline__ void bvh_advance(const R1DeviceScene &S, const V3 o, const V3 d, Trav &tv, TS *trav, const int tid,
-                                            const uint32_t n_alive, unsigned long long *wstat, const float4 *lnodes /* LDS */, const uint32_t top = 0u /* !LN: nodes [0, top) are in lnodes */,
-                                            const uint32_t *entry_tab = nullptr, const uint32_t entry_idx = 0xFFFFFFFFu, const uint16_t *entry_lds = nullptr /* LDS; null: entry_tab */)
+                                            const uint32_t n_alive, unsigned long long *wstat, const float4 *lnodes /* LDS */, const uint32_t top = 0u /* !LN: nodes [0, top) are in lnodes */)
 {
     const float4 *__restrict__ nodes = S.bvh_nodes;
     const float4 *__restrict__ prims = S.bvh_prims;
@@ -858,50 +842,6 @@ __device__ __forceinline__ void bvh_advance(const R1DeviceScene &S, const V3 o, 
             if ((tid & 63) == __ffsll((long long)__ballot(1)) - 1)
                 wstat[2] += 1;
         }
-#if R1_BVH4
-        if (LN)
-        {
-            // a 4-wide node (r1_capi.cpp build_wide): two child PAIRS in the binary node's row form — {m0x m1x m0y m1y} {m0z m1z e0x e1x}
-            // {e0y e1y e0z e1z}, twice — and {ref[4]}.  Four box tests; every hit becomes ONE word — the upper half of its entry distance
-            // (clamped at 0: the bits of a float >= 0 order as integers) over its 16-bit reference, all ones for a miss — the four words
-            // are sorted (5 min / max pairs), the nearest is visited next and the others go on the stack far-to-near.
-            // (the second pair is fetched after the first is tested — the index passes through the asm statement together with the first
-            //  pair's words: 24 live node floats at once do not fit the 72 registers of the 7-wave build)
-            uint32_t at = 7u * cur;
-            const uint4 rf = *(const uint4 *)(lnodes + at + 6u);
-            float t0, t1, t2, t3;
-            float4 q0 = lnodes[at + 0u], q1 = lnodes[at + 1u], q2 = lnodes[at + 2u];
-            const bool g0 = bvh_box(q0.x, q0.z, q1.x, q1.z, q2.x, q2.z, pa_ray, oi, inv, ainv, best, t0);
-            const bool g1 = bvh_box(q0.y, q0.w, q1.y, q1.w, q2.y, q2.w, pa_ray, oi, inv, ainv, best, t1);
-            uint32_t k0 = g0 ? ((__float_as_uint(fmaxf(t0, 0.0f)) & 0xFFFF0000u) | rf.x) : 0xFFFFFFFFu;
-            uint32_t k1 = g1 ? ((__float_as_uint(fmaxf(t1, 0.0f)) & 0xFFFF0000u) | rf.y) : 0xFFFFFFFFu;
-            asm volatile("" : "+v"(at), "+v"(k0), "+v"(k1));
-            q0 = lnodes[at + 3u], q1 = lnodes[at + 4u], q2 = lnodes[at + 5u];
-            const bool g2 = bvh_box(q0.x, q0.z, q1.x, q1.z, q2.x, q2.z, pa_ray, oi, inv, ainv, best, t2);
-            const bool g3 = bvh_box(q0.y, q0.w, q1.y, q1.w, q2.y, q2.w, pa_ray, oi, inv, ainv, best, t3);
-            uint32_t k2 = g2 ? ((__float_as_uint(fmaxf(t2, 0.0f)) & 0xFFFF0000u) | rf.z) : 0xFFFFFFFFu;
-            uint32_t k3 = g3 ? ((__float_as_uint(fmaxf(t3, 0.0f)) & 0xFFFF0000u) | rf.w) : 0xFFFFFFFFu;
-            uint32_t lo, hi;
-            lo = min(k0, k1), hi = max(k0, k1), k0 = lo, k1 = hi;
-            lo = min(k2, k3), hi = max(k2, k3), k2 = lo, k3 = hi;
-            lo = min(k0, k2), hi = max(k0, k2), k0 = lo, k2 = hi;
-            lo = min(k1, k3), hi = max(k1, k3), k1 = lo, k3 = hi;
-            lo = min(k1, k2), hi = max(k1, k2), k1 = lo, k2 = hi;
-            if (k3 != 0xFFFFFFFFu)
-                trav_put(trav, sp * R1_BLOCK + tid, k3 & 0xFFFFu), ++sp;
-            if (k2 != 0xFFFFFFFFu)
-                trav_put(trav, sp * R1_BLOCK + tid, k2 & 0xFFFFu), ++sp;
-            if (k1 != 0xFFFFFFFFu)
-                trav_put(trav, sp * R1_BLOCK + tid, k1 & 0xFFFFu), ++sp;
-            if (k0 != 0xFFFFFFFFu)
-                cur = k0 & 0xFFFFu;
-            else if (sp > 0)
-                cur = trav_get(trav, --sp * R1_BLOCK + tid);
-            else
-                cur = R1_BVH_DONE;
-            return;
-        }
-#endif
         // {m0x m1x m0y m1y} {m0z m1z e0x e1x} {e0y e1y e0z e1z} {A K child0 child1}
         float4 q0, q1, q2, q3;
         if (LN || cur < top)
@@ -916,7 +856,7 @@ __device__ __forceinline__ void bvh_advance(const R1DeviceScene &S, const V3 o, 
         float tn0, tn1;
         // The pad.  Table in LDS (LN): A R2 |1/d| of the whole tree, computed once per call (`pa_ray`; the nodes' K are part of
         // their half extents, r1_bvh.cpp).  Table in global memory: per node, pad = A dist2 + K with dist2 = R2 or — wave-uniform,
-        // scenes of small spheres — |m0 + m1 - 2 o|^2; such trees always run through these kernels (r1_capi.cpp enqueue_frame).
+        // scenes of small spheres — |m0 + m1 - 2 o|^2; such trees always run through these kernels (r1_capi.cpp big_scene).
         V3 pa = pa_ray;
         if (!LN)
         {
@@ -962,7 +902,6 @@ __device__ __forceinline__ void bvh_advance(const R1DeviceScene &S, const V3 o, 
     // their own, spilled 5-22 VGPRs to scratch in the 72-register builds; this form leaves every tree kernel the VGPR count it had.
     // F = min(a_u + b_u, best) follows `best` where it moves — after a leaf: recomputed before each run of the node loop instead, the
     // synchronous-frame and PIXEL kernels took 1-6 VGPRs more and the rate was 0.1 % lower.
-    constexpr bool FLAT_OK = LN && !ENTRY && !R1_BVH4;
     auto visit_flat = [&]() {
         if (STATS)
         {
@@ -1007,7 +946,7 @@ __device__ __forceinline__ void bvh_advance(const R1DeviceScene &S, const V3 o, 
         const int k = root_leaf == 1u ? 1 : 0; // column of the OTHER child in the node's rows
         const float *nf = (const float *)lnodes; // node 0: always in the workgroup's LDS copy (big scenes keep the top of the tree there: at least node 0, r1_capi.cpp)
         const uint32_t leaf = __float_as_uint(nf[14 + (1 - k)]);
-        uint32_t other = __float_as_uint(nf[14 + k]);
+        const uint32_t other = __float_as_uint(nf[14 + k]);
         const uint32_t lp = (leaf >> COUNT_SHIFT) & 7u;
         if (STATS)
         {
@@ -1031,31 +970,17 @@ __device__ __forceinline__ void bvh_advance(const R1DeviceScene &S, const V3 o, 
         }
         float tn;
         const bool h = bvh_box(nf[0 + k], nf[2 + k], nf[4 + k], nf[6 + k], nf[8 + k], nf[10 + k], pa, oi, inv, ainv, best, tn);
-        if (ENTRY && entry_idx != 0xFFFFFFFFu && h)
-        {
-            if (LN && entry_lds != nullptr) // (wave-uniform)
-            {
-                other = entry_lds[entry_idx];
-                other = other == 0xFFFFu ? R1_BVH_DONE : other;
-            }
-            else
-                other = ((const r1_gu32 *)entry_tab)[entry_idx];
-        }
         cur = h ? other : R1_BVH_DONE;
         // (the sibling's own visit taken into this step as well — `if (cur < LEAF_BIT) visit_node();` here — measured 35.5 against 36.2
         //  Grays/s: a generic visit runs at 0.54 lane utilisation inside the loop and at the ~0.34 of the starting lanes out here)
     }
-#if R1_BVH4
-    if (LN && cur == 0u)
-        cur = 1u; // a tree without the root step: slot 0 of the 4-wide table is the binary root for the root step's use, the collapsed root is node 1
-#endif
     // Flat trees: the slab, once per call and after the root step (its leaf has moved `best`, and it tests node 0's box with all three
     // axes).  A ray whose slab interval is empty, N > F, is done — whatever its walk still holds lies in the slab (every leaf box below
     // the boxes of the loop does), so every test it could still make would fail: the root step's "N <= F", which holds as well for a walk
     // carried over from an earlier call.
     // (the flag is made a scalar: the compiler cannot know that a value from LDS is wave-uniform, and a branch it takes for divergent runs
     //  both node loops one after the other)
-    if (FLAT_OK && (__builtin_amdgcn_readfirstlane((int)__float_as_uint(lnodes[3].y)) & 4) != 0)
+    if (LN && (__builtin_amdgcn_readfirstlane((int)__float_as_uint(lnodes[3].y)) & 4) != 0)
     {
         const float a_u = __fmaf_rn(lnodes[7].x, inv.y, -oi.y), b_u = __fmaf_rn(lnodes[7].y, ainv.y, pa_ray.y);
         const float tyf = a_u + b_u;
@@ -1072,7 +997,7 @@ __device__ __forceinline__ void bvh_advance(const R1DeviceScene &S, const V3 o, 
         if (CARRY && R1_CARRY_DIV * (uint32_t)__popcll(walking) <= n_alive)
             break; // (n_alive <= 3: never true while a lane walks, so the last walks of a wave run to their end)
         // inner nodes: descend to the nearer child, remember the farther one
-        if (FLAT_OK && (__builtin_amdgcn_readfirstlane((int)__float_as_uint(lnodes[3].y)) & 4) != 0)
+        if (LN && (__builtin_amdgcn_readfirstlane((int)__float_as_uint(lnodes[3].y)) & 4) != 0)
             while (cur < LEAF_BIT)
                 visit_flat();
         else
@@ -1096,7 +1021,7 @@ __device__ __forceinline__ void bvh_advance(const R1DeviceScene &S, const V3 o, 
                 leaf_quad(prims, ids, first + j, take, o, d, best, best_id);
             }
             cur = sp > 0 ? trav_get(trav, --sp * R1_BLOCK + tid) : R1_BVH_DONE;
-            if (FLAT_OK && (__builtin_amdgcn_readfirstlane((int)__float_as_uint(lnodes[3].y)) & 4) != 0)
+            if (LN && (__builtin_amdgcn_readfirstlane((int)__float_as_uint(lnodes[3].y)) & 4) != 0)
                 pa_ray.y = best < pa_ray.y ? best : pa_ray.y; // F = min(a_u + b_u, best): best has moved in the leaf, and only down
         }
     }
@@ -1624,9 +1549,6 @@ __device__ __forceinline__ bool shade_level(const R1TraceArgs &A, Path &p, const
 //     that finds a record of an earlier launch in a tile it owes simply reads the tile again (past the vector L1: sc0 loads).
 // Per launch, behind the queue pointer (one of two sets, zeroed by the launch after): line x = XCD x's cursor (uint64); line 16 = the
 // launch's next unclaimed tile.
-#ifndef R1_LAND_EXP
-#define R1_LAND_EXP 0 // measurements only (make tuning EXTRA=-DR1_LAND_EXP=n; frames are NOT valid): 1 no tile is resolved, 2 and no countdown atomics
-#endif
 #define R1_LAND_OWED 24u        // tiles of a wave's list kept in LDS (the rest: its row of the spill area in global memory)
 #define R1_LAND_LOADS 8      // records of one pixel a lane keeps in flight while it sums a tile (4 registers each; 10 spill in the 72-register builds)
 #define R1_LAND_MAX_XCD 8u
@@ -1665,7 +1587,7 @@ __device__ __forceinline__ void land_note(const R1TraceArgs &A, uint32_t *row, c
 // stalled the wave for a memory-side round trip at every chunk: +3 % per frame).  Who sums the tile is settled when waves exit.
 __device__ __forceinline__ void land_flush(const R1TraceArgs &A, const uint32_t t, const uint32_t n)
 {
-    if (n == 0u || R1_LAND_EXP >= 2)
+    if (n == 0u)
         return;
     (void)__hip_atomic_fetch_sub(A.land_cnt + t * R1_LAND_CNT_STRIDE, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -1783,11 +1705,6 @@ __device__ __forceinline__ bool land_resolve_tile(const R1TraceArgs &A, const ui
 template <int LOADS>
 __device__ __forceinline__ void land_exit(const R1TraceArgs &A, uint32_t *row, const int lane)
 {
-    if (R1_LAND_EXP)
-        return;
-#ifdef R1_LAND_EXIT_PRIO
-    __builtin_amdgcn_s_setprio(R1_LAND_EXIT_PRIO); // (a wave that sums tiles holds its workgroup's slot: let it finish first)
-#endif
     if (lane == 0)
     {
         land_flush(A, row[2], row[3]);
@@ -1890,7 +1807,7 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
     constexpr bool LAT = MODE == 1 || (PASS && !BIG), PIX = MODE == 2, BATCH = MODE == 3 || CPATH; // MODE 3 = MODE 0 whose queue spans the frames of a batch
     // tiles resolved inside the kernel: the throughput builds of the tree kernels (frames in flight, MODE 0 / 3); a
     // launch through them is a landing launch (r1_launch_trace checks).  The synchronous frame keeps the resolve launch (measured
-    // slower with its tiles summed at wave exit, R1_LAND_SYNC), and so do the exhaustive sweep's kernels.
+    // slower with its tiles summed at wave exit), and so do the exhaustive sweep's kernels.
     constexpr bool LAND = R1_LAND_MODE(MODE) && !STATS && VARIANT == 4; // (the exhaustive sweep keeps the resolve launch: its loop pays 14 % for the bookkeeping, 16.6 against 19.2 Grays/s)
     const uint32_t tb = blockIdx.x, n_tb = gridDim.x;
     // LAND: this workgroup's XCD (HW_REG_XCC_ID), the tiles of the launch
@@ -1963,8 +1880,8 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
         float4 *dst = (float4 *)(s_trav + trav_words);
         for (uint32_t i = (uint32_t)tid; i < A.bvh_lds_f4; i += R1_BLOCK)
         {
-            float4 q = (R1_BVH4 && LN) ? A.bvh_wide[i] : A.scene.bvh_nodes[i]; // (4-wide table: references already in the 16-bit form)
-            if (LN && !R1_BVH4 && (i & 3u) == 3u) // {A K child0 child1}: the small-scene kernels walk with 16-bit child references
+            float4 q = A.scene.bvh_nodes[i];
+            if (LN && (i & 3u) == 3u) // {A K child0 child1}: the small-scene kernels walk with 16-bit child references
                 q.z = __uint_as_float(r1_ref16(__float_as_uint(q.z))), q.w = __uint_as_float(r1_ref16(__float_as_uint(q.w)));
             dst[i] = q;
         }
@@ -1973,12 +1890,9 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
         // (bit 2 of the code: a flat tree, whose y slab sits in node 1's pad slots — A again and a zero in the table, and the node loop fetches
         //  neither from LDS; r1_bvh.cpp "flat axis", a flat tree has at least two nodes)
         if (LN && tid == 3)
-            ((float *)dst)[13] = __uint_as_float(A.scene.bvh_root_leaf | ((!R1_BVH4 && A.scene.bvh_flat_e >= 0.0f) ? 4u : 0u));
-        if (LN && !R1_BVH4 && tid == 7 && A.scene.bvh_flat_e >= 0.0f)
+            ((float *)dst)[13] = __uint_as_float(A.scene.bvh_root_leaf | (A.scene.bvh_flat_e >= 0.0f ? 4u : 0u));
+        if (LN && tid == 7 && A.scene.bvh_flat_e >= 0.0f)
             ((float *)dst)[28] = A.scene.bvh_flat_m, ((float *)dst)[29] = A.scene.bvh_flat_e;
-        if (LN && !BATCH && R1_ENTRY_MODE(MODE) && A.entry_lds) // the primary rays' entry nodes, 16 bits each (all ones: the walk is over after the root step)
-            for (uint32_t i = (uint32_t)tid; i < A.entry_lds; i += R1_BLOCK)
-                ((uint16_t *)(dst + A.bvh_lds_f4))[i] = (uint16_t)A.bvh_entry[i];
         __syncthreads();
     }
 
@@ -2242,16 +2156,12 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
         else if (VARIANT == 4)
         {
             // while-while with carry-over
-            constexpr bool ENTRY = R1_ENTRY_MODE(MODE);
 #if R1_FRESH
             R1_FRESH_ARGS(HA) // (table pointers, the tree's centre: fetched for the walk, free again after it)
 #else
             const R1TraceArgs &HA = A;
 #endif
-            // (a primary ray that starts its walk: depth 0 and at the root)
-            const uint32_t entry_idx = ENTRY && p.depth == 0 && tv.cur == 0u ? fastdiv(p.k, HA.div_full) : 0xFFFFFFFFu;
-            bvh_advance<STATS, true, LN, TS, ENTRY>(HA.scene, p.o, p.d, tv, (TS *)s_trav, tid, (uint32_t)__popcll(live_now), wstat, lnodes, top, HA.bvh_entry, entry_idx,
-                                                    (LN && !BATCH && HA.entry_lds) ? (const uint16_t *)(lnodes + HA.bvh_lds_f4) : nullptr);
+            bvh_advance<STATS, true, LN, TS>(HA.scene, p.o, p.d, tv, (TS *)s_trav, tid, (uint32_t)__popcll(live_now), wstat, lnodes, top);
             ready = alive && tv.cur == R1_BVH_DONE;
             if (tv.best_id != 0xFFFFFFFFu)
                 t_hit = tv.best, hit = (int)tv.best_id;

@@ -416,7 +416,7 @@ def test_non_finite_spheres_are_never_hit(renderer):
         assert got[1] == orays and got[2].tobytes() == osamples.tobytes(), v
 
 
-# ---- per-tile entry nodes --------------------------------------------------------------------------------------
+# ---- the root step under adversarial cameras ---------------------------------------------------------------------------------------
 
 
 def _look(lookfrom, lookat, vfov, aspect, aperture, focus, vup=(0, 1, 0)):
@@ -449,10 +449,11 @@ ENTRY_CAMERAS = {
 @pytest.mark.parametrize("cam", list(ENTRY_CAMERAS))
 @pytest.mark.parametrize("name,w,h,spp,tile", [("large", 192, 128, 3, 32), ("large", 100, 75, 2, 8), ("medium", 128, 96, 4, 16), ("grid", 96, 64, 2, 16)])
 def test_entry_nodes_keep_every_hit(renderer, cam, name, w, h, spp, tile):
-    """A primary ray starts below the root's inner child at the node all primary rays of its tile stay under (r1_capi.cpp
-    compute_entries).  Whatever the camera — a lens wider than the lattice's cells, an origin among the small spheres, a view away
-    from the scene, a focal plane closer than the lens radius — the samples are the oracle's to the bit, through the synchronous
-    frame (MODE 1) and through the frames-in-flight kernel (MODE 0, tiles summed in the kernel)."""
+    """Every walk starts with the root step: the root's leaf, then the box of its inner child (bvh_advance).  Whatever the camera — a
+    lens wider than the lattice's cells, an origin among the small spheres, a view away from the scene, a focal plane closer than the
+    lens radius — the samples are the oracle's to the bit, through the synchronous frame (MODE 1) and through the frames-in-flight
+    kernel (MODE 0, tiles summed in the kernel).  (Written for the per-tile entry nodes of DESIGN.md §4.11, whose code is gone: hence
+    the name.)"""
     sc = r1.create_grid_scene(w, h, 48, 36) if name == "grid" else MAKE[name](w, h)  # (grid: the big-scene kernels, pads measured per node)
     sa = oracle_scene(sc)
     if ENTRY_CAMERAS[cam] is not None:
