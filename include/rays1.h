@@ -174,6 +174,44 @@ int r1_set_scene(r1_context *ctx, const r1_scene *scene, const r1_camera *camera
  * first_sample > 0 returns R1_EINVAL).  r1_set_scene(the same arrays, this camera) afterwards still finds everything current. */
 int r1_set_camera(r1_context *ctx, const r1_camera *camera);
 
+/* ---- moving spheres ---- */
+
+/* New centres for the spheres [first, first + count) of the scene: SCENE indices into the arrays given to the last r1_set_scene,
+ * placeholders counted; entries of spheres that are not active (inv_radius == 0, or non-finite at r1_set_scene) are ignored.  Radii,
+ * materials, the active set and the active order do not change: only r1_set_scene changes them.  x, y, z are host memory, `count`
+ * floats each, read during the call only (through a page-locked staging buffer of the context).  The centres are written in place
+ * into the tables the box-tree kernels read and the tree is REFITTED on the device: its topology stays, every box is recomputed
+ * bottom-up from the new centres in the builder's own arithmetic (r1_bvh_fill.h), one small launch per height of the tree.  Leaves
+ * apply the reference's own per-sphere test, ties go to the lowest active index and a box only has to be conservative, so every render
+ * and every ray query afterwards gives bit-identical pixels, ray counts and hit records to a fresh context after r1_set_scene with the
+ * moved arrays; a tree whose topology has gone stale only visits more nodes (what tools/update_bench.py measures of
+ * that, and so the point at which r1_set_scene pays).
+ * Everything is enqueued on `hip_stream` (a hipStream_t; NULL = the context's stream) and nothing is waited for but the previous
+ * update's reading of the staging buffer: work enqueued earlier on that stream sees the old scene, work enqueued later the new one.
+ * What keeps working: renders with R1_VARIANT_DEFAULT, _BVH, _BVH_STATS and _REFERENCE (which reads only the sphere table the update
+ * rewrites), r1_cast_rays* with DEFAULT, BVH and REFERENCE.  What stops until the next r1_set_scene: the sphere groups of the
+ * exhaustive sweep and the uniform grid are NOT refitted, so R1_VARIANT_PREFILTER, _STATS, _WAVEFRONT, _GRID and _GRID_STATS renders
+ * and a GRID cast return R1_EINVAL (r1_last_error says that the scene has moved and that r1_set_scene rebuilds them).  The tree's flat
+ * y slab (r1_bvh_info.flat_axis) is dropped: the kernels take their generic loop.
+ * R1_EINVAL before the first r1_set_scene, for first + count beyond the scene's count, for NULL pointers with count > 0, and for a
+ * non-finite new centre of an ACTIVE sphere (nothing is changed or enqueued then); count == 0 is R1_OK and touches nothing.  An update
+ * ends a progressive accumulation as r1_set_camera does and leaves r1_last_launch_info / r1_last_timing alone.  The context's host
+ * copies of the centres follow, but after ANY update r1_set_scene rebuilds everything, whatever arrays it is given (the original ones
+ * included), and re-enables every variant.
+ * One update at a time per context: an update rewrites the context's tables in place through ONE scratch area and changes the context's
+ * host state (the refused variants, the dropped slab) when it is ENQUEUED, not when it runs.  Updates of one context therefore go to
+ * one stream, or the caller orders them; renders and casts that must see a given state go to that stream too, or are ordered against it
+ * by the caller.  r1_set_scene waits for the context's OWN stream only and may reallocate every table: an update or a frame still in
+ * flight on another stream must have finished before it is called.  One thread at a time per context, as for every entry point.
+ * There is no r1_multi form: more than one device has never run on hardware here. */
+int r1_update_centers(r1_context *ctx, uint32_t first, uint32_t count, const float *x, const float *y, const float *z, void *hip_stream);
+
+/* The same from DEVICE memory: three device pointers to `count` floats each, 4-byte aligned (R1_EINVAL otherwise), read by a launch on
+ * `hip_stream`; waits for nothing.  The host cannot see the values: a sphere whose new centre is non-finite can never be hit (see
+ * r1_scene), the refit leaves it out of every box, and the pixels equal r1_set_scene with the same arrays, where that sphere is
+ * dropped as inactive.  The context's host copies of the centres are NOT updated. */
+int r1_update_centers_device(r1_context *ctx, uint32_t first, uint32_t count, const void *d_x, const void *d_y, const void *d_z, void *hip_stream);
+
 /* Renders the frame (or this shard's tiles of it) and returns everything on the host.
  * Replaces TileRenderScheduler::run + render_tile (rayweek1.cpp:785-842, :722-782).
  *   rgb_out      width*height*3 bytes, row-major, row 0 = bottom row, Pix{r,g,b}
@@ -550,6 +588,20 @@ typedef struct r1_bvh_info
 } r1_bvh_info;
 int r1_bvh_describe(const r1_scene *scene, int32_t leaf_max, r1_bvh_info *info, float *nodes_out, size_t nodes_cap, uint32_t *ids_out,
                     size_t ids_cap);
+
+/* The CPU-side pin of the refit's arithmetic (no GPU): builds the tree of `built` exactly as r1_set_scene does, refits it on the host —
+ * the device refit's steps over the same topology tables, in r1_bvh_fill.h's arithmetic — to the scene-indexed centres x, y, z
+ * (built->count entries each; entries of spheres that are not active are ignored, a non-finite centre leaves its sphere out of every
+ * box) and returns the node rows.  The ids are those of r1_bvh_describe(built); info->flat_axis is -1.  A child without a sphere in it
+ * (an empty leaf, or a subtree whose centres are all non-finite) has half extents -inf.  R1_EINVAL for NULL built, info, x, y or z. */
+int r1_bvh_refit_describe(const r1_scene *built, const float *x, const float *y, const float *z, int32_t leaf_max, r1_bvh_info *info,
+                          float *nodes_out, size_t nodes_cap);
+
+/* Diagnostic, synchronous: the node rows of the context's tree as the device holds them (16 floats per node, as r1_bvh_describe), after
+ * waiting for the context's stream (an update enqueued on another stream is the caller's to wait for).  *nodes receives the number of
+ * nodes; nodes_out may be NULL (the count alone), else nodes_cap >= 16 * *nodes floats (R1_ELIMIT otherwise).  Before any update it
+ * equals r1_bvh_describe, after one r1_bvh_refit_describe, bit for bit. */
+int r1_bvh_download(r1_context *ctx, float *nodes_out, size_t nodes_cap, size_t *nodes);
 
 /* Shape of the uniform grid R1_VARIANT_GRID uses (r1_grid.cpp), built on the host exactly as the render path builds it.  Optional
  * outputs: `start_out` the cells' CSR offsets (cells[0] * cells[1] * cells[2] + 1 entries; cell (jx, jy, jz) is

@@ -191,6 +191,10 @@ SYMBOLS = [
     ("r1_host_scene_view", C.c_int, [C.c_void_p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p]),
     ("r1_camera_look_at", C.c_int, [_f32p, _f32p, _f32p, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(CCamera)]),
     ("r1_bvh_describe", C.c_int, [C.POINTER(CScene), C.c_int32, C.POINTER(BvhInfo), _f32p, C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t]),
+    ("r1_update_centers", C.c_int, [_ctx, C.c_uint32, C.c_uint32, _f32p, _f32p, _f32p, C.c_void_p]),
+    ("r1_update_centers_device", C.c_int, [_ctx, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("r1_bvh_refit_describe", C.c_int, [C.POINTER(CScene), _f32p, _f32p, _f32p, C.c_int32, C.POINTER(BvhInfo), _f32p, C.c_size_t]),
+    ("r1_bvh_download", C.c_int, [_ctx, _f32p, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("r1_grid_describe", C.c_int, [C.POINTER(CScene), C.POINTER(GridInfo), C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t,
                                    C.POINTER(C.c_uint32), C.c_size_t]),
     ("r1_grid_visit", C.c_int, [C.POINTER(CScene), _f32p, _f32p, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_size_t), _i32p, _f32p, _i32p]),
@@ -356,6 +360,28 @@ class Renderer:
     def set_camera(self, ccamera):
         """r1_set_camera: the camera alone (nothing is built, uploaded or waited for)."""
         _check(lib().r1_set_camera(self._c, C.byref(ccamera)))
+
+    def update_centers(self, first, x, y, z, stream_ptr=None):
+        """r1_update_centers: new centres for the spheres [first, first + len(x)) of the scene (scene indices, placeholders counted), host
+        arrays; the box tree is refitted on the device.  Enqueues on `stream_ptr` (None: the context's stream)."""
+        x, y, z = (np.ascontiguousarray(v, np.float32) for v in (x, y, z))
+        if not (x.ndim == 1 and x.shape == y.shape == z.shape):
+            raise R1Error(R1_EINVAL, "update_centers: x, y and z must be one-dimensional and of one length")
+        _check(lib().r1_update_centers(self._c, first, x.shape[0], x.ctypes.data_as(_f32p), y.ctypes.data_as(_f32p), z.ctypes.data_as(_f32p),
+                                       C.c_void_p(stream_ptr) if stream_ptr else None))
+
+    def update_centers_device(self, first, count, d_x_ptr, d_y_ptr, d_z_ptr, stream_ptr=None):
+        """r1_update_centers_device: the same from three device pointers to `count` floats each; waits for nothing."""
+        _check(lib().r1_update_centers_device(self._c, first, count, C.c_void_p(d_x_ptr), C.c_void_p(d_y_ptr), C.c_void_p(d_z_ptr),
+                                              _stream_arg(stream_ptr)))
+
+    def bvh_download(self):
+        """r1_bvh_download: the box tree's node rows as the device holds them, float32[n, 16] (diagnostic, synchronous)."""
+        n = C.c_size_t()
+        _check(lib().r1_bvh_download(self._c, None, 0, C.byref(n)))
+        nodes = np.zeros((n.value, 16), np.float32)
+        _check(lib().r1_bvh_download(self._c, nodes.ctypes.data_as(_f32p), nodes.size, C.byref(n)))
+        return nodes
 
     def render(self, params):
         img = np.zeros((params.height, params.width, 3), np.uint8)
@@ -674,6 +700,23 @@ def bvh_describe(cscene, leaf_max=0):
     d["flat_m"], d["flat_e"] = np.float32(info.flat_m), np.float32(info.flat_e)
     d["centre"] = np.array(list(info.centre), np.float32)
     return d, nodes, ids[:2 * info.pairs]
+
+
+def bvh_refit_describe(cscene, x, y, z, leaf_max=0):
+    """r1_bvh_refit_describe: the tree r1_set_scene builds for `cscene`, refitted on the host to the scene-indexed centres x, y, z (cscene.count
+    entries each): (info dict, nodes float32[n, 16]).  The ids are bvh_describe(cscene)'s."""
+    x, y, z = (np.ascontiguousarray(v, np.float32) for v in (x, y, z))
+    if not (x.shape == y.shape == z.shape == (cscene.count,)):
+        raise R1Error(R1_EINVAL, "bvh_refit_describe: x, y and z need cscene.count entries each")
+    info = BvhInfo()
+    xp, yp, zp = (v.ctypes.data_as(_f32p) for v in (x, y, z))
+    _check(lib().r1_bvh_refit_describe(C.byref(cscene), xp, yp, zp, leaf_max, C.byref(info), None, 0))
+    nodes = np.zeros((info.nodes, 16), np.float32)
+    _check(lib().r1_bvh_refit_describe(C.byref(cscene), xp, yp, zp, leaf_max, C.byref(info), nodes.ctypes.data_as(_f32p), nodes.size))
+    d = {k: int(getattr(info, k)) for k, _ in BvhInfo._fields_ if k not in ("centre", "flat_m", "flat_e")}
+    d["flat_m"], d["flat_e"] = np.float32(info.flat_m), np.float32(info.flat_e)
+    d["centre"] = np.array(list(info.centre), np.float32)
+    return d, nodes
 
 
 def grid_describe(cscene):

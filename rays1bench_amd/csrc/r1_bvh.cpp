@@ -51,6 +51,7 @@
 #include <hip/hip_runtime.h>
 
 #include "r1_device.h"
+#include "r1_bvh.h"
 #include "../../include/rays1.h"
 
 #include <algorithm>
@@ -60,59 +61,11 @@
 #include <cstring>
 #include <vector>
 
-struct R1Bvh
-{
-    std::vector<float> nodes;   // 16 floats per node, see R1DeviceScene::bvh_nodes
-    std::vector<float> prims;   // leaf order, 8 floats per PAIR of spheres: {cx_a cx_b cy_a cy_b cz_a cz_b rsq_a rsq_b}
-    std::vector<uint32_t> ids;  // 2 per pair: active index, 0xFFFFFFFF for the partner of an odd sphere
-    int max_depth = 0;          // inner nodes on the longest root-to-leaf path
-    uint32_t n_leaves = 0;
-    float centre[3] = {0, 0, 0}; // C of the pad formula (see above)
-    int pad_local = 0;           // 1: pad measured per node (scenes of small spheres), 0: from `centre`
-    int root_leaf = 0;           // 1 / 2: child 0 / 1 of the root is a leaf of <= 2 sphere pairs and the other child an inner node (the root step), 0: no
-    int flat_axis = -1;          // 0 / 1 / 2: every box the node loop tests has nearly the same slab along this axis (see "flat axis" below), -1: none
-    float flat_m = 0, flat_e = 0; // that axis: centre and half extent of the union of those slabs, rounded outward
-};
-
 namespace
 {
 
-struct Box
-{
-    double lo[3], hi[3];   // of the spheres' extents c +- r
-    double clo[3], chi[3]; // of the centres
-    double kmax;           // max 1 / (2 r_eff)
-    double rmax;           // max r
-    double floor_pad;      // max r_floor / 2 over degenerate members
-    void clear()
-    {
-        for (int a = 0; a < 3; ++a)
-            lo[a] = clo[a] = 1e300, hi[a] = chi[a] = -1e300;
-        kmax = rmax = floor_pad = 0;
-    }
-    void merge(const Box &b)
-    {
-        for (int a = 0; a < 3; ++a)
-        {
-            lo[a] = std::min(lo[a], b.lo[a]), hi[a] = std::max(hi[a], b.hi[a]);
-            clo[a] = std::min(clo[a], b.clo[a]), chi[a] = std::max(chi[a], b.chi[a]);
-        }
-        kmax = std::max(kmax, b.kmax), rmax = std::max(rmax, b.rmax), floor_pad = std::max(floor_pad, b.floor_pad);
-    }
-    double area() const
-    {
-        const double dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2];
-        return dx * dy + dy * dz + dz * dx;
-    }
-};
-
-float round_up(double v)
-{
-    float f = (float)v;
-    if ((double)f < v)
-        f = nextafterf(f, INFINITY);
-    return nextafterf(f, INFINITY);
-}
+typedef R1Box Box;                                       // r1_bvh_fill.h: the arithmetic the device refit shares
+inline float round_up(double v) { return r1f_round_up(v); }
 
 struct Builder
 {
@@ -124,7 +77,6 @@ struct Builder
     int leaf_max;
     double centre[3]; // C of the pad formula, == out->centre
     bool pad_local = false;
-    double d_typ = 1.0; // pad_local: the distance at which the per-node pad is tight (twice the median distance of the centres from C)
 
     static const uint32_t LEAF = 0x80000000u;
 
@@ -135,22 +87,6 @@ struct Builder
         for (uint32_t i = b; i < e; ++i)
             r.merge(sphere[order[i]]);
         return r;
-    }
-
-    // child box -> {m, e} in fp32 covering [lo, hi], and this child's (w2, k)
-    static void encode(const Box &bx, float m[3], float e[3], double &w2, double &k)
-    {
-        double h2 = 0;
-        for (int a = 0; a < 3; ++a)
-        {
-            m[a] = (float)(0.5 * (bx.lo[a] + bx.hi[a]));
-            e[a] = round_up(std::max(bx.hi[a] - (double)m[a], (double)m[a] - bx.lo[a]));
-            const double hc = std::max(std::fabs(bx.clo[a] - (double)m[a]), std::fabs(bx.chi[a] - (double)m[a]));
-            h2 += hc * hc;
-        }
-        const double u = ldexp(1.0, -24);
-        w2 = 2.0 * (40.0 * u * bx.kmax) + ldexp(1.0, -19);
-        k = w2 * h2 + ldexp(1.0, -20) + 4.0 * u * bx.rmax + bx.floor_pad;
     }
 
     uint32_t make_leaf(uint32_t b, uint32_t e)
@@ -302,65 +238,11 @@ struct Builder
         return node;
     }
 
+    // the node's row from its children's boxes (r1_bvh_fill.h) and the child references
     void fill(uint32_t node, const Box &b0, uint32_t c0, const Box &b1, uint32_t c1)
     {
-        float m0[3], e0[3], m1[3], e1[3];
-        double w0, k0, w1, k1;
-        encode(b0, m0, e0, w0, k0);
-        encode(b1, m1, e1, w1, k1);
         float *p = &out->nodes[16 * (size_t)node];
-        // pad = A |o - C|^2 + K, or A |m0 + m1 - 2 o|^2 + K (see the header): >= w2 |m - o|^2 + k for both children
-        const double u = ldexp(1.0, -24), w2 = std::max(w0, w1), k = std::max(k0, k1);
-        const double head = 1.0 + ldexp(1.0, -18);
-        float A, K;
-        if (!pad_local)
-        {
-            static const int child_k = (int)r1_knob("R1_BVH_CHILD_K", 1); // tuning experiments: 0 = both children carry the worse child's K
-            const double c1n = std::fabs(centre[0]) + std::fabs(centre[1]) + std::fabs(centre[2]);
-            double g2c[2], kc[2] = {k0, k1}, wc[2] = {w0, w1};
-            int j = 0;
-            for (const float *m : {m0, m1})
-            {
-                double q = 0;
-                for (int a = 0; a < 3; ++a)
-                    q += ((double)m[a] - centre[a]) * ((double)m[a] - centre[a]);
-                g2c[j++] = q;
-            }
-            if (!child_k)
-                g2c[0] = g2c[1] = std::max(g2c[0], g2c[1]), kc[0] = kc[1] = k, wc[0] = wc[1] = w2;
-            A = round_up((2.0 * w2 + u) * head), K = 0.0f;
-            // K folded into the half extents here, e' = e + K rounded up, each child its own (see r1_build_bvh: "ONE A for the whole tree")
-            j = 0;
-            for (float *e : {e0, e1})
-            {
-                const float Kc = round_up((kc[j] + 2.0 * wc[j] * g2c[j] + u * (1.0 + c1n)) * head);
-                for (int a = 0; a < 3; ++a)
-                    e[a] = round_up((double)e[a] + (double)Kc);
-                ++j;
-            }
-        }
-        else
-        {
-            double g2 = 0, mn2 = 0, M = 0, M0 = 0, M1 = 0;
-            for (int a = 0; a < 3; ++a)
-            {
-                const double h = 0.5 * ((double)m0[a] - (double)m1[a]), mn = 0.5 * ((double)m0[a] + (double)m1[a]);
-                g2 += h * h, mn2 += mn * mn;
-                M0 = std::max(M0, std::fabs((double)m0[a])), M1 = std::max(M1, std::fabs((double)m1[a]));
-            }
-            M = M0 + M1;
-            // (D + g)^2 <= (1 + eps) D^2 + (1 + 1 / eps) g^2 for every eps > 0: tight at D = g / eps.  eps = g / d_typ makes the
-            // pad exact for origins d_typ away (the scene's scale), instead of twice what is needed (eps = 1) everywhere
-            const double eps = std::min(1.0, std::max(1.0 / 64.0, std::sqrt(g2) / d_typ));
-            const double a_loc = (0.25 * (1.0 + eps) * w2 + u / 8.0) * (1.0 + ldexp(1.0, -10));
-            A = round_up(a_loc * head);
-            K = round_up((k + (1.0 + 1.0 / eps) * w2 * g2 + u * (0.5 + std::sqrt(mn2)) + a_loc * 3075.0 * 288.0 * u * u * M * M) * head);
-        }
-        // {m0x m1x m0y m1y} {m0z m1z e0x e1x} {e0y e1y e0z e1z} {A K child0 child1}
-        p[0] = m0[0], p[1] = m1[0], p[2] = m0[1], p[3] = m1[1];
-        p[4] = m0[2], p[5] = m1[2], p[6] = e0[0], p[7] = e1[0];
-        p[8] = e0[1], p[9] = e1[1], p[10] = e0[2], p[11] = e1[2];
-        p[12] = A, p[13] = K;
+        r1f_fill(out->fill, b0, b1, p);
         memcpy(&p[14], &c0, 4);
         memcpy(&p[15], &c1, 4);
     }
@@ -389,19 +271,9 @@ void r1_build_bvh(uint32_t na, const float *cx, const float *cy, const float *cz
     {
         B.order[a] = a;
         Box &s = B.sphere[a];
-        const double c[3] = {cx[a], cy[a], cz[a]};
         // extents cover rbound (>= the radius the exact test reads, r1_bound_radius); the error terms
         // E1 / (2 r) follow the radius the test itself uses, sqrt(radius_sq) — the smaller, safer one
-        const double r = rbound[a];
-        const double r_test = rsq[a] > 0 ? std::min(r, std::sqrt((double)rsq[a])) : 0.0;
-        // degenerate radii: bound sqrt(r^2 + E1) - r through r_floor (AM-GM), see the header
-        const double r_floor = 1e-4 * (1.0 + std::fabs(c[0]) + std::fabs(c[1]) + std::fabs(c[2]));
-        const double r_eff = std::max(r_test, r_floor);
-        for (int k = 0; k < 3; ++k)
-            s.lo[k] = c[k] - r, s.hi[k] = c[k] + r, s.clo[k] = s.chi[k] = c[k];
-        s.kmax = 1.0 / (2.0 * r_eff);
-        s.rmax = r;
-        s.floor_pad = r_test < r_floor ? 0.5 * r_floor : 0.0;
+        r1f_sphere_box(cx[a], cy[a], cz[a], rbound[a], r1_test_radius(rbound[a], rsq[a]), s);
     }
     // C: the per-axis median of the centres (the ground sphere's centre, 1000 units below, must not drag it away)
     for (int k = 0; k < 3; ++k)
@@ -439,8 +311,13 @@ void r1_build_bvh(uint32_t na, const float *cx, const float *cy, const float *cz
         if (pad_env >= 0)
             local = pad_env != 0;
         B.pad_local = local;
-        B.d_typ = na ? std::max(std::sqrt(4.0 * dd[na / 2]), 1e-30) : 1.0;
         out.pad_local = local ? 1 : 0;
+        // what fill() computes with, and every later refit of this tree (r1_bvh_fill.h)
+        static const int child_k = (int)r1_knob("R1_BVH_CHILD_K", 1); // tuning experiments: 0 = both children carry the worse child's K
+        for (int k = 0; k < 3; ++k)
+            out.fill.centre[k] = B.centre[k];
+        out.fill.d_typ = na ? std::max(std::sqrt(4.0 * dd[na / 2]), 1e-30) : 1.0; // twice the median distance of the centres from C
+        out.fill.pad_local = out.pad_local, out.fill.child_k = child_k;
     }
     // the root is node 0
     out.nodes.resize(16);
@@ -672,51 +549,186 @@ double r1_bound_radius(float radius_sq, float inv_radius)
     return std::max(from_sq, from_inv);
 }
 
-// Host-only view of the index (include/rays1.h): what r1_set_scene would build for this scene.
-extern "C" int r1_bvh_describe(const r1_scene *s, int32_t leaf_max, r1_bvh_info *info, float *nodes_out, size_t nodes_cap, uint32_t *ids_out,
-                               size_t ids_cap)
+// The radius whose error terms E1 / (2 r) the pad follows: the one the exact test itself uses, sqrt(radius_sq), never more than the bound
+// radius — the smaller, safer one (r1f_sphere_box's r_test).
+double r1_test_radius(double rbound, float radius_sq) { return radius_sq > 0 ? std::min(rbound, std::sqrt((double)radius_sq)) : 0.0; }
+
+// ---- refit ----------------------------------------------------------------------
+
+static int node_height(const R1Bvh &b, uint32_t n, std::vector<int> &h)
 {
-    if (!s || !info || !s->center_x || !s->center_y || !s->center_z || !s->radius_sq || !s->inv_radius)
-        return R1_EINVAL;
+    if (h[n] >= 0)
+        return h[n];
+    int v = 0;
+    for (int c = 0; c < 2; ++c)
+    {
+        uint32_t r;
+        memcpy(&r, &b.nodes[16 * (size_t)n + 14 + c], 4);
+        if (!(r & 0x80000000u))
+            v = std::max(v, 1 + node_height(b, r, h)); // (at most R1_BVH_STACK levels)
+    }
+    return h[n] = v;
+}
+
+void r1_bvh_topology(const R1Bvh &b, uint32_t na, R1RefitTopo &t)
+{
+    const uint32_t NONE = 0xFFFFFFFFu, nn = (uint32_t)(b.nodes.size() / 16);
+    t.slot.assign(na ? na : 1, NONE);
+    for (size_t q = 0; q < b.ids.size(); ++q)
+        if (b.ids[q] < na)
+            t.slot[b.ids[q]] = (uint32_t)q;
+    t.leaf_ref.clear();
+    t.child_box.assign(2 * (size_t)nn, NONE);
+    for (uint32_t n = 0; n < nn; ++n)
+        for (int c = 0; c < 2; ++c)
+        {
+            uint32_t r;
+            memcpy(&r, &b.nodes[16 * (size_t)n + 14 + c], 4);
+            if (!(r & 0x80000000u))
+                t.child_box[2 * (size_t)n + c] = r;
+            else if ((r >> 28) & 7u)
+                t.child_box[2 * (size_t)n + c] = nn + (uint32_t)t.leaf_ref.size(), t.leaf_ref.push_back(r);
+        }
+    std::vector<int> h(nn, -1);
+    int top = 0;
+    for (uint32_t n = 0; n < nn; ++n)
+        top = std::max(top, node_height(b, n, h));
+    t.height_off.assign((size_t)top + 2, 0u);
+    for (uint32_t n = 0; n < nn; ++n)
+        ++t.height_off[(size_t)h[n] + 1];
+    for (int k = 0; k <= top; ++k)
+        t.height_off[(size_t)k + 1] += t.height_off[k];
+    t.by_height.assign(nn, 0u);
+    std::vector<uint32_t> at(t.height_off.begin(), t.height_off.end() - 1);
+    for (uint32_t n = 0; n < nn; ++n)
+        t.by_height[at[h[n]]++] = n;
+}
+
+void r1_bvh_refit_host(R1Bvh &b, const R1RefitTopo &t, uint32_t na, const float *cx, const float *cy, const float *cz, const float *rsq,
+                       const double *rbound)
+{
+    if (na == 0)
+        return; // nothing to refit
+    const size_t nn = b.nodes.size() / 16, nl = t.leaf_ref.size();
+    std::vector<float> exact(4 * (size_t)na);
+    std::vector<double> radii(2 * (size_t)na);
+    for (uint32_t a = 0; a < na; ++a)
+    {
+        exact[4 * (size_t)a + 0] = cx[a], exact[4 * (size_t)a + 1] = cy[a], exact[4 * (size_t)a + 2] = cz[a], exact[4 * (size_t)a + 3] = rsq[a];
+        radii[2 * (size_t)a + 0] = rbound[a], radii[2 * (size_t)a + 1] = r1_test_radius(rbound[a], rsq[a]);
+    }
+    std::vector<R1Box> box(nn + nl);
+    for (size_t l = 0; l < nl; ++l) // "leaf boxes"
+        r1f_refit_leaf(t.leaf_ref[l], b.ids.data(), exact.data(), radii.data(), box[nn + l]);
+    float a_max = 0.0f;
+    for (size_t k = 0; k + 1 < t.height_off.size(); ++k) // one launch per height, lowest first
+        for (uint32_t i = t.height_off[k]; i < t.height_off[k + 1]; ++i)
+            a_max = std::max(a_max, r1f_refit_node(b.fill, t.by_height[i], t.child_box.data(), box.data(), b.nodes.data()));
+    if (!b.pad_local) // "finish": ONE A for the whole tree, as the builder's last step
+        for (size_t n = 0; n < nn; ++n)
+            b.nodes[16 * n + 12] = a_max;
+    b.flat_axis = -1, b.flat_m = b.flat_e = 0.0f; // (no slab is computed for a moved scene)
+}
+
+// the tree r1_set_scene builds for `s`, and what it was built from (active order)
+struct Described
+{
     std::vector<float> x, y, z, r;
     std::vector<double> rb;
     std::vector<uint32_t> scene_index;
-    if (r1_active_spheres(s, scene_index) != R1_OK)
-        return R1_EINVAL;
-    for (uint32_t i : scene_index)
-    {
-        x.push_back(s->center_x[i]), y.push_back(s->center_y[i]), z.push_back(s->center_z[i]), r.push_back(s->radius_sq[i]);
-        rb.push_back(r1_bound_radius(s->radius_sq[i], s->inv_radius[i]));
-    }
-    const uint32_t na = (uint32_t)x.size();
-    if (na == 0)
-        x.push_back(0), y.push_back(0), z.push_back(0), r.push_back(0), rb.push_back(0);
+    uint32_t na = 0;
     R1Bvh b;
-    r1_build_bvh(na, x.data(), y.data(), z.data(), r.data(), rb.data(),
-                 leaf_max > 0 ? leaf_max : (na > R1_MAX_ACTIVE_10BIT ? 2 * R1_BVH_LEAF : R1_BVH_LEAF), b);
+};
+static int describe_build(const r1_scene *s, int32_t leaf_max, Described &d)
+{
+    if (!s->center_x || !s->center_y || !s->center_z || !s->radius_sq || !s->inv_radius)
+        return R1_EINVAL;
+    if (r1_active_spheres(s, d.scene_index) != R1_OK)
+        return R1_EINVAL;
+    for (uint32_t i : d.scene_index)
+    {
+        d.x.push_back(s->center_x[i]), d.y.push_back(s->center_y[i]), d.z.push_back(s->center_z[i]), d.r.push_back(s->radius_sq[i]);
+        d.rb.push_back(r1_bound_radius(s->radius_sq[i], s->inv_radius[i]));
+    }
+    d.na = (uint32_t)d.x.size();
+    if (d.na == 0)
+        d.x.push_back(0), d.y.push_back(0), d.z.push_back(0), d.r.push_back(0), d.rb.push_back(0);
+    r1_build_bvh(d.na, d.x.data(), d.y.data(), d.z.data(), d.r.data(), d.rb.data(),
+                 leaf_max > 0 ? leaf_max : (d.na > R1_MAX_ACTIVE_10BIT ? 2 * R1_BVH_LEAF : R1_BVH_LEAF), d.b);
+    return R1_OK;
+}
+static void describe_info(const Described &d, r1_bvh_info *info)
+{
+    const R1Bvh &b = d.b;
     info->nodes = (int32_t)(b.nodes.size() / 16);
     info->leaves = (int32_t)b.n_leaves;
     info->depth = b.max_depth;
     info->stack_entries = R1_BVH_STACK;
-    info->spheres = (int32_t)na;
+    info->spheres = (int32_t)d.na;
     for (int k = 0; k < 3; ++k)
         info->centre[k] = b.centre[k];
     info->pad_local = b.pad_local;
     info->root_leaf = b.root_leaf;
     info->flat_axis = b.flat_axis, info->flat_m = b.flat_m, info->flat_e = b.flat_e;
+    info->pairs = (int32_t)(b.ids.size() / 2);
+}
+
+// Host-only pin of the refit (include/rays1.h): the tree of `built`, refitted to the scene-indexed centres x, y, z.
+extern "C" int r1_bvh_refit_describe(const r1_scene *built, const float *x, const float *y, const float *z, int32_t leaf_max, r1_bvh_info *info,
+                                     float *nodes_out, size_t nodes_cap)
+{
+    if (!built || !info || !x || !y || !z)
+    {
+        r1_set_error("r1_bvh_refit_describe: null argument");
+        return R1_EINVAL;
+    }
+    Described d;
+    int rc = describe_build(built, leaf_max, d);
+    if (rc)
+        return rc;
+    R1RefitTopo t;
+    r1_bvh_topology(d.b, d.na, t);
+    for (uint32_t a = 0; a < d.na; ++a)
+    {
+        const uint32_t i = d.scene_index[a];
+        d.x[a] = x[i], d.y[a] = y[i], d.z[a] = z[i];
+    }
+    r1_bvh_refit_host(d.b, t, d.na, d.x.data(), d.y.data(), d.z.data(), d.r.data(), d.rb.data());
+    describe_info(d, info);
+    info->flat_axis = -1, info->flat_m = info->flat_e = 0.0f;
+    if (nodes_out)
+    {
+        if (nodes_cap < d.b.nodes.size())
+            return R1_ELIMIT;
+        memcpy(nodes_out, d.b.nodes.data(), d.b.nodes.size() * 4);
+    }
+    return R1_OK;
+}
+
+// Host-only view of the index (include/rays1.h): what r1_set_scene would build for this scene.
+extern "C" int r1_bvh_describe(const r1_scene *s, int32_t leaf_max, r1_bvh_info *info, float *nodes_out, size_t nodes_cap, uint32_t *ids_out,
+                               size_t ids_cap)
+{
+    if (!s || !info)
+        return R1_EINVAL;
+    Described d;
+    int rc = describe_build(s, leaf_max, d);
+    if (rc)
+        return rc;
+    const R1Bvh &b = d.b;
+    describe_info(d, info);
     if (nodes_out)
     {
         if (nodes_cap < b.nodes.size())
             return R1_ELIMIT;
         memcpy(nodes_out, b.nodes.data(), b.nodes.size() * 4);
     }
-    info->pairs = (int32_t)(b.ids.size() / 2);
     if (ids_out)
     {
         if (ids_cap < b.ids.size())
             return R1_ELIMIT;
         for (size_t i = 0; i < b.ids.size(); ++i) // leaf slot (2 per pair) -> index into the caller's scene arrays
-            ids_out[i] = b.ids[i] == 0xFFFFFFFFu || na == 0 ? 0xFFFFFFFFu : scene_index[b.ids[i]];
+            ids_out[i] = b.ids[i] == 0xFFFFFFFFu || d.na == 0 ? 0xFFFFFFFFu : d.scene_index[b.ids[i]];
     }
     return R1_OK;
 }

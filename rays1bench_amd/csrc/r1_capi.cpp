@@ -44,24 +44,11 @@ extern "C" hipError_t r1_launch_cast(const R1CastArgs *args, int structure, int 
 extern "C" hipError_t r1_cast_occupancy(int structure, int big, int plain, size_t dyn_lds, int *blocks_per_cu);
 extern "C" int r1_params_check(const r1_params *p); // r1_host.cpp
 
-// r1_bvh.cpp
-struct R1Bvh
-{
-    std::vector<float> nodes;
-    std::vector<float> prims;
-    std::vector<uint32_t> ids;
-    int max_depth = 0;
-    uint32_t n_leaves = 0;
-    float centre[3] = {0, 0, 0};
-    int pad_local = 0;
-    int root_leaf = 0;
-    int flat_axis = -1;
-    float flat_m = 0, flat_e = 0;
-};
-void r1_build_bvh(uint32_t na, const float *cx, const float *cy, const float *cz, const float *rsq, const double *rbound, int leaf_max,
-                  R1Bvh &out);
-int r1_active_spheres(const r1_scene *s, std::vector<uint32_t> &active_to_scene); // inv_radius != 0, finite (r1_bvh.cpp)
-double r1_bound_radius(float radius_sq, float inv_radius);
+#include "r1_bvh.h" // r1_bvh.cpp: the built tree, a refit's topology tables
+
+// r1_refit.hip: the kernels of r1_update_centers* 
+extern "C" hipError_t r1_launch_refit_move(const R1RefitArgs *a, uint32_t first, uint32_t count, const float *x, const float *y, const float *z, hipStream_t stream);
+extern "C" hipError_t r1_launch_refit(const R1RefitArgs *a, const uint32_t *height_off, uint32_t heights, hipStream_t stream);
 
 // ---- errors ---------------------------------------------------------------------------------
 
@@ -189,6 +176,18 @@ struct r1_context
     uint32_t cast_cursor_next = 0;
     DevBuf cast_ws;            // r1_cast_rays: one chunk's rays and results (R1_CAST_CHUNK x 64 bytes)
     int cast_occupancy[8] = {0}; // blocks per CU of the cast kernels, [structure slot * 2 + big]
+    // moving spheres (r1_update_centers*): the refit's tables — topology, uploaded once per r1_set_scene — and its scratch
+    DevBuf refit_tab;          // uint32: scene -> active index, then R1RefitTopo's slot, leaf_ref, child_box, by_height
+    DevBuf refit_radii;        // [active][2] fp64 {bound radius, test radius}
+    DevBuf refit_box;          // 256 bytes (word 0: the largest A), then [nodes + leaves] R1Box
+    R1RefitArgs refit;         // pointers into the tables above and the scene's
+    std::vector<uint32_t> refit_height_off; // R1RefitTopo::height_off
+    std::vector<uint32_t> scene_to_active;  // 0xFFFFFFFF: not active
+    bool moved = false;        // an update since the last r1_set_scene: the sphere groups and the grid are stale, src_f32 may be
+    float *stage = nullptr, *stage_dev = nullptr; // host form: page-locked staging of the centres, read by the move kernel
+    size_t stage_cap = 0;      // floats
+    hipEvent_t stage_ev = nullptr; // recorded behind the move kernel that reads `stage`
+    bool stage_busy = false;
 
     r1_launch_info info;
 };
@@ -304,6 +303,11 @@ extern "C" void r1_destroy(r1_context *c)
     release(c->land_spill), release(c->gstack), release(c->counters), release(c->samples), release(c->image), release(c->batch_rays);
     release(c->wave_log), release(c->accum), release(c->path_cams), release(c->accum_even), release(c->adapt_list), release(c->adapt_report);
     release(c->active_dev), release(c->cast_cursors), release(c->cast_ws);
+    release(c->refit_tab), release(c->refit_radii), release(c->refit_box);
+    if (c->stage)
+        (void)hipHostFree(c->stage);
+    if (c->stage_ev)
+        (void)hipEventDestroy(c->stage_ev);
     if (c->host_word)
         (void)hipHostFree(c->host_word);
     for (hipEvent_t e : c->ring)
@@ -500,7 +504,8 @@ extern "C" int r1_set_scene(r1_context *c, const r1_scene *s, const r1_camera *c
     R1_HIP(hipSetDevice(c->device));
 
     const float *const src[9] = {s->center_x, s->center_y, s->center_z, s->radius_sq, s->inv_radius, s->albedo_r, s->albedo_g, s->albedo_b, s->mat_param};
-    if (c->have_scene && c->src_mat.size() == s->count && memcmp(&c->src_cam, cam, sizeof(*cam)) == 0 &&
+    // (not after r1_update_centers*: the device holds other centres than src_f32, or the groups and the grid are those of other centres)
+    if (c->have_scene && !c->moved && c->src_mat.size() == s->count && memcmp(&c->src_cam, cam, sizeof(*cam)) == 0 &&
         (s->count == 0 || memcmp(c->src_mat.data(), s->mat_type, s->count) == 0))
     {
         bool same = true;
@@ -661,7 +666,41 @@ extern "C" int r1_set_scene(r1_context *c, const r1_scene *s, const r1_camera *c
         return rc;
     if (na)
         R1_HIP(hipMemcpyAsync(c->active_dev.p, c->active_to_scene.data(), (size_t)na * 4, hipMemcpyHostToDevice, c->stream));
+    // what a refit needs besides the tree (r1_update_centers*): topology and the radii, once per scene
+    R1RefitTopo topo;
+    r1_bvh_topology(bvh, na, topo);
+    c->scene_to_active.assign(s->count ? s->count : 1, 0xFFFFFFFFu);
+    for (uint32_t a = 0; a < na; ++a)
+        c->scene_to_active[c->active_to_scene[a]] = a;
+    std::vector<uint32_t> rtab;
+    size_t roff[5];
+    {
+        const std::vector<uint32_t> *parts[5] = {&c->scene_to_active, &topo.slot, &topo.leaf_ref, &topo.child_box, &topo.by_height};
+        for (int k = 0; k < 5; ++k)
+            roff[k] = rtab.size(), rtab.insert(rtab.end(), parts[k]->begin(), parts[k]->end());
+    }
+    std::vector<double> radii(2 * (size_t)(na ? na : 1), 0.0);
+    for (uint32_t a = 0; a < na; ++a)
+        radii[2 * (size_t)a + 0] = ar_[a], radii[2 * (size_t)a + 1] = r1_test_radius(ar_[a], exact[4 * (size_t)a + 3]);
+    const size_t n_box = bvh.nodes.size() / 16 + topo.leaf_ref.size();
+    if ((rc = ensure(c->refit_tab, rtab.size() * 4)) || (rc = ensure(c->refit_radii, radii.size() * 8)) ||
+        (rc = ensure(c->refit_box, 256 + n_box * sizeof(R1Box))))
+        return rc;
+    R1_HIP(hipMemcpyAsync(c->refit_tab.p, rtab.data(), rtab.size() * 4, hipMemcpyHostToDevice, c->stream));
+    R1_HIP(hipMemcpyAsync(c->refit_radii.p, radii.data(), radii.size() * 8, hipMemcpyHostToDevice, c->stream));
     R1_HIP(hipStreamSynchronize(c->stream)); // the host vectors go out of scope
+    {
+        R1RefitArgs &r = c->refit;
+        const uint32_t *tab = (const uint32_t *)c->refit_tab.p;
+        r.exact = (float *)c->exact.p, r.prims = (float *)c->bvh_prims.p, r.nodes = (float *)c->bvh_nodes.p, r.ids = (const uint32_t *)c->bvh_ids.p;
+        r.scene_to_active = tab + roff[0], r.slot = tab + roff[1], r.leaf_ref = tab + roff[2], r.child_box = tab + roff[3], r.by_height = tab + roff[4];
+        r.radii = (const double *)c->refit_radii.p;
+        r.a_max = (uint32_t *)c->refit_box.p, r.box = (R1Box *)((char *)c->refit_box.p + 256);
+        r.n_nodes = (uint32_t)(bvh.nodes.size() / 16), r.n_leaves = (uint32_t)topo.leaf_ref.size();
+        r.fill = bvh.fill;
+        c->refit_height_off = topo.height_off;
+    }
+    c->moved = false;
     c->n_bvh_nodes = (uint32_t)(bvh.nodes.size() / 16);
     c->n_bvh_leaves = bvh.n_leaves;
     c->bvh_depth = bvh.max_depth;
@@ -708,6 +747,128 @@ extern "C" int r1_set_camera(r1_context *c, const r1_camera *cam)
     c->pass_valid = false; // (a progressive frame does not continue across a change of view, as across r1_set_scene)
     c->cam = device_camera(*cam);
     c->src_cam = *cam;       // r1_set_scene(same arrays, this camera) is still the shortcut
+    return R1_OK;
+}
+
+// ---- moving spheres (include/rays1.h "moving spheres", r1_refit.hip) --------------------------------------------------
+
+static int update_check(const char *who, r1_context *c, uint32_t first, uint32_t count, const void *x, const void *y, const void *z)
+{
+    if (!c)
+    {
+        r1_set_error("%s: ctx is NULL", who);
+        return R1_EINVAL;
+    }
+    if (!c->have_scene)
+    {
+        r1_set_error("%s: no scene set (call r1_set_scene first)", who);
+        return R1_EINVAL;
+    }
+    if ((uint64_t)first + count > c->n_padded_scene)
+    {
+        r1_set_error("%s: spheres [%u, %llu) are beyond the scene's %u", who, first, (unsigned long long)first + count, c->n_padded_scene);
+        return R1_EINVAL;
+    }
+    if (count && (!x || !y || !z))
+    {
+        r1_set_error("%s: x, y and z must not be NULL with count > 0", who);
+        return R1_EINVAL;
+    }
+    return R1_OK;
+}
+
+// The move and the refit on `st`, centres from memory the device can read; then what an update changes in the context.  Nothing is waited
+// for.  `moved_ev` (or null) is recorded straight behind the move kernel, the only reader of the centres.  Leaves the launch info and the
+// timing events alone.
+static int update_enqueue(r1_context *c, uint32_t first, uint32_t count, const float *dx, const float *dy, const float *dz, hipStream_t st,
+                          hipEvent_t moved_ev)
+{
+    R1_HIP(r1_launch_refit_move(&c->refit, first, count, dx, dy, dz, st));
+    if (moved_ev)
+        R1_HIP(hipEventRecord(moved_ev, st));
+    if (c->n_active) // (a tree of 0 spheres has nothing to refit)
+        R1_HIP(r1_launch_refit(&c->refit, c->refit_height_off.data(), (uint32_t)c->refit_height_off.size() - 1u, st));
+    c->moved = true;
+    c->grid_valid = false;
+    c->pass_valid = false; // (a progressive frame does not continue across a change of the scene)
+    // the flat y slab (r1_bvh.cpp) is dropped, not refitted: it travels by value in the launches' arguments, and spheres that leave the
+    // plane are exactly the case it must not miss.  The kernels take the generic loop they already have.
+    c->bvh_flat_m = 0.0f, c->bvh_flat_e = -1.0f;
+    return R1_OK;
+}
+
+extern "C" int r1_update_centers(r1_context *c, uint32_t first, uint32_t count, const float *x, const float *y, const float *z, void *hip_stream)
+{
+    int rc = update_check("r1_update_centers", c, first, count, x, y, z);
+    if (rc || count == 0)
+        return rc;
+    for (uint32_t i = 0; i < count; ++i)
+        if (c->scene_to_active[first + i] != 0xFFFFFFFFu && !(std::isfinite(x[i]) && std::isfinite(y[i]) && std::isfinite(z[i])))
+        {
+            r1_set_error("r1_update_centers: the new centre of sphere %u is not finite", first + i);
+            return R1_EINVAL;
+        }
+    R1_HIP(hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    // the staging buffer: the move kernel of the previous update may still be reading it
+    if (c->stage_busy)
+        R1_HIP(hipEventSynchronize(c->stage_ev));
+    c->stage_busy = false;
+    if (!c->stage_ev)
+        R1_HIP(hipEventCreateWithFlags(&c->stage_ev, hipEventDisableTiming));
+    if (c->stage_cap < 3 * (size_t)count)
+    {
+        if (c->stage)
+            R1_HIP(hipHostFree(c->stage));
+        c->stage = c->stage_dev = nullptr, c->stage_cap = 0;
+        R1_HIP(hipHostMalloc((void **)&c->stage, 3 * (size_t)count * 4, hipHostMallocMapped));
+        R1_HIP(hipHostGetDevicePointer((void **)&c->stage_dev, c->stage, 0));
+        c->stage_cap = 3 * (size_t)count;
+    }
+    memcpy(c->stage, x, (size_t)count * 4), memcpy(c->stage + count, y, (size_t)count * 4), memcpy(c->stage + 2 * (size_t)count, z, (size_t)count * 4);
+    c->stage_busy = true; // (from here on: a launch that failed half-way may still have enqueued the move)
+    if ((rc = update_enqueue(c, first, count, c->stage_dev, c->stage_dev + count, c->stage_dev + 2 * (size_t)count, st, c->stage_ev)))
+        return rc;
+    // the context's host copies follow (entries of spheres that are not active too: they are what r1_set_scene would be given)
+    memcpy(c->src_f32[0].data() + first, x, (size_t)count * 4), memcpy(c->src_f32[1].data() + first, y, (size_t)count * 4);
+    memcpy(c->src_f32[2].data() + first, z, (size_t)count * 4);
+    return R1_OK;
+}
+
+extern "C" int r1_update_centers_device(r1_context *c, uint32_t first, uint32_t count, const void *d_x, const void *d_y, const void *d_z, void *hip_stream)
+{
+    int rc = update_check("r1_update_centers_device", c, first, count, d_x, d_y, d_z);
+    if (rc || count == 0)
+        return rc;
+    if (((uintptr_t)d_x | (uintptr_t)d_y | (uintptr_t)d_z) & 3u)
+    {
+        r1_set_error("r1_update_centers_device: d_x, d_y and d_z must be 4-byte aligned");
+        return R1_EINVAL;
+    }
+    R1_HIP(hipSetDevice(c->device));
+    return update_enqueue(c, first, count, (const float *)d_x, (const float *)d_y, (const float *)d_z, hip_stream ? (hipStream_t)hip_stream : c->stream, nullptr);
+}
+
+extern "C" int r1_bvh_download(r1_context *c, float *nodes_out, size_t nodes_cap, size_t *nodes)
+{
+    if (!c || !nodes)
+    {
+        r1_set_error("r1_bvh_download: %s is NULL", !c ? "ctx" : "nodes");
+        return R1_EINVAL;
+    }
+    if (!c->have_scene)
+    {
+        r1_set_error("r1_bvh_download: no scene set (call r1_set_scene first)");
+        return R1_EINVAL;
+    }
+    *nodes = c->n_bvh_nodes;
+    if (!nodes_out)
+        return R1_OK;
+    if (nodes_cap < 16 * (size_t)c->n_bvh_nodes)
+        return R1_ELIMIT;
+    R1_HIP(hipSetDevice(c->device));
+    R1_HIP(hipMemcpyAsync(nodes_out, c->bvh_nodes.p, 64 * (size_t)c->n_bvh_nodes, hipMemcpyDeviceToHost, c->stream));
+    R1_HIP(hipStreamSynchronize(c->stream));
     return R1_OK;
 }
 
@@ -1449,6 +1610,12 @@ static int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int blo
     if (rc)
         return rc;
     const int variant = resolve_variant(c, p->variant, throughput_mode);
+    if (c->moved && variant != 1 && variant != 4 && variant != 5)
+    {
+        r1_set_error("variant %d: the scene has moved (r1_update_centers) and only the box tree was refitted, not the sphere groups and the uniform grid; "
+                     "r1_set_scene rebuilds them", variant);
+        return R1_EINVAL;
+    }
     R1_HIP(hipSetDevice(c->device));
     if ((variant == 7 || variant == 8) && (rc = ensure_grid(c)))
         return rc;
@@ -2059,6 +2226,11 @@ static int cast_check(const char *who, r1_context *c, int32_t variant, int32_t m
     if (!c->have_scene)
     {
         r1_set_error("%s: no scene set (call r1_set_scene first)", who);
+        return R1_EINVAL;
+    }
+    if (c->moved && *structure == 7)
+    {
+        r1_set_error("%s: the scene has moved (r1_update_centers) and the uniform grid was not refitted; r1_set_scene rebuilds it", who);
         return R1_EINVAL;
     }
     return R1_OK;

@@ -1,0 +1,413 @@
+"""GPU tests of moving spheres: r1_update_centers* writes new centres into the tables the tree kernels read and refits
+the box tree on the device.  The contract: every render and ray query afterwards gives, byte for byte and ray for ray, what a FRESH context
+gives after r1_set_scene with the moved arrays.  Nothing here has a tolerance."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import rays1bench_amd as r1
+from rays1bench_amd import binding
+from test_bvh_host import F, _raw_scene
+from test_refit_host import MOVES, edge_scene, lattice_of, moved_centres, random_cloud, raw_from_arrays
+
+pytestmark = pytest.mark.gpu
+
+MOVED_RULE = "the scene has moved"
+# (scene, render width, height, spp, pad_local, big-scene kernels)
+CASES = {"large": (96, 64, 4, 0, False), "grid40x30": (64, 48, 2, 0, True), "grid160x100": (64, 48, 2, 1, True)}
+
+
+@pytest.fixture(scope="module")
+def upd():
+    assert r1.device_count() >= 1, "no HIP device: the product has no CPU fallback"
+    r = r1.Renderer(0)
+    yield r
+    r.close()
+
+
+@pytest.fixture(scope="module")
+def fresh():
+    r = r1.Renderer(0)
+    yield r
+    r.close()
+
+
+@pytest.fixture(scope="module")
+def scenes():
+    """name -> (Scene, arrays): built once, never changed."""
+    out = {}
+    for name, (w, h, spp, pad_local, big) in CASES.items():
+        if name == "large":
+            sc = r1.create_large_scene(w, h)
+        else:
+            gw, gh = (int(v) for v in name[4:].split("x"))
+            sc = r1.create_grid_scene(w, h, gw, gh)
+        out[name] = (sc, sc.arrays())
+    return out
+
+
+def params(name, variant=0, seed=777):
+    w, h, spp = CASES[name][:3]
+    return r1.make_params(w, h, spp, seed, variant=variant)
+
+
+def expect_refusal(fn, rule, code=binding.R1_EINVAL):
+    with pytest.raises(binding.R1Error) as e:
+        fn()
+    assert e.value.code == code, e.value
+    assert rule in str(e.value), e.value
+
+
+def fresh_render(fresh, a, cam, x, y, z, p):
+    """(image, rays) of a fresh build: r1_set_scene with the moved arrays on the other context."""
+    cs, keep = raw_from_arrays(a, x, y, z)
+    fresh.set_scene_raw(cs, cam)
+    img, rays, _ = fresh.render(p)
+    return img, rays
+
+
+def same(got, want, what):
+    assert got[1] == want[1], (what, "rays", got[1], want[1])
+    assert got[0].tobytes() == want[0].tobytes(), (what, "pixels")
+
+
+# ---- 5, 6, 7: the moved cases on the three kernel families ------------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("move", ("identity",) + MOVES)
+@pytest.mark.parametrize("name", list(CASES))
+def test_update_equals_fresh_build(upd, fresh, scenes, name, move):
+    sc, a = scenes[name]
+    x, y, z = moved_centres(a, move)
+    upd.set_scene(sc)
+    info = binding.bvh_describe(sc.spheres.contents)[0]
+    assert info["pad_local"] == CASES[name][3] and (info["spheres"] > 1023) == CASES[name][4], info
+    if name == "large":
+        assert info["flat_axis"] == 1  # a tree that was flat: the update drops the slab
+    upd.update_centers(0, x, y, z)
+    p = params(name)
+    got = upd.render(p)[:2]
+    assert upd.launch_info()["kernel"] == binding.VARIANT_BVH
+    want = fresh_render(fresh, a, sc.camera.contents, x, y, z, p)
+    same(got, want, (name, move, "default"))
+    same(upd.render(params(name, binding.VARIANT_BVH))[:2], want, (name, move, "bvh"))
+    same(upd.render(params(name, binding.VARIANT_REFERENCE))[:2], want, (name, move, "reference on the updated context"))
+    if move == "lift":
+        gs, ws = upd.render_samples(p), fresh.render_samples(p)
+        assert gs[1] == ws[1] == want[1] and gs[0].tobytes() == want[0].tobytes()
+        assert gs[2].tobytes() == ws[2].tobytes(), (name, move, "samples")
+
+
+# ---- 10: the refitted rows, bit for bit ---------------------------------------------------------------------------------------------
+
+
+def first_difference(got, want):
+    bad = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
+    n, k = (int(v) for v in bad[0])
+    return f"{len(bad)} words differ; first: node {n} word {k}: device {got[n, k]!r} ({got.view(np.uint32)[n, k]:#x}) host {want[n, k]!r} ({want.view(np.uint32)[n, k]:#x})"
+
+
+@pytest.mark.parametrize("name", list(CASES))
+def test_downloaded_rows_equal_the_host_refit(upd, scenes, name):
+    sc, a = scenes[name]
+    upd.set_scene(sc)
+    built = binding.bvh_describe(sc.spheres.contents)[1]
+    assert upd.bvh_download().tobytes() == built.tobytes()  # before any update: the builder's rows
+    for move in ("identity",) + MOVES:
+        x, y, z = moved_centres(a, move)
+        upd.update_centers(0, x, y, z)
+        got, want = upd.bvh_download(), binding.bvh_refit_describe(sc.spheres.contents, x, y, z)[1]
+        assert got.shape == want.shape
+        assert got.tobytes() == want.tobytes(), (name, move, first_difference(got, want))
+
+
+@pytest.mark.parametrize("name", ["large", "grid160x100"])
+def test_ten_successive_updates_equal_one_refit(upd, fresh, scenes, name):
+    """Each update starts from the previous positions; boxes are recomputed, never accumulated."""
+    sc, a = scenes[name]
+    lat = lattice_of(a)
+    rng = np.random.default_rng(99)
+    x, y, z = (a[k].copy() for k in ("center_x", "center_y", "center_z"))
+    upd.set_scene(sc)
+    for step in range(10):
+        for v in (x, y, z):
+            v[lat] = (v[lat] + rng.uniform(-0.15, 0.15, len(lat))).astype(F)
+        upd.update_centers(0, x, y, z)
+    got, want = upd.bvh_download(), binding.bvh_refit_describe(sc.spheres.contents, x, y, z)[1]
+    assert got.tobytes() == want.tobytes(), first_difference(got, want)
+    p = params(name)
+    same(upd.render(p)[:2], fresh_render(fresh, a, sc.camera.contents, x, y, z, p), (name, "after ten updates"))
+
+
+# ---- 8: edge trees, partial ranges ----------------------------------------------------------------------------------------------------
+
+
+def edge_camera(w, h):
+    return binding.camera_look_at([0, 2, 14], [0, 0, 0], [0, 1, 0], 40.0, w / h, 0.05, 14.0)
+
+
+def edge_arrays(arrs, mt):
+    d = dict(arrs)
+    d["mat_type"] = mt
+    return d
+
+
+@pytest.mark.parametrize("n_active", [0, 1, 4, 5])
+def test_edge_trees_with_placeholders(upd, fresh, n_active):
+    cs, arrs, mt = edge_scene(n_active)
+    a = edge_arrays(arrs, mt)
+    w, h = 64, 48
+    cam = edge_camera(w, h)
+    p = r1.make_params(w, h, 3, 31)
+    rng = np.random.default_rng(40 + n_active)
+    x, y, z = ((arrs[k] + rng.uniform(-2, 2, cs.count)).astype(F) for k in ("center_x", "center_y", "center_z"))
+    upd.set_scene_raw(cs, cam)
+    upd.update_centers(0, x, y, z)
+    want = fresh_render(fresh, a, cam, x, y, z, p)
+    same(upd.render(p)[:2], want, (n_active, "whole range"))
+    same(upd.render(r1.make_params(w, h, 3, 31, variant=binding.VARIANT_REFERENCE))[:2], want, (n_active, "reference"))
+    if n_active:
+        assert want[0].tobytes() != fresh_render(fresh, a, cam, None, None, None, p)[0].tobytes()  # the move shows
+    assert upd.bvh_download().tobytes() == binding.bvh_refit_describe(cs, x, y, z)[1].tobytes()
+
+
+@pytest.mark.parametrize("seed", [0, 1, 2, 4])
+def test_random_raw_scenes(upd, fresh, seed):
+    """Random clouds of mixed radii (degenerate ones, coincident centres, a ground sphere) with every centre redrawn."""
+    cs, arrs, mt, rad, c2 = random_cloud(seed)
+    a = edge_arrays(arrs, mt)
+    w, h = 64, 48
+    cam = binding.camera_look_at([0, 6, 40], [0, 0, 0], [0, 1, 0], 50.0, w / h, 0.0, 40.0)
+    p = r1.make_params(w, h, 2, 33)
+    x, y, z = c2[:, 0].copy(), c2[:, 1].copy(), c2[:, 2].copy()
+    upd.set_scene_raw(cs, cam)
+    upd.update_centers(0, x, y, z)
+    want = fresh_render(fresh, a, cam, x, y, z, p)
+    same(upd.render(p)[:2], want, (seed, "default"))
+    same(upd.render(r1.make_params(w, h, 2, 33, variant=binding.VARIANT_REFERENCE))[:2], want, (seed, "reference"))
+    got, host = upd.bvh_download(), binding.bvh_refit_describe(cs, x, y, z)[1]
+    assert got.tobytes() == host.tobytes(), first_difference(got, host)
+
+
+def test_partial_range_spanning_placeholders(upd, fresh):
+    cs, arrs, mt = edge_scene(5)
+    a = edge_arrays(arrs, mt)
+    w, h = 64, 48
+    cam = edge_camera(w, h)
+    p = r1.make_params(w, h, 3, 32)
+    first, count = 2, cs.count - 5
+    assert (arrs["inv_radius"][first:first + count] == 0).any() and (arrs["inv_radius"][first:first + count] != 0).any()
+    rng = np.random.default_rng(8)
+    x, y, z = (arrs[k].copy() for k in ("center_x", "center_y", "center_z"))
+    for v in (x, y, z):
+        v[first:first + count] = (v[first:first + count] + rng.uniform(-2, 2, count)).astype(F)
+    upd.set_scene_raw(cs, cam)
+    upd.update_centers(first, x[first:first + count], y[first:first + count], z[first:first + count])
+    same(upd.render(p)[:2], fresh_render(fresh, a, cam, x, y, z, p), "partial range")
+    # a non-finite entry of a placeholder is ignored
+    xs = x[first:first + count].copy()
+    xs[np.nonzero(arrs["inv_radius"][first:first + count] == 0)[0][0]] = np.nan
+    upd.update_centers(first, xs, y[first:first + count], z[first:first + count])
+    same(upd.render(p)[:2], fresh_render(fresh, a, cam, x, y, z, p), "NaN in a placeholder's entry")
+    # count == 0 touches nothing, whatever the pointers
+    assert binding.lib().r1_update_centers(upd._c, 3, 0, None, None, None, None) == binding.R1_OK
+
+
+# ---- 9: the device form ---------------------------------------------------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("name", ["large", "grid160x100"])
+def test_device_form_equals_host_form_and_a_nan_centre_equals_set_scene(upd, fresh, scenes, name):
+    import torch
+    sc, a = scenes[name]
+    p = params(name)
+    x, y, z = moved_centres(a, "jitter")
+    upd.set_scene(sc)
+    upd.update_centers(0, x, y, z)
+    host_form = upd.render(p)[:2]
+    host_rows = upd.bvh_download()
+    upd.set_scene(sc)
+    t = [torch.from_numpy(v).cuda() for v in (x, y, z)]
+    upd.update_centers_device(0, len(x), t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
+    same(upd.render(p)[:2], host_form, (name, "device form"))
+    assert upd.bvh_download().tobytes() == host_rows.tobytes()
+    same(host_form, fresh_render(fresh, a, sc.camera.contents, x, y, z, p), (name, "host form"))
+    # one sphere with a NaN centre: it can never be hit; r1_set_scene with the same arrays drops it as inactive
+    lat = lattice_of(a)
+    xn = x.copy()
+    xn[lat[len(lat) // 3]] = np.nan
+    tn = torch.from_numpy(xn).cuda()
+    upd.update_centers_device(0, len(x), tn.data_ptr(), t[1].data_ptr(), t[2].data_ptr())
+    want = fresh_render(fresh, a, sc.camera.contents, xn, y, z, p)
+    same(upd.render(p)[:2], want, (name, "NaN centre"))
+    same(upd.render(params(name, binding.VARIANT_REFERENCE))[:2], want, (name, "NaN centre, reference"))
+    got, host = upd.bvh_download(), binding.bvh_refit_describe(sc.spheres.contents, xn, y, z)[1]
+    assert got.tobytes() == host.tobytes(), first_difference(got, host)
+    # a partial range through the device form
+    first, count = 7, len(x) - 20
+    upd.set_scene(sc)
+    upd.update_centers_device(first, count, t[0][first:].data_ptr(), t[1][first:].data_ptr(), t[2][first:].data_ptr())
+    xp, yp, zp = (a[k].copy() for k in ("center_x", "center_y", "center_z"))
+    xp[first:first + count], yp[first:first + count], zp[first:first + count] = x[first:first + count], y[first:first + count], z[first:first + count]
+    same(upd.render(p)[:2], fresh_render(fresh, a, sc.camera.contents, xp, yp, zp, p), (name, "device form, partial range"))
+
+
+# ---- 11: ray queries --------------------------------------------------------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("name", list(CASES))
+def test_ray_queries_after_an_update(upd, scenes, name):
+    sc, a = scenes[name]
+    x, y, z = moved_centres(a, "lift")
+    upd.set_scene(sc)
+    upd.update_centers(0, x, y, z)
+    cs, keep = raw_from_arrays(a, x, y, z)
+    rng = np.random.default_rng(17)
+    n = 4096
+    rays = np.zeros((n, 8), F)
+    rays[:, 0:3] = np.stack([rng.uniform(-12, 12, n), rng.uniform(0.0, 6, n), rng.uniform(-12, 12, n)], 1)
+    act = np.nonzero(a["inv_radius"] != 0)[0]
+    tgt = act[rng.integers(0, len(act), n)]
+    d = np.stack([x[tgt], y[tgt], z[tgt]], 1).astype(np.float64) + rng.normal(0, 0.05, (n, 3)) - rays[:, 0:3]
+    rays[:, 4:7] = (d / np.linalg.norm(d, axis=1, keepdims=True)).astype(F)
+    rays[:, 3] = np.where(rng.random(n) < 0.25, rng.uniform(0.5, 8, n), np.finfo(F).max).astype(F)
+    for mode in (binding.CAST_CLOSEST, binding.CAST_ANY):
+        want = binding.cast_rays_host(cs, rays, mode)
+        assert (want["index"] >= 0).sum() > n // 4 if mode == binding.CAST_CLOSEST else want.sum() > n // 4
+        for variant in (binding.VARIANT_DEFAULT, binding.VARIANT_REFERENCE):
+            got = upd.cast_rays(rays, mode, variant)
+            assert got.tobytes() == want.tobytes(), (name, mode, variant)
+    expect_refusal(lambda: upd.cast_rays(rays, binding.CAST_CLOSEST, binding.VARIANT_GRID), MOVED_RULE)
+
+
+# ---- 12: stream order -------------------------------------------------------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("name", ["large", "grid40x30"])
+def test_stream_order_and_a_path_batch_after_an_update(upd, fresh, scenes, name):
+    sc, a = scenes[name]
+    w, h = CASES[name][:2]
+    p = params(name)
+    x, y, z = moved_centres(a, "lift")
+    fa, fb = binding.HostFrames(w, h, 1), binding.HostFrames(w, h, 1)
+    cams = binding.orbit_cameras(sc, 5)[1:4]
+    hp = binding.HostFrames(w, h, 3)
+    try:
+        upd.set_scene(sc)
+        upd.render_async(p, fa)          # frame A: the old scene
+        upd.update_centers(0, x, y, z)
+        upd.render_async(p, fb)          # frame B: the moved one
+        upd.sync()                       # one wait for all three
+        old = fresh_render(fresh, a, sc.camera.contents, None, None, None, p)
+        assert fa.rays(0) == old[1] and fa.image(0).tobytes() == old[0].tobytes(), "frame A must see the old scene"
+        new = fresh_render(fresh, a, sc.camera.contents, x, y, z, p)
+        assert fb.rays(0) == new[1] and fb.image(0).tobytes() == new[0].tobytes(), "frame B must see the moved scene"
+        assert old[0].tobytes() != new[0].tobytes()
+        # a path batch of three cameras on the updated context = per-frame renders on the fresh one
+        upd.render_path_async(p, cams, hp, seed_stride=3)
+        upd.sync()
+        for f, cam in enumerate(cams):
+            fresh.set_camera(cam)
+            img, rays, _ = fresh.render(r1.make_params(w, h, p.spp, p.seed + 3 * f))
+            assert hp.rays(f) == rays and hp.image(f).tobytes() == img.tobytes(), (name, "path frame", f)
+    finally:
+        fa.close(), fb.close(), hp.close()
+
+
+# ---- 13: state ---------------------------------------------------------------------------------------------------------------------------
+
+
+def test_state_rules(upd, fresh, scenes):
+    sc, a = scenes["large"]
+    n = sc.count
+    p = params("large")
+    x, y, z = moved_centres(a, "jitter")
+    blank = r1.Renderer(0)
+    try:
+        expect_refusal(lambda: blank.update_centers(0, x, y, z), "no scene set")
+        import torch
+        t = torch.zeros(8, device="cuda")
+        expect_refusal(lambda: blank.update_centers_device(0, 8, t.data_ptr(), t.data_ptr(), t.data_ptr()), "no scene set")
+    finally:
+        blank.close()
+    upd.set_scene(sc)
+    original = upd.render(p)[:2]
+    info0 = upd.launch_info()
+    expect_refusal(lambda: upd.update_centers(1, x, y, z), "beyond the scene")
+    expect_refusal(lambda: upd.update_centers(n, x[:1], y[:1], z[:1]), "beyond the scene")
+    fp = lambda v: v.ctypes.data_as(C.POINTER(C.c_float))
+    assert binding.lib().r1_update_centers(upd._c, 0, n, None, fp(y), fp(z), None) == binding.R1_EINVAL
+    assert binding.lib().r1_update_centers_device(upd._c, 0, n, None, None, None, None) == binding.R1_EINVAL
+    lat = lattice_of(a)
+    for bad in (np.nan, np.inf):
+        yb = y.copy()
+        yb[lat[3]] = bad
+        expect_refusal(lambda: upd.update_centers(0, x, yb, z), "not finite")
+    # nothing was changed or enqueued by the refused calls: the un-updated scene, every variant still served
+    same(upd.render(p)[:2], original, "after refused updates")
+    same(upd.render(params("large", binding.VARIANT_PREFILTER))[:2], original, "prefilter before any update")
+    # a progressive accumulation ends at an update, as at r1_set_camera
+    half = r1.make_params(p.width, p.height, 2, p.seed)
+    upd.render_pass(half, 0)
+    upd.render_pass(half, 2)
+    same(upd.render(p)[:2], original, "plain render between")
+    upd.render_pass(half, 0)
+    before = upd.launch_info()
+    upd.update_centers(0, x, y, z)
+    assert upd.launch_info() == before           # an update is no launch of a frame
+    with pytest.raises(binding.R1Error) as e:
+        upd.render_pass(half, 2)
+    assert e.value.code == binding.R1_EINVAL
+    # the variants whose structures were not refitted stop, and say why
+    for variant in (binding.VARIANT_PREFILTER, binding.VARIANT_STATS, binding.VARIANT_WAVEFRONT, binding.VARIANT_GRID, binding.VARIANT_GRID_STATS):
+        expect_refusal(lambda: upd.render(params("large", variant)), MOVED_RULE)
+        expect_refusal(lambda: upd.render(params("large", variant)), "r1_set_scene rebuilds")
+    rays = np.zeros((4, 8), F)
+    rays[:, 6] = -1
+    rays[:, 3] = 100
+    expect_refusal(lambda: upd.cast_rays(rays, binding.CAST_CLOSEST, binding.VARIANT_GRID), MOVED_RULE)
+    moved = upd.render(p)[:2]
+    same(upd.render(params("large", binding.VARIANT_BVH_STATS))[:2], moved, "the tree's diagnostic build after an update")
+    same(moved, fresh_render(fresh, a, sc.camera.contents, x, y, z, p), "moved")
+    assert moved[0].tobytes() != original[0].tobytes()
+    # the trap: r1_set_scene with the ORIGINAL arrays must rebuild, not find "everything current"
+    upd.set_scene(sc)
+    same(upd.render(p)[:2], original, "r1_set_scene(original arrays) after an update")
+    same(upd.render(params("large", binding.VARIANT_GRID))[:2], original, "grid re-enabled")
+    same(upd.render(params("large", binding.VARIANT_PREFILTER))[:2], original, "prefilter re-enabled")
+    # the same trap through the device form, where the host copies never saw the move
+    import torch
+    t = [torch.from_numpy(v).cuda() for v in (x, y, z)]
+    upd.update_centers_device(0, n, t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
+    same(upd.render(p)[:2], moved, "device form")
+    upd.set_scene(sc)
+    same(upd.render(p)[:2], original, "r1_set_scene(original arrays) after a device-form update")
+    # r1_set_scene with the moved arrays = the updated context's render
+    upd.update_centers(0, x, y, z)
+    got = upd.render(p)[:2]
+    cs, keep = raw_from_arrays(a, x, y, z)
+    upd.set_scene_raw(cs, sc.camera.contents)
+    same(upd.render(p)[:2], got, "r1_set_scene(moved arrays) on the updated context")
+    same(upd.render(params("large", binding.VARIANT_GRID))[:2], got, "grid on the moved arrays")
+    assert info0["kernel"] == binding.VARIANT_BVH
+
+
+def test_rayweek1_hip_bounce(tmp_path):
+    """The drop-in program's --bounce: one `bounce:` line per scene, and with -w the first and the middle frame, which differ."""
+    exe = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "rays1bench_amd", "lib", "rayweek1_hip")
+    w, h, spp = 64, 48, 2
+    out = subprocess.run([exe, "--bounce", "4", "-n", "1", "-w", "--width", str(w), "--height", str(h), "--spp", str(spp)], cwd=tmp_path,
+                         capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if " bounce: " in l]
+    assert [l.split()[0] for l in lines] == ["small", "medium", "large"], out.stdout[-2000:]
+    for l in lines:
+        m = re.search(r"bounce: 4 frames, (\d+) of (\d+) spheres moving, update ([0-9.]+) ms per frame .* render ([0-9.]+) ms per frame, (\d+) rays", l)
+        assert m and int(m.group(5)) > 0, l
+    assert "480 of" in lines[2]
+    a, b = ((tmp_path / f"bounce_large_{f:03d}.tga").read_bytes() for f in (0, 2))
+    assert len(a) == len(b) == 18 + w * h * 3 and a != b
