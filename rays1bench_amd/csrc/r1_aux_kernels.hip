@@ -1,6 +1,7 @@
 // r1_aux_kernels.hip — the kernels around the trace kernel (wavefront variant, resolve, progressive accumulate, batch counts, assemble) and the launch
 // dispatch called from r1_capi.cpp.  The trace kernel template and its device functions: r1_trace.hpp.
 #include "r1_trace.hpp"
+#include "r1_internal.h"
 
 
 // ============================================================================================
@@ -491,83 +492,35 @@ extern "C" hipError_t r1_launch_put_cameras(void *dst, const float *cameras20, i
 }
 
 // The trace kernel's instantiations live in six translation units (tree / exhaustive sweep / uniform grid x small / big scenes); each exports one
-// launch and one occupancy function for its family.
-#define R1_TU_DECL(NAME)                                                                                                               \
-    extern "C" hipError_t r1_tu_##NAME##_launch(const R1TraceArgs *args, int variant, int mode, int batch, int blocks, size_t dyn_lds, \
-                                                hipStream_t stream);                                                                  \
-    extern "C" hipError_t r1_tu_##NAME##_occupancy(int variant, int mode, size_t dyn_lds, int *blocks_per_cu);
-R1_TU_DECL(tree_small)
-R1_TU_DECL(tree_big)
-R1_TU_DECL(sweep_small)
-R1_TU_DECL(sweep_big)
-R1_TU_DECL(grid_small)
-R1_TU_DECL(grid_big)
-#undef R1_TU_DECL
+// launch and one occupancy function for its family (r1_internal.h), which finds the build in the family's list.
 
-// The kernel mode that is built for (variant, big) given what the caller would like (0 samples + one guided queue,
-// 1 latency, 2 pixel): the reference-form sweep only exists in mode 0, the diagnostic builds follow the latency
-// mode, big scenes have no latency mode.
-extern "C" int r1_trace_mode(int variant, int big, int wanted)
+// b: the build r1_pick chose (r1_capi.cpp choose_kernel); which builds exist is the lists' business, what is checked here is that the arguments are
+// those the build reads.  grid_lds: the grid kernels' 16-bit tables in LDS (small scenes; R1GridArgs::lds_bytes, which lives in device memory)
+extern "C" hipError_t r1_launch_trace(const R1TraceArgs *args, R1Build b, int blocks, size_t grid_lds, hipStream_t stream)
 {
-    if (wanted == 4) // progressive passes: the product variants' MODE 4 builds (r1_pass_kernel); none of the diagnostic builds
-        return variant == 1 || variant == 2 || variant == 4 || variant == 7 ? 4 : -1;
-    if (wanted == 6) // adaptive sampling: the MODE 6 builds (r1_adaptive_kernel) of the tree, the grouped sweep and the grid
-        return variant == 2 || variant == 4 || variant == 7 ? 6 : -1;
-    if (variant == 1)
-        return 0;
-    if (variant == 3 || variant == 5 || variant == 8)
-        return big ? 0 : 1;
-    if (wanted == 1)
-        return big ? 0 : 1;
-    return wanted == 2 ? 2 : 0;
-}
-
-// grid_lds: the grid kernels' 16-bit tables in LDS (small scenes; R1GridArgs::lds_bytes, which lives in device memory)
-// path: a camera path (the MODE 5 builds: mode 0 with a batch block that ends in the camera table, R1PathArgs)
-extern "C" hipError_t r1_launch_trace(const R1TraceArgs *args, int variant, int big_in, int mode, int path, int blocks, size_t grid_lds, hipStream_t stream)
-{
-    const bool big = big_in != 0; // 32-bit hit indices, attenuation stack in the global workspace
-    const bool tree = variant == 4 || variant == 5;
-    const bool grid = variant == 7 || variant == 8;
-    const size_t walk_lds = r1_walk_lds(tree ? 4 : grid ? 7 : 0, big, args->bvh_depth, args->bvh_lds_f4, grid_lds);
-    if (mode != r1_trace_mode(variant, big_in, mode))
-        return hipErrorInvalidValue; // the caller sizes its arguments by the mode: it must be the one that is built
-    const int batch = args->batch != nullptr; // frame batches: the MODE 3 build of the throughput kernels (variants 2, 4 and 7 only)
-    if (batch && mode != 4 && mode != 6 && (mode != 0 || (variant != 2 && variant != 4 && variant != 7)))
+    // (a batch's or path's numbers, a pass's first sample and a listed pass's tile list are read through args->batch; the single-frame builds take none)
+    if ((r1_mode_is_batch(b.mode) || r1_mode_is_pass(b.mode)) != (args->batch != nullptr))
         return hipErrorInvalidValue;
-    if ((mode == 4 || mode == 6) && !batch)
-        return hipErrorInvalidValue; // (a pass reads its first sample, a listed pass its tile list too, through args->batch)
-    if (path && (!batch || mode != 0))
-        return hipErrorInvalidValue; // (batches only, and so variants 2, 4 and 7 only)
-    if (variant == 3 && big)
-        variant = 2; // (no diagnostic build of the LDS-tiled sweep)
     // the throughput builds of the product kernels sum their tiles themselves (R1_LAND): a launch through them says on how many XCDs
-    const bool land_kernel = variant == 4 && R1_LAND_MODE(mode);
-    if (land_kernel != (args->land_res > 0u))
+    if (r1_build_lands(b.variant, b.stats, b.mode) != (args->land_res > 0u))
         return hipErrorInvalidValue;
-    if (path)
-        mode = 5; // (lands its tiles as mode 0 / 3 does)
-    if (tree)
-        return big ? r1_tu_tree_big_launch(args, variant, mode, batch, blocks, walk_lds, stream) : r1_tu_tree_small_launch(args, variant, mode, batch, blocks, walk_lds, stream);
-    if (grid && args->grid == nullptr)
+    const size_t walk_lds = r1_walk_lds(b.variant, b.big, args->bvh_depth, args->bvh_lds_f4, grid_lds);
+    if (r1_is_tree(b.variant))
+        return b.big ? r1_tu_tree_big_launch(args, b, blocks, walk_lds, stream) : r1_tu_tree_small_launch(args, b, blocks, walk_lds, stream);
+    if (r1_is_grid(b.variant) && args->grid == nullptr)
         return hipErrorInvalidValue; // (the grid kernels read their tables through this pointer)
-    if (grid && mode == 2 && !big)
-        return hipErrorInvalidValue; // (the grid's PIXEL mode runs through its big-scene kernel)
-    if (grid)
-        return big ? r1_tu_grid_big_launch(args, variant, mode, batch, blocks, walk_lds, stream) : r1_tu_grid_small_launch(args, variant, mode, batch, blocks, walk_lds, stream);
-    return big ? r1_tu_sweep_big_launch(args, variant, mode, batch, blocks, 0, stream) : r1_tu_sweep_small_launch(args, variant, mode, batch, blocks, 0, stream);
+    if (r1_is_grid(b.variant))
+        return b.big ? r1_tu_grid_big_launch(args, b, blocks, walk_lds, stream) : r1_tu_grid_small_launch(args, b, blocks, walk_lds, stream);
+    return b.big ? r1_tu_sweep_big_launch(args, b, blocks, walk_lds, stream) : r1_tu_sweep_small_launch(args, b, blocks, walk_lds, stream);
 }
 
-extern "C" hipError_t r1_trace_occupancy(int variant, int big, int mode, size_t dyn_lds, int *blocks_per_cu)
+extern "C" hipError_t r1_trace_occupancy(R1Build b, size_t dyn_lds, int *blocks_per_cu)
 {
-    const bool tree = variant == 4 || variant == 5;
-    if (variant == 3 && big)
-        variant = 2;
-    if (tree)
-        return big ? r1_tu_tree_big_occupancy(variant, mode, dyn_lds, blocks_per_cu) : r1_tu_tree_small_occupancy(variant, mode, dyn_lds, blocks_per_cu);
-    if (variant == 7 || variant == 8)
-        return big ? r1_tu_grid_big_occupancy(variant, mode, dyn_lds, blocks_per_cu) : r1_tu_grid_small_occupancy(variant, mode, dyn_lds, blocks_per_cu);
-    return big ? r1_tu_sweep_big_occupancy(variant, mode, 0, blocks_per_cu) : r1_tu_sweep_small_occupancy(variant, mode, 0, blocks_per_cu);
+    if (r1_is_tree(b.variant))
+        return b.big ? r1_tu_tree_big_occupancy(b, dyn_lds, blocks_per_cu) : r1_tu_tree_small_occupancy(b, dyn_lds, blocks_per_cu);
+    if (r1_is_grid(b.variant))
+        return b.big ? r1_tu_grid_big_occupancy(b, dyn_lds, blocks_per_cu) : r1_tu_grid_small_occupancy(b, dyn_lds, blocks_per_cu);
+    return b.big ? r1_tu_sweep_big_occupancy(b, 0, blocks_per_cu) : r1_tu_sweep_small_occupancy(b, 0, blocks_per_cu);
 }
 
 // generate + (max_bounces + 1) x (intersect, shade); every launch reads its queue length on the device

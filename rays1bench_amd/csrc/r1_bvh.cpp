@@ -52,6 +52,7 @@
 
 #include "r1_device.h"
 #include "r1_bvh.h"
+#include "r1_internal.h"
 #include "../../include/rays1.h"
 
 #include <algorithm>
@@ -516,7 +517,6 @@ void r1_build_bvh(uint32_t na, const float *cx, const float *cy, const float *cz
 // reference's arithmetic (NaN/inf discriminant or roots fail every compare, rayweek1.cpp:204,
 // :297-309) and is dropped like a placeholder, which also keeps such values out of the builders.
 // One helper for r1_set_scene and r1_bvh_describe, so both see the same spheres.
-extern "C" void r1_set_error(const char *fmt, ...);
 int r1_active_spheres(const r1_scene *s, std::vector<uint32_t> &active_to_scene)
 {
     active_to_scene.clear();

@@ -22,33 +22,8 @@
 #include "r1_device.h"
 #include "r1_grid.h"
 
-extern "C" hipError_t r1_launch_trace(const R1TraceArgs *args, int variant, int big, int mode, int path, int blocks, size_t grid_lds, hipStream_t stream);
-extern "C" int r1_trace_mode(int variant, int big, int wanted); // 0 samples + one queue, 1 latency, 2 pixel, 4 pass, 6 listed pass: what is built for (variant, big)
-extern "C" hipError_t r1_launch_resolve(const R1ResolveArgs *args, int max_rows, hipStream_t stream);
-extern "C" hipError_t r1_launch_accum(const R1AccumArgs *args, hipStream_t stream);
-extern "C" hipError_t r1_launch_adapt_accum(const R1AdaptArgs *args, hipStream_t stream);
-extern "C" hipError_t r1_launch_adapt_compact(const uint32_t *cur, uint32_t n_cur, const R1TileReport *report, uint32_t at_cap, uint32_t *next, uint32_t *count_out,
-                                              hipStream_t stream);
-extern "C" hipError_t r1_launch_wavefront(R1WaveArgs *w, int blocks, hipStream_t stream);
-extern "C" hipError_t r1_launch_land_arm(uint32_t *tile_cnt, unsigned long long *frame_rays, uint32_t *frame_left, uint32_t n_frames, uint32_t n_local_tiles,
-                                         int width, int height, int spp, int tile_w, int tile_h, int tiles_x, int shard, int num_shards, hipStream_t stream);
-extern "C" hipError_t r1_launch_put6(void *dst, const uint32_t *words, hipStream_t stream);
-extern "C" hipError_t r1_launch_put8(void *dst, const uint32_t *words, hipStream_t stream);
-extern "C" hipError_t r1_launch_put_cameras(void *dst, const float *cameras20, int n, hipStream_t stream); // n cameras of 20 floats each, host memory read during the call
-extern "C" hipError_t r1_launch_assemble(const void *blocks, void *rgb, int width, int height, int tile_w, int tile_h, int tiles_x, int num_shards,
-                                         size_t shard_stride, int n_frames, size_t frame_in, size_t frame_out, size_t total_offset, long long total_out,
-                                         int want_total, hipStream_t stream);
-extern "C" size_t r1_frame_record_bytes(const r1_params *p); // r1_host.cpp
-extern "C" hipError_t r1_trace_occupancy(int variant, int big, int mode, size_t dyn_lds, int *blocks_per_cu);
-extern "C" hipError_t r1_launch_cast(const R1CastArgs *args, int structure, int big, int plain, int blocks, size_t dyn_lds, hipStream_t stream); // r1_cast.hip
-extern "C" hipError_t r1_cast_occupancy(int structure, int big, int plain, size_t dyn_lds, int *blocks_per_cu);
-extern "C" int r1_params_check(const r1_params *p); // r1_host.cpp
-
 #include "r1_bvh.h" // r1_bvh.cpp: the built tree, a refit's topology tables
-
-// r1_refit.hip: the kernels of r1_update_centers* 
-extern "C" hipError_t r1_launch_refit_move(const R1RefitArgs *a, uint32_t first, uint32_t count, const float *x, const float *y, const float *z, hipStream_t stream);
-extern "C" hipError_t r1_launch_refit(const R1RefitArgs *a, const uint32_t *height_off, uint32_t heights, hipStream_t stream);
+#include "r1_internal.h"
 
 // ---- errors ---------------------------------------------------------------------------------
 
@@ -154,11 +129,11 @@ struct r1_context
     // one page-locked, device-visible word: the synchronous entry points let the frame's last launch store the ray count
     // straight into host memory (8 bytes over PCIe at the end of r1_resolve_kernel) instead of enqueueing a second copy
     unsigned long long *host_word = nullptr, *host_word_dev = nullptr;
-    int default_variant = 4;    // what R1_VARIANT_DEFAULT resolves to for the scene in the context (r1_set_scene): synchronous frames
-    int default_variant_tp = 4; // ... and frames in flight (the throughput kernels: measured apart, the two kernel families do not rank alike)
-    int occupancy[224] = {0}; // [variant + 16 * big + 32 * mode]
+    int default_variant = R1_V_TREE;    // what R1_VARIANT_DEFAULT resolves to for the scene in the context (r1_set_scene): synchronous frames
+    int default_variant_tp = R1_V_TREE; // ... and frames in flight (the throughput kernels: measured apart, the two kernel families do not rank alike)
+    int occupancy[8 * 2 * 2 * R1_MODES] = {0}; // blocks per CU of the trace kernel's builds, [occupancy_slot(build)]
     bool pixel_mode = false; // r1_set_pixel_mode
-    DevBuf gstack; // blocks per CU of the trace kernel, by variant
+    DevBuf gstack;
     DevBuf land_spill; // R1_LAND: [waves of the grid][tiles of the launch] every wave's list of the tiles it took chunks from
     // progressive passes (r1_render_pass): the frame being accumulated
     DevBuf accum;              // [local tile][pixel of the padded tile] fp32 {r, g, b, 0}
@@ -289,6 +264,23 @@ extern "C" int r1_create(int device, r1_context **out)
 // internal (r1_multi.cpp): the context's own stream, so that the in-process multi-GPU path runs its collectives on the stream the
 // context's uploads and frames already use instead of a second stream per device (every stream wants a hardware queue)
 extern "C" void *r1_context_stream(r1_context *c) { return c ? (void *)c->stream : nullptr; }
+
+// internal (tests/test_builds_host.py): r1_pick as the frames' choose_kernel calls it
+extern "C" int r1_pick_build(int variant, int big, int want, int *build4)
+{
+    R1Build b = {0, false, false, 0};
+    if (!r1_pick(variant, big != 0, want, b))
+        return 0;
+    build4[0] = b.variant, build4[1] = b.stats ? 1 : 0, build4[2] = b.big ? 1 : 0, build4[3] = b.mode;
+    return 1;
+}
+
+// internal (the same test): what the predicates of r1_builds.h answer
+extern "C" void r1_build_facts(int variant, int mode, int big, int *facts6)
+{
+    facts6[0] = r1_is_tree(variant), facts6[1] = r1_is_grid(variant), facts6[2] = r1_is_stats(variant), facts6[3] = r1_base_variant(variant);
+    facts6[4] = r1_mode_is_tp_family(mode), facts6[5] = r1_runs_as_latency(mode, big != 0);
+}
 
 extern "C" void r1_destroy(r1_context *c)
 {
@@ -726,7 +718,7 @@ extern "C" int r1_set_scene(r1_context *c, const r1_scene *s, const r1_camera *c
     c->src_mat.assign(s->mat_type, s->mat_type + s->count);
     c->src_cam = *cam;
     c->have_scene = true;
-    c->default_variant = c->default_variant_tp = 4;
+    c->default_variant = c->default_variant_tp = R1_V_TREE;
     return R1_OK;
 }
 
@@ -967,9 +959,9 @@ struct Landing
     bool used = false;
 };
 
-// A progressive pass (r1_render_pass): samples [first_sample, first_sample + spp) traced by the MODE 4 kernels, then r1_accum_kernel instead of
+// A progressive pass (r1_render_pass): samples [first_sample, first_sample + spp) traced by the R1_MODE_PASS kernels, then r1_accum_kernel instead of
 // the resolve launch.  d_out of enqueue_frame receives the preview unless `image` is false.
-// A pass of r1_render_adaptive has a tile list: the launch's tiles are list[0, n_listed) of the frame's, traced by the MODE 6 kernels and summed
+// A pass of r1_render_adaptive has a tile list: the launch's tiles are list[0, n_listed) of the frame's, traced by the R1_MODE_LISTED kernels and summed
 // and tested by r1_adapt_accum_kernel (accumulators and reports: the context's, indexed by tile of the frame).
 struct Pass
 {
@@ -1064,12 +1056,12 @@ static int ensure_grid(r1_context *c)
 
 // ---- one frame, step by step (enqueue_frame at the end) ------------------------------------------------------------------------------
 
-// What a frame launches (internal variant numbering = the public enum, DEFAULT resolved): decided once by choose_kernel, read by every step.
+// What a frame launches: decided once by choose_kernel, read by every step.
 struct Choice
 {
-    int variant, big, mode;
-    bool tree, grid, stats, wavefront; // box tree (4, 5), uniform grid (7, 8), a diagnostic build (3, 5, 8), variant 6
-    bool pixel, path, listed;          // PIXEL mode; a camera path of >= 2 frames; a pass over listed tiles
+    int variant;      // what was asked for, R1_V_* (DEFAULT resolved): r1_launch_info's kernel; a diagnostic wish (r1_is_stats) keeps its counters
+                      // even where the product build runs in its place
+    R1Build b;        // the build of the trace body that runs (r1_pick); the wavefront variant: the build its launches are sized by
     bool land;        // tiles resolved inside the trace kernel: the product kernels' launches; the diagnostic builds, the reference-form
                       // sweep, the wavefront variant and PIXEL mode keep the round-3 form (records + r1_resolve_kernel, or no records at all)
     bool fused_clear; // the frame's last launch publishes the ray count and zeroes the counter block (close_frame)
@@ -1090,11 +1082,12 @@ static bool big_scene(const r1_context *c, bool tree, bool grid, bool grid_pixel
 // the exhaustive sweep, BVH always the tree; all of them produce the same pixels.
 static int resolve_variant(const r1_context *c, int32_t wanted, bool throughput_mode)
 {
-    static_assert(R1_VARIANT_REFERENCE == 1 && R1_VARIANT_STATS == 3 && R1_VARIANT_BVH == 4 && R1_VARIANT_BVH_STATS == 5 && R1_VARIANT_WAVEFRONT == 6 &&
-                  R1_VARIANT_GRID == 7 && R1_VARIANT_GRID_STATS == 8, "the kernels' variant numbers");
+    static_assert(R1_VARIANT_REFERENCE == R1_V_REFERENCE && R1_VARIANT_PREFILTER == R1_V_SWEEP && R1_VARIANT_STATS == R1_V_SWEEP_STATS &&
+                  R1_VARIANT_BVH == R1_V_TREE && R1_VARIANT_BVH_STATS == R1_V_TREE_STATS && R1_VARIANT_WAVEFRONT == R1_V_WAVEFRONT &&
+                  R1_VARIANT_GRID == R1_V_GRID && R1_VARIANT_GRID_STATS == R1_V_GRID_STATS, "the kernels' variant numbers (r1_builds.h)");
     if (wanted == R1_VARIANT_DEFAULT)
         return throughput_mode ? c->default_variant_tp : c->default_variant;
-    return wanted >= R1_VARIANT_REFERENCE && wanted <= R1_VARIANT_GRID_STATS ? wanted : 2;
+    return wanted >= R1_VARIANT_REFERENCE && wanted <= R1_VARIANT_GRID_STATS ? wanted : R1_V_SWEEP;
 }
 
 // Kernel choice, after the launch's tiles are known (size_tiles) and the grid is built.  Kernel mode: the host-returning entry points run
@@ -1104,28 +1097,38 @@ static int resolve_variant(const r1_context *c, int32_t wanted, bool throughput_
 static int choose_kernel(const r1_context *c, const r1_params *p, int variant, bool throughput_mode, const Batch *batch, const Pass *pass, Choice &k)
 {
     k.variant = variant;
-    k.tree = variant == 4 || variant == 5, k.grid = variant == 7 || variant == 8, k.stats = variant == 3 || variant == 5 || variant == 8, k.wavefront = variant == 6;
-    k.listed = pass && pass->list;
-    k.path = batch && batch->cameras && batch->n_frames > 1; // (a path of one frame: the single-frame kernel with that camera by value)
-    k.big = big_scene(c, k.tree, k.grid, throughput_mode && c->pixel_mode) ? 1 : 0;
-    static const int tp_mode_env = (int)r1_knob("R1_TP_MODE", -1); // tuning experiments
-    const int tp_mode = c->pixel_mode ? 2 : (tp_mode_env >= 0 && tp_mode_env <= 2 ? tp_mode_env : 0);
-    k.mode = k.wavefront ? 0 : r1_trace_mode(variant, k.big, pass ? (k.listed ? 6 : 4) : (throughput_mode ? tp_mode : 1));
-    if (k.mode < 0)
+    const bool wavefront = variant == R1_V_WAVEFRONT;
+    const bool big = big_scene(c, r1_is_tree(variant), r1_is_grid(variant), throughput_mode && c->pixel_mode);
+    const bool frames = batch && batch->n_frames > 1; // (a batch or path of one frame: the single-frame kernel, a path's camera by value)
+    static const int tp_mode_env = (int)r1_knob("R1_TP_MODE", -1); // tuning experiments: R1_MODE_TP, _LAT or _PIXEL for the throughput entry points
+    int want = R1_MODE_LAT;
+    if (pass)
+        want = pass->list ? R1_MODE_LISTED : R1_MODE_PASS;
+    else if (throughput_mode && (c->pixel_mode || tp_mode_env == R1_MODE_PIXEL))
+        want = R1_MODE_PIXEL;
+    else if (throughput_mode && !(tp_mode_env == R1_MODE_LAT && !big)) // (big scenes have no latency build: the knob leaves them alone)
+        want = !frames ? R1_MODE_TP : batch->cameras ? R1_MODE_PATH : R1_MODE_BATCH;
+    // (the wavefront variant has kernels of its own; its grid is sized as the grouped sweep's frames in flight are)
+    const bool built = wavefront ? r1_pick(R1_V_SWEEP, big, R1_MODE_TP, k.b) : r1_pick(variant, big, want, k.b);
+    if (!built && pass)
     {
         r1_set_error("variant %d has no progressive-pass build", p->variant);
         return R1_EINVAL;
     }
-    k.pixel = k.mode == 2;
-    if (batch && (k.mode != 0 || k.wavefront || k.stats || variant == 1))
+    if (batch && (!built || !r1_mode_is_tp_family(k.b.mode) || wavefront || r1_is_stats(variant) || variant == R1_V_REFERENCE))
     {
         r1_set_error("frame batches run through the throughput kernels only (no PIXEL mode, no diagnostic / reference-form / wavefront variant)");
         return R1_EINVAL;
     }
-    k.land = variant == 4 && R1_LAND_MODE(k.mode) && c->total_samples > 0;
+    if (!built)
+    {
+        r1_set_error("variant %d has no kernel for this call", p->variant);
+        return R1_EINVAL;
+    }
+    k.land = r1_build_lands(k.b.variant, k.b.stats, k.b.mode) && c->total_samples > 0;
     // Frames without a resolve launch, and the diagnostic builds, whose counters are read back afterwards, count into the caller's word
     // and clear with memsets.
-    k.fused_clear = !k.land && !k.pixel && c->n_local_tiles && c->total_samples && !k.stats;
+    k.fused_clear = !k.land && k.b.mode != R1_MODE_PIXEL && c->n_local_tiles && c->total_samples && !r1_is_stats(variant);
     return R1_OK;
 }
 
@@ -1153,14 +1156,14 @@ static int size_tiles(r1_context *c, const r1_params *p, int n_frames, const Pas
 static int ensure_records(r1_context *c, const r1_params *p, const Choice &k, const Batch *batch, hipStream_t st)
 {
     int rc;
-    if (batch && !(R1_LAND && k.variant == 4))
+    if (batch && !(R1_LAND && k.variant == R1_V_TREE))
     {
         // partial ray counts of the resolve launch: one uint64 per (tile of the batch, workgroup column)
         const size_t cols = ((size_t)p->tile_w * p->tile_h + 255) / 256;
         if ((rc = ensure(c->batch_rays, (size_t)batch->n_frames * (c->n_local_tiles ? c->n_local_tiles : 1) * cols * 8)))
             return rc;
     }
-    if (k.pixel)
+    if (k.b.mode == R1_MODE_PIXEL)
         return R1_OK;
     const size_t want = (size_t)(c->total_samples ? c->total_samples : 1) * 16;
     const bool fresh = !c->samples.p || c->samples.cap < want;
@@ -1212,12 +1215,12 @@ static void frame_args(const r1_context *c, const r1_params *p, const Choice &k,
     a.coop_lanes = coop_env >= 0 ? (uint32_t)coop_env : R1_COOP_LANES;
     a.samples = (float4 *)c->samples.p;
     a.num_rays = k.fused_clear ? (unsigned long long *)((char *)c->counters.p + 32) : (unsigned long long *)d_rays;
-    a.stats = k.stats ? (unsigned long long *)((char *)c->counters.p + 128) : nullptr;
-    if (k.grid)
-        a.grid = (const R1GridArgs *)(k.big ? c->grid_dev32.p : c->grid_dev.p), a.scene.bvh_root_leaf = 0u; // (the grid kernels' fallback walks the tree from its root: no root step, r1_trace.hpp)
+    a.stats = r1_is_stats(k.variant) ? (unsigned long long *)((char *)c->counters.p + 128) : nullptr;
+    if (r1_is_grid(k.variant))
+        a.grid = (const R1GridArgs *)(k.b.big ? c->grid_dev32.p : c->grid_dev.p), a.scene.bvh_root_leaf = 0u; // (the grid kernels' fallback walks the tree from its root: no root step, r1_trace.hpp)
     static const int big_top_env = (int)r1_knob("R1_BIG_TOP", R1_BVH_TOP_NODES); // tuning experiments
-    fill_walk(c, k.tree, k.big, (uint32_t)std::max(1, big_top_env), a);
-    if (k.pixel)
+    fill_walk(c, r1_is_tree(k.variant), k.b.big, (uint32_t)std::max(1, big_top_env), a);
+    if (k.b.mode == R1_MODE_PIXEL)
     {
         // the queue holds the padded pixels of the shard's tiles, and `samples` is the output the kernel resolves into
         const uint32_t tp = (uint32_t)(p->tile_w * p->tile_h);
@@ -1274,21 +1277,22 @@ static int put_path_cameras(r1_context *c, const Batch *batch, hipStream_t st, c
 }
 
 // R1TraceArgs::batch (null in a single frame): a batch's numbers, behind them a path's camera table; or a pass's first sample and tile
-// list, which the MODE 4 / 6 kernels read where a sample is seeded.
+// list, which the R1_MODE_PASS / _LISTED kernels read where a sample is seeded.
 static int put_batch_block(r1_context *c, const Choice &k, const Batch *batch, const Pass *pass, hipStream_t st, R1TraceArgs &a)
 {
     static_assert(sizeof(R1BatchArgs) == 24 && sizeof(R1PassArgs) == 24, "r1_launch_put6 writes the six words of R1BatchArgs / R1PassArgs");
     static_assert(sizeof(R1PathArgs) == 32 && __builtin_offsetof(R1PathArgs, cameras) == 24, "r1_launch_put8 writes the eight words of R1PathArgs into a 32-byte slot");
     int rc;
-    if (batch && batch->n_frames > 1)
+    if (r1_mode_is_batch(k.b.mode))
     {
+        const bool path = k.b.mode == R1_MODE_PATH;
         R1PathArgs pa;
         memset(&pa, 0, sizeof(pa));
         pa.batch.n_frames = (uint32_t)batch->n_frames, pa.batch.seed_stride = batch->seed_stride;
         pa.batch.div_tiles = make_div(c->n_local_tiles ? c->n_local_tiles : 1u), pa.batch.n_local_tiles = c->n_local_tiles;
-        if (k.path && (rc = put_path_cameras(c, batch, st, &pa.cameras)))
+        if (path && (rc = put_path_cameras(c, batch, st, &pa.cameras)))
             return rc;
-        if ((rc = put_batch_args(c, &pa, k.path ? 8 : 6, k.path ? nullptr : &pa.batch, st, &a.batch)))
+        if ((rc = put_batch_args(c, &pa, path ? 8 : 6, path ? nullptr : &pa.batch, st, &a.batch)))
             return rc;
     }
     if (pass)
@@ -1303,12 +1307,16 @@ static int put_batch_block(r1_context *c, const Choice &k, const Batch *batch, c
 }
 
 // Workgroups per CU of the chosen kernel with the dynamic LDS its launch will have (r1_walk_lds: the size r1_launch_trace launches with),
-// 1 .. 8.  Asked once per (variant, big, mode) of a scene: the tree kernels' LDS footprint follows the tree, r1_set_scene clears the cache.
+// 1 .. 8.  Asked once per build and scene: the tree kernels' LDS footprint follows the tree, r1_set_scene clears the cache.
+static int occupancy_slot(const R1Build &b) { return ((b.variant * 2 + (b.stats ? 1 : 0)) * 2 + (b.big ? 1 : 0)) * R1_MODES + b.mode; }
 static int blocks_per_cu(r1_context *c, const Choice &k, const R1TraceArgs &a, int *per_cu)
 {
-    int &occ = c->occupancy[k.variant + 16 * k.big + 32 * k.mode];
+    R1Build b = k.b;
+    if (r1_mode_is_batch(b.mode))
+        b.mode = R1_MODE_TP; // (the batch build of a kernel has the occupancy of its single-frame build)
+    int &occ = c->occupancy[occupancy_slot(b)];
     if (occ == 0)
-        R1_HIP(r1_trace_occupancy(k.variant, k.big, k.mode, r1_walk_lds(k.tree ? 4 : k.grid ? 7 : 0, k.big, a.bvh_depth, a.bvh_lds_f4, c->grid_args.lds_bytes), &occ));
+        R1_HIP(r1_trace_occupancy(b, r1_walk_lds(b.variant, b.big, a.bvh_depth, a.bvh_lds_f4, c->grid_args.lds_bytes), &occ));
     static const int per_cu_env = (int)r1_knob("R1_BLOCKS_PER_CU", 0); // tuning experiments
     *per_cu = std::min(std::max(occ, 1), 8);
     if (per_cu_env > 0 && per_cu_env < *per_cu)
@@ -1318,8 +1326,8 @@ static int blocks_per_cu(r1_context *c, const Choice &k, const R1TraceArgs &a, i
 
 // The persistent grid and how its waves take work from the queue.  Changes nothing but its result.
 struct GridSize { long long blocks; uint32_t chunk_min, chunk_max, nq; };
-// total: sample slots of the launch; pixels: PIXEL mode — the padded pixels the queue holds instead — else 0
-static GridSize size_grid(int cus, int per_cu, uint32_t total, uint32_t pixels, int mode, bool throughput_mode, int num_shards, bool big)
+// total: sample slots of the launch; pixels: PIXEL mode — the padded pixels the queue holds instead — else 0; latency: r1_runs_as_latency of the build
+static GridSize size_grid(int cus, int per_cu, uint32_t total, uint32_t pixels, bool pixel_mode, bool latency, bool throughput_mode, int num_shards)
 {
     GridSize g;
     // Latency mode (the synchronous host entry points: one frame, the caller waits): as many waves as fit, every lane at least one
@@ -1345,7 +1353,7 @@ static GridSize size_grid(int cus, int per_cu, uint32_t total, uint32_t pixels, 
     // but they must stay small against a wave's share of the frame (8 shards: 1024 costs 12 %).
     static const int chunk_max_env = (int)r1_knob("R1_CHUNK", 0), chunk_min_env = (int)r1_knob("R1_CHUNK_MIN", 0), nq_env = (int)r1_knob("R1_NQ", 0);
     const long long waves = g.blocks * (R1_BLOCK / 64);
-    if (mode == 2) // chunks in pixels (a wave holds 64 pixels at a time)
+    if (pixel_mode) // chunks in pixels (a wave holds 64 pixels at a time)
     {
         g.chunk_max = (uint32_t)std::min(128LL, std::max(16LL, (long long)pixels / (waves * 12)));
         g.chunk_min = 8;
@@ -1360,7 +1368,7 @@ static GridSize size_grid(int cus, int per_cu, uint32_t total, uint32_t pixels, 
     // dry is the frame's tail: with 256-sample chunks the waves found the queue empty over a span of 0.7 ms), which one counter cannot
     // serve: sub-queues.
     g.nq = 1;
-    if (mode == 1 || ((mode == 4 || mode == 6) && !big))
+    if (latency)
     {
         // a wave only ever pulls from its home sub-queue (r1_trace.hpp: home = (4 (block / 8) + wave) % nq), so every
         // sub-queue needs home waves: the full groups of 8 workgroups must cover all nq residues
@@ -1471,11 +1479,11 @@ static int prepare_memory(r1_context *c, const Choice &k, long long blocks, int 
 {
     int rc;
     // (the small-scene tree kernels keep the first 3 * R1_STACK_LDS_WORDS stack entries in LDS and use the workspace beyond)
-    if (k.big || (R1_STACK_LDS_WORDS < R1_STACK_WORDS && (k.tree || k.grid)))
+    if (k.b.big || (R1_STACK_LDS_WORDS < R1_STACK_WORDS && (r1_is_tree(k.variant) || r1_is_grid(k.variant))))
     {
         // sized for the largest grid of this kernel (not this frame's): a frame with a bigger grid must not reallocate
         // (sized for the build that keeps the fewest words in LDS: the latency / diagnostic builds keep R1_STACK_LDS_WORDS, the throughput builds R1_STACK_LDS_WORDS_TP)
-        const size_t entries = k.big ? R1_STACK_ENTRIES : R1_STACK_ENTRIES - 3 * (R1_STACK_LDS_WORDS < R1_STACK_LDS_WORDS_TP ? R1_STACK_LDS_WORDS : R1_STACK_LDS_WORDS_TP);
+        const size_t entries = k.b.big ? R1_STACK_ENTRIES : R1_STACK_ENTRIES - 3 * (R1_STACK_LDS_WORDS < R1_STACK_LDS_WORDS_TP ? R1_STACK_LDS_WORDS : R1_STACK_LDS_WORDS_TP);
         const size_t max_blocks = std::max((size_t)blocks, (size_t)c->cus * (size_t)per_cu);
         if ((rc = ensure(c->gstack, entries * max_blocks * R1_BLOCK * 4)))
             return rc;
@@ -1484,7 +1492,7 @@ static int prepare_memory(r1_context *c, const Choice &k, long long blocks, int 
     if (!k.land && !c->counters_clean)
         R1_HIP(hipMemsetAsync(c->counters.p, 0, R1_COUNTER_BYTES, st));
     c->counters_clean = false;
-    if (k.stats)
+    if (r1_is_stats(k.variant))
     {
         c->wave_log_waves = (uint32_t)blocks * (R1_BLOCK / 64);
         if ((rc = ensure(c->wave_log, (size_t)c->wave_log_waves * 32)))
@@ -1536,7 +1544,7 @@ static int close_frame(r1_context *c, const r1_params *p, const Choice &k, const
     unsigned long long *rays_dst = k.fused_clear ? (unsigned long long *)d_rays : nullptr;
     uint32_t *reset = k.fused_clear ? (uint32_t *)c->counters.p : nullptr;
     static const int resolve_rows = (int)r1_knob("R1_RESOLVE_ROWS", R1_RESOLVE_ROWS_TP); // tuning experiments
-    if (k.listed && c->n_local_tiles)
+    if (k.b.mode == R1_MODE_LISTED && c->n_local_tiles)
     {
         // adaptive sampling: the records go into the listed tiles' two accumulators, their `all` bytes into d_out, and every listed tile is tested
         const int32_t n = pass->first_sample + p->spp;
@@ -1570,7 +1578,7 @@ static int close_frame(r1_context *c, const r1_params *p, const Choice &k, const
     }
     else if (k.land)
         ; // the trace launch resolved its tiles itself
-    else if (c->n_local_tiles && !k.pixel)
+    else if (c->n_local_tiles && k.b.mode != R1_MODE_PIXEL)
     {
         R1ResolveArgs r;
         memset(&r, 0, sizeof(r));
@@ -1610,14 +1618,14 @@ static int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int blo
     if (rc)
         return rc;
     const int variant = resolve_variant(c, p->variant, throughput_mode);
-    if (c->moved && variant != 1 && variant != 4 && variant != 5)
+    if (c->moved && variant != R1_V_REFERENCE && !r1_is_tree(variant))
     {
         r1_set_error("variant %d: the scene has moved (r1_update_centers) and only the box tree was refitted, not the sphere groups and the uniform grid; "
                      "r1_set_scene rebuilds them", variant);
         return R1_EINVAL;
     }
     R1_HIP(hipSetDevice(c->device));
-    if ((variant == 7 || variant == 8) && (rc = ensure_grid(c)))
+    if (r1_is_grid(variant) && (rc = ensure_grid(c)))
         return rc;
     if ((rc = size_tiles(c, p, batch ? batch->n_frames : 1, pass)))
         return rc;
@@ -1634,7 +1642,8 @@ static int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int blo
     int per_cu = 1, land_parity = 0;
     if ((rc = blocks_per_cu(c, k, a, &per_cu)))
         return rc;
-    const GridSize g = size_grid(c->cus, per_cu, c->total_samples, k.pixel ? a.total_samples : 0u, k.mode, throughput_mode, p->num_shards, k.big != 0);
+    const bool pixel_mode = k.b.mode == R1_MODE_PIXEL;
+    const GridSize g = size_grid(c->cus, per_cu, c->total_samples, pixel_mode ? a.total_samples : 0u, pixel_mode, r1_runs_as_latency(k.b.mode, k.b.big), throughput_mode, p->num_shards);
     a.chunk_min = g.chunk_min, a.chunk_max = g.chunk_max, a.nq = g.nq;
     long long blocks = g.blocks;
     if (k.land && (rc = land_setup(c, p, batch, landing, blocks, block_layout, st, a, d_out, d_rays, land_parity)))
@@ -1645,9 +1654,9 @@ static int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int blo
         return rc;
 
     R1_HIP(hipEventRecord(e[0], st));
-    if (c->total_samples && !k.wavefront)
-        R1_HIP(r1_launch_trace(&a, variant, k.big, k.mode, k.path ? 1 : 0, (int)blocks, k.grid && !k.big ? c->grid_args.lds_bytes : 0u, st));
-    if (c->total_samples && k.wavefront && (rc = launch_wavefront(c, a, st, &blocks)))
+    if (c->total_samples && variant != R1_V_WAVEFRONT)
+        R1_HIP(r1_launch_trace(&a, k.b, (int)blocks, r1_is_grid(variant) && !k.b.big ? c->grid_args.lds_bytes : 0u, st));
+    if (c->total_samples && variant == R1_V_WAVEFRONT && (rc = launch_wavefront(c, a, st, &blocks)))
         return rc;
     R1_HIP(hipEventRecord(e[1], st));
     if ((rc = close_frame(c, p, k, batch, pass, a.tiles_x, d_out, block_layout, d_rays, throughput_mode, st)))
@@ -1706,7 +1715,7 @@ static int render_host(r1_context *c, const r1_params *p, uint8_t *rgb_out, uint
         return rc;
     // the ray count: stored by the frame's last launch straight into the context's page-locked word (no second copy to
     // enqueue and wait for); the diagnostic builds count with atomics and keep a device word + copy
-    const bool stats = p->variant == R1_VARIANT_STATS || p->variant == R1_VARIANT_BVH_STATS || p->variant == R1_VARIANT_GRID_STATS;
+    const bool stats = r1_is_stats(p->variant);
     const bool direct = !stats && c->host_word_dev;
     // a page-locked pixel buffer (r1_host_alloc) receives the tiles straight from the trace kernel's resolvers: no copy either
     Landing land_to;
@@ -1829,7 +1838,7 @@ extern "C" int r1_render_pass(r1_context *c, const r1_params *p, int32_t first_s
         r1_set_error("r1_render_pass renders whole frames (num_shards == 1)");
         return R1_EINVAL;
     }
-    if (p->variant == R1_VARIANT_STATS || p->variant == R1_VARIANT_BVH_STATS || p->variant == R1_VARIANT_GRID_STATS || p->variant == R1_VARIANT_WAVEFRONT)
+    if (r1_is_stats(p->variant) || p->variant == R1_VARIANT_WAVEFRONT)
     {
         r1_set_error("r1_render_pass: variant %d (a diagnostic build or the wavefront variant) has no progressive-pass build", p->variant);
         return R1_EINVAL;
@@ -2141,7 +2150,7 @@ extern "C" int r1_render_batch_async(r1_context *c, const r1_params *p, int32_t 
     return R1_OK;
 }
 
-// A camera path: r1_render_batch_async with cameras[f] in place of the context's camera for frame f (the MODE 5 kernels; one frame: the
+// A camera path: r1_render_batch_async with cameras[f] in place of the context's camera for frame f (the R1_MODE_PATH kernels; one frame: the
 // single-frame kernel with cameras[0] by value).  The context's own camera is not touched.
 extern "C" int r1_render_path_async(r1_context *c, const r1_params *p, int32_t n_frames, uint32_t seed_stride, const r1_camera *cameras, void *host_frames,
                                     void *hip_stream)
@@ -2200,7 +2209,7 @@ extern "C" int r1_render_shard_device_batch(r1_context *c, const r1_params *p, i
 
 static_assert(sizeof(r1_ray) == 32 && sizeof(r1_hit) == 32, "the cast kernels read and write these layouts as two float4");
 
-// the checks every cast entry point makes before it touches anything; *structure: 4 box tree, 7 uniform grid, 1 reference form
+// the checks every cast entry point makes before it touches anything; *structure: what the rays walk — R1_V_TREE, R1_V_GRID or R1_V_REFERENCE
 static int cast_check(const char *who, r1_context *c, int32_t variant, int32_t mode, int *structure)
 {
     if (!c)
@@ -2216,9 +2225,9 @@ static int cast_check(const char *who, r1_context *c, int32_t variant, int32_t m
     switch (variant)
     {
     case R1_VARIANT_DEFAULT:
-    case R1_VARIANT_BVH: *structure = 4; break;
-    case R1_VARIANT_GRID: *structure = 7; break;
-    case R1_VARIANT_REFERENCE: *structure = 1; break;
+    case R1_VARIANT_BVH: *structure = R1_V_TREE; break;
+    case R1_VARIANT_GRID: *structure = R1_V_GRID; break;
+    case R1_VARIANT_REFERENCE: *structure = R1_V_REFERENCE; break;
     default:
         r1_set_error("%s: variant %d casts no rays (DEFAULT, BVH, GRID and REFERENCE do)", who, variant);
         return R1_EINVAL;
@@ -2228,7 +2237,7 @@ static int cast_check(const char *who, r1_context *c, int32_t variant, int32_t m
         r1_set_error("%s: no scene set (call r1_set_scene first)", who);
         return R1_EINVAL;
     }
-    if (c->moved && *structure == 7)
+    if (c->moved && *structure == R1_V_GRID)
     {
         r1_set_error("%s: the scene has moved (r1_update_centers) and the uniform grid was not refitted; r1_set_scene rebuilds it", who);
         return R1_EINVAL;
@@ -2243,27 +2252,27 @@ static int cast_enqueue(r1_context *c, int structure, int32_t mode, const void *
     int rc;
     R1_HIP(hipSetDevice(c->device));
     if (c->n_active == 0)
-        structure = 1; // (no sphere can be hit: the reference form's loop of zero trips writes the misses; there is no tree to stage)
-    if (structure == 7 && (rc = ensure_grid(c)))
+        structure = R1_V_REFERENCE; // (no sphere can be hit: the reference form's loop of zero trips writes the misses; there is no tree to stage)
+    if (structure == R1_V_GRID && (rc = ensure_grid(c)))
         return rc;
-    const bool big = big_scene(c, structure == 4, structure == 7, false);
+    const bool big = big_scene(c, structure == R1_V_TREE, structure == R1_V_GRID, false);
     static const int plain_env = (int)r1_knob("R1_CAST_PLAIN", 0); // tuning library only: the plain form of the tree cast (r1_cast.hip), for measuring
-    const int plain = structure == 4 && plain_env ? 1 : 0;
+    const int plain = structure == R1_V_TREE && plain_env ? 1 : 0;
 
     R1CastArgs a;
     memset(&a, 0, sizeof(a));
     fill_scene(c, a.t.scene); // (the sweep's tables ride along: the cast kernels read none of them)
     // (the grid's fallback and the plain form walk the tree from its root, read from global memory: no root step)
-    if (structure == 7 || plain)
+    if (structure == R1_V_GRID || plain)
         a.t.scene.bvh_root_leaf = 0u;
-    fill_walk(c, structure == 4 && !plain, big, R1_BVH_TOP_NODES, a.t);
-    if (structure == 7)
+    fill_walk(c, structure == R1_V_TREE && !plain, big, R1_BVH_TOP_NODES, a.t);
+    if (structure == R1_V_GRID)
         a.t.grid = (const R1GridArgs *)(big ? c->grid_dev32.p : c->grid_dev.p);
     a.active_to_scene = (const uint32_t *)c->active_dev.p;
     a.mode = (uint32_t)mode;
     // (the plain form: a 32-bit traversal stack and no node table)
     const size_t dyn_lds = plain ? (size_t)a.t.bvh_depth * R1_BLOCK * 4 : r1_walk_lds(structure, big, a.t.bvh_depth, a.t.bvh_lds_f4, c->grid_args.lds_bytes);
-    int &occ = c->cast_occupancy[(structure == 4 ? 0 : structure == 7 ? 2 : 4) + (big ? 1 : 0)];
+    int &occ = c->cast_occupancy[(structure == R1_V_TREE ? 0 : structure == R1_V_GRID ? 2 : 4) + (big ? 1 : 0)];
     if (occ == 0)
         R1_HIP(r1_cast_occupancy(structure, big ? 1 : 0, plain, dyn_lds, &occ));
     const int per_cu = occ < 1 ? 1 : (occ > 8 ? 8 : occ);

@@ -10,6 +10,7 @@
 // anything below it replaces it by the same rule.  The grid's walk starts at FLT_MAX and is filtered the same way.
 // A ray with a non-finite origin or (normalised) direction, or a t_max that is NaN or <= 0.001, is a miss before any walk (cast_load).
 #include "r1_trace.hpp"
+#include "r1_internal.h"
 
 #ifndef R1_CAST_WAVES_SMALL
 #define R1_CAST_WAVES_SMALL 8 // waves per SIMD the small-scene kernels are built for (registers, LDS: profiles/r10/cast.txt)
@@ -261,29 +262,29 @@ __global__ void __launch_bounds__(R1_BLOCK) r1_cast_plain_kernel(const R1CastArg
 #endif
 
 // ---- launchers (called from r1_capi.cpp) --------------------------------------------------------------------------------------------------
-// structure: 4 box tree, 7 uniform grid, 1 reference form; plain: the tuning library's plain tree form
+// variant: R1_V_TREE, R1_V_GRID or R1_V_REFERENCE — the structure the rays walk; plain: the tuning library's plain tree form
 #define R1_CAST_DISPATCH(X)                                                                                                            \
-    if (structure == 1)                                                                                                                \
+    if (variant == R1_V_REFERENCE)                                                                                                     \
         X(r1_cast_reference_kernel);                                                                                                   \
-    else if (structure == 7 && big)                                                                                                    \
+    else if (variant == R1_V_GRID && big)                                                                                              \
         X(r1_cast_grid_kernel<true>);                                                                                                  \
-    else if (structure == 7)                                                                                                           \
+    else if (variant == R1_V_GRID)                                                                                                     \
         X(r1_cast_grid_kernel<false>);                                                                                                 \
-    else if (structure == 4 && big)                                                                                                    \
+    else if (variant == R1_V_TREE && big)                                                                                              \
         X(r1_cast_tree_kernel<true>);                                                                                                  \
-    else if (structure == 4)                                                                                                           \
+    else if (variant == R1_V_TREE)                                                                                                     \
         X(r1_cast_tree_kernel<false>);
 
-extern "C" hipError_t r1_launch_cast(const R1CastArgs *args, int structure, int big, int plain, int blocks, size_t dyn_lds, hipStream_t stream)
+extern "C" hipError_t r1_launch_cast(const R1CastArgs *args, int variant, int big, int plain, int blocks, size_t dyn_lds, hipStream_t stream)
 {
 #ifdef R1_TUNING
-    if (plain && structure == 4)
+    if (plain && variant == R1_V_TREE)
     {
         hipLaunchKernelGGL(r1_cast_plain_kernel, dim3(blocks), dim3(R1_BLOCK), dyn_lds, stream, *args);
         return hipGetLastError();
     }
 #endif
-    if (plain || (structure != 1 && structure != 4 && structure != 7))
+    if (plain || (variant != R1_V_REFERENCE && variant != R1_V_TREE && variant != R1_V_GRID))
         return hipErrorInvalidValue;
 #define R1_GO(K) hipLaunchKernelGGL((K), dim3(blocks), dim3(R1_BLOCK), dyn_lds, stream, *args)
     R1_CAST_DISPATCH(R1_GO)
@@ -291,10 +292,10 @@ extern "C" hipError_t r1_launch_cast(const R1CastArgs *args, int structure, int 
     return hipGetLastError();
 }
 
-extern "C" hipError_t r1_cast_occupancy(int structure, int big, int plain, size_t dyn_lds, int *blocks_per_cu)
+extern "C" hipError_t r1_cast_occupancy(int variant, int big, int plain, size_t dyn_lds, int *blocks_per_cu)
 {
 #ifdef R1_TUNING
-    if (plain && structure == 4)
+    if (plain && variant == R1_V_TREE)
         return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, r1_cast_plain_kernel, R1_BLOCK, dyn_lds);
 #endif
 #define R1_OCC(K) return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, (K), R1_BLOCK, dyn_lds)

@@ -19,7 +19,7 @@
                               // round 3) a workgroup holds 22 KB = SEVEN workgroups per CU (23.4 KB each at most; six with round 2's 32-bit
                               // traversal stack); 4 / 6 / 8 / 10 / 12 words at six workgroups: 28.4 / 29.1 / 29.3 (32.3) / (32.5) / 28.2 Grays/s
 #ifndef R1_STACK_LDS_WORDS_TP
-#define R1_STACK_LDS_WORDS_TP 10 // the same for the THROUGHPUT builds of that kernel (MODE 0 / 3), kept apart for experiments: 6 words with the 32-bit
+#define R1_STACK_LDS_WORDS_TP 10 // the same for the THROUGHPUT builds of that kernel (r1_mode_is_tp_family), kept apart for experiments: 6 words with the 32-bit
 #endif                           // traversal stack was the first way to seven workgroups (+3 % from the wave, -1.7 % from the deeper global overflow)
 #define R1_RESOLVE_ROWS_TP 256 // frames in flight: rows of workgroups of the resolve launch (0 = one per tile; 16 / 64 / 256 / one per tile: 29.4 / 30.6 / 31.3 / 30.7 Grays/s over 20 steps, 34.9 / 34.85 / 34.87 / 34.7 over 300), see r1_launch_resolve
 #define R1_NODES_LDS_MAX 256  // tree kernel: scenes whose tree has at most this many nodes (16 KB) run the small-scene kernels, which keep
@@ -58,6 +58,7 @@
 #ifndef R1_LAND
 #define R1_LAND 1
 #endif
+#include "r1_builds.h" // the names of variants and modes, the predicates (r1_build_lands: which builds land their tiles), the list of builds
 // exhaustive sweep, exact phase (exact_trips): member spheres from a table in group order (one global fetch in the dependent chain instead
 // of two)
 #ifndef R1_EXACT_G
@@ -66,9 +67,6 @@
 #ifndef R1_SWEEP_PAIRS2
 #define R1_SWEEP_PAIRS2 1 // exhaustive sweep, group test: two pairs of groups interleaved (sweep_prefilter)
 #endif
-// (the synchronous frame's kernels, MODE 1, keep the resolve launch: 1.276 against 1.077 ms on the device with their tiles summed at wave
-// exit, i.e. at the end of the frame's critical path; profiles/r04/land_sync_frame.txt)
-#define R1_LAND_MODE(mode) (R1_LAND && ((mode) == 0 || (mode) == 3 || (mode) == 5))
 #define R1_LAND_CNT_STRIDE 32u  // words between two tiles' countdowns: every countdown on its own 128-byte line (an atomic on ONE line sustains ~88 M/s on this chip,
                                // tools/ubench_atomic.hip; the ~40 tiles a synchronous frame's waves work on at a time shared two lines at first: 3.8 ms per frame instead of 1.1)
 #define R1_LAND_MAX_WAIT (1u << 16) // passes over a claimed tile that still find a record of an earlier launch before the wave gives up and flags the launch
@@ -114,7 +112,7 @@ struct R1BatchArgs
     uint32_t n_local_tiles;
 };
 
-// Camera paths (r1_render_path_async, the MODE 5 builds): a batch's numbers and, behind them, the table of its frames' cameras — n_frames
+// Camera paths (r1_render_path_async, the R1_MODE_PATH builds): a batch's numbers and, behind them, the table of its frames' cameras — n_frames
 // entries of R1_PATH_CAM_F4 float4 (an R1DeviceCamera's 19 floats and one of padding: 16-byte aligned rows), device memory.  Eight words: one
 // batch-argument slot, written by r1_launch_put8.
 #define R1_PATH_CAM_F4 5
@@ -124,9 +122,9 @@ struct R1PathArgs
     const float *cameras;
 };
 
-// Progressive passes (r1_render_pass, the MODE 4 builds): the pass's first global sample index, device memory behind R1TraceArgs::batch
+// Progressive passes (r1_render_pass, the R1_MODE_PASS builds): the pass's first global sample index, device memory behind R1TraceArgs::batch
 // (null in every single-frame launch).  Six words: written by r1_launch_put6 into a batch-argument slot.
-// Adaptive sampling (r1_render_adaptive, the MODE 6 builds): behind it the pass's tile list — the launch's local tile j is tile list[j] of
+// Adaptive sampling (r1_render_adaptive, the R1_MODE_LISTED builds): behind it the pass's tile list — the launch's local tile j is tile list[j] of
 // the frame — device memory; null in a pass of r1_render_pass, whose kernels never read it.
 struct R1PassArgs
 {
@@ -262,15 +260,16 @@ struct R1TraceArgs
                                   // of such a chain from ~16 k cycles of dependent node fetches to ~4 k
 };
 
-// Dynamic LDS of a workgroup that walks the box tree (structure 4) or the uniform grid (7), trace and cast kernels alike; 0 for anything else.
+// Dynamic LDS of a workgroup that walks the box tree (variant R1_V_TREE) or the uniform grid (R1_V_GRID), trace and cast kernels alike, their diagnostic
+// builds included; 0 for anything else.
 // Tree: the traversal stack — bvh_depth entries per thread, 16-bit for small scenes and 32-bit for big ones — then bvh_lds_f4 float4 of the
 // node table.  Grid: the tree fallback's stack (32-bit entries), then (small scenes) grid_lds bytes of cell table and ids.  The occupancy
 // query and the launch both size by this one function: the grid of a frame is sized for the occupancy its launch has.
-static inline size_t r1_walk_lds(int structure, bool big, int32_t bvh_depth, uint32_t bvh_lds_f4, size_t grid_lds)
+static inline size_t r1_walk_lds(int variant, bool big, int32_t bvh_depth, uint32_t bvh_lds_f4, size_t grid_lds)
 {
-    if (structure == 4)
+    if (r1_is_tree(variant))
         return (size_t)bvh_depth * R1_BLOCK * (big ? 4 : 2) + (size_t)bvh_lds_f4 * 16;
-    if (structure == 7)
+    if (r1_is_grid(variant))
         return (size_t)bvh_depth * R1_BLOCK * 4 + (big ? 0 : grid_lds);
     return 0;
 }

@@ -12,6 +12,7 @@
 // operation by operation and this file is compiled with -ffp-contract=off.
 
 #include "../../include/rays1.h"
+#include "r1_internal.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -21,7 +22,6 @@
 #include <new>
 #include <vector>
 
-extern "C" void r1_set_error(const char *fmt, ...); // r1_capi.cpp
 
 namespace
 {

@@ -1,0 +1,65 @@
+// r1_internal.h — the C-linkage functions of the library that one file defines and another calls, and that include/rays1.h does not declare.
+// Included by the file that defines each of them and by every file that calls it: with C linkage a prototype that drifts would still link,
+// this way it does not compile.
+#ifndef R1_INTERNAL_H
+#define R1_INTERNAL_H
+
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../include/rays1.h"
+#include "r1_device.h"
+
+struct R1RefitArgs; // r1_bvh_fill.h
+
+extern "C"
+{
+// r1_capi.cpp
+void r1_set_error(const char *fmt, ...);
+void *r1_context_stream(r1_context *c); // the context's own stream (r1_multi.cpp runs its collectives on it)
+int r1_pick_build(int variant, int big, int want, int *build4); // r1_pick for tests: 1 and build4 = {variant, stats, big, mode}, or 0
+void r1_build_facts(int variant, int mode, int big, int *facts6);  // the predicates for tests: {tree, grid, stats, base variant, tp family, runs as latency}
+
+// r1_host.cpp
+int r1_params_check(const r1_params *p);
+
+// r1_trace_<family>.hip (r1_trace_tu.inc): the family's builds, by walking its list; hipErrorInvalidValue: not one of them
+#define R1_TU_DECL(NAME)                                                                                                       \
+    hipError_t r1_tu_##NAME##_launch(const R1TraceArgs *args, R1Build b, int blocks, size_t dyn_lds, hipStream_t stream);     \
+    hipError_t r1_tu_##NAME##_occupancy(R1Build b, size_t dyn_lds, int *blocks_per_cu);
+R1_TU_DECL(tree_small)
+R1_TU_DECL(tree_big)
+R1_TU_DECL(sweep_small)
+R1_TU_DECL(sweep_big)
+R1_TU_DECL(grid_small)
+R1_TU_DECL(grid_big)
+#undef R1_TU_DECL
+
+// r1_aux_kernels.hip
+hipError_t r1_launch_trace(const R1TraceArgs *args, R1Build b, int blocks, size_t grid_lds, hipStream_t stream);
+hipError_t r1_trace_occupancy(R1Build b, size_t dyn_lds, int *blocks_per_cu);
+hipError_t r1_launch_resolve(const R1ResolveArgs *args, int max_rows, hipStream_t stream);
+hipError_t r1_launch_accum(const R1AccumArgs *args, hipStream_t stream);
+hipError_t r1_launch_adapt_accum(const R1AdaptArgs *args, hipStream_t stream);
+hipError_t r1_launch_adapt_compact(const uint32_t *cur, uint32_t n_cur, const R1TileReport *report, uint32_t at_cap, uint32_t *next, uint32_t *count_out,
+                                   hipStream_t stream);
+hipError_t r1_launch_wavefront(R1WaveArgs *w, int blocks, hipStream_t stream);
+hipError_t r1_launch_land_arm(uint32_t *tile_cnt, unsigned long long *frame_rays, uint32_t *frame_left, uint32_t n_frames, uint32_t n_local_tiles, int width,
+                              int height, int spp, int tile_w, int tile_h, int tiles_x, int shard, int num_shards, hipStream_t stream);
+hipError_t r1_launch_put6(void *dst, const uint32_t *words, hipStream_t stream);
+hipError_t r1_launch_put8(void *dst, const uint32_t *words, hipStream_t stream);
+hipError_t r1_launch_put_cameras(void *dst, const float *cameras20, int n, hipStream_t stream); // n cameras of 20 floats each, host memory read during the call
+hipError_t r1_launch_assemble(const void *blocks, void *rgb, int width, int height, int tile_w, int tile_h, int tiles_x, int num_shards, size_t shard_stride,
+                              int n_frames, size_t frame_in, size_t frame_out, size_t total_offset, long long total_out, int want_total, hipStream_t stream);
+
+// r1_cast.hip; variant: R1_V_TREE, R1_V_GRID or R1_V_REFERENCE; plain: the tuning library's plain tree form
+hipError_t r1_launch_cast(const R1CastArgs *args, int variant, int big, int plain, int blocks, size_t dyn_lds, hipStream_t stream);
+hipError_t r1_cast_occupancy(int variant, int big, int plain, size_t dyn_lds, int *blocks_per_cu);
+
+// r1_refit.hip: the kernels of r1_update_centers* 
+hipError_t r1_launch_refit_move(const R1RefitArgs *a, uint32_t first, uint32_t count, const float *x, const float *y, const float *z, hipStream_t stream);
+hipError_t r1_launch_refit(const R1RefitArgs *a, const uint32_t *height_off, uint32_t heights, hipStream_t stream);
+}
+
+#endif

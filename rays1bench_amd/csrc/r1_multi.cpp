@@ -22,9 +22,8 @@
 #include <vector>
 
 #include "../../include/rays1.h"
+#include "r1_internal.h"
 
-extern "C" void r1_set_error(const char *fmt, ...);
-extern "C" void *r1_context_stream(r1_context *c); // r1_capi.cpp (internal): the context's own stream
 
 namespace
 {

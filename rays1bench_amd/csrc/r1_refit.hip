@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include "r1_bvh_fill.h"
+#include "r1_internal.h"
 
 #define R1_REFIT_BLOCK 256
 

@@ -1242,15 +1242,15 @@ __device__ __forceinline__ bool tile_pixel(const R1TraceArgs &A, const uint32_t 
 
 // sample slot k -> (tile, pixel, sample); then seeds + primary ray.
 // Returns false for a void slot (pixel of an edge tile that lies outside the image).
-// PASS (progressive passes, MODE 4): s is the pass-local sample index — the record's place — and the sample is seeded with its global
+// PASS (progressive passes, R1_MODE_PASS): s is the pass-local sample index — the record's place — and the sample is seeded with its global
 // index s + first_sample, which the pass's R1PassArgs hold behind A.batch.
-// PATH (camera paths, MODE 5): a batch whose frame f is seen through camera f of the table behind the batch's numbers (R1PathArgs).  The
+// PATH (camera paths, R1_MODE_PATH): a batch whose frame f is seen through camera f of the table behind the batch's numbers (R1PathArgs).  The
 // queue is frame-major and a wave's chunk may straddle frames, so f is a per-lane value and every lane loads its frame's camera itself:
-// five vector loads where start_ray needs them, dead before the walk — the builds keep the VGPR count of their MODE 3 siblings
+// five vector loads where start_ray needs them, dead before the walk — the builds keep the VGPR count of their R1_MODE_BATCH siblings
 // (tools/kernel_meta.py).  The other form — a loop over the wave's distinct f, the camera through scalar loads, the lanes of that frame
 // masked in — is not kept: hipcc proves `frame == f0` inside the masked arm, addresses the camera by the lane's own f again and hoists
 // start_ray out of the loop, i.e. emits these very loads behind a loop that only builds the address.
-// LIST (adaptive sampling, MODE 6): a PASS whose local tile j is tile list[j] of the frame (R1PassArgs::list); the record keeps the list
+// LIST (adaptive sampling, R1_MODE_LISTED): a PASS whose local tile j is tile list[j] of the frame (R1PassArgs::list); the record keeps the list
 // position.  j is a per-lane value (a wave's chunk may straddle tiles), so every lane loads its own entry, as a camera path's lanes do.
 template <bool BATCH = false, bool PASS = false, bool PATH = false, bool LIST = false>
 __device__ __forceinline__ bool start_sample(const R1TraceArgs &A, Path &p, uint32_t k)
@@ -1262,7 +1262,7 @@ __device__ __forceinline__ bool start_sample(const R1TraceArgs &A, Path &p, uint
     const uint32_t pix = fastdiv(r, A.div_spp);
     const uint32_t s = r - pix * (uint32_t)A.spp;
     uint32_t jl = j, seed = A.seed, frame = 0;
-    if (BATCH) // (its own build of the kernel, MODE 3: the single-frame kernels stay as they were, to the register)
+    if (BATCH) // (its own build of the kernel, R1_MODE_BATCH: the single-frame kernels stay as they were, to the register)
     {
         typedef const uint32_t __attribute__((address_space(4))) *cu32_ptr;
         const cu32_ptr b = (cu32_ptr)A.batch; // {n_frames, seed_stride, div_tiles{mul, shift, pow2}, n_local_tiles}
@@ -1772,7 +1772,7 @@ __device__ __forceinline__ void land_exit(const R1TraceArgs &A, uint32_t *row, c
 // The big-scene tree kernel waits for node fetches from L2, not for the VALU: it is built for 8 waves per SIMD (<= 64 VGPRs,
 // which it meets without the spare sample, and <= 96 SGPRs — at its natural 106 the 800 SGPRs of a SIMD hold seven waves):
 // 13.1 -> 14.4 Grays/s on 100 004 spheres.
-// (round 3: the small-scene tree kernels for frames in flight, MODE 0 / 3, run SEVEN workgroups per CU — their LDS footprint is 22 KB with
+// (round 3: the small-scene tree kernels for frames in flight, R1_MODE_TP / _BATCH, run SEVEN workgroups per CU — their LDS footprint is 22 KB with
 // R1_STACK_LDS_WORDS_TP — so they are built for 7 waves per SIMD: <= 73 VGPRs, which the kernel meets at 69, and <= 96 SGPRs)
 template <int VARIANT, bool STATS, bool BIG, int MODE>
 struct TraceWaves
@@ -1785,30 +1785,24 @@ struct TraceWaves
                             //  LDS stack less — it spills and is no faster: profiles/r04/retune_after_fresh_args.txt)
 #endif
     // (the grid's PIXEL-mode build — big-scene kernel only — is built for four waves: at eight it keeps a scratch slot for its SGPR spills)
-    static constexpr int value = STATS ? 1 : (VARIANT == 7 && MODE == 2) ? 4 : ((VARIANT == 4 || VARIANT == 7) ? (BIG ? 8 : ((MODE == 0 || MODE == 3 || MODE == 5) ? R1_TREE_WAVES_TP : R1_TREE_WAVES_LAT)) : (VARIANT == 2 && !BIG ? 5 : 1));
+    static constexpr int value = STATS ? 1 : (VARIANT == R1_V_GRID && MODE == R1_MODE_PIXEL) ? 4 : ((r1_is_tree(VARIANT) || r1_is_grid(VARIANT)) ? (BIG ? 8 : (r1_mode_is_tp_family(MODE) ? R1_TREE_WAVES_TP : R1_TREE_WAVES_LAT)) : (VARIANT == R1_V_SWEEP && !BIG ? 5 : 1));
 };
 
-// MODE 1 = LAT = latency-mode build (the synchronous entry points: one frame, full grid): sub-queues and
-// the cooperative tail are compiled in.  The throughput-mode build (frames in flight, few
-// long-lived waves per frame) leaves them out: they cost it registers and bring it nothing.
-// MODE 0 = frames in flight (the throughput entry point): samples in one guided queue, few long-lived waves per frame.
-// MODE 2 = PIXEL mode (the throughput entry point after r1_set_pixel_mode; see struct Pixel): the queue holds pixels.
-// MODE 5 = a camera path (r1_render_path_async): MODE 3 with one camera per frame, read from a device table where a sample starts.
-// MODE 4 = a progressive pass (r1_render_pass): small scenes as MODE 1, big scenes as MODE 0 without landing; the records take the pass-local
-// sample index, the seeds the global one (start_sample), and r1_accum_kernel sums them into the frame's accumulator.
-// MODE 6 = a pass over listed tiles (r1_render_adaptive): MODE 4 whose local tile j is tile list[j] (start_sample); r1_adapt_accum_kernel sums.
-// (the body of the kernel; r1_trace_kernel and, for the uniform grid, r1_grid_kernel below are its __global__ instances; r1_pass_kernel the MODE 4 ones)
+// MODE: one of R1_MODE_* (r1_builds.h names the seven and says what each is; which (VARIANT, STATS, BIG, MODE) are built: R1_BUILDS_* there).
+// The latency build (r1_runs_as_latency: R1_MODE_LAT, and a pass on a small scene) compiles in the sub-queues and the cooperative tail; the
+// throughput builds (r1_mode_is_tp_family: frames in flight, few long-lived waves per frame) leave them out: they cost them registers and
+// bring them nothing.  A pass on a big scene runs as R1_MODE_TP without landing; r1_accum_kernel / r1_adapt_accum_kernel sum a pass's records.
+// (the body of the kernel; r1_trace_kernel and, for the uniform grid, r1_grid_kernel below are its __global__ instances; r1_pass_kernel,
+// r1_path_kernel and r1_adaptive_kernel those of R1_MODE_PASS, _PATH and _LISTED)
 template <int VARIANT, bool STATS, bool BIG, int MODE>
 __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
 {
-    constexpr bool LISTED = MODE == 6;
-    constexpr bool PASS = MODE == 4 || LISTED;
-    constexpr bool CPATH = MODE == 5; // MODE 5 = MODE 3 whose frames each have a camera of their own (start_sample)
-    constexpr bool LAT = MODE == 1 || (PASS && !BIG), PIX = MODE == 2, BATCH = MODE == 3 || CPATH; // MODE 3 = MODE 0 whose queue spans the frames of a batch
-    // tiles resolved inside the kernel: the throughput builds of the tree kernels (frames in flight, MODE 0 / 3); a
-    // launch through them is a landing launch (r1_launch_trace checks).  The synchronous frame keeps the resolve launch (measured
-    // slower with its tiles summed at wave exit), and so do the exhaustive sweep's kernels.
-    constexpr bool LAND = R1_LAND_MODE(MODE) && !STATS && VARIANT == 4; // (the exhaustive sweep keeps the resolve launch: its loop pays 14 % for the bookkeeping, 16.6 against 19.2 Grays/s)
+    constexpr bool LISTED = MODE == R1_MODE_LISTED, PASS = r1_mode_is_pass(MODE);
+    constexpr bool CPATH = MODE == R1_MODE_PATH, BATCH = r1_mode_is_batch(MODE); // (a path's frames each have a camera of their own, start_sample)
+    constexpr bool LAT = r1_runs_as_latency(MODE, BIG), PIX = MODE == R1_MODE_PIXEL;
+    // tiles resolved inside the kernel: the throughput builds of the tree kernels; a launch through them is a landing
+    // launch (r1_launch_trace checks)
+    constexpr bool LAND = r1_build_lands(VARIANT, STATS, MODE);
     const uint32_t tb = blockIdx.x, n_tb = gridDim.x;
     // LAND: this workgroup's XCD (HW_REG_XCC_ID), the tiles of the launch
     const uint32_t xcd = LAND ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(xcc_id() & 7u)) : 0u;
@@ -1838,15 +1832,15 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
         log_start = __builtin_amdgcn_s_memrealtime();
     }
     // words of the attenuation stack in LDS (the rest of a deep path's entries live in the global workspace)
-    constexpr int LW = (VARIANT == 4 || VARIANT == 7) ? (((MODE == 0 || MODE == 3 || MODE == 5) && !STATS) ? R1_STACK_LDS_WORDS_TP : R1_STACK_LDS_WORDS) : R1_STACK_WORDS;
+    constexpr int LW = (r1_is_tree(VARIANT) || r1_is_grid(VARIANT)) ? ((r1_mode_is_tp_family(MODE) && !STATS) ? R1_STACK_LDS_WORDS_TP : R1_STACK_LDS_WORDS) : R1_STACK_WORDS;
     __shared__ uint32_t s_stack[BIG ? 1 : LW * R1_BLOCK];
-    __shared__ uint32_t s_cand[VARIANT == 2 ? (BIG ? R1_CAND_CAP : R1_BIT_WORDS) * R1_BLOCK : 1];
-    __shared__ IDX s_pairs[VARIANT == 2 ? (R1_BLOCK / 64) * PairBits<IDX>::cap : 1];
+    __shared__ uint32_t s_cand[VARIANT == R1_V_SWEEP ? (BIG ? R1_CAND_CAP : R1_BIT_WORDS) * R1_BLOCK : 1];
+    __shared__ IDX s_pairs[VARIANT == R1_V_SWEEP ? (R1_BLOCK / 64) * PairBits<IDX>::cap : 1];
     // R1_VARIANT_BVH: traversal stack [tree depth][thread], sized at launch (dynamic LDS)
     extern __shared__ uint32_t s_trav[];
     const uint32_t gstride = n_tb * R1_BLOCK, gtid = tb * R1_BLOCK + threadIdx.x;
-    __shared__ unsigned long long s_best[VARIANT == 2 ? R1_BLOCK : 1];
-    __shared__ f4 s_tile[BIG && VARIANT == 2 ? 2 * R1_TILE_F4 : 1];
+    __shared__ unsigned long long s_best[VARIANT == R1_V_SWEEP ? R1_BLOCK : 1];
+    __shared__ f4 s_tile[BIG && VARIANT == R1_V_SWEEP ? 2 * R1_TILE_F4 : 1];
 
     const int tid = (int)threadIdx.x;
     const int lane = tid & 63;
@@ -1855,14 +1849,14 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
     // the node table in LDS, behind the traversal stack.  A node visit is four dependent 16-byte loads per lane; LDS
     // answers sooner than the vector L1, and the table no longer competes with the sphere tables for its 32 KB:
     // 26.9 -> 29.3 Grays/s, one synchronous frame 1.34 -> 1.17 ms (large scene, 128 nodes = 8 KB).
-    constexpr bool LN = VARIANT == 4 && !BIG;
+    constexpr bool LN = VARIANT == R1_V_TREE && !BIG;
     typedef typename IdxType<!LN>::type TS; // traversal-stack entry: uint16_t for the small-scene tree kernels, else uint32_t
-    const size_t trav_words = VARIANT == 4 ? (size_t)A.bvh_depth * R1_BLOCK * sizeof(TS) / 4 : 0; // (bvh_depth x 256 entries: a multiple of 16 bytes either way)
+    const size_t trav_words = VARIANT == R1_V_TREE ? (size_t)A.bvh_depth * R1_BLOCK * sizeof(TS) / 4 : 0; // (bvh_depth x 256 entries: a multiple of 16 bytes either way)
     // R1_VARIANT_GRID: the fallback's traversal stack (32-bit entries: the tree walk of bvh_advance from the table in global memory), then
     // (small scenes) the workgroup's copy of the grid's 16-bit cell table and ids
-    const size_t gtrav_words = VARIANT == 7 ? (size_t)A.bvh_depth * R1_BLOCK : 0;
+    const size_t gtrav_words = VARIANT == R1_V_GRID ? (size_t)A.bvh_depth * R1_BLOCK : 0;
     const uint16_t *ltab = (const uint16_t *)(s_trav + gtrav_words);
-    if (VARIANT == 7 && !BIG)
+    if (VARIANT == R1_V_GRID && !BIG)
     {
         float4 *dst = (float4 *)(s_trav + gtrav_words);
         const R1GridCArgs *ga = (const R1GridCArgs *)(uintptr_t)A.grid;
@@ -1875,7 +1869,7 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
     const float4 *lnodes = (const float4 *)(s_trav + trav_words);
     // (big scenes: A.bvh_lds_f4 covers the first nodes of the breadth-first top of the tree only)
     const uint32_t top = LN ? 0u : A.bvh_lds_f4 >> 2;
-    if (VARIANT == 4 && A.bvh_lds_f4)
+    if (VARIANT == R1_V_TREE && A.bvh_lds_f4)
     {
         float4 *dst = (float4 *)(s_trav + trav_words);
         for (uint32_t i = (uint32_t)tid; i < A.bvh_lds_f4; i += R1_BLOCK)
@@ -1907,7 +1901,7 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
     trav_start(tv);
     tv.cur = R1_BVH_DONE;
     unsigned long long lane_rays = 0;
-    // Frames in flight (MODE 0; tree kernels and the small-scene exhaustive sweep, 18.25 -> 19.0 Grays/s at 96 VGPRs, its
+    // Frames in flight (R1_MODE_TP; tree kernels and the small-scene exhaustive sweep, 18.25 -> 19.0 Grays/s at 96 VGPRs, its
     // limit for five waves per SIMD): every lane keeps ONE prepared sample (its primary ray and stream states,
     // 11 registers) next to the path it is tracing.  A lane whose path ends takes its own spare, and spares are generated
     // for all lanes that lack one at once — when a lane has died without one, or R1_SPARE_MIN lanes lack one — instead of
@@ -1921,7 +1915,7 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
 #ifndef R1_SPARE_MIN
 #define R1_SPARE_MIN 40u
 #endif
-    constexpr bool SPARE = R1_SPARE && !BIG && (VARIANT == 4 || VARIANT == 2 || VARIANT == 7) && (MODE == 0 || MODE == 3 || MODE == 5); // (big scenes: the registers buy an eighth wave instead)
+    constexpr bool SPARE = R1_SPARE && !BIG && (VARIANT == R1_V_TREE || VARIANT == R1_V_SWEEP || VARIANT == R1_V_GRID) && r1_mode_is_tp_family(MODE); // (big scenes: the registers buy an eighth wave instead)
     Path spare = p;
     bool has_spare = false;
 
@@ -1957,7 +1951,7 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
             // the next sample of the pixel in hand: no queue, no index arithmetic
             start_ray(A, A.cam, p, (int)(px.xy & 0xFFFFu), (int)(px.xy >> 16), px.s, A.seed);
             alive = true;
-            if (VARIANT == 4)
+            if (VARIANT == R1_V_TREE)
                 trav_start(tv);
         }
         if (SPARE && !alive && has_spare)
@@ -2095,7 +2089,7 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
                 }
                 else
                     alive = start_sample<BATCH, PASS, CPATH, LISTED>(FA, p, q_next + rank); // false: void slot, ask again
-                if (VARIANT == 4 && alive)
+                if (VARIANT == R1_V_TREE && alive)
                     trav_start(tv);
             }
             q_next += min((uint32_t)__popcll(need), avail);
@@ -2108,7 +2102,7 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
             alive = true, has_spare = false;
             trav_start(tv);
         }
-        if (BIG && VARIANT == 2)
+        if (BIG && VARIANT == R1_V_SWEEP)
         {
             // lock-step workgroup: leave together (every wave must reach the sweep's barriers)
             if (!__syncthreads_or(alive ? 1 : 0))
@@ -2143,17 +2137,17 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
         int hit = -1;
         bool ready = alive; // lanes whose hit test is complete after this step (tree kernels: the others carry their walk over)
         const unsigned long long live_now = __ballot(alive);
-        if (LAT && !BIG && VARIANT != 1 && exhausted && (uint32_t)__popcll(live_now) <= A.coop_lanes)
+        if (LAT && !BIG && VARIANT != R1_V_REFERENCE && exhausted && (uint32_t)__popcll(live_now) <= A.coop_lanes)
         {
             cooperative_sweep(A.scene, live_now, p.o, p.d, t_hit, hit, lane); // the frame's tail: few paths left in this wave
             tv.cur = R1_BVH_DONE;                                            // (a walk in progress is simply dropped: this sweep is complete by itself)
         }
-        else if (VARIANT == 1)
+        else if (VARIANT == R1_V_REFERENCE)
         {
             if (alive)
                 sweep_reference(A.scene, p.o, p.d, t_hit, hit);
         }
-        else if (VARIANT == 4)
+        else if (VARIANT == R1_V_TREE)
         {
             // while-while with carry-over
 #if R1_FRESH
@@ -2166,7 +2160,7 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
             if (tv.best_id != 0xFFFFFFFFu)
                 t_hit = tv.best, hit = (int)tv.best_id;
         }
-        else if (VARIANT == 7)
+        else if (VARIANT == R1_V_GRID)
         {
 #if R1_FRESH
             R1_FRESH_ARGS(HA) // (table pointers and the grid's geometry: fetched for the walk, free again after it)
@@ -2242,7 +2236,7 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
                     lane_rays += path_rays(p); // (LAND: the waves that sum the tiles add up the records' counts)
                 alive = false, fin = true;
             }
-            else if (VARIANT == 4)
+            else if (VARIANT == R1_V_TREE)
                 trav_start(tv); // the scattered ray starts its walk at the root
         }
         if (LAND && fin)
@@ -2260,7 +2254,7 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
         for (int off = 32; off > 0; off >>= 1)
             c9 += __shfl_down(c9, off, 64);
         wstat[9] = c9;
-        if (VARIANT == 4 || VARIANT == 7)
+        if (VARIANT == R1_V_TREE || VARIANT == R1_V_GRID)
         {
             // per-lane counters of sweep_bvh / grid_trace
             const int slots[5] = {2, 3, 5, 16, 17};
@@ -2275,7 +2269,7 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
         if (lane == 0 && wave_log)
         {
             unsigned long long *rec = wave_log + 4 * (size_t)(blockIdx.x * (R1_BLOCK / 64) + (threadIdx.x >> 6));
-            if (VARIANT == 7) // (the log lives in global memory: say so, no generic stores)
+            if (VARIANT == R1_V_GRID) // (the log lives in global memory: say so, no generic stores)
             {
                 typedef unsigned long long __attribute__((address_space(1))) gu64;
                 gu64 *grec = (gu64 *)(uintptr_t)rec;
@@ -2292,7 +2286,7 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
             atomicMax(&A.stats[11], ~wstat[8]);                     // ~shortest wave
             atomicMax(&A.stats[12], (unsigned long long)__builtin_readcyclecounter());  // last wave end (this XCD's counter)
             atomicMax(&A.stats[13], ~wstat[14]);                    // ~first wave start
-            if (VARIANT == 4 || VARIANT == 7)
+            if (VARIANT == R1_V_TREE || VARIANT == R1_V_GRID)
             {
                 atomicAdd(&A.stats[14], wstat[16]);                 // tree: leaf trips summed over lanes (grid: fallback lanes)
                 atomicAdd(&A.stats[15], wstat[17]);                 // tree: root steps (bvh_advance) summed over lanes
@@ -2301,7 +2295,7 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
     }
 
     if (LAND)
-        land_exit<(BIG && VARIANT == 4) ? 6 : R1_LAND_LOADS>(A, row, lane); // (the big-scene tree kernels are built for 64 registers)
+        land_exit<(BIG && VARIANT == R1_V_TREE) ? 6 : R1_LAND_LOADS>(A, row, lane); // (the big-scene tree kernels are built for 64 registers)
 #undef row
     // ray count: wave reduction, one atomic per wave (rayweek1.cpp:809-813)
     if (!LAND)
@@ -2321,31 +2315,31 @@ __global__ void __launch_bounds__(R1_BLOCK, (TraceWaves<VARIANT, STATS, BIG, MOD
 
 // R1_VARIANT_GRID: the same body under a name of its own (VARIANT 7)
 template <bool STATS, bool BIG, int MODE>
-__global__ void __launch_bounds__(R1_BLOCK, (TraceWaves<7, STATS, BIG, MODE>::value)) r1_grid_kernel(const R1TraceArgs A)
+__global__ void __launch_bounds__(R1_BLOCK, (TraceWaves<R1_V_GRID, STATS, BIG, MODE>::value)) r1_grid_kernel(const R1TraceArgs A)
 {
-    r1_trace_body<7, STATS, BIG, MODE>(A);
+    r1_trace_body<R1_V_GRID, STATS, BIG, MODE>(A);
 }
 
-// Progressive passes (MODE 4): the same body under a name of its own, for the tree (4), the exhaustive sweeps (2, 1) and the grid (7)
+// Progressive passes (R1_MODE_PASS): the same body under a name of its own, for the tree, the exhaustive sweeps (grouped and reference form) and the grid
 template <int VARIANT, bool BIG>
-__global__ void __launch_bounds__(R1_BLOCK, (TraceWaves<VARIANT, false, BIG, 4>::value)) r1_pass_kernel(const R1TraceArgs A)
+__global__ void __launch_bounds__(R1_BLOCK, (TraceWaves<VARIANT, false, BIG, R1_MODE_PASS>::value)) r1_pass_kernel(const R1TraceArgs A)
 {
-    r1_trace_body<VARIANT, false, BIG, 4>(A);
+    r1_trace_body<VARIANT, false, BIG, R1_MODE_PASS>(A);
 }
 
-// Adaptive sampling (MODE 6): the same body under a name of its own, for the tree (4), the grouped sweep (2) and the grid (7); built for the
+// Adaptive sampling (R1_MODE_LISTED): the same body under a name of its own, for the tree, the grouped sweep and the grid; built for the
 // waves of its r1_pass_kernel sibling
 template <int VARIANT, bool BIG>
-__global__ void __launch_bounds__(R1_BLOCK, (TraceWaves<VARIANT, false, BIG, 4>::value)) r1_adaptive_kernel(const R1TraceArgs A)
+__global__ void __launch_bounds__(R1_BLOCK, (TraceWaves<VARIANT, false, BIG, R1_MODE_PASS>::value)) r1_adaptive_kernel(const R1TraceArgs A)
 {
-    r1_trace_body<VARIANT, false, BIG, 6>(A);
+    r1_trace_body<VARIANT, false, BIG, R1_MODE_LISTED>(A);
 }
 
-// Camera paths (MODE 5): the same body under a name of its own, for the families that have a batch build: tree (4), grouped sweep (2), grid (7)
+// Camera paths (R1_MODE_PATH): the same body under a name of its own, for the families that have a batch build: tree, grouped sweep, grid
 template <int VARIANT, bool BIG>
-__global__ void __launch_bounds__(R1_BLOCK, (TraceWaves<VARIANT, false, BIG, 5>::value)) r1_path_kernel(const R1TraceArgs A)
+__global__ void __launch_bounds__(R1_BLOCK, (TraceWaves<VARIANT, false, BIG, R1_MODE_PATH>::value)) r1_path_kernel(const R1TraceArgs A)
 {
-    r1_trace_body<VARIANT, false, BIG, 5>(A);
+    r1_trace_body<VARIANT, false, BIG, R1_MODE_PATH>(A);
 }
 
 #endif // R1_TRACE_HPP

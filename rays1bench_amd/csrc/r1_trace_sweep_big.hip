@@ -1,5 +1,4 @@
-// r1_trace_sweep_big.hip — the trace kernel's instantiations for one family (r1_trace_tu.inc says which); kernel and device functions: r1_trace.hpp
+// r1_trace_sweep_big.hip — the trace kernel's instantiations for one family (r1_builds.h lists them); kernel and device functions: r1_trace.hpp
 #define R1_TU_NAME sweep_big
-#define R1_TU_BIG true
-#define R1_TU_TREE 0
+#define R1_TU_BUILDS R1_BUILDS_SWEEP_BIG
 #include "r1_trace_tu.inc"

@@ -56,6 +56,8 @@ def kernels_of(co):
             if len(t) < 1:
                 continue
             op = t[0]
+            if op == "...":  # objdump's elision of the zero padding behind the last function of a code object: not an instruction
+                continue
             meta[cur]["insts"] += 1
             if op.startswith("flat_load"):
                 meta[cur]["flat_load"] += 1
