@@ -738,6 +738,34 @@ def grid_describe(cscene):
     return d, start, ids[:info.registrations], outl[:info.outliers]
 
 
+class SweepInfo(C.Structure):
+    _fields_ = [("spheres", C.c_int32), ("groups", C.c_int32), ("multi", C.c_int32), ("n_sweep", C.c_int32), ("slots", C.c_int32),
+                ("group_max", C.c_int32)]
+
+
+def sweep_describe(cscene):
+    """Host-side build of the sweep's tables (R1_VARIANT_PREFILTER) as r1_set_scene builds them; r1_sweep_describe is internal
+    (csrc/r1_internal.h, not include/rays1.h), so its prototype is set here.  Returns a dict: the SweepInfo fields; `groups`
+    float64[n, 8] = per group {centre x, y, z as stored in fp32, stored Kp, covering radius R around that centre, the radius the
+    R1_GROUP_RATIO rule saw, c_max2, n}; the raw tables `sweep` float32[slots / 2, 8] (pair layout), `members` uint32[slots, group_max]
+    (active indices, 0xFFFFFFFF = none), `exact_g` float32[slots, group_max, 4]; `active` uint32[spheres]: active -> scene index."""
+    f = lib().r1_sweep_describe
+    u32p, f64p, sz = C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.c_size_t
+    f.restype, f.argtypes = C.c_int, [C.POINTER(CScene), C.POINTER(SweepInfo), f64p, sz, _f32p, sz, u32p, sz, _f32p, sz, u32p, sz]
+    info = SweepInfo()
+    _check(f(C.byref(cscene), C.byref(info), None, 0, None, 0, None, 0, None, 0, None, 0))
+    groups = np.zeros((max(info.groups, 1), 8), np.float64)
+    sweep = np.zeros((info.slots // 2, 8), np.float32)
+    members = np.zeros((info.slots, info.group_max), np.uint32)
+    exact_g = np.zeros((info.slots, info.group_max, 4), np.float32)
+    active = np.zeros(max(info.spheres, 1), np.uint32)
+    _check(f(C.byref(cscene), C.byref(info), groups.ctypes.data_as(f64p), groups.size, sweep.ctypes.data_as(_f32p), sweep.size,
+             members.ctypes.data_as(u32p), members.size, exact_g.ctypes.data_as(_f32p), exact_g.size, active.ctypes.data_as(u32p), active.size))
+    d = {k: int(getattr(info, k)) for k, _ in SweepInfo._fields_}
+    d.update(group_rows=groups[:info.groups], sweep=sweep, members=members, exact_g=exact_g, active=active[:info.spheres])
+    return d
+
+
 def grid_visit(cscene, o, d, cap=1 << 16):
     """One ray through the grid on the host, in the kernel's arithmetic: (presented scene indices in order, hit index or -1, hit t,
     fallback flag)."""

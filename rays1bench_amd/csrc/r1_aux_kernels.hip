@@ -1,5 +1,5 @@
 // r1_aux_kernels.hip — the kernels around the trace kernel (wavefront variant, resolve, progressive accumulate, batch counts, assemble) and the launch
-// dispatch called from r1_capi.cpp.  The trace kernel template and its device functions: r1_trace.hpp.
+// dispatch called from r1_frame.cpp and r1_render.cpp.  The trace kernel template and its device functions: r1_trace.hpp.
 #include "r1_trace.hpp"
 #include "r1_internal.h"
 
@@ -448,7 +448,7 @@ __global__ void r1_put_cameras_kernel(float4 *dst, const R1CameraRows rows, uint
         dst[threadIdx.x] = rows.row[threadIdx.x];
 }
 
-// ---- launchers (called from r1_capi.cpp) -----------------------------------------------------
+// ---- launchers (called from r1_frame.cpp, r1_render.cpp) -----------------------------------------------------
 
 extern "C" hipError_t r1_launch_land_arm(uint32_t *tile_cnt, unsigned long long *frame_rays, uint32_t *frame_left, uint32_t n_frames, uint32_t n_local_tiles,
                                          int width, int height, int spp, int tile_w, int tile_h, int tiles_x, int shard, int num_shards, hipStream_t stream)
@@ -494,7 +494,7 @@ extern "C" hipError_t r1_launch_put_cameras(void *dst, const float *cameras20, i
 // The trace kernel's instantiations live in six translation units (tree / exhaustive sweep / uniform grid x small / big scenes); each exports one
 // launch and one occupancy function for its family (r1_internal.h), which finds the build in the family's list.
 
-// b: the build r1_pick chose (r1_capi.cpp choose_kernel); which builds exist is the lists' business, what is checked here is that the arguments are
+// b: the build r1_pick chose (r1_frame.cpp choose_kernel); which builds exist is the lists' business, what is checked here is that the arguments are
 // those the build reads.  grid_lds: the grid kernels' 16-bit tables in LDS (small scenes; R1GridArgs::lds_bytes, which lives in device memory)
 extern "C" hipError_t r1_launch_trace(const R1TraceArgs *args, R1Build b, int blocks, size_t grid_lds, hipStream_t stream)
 {

@@ -7,7 +7,7 @@
 #error "r1_builds.h is included through r1_device.h (r1_build_lands reads R1_LAND)"
 #endif
 
-// Internal variant numbers = the public enum of include/rays1.h (r1_capi.cpp resolve_variant asserts it), DEFAULT resolved.
+// Internal variant numbers = the public enum of include/rays1.h (r1_frame.cpp resolve_variant asserts it), DEFAULT resolved.
 constexpr int R1_V_REFERENCE = 1;   // exhaustive sweep, the reference's form
 constexpr int R1_V_SWEEP = 2;       // grouped exhaustive sweep (R1_VARIANT_PREFILTER)
 constexpr int R1_V_SWEEP_STATS = 3; // ... its diagnostic build
@@ -52,7 +52,7 @@ struct R1Build
 };
 
 // What each translation unit instantiates (r1_trace_tu.inc walks its list to launch and to ask for occupancy), X(variant, stats, big, mode).
-// The grid's PIXEL mode exists for big scenes only (the small-scene build would spill; r1_capi.cpp big_scene sends small scenes there), the
+// The grid's PIXEL mode exists for big scenes only (the small-scene build would spill; r1_frame.cpp big_scene sends small scenes there), the
 // latency mode for small scenes only, the diagnostic builds in the mode a synchronous frame runs in, the reference form as TP and PASS.
 #define R1_BUILDS_TREE_SMALL(X)                 \
     X(R1_V_TREE, false, false, R1_MODE_TP)      \

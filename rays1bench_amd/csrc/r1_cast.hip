@@ -261,7 +261,7 @@ __global__ void __launch_bounds__(R1_BLOCK) r1_cast_plain_kernel(const R1CastArg
 }
 #endif
 
-// ---- launchers (called from r1_capi.cpp) --------------------------------------------------------------------------------------------------
+// ---- launchers (called from r1_queries.cpp) --------------------------------------------------------------------------------------------------
 // variant: R1_V_TREE, R1_V_GRID or R1_V_REFERENCE — the structure the rays walk; plain: the tuning library's plain tree form
 #define R1_CAST_DISPATCH(X)                                                                                                            \
     if (variant == R1_V_REFERENCE)                                                                                                     \

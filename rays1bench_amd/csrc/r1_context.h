@@ -1,0 +1,223 @@
+// r1_context.h — what the files that implement the C-ABI on the HIP runtime share: the context, its device buffers, and the steps that
+// one of them defines and another calls.  Private to r1_capi.cpp (context, errors, timing), r1_scene.cpp (scene upload, moving spheres),
+// r1_frame.cpp (one frame, step by step), r1_render.cpp (the render entry points) and r1_queries.cpp (ray queries); C-linkage functions
+// shared between files stay in r1_internal.h.
+#ifndef R1_CONTEXT_H
+#define R1_CONTEXT_H
+
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include <vector>
+
+#include "../../include/rays1.h"
+#include "r1_device.h"
+#include "r1_grid.h"
+#include "r1_bvh.h" // r1_bvh.cpp: the built tree, a refit's topology tables
+#include "r1_internal.h"
+
+#pragma GCC visibility push(hidden)
+
+#define R1_HIP(call)                                                                                                   \
+    do                                                                                                                 \
+    {                                                                                                                  \
+        hipError_t e_ = (call);                                                                                        \
+        if (e_ != hipSuccess)                                                                                          \
+        {                                                                                                              \
+            r1_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__);                   \
+            return e_ == hipErrorOutOfMemory ? R1_ENOMEM : R1_EHIP;                                                    \
+        }                                                                                                              \
+    } while (0)
+
+// A device allocation that only grows (ensure) and is freed with its owner: a context's buffers go when the context is deleted, on the
+// device that is current then.
+struct DevBuf
+{
+    void *p = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf()
+    {
+        if (p)
+            (void)hipFree(p);
+    }
+};
+
+inline int ensure(DevBuf &b, size_t bytes)
+{
+    if (bytes <= b.cap && b.p)
+        return R1_OK;
+    if (b.p)
+    {
+        R1_HIP(hipFree(b.p));
+        b.p = nullptr;
+        b.cap = 0;
+    }
+    size_t want = bytes < 256 ? 256 : bytes;
+    R1_HIP(hipMalloc(&b.p, want));
+    b.cap = want;
+    return R1_OK;
+}
+
+struct r1_context
+{
+    int device = 0;
+    int cus = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
+    hipEvent_t last0 = nullptr, last1 = nullptr, last2 = nullptr; // the events the last enqueued frame recorded (own set or ring slot)
+    bool timing_valid = false;
+    // optional per-frame event ring (r1_timing_begin/_end): 3 events per frame
+    std::vector<hipEvent_t> ring;
+    int ring_frames = 0, ring_used = 0;
+    bool ring_on = false;
+
+    // scene
+    DevBuf sweep, exact, exact_g, shade, mat, members;
+    DevBuf bvh_nodes, bvh_prims, bvh_ids; // R1_VARIANT_BVH (r1_bvh.cpp)
+    // R1_VARIANT_GRID (r1_grid.cpp): built on the first render that asks for it after r1_set_scene (ensure_grid)
+    DevBuf grid_tab, grid_out, grid_dev;  // cell table + ids, outliers, the R1GridArgs the kernels read
+    DevBuf grid_tab32, grid_dev32;        // the same in the big-scene kernel's 32-bit form (small scenes: for PIXEL mode, see big_scene)
+    bool grid_valid = false;
+    bool grid_small = false;  // 16-bit tables that the small-scene kernel keeps in LDS
+    R1GridArgs grid_args;     // (pointers into grid_tab / grid_out; a copy of it in grid_dev)
+    DevBuf wf_paths, wf_hits, wf_queue, wf_counts; // R1_VARIANT_WAVEFRONT workspace
+    DevBuf wave_log;                               // STATS builds: per-wave {start, queue empty, end, iterations}
+    unsigned long long wave_log_ptr = 0;
+    uint32_t wave_log_waves = 0;
+    uint32_t n_bvh_nodes = 0, n_bvh_leaves = 0;
+    int bvh_depth = 0;
+    float bvh_centre[3] = {0, 0, 0};
+    int bvh_pad_local = 0;
+    int bvh_root_leaf = 0;
+    float bvh_flat_m = 0.0f, bvh_flat_e = -1.0f; // the tree's flat y slab (r1_bvh.cpp), e < 0: none
+    uint32_t n_active = 0, n_sweep = 0, n_padded_scene = 0, n_groups = 0, n_multi = 0;
+    std::vector<uint32_t> active_to_scene;
+    R1DeviceCamera cam;
+    bool have_scene = false;
+    // what the device tables were built from: r1_set_scene with the same arrays again (the drop-in's benchmark()
+    // uploads its scene on every run, rayweek1.cpp:969-984) keeps the tables and the tree
+    std::vector<float> src_f32[9];
+    std::vector<uint8_t> src_mat;
+    r1_camera src_cam;
+
+    // per-frame workspace
+    DevBuf counters, samples, image;
+    // frame batches: the batch's numbers live in one of eight device slots (counter tail + 64 + 32 i), written by a one-thread launch whose
+    // values travel in its kernel arguments (an asynchronous copy from a host member could be overtaken by the next call)
+    R1BatchArgs batch_args_last = {0, 0, {0, 0, 0}, 0};
+    hipStream_t batch_args_stream = nullptr;
+    int batch_args_slot = -1;
+    // camera paths: the launch's table of cameras (R1PathArgs::cameras), two halves taken in turn so that a launch still reading the
+    // previous table is not disturbed; written in stream order by launches whose values travel in their kernel arguments
+    DevBuf path_cams;
+    int path_cams_half = 0;
+    // R1_LAND (tiles resolved inside the trace kernel): per-context state
+    bool land_prev = false;      // the last launch through this context was a LAND launch
+    int land_parity = 0;         // the set of queue heads that launch used
+    uint32_t land_gen = 0;       // launch generation: the tag of its sample records (1 .. 2^24 - 1)
+    bool land_armed = false;     // the countdowns / accumulators behind the counter block hold the values of land_key
+    r1_params land_key;
+    int land_frames = 0;
+    DevBuf batch_rays;  // frame batches: per-frame ray-count accumulators of the resolve launch + its finished-workgroup counter
+    int tile_frames = 0; // frames per launch the tile arithmetic below was made for
+    bool counters_clean = false; // the last frame's resolve launch zeroed the counter block: the next frame needs no memset
+    r1_params tile_key;
+    bool tile_key_valid = false;
+    uint32_t n_local_tiles = 0, total_samples = 0, full = 0;
+
+    // one page-locked, device-visible word: the synchronous entry points let the frame's last launch store the ray count
+    // straight into host memory (8 bytes over PCIe at the end of r1_resolve_kernel) instead of enqueueing a second copy
+    unsigned long long *host_word = nullptr, *host_word_dev = nullptr;
+    int default_variant = R1_V_TREE;    // what R1_VARIANT_DEFAULT resolves to for the scene in the context (r1_set_scene): synchronous frames
+    int default_variant_tp = R1_V_TREE; // ... and frames in flight (the throughput kernels: measured apart, the two kernel families do not rank alike)
+    int occupancy[8 * 2 * 2 * R1_MODES] = {0}; // blocks per CU of the trace kernel's builds, [occupancy_slot(build)]
+    bool pixel_mode = false; // r1_set_pixel_mode
+    DevBuf gstack;
+    DevBuf land_spill; // R1_LAND: [waves of the grid][tiles of the launch] every wave's list of the tiles it took chunks from
+    // progressive passes (r1_render_pass): the frame being accumulated
+    DevBuf accum;              // [local tile][pixel of the padded tile] fp32 {r, g, b, 0}
+    bool pass_valid = false;   // accum holds samples [0, pass_samples) of pass_key's frame (false after r1_set_scene or a failed pass)
+    r1_params pass_key;        // the params that started it (spp: that pass's)
+    int32_t pass_samples = 0;
+    uint64_t pass_rays = 0;    // color() calls of those samples
+    // adaptive sampling (r1_render_adaptive): `accum` is its `all` accumulator, indexed by tile of the frame as accum_even is
+    DevBuf accum_even;         // [tile][pixel of the padded tile] the sums over the samples of even global index
+    DevBuf adapt_list;         // two tile lists of a frame's tiles each (this pass's, the next one's), then the next one's length
+    DevBuf adapt_report;       // [tile] R1TileReport
+    // ray queries (r1_cast_rays*): nothing here is read or written by a render
+    DevBuf active_dev;         // active_to_scene on the device, uploaded once per r1_set_scene
+    DevBuf cast_cursors;       // R1_CAST_CURSORS ray cursors, 128 bytes apart, taken in turn
+    uint32_t cast_cursor_next = 0;
+    DevBuf cast_ws;            // r1_cast_rays: one chunk's rays and results (R1_CAST_CHUNK x 64 bytes)
+    int cast_occupancy[8] = {0}; // blocks per CU of the cast kernels, [structure slot * 2 + big]
+    // moving spheres (r1_update_centers*): the refit's tables — topology, uploaded once per r1_set_scene — and its scratch
+    DevBuf refit_tab;          // uint32: scene -> active index, then R1RefitTopo's slot, leaf_ref, child_box, by_height
+    DevBuf refit_radii;        // [active][2] fp64 {bound radius, test radius}
+    DevBuf refit_box;          // 256 bytes (word 0: the largest A), then [nodes + leaves] R1Box
+    R1RefitArgs refit;         // pointers into the tables above and the scene's
+    std::vector<uint32_t> refit_height_off; // R1RefitTopo::height_off
+    std::vector<uint32_t> scene_to_active;  // 0xFFFFFFFF: not active
+    bool moved = false;        // an update since the last r1_set_scene: the sphere groups and the grid are stale, src_f32 may be
+    float *stage = nullptr, *stage_dev = nullptr; // host form: page-locked staging of the centres, read by the move kernel
+    size_t stage_cap = 0;      // floats
+    hipEvent_t stage_ev = nullptr; // recorded behind the move kernel that reads `stage`
+    bool stage_busy = false;
+
+    r1_launch_info info;
+};
+
+// Frame batch of the throughput entry points: n_frames frames in one launch (r1_device.h R1TraceArgs::n_frames); frame f is
+// written to d_out + f * out_stride and its uint64 ray count to d_out + f * out_stride + rays_offset.
+struct Batch
+{
+    int n_frames = 1;
+    uint32_t seed_stride = 0;
+    size_t out_stride = 0, rays_offset = 0;
+    const r1_camera *cameras = nullptr; // a camera path: [n_frames], host memory; null: every frame through the context's camera
+};
+
+// Where the caller finally wants the frame, if the device can write there (page-locked host memory): launches that resolve their own
+// tiles (R1_LAND) store the pixels and the count there directly and set `used`; the entry point then enqueues no copy.
+struct Landing
+{
+    void *out = nullptr;  // device address of the caller's pixels (row-major image, or the frame records of a batch)
+    void *rays = nullptr; // ... of its ray count (single frames)
+    bool used = false;
+};
+
+// A progressive pass (r1_render_pass): samples [first_sample, first_sample + spp) traced by the R1_MODE_PASS kernels, then r1_accum_kernel instead of
+// the resolve launch.  d_out of enqueue_frame receives the preview unless `image` is false.
+// A pass of r1_render_adaptive has a tile list: the launch's tiles are list[0, n_listed) of the frame's, traced by the R1_MODE_LISTED kernels and summed
+// and tested by r1_adapt_accum_kernel (accumulators and reports: the context's, indexed by tile of the frame).
+struct Pass
+{
+    int32_t first_sample = 0;
+    bool image = true;
+    const uint32_t *list = nullptr; // device memory
+    uint32_t n_listed = 0;
+    const r1_adaptive *rule = nullptr;
+};
+
+// ---- the steps that cross a file boundary ------------------------------------------------------------------------------------------------
+
+// r1_capi.cpp: a resolver of an earlier launch gave up waiting (the error of r1_sync and of the synchronous render)
+int land_check(r1_context *c);
+
+// r1_scene.cpp
+R1DeviceCamera device_camera(const r1_camera &cam); // what the kernels read of a camera
+int ensure_grid(r1_context *c);                     // R1_VARIANT_GRID: the grid of the context's scene, built and uploaded once per scene
+
+// r1_frame.cpp
+bool big_scene(const r1_context *c, bool tree, bool grid, bool grid_pixel);
+void fill_scene(const r1_context *c, R1DeviceScene &s);
+void fill_walk(const r1_context *c, bool tree_lds, bool big, uint32_t top_nodes, R1TraceArgs &a);
+int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int block_layout, void *d_rays, hipStream_t st, bool throughput_mode,
+                  const Batch *batch = nullptr, Landing *landing = nullptr, const Pass *pass = nullptr);
+
+#pragma GCC visibility pop
+
+#endif

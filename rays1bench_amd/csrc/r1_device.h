@@ -1,4 +1,4 @@
-// r1_device.h — device-side data layout shared by r1_trace.hpp and r1_capi.cpp.
+// r1_device.h — device-side data layout shared by r1_trace.hpp and the host files behind r1_context.h.
 #ifndef R1_DEVICE_H
 #define R1_DEVICE_H
 
@@ -25,12 +25,12 @@
 #define R1_NODES_LDS_MAX 256  // tree kernel: scenes whose tree has at most this many nodes (16 KB) run the small-scene kernels, which keep
                               // the node table in LDS; bigger trees run the big-scene kernels (node table through the vector L1)
 #define R1_CHUNK 256        // most samples a wave takes from the global queue per atomic (small frames) ...
-#define R1_CHUNK_BIG 1024   // ... growing with a wave's share of the frame up to this (r1_capi.cpp size_grid)
+#define R1_CHUNK_BIG 1024   // ... growing with a wave's share of the frame up to this (r1_frame.cpp size_grid)
 #define R1_CHUNK_MIN 32      // fewest (end of the queue: guided self-scheduling)
 #define R1_GROUP_MAX 4         // spheres per group (level 1 of the sweep tests group bounds)
 #define R1_GROUP_MIN_SPHERES 128 // scenes with fewer active spheres are swept ungrouped
 #define R1_GROUP_RATIO 3.5     // a group's bounding radius stays within this factor of its smallest member radius
-#define R1_SAMPLES_PER_LANE 125    // throughput mode grid sizing: samples each lane should get (r1_capi.cpp size_grid): 1200x800x10 -> 300
+#define R1_SAMPLES_PER_LANE 125    // throughput mode grid sizing: samples each lane should get (r1_frame.cpp size_grid): 1200x800x10 -> 300
                                    // workgroups per frame.  Re-tuned after DESIGN §4.13 (a cheaper refill shifts the balance towards fewer,
                                    // longer-lived workgroups; tools/spl_sweep2.sh, three alternating rounds): 100 / 115 / 125 / 135 / 150 samples
                                    // -> 36.46 / 36.75 / 36.90 / 37.00 / 37.3 Grays/s over 300 steps and 32.7 / 33.3 / 33.4 / 32.7 / 32.0 over the
@@ -97,7 +97,7 @@ static inline double r1_knob_f(const char *, double dflt) { return dflt; }
 #endif
 
 // Division of n < 2^31 by a launch constant: pow2 ? n >> shift : mulhi(n, mul) >> shift, with
-// mul = ceil(2^(32+shift) / d), shift = floor(log2 d) (exact for every n < 2^31; r1_capi.cpp).
+// mul = ceil(2^(32+shift) / d), shift = floor(log2 d) (exact for every n < 2^31; r1_frame.cpp make_div).
 struct R1FastDiv
 {
     uint32_t mul, shift, pow2;

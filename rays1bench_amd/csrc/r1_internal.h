@@ -13,6 +13,15 @@
 
 struct R1RefitArgs; // r1_bvh_fill.h
 
+// what r1_sweep_describe says of the sweep's tables besides the arrays
+struct r1_sweep_info
+{
+    int32_t spheres;   // active spheres
+    int32_t groups, multi, n_sweep; // R1Sweep's n_groups, n_multi, n_sweep
+    int32_t slots;     // groups the tables hold: n_sweep + the prefetch chunk or tile
+    int32_t group_max; // R1_GROUP_MAX
+};
+
 extern "C"
 {
 // r1_capi.cpp
@@ -20,6 +29,10 @@ void r1_set_error(const char *fmt, ...);
 void *r1_context_stream(r1_context *c); // the context's own stream (r1_multi.cpp runs its collectives on it)
 int r1_pick_build(int variant, int big, int want, int *build4); // r1_pick for tests: 1 and build4 = {variant, stats, big, mode}, or 0
 void r1_build_facts(int variant, int mode, int big, int *facts6);  // the predicates for tests: {tree, grid, stats, base variant, tp family, runs as latency}
+
+// r1_sweep.cpp: the sweep's tables for tests, as r1_set_scene builds them (buffers: caller's, with capacities in elements; NULL: not wanted)
+int r1_sweep_describe(const r1_scene *s, r1_sweep_info *info, double *groups_out, size_t groups_cap, float *sweep_out, size_t sweep_cap,
+                      uint32_t *members_out, size_t members_cap, float *exact_g_out, size_t exact_g_cap, uint32_t *active_out, size_t active_cap);
 
 // r1_host.cpp
 int r1_params_check(const r1_params *p);

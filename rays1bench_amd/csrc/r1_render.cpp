@@ -1,0 +1,630 @@
+// r1_render.cpp — the entry points that render: synchronous frames, progressive passes, adaptive sampling, frames in flight, batches and
+// camera paths, shards and their assembly.  Each checks its arguments, calls enqueue_frame (r1_frame.cpp) and brings the results home.
+
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "r1_context.h"
+
+// ---- public render entry points ---------------------------------------------------------------------
+
+// device address of page-locked host memory (r1_host_alloc, hipHostMalloc, hipHostRegister), or null for anything else
+static void *mapped_host(const void *ptr)
+{
+    if (!ptr)
+        return nullptr;
+    hipPointerAttribute_t at;
+    memset(&at, 0, sizeof(at));
+    if (hipPointerGetAttributes(&at, ptr) != hipSuccess)
+    {
+        (void)hipGetLastError(); // ordinary (pageable) memory is not an error here
+        return nullptr;
+    }
+    return at.type == hipMemoryTypeHost ? at.devicePointer : nullptr;
+}
+
+// tile t of the frame: its corner and its size inside the image (the last column and row of tiles may be cut)
+struct TileRect { int x0, y0, tw, th; };
+static TileRect tile_rect(const r1_params *p, int t)
+{
+    const int tiles_x = (p->width + p->tile_w - 1) / p->tile_w;
+    const int x0 = (t % tiles_x) * p->tile_w, y0 = (t / tiles_x) * p->tile_h;
+    return {x0, y0, p->tile_w < p->width - x0 ? p->tile_w : p->width - x0, p->tile_h < p->height - y0 ? p->tile_h : p->height - y0};
+}
+
+// The ray count of a frame the caller waits for.  direct: the frame's last launch stores it straight into the context's page-locked word
+// (8 bytes over PCIe, no second copy to enqueue and wait for); else it is copied from behind the counter block.  rays_word: what
+// enqueue_frame is given.  read_rays: after the frame and the caller's own copies are enqueued — waits for the context's stream.
+static void *rays_word(const r1_context *c, bool direct) { return direct ? (void *)c->host_word_dev : nullptr; }
+static int read_rays(r1_context *c, bool direct, uint64_t *rays)
+{
+    if (!direct) // (behind the block the frame's last launch zeroes)
+        R1_HIP(hipMemcpyAsync(rays, (char *)c->counters.p + R1_COUNTER_BYTES, 8, hipMemcpyDeviceToHost, c->stream));
+    R1_HIP(hipStreamSynchronize(c->stream));
+    if (direct)
+        *rays = *(volatile unsigned long long *)c->host_word;
+    return R1_OK;
+}
+
+static int render_host(r1_context *c, const r1_params *p, uint8_t *rgb_out, uint64_t *num_rays_out, double *device_seconds_out,
+                       float *samples_out)
+{
+    if (!c || !p || !rgb_out)
+    {
+        r1_set_error("r1_render: null argument");
+        return R1_EINVAL;
+    }
+    int rc = r1_params_check(p);
+    if (rc)
+        return rc;
+    if (samples_out && p->num_shards != 1)
+    {
+        r1_set_error("r1_render_samples needs num_shards == 1");
+        return R1_EINVAL;
+    }
+    R1_HIP(hipSetDevice(c->device));
+    const bool sharded = p->num_shards > 1;
+    const size_t img_bytes = (size_t)p->width * p->height * 3;
+    const size_t out_bytes = sharded ? r1_shard_block_bytes(p) : img_bytes;
+    if ((rc = ensure(c->image, out_bytes + 64)))
+        return rc;
+    // (the diagnostic builds count with atomics and keep a device word + copy)
+    const bool stats = r1_is_stats(p->variant);
+    const bool direct = !stats && c->host_word_dev;
+    // a page-locked pixel buffer (r1_host_alloc) receives the tiles straight from the trace kernel's resolvers: no copy either
+    Landing land_to;
+    if (direct && !sharded)
+        land_to.out = mapped_host(rgb_out), land_to.rays = c->host_word_dev;
+    if ((rc = enqueue_frame(c, p, c->image.p, sharded ? 1 : 0, rays_word(c, direct), c->stream, false, nullptr, &land_to)))
+        return rc;
+
+    uint64_t rays = 0;
+    if (!sharded)
+    {
+        if (!land_to.used)
+            R1_HIP(hipMemcpyAsync(rgb_out, c->image.p, img_bytes, hipMemcpyDeviceToHost, c->stream));
+        if ((rc = read_rays(c, direct, &rays)))
+            return rc;
+    }
+    else
+    {
+        std::vector<uint8_t> block(out_bytes);
+        R1_HIP(hipMemcpyAsync(block.data(), c->image.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
+        if ((rc = read_rays(c, direct, &rays)))
+            return rc;
+        for (uint32_t lt = 0; lt < c->n_local_tiles; ++lt)
+        {
+            const TileRect r = tile_rect(p, p->shard + (int)lt * p->num_shards);
+            for (int ly = 0; ly < r.th; ++ly)
+                memcpy(rgb_out + ((size_t)(r.y0 + ly) * p->width + r.x0) * 3,
+                       block.data() + ((size_t)lt * p->tile_h * p->tile_w + (size_t)ly * p->tile_w) * 3, (size_t)r.tw * 3);
+        }
+    }
+    if ((rc = land_check(c)))
+        return rc;
+    if (num_rays_out)
+        *num_rays_out = rays;
+    if (device_seconds_out)
+    {
+        float ms = 0;
+        R1_HIP(hipEventElapsedTime(&ms, c->last0, c->last2)); // the events THIS frame recorded (a ring slot while r1_timing_begin is on)
+        *device_seconds_out = ms * 1e-3;
+    }
+    if (samples_out)
+    {
+        // device order is [padded tile][sample][pixel in tile]; the ABI order is
+        // ((y*width + x)*spp + s)
+        std::vector<float> tmp((size_t)c->total_samples * 4);
+        R1_HIP(hipMemcpyAsync(tmp.data(), c->samples.p, tmp.size() * 4, hipMemcpyDeviceToHost, c->stream));
+        R1_HIP(hipStreamSynchronize(c->stream));
+        for (uint32_t lt = 0; lt < c->n_local_tiles; ++lt)
+        {
+            const TileRect r = tile_rect(p, (int)lt); // (num_shards == 1: local tile = tile of the frame)
+            const float *src = tmp.data() + (size_t)lt * c->full * 4;
+            const size_t tile_px = (size_t)p->tile_w * p->tile_h;
+            for (int ly = 0; ly < r.th; ++ly)
+                for (int lx = 0; lx < r.tw; ++lx)
+                    for (int sm = 0; sm < p->spp; ++sm)
+                    {
+                        float *dst = samples_out + (((size_t)(r.y0 + ly) * p->width + (r.x0 + lx)) * p->spp + sm) * 4;
+                        memcpy(dst, src + ((size_t)sm * tile_px + (size_t)(ly * p->tile_w + lx)) * 4, 16);
+                        if (c->land_prev) // the launch tagged its records' ray-count words (R1_LAND): the ABI's word is the count alone
+                        {
+                            uint32_t wv;
+                            memcpy(&wv, dst + 3, 4);
+                            wv &= 255u;
+                            memcpy(dst + 3, &wv, 4);
+                        }
+                    }
+        }
+    }
+    return R1_OK;
+}
+
+extern "C" int r1_render(r1_context *c, const r1_params *p, uint8_t *rgb_out, uint64_t *num_rays_out, double *device_seconds_out)
+{
+    return render_host(c, p, rgb_out, num_rays_out, device_seconds_out, nullptr);
+}
+
+extern "C" int r1_render_samples(r1_context *c, const r1_params *p, uint8_t *rgb_out, uint64_t *num_rays_out, float *samples_out)
+{
+    if (!samples_out)
+    {
+        r1_set_error("r1_render_samples: null samples_out");
+        return R1_EINVAL;
+    }
+    return render_host(c, p, rgb_out, num_rays_out, nullptr, samples_out);
+}
+
+// Progressive rendering: samples [first_sample, first_sample + spp) of every pixel, added in sample order to the context's fp32 accumulator.  The
+// accumulator then holds exactly the sums the resolve of a frame of first_sample + spp samples computes (a sample's streams depend on (seed,
+// pixel, sample index) only, include/rays1_seed.h), so every preview is that frame's image, bit for bit.
+static bool same_pass_frame(const r1_params &a, const r1_params &b) // every field but spp
+{
+    return a.width == b.width && a.height == b.height && a.max_bounces == b.max_bounces && a.seed == b.seed && a.tile_w == b.tile_w &&
+           a.tile_h == b.tile_h && a.shard == b.shard && a.num_shards == b.num_shards && a.variant == b.variant;
+}
+
+extern "C" int r1_render_pass(r1_context *c, const r1_params *p, int32_t first_sample, uint8_t *rgb_out, uint64_t *num_rays_out)
+{
+    if (!c || !p)
+    {
+        r1_set_error("r1_render_pass: null argument");
+        return R1_EINVAL;
+    }
+    int rc = r1_params_check(p);
+    if (rc)
+        return rc;
+    if (p->num_shards != 1)
+    {
+        r1_set_error("r1_render_pass renders whole frames (num_shards == 1)");
+        return R1_EINVAL;
+    }
+    if (r1_is_stats(p->variant) || p->variant == R1_VARIANT_WAVEFRONT)
+    {
+        r1_set_error("r1_render_pass: variant %d (a diagnostic build or the wavefront variant) has no progressive-pass build", p->variant);
+        return R1_EINVAL;
+    }
+    if (first_sample < 0 || (int64_t)first_sample + p->spp > (int64_t)INT32_MAX)
+    {
+        r1_set_error("r1_render_pass: first_sample %d + spp %d is not within [0, INT32_MAX]", first_sample, p->spp);
+        return R1_EINVAL;
+    }
+    if (first_sample > 0 && !(c->pass_valid && c->pass_samples == first_sample && same_pass_frame(c->pass_key, *p)))
+    {
+        if (!c->pass_valid)
+            r1_set_error("r1_render_pass: no accumulation to continue (start one with first_sample 0)");
+        else if (c->pass_samples != first_sample)
+            r1_set_error("r1_render_pass: first_sample %d, but %d samples are accumulated", first_sample, c->pass_samples);
+        else
+            r1_set_error("r1_render_pass: the parameters differ from those that started the accumulation (only spp may change)");
+        return R1_EINVAL;
+    }
+    if (!c->have_scene)
+    {
+        r1_set_error("no scene set (call r1_set_scene first)");
+        return R1_EINVAL;
+    }
+    int32_t tiles = 0;
+    if ((rc = r1_tile_count(p, &tiles, nullptr)))
+        return rc;
+    if ((uint64_t)p->tile_w * p->tile_h * p->spp * (uint64_t)tiles >= ((uint64_t)1 << 31))
+    {
+        r1_set_error("a pass of %dx%dx%d with %dx%d tiles exceeds 2^31 sample slots per launch", p->width, p->height, p->spp, p->tile_w, p->tile_h);
+        return R1_ELIMIT;
+    }
+    R1_HIP(hipSetDevice(c->device));
+    const size_t img_bytes = (size_t)p->width * p->height * 3;
+    if (rgb_out && (rc = ensure(c->image, img_bytes + 64)))
+        return rc;
+    // from here on a failure leaves the accumulator in an unknown state: only first_sample == 0 is accepted next
+    c->pass_valid = false;
+    const bool direct = c->host_word_dev != nullptr; // the pass's ray count straight into the page-locked word, as r1_render
+    Pass ps;
+    ps.first_sample = first_sample;
+    ps.image = rgb_out != nullptr;
+    if ((rc = enqueue_frame(c, p, c->image.p, 0, rays_word(c, direct), c->stream, false, nullptr, nullptr, &ps)))
+        return rc;
+    uint64_t rays = 0;
+    if (rgb_out)
+        R1_HIP(hipMemcpyAsync(rgb_out, c->image.p, img_bytes, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = read_rays(c, direct, &rays)))
+        return rc;
+    c->pass_rays = (first_sample == 0 ? 0u : c->pass_rays) + rays;
+    c->pass_samples = first_sample + p->spp;
+    c->pass_key = *p;
+    c->pass_valid = true;
+    if (num_rays_out)
+        *num_rays_out = c->pass_rays;
+    return R1_OK;
+}
+
+// ---- adaptive sampling --------------------------------------------------------------
+static bool adaptive_variant(int v) { return v == R1_VARIANT_DEFAULT || v == R1_VARIANT_PREFILTER || v == R1_VARIANT_BVH || v == R1_VARIANT_GRID; }
+
+// The one place the options of r1_render_adaptive are validated: the cumulative sample counts after every pass.
+extern "C" int r1_adaptive_schedule(const r1_params *p, const r1_adaptive *o, int32_t *n_out, size_t cap, size_t *count)
+{
+    if (!p || !o || (!n_out && !count))
+    {
+        r1_set_error("r1_adaptive_schedule: null argument");
+        return R1_EINVAL;
+    }
+    int rc = r1_params_check(p);
+    if (rc)
+        return rc;
+    if (p->num_shards != 1)
+    {
+        r1_set_error("adaptive sampling renders whole frames (num_shards == 1, not %d)", p->num_shards);
+        return R1_EINVAL;
+    }
+    if (!adaptive_variant(p->variant))
+    {
+        r1_set_error("adaptive sampling: variant %d (the reference form, a diagnostic build or the wavefront variant) has no listed-tile build", p->variant);
+        return R1_EINVAL;
+    }
+    if (o->min_spp < 1)
+    {
+        r1_set_error("adaptive sampling: min_spp %d is not >= 1", o->min_spp);
+        return R1_EINVAL;
+    }
+    if (o->pass_spp < 1)
+    {
+        r1_set_error("adaptive sampling: pass_spp %d is not >= 1", o->pass_spp);
+        return R1_EINVAL;
+    }
+    if (o->max_delta < -1 || o->max_delta > 255)
+    {
+        r1_set_error("adaptive sampling: max_delta %d is not within [-1, 255]", o->max_delta);
+        return R1_EINVAL;
+    }
+    if (o->mean_delta_q8 < 0 || o->mean_delta_q8 > 65280)
+    {
+        r1_set_error("adaptive sampling: mean_delta_q8 %d is not within [0, 65280]", o->mean_delta_q8);
+        return R1_EINVAL;
+    }
+    int32_t tiles = 0;
+    if ((rc = r1_tile_count(p, &tiles, nullptr)))
+        return rc;
+    const int32_t n0 = o->min_spp < p->spp ? o->min_spp : p->spp;
+    const int32_t longest = std::max(n0, std::min(o->pass_spp, p->spp - n0)); // samples of the longest pass
+    if ((uint64_t)p->tile_w * p->tile_h * (uint64_t)longest * (uint64_t)tiles >= ((uint64_t)1 << 31))
+    {
+        r1_set_error("a pass of %dx%dx%d with %dx%d tiles exceeds 2^31 sample slots per launch", p->width, p->height, longest, p->tile_w, p->tile_h);
+        return R1_ELIMIT;
+    }
+    if ((uint64_t)p->tile_w * p->tile_h > ((uint64_t)1 << 22))
+    {
+        r1_set_error("adaptive sampling: tiles of %dx%d pixels exceed 2^22 (a tile's err_sum is a 32-bit sum of byte differences)", p->tile_w, p->tile_h);
+        return R1_ELIMIT;
+    }
+    const size_t n_pass = 1 + ((size_t)(p->spp - n0) + (size_t)o->pass_spp - 1) / (size_t)o->pass_spp;
+    if (count)
+        *count = n_pass;
+    if (!n_out)
+        return R1_OK;
+    if (cap < n_pass)
+    {
+        r1_set_error("r1_adaptive_schedule: cap %zu, the schedule has %zu passes", cap, n_pass);
+        return R1_EINVAL;
+    }
+    int64_t n = n0;
+    for (size_t k = 0; k < n_pass; ++k, n += o->pass_spp)
+        n_out[k] = (int32_t)std::min<int64_t>(n, p->spp);
+    return R1_OK;
+}
+
+static_assert(sizeof(r1_tile_report) == sizeof(R1TileReport) && sizeof(r1_tile_report) == 16 && sizeof(r1_adaptive_result) == 24, "public structs without padding; the device writes r1_tile_report's layout");
+
+extern "C" int r1_render_adaptive(r1_context *c, const r1_params *p, const r1_adaptive *opt, uint8_t *rgb_out, uint64_t *num_rays_out, r1_tile_report *tiles_out,
+                                  r1_adaptive_result *result_out)
+{
+    if (!c || !p || !opt || !rgb_out)
+    {
+        r1_set_error("r1_render_adaptive: null argument");
+        return R1_EINVAL;
+    }
+    size_t n_pass = 0;
+    int rc = r1_adaptive_schedule(p, opt, nullptr, 0, &n_pass);
+    if (rc)
+        return rc;
+    std::vector<int32_t> sched(n_pass);
+    if ((rc = r1_adaptive_schedule(p, opt, sched.data(), n_pass, nullptr)))
+        return rc;
+    if (!c->have_scene)
+    {
+        r1_set_error("no scene set (call r1_set_scene first)");
+        return R1_EINVAL;
+    }
+    int32_t tiles = 0;
+    if ((rc = r1_tile_count(p, &tiles, nullptr)))
+        return rc;
+    R1_HIP(hipSetDevice(c->device));
+    const size_t img_bytes = (size_t)p->width * p->height * 3;
+    const size_t tile_px = (size_t)p->tile_w * p->tile_h;
+    if ((rc = ensure(c->image, img_bytes + 64)) || (rc = ensure(c->accum, (size_t)tiles * tile_px * 16)) || (rc = ensure(c->accum_even, (size_t)tiles * tile_px * 16)) ||
+        (rc = ensure(c->adapt_list, ((size_t)2 * tiles + 1) * 4)) || (rc = ensure(c->adapt_report, (size_t)tiles * sizeof(R1TileReport))))
+        return rc;
+    c->pass_valid = false; // (the `all` accumulator is r1_render_pass's: an accumulation of the context ends here, as at first_sample 0)
+    const bool direct = c->host_word_dev != nullptr; // ray count and list length straight into the context's page-locked words, as r1_render_pass
+    uint32_t *const lists[2] = {(uint32_t *)c->adapt_list.p, (uint32_t *)c->adapt_list.p + tiles};
+    uint32_t *const d_count = direct ? (uint32_t *)c->host_word_dev + 4 : (uint32_t *)c->adapt_list.p + 2 * (size_t)tiles;
+    R1_HIP(r1_launch_adapt_compact(nullptr, (uint32_t)tiles, (const R1TileReport *)c->adapt_report.p, 0u, lists[0], d_count, c->stream)); // every tile, in order
+    uint32_t m = (uint32_t)tiles;
+    uint64_t rays_sum = 0;
+    int32_t passes = 0;
+    for (size_t k = 0; k < n_pass && m; ++k)
+    {
+        const int32_t first = k ? sched[k - 1] : 0;
+        r1_params pp = *p;
+        pp.spp = sched[k] - first;
+        Pass ps;
+        ps.first_sample = first;
+        ps.list = lists[k & 1], ps.n_listed = m, ps.rule = opt;
+        if ((rc = enqueue_frame(c, &pp, c->image.p, 0, rays_word(c, direct), c->stream, false, nullptr, nullptr, &ps)))
+            return rc;
+        R1_HIP(r1_launch_adapt_compact(lists[k & 1], m, (const R1TileReport *)c->adapt_report.p, sched[k] == p->spp ? 1u : 0u, lists[(k & 1) ^ 1], d_count, c->stream));
+        uint64_t rays = 0;
+        uint32_t next = 0;
+        if (!direct)
+            R1_HIP(hipMemcpyAsync(&next, d_count, 4, hipMemcpyDeviceToHost, c->stream));
+        if ((rc = read_rays(c, direct, &rays)))
+            return rc;
+        if (direct)
+            next = ((volatile uint32_t *)c->host_word)[4];
+        rays_sum += rays; // (summed on the host, pass by pass, as r1_render_pass does)
+        ++passes;
+        if (next > m)
+        {
+            r1_set_error("r1_render_adaptive: a pass left %u active tiles of %u", next, m);
+            return R1_EHIP;
+        }
+        m = next;
+    }
+    std::vector<r1_tile_report> local;
+    r1_tile_report *rep = tiles_out;
+    if (!rep)
+    {
+        local.resize((size_t)tiles);
+        rep = local.data();
+    }
+    R1_HIP(hipMemcpyAsync(rep, c->adapt_report.p, (size_t)tiles * sizeof(R1TileReport), hipMemcpyDeviceToHost, c->stream));
+    R1_HIP(hipMemcpyAsync(rgb_out, c->image.p, img_bytes, hipMemcpyDeviceToHost, c->stream));
+    R1_HIP(hipStreamSynchronize(c->stream));
+    if (num_rays_out)
+        *num_rays_out = rays_sum;
+    if (result_out)
+    {
+        uint64_t samples = 0;
+        int32_t settled = 0;
+        for (int32_t t = 0; t < tiles; ++t)
+        {
+            const TileRect r = tile_rect(p, t);
+            samples += (uint64_t)rep[t].spp * (uint64_t)(r.tw * r.th);
+            settled += rep[t].settled ? 1 : 0;
+        }
+        result_out->samples = samples;
+        result_out->passes = passes, result_out->tiles = tiles, result_out->tiles_settled = settled, result_out->reserved = 0;
+    }
+    return R1_OK;
+}
+
+// Pipelined form of r1_render (frames in flight, results on the HOST): the frame is enqueued with the throughput
+// kernels on `hip_stream` (or the context's stream), followed by the copies of the row-major image and of the ray
+// count into the caller's buffers.  Nothing is waited for: the buffers are valid once the stream is idle (r1_sync for
+// the context's stream).  One frame per context at a time — a caller keeps K frames in flight with K contexts, as
+// bench.py does.  Page-locked buffers (r1_host_alloc) let the copies overlap the other frames' kernels; pageable
+// memory works but makes each copy wait for its frame.
+extern "C" int r1_render_async(r1_context *c, const r1_params *p, uint8_t *rgb_out, uint64_t *num_rays_out, void *hip_stream)
+{
+    if (!c || !p || ((rgb_out == nullptr) != (num_rays_out == nullptr)))
+    {
+        r1_set_error("r1_render_async: null argument (rgb_out and num_rays_out are given together, or both NULL)");
+        return R1_EINVAL;
+    }
+    int rc = r1_params_check(p);
+    if (rc)
+        return rc;
+    if (p->num_shards != 1)
+    {
+        r1_set_error("r1_render_async renders whole frames (num_shards == 1); shards go through r1_render_shard_device");
+        return R1_EINVAL;
+    }
+    R1_HIP(hipSetDevice(c->device));
+    const size_t img_bytes = (size_t)p->width * p->height * 3;
+    if ((rc = ensure(c->image, img_bytes + 64)))
+        return rc;
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    // page-locked buffers (r1_host_alloc) receive the tiles and the count straight from the trace kernel's resolvers: nothing to copy
+    Landing land_to;
+    if (rgb_out && ((uintptr_t)num_rays_out & 7u) == 0)
+        land_to.out = mapped_host(rgb_out), land_to.rays = mapped_host(num_rays_out);
+    if ((rc = enqueue_frame(c, p, c->image.p, 0, nullptr, st, true, nullptr, &land_to)))
+        return rc;
+    if (rgb_out && !land_to.used) // (both NULL: the frame stays in the context's device buffers — a measurement aid, bench.py's value_device_resident)
+    {
+        R1_HIP(hipMemcpyAsync(rgb_out, c->image.p, img_bytes, hipMemcpyDeviceToHost, st));
+        R1_HIP(hipMemcpyAsync(num_rays_out, (char *)c->counters.p + R1_COUNTER_BYTES, 8, hipMemcpyDeviceToHost, st));
+    }
+    return R1_OK;
+}
+
+// n_frames frames of the same scene, camera and size in ONE launch (frame f seeded params->seed + f * seed_stride): the
+// persistent waves flow from one frame into the next, so the ramp and drain of a launch are paid once per batch.
+// Whole frames (num_shards == 1): host_frames receives n_frames frame records (r1_frame_record_bytes each) with ONE copy.
+// cameras (null: the context's camera for every frame): a camera path.  `who`: the entry point, which has checked its own arguments.
+static int render_frames_async(const char *who, r1_context *c, const r1_params *p, int32_t n_frames, uint32_t seed_stride, const r1_camera *cameras,
+                               void *host_frames, void *hip_stream)
+{
+    int rc = r1_params_check(p);
+    if (rc)
+        return rc;
+    if (p->num_shards != 1)
+    {
+        r1_set_error("%s renders whole frames (num_shards == 1)%s", who, cameras ? "" : "; shards go through r1_render_shard_device_batch");
+        return R1_EINVAL;
+    }
+    R1_HIP(hipSetDevice(c->device));
+    const size_t frame = r1_frame_record_bytes(p);
+    if ((rc = ensure(c->image, frame * (size_t)n_frames)))
+        return rc;
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    Batch b;
+    b.n_frames = n_frames, b.seed_stride = seed_stride, b.out_stride = frame, b.rays_offset = frame - 8;
+    b.cameras = cameras;
+    Landing land_to;
+    if (host_frames && ((uintptr_t)host_frames & 7u) == 0)
+        land_to.out = mapped_host(host_frames);
+    if ((rc = enqueue_frame(c, p, c->image.p, 0, nullptr, st, true, &b, &land_to)))
+        return rc;
+    if (host_frames && !land_to.used) // (NULL: the frames stay in the context's device buffer — a measurement aid)
+        R1_HIP(hipMemcpyAsync(host_frames, c->image.p, frame * (size_t)n_frames, hipMemcpyDeviceToHost, st));
+    return R1_OK;
+}
+
+extern "C" int r1_render_batch_async(r1_context *c, const r1_params *p, int32_t n_frames, uint32_t seed_stride, void *host_frames, void *hip_stream)
+{
+    if (!c || !p || n_frames < 1)
+    {
+        r1_set_error("r1_render_batch_async: bad argument");
+        return R1_EINVAL;
+    }
+    return render_frames_async("r1_render_batch_async", c, p, n_frames, seed_stride, nullptr, host_frames, hip_stream);
+}
+
+// A camera path: r1_render_batch_async with cameras[f] in place of the context's camera for frame f (the R1_MODE_PATH kernels; one frame: the
+// single-frame kernel with cameras[0] by value).  The context's own camera is not touched.
+extern "C" int r1_render_path_async(r1_context *c, const r1_params *p, int32_t n_frames, uint32_t seed_stride, const r1_camera *cameras, void *host_frames,
+                                    void *hip_stream)
+{
+    if (!c || !p || !cameras || n_frames < 1)
+    {
+        r1_set_error("r1_render_path_async: bad argument (%s)", !c ? "ctx is NULL" : !p ? "params is NULL" : !cameras ? "cameras is NULL" : "n_frames < 1");
+        return R1_EINVAL;
+    }
+    return render_frames_async("r1_render_path_async", c, p, n_frames, seed_stride, cameras, host_frames, hip_stream);
+}
+
+// The same for one shard of n_frames frames: d_records receives n_frames records (r1_shard_record_bytes each: dense tile
+// block + uint64 ray count), device memory — what a rank hands to ONE all-gather per batch.
+extern "C" int r1_render_shard_device_batch(r1_context *c, const r1_params *p, int32_t n_frames, uint32_t seed_stride, void *d_records, void *hip_stream)
+{
+    if (!c || !p || !d_records || n_frames < 1 || ((uintptr_t)d_records & 7u))
+    {
+        r1_set_error("r1_render_shard_device_batch: bad argument (d_records must be 8-byte aligned)");
+        return R1_EINVAL;
+    }
+    int rc = r1_params_check(p);
+    if (rc)
+        return rc;
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    const size_t record = r1_shard_record_bytes(p);
+    Batch b;
+    b.n_frames = n_frames, b.seed_stride = seed_stride, b.out_stride = record, b.rays_offset = record - 8;
+    return enqueue_frame(c, p, d_records, 1, nullptr, st, true, &b);
+}
+
+extern "C" int r1_render_shard_device(r1_context *c, const r1_params *p, void *d_block, void *d_num_rays, void *hip_stream)
+{
+    if (!c || !p || !d_block || !d_num_rays)
+    {
+        r1_set_error("r1_render_shard_device: null argument");
+        return R1_EINVAL;
+    }
+    if ((uintptr_t)d_num_rays & 7u)
+    {
+        r1_set_error("r1_render_shard_device: d_num_rays must be 8-byte aligned (a uint64 the kernels store and add to atomically)");
+        return R1_EINVAL;
+    }
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    return enqueue_frame(c, p, d_block, 1, d_num_rays, st, true);
+}
+
+extern "C" int r1_render_shard_device_once(r1_context *c, const r1_params *p, void *d_block, void *d_num_rays, void *hip_stream)
+{
+    if (!c || !p || !d_block || !d_num_rays)
+    {
+        r1_set_error("r1_render_shard_device_once: null argument");
+        return R1_EINVAL;
+    }
+    if ((uintptr_t)d_num_rays & 7u)
+    {
+        r1_set_error("r1_render_shard_device_once: d_num_rays must be 8-byte aligned");
+        return R1_EINVAL;
+    }
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    return enqueue_frame(c, p, d_block, 1, d_num_rays, st, false);
+}
+
+static int assemble_common(r1_context *c, const r1_params *p, const void *d_blocks, size_t shard_stride_bytes, void *d_rgb, void *d_total_rays,
+                           void *hip_stream, int n_frames = 1, size_t frame_in = 0, size_t frame_out = 0)
+{
+    if (!c || !p || !d_blocks || !d_rgb)
+    {
+        r1_set_error("r1_assemble_device: null argument");
+        return R1_EINVAL;
+    }
+    int32_t total = 0, per = 0;
+    int rc = r1_tile_count(p, &total, &per);
+    if (rc)
+        return rc;
+    const size_t tight = (size_t)per * p->tile_w * p->tile_h * 3;
+    if (shard_stride_bytes == 0)
+        shard_stride_bytes = tight;
+    if (shard_stride_bytes < tight)
+    {
+        r1_set_error("r1_assemble_device: shard stride %zu smaller than a shard block (%zu bytes)", shard_stride_bytes, tight);
+        return R1_EINVAL;
+    }
+    if (d_total_rays && (((uintptr_t)d_total_rays | (uintptr_t)d_blocks | shard_stride_bytes | frame_in | frame_out) & 7u))
+    {
+        r1_set_error("r1_assemble_device_records: records and totals must be 8-byte aligned");
+        return R1_EINVAL;
+    }
+    R1_HIP(hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    const int tiles_x = (p->width + p->tile_w - 1) / p->tile_w;
+    const size_t record = r1_shard_record_bytes(p);
+    R1_HIP(r1_launch_assemble(d_blocks, d_rgb, p->width, p->height, p->tile_w, p->tile_h, tiles_x, p->num_shards, shard_stride_bytes, n_frames, frame_in,
+                              frame_out, record - 8, d_total_rays ? (long long)((char *)d_total_rays - (char *)d_rgb) : 0, d_total_rays ? 1 : 0, st));
+    return R1_OK;
+}
+
+extern "C" int r1_assemble_device_strided(r1_context *c, const r1_params *p, const void *d_blocks, size_t shard_stride_bytes, void *d_rgb,
+                                          void *hip_stream)
+{
+    return assemble_common(c, p, d_blocks, shard_stride_bytes, d_rgb, nullptr, hip_stream);
+}
+
+extern "C" int r1_assemble_device_records(r1_context *c, const r1_params *p, const void *d_records, void *d_rgb, void *d_total_rays, void *hip_stream)
+{
+    if (!d_total_rays)
+    {
+        r1_set_error("r1_assemble_device_records: null d_total_rays");
+        return R1_EINVAL;
+    }
+    return assemble_common(c, p, d_records, r1_shard_record_bytes(p), d_rgb, d_total_rays, hip_stream);
+}
+
+// Batches: d_gathered = what one all-gather of every shard's n_frames records returns, [shard][frame][record]; d_frames receives
+// n_frames frame records (r1_frame_record_bytes each: row-major image, padded to 8 bytes, + the frame's uint64 ray count).
+extern "C" int r1_assemble_device_records_batch(r1_context *c, const r1_params *p, int32_t n_frames, const void *d_gathered, void *d_frames,
+                                                void *hip_stream)
+{
+    if (n_frames < 1 || !d_frames)
+    {
+        r1_set_error("r1_assemble_device_records_batch: bad argument");
+        return R1_EINVAL;
+    }
+    const size_t record = r1_shard_record_bytes(p), frame = r1_frame_record_bytes(p);
+    if (!record)
+        return R1_EINVAL;
+    return assemble_common(c, p, d_gathered, record * (size_t)n_frames, d_frames, (char *)d_frames + frame - 8, hip_stream, n_frames, record, frame);
+}
+
+extern "C" int r1_assemble_device(r1_context *c, const r1_params *p, const void *d_blocks, void *d_rgb, void *hip_stream)
+{
+    return r1_assemble_device_strided(c, p, d_blocks, 0, d_rgb, hip_stream);
+}

@@ -1,0 +1,402 @@
+// r1_scene.cpp — what a context knows of its scene: r1_set_scene (active spheres, the sweep's tables, the box tree, the refit's tables;
+// uploads through the context's own stream), the camera alone, moving spheres, and the uniform grid built on first use.
+
+#include <math.h>
+#include <string.h>
+
+#include <cmath>
+#include <vector>
+
+#include "r1_context.h"
+#include "r1_sweep.h"
+
+// ---- R1_VARIANT_DEFAULT -------------------------------------------------------------------------------------------------------------
+// DEFAULT is the box tree for every scene: a property of the build, so what a context launches depends on its arguments only and
+// the ranks of a multi-GPU job always run the same kernel.  (Round 3 timed scenes of 9..127 spheres through both kernels when
+// they were set, because the reference's dense medium scene was 4-5 % faster through the ungrouped sweep in round 2.  Since the
+// root step of the walk the tree is ahead on every row of the crossover table, profiles/r04/tree_vs_sweep_crossover*.txt — by
+// 0-3 % for one synchronous frame of the medium scene, 7 % with frames in flight — and a probe inside r1_set_scene made the first
+// timed benchmark() call, the kernel choice of each rank and a 62 MB workspace depend on a wall-clock race: VERDICT r03 / ADVICE r03.)
+
+// what the kernels read of a camera (Camera::getRay, rayweek1.cpp:381-386, does not use w)
+R1DeviceCamera device_camera(const r1_camera &cam)
+{
+    R1DeviceCamera d;
+    memcpy(d.origin, cam.origin, 12);
+    memcpy(d.lower_left, cam.lower_left, 12);
+    memcpy(d.horizontal, cam.horizontal, 12);
+    memcpy(d.vertical, cam.vertical, 12);
+    memcpy(d.u, cam.u, 12);
+    memcpy(d.v, cam.v, 12);
+    d.lens_radius = cam.lens_radius;
+    return d;
+}
+
+extern "C" int r1_set_scene(r1_context *c, const r1_scene *s, const r1_camera *cam)
+{
+    if (!c || !s || !cam || !s->center_x || !s->center_y || !s->center_z || !s->radius_sq || !s->inv_radius || !s->mat_type ||
+        !s->albedo_r || !s->albedo_g || !s->albedo_b || !s->mat_param)
+    {
+        r1_set_error("r1_set_scene: null argument");
+        return R1_EINVAL;
+    }
+    c->pass_valid = false; // (a progressive frame does not continue across a scene upload, even of the same arrays)
+    R1_HIP(hipSetDevice(c->device));
+
+    const float *const src[9] = {s->center_x, s->center_y, s->center_z, s->radius_sq, s->inv_radius, s->albedo_r, s->albedo_g, s->albedo_b, s->mat_param};
+    // (not after r1_update_centers*: the device holds other centres than src_f32, or the groups and the grid are those of other centres)
+    if (c->have_scene && !c->moved && c->src_mat.size() == s->count && memcmp(&c->src_cam, cam, sizeof(*cam)) == 0 &&
+        (s->count == 0 || memcmp(c->src_mat.data(), s->mat_type, s->count) == 0))
+    {
+        bool same = true;
+        for (int k = 0; k < 9 && same; ++k)
+            same = s->count == 0 || memcmp(c->src_f32[k].data(), src[k], (size_t)s->count * 4) == 0;
+        if (same)
+            return R1_OK; // bit-identical scene and camera: everything on the device is current
+    }
+    c->have_scene = false;
+    c->grid_valid = false;
+
+    // active spheres: inv_radius != 0 (rayweek1.cpp:291); order preserved so that ties keep
+    // the earlier index as in the reference's in-order resolve loop
+    int rc_active = r1_active_spheres(s, c->active_to_scene);
+    if (rc_active != R1_OK)
+        return rc_active;
+    for (uint32_t i : c->active_to_scene)
+        if (s->mat_type[i] > R1_MAT_DIELECTRIC)
+        {
+            r1_set_error("r1_set_scene: sphere %u is hittable but has no material", i);
+            return R1_EINVAL;
+        }
+    const uint32_t na = (uint32_t)c->active_to_scene.size();
+    if (na > R1_MAX_ACTIVE)
+    {
+        r1_set_error("r1_set_scene: %u hittable spheres; this build supports up to %u", na, R1_MAX_ACTIVE);
+        return R1_ELIMIT;
+    }
+    // the sweep's tables (r1_sweep.cpp): sphere groups, their members, the per-sphere rows
+    R1Sweep sw;
+    r1_build_sweep(s, c->active_to_scene, sw);
+
+    // the optional spatial index over the same active spheres (R1_VARIANT_BVH)
+    R1Bvh bvh;
+    {
+        std::vector<float> fx(na ? na : 1), fy(na ? na : 1), fz(na ? na : 1), fr(na ? na : 1);
+        for (uint32_t a = 0; a < na; ++a)
+            fx[a] = sw.exact[4 * a + 0], fy[a] = sw.exact[4 * a + 1], fz[a] = sw.exact[4 * a + 2], fr[a] = sw.exact[4 * a + 3];
+        static const int leaf_env = (int)r1_knob("R1_BVH_LEAF", 0);
+        // leaf size: 4 spheres (2 pairs) on the reference's scenes; 8 on big lattices (measured:
+        // 100 004 spheres 3.43 ms against 3.67 ms per 1920x1080x4 frame)
+        const int leaf_default = na > R1_MAX_ACTIVE_10BIT ? 2 * R1_BVH_LEAF : R1_BVH_LEAF;
+        r1_build_bvh(na, fx.data(), fy.data(), fz.data(), fr.data(), sw.rbound.data(), leaf_env > 0 ? leaf_env : leaf_default, bvh);
+        if (bvh.max_depth > R1_BVH_STACK)
+        {
+            r1_set_error("r1_set_scene: spatial index deeper (%d) than the traversal stack (%d)", bvh.max_depth, R1_BVH_STACK);
+            return R1_ELIMIT;
+        }
+    }
+    // leaf_quad fetches a sphere index speculatively for lanes that hold no flagged sphere (slot 3 of the step, whatever the step's
+    // pair count): two sentinel words behind the last pair keep that read inside the table
+    bvh.ids.resize(bvh.ids.size() + 2, 0xFFFFFFFFu);
+
+    // what a refit needs besides the tree (r1_update_centers*): topology and the radii, once per scene
+    R1RefitTopo topo;
+    r1_bvh_topology(bvh, na, topo);
+    c->scene_to_active.assign(s->count ? s->count : 1, 0xFFFFFFFFu);
+    for (uint32_t a = 0; a < na; ++a)
+        c->scene_to_active[c->active_to_scene[a]] = a;
+    std::vector<uint32_t> rtab;
+    size_t roff[5];
+    {
+        const std::vector<uint32_t> *parts[5] = {&c->scene_to_active, &topo.slot, &topo.leaf_ref, &topo.child_box, &topo.by_height};
+        for (int k = 0; k < 5; ++k)
+            roff[k] = rtab.size(), rtab.insert(rtab.end(), parts[k]->begin(), parts[k]->end());
+    }
+    std::vector<double> radii(2 * (size_t)(na ? na : 1), 0.0);
+    for (uint32_t a = 0; a < na; ++a)
+        radii[2 * (size_t)a + 0] = sw.rbound[a], radii[2 * (size_t)a + 1] = r1_test_radius(sw.rbound[a], sw.exact[4 * (size_t)a + 3]);
+    const size_t n_box = bvh.nodes.size() / 16 + topo.leaf_ref.size();
+
+    // Uploads go through the context's OWN stream (then one wait): librays1 never touches the null stream.  A process
+    // that keeps K frames in flight on K contexts with GPU_MAX_HW_QUEUES = K would otherwise hand one of its K hardware
+    // queues to the null stream, and two frames would share a queue and run one after the other (measured: 20 frames
+    // land in 20.1 ms instead of 17.0, tools/submit_times.py, profiles/r03/stream_queue_mapping.txt).
+    const struct
+    {
+        DevBuf &buf;
+        const void *data;
+        size_t bytes;
+    } uploads[] = {
+        {c->sweep, sw.sweep.data(), sw.sweep.size() * 4},
+        {c->exact, sw.exact.data(), sw.exact.size() * 4},
+        {c->shade, sw.shade.data(), sw.shade.size() * 4},
+        {c->mat, sw.mat.data(), sw.mat.size() * 4},
+        {c->members, sw.members.data(), sw.members.size() * 4},
+        {c->exact_g, sw.exact_g.data(), sw.exact_g.size() * 4},
+        {c->bvh_nodes, bvh.nodes.data(), bvh.nodes.size() * 4},
+        {c->bvh_prims, bvh.prims.data(), bvh.prims.size() * 4},
+        {c->bvh_ids, bvh.ids.data(), bvh.ids.size() * 4},
+        {c->active_dev, c->active_to_scene.data(), (size_t)na * 4}, // ray queries report SCENE indices: the active spheres' scene indices
+        {c->refit_tab, rtab.data(), rtab.size() * 4},
+        {c->refit_radii, radii.data(), radii.size() * 8},
+    };
+    int rc;
+    for (const auto &u : uploads)
+        if ((rc = ensure(u.buf, u.bytes)))
+            return rc;
+    if ((rc = ensure(c->refit_box, 256 + n_box * sizeof(R1Box))))
+        return rc;
+    R1_HIP(hipStreamSynchronize(c->stream));
+    for (const auto &u : uploads)
+        if (u.bytes)
+            R1_HIP(hipMemcpyAsync(u.buf.p, u.data, u.bytes, hipMemcpyHostToDevice, c->stream));
+    R1_HIP(hipStreamSynchronize(c->stream)); // the host vectors go out of scope
+    {
+        R1RefitArgs &r = c->refit;
+        const uint32_t *tab = (const uint32_t *)c->refit_tab.p;
+        r.exact = (float *)c->exact.p, r.prims = (float *)c->bvh_prims.p, r.nodes = (float *)c->bvh_nodes.p, r.ids = (const uint32_t *)c->bvh_ids.p;
+        r.scene_to_active = tab + roff[0], r.slot = tab + roff[1], r.leaf_ref = tab + roff[2], r.child_box = tab + roff[3], r.by_height = tab + roff[4];
+        r.radii = (const double *)c->refit_radii.p;
+        r.a_max = (uint32_t *)c->refit_box.p, r.box = (R1Box *)((char *)c->refit_box.p + 256);
+        r.n_nodes = (uint32_t)(bvh.nodes.size() / 16), r.n_leaves = (uint32_t)topo.leaf_ref.size();
+        r.fill = bvh.fill;
+        c->refit_height_off = topo.height_off;
+    }
+    c->moved = false;
+    c->n_bvh_nodes = (uint32_t)(bvh.nodes.size() / 16);
+    c->n_bvh_leaves = bvh.n_leaves;
+    c->bvh_depth = bvh.max_depth;
+    for (int k = 0; k < 3; ++k)
+        c->bvh_centre[k] = bvh.centre[k];
+    c->bvh_pad_local = bvh.pad_local;
+    c->bvh_root_leaf = bvh.root_leaf;
+    // (the kernels' flat walk is written for y, the up axis of the reference's scenes; a tree flat along x or z walks the generic loop)
+    c->bvh_flat_m = bvh.flat_axis == 1 ? bvh.flat_m : 0.0f, c->bvh_flat_e = bvh.flat_axis == 1 ? bvh.flat_e : -1.0f;
+    for (int &o : c->occupancy)
+        o = 0; // the tree kernels' LDS footprint follows the tree (depth of the traversal stack, size of the node table)
+    for (int &o : c->cast_occupancy)
+        o = 0;
+    c->n_groups = sw.n_groups;
+    c->n_multi = sw.n_multi;
+
+    c->n_active = na;
+    c->n_sweep = sw.n_sweep;
+    c->n_padded_scene = s->count;
+    c->cam = device_camera(*cam);
+    for (int k = 0; k < 9; ++k)
+        c->src_f32[k].assign(src[k], src[k] + s->count);
+    c->src_mat.assign(s->mat_type, s->mat_type + s->count);
+    c->src_cam = *cam;
+    c->have_scene = true;
+    c->default_variant = c->default_variant_tp = R1_V_TREE;
+    return R1_OK;
+}
+
+// The camera alone: it travels by value in every launch's arguments, so nothing is built, uploaded or waited for, and launches already
+// enqueued keep the camera they were enqueued with.
+extern "C" int r1_set_camera(r1_context *c, const r1_camera *cam)
+{
+    if (!c || !cam)
+    {
+        r1_set_error("r1_set_camera: %s is NULL", !c ? "ctx" : "camera");
+        return R1_EINVAL;
+    }
+    if (!c->have_scene)
+    {
+        r1_set_error("r1_set_camera: no scene set (call r1_set_scene first)");
+        return R1_EINVAL;
+    }
+    c->pass_valid = false; // (a progressive frame does not continue across a change of view, as across r1_set_scene)
+    c->cam = device_camera(*cam);
+    c->src_cam = *cam;       // r1_set_scene(same arrays, this camera) is still the shortcut
+    return R1_OK;
+}
+
+// ---- moving spheres (include/rays1.h "moving spheres", r1_refit.hip) --------------------------------------------------
+
+static int update_check(const char *who, r1_context *c, uint32_t first, uint32_t count, const void *x, const void *y, const void *z)
+{
+    if (!c)
+    {
+        r1_set_error("%s: ctx is NULL", who);
+        return R1_EINVAL;
+    }
+    if (!c->have_scene)
+    {
+        r1_set_error("%s: no scene set (call r1_set_scene first)", who);
+        return R1_EINVAL;
+    }
+    if ((uint64_t)first + count > c->n_padded_scene)
+    {
+        r1_set_error("%s: spheres [%u, %llu) are beyond the scene's %u", who, first, (unsigned long long)first + count, c->n_padded_scene);
+        return R1_EINVAL;
+    }
+    if (count && (!x || !y || !z))
+    {
+        r1_set_error("%s: x, y and z must not be NULL with count > 0", who);
+        return R1_EINVAL;
+    }
+    return R1_OK;
+}
+
+// The move and the refit on `st`, centres from memory the device can read; then what an update changes in the context.  Nothing is waited
+// for.  `moved_ev` (or null) is recorded straight behind the move kernel, the only reader of the centres.  Leaves the launch info and the
+// timing events alone.
+static int update_enqueue(r1_context *c, uint32_t first, uint32_t count, const float *dx, const float *dy, const float *dz, hipStream_t st,
+                          hipEvent_t moved_ev)
+{
+    R1_HIP(r1_launch_refit_move(&c->refit, first, count, dx, dy, dz, st));
+    if (moved_ev)
+        R1_HIP(hipEventRecord(moved_ev, st));
+    if (c->n_active) // (a tree of 0 spheres has nothing to refit)
+        R1_HIP(r1_launch_refit(&c->refit, c->refit_height_off.data(), (uint32_t)c->refit_height_off.size() - 1u, st));
+    c->moved = true;
+    c->grid_valid = false;
+    c->pass_valid = false; // (a progressive frame does not continue across a change of the scene)
+    // the flat y slab (r1_bvh.cpp) is dropped, not refitted: it travels by value in the launches' arguments, and spheres that leave the
+    // plane are exactly the case it must not miss.  The kernels take the generic loop they already have.
+    c->bvh_flat_m = 0.0f, c->bvh_flat_e = -1.0f;
+    return R1_OK;
+}
+
+extern "C" int r1_update_centers(r1_context *c, uint32_t first, uint32_t count, const float *x, const float *y, const float *z, void *hip_stream)
+{
+    int rc = update_check("r1_update_centers", c, first, count, x, y, z);
+    if (rc || count == 0)
+        return rc;
+    for (uint32_t i = 0; i < count; ++i)
+        if (c->scene_to_active[first + i] != 0xFFFFFFFFu && !(std::isfinite(x[i]) && std::isfinite(y[i]) && std::isfinite(z[i])))
+        {
+            r1_set_error("r1_update_centers: the new centre of sphere %u is not finite", first + i);
+            return R1_EINVAL;
+        }
+    R1_HIP(hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    // the staging buffer: the move kernel of the previous update may still be reading it
+    if (c->stage_busy)
+        R1_HIP(hipEventSynchronize(c->stage_ev));
+    c->stage_busy = false;
+    if (!c->stage_ev)
+        R1_HIP(hipEventCreateWithFlags(&c->stage_ev, hipEventDisableTiming));
+    if (c->stage_cap < 3 * (size_t)count)
+    {
+        if (c->stage)
+            R1_HIP(hipHostFree(c->stage));
+        c->stage = c->stage_dev = nullptr, c->stage_cap = 0;
+        R1_HIP(hipHostMalloc((void **)&c->stage, 3 * (size_t)count * 4, hipHostMallocMapped));
+        R1_HIP(hipHostGetDevicePointer((void **)&c->stage_dev, c->stage, 0));
+        c->stage_cap = 3 * (size_t)count;
+    }
+    memcpy(c->stage, x, (size_t)count * 4), memcpy(c->stage + count, y, (size_t)count * 4), memcpy(c->stage + 2 * (size_t)count, z, (size_t)count * 4);
+    c->stage_busy = true; // (from here on: a launch that failed half-way may still have enqueued the move)
+    if ((rc = update_enqueue(c, first, count, c->stage_dev, c->stage_dev + count, c->stage_dev + 2 * (size_t)count, st, c->stage_ev)))
+        return rc;
+    // the context's host copies follow (entries of spheres that are not active too: they are what r1_set_scene would be given)
+    memcpy(c->src_f32[0].data() + first, x, (size_t)count * 4), memcpy(c->src_f32[1].data() + first, y, (size_t)count * 4);
+    memcpy(c->src_f32[2].data() + first, z, (size_t)count * 4);
+    return R1_OK;
+}
+
+extern "C" int r1_update_centers_device(r1_context *c, uint32_t first, uint32_t count, const void *d_x, const void *d_y, const void *d_z, void *hip_stream)
+{
+    int rc = update_check("r1_update_centers_device", c, first, count, d_x, d_y, d_z);
+    if (rc || count == 0)
+        return rc;
+    if (((uintptr_t)d_x | (uintptr_t)d_y | (uintptr_t)d_z) & 3u)
+    {
+        r1_set_error("r1_update_centers_device: d_x, d_y and d_z must be 4-byte aligned");
+        return R1_EINVAL;
+    }
+    R1_HIP(hipSetDevice(c->device));
+    return update_enqueue(c, first, count, (const float *)d_x, (const float *)d_y, (const float *)d_z, hip_stream ? (hipStream_t)hip_stream : c->stream, nullptr);
+}
+
+extern "C" int r1_bvh_download(r1_context *c, float *nodes_out, size_t nodes_cap, size_t *nodes)
+{
+    if (!c || !nodes)
+    {
+        r1_set_error("r1_bvh_download: %s is NULL", !c ? "ctx" : "nodes");
+        return R1_EINVAL;
+    }
+    if (!c->have_scene)
+    {
+        r1_set_error("r1_bvh_download: no scene set (call r1_set_scene first)");
+        return R1_EINVAL;
+    }
+    *nodes = c->n_bvh_nodes;
+    if (!nodes_out)
+        return R1_OK;
+    if (nodes_cap < 16 * (size_t)c->n_bvh_nodes)
+        return R1_ELIMIT;
+    R1_HIP(hipSetDevice(c->device));
+    R1_HIP(hipMemcpyAsync(nodes_out, c->bvh_nodes.p, 64 * (size_t)c->n_bvh_nodes, hipMemcpyDeviceToHost, c->stream));
+    R1_HIP(hipStreamSynchronize(c->stream));
+    return R1_OK;
+}
+
+// R1_VARIANT_GRID: builds the uniform grid of the context's scene (from the arrays r1_set_scene received, so that r1_grid_describe and
+// r1_grid_visit see the same grid) and uploads it, once per scene.  Contexts that never ask for the grid pay nothing for it.
+int ensure_grid(r1_context *c)
+{
+    if (c->grid_valid)
+        return R1_OK;
+    r1_scene s;
+    s.count = (uint32_t)c->src_mat.size();
+    s.center_x = c->src_f32[0].data(), s.center_y = c->src_f32[1].data(), s.center_z = c->src_f32[2].data();
+    s.radius_sq = c->src_f32[3].data(), s.inv_radius = c->src_f32[4].data(), s.mat_type = c->src_mat.data();
+    s.albedo_r = c->src_f32[5].data(), s.albedo_g = c->src_f32[6].data(), s.albedo_b = c->src_f32[7].data(), s.mat_param = c->src_f32[8].data();
+    R1Grid g;
+    if (r1_grid_from_scene(&s, g) != R1_OK)
+    {
+        r1_set_error("grid: the scene's spheres could not be read");
+        return R1_EINVAL;
+    }
+    // small-scene kernel: 16-bit cell starts and ids, all of it copied into every workgroup's LDS
+    const size_t halves = g.start.size() + g.ids.size();
+    c->grid_small = c->n_active <= R1_MAX_ACTIVE_10BIT && halves <= R1_GRID_LDS_HALVES && g.ids.size() < 65536u;
+    std::vector<uint32_t> tab32;
+    std::vector<uint16_t> tab16;
+    size_t tab_bytes;
+    if (c->grid_small)
+    {
+        tab16.assign((halves + 7) & ~(size_t)7, 0); // (whole 16-byte rows: the kernel copies float4)
+        for (size_t q = 0; q < g.start.size(); ++q)
+            tab16[q] = (uint16_t)g.start[q];
+        for (size_t q = 0; q < g.ids.size(); ++q)
+            tab16[g.start.size() + q] = (uint16_t)g.ids[q];
+        tab_bytes = tab16.size() * 2;
+    }
+    tab32 = g.start;
+    tab32.insert(tab32.end(), g.ids.begin(), g.ids.end());
+    if (!c->grid_small)
+        tab_bytes = tab32.size() * 4;
+    std::vector<uint32_t> outl = g.outliers;
+    if (outl.empty())
+        outl.push_back(0u);
+    int rc;
+    R1_HIP(hipSetDevice(c->device));
+    R1_HIP(hipDeviceSynchronize()); // (launches of an earlier grid may still read the buffers that are about to be replaced)
+    if ((rc = ensure(c->grid_tab, tab_bytes)) || (rc = ensure(c->grid_out, outl.size() * 4)) || (rc = ensure(c->grid_tab32, tab32.size() * 4)))
+        return rc;
+    R1_HIP(hipMemcpyAsync(c->grid_tab32.p, tab32.data(), tab32.size() * 4, hipMemcpyHostToDevice, c->stream));
+    R1_HIP(hipMemcpyAsync(c->grid_tab.p, c->grid_small ? (const void *)tab16.data() : (const void *)tab32.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));
+    R1_HIP(hipMemcpyAsync(c->grid_out.p, outl.data(), outl.size() * 4, hipMemcpyHostToDevice, c->stream));
+    R1_HIP(hipStreamSynchronize(c->stream));
+    R1GridArgs &G = c->grid_args;
+    memset(&G, 0, sizeof(G));
+    G.geom = g.geom;
+    G.outliers = (const uint32_t *)c->grid_out.p;
+    G.n_out = (uint32_t)g.outliers.size();
+    G.n_start = (uint32_t)g.start.size();
+    G.tab = (const uint32_t *)c->grid_tab.p;
+    G.lds_bytes = c->grid_small ? (uint32_t)tab_bytes : 0u;
+    R1GridArgs G32 = G;
+    G32.tab = (const uint32_t *)c->grid_tab32.p, G32.lds_bytes = 0;
+    if ((rc = ensure(c->grid_dev, sizeof(G))) || (rc = ensure(c->grid_dev32, sizeof(G))))
+        return rc;
+    R1_HIP(hipMemcpyAsync(c->grid_dev.p, c->grid_small ? &G : &G32, sizeof(G), hipMemcpyHostToDevice, c->stream));
+    R1_HIP(hipMemcpyAsync(c->grid_dev32.p, &G32, sizeof(G), hipMemcpyHostToDevice, c->stream));
+    R1_HIP(hipStreamSynchronize(c->stream));
+    c->grid_valid = true;
+    return R1_OK;
+}

@@ -245,7 +245,7 @@ __device__ __forceinline__ void sweep_reference(const R1DeviceScene &S, const V3
 // For unit d:  discr = (co.d)^2 - |co|^2 + r^2  with co = c - o
 //            = (c.d - o.d)^2 - (|o|^2 - 2 c.o) - (|c|^2 - r^2)
 // The test is applied to GROUPS of <= R1_GROUP_MAX nearby spheres through a bounding sphere
-// (g, R) that contains every member (host, r1_capi.cpp build_groups):
+// (g, R) that contains every member (host, r1_sweep.cpp build_groups):
 // Per ray:    negod = -(o.d), m2o = -2 o, oo' = |o|^2 (1 - 2^-15)
 // Per group:  Kp = (|g|^2 - R^2) - 2^-15 (C^2 + R^2), rounded down, C^2 >= |g|^2 and every |c_i|^2
 // Test:       fma(nb', nb', -t') >= Kp   with two 3-FMA chains nb', t'        => 7 FMA + 1 compare
@@ -493,7 +493,7 @@ __device__ __forceinline__ void sweep_prefilter(const R1DeviceScene &S, const bo
     wbest[lane] = NONE;
     int cnt = 0;
 
-    // Pair layout (r1_capi.cpp): 8 floats per two spheres {cx0 cx1 cy0 cy1 cz0 cz1 Kp0 Kp1}, so
+    // Pair layout (r1_sweep.cpp): 8 floats per two spheres {cx0 cx1 cy0 cy1 cz0 cz1 Kp0 Kp1}, so
     // that every v_pk_fma_f32 takes an aligned SGPR pair straight from the scalar load: two
     // spheres per VALU instruction, 3.5 + 1 instructions per sphere.  A chunk = 8 spheres =
     // two s_load_dwordx16; the NEXT chunk is requested before the current one is evaluated
@@ -502,7 +502,7 @@ __device__ __forceinline__ void sweep_prefilter(const R1DeviceScene &S, const bo
     const v2f mxx = {mx, mx}, myy = {my, my}, mzz = {mz, mz};
     const v2f nod = {negod, negod}, ooa = {oo_adj, oo_adj};
     const cf16_ptr tab = (cf16_ptr)S.sweep;
-    const uint32_t chunks = S.n_sweep >> 3; // r1_capi.cpp pads to 8 spheres + one prefetch chunk
+    const uint32_t chunks = S.n_sweep >> 3; // r1_sweep.cpp pads to 8 spheres + one prefetch chunk
 
 #define R1_PAIR(P, L, B)                                                                                               \
     {                                                                                                                  \
@@ -856,7 +856,7 @@ __device__ __forceinline__ void bvh_advance(const R1DeviceScene &S, const V3 o, 
         float tn0, tn1;
         // The pad.  Table in LDS (LN): A R2 |1/d| of the whole tree, computed once per call (`pa_ray`; the nodes' K are part of
         // their half extents, r1_bvh.cpp).  Table in global memory: per node, pad = A dist2 + K with dist2 = R2 or — wave-uniform,
-        // scenes of small spheres — |m0 + m1 - 2 o|^2; such trees always run through these kernels (r1_capi.cpp big_scene).
+        // scenes of small spheres — |m0 + m1 - 2 o|^2; such trees always run through these kernels (r1_frame.cpp big_scene).
         V3 pa = pa_ray;
         if (!LN)
         {
@@ -944,7 +944,7 @@ __device__ __forceinline__ void bvh_advance(const R1DeviceScene &S, const V3 o, 
     if (root_leaf != 0u && cur == 0u) // (the first condition is wave-uniform)
     {
         const int k = root_leaf == 1u ? 1 : 0; // column of the OTHER child in the node's rows
-        const float *nf = (const float *)lnodes; // node 0: always in the workgroup's LDS copy (big scenes keep the top of the tree there: at least node 0, r1_capi.cpp)
+        const float *nf = (const float *)lnodes; // node 0: always in the workgroup's LDS copy (big scenes keep the top of the tree there: at least node 0, r1_frame.cpp fill_walk)
         const uint32_t leaf = __float_as_uint(nf[14 + (1 - k)]);
         const uint32_t other = __float_as_uint(nf[14 + k]);
         const uint32_t lp = (leaf >> COUNT_SHIFT) & 7u;
@@ -1503,7 +1503,7 @@ __device__ __forceinline__ bool shade_level(const R1TraceArgs &A, Path &p, const
             }
             // packed stack: one LDS word holds entries 3w, 3w+1, 3w+2 (10 bits each); walk it word by word from the top
             // entry down.  The three albedos of a word are fetched together, whether the word is full or not (any 10-bit
-            // index is inside the table, r1_capi.cpp), and the slots above the top entry multiply by 1.0f, which changes
+            // index is inside the table, r1_sweep.cpp), and the slots above the top entry multiply by 1.0f, which changes
             // no bit: one round trip to the table per word instead of one per entry.
             int w = (top - 1) / 3, j = (top - 1) - 3 * w;
             int t_ = tid;
@@ -1845,7 +1845,7 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
     const int tid = (int)threadIdx.x;
     const int lane = tid & 63;
 
-    // Tree kernels, small scenes (!BIG: at most R1_NODES_LDS_MAX nodes, r1_capi.cpp): the workgroup keeps its own copy of
+    // Tree kernels, small scenes (!BIG: at most R1_NODES_LDS_MAX nodes, r1_frame.cpp big_scene): the workgroup keeps its own copy of
     // the node table in LDS, behind the traversal stack.  A node visit is four dependent 16-byte loads per lane; LDS
     // answers sooner than the vector L1, and the table no longer competes with the sphere tables for its 32 KB:
     // 26.9 -> 29.3 Grays/s, one synchronous frame 1.34 -> 1.17 ms (large scene, 128 nodes = 8 KB).

@@ -523,7 +523,7 @@ def test_pixel_mode_writes_the_same_pixels_and_counts(case):
         sc, w, h, spp, shards, tw, th = r1.create_grid_scene(160, 120, 50, 32), 160, 120, 4, 2, 32, 32
     elif case == "sweep_kernel":
         sc, w, h, spp, shards, tw, th, variant = r1.create_large_scene(320, 200), 320, 200, 6, 1, 32, 32, binding.VARIANT_PREFILTER
-    else:  # R1_VARIANT_GRID on a small scene: PIXEL mode runs the grid's big-scene kernel (r1_capi.cpp)
+    else:  # R1_VARIANT_GRID on a small scene: PIXEL mode runs the grid's big-scene kernel (r1_frame.cpp big_scene)
         sc, w, h, spp, shards, tw, th, variant = r1.create_large_scene(150, 90), 150, 90, 3, 2, 24, 40, binding.VARIANT_GRID
     rend = r1.Renderer(0)
     try:
@@ -552,7 +552,7 @@ def test_pixel_mode_writes_the_same_pixels_and_counts(case):
 
 def test_frame_sequences_on_one_context_keep_the_counter_block_consistent():
     """The resolve launch of a frame publishes its ray count and zeroes the context's counter block for the NEXT frame
-    (r1_capi.cpp: fused_clear); diagnostic frames, PIXEL-mode frames and empty shards clear with memsets instead.  Every
+    (r1_frame.cpp: fused_clear); diagnostic frames, PIXEL-mode frames and empty shards clear with memsets instead.  Every
     order of these on ONE context must give the same counts and pixels: a frame that inherits a dirty block would
     start with an advanced sample queue (too few rays) or a non-zero count (too many)."""
     torch = pytest.importorskip("torch")

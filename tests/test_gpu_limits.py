@@ -35,7 +35,7 @@ pytestmark = pytest.mark.gpu
 
 SENTINEL = 0xCD
 CHILD_TIMEOUT_S = 240
-SLOTS = "2^31 sample slots per launch"  # the padded-slot rule (r1_capi.cpp prepare_tiles, r1_render_pass)
+SLOTS = "2^31 sample slots per launch"  # the padded-slot rule (r1_frame.cpp prepare_tiles, r1_render.cpp r1_render_pass)
 BVH, TILE4G_SPPS = binding.VARIANT_BVH, (8191, 8192, 16383, 16384, 20000)
 
 
