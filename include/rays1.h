@@ -30,6 +30,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "rays1_seed.h" /* r1_sample_seed: the four stream states of a path (path queries) */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -561,6 +563,67 @@ int r1_cast_rays_device(r1_context *ctx, int32_t variant, int32_t mode, const vo
 /* The same without a device: every ray against every sphere in the reference's arithmetic, on host threads.  For callers without
  * a GPU at hand, and the checker of the two entry points above (tests/golden/cast_*.bin pin it to the reference's own output). */
 int r1_cast_rays_host(const r1_scene *scene, int32_t mode, const r1_ray *rays, size_t n, void *out);
+
+/* ---- path queries: color() for caller-supplied rays ---------------------------------------- */
+
+/* Radiance along rays that no camera of this library generated (panoramas, stereo pairs, orthographic views, light probes, re-traced
+ * samples).  The contract of the three trace forms is the reference's `color(Ray(o, d), scene, 0)` (rayweek1.cpp:517-534), bit for
+ * bit: out[i] = {what it returns, the number of color() invocations it made}, with ThreadData::state = seeds[i].scalar and lanes 0..2
+ * of ThreadData::state4 = seeds[i].lane0..2 when it is called.
+ *   direction    d is normalised as the Ray constructor does it, d * (1 / sqrt(dot(d, d))), in fp32 — once.
+ *   t_max, pad   of the r1_ray are ignored: color() always passes FLT_MAX.
+ *   max_bounces  MAX_BOUNCES, 1..R1_MAX_BOUNCES_LIMIT; anything else is R1_EINVAL.
+ *   non-finite   a ray with a non-finite component in o, or in d after normalisation (a zero direction normalises to NaN, one of
+ *                1e-30 to infinity), runs no color(): its record is {0, 0, 0, rays = 0}.  The ray queries' test, identical in all
+ *                three forms.
+ *   zero states  xorshift32 has the fixed point 0, and random_in_unit_sphere on an all-zero stream never ends: a stream state of 0
+ *                is replaced by r1_nonzero()'s constant before the path starts (r1_seed_guard of rays1_seed.h, called by the
+ *                device's load and by the host form).  This is the guard against a caller-made GPU hang.
+ *   seeds NULL   ray i is seeded with the seeding contract's states for (seed 0, pixel (uint32_t)i, sample 0); for the device form
+ *                i is the index within the call.
+ *   variants     as for the ray queries: R1_VARIANT_DEFAULT / _BVH (box tree), _GRID, _REFERENCE, same bytes from each; every other
+ *                variant is R1_EINVAL (r1_last_error names it).  After r1_update_centers* GRID is refused ("the scene has moved"),
+ *                the others see the moved scene.
+ *   no spheres   a scene without an active sphere gives the sky for every valid ray.
+ * Argument rules, in the ray queries' order: R1_EINVAL for a NULL ctx, then for a bad variant or max_bounces, then before the first
+ * r1_set_scene; then n == 0 is R1_OK and touches nothing; then R1_EINVAL for NULL rays / out.
+ * A trace changes no state another entry point sees: a progressive accumulation survives it, r1_last_launch_info / r1_last_timing
+ * keep describing the last render, the context's camera plays no part.
+ * Launches in flight: ONE trace launch per context.  The attenuation stack of the paths is a per-context workspace of max_bounces x
+ * 4 bytes per thread of the launch — at most 51 x 4 x 256 threads x 8 workgroups per compute unit, 107 MB on a 256-CU device; typical
+ * launches hold fewer workgroups — which grows on demand and is freed with the context.  K traces in flight = K contexts, as for frames. */
+typedef struct r1_radiance
+{
+    float r, g, b;
+    uint32_t rays;
+} r1_radiance; /* 16 bytes: the record of r1_render_samples */
+
+/* Rays the host-memory form works through at a time, in the workspace the ray queries cache in the context (64 bytes per ray: 32 ray +
+ * 16 seed + 16 record). */
+#define R1_TRACE_CHUNK (1u << 20)
+
+/* Host memory in and out, synchronous. */
+int r1_trace_rays(r1_context *ctx, int32_t variant, int32_t max_bounces, const r1_ray *rays, const r1_sample_seed *seeds, size_t n,
+                  r1_radiance *out);
+
+/* The same over DEVICE memory: enqueues on `hip_stream` (a hipStream_t; NULL = the context's stream) and waits for nothing.  d_rays
+ * (n r1_ray), d_seeds (n r1_sample_seed, or NULL) and d_out (n r1_radiance) are 16-byte aligned (R1_EINVAL otherwise). */
+int r1_trace_rays_device(r1_context *ctx, int32_t variant, int32_t max_bounces, const void *d_rays, const void *d_seeds, size_t n,
+                         void *d_out, void *hip_stream);
+
+/* The same without a device: every active sphere in index order with the host's exact test (the one behind r1_cast_rays_host), the
+ * color() levels in scalar C++ in the reference's operation order, on host threads.  The checker of the two forms above. */
+int r1_trace_rays_host(const r1_scene *scene, int32_t max_bounces, const r1_ray *rays, const r1_sample_seed *seeds, size_t n,
+                       r1_radiance *out);
+
+/* Host only, pure arithmetic: rayweek1.cpp:757-760 under the seeding contract.  For sample s[i] of pixel (x[i], y[i]) of a
+ * params->width x height image with params->seed: the ray's origin (origin + lens offset), the UN-normalised direction exactly as
+ * getRay hands it to the Ray constructor (the trace forms normalise once; twice may differ in the last bit), t_max = FLT_MAX, and the
+ * four stream states AFTER the camera's draws (the jitter draw that advances lanes 0..2, the rejection loop of random_in_unit_disk on
+ * the scalar stream).  This followed by any trace form equals that sample's record of r1_render_samples, bit for bit.  R1_EINVAL for
+ * NULL pointers with n > 0, a pixel outside the image, or s < 0. */
+int r1_camera_rays(const r1_camera *camera, const r1_params *params, const int32_t *x, const int32_t *y, const int32_t *s, size_t n,
+                   r1_ray *rays_out, r1_sample_seed *seeds_out);
 
 /* ---- host-side helpers of the drop-in (no GPU needed) ------------------------------ */
 

@@ -71,4 +71,16 @@ R1_HD r1_sample_seed r1_seed_sample(uint32_t seed, uint32_t pixel, uint32_t samp
     return s;
 }
 
+/* Caller-supplied stream states (r1_trace_rays*, rays1.h "path queries"): a state of 0 is replaced by r1_nonzero()'s constant before the
+ * path starts.  An all-zero stream never leaves 0, and the rejection loop of random_in_unit_sphere on such a stream never ends: this
+ * is what keeps a caller's array of zeros from hanging a GPU.  The device's load and the host form both call this one function. */
+R1_HD r1_sample_seed r1_seed_guard(r1_sample_seed s)
+{
+    s.scalar = r1_nonzero(s.scalar);
+    s.lane0  = r1_nonzero(s.lane0);
+    s.lane1  = r1_nonzero(s.lane1);
+    s.lane2  = r1_nonzero(s.lane2);
+    return s;
+}
+
 #endif /* RAYS1_SEED_H */

@@ -100,6 +100,10 @@ RAY_DTYPE = np.dtype([("o", np.float32, 3), ("t_max", np.float32), ("d", np.floa
 HIT_DTYPE = np.dtype([("t", np.float32), ("index", np.int32), ("p", np.float32, 3), ("n", np.float32, 3)])
 CAST_CLOSEST, CAST_ANY = 0, 1
 CAST_CHUNK = 1 << 20  # R1_CAST_CHUNK: rays per launch of r1_cast_rays
+# r1_sample_seed / r1_radiance (16 bytes each) of the path queries
+SEED_DTYPE = np.dtype([("scalar", np.uint32), ("lane0", np.uint32), ("lane1", np.uint32), ("lane2", np.uint32)])
+RADIANCE_DTYPE = np.dtype([("r", np.float32), ("g", np.float32), ("b", np.float32), ("rays", np.uint32)])
+TRACE_CHUNK = 1 << 20  # R1_TRACE_CHUNK: rays r1_trace_rays works through at a time
 
 
 def make_params(width, height, spp, seed=10001, max_bounces=50, tile_w=32, tile_h=32, shard=0, num_shards=1, variant=0):
@@ -201,6 +205,10 @@ SYMBOLS = [
     ("r1_cast_rays", C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("r1_cast_rays_device", C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     ("r1_cast_rays_host", C.c_int, [C.POINTER(CScene), C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("r1_trace_rays", C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("r1_trace_rays_device", C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    ("r1_trace_rays_host", C.c_int, [C.POINTER(CScene), C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("r1_camera_rays", C.c_int, [C.POINTER(CCamera), C.POINTER(Params), _i32p, _i32p, _i32p, C.c_size_t, C.c_void_p, C.c_void_p]),
     ("r1_tga_write_rgb24", C.c_int, [C.c_char_p, C.c_int32, C.c_int32, _u8p]),
     ("r1_log_results", C.c_int, [C.c_char_p, C.c_char_p, _dblp, _u64p, C.c_int32]),
 ]
@@ -483,6 +491,23 @@ class Renderer:
         """r1_cast_rays_device: the same over device memory (16-byte aligned: n r1_ray in, n r1_hit or n bytes out); enqueues on
         `stream` and waits for nothing."""
         _check(lib().r1_cast_rays_device(self._c, variant, mode, C.c_void_p(d_rays_ptr), n, C.c_void_p(d_out_ptr), _stream_arg(stream)))
+
+    def trace_rays(self, rays, seeds=None, max_bounces=50, variant=0):
+        """r1_trace_rays: color() for caller-supplied rays, host memory in and out.  `rays` as for cast_rays (t_max is ignored); `seeds`: a
+        SEED_DTYPE array or uint32 (n, 4) rows {scalar, lane0, lane1, lane2}, or None (ray i: the seeding contract's states for seed 0,
+        pixel i, sample 0).  Returns a RADIANCE_DTYPE array in ray order."""
+        rays = _as_rays(rays)
+        seeds = _as_seeds(seeds, rays.shape[0])
+        out = np.zeros(rays.shape[0], RADIANCE_DTYPE)
+        _check(lib().r1_trace_rays(self._c, variant, max_bounces, rays.ctypes.data, seeds.ctypes.data if seeds is not None else None,
+                                   rays.shape[0], out.ctypes.data))
+        return out
+
+    def trace_rays_device(self, d_rays_ptr, d_seeds_ptr, n, d_out_ptr, max_bounces=50, variant=0, stream=None):
+        """r1_trace_rays_device: the same over device memory (16-byte aligned: n r1_ray and n r1_sample_seed — or 0 / None — in, n
+        r1_radiance out); enqueues on `stream` (a hipStream_t value; None: the context's stream) and waits for nothing."""
+        _check(lib().r1_trace_rays_device(self._c, variant, max_bounces, C.c_void_p(d_rays_ptr), C.c_void_p(d_seeds_ptr) if d_seeds_ptr else None, n,
+                                          C.c_void_p(d_out_ptr), _stream_arg(stream)))
 
     def set_pixel_mode(self, on):
         _check(lib().r1_set_pixel_mode(self._c, 1 if on else 0))
@@ -801,6 +826,38 @@ def cast_rays_host(cscene, rays, mode=CAST_CLOSEST):
     out = _cast_out(rays.shape[0], mode)
     _check(lib().r1_cast_rays_host(C.byref(cscene), mode, rays.ctypes.data, rays.shape[0], out.ctypes.data))
     return out
+
+
+def _as_seeds(seeds, n):
+    if seeds is None:
+        return None
+    seeds = np.asarray(seeds)
+    if (seeds.dtype == SEED_DTYPE and seeds.shape == (n,)) or (seeds.dtype == np.uint32 and seeds.shape == (n, 4)):
+        return np.ascontiguousarray(seeds)
+    raise R1Error(R1_EINVAL, "seeds: a SEED_DTYPE array or a uint32 (n, 4) array, one per ray")
+
+
+def trace_rays_host(cscene, rays, seeds=None, max_bounces=50):
+    """r1_trace_rays_host: color() for caller-supplied rays in scalar C++ on host threads (no device).  Same input and output forms as
+    Renderer.trace_rays."""
+    rays = _as_rays(rays)
+    seeds = _as_seeds(seeds, rays.shape[0])
+    out = np.zeros(rays.shape[0], RADIANCE_DTYPE)
+    _check(lib().r1_trace_rays_host(C.byref(cscene), max_bounces, rays.ctypes.data, seeds.ctypes.data if seeds is not None else None,
+                                    rays.shape[0], out.ctypes.data))
+    return out
+
+
+def camera_rays(ccamera, params, x, y, s):
+    """r1_camera_rays: the rays (un-normalised directions, t_max = FLT_MAX) and the stream states after the camera's draws of samples
+    s[i] of pixels (x[i], y[i]).  Returns (RAY_DTYPE array, SEED_DTYPE array); traced, they are those samples' records of render_samples."""
+    x, y, s = (np.ascontiguousarray(v, np.int32) for v in (x, y, s))
+    if not (x.ndim == 1 and x.shape == y.shape == s.shape):
+        raise R1Error(R1_EINVAL, "camera_rays: x, y and s are 1-D arrays of one length")
+    rays, seeds = np.zeros(x.shape[0], RAY_DTYPE), np.zeros(x.shape[0], SEED_DTYPE)
+    _check(lib().r1_camera_rays(C.byref(ccamera), C.byref(params), x.ctypes.data_as(_i32p), y.ctypes.data_as(_i32p), s.ctypes.data_as(_i32p),
+                                x.shape[0], rays.ctypes.data, seeds.ctypes.data))
+    return rays, seeds
 
 
 class RESULT:

@@ -11,18 +11,18 @@
 #include <stdint.h>
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
-#define R1_HD __host__ __device__ inline
+#define R1F_HD __host__ __device__ inline
 #else
-#define R1_HD inline
+#define R1F_HD inline
 #endif
 
-R1_HD double r1f_min(double a, double b) { return b < a ? b : a; } // std::min
-R1_HD double r1f_max(double a, double b) { return a < b ? b : a; } // std::max
-R1_HD double r1f_abs(double a) { return __builtin_fabs(a); }
-R1_HD bool r1f_finite(float v) { return __builtin_fabsf(v) <= 3.402823466e38f; } // false for NaN and +-inf
+R1F_HD double r1f_min(double a, double b) { return b < a ? b : a; } // std::min
+R1F_HD double r1f_max(double a, double b) { return a < b ? b : a; } // std::max
+R1F_HD double r1f_abs(double a) { return __builtin_fabs(a); }
+R1F_HD bool r1f_finite(float v) { return __builtin_fabsf(v) <= 3.402823466e38f; } // false for NaN and +-inf
 
 // nextafterf(f, +inf)
-R1_HD float r1f_next_up(float f)
+R1F_HD float r1f_next_up(float f)
 {
     if (f != f || f == __builtin_inff())
         return f;
@@ -33,7 +33,7 @@ R1_HD float r1f_next_up(float f)
 }
 
 // smallest float >= v, then one more step up (guards the double->float conversion)
-R1_HD float r1f_round_up(double v)
+R1F_HD float r1f_round_up(double v)
 {
     float f = (float)v;
     if ((double)f < v)
@@ -48,20 +48,20 @@ struct R1Box
     double kmax;           // max 1 / (2 r_eff)
     double rmax;           // max r
     double floor_pad;      // max r_floor / 2 over degenerate members
-    R1_HD void clear()
+    R1F_HD void clear()
     {
         for (int a = 0; a < 3; ++a)
             lo[a] = clo[a] = 1e300, hi[a] = chi[a] = -1e300;
         kmax = rmax = floor_pad = 0;
     }
-    R1_HD void zero() // the box of a tree without spheres
+    R1F_HD void zero() // the box of a tree without spheres
     {
         for (int a = 0; a < 3; ++a)
             lo[a] = clo[a] = hi[a] = chi[a] = 0;
         kmax = rmax = floor_pad = 0;
     }
-    R1_HD bool empty() const { return lo[0] > hi[0]; } // nothing merged since clear()
-    R1_HD void merge(const R1Box &b)
+    R1F_HD bool empty() const { return lo[0] > hi[0]; } // nothing merged since clear()
+    R1F_HD void merge(const R1Box &b)
     {
         for (int a = 0; a < 3; ++a)
         {
@@ -70,7 +70,7 @@ struct R1Box
         }
         kmax = r1f_max(kmax, b.kmax), rmax = r1f_max(rmax, b.rmax), floor_pad = r1f_max(floor_pad, b.floor_pad);
     }
-    R1_HD double area() const
+    R1F_HD double area() const
     {
         const double dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2];
         return dx * dy + dy * dz + dz * dx;
@@ -79,7 +79,7 @@ struct R1Box
 
 // One sphere's box.  c: the fp32 centre the exact test reads; r: the radius the boxes must cover (r1_bound_radius, >= the radius the exact test
 // reads); r_test: the radius the test itself uses, min(r, sqrt(radius_sq)) or 0 — the error terms E1 / (2 r) follow this smaller, safer one.
-R1_HD void r1f_sphere_box(float cx, float cy, float cz, double r, double r_test, R1Box &s)
+R1F_HD void r1f_sphere_box(float cx, float cy, float cz, double r, double r_test, R1Box &s)
 {
     const double c[3] = {cx, cy, cz};
     // degenerate radii: bound sqrt(r^2 + E1) - r through r_floor (AM-GM), see r1_bvh.cpp
@@ -102,7 +102,7 @@ struct R1FillConst
 };
 
 // child box -> {m, e} in fp32 covering [lo, hi], and this child's (w2, k)
-R1_HD void r1f_encode(const R1Box &bx, float m[3], float e[3], double &w2, double &k)
+R1F_HD void r1f_encode(const R1Box &bx, float m[3], float e[3], double &w2, double &k)
 {
     double h2 = 0;
     for (int a = 0; a < 3; ++a)
@@ -120,7 +120,7 @@ R1_HD void r1f_encode(const R1Box &bx, float m[3], float e[3], double &w2, doubl
 // Words 0..13 of a node's row, {m0x m1x m0y m1y} {m0z m1z e0x e1x} {e0y e1y e0z e1z} {A K . .}, from its two children's boxes; the child
 // references (words 14, 15) are the caller's.
 // pad = A |o - C|^2 + K, or A |m0 + m1 - 2 o|^2 + K (r1_bvh.cpp's header): >= w2 |m - o|^2 + k for both children
-R1_HD void r1f_fill(const R1FillConst &T, const R1Box &b0, const R1Box &b1, float *p)
+R1F_HD void r1f_fill(const R1FillConst &T, const R1Box &b0, const R1Box &b1, float *p)
 {
     float m0[3], e0[3], m1[3], e1[3];
     double w0, k0, w1, k1;
@@ -179,7 +179,7 @@ R1_HD void r1f_fill(const R1FillConst &T, const R1Box &b0, const R1Box &b1, floa
 // The refit's form of r1f_fill: a child without a sphere in it — an empty leaf (the second child of the root of a tree of <= leaf_max
 // spheres), or a subtree whose spheres all have non-finite centres — never passes: half extents -inf; its centre and its share of the pad
 // are its sibling's, as the builder writes a one-child root.  Both children empty: the box of a tree without spheres (all zero).
-R1_HD void r1f_fill_refit(const R1FillConst &T, const R1Box &b0, const R1Box &b1, float *p)
+R1F_HD void r1f_fill_refit(const R1FillConst &T, const R1Box &b0, const R1Box &b1, float *p)
 {
     const bool n0 = b0.empty(), n1 = b1.empty();
     if (!n0 && !n1)
@@ -204,7 +204,7 @@ R1_HD void r1f_fill_refit(const R1FillConst &T, const R1Box &b0, const R1Box &b1
 // A leaf's box from its spheres' current centres.  ref: the leaf's child reference; ids: the tree's leaf slots (2 per pair, active indices);
 // exact: [active][4] {cx cy cz radius_sq}; radii: [active][2] {bound radius, test radius}.  A sphere with a non-finite centre can never be
 // hit and is in no box.
-R1_HD void r1f_refit_leaf(uint32_t ref, const uint32_t *ids, const float *exact, const double *radii, R1Box &bx)
+R1F_HD void r1f_refit_leaf(uint32_t ref, const uint32_t *ids, const float *exact, const double *radii, R1Box &bx)
 {
     const uint32_t first = ref & 0x0FFFFFFFu, pairs = (ref >> 28) & 7u;
     bx.clear();
@@ -224,7 +224,7 @@ R1_HD void r1f_refit_leaf(uint32_t ref, const uint32_t *ids, const float *exact,
 
 // Node n's row (words 0..13) from its children's boxes, and its own box for its parent.  child_box: [2 x nodes] scratch entry of each child
 // (0xFFFFFFFF: an empty leaf); box: the scratch (entries of all children of n are final).  Returns the row's A.
-R1_HD float r1f_refit_node(const R1FillConst &T, uint32_t n, const uint32_t *child_box, R1Box *box, float *nodes)
+R1F_HD float r1f_refit_node(const R1FillConst &T, uint32_t n, const uint32_t *child_box, R1Box *box, float *nodes)
 {
     R1Box b0, b1;
     const uint32_t i0 = child_box[2 * (size_t)n + 0], i1 = child_box[2 * (size_t)n + 1];

@@ -62,14 +62,7 @@ __device__ __forceinline__ void cast_store(const R1CastArgs &A, const uint32_t i
 // A wave's next chunk of the ray array, from the launch's one cursor; false: none left.  Called by all 64 lanes, wave-uniform result.
 __device__ __forceinline__ bool cast_claim(const R1CastArgs &A, const int lane, uint32_t &q_next, uint32_t &q_end)
 {
-    uint32_t base = 0;
-    if (lane == 0)
-        base = atomicAdd(A.cursor, A.claim);
-    base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-    if (base >= A.n)
-        return false;
-    q_next = base, q_end = min(base + A.claim, A.n);
-    return true;
+    return chunk_claim(A.cursor, A.claim, A.n, lane, q_next, q_end);
 }
 
 } // namespace

@@ -154,6 +154,9 @@ struct r1_context
     uint32_t cast_cursor_next = 0;
     DevBuf cast_ws;            // r1_cast_rays: one chunk's rays and results (R1_CAST_CHUNK x 64 bytes)
     int cast_occupancy[8] = {0}; // blocks per CU of the cast kernels, [structure slot * 2 + big]
+    // path queries (r1_trace_rays*): one launch in flight per context
+    DevBuf trace_stack;        // the paths' attenuation stack, [max_bounces][threads of the launch] hit indices
+    int trace_occupancy[8] = {0}; // blocks per CU of the path-query kernels, [structure slot * 2 + big]
     // moving spheres (r1_update_centers*): the refit's tables — topology, uploaded once per r1_set_scene — and its scratch
     DevBuf refit_tab;          // uint32: scene -> active index, then R1RefitTopo's slot, leaf_ref, child_box, by_height
     DevBuf refit_radii;        // [active][2] fp64 {bound radius, test radius}

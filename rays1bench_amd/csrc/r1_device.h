@@ -302,6 +302,22 @@ struct R1CastArgs
 #define R1_CAST_LAUNCH_MAX (1u << 30) // rays per launch (32-bit ray indices with room for a claim beyond the end); longer arrays take several launches
 #define R1_CAST_CURSORS 64u           // cursors of a context, 128 bytes apart, taken in turn: launches in flight on different streams each have their own
 
+// Path queries (r1_trace_rays / r1_trace_rays_device, r1_trace_rays.hip): color() for caller-supplied rays, through the same walks and
+// the same shade_level.
+struct R1TraceRaysArgs
+{
+    R1TraceArgs t;          // what the walks and shade_level read: scene tables, bvh_lds_f4, bvh_depth, grid, max_bounces, gstack — the attenuation
+                            // stack, [max_bounces][gstride] hit indices (everything else zero)
+    const float4 *rays;     // [n][2] {ox oy oz -} {dx dy dz -}: the public r1_ray
+    const uint4 *seeds;     // [n] {scalar, lane0, lane1, lane2}: the public r1_sample_seed; null: r1_seed_sample(0, first + i, 0)
+    float4 *out;            // [n] {r, g, b, bit_cast<float>(rays)}: the public r1_radiance
+    uint32_t *cursor;       // the launch's ray cursor (zero before the launch): the waves claim `claim` rays at a time
+    uint32_t n;             // <= R1_CAST_LAUNCH_MAX
+    uint32_t claim;         // rays per claim (a multiple of 64)
+    uint32_t first;         // index within the call of the launch's ray 0 (seeds == null)
+    uint32_t gstride;       // threads of the launch
+};
+
 struct R1ResolveArgs
 {
     const float4 *samples;

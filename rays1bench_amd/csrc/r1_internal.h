@@ -70,6 +70,10 @@ hipError_t r1_launch_assemble(const void *blocks, void *rgb, int width, int heig
 hipError_t r1_launch_cast(const R1CastArgs *args, int variant, int big, int plain, int blocks, size_t dyn_lds, hipStream_t stream);
 hipError_t r1_cast_occupancy(int variant, int big, int plain, size_t dyn_lds, int *blocks_per_cu);
 
+// r1_trace_rays.hip; variant as for r1_launch_cast
+hipError_t r1_launch_trace_rays(const R1TraceRaysArgs *args, int variant, int big, int blocks, size_t dyn_lds, hipStream_t stream);
+hipError_t r1_trace_rays_occupancy(int variant, int big, size_t dyn_lds, int *blocks_per_cu);
+
 // r1_refit.hip: the kernels of r1_update_centers* 
 hipError_t r1_launch_refit_move(const R1RefitArgs *a, uint32_t first, uint32_t count, const float *x, const float *y, const float *z, hipStream_t stream);
 hipError_t r1_launch_refit(const R1RefitArgs *a, const uint32_t *height_off, uint32_t heights, hipStream_t stream);

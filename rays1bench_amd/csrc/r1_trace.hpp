@@ -1151,6 +1151,20 @@ __device__ __forceinline__ void cooperative_sweep(const R1DeviceScene &S, unsign
     }
 }
 
+// Ray queries (r1_cast.hip, r1_trace_rays.hip): a wave's next chunk of an array of n rays, `claim` at a time from the launch's one cursor;
+// false: none left.  Called by all 64 lanes, wave-uniform result.
+__device__ __forceinline__ bool chunk_claim(uint32_t *cursor, const uint32_t claim, const uint32_t n, const int lane, uint32_t &q_next, uint32_t &q_end)
+{
+    uint32_t base = 0;
+    if (lane == 0)
+        base = atomicAdd(cursor, claim);
+    base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+    if (base >= n)
+        return false;
+    q_next = base, q_end = min(base + claim, n);
+    return true;
+}
+
 // Attenuation stack.  Small scenes: packed in LDS, three 10-bit sphere indices per word.  Big
 // scenes (> 1023 active spheres): one u32 per entry in a global workspace laid out
 // [entry][global thread] (coalesced); its traffic is nothing next to a 100 k-sphere sweep.
