@@ -1,6 +1,6 @@
 // r1_context.h — what the files that implement the C-ABI on the HIP runtime share: the context, its device buffers, and the steps that
 // one of them defines and another calls.  Private to r1_capi.cpp (context, errors, timing), r1_scene.cpp (scene upload, moving spheres),
-// r1_frame.cpp (one frame, step by step), r1_render.cpp (the render entry points) and r1_queries.cpp (ray queries); C-linkage functions
+// r1_frame.cpp (one frame, step by step), r1_render.cpp (the render entry points) and r1_queries.cpp (ray and path queries); C-linkage functions
 // shared between files stay in r1_internal.h.
 #ifndef R1_CONTEXT_H
 #define R1_CONTEXT_H
@@ -152,11 +152,10 @@ struct r1_context
     DevBuf active_dev;         // active_to_scene on the device, uploaded once per r1_set_scene
     DevBuf cast_cursors;       // R1_CAST_CURSORS ray cursors, 128 bytes apart, taken in turn
     uint32_t cast_cursor_next = 0;
-    DevBuf cast_ws;            // r1_cast_rays: one chunk's rays and results (R1_CAST_CHUNK x 64 bytes)
-    int cast_occupancy[8] = {0}; // blocks per CU of the cast kernels, [structure slot * 2 + big]
+    DevBuf cast_ws;            // r1_cast_rays, r1_trace_rays: one chunk's rays, seeds and records (R1_CAST_CHUNK x 64 bytes)
+    int query_occupancy[R1_JOBS][8] = {{0}}; // blocks per CU of the query kernels, [job][structure slot * 2 + big]; follows the tree as `occupancy` does
     // path queries (r1_trace_rays*): one launch in flight per context
     DevBuf trace_stack;        // the paths' attenuation stack, [max_bounces][threads of the launch] hit indices
-    int trace_occupancy[8] = {0}; // blocks per CU of the path-query kernels, [structure slot * 2 + big]
     // moving spheres (r1_update_centers*): the refit's tables — topology, uploaded once per r1_set_scene — and its scratch
     DevBuf refit_tab;          // uint32: scene -> active index, then R1RefitTopo's slot, leaf_ref, child_box, by_height
     DevBuf refit_radii;        // [active][2] fp64 {bound radius, test radius}

@@ -287,7 +287,15 @@ struct R1WaveArgs
     int32_t level;        // color() depth this launch works on
 };
 
-// Ray queries (r1_cast_rays / r1_cast_rays_device, r1_cast.hip): caller-supplied rays through the trace kernels' walks.
+// The jobs of the query kernels (r1_query_kernels.hip): what a lane does with a caller-supplied ray
+enum
+{
+    R1_JOB_CAST = 0, // ray queries: closest hit or occlusion
+    R1_JOB_PATH = 1, // path queries: color()
+    R1_JOBS = 2
+};
+
+// Ray queries (r1_cast_rays / r1_cast_rays_device, r1_query_kernels.hip): caller-supplied rays through the trace kernels' walks.
 struct R1CastArgs
 {
     R1TraceArgs t;          // what the walks read: scene tables, bvh_lds_f4, bvh_depth, grid (everything else zero)
@@ -302,7 +310,7 @@ struct R1CastArgs
 #define R1_CAST_LAUNCH_MAX (1u << 30) // rays per launch (32-bit ray indices with room for a claim beyond the end); longer arrays take several launches
 #define R1_CAST_CURSORS 64u           // cursors of a context, 128 bytes apart, taken in turn: launches in flight on different streams each have their own
 
-// Path queries (r1_trace_rays / r1_trace_rays_device, r1_trace_rays.hip): color() for caller-supplied rays, through the same walks and
+// Path queries (r1_trace_rays / r1_trace_rays_device, r1_query_kernels.hip): color() for caller-supplied rays, through the same walks and
 // the same shade_level.
 struct R1TraceRaysArgs
 {

@@ -66,11 +66,11 @@ hipError_t r1_launch_put_cameras(void *dst, const float *cameras20, int n, hipSt
 hipError_t r1_launch_assemble(const void *blocks, void *rgb, int width, int height, int tile_w, int tile_h, int tiles_x, int num_shards, size_t shard_stride,
                               int n_frames, size_t frame_in, size_t frame_out, size_t total_offset, long long total_out, int want_total, hipStream_t stream);
 
-// r1_cast.hip; variant: R1_V_TREE, R1_V_GRID or R1_V_REFERENCE; plain: the tuning library's plain tree form
+// r1_query_kernels.hip, the cast job; variant: R1_V_TREE, R1_V_GRID or R1_V_REFERENCE; plain: the tuning library's plain tree form
 hipError_t r1_launch_cast(const R1CastArgs *args, int variant, int big, int plain, int blocks, size_t dyn_lds, hipStream_t stream);
 hipError_t r1_cast_occupancy(int variant, int big, int plain, size_t dyn_lds, int *blocks_per_cu);
 
-// r1_trace_rays.hip; variant as for r1_launch_cast
+// r1_query_kernels.hip, the path job; variant as for r1_launch_cast
 hipError_t r1_launch_trace_rays(const R1TraceRaysArgs *args, int variant, int big, int blocks, size_t dyn_lds, hipStream_t stream);
 hipError_t r1_trace_rays_occupancy(int variant, int big, size_t dyn_lds, int *blocks_per_cu);
 

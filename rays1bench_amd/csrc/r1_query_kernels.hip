@@ -1,0 +1,443 @@
+// r1_query_kernels.hip — the kernels of the ray queries (r1_cast_rays*) and of the path queries (r1_trace_rays*, §4.22):
+// caller-supplied rays through the trace kernels' walks (r1_trace.hpp: bvh_advance, grid_trace, sweep_reference, as they are).  There is
+// one loop per structure — box tree, uniform grid, reference form — and a JOB says what a lane does with a ray: how it is loaded and
+// when it is no ray at all, how its walk is seeded, what a complete walk leads to and which record is written.
+//   Args                     the kernel's argument struct; every job's has t, rays, cursor, n and claim
+//   waves(big)               the occupancy bound given to the compiler
+//   idle()                   the state of a lane without a ray (the walks are called by all 64 lanes)
+//   load(A, i)               ray i of the launch; false: the ray takes no walk
+//   seed(best)               where a walk's closest offer starts, if not at FLT_MAX
+//   O(), D()                 what the walk follows
+//   step(A, id, t, ..)       a walk is complete (id 0xFFFFFFFF: nothing hit); true: the ray's answer is known, false: O(), D() are the job's next walk
+//   finish(A, i, walked)     writes ray i's record and frees the lane; walked false: the ray took no walk (load said so)
+//   BOUNCES                  false: step() always returns true — one walk per ray.  The grid loop then drops its loop over walks and writes the record
+//                            of a ray without a walk behind the walk with the others: a second place that writes records costs the cast's grid kernels
+//                            6 VGPRs (profiles/r15/query_kernel_meta.txt)
+// The loops keep the ray's index themselves and hand it to finish(): a job holds no state that is unset before its first load.
+#include "r1_trace.hpp"
+#include "r1_internal.h"
+
+#ifndef R1_CAST_WAVES_SMALL
+#define R1_CAST_WAVES_SMALL 8 // waves per SIMD the cast kernels for small scenes are built for (registers, LDS: profiles/r10/cast.txt)
+#endif
+#ifndef R1_CAST_WAVES_BIG
+#define R1_CAST_WAVES_BIG 8
+#endif
+#ifndef R1_PATHQ_WAVES
+#define R1_PATHQ_WAVES 6 // the occupancy bound the compiler is given for the path jobs' tree and grid kernels.  They come to 58 .. 60 VGPRs under it, so eight
+#endif                   // waves per SIMD fit all the same; asked for eight, the compiler parks 12 .. 20 SGPRs in VGPR lanes (44 .. 48 v_readlane / v_writelane in
+                         // the loops) to reach the same register count (profiles/r14/trace_rays_kernel_meta.txt)
+
+namespace
+{
+
+__device__ __forceinline__ bool query_finite(const float v) { return (__float_as_uint(v) & 0x7F800000u) != 0x7F800000u; }
+
+} // namespace
+
+// ---- the cast job: Hitable::hit(Ray(o, d), 0.001f, t_max, &rec) of the reference (rayweek1.cpp:104-108, :152-339) ----------------------------
+// One 32-byte record per ray (R1_CAST_CLOSEST) or one byte (R1_CAST_ANY); no color().
+// t_max is strict (rayweek1.cpp:298, :307: `temp < t_max`).  A sphere's offer is fixed before the compare with t_max (the comment above
+// exact_offer), so the answer is the minimum offer, ties to the lowest index, IF it is < t_max.  The tree walk is seeded with best = t_max
+// so that it prunes what lies beyond; the walks' update rule (t < best) | (t == best & id < best_id) starts at best_id = 0xFFFFFFFF and
+// so admits an offer EQUAL to t_max — which is why every form ends in store's `best < t_max`: an admitted t == t_max is a miss, and
+// anything below it replaces it by the same rule.  The grid's walk starts at FLT_MAX and is filtered the same way; the reference form's
+// exact_test compares with the running t_max itself, strictly: seeded with the ray's t_max it IS rayweek1.cpp:284-314.
+// A ray with a non-finite origin or (normalised) direction, or a t_max that is NaN or <= 0.001, is a miss before any walk (load).
+struct R1CastJob
+{
+    typedef R1CastArgs Args;
+    static constexpr bool BOUNCES = false;
+    static constexpr int waves(const bool big) { return big ? R1_CAST_WAVES_BIG : R1_CAST_WAVES_SMALL; }
+
+    V3 o, d;
+    float t_max; // (+inf -> FLT_MAX)
+    uint32_t best_id; // the walk's answer (step)
+    float best;
+
+    __device__ __forceinline__ void idle() { o = mk(0, 0, 0), d = mk(0, 0, 1), t_max = FLT_MAX; }
+    __device__ __forceinline__ bool load(const Args &A, const uint32_t i)
+    {
+        const float4 a = A.rays[2 * (size_t)i], b = A.rays[2 * (size_t)i + 1];
+        o = mk(a.x, a.y, a.z);
+        d = vunit(mk(b.x, b.y, b.z)); // Ray::Ray, rayweek1.cpp:107
+        t_max = a.w > FLT_MAX ? FLT_MAX : a.w;
+        return query_finite(o.x) && query_finite(o.y) && query_finite(o.z) && query_finite(d.x) && query_finite(d.y) && query_finite(d.z) && t_max > 0.001f; // (false for a NaN t_max)
+    }
+    __device__ __forceinline__ void seed(float &best) const { best = t_max; }
+    __device__ __forceinline__ V3 O() const { return o; }
+    __device__ __forceinline__ V3 D() const { return d; }
+    __device__ __forceinline__ bool step(const Args &, const uint32_t id, const float t, uint32_t, int)
+    {
+        best_id = id, best = t;
+        return true;
+    }
+    __device__ __forceinline__ void finish(const Args &A, const uint32_t i, const bool walked) const { store(A, i, walked ? best_id : 0xFFFFFFFFu, best); }
+    // the hit record of rayweek1.cpp:316-322 (as shade_level computes hp and n), or the miss record; R1_CAST_ANY: one byte
+    __device__ __forceinline__ void store(const Args &A, const uint32_t ray, const uint32_t best_id, const float best) const
+    {
+        const bool hit = best_id != 0xFFFFFFFFu && best < t_max;
+        if (A.mode != 0u) // (wave-uniform)
+        {
+            ((uint8_t *)A.out)[ray] = hit ? 1 : 0;
+            return;
+        }
+        float4 r0 = make_float4(FLT_MAX, __int_as_float(-1), 0.0f, 0.0f), r1 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (hit)
+        {
+            const f4 e = ((const f4 *)A.t.scene.exact)[best_id];
+            const float inv_radius = ((const f4 *)A.t.scene.shade)[best_id].x;
+            const uint32_t scene_index = ((const r1_gu32 *)A.active_to_scene)[best_id];
+            const V3 hp = vadd(o, vscale(d, best));
+            const V3 n = vscale(vsub(hp, mk(e.x, e.y, e.z)), inv_radius);
+            r0 = make_float4(best, __uint_as_float(scene_index), hp.x, hp.y);
+            r1 = make_float4(hp.z, n.x, n.y, n.z);
+        }
+        float4 *dst = (float4 *)A.out + 2 * (size_t)ray;
+        dst[0] = r0, dst[1] = r1;
+    }
+};
+
+// ---- the path job: color(Ray(o, d), scene, 0) of the reference (rayweek1.cpp:517-534) with the caller's stream states -------------------------
+// A complete walk is one level of color(): shade_level, and then either the next walk of the same path or one 16-byte record
+// {r, g, b, color() invocations}.  Same walks and same shade_level as the trace kernels, so the same bits.
+// The attenuation stack is shade_level<true>'s: one hit index per entry in a global workspace laid out [entry][thread of the launch]
+// (coalesced; r1_queries.cpp sizes it max_bounces x threads).  It needs no LDS, so these kernels keep the cast kernels' LDS budget, and
+// it holds 32-bit indices, so small and big scenes share the code.
+// t_max of a ray is ignored: color() always passes FLT_MAX (rayweek1.cpp:519).  A ray with a non-finite origin or (normalised) direction runs no
+// color(): its record is {0, 0, 0, 0} (load's rule is the cast job's).  A stream state of zero is replaced before the path starts (r1_seed_guard, rays1_seed.h): xorshift32
+// stays at zero for ever and random_in_unit_sphere would never return.
+struct R1PathJob
+{
+    typedef R1TraceRaysArgs Args;
+    static constexpr bool BOUNCES = true;
+    static constexpr int waves(bool) { return R1_PATHQ_WAVES; }
+
+    Path p; // (p.k: the ray's index in the launch)
+    V3 col; // the path's radiance once step() has said that it ended
+
+    __device__ __forceinline__ void idle()
+    {
+        p.o = mk(0, 0, 0), p.d = mk(0, 0, 1);
+        p.s_scalar = p.s0 = p.s1 = p.s2 = 1u, p.k = 0u, p.depth = 0, p.sp = 0;
+    }
+    __device__ __forceinline__ bool load(const Args &A, const uint32_t i)
+    {
+        const float4 a = A.rays[2 * (size_t)i], b = A.rays[2 * (size_t)i + 1];
+        p.o = mk(a.x, a.y, a.z);
+        p.d = vunit(mk(b.x, b.y, b.z)); // Ray::Ray, rayweek1.cpp:107
+        r1_sample_seed sd;
+        if (A.seeds) // (wave-uniform)
+        {
+            const uint4 s = A.seeds[i];
+            sd.scalar = s.x, sd.lane0 = s.y, sd.lane1 = s.z, sd.lane2 = s.w;
+        }
+        else
+            sd = r1_seed_sample(0u, A.first + i, 0u);
+        sd = r1_seed_guard(sd);
+        p.s_scalar = sd.scalar, p.s0 = sd.lane0, p.s1 = sd.lane1, p.s2 = sd.lane2;
+        p.k = i, p.depth = 0, p.sp = 0;
+        return query_finite(p.o.x) && query_finite(p.o.y) && query_finite(p.o.z) && query_finite(p.d.x) && query_finite(p.d.y) && query_finite(p.d.z);
+    }
+    __device__ __forceinline__ void seed(float &) const {}
+    __device__ __forceinline__ V3 O() const { return p.o; }
+    __device__ __forceinline__ V3 D() const { return p.d; }
+    __device__ __forceinline__ bool step(const Args &A, const uint32_t best_id, const float best, const uint32_t gtid, const int tid)
+    {
+        const int hit = best_id != 0xFFFFFFFFu ? (int)best_id : -1;
+        return shade_level<true>(A.t, p, hit, best, nullptr, A.gstride, gtid, tid, col); // false: the scattered ray is in p, the next walk
+    }
+    __device__ __forceinline__ void finish(const Args &A, const uint32_t i, const bool walked) const
+    {
+        A.out[i] = walked ? make_float4(col.x, col.y, col.z, __uint_as_float(path_rays(p))) : make_float4(0.0f, 0.0f, 0.0f, 0.0f); // (no walk: no color())
+    }
+};
+
+// ---- LDS staging (as r1_trace_body stages its own copies) ---------------------------------------------------------------------------------
+namespace
+{
+
+// The workgroup's copy of the node table at dst.  Small scenes (LN): the whole table with 16-bit child references, the root step's code
+// in node 0's K slot and the flat tree's y slab in node 1's pad slots, where bvh_advance<LN> looks for them.  Big scenes: the
+// breadth-first top of the table; the rest goes through the vector L1.
+// (T by value: read through a reference, the root step's words are no longer kernel arguments the compiler may fetch ahead of the
+// tid tests, and the prologue comes out nine instructions longer than r1_trace_body's)
+template <bool LN>
+__device__ __forceinline__ void stage_nodes(const R1TraceArgs T, float4 *dst, const int tid)
+{
+    for (uint32_t i = (uint32_t)tid; i < T.bvh_lds_f4; i += R1_BLOCK)
+    {
+        float4 q = T.scene.bvh_nodes[i];
+        if (LN && (i & 3u) == 3u) // {A K child0 child1}: 16-bit child references
+            q.z = __uint_as_float(r1_ref16(__float_as_uint(q.z))), q.w = __uint_as_float(r1_ref16(__float_as_uint(q.w)));
+        dst[i] = q;
+    }
+    // (written by the threads that copied those rows: program order)
+    if (LN && tid == 3)
+        ((float *)dst)[13] = __uint_as_float(T.scene.bvh_root_leaf | (T.scene.bvh_flat_e >= 0.0f ? 4u : 0u));
+    if (LN && tid == 7 && T.scene.bvh_flat_e >= 0.0f)
+        ((float *)dst)[28] = T.scene.bvh_flat_m, ((float *)dst)[29] = T.scene.bvh_flat_e;
+    __syncthreads();
+}
+
+// small scenes: the workgroup's copy of the grid's 16-bit cell table and ids at dst
+__device__ __forceinline__ void stage_grid(const R1TraceArgs T, float4 *dst, const int tid)
+{
+    const R1GridCArgs *ga = (const R1GridCArgs *)(uintptr_t)T.grid;
+    const float4 *src = (const float4 *)(const r1_gu32 *)ga->tab;
+    const uint32_t n16 = ga->lds_bytes / 16u;
+    for (uint32_t i = (uint32_t)tid; i < n16; i += R1_BLOCK)
+        dst[i] = src[i];
+    __syncthreads();
+}
+
+} // namespace
+
+// ---- box tree ---------------------------------------------------------------------------------------------------------------------------
+// Persistent: the waves claim chunks of the ray array from one atomic cursor, and bvh_advance runs with CARRY — a lane whose walk is
+// complete hands it to its job and, once the job has written its record, takes the next ray while the longest walks of the wave go on
+// (the shape of the trace kernels' loop, r1_trace_body).  A job that goes on (a path that scattered) starts its next walk at the root
+// next to the walks the wave carries.  LDS: the traversal stack, then the node table (stage_nodes).
+template <class JOB, bool BIG>
+__global__ void __launch_bounds__(R1_BLOCK, JOB::waves(BIG)) r1_query_tree_kernel(const typename JOB::Args A)
+{
+    constexpr bool LN = !BIG;
+    typedef typename IdxType<!LN>::type TS; // traversal-stack entry: uint16_t with the LDS table, else uint32_t
+    extern __shared__ uint32_t s_trav[];
+    const int tid = (int)threadIdx.x, lane = tid & 63;
+    const uint32_t gtid = blockIdx.x * R1_BLOCK + threadIdx.x;
+    const size_t trav_words = (size_t)A.t.bvh_depth * R1_BLOCK * sizeof(TS) / 4;
+    const float4 *lnodes = (const float4 *)(s_trav + trav_words);
+    const uint32_t top = LN ? 0u : A.t.bvh_lds_f4 >> 2;
+    stage_nodes<LN>(A.t, (float4 *)(s_trav + trav_words), tid);
+
+    JOB J;
+    J.idle();
+    uint32_t ray = 0;
+    bool alive = false;
+    Trav tv;
+    trav_start(tv);
+    tv.cur = R1_BVH_DONE;
+    uint32_t q_next = 0, q_end = 0;
+    bool exhausted = false;
+    for (;;)
+    {
+        // ---- refill: the lanes without a ray take the next ones of the wave's chunk ----
+        unsigned long long need = __ballot(!alive);
+        while (need)
+        {
+            if (q_next == q_end)
+            {
+                if (exhausted)
+                    break;
+                if (!chunk_claim(A.cursor, A.claim, A.n, lane, q_next, q_end))
+                {
+                    exhausted = true;
+                    break;
+                }
+            }
+            const uint32_t avail = q_end - q_next;
+            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need, 0u));
+            if (!alive && rank < avail)
+            {
+                ray = q_next + rank;
+                alive = J.load(A, ray);
+                if (alive)
+                    trav_start(tv), J.seed(tv.best);
+                else
+                    J.finish(A, ray, false); // no walk; the lane asks again
+            }
+            q_next += min((uint32_t)__popcll(need), avail);
+            need = __ballot(!alive);
+        }
+        const unsigned long long live = __ballot(alive);
+        if (live == 0ull)
+            break;
+        // ---- walk with carry-over, then the job of the lanes whose walk is complete ----
+        bvh_advance<false, true, LN, TS>(A.t.scene, J.O(), J.D(), tv, (TS *)s_trav, tid, (uint32_t)__popcll(live), nullptr, lnodes, top);
+        if (alive && tv.cur == R1_BVH_DONE)
+        {
+            if (J.step(A, tv.best_id, tv.best, gtid, tid))
+            {
+                J.finish(A, ray, true);
+                alive = false;
+            }
+            else
+                trav_start(tv), J.seed(tv.best);
+        }
+    }
+}
+
+// ---- uniform grid -----------------------------------------------------------------------------------------------------------------------
+// grid_trace is a complete walk per call, so a wave works its chunk off 64 rays at a time; a job that BOUNCES loops over the walks of
+// those 64 until the last of them has ended.  Small scenes: the grid's 16-bit table in LDS behind the fallback's traversal stack; rays
+// too far for the grid take the tree walk from the global table (root_leaf = 0 in the arguments: it starts at the root), exactly as the
+// grid trace kernel arranges it.
+template <class JOB, bool BIG>
+__global__ void __launch_bounds__(R1_BLOCK, JOB::waves(BIG)) r1_query_grid_kernel(const typename JOB::Args A)
+{
+    extern __shared__ uint32_t s_trav[];
+    const int tid = (int)threadIdx.x, lane = tid & 63;
+    const uint32_t gtid = blockIdx.x * R1_BLOCK + threadIdx.x;
+    const size_t gtrav_words = (size_t)A.t.bvh_depth * R1_BLOCK;
+    const uint16_t *ltab = (const uint16_t *)(s_trav + gtrav_words);
+    if (!BIG)
+        stage_grid(A.t, (float4 *)(s_trav + gtrav_words), tid);
+    uint32_t q_next = 0, q_end = 0;
+    for (;;)
+    {
+        if (q_next == q_end && !chunk_claim(A.cursor, A.claim, A.n, lane, q_next, q_end))
+            break;
+        const uint32_t ray = q_next + (uint32_t)lane;
+        const bool mine = ray < q_end;
+        q_next = min(q_next + 64u, q_end);
+        JOB J;
+        J.idle();
+        bool alive = false;
+        if (mine)
+        {
+            alive = J.load(A, ray);
+            if (JOB::BOUNCES && !alive)
+                J.finish(A, ray, false); // (!BOUNCES: written below)
+        }
+        while (!JOB::BOUNCES || __ballot(alive) != 0ull)
+        {
+            float best;
+            uint32_t best_id;
+            const bool fb = grid_trace<false, !BIG>(A.t, (R1GridCArgs *)(uintptr_t)A.t.grid, alive, J.O(), J.D(), best, best_id, ltab, tid, nullptr);
+            if (__ballot(fb) != 0ull)
+            {
+                // fallback: the tree walk from scratch, exact for any origin; the outliers' offer is kept (the tree presents them again)
+                Trav fv;
+                trav_start(fv);
+                fv.best = best, fv.best_id = best_id;
+                if (!fb)
+                    fv.cur = R1_BVH_DONE;
+                bvh_advance<false, false, false, uint32_t>(A.t.scene, J.O(), J.D(), fv, s_trav, tid, 64u, nullptr, nullptr);
+                best = fv.best, best_id = fv.best_id;
+            }
+            if ((JOB::BOUNCES ? alive : mine) && J.step(A, best_id, best, gtid, tid))
+            {
+                J.finish(A, ray, JOB::BOUNCES || alive); // (BOUNCES: only a lane that is alive comes here)
+                alive = false;
+            }
+            if (!JOB::BOUNCES)
+                break; // (one walk per ray: no vote)
+        }
+    }
+}
+
+// ---- reference form: every active sphere through exact_test in index order, walk by walk (the reference's own loop; the on-device cross-check) ----
+template <class JOB>
+__global__ void __launch_bounds__(R1_BLOCK) r1_query_reference_kernel(const typename JOB::Args A)
+{
+    const uint32_t stride = gridDim.x * R1_BLOCK;
+    const uint32_t gtid = blockIdx.x * R1_BLOCK + threadIdx.x;
+    for (uint32_t i = gtid; i < A.n; i += stride)
+    {
+        JOB J;
+        const bool alive = J.load(A, i);
+        while (alive)
+        {
+            float t_hit = FLT_MAX;
+            int hit = -1;
+            J.seed(t_hit);
+            sweep_reference(A.t.scene, J.O(), J.D(), t_hit, hit);
+            if (J.step(A, (uint32_t)hit, hit >= 0 ? t_hit : FLT_MAX, gtid, (int)threadIdx.x))
+                break;
+        }
+        J.finish(A, i, alive);
+    }
+}
+
+#ifdef R1_TUNING
+// The plain form of the tree cast, for measuring only (R1_CAST_PLAIN=1 in the tuning library; tools/cast_bench.py): r1_wf_intersect's —
+// grid-stride, one complete walk per ray from the table in global memory, the longest of 64 walks sets the wave's trip count.
+__global__ void __launch_bounds__(R1_BLOCK) r1_cast_plain_kernel(const R1CastArgs A)
+{
+    extern __shared__ uint32_t s_trav[];
+    const uint32_t stride = gridDim.x * R1_BLOCK;
+    const uint32_t rounds = (A.n + stride - 1) / stride; // every lane makes the same number of trips (bvh_advance is called by all 64)
+    for (uint32_t r = 0; r < rounds; ++r)
+    {
+        const uint32_t i = r * stride + blockIdx.x * R1_BLOCK + threadIdx.x;
+        R1CastJob J;
+        J.idle();
+        bool alive = false;
+        if (i < A.n)
+            alive = J.load(A, i);
+        Trav tv;
+        trav_start(tv);
+        J.seed(tv.best);
+        if (!alive)
+            tv.cur = R1_BVH_DONE;
+        bvh_advance<false, false, false, uint32_t>(A.t.scene, J.O(), J.D(), tv, s_trav, (int)threadIdx.x, 64u, nullptr, nullptr);
+        J.step(A, tv.best_id, tv.best, 0u, 0);
+        if (i < A.n)
+            J.finish(A, i, alive);
+    }
+}
+#endif
+
+// ---- launchers (called from r1_queries.cpp) --------------------------------------------------------------------------------------------------
+// variant: R1_V_TREE, R1_V_GRID or R1_V_REFERENCE — the structure the rays walk; null: no such kernel
+template <class JOB>
+static const void *query_kernel(const int variant, const int big)
+{
+    if (variant == R1_V_REFERENCE)
+        return (const void *)r1_query_reference_kernel<JOB>;
+    if (variant == R1_V_GRID)
+        return big ? (const void *)r1_query_grid_kernel<JOB, true> : (const void *)r1_query_grid_kernel<JOB, false>;
+    if (variant == R1_V_TREE)
+        return big ? (const void *)r1_query_tree_kernel<JOB, true> : (const void *)r1_query_tree_kernel<JOB, false>;
+    return nullptr;
+}
+
+// plain: the tuning library's plain tree form of the cast job
+static const void *query_kernel(const int job, const int variant, const int big, const int plain)
+{
+#ifdef R1_TUNING
+    if (plain && job == R1_JOB_CAST && variant == R1_V_TREE)
+        return (const void *)r1_cast_plain_kernel;
+#endif
+    if (plain)
+        return nullptr;
+    return job == R1_JOB_CAST ? query_kernel<R1CastJob>(variant, big) : job == R1_JOB_PATH ? query_kernel<R1PathJob>(variant, big) : nullptr;
+}
+
+// One launcher and one occupancy query, keyed by job, structure and big; args: the job's argument struct.  The C names below are their
+// typed fronts for r1_queries.cpp.
+static hipError_t query_launch(int job, const void *args, int variant, int big, int plain, int blocks, size_t dyn_lds, hipStream_t stream)
+{
+    const void *kernel = query_kernel(job, variant, big, plain);
+    if (!kernel)
+        return hipErrorInvalidValue;
+    void *argv[1] = {(void *)args};
+    (void)hipLaunchKernel(kernel, dim3(blocks), dim3(R1_BLOCK), argv, dyn_lds, stream);
+    return hipGetLastError(); // (a launch's error, read and cleared as behind hipLaunchKernelGGL)
+}
+
+static hipError_t query_occupancy(int job, int variant, int big, int plain, size_t dyn_lds, int *blocks_per_cu)
+{
+    const void *kernel = query_kernel(job, variant, big, plain);
+    if (!kernel)
+        return hipErrorInvalidValue;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, kernel, R1_BLOCK, dyn_lds);
+}
+
+extern "C" hipError_t r1_launch_cast(const R1CastArgs *args, int variant, int big, int plain, int blocks, size_t dyn_lds, hipStream_t stream)
+{
+    return query_launch(R1_JOB_CAST, args, variant, big, plain, blocks, dyn_lds, stream);
+}
+extern "C" hipError_t r1_cast_occupancy(int variant, int big, int plain, size_t dyn_lds, int *blocks_per_cu)
+{
+    return query_occupancy(R1_JOB_CAST, variant, big, plain, dyn_lds, blocks_per_cu);
+}
+extern "C" hipError_t r1_launch_trace_rays(const R1TraceRaysArgs *args, int variant, int big, int blocks, size_t dyn_lds, hipStream_t stream)
+{
+    return query_launch(R1_JOB_PATH, args, variant, big, 0, blocks, dyn_lds, stream);
+}
+extern "C" hipError_t r1_trace_rays_occupancy(int variant, int big, size_t dyn_lds, int *blocks_per_cu)
+{
+    return query_occupancy(R1_JOB_PATH, variant, big, 0, dyn_lds, blocks_per_cu);
+}

@@ -174,8 +174,7 @@ extern "C" int r1_set_scene(r1_context *c, const r1_scene *s, const r1_camera *c
     c->bvh_flat_m = bvh.flat_axis == 1 ? bvh.flat_m : 0.0f, c->bvh_flat_e = bvh.flat_axis == 1 ? bvh.flat_e : -1.0f;
     for (int &o : c->occupancy)
         o = 0; // the tree kernels' LDS footprint follows the tree (depth of the traversal stack, size of the node table)
-    for (int &o : c->cast_occupancy)
-        o = 0;
+    memset(c->query_occupancy, 0, sizeof(c->query_occupancy));
     c->n_groups = sw.n_groups;
     c->n_multi = sw.n_multi;
 

@@ -1151,7 +1151,7 @@ __device__ __forceinline__ void cooperative_sweep(const R1DeviceScene &S, unsign
     }
 }
 
-// Ray queries (r1_cast.hip, r1_trace_rays.hip): a wave's next chunk of an array of n rays, `claim` at a time from the launch's one cursor;
+// Ray and path queries (r1_query_kernels.hip): a wave's next chunk of an array of n rays, `claim` at a time from the launch's one cursor;
 // false: none left.  Called by all 64 lanes, wave-uniform result.
 __device__ __forceinline__ bool chunk_claim(uint32_t *cursor, const uint32_t claim, const uint32_t n, const int lane, uint32_t &q_next, uint32_t &q_end)
 {
@@ -1870,6 +1870,7 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
     // (small scenes) the workgroup's copy of the grid's 16-bit cell table and ids
     const size_t gtrav_words = VARIANT == R1_V_GRID ? (size_t)A.bvh_depth * R1_BLOCK : 0;
     const uint16_t *ltab = (const uint16_t *)(s_trav + gtrav_words);
+    // (this staging and the node table's below stay inline: moved into the query kernels' stage_grid / stage_nodes they change these kernels' code)
     if (VARIANT == R1_V_GRID && !BIG)
     {
         float4 *dst = (float4 *)(s_trav + gtrav_words);

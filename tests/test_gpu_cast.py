@@ -1,4 +1,4 @@
-"""GPU tests of the ray queries (r1_cast_rays / r1_cast_rays_device): the cast kernels (r1_cast.hip) against the
+"""GPU tests of the ray queries (r1_cast_rays / r1_cast_rays_device): the cast kernels (r1_query_kernels.hip) against the
 reference's own Hitable::hit through tests/golden/cast_*.bin, and against r1_cast_rays_host — which tests/test_cast_host.py pins to the
 same fixtures — on large seeded ray sets.  The box tree, the uniform grid and the reference form must return the same bytes.  Every
 comparison is exact: the contract is bit identity."""

@@ -1,4 +1,4 @@
-"""GPU test of the ray queries (r1_cast.hip) over the scenes of tests/edge_scenes.py, small and big: 4096 rays per scene — the frame's
+"""GPU test of the ray queries (r1_query_kernels.hip) over the scenes of tests/edge_scenes.py, small and big: 4096 rays per scene — the frame's
 primary rays, scatter rays from their hit points and a sixteenth with t_max at the hit's own t and at its two fp32 neighbours
 (edge_scenes.cast_rays) — CLOSEST and ANY through the box tree, the uniform grid and the reference form.  Every answer must equal
 r1_cast_rays_host's (every ray against every sphere, pinned to the reference by tests/test_cast_host.py), byte for byte."""

@@ -1,4 +1,4 @@
-"""GPU tests of the path queries (r1_trace_rays / r1_trace_rays_device): the path-query kernels (r1_trace_rays.hip)
+"""GPU tests of the path queries (r1_trace_rays / r1_trace_rays_device): the path-query kernels (r1_query_kernels.hip)
 against the reference's own color() through tests/golden/samples_*.bin, against r1_render_samples for whole frames, and against
 r1_trace_rays_host — which tests/test_trace_rays_host.py pins to the same fixtures and to the oracle — everywhere else.  The box tree, the
 uniform grid and the reference form must return the same bytes.  Every comparison is exact: bytes of r, g, b and equality of rays.
