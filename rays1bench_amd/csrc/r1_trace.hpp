@@ -115,13 +115,12 @@ __device__ __forceinline__ void fresh_args(R1ArgWords &u)
     fresh_args(L##_words);                                                                                                                \
     const R1TraceArgs &L = L##_words.a;
 
-// Correctly rounded sqrt / division.  NOT __fsqrt_rn/__fdiv_rn: without
+// Correctly rounded sqrt.  NOT __fsqrt_rn: without
 // OCML_BASIC_ROUNDED_OPERATIONS hipcc maps __fsqrt_rn to the approximate v_sqrt_f32.  Plain
 // sqrtf() and `/` are IEEE under -fhip-fp32-correctly-rounded-divide-sqrt (set in the Makefile).
-// The hit tests take their roots through r1_sqrt_exact (r1_exact_math.h): the same bits from half the instructions wherever no
+// The hit tests and refract take their roots through r1_sqrt_exact (r1_exact_math.h): the same bits from half the instructions wherever no
 // lane of the wave holds a tiny, zero, negative, infinite or NaN input, the compiler's function for the wave otherwise.
 __device__ __forceinline__ float ieee_sqrt(float x) { return __builtin_sqrtf(x); }
-__device__ __forceinline__ float ieee_div(float a, float b) { return a / b; }
 
 __device__ __forceinline__ V3 mk(float x, float y, float z)
 {
@@ -135,8 +134,12 @@ __device__ __forceinline__ V3 vscale(V3 a, float s) { return mk(a.x * s, a.y * s
 __device__ __forceinline__ V3 vneg(V3 a) { return mk(-a.x, -a.y, -a.z); }
 // mymath.h:205-207: sum(a*b) = (x + y) + z
 __device__ __forceinline__ float vdot(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-// mymath.h:211: v * (1.0f / length(v)); Ray::Ray normalises every direction (rayweek1.cpp:107)
-__device__ __forceinline__ V3 vunit(V3 v) { return vscale(v, ieee_div(1.0f, ieee_sqrt(vdot(v, v)))); }
+// mymath.h:211: v * (1.0f / length(v)); Ray::Ray normalises every direction (rayweek1.cpp:107).  The reciprocal length has the bits of
+// 1.0f / ieee_sqrt(x) for every x, from one v_rsq_f32 (r1_exact_math.h): vunit is branch-free (the refill
+// loop's site takes no new control flow without spilling the camera), vunit_guarded decides once per wave and belongs where the
+// lanes of a branch normalise together (the ballot runs under the branch's exec mask).
+__device__ __forceinline__ V3 vunit(V3 v) { return vscale(v, r1_rlen_total(vdot(v, v))); }
+__device__ __forceinline__ V3 vunit_guarded(V3 v) { return vscale(v, r1_rlen_guarded(vdot(v, v), __builtin_amdgcn_ballot_w64(true))); }
 __device__ __forceinline__ V3 ld3(const float *p) { return mk(p[0], p[1], p[2]); }
 
 // mymath.h:17-25
@@ -1459,14 +1462,14 @@ __device__ __forceinline__ bool shade_level(const R1TraceArgs &A, Path &p, const
                 V3 refracted = mk(0, 0, 0);
                 if (discriminant > 0)
                 {
-                    refracted = vsub(vscale(vsub(p.d, vscale(outward, dt)), ni_over_nt), vscale(outward, ieee_sqrt(discriminant)));
+                    refracted = vsub(vscale(vsub(p.d, vscale(outward, dt)), ni_over_nt), vscale(outward, r1_sqrt_exact(discriminant, true)));
                     // schlick rayweek1.cpp:454-459; r0 = ((1 - ref)/(1 + ref))^2 comes from the host
                     const float r0 = mt.w;
                     reflect_prob = r0 + (1.0f - r0) * pow5(1.0f - cosine);
                 }
                 dir = (rand01(p.s_scalar) < reflect_prob) ? reflected : refracted;
             }
-            const V3 nd = vunit(dir);
+            const V3 nd = vunit_guarded(dir);
             p.o = hp;
             p.d = nd;
             if (type == 2u || type == 0u || vdot(nd, n) > 0)
