@@ -90,6 +90,7 @@ struct r1_context
     uint32_t wave_log_waves = 0;
     uint32_t n_bvh_nodes = 0, n_bvh_leaves = 0;
     int bvh_depth = 0;
+    uint32_t bvh_leaf_pairs = 0; // the most sphere pairs in a leaf (R1_BVH_LEAF / 2 unless a tuning knob builds larger leaves)
     float bvh_centre[3] = {0, 0, 0};
     int bvh_pad_local = 0;
     int bvh_root_leaf = 0;

@@ -177,7 +177,8 @@ struct R1DeviceScene
     // centre m_i and half extent e_i, inflated per ray by pad = A |o - bvh_centre|^2 + K.  Child
     // reference: bit 31 clear = inner node index; set = leaf, bits 28..30 number of sphere PAIRS,
     // bits 0..27 first pair of bvh_prims (2 float4 per pair {cx_a cx_b cy_a cy_b} {cz_a cz_b rsq_a
-    // rsq_b}) / bvh_ids (2 active indices per pair).  Node 0 is the root.
+    // rsq_b}) / bvh_ids (2 active indices per pair).  Node 0 is the root.  Behind the last pair of either table stands a sentinel
+    // (one pair of radius_sq = -inf; two words 0xFFFFFFFF): a leaf test reads one pair past a leaf that ends on an odd pair (r1_scene.cpp).
     const float4 *bvh_nodes;
     const float4 *bvh_prims;
     const uint32_t *bvh_ids;

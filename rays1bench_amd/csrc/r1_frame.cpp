@@ -100,13 +100,14 @@ struct Choice
 
 // Big-scene kernels — 32-bit hit indices, the attenuation stack in a global workspace (the packed LDS stack holds 10-bit indices) and the
 // tree's node table through the vector L1: > 1023 hittable spheres, or — tree kernels — a node table too large for LDS, or a tree whose pad
-// is measured per node (small spheres: only the kernels that walk the table in global memory carry that arm, bvh_advance); grid kernels:
+// is measured per node (small spheres: only the kernels that walk the table in global memory carry that arm, bvh_advance), or a tree with
+// leaves of more than two sphere pairs (a tuning library's R1_BVH_LEAF: only those kernels keep the pair loop of a leaf visit); grid kernels:
 // tables too large for LDS — the small-scene grid kernel's fallback reads the tree from global memory, any tree will do — and PIXEL mode
 // (`grid_pixel`), which the grid runs through its big-scene kernel only: the small one's PIXEL build would spill.  Tried for the tree kernel
 // on small scenes too (more workgroups per CU): 15 % slower.  A grid's answer holds after ensure_grid.
 bool big_scene(const r1_context *c, bool tree, bool grid, bool grid_pixel)
 {
-    return c->n_active > R1_MAX_ACTIVE_10BIT || (tree && (c->n_bvh_nodes > R1_NODES_LDS_MAX || c->bvh_pad_local)) || (grid && (!c->grid_small || grid_pixel));
+    return c->n_active > R1_MAX_ACTIVE_10BIT || (tree && (c->n_bvh_nodes > R1_NODES_LDS_MAX || c->bvh_pad_local || c->bvh_leaf_pairs > 2u)) || (grid && (!c->grid_small || grid_pixel));
 }
 
 // The public enum's numbers are the internal ones.  DEFAULT = the box tree (a property of the build, see above); PREFILTER always forces

@@ -4,6 +4,7 @@
 #include <math.h>
 #include <string.h>
 
+#include <algorithm>
 #include <cmath>
 #include <vector>
 
@@ -98,10 +99,21 @@ extern "C" int r1_set_scene(r1_context *c, const r1_scene *s, const r1_camera *c
     // leaf_quad fetches a sphere index speculatively for lanes that hold no flagged sphere (slot 3 of the step, whatever the step's
     // pair count): two sentinel words behind the last pair keep that read inside the table
     bvh.ids.resize(bvh.ids.size() + 2, 0xFFFFFFFFu);
+    // ... and the second PAIR of every leaf, whatever the leaf's pair count: behind the table's last leaf, which may hold
+    // one pair, that is this sentinel pair — centres 0, both radius_sq = -inf like an odd sphere's partner.  Not part of the tree: no leaf
+    // reference counts it, no slot of the refit's tables points at it (r1_bvh_topology is computed from the ids in front of it).
+    {
+        const float sentinel[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, -INFINITY, -INFINITY};
+        bvh.prims.insert(bvh.prims.end(), sentinel, sentinel + 8);
+    }
 
     // what a refit needs besides the tree (r1_update_centers*): topology and the radii, once per scene
     R1RefitTopo topo;
     r1_bvh_topology(bvh, na, topo);
+    // the most pairs a leaf holds: the kernels that keep the node table in LDS test a leaf in ONE step of two pairs (r1_frame.cpp big_scene)
+    uint32_t leaf_pairs = 0;
+    for (uint32_t ref : topo.leaf_ref)
+        leaf_pairs = std::max(leaf_pairs, (ref >> 28) & 7u);
     c->scene_to_active.assign(s->count ? s->count : 1, 0xFFFFFFFFu);
     for (uint32_t a = 0; a < na; ++a)
         c->scene_to_active[c->active_to_scene[a]] = a;
@@ -166,6 +178,7 @@ extern "C" int r1_set_scene(r1_context *c, const r1_scene *s, const r1_camera *c
     c->n_bvh_nodes = (uint32_t)(bvh.nodes.size() / 16);
     c->n_bvh_leaves = bvh.n_leaves;
     c->bvh_depth = bvh.max_depth;
+    c->bvh_leaf_pairs = leaf_pairs;
     for (int k = 0; k < 3; ++k)
         c->bvh_centre[k] = bvh.centre[k];
     c->bvh_pad_local = bvh.pad_local;

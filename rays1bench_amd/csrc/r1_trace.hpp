@@ -720,23 +720,30 @@ __device__ __forceinline__ bool bvh_box(const float mx, const float my, const fl
 // four spheres instead of four times (it used to cost 155 VALU instructions per pair, two thirds of them
 // pass 2).  Same offers as exact_offer, same update rule (minimum offer, ties to the lowest sphere index).
 // `pairs` = 1 or 2; an odd sphere's partner has radius_sq = -inf (discriminant -inf: never flagged).
+// BOTH pairs are fetched and evaluated whatever `pairs` says: a one-pair leaf reads the first pair of the next leaf in
+// the table — or, behind the last leaf, the sentinel pair r1_scene.cpp appends — and `mask` keeps those two slots from ever being flagged,
+// whatever their discriminants come out as (finite, inf, NaN).  The branch around the second fetch cost eight register copies (pair A
+// into pair B's registers), an exec-mask region and the compare in front of every leaf, on scenes whose leaves nearly all hold two pairs.
 __device__ __forceinline__ void leaf_quad(const float4 *__restrict__ prims, const uint32_t *__restrict__ ids, const uint32_t first,
                                           const uint32_t pairs, const V3 o, const V3 d, float &best, uint32_t &best_id)
 {
-    const float4 a0 = prims[2 * (size_t)first], a1 = prims[2 * (size_t)first + 1];
-    float4 b0 = a0, b1 = a1;
-    if (pairs > 1u)
-        b0 = prims[2 * (size_t)first + 2], b1 = prims[2 * (size_t)first + 3];
     float nb[4], ds[4];
 #pragma unroll
-    for (int q = 0; q < 4; ++q)
+    for (int h = 0; h < 2; ++h)
     {
-        const float4 p0 = q < 2 ? a0 : b0, p1 = q < 2 ? a1 : b1;
-        const float cx = (q & 1) ? p0.y : p0.x, cy = (q & 1) ? p0.w : p0.z, cz = (q & 1) ? p1.y : p1.x, rsq = (q & 1) ? p1.w : p1.z;
-        const float cox = cx - o.x, coy = cy - o.y, coz = cz - o.z;
-        nb[q] = __fmaf_rn(coz, d.z, __fmaf_rn(coy, d.y, cox * d.x));
-        const float c = __fmaf_rn(coz, coz, __fmaf_rn(coy, coy, cox * cox)) - rsq;
-        ds[q] = nb[q] * nb[q] - c;
+        if (h)
+            __builtin_amdgcn_sched_barrier(0); // pair B's arithmetic stays behind pair A's: left to mix them, hipcc spills in the 72-register builds (all four loads still issue together)
+        const float4 p0 = prims[2 * (size_t)first + 2 * h], p1 = prims[2 * (size_t)first + 2 * h + 1];
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+        {
+            const int q = 2 * h + s;
+            const float cx = s ? p0.y : p0.x, cy = s ? p0.w : p0.z, cz = s ? p1.y : p1.x, rsq = s ? p1.w : p1.z;
+            const float cox = cx - o.x, coy = cy - o.y, coz = cz - o.z;
+            nb[q] = __fmaf_rn(coz, d.z, __fmaf_rn(coy, d.y, cox * d.x));
+            const float c = __fmaf_rn(coz, coz, __fmaf_rn(coy, coy, cox * cox)) - rsq;
+            ds[q] = nb[q] * nb[q] - c;
+        }
     }
     // bit q of `mask`: slot q's discriminant has a clear sign bit (rayweek1.cpp:204).  The four sign bits are shifted together with
     // v_alignbit_b32 ((hi:lo) >> 31 = hi << 1 | sign of lo): 4 + 3 instructions instead of 12 for compare + select + or per slot.
@@ -749,8 +756,11 @@ __device__ __forceinline__ void leaf_quad(const float4 *__restrict__ prims, cons
     // computes on slot 3's numbers and is kept from the update by `have`), and the sphere's index is fetched before its offer is
     // known to count.  The branched form (only lanes with a flagged sphere, the index only for an offer in range) cost seven register
     // moves per trip for the loop-carried best / best_id and two exec-mask regions.
-    unsigned long long flagged;
-    while ((flagged = __builtin_amdgcn_ballot_w64(mask != 0u)) != 0ull) // wave-uniform
+    // A guarded do-while on purpose: written as `while (ballot)`, the loop-carried best / best_id went through a second register pair —
+    // two copies in front of the loop and two more in every trip; in this form the selects below write the caller's registers.
+    unsigned long long flagged = __builtin_amdgcn_ballot_w64(mask != 0u); // wave-uniform
+    if (flagged != 0ull)
+    do
     {
         const bool have = mask != 0u;
         const uint32_t q = (uint32_t)__builtin_ctz(mask | 8u); // the lowest flagged slot; 3 for a lane that has none left
@@ -765,7 +775,8 @@ __device__ __forceinline__ void leaf_quad(const float4 *__restrict__ prims, cons
         const bool upd = have & (t > 0.001f) & (t < FLT_MAX) & ((t < best) | ((t == best) & (id < best_id)));
         best = upd ? t : best;
         best_id = upd ? id : best_id;
-    }
+        flagged = __builtin_amdgcn_ballot_w64(mask != 0u);
+    } while (flagged != 0ull);
 }
 
 // Traversal-stack entries.  Big scenes: the 32-bit child reference as it is.  Small scenes (the kernels that keep the node table in LDS:
@@ -1011,6 +1022,20 @@ __device__ __forceinline__ void bvh_advance(const R1DeviceScene &S, const V3 o, 
             // leaf: `cnt` PAIRS of spheres {cx_a cx_b cy_a cy_b} {cz_a cz_b rsq_a rsq_b}; an odd
             // sphere's partner has radius_sq = -inf (discriminant -inf: never offers a hit)
             const uint32_t first = cur & INDEX_MASK, cnt = (cur >> COUNT_SHIFT) & 7u;
+            if (LN)
+            {
+                // The LDS walks' trees have leaves of at most R1_BVH_LEAF = 4 spheres = 2 pairs (r1_frame.cpp big_scene sends any other tree
+                // through the !LN kernels): one leaf_quad call, no pair loop, and a 12-bit `first` the sphere-index fetch can add to a scalar base.
+                static_assert(R1_BVH_LEAF <= 4, "the LDS walks test a leaf with ONE leaf_quad call: at most two pairs");
+                if (STATS)
+                {
+                    wstat[5] += (unsigned long long)cnt, wstat[16] += 1ull;
+                    if ((tid & 63) == __ffsll((long long)__ballot(1)) - 1)
+                        wstat[3] += 1;
+                }
+                leaf_quad(prims, ids, first, cnt, o, d, best, best_id);
+            }
+            else
             for (uint32_t j = 0; j < cnt; j += 2u)
             {
                 const uint32_t take = cnt - j < 2u ? 1u : 2u;
@@ -2132,15 +2157,15 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
         // a 10-spp frame when the wave shares its SIMD with three others).  Waves that carry a
         // deep path ask for issue priority so that the chain finishes before the queue runs dry.
         {
-            const int prio = __ballot(alive && p.depth >= 36) ? 3 : __ballot(alive && p.depth >= 24) ? 2 : __ballot(alive && p.depth >= 12) ? 1 : 0;
-            if (prio == 3)
-                __builtin_amdgcn_s_setprio(3);
-            else if (prio == 2)
-                __builtin_amdgcn_s_setprio(2);
-            else if (prio == 1)
-                __builtin_amdgcn_s_setprio(1);
-            else
+            // (one vote first: in most iterations no lane is 12 deep, and the two deeper votes are taken only behind it)
+            if (__ballot(alive && p.depth >= 12) == 0ull)
                 __builtin_amdgcn_s_setprio(0);
+            else if (__ballot(alive && p.depth >= 36) != 0ull)
+                __builtin_amdgcn_s_setprio(3);
+            else if (__ballot(alive && p.depth >= 24) != 0ull)
+                __builtin_amdgcn_s_setprio(2);
+            else
+                __builtin_amdgcn_s_setprio(1);
         }
         if (STATS)
         {
