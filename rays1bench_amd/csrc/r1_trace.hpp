@@ -50,6 +50,7 @@
 #include "r1_device.h"
 #include "r1_grid_dda.h"
 #include "r1_exact_math.h"
+#include "r1_scatter.h"
 #include "../../include/rays1_seed.h"
 
 #pragma clang fp contract(off)
@@ -193,14 +194,6 @@ __device__ __forceinline__ V3 random_in_unit_sphere(Path &p)
         r = mk(rand02_minus1(p.s0), rand02_minus1(p.s1), rand02_minus1(p.s2));
     } while (vdot(r, r) >= 1);
     return r;
-}
-
-// exactly rounded x^5 (the reference calls powf(x, 5), rayweek1.cpp:458)
-__device__ __forceinline__ float pow5(float x)
-{
-    double d = (double)x;
-    double d2 = d * d;
-    return (float)(d2 * d2 * d);
 }
 
 // ---- the exact ray/sphere test: pass 1 + pass 2 of Hitable::hit for ONE sphere -----------
@@ -1449,50 +1442,30 @@ __device__ __forceinline__ bool shade_level(const R1TraceArgs &A, Path &p, const
                 rius = random_in_unit_sphere(p);
             V3 dir; // un-normalised scattered direction; Ray::Ray normalises (rayweek1.cpp:107)
             if (type == 0u)
-            {
-                // Lambertian::scatter rayweek1.cpp:403-409
-                const V3 target = vadd(vadd(hp, n), rius);
-                dir = vsub(target, hp);
-            }
-            else if (type == 1u)
-            {
-                // Metal::scatter rayweek1.cpp:427-433; reflect :414-417
-                const V3 refl = vsub(p.d, vscale(n, 2.0f * vdot(p.d, n)));
-                dir = vadd(refl, vscale(rius, mt.y));
-            }
+                dir = r1s_lambertian(hp, n, rius); // Lambertian::scatter rayweek1.cpp:403-409
             else
             {
-                // Dielectric::scatter rayweek1.cpp:470-511 (attenuation 1: nothing to push)
-                const float ref_idx = mt.y;
+                // Metal and Dielectric both reflect (rayweek1.cpp:414-417): once, for whichever of the two arms the wave's lanes take
+                // (r1_scatter.h)
                 const float ddn = vdot(p.d, n);
-                const V3 reflected = vsub(p.d, vscale(n, 2.0f * ddn));
-                V3 outward;
-                float ni_over_nt, cosine;
-                if (ddn > 0)
-                {
-                    outward = vneg(n);
-                    ni_over_nt = ref_idx;
-                    cosine = ref_idx * ddn;
-                }
+                const V3 refl = r1s_reflect(p.d, n, ddn);
+                if (type == 1u)
+                    dir = r1s_metal(refl, rius, mt.y); // Metal::scatter rayweek1.cpp:427-433
                 else
                 {
-                    outward = n;
-                    ni_over_nt = mt.z; // 1.0f / _refIdx, divided on the host (same IEEE division)
-                    cosine = -ddn;
+                    // Dielectric::scatter rayweek1.cpp:470-511 (attenuation 1: nothing to push), without the outward normal;
+                    // mt.z = 1.0f / _refIdx, divided on the host (same IEEE division)
+                    const R1Dielectric k = r1s_dielectric(p.d, n, ddn, mt.y, mt.z);
+                    // refract rayweek1.cpp:439-452
+                    float reflect_prob = 1.0f;
+                    V3 refracted = mk(0, 0, 0);
+                    if (k.discriminant > 0)
+                    {
+                        refracted = r1s_refracted(p.d, n, ddn, k, r1_sqrt_exact(k.discriminant, true));
+                        reflect_prob = r1s_schlick(mt.w, k.cosine); // rayweek1.cpp:454-459
+                    }
+                    dir = (rand01(p.s_scalar) < reflect_prob) ? refl : refracted;
                 }
-                // refract rayweek1.cpp:439-452
-                const float dt = vdot(p.d, outward);
-                const float discriminant = 1.0f - ni_over_nt * ni_over_nt * (1.0f - dt * dt);
-                float reflect_prob = 1.0f;
-                V3 refracted = mk(0, 0, 0);
-                if (discriminant > 0)
-                {
-                    refracted = vsub(vscale(vsub(p.d, vscale(outward, dt)), ni_over_nt), vscale(outward, r1_sqrt_exact(discriminant, true)));
-                    // schlick rayweek1.cpp:454-459; r0 = ((1 - ref)/(1 + ref))^2 comes from the host
-                    const float r0 = mt.w;
-                    reflect_prob = r0 + (1.0f - r0) * pow5(1.0f - cosine);
-                }
-                dir = (rand01(p.s_scalar) < reflect_prob) ? reflected : refracted;
             }
             const V3 nd = vunit_guarded(dir);
             p.o = hp;
