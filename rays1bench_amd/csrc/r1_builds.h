@@ -43,6 +43,15 @@ constexpr bool r1_runs_as_latency(int mode, bool big) { return mode == R1_MODE_L
 // profiles/r04/land_sync_frame.txt), and so does the exhaustive sweep (its loop pays 14 % for the bookkeeping, 16.6 against 19.2 Grays/s)
 constexpr bool r1_build_lands(int variant, bool stats, int mode) { return R1_LAND && variant == R1_V_TREE && !stats && r1_mode_is_tp_family(mode); }
 
+// The root step of the tree walk tests its leaf sphere by sphere (r1_trace.hpp leaf_root) instead of through leaf_quad's slot loop: one choice
+// per build, taken where the build keeps its waves per SIMD, gains no scratch and no more than a handful of spilled-SGPR lane moves with it
+// (tools/kernel_meta.py; profiles/r19/kernel_meta_*.txt).  The path builds hold the camera table's scalars across the walk and
+// spill 16-36 more lane moves with the leaf's spheres in scalar registers as well; the small PIXEL build 12 more.
+constexpr bool r1_root_by_slots(bool stats, bool big, int mode)
+{
+    return stats || (mode != R1_MODE_PATH && !(mode == R1_MODE_PIXEL && !big));
+}
+
 // A build of the trace body: the template arguments of the kernel that runs (r1_trace_body<variant, stats, big, mode>).
 struct R1Build
 {

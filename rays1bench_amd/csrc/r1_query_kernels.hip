@@ -49,6 +49,7 @@ struct R1CastJob
     typedef R1CastArgs Args;
     static constexpr bool BOUNCES = false;
     static constexpr int waves(const bool big) { return big ? R1_CAST_WAVES_BIG : R1_CAST_WAVES_SMALL; }
+    static constexpr bool root_by_slots(const bool big) { return !big; } // (r1_builds.h r1_root_by_slots: the big-scene cast kernel would spill seven SGPRs with it)
 
     V3 o, d;
     float t_max; // (+inf -> FLT_MAX)
@@ -112,6 +113,7 @@ struct R1PathJob
     typedef R1TraceRaysArgs Args;
     static constexpr bool BOUNCES = true;
     static constexpr int waves(bool) { return R1_PATHQ_WAVES; }
+    static constexpr bool root_by_slots(bool) { return true; }
 
     Path p; // (p.k: the ray's index in the launch)
     V3 col; // the path's radiance once step() has said that it ended
@@ -254,7 +256,7 @@ __global__ void __launch_bounds__(R1_BLOCK, JOB::waves(BIG)) r1_query_tree_kerne
         if (live == 0ull)
             break;
         // ---- walk with carry-over, then the job of the lanes whose walk is complete ----
-        bvh_advance<false, true, LN, TS>(A.t.scene, J.O(), J.D(), tv, (TS *)s_trav, tid, (uint32_t)__popcll(live), nullptr, lnodes, top);
+        bvh_advance<false, true, LN, TS, JOB::root_by_slots(BIG)>(A.t.scene, J.O(), J.D(), tv, (TS *)s_trav, tid, (uint32_t)__popcll(live), nullptr, lnodes, top);
         if (alive && tv.cur == R1_BVH_DONE)
         {
             if (J.step(A, tv.best_id, tv.best, gtid, tid))

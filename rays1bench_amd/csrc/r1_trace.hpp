@@ -772,6 +772,51 @@ __device__ __forceinline__ void leaf_quad(const float4 *__restrict__ prims, cons
     } while (flagged != 0ull);
 }
 
+// The leaf of the ROOT step (bvh_advance), sphere by sphere: all lanes of the step test the SAME <= 4 spheres — the ground and the big
+// balls — and nearly every lane's line meets the ground, so the slot leaf_quad's loop searches for is the same slot for everybody.  Here
+// each slot runs pass 1 and ONE vote, and pass 2 in straight-line code under it where any lane of the step is flagged: no slot search, no
+// select chains over nb[4] / ds[4] (the arrays are gone), no loop vote, and `first` / `pairs` are wave-uniform (the caller makes them
+// scalars), so the spheres and their indices arrive by scalar loads.  113 + 22 v VALU instructions (v: slots with a flagged lane)
+// against 120 + 52 t (t: the most flagged slots any lane holds) — DESIGN.md §4.26.  The offers are leaf_quad's operation for operation
+// and the slots come in index order, so the result is the same minimum offer with ties to the lowest index; an odd sphere's partner
+// (radius_sq = -inf: discriminant -inf) is never flagged, and a one-pair leaf fetches one pair.
+__device__ __forceinline__ void leaf_root(const float4 *__restrict__ prims, const uint32_t *__restrict__ ids, const uint32_t first,
+                                          const uint32_t pairs, const V3 o, const V3 d, float &best, uint32_t &best_id)
+{
+    typedef const uint32_t __attribute__((address_space(4))) *cu32_ptr;
+    const cf4_ptr sp = (cf4_ptr)(const f4 *)prims + 2 * (size_t)first;
+    const cu32_ptr si = (cu32_ptr)ids + 2 * (size_t)first;
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+    {
+        if (h && pairs < 2u) // (wave-uniform)
+            break;
+        const f4 p0 = sp[2 * h], p1 = sp[2 * h + 1];
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+        {
+            const float cx = s ? p0.y : p0.x, cy = s ? p0.w : p0.z, cz = s ? p1.y : p1.x, rsq = s ? p1.w : p1.z;
+            const float cox = cx - o.x, coy = cy - o.y, coz = cz - o.z;
+            const float nb = __fmaf_rn(coz, d.z, __fmaf_rn(coy, d.y, cox * d.x));
+            const float c = __fmaf_rn(coz, coz, __fmaf_rn(coy, coy, cox * cox)) - rsq;
+            const float ds = nb * nb - c;
+            // the lanes of the step whose discriminant has a clear sign bit (rayweek1.cpp:204); the others hold anything below and never update
+            const unsigned long long any = __builtin_amdgcn_ballot_w64((int)__float_as_uint(ds) >= 0);
+            if (any != 0ull)
+            {
+                const bool flag = (int)__float_as_uint(ds) >= 0;
+                const uint32_t id = si[2 * h + s]; // (behind the vote: fetched with the pair, the two indices cost the big-scene PIXEL build ten more lane moves and no run was faster)
+                const float root = r1_sqrt_exact_lanes(ds, any);
+                const float t1 = nb - root;
+                const float t = (t1 > 0.001f) ? t1 : nb + root;
+                const bool upd = flag & (t > 0.001f) & (t < FLT_MAX) & ((t < best) | ((t == best) & (id < best_id)));
+                best = upd ? t : best;
+                best_id = upd ? id : best_id;
+            }
+        }
+    }
+}
+
 // Traversal-stack entries.  Big scenes: the 32-bit child reference as it is.  Small scenes (the kernels that keep the node table in LDS:
 // <= 256 nodes, <= 1023 spheres = 512 pairs): 16 bits — bit 15 leaf, bits 12..14 the pair count, bits 0..11 the node or first pair —
 // which halves the stack in LDS (4 KB instead of 8 for the large scene's tree: together with the 10-word attenuation stack and the
@@ -813,7 +858,8 @@ __device__ __forceinline__ void trav_start(Trav &t)
 // utilisation of the node / leaf steps 0.53 / 0.69 -> 0.74 / 0.75, and 5 % SLOWER once the node table sat in LDS, because
 // the vote costs ~20 VALU instructions per trip; removed in round 3)
 // LN: the node table is read from `lnodes`, the workgroup's copy in LDS (the trace kernel on small scenes), instead of S.bvh_nodes.
-template <bool STATS, bool CARRY, bool LN, typename TS>
+// SLOTS: the root step tests its leaf with leaf_root instead of leaf_quad (r1_builds.h r1_root_by_slots: one choice per build).
+template <bool STATS, bool CARRY, bool LN, typename TS, bool SLOTS = false>
 __device__ __forceinline__ void bvh_advance(const R1DeviceScene &S, const V3 o, const V3 d, Trav &tv, TS *trav, const int tid,
                                             const uint32_t n_alive, unsigned long long *wstat, const float4 *lnodes /* LDS */, const uint32_t top = 0u /* !LN: nodes [0, top) are in lnodes */)
 {
@@ -961,7 +1007,10 @@ __device__ __forceinline__ void bvh_advance(const R1DeviceScene &S, const V3 o, 
             if ((tid & 63) == __ffsll((long long)__ballot(1)) - 1)
                 wstat[3] += 1;
         }
-        leaf_quad(prims, ids, leaf & INDEX_MASK, lp, o, d, best, best_id);
+        if (SLOTS) // (the reference is the same LDS word for every lane: made a scalar, the compiler cannot know)
+            leaf_root(prims, ids, (uint32_t)__builtin_amdgcn_readfirstlane((int)(leaf & INDEX_MASK)), (uint32_t)__builtin_amdgcn_readfirstlane((int)lp), o, d, best, best_id);
+        else
+            leaf_quad(prims, ids, leaf & INDEX_MASK, lp, o, d, best, best_id);
         // (the other child's box is fetched only now: six more live registers across the leaf test spill in the 7-wave builds)
         V3 pa = pa_ray;
         if (!LN)
@@ -2171,7 +2220,7 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
 #else
             const R1TraceArgs &HA = A;
 #endif
-            bvh_advance<STATS, true, LN, TS>(HA.scene, p.o, p.d, tv, (TS *)s_trav, tid, (uint32_t)__popcll(live_now), wstat, lnodes, top);
+            bvh_advance<STATS, true, LN, TS, r1_root_by_slots(STATS, BIG, MODE)>(HA.scene, p.o, p.d, tv, (TS *)s_trav, tid, (uint32_t)__popcll(live_now), wstat, lnodes, top);
             ready = alive && tv.cur == R1_BVH_DONE;
             if (tv.best_id != 0xFFFFFFFFu)
                 t_hit = tv.best, hit = (int)tv.best_id;
