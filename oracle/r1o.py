@@ -89,6 +89,22 @@ class SceneArrays:
         return cls(arrays, cam)
 
 
+def scene_file_bytes(sa):
+    """The flat little-endian scene file that oracle/ref_harness.cpp's rawframe / rawcast load: the count, the 22 camera floats, the
+    nine float arrays in SCENE_F32's order, then mat_type."""
+    return b"".join([struct.pack("<I", sa.count), sa.camera_array.astype("<f4").tobytes()]
+                    + [sa.arrays[k].astype("<f4").tobytes() for k in SCENE_F32] + [sa.arrays["mat_type"].tobytes()])
+
+
+def write_golden(path, items):
+    """items: (tag, dtype letter of _DT, array) in file order"""
+    with open(path, "wb") as f:
+        f.write(b"R1GOLD01")
+        for tag, dt, a in items:
+            a = np.ascontiguousarray(a, _DT[dt])
+            f.write(tag.encode().ljust(8, b"\0") + dt.encode() + struct.pack("<Q", a.size) + a.tobytes())
+
+
 # ---- fixture files ("R1GOLD01" tagged binary written by oracle/ref_harness*.cpp) --------
 
 _DT = {"f": np.float32, "u": np.uint32, "b": np.uint8, "q": np.uint64}

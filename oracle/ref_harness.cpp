@@ -7,7 +7,9 @@
 //   (1) generate the golden fixtures under tests/golden/ (oracle/gen_golden.py),
 //   (2) pin oracle/r1_oracle.c against the real reference, bit for bit,
 //   (3) time the reference's own scheduler/render_tile as bench.py's
-//       cpu_baseline {"kind": "reference"}.
+//       cpu_baseline {"kind": "reference"},
+//   (4) run the reference's own hit / scatter / color on a CALLER'S scene of at most 1024 sphere
+//       slots (`rawframe`, `rawcast`: the edge scenes of the test suite, oracle/gen_edge_golden.py).
 // Only this container can build it (the GPU box has no /root/reference); the built
 // binary lives in oracle/_ref/ (git-ignored, travels with gpurun).
 //
@@ -37,6 +39,16 @@
 #include <mm_malloc.h>
 #include <vector>
 #include <string>
+
+// The depth limit is a macro of the reference's common.h (common.h:19), not guarded: a build with -DR1_REF_MAX_BOUNCES=<n> reads that header
+// first — it is `#pragma once`, so the translation unit's own #include of it is then a no-op — and redefines the macro before color()
+// (rayweek1.cpp:523) is compiled.  Nothing else of the reference depends on it.
+#ifdef R1_REF_MAX_BOUNCES
+#define MULTITHREADED 1
+#include "../common/common.h"
+#undef MAX_BOUNCES
+#define MAX_BOUNCES R1_REF_MAX_BOUNCES
+#endif
 
 // Dielectric::_refIdx is private by `class` default access (rayweek1.cpp:461-463) and the
 // scene dump needs it; every standard header the TU uses is already included above, so
@@ -152,14 +164,17 @@ static void vec3_out(float *dst, Vec3 v)
 // ------------------------------------------------------------------------------------
 // scene dump
 
-static int cmd_scene(int argc, const char **argv)
+// The flat form of a Scene: material table + camera (the sphere arrays are read in place).
+struct FlatScene
 {
-    // scene <scene> <w> <h> <out>
-    if (argc < 4)
-        return 1;
-    const SceneDesc *d = find_scene(argv[0]);
-    int w = atoi(argv[1]), h = atoi(argv[2]);
-    Scene *scene = make_scene(d, w, h);
+    uint32_t n = 0;
+    std::vector<uint8_t> type;
+    std::vector<float> ar, ag, ab, par;
+    float cam[22];
+};
+
+static bool flatten(const Scene *scene, FlatScene *out)
+{
     const SphereSOA::InstanceData *s = scene->hitables->_soa_spheres.getData();
     uint32_t n = s->_count;
 
@@ -169,8 +184,11 @@ static int cmd_scene(int argc, const char **argv)
     Dielectric g(1);
     void *vl = *(void **)&l, *vm = *(void **)&m, *vg = *(void **)&g;
 
-    std::vector<uint8_t> type(n);
-    std::vector<float> ar(n), ag(n), ab(n), par(n);
+    out->n = n;
+    out->type.assign(n, 0);
+    std::vector<uint8_t> &type = out->type;
+    std::vector<float> &ar = out->ar, &ag = out->ag, &ab = out->ab, &par = out->par;
+    ar.assign(n, 0), ag.assign(n, 0), ab.assign(n, 0), par.assign(n, 0);
     for (uint32_t i = 0; i < n; ++i)
     {
         Material *mat = s->material[i];
@@ -203,11 +221,11 @@ static int cmd_scene(int argc, const char **argv)
         else
         {
             fprintf(stderr, "unknown material vtable\n");
-            return 5;
+            return false;
         }
     }
 
-    float cam[22];
+    float *cam = out->cam;
     vec3_out(cam + 0, scene->camera._origin);
     vec3_out(cam + 3, scene->camera._lowerLeftCorner);
     vec3_out(cam + 6, scene->camera._horizontal);
@@ -216,6 +234,22 @@ static int cmd_scene(int argc, const char **argv)
     vec3_out(cam + 15, scene->camera._v);
     vec3_out(cam + 18, scene->camera._w);
     cam[21] = scene->camera._lensRadius;
+    return true;
+}
+
+static int cmd_scene(int argc, const char **argv)
+{
+    // scene <scene> <w> <h> <out>
+    if (argc < 4)
+        return 1;
+    const SceneDesc *d = find_scene(argv[0]);
+    int w = atoi(argv[1]), h = atoi(argv[2]);
+    Scene *scene = make_scene(d, w, h);
+    const SphereSOA::InstanceData *s = scene->hitables->_soa_spheres.getData();
+    FlatScene fs;
+    if (!flatten(scene, &fs))
+        return 5;
+    uint32_t n = fs.n;
 
     Writer wr(argv[3]);
     uint32_t dims[3] = {(uint32_t)w, (uint32_t)h, n};
@@ -225,12 +259,12 @@ static int cmd_scene(int argc, const char **argv)
     wr.f32("cz", s->center_z, n);
     wr.f32("rsq", s->radius_sq, n);
     wr.f32("invr", s->inv_radius, n);
-    wr.u8("mtype", type.data(), n);
-    wr.f32("alb_r", ar.data(), n);
-    wr.f32("alb_g", ag.data(), n);
-    wr.f32("alb_b", ab.data(), n);
-    wr.f32("mparam", par.data(), n);
-    wr.f32("camera", cam, 22);
+    wr.u8("mtype", fs.type.data(), n);
+    wr.f32("alb_r", fs.ar.data(), n);
+    wr.f32("alb_g", fs.ag.data(), n);
+    wr.f32("alb_b", fs.ab.data(), n);
+    wr.f32("mparam", fs.par.data(), n);
+    wr.f32("camera", fs.cam, 22);
     delete scene;
     return 0;
 }
@@ -311,18 +345,8 @@ static int cmd_samples(int argc, const char **argv)
 
 // full frame under the seeding contract: per-sample results summed in sample order and
 // resolved exactly as rayweek1.cpp:765-775
-static int cmd_frame(int argc, const char **argv)
+static int write_frame(Scene *scene, const char *name, int w, int h, int spp, uint32_t seed, int nthreads, const char *out, bool dump)
 {
-    // frame <scene> <w> <h> <spp> <seed> <threads> <out> [dump_samples]
-    if (argc < 7)
-        return 1;
-    const SceneDesc *d = find_scene(argv[0]);
-    int w = atoi(argv[1]), h = atoi(argv[2]), spp = atoi(argv[3]);
-    uint32_t seed = (uint32_t)strtoul(argv[4], 0, 0);
-    int nthreads = atoi(argv[5]);
-    bool dump = argc > 7 && atoi(argv[7]) != 0;
-    Scene *scene = make_scene(d, w, h);
-
     std::vector<uint8_t> img((size_t)w * h * 3);
     std::vector<uint64_t> row_rays(h, 0);
     std::vector<float> samp;
@@ -368,7 +392,7 @@ static int cmd_frame(int argc, const char **argv)
     for (int y = 0; y < h; ++y)
         total += row_rays[y];
 
-    Writer wr(argv[6]);
+    Writer wr(out);
     uint32_t hdr[4] = {(uint32_t)w, (uint32_t)h, (uint32_t)spp, seed};
     wr.u32("hdr", hdr, 4);
     wr.u8("image", img.data(), img.size());
@@ -376,8 +400,212 @@ static int cmd_frame(int argc, const char **argv)
     wr.u64("rowrays", row_rays.data(), h);
     if (dump)
         wr.f32("samples", samp.data(), samp.size());
-    printf("{\"scene\": \"%s\", \"w\": %d, \"h\": %d, \"spp\": %d, \"seed\": %u, \"rays\": %llu}\n", d->name, w, h, spp, seed,
+    printf("{\"scene\": \"%s\", \"w\": %d, \"h\": %d, \"spp\": %d, \"seed\": %u, \"rays\": %llu}\n", name, w, h, spp, seed,
            (unsigned long long)total);
+    return 0;
+}
+
+static int cmd_frame(int argc, const char **argv)
+{
+    // frame <scene> <w> <h> <spp> <seed> <threads> <out> [dump_samples]
+    if (argc < 7)
+        return 1;
+    const SceneDesc *d = find_scene(argv[0]);
+    int w = atoi(argv[1]), h = atoi(argv[2]), spp = atoi(argv[3]);
+    uint32_t seed = (uint32_t)strtoul(argv[4], 0, 0);
+    int nthreads = atoi(argv[5]);
+    bool dump = argc > 7 && atoi(argv[7]) != 0;
+    Scene *scene = make_scene(d, w, h);
+    int rc = write_frame(scene, d->name, w, h, spp, seed, nthreads, argv[6], dump);
+    delete scene;
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------
+// The reference on a caller's scene.  A scene file is a flat little-endian dump:
+//   u32 count | 22 f32 camera (r1o.SceneArrays.camera_array) | f32[count] center_x center_y center_z radius_sq inv_radius
+//   albedo_r albedo_g albedo_b mat_param | u8[count] mat_type
+// The loader goes through the reference's own container (reserve, add) and material constructors, then overwrites what those
+// compute or clamp with the file's words: add() derives radius_sq and inv_radius from a radius and zeroes a non-positive radius's
+// inv_radius (soa_sphere.cpp:80-81), Metal's constructor clamps fuzz (rayweek1.cpp:424).  The reference has no field for a
+// Dielectric's albedo (its attenuation is 1, rayweek1.cpp:472), a Lambertian's parameter or a placeholder's material words: those
+// words of the file are not representable and are left out of the self-check below, which compares every other word of the file
+// with what flatten() — cmd_scene's reader — gets back from the loaded Scene.
+
+enum { RAW_MAX_SPHERES = 1024 }; // Hitable::hit keeps three arrays of this many entries on its stack (rayweek1.cpp:174-178)
+
+static Scene *load_scene(const char *path)
+{
+    FILE *f = fopen(path, "rb");
+    if (!f)
+    {
+        fprintf(stderr, "cannot open %s\n", path);
+        exit(4);
+    }
+    uint32_t n = 0;
+    float cam[22];
+    if (fread(&n, 4, 1, f) != 1 || fread(cam, 4, 22, f) != 22)
+    {
+        fprintf(stderr, "%s: short scene file\n", path);
+        exit(7);
+    }
+    if (n == 0 || n > RAW_MAX_SPHERES || n % SIMD_WIDTH != 0)
+    {
+        fprintf(stderr, "%s: %u sphere slots; the reference's hit() takes a multiple of %d, at most %d\n", path, n, SIMD_WIDTH, (int)RAW_MAX_SPHERES);
+        exit(7);
+    }
+    std::vector<float> fl((size_t)9 * n);
+    std::vector<uint8_t> type(n);
+    char extra;
+    if (fread(fl.data(), 4, fl.size(), f) != fl.size() || fread(type.data(), 1, n, f) != n || fread(&extra, 1, 1, f) != 0)
+    {
+        fprintf(stderr, "%s: the file's size does not fit its count %u\n", path, n);
+        exit(7);
+    }
+    fclose(f);
+    const float *cx = &fl[0], *cy = &fl[n], *cz = &fl[2 * (size_t)n], *rsq = &fl[3 * (size_t)n], *invr = &fl[4 * (size_t)n];
+    const float *ar = &fl[5 * (size_t)n], *ag = &fl[6 * (size_t)n], *ab = &fl[7 * (size_t)n], *par = &fl[8 * (size_t)n];
+
+    Scene *scene = new Scene;
+    Hitable *world = new Hitable;
+    scene->hitables = world;
+    world->_soa_spheres.reserve(n + SIMD_WIDTH);
+    for (uint32_t i = 0; i < n; ++i)
+    {
+        Material *m = nullptr;
+        if (type[i] == 0)
+            m = new Lambertian(Vec3(ar[i], ag[i], ab[i]));
+        else if (type[i] == 1)
+            m = new Metal(Vec3(ar[i], ag[i], ab[i]), par[i]);
+        else if (type[i] == 2)
+            m = new Dielectric(par[i]);
+        else if (type[i] != 255)
+        {
+            fprintf(stderr, "%s: slot %u has material type %u\n", path, i, type[i]);
+            exit(7);
+        }
+        world->_soa_spheres.add(Vec3(cx[i], cy[i], cz[i]), 1.0f, m);
+        if (type[i] == 1)
+            ((Metal *)m)->fuzz = par[i];
+        else if (type[i] == 2)
+            ((Dielectric *)m)->_refIdx = par[i];
+    }
+    SphereSOA::InstanceData *s = world->_soa_spheres.getData();
+    if (s->_count != n || s->_capacity < n)
+    {
+        fprintf(stderr, "%s: the container holds %u of %u slots\n", path, s->_count, n);
+        exit(7);
+    }
+    memcpy(s->center_x, cx, 4 * (size_t)n);
+    memcpy(s->center_y, cy, 4 * (size_t)n);
+    memcpy(s->center_z, cz, 4 * (size_t)n);
+    memcpy(s->radius_sq, rsq, 4 * (size_t)n);
+    memcpy(s->inv_radius, invr, 4 * (size_t)n);
+
+    scene->camera._origin = Vec3(cam + 0);
+    scene->camera._lowerLeftCorner = Vec3(cam + 3);
+    scene->camera._horizontal = Vec3(cam + 6);
+    scene->camera._vertical = Vec3(cam + 9);
+    scene->camera._u = Vec3(cam + 12);
+    scene->camera._v = Vec3(cam + 15);
+    scene->camera._w = Vec3(cam + 18);
+    scene->camera._lensRadius = cam[21];
+
+    // self-check: cmd_scene's reader gives the file's words back
+    FlatScene fs;
+    bool same = flatten(scene, &fs) && fs.n == n && memcmp(fs.cam, cam, sizeof(cam)) == 0 && memcmp(fs.type.data(), type.data(), n) == 0 &&
+                memcmp(s->center_x, cx, 4 * (size_t)n) == 0 && memcmp(s->center_y, cy, 4 * (size_t)n) == 0 &&
+                memcmp(s->center_z, cz, 4 * (size_t)n) == 0 && memcmp(s->radius_sq, rsq, 4 * (size_t)n) == 0 &&
+                memcmp(s->inv_radius, invr, 4 * (size_t)n) == 0;
+    for (uint32_t i = 0; same && i < n; ++i)
+    {
+        if (type[i] == 0 || type[i] == 1)
+            same = memcmp(&fs.ar[i], &ar[i], 4) == 0 && memcmp(&fs.ag[i], &ag[i], 4) == 0 && memcmp(&fs.ab[i], &ab[i], 4) == 0;
+        if (same && (type[i] == 1 || type[i] == 2))
+            same = memcmp(&fs.par[i], &par[i], 4) == 0;
+    }
+    if (!same)
+    {
+        fprintf(stderr, "%s: the loaded scene does not dump to the file's words\n", path);
+        exit(3);
+    }
+    return scene;
+}
+
+static int cmd_rawframe(int argc, const char **argv)
+{
+    // rawframe <scene file> <w> <h> <spp> <seed> <out> [dump_samples]
+    if (argc < 6)
+        return 1;
+    int w = atoi(argv[1]), h = atoi(argv[2]), spp = atoi(argv[3]);
+    uint32_t seed = (uint32_t)strtoul(argv[4], 0, 0);
+    bool dump = argc > 6 && atoi(argv[6]) != 0;
+    if (w <= 0 || h <= 0 || spp <= 0)
+        return 1;
+    Scene *scene = load_scene(argv[0]);
+    int rc = write_frame(scene, "raw", w, h, spp, seed, 4, argv[5], dump);
+    delete scene;
+    return rc;
+}
+
+// the reference's own Hitable::hit (rayweek1.cpp:152-339) through its own Ray constructor (:104-108), for tools/gen_cast_golden.py
+// (the reference's three scenes) and oracle/gen_edge_golden.py: 32-byte records {t, index (0xFFFFFFFF: miss), p, n}
+static int cmd_rawcast(int argc, const char **argv)
+{
+    // rawcast <scene file> <rays.f32> <hits.bin>
+    if (argc < 3)
+        return 1;
+    Scene *scene = load_scene(argv[0]);
+    const SphereSOA::InstanceData *s = scene->hitables->_soa_spheres.getData();
+    const uint32_t count = s->_count;
+
+    FILE *f = fopen(argv[1], "rb");
+    if (!f)
+        return 4;
+    fseek(f, 0, SEEK_END);
+    const long bytes = ftell(f);
+    fseek(f, 0, SEEK_SET);
+    const size_t n = (size_t)bytes / 32;
+    std::vector<float> rays(8 * n);
+    if (bytes % 32 != 0 || fread(rays.data(), 32, n, f) != n)
+        return 4;
+    fclose(f);
+
+    std::vector<uint32_t> out(8 * n);
+    for (size_t i = 0; i < n; ++i)
+    {
+        const float *q = &rays[8 * i];
+        const Ray r(Vec3(q[0], q[1], q[2]), Vec3(q[4], q[5], q[6]));
+        HitRecord rec;
+        memset(&rec, 0, sizeof(rec));
+        const bool hit = scene->hitables->hit(r, 0.001f, q[3], &rec);
+        float rec_f[7] = {FLT_MAX, 0, 0, 0, 0, 0, 0};
+        uint32_t index = 0xFFFFFFFFu;
+        if (hit)
+        {
+            // the index is the slot whose material object the record names: every real sphere owns its own
+            uint32_t found = 0;
+            for (uint32_t k = 0; k < count; ++k)
+                if (s->material[k] == rec.material && s->material[k] != nullptr)
+                    index = k, ++found;
+            if (found != 1)
+            {
+                fprintf(stderr, "ray %zu: the hit's material names %u spheres\n", i, found);
+                return 6;
+            }
+            rec_f[0] = rec.t;
+            rec_f[1] = rec.p.getX(), rec_f[2] = rec.p.getY(), rec_f[3] = rec.p.getZ();
+            rec_f[4] = rec.normal.getX(), rec_f[5] = rec.normal.getY(), rec_f[6] = rec.normal.getZ();
+        }
+        uint32_t *o = &out[8 * i];
+        memcpy(&o[0], &rec_f[0], 4);
+        o[1] = index;
+        memcpy(&o[2], &rec_f[1], 24);
+    }
+    f = fopen(argv[2], "wb");
+    if (!f || fwrite(out.data(), 32, n, f) != n)
+        return 4;
+    fclose(f);
     delete scene;
     return 0;
 }
@@ -639,7 +867,7 @@ int main(int argc, const char **argv)
 {
     if (argc < 2)
     {
-        fprintf(stderr, "usage: %s scene|samples|frame|seq|bench|kat ...\n", argv[0]);
+        fprintf(stderr, "usage: %s scene|samples|frame|rawframe|rawcast|seq|bench|kat ...\n", argv[0]);
         return 1;
     }
     const char *cmd = argv[1];
@@ -650,6 +878,10 @@ int main(int argc, const char **argv)
         rc = cmd_samples(argc - 2, argv + 2);
     else if (!strcmp(cmd, "frame"))
         rc = cmd_frame(argc - 2, argv + 2);
+    else if (!strcmp(cmd, "rawframe"))
+        rc = cmd_rawframe(argc - 2, argv + 2);
+    else if (!strcmp(cmd, "rawcast"))
+        rc = cmd_rawcast(argc - 2, argv + 2);
     else if (!strcmp(cmd, "seq"))
         rc = cmd_seq(argc - 2, argv + 2);
     else if (!strcmp(cmd, "bench"))

@@ -7,7 +7,10 @@ tests render; tests/test_gpu_builds_edges.py and tests/test_gpu_cast_edges.py ru
 The geometry restates what tests/test_gpu_bvh.py and tests/test_gpu_configs.py construct (their helpers, their generators' seeds); the
 `palette` scene is new, and so is `noise_lds`: a tree of mostly tiny spheres measures its pad per node and then runs through the big-scene
 tree kernels whatever its size, as `noise`/small does, so `noise_lds` takes hits by rounding alone through the small-scene tree kernels.  One oracle run per (scene, size, camera, seed) is cached here and shared by the test modules: a sample depends
-on (seed, pixel, sample index) only, so the run at the largest spp holds every smaller frame as a prefix."""
+on (seed, pixel, sample index) only, so the run at the largest spp holds every smaller frame as a prefix.
+
+The small size's expectations — frames, records and the hits of every fourth query ray — are also held as fixtures from the reference's own
+code (tests/golden/ref_edge_*.bin), to which tests/test_reference_edges_host.py holds the oracle and tests/test_gpu_reference_edges.py the kernels."""
 import ctypes as C
 import functools
 

@@ -4,7 +4,8 @@ spheres, and a one-pair leaf at the END of the table, whose second pair — fetc
 appends.  LEAVES[name] is the leaf table r1_bvh_describe must report for the small size, [(first pair, pairs)] in table order, and
 IDS[name] the sphere of every slot (-1: the partner of an odd sphere): tests assert them, so a change of the builder cannot silently
 take a shape away.  The `big` size adds tests/edge_scenes.py's fillers (past 1023 active spheres: the big-scene kernels, leaves of up to
-four pairs, the pair loop).  One oracle run per (scene, size, camera, seed, spp) is cached here."""
+four pairs, the pair loop).  One oracle run per (scene, size, camera, seed, spp) is cached here.  The small size's frames and records are also
+held as fixtures from the reference's own code (tests/golden/ref_leaf_*.bin; tests/test_reference_edges_host.py, tests/test_gpu_reference_edges.py)."""
 import functools
 
 import numpy as np

@@ -13,7 +13,8 @@ among 1080 tiny spheres the builder peels the ground alone, so the big trees' ro
 one-pair arm of the root step — and `behind`, which has no ground, has no root leaf there (asserted as well: the generic walk).
 `wide` is `k4` over a 34 x 34 lattice and no fillers: 1160 spheres whose median radius is the lattice's, so the big-scene kernels meet a
 root leaf of two full pairs as well (one size: `big`).
-One oracle run per (scene, order, size, camera, seed, spp) is cached here."""
+One oracle run per (scene, order, size, camera, seed, spp) is cached here.  The small size's frames and records, both orders, are also held as
+fixtures from the reference's own code (tests/golden/ref_root_*.bin; tests/test_reference_edges_host.py, tests/test_gpu_reference_edges.py)."""
 import functools
 
 import numpy as np

@@ -12,7 +12,8 @@ count against the CPU ORACLE's, as tests/test_gpu_builds_edges.py does.  The sce
 each in a `small` size (the small-scene kernels) and a `big` one (fillers of the scene's own material past 1023 spheres).  Every build of
 r1_builds.h is reached: the tree, the sweep and the grid through the synchronous frame with its records (LAT; big: TP), r1_render_async
 (TP), PIXEL mode, a batch (BATCH), a camera path (PATH), progressive passes (PASS) and the adaptive call (LISTED); the reference form and
-the diagnostic builds through the synchronous frame; and the path-query entry over the frame's own camera rays.  No tolerance anywhere."""
+the diagnostic builds through the synchronous frame; and the path-query entry over the frame's own camera rays.  No tolerance anywhere.  The small size's frames and records are also held as fixtures
+from the reference's own code at 51 bounces (tests/golden/ref_scatter_*.bin; tests/test_reference_edges_host.py, tests/test_gpu_reference_edges.py)."""
 import numpy as np
 import pytest
 

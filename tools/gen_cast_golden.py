@@ -1,14 +1,15 @@
 #!/usr/bin/env python3
 """tools/gen_cast_golden.py — writes tests/golden/cast_{small,medium,large}.bin: 4096 seeded rays per scene and what the REFERENCE'S
-OWN Hitable::hit answers for them (tools/ref_cast_harness.cpp, which includes the reference's translation unit by path and is compiled
-with the STRICT flags of oracle/Makefile into a temporary directory; no reference source text and nothing compiled from it enters this
-repository).  Runs only where the reference's sources are present; the tests read the committed files.
+OWN Hitable::hit answers for them (oracle/ref_harness.cpp's `rawcast`, which includes the reference's translation unit by path and is
+compiled with the STRICT flags of oracle/Makefile into the git-ignored oracle/_ref/; no reference source text and nothing compiled from it
+enters this repository).  Runs only where the reference's sources are present; the tests read the committed files.
 
     python tools/gen_cast_golden.py --ref /path/to/reference
 
 Files are in the "R1GOLD01" tagged format (oracle/r1o.py read_golden): rays (f, 8 per ray: ox oy oz t_max dx dy dz 0), index (u,
-0xFFFFFFFF = miss), t, p, n (f).  The generator asserts that the reference's sphere arrays equal tests/golden/scene_<name>_200x100.bin
-byte for byte (the tests load the spheres from there) and that the reference reports at least 5 % hits and 5 % misses in each of the
+0xFFFFFFFF = miss), t, p, n (f).  The reference's scene is tests/golden/scene_<name>_200x100.bin — its own dump of create_<name>_scene(),
+from which the tests load the spheres too — loaded back into the reference's Scene by the harness, which checks on every load that its
+dump gives the file's words again.  The generator asserts that the reference reports at least 5 % hits and 5 % misses in each of the
 first five ray classes; re-seed if a class misses that, never relax it.
 
 Ray classes (the same recipe for each scene; `field` = the box of the centres of the spheres of radius < 100, i.e. without the ground):
@@ -26,7 +27,6 @@ Ray classes (the same recipe for each scene; `field` = the box of the centres of
 import argparse
 import hashlib
 import os
-import struct
 import subprocess
 import sys
 import tempfile
@@ -38,7 +38,6 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import r1o  # noqa: E402
 
 GOLD = os.path.join(ROOT, "tests", "golden")
-STRICT = "-O2 -mavx2 -mfma -ffp-contract=off -fno-rtti -fno-exceptions -std=c++17 -pthread -DNDEBUG -w".split()
 SEEDS = {"small": 20001, "medium": 20002, "large": 20003}
 FLT_MAX = np.float32(np.finfo(np.float32).max)
 CLASSES = (("camera", 1024), ("volume", 1024), ("scatter", 1024), ("axis", 512), ("grazing", 256), ("bounded", 256))
@@ -46,24 +45,21 @@ f32 = np.float32
 
 
 def build_harness(ref, tmp):
-    exe = os.path.join(tmp, "ref_cast")
-    tu = os.path.join(ref, "src", "step13", "rayweek1.cpp")
-    subprocess.check_call(["g++"] + STRICT + [f'-DREF_STEP13_TU="{tu}"', "-I" + os.path.join(ref, "src", "step13"), "-o", exe,
-                                              os.path.join(ROOT, "tools", "ref_cast_harness.cpp"), os.path.join(ref, "src", "step13", "soa_sphere.cpp")])
-    return exe
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "ref", "REF=" + ref])
+    return os.path.join(ROOT, "oracle", "_ref", "ref_step13_strict")
 
 
 def reference_hits(exe, tmp, scene, rays):
-    """rays (n, 8) float32 -> (index u32, t, p, n) from the reference, and its sphere arrays"""
-    rp, hp, sp = (os.path.join(tmp, n) for n in ("rays.f32", "hits.bin", "spheres.f32"))
+    """rays (n, 8) float32 -> (index u32, t, p, n) from the reference on the scene of tests/golden/scene_<scene>_200x100.bin"""
+    sp, rp, hp = (os.path.join(tmp, n) for n in ("scene.bin", "rays.f32", "hits.bin"))
+    sa = r1o.SceneArrays.from_golden(r1o.read_golden(os.path.join(GOLD, f"scene_{scene}_200x100.bin")))
+    with open(sp, "wb") as f:
+        f.write(r1o.scene_file_bytes(sa))
     np.ascontiguousarray(rays, f32).tofile(rp)
-    subprocess.check_call([exe, scene, rp, hp, sp])
+    subprocess.check_call([exe, "rawcast", sp, rp, hp])
     w = np.fromfile(hp, np.uint32).reshape(-1, 8)
     fl = w.view(f32)
-    sph = np.fromfile(sp, np.uint32)
-    count = int(sph[0])
-    arrays = sph[1:].view(f32).reshape(5, count)
-    return w[:, 1].copy(), fl[:, 0].copy(), fl[:, 2:5].copy(), fl[:, 5:8].copy(), arrays
+    return w[:, 1].copy(), fl[:, 0].copy(), fl[:, 2:5].copy(), fl[:, 5:8].copy()
 
 
 def unit_ball(rng, n):
@@ -121,7 +117,7 @@ def make_rays(exe, tmp, name, gold):
 
     # scatter: from the reference's own hits of the rays above
     first = np.concatenate([camera, volume])
-    idx, t, p, nrm, _ = reference_hits(exe, tmp, name, first)
+    idx, t, p, nrm = reference_hits(exe, tmp, name, first)
     hit = np.nonzero(idx != 0xFFFFFFFF)[0]
     assert hit.size >= 256, (name, hit.size)
     pick = rng.choice(hit, 1024, replace=hit.size < 1024)
@@ -162,7 +158,7 @@ def make_rays(exe, tmp, name, gold):
 
     # bounded: rays of the classes above that hit, with t_max at and around the reference's t and around 0.001
     free = np.concatenate([camera, volume, scatter, axis, grazing])
-    idx, t, p, nrm, _ = reference_hits(exe, tmp, name, free)
+    idx, t, p, nrm = reference_hits(exe, tmp, name, free)
     hit = np.nonzero(idx != 0xFFFFFFFF)[0]
     pick = rng.choice(hit, 256, replace=False)
     bounded = free[pick].copy()
@@ -178,14 +174,6 @@ def make_rays(exe, tmp, name, gold):
     return np.concatenate([free, bounded]).astype(f32)
 
 
-def write_golden(path, items):
-    with open(path, "wb") as f:
-        f.write(b"R1GOLD01")
-        for tag, dt, a in items:
-            a = np.ascontiguousarray(a)
-            f.write(tag.encode().ljust(8, b"\0") + dt.encode() + struct.pack("<Q", a.size) + a.tobytes())
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref", required=True, help="root of the reference's source tree (the directory that holds src/step13)")
@@ -196,9 +184,7 @@ def main():
             gold = r1o.read_golden(os.path.join(GOLD, f"scene_{name}_200x100.bin"))
             rays = make_rays(exe, tmp, name, gold)
             assert rays.shape == (4096, 8)
-            idx, t, p, nrm, arrays = reference_hits(exe, tmp, name, rays)
-            for row, key in zip(arrays, ("cx", "cy", "cz", "rsq", "invr")):
-                assert row.tobytes() == gold[key].tobytes(), (name, key)  # the tests load the spheres from the committed scene file
+            idx, t, p, nrm = reference_hits(exe, tmp, name, rays)
             at = 0
             for cls, n in CLASSES:
                 hits = int((idx[at:at + n] != 0xFFFFFFFF).sum())
@@ -207,7 +193,7 @@ def main():
                     assert hits * 20 >= n and (n - hits) * 20 >= n, (name, cls, hits, n)
                 at += n
             out = os.path.join(GOLD, f"cast_{name}.bin")
-            write_golden(out, (("rays", "f", rays), ("index", "u", idx), ("t", "f", t), ("p", "f", p), ("n", "f", nrm)))
+            r1o.write_golden(out, (("rays", "f", rays), ("index", "u", idx), ("t", "f", t), ("p", "f", p), ("n", "f", nrm)))
             assert os.path.getsize(out) <= 280130
             with open(out, "rb") as f:
                 print(f"{name:7s} {os.path.basename(out)} md5 {hashlib.md5(f.read()).hexdigest()}")
