@@ -179,8 +179,9 @@ int r1_set_camera(r1_context *ctx, const r1_camera *camera);
 /* ---- moving spheres ---- */
 
 /* New centres for the spheres [first, first + count) of the scene: SCENE indices into the arrays given to the last r1_set_scene,
- * placeholders counted; entries of spheres that are not active (inv_radius == 0, or non-finite at r1_set_scene) are ignored.  Radii,
- * materials, the active set and the active order do not change: only r1_set_scene changes them.  x, y, z are host memory, `count`
+ * placeholders counted; entries of spheres that are not active (inv_radius == 0, or non-finite at r1_set_scene) are ignored.  Radii and
+ * materials stay (r1_update_spheres below changes them too); the active set and the active order do not change: only r1_set_scene changes
+ * them.  x, y, z are host memory, `count`
  * floats each, read during the call only (through a page-locked staging buffer of the context).  The centres are written in place
  * into the tables the box-tree kernels read and the tree is REFITTED on the device: its topology stays, every box is recomputed
  * bottom-up from the new centres in the builder's own arithmetic (r1_bvh_fill.h), one small launch per height of the tree.  Leaves
@@ -213,6 +214,49 @@ int r1_update_centers(r1_context *ctx, uint32_t first, uint32_t count, const flo
  * r1_scene), the refit leaves it out of every box, and the pixels equal r1_set_scene with the same arrays, where that sphere is
  * dropped as inactive.  The context's host copies of the centres are NOT updated. */
 int r1_update_centers_device(r1_context *ctx, uint32_t first, uint32_t count, const void *d_x, const void *d_y, const void *d_z, void *hip_stream);
+
+/* ---- sphere updates: radii and materials too ---- */
+
+/* New values for the spheres [first, first + count) of the scene, in three GROUPS: centres (center_x, _y, _z), radii (radius_sq, inv_radius: of
+ * the same radius, as in r1_scene) and materials (mat_type with albedo_r, _g, _b and mat_param).  Every group: all of its pointers or none
+ * (NULL = this property stays).  Arrays of `count` entries each; entry i belongs to scene index first + i. */
+typedef struct r1_sphere_update
+{
+    const float *center_x, *center_y, *center_z;
+    const float *radius_sq, *inv_radius;
+    const uint8_t *mat_type;
+    const float *albedo_r, *albedo_g, *albedo_b, *mat_param;
+} r1_sphere_update;
+
+/* r1_update_centers' contract for every property of a sphere but its being active: afterwards every render, ray query and path query through
+ * the context is bit-identical — pixels, ray counts, sample records, hit records — to a fresh context after r1_set_scene with the edited
+ * arrays.  Indices, ignored entries of spheres that are not active, the staging of the host arrays, the stream order (everything is enqueued
+ * on `hip_stream`, nothing is waited for but the previous update's reading of the staging buffer), "one update at a time per context" and the
+ * end of a progressive accumulation are r1_update_centers' own; the active set and the active order never change; there is no r1_multi form.
+ *   centres    r1_update_centers' rules (a non-finite new centre of an active sphere: R1_EINVAL).
+ *   radii      the device rewrites the radius in every table the box-tree kernels and the shading read and REFITS the tree (with the centres,
+ *              if both are given: one refit).  The context is then in the state of a centre update: the flat y slab is dropped, PREFILTER,
+ *              STATS, WAVEFRONT, GRID, GRID_STATS and a GRID cast return R1_EINVAL ("the scene has moved") until the next r1_set_scene.  An
+ *              active sphere whose new pair would make it inactive (inv_radius 0 or NaN, radius_sq not finite) is R1_EINVAL; a negative
+ *              inv_radius and pairs that disagree are accepted as r1_set_scene accepts them.
+ *   materials  the device rewrites the sphere's albedo and material row.  Nothing else changes: no refit, every variant and the grid stay
+ *              valid, the flat slab stays.  mat_type > R1_MAT_DIELECTRIC for an active sphere is R1_EINVAL.
+ * R1_EINVAL before anything is changed or enqueued: before the first r1_set_scene, first + count beyond the scene, then (count == 0 is R1_OK
+ * and touches nothing) u == NULL, a group given in part, every group NULL, and the value rules above.  The context's host copies follow.
+ * After ANY update r1_set_scene, whatever arrays it is given, leaves the context equal to a fresh one. */
+int r1_update_spheres(r1_context *ctx, uint32_t first, uint32_t count, const r1_sphere_update *u, void *hip_stream);
+
+/* The same from DEVICE memory: the float arrays 4-byte aligned (R1_EINVAL otherwise; mat_type needs no alignment), read by launches on
+ * `hip_stream`; waits for nothing.  The host cannot see the values: a radius pair that would make a sphere inactive leaves it never hittable
+ * (its pixels equal r1_set_scene with those arrays, where the sphere is dropped), an entry whose mat_type is no material is skipped (the
+ * sphere keeps its material), a non-finite centre is r1_update_centers_device's.  The context's host copies are NOT updated. */
+int r1_update_spheres_device(r1_context *ctx, uint32_t first, uint32_t count, const r1_sphere_update *u, void *hip_stream);
+
+/* Diagnostic, synchronous (waits for the context's stream, as r1_bvh_download): the device's per-sphere rows of the n active spheres, in
+ * active order: exact [n][4] {cx cy cz radius_sq}, shade [n][4] {inv_radius, albedo r g b}, mat [n][4] {type, the bits of param, of
+ * 1 / ref_idx and of schlick's r0}, radii [n][2] {bound radius, test radius} (fp64).  Each may be NULL; all NULL: *n_active alone.
+ * R1_ELIMIT if cap_active (entries of each given array, in spheres) < n. */
+int r1_tables_download(r1_context *ctx, float *exact, float *shade, uint32_t *mat, double *radii, size_t cap_active, size_t *n_active);
 
 /* Renders the frame (or this shard's tiles of it) and returns everything on the host.
  * Replaces TileRenderScheduler::run + render_tile (rayweek1.cpp:785-842, :722-782).
@@ -659,6 +703,12 @@ int r1_bvh_describe(const r1_scene *scene, int32_t leaf_max, r1_bvh_info *info, 
  * (an empty leaf, or a subtree whose centres are all non-finite) has half extents -inf.  R1_EINVAL for NULL built, info, x, y or z. */
 int r1_bvh_refit_describe(const r1_scene *built, const float *x, const float *y, const float *z, int32_t leaf_max, r1_bvh_info *info,
                           float *nodes_out, size_t nodes_cap);
+
+/* The same with scene-indexed radii as well (radius_sq and inv_radius, built->count entries each; both NULL: the built scene's): the pin of
+ * r1_update_spheres*' refit.  Each pair is taken as the device's set kernel writes it: one that would make its sphere inactive leaves the
+ * sphere never hittable, a point in its boxes. */
+int r1_bvh_refit_describe_spheres(const r1_scene *built, const float *x, const float *y, const float *z, const float *radius_sq,
+                                  const float *inv_radius, int32_t leaf_max, r1_bvh_info *info, float *nodes_out, size_t nodes_cap);
 
 /* Diagnostic, synchronous: the node rows of the context's tree as the device holds them (16 floats per node, as r1_bvh_describe), after
  * waiting for the context's stream (an update enqueued on another stream is the caller's to wait for).  *nodes receives the number of

@@ -81,6 +81,12 @@ class BvhInfo(C.Structure):
                 ("flat_axis", C.c_int32), ("flat_m", C.c_float), ("flat_e", C.c_float)]
 
 
+class SphereUpdate(C.Structure):
+    """r1_sphere_update: the groups of r1_update_spheres* (NULL pointers: the property stays); void pointers, host or device."""
+    _fields_ = [(n, C.c_void_p) for n in ("center_x", "center_y", "center_z", "radius_sq", "inv_radius", "mat_type", "albedo_r", "albedo_g", "albedo_b",
+                                          "mat_param")]
+
+
 class Adaptive(C.Structure):
     """r1_adaptive: the schedule (min_spp, then pass_spp per pass, up to params.spp) and the stopping rule of r1_render_adaptive."""
     _fields_ = [("min_spp", C.c_int32), ("pass_spp", C.c_int32), ("max_delta", C.c_int32), ("mean_delta_q8", C.c_int32)]
@@ -198,6 +204,10 @@ SYMBOLS = [
     ("r1_update_centers", C.c_int, [_ctx, C.c_uint32, C.c_uint32, _f32p, _f32p, _f32p, C.c_void_p]),
     ("r1_update_centers_device", C.c_int, [_ctx, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("r1_bvh_refit_describe", C.c_int, [C.POINTER(CScene), _f32p, _f32p, _f32p, C.c_int32, C.POINTER(BvhInfo), _f32p, C.c_size_t]),
+    ("r1_update_spheres", C.c_int, [_ctx, C.c_uint32, C.c_uint32, C.POINTER(SphereUpdate), C.c_void_p]),
+    ("r1_update_spheres_device", C.c_int, [_ctx, C.c_uint32, C.c_uint32, C.POINTER(SphereUpdate), C.c_void_p]),
+    ("r1_bvh_refit_describe_spheres", C.c_int, [C.POINTER(CScene), _f32p, _f32p, _f32p, _f32p, _f32p, C.c_int32, C.POINTER(BvhInfo), _f32p, C.c_size_t]),
+    ("r1_tables_download", C.c_int, [_ctx, _f32p, _f32p, C.POINTER(C.c_uint32), _dblp, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("r1_bvh_download", C.c_int, [_ctx, _f32p, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("r1_grid_describe", C.c_int, [C.POINTER(CScene), C.POINTER(GridInfo), C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t,
                                    C.POINTER(C.c_uint32), C.c_size_t]),
@@ -351,6 +361,24 @@ def create_grid_scene(width, height, grid_w, grid_h):
     return Scene(SCENE_GRID, width, height, grid_w, grid_h)
 
 
+_SPHERE_GROUPS = (("center_x", "center_y", "center_z"), ("radius_sq", "inv_radius"), ("mat_type", "albedo_r", "albedo_g", "albedo_b", "mat_param"))
+
+
+def _sphere_update(who, centers, radii, materials, pointer_of):
+    """A SphereUpdate from the three groups (None: the group's pointers stay NULL); pointer_of(field, value) gives each array's address."""
+    if centers is None and radii is None and materials is None:
+        raise R1Error(R1_EINVAL, f"{who}: every group is None")
+    u = SphereUpdate()
+    for group, fields in zip((centers, radii, materials), _SPHERE_GROUPS):
+        if group is None:
+            continue
+        if len(group) != len(fields):
+            raise R1Error(R1_EINVAL, f"{who}: {len(fields)} arrays for {fields}")
+        for k, v in zip(fields, group):
+            setattr(u, k, pointer_of(k, v))
+    return u
+
+
 class Renderer:
     """One r1_context (device, stream, cached scene + workspace)."""
 
@@ -382,6 +410,42 @@ class Renderer:
         """r1_update_centers_device: the same from three device pointers to `count` floats each; waits for nothing."""
         _check(lib().r1_update_centers_device(self._c, first, count, C.c_void_p(d_x_ptr), C.c_void_p(d_y_ptr), C.c_void_p(d_z_ptr),
                                               _stream_arg(stream_ptr)))
+
+    def update_spheres(self, first, centers=None, radii=None, materials=None, stream_ptr=None):
+        """r1_update_spheres: new values for the spheres [first, first + n) of the scene (scene indices, placeholders counted), host arrays of
+        one length n.  centers = (x, y, z); radii = (radius_sq, inv_radius); materials = (mat_type, albedo_r, albedo_g, albedo_b, mat_param);
+        None: the property stays (all three None: R1_EINVAL, as the C call refuses an update without a group).  A change of centre or radius
+        refits the box tree on the device; materials alone change no index.  Enqueues on `stream_ptr` (None: the context's stream)."""
+        keep, n = [], None
+
+        def host_array(k, v):
+            nonlocal n
+            v = np.ascontiguousarray(v, np.uint8 if k == "mat_type" else np.float32)
+            if v.ndim != 1 or (n is not None and v.shape[0] != n):
+                raise R1Error(R1_EINVAL, "update_spheres: every array must be one-dimensional and of one length")
+            n = v.shape[0]
+            keep.append(v)
+            return v.ctypes.data
+
+        u = _sphere_update("update_spheres", centers, radii, materials, host_array)
+        _check(lib().r1_update_spheres(self._c, first, n, C.byref(u), C.c_void_p(stream_ptr) if stream_ptr else None))
+
+    def update_spheres_device(self, first, count, centers=None, radii=None, materials=None, stream_ptr=None):
+        """r1_update_spheres_device: the same from device pointers (ints) to `count` entries each, grouped as for update_spheres; waits for
+        nothing."""
+        u = _sphere_update("update_spheres_device", centers, radii, materials, lambda k, v: int(v))
+        _check(lib().r1_update_spheres_device(self._c, first, count, C.byref(u), _stream_arg(stream_ptr)))
+
+    def tables_download(self):
+        """r1_tables_download: the device's rows of the active spheres, in active order (diagnostic, synchronous): {"exact": float32[n, 4],
+        "shade": float32[n, 4], "mat": uint32[n, 4], "radii": float64[n, 2]}."""
+        n = C.c_size_t()
+        _check(lib().r1_tables_download(self._c, None, None, None, None, 0, C.byref(n)))
+        t = {"exact": np.zeros((n.value, 4), np.float32), "shade": np.zeros((n.value, 4), np.float32), "mat": np.zeros((n.value, 4), np.uint32),
+             "radii": np.zeros((n.value, 2), np.float64)}
+        _check(lib().r1_tables_download(self._c, t["exact"].ctypes.data_as(_f32p), t["shade"].ctypes.data_as(_f32p),
+                                        t["mat"].ctypes.data_as(C.POINTER(C.c_uint32)), t["radii"].ctypes.data_as(_dblp), n.value, C.byref(n)))
+        return t
 
     def bvh_download(self):
         """r1_bvh_download: the box tree's node rows as the device holds them, float32[n, 16] (diagnostic, synchronous)."""
@@ -730,14 +794,29 @@ def bvh_describe(cscene, leaf_max=0):
 def bvh_refit_describe(cscene, x, y, z, leaf_max=0):
     """r1_bvh_refit_describe: the tree r1_set_scene builds for `cscene`, refitted on the host to the scene-indexed centres x, y, z (cscene.count
     entries each): (info dict, nodes float32[n, 16]).  The ids are bvh_describe(cscene)'s."""
-    x, y, z = (np.ascontiguousarray(v, np.float32) for v in (x, y, z))
-    if not (x.shape == y.shape == z.shape == (cscene.count,)):
-        raise R1Error(R1_EINVAL, "bvh_refit_describe: x, y and z need cscene.count entries each")
+    return _refit_describe("bvh_refit_describe", cscene, x, y, z, None, None, leaf_max)
+
+
+def bvh_refit_describe_spheres(cscene, x, y, z, radius_sq=None, inv_radius=None, leaf_max=0):
+    """r1_bvh_refit_describe_spheres: bvh_refit_describe with scene-indexed radii as well (both None: the built scene's)."""
+    if (radius_sq is None) != (inv_radius is None):
+        raise R1Error(R1_EINVAL, "bvh_refit_describe_spheres: radius_sq and inv_radius go together")
+    return _refit_describe("bvh_refit_describe_spheres", cscene, x, y, z, radius_sq, inv_radius, leaf_max)
+
+
+def _refit_describe(who, cscene, x, y, z, radius_sq, inv_radius, leaf_max):
+    """The two host refits, r1_<who>: the same arguments but for the radii in front of leaf_max."""
+    arrays = [np.ascontiguousarray(v, np.float32) for v in (x, y, z) + (() if radius_sq is None else (radius_sq, inv_radius))]
+    if any(v.shape != (cscene.count,) for v in arrays):
+        raise R1Error(R1_EINVAL, f"{who}: every array needs cscene.count entries")
+    ptrs = [v.ctypes.data_as(_f32p) for v in arrays]
+    fn = getattr(lib(), "r1_" + who)
+    if who == "bvh_refit_describe_spheres" and radius_sq is None:
+        ptrs += [None, None]
     info = BvhInfo()
-    xp, yp, zp = (v.ctypes.data_as(_f32p) for v in (x, y, z))
-    _check(lib().r1_bvh_refit_describe(C.byref(cscene), xp, yp, zp, leaf_max, C.byref(info), None, 0))
+    _check(fn(C.byref(cscene), *ptrs, leaf_max, C.byref(info), None, 0))
     nodes = np.zeros((info.nodes, 16), np.float32)
-    _check(lib().r1_bvh_refit_describe(C.byref(cscene), xp, yp, zp, leaf_max, C.byref(info), nodes.ctypes.data_as(_f32p), nodes.size))
+    _check(fn(C.byref(cscene), *ptrs, leaf_max, C.byref(info), nodes.ctypes.data_as(_f32p), nodes.size))
     d = {k: int(getattr(info, k)) for k, _ in BvhInfo._fields_ if k not in ("centre", "flat_m", "flat_e")}
     d["flat_m"], d["flat_e"] = np.float32(info.flat_m), np.float32(info.flat_e)
     d["centre"] = np.array(list(info.centre), np.float32)

@@ -542,16 +542,11 @@ int r1_active_spheres(const r1_scene *s, std::vector<uint32_t> &active_to_scene)
 // 1/r of the same r (soa_sphere.cpp:70-85), but a C-ABI caller may hand over arrays that disagree
 // (or a negative inv_radius): taking the larger of the two keeps every bound conservative for
 // whatever the exact test can accept instead of silently dropping hits.
-double r1_bound_radius(float radius_sq, float inv_radius)
-{
-    const double from_sq = radius_sq > 0 ? std::sqrt((double)radius_sq) : 0.0;
-    const double from_inv = std::isfinite(inv_radius) && inv_radius != 0 ? 1.0 / std::fabs((double)inv_radius) : 0.0;
-    return std::max(from_sq, from_inv);
-}
+double r1_bound_radius(float radius_sq, float inv_radius) { return r1f_bound_radius(radius_sq, inv_radius); }
 
 // The radius whose error terms E1 / (2 r) the pad follows: the one the exact test itself uses, sqrt(radius_sq), never more than the bound
-// radius — the smaller, safer one (r1f_sphere_box's r_test).
-double r1_test_radius(double rbound, float radius_sq) { return radius_sq > 0 ? std::min(rbound, std::sqrt((double)radius_sq)) : 0.0; }
+// radius — the smaller, safer one (r1f_sphere_box's r_test).  Both in r1_bvh_fill.h: the device derives them too (r1_update_spheres*).
+double r1_test_radius(double rbound, float radius_sq) { return r1f_test_radius(rbound, radius_sq); }
 
 // ---- refit ----------------------------------------------------------------------
 
@@ -673,13 +668,15 @@ static void describe_info(const Described &d, r1_bvh_info *info)
     info->pairs = (int32_t)(b.ids.size() / 2);
 }
 
-// Host-only pin of the refit (include/rays1.h): the tree of `built`, refitted to the scene-indexed centres x, y, z.
-extern "C" int r1_bvh_refit_describe(const r1_scene *built, const float *x, const float *y, const float *z, int32_t leaf_max, r1_bvh_info *info,
-                                     float *nodes_out, size_t nodes_cap)
+// Host-only pin of the refit (include/rays1.h): the tree of `built`, refitted to the scene-indexed centres x, y, z and, where given, to the
+// scene-indexed radii — each pair as the device's set kernel writes it (r1f_radius_rows: a pair that would make the sphere inactive leaves it
+// never hittable, radius_sq -inf and radii {0, 0}).
+static int refit_describe(const char *who, const r1_scene *built, const float *x, const float *y, const float *z, const float *radius_sq,
+                          const float *inv_radius, int32_t leaf_max, r1_bvh_info *info, float *nodes_out, size_t nodes_cap)
 {
-    if (!built || !info || !x || !y || !z)
+    if (!built || !info || !x || !y || !z || !radius_sq != !inv_radius)
     {
-        r1_set_error("r1_bvh_refit_describe: null argument");
+        r1_set_error("%s: null argument", who);
         return R1_EINVAL;
     }
     Described d;
@@ -692,6 +689,13 @@ extern "C" int r1_bvh_refit_describe(const r1_scene *built, const float *x, cons
     {
         const uint32_t i = d.scene_index[a];
         d.x[a] = x[i], d.y[a] = y[i], d.z[a] = z[i];
+        if (radius_sq)
+        {
+            float inv;
+            double rr[2];
+            r1f_radius_rows(radius_sq[i], inv_radius[i], d.r[a], inv, rr);
+            d.rb[a] = rr[0]; // (r1_bvh_refit_host derives the test radius from this and d.r as r1f_radius_rows does)
+        }
     }
     r1_bvh_refit_host(d.b, t, d.na, d.x.data(), d.y.data(), d.z.data(), d.r.data(), d.rb.data());
     describe_info(d, info);
@@ -703,6 +707,18 @@ extern "C" int r1_bvh_refit_describe(const r1_scene *built, const float *x, cons
         memcpy(nodes_out, d.b.nodes.data(), d.b.nodes.size() * 4);
     }
     return R1_OK;
+}
+
+extern "C" int r1_bvh_refit_describe(const r1_scene *built, const float *x, const float *y, const float *z, int32_t leaf_max, r1_bvh_info *info,
+                                     float *nodes_out, size_t nodes_cap)
+{
+    return refit_describe("r1_bvh_refit_describe", built, x, y, z, nullptr, nullptr, leaf_max, info, nodes_out, nodes_cap);
+}
+
+extern "C" int r1_bvh_refit_describe_spheres(const r1_scene *built, const float *x, const float *y, const float *z, const float *radius_sq,
+                                             const float *inv_radius, int32_t leaf_max, r1_bvh_info *info, float *nodes_out, size_t nodes_cap)
+{
+    return refit_describe("r1_bvh_refit_describe_spheres", built, x, y, z, radius_sq, inv_radius, leaf_max, info, nodes_out, nodes_cap);
 }
 
 // Host-only view of the index (include/rays1.h): what r1_set_scene would build for this scene.

@@ -41,6 +41,52 @@ R1F_HD float r1f_round_up(double v)
     return r1f_next_up(f);
 }
 
+// ---- what the builders derive per sphere from the caller's arrays (r1_bvh.cpp r1_bound_radius / r1_test_radius, r1_sweep.cpp's material rows):
+// here so that the device derives the same bits when a sphere's radius or material changes in place (r1_refit.hip) ----
+
+// Radius every conservative bound must cover: the larger of sqrt(radius_sq) and 1 / |inv_radius| (r1_bvh.cpp r1_bound_radius has the why)
+R1F_HD double r1f_bound_radius(float radius_sq, float inv_radius)
+{
+    const double from_sq = radius_sq > 0 ? __builtin_sqrt((double)radius_sq) : 0.0;
+    const double from_inv = r1f_finite(inv_radius) && inv_radius != 0 ? 1.0 / r1f_abs((double)inv_radius) : 0.0;
+    return r1f_max(from_sq, from_inv);
+}
+
+// The radius whose error terms the pad follows: sqrt(radius_sq), never more than the bound radius (r1f_sphere_box's r_test)
+R1F_HD double r1f_test_radius(double rbound, float radius_sq) { return radius_sq > 0 ? r1f_min(rbound, __builtin_sqrt((double)radius_sq)) : 0.0; }
+
+// Would r1_active_spheres keep a sphere of this pair?  inv_radius != 0 (rayweek1.cpp:291) and not NaN, radius_sq finite.
+R1F_HD bool r1f_hittable_radius(float radius_sq, float inv_radius) { return inv_radius == inv_radius && inv_radius != 0 && r1f_finite(radius_sq); }
+
+// A new {radius_sq, inv_radius} of an active sphere, as every table holds it: rsq (exact[a].w and the sphere's word of its leaf pair), inv
+// (shade[a].x) and radii {bound, test}.  A pair r1_active_spheres would drop makes the sphere never hittable in place: radius_sq = -inf as the
+// partner of an odd sphere has it (the exact test's discriminant is -inf), radii {0, 0}.
+R1F_HD void r1f_radius_rows(float radius_sq, float inv_radius, float &rsq, float &inv, double radii[2])
+{
+    if (!r1f_hittable_radius(radius_sq, inv_radius))
+    {
+        rsq = -__builtin_inff(), inv = 0.0f, radii[0] = radii[1] = 0.0;
+        return;
+    }
+    rsq = radius_sq, inv = inv_radius;
+    radii[0] = r1f_bound_radius(radius_sq, inv_radius);
+    radii[1] = r1f_test_radius(radii[0], radius_sq);
+}
+
+// A material's row {type, param, 1 / ref_idx, schlick r0}: the dielectric constants the reference recomputes per hit with IEEE fp32 operations
+// (rayweek1.cpp:489 `1.0f / _refIdx`, :456-457 schlick r0), the same operations in the same order, done once.  Both need a correctly rounded
+// fp32 divide that keeps denormals (the Makefile's -fhip-fp32-correctly-rounded-divide-sqrt on the device; DESIGN.md §4.27 has the check).
+R1F_HD void r1f_material_row(uint32_t type, float param, float row[4])
+{
+    const float ref_idx = param;
+    float r0 = (1 - ref_idx) / (1 + ref_idx);
+    r0 = r0 * r0;
+    row[0] = __builtin_bit_cast(float, type);
+    row[1] = ref_idx;
+    row[2] = type == 2u /* R1_MAT_DIELECTRIC */ ? 1.0f / ref_idx : 0.0f;
+    row[3] = type == 2u ? r0 : 0.0f;
+}
+
 struct R1Box
 {
     double lo[3], hi[3];   // of the spheres' extents c +- r
@@ -264,5 +310,19 @@ struct R1RefitArgs
     uint32_t n_nodes, n_leaves;
     R1FillConst fill;
 };
+
+// What r1_refit_set_kernel reads and writes besides (r1_update_spheres*): the scene's shading rows and the refit's radii, and the caller's
+// arrays of the range (device-readable memory, entry i belongs to scene index first + i; a group that is not written: null)
+struct R1SetArgs
+{
+    float *shade;  // [active][4] {inv_radius, albedo r, g, b}
+    float *mat;    // [active][4] {type, param, 1 / ref_idx, schlick r0}
+    double *radii; // [active][2]: R1RefitArgs::radii, writable
+    const float *radius_sq, *inv_radius;
+    const uint8_t *mat_type;
+    const float *albedo_r, *albedo_g, *albedo_b, *mat_param;
+};
+#define R1_SET_RADII 1u
+#define R1_SET_MATERIALS 2u
 
 #endif

@@ -165,9 +165,10 @@ struct r1_context
     std::vector<uint32_t> refit_height_off; // R1RefitTopo::height_off
     std::vector<uint32_t> scene_to_active;  // 0xFFFFFFFF: not active
     bool moved = false;        // an update since the last r1_set_scene: the sphere groups and the grid are stale, src_f32 may be
-    float *stage = nullptr, *stage_dev = nullptr; // host form: page-locked staging of the centres, read by the move kernel
+    bool src_stale = false;    // r1_update_spheres_device since the last r1_set_scene: the host copies (src_f32, src_mat) never saw its values
+    float *stage = nullptr, *stage_dev = nullptr; // host form: page-locked staging of the caller's arrays, read by the move and the set kernel
     size_t stage_cap = 0;      // floats
-    hipEvent_t stage_ev = nullptr; // recorded behind the move kernel that reads `stage`
+    hipEvent_t stage_ev = nullptr; // recorded behind the last kernel that reads `stage`
     bool stage_busy = false;
 
     r1_launch_info info;

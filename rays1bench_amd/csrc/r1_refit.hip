@@ -1,5 +1,6 @@
 // r1_refit.hip — moving spheres (r1_update_centers*): new centres into the tables the tree kernels read, then the box tree's
-// rows recomputed bottom-up over its unchanged topology, in r1_bvh_fill.h's arithmetic — the host builder's own, bit for bit.
+// rows recomputed bottom-up over its unchanged topology, in r1_bvh_fill.h's arithmetic — the host builder's own, bit for bit.  And sphere
+// updates (r1_update_spheres*, §4.27): radii and materials into the same tables, then the same refit where a radius changed.
 //
 // The hand-over between the tree's heights is the KERNEL BOUNDARY: plain stores are not seen across XCDs inside a kernel, and a release fence
 // costs ~105 us under load (profiles/r04/xcd_visibility.txt) — a bottom-up walk with arrival counters inside one kernel
@@ -29,6 +30,45 @@ __global__ void __launch_bounds__(R1_REFIT_BLOCK) r1_refit_move_kernel(R1RefitAr
     const uint32_t q = A.slot[a];
     float *p = A.prims + 8 * (size_t)(q >> 1) + (q & 1u);
     p[0] = cx, p[2] = cy, p[4] = cz;
+}
+
+// Radii and materials changed in place (r1_update_spheres*).  One lane per sphere of the range [first, first + count) of the
+// SCENE; `groups` says which of the two groups the launch writes.  R1_SET_RADII: the new radius_sq into exact[a].w and into the sphere's word
+// of its leaf pair (the slot the move kernel addresses), inv_radius into shade[a].x, {bound, test} radius into the refit's table — what the
+// builders derive, in their arithmetic (r1f_radius_rows); a pair that r1_active_spheres would drop makes the sphere never hittable.
+// R1_SET_MATERIALS: the albedo into shade[a].yzw and the whole mat[a] row (r1f_material_row); a type that is no material is skipped.
+__global__ void __launch_bounds__(R1_REFIT_BLOCK) r1_refit_set_kernel(R1RefitArgs A, R1SetArgs S, uint32_t first, uint32_t count, uint32_t groups)
+{
+    const uint32_t i = blockIdx.x * R1_REFIT_BLOCK + threadIdx.x;
+    if (i >= count)
+        return;
+    const uint32_t a = A.scene_to_active[first + i];
+    if (a == 0xFFFFFFFFu)
+        return;
+    float *sh = S.shade + 4 * (size_t)a;
+    if (groups & R1_SET_RADII)
+    {
+        float rsq, inv;
+        double rr[2];
+        r1f_radius_rows(S.radius_sq[i], S.inv_radius[i], rsq, inv, rr);
+        A.exact[4 * (size_t)a + 3] = rsq;
+        const uint32_t q = A.slot[a];
+        A.prims[8 * (size_t)(q >> 1) + 6 + (q & 1u)] = rsq;
+        sh[0] = inv;
+        S.radii[2 * (size_t)a + 0] = rr[0], S.radii[2 * (size_t)a + 1] = rr[1];
+    }
+    if (groups & R1_SET_MATERIALS)
+    {
+        const uint32_t type = S.mat_type[i];
+        if (type <= 2u /* R1_MAT_DIELECTRIC */)
+        {
+            float row[4];
+            r1f_material_row(type, S.mat_param[i], row);
+            sh[1] = S.albedo_r[i], sh[2] = S.albedo_g[i], sh[3] = S.albedo_b[i];
+            float *m = S.mat + 4 * (size_t)a;
+            m[0] = row[0], m[1] = row[1], m[2] = row[2], m[3] = row[3];
+        }
+    }
 }
 
 // One lane per leaf: its spheres' boxes merged in fp64 into the leaf's scratch entry.  Lane 0 of the launch also zeroes the largest-A word
@@ -72,6 +112,14 @@ extern "C" hipError_t r1_launch_refit_move(const R1RefitArgs *a, uint32_t first,
     if (count == 0)
         return hipSuccess;
     hipLaunchKernelGGL(r1_refit_move_kernel, dim3(refit_blocks(count)), dim3(R1_REFIT_BLOCK), 0, stream, *a, first, count, x, y, z);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t r1_launch_refit_set(const R1RefitArgs *a, const R1SetArgs *s, uint32_t first, uint32_t count, uint32_t groups, hipStream_t stream)
+{
+    if (count == 0 || !(groups & (R1_SET_RADII | R1_SET_MATERIALS)))
+        return hipSuccess;
+    hipLaunchKernelGGL(r1_refit_set_kernel, dim3(refit_blocks(count)), dim3(R1_REFIT_BLOCK), 0, stream, *a, *s, first, count, groups);
     return hipGetLastError();
 }
 

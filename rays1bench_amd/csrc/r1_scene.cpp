@@ -45,8 +45,9 @@ extern "C" int r1_set_scene(r1_context *c, const r1_scene *s, const r1_camera *c
     R1_HIP(hipSetDevice(c->device));
 
     const float *const src[9] = {s->center_x, s->center_y, s->center_z, s->radius_sq, s->inv_radius, s->albedo_r, s->albedo_g, s->albedo_b, s->mat_param};
-    // (not after r1_update_centers*: the device holds other centres than src_f32, or the groups and the grid are those of other centres)
-    if (c->have_scene && !c->moved && c->src_mat.size() == s->count && memcmp(&c->src_cam, cam, sizeof(*cam)) == 0 &&
+    // (not after r1_update_centers*: the device holds other centres than src_f32, or the groups and the grid are those of other centres;
+    // nor after a device-form r1_update_spheres_device of materials, which the host copies never saw)
+    if (c->have_scene && !c->moved && !c->src_stale && c->src_mat.size() == s->count && memcmp(&c->src_cam, cam, sizeof(*cam)) == 0 &&
         (s->count == 0 || memcmp(c->src_mat.data(), s->mat_type, s->count) == 0))
     {
         bool same = true;
@@ -174,7 +175,7 @@ extern "C" int r1_set_scene(r1_context *c, const r1_scene *s, const r1_camera *c
         r.fill = bvh.fill;
         c->refit_height_off = topo.height_off;
     }
-    c->moved = false;
+    c->moved = false, c->src_stale = false;
     c->n_bvh_nodes = (uint32_t)(bvh.nodes.size() / 16);
     c->n_bvh_leaves = bvh.n_leaves;
     c->bvh_depth = bvh.max_depth;
@@ -271,6 +272,27 @@ static int update_enqueue(r1_context *c, uint32_t first, uint32_t count, const f
     return R1_OK;
 }
 
+// The page-locked staging buffer of the host forms, at least `floats` floats of it, free to be written: the kernels of the previous update may
+// still be reading it, so their event is waited for first.
+static int stage_reserve(r1_context *c, size_t floats)
+{
+    if (c->stage_busy)
+        R1_HIP(hipEventSynchronize(c->stage_ev));
+    c->stage_busy = false;
+    if (!c->stage_ev)
+        R1_HIP(hipEventCreateWithFlags(&c->stage_ev, hipEventDisableTiming));
+    if (c->stage_cap < floats)
+    {
+        if (c->stage)
+            R1_HIP(hipHostFree(c->stage));
+        c->stage = c->stage_dev = nullptr, c->stage_cap = 0;
+        R1_HIP(hipHostMalloc((void **)&c->stage, floats * 4, hipHostMallocMapped));
+        R1_HIP(hipHostGetDevicePointer((void **)&c->stage_dev, c->stage, 0));
+        c->stage_cap = floats;
+    }
+    return R1_OK;
+}
+
 extern "C" int r1_update_centers(r1_context *c, uint32_t first, uint32_t count, const float *x, const float *y, const float *z, void *hip_stream)
 {
     int rc = update_check("r1_update_centers", c, first, count, x, y, z);
@@ -284,21 +306,8 @@ extern "C" int r1_update_centers(r1_context *c, uint32_t first, uint32_t count, 
         }
     R1_HIP(hipSetDevice(c->device));
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    // the staging buffer: the move kernel of the previous update may still be reading it
-    if (c->stage_busy)
-        R1_HIP(hipEventSynchronize(c->stage_ev));
-    c->stage_busy = false;
-    if (!c->stage_ev)
-        R1_HIP(hipEventCreateWithFlags(&c->stage_ev, hipEventDisableTiming));
-    if (c->stage_cap < 3 * (size_t)count)
-    {
-        if (c->stage)
-            R1_HIP(hipHostFree(c->stage));
-        c->stage = c->stage_dev = nullptr, c->stage_cap = 0;
-        R1_HIP(hipHostMalloc((void **)&c->stage, 3 * (size_t)count * 4, hipHostMallocMapped));
-        R1_HIP(hipHostGetDevicePointer((void **)&c->stage_dev, c->stage, 0));
-        c->stage_cap = 3 * (size_t)count;
-    }
+    if ((rc = stage_reserve(c, 3 * (size_t)count)))
+        return rc;
     memcpy(c->stage, x, (size_t)count * 4), memcpy(c->stage + count, y, (size_t)count * 4), memcpy(c->stage + 2 * (size_t)count, z, (size_t)count * 4);
     c->stage_busy = true; // (from here on: a launch that failed half-way may still have enqueued the move)
     if ((rc = update_enqueue(c, first, count, c->stage_dev, c->stage_dev + count, c->stage_dev + 2 * (size_t)count, st, c->stage_ev)))
@@ -321,6 +330,188 @@ extern "C" int r1_update_centers_device(r1_context *c, uint32_t first, uint32_t 
     }
     R1_HIP(hipSetDevice(c->device));
     return update_enqueue(c, first, count, (const float *)d_x, (const float *)d_y, (const float *)d_z, hip_stream ? (hipStream_t)hip_stream : c->stream, nullptr);
+}
+
+// ---- sphere updates: radii and materials besides the centres (include/rays1.h "sphere updates", r1_refit.hip) -----------
+
+// which groups of *u are given (bit 0 centres, R1_SET_RADII << 1, R1_SET_MATERIALS << 1), or -1: a group given in part, or none at all
+static int update_groups(const char *who, const r1_sphere_update *u)
+{
+    const int nc = !!u->center_x + !!u->center_y + !!u->center_z, nr = !!u->radius_sq + !!u->inv_radius;
+    const int nm = !!u->mat_type + !!u->albedo_r + !!u->albedo_g + !!u->albedo_b + !!u->mat_param;
+    if ((nc && nc != 3) || (nr && nr != 2) || (nm && nm != 5))
+    {
+        r1_set_error("%s: the %s group is given in part (all of a group's pointers, or none)", who, nc && nc != 3 ? "centres" : (nr && nr != 2 ? "radii" : "materials"));
+        return -1;
+    }
+    if (!nc && !nr && !nm)
+    {
+        r1_set_error("%s: every group of the update is NULL with count > 0", who);
+        return -1;
+    }
+    return (nc ? 1 : 0) | (nr ? (int)(R1_SET_RADII << 1) : 0) | (nm ? (int)(R1_SET_MATERIALS << 1) : 0);
+}
+
+// update_check's rules in its order, then count == 0 (R1_OK, *groups stays 0), then the rules of *u
+static int spheres_check(const char *who, r1_context *c, uint32_t first, uint32_t count, const r1_sphere_update *u, int *groups)
+{
+    if (!c)
+    {
+        r1_set_error("%s: ctx is NULL", who);
+        return R1_EINVAL;
+    }
+    if (!c->have_scene)
+    {
+        r1_set_error("%s: no scene set (call r1_set_scene first)", who);
+        return R1_EINVAL;
+    }
+    if ((uint64_t)first + count > c->n_padded_scene)
+    {
+        r1_set_error("%s: spheres [%u, %llu) are beyond the scene's %u", who, first, (unsigned long long)first + count, c->n_padded_scene);
+        return R1_EINVAL;
+    }
+    if (count == 0)
+        return R1_OK;
+    if (!u)
+    {
+        r1_set_error("%s: u is NULL", who);
+        return R1_EINVAL;
+    }
+    return (*groups = update_groups(who, u)) < 0 ? R1_EINVAL : R1_OK;
+}
+
+// The launches on `st`, every array of *d from memory the device can read: the move (the centres' own kernel), the set kernel, `read_ev` (or
+// null) straight behind the last reader of the caller's arrays, then ONE refit if a centre or a radius changed; then what the update changes in
+// the context.  A change of radius leaves the context in the state of a centre update; materials alone change no index and refuse nothing.
+static int spheres_enqueue(r1_context *c, uint32_t first, uint32_t count, const r1_sphere_update *d, int groups, hipStream_t st, hipEvent_t read_ev)
+{
+    if (groups & 1)
+        R1_HIP(r1_launch_refit_move(&c->refit, first, count, d->center_x, d->center_y, d->center_z, st));
+    if (groups >> 1)
+    {
+        R1SetArgs s;
+        s.shade = (float *)c->shade.p, s.mat = (float *)c->mat.p, s.radii = (double *)c->refit_radii.p;
+        s.radius_sq = d->radius_sq, s.inv_radius = d->inv_radius, s.mat_type = d->mat_type;
+        s.albedo_r = d->albedo_r, s.albedo_g = d->albedo_g, s.albedo_b = d->albedo_b, s.mat_param = d->mat_param;
+        R1_HIP(r1_launch_refit_set(&c->refit, &s, first, count, (uint32_t)groups >> 1, st));
+    }
+    if (read_ev)
+        R1_HIP(hipEventRecord(read_ev, st));
+    c->pass_valid = false; // (a progressive frame does not continue across a change of the scene)
+    if (!(groups & (1 | (int)(R1_SET_RADII << 1))))
+        return R1_OK;
+    if (c->n_active) // (a tree of 0 spheres has nothing to refit)
+        R1_HIP(r1_launch_refit(&c->refit, c->refit_height_off.data(), (uint32_t)c->refit_height_off.size() - 1u, st));
+    c->moved = true;
+    c->grid_valid = false;
+    c->bvh_flat_m = 0.0f, c->bvh_flat_e = -1.0f; // the flat y slab is dropped, as update_enqueue drops it
+    return R1_OK;
+}
+
+extern "C" int r1_update_spheres(r1_context *c, uint32_t first, uint32_t count, const r1_sphere_update *u, void *hip_stream)
+{
+    int groups = 0, rc = spheres_check("r1_update_spheres", c, first, count, u, &groups);
+    if (rc || count == 0)
+        return rc;
+    const bool centres = groups & 1, radii = groups & (int)(R1_SET_RADII << 1), mats = groups & (int)(R1_SET_MATERIALS << 1);
+    for (uint32_t i = 0; i < count; ++i)
+    {
+        if (c->scene_to_active[first + i] == 0xFFFFFFFFu)
+            continue;
+        if (centres && !(std::isfinite(u->center_x[i]) && std::isfinite(u->center_y[i]) && std::isfinite(u->center_z[i])))
+        {
+            r1_set_error("r1_update_spheres: the new centre of sphere %u is not finite", first + i);
+            return R1_EINVAL;
+        }
+        if (radii && !r1f_hittable_radius(u->radius_sq[i], u->inv_radius[i]))
+        {
+            r1_set_error("r1_update_spheres: the new radius of sphere %u (radius_sq %g, inv_radius %g) would make it inactive; the active set does not change",
+                         first + i, (double)u->radius_sq[i], (double)u->inv_radius[i]);
+            return R1_EINVAL;
+        }
+        if (mats && u->mat_type[i] > R1_MAT_DIELECTRIC)
+        {
+            r1_set_error("r1_update_spheres: sphere %u is hittable but mat_type %u is no material", first + i, (unsigned)u->mat_type[i]);
+            return R1_EINVAL;
+        }
+    }
+    R1_HIP(hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    // the staging buffer (the centres' own, grown): up to 9 floats and 1 byte per sphere; the previous update's kernels may still be reading it
+    const size_t n_f32 = (centres ? 3 : 0) + (radii ? 2 : 0) + (mats ? 4 : 0);
+    if ((rc = stage_reserve(c, n_f32 * count + (mats ? ((size_t)count + 3) / 4 : 0))))
+        return rc;
+    // the given arrays one after the other, the material types behind the last of them
+    const float *const src[9] = {u->center_x, u->center_y, u->center_z, u->radius_sq, u->inv_radius, u->albedo_r, u->albedo_g, u->albedo_b, u->mat_param};
+    const float *dev[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    size_t at = 0;
+    for (int k = 0; k < 9; ++k)
+        if (src[k])
+            memcpy(c->stage + at, src[k], (size_t)count * 4), dev[k] = c->stage_dev + at, at += count;
+    r1_sphere_update d;
+    d.center_x = dev[0], d.center_y = dev[1], d.center_z = dev[2], d.radius_sq = dev[3], d.inv_radius = dev[4];
+    d.albedo_r = dev[5], d.albedo_g = dev[6], d.albedo_b = dev[7], d.mat_param = dev[8], d.mat_type = nullptr;
+    if (mats)
+        memcpy(c->stage + at, u->mat_type, count), d.mat_type = (const uint8_t *)(c->stage_dev + at);
+    c->stage_busy = true; // (from here on: a launch that failed half-way may still have enqueued a reader)
+    if ((rc = spheres_enqueue(c, first, count, &d, groups, st, c->stage_ev)))
+        return rc;
+    // the context's host copies follow (entries of spheres that are not active too: they are what r1_set_scene would be given)
+    for (int k = 0; k < 9; ++k)
+        if (src[k])
+            memcpy(c->src_f32[k].data() + first, src[k], (size_t)count * 4);
+    if (mats)
+        memcpy(c->src_mat.data() + first, u->mat_type, count);
+    return R1_OK;
+}
+
+extern "C" int r1_update_spheres_device(r1_context *c, uint32_t first, uint32_t count, const r1_sphere_update *u, void *hip_stream)
+{
+    int groups = 0, rc = spheres_check("r1_update_spheres_device", c, first, count, u, &groups);
+    if (rc || count == 0)
+        return rc;
+    if (((uintptr_t)u->center_x | (uintptr_t)u->center_y | (uintptr_t)u->center_z | (uintptr_t)u->radius_sq | (uintptr_t)u->inv_radius | (uintptr_t)u->albedo_r |
+         (uintptr_t)u->albedo_g | (uintptr_t)u->albedo_b | (uintptr_t)u->mat_param) & 3u)
+    {
+        r1_set_error("r1_update_spheres_device: every float array must be 4-byte aligned");
+        return R1_EINVAL;
+    }
+    R1_HIP(hipSetDevice(c->device));
+    if ((rc = spheres_enqueue(c, first, count, u, groups, hip_stream ? (hipStream_t)hip_stream : c->stream, nullptr)))
+        return rc;
+    c->src_stale = true; // the host cannot see the values: r1_set_scene rebuilds whatever it is given
+    return R1_OK;
+}
+
+extern "C" int r1_tables_download(r1_context *c, float *exact, float *shade, uint32_t *mat, double *radii, size_t cap_active, size_t *n_active)
+{
+    if (!c || !n_active)
+    {
+        r1_set_error("r1_tables_download: %s is NULL", !c ? "ctx" : "n_active");
+        return R1_EINVAL;
+    }
+    if (!c->have_scene)
+    {
+        r1_set_error("r1_tables_download: no scene set (call r1_set_scene first)");
+        return R1_EINVAL;
+    }
+    const size_t na = *n_active = c->n_active;
+    if (!exact && !shade && !mat && !radii)
+        return R1_OK;
+    if (cap_active < na)
+        return R1_ELIMIT;
+    R1_HIP(hipSetDevice(c->device));
+    const struct
+    {
+        void *dst;
+        const void *src;
+        size_t bytes;
+    } parts[4] = {{exact, c->exact.p, 16 * na}, {shade, c->shade.p, 16 * na}, {mat, c->mat.p, 16 * na}, {radii, c->refit_radii.p, 16 * na}};
+    for (const auto &q : parts)
+        if (q.dst && q.bytes)
+            R1_HIP(hipMemcpyAsync(q.dst, q.src, q.bytes, hipMemcpyDeviceToHost, c->stream));
+    R1_HIP(hipStreamSynchronize(c->stream));
+    return R1_OK;
 }
 
 extern "C" int r1_bvh_download(r1_context *c, float *nodes_out, size_t nodes_cap, size_t *nodes)

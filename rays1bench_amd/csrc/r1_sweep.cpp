@@ -225,16 +225,8 @@ void r1_build_sweep(const r1_scene *s, const std::vector<uint32_t> &active_to_sc
         exact[4 * a + 0] = cx, exact[4 * a + 1] = cy, exact[4 * a + 2] = cz, exact[4 * a + 3] = rsq;
         shade[4 * a + 0] = s->inv_radius[i], shade[4 * a + 1] = s->albedo_r[i], shade[4 * a + 2] = s->albedo_g[i],
                       shade[4 * a + 3] = s->albedo_b[i];
-        uint32_t type = s->mat_type[i];
-        memcpy(&mat[4 * a], &type, 4);
-        const float ref_idx = s->mat_param[i];
-        mat[4 * a + 1] = ref_idx;
-        // Dielectric constants the reference recomputes per hit with IEEE float ops
-        // (rayweek1.cpp:489 `1.0f / _refIdx`, :456-457 schlick r0): same operations, done once
-        float r0 = (1 - ref_idx) / (1 + ref_idx);
-        r0 = r0 * r0;
-        mat[4 * a + 2] = type == R1_MAT_DIELECTRIC ? 1.0f / ref_idx : 0.0f;
-        mat[4 * a + 3] = type == R1_MAT_DIELECTRIC ? r0 : 0.0f;
+        // the material's row, dielectric constants included: r1_bvh_fill.h, the arithmetic r1_update_spheres* runs on the device too
+        r1f_material_row(s->mat_type[i], s->mat_param[i], &mat[4 * a]);
     }
 
     // the members' spheres once more, in group order (exact_trips fetches sphere and index side by side)

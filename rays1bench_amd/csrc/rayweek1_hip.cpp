@@ -72,6 +72,7 @@ static int g_backend = 0; // 0 hip, 1 cpu-step1, 12 cpu-step12
 static int g_pipeline = 0; // --pipeline FRAMES: after the benchmark() runs, FRAMES frames per scene with several in flight (r1_render_async)
 static int g_inflight = 20;
 static int g_bounce = 0;   // --bounce FRAMES: after the benchmark() runs, FRAMES frames per scene with the lattice spheres bobbing in y, one r1_update_centers between frames
+static int g_pulse = 0;    // --pulse FRAMES: after the benchmark() runs, FRAMES frames per scene with the lattice spheres' radii breathing and their albedo cycling, one r1_update_spheres between frames
 static int g_orbit = 0;    // --orbit FRAMES: after the benchmark() runs, FRAMES frames per scene with the camera turned about the vertical axis through lookat (r1_render_path_async)
 static int g_passes = 0;   // --passes K: every frame in K progressive passes (r1_render_pass); 0 = one r1_render
 static bool g_adaptive = false; // --adaptive: every frame through r1_render_adaptive
@@ -637,10 +638,110 @@ static int bounce(const char *scene_name, int kind, int frames, bool write_tga)
     return rc == R1_OK ? 0 : 1;
 }
 
+// --pulse FRAMES: the lattice spheres (as for --bounce) breathe and change colour.  In frame f, with t = f / FRAMES, sphere i (scene index) has
+//      radius  r_i * (1 + 0.3 sin(2 pi t) cos(2 pi (i mod 8) / 8))          stored as SphereSOA::add stores a radius: r * r and 1 / r in fp32
+//      albedo  a_i + (a_i rotated r -> g -> b -> r  -  a_i) * (1 - cos(2 pi t)) / 2
+// the factors evaluated in fp64 and rounded to fp32; a factor of exactly 1 (frame 0) keeps the scene's own pair, so frame 0 is benchmark()'s
+// frame.  Material types and parameters stay.  One r1_update_spheres (radii and materials of every sphere) is enqueued between frames: the
+// box tree is refitted on the device, never rebuilt.  Prints one `pulse:` line per scene; with -w writes frame 0 and the middle frame.
+static int pulse(const char *scene_name, int kind, int frames, bool write_tga)
+{
+    r1_host_scene *hs = nullptr;
+    if (r1_host_scene_create(kind, g_screen_w, g_screen_h, 0, 0, &hs) != R1_OK)
+        return 1;
+    const r1_scene *sc = r1_host_scene_spheres(hs);
+    r1_params p;
+    memset(&p, 0, sizeof(p));
+    p.width = g_screen_w, p.height = g_screen_h, p.spp = g_spp, p.max_bounces = g_max_bounces, p.seed = g_seed;
+    p.tile_w = 32, p.tile_h = 32, p.shard = 0, p.num_shards = 1, p.variant = g_variant;
+    // the four largest hittable spheres stay as they are
+    std::vector<uint32_t> act;
+    for (uint32_t i = 0; i < sc->count; ++i)
+        if (sc->inv_radius[i] != 0)
+            act.push_back(i);
+    std::stable_sort(act.begin(), act.end(), [&](uint32_t a, uint32_t b) { return sc->radius_sq[a] > sc->radius_sq[b]; });
+    std::vector<char> pulses(sc->count ? sc->count : 1, 0);
+    for (size_t k = 4; k < act.size(); ++k)
+        pulses[act[k]] = 1;
+    std::vector<float> rsq(sc->radius_sq, sc->radius_sq + sc->count), inv(sc->inv_radius, sc->inv_radius + sc->count);
+    std::vector<float> ar(sc->albedo_r, sc->albedo_r + sc->count), ag(sc->albedo_g, sc->albedo_g + sc->count), ab(sc->albedo_b, sc->albedo_b + sc->count);
+    const size_t img_bytes = (size_t)g_screen_w * g_screen_h * 3, rec = r1_frame_record_bytes(&p);
+    r1_context *ctx = nullptr;
+    uint8_t *host = nullptr;
+    const int visible = r1_device_count();
+    int rc = r1_create(g_device % (visible > 0 ? visible : 1), &ctx);
+    if (rc == R1_OK)
+        rc = r1_set_scene(ctx, sc, r1_host_scene_camera(hs));
+    if (rc == R1_OK)
+        rc = r1_host_alloc(rec, (void **)&host);
+    const int keep_frame[2] = {0, frames / 2};
+    std::vector<uint8_t> keep[2];
+    uint64_t rays = 0;
+    double t_update = 0, t_render = 0;
+    for (int f = -1; f < frames && rc == R1_OK; ++f) // f = -1: workspaces and queues (frame 0 once more, not timed)
+    {
+        const int ff = f < 0 ? 0 : f;
+        const double t = (double)ff / (double)frames, swing = 0.3 * sin(2.0 * M_PI * t), mix = 0.5 * (1.0 - cos(2.0 * M_PI * t));
+        for (uint32_t i = 0; i < sc->count; ++i)
+            if (pulses[i])
+            {
+                const double scale = 1.0 + swing * cos(2.0 * M_PI * (double)(i % 8u) / 8.0);
+                rsq[i] = sc->radius_sq[i], inv[i] = sc->inv_radius[i];
+                if (scale != 1.0)
+                {
+                    const float r = (float)(scale / (double)sc->inv_radius[i]);
+                    rsq[i] = r * r, inv[i] = 1.0f / r;
+                }
+                const float a[3] = {sc->albedo_r[i], sc->albedo_g[i], sc->albedo_b[i]};
+                ar[i] = (float)((double)a[0] + ((double)a[2] - (double)a[0]) * mix);
+                ag[i] = (float)((double)a[1] + ((double)a[0] - (double)a[1]) * mix);
+                ab[i] = (float)((double)a[2] + ((double)a[1] - (double)a[2]) * mix);
+            }
+        r1_sphere_update u;
+        memset(&u, 0, sizeof(u));
+        u.radius_sq = rsq.data(), u.inv_radius = inv.data();
+        u.mat_type = sc->mat_type, u.albedo_r = ar.data(), u.albedo_g = ag.data(), u.albedo_b = ab.data(), u.mat_param = sc->mat_param;
+        auto t0 = std::chrono::high_resolution_clock::now();
+        rc = r1_update_spheres(ctx, 0, sc->count, &u, nullptr);
+        if (rc == R1_OK)
+            rc = r1_sync(ctx);
+        auto t1 = std::chrono::high_resolution_clock::now();
+        if (rc == R1_OK)
+            rc = r1_render_async(ctx, &p, host, (uint64_t *)(host + rec - 8), nullptr);
+        if (rc == R1_OK)
+            rc = r1_sync(ctx);
+        auto t2 = std::chrono::high_resolution_clock::now();
+        if (f < 0 || rc != R1_OK)
+            continue;
+        t_update += std::chrono::duration<double>(t1 - t0).count(), t_render += std::chrono::duration<double>(t2 - t1).count();
+        rays += *(const uint64_t *)(host + rec - 8);
+        for (int w = 0; w < 2; ++w)
+            if (write_tga && f == keep_frame[w])
+                keep[w].assign(host, host + img_bytes);
+    }
+    if (rc == R1_OK)
+        printf("%s pulse: %d frames, %zu of %u spheres pulsing, update %.3f ms per frame (enqueue to idle), render %.3f ms per frame, %llu rays, %0.2f mrays/s\n",
+               scene_name, frames, act.size() > 4 ? act.size() - 4 : (size_t)0, sc->count, t_update / frames * 1e3, t_render / frames * 1e3,
+               (unsigned long long)rays, rays / (t_update + t_render) / 1e6);
+    else
+        fprintf(stderr, "pulse %s: %s\n", scene_name, r1_last_error());
+    for (int w = 0; w < 2 && rc == R1_OK && write_tga; ++w)
+        if (!keep[w].empty() && (w == 0 || keep_frame[1] != keep_frame[0]))
+        {
+            char filename[128];
+            snprintf(filename, sizeof(filename), "pulse_%s_%03d.tga", scene_name, keep_frame[w]);
+            r1_tga_write_rgb24(filename, g_screen_w, g_screen_h, keep[w].data());
+        }
+    r1_host_free(host);
+    r1_destroy(ctx);
+    r1_host_scene_destroy(hs);
+    return rc == R1_OK ? 0 : 1;
+}
+
 int main(int argc, const char *argv[])
 {
     bool write_tga = false;
-    bool passes_given = false, orbit_given = false, bounce_given = false, adapt_fields_ok = true, adapt_sub_given = false;
+    bool passes_given = false, orbit_given = false, bounce_given = false, pulse_given = false, adapt_fields_ok = true, adapt_sub_given = false;
     int num_runs = 1;
     const static int MAX_NUMS = 32;
     RESULT results[MAX_NUMS];
@@ -684,6 +785,11 @@ int main(int argc, const char *argv[])
         {
             g_bounce = atoi(argv[++i]);
             bounce_given = true;
+        }
+        else if (strcmp(argv[i], "--pulse") == 0 && i + 1 < argc)
+        {
+            g_pulse = atoi(argv[++i]);
+            pulse_given = true;
         }
         else if (strcmp(argv[i], "--passes") == 0 && i + 1 < argc)
         {
@@ -736,6 +842,13 @@ int main(int argc, const char *argv[])
     {
         fprintf(stderr, "bad --bounce %d: needs FRAMES >= 1, the hip backend, one device (no --gather rccl), --variant 0 or 4 (an update refits the box tree only), "
                         "no --passes and no --adaptive\n", g_bounce);
+        return 1;
+    }
+    if (pulse_given && (g_pulse < 1 || g_backend != 0 || g_devices > 1 || g_gather == 1 || passes_given || g_adaptive ||
+                        !(g_variant == R1_VARIANT_DEFAULT || g_variant == R1_VARIANT_BVH)))
+    {
+        fprintf(stderr, "bad --pulse %d: needs FRAMES >= 1, the hip backend, one device (no --gather rccl), --variant 0 or 4 (a change of radius refits the box tree only), "
+                        "no --passes and no --adaptive\n", g_pulse);
         return 1;
     }
     if (passes_given && (g_passes < 1 || g_passes > g_spp || g_backend != 0 || g_devices > 1 || g_gather == 1 || g_pipeline > 0))
@@ -843,6 +956,13 @@ int main(int argc, const char *argv[])
         rc_pipe |= bounce("small", R1_SCENE_SMALL, g_bounce, write_tga);
         rc_pipe |= bounce("medium", R1_SCENE_MEDIUM, g_bounce, write_tga);
         rc_pipe |= bounce("large", R1_SCENE_LARGE, g_bounce, write_tga);
+    }
+
+    if (g_pulse > 0)
+    {
+        rc_pipe |= pulse("small", R1_SCENE_SMALL, g_pulse, write_tga);
+        rc_pipe |= pulse("medium", R1_SCENE_MEDIUM, g_pulse, write_tga);
+        rc_pipe |= pulse("large", R1_SCENE_LARGE, g_pulse, write_tga);
     }
 
     if (pixels_pinned)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""tools/update_bench.py — moving spheres (r1_update_centers*) against the only way there was to move one, r1_set_scene
-(measurement tool; needs a GPU, reads no file outside the repository).
+"""tools/update_bench.py — moving spheres (r1_update_centers*) and sphere updates (r1_update_spheres*, §4.27) against the
+only way there was to change a sphere, r1_set_scene (measurement tool; needs a GPU, reads no file outside the repository).
 
 On the 100 004-sphere lattice of BASELINE config 5 (grid 400 x 250) at 1200 x 800 x 10, one context, in ONE session and alternating:
   (a) the time of one update of every centre, host form and device form (enqueue to stream idle), against one r1_set_scene with the
@@ -10,8 +10,14 @@ On the 100 004-sphere lattice of BASELINE config 5 (grid 400 x 250) at 1200 x 80
       frames are compared byte for byte on the way.
 On the large scene (484 spheres, a tree with a flat y slab):
   (c) a frame after an identity update against one before it: the price of the dropped slab.
+On config 5's scene again, sphere updates (none of these is a pass / fail threshold):
+  (d) one update of all radii, host form and device form, against one r1_set_scene with the same arrays;
+  (e) one materials-only update (every albedo and material row, no refit), host and device form, against the same;
+  (f) the frame time after a radii update that scales the lattice radii by 0.5, 1 and 2 against a fresh build of that scene (the refitted
+      tree keeps the topology of the original radii), the two frames compared byte for byte on the way, with the node visits and leaf
+      trips of both trees from the diagnostic build.
 Frames are r1_render_async into page-locked memory, timed from the enqueue to the stream idle by the host's clock.
-Writes its report to profiles/r11/update.txt (--out FILE: somewhere else).
+Writes its report to profiles/r20/update.txt (--out FILE: somewhere else).
 usage: tools/update_bench.py [--rounds N] [--frames N] [--out FILE]"""
 import argparse
 import ctypes as C
@@ -29,7 +35,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--frames", type=int, default=8, help="frames per timing of (b) and (c)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r11", "update.txt"), help="where the report is written")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r20", "update.txt"), help="where the report is written")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -41,10 +47,12 @@ def main():
         act = np.nonzero(a["inv_radius"] != 0)[0]
         return np.setdiff1d(act, act[np.argsort(a["radius_sq"][act], kind="stable")[-4:]])
 
-    def raw_from_arrays(a, x, y, z):
-        """a CScene over the scene's arrays with other centres (the returned dict keeps the arrays alive)"""
+    def raw_from_arrays(a, x, y, z, **other):
+        """a CScene over the scene's arrays with other centres, and other arrays by name (the returned dict keeps the arrays alive)"""
         keep = {k: np.ascontiguousarray(a[k], np.float32).copy() for k in FIELDS}
         keep["center_x"], keep["center_y"], keep["center_z"] = (np.ascontiguousarray(v, np.float32).copy() for v in (x, y, z))
+        for k, v in other.items():
+            keep[k] = np.ascontiguousarray(v, np.float32).copy()
         keep["mat_type"] = np.ascontiguousarray(a["mat_type"], np.uint8).copy()
         cs = binding.CScene()
         cs.count = len(keep["mat_type"])
@@ -122,8 +130,8 @@ def main():
     say(f"  r1_set_scene              {spread(t_set)}")
     say(f"  r1_set_scene / update: host form {statistics.median(t_set) / statistics.median(t_host):.1f} x, device form "
         f"{statistics.median(t_set) / statistics.median(t_dev):.1f} x")
-    li = ctx.launch_info()
-    say(f"  (tree: {li['bvh_nodes']} nodes, {li['bvh_leaves']} leaves, depth {li['bvh_depth']}: one launch per height)")
+    bi = binding.bvh_describe(sc.spheres.contents)[0]
+    say(f"  (tree: {bi['nodes']} nodes, {bi['leaves']} leaves, depth {bi['depth']}: one launch per height)")
     say()
     say(f"(b) frame time after a refit against a fresh build of the same moved scene ({args.frames} frames per timing, {args.rounds} rounds, alternating)")
     for d in (0.0, 0.25, 1.0, 4.0):
@@ -160,6 +168,89 @@ def main():
     say(f"  after (generic loop)  {spread(t_a)}")
     say(f"  after / before: {statistics.median(t_a) / statistics.median(t_b):.3f}")
     before.close(), after.close()
+
+    # ---- sphere updates on config 5's scene ----
+    cx, cy, cz = (a[k] for k in ("center_x", "center_y", "center_z"))
+
+    def scaled(f):
+        """the lattice radii times f, stored as SphereSOA::add stores a radius"""
+        rad = np.zeros(n, np.float32)
+        rad[lat] = (np.float32(f) / a["inv_radius"][lat]).astype(np.float32)
+        rsq, inv = a["radius_sq"].copy(), a["inv_radius"].copy()
+        rsq[lat], inv[lat] = (rad[lat] * rad[lat]).astype(np.float32), (np.float32(1) / rad[lat]).astype(np.float32)
+        return rsq, inv
+
+    ctx, other = r1.Renderer(0), r1.Renderer(0)
+    ctx.set_scene(sc)
+
+    def one_update(title, label, host_args, dev_ptrs, cs):
+        t_host, t_dev, t_set = [], [], []
+        for r in range(args.rounds + 1):
+            def host_form():
+                ctx.update_spheres(0, **host_args[r % 2])
+                ctx.sync()
+
+            def device_form():
+                ctx.update_spheres_device(0, n, stream_ptr=None, **dev_ptrs[r % 2])
+                ctx.sync()
+
+            th, td, ts = ms(host_form), ms(device_form), ms(lambda: ctx.set_scene_raw(cs[r % 2], sc.camera.contents))
+            if r:
+                t_host.append(th), t_dev.append(td), t_set.append(ts)
+            ctx.set_scene(sc)
+        say(title)
+        say(f"  r1_update_spheres ({label})         {spread(t_host)}")
+        say(f"  r1_update_spheres_device ({label})  {spread(t_dev)}")
+        say(f"  r1_set_scene                        {spread(t_set)}")
+        say(f"  r1_set_scene / update: host form {statistics.median(t_set) / statistics.median(t_host):.1f} x, device form "
+            f"{statistics.median(t_set) / statistics.median(t_dev):.1f} x")
+
+    say()
+    host_args, dev_ptrs, keep_alive, css = [], [], [], []  # (keep_alive: the device arrays behind dev_ptrs)
+    for f in (0.8, 1.25):
+        rsq, inv = scaled(f)
+        t = [torch.from_numpy(v).cuda() for v in (rsq, inv)]
+        host_args.append({"radii": (rsq, inv)}), dev_ptrs.append({"radii": tuple(v.data_ptr() for v in t)}), keep_alive.append(t)
+        css.append(raw_from_arrays(a, cx, cy, cz, radius_sq=rsq, inv_radius=inv))
+    torch.cuda.synchronize()
+    one_update("(d) one update of all radii against one r1_set_scene with the same arrays (alternating, lattice radii x 0.8 and x 1.25 by turns)", "radii",
+               host_args, dev_ptrs, [c[0] for c in css])
+    say()
+    host_args, dev_ptrs, keep_alive, css = [], [], [], []
+    for turn in (1, 2):
+        alb = [np.roll(np.stack([a["albedo_r"], a["albedo_g"], a["albedo_b"]]), turn, 0)[k].copy() for k in range(3)]
+        mats = (a["mat_type"], alb[0], alb[1], alb[2], a["mat_param"])
+        t = [torch.from_numpy(np.ascontiguousarray(v)).cuda() for v in mats]
+        host_args.append({"materials": mats}), dev_ptrs.append({"materials": tuple(v.data_ptr() for v in t)}), keep_alive.append(t)
+        css.append(raw_from_arrays(a, cx, cy, cz, albedo_r=alb[0], albedo_g=alb[1], albedo_b=alb[2]))
+    torch.cuda.synchronize()
+    one_update("(e) one materials-only update (every albedo and material row; no refit) against one r1_set_scene with the same arrays (alternating, "
+               "the albedo channels rotated by one and by two)", "materials", host_args, dev_ptrs, [c[0] for c in css])
+    say()
+    say(f"(f) frame time after a radii update against a fresh build of the same scene ({args.frames} frames per timing, {args.rounds} rounds, alternating)")
+    for f in (0.5, 1.0, 2.0):
+        rsq, inv = scaled(f)
+        cs, keep = raw_from_arrays(a, cx, cy, cz, radius_sq=rsq, inv_radius=inv)
+        ctx.set_scene(sc)
+        ctx.update_spheres(0, radii=(rsq, inv))
+        other.set_scene_raw(cs, sc.camera.contents)
+        t_refit, t_fresh, same = [], [], True
+        for r in range(args.rounds):
+            t_refit += frame_ms(ctx, args.frames)
+            img_refit, rays_refit = hf.image(0).copy(), hf.rays(0)
+            t_fresh += frame_ms(other, args.frames)
+            same = same and rays_refit == hf.rays(0) and img_refit.tobytes() == hf.image(0).tobytes()
+        mr, mf = statistics.median(t_refit), statistics.median(t_fresh)
+        visits = []
+        for c in (ctx, other):  # the walk itself, from the tree's diagnostic build: node visits and leaf trips summed over lanes, one frame
+            c.render(r1.make_params(w, h, spp, seed, variant=binding.VARIANT_BVH_STATS))
+            raw = c.last_stats()["raw"]
+            visits.append((raw[9], raw[14]))
+        say(f"  lattice radii x {f:3.1f}: refitted {mr:7.3f} ms (min {min(t_refit):.3f}), fresh build {mf:7.3f} ms (min {min(t_fresh):.3f}), "
+            f"refitted / fresh {mr / mf:5.2f}; pixels and rays {'equal' if same else 'DIFFER'}")
+        say(f"      node visits per frame: refitted {visits[0][0]}, fresh {visits[1][0]} ({visits[0][0] / visits[1][0]:.2f}); "
+            f"leaf trips x lanes: refitted {visits[0][1]}, fresh {visits[1][1]} ({visits[0][1] / visits[1][1]:.2f})")
+    ctx.close(), other.close()
     hf.close()
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
