@@ -1,6 +1,9 @@
 // r1_aux_kernels.hip — the kernels around the trace kernel (wavefront variant, resolve, progressive accumulate, batch counts, assemble) and the launch
-// dispatch called from r1_frame.cpp and r1_render.cpp.  The trace kernel template and its device functions: r1_trace.hpp.
-#include "r1_trace.hpp"
+// dispatch called from r1_frame.cpp and r1_render.cpp.  From the trace kernels' device functions it takes sweep_bvh (r1_hit_tree.hpp), start_sample,
+// path_store / path_load and quantise_pixel (r1_sample.hpp) and shade_level (r1_shade.hpp); the trace kernel itself: r1_trace.hpp.
+#include "r1_hit_tree.hpp"
+#include "r1_sample.hpp"
+#include "r1_shade.hpp"
 #include "r1_internal.h"
 
 

@@ -3,10 +3,6 @@
 #ifndef R1_BUILDS_H
 #define R1_BUILDS_H
 
-#ifndef R1_LAND
-#error "r1_builds.h is included through r1_device.h (r1_build_lands reads R1_LAND)"
-#endif
-
 // Internal variant numbers = the public enum of include/rays1.h (r1_frame.cpp resolve_variant asserts it), DEFAULT resolved.
 constexpr int R1_V_REFERENCE = 1;   // exhaustive sweep, the reference's form
 constexpr int R1_V_SWEEP = 2;       // grouped exhaustive sweep (R1_VARIANT_PREFILTER)
@@ -20,7 +16,7 @@ constexpr int R1_V_GRID_STATS = 8;
 // The MODE template argument of r1_trace_body, and what a caller asks r1_pick for.
 constexpr int R1_MODE_TP = 0;     // frames in flight (the throughput entry points): samples in one guided queue, few long-lived waves per frame
 constexpr int R1_MODE_LAT = 1;    // latency (the synchronous entry points: one frame, full grid): sub-queues and the cooperative tail
-constexpr int R1_MODE_PIXEL = 2;  // the throughput entry points after r1_set_pixel_mode: the queue holds pixels (r1_trace.hpp struct Pixel)
+constexpr int R1_MODE_PIXEL = 2;  // the throughput entry points after r1_set_pixel_mode: the queue holds pixels (r1_sample.hpp struct Pixel)
 constexpr int R1_MODE_BATCH = 3;  // TP whose queue spans the frames of a batch (R1BatchArgs)
 constexpr int R1_MODE_PASS = 4;   // a progressive pass (r1_render_pass): records take the pass-local sample index, seeds the global one (R1PassArgs)
 constexpr int R1_MODE_PATH = 5;   // BATCH with one camera per frame, read from a device table where a sample starts (R1PathArgs)
@@ -41,9 +37,9 @@ constexpr bool r1_runs_as_latency(int mode, bool big) { return mode == R1_MODE_L
 // tiles resolved inside the kernel (R1_LAND): the throughput builds of the tree's product kernel.  The synchronous frame keeps the
 // resolve launch (1.276 against 1.077 ms on the device with its tiles summed at wave exit, i.e. at the end of the frame's critical path;
 // profiles/r04/land_sync_frame.txt), and so does the exhaustive sweep (its loop pays 14 % for the bookkeeping, 16.6 against 19.2 Grays/s)
-constexpr bool r1_build_lands(int variant, bool stats, int mode) { return R1_LAND && variant == R1_V_TREE && !stats && r1_mode_is_tp_family(mode); }
+constexpr bool r1_build_lands(int variant, bool stats, int mode) { return variant == R1_V_TREE && !stats && r1_mode_is_tp_family(mode); }
 
-// The root step of the tree walk tests its leaf sphere by sphere (r1_trace.hpp leaf_root) instead of through leaf_quad's slot loop: one choice
+// The root step of the tree walk tests its leaf sphere by sphere (r1_hit_tree.hpp leaf_root) instead of through leaf_quad's slot loop: one choice
 // per build, taken where the build keeps its waves per SIMD, gains no scratch and no more than a handful of spilled-SGPR lane moves with it
 // (tools/kernel_meta.py; profiles/r19/kernel_meta_*.txt).  The path builds hold the camera table's scalars across the walk and
 // spill 16-36 more lane moves with the leaf's spheres in scalar registers as well; the small PIXEL build 12 more.

@@ -1,6 +1,6 @@
 // r1_capi.cpp — the C-ABI of include/rays1.h on top of the HIP runtime: errors, the context's life, timing and what the last launch
 // left to read.  Host code only.  The scene upload is r1_scene.cpp, a frame's steps r1_frame.cpp, the render entry points r1_render.cpp,
-// the ray queries r1_queries.cpp (the kernels live in r1_trace.hpp).
+// the ray queries r1_queries.cpp (the trace kernel lives in r1_trace.hpp).
 //
 // There is no CPU fallback anywhere in these files: without a HIP device every compute entry point returns R1_ENODEVICE / R1_EHIP.
 
@@ -80,9 +80,9 @@ extern "C" int r1_create(int device, r1_context **out)
         delete c;
         return R1_EHIP;
     }
-    if (hipHostMalloc((void **)&c->host_word, 64, hipHostMallocMapped) == hipSuccess)
+    if (hipHostMalloc((void **)&c->host_word, sizeof(R1HostWords), hipHostMallocMapped) == hipSuccess)
     {
-        memset(c->host_word, 0, 64); // (the runtime may hand back a recycled block: word 2 is land_check's "a resolver gave up" flag)
+        memset(c->host_word, 0, sizeof(R1HostWords)); // (the runtime may hand back a recycled block: land_error is land_check's "a resolver gave up" flag)
         if (hipHostGetDevicePointer((void **)&c->host_word_dev, c->host_word, 0) != hipSuccess)
         {
             (void)hipHostFree(c->host_word);
@@ -149,9 +149,10 @@ extern "C" void r1_destroy(r1_context *c)
 // a resolver of an earlier launch gave up waiting (R1_LAND_MAX_WAIT): the frames of that launch are not valid
 int land_check(r1_context *c)
 {
-    if (c->host_word && ((volatile uint32_t *)c->host_word)[2])
+    volatile uint32_t *const error = c->host_word ? &c->host_word->land_error : nullptr;
+    if (error && *error)
     {
-        ((volatile uint32_t *)c->host_word)[2] = 0;
+        *error = 0;
         r1_set_error("a launch did not resolve all of its tiles (a resolver workgroup gave up waiting): its frames are not valid");
         return R1_EHIP;
     }
@@ -216,7 +217,7 @@ extern "C" int r1_last_stats(r1_context *c, uint64_t *out16)
         return R1_EINVAL;
     R1_HIP(hipSetDevice(c->device));
     R1_HIP(hipStreamSynchronize(c->stream));
-    R1_HIP(hipMemcpyAsync(out16, (char *)c->counters.p + 128, 128, hipMemcpyDeviceToHost, c->stream));
+    R1_HIP(hipMemcpyAsync(out16, counter_at(c, R1_CNT_STATS), 8 * R1_STATS_WORDS, hipMemcpyDeviceToHost, c->stream));
     R1_HIP(hipStreamSynchronize(c->stream));
     return R1_OK;
 }

@@ -107,7 +107,7 @@ struct r1_context
 
     // per-frame workspace
     DevBuf counters, samples, image;
-    // frame batches: the batch's numbers live in one of eight device slots (counter tail + 64 + 32 i), written by a one-thread launch whose
+    // frame batches: the batch's numbers live in one of the batch-argument slots of the counter allocation (r1_device.h R1_TAIL_BATCH_SLOTS), written by a one-thread launch whose
     // values travel in its kernel arguments (an asynchronous copy from a host member could be overtaken by the next call)
     R1BatchArgs batch_args_last = {0, 0, {0, 0, 0}, 0};
     hipStream_t batch_args_stream = nullptr;
@@ -130,9 +130,9 @@ struct r1_context
     bool tile_key_valid = false;
     uint32_t n_local_tiles = 0, total_samples = 0, full = 0;
 
-    // one page-locked, device-visible word: the synchronous entry points let the frame's last launch store the ray count
-    // straight into host memory (8 bytes over PCIe at the end of r1_resolve_kernel) instead of enqueueing a second copy
-    unsigned long long *host_word = nullptr, *host_word_dev = nullptr;
+    // 64 page-locked, device-visible bytes (r1_device.h R1HostWords): the synchronous entry points let the frame's last launch store the
+    // ray count straight into host memory (8 bytes over PCIe at the end of r1_resolve_kernel) instead of enqueueing a second copy
+    R1HostWords *host_word = nullptr, *host_word_dev = nullptr; // the host's address, the device's
     int default_variant = R1_V_TREE;    // what R1_VARIANT_DEFAULT resolves to for the scene in the context (r1_set_scene): synchronous frames
     int default_variant_tp = R1_V_TREE; // ... and frames in flight (the throughput kernels: measured apart, the two kernel families do not rank alike)
     int occupancy[8 * 2 * 2 * R1_MODES] = {0}; // blocks per CU of the trace kernel's builds, [occupancy_slot(build)]
@@ -173,6 +173,9 @@ struct r1_context
 
     r1_launch_info info;
 };
+
+// an address inside the context's counter allocation, by its offset in the layout of r1_device.h (R1_CNT_*, R1_TAIL_*, r1_land_area)
+inline char *counter_at(const r1_context *c, size_t offset) { return (char *)c->counters.p + offset; }
 
 // Frame batch of the throughput entry points: n_frames frames in one launch (r1_device.h R1TraceArgs::n_frames); frame f is
 // written to d_out + f * out_stride and its uint64 ray count to d_out + f * out_stride + rays_offset.

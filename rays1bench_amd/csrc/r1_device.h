@@ -1,7 +1,9 @@
-// r1_device.h — device-side data layout shared by r1_trace.hpp and the host files behind r1_context.h.
+// r1_device.h — device-side data layout shared by the device headers (r1_trace.hpp and the headers it is made of) and the host files behind
+// r1_context.h: launch geometry, the layout of the context's counter allocation and host words, the kernels' argument structs.
 #ifndef R1_DEVICE_H
 #define R1_DEVICE_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #include "r1_grid_dda.h"
@@ -49,31 +51,71 @@
 #define R1_BVH_TOP_NODES 63    // box tree: the first nodes in breadth-first order (6 levels); the big-scene kernels keep them in LDS (4 KB: 0 / 63 / 127 / 255 nodes -> 12.9 / 13.3 / 13.0 / 12.6 Grays/s on 100 004 spheres, the larger copies cost workgroups per CU)
 #define R1_BVH_LEAF 4          // spheres per leaf (<= 14; stored as pairs)
 #define R1_SUBQUEUES 16        // latency mode: sub-queues of the sample queue (R1TraceArgs::nq)
-#define R1_COUNTER_BYTES 4096  // per-context counter block: queue heads, ray count (+32), drain counts, stats (+128), sub-queues at +1024;
-                               // the allocation carries 64 more bytes: the published ray count of the synchronous entry points
+#define R1_COUNTER_BYTES 4096  // block 0 of the context's counter allocation (R1_CNT_* below), zeroed between frames
 #define R1_COOP_LANES 2        // R1TraceArgs::coop_lanes (one synchronous frame: 2 -> 1.144 ms, 4 -> 1.160, 8 -> 1.193, 16 -> 1.263)
-// Tiles resolved INSIDE the trace kernel (round 4; r1_trace.hpp has the protocol): the throughput kernels sum every
+// Tiles resolved INSIDE the trace kernel (R1_LAND: round 4; r1_land.hpp has the protocol): the throughput kernels sum every
 // 32 x 32 tile themselves, on the XCD that traced it, and store the pixels where the frame is wanted — device memory or the caller's
-// page-locked host buffer.  No resolve launch, no copy.  0 builds the round-3 form (r1_resolve_kernel after the trace kernel) for A/B.
-#ifndef R1_LAND
-#define R1_LAND 1
-#endif
+// page-locked host buffer.  No resolve launch, no copy.
 #include "r1_builds.h" // the names of variants and modes, the predicates (r1_build_lands: which builds land their tiles), the list of builds
-// exhaustive sweep, exact phase (exact_trips): member spheres from a table in group order (one global fetch in the dependent chain instead
-// of two)
-#ifndef R1_EXACT_G
-#define R1_EXACT_G 1
-#endif
-#ifndef R1_SWEEP_PAIRS2
-#define R1_SWEEP_PAIRS2 1 // exhaustive sweep, group test: two pairs of groups interleaved (sweep_prefilter)
-#endif
 #define R1_LAND_CNT_STRIDE 32u  // words between two tiles' countdowns: every countdown on its own 128-byte line (an atomic on ONE line sustains ~88 M/s on this chip,
                                // tools/ubench_atomic.hip; the ~40 tiles a synchronous frame's waves work on at a time shared two lines at first: 3.8 ms per frame instead of 1.1)
 #define R1_LAND_MAX_WAIT (1u << 16) // passes over a claimed tile that still find a record of an earlier launch before the wave gives up and flags the launch
                                     // (a record's store is on its way for microseconds; a bug would otherwise hang the device instead of failing the call)
-#define R1_COUNTER_TAIL 4096   // behind the R1_COUNTER_BYTES block: +0 published ray count, +64 batch-argument slots (8 x 32 B), +1024 the second
-                               // set of queue heads (frames alternate between the sets; the resolvers of a launch zero the set the
-                               // launch before it used), then per launch: frame accumulators and the per-tile countdowns
+#define R1_COUNTER_TAIL 4096   // the tail of the counter allocation, behind block 0 (R1_TAIL_* below), never zeroed as a whole
+#define R1_LAND_MAX_XCD 8u     // XCDs of the chip: each has a cursor among the queue heads (r1_land.hpp)
+
+// ---- the context's counter allocation (r1_context::counters), byte offsets from its start ------------------------------------------
+// Block 0, [0, R1_COUNTER_BYTES): what a frame counts in.  The frame's closing launch — or a memset — zeroes all of it between frames.
+constexpr size_t R1_CNT_RAYS = 32;      // uint64: the ray count the trace kernel accumulates (the 32 bytes in front of it are not used)
+constexpr size_t R1_CNT_STATS = 128;    // R1_STATS_WORDS uint64: the diagnostic builds' published counters (R1TraceArgs::stats, r1_last_stats) ...
+constexpr uint32_t R1_STATS_WORDS = 16;
+constexpr size_t R1_CNT_WAVE_LOG = R1_CNT_STATS + 8 * R1_STATS_WORDS; // ... and behind them, as stats[R1_STATS_WORDS], the address of the wave log
+constexpr size_t R1_CNT_HEADS = 1024;   // the queue heads (R1TraceArgs::queue): R1_HEADS of them, each on a 128-byte line of its own
+constexpr uint32_t R1_HEAD_WORDS = 32;  // uint32 words from one head to the next
+constexpr uint32_t R1_HEADS = (R1_COUNTER_BYTES - R1_CNT_HEADS) / (4 * R1_HEAD_WORDS);
+// The tail, [R1_COUNTER_BYTES, R1_COUNTER_BYTES + R1_COUNTER_TAIL)
+constexpr size_t R1_TAIL_RAYS = R1_COUNTER_BYTES + 0;           // uint64: the published ray count (the count word of a caller that names none)
+constexpr size_t R1_TAIL_BATCH_SLOTS = R1_COUNTER_BYTES + 64;   // R1_BATCH_SLOTS batch-argument slots of R1_BATCH_SLOT_BYTES (R1BatchArgs, R1PathArgs, R1PassArgs)
+constexpr uint32_t R1_BATCH_SLOTS = 8, R1_BATCH_SLOT_BYTES = 32;
+constexpr size_t R1_TAIL_HEADS = R1_COUNTER_BYTES + 1024;       // the second set of queue heads: landing launches alternate between the sets, and
+                                                                // workgroup 0 of a launch zeroes the set the launch before it used
+// Behind the tail, per landing launch of F frames: frame_rays[F] (uint64 accumulators), frame_left[F] (uint32 tiles to go), then — from the
+// next 128-byte line on — the tiles' countdowns, R1_LAND_CNT_STRIDE words apart
+constexpr size_t R1_CNT_LAND = (size_t)R1_COUNTER_BYTES + R1_COUNTER_TAIL;
+struct R1LandArea
+{
+    size_t frame_rays, frame_left, tile_cnt, end;
+};
+constexpr R1LandArea r1_land_area(size_t n_frames, size_t tiles)
+{
+    const size_t cnt = R1_CNT_LAND + ((n_frames * 16 + 127) & ~(size_t)127);
+    return {R1_CNT_LAND, R1_CNT_LAND + n_frames * 8, cnt, cnt + tiles * 4 * R1_LAND_CNT_STRIDE};
+}
+// The queue heads by role (index of the head; word R1_HEAD_WORDS * index of R1TraceArgs::queue)
+constexpr uint32_t R1_HEAD_XCD = 0;        // landing launches: heads [0, R1_LAND_MAX_XCD) are the XCDs' cursors {group + 1, next sample slot} (uint64)
+constexpr uint32_t R1_HEAD_SUBQUEUE = 0;   // latency launches: heads [0, nq <= R1_SUBQUEUES) are the sub-queues' chunk counters; any other launch: head 0 is the queue
+constexpr uint32_t R1_HEAD_DISPENSER = 16; // landing launches: the next unclaimed tile group
+constexpr uint32_t R1_HEAD_DEBUG = 17, R1_HEAD_DEBUG_COUNT = 7; // R1_LAND_DEBUG builds (tools/land_debug.py)
+static_assert(R1_CNT_RAYS + 8 <= R1_CNT_STATS && R1_CNT_WAVE_LOG + 8 <= R1_CNT_HEADS && R1_CNT_HEADS + R1_HEADS * 4 * R1_HEAD_WORDS == R1_COUNTER_BYTES,
+              "block 0: ray count, published counters, wave log address, queue heads");
+static_assert(8 <= R1_TAIL_BATCH_SLOTS - R1_TAIL_RAYS && R1_TAIL_BATCH_SLOTS + R1_BATCH_SLOTS * R1_BATCH_SLOT_BYTES <= R1_TAIL_HEADS &&
+                  R1_TAIL_HEADS + R1_HEADS * 4 * R1_HEAD_WORDS <= R1_CNT_LAND,
+              "the tail: published ray count, batch-argument slots, the second set of queue heads");
+static_assert(R1_HEAD_XCD + R1_LAND_MAX_XCD <= R1_HEAD_DISPENSER && R1_HEAD_SUBQUEUE + R1_SUBQUEUES <= R1_HEAD_DISPENSER && R1_HEAD_DISPENSER < R1_HEAD_DEBUG &&
+                  R1_HEAD_DEBUG + R1_HEAD_DEBUG_COUNT <= R1_HEADS,
+              "the queue heads' roles fit the heads and do not overlap");
+static_assert(R1_LAND_CNT_STRIDE * 4 == 128 && R1_CNT_LAND % 128 == 0 && r1_land_area(3, 1).tile_cnt % 128 == 0, "every countdown on a 128-byte line of its own");
+
+// The context's page-locked, device-visible host words (r1_context::host_word): what a launch stores straight into host memory
+struct R1HostWords
+{
+    unsigned long long rays; // the frame's ray count (the synchronous entry points)
+    uint32_t land_error;     // set by a wave that gave up on a tile (R1LandArgs::error); read and cleared by land_check
+    uint32_t pad0;
+    uint32_t adapt_count;    // adaptive sampling: the next pass's list length
+    uint32_t pad1[11];
+};
+static_assert(sizeof(R1HostWords) == 64 && offsetof(R1HostWords, land_error) == 8 && offsetof(R1HostWords, adapt_count) == 16, "the host words' layout");
 
 // Tuning knobs.  The SHIPPED library never reads the environment: what it does depends on its arguments only.  A build made
 // with -DR1_TUNING (`make tuning` -> lib/librays1_tuning.so; the scripts under tools/ load it explicitly) reads the R1_*
@@ -144,7 +186,7 @@ struct R1LandArgs
     unsigned long long *frame_rays; // [n_frames] ray-count accumulators (zero between launches)
     uint32_t *frame_left;           // [n_frames] tiles not yet resolved (n_local_tiles between launches)
     uint32_t *clear_heads;          // queue heads and wave counts of the set the PREVIOUS launch through this context used: zeroed by workgroup 0
-    uint32_t clear_count;           // ... that many words, 32 words apart
+    uint32_t clear_count;           // ... that many words, R1_HEAD_WORDS words apart
     uint32_t n_frames;              // frames of the launch (1: a single frame)
     uint32_t rays_in_out, block_layout;
     float inv_spp;                  // (float)(1.0f / spp), rayweek1.cpp:765
@@ -165,7 +207,7 @@ struct R1DeviceScene
     // {type, param}.
     const float4 *exact;
     const float4 *shade;   // {inv_radius, albedo_r, albedo_g, albedo_b}
-    const float4 *exact_g;   // R1_EXACT_G: the same {cx, cy, cz, radius_sq} in GROUP order, [n_sweep (+pad)][R1_GROUP_MAX] ({0, 0, 0, -inf} = none: never an offer):
+    const float4 *exact_g;   // the same {cx, cy, cz, radius_sq} in GROUP order, [n_sweep (+pad)][R1_GROUP_MAX] ({0, 0, 0, -inf} = none: never an offer):
                              // the exact phase fetches a member's sphere and its index side by side instead of one after the other
     const uint32_t *members; // [n_sweep (+pad)][R1_GROUP_MAX] active indices of a group's spheres, 0xFFFFFFFF = none
     const float4 *mat;     // {bit_cast<float>(type), param, 1/ref_idx, ((1-ref)/(1+ref))^2} (last two: dielectrics)
@@ -232,12 +274,12 @@ struct R1TraceArgs
     R1FastDiv div_full, div_spp, div_tw, div_tx; // by full, spp, tile_w, tiles_x
     uint32_t total_samples;      // n_local_tiles * full (queue length)
     uint32_t chunk_min, chunk_max; // samples a wave takes from the queue per atomic (guided: remaining / (2 waves), clamped)
-    uint32_t *queue;             // global sample counter(s) (zeroed before the launch); sub-queue q at queue + 32 q (its own 128-byte line)
+    uint32_t *queue;             // global sample counter(s) (zeroed before the launch); head i at queue + R1_HEAD_WORDS * i (its own 128-byte line; roles: R1_HEAD_*)
     uint32_t nq;                 // 1: one guided queue (chunk_min..chunk_max).  > 1 (latency mode): nq sub-queues of fixed chunks of
                                  // chunk_max slots, chunk c belongs to sub-queue c % nq and a wave only pulls from sub-queue wave % nq:
                                  // a returning atomic on ONE line sustains 88 M/s on this chip (tools/ubench_atomic.hip), too few for
                                  // 6144 waves taking a wave-full at a time
-    float4 *samples;             // [total_samples] {r, g, b, bit_cast<float>(rays)}.  PIXEL mode (r1_trace.hpp struct Pixel): the
+    float4 *samples;             // [total_samples] {r, g, b, bit_cast<float>(rays)}.  PIXEL mode (r1_sample.hpp struct Pixel): the
                                  // queue holds PIXELS (full = tile_w * tile_h, total_samples = padded pixels of the shard) and this
                                  // is the uint8 RGB output the kernel resolves into
     unsigned long long *num_rays; // accumulated color() invocations

@@ -59,11 +59,8 @@ static int prepare_tiles(r1_context *c, const r1_params *p, int n_frames)
     return R1_OK;
 }
 
-// The context's counter allocation: [0, R1_COUNTER_BYTES) queue heads (set 0), ray count, diagnostic counters — the block the round-3
-// kernels zero between frames; then R1_COUNTER_TAIL bytes: +0 the published ray count, +64 eight batch-argument slots, +1024 queue heads
-// (set 1); then, per launch (R1_LAND): frame_rays[F] (uint64), frame_left[F] (uint32, padded), tile_cnt[F x local tiles] (uint32).
+// The context's counter allocation (its layout: r1_device.h R1_CNT_*, R1_TAIL_*, r1_land_area), sized for the launch's landing area.
 // Called by every entry point BEFORE it takes addresses inside the allocation (it may move when the launch needs more room).
-static size_t land_frames_off() { return (size_t)R1_COUNTER_BYTES + R1_COUNTER_TAIL; }
 static int ensure_counters(r1_context *c, const r1_params *p, int n_frames)
 {
     int rc = prepare_tiles(c, p, n_frames);
@@ -71,7 +68,7 @@ static int ensure_counters(r1_context *c, const r1_params *p, int n_frames)
         return rc;
     const size_t F = (size_t)(n_frames > 0 ? n_frames : 1);
     const size_t tiles = F * (size_t)(c->n_local_tiles ? c->n_local_tiles : 1);
-    const size_t need = land_frames_off() + ((F * 16 + 127) & ~(size_t)127) + tiles * 4 * R1_LAND_CNT_STRIDE;
+    const size_t need = r1_land_area(F, tiles).end;
     if (c->counters.p && need <= c->counters.cap)
         return R1_OK;
     R1_HIP(hipStreamSynchronize(c->stream)); // (a frame in flight on another stream is the caller's to order: one frame per context at a time)
@@ -188,7 +185,7 @@ static int size_tiles(r1_context *c, const r1_params *p, int n_frames, const Pas
 static int ensure_records(r1_context *c, const r1_params *p, const Choice &k, const Batch *batch, hipStream_t st)
 {
     int rc;
-    if (batch && !(R1_LAND && k.variant == R1_V_TREE))
+    if (batch && k.variant != R1_V_TREE)
     {
         // partial ray counts of the resolve launch: one uint64 per (tile of the batch, workgroup column)
         const size_t cols = ((size_t)p->tile_w * p->tile_h + 255) / 256;
@@ -242,14 +239,14 @@ static void frame_args(const r1_context *c, const r1_params *p, const Choice &k,
     a.shard = p->shard, a.num_shards = p->num_shards;
     a.n_local_tiles = c->n_local_tiles, a.full = c->full, a.total_samples = c->total_samples;
     a.div_full = make_div(c->full), a.div_spp = make_div((uint32_t)p->spp), a.div_tw = make_div((uint32_t)p->tile_w), a.div_tx = make_div((uint32_t)a.tiles_x);
-    a.queue = (uint32_t *)((char *)c->counters.p + 1024);
+    a.queue = (uint32_t *)counter_at(c, R1_CNT_HEADS);
     static const int coop_env = (int)r1_knob("R1_COOP_LANES", -1);
     a.coop_lanes = coop_env >= 0 ? (uint32_t)coop_env : R1_COOP_LANES;
     a.samples = (float4 *)c->samples.p;
-    a.num_rays = k.fused_clear ? (unsigned long long *)((char *)c->counters.p + 32) : (unsigned long long *)d_rays;
-    a.stats = r1_is_stats(k.variant) ? (unsigned long long *)((char *)c->counters.p + 128) : nullptr;
+    a.num_rays = k.fused_clear ? (unsigned long long *)counter_at(c, R1_CNT_RAYS) : (unsigned long long *)d_rays;
+    a.stats = r1_is_stats(k.variant) ? (unsigned long long *)counter_at(c, R1_CNT_STATS) : nullptr;
     if (r1_is_grid(k.variant))
-        a.grid = (const R1GridArgs *)(k.b.big ? c->grid_dev32.p : c->grid_dev.p), a.scene.bvh_root_leaf = 0u; // (the grid kernels' fallback walks the tree from its root: no root step, r1_trace.hpp)
+        a.grid = (const R1GridArgs *)(k.b.big ? c->grid_dev32.p : c->grid_dev.p), a.scene.bvh_root_leaf = 0u; // (the grid kernels' fallback walks the tree from its root: no root step, r1_hit_tree.hpp bvh_advance)
     static const int big_top_env = (int)r1_knob("R1_BIG_TOP", R1_BVH_TOP_NODES); // tuning experiments
     fill_walk(c, r1_is_tree(k.variant), k.b.big, (uint32_t)std::max(1, big_top_env), a);
     if (k.b.mode == R1_MODE_PIXEL)
@@ -262,7 +259,7 @@ static void frame_args(const r1_context *c, const r1_params *p, const Choice &k,
     }
 }
 
-// Takes a batch-argument slot (eight 32-byte slots in the counter allocation behind the published ray count) and writes `words` into it by a
+// Takes a batch-argument slot (R1_BATCH_SLOTS slots in the counter allocation's tail, R1_TAIL_BATCH_SLOTS) and writes `words` into it by a
 // launch of its own, in stream order: the previous launch through this context has finished reading its copy by the time this one is
 // written, and a NEW slot leaves a launch still reading the previous numbers undisturbed.  `cache` (a batch's numbers): an unchanged batch
 // on the same stream reuses its slot and writes nothing.  cache == null (a path, whose block ends in a table address, and a pass): always a
@@ -270,18 +267,19 @@ static void frame_args(const r1_context *c, const r1_params *p, const Choice &k,
 // n_frames >= 2).  Returns the slot.
 static int put_batch_args(r1_context *c, const void *words, int n_words, const R1BatchArgs *cache, hipStream_t st, const R1BatchArgs **slot)
 {
-    char *const slots = (char *)c->counters.p + R1_COUNTER_BYTES + 64;
+    char *const slots = counter_at(c, R1_TAIL_BATCH_SLOTS);
+    static_assert((R1_BATCH_SLOTS & (R1_BATCH_SLOTS - 1)) == 0, "the slots are taken in turn with a mask");
     if (!cache || c->batch_args_slot < 0 || c->batch_args_stream != st || memcmp(cache, &c->batch_args_last, sizeof(*cache)) != 0)
     {
-        c->batch_args_slot = (c->batch_args_slot + 1) & 7;
+        c->batch_args_slot = (c->batch_args_slot + 1) & (int)(R1_BATCH_SLOTS - 1);
         if (cache)
             c->batch_args_last = *cache;
         else
             memset(&c->batch_args_last, 0, sizeof(c->batch_args_last));
         c->batch_args_stream = st;
-        R1_HIP((n_words == 8 ? r1_launch_put8 : r1_launch_put6)(slots + 32 * c->batch_args_slot, (const uint32_t *)words, st));
+        R1_HIP((n_words == 8 ? r1_launch_put8 : r1_launch_put6)(slots + R1_BATCH_SLOT_BYTES * c->batch_args_slot, (const uint32_t *)words, st));
     }
-    *slot = (const R1BatchArgs *)(slots + 32 * c->batch_args_slot);
+    *slot = (const R1BatchArgs *)(slots + R1_BATCH_SLOT_BYTES * c->batch_args_slot);
     return R1_OK;
 }
 
@@ -402,9 +400,9 @@ static GridSize size_grid(int cus, int per_cu, uint32_t total, uint32_t pixels, 
     g.nq = 1;
     if (latency)
     {
-        // a wave only ever pulls from its home sub-queue (r1_trace.hpp: home = (4 (block / 8) + wave) % nq), so every
+        // a wave only ever pulls from its home sub-queue (r1_trace.hpp r1_trace_body: home = (4 (block / 8) + wave) % nq), so every
         // sub-queue needs home waves: the full groups of 8 workgroups must cover all nq residues
-        const long long nq = std::min<long long>({nq_env > 0 ? nq_env : R1_SUBQUEUES, 4 * (g.blocks / 8), (R1_COUNTER_BYTES - 1024) / 128});
+        const long long nq = std::min<long long>({nq_env > 0 ? nq_env : R1_SUBQUEUES, 4 * (g.blocks / 8), (long long)R1_HEADS});
         if (nq > 1)
         {
             g.nq = (uint32_t)nq;
@@ -433,13 +431,13 @@ static int land_setup(r1_context *c, const r1_params *p, const Batch *batch, Lan
     if (!prev)
     {
         R1_HIP(hipMemsetAsync(c->counters.p, 0, R1_COUNTER_BYTES, st));
-        R1_HIP(hipMemsetAsync((char *)c->counters.p + R1_COUNTER_BYTES + 1024, 0, R1_COUNTER_BYTES - 1024, st)); // (not the batch-argument slots in front of it)
+        R1_HIP(hipMemsetAsync(counter_at(c, R1_TAIL_HEADS), 0, R1_HEADS * 4 * R1_HEAD_WORDS, st)); // (not the batch-argument slots in front of it)
     }
-    char *const set0 = (char *)c->counters.p + 1024, *const set1 = (char *)c->counters.p + R1_COUNTER_BYTES + 1024;
+    char *const set0 = counter_at(c, R1_CNT_HEADS), *const set1 = counter_at(c, R1_TAIL_HEADS);
     a.queue = (uint32_t *)(land_parity ? set1 : set0);
     a.land.clear_heads = (uint32_t *)(land_parity ? set0 : set1);
-    a.land.clear_count = (R1_COUNTER_BYTES - 1024) / 128;
-    static_assert((R1_COUNTER_BYTES - 1024) / 128 <= R1_BLOCK && R1_COUNTER_TAIL >= 1024 + (R1_COUNTER_BYTES - 1024), "the second set of queue heads fits the tail");
+    a.land.clear_count = R1_HEADS;
+    static_assert(R1_HEADS <= R1_BLOCK, "workgroup 0 clears a set of queue heads in one or a few trips");
     // the launch's generation tags its sample records (1 .. 2^24 - 1; on wrap-around the records are wiped).  Advanced at once, even by
     // a call that is refused later: a tag no launch used costs nothing, one used again could let stale records pass for new ones
     c->land_gen = (c->land_gen + 1) & 0xFFFFFFu;
@@ -450,9 +448,10 @@ static int land_setup(r1_context *c, const r1_params *p, const Batch *batch, Lan
     }
     a.land_tag = c->land_gen << 8;
     a.land_res = 1; // (a landing launch: r1_launch_trace checks that the kernel and the launch agree)
-    unsigned long long *frame_rays = (unsigned long long *)((char *)c->counters.p + land_frames_off());
-    uint32_t *frame_left = (uint32_t *)(frame_rays + n_frames);
-    a.land_cnt = (uint32_t *)((char *)frame_rays + (((size_t)n_frames * 16 + 127) & ~(size_t)127)); // (every countdown on a 128-byte line of its own)
+    const R1LandArea area = r1_land_area((size_t)n_frames, 0);
+    unsigned long long *frame_rays = (unsigned long long *)counter_at(c, area.frame_rays);
+    uint32_t *frame_left = (uint32_t *)counter_at(c, area.frame_left);
+    a.land_cnt = (uint32_t *)counter_at(c, area.tile_cnt); // (every countdown on a 128-byte line of its own)
     if (!armed || c->land_frames != n_frames || !same_tiling(c->land_key, *p))
     {
         R1_HIP(r1_launch_land_arm(a.land_cnt, frame_rays, frame_left, (uint32_t)n_frames, c->n_local_tiles, p->width, p->height, p->spp, p->tile_w, p->tile_h,
@@ -471,7 +470,7 @@ static int land_setup(r1_context *c, const r1_params *p, const Batch *batch, Lan
     a.land.frame_rays = frame_rays, a.land.frame_left = frame_left;
     a.land.n_frames = (uint32_t)n_frames, a.land.block_layout = (uint32_t)block_layout;
     a.land.inv_spp = (float)(1.0f / p->spp); // rayweek1.cpp:765
-    a.land.error = c->host_word_dev ? (uint32_t *)(c->host_word_dev + 1) : nullptr;
+    a.land.error = c->host_word_dev ? &c->host_word_dev->land_error : nullptr;
     // every wave's list of tiles: a row as long as the launch has tiles (the cursors only move forward: a wave meets a tile at
     // most once; with uneven residency — twenty frames in flight, a frame's first workgroups do most of its work — a
     // shorter list overflowed at 250 spp)
@@ -531,7 +530,7 @@ static int prepare_memory(r1_context *c, const Choice &k, long long blocks, int 
             return rc;
         R1_HIP(hipMemsetAsync(c->wave_log.p, 0, (size_t)c->wave_log_waves * 32, st));
         c->wave_log_ptr = (unsigned long long)c->wave_log.p;
-        R1_HIP(hipMemcpyAsync((char *)c->counters.p + 128 + 16 * 8, &c->wave_log_ptr, 8, hipMemcpyHostToDevice, st));
+        R1_HIP(hipMemcpyAsync(counter_at(c, R1_CNT_WAVE_LOG), &c->wave_log_ptr, 8, hipMemcpyHostToDevice, st));
     }
     if (!k.fused_clear && !k.land)
         R1_HIP(hipMemsetAsync(d_rays, 0, 8, st));
@@ -572,7 +571,7 @@ static int launch_wavefront(r1_context *c, const R1TraceArgs &a, hipStream_t st,
 static int close_frame(r1_context *c, const r1_params *p, const Choice &k, const Batch *batch, const Pass *pass, int tiles_x, void *d_out, int block_layout,
                        void *d_rays, bool throughput_mode, hipStream_t st)
 {
-    const unsigned long long *rays_src = k.fused_clear ? (const unsigned long long *)((char *)c->counters.p + 32) : nullptr;
+    const unsigned long long *rays_src = k.fused_clear ? (const unsigned long long *)counter_at(c, R1_CNT_RAYS) : nullptr;
     unsigned long long *rays_dst = k.fused_clear ? (unsigned long long *)d_rays : nullptr;
     uint32_t *reset = k.fused_clear ? (uint32_t *)c->counters.p : nullptr;
     static const int resolve_rows = (int)r1_knob("R1_RESOLVE_ROWS", R1_RESOLVE_ROWS_TP); // tuning experiments
@@ -637,7 +636,7 @@ static int close_frame(r1_context *c, const r1_params *p, const Choice &k, const
 }
 
 // Enqueues the frame (trace + resolve) on `st`.  d_out / d_rays are device addresses; d_rays == NULL stands for the context's own
-// count word (counters + R1_COUNTER_BYTES; the allocation may move in here, so callers take that address afterwards).
+// count word (R1_TAIL_RAYS of the counter allocation; the allocation may move in here, so callers take that address afterwards).
 int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int block_layout, void *d_rays, hipStream_t st,
                          bool throughput_mode, const Batch *batch, Landing *landing, const Pass *pass)
 {
@@ -662,7 +661,7 @@ int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int block_layo
     if ((rc = size_tiles(c, p, batch ? batch->n_frames : 1, pass)))
         return rc;
     if (!d_rays) // (only now: the counter allocation may have moved)
-        d_rays = (char *)c->counters.p + R1_COUNTER_BYTES;
+        d_rays = counter_at(c, R1_TAIL_RAYS);
     Choice k;
     if ((rc = choose_kernel(c, p, variant, throughput_mode, batch, pass, k)) || (rc = ensure_records(c, p, k, batch, st)))
         return rc;

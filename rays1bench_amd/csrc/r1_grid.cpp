@@ -1,6 +1,6 @@
 // r1_grid.cpp — host-side builder of the uniform grid (R1_VARIANT_GRID, SURVEY.md §8f-1: "a uniform grid/BVH over the 100 k-sphere
 // field, kept optional so brute-force parity mode remains").  Like the box tree (r1_bvh.cpp) the grid only decides WHICH spheres are
-// presented to the reference's per-sphere test (exact_offer in r1_trace.hpp = rayweek1.cpp:192-202, :294-313); it is conservative with
+// presented to the reference's per-sphere test (exact_offer in r1_hit_sweep.hpp = rayweek1.cpp:192-202, :294-313); it is conservative with
 // respect to that fp32 test, not to geometry, so pixels and ray counts stay bit-identical to the exhaustive sweep.
 //
 // Structure.  Outliers — spheres more than R1_GRID_OUTLIER_RATIO (4) x the median radius, or whose padded ball would register in more
@@ -380,7 +380,7 @@ extern "C" int r1_grid_describe(const r1_scene *s, r1_grid_info *info, uint32_t 
     return R1_OK;
 }
 
-// exact_offer (r1_trace.hpp) on the host: the same operations, the same order
+// exact_offer (r1_hit_sweep.hpp) on the host: the same operations, the same order
 static float host_offer(const float *e, const float o[3], const float d[3])
 {
     const float cox = e[0] - o[0], coy = e[1] - o[1], coz = e[2] - o[2];

@@ -1,4 +1,4 @@
-// r1_grid_dda.h — the uniform grid's cell walk (R1_VARIANT_GRID), shared by the trace kernel (r1_trace.hpp grid_trace) and the
+// r1_grid_dda.h — the uniform grid's cell walk (R1_VARIANT_GRID), shared by the trace kernel (r1_hit_grid.hpp grid_trace) and the
 // host's r1_grid_visit (r1_grid.cpp), so that the CPU tests check the kernel's own arithmetic.  Why the walk is exact: r1_grid.cpp.
 //
 // Only correctly rounded operations: + - x, fmaf, floorf and IEEE '/' for the once-per-ray reciprocals (the build passes

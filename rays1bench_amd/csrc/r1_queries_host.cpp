@@ -40,7 +40,7 @@ inline bool ray_start(const r1_ray &r, V3 &o, V3 &d)
     return finite_f(o.x) && finite_f(o.y) && finite_f(o.z) && finite_f(d.x) && finite_f(d.y) && finite_f(d.z);
 }
 
-// what one sphere offers a ray (exact_offer of r1_trace.hpp, host_offer of r1_grid.cpp)
+// what one sphere offers a ray (exact_offer of r1_hit_sweep.hpp, host_offer of r1_grid.cpp)
 inline float cast_offer(const float *e, const V3 o, const V3 d)
 {
     const float cox = e[0] - o.x, coy = e[1] - o.y, coz = e[2] - o.z;
@@ -62,7 +62,7 @@ inline float cast_offer(const float *e, const V3 o, const V3 d)
 }
 
 // Hitable::hit(r, 0.001f, FLT_MAX, rec) (rayweek1.cpp:152-339): the active sphere with the smallest offer — a sphere's offer is fixed
-// before the compare with t_max (the comment above exact_offer in r1_trace.hpp derives it) — or na: none.  ex: [active] {cx cy cz radius_sq}
+// before the compare with t_max (the comment above exact_offer in r1_hit_sweep.hpp derives it) — or na: none.  ex: [active] {cx cy cz radius_sq}
 inline size_t closest(const std::vector<float> &ex, const size_t na, const V3 o, const V3 d, float &best)
 {
     size_t hit = na;
@@ -157,7 +157,7 @@ void cast_range(const std::vector<float> &ex, const std::vector<uint32_t> &scene
 
 // ---- path queries: color(Ray(o, d), scene, 0) (rayweek1.cpp:517-534) for caller-supplied rays and stream states --------------------------
 // Per level the hit test above, then the level's scatter in scalar C++, operation by operation in the reference's order — what
-// shade_level of r1_trace.hpp does on the device, with the same host-made material constants (r1_sweep.cpp).  The attenuations are
+// shade_level of r1_shade.hpp does on the device, with the same host-made material constants (r1_sweep.cpp).  The attenuations are
 // applied innermost first once the path has reached the sky: a0 * (a1 * (... * sky)), rayweek1.cpp:525.
 
 // mymath.h:17-35 (the x4 forms :41-73 lane by lane)
@@ -269,7 +269,7 @@ void trace_range(const TraceScene &T, int32_t max_bounces, const r1_ray *rays, c
                 if (discriminant > 0)
                 {
                     refracted = sub(scale(sub(d, scale(outward, dt)), ni_over_nt), scale(outward, sqrtf(discriminant)));
-                    // schlick rayweek1.cpp:454-459, x^5 exactly rounded (pow5 of r1_trace.hpp)
+                    // schlick rayweek1.cpp:454-459, x^5 exactly rounded (r1s_pow5 of r1_scatter.h)
                     const float r0 = mt[2];
                     const double x = (double)(1.0f - cosine), x2 = x * x;
                     reflect_prob = r0 + (1.0f - r0) * (float)(x2 * x2 * x);
@@ -367,7 +367,7 @@ extern "C" int r1_trace_rays_host(const r1_scene *s, int32_t max_bounces, const 
     return R1_OK;
 }
 
-// rayweek1.cpp:757-760 under the seeding contract — start_ray of r1_trace.hpp on the host, without the Ray constructor's normalisation
+// rayweek1.cpp:757-760 under the seeding contract — start_ray of r1_sample.hpp on the host, without the Ray constructor's normalisation
 extern "C" int r1_camera_rays(const r1_camera *cam, const r1_params *p, const int32_t *x, const int32_t *y, const int32_t *s, size_t n, r1_ray *rays_out,
                               r1_sample_seed *seeds_out)
 {

@@ -1,5 +1,6 @@
 // r1_query_kernels.hip — the kernels of the ray queries (r1_cast_rays*) and of the path queries (r1_trace_rays*, §4.22):
-// caller-supplied rays through the trace kernels' walks (r1_trace.hpp: bvh_advance, grid_trace, sweep_reference, as they are).  There is
+// caller-supplied rays through the trace kernels' walks as they are — sweep_reference (r1_hit_sweep.hpp), bvh_advance (r1_hit_tree.hpp), grid_trace
+// (r1_hit_grid.hpp) — claimed with chunk_claim (r1_sample.hpp) and, the path jobs, shaded by shade_level (r1_shade.hpp).  There is
 // one loop per structure — box tree, uniform grid, reference form — and a JOB says what a lane does with a ray: how it is loaded and
 // when it is no ray at all, how its walk is seeded, what a complete walk leads to and which record is written.
 //   Args                     the kernel's argument struct; every job's has t, rays, cursor, n and claim
@@ -14,7 +15,11 @@
 //                            of a ray without a walk behind the walk with the others: a second place that writes records costs the cast's grid kernels
 //                            6 VGPRs (profiles/r15/query_kernel_meta.txt)
 // The loops keep the ray's index themselves and hand it to finish(): a job holds no state that is unset before its first load.
-#include "r1_trace.hpp"
+#include "r1_hit_sweep.hpp"
+#include "r1_hit_tree.hpp"
+#include "r1_hit_grid.hpp"
+#include "r1_sample.hpp"
+#include "r1_shade.hpp"
 #include "r1_internal.h"
 
 #ifndef R1_CAST_WAVES_SMALL

@@ -37,14 +37,14 @@ static TileRect tile_rect(const r1_params *p, int t)
 // The ray count of a frame the caller waits for.  direct: the frame's last launch stores it straight into the context's page-locked word
 // (8 bytes over PCIe, no second copy to enqueue and wait for); else it is copied from behind the counter block.  rays_word: what
 // enqueue_frame is given.  read_rays: after the frame and the caller's own copies are enqueued — waits for the context's stream.
-static void *rays_word(const r1_context *c, bool direct) { return direct ? (void *)c->host_word_dev : nullptr; }
+static void *rays_word(const r1_context *c, bool direct) { return direct ? (void *)&c->host_word_dev->rays : nullptr; }
 static int read_rays(r1_context *c, bool direct, uint64_t *rays)
 {
     if (!direct) // (behind the block the frame's last launch zeroes)
-        R1_HIP(hipMemcpyAsync(rays, (char *)c->counters.p + R1_COUNTER_BYTES, 8, hipMemcpyDeviceToHost, c->stream));
+        R1_HIP(hipMemcpyAsync(rays, counter_at(c, R1_TAIL_RAYS), 8, hipMemcpyDeviceToHost, c->stream));
     R1_HIP(hipStreamSynchronize(c->stream));
     if (direct)
-        *rays = *(volatile unsigned long long *)c->host_word;
+        *rays = *(volatile unsigned long long *)&c->host_word->rays;
     return R1_OK;
 }
 
@@ -76,7 +76,7 @@ static int render_host(r1_context *c, const r1_params *p, uint8_t *rgb_out, uint
     // a page-locked pixel buffer (r1_host_alloc) receives the tiles straight from the trace kernel's resolvers: no copy either
     Landing land_to;
     if (direct && !sharded)
-        land_to.out = mapped_host(rgb_out), land_to.rays = c->host_word_dev;
+        land_to.out = mapped_host(rgb_out), land_to.rays = &c->host_word_dev->rays;
     if ((rc = enqueue_frame(c, p, c->image.p, sharded ? 1 : 0, rays_word(c, direct), c->stream, false, nullptr, &land_to)))
         return rc;
 
@@ -350,7 +350,7 @@ extern "C" int r1_render_adaptive(r1_context *c, const r1_params *p, const r1_ad
     c->pass_valid = false; // (the `all` accumulator is r1_render_pass's: an accumulation of the context ends here, as at first_sample 0)
     const bool direct = c->host_word_dev != nullptr; // ray count and list length straight into the context's page-locked words, as r1_render_pass
     uint32_t *const lists[2] = {(uint32_t *)c->adapt_list.p, (uint32_t *)c->adapt_list.p + tiles};
-    uint32_t *const d_count = direct ? (uint32_t *)c->host_word_dev + 4 : (uint32_t *)c->adapt_list.p + 2 * (size_t)tiles;
+    uint32_t *const d_count = direct ? &c->host_word_dev->adapt_count : (uint32_t *)c->adapt_list.p + 2 * (size_t)tiles;
     R1_HIP(r1_launch_adapt_compact(nullptr, (uint32_t)tiles, (const R1TileReport *)c->adapt_report.p, 0u, lists[0], d_count, c->stream)); // every tile, in order
     uint32_t m = (uint32_t)tiles;
     uint64_t rays_sum = 0;
@@ -373,7 +373,7 @@ extern "C" int r1_render_adaptive(r1_context *c, const r1_params *p, const r1_ad
         if ((rc = read_rays(c, direct, &rays)))
             return rc;
         if (direct)
-            next = ((volatile uint32_t *)c->host_word)[4];
+            next = *(volatile uint32_t *)&c->host_word->adapt_count;
         rays_sum += rays; // (summed on the host, pass by pass, as r1_render_pass does)
         ++passes;
         if (next > m)
@@ -446,7 +446,7 @@ extern "C" int r1_render_async(r1_context *c, const r1_params *p, uint8_t *rgb_o
     if (rgb_out && !land_to.used) // (both NULL: the frame stays in the context's device buffers — a measurement aid, bench.py's value_device_resident)
     {
         R1_HIP(hipMemcpyAsync(rgb_out, c->image.p, img_bytes, hipMemcpyDeviceToHost, st));
-        R1_HIP(hipMemcpyAsync(num_rays_out, (char *)c->counters.p + R1_COUNTER_BYTES, 8, hipMemcpyDeviceToHost, st));
+        R1_HIP(hipMemcpyAsync(num_rays_out, counter_at(c, R1_TAIL_RAYS), 8, hipMemcpyDeviceToHost, st));
     }
     return R1_OK;
 }

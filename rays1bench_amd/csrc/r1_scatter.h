@@ -1,5 +1,5 @@
 // r1_scatter.h — the direction arithmetic of Material::scatter (rayweek1.cpp:403-409, :427-433, :470-511) for the three materials,
-// shared by shade_level (r1_trace.hpp) and the host (tools/check_scatter_host.cpp, tests/test_scatter_host.py), so that the CPU
+// shared by shade_level (r1_shade.hpp) and the host (tools/check_scatter_host.cpp, tests/test_scatter_host.py), so that the CPU
 // test checks the kernels' own arithmetic.  The draws, the exact square root, the normalisation, the attenuation stack and the depth
 // rule stay with the caller; what is here is + - x, compares and selects on fp32 (the build passes -ffp-contract=off), and x^5
 // through double.  The vector type V is the caller's: any struct of three floats x, y, z.

@@ -1,4 +1,4 @@
-// r1_sweep.cpp — host builder of the sweep's tables (R1_VARIANT_PREFILTER, r1_trace.hpp sweep_prefilter): sphere groups with a conservative
+// r1_sweep.cpp — host builder of the sweep's tables (R1_VARIANT_PREFILTER, r1_hit_sweep.hpp sweep_prefilter): sphere groups with a conservative
 // bounding sphere each, in pair layout, and the per-sphere rows.  Host code only: no HIP call, no context; r1_sweep_describe shows the
 // tables to tests/test_sweep_host.py.
 
@@ -25,7 +25,7 @@ static float round_down(double v)
 
 // ---- sphere groups (level 1 of the sweep) ------------------------------------------------------
 // The sweep tests GROUPS of up to R1_GROUP_MAX nearby spheres against a bounding sphere first and
-// re-tests the members of flagged groups exactly (r1_trace.hpp).  Grouping is a pure work
+// re-tests the members of flagged groups exactly (r1_hit_sweep.hpp exact_trips).  Grouping is a pure work
 // reduction: every active sphere belongs to exactly one group, the group test is conservative,
 // and hits are still resolved per sphere in the reference's arithmetic and index order.
 struct R1Group

@@ -1,4 +1,4 @@
-// r1_trace_grid_small.hip — the trace kernel's instantiations for one family (r1_builds.h lists them); kernel and device functions: r1_trace.hpp
+// r1_trace_grid_small.hip — the trace kernel's instantiations for one family (r1_builds.h lists them); the kernel: r1_trace.hpp, its device functions: the headers that file includes
 #define R1_TU_NAME grid_small
 #define R1_TU_BUILDS R1_BUILDS_GRID_SMALL
 #include "r1_trace_tu.inc"

@@ -1,4 +1,4 @@
-"""CPU tests of the flat axis of a box tree (r1_bvh.cpp "flat axis", r1_trace.hpp visit_flat; no GPU).
+"""CPU tests of the flat axis of a box tree (r1_bvh.cpp "flat axis", r1_hit_tree.hpp bvh_advance: visit_flat; no GPU).
 
 The builder names at most one axis along which the union of the slabs of every box the node loop tests is at most 1.25 x the
 narrowest of them, and reports the union as (flat_m, flat_e) rounded outward; the small-scene tree kernels then test that ONE slab

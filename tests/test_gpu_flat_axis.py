@@ -1,4 +1,4 @@
-"""GPU tests of the flat walk of the box-tree kernels (r1_trace.hpp visit_flat).
+"""GPU tests of the flat walk of the box-tree kernels (r1_hit_tree.hpp bvh_advance: visit_flat).
 
 The large scene's tree is flat along y (r1_bvh_info.flat_axis == 1): the small-scene tree kernels test ONE y slab once per call of the
 walk and two axes per child box.  That changes which boxes a ray passes, never what it hits: through every entry point — r1_render,

@@ -23,7 +23,7 @@ def _fma(a, b, c):
 
 
 def offers(cx, cy, cz, rsq, o, d):
-    """exact_offer (r1_trace.hpp, rayweek1.cpp:192-202, :294-313) vectorised over spheres: the t each sphere offers, inf for none."""
+    """exact_offer (r1_hit_sweep.hpp, rayweek1.cpp:192-202, :294-313) vectorised over spheres: the t each sphere offers, inf for none."""
     cox, coy, coz = (cx - o[0]).astype(F), (cy - o[1]).astype(F), (cz - o[2]).astype(F)
     nb = _fma(coz, d[2], _fma(coy, d[1], (cox * d[0]).astype(F)))
     c = (_fma(coz, coz, _fma(coy, coy, (cox * cox).astype(F))) - rsq).astype(F)

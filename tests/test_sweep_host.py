@@ -2,7 +2,7 @@
 through r1_sweep_describe.  The sweep tests GROUPS of nearby spheres against a bounding sphere and re-tests the members of flagged groups
 exactly, so it computes the reference's pixels only while the group test is conservative: whenever the reference's own fp32 discriminant
 accepts a member, the group must be flagged.  Checked here: the partition into groups, the covering radius and the Kp bound in float64,
-the table layout the kernel reads (r1_trace.hpp sweep_prefilter, exact_trips), and the conservative property itself on rays, with the
+the table layout the kernel reads (r1_hit_sweep.hpp sweep_prefilter, exact_trips), and the conservative property itself on rays, with the
 kernel's fp32 FMA chains restated in numpy."""
 import re
 
@@ -154,7 +154,7 @@ def make_rays(t, cam, n, rng):
 
 
 def reference_accepts(t, o, d):
-    """[ray, sphere]: the sign bit of the reference's fp32 discriminant is clear (rayweek1.cpp:192-204; exact_offer, r1_trace.hpp)"""
+    """[ray, sphere]: the sign bit of the reference's fp32 discriminant is clear (rayweek1.cpp:192-204; exact_offer, r1_hit_sweep.hpp)"""
     ox, oy, oz, dx, dy, dz = (v[:, None] for v in (o[:, 0], o[:, 1], o[:, 2], d[:, 0], d[:, 1], d[:, 2]))
     cox, coy, coz = (t.c32[None, :, 0] - ox).astype(F), (t.c32[None, :, 1] - oy).astype(F), (t.c32[None, :, 2] - oz).astype(F)
     nb = _fma(coz, dz, _fma(coy, dy, (cox * dx).astype(F)))

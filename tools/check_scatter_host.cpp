@@ -37,7 +37,7 @@ bool same(const float a, const float b) { return bits(a) == bits(b); }
 bool same(const V3 a, const V3 b) { return same(a.x, b.x) && same(a.y, b.y) && same(a.z, b.z); }
 bool same(const V3 a, const float *b) { return same(a.x, b[0]) && same(a.y, b[1]) && same(a.z, b[2]); }
 
-// the draws and the normalisation as shade_level makes them (r1_trace.hpp)
+// the draws and the normalisation as shade_level makes them (r1_shade.hpp)
 uint32_t xorshift32(uint32_t &state)
 {
     uint32_t x = state;

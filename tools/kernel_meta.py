@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
-"""tools/kernel_meta.py [lib] [--json] — register / LDS / spill metadata and an instruction census (flat_load, scratch_, v_mfma)
+"""tools/kernel_meta.py [lib] [--json | --disasm FILE] — register / LDS / spill metadata and an instruction census (flat_load, scratch_, v_mfma)
 of every kernel in every gfx950 code object of librays1.so.  The library is linked from several translation units, so its
 .hip_fatbin section holds several offload bundles; each is unbundled and read with llvm-readelf / llvm-objdump.
-Used by tests/test_host.py (no generic loads, no scratch, no MFMA in the product kernels) and by hand."""
+Used by tests/test_host.py (no generic loads, no scratch, no MFMA in the product kernels) and by hand.
+--disasm FILE writes the disassembly of all code objects, one after the other, without the lines that name the temporary file: two
+builds have the same device code iff `cmp` finds their files equal (the build is deterministic)."""
 import json
 import os
 import re
@@ -80,9 +82,27 @@ def collect(lib):
         return allk
 
 
+def disassemble(lib, path):
+    with tempfile.TemporaryDirectory() as tmp, open(path, "w") as out:
+        for co in code_objects(lib, tmp):
+            dis = subprocess.run([f"{LLVM}/llvm-objdump", "-d", "--no-show-raw-insn", co], capture_output=True, text=True, check=True).stdout
+            out.writelines(line + "\n" for line in dis.splitlines() if "file format" not in line)
+
+
 def main():
-    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    argv = sys.argv[1:]
+    disasm = None
+    if "--disasm" in argv:
+        at = argv.index("--disasm")
+        if at + 1 >= len(argv):
+            sys.exit("--disasm needs a file name")
+        disasm = argv[at + 1]
+        del argv[at:at + 2]
+    args = [a for a in argv if not a.startswith("--")]
     lib = os.path.realpath(args[0] if args else os.path.join(os.path.dirname(__file__), "..", "rays1bench_amd", "lib", "librays1.so"))
+    if disasm:
+        disassemble(lib, disasm)
+        return
     k = collect(lib)
     if "--json" in sys.argv:
         print(json.dumps(k, indent=1, sort_keys=True))
