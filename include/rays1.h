@@ -252,6 +252,27 @@ int r1_update_spheres(r1_context *ctx, uint32_t first, uint32_t count, const r1_
  * sphere keeps its material), a non-finite centre is r1_update_centers_device's.  The context's host copies are NOT updated. */
 int r1_update_spheres_device(r1_context *ctx, uint32_t first, uint32_t count, const r1_sphere_update *u, void *hip_stream);
 
+/* ---- re-sort: the spheres re-dealt into the tree's leaves ---- */
+
+/* A refit keeps the tree's topology, so the tree goes stale as the spheres wander.  This call keeps the topology too —
+ * every table shape, every kernel — and re-deals the spheres into the leaf slots on the device, by a rank split along the widest axis of
+ * the centres at every inner node (csrc/r1_bvh_sort.h has the rule; leaves the builder made of outliers, the ground and the big balls of
+ * the reference's scenes, keep their spheres), from the centres the device holds; then it refits.  Enqueued on `hip_stream` (NULL: the
+ * context's stream); waits for nothing.  Afterwards every render, ray query and path query is bit-identical — pixels, ray counts, hit
+ * records, sample records — to a fresh context after r1_set_scene with the context's current spheres: the updates' own contract.
+ * It counts as an update for the context's state: the flat y slab is dropped; PREFILTER, STATS, WAVEFRONT, GRID, GRID_STATS and a GRID
+ * cast return R1_EINVAL ("the scene has moved") until the next r1_set_scene; a progressive accumulation ends; "one update at a time per
+ * context" holds; r1_last_launch_info / r1_last_timing are left alone.  Valid before any update too.  R1_EINVAL before the first
+ * r1_set_scene.  A tree without a movable sphere: R1_OK, nothing is changed or enqueued, the state stays.  A pure function of the
+ * centres, the active order and the topology: a second call with no update in between changes no byte.  r1_update_centers* and
+ * r1_update_spheres* keep working afterwards.  There is no r1_multi form. */
+int r1_resort_spheres(r1_context *ctx, void *hip_stream);
+
+/* Diagnostic, synchronous (as r1_bvh_download): the tree's leaf slots as the device holds them, as scene indices (0xFFFFFFFF: the empty
+ * partner of an odd sphere) — what r1_bvh_describe returns in ids_out before any re-sort, r1_bvh_resort_describe after one.  *n receives
+ * the number of slots; ids_out may be NULL (the count alone), else ids_cap >= *n (R1_ELIMIT otherwise). */
+int r1_bvh_ids_download(r1_context *ctx, uint32_t *ids_out, size_t ids_cap, size_t *n);
+
 /* Diagnostic, synchronous (waits for the context's stream, as r1_bvh_download): the device's per-sphere rows of the n active spheres, in
  * active order: exact [n][4] {cx cy cz radius_sq}, shade [n][4] {inv_radius, albedo r g b}, mat [n][4] {type, the bits of param, of
  * 1 / ref_idx and of schlick's r0}, radii [n][2] {bound radius, test radius} (fp64).  Each may be NULL; all NULL: *n_active alone.
@@ -709,6 +730,14 @@ int r1_bvh_refit_describe(const r1_scene *built, const float *x, const float *y,
  * sphere never hittable, a point in its boxes. */
 int r1_bvh_refit_describe_spheres(const r1_scene *built, const float *x, const float *y, const float *z, const float *radius_sq,
                                   const float *inv_radius, int32_t leaf_max, r1_bvh_info *info, float *nodes_out, size_t nodes_cap);
+
+/* The CPU-side pin of r1_resort_spheres (no GPU): builds the tree of `built`, re-deals its movable spheres for the scene-indexed centres
+ * and radii (as r1_bvh_refit_describe_spheres takes them; radius_sq and inv_radius both NULL: the built scene's) by the device's steps
+ * over the same tables (csrc/r1_bvh_sort.h), refits, and returns the node rows and the leaf slots (scene indices, 0xFFFFFFFF: empty, as
+ * r1_bvh_describe).  Pinned and empty slots are those of r1_bvh_describe(built); info->flat_axis is -1. */
+int r1_bvh_resort_describe(const r1_scene *built, const float *x, const float *y, const float *z, const float *radius_sq,
+                           const float *inv_radius, int32_t leaf_max, r1_bvh_info *info, float *nodes_out, size_t nodes_cap, uint32_t *ids_out,
+                           size_t ids_cap);
 
 /* Diagnostic, synchronous: the node rows of the context's tree as the device holds them (16 floats per node, as r1_bvh_describe), after
  * waiting for the context's stream (an update enqueued on another stream is the caller's to wait for).  *nodes receives the number of

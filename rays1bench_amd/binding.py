@@ -209,6 +209,10 @@ SYMBOLS = [
     ("r1_bvh_refit_describe_spheres", C.c_int, [C.POINTER(CScene), _f32p, _f32p, _f32p, _f32p, _f32p, C.c_int32, C.POINTER(BvhInfo), _f32p, C.c_size_t]),
     ("r1_tables_download", C.c_int, [_ctx, _f32p, _f32p, C.POINTER(C.c_uint32), _dblp, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("r1_bvh_download", C.c_int, [_ctx, _f32p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("r1_resort_spheres", C.c_int, [_ctx, C.c_void_p]),
+    ("r1_bvh_ids_download", C.c_int, [_ctx, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("r1_bvh_resort_describe", C.c_int, [C.POINTER(CScene), _f32p, _f32p, _f32p, _f32p, _f32p, C.c_int32, C.POINTER(BvhInfo), _f32p, C.c_size_t,
+                                         C.POINTER(C.c_uint32), C.c_size_t]),
     ("r1_grid_describe", C.c_int, [C.POINTER(CScene), C.POINTER(GridInfo), C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t,
                                    C.POINTER(C.c_uint32), C.c_size_t]),
     ("r1_grid_visit", C.c_int, [C.POINTER(CScene), _f32p, _f32p, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_size_t), _i32p, _f32p, _i32p]),
@@ -454,6 +458,20 @@ class Renderer:
         nodes = np.zeros((n.value, 16), np.float32)
         _check(lib().r1_bvh_download(self._c, nodes.ctypes.data_as(_f32p), nodes.size, C.byref(n)))
         return nodes
+
+    def resort_spheres(self, stream=None):
+        """r1_resort_spheres: the spheres re-dealt into the box tree's leaves on the device, then the refit; the topology stays.  Enqueues on
+        `stream` (a stream pointer; None: the context's stream) and waits for nothing."""
+        _check(lib().r1_resort_spheres(self._c, _stream_arg(stream)))
+
+    def bvh_ids_download(self):
+        """r1_bvh_ids_download: the tree's leaf slots as the device holds them, uint32 scene indices, 0xFFFFFFFF = empty (diagnostic,
+        synchronous)."""
+        n = C.c_size_t()
+        _check(lib().r1_bvh_ids_download(self._c, None, 0, C.byref(n)))
+        ids = np.zeros(max(n.value, 1), np.uint32)
+        _check(lib().r1_bvh_ids_download(self._c, ids.ctypes.data_as(C.POINTER(C.c_uint32)), ids.size, C.byref(n)))
+        return ids[:n.value]
 
     def render(self, params):
         img = np.zeros((params.height, params.width, 3), np.uint8)
@@ -802,6 +820,27 @@ def bvh_refit_describe_spheres(cscene, x, y, z, radius_sq=None, inv_radius=None,
     if (radius_sq is None) != (inv_radius is None):
         raise R1Error(R1_EINVAL, "bvh_refit_describe_spheres: radius_sq and inv_radius go together")
     return _refit_describe("bvh_refit_describe_spheres", cscene, x, y, z, radius_sq, inv_radius, leaf_max)
+
+
+def bvh_resort_describe(cscene, x, y, z, radius_sq=None, inv_radius=None, leaf_max=0):
+    """r1_bvh_resort_describe: the tree r1_set_scene builds for `cscene`, its movable spheres re-dealt on the host for the scene-indexed centres
+    (and radii; both None: the built scene's), then refitted: (info dict, nodes float32[n, 16], ids uint32[2 * pairs], 0xFFFFFFFF = empty)."""
+    if (radius_sq is None) != (inv_radius is None):
+        raise R1Error(R1_EINVAL, "bvh_resort_describe: radius_sq and inv_radius go together")
+    arrays = [np.ascontiguousarray(v, np.float32) for v in (x, y, z) + (() if radius_sq is None else (radius_sq, inv_radius))]
+    if any(v.shape != (cscene.count,) for v in arrays):
+        raise R1Error(R1_EINVAL, "bvh_resort_describe: every array needs cscene.count entries")
+    ptrs = [v.ctypes.data_as(_f32p) for v in arrays] + ([None, None] if radius_sq is None else [])
+    info = BvhInfo()
+    _check(lib().r1_bvh_resort_describe(C.byref(cscene), *ptrs, leaf_max, C.byref(info), None, 0, None, 0))
+    nodes = np.zeros((info.nodes, 16), np.float32)
+    ids = np.zeros(max(2 * info.pairs, 2), np.uint32)
+    _check(lib().r1_bvh_resort_describe(C.byref(cscene), *ptrs, leaf_max, C.byref(info), nodes.ctypes.data_as(_f32p), nodes.size,
+                                        ids.ctypes.data_as(C.POINTER(C.c_uint32)), ids.size))
+    d = {k: int(getattr(info, k)) for k, _ in BvhInfo._fields_ if k not in ("centre", "flat_m", "flat_e")}
+    d["flat_m"], d["flat_e"] = np.float32(info.flat_m), np.float32(info.flat_e)
+    d["centre"] = np.array(list(info.centre), np.float32)
+    return d, nodes, ids[:2 * info.pairs]
 
 
 def _refit_describe(who, cscene, x, y, z, radius_sq, inv_radius, leaf_max):

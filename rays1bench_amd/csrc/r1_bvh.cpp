@@ -90,7 +90,7 @@ struct Builder
         return r;
     }
 
-    uint32_t make_leaf(uint32_t b, uint32_t e)
+    uint32_t make_leaf(uint32_t b, uint32_t e, bool pinned = false)
     {
         // spheres are stored in PAIRS (two spheres per pair of 16-byte loads); the partner of
         // an odd sphere has radius_sq = -inf, which makes its discriminant -inf: never flagged
@@ -107,17 +107,18 @@ struct Builder
             out->prims.insert(out->prims.end(), v, v + 8);
             out->ids.push_back(ia);
             out->ids.push_back(has_b ? ib : 0xFFFFFFFFu);
+            out->pair_pinned.push_back(pinned ? 1 : 0); // (a side table: r1_bvh_sort.h)
         }
         ++out->n_leaves;
         return LEAF | (pairs << 28) | first;
     }
 
-    // returns the child reference for order[b, e); bx = its bounds
-    uint32_t build(uint32_t b, uint32_t e, int depth, const Box &bx)
+    // returns the child reference for order[b, e); bx = its bounds; peeled: these are the outliers a peel set apart (one leaf, pinned)
+    uint32_t build(uint32_t b, uint32_t e, int depth, const Box &bx, bool peeled = false)
     {
         const uint32_t n = e - b;
         if (n <= (uint32_t)leaf_max)
-            return make_leaf(b, e);
+            return make_leaf(b, e, peeled);
 
         // levels a balanced split of n spheres still needs; SAH only while the depth budget allows
         int need = 0;
@@ -127,6 +128,7 @@ struct Builder
 
         uint32_t mid = 0;
         int axis = 0;
+        bool peel = false;
         // Outliers first: a few spheres much larger than the rest of the node (the ground and the r = 2 balls among the
         // r = 0.45 lattice of the reference's large scene) would inflate every box on their way down a centroid split
         // (the balls sat four levels deep and made the boxes above them 2.7 high instead of 0.5).  Up to `leaf_max`
@@ -147,7 +149,7 @@ struct Builder
             if (nb >= 1 && nb <= (uint32_t)leaf_max)
             {
                 std::stable_partition(order.begin() + b, order.begin() + e, [&](uint32_t q) { return sphere[q].rmax > big; });
-                mid = b + nb;
+                mid = b + nb, peel = true;
             }
         }
         if (mid == 0)
@@ -233,7 +235,7 @@ struct Builder
         out->nodes.resize(out->nodes.size() + 16);
         out->max_depth = std::max(out->max_depth, depth + 1);
         const Box b0 = bound(b, mid), b1 = bound(mid, e);
-        const uint32_t c0 = build(b, mid, depth + 1, b0);
+        const uint32_t c0 = build(b, mid, depth + 1, b0, peel);
         const uint32_t c1 = build(mid, e, depth + 1, b1);
         fill(node, b0, c0, b1, c1);
         return node;
@@ -256,7 +258,7 @@ struct Builder
 void r1_build_bvh(uint32_t na, const float *cx, const float *cy, const float *cz, const float *rsq, const double *rbound, int leaf_max,
                   R1Bvh &out)
 {
-    out.nodes.clear(), out.prims.clear(), out.ids.clear();
+    out.nodes.clear(), out.prims.clear(), out.ids.clear(), out.pair_pinned.clear();
     out.max_depth = 0, out.n_leaves = 0;
     if (leaf_max < 1)
         leaf_max = 1;
@@ -509,7 +511,7 @@ void r1_build_bvh(uint32_t na, const float *cx, const float *cy, const float *cz
     }
     // keep the tables non-empty for the uploader
     if (out.prims.empty())
-        out.prims.assign(8, 0.0f), out.ids.assign(2, 0xFFFFFFFFu);
+        out.prims.assign(8, 0.0f), out.ids.assign(2, 0xFFFFFFFFu), out.pair_pinned.assign(1, 0);
 }
 
 // The hittable ("active") spheres of a caller's scene, in scene order: inv_radius != 0
@@ -625,6 +627,115 @@ void r1_bvh_refit_host(R1Bvh &b, const R1RefitTopo &t, uint32_t na, const float 
     b.flat_axis = -1, b.flat_m = b.flat_e = 0.0f; // (no slab is computed for a moved scene)
 }
 
+// ---- re-sort --------------------------------------------------------
+
+// movable slots below `ref`, in the order a walk with child 0 first meets them: the builder's slot order
+static uint32_t sort_walk(const R1Bvh &b, uint32_t ref, size_t depth, R1SortTopo &s, std::vector<std::vector<R1SortSeg>> &by_depth)
+{
+    if (ref & 0x80000000u)
+    {
+        const uint32_t first = ref & 0x0FFFFFFFu, pairs = (ref >> 28) & 7u;
+        uint32_t m = 0;
+        for (uint32_t q = 2u * first; q < 2u * (first + pairs); ++q)
+            if (b.ids[q] != 0xFFFFFFFFu && !b.pair_pinned[q >> 1])
+                s.mslot.push_back(q), s.mov.push_back(b.ids[q]), ++m;
+        return m;
+    }
+    uint32_t c[2];
+    memcpy(c, &b.nodes[16 * (size_t)ref + 14], 8);
+    const uint32_t at = (uint32_t)s.mslot.size();
+    const uint32_t k = sort_walk(b, c[0], depth + 1, s, by_depth);
+    const uint32_t m = k + sort_walk(b, c[1], depth + 1, s, by_depth);
+    if (k > 0 && k < m)
+    {
+        if (by_depth.size() <= depth)
+            by_depth.resize(depth + 1);
+        by_depth[depth].push_back(R1SortSeg{at, k, at + m});
+    }
+    return m;
+}
+
+void r1_bvh_sort_topology(const R1Bvh &b, R1SortTopo &s)
+{
+    s.mov.clear(), s.mslot.clear(), s.seg.clear(), s.pos_seg.clear();
+    s.depth_off.assign(1, 0u);
+    std::vector<std::vector<R1SortSeg>> by_depth;
+    if (b.nodes.size() >= 16)
+        sort_walk(b, 0u, 0, s, by_depth);
+    std::sort(s.mov.begin(), s.mov.end());
+    const size_t m = s.mov.size();
+    for (const std::vector<R1SortSeg> &level : by_depth)
+    {
+        if (level.empty())
+            continue;
+        const size_t row = s.pos_seg.size();
+        s.pos_seg.resize(row + m, R1S_NONE);
+        for (const R1SortSeg &g : level) // (the walk meets one depth's nodes in ascending b)
+        {
+            for (uint32_t p = g.b; p < g.e; ++p)
+                s.pos_seg[row + p] = (uint32_t)s.seg.size();
+            s.seg.push_back(g);
+        }
+        s.depth_off.push_back((uint32_t)s.seg.size());
+    }
+}
+
+void r1_bvh_resort_host(R1Bvh &b, R1RefitTopo &t, const R1SortTopo &s, const float *cx, const float *cy, const float *cz, const float *rsq)
+{
+    const size_t m = s.mov.size();
+    if (m == 0)
+        return;
+    const float *const c[3] = {cx, cy, cz};
+    // "three sorted lists": (key, active index) — every composite key is distinct, so any sorting algorithm gives this order
+    std::vector<uint32_t> list[3], next(m);
+    for (int a = 0; a < 3; ++a)
+    {
+        list[a] = s.mov;
+        std::sort(list[a].begin(), list[a].end(), [&](uint32_t p, uint32_t q) { return r1s_before(r1s_key(r1s_clamp(c[a][p])), p, r1s_key(r1s_clamp(c[a][q])), q); });
+    }
+    std::vector<uint8_t> left(t.slot.size(), 0);
+    std::vector<uint32_t> axis(s.seg.size(), 0u);
+    for (size_t d = 0; d + 1 < s.depth_off.size(); ++d) // "per depth of the tree"
+    {
+        const uint32_t *pos_seg = &s.pos_seg[d * m];
+        for (uint32_t g = s.depth_off[d]; g < s.depth_off[d + 1]; ++g) // "axis"
+        {
+            float first[3], last[3];
+            for (int a = 0; a < 3; ++a)
+                first[a] = r1s_clamp(c[a][list[a][s.seg[g].b]]), last[a] = r1s_clamp(c[a][list[a][s.seg[g].e - 1]]);
+            axis[g] = (uint32_t)r1s_axis(first, last);
+        }
+        for (uint32_t p = 0; p < m; ++p) // "flag"
+            if (pos_seg[p] != R1S_NONE)
+                left[list[axis[pos_seg[p]]][p]] = p < s.seg[pos_seg[p]].b + s.seg[pos_seg[p]].k ? 1 : 0;
+        for (int a = 0; a < 3; ++a) // "prefix sum and stable segmented partition"
+        {
+            uint32_t sum = 0, base = 0;
+            for (uint32_t p = 0; p < m; ++p)
+            {
+                const uint32_t g = pos_seg[p], sphere = list[a][p];
+                if (g == R1S_NONE)
+                {
+                    next[p] = sphere;
+                    continue;
+                }
+                if (p == s.seg[g].b)
+                    base = sum;
+                next[r1s_dest(s.seg[g].b, s.seg[g].k, p, sum - base, left[sphere] != 0)] = sphere;
+                sum += left[sphere];
+            }
+            list[a].swap(next);
+        }
+    }
+    for (uint32_t p = 0; p < m; ++p) // "write-back": inside a leaf the spheres stand in the order of the x list
+    {
+        const uint32_t sphere = list[0][p], q = s.mslot[p];
+        b.ids[q] = sphere, t.slot[sphere] = q;
+        float *pr = &b.prims[8 * (size_t)(q >> 1) + (q & 1u)];
+        pr[0] = cx[sphere], pr[2] = cy[sphere], pr[4] = cz[sphere], pr[6] = rsq[sphere];
+    }
+}
+
 // the tree r1_set_scene builds for `s`, and what it was built from (active order)
 struct Described
 {
@@ -719,6 +830,57 @@ extern "C" int r1_bvh_refit_describe_spheres(const r1_scene *built, const float 
                                              const float *inv_radius, int32_t leaf_max, r1_bvh_info *info, float *nodes_out, size_t nodes_cap)
 {
     return refit_describe("r1_bvh_refit_describe_spheres", built, x, y, z, radius_sq, inv_radius, leaf_max, info, nodes_out, nodes_cap);
+}
+
+// Host-only pin of the re-sort (include/rays1.h): the tree of `built`, its movable spheres re-dealt by r1_bvh_sort.h's rule to the scene-indexed
+// centres (and radii, taken as refit_describe takes them), then refitted.
+extern "C" int r1_bvh_resort_describe(const r1_scene *built, const float *x, const float *y, const float *z, const float *radius_sq,
+                                      const float *inv_radius, int32_t leaf_max, r1_bvh_info *info, float *nodes_out, size_t nodes_cap,
+                                      uint32_t *ids_out, size_t ids_cap)
+{
+    if (!built || !info || !x || !y || !z || !radius_sq != !inv_radius)
+    {
+        r1_set_error("r1_bvh_resort_describe: null argument");
+        return R1_EINVAL;
+    }
+    Described d;
+    int rc = describe_build(built, leaf_max, d);
+    if (rc)
+        return rc;
+    R1RefitTopo t;
+    R1SortTopo s;
+    r1_bvh_topology(d.b, d.na, t);
+    r1_bvh_sort_topology(d.b, s);
+    for (uint32_t a = 0; a < d.na; ++a)
+    {
+        const uint32_t i = d.scene_index[a];
+        d.x[a] = x[i], d.y[a] = y[i], d.z[a] = z[i];
+        if (radius_sq)
+        {
+            float inv;
+            double rr[2];
+            r1f_radius_rows(radius_sq[i], inv_radius[i], d.r[a], inv, rr);
+            d.rb[a] = rr[0];
+        }
+    }
+    r1_bvh_resort_host(d.b, t, s, d.x.data(), d.y.data(), d.z.data(), d.r.data());
+    r1_bvh_refit_host(d.b, t, d.na, d.x.data(), d.y.data(), d.z.data(), d.r.data(), d.rb.data());
+    describe_info(d, info);
+    info->flat_axis = -1, info->flat_m = info->flat_e = 0.0f;
+    if (nodes_out)
+    {
+        if (nodes_cap < d.b.nodes.size())
+            return R1_ELIMIT;
+        memcpy(nodes_out, d.b.nodes.data(), d.b.nodes.size() * 4);
+    }
+    if (ids_out)
+    {
+        if (ids_cap < d.b.ids.size())
+            return R1_ELIMIT;
+        for (size_t i = 0; i < d.b.ids.size(); ++i)
+            ids_out[i] = d.b.ids[i] == 0xFFFFFFFFu || d.na == 0 ? 0xFFFFFFFFu : d.scene_index[d.b.ids[i]];
+    }
+    return R1_OK;
 }
 
 // Host-only view of the index (include/rays1.h): what r1_set_scene would build for this scene.

@@ -1,4 +1,5 @@
-// r1_bvh.h — what r1_bvh.cpp hands to the rest of the host code: the built tree, the topology tables of a refit, and the host refit.
+// r1_bvh.h — what r1_bvh.cpp hands to the rest of the host code: the built tree, the topology tables of a refit and of a re-sort, and the host
+// forms of both.
 #ifndef R1_BVH_H
 #define R1_BVH_H
 
@@ -7,6 +8,7 @@
 #include <vector>
 
 #include "r1_bvh_fill.h"
+#include "r1_bvh_sort.h"
 #include "../../include/rays1.h"
 
 struct R1Bvh
@@ -14,6 +16,7 @@ struct R1Bvh
     std::vector<float> nodes;   // 16 floats per node, see R1DeviceScene::bvh_nodes
     std::vector<float> prims;   // leaf order, 8 floats per PAIR of spheres: {cx_a cx_b cy_a cy_b cz_a cz_b rsq_a rsq_b}
     std::vector<uint32_t> ids;  // 2 per pair: active index, 0xFFFFFFFF for the partner of an odd sphere
+    std::vector<uint8_t> pair_pinned; // 1 per pair: the pair's leaf was made by the builder's outlier peel, a re-sort leaves its spheres where they are
     int max_depth = 0;          // inner nodes on the longest root-to-leaf path
     uint32_t n_leaves = 0;
     float centre[3] = {0, 0, 0}; // C of the pad formula (r1_bvh.cpp's header)
@@ -35,6 +38,17 @@ struct R1RefitTopo
     std::vector<uint32_t> height_off; // [heights + 1] by_height[height_off[h] .. height_off[h + 1]) are the nodes of height h
 };
 
+// What a re-sort needs besides the tree and the refit's tables (r1_bvh_sort.h): topology too.  Positions 0 .. M are the movable
+// slots in ascending slot order; a splitting node is an inner node whose two children both hold movable slots.
+struct R1SortTopo
+{
+    std::vector<uint32_t> mov;       // [M] the movable spheres, ascending active index (a re-sort permutes them among the movable slots)
+    std::vector<uint32_t> mslot;     // [M] position p's slot in ids / prims
+    std::vector<R1SortSeg> seg;      // the splitting nodes, depth by depth (depths without one are left out), ascending b within a depth
+    std::vector<uint32_t> depth_off; // [depths + 1] seg[depth_off[d] .. depth_off[d + 1]) are depth d's
+    std::vector<uint32_t> pos_seg;   // [depths][M] the index in `seg` of depth d's node that holds position p, or R1S_NONE
+};
+
 void r1_build_bvh(uint32_t na, const float *cx, const float *cy, const float *cz, const float *rsq, const double *rbound, int leaf_max, R1Bvh &out);
 int r1_active_spheres(const r1_scene *s, std::vector<uint32_t> &active_to_scene); // inv_radius != 0, finite
 double r1_bound_radius(float radius_sq, float inv_radius);
@@ -42,6 +56,10 @@ double r1_test_radius(double rbound, float radius_sq); // the radius whose error
 void r1_bvh_topology(const R1Bvh &b, uint32_t na, R1RefitTopo &t);
 // The device refit's steps on the host, in its order and with its tables: new node rows for centres cx, cy, cz (active order; non-finite:
 // the sphere is in no box).  A tree of 0 spheres is left alone.
+void r1_bvh_sort_topology(const R1Bvh &b, R1SortTopo &s);
+// The device re-sort's steps on the host, over its tables: the movable spheres re-dealt into the movable slots by r1_bvh_sort.h's rule for
+// centres cx, cy, cz (active order); rewrites b.ids, b.prims (centre and rsq of the moved spheres) and t.slot.  The refit is the caller's.
+void r1_bvh_resort_host(R1Bvh &b, R1RefitTopo &t, const R1SortTopo &s, const float *cx, const float *cy, const float *cz, const float *rsq);
 void r1_bvh_refit_host(R1Bvh &b, const R1RefitTopo &t, uint32_t na, const float *cx, const float *cy, const float *cz, const float *rsq,
                        const double *rbound);
 

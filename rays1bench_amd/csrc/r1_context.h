@@ -164,6 +164,12 @@ struct r1_context
     R1RefitArgs refit;         // pointers into the tables above and the scene's
     std::vector<uint32_t> refit_height_off; // R1RefitTopo::height_off
     std::vector<uint32_t> scene_to_active;  // 0xFFFFFFFF: not active
+    // re-sort (r1_resort_spheres): its topology tables, uploaded with the refit's, and its scratch, kept from call to call
+    DevBuf sort_tab;           // uint32: R1SortTopo's mov, mslot, seg (3 words each), pos_seg
+    DevBuf sort_ws;            // uint32: two list buffers and two key buffers of 3 M, the scan's 3 M, the flags, the nodes' axes, the histogram, the block sums
+    R1SortArgs sort;           // pointers into the two above and the scene's; m == 0: nothing is movable
+    std::vector<uint32_t> sort_depth_off; // R1SortTopo::depth_off
+    uint32_t n_bvh_ids = 0;    // leaf slots of the tree (2 per pair), without the sentinel words behind them
     bool moved = false;        // an update since the last r1_set_scene: the sphere groups and the grid are stale, src_f32 may be
     bool src_stale = false;    // r1_update_spheres_device since the last r1_set_scene: the host copies (src_f32, src_mat) never saw its values
     float *stage = nullptr, *stage_dev = nullptr; // host form: page-locked staging of the caller's arrays, read by the move and the set kernel

@@ -13,6 +13,7 @@
 
 struct R1RefitArgs; // r1_bvh_fill.h
 struct R1SetArgs;
+struct R1SortArgs; // r1_bvh_sort.h
 
 // what r1_sweep_describe says of the sweep's tables besides the arrays
 struct r1_sweep_info
@@ -79,6 +80,10 @@ hipError_t r1_trace_rays_occupancy(int variant, int big, size_t dyn_lds, int *bl
 hipError_t r1_launch_refit_move(const R1RefitArgs *a, uint32_t first, uint32_t count, const float *x, const float *y, const float *z, hipStream_t stream);
 hipError_t r1_launch_refit_set(const R1RefitArgs *a, const R1SetArgs *s, uint32_t first, uint32_t count, uint32_t groups, hipStream_t stream); // r1_update_spheres* (§4.27)
 hipError_t r1_launch_refit(const R1RefitArgs *a, const uint32_t *height_off, uint32_t heights, hipStream_t stream);
+
+// r1_resort.hip: the kernels of r1_resort_spheres
+hipError_t r1_launch_resort(const R1SortArgs *a, const uint32_t *depth_off, uint32_t depths, hipStream_t stream);
+size_t r1_sort_sums_words(size_t n); // words of block sums its prefix sum over n items needs
 }
 
 #endif

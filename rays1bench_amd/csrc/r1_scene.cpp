@@ -1,5 +1,6 @@
 // r1_scene.cpp — what a context knows of its scene: r1_set_scene (active spheres, the sweep's tables, the box tree, the refit's tables;
-// uploads through the context's own stream), the camera alone, moving spheres, and the uniform grid built on first use.
+// uploads through the context's own stream), the camera alone, moving spheres, sphere updates, the re-sort, and the uniform grid built on
+// first use.
 
 #include <math.h>
 #include <string.h>
@@ -97,6 +98,10 @@ extern "C" int r1_set_scene(r1_context *c, const r1_scene *s, const r1_camera *c
             return R1_ELIMIT;
         }
     }
+    // what a re-sort needs besides (r1_resort_spheres): which slots are movable and the splitting nodes' segments, computed before the sentinels
+    R1SortTopo stopo;
+    r1_bvh_sort_topology(bvh, stopo);
+    const uint32_t n_ids = (uint32_t)bvh.ids.size();
     // leaf_quad fetches a sphere index speculatively for lanes that hold no flagged sphere (slot 3 of the step, whatever the step's
     // pair count): two sentinel words behind the last pair keep that read inside the table
     bvh.ids.resize(bvh.ids.size() + 2, 0xFFFFFFFFu);
@@ -125,6 +130,19 @@ extern "C" int r1_set_scene(r1_context *c, const r1_scene *s, const r1_camera *c
         for (int k = 0; k < 5; ++k)
             roff[k] = rtab.size(), rtab.insert(rtab.end(), parts[k]->begin(), parts[k]->end());
     }
+    std::vector<uint32_t> stab;
+    size_t soff[4];
+    {
+        const size_t m = stopo.mov.size();
+        soff[0] = 0, soff[1] = m, soff[2] = 2 * m, soff[3] = 2 * m + 3 * stopo.seg.size();
+        stab.resize(soff[3] + stopo.pos_seg.size());
+        if (m)
+            memcpy(&stab[soff[0]], stopo.mov.data(), m * 4), memcpy(&stab[soff[1]], stopo.mslot.data(), m * 4);
+        if (!stopo.seg.empty())
+            memcpy(&stab[soff[2]], stopo.seg.data(), stopo.seg.size() * sizeof(R1SortSeg));
+        if (!stopo.pos_seg.empty())
+            memcpy(&stab[soff[3]], stopo.pos_seg.data(), stopo.pos_seg.size() * 4);
+    }
     std::vector<double> radii(2 * (size_t)(na ? na : 1), 0.0);
     for (uint32_t a = 0; a < na; ++a)
         radii[2 * (size_t)a + 0] = sw.rbound[a], radii[2 * (size_t)a + 1] = r1_test_radius(sw.rbound[a], sw.exact[4 * (size_t)a + 3]);
@@ -152,6 +170,7 @@ extern "C" int r1_set_scene(r1_context *c, const r1_scene *s, const r1_camera *c
         {c->active_dev, c->active_to_scene.data(), (size_t)na * 4}, // ray queries report SCENE indices: the active spheres' scene indices
         {c->refit_tab, rtab.data(), rtab.size() * 4},
         {c->refit_radii, radii.data(), radii.size() * 8},
+        {c->sort_tab, stab.data(), stab.size() * 4},
     };
     int rc;
     for (const auto &u : uploads)
@@ -174,6 +193,15 @@ extern "C" int r1_set_scene(r1_context *c, const r1_scene *s, const r1_camera *c
         r.n_nodes = (uint32_t)(bvh.nodes.size() / 16), r.n_leaves = (uint32_t)topo.leaf_ref.size();
         r.fill = bvh.fill;
         c->refit_height_off = topo.height_off;
+        // the re-sort's tables; its scratch is laid out at the first r1_resort_spheres of the scene (sort.list[0] == null until then)
+        R1SortArgs &q = c->sort;
+        const uint32_t *st = (const uint32_t *)c->sort_tab.p;
+        memset(&q, 0, sizeof(q));
+        q.exact = r.exact, q.prims = r.prims, q.ids = (uint32_t *)c->bvh_ids.p, q.slot = (uint32_t *)c->refit_tab.p + roff[1];
+        q.mov = st + soff[0], q.mslot = st + soff[1], q.seg = (const R1SortSeg *)(st + soff[2]), q.pos_seg = st + soff[3];
+        q.m = (uint32_t)stopo.mov.size();
+        c->sort_depth_off = stopo.depth_off;
+        c->n_bvh_ids = n_ids;
     }
     c->moved = false, c->src_stale = false;
     c->n_bvh_nodes = (uint32_t)(bvh.nodes.size() / 16);
@@ -480,6 +508,82 @@ extern "C" int r1_update_spheres_device(r1_context *c, uint32_t first, uint32_t 
     if ((rc = spheres_enqueue(c, first, count, u, groups, hip_stream ? (hipStream_t)hip_stream : c->stream, nullptr)))
         return rc;
     c->src_stale = true; // the host cannot see the values: r1_set_scene rebuilds whatever it is given
+    return R1_OK;
+}
+
+// ---- re-sort: the spheres re-dealt into the tree's leaves (include/rays1.h "re-sort", r1_resort.hip) ----------------------
+
+// the scratch of the scene's re-sorts, laid out once per scene in an allocation that only grows
+static int resort_scratch(r1_context *c)
+{
+    R1SortArgs &q = c->sort;
+    if (q.list[0])
+        return R1_OK;
+    const size_t m = q.m, na = c->n_active ? c->n_active : 1, n_seg = c->sort_depth_off.back();
+    const size_t hist = 3 * 256 * ((m + 255) / 256);
+    const size_t sums = std::max(r1_sort_sums_words(3 * m), r1_sort_sums_words(hist));
+    const size_t words = 5 * 3 * m + na + (n_seg ? n_seg : 1) + hist + (sums ? sums : 1);
+    int rc = ensure(c->sort_ws, words * 4);
+    if (rc)
+        return rc;
+    uint32_t *w = (uint32_t *)c->sort_ws.p;
+    q.list[1] = w + 3 * m, q.key[0] = w + 6 * m, q.key[1] = w + 9 * m, q.scan = w + 12 * m;
+    q.flag = w + 15 * m, q.seg_axis = q.flag + na, q.hist = q.seg_axis + (n_seg ? n_seg : 1), q.sums = q.hist + hist;
+    q.list[0] = w;
+    return R1_OK;
+}
+
+extern "C" int r1_resort_spheres(r1_context *c, void *hip_stream)
+{
+    if (!c)
+    {
+        r1_set_error("r1_resort_spheres: ctx is NULL");
+        return R1_EINVAL;
+    }
+    if (!c->have_scene)
+    {
+        r1_set_error("r1_resort_spheres: no scene set (call r1_set_scene first)");
+        return R1_EINVAL;
+    }
+    if (c->sort.m == 0) // nothing is movable: nothing changes, the context's state included
+        return R1_OK;
+    R1_HIP(hipSetDevice(c->device));
+    int rc = resort_scratch(c);
+    if (rc)
+        return rc;
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    R1_HIP(r1_launch_resort(&c->sort, c->sort_depth_off.data(), (uint32_t)c->sort_depth_off.size() - 1u, st));
+    R1_HIP(r1_launch_refit(&c->refit, c->refit_height_off.data(), (uint32_t)c->refit_height_off.size() - 1u, st));
+    // the context's state: that of an update (update_enqueue)
+    c->moved = true;
+    c->grid_valid = false;
+    c->pass_valid = false;
+    c->bvh_flat_m = 0.0f, c->bvh_flat_e = -1.0f;
+    return R1_OK;
+}
+
+extern "C" int r1_bvh_ids_download(r1_context *c, uint32_t *ids_out, size_t ids_cap, size_t *n)
+{
+    if (!c || !n)
+    {
+        r1_set_error("r1_bvh_ids_download: %s is NULL", !c ? "ctx" : "n");
+        return R1_EINVAL;
+    }
+    if (!c->have_scene)
+    {
+        r1_set_error("r1_bvh_ids_download: no scene set (call r1_set_scene first)");
+        return R1_EINVAL;
+    }
+    *n = c->n_bvh_ids;
+    if (!ids_out)
+        return R1_OK;
+    if (ids_cap < c->n_bvh_ids)
+        return R1_ELIMIT;
+    R1_HIP(hipSetDevice(c->device));
+    R1_HIP(hipMemcpyAsync(ids_out, c->bvh_ids.p, 4 * (size_t)c->n_bvh_ids, hipMemcpyDeviceToHost, c->stream));
+    R1_HIP(hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < c->n_bvh_ids; ++i) // active index -> index into the caller's scene arrays, as r1_bvh_describe gives them
+        ids_out[i] = ids_out[i] < c->n_active ? c->active_to_scene[ids_out[i]] : 0xFFFFFFFFu;
     return R1_OK;
 }
 

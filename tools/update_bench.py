@@ -16,9 +16,15 @@ On config 5's scene again, sphere updates (none of these is a pass / fail thresh
   (f) the frame time after a radii update that scales the lattice radii by 0.5, 1 and 2 against a fresh build of that scene (the refitted
       tree keeps the topology of the original radii), the two frames compared byte for byte on the way, with the node visits and leaf
       trips of both trees from the diagnostic build.
+The re-sort (r1_resort_spheres, §4.29; none of these is a pass / fail threshold either):
+  (g.1) the time of one re-sort (enqueue to stream idle) on config 5's scene and on the large scene, beside one update of all centres and one
+        r1_set_scene;
+  (g.2) on config 5's scene, the frame after the refit alone, after the re-sort and after a fresh build of the same moved scene, for
+        displacements of 0, 0.25, 1 and 4 spacings and for the lattice's centres permuted among its spheres — three contexts, alternating in
+        one session, pixels and rays compared in every triple; and from it the displacement from which a re-sort pays for itself.
 Frames are r1_render_async into page-locked memory, timed from the enqueue to the stream idle by the host's clock.
-Writes its report to profiles/r20/update.txt (--out FILE: somewhere else).
-usage: tools/update_bench.py [--rounds N] [--frames N] [--out FILE]"""
+Writes its report to profiles/r20/update.txt (--out FILE: somewhere else) and section (g)'s to profiles/r22/resort.txt (--resort-out FILE).
+usage: tools/update_bench.py [--rounds N] [--frames N] [--out FILE] [--section all|a-f|g] [--resort-out FILE]"""
 import argparse
 import ctypes as C
 import os
@@ -36,6 +42,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--frames", type=int, default=8, help="frames per timing of (b) and (c)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r20", "update.txt"), help="where the report is written")
+    ap.add_argument("--section", choices=("all", "a-f", "g"), default="all", help="g: the re-sort's section alone")
+    ap.add_argument("--resort-out", default=os.path.join(ROOT, "profiles", "r22", "resort.txt"), help="where section (g)'s report is written")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -85,6 +93,94 @@ def main():
             ctx.sync()
         go()  # workspaces
         return [ms(go) for _ in range(n)]
+
+    def section_g():
+        """the re-sort; its own report"""
+        del lines[:]
+        sc = r1.create_grid_scene(w, h, 400, 250)
+        a = sc.arrays()
+        lat = lattice_of(a)
+        spacing = float(np.ptp(a["center_x"][lat])) / 399.0
+        rng = np.random.default_rng(5)
+        ang = rng.uniform(0, 2 * np.pi, len(lat))
+
+        def displaced(d):
+            x, y, z = (a[k].copy() for k in ("center_x", "center_y", "center_z"))
+            if d == "permuted":
+                q = lat[np.random.default_rng(7).permutation(len(lat))]
+                x[lat], y[lat], z[lat] = x[q], y[q], z[q]
+                return x, y, z
+            x[lat] = (x[lat] + d * spacing * np.cos(ang)).astype(np.float32)
+            z[lat] = (z[lat] + d * spacing * np.sin(ang)).astype(np.float32)
+            return x, y, z
+
+        say(f"(g.1) one re-sort against one update of all centres and one r1_set_scene ({args.rounds} rounds, alternating; enqueue to stream idle, host clock)")
+        resort_ms = {}
+        for title, scene in (("config 5's scene", sc), ("the large scene", r1.create_large_scene(w, h))):
+            b = scene.arrays()
+            ctx = r1.Renderer(0)
+            ctx.set_scene(scene)
+            t_sort, t_upd, t_set = [], [], []
+            for r in range(args.rounds + 1):
+                bx = (b["center_x"] + np.float32(0.01 * (r % 2))).astype(np.float32)
+                cs, keep = raw_from_arrays(b, bx, b["center_y"], b["center_z"])
+
+                def update():
+                    ctx.update_centers(0, bx, b["center_y"], b["center_z"])
+                    ctx.sync()
+
+                def resort():
+                    ctx.resort_spheres()
+                    ctx.sync()
+
+                tu, tr, ts = ms(update), ms(resort), ms(lambda: ctx.set_scene_raw(cs, scene.camera.contents))
+                if r:  # (round 0: scratch, staging buffer, first launches)
+                    t_sort.append(tr), t_upd.append(tu), t_set.append(ts)
+            info = binding.bvh_describe(scene.spheres.contents)[0]
+            say(f"  {title}: {scene.count} spheres, {len(lattice_of(b))} movable, tree of {info['nodes']} nodes, depth {info['depth']}")
+            say(f"    r1_resort_spheres  {spread(t_sort)}")
+            say(f"    r1_update_centers  {spread(t_upd)}")
+            say(f"    r1_set_scene       {spread(t_set)}")
+            say(f"    r1_set_scene / re-sort {statistics.median(t_set) / statistics.median(t_sort):.1f} x")
+            resort_ms[title] = statistics.median(t_sort)
+            ctx.close()
+        say()
+        say(f"(g.2) config 5's scene, {w} x {h} x {spp}: the frame after the refit alone, after the re-sort, after a fresh build of the same moved scene "
+            f"({args.frames} frames per timing, {args.rounds} rounds, alternating; permuted: 1 frame per timing, 2 rounds)")
+        refit, sorted_, fresh = r1.Renderer(0), r1.Renderer(0), r1.Renderer(0)
+        cost = resort_ms["config 5's scene"]
+        for d in (0.0, 0.25, 1.0, 4.0, "permuted"):
+            x, y, z = displaced(d)
+            cs, keep = raw_from_arrays(a, x, y, z)
+            for c in (refit, sorted_):
+                c.set_scene(sc)
+                c.update_centers(0, x, y, z)
+            sorted_.resort_spheres()
+            fresh.set_scene_raw(cs, sc.camera.contents)
+            frames, rounds = (1, 2) if d == "permuted" else (args.frames, args.rounds)
+            t = {"refit": [], "sorted": [], "fresh": []}
+            same = True
+            for r in range(rounds):
+                out = []
+                for name, c in (("refit", refit), ("sorted", sorted_), ("fresh", fresh)):
+                    t[name] += frame_ms(c, frames)
+                    out.append((hf.image(0).tobytes(), hf.rays(0)))
+                same = same and out[0] == out[1] == out[2]
+            m = {k: statistics.median(v) for k, v in t.items()}
+            label = "lattice permuted         " if d == "permuted" else f"displacement {d:4.2f} spacings"
+            gain = m["refit"] - m["sorted"]
+            pays = f"pays for itself after {cost / gain:.1f} frames" if gain > 0 else "does not pay"
+            say(f"  {label}: refit alone {m['refit']:9.3f} ms, re-sorted {m['sorted']:8.3f} ms, fresh build {m['fresh']:8.3f} ms; refit / fresh {m['refit'] / m['fresh']:7.2f}, "
+                f"re-sorted / fresh {m['sorted'] / m['fresh']:5.2f}; a re-sort ({cost:.3f} ms) {pays}; pixels and rays {'equal' if same else 'DIFFER'}")
+        refit.close(), sorted_.close(), fresh.close()
+        os.makedirs(os.path.dirname(os.path.abspath(args.resort_out)), exist_ok=True)
+        with open(args.resort_out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+    if args.section == "g":
+        section_g()
+        hf.close()
+        return
 
     # ---- config 5's scene ----
     sc = r1.create_grid_scene(w, h, 400, 250)
@@ -251,10 +347,12 @@ def main():
         say(f"      node visits per frame: refitted {visits[0][0]}, fresh {visits[1][0]} ({visits[0][0] / visits[1][0]:.2f}); "
             f"leaf trips x lanes: refitted {visits[0][1]}, fresh {visits[1][1]} ({visits[0][1] / visits[1][1]:.2f})")
     ctx.close(), other.close()
-    hf.close()
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         f.write("\n".join(lines) + "\n")
+    if args.section == "all":
+        section_g()
+    hf.close()
 
 
 if __name__ == "__main__":
