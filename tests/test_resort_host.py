@@ -39,7 +39,10 @@ def built(name):
 def pinned_slots(a, info, nodes, ids):
     """The slots a re-sort must leave alone on the project's scenes: the builder peels the ground and the three big balls — every active sphere
     outside lattice_of() — into ONE leaf under the root (info.root_leaf says which child), and the lattice of near-equal radii offers no
-    further outlier.  Returned: sorted slot indices; checked: that leaf holds exactly those spheres."""
+    further outlier.  That holds for these scenes, not for the builder: it peels per node, against that node's own median radius, so a peel
+    can recur below the root (tests/resort_scenes.py tiers("low"): a cluster of r = 0.1 with two r = 1.0 spheres beside a cluster of r = 1.0
+    pins a second leaf at depth 3); resort_scenes.peeled_leaves restates the rule for any tree and tests/test_resort_scenes_host.py holds
+    the re-sort to it.  Returned: sorted slot indices; checked: that leaf holds exactly those spheres."""
     if not info["root_leaf"]:
         return []
     ref = int(nodes[0].view(np.uint32)[REF[info["root_leaf"] - 1]])
