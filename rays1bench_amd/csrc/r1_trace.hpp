@@ -223,6 +223,25 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
     constexpr bool SPARE = !BIG && (VARIANT == R1_V_TREE || VARIANT == R1_V_SWEEP || VARIANT == R1_V_GRID) && r1_mode_is_tp_family(MODE); // (big scenes: the registers buy an eighth wave instead)
     Path spare = p;
     bool has_spare = false;
+    // The bookkeeping around the loop's arithmetic, trimmed in the builds that both land their tiles and keep a spare: the
+    // frames-in-flight tree kernels <4,false,false,TP / BATCH / PATH>.  Every other build keeps its code to the instruction.
+    constexpr bool TRIM = LAND && SPARE;
+#ifndef R1_TRIM_VOTES
+#define R1_TRIM_VOTES 1 // the wave votes (0: as in every other build; `make tuning EXTRA=-DR1_TRIM_VOTES=0` measures the step alone)
+#endif
+#ifndef R1_TRIM_WALK
+#define R1_TRIM_WALK 1 // the walk's state at the end of a sample and at the hand-over of the spare
+#endif
+    constexpr bool TRIM_VOTES = TRIM && R1_TRIM_VOTES, TRIM_WALK = TRIM && R1_TRIM_WALK;
+    // Votes.  __ballot turns a condition the compiler holds as a lane mask into v_cndmask 0,1 + v_cmp_ne, and so does the ballot builtin on a
+    // bool that is carried around the loop; on a comparison it is the one v_cmp that writes the mask.  The trimmed builds vote on comparisons
+    // of per-lane words, and combine the masks on the scalar pipe.
+    // Between the end of one iteration and the next one's walk a lane of a tree kernel is dead exactly when its walk is marked complete: a lane
+    // that ends its sample leaves tv.cur at R1_BVH_DONE (it was `ready`), trav_start and a carried walk leave it elsewhere.  The trimmed builds
+    // read `alive` from that word there, so that no lane mask lives across the refill loop (the mask and its complement were parked in four
+    // lanes of the spill register in every iteration, and fetched back).
+#define R1_DEAD (TRIM_VOTES ? tv.cur == R1_BVH_DONE : !alive)
+#define R1_VOTE(c) (TRIM_VOTES ? (unsigned long long)__builtin_amdgcn_ballot_w64(c) : (unsigned long long)__ballot(c))
 
     // wave-uniform queue state.  Chunks shrink as the queue drains (guided self-scheduling):
     // a wave asks for ~1/(2*waves) of what it last saw remaining, between R1_CHUNK_MIN and
@@ -259,18 +278,23 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
             if (VARIANT == R1_V_TREE)
                 trav_start(tv);
         }
-        if (SPARE && !alive && has_spare)
+        if (SPARE && R1_DEAD && has_spare)
         {
             p.o = spare.o, p.d = spare.d, p.s_scalar = spare.s_scalar, p.s0 = spare.s0, p.s1 = spare.s1, p.s2 = spare.s2, p.k = spare.k;
             p.depth = 0, p.sp = 0;
             alive = true, has_spare = false;
-            trav_start(tv);
+            if (TRIM_WALK)
+                tv.cur = 0u; // (the rest of trav_start is in place since the lane's last sample ended, see below)
+            else
+                trav_start(tv);
         }
-        unsigned long long need = __ballot(!alive);
+        unsigned long long need = R1_VOTE(R1_DEAD);
         if (SPARE)
         {
-            const unsigned long long lack = __ballot(!has_spare);
-            need = (need != 0ull || (uint32_t)__popcll(lack) >= R1_SPARE_MIN) ? lack : 0ull;
+            const unsigned long long lack = R1_VOTE(!has_spare);
+            // (the trimmed builds count the halves: the 64-bit count is compared as a 64-bit number, for which the scalar pipe has no instruction)
+            const uint32_t n_lack = TRIM_VOTES ? (uint32_t)__builtin_popcount((uint32_t)lack) + (uint32_t)__builtin_popcount((uint32_t)(lack >> 32)) : (uint32_t)__popcll(lack);
+            need = (need != 0ull || n_lack >= R1_SPARE_MIN) ? lack : 0ull;
         }
         while (need)
         {
@@ -394,14 +418,17 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
                     trav_start(tv);
             }
             q_next += min((uint32_t)__popcll(need), avail);
-            need = SPARE ? __ballot(!has_spare) : __ballot(!alive);
+            need = SPARE ? R1_VOTE(!has_spare) : R1_VOTE(!alive);
         }
-        if (SPARE && !alive && has_spare) // the lanes that had died without a spare start on the one they just got
+        if (SPARE && R1_DEAD && has_spare) // the lanes that had died without a spare start on the one they just got
         {
             p.o = spare.o, p.d = spare.d, p.s_scalar = spare.s_scalar, p.s0 = spare.s0, p.s1 = spare.s1, p.s2 = spare.s2, p.k = spare.k;
             p.depth = 0, p.sp = 0;
             alive = true, has_spare = false;
-            trav_start(tv);
+            if (TRIM_WALK)
+                tv.cur = 0u;
+            else
+                trav_start(tv);
         }
         if (BIG && VARIANT == R1_V_SWEEP)
         {
@@ -409,11 +436,30 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
             if (!__syncthreads_or(alive ? 1 : 0))
                 break;
         }
-        else if (__ballot(alive) == 0ull)
+        else if (!TRIM_VOTES && __ballot(alive) == 0ull)
+            break;
+        // (the trimmed builds take the vote on `alive` once for the exit test, the priority votes and the walk, and vote on the depth word
+        //  alone — one v_cmp each — masking with it on the scalar pipe; a dead lane's stale depth is masked off)
+        if (TRIM_VOTES)
+            alive = !R1_DEAD;
+        const unsigned long long live_once = TRIM_VOTES ? (unsigned long long)__builtin_amdgcn_ballot_w64(!R1_DEAD) : 0ull;
+        if (TRIM_VOTES && live_once == 0ull)
             break;
         // A frame's critical path is its longest bounce chain (up to 51 dependent sweeps, ~1/3 of
         // a 10-spp frame when the wave shares its SIMD with three others).  Waves that carry a
         // deep path ask for issue priority so that the chain finishes before the queue runs dry.
+        if (TRIM_VOTES)
+        {
+            if ((__builtin_amdgcn_ballot_w64(p.depth >= 12) & live_once) == 0ull)
+                __builtin_amdgcn_s_setprio(0);
+            else if ((__builtin_amdgcn_ballot_w64(p.depth >= 36) & live_once) != 0ull)
+                __builtin_amdgcn_s_setprio(3);
+            else if ((__builtin_amdgcn_ballot_w64(p.depth >= 24) & live_once) != 0ull)
+                __builtin_amdgcn_s_setprio(2);
+            else
+                __builtin_amdgcn_s_setprio(1);
+        }
+        else
         {
             // (one vote first: in most iterations no lane is 12 deep, and the two deeper votes are taken only behind it)
             if (__ballot(alive && p.depth >= 12) == 0ull)
@@ -437,7 +483,7 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
         float t_hit = FLT_MAX;
         int hit = -1;
         bool ready = alive; // lanes whose hit test is complete after this step (tree kernels: the others carry their walk over)
-        const unsigned long long live_now = __ballot(alive);
+        const unsigned long long live_now = TRIM_VOTES ? live_once : __ballot(alive);
         if (LAT && !BIG && VARIANT != R1_V_REFERENCE && exhausted && (uint32_t)__popcll(live_now) <= A.coop_lanes)
         {
             cooperative_sweep(A.scene, live_now, p.o, p.d, t_hit, hit, lane); // the frame's tail: few paths left in this wave
@@ -521,8 +567,17 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
                     lane_rays += path_rays(p); // (LAND: the waves that sum the tiles add up the records' counts)
                 alive = false, fin = true;
             }
-            else if (VARIANT == R1_V_TREE)
+            else if (VARIANT == R1_V_TREE && !TRIM_WALK)
                 trav_start(tv); // the scattered ray starts its walk at the root
+            // (the trimmed builds reset the walk of every ready lane, ended samples included, and mark those complete again: the same
+            //  constants for all of them — the other form kept the ended lanes' old offer alive through three register copies and three
+            //  more where the branches join — and a hand-over only has to open the walk)
+            if (TRIM_WALK)
+            {
+                trav_start(tv);
+                if (fin)
+                    tv.cur = R1_BVH_DONE;
+            }
         }
         if (LAND && fin)
             land_count(SA, row, p.k);
@@ -582,6 +637,8 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
     if (LAND)
         land_exit<(BIG && VARIANT == R1_V_TREE) ? 6 : R1_LAND_LOADS>(A, row, lane); // (the big-scene tree kernels are built for 64 registers)
 #undef row
+#undef R1_VOTE
+#undef R1_DEAD
     // ray count: wave reduction, one atomic per wave (rayweek1.cpp:809-813)
     if (!LAND)
     {
