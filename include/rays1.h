@@ -236,7 +236,8 @@ typedef struct r1_sphere_update
  *   centres    r1_update_centers' rules (a non-finite new centre of an active sphere: R1_EINVAL).
  *   radii      the device rewrites the radius in every table the box-tree kernels and the shading read and REFITS the tree (with the centres,
  *              if both are given: one refit).  The context is then in the state of a centre update: the flat y slab is dropped, PREFILTER,
- *              STATS, WAVEFRONT, GRID, GRID_STATS and a GRID cast return R1_EINVAL ("the scene has moved") until the next r1_set_scene.  An
+ *              STATS, WAVEFRONT, GRID, GRID_STATS and a GRID cast return R1_EINVAL ("the scene has moved") until the next r1_set_scene (the
+ *              grid: or until r1_regrid, below).  An
  *              active sphere whose new pair would make it inactive (inv_radius 0 or NaN, radius_sq not finite) is R1_EINVAL; a negative
  *              inv_radius and pairs that disagree are accepted as r1_set_scene accepts them.
  *   materials  the device rewrites the sphere's albedo and material row.  Nothing else changes: no refit, every variant and the grid stay
@@ -774,6 +775,43 @@ int r1_grid_describe(const r1_scene *scene, r1_grid_info *info, uint32_t *start_
  * returns).  Builds the grid on every call.  No GPU needed. */
 int r1_grid_visit(const r1_scene *scene, const float o[3], const float d[3], uint32_t *presented, size_t cap, size_t *n_presented,
                   int32_t *hit_index, float *hit_t, int32_t *fallback);
+
+/* ---- regrid: moved spheres re-registered in the uniform grid ---- */
+
+/* Every update and r1_resort_spheres leave the uniform grid stale: GRID, GRID_STATS and a GRID query return R1_EINVAL ("the scene has
+ * moved").  This call re-registers the spheres the device holds in the grid, on the device, by the rule "geometry kept": the PLAN of the
+ * grid built for the arrays of r1_set_scene stays — which axes are flat, the cells of the others, V, the margins, the outlier radius — and
+ * every sphere is an outlier (its radius, its ball outside the plan's box, or too many cells) or registered in the cells its ball overlaps;
+ * a flat axis's one cell is re-stretched over the spheres.  Enqueued on `hip_stream` (NULL: the context's stream); nothing is read back.
+ * Afterwards renders and queries through GRID and GRID_STATS are accepted again and bit-identical — pixels, ray counts, records — to a
+ * fresh context after r1_set_scene with the context's current spheres, until the next update or re-sort; PREFILTER, STATS and WAVEFRONT
+ * stay refused.  It is not an update: the flat slab, a progressive accumulation, r1_last_launch_info / r1_last_timing stay as they are;
+ * "one update at a time per context" holds for it.  A pure function of the plan and the device's rows: a second call changes no byte.
+ * The id table has a fixed capacity, twice the plan's registrations + 64 (from the first regrid of a scene on; a scene whose 16-bit
+ * tables no longer fit the small kernel's LDS then runs the big-scene kernel).  Spheres that would register beyond it leave the grid
+ * in OVERFLOW: every ray takes the tree fallback — still exact, only slow — until a later regrid fits; r1_grid_download reports it.
+ * R1_EINVAL before the first r1_set_scene.  On a scene that has not moved it builds the grid as the first GRID render would, then
+ * re-registers.  On a moved scene whose grid was never built: R1_EINVAL — call r1_regrid once, or render once through the grid, before
+ * the first update (the plan can only come from the arrays r1_set_scene received).  There is no r1_multi form. */
+int r1_regrid(r1_context *ctx, void *hip_stream);
+
+/* Diagnostic, synchronous: the grid as the device holds it, after waiting for the device; `info` and the optional outputs as
+ * r1_grid_describe fills them (build_ms 0).  Overflow is reported as info->registrations = -1 (every start is then 0, no ids).
+ * R1_EINVAL while the context holds no current grid (never built, or stale); R1_ELIMIT if a given capacity is too small. */
+int r1_grid_download(r1_context *ctx, r1_grid_info *info, uint32_t *start_out, size_t start_cap, uint32_t *ids_out, size_t ids_cap,
+                     uint32_t *outliers_out, size_t outliers_cap);
+
+/* The CPU-side pin of r1_regrid (no GPU): the plan of the grid of `built`, then the device's steps over the scene-indexed centres and
+ * radii (as r1_bvh_refit_describe_spheres takes them; radius_sq and inv_radius both NULL: the built scene's) through the same functions
+ * (csrc/r1_grid_fill.h).  Outputs as r1_grid_describe; overflow as r1_grid_download reports it. */
+int r1_grid_regrid_describe(const r1_scene *built, const float *x, const float *y, const float *z, const float *radius_sq,
+                            const float *inv_radius, r1_grid_info *info, uint32_t *start_out, size_t start_cap, uint32_t *ids_out,
+                            size_t ids_cap, uint32_t *outliers_out, size_t outliers_cap);
+
+/* r1_grid_visit through the tables r1_grid_regrid_describe returns, against the moved spheres. */
+int r1_grid_regrid_visit(const r1_scene *built, const float *x, const float *y, const float *z, const float *radius_sq,
+                         const float *inv_radius, const float o[3], const float d[3], uint32_t *presented, size_t cap, size_t *n_presented,
+                         int32_t *hit_index, float *hit_t, int32_t *fallback);
 
 enum
 {

@@ -216,6 +216,13 @@ SYMBOLS = [
     ("r1_grid_describe", C.c_int, [C.POINTER(CScene), C.POINTER(GridInfo), C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t,
                                    C.POINTER(C.c_uint32), C.c_size_t]),
     ("r1_grid_visit", C.c_int, [C.POINTER(CScene), _f32p, _f32p, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_size_t), _i32p, _f32p, _i32p]),
+    ("r1_regrid", C.c_int, [_ctx, C.c_void_p]),
+    ("r1_grid_download", C.c_int, [_ctx, C.POINTER(GridInfo), C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t,
+                                   C.POINTER(C.c_uint32), C.c_size_t]),
+    ("r1_grid_regrid_describe", C.c_int, [C.POINTER(CScene), _f32p, _f32p, _f32p, _f32p, _f32p, C.POINTER(GridInfo), C.POINTER(C.c_uint32), C.c_size_t,
+                                          C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t]),
+    ("r1_grid_regrid_visit", C.c_int, [C.POINTER(CScene), _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, C.POINTER(C.c_uint32), C.c_size_t,
+                                       C.POINTER(C.c_size_t), _i32p, _f32p, _i32p]),
     ("r1_cast_rays", C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("r1_cast_rays_device", C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     ("r1_cast_rays_host", C.c_int, [C.POINTER(CScene), C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -463,6 +470,16 @@ class Renderer:
         """r1_resort_spheres: the spheres re-dealt into the box tree's leaves on the device, then the refit; the topology stays.  Enqueues on
         `stream` (a stream pointer; None: the context's stream) and waits for nothing."""
         _check(lib().r1_resort_spheres(self._c, _stream_arg(stream)))
+
+    def regrid(self, stream=None):
+        """r1_regrid: the spheres the device holds re-registered in the uniform grid on the device; GRID renders and queries are accepted
+        again.  Enqueues on `stream` (a stream pointer; None: the context's stream) and waits for nothing."""
+        _check(lib().r1_regrid(self._c, _stream_arg(stream)))
+
+    def grid_download(self):
+        """r1_grid_download: the grid as the device holds it, as grid_describe returns it (diagnostic, synchronous); overflow:
+        info["registrations"] == -1."""
+        return _grid_tables(lambda *a: lib().r1_grid_download(self._c, *a))
 
     def bvh_ids_download(self):
         """r1_bvh_ids_download: the tree's leaf slots as the device holds them, uint32 scene indices, 0xFFFFFFFF = empty (diagnostic,
@@ -862,23 +879,68 @@ def _refit_describe(who, cscene, x, y, z, radius_sq, inv_radius, leaf_max):
     return d, nodes
 
 
-def grid_describe(cscene):
-    """Host-side build of the R1_VARIANT_GRID index: (info dict, start uint32[cells + 1], ids uint32[registrations], outliers uint32[n]);
-    ids and outliers are scene indices."""
+def _grid_tables(call):
+    """The two-call protocol of r1_grid_describe and its kin: `call(info, start, start_cap, ids, ids_cap, outliers, outliers_cap)`."""
     info = GridInfo()
-    _check(lib().r1_grid_describe(C.byref(cscene), C.byref(info), None, 0, None, 0, None, 0))
+    _check(call(C.byref(info), None, 0, None, 0, None, 0))
     ncells = int(info.cells[0]) * int(info.cells[1]) * int(info.cells[2])
+    regs = max(info.registrations, 0)
     start = np.zeros(ncells + 1, np.uint32)
-    ids = np.zeros(max(info.registrations, 1), np.uint32)
+    ids = np.zeros(max(regs, 1), np.uint32)
     outl = np.zeros(max(info.outliers, 1), np.uint32)
     u32p = C.POINTER(C.c_uint32)
-    _check(lib().r1_grid_describe(C.byref(cscene), C.byref(info), start.ctypes.data_as(u32p), start.size, ids.ctypes.data_as(u32p), ids.size,
-                                  outl.ctypes.data_as(u32p), outl.size))
+    _check(call(C.byref(info), start.ctypes.data_as(u32p), start.size, ids.ctypes.data_as(u32p), ids.size, outl.ctypes.data_as(u32p), outl.size))
     d = {}
     for k, t in GridInfo._fields_:
         v = getattr(info, k)
         d[k] = np.array(list(v), np.float32 if k != "cells" else np.int64) if hasattr(v, "__len__") else v
-    return d, start, ids[:info.registrations], outl[:info.outliers]
+    return d, start, ids[:regs], outl[:info.outliers]
+
+
+def grid_describe(cscene):
+    """Host-side build of the R1_VARIANT_GRID index: (info dict, start uint32[cells + 1], ids uint32[registrations], outliers uint32[n]);
+    ids and outliers are scene indices."""
+    return _grid_tables(lambda *a: lib().r1_grid_describe(C.byref(cscene), *a))
+
+
+def _regrid_arrays(who, cscene, x, y, z, radius_sq, inv_radius):
+    if (radius_sq is None) != (inv_radius is None):
+        raise R1Error(R1_EINVAL, f"{who}: radius_sq and inv_radius go together")
+    arrays = [np.ascontiguousarray(v, np.float32) for v in (x, y, z) + (() if radius_sq is None else (radius_sq, inv_radius))]
+    if any(v.shape != (cscene.count,) for v in arrays):
+        raise R1Error(R1_EINVAL, f"{who}: every array needs cscene.count entries")
+    return arrays, [v.ctypes.data_as(_f32p) for v in arrays] + ([None, None] if radius_sq is None else [])
+
+
+def grid_plan(cscene):
+    """What a regrid keeps of the grid of `cscene` besides grid_describe's geometry (r1_grid_plan_describe, internal as r1_sweep_describe
+    is): {"V", "delta", "big", "M": float, "flat": bool[3]}."""
+    f = lib().r1_grid_plan_describe
+    f.restype, f.argtypes = C.c_int, [C.POINTER(CScene), _dblp, _i32p]
+    d4, flat = np.zeros(4, np.float64), np.zeros(3, np.int32)
+    _check(f(C.byref(cscene), d4.ctypes.data_as(_dblp), flat.ctypes.data_as(_i32p)))
+    return {"V": float(d4[0]), "delta": float(d4[1]), "big": float(d4[2]), "M": float(d4[3]), "flat": flat != 0}
+
+
+def regrid_describe(cscene, x, y, z, radius_sq=None, inv_radius=None):
+    """r1_grid_regrid_describe: the grid r1_set_scene's arrays give `cscene`, its plan kept and the scene-indexed centres (and radii; both
+    None: the built scene's) re-registered on the host by the device's steps: as grid_describe returns it; overflow: registrations == -1."""
+    keep, ptrs = _regrid_arrays("regrid_describe", cscene, x, y, z, radius_sq, inv_radius)
+    return _grid_tables(lambda *a: lib().r1_grid_regrid_describe(C.byref(cscene), *ptrs, *a))
+
+
+def regrid_visit(cscene, x, y, z, o, d, radius_sq=None, inv_radius=None, cap=1 << 16):
+    """grid_visit through the regridded tables, against the moved spheres."""
+    keep, ptrs = _regrid_arrays("regrid_visit", cscene, x, y, z, radius_sq, inv_radius)
+    o = np.ascontiguousarray(o, np.float32)
+    d = np.ascontiguousarray(d, np.float32)
+    pres = np.zeros(cap, np.uint32)
+    n, hi, ht, fb = C.c_size_t(), C.c_int32(), C.c_float(), C.c_int32()
+    _check(lib().r1_grid_regrid_visit(C.byref(cscene), *ptrs, o.ctypes.data_as(_f32p), d.ctypes.data_as(_f32p), pres.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                      cap, C.byref(n), C.byref(hi), C.byref(ht), C.byref(fb)))
+    if n.value > cap:
+        return regrid_visit(cscene, x, y, z, o, d, radius_sq, inv_radius, int(n.value))
+    return pres[:n.value], int(hi.value), float(ht.value), bool(fb.value)
 
 
 class SweepInfo(C.Structure):

@@ -14,6 +14,7 @@
 #include "../../include/rays1.h"
 #include "r1_device.h"
 #include "r1_grid.h"
+#include "r1_grid_fill.h"
 #include "r1_bvh.h" // r1_bvh.cpp: the built tree, a refit's topology tables
 #include "r1_internal.h"
 
@@ -84,6 +85,13 @@ struct r1_context
     bool grid_valid = false;
     bool grid_small = false;  // 16-bit tables that the small-scene kernel keeps in LDS
     R1GridArgs grid_args;     // (pointers into grid_tab / grid_out; a copy of it in grid_dev)
+    // r1_regrid (r1_regrid.hip).  grid_valid says "the tables are those of the spheres the device holds": every update clears
+    // it, a regrid sets it again.  grid_planned says "the grid's buffers and plan belong to this scene": only r1_set_scene clears it.
+    bool grid_planned = false;
+    R1GridPlan grid_plan;     // what ensure_grid's build decided for the arrays of r1_set_scene
+    bool regrid_ready = false; // the scene's first regrid has grown the tables to the capacity and laid out the scratch
+    R1RegridArgs regrid;
+    DevBuf regrid_ws;
     DevBuf wf_paths, wf_hits, wf_queue, wf_counts; // R1_VARIANT_WAVEFRONT workspace
     DevBuf wave_log;                               // STATS builds: per-wave {start, queue empty, end, iterations}
     unsigned long long wave_log_ptr = 0;

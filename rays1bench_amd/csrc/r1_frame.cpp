@@ -649,7 +649,7 @@ int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int block_layo
     if (rc)
         return rc;
     const int variant = resolve_variant(c, p->variant, throughput_mode);
-    if (c->moved && variant != R1_V_REFERENCE && !r1_is_tree(variant))
+    if (c->moved && variant != R1_V_REFERENCE && !r1_is_tree(variant) && !(r1_is_grid(variant) && c->grid_valid)) // (a grid r1_regrid re-registered serves)
     {
         r1_set_error("variant %d: the scene has moved (r1_update_centers) and only the box tree was refitted, not the sphere groups and the uniform grid; "
                      "r1_set_scene rebuilds them", variant);

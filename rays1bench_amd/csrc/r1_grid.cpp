@@ -51,6 +51,8 @@
 #include <vector>
 
 #include "r1_grid.h"
+#include "r1_grid_fill.h"
+#include "r1_internal.h"
 
 int r1_active_spheres(const r1_scene *s, std::vector<uint32_t> &active_to_scene); // r1_bvh.cpp
 double r1_bound_radius(float radius_sq, float inv_radius);
@@ -110,7 +112,7 @@ void r1_build_grid(uint32_t na, const float *cx, const float *cy, const float *c
     {
         std::vector<double> rs(rbound, rbound + na);
         std::nth_element(rs.begin(), rs.begin() + na / 2, rs.end());
-        const double big = ratio_env * rs[na / 2];
+        const double big = g.big = ratio_env * rs[na / 2];
         for (uint32_t i = 0; i < na; ++i)
             out[i] = rbound[i] > big ? 1 : 0;
     }
@@ -231,6 +233,9 @@ void r1_build_grid(uint32_t na, const float *cx, const float *cy, const float *c
         double bound_m = 0;
         for (int a = 0; a < 3; ++a)
             bound_m = std::max(bound_m, std::max(std::fabs((double)g.geom.lo[a]), std::fabs((double)g.geom.lo[a] + g.geom.n[a] * (double)g.geom.cell[a])));
+        g.M = M, g.delta = delta; // (the plan of a regrid: this pass's)
+        for (int a = 0; a < 3; ++a)
+            g.flat[a] = flat[a];
         if (bound_m <= M || pass >= 4)
             break;
         M = bound_m * (1.0 + 1e-3) + 1.0;
@@ -333,16 +338,10 @@ int r1_grid_from_scene(const r1_scene *s, R1Grid &g)
     return grid_from_scene(s, g, scene_index, ex);
 }
 
-extern "C" int r1_grid_describe(const r1_scene *s, r1_grid_info *info, uint32_t *start_out, size_t start_cap, uint32_t *ids_out, size_t ids_cap,
-                                uint32_t *outliers_out, size_t outliers_cap)
+// info and the optional outputs of r1_grid_describe, r1_grid_regrid_describe and r1_grid_download, from a grid in active indices
+int r1_grid_report(const R1Grid &g, const std::vector<uint32_t> &scene_index, bool overflow, r1_grid_info *info, uint32_t *start_out, size_t start_cap,
+                   uint32_t *ids_out, size_t ids_cap, uint32_t *outliers_out, size_t outliers_cap)
 {
-    if (!s || !info || !s->center_x || !s->center_y || !s->center_z || !s->radius_sq || !s->inv_radius)
-        return R1_EINVAL;
-    R1Grid g;
-    std::vector<uint32_t> scene_index;
-    std::vector<float> ex;
-    if (grid_from_scene(s, g, scene_index, ex) != R1_OK)
-        return R1_EINVAL;
     memset(info, 0, sizeof(*info));
     for (int a = 0; a < 3; ++a)
     {
@@ -354,7 +353,7 @@ extern "C" int r1_grid_describe(const r1_scene *s, r1_grid_info *info, uint32_t 
     info->v_safe = (float)g.v_safe;
     info->spheres = (int32_t)scene_index.size();
     info->outliers = (int32_t)g.outliers.size();
-    info->registrations = (int32_t)g.ids.size();
+    info->registrations = overflow ? -1 : (int32_t)g.ids.size();
     info->max_occupancy = (int32_t)g.max_occupancy;
     info->build_ms = (float)g.build_ms;
     if (start_out)
@@ -380,6 +379,19 @@ extern "C" int r1_grid_describe(const r1_scene *s, r1_grid_info *info, uint32_t 
     return R1_OK;
 }
 
+extern "C" int r1_grid_describe(const r1_scene *s, r1_grid_info *info, uint32_t *start_out, size_t start_cap, uint32_t *ids_out, size_t ids_cap,
+                                uint32_t *outliers_out, size_t outliers_cap)
+{
+    if (!s || !info || !s->center_x || !s->center_y || !s->center_z || !s->radius_sq || !s->inv_radius)
+        return R1_EINVAL;
+    R1Grid g;
+    std::vector<uint32_t> scene_index;
+    std::vector<float> ex;
+    if (grid_from_scene(s, g, scene_index, ex) != R1_OK)
+        return R1_EINVAL;
+    return r1_grid_report(g, scene_index, false, info, start_out, start_cap, ids_out, ids_cap, outliers_out, outliers_cap);
+}
+
 // exact_offer (r1_hit_sweep.hpp) on the host: the same operations, the same order
 static float host_offer(const float *e, const float o[3], const float d[3])
 {
@@ -401,17 +413,10 @@ static float host_offer(const float *e, const float o[3], const float d[3])
     return offer;
 }
 
-extern "C" int r1_grid_visit(const r1_scene *s, const float o[3], const float d[3], uint32_t *presented, size_t cap, size_t *n_presented,
-                             int32_t *hit_index, float *hit_t, int32_t *fallback)
+// One ray through given tables (active indices; ex: the spheres' exact rows), as the kernel walks them
+static void visit_tables(const R1Grid &g, const std::vector<uint32_t> &scene_index, const std::vector<float> &ex, const float o[3], const float d[3],
+                         uint32_t *presented, size_t cap, size_t *n_presented, int32_t *hit_index, float *hit_t, int32_t *fallback)
 {
-    if (!s || !o || !d || !n_presented || !hit_index || !hit_t || !fallback || !s->center_x || !s->center_y || !s->center_z ||
-        !s->radius_sq || !s->inv_radius)
-        return R1_EINVAL;
-    R1Grid g;
-    std::vector<uint32_t> scene_index;
-    std::vector<float> ex;
-    if (grid_from_scene(s, g, scene_index, ex) != R1_OK)
-        return R1_EINVAL;
     size_t np = 0;
     float best = FLT_MAX;
     uint32_t best_id = 0xFFFFFFFFu;
@@ -450,5 +455,174 @@ extern "C" int r1_grid_visit(const r1_scene *s, const float o[3], const float d[
     *n_presented = np;
     *hit_index = best_id == 0xFFFFFFFFu ? -1 : (int32_t)scene_index[best_id];
     *hit_t = best;
+}
+
+extern "C" int r1_grid_visit(const r1_scene *s, const float o[3], const float d[3], uint32_t *presented, size_t cap, size_t *n_presented,
+                             int32_t *hit_index, float *hit_t, int32_t *fallback)
+{
+    if (!s || !o || !d || !n_presented || !hit_index || !hit_t || !fallback || !s->center_x || !s->center_y || !s->center_z ||
+        !s->radius_sq || !s->inv_radius)
+        return R1_EINVAL;
+    R1Grid g;
+    std::vector<uint32_t> scene_index;
+    std::vector<float> ex;
+    if (grid_from_scene(s, g, scene_index, ex) != R1_OK)
+        return R1_EINVAL;
+    visit_tables(g, scene_index, ex, o, d, presented, cap, n_presented, hit_index, hit_t, fallback);
+    return R1_OK;
+}
+
+// ---- regrid: the moved spheres re-registered against the build's plan -----------------------------------------
+
+static_assert(R1_GRID_SPAN_LIMIT == R1_GRID_SPAN_MAX, "r1_grid_fill.h counts cells up to the builder's limit");
+
+void r1_grid_plan(const R1Grid &g, R1GridPlan &p)
+{
+    memset(&p, 0, sizeof(p));
+    for (int a = 0; a < 3; ++a)
+        p.lo[a] = g.geom.lo[a], p.cell[a] = g.geom.cell[a], p.inv_cell[a] = g.geom.inv_cell[a], p.n[a] = g.geom.n[a], p.flat[a] = g.flat[a] ? 1 : 0;
+    p.V = g.v_safe, p.delta = g.delta, p.big = g.big, p.M = g.M;
+    // (a build that registered nothing stores v2 = inf: the plan keeps the V it chose, as r1_build_grid rounds it)
+    p.v2 = round_down_f(g.v_safe * g.v_safe * (1.0 - ldexp(1.0, -20)));
+    p.n_start = (uint32_t)g.start.size();
+    p.regs = (uint32_t)g.ids.size();
+}
+
+// the plan of the grid of `built`, for tests: doubles4 = {V, delta, big, M}, flat3 = which axes have one cell
+extern "C" int r1_grid_plan_describe(const r1_scene *built, double *doubles4, int32_t *flat3)
+{
+    if (!built || !doubles4 || !flat3 || !built->center_x || !built->center_y || !built->center_z || !built->radius_sq || !built->inv_radius)
+        return R1_EINVAL;
+    R1Grid g;
+    if (r1_grid_from_scene(built, g) != R1_OK)
+        return R1_EINVAL;
+    R1GridPlan p;
+    r1_grid_plan(g, p);
+    doubles4[0] = p.V, doubles4[1] = p.delta, doubles4[2] = p.big, doubles4[3] = p.M;
+    for (int a = 0; a < 3; ++a)
+        flat3[a] = p.flat[a];
+    return R1_OK;
+}
+
+bool r1_grid_regrid_host(const R1GridPlan &P, uint32_t na, const float *exact, const double *radii, R1Grid &out)
+{
+    out = R1Grid();
+    // 1. classify: class, span and the extents
+    std::vector<uint32_t> span(na, 0u);
+    std::vector<uint8_t> outl(na, 0);
+    std::vector<double> rho(na, 0.0);
+    R1GridExtent ext;
+    ext.clear();
+    size_t total = 0;
+    for (uint32_t i = 0; i < na; ++i)
+    {
+        const float *e = exact + 4 * (size_t)i;
+        bool cand;
+        const uint32_t k = r1gf_classify(P, e[0], e[1], e[2], radii[2 * (size_t)i], radii[2 * (size_t)i + 1], rho[i], span[i], cand);
+        outl[i] = k == R1GF_OUTLIER;
+        ext.add(e[0], e[1], e[2], rho[i], cand, k == R1GF_CANDIDATE);
+        total += span[i];
+    }
+    // 2. the geometry
+    for (int a = 0; a < 3; ++a)
+        out.geom.n[a] = P.n[a];
+    r1gf_geometry(P, ext, out.geom.lo, out.geom.cell, out.geom.inv_cell, out.geom.clo, out.geom.chi);
+    // 3. the outlier list, the total against the capacity
+    for (uint32_t i = 0; i < na; ++i)
+        if (outl[i])
+            out.outliers.push_back(i);
+    const bool overflow = total > r1gf_capacity(P.regs);
+    out.geom.v2 = overflow ? -1.0f : (total ? P.v2 : INFINITY);
+    out.v_safe = P.V, out.M = P.M, out.delta = P.delta, out.big = P.big;
+    for (int a = 0; a < 3; ++a)
+        out.flat[a] = P.flat[a] != 0;
+    out.start.assign(P.n_start, 0u);
+    if (overflow)
+        return true;
+    // 4. + 5. the (cell, id) pairs in sphere order, sorted by cell: ascending ids within a cell
+    std::vector<std::pair<uint32_t, uint32_t>> pairs(total);
+    size_t at = 0;
+    uint32_t keys[R1_GRID_SPAN_LIMIT + 1], vals[R1_GRID_SPAN_LIMIT + 1];
+    for (uint32_t i = 0; i < na; ++i)
+        if (span[i])
+        {
+            const float *e = exact + 4 * (size_t)i;
+            const uint32_t n = r1gf_cells(P, e[0], e[1], e[2], rho[i], keys, vals, i);
+            for (uint32_t k = 0; k < n; ++k)
+                pairs[at++] = {keys[k], vals[k]};
+            out.pad = std::max(out.pad, rho[i] - radii[2 * (size_t)i]);
+        }
+    std::sort(pairs.begin(), pairs.end());
+    // 6. the starts
+    out.ids.resize(total);
+    for (size_t q = 0; q < total; ++q)
+        out.ids[q] = pairs[q].second, ++out.start[pairs[q].first + 1];
+    for (size_t q = 1; q < out.start.size(); ++q)
+    {
+        out.max_occupancy = std::max(out.max_occupancy, out.start[q]);
+        out.start[q] += out.start[q - 1];
+    }
+    return false;
+}
+
+// the plan of `built` and the moved scene's rows in active order: exact [na][4], radii [na][2] as the device's set kernel writes them
+static int regrid_inputs(const r1_scene *built, const float *x, const float *y, const float *z, const float *radius_sq, const float *inv_radius,
+                         R1GridPlan &plan, std::vector<uint32_t> &scene_index, std::vector<float> &ex, std::vector<double> &radii)
+{
+    if (!built || !x || !y || !z || (!radius_sq) != (!inv_radius) || !built->center_x || !built->center_y || !built->center_z || !built->radius_sq ||
+        !built->inv_radius)
+        return R1_EINVAL;
+    R1Grid g;
+    if (grid_from_scene(built, g, scene_index, ex) != R1_OK)
+        return R1_EINVAL;
+    r1_grid_plan(g, plan);
+    const uint32_t na = (uint32_t)scene_index.size();
+    radii.assign(2 * (size_t)na + 2, 0.0);
+    for (uint32_t a = 0; a < na; ++a)
+    {
+        const uint32_t i = scene_index[a];
+        float rsq, inv;
+        r1f_radius_rows(radius_sq ? radius_sq[i] : built->radius_sq[i], inv_radius ? inv_radius[i] : built->inv_radius[i], rsq, inv, &radii[2 * (size_t)a]);
+        ex[4 * (size_t)a] = x[i], ex[4 * (size_t)a + 1] = y[i], ex[4 * (size_t)a + 2] = z[i], ex[4 * (size_t)a + 3] = rsq;
+    }
+    return R1_OK;
+}
+
+extern "C" int r1_grid_regrid_describe(const r1_scene *built, const float *x, const float *y, const float *z, const float *radius_sq,
+                                       const float *inv_radius, r1_grid_info *info, uint32_t *start_out, size_t start_cap, uint32_t *ids_out,
+                                       size_t ids_cap, uint32_t *outliers_out, size_t outliers_cap)
+{
+    if (!info)
+        return R1_EINVAL;
+    const auto t_begin = std::chrono::steady_clock::now();
+    R1GridPlan plan;
+    std::vector<uint32_t> scene_index;
+    std::vector<float> ex;
+    std::vector<double> radii;
+    int rc = regrid_inputs(built, x, y, z, radius_sq, inv_radius, plan, scene_index, ex, radii);
+    if (rc)
+        return rc;
+    R1Grid g;
+    const bool overflow = r1_grid_regrid_host(plan, (uint32_t)scene_index.size(), ex.data(), radii.data(), g);
+    g.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    return r1_grid_report(g, scene_index, overflow, info, start_out, start_cap, ids_out, ids_cap, outliers_out, outliers_cap);
+}
+
+extern "C" int r1_grid_regrid_visit(const r1_scene *built, const float *x, const float *y, const float *z, const float *radius_sq,
+                                    const float *inv_radius, const float o[3], const float d[3], uint32_t *presented, size_t cap,
+                                    size_t *n_presented, int32_t *hit_index, float *hit_t, int32_t *fallback)
+{
+    if (!o || !d || !n_presented || !hit_index || !hit_t || !fallback)
+        return R1_EINVAL;
+    R1GridPlan plan;
+    std::vector<uint32_t> scene_index;
+    std::vector<float> ex;
+    std::vector<double> radii;
+    int rc = regrid_inputs(built, x, y, z, radius_sq, inv_radius, plan, scene_index, ex, radii);
+    if (rc)
+        return rc;
+    R1Grid g;
+    r1_grid_regrid_host(plan, (uint32_t)scene_index.size(), ex.data(), radii.data(), g);
+    visit_tables(g, scene_index, ex, o, d, presented, cap, n_presented, hit_index, hit_t, fallback);
     return R1_OK;
 }

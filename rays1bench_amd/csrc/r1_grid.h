@@ -23,9 +23,25 @@ struct R1Grid
     double pad = 0;    // largest registration pad: rho_i - r_i over the registered spheres
     double v_safe = 0; // V: origins within V of every registered centre walk the grid, the others take the tree
     double build_ms = 0;
+    // the plan a regrid keeps (r1_grid_fill.h R1GridPlan): the last layout pass's coordinate bound and walk margin, the
+    // outlier radius (R1_GRID_OUTLIER_RATIO x the median bound radius) and which axes got one cell
+    double M = 0, delta = 0, big = 0;
+    bool flat[3] = {false, false, false};
 };
 
 void r1_build_grid(uint32_t na, const float *cx, const float *cy, const float *cz, const float *rsq, const double *rbound, R1Grid &g);
 int r1_grid_from_scene(const r1_scene *s, R1Grid &g); // the active spheres of s, filtered as r1_set_scene does
+
+struct r1_grid_info;
+// info and the optional outputs of r1_grid_describe, r1_grid_regrid_describe and r1_grid_download, from a grid in active indices
+int r1_grid_report(const R1Grid &g, const std::vector<uint32_t> &scene_index, bool overflow, r1_grid_info *info, uint32_t *start_out, size_t start_cap,
+                   uint32_t *ids_out, size_t ids_cap, uint32_t *outliers_out, size_t outliers_cap);
+
+struct R1GridPlan;
+void r1_grid_plan(const R1Grid &g, R1GridPlan &p); // what a regrid keeps of a build
+// The host restatement of r1_regrid (r1_regrid.hip's steps through r1_grid_fill.h): the na active spheres' rows exact [na][4] and radii
+// [na][2] re-registered against the plan.  out: geom, start, ids, outliers, pad, max_occupancy; returns true if the registrations exceed
+// the id table's capacity (then v2 = -1, every start 0, no ids).
+bool r1_grid_regrid_host(const R1GridPlan &p, uint32_t na, const float *exact, const double *radii, R1Grid &out);
 
 #endif

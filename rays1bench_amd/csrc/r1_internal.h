@@ -14,6 +14,7 @@
 struct R1RefitArgs; // r1_bvh_fill.h
 struct R1SetArgs;
 struct R1SortArgs; // r1_bvh_sort.h
+struct R1RegridArgs; // r1_grid_fill.h
 
 // what r1_sweep_describe says of the sweep's tables besides the arrays
 struct r1_sweep_info
@@ -35,6 +36,9 @@ void r1_build_facts(int variant, int mode, int big, int *facts6);  // the predic
 // r1_sweep.cpp: the sweep's tables for tests, as r1_set_scene builds them (buffers: caller's, with capacities in elements; NULL: not wanted)
 int r1_sweep_describe(const r1_scene *s, r1_sweep_info *info, double *groups_out, size_t groups_cap, float *sweep_out, size_t sweep_cap,
                       uint32_t *members_out, size_t members_cap, float *exact_g_out, size_t exact_g_cap, uint32_t *active_out, size_t active_cap);
+
+// r1_grid.cpp: the plan a regrid keeps of the grid of `built` (r1_grid_fill.h R1GridPlan), for tests: {V, delta, big, M} and the flat axes
+int r1_grid_plan_describe(const r1_scene *built, double *doubles4, int32_t *flat3);
 
 // r1_host.cpp
 int r1_params_check(const r1_params *p);
@@ -84,6 +88,11 @@ hipError_t r1_launch_refit(const R1RefitArgs *a, const uint32_t *height_off, uin
 // r1_resort.hip: the kernels of r1_resort_spheres
 hipError_t r1_launch_resort(const R1SortArgs *a, const uint32_t *depth_off, uint32_t depths, hipStream_t stream);
 size_t r1_sort_sums_words(size_t n); // words of block sums its prefix sum over n items needs
+void r1_scan_enqueue(uint32_t *data, uint32_t n, uint32_t *sums, hipStream_t stream); // exclusive prefix sum of data[0, n) in place, three launches per level
+
+// r1_regrid.hip: the kernels of r1_regrid
+hipError_t r1_launch_regrid(const R1RegridArgs *a, hipStream_t stream);
+size_t r1_regrid_blocks(size_t n); // workgroups of n items
 }
 
 #endif

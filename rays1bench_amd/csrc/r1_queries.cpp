@@ -47,7 +47,7 @@ static int query_check(const char *who, int job, r1_context *c, int32_t variant,
         r1_set_error("%s: no scene set (call r1_set_scene first)", who);
         return R1_EINVAL;
     }
-    if (c->moved && *structure == R1_V_GRID)
+    if (c->moved && *structure == R1_V_GRID && !c->grid_valid) // (a grid r1_regrid re-registered serves)
     {
         r1_set_error("%s: the scene has moved (r1_update_centers) and the uniform grid was not refitted; r1_set_scene rebuilds it", who);
         return R1_EINVAL;

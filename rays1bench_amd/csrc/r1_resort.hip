@@ -73,6 +73,9 @@ static void scan_enqueue(uint32_t *data, uint32_t n, uint32_t *sums, hipStream_t
     hipLaunchKernelGGL(r1_scan_apply_kernel, dim3(nb), dim3(R1_SORT_BLOCK), 0, stream, data, n, (const uint32_t *)sums);
 }
 
+// the same for r1_regrid.hip
+extern "C" void r1_scan_enqueue(uint32_t *data, uint32_t n, uint32_t *sums, hipStream_t stream) { scan_enqueue(data, n, sums, stream); }
+
 // words of block sums a prefix sum over n items needs, all levels
 extern "C" size_t r1_sort_sums_words(size_t n)
 {

@@ -1,0 +1,429 @@
+"""GPU tests of the regrid: r1_regrid re-registers the spheres the device holds in the uniform grid, on the device, against
+the plan of the grid built for the arrays of r1_set_scene.  The contract is the updates' own: every render and query through the grid
+afterwards gives, byte for byte and ray for ray, what a FRESH context gives after r1_set_scene with the context's current spheres; and the
+device's tables equal the host restatement's (r1_grid_regrid_describe), byte for byte.  Nothing here has a tolerance."""
+import numpy as np
+import pytest
+
+import rays1bench_amd as r1
+from rays1bench_amd import binding
+from test_bvh_host import F, _raw_scene
+from test_gpu_update import MOVED_RULE, edge_arrays, edge_camera, expect_refusal, same
+from test_refit_host import MOVES, edge_scene, lattice_of, make_scene, moved_centres, raw_from_arrays
+
+pytestmark = pytest.mark.gpu
+
+# The kernels of r1_regrid.hip work in blocks of 256 lanes, one item per lane (R1_REGRID_BLOCK), and their prefix sums are r1_resort.hip's
+# three-launch form, which recurses where the block sums exceed a block.  With N active spheres, a plan of R registrations, capacity
+# C = 2 R + 64 and P pairs:
+#   classify and the two prefix sums run over N + 1 items:  one block while N <= 255, two from N = 256; emit runs over N: two from N = 257;
+#                                                           a second level of the prefix sum from N + 1 > 65 536;
+#   the radix sort's histogram has 256 x ceil(C / 256) entries: its prefix sum has a second level from C > 65 536;
+#   the sort's blocks of pairs: one while P <= 256.
+# The cases: raw lattices of 255 / 256 / 257 spheres; small (N = 4), large (484) and grid40x30 (1204, the big form); grid300x220 (66 004
+# spheres, C = 768 744, P > 65 536: the second level of every prefix sum) — asserted in test_the_cases_cover_the_block_and_scan_edges.
+BLOCK = 256
+LEVELS = (BLOCK - 1, BLOCK, BLOCK * BLOCK)  # N: one block of classify | two; of emit | two; items of one prefix-sum level
+FRAME = (96, 64, 4)
+NAMES = ("large", "small", "grid40x30")
+BIG = "grid300x220"
+BIG_FRAME = (96, 54, 1)
+RADIUS_FACTOR = 0.5
+
+
+@pytest.fixture(scope="module")
+def upd():
+    assert r1.device_count() >= 1, "no HIP device: the product has no CPU fallback"
+    r = r1.Renderer(0)
+    yield r
+    r.close()
+
+
+@pytest.fixture(scope="module")
+def fresh():
+    r = r1.Renderer(0)
+    yield r
+    r.close()
+
+
+@pytest.fixture(scope="module")
+def scenes():
+    """name -> (Scene, arrays): built once, never changed."""
+    out = {}
+    for name in NAMES + (BIG,):
+        sc = make_scene(name)
+        out[name] = (sc, sc.arrays())
+    return out
+
+
+def frame(variant=0, seed=777, shape=FRAME):
+    return r1.make_params(*shape, seed, variant=variant)
+
+
+def edited(a, x, y, z, rsq=None, inv=None):
+    e = dict(a)
+    e.update(center_x=x, center_y=y, center_z=z)
+    if rsq is not None:
+        e.update(radius_sq=rsq, inv_radius=inv)
+    return e
+
+
+def fresh_frames(fresh, e, cam, shape=FRAME, reference=True):
+    """A fresh context's r1_set_scene with the edited arrays: its frame through the grid, asserted equal through the tree and REFERENCE."""
+    cs, keep = raw_from_arrays(e)
+    fresh.set_scene_raw(cs, cam)
+    want = fresh.render(frame(binding.VARIANT_GRID, shape=shape))[:2]
+    same(fresh.render(frame(shape=shape))[:2], want, "fresh: the tree")
+    if reference:
+        same(fresh.render(frame(binding.VARIANT_REFERENCE, shape=shape))[:2], want, "fresh: reference")
+    return want
+
+
+def tables_equal(got, want, what):
+    for k in want[0]:
+        if k != "build_ms":
+            assert np.array_equal(np.asarray(got[0][k]), np.asarray(want[0][k])), (what, k, got[0][k], want[0][k])
+    for n, g, w in zip(("start", "ids", "outliers"), got[1:], want[1:]):
+        assert g.shape == w.shape and g.tobytes() == w.tobytes(), (what, n, g[:8], w[:8])
+
+
+def device_equals_host(upd, cs, e, what):
+    want = binding.regrid_describe(cs, e["center_x"], e["center_y"], e["center_z"], e["radius_sq"], e["inv_radius"])
+    tables_equal(upd.grid_download(), want, what)
+    return want
+
+
+def scaled_radii(a, f=RADIUS_FACTOR):
+    f = F(f)
+    return (a["radius_sq"] * f * f).astype(F), (a["inv_radius"] / f).astype(F)
+
+
+def to_device(*arrays):
+    import torch
+    return [torch.from_numpy(np.ascontiguousarray(v)).cuda() for v in arrays]
+
+
+def lattice_256(n):
+    """A raw scene of n hittable spheres: a jittered 17 x 16 lattice in the plane, radius 0.2, and one ground sphere."""
+    rng = np.random.default_rng(n)
+    j = np.arange(n - 1)
+    c = np.stack([(j % 17) * 0.8 - 6.4, np.full(n - 1, 0.2), (j // 17) * 0.8 - 6.0], 1) + rng.uniform(-0.05, 0.05, (n - 1, 3)) * [1, 0, 1]
+    c = np.concatenate([c, [[0.0, -1000.0, 0.0]]])
+    rad = np.concatenate([np.full(n - 1, 0.2), [1000.0]])
+    return _raw_scene(c, rad)
+
+
+def test_the_cases_cover_the_block_and_scan_edges(scenes):
+    n = {name: int((a["inv_radius"] != 0).sum()) for name, (sc, a) in scenes.items()}
+    assert n == {"large": 484, "small": 4, "grid40x30": 1204, BIG: 66004}, n
+    assert n["small"] + 1 <= LEVELS[1] < n["large"] + 1                      # classify and the prefix sums: one block | several
+    assert n["grid40x30"] > 1023                                             # more than R1_MAX_ACTIVE_10BIT: the big form
+    assert n["grid40x30"] + 1 <= LEVELS[2] < n[BIG] + 1                      # the spheres' prefix sums: the second level
+    sc, a = scenes[BIG]
+    built = binding.grid_describe(sc.spheres.contents)[0]
+    assert 2 * built["registrations"] + 64 > LEVELS[2]                       # the histogram's prefix sum: the second level
+    x, y, z = moved_centres(a, "lift")
+    assert binding.regrid_describe(sc.spheres.contents, x, y, z)[0]["registrations"] > 65536
+    for k in (LEVELS[0], LEVELS[1], LEVELS[1] + 1):
+        cs, arrs, mt = lattice_256(k)
+        assert binding.grid_describe(cs)[0]["spheres"] == k
+
+
+# ---- equals a fresh build; device equals host ---------------------------------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("move", MOVES)
+@pytest.mark.parametrize("name", NAMES)
+def test_regrid_equals_fresh_build_and_host_pin(upd, fresh, scenes, name, move):
+    sc, a = scenes[name]
+    cs, cam = sc.spheres.contents, sc.camera.contents
+    x, y, z = moved_centres(a, move)
+    p = frame(binding.VARIANT_GRID)
+    # the host form
+    e = edited(a, x, y, z)
+    want = fresh_frames(fresh, e, cam)
+    upd.set_scene(sc)
+    upd.regrid()                                     # the plan, before the first update
+    upd.update_centers(0, x, y, z)
+    upd.regrid()
+    device_equals_host(upd, cs, e, (name, move, "host form"))
+    same(upd.render(p)[:2], want, (name, move, "host form"))
+    assert upd.launch_info()["kernel"] == binding.VARIANT_GRID
+    same(upd.render(frame(binding.VARIANT_GRID_STATS))[:2], want, (name, move, "host form, diagnostic build"))
+    # the device form, from the unmoved scene again
+    upd.set_scene(sc)
+    same(upd.render(p)[:2], fresh_frames(fresh, a, cam, reference=False), (name, "unmoved"))   # (the grid built by a render: the plan)
+    t = to_device(x, y, z)
+    upd.update_centers_device(0, len(x), t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
+    upd.regrid()
+    device_equals_host(upd, cs, e, (name, move, "device form"))
+    same(upd.render(p)[:2], want, (name, move, "device form"))
+    # a radius update on top of it
+    rsq, inv = scaled_radii(a)
+    upd.update_spheres(0, radii=(rsq, inv))
+    upd.regrid()
+    e = edited(a, x, y, z, rsq, inv)
+    device_equals_host(upd, cs, e, (name, move, "radii"))
+    same(upd.render(p)[:2], fresh_frames(fresh, e, cam), (name, move, "radii"))
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_queries_through_the_regridded_grid(upd, scenes, name):
+    sc, a = scenes[name]
+    x, y, z = moved_centres(a, "lift")
+    upd.set_scene(sc)
+    upd.regrid()
+    upd.update_centers(0, x, y, z)
+    upd.regrid()
+    cs, keep = raw_from_arrays(a, x, y, z)
+    rng = np.random.default_rng(29)
+    n = 4096
+    rays = np.zeros((n, 8), F)
+    rays[:, 0:3] = np.stack([rng.uniform(-12, 12, n), rng.uniform(0.0, 6, n), rng.uniform(-12, 12, n)], 1)
+    act = np.nonzero(a["inv_radius"] != 0)[0]
+    tgt = act[rng.integers(0, len(act), n)]
+    d = np.stack([x[tgt], y[tgt], z[tgt]], 1).astype(np.float64) + rng.normal(0, 0.05, (n, 3)) - rays[:, 0:3]
+    rays[:, 4:7] = (d / np.linalg.norm(d, axis=1, keepdims=True)).astype(F)
+    rays[:, 3] = np.where(rng.random(n) < 0.25, rng.uniform(0.5, 8, n), np.finfo(F).max).astype(F)
+    for mode in (binding.CAST_CLOSEST, binding.CAST_ANY):
+        want = binding.cast_rays_host(cs, rays, mode)
+        assert (want["index"] >= 0).sum() > n // 4 if mode == binding.CAST_CLOSEST else want.sum() > n // 4
+        assert upd.cast_rays(rays, mode, binding.VARIANT_GRID).tobytes() == want.tobytes(), (name, mode)
+    want = binding.trace_rays_host(cs, rays)
+    assert (want["rays"] > 1).sum() > n // 4
+    assert upd.trace_rays(rays, variant=binding.VARIANT_GRID).tobytes() == want.tobytes(), (name, "trace")
+
+
+# ---- repeated regrids, updates in between, the re-sort, materials --------------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_second_regrid_update_regrid_and_resort(upd, fresh, scenes, name):
+    sc, a = scenes[name]
+    cs, cam = sc.spheres.contents, sc.camera.contents
+    p = frame(binding.VARIANT_GRID)
+    upd.set_scene(sc)
+    upd.regrid()
+    x, y, z = moved_centres(a, "jitter")
+    upd.update_centers(0, x, y, z)
+    upd.regrid()
+    first = upd.grid_download()
+    shot = upd.render(p)[:2]
+    # a second regrid changes no byte
+    upd.regrid()
+    tables_equal(upd.grid_download(), first, (name, "second regrid"))
+    same(upd.render(p)[:2], shot, (name, "second regrid"))
+    # an update invalidates the grid again, a further regrid restores it
+    x, y, z = moved_centres(a, "lift")
+    upd.update_centers(0, x, y, z)
+    expect_refusal(lambda: upd.render(p), MOVED_RULE)
+    expect_refusal(lambda: upd.grid_download(), "no current grid")
+    upd.regrid()
+    e = edited(a, x, y, z)
+    device_equals_host(upd, cs, e, (name, "update, regrid, update, regrid"))
+    want = fresh_frames(fresh, e, cam)
+    same(upd.render(p)[:2], want, (name, "update, regrid, update, regrid"))
+    # the re-sort: an update for the grid too; the spheres stay where they are
+    upd.resort_spheres()
+    expect_refusal(lambda: upd.render(p), MOVED_RULE)
+    upd.regrid()
+    device_equals_host(upd, cs, e, (name, "re-sort, regrid"))
+    same(upd.render(p)[:2], want, (name, "re-sort, regrid"))
+    same(upd.render(frame())[:2], want, (name, "re-sort, regrid: the tree"))
+    # a materials-only update keeps the grid valid, as today
+    n = sc.count
+    mats = (a["mat_type"], a["albedo_b"], a["albedo_r"], a["albedo_g"], a["mat_param"])
+    upd.update_spheres(0, materials=mats)
+    e = dict(e)
+    e.update(albedo_r=a["albedo_b"], albedo_g=a["albedo_r"], albedo_b=a["albedo_g"])
+    got = upd.render(p)[:2]
+    same(got, fresh_frames(fresh, e, cam), (name, "materials"))
+    assert got[0].tobytes() != want[0].tobytes() and n == len(x)
+
+
+# ---- state ------------------------------------------------------------------------------------------------------------------------------------
+
+
+def test_state_rules(upd, fresh, scenes):
+    sc, a = scenes["large"]
+    cs, cam = sc.spheres.contents, sc.camera.contents
+    p = frame(binding.VARIANT_GRID)
+    blank = r1.Renderer(0)
+    try:
+        expect_refusal(lambda: blank.regrid(), "no scene set")
+        expect_refusal(lambda: blank.grid_download(), "no scene set")
+    finally:
+        blank.close()
+    # a moved scene whose grid was never built
+    x, y, z = moved_centres(a, "jitter")
+    upd.set_scene(sc)
+    expect_refusal(lambda: upd.grid_download(), "no current grid")
+    upd.update_centers(0, x, y, z)
+    expect_refusal(lambda: upd.regrid(), "before the first update")
+    expect_refusal(lambda: upd.render(p), MOVED_RULE)
+    # an unmoved scene: the build, then the regrid of it — byte for byte the builder's tables
+    upd.set_scene(sc)
+    upd.regrid()
+    tables_equal(upd.grid_download(), binding.grid_describe(cs), "regrid of the unmoved scene")
+    original = upd.render(p)[:2]
+    same(original, fresh_frames(fresh, a, cam), "unmoved")
+    same(upd.render(frame(binding.VARIANT_PREFILTER))[:2], original, "a regrid is no update: the sweep is still served")
+    # a regrid leaves a progressive accumulation and the launch info alone
+    half = r1.make_params(FRAME[0], FRAME[1], 2, 777)
+    upd.render_pass(half, 0)
+    before = upd.launch_info()
+    upd.regrid()
+    assert upd.launch_info() == before
+    upd.render_pass(half, 2)
+    # after an update and a regrid: the grid is served, the sweep and the wavefront stay refused
+    upd.update_centers(0, x, y, z)
+    upd.regrid()
+    same(upd.render(p)[:2], fresh_frames(fresh, edited(a, x, y, z), cam), "moved")
+    for variant in (binding.VARIANT_PREFILTER, binding.VARIANT_STATS, binding.VARIANT_WAVEFRONT):
+        expect_refusal(lambda: upd.render(frame(variant)), MOVED_RULE)
+    # r1_set_scene starts over: a grid built by a render is a plan too
+    upd.set_scene(sc)
+    same(upd.render(p)[:2], original, "grid after r1_set_scene")
+    upd.update_centers(0, x, y, z)
+    upd.regrid()
+    device_equals_host(upd, cs, edited(a, x, y, z), "plan from a render")
+
+
+@pytest.mark.parametrize("n_active", [0, 1, 4, 5])
+def test_edge_scenes_and_a_nan_centre(upd, fresh, n_active):
+    cs, arrs, mt = edge_scene(n_active)
+    a = edge_arrays(arrs, mt)
+    cam = edge_camera(64, 48)
+    shape = (64, 48, 3)
+    rng = np.random.default_rng(70 + n_active)
+    x, y, z = ((arrs[k] + rng.uniform(-1, 1, cs.count)).astype(F) for k in ("center_x", "center_y", "center_z"))
+    upd.set_scene_raw(cs, cam)
+    upd.regrid()
+    tables_equal(upd.grid_download(), binding.grid_describe(cs), (n_active, "unmoved"))
+    upd.update_centers(0, x, y, z)
+    upd.regrid()
+    e = edited(a, x, y, z)
+    device_equals_host(upd, cs, e, (n_active, "moved"))
+    same(upd.render(frame(binding.VARIANT_GRID, shape=shape))[:2], fresh_frames(fresh, e, cam, shape), (n_active, "moved"))
+    if n_active == 0:
+        return
+    # a NaN and a +inf centre through the device form: in neither list, never hit; r1_set_scene with the same arrays drops them
+    act = np.nonzero(arrs["inv_radius"] != 0)[0]
+    xn, yn = x.copy(), y.copy()
+    xn[act[-1]] = np.nan
+    if n_active > 1:
+        yn[act[0]] = np.inf
+    t = to_device(xn, yn, z)
+    upd.update_centers_device(0, len(xn), t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
+    upd.regrid()
+    e = edited(a, xn, yn, z)
+    got = device_equals_host(upd, cs, e, (n_active, "non-finite"))
+    assert not ({int(act[-1])} & (set(got[2].tolist()) | set(got[3].tolist())))
+    same(upd.render(frame(binding.VARIANT_GRID, shape=shape))[:2], fresh_frames(fresh, e, cam, shape), (n_active, "non-finite"))
+
+
+# ---- overflow -----------------------------------------------------------------------------------------------------------------------------------
+
+
+def test_overflow_and_back(upd, fresh, scenes):
+    """tests/test_regrid_host.py's overflow input: radii x 3 on grid 40 x 30 (the CPU test asserts that the pin reports it)."""
+    sc, a = scenes["grid40x30"]
+    cs, cam = sc.spheres.contents, sc.camera.contents
+    p = frame(binding.VARIANT_GRID)
+    upd.set_scene(sc)
+    upd.regrid()
+    rsq, inv = scaled_radii(a, 3.0)
+    upd.update_spheres(0, radii=(rsq, inv))
+    upd.regrid()
+    e = edited(a, a["center_x"], a["center_y"], a["center_z"], rsq, inv)
+    info, start, ids, outl = upd.grid_download()
+    assert info["registrations"] == -1 and not start.any() and len(ids) == 0
+    device_equals_host(upd, cs, e, "overflow")
+    same(upd.render(p)[:2], fresh_frames(fresh, e, cam), "overflow: every ray the tree fallback, the frame still exact")
+    # radii x 1 again: the grid is back
+    upd.update_spheres(0, radii=(a["radius_sq"], a["inv_radius"]))
+    upd.regrid()
+    tables_equal(upd.grid_download(), binding.grid_describe(cs), "back from overflow")
+    same(upd.render(p)[:2], fresh_frames(fresh, a, cam), "back from overflow")
+
+
+# ---- stream order -----------------------------------------------------------------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("name", ["large", "grid40x30"])
+def test_stream_order(upd, fresh, scenes, name):
+    """Frame A, the update, the regrid and frame B on one stream, one wait: A is the old scene's, B the moved one's, both through the grid."""
+    sc, a = scenes[name]
+    cs, cam = sc.spheres.contents, sc.camera.contents
+    w, h = FRAME[:2]
+    p = frame(binding.VARIANT_GRID)
+    x, y, z = moved_centres(a, "lift")
+    fa, fb = binding.HostFrames(w, h, 1), binding.HostFrames(w, h, 1)
+    try:
+        upd.set_scene(sc)
+        upd.regrid()
+        upd.sync()
+        upd.render_async(p, fa)
+        upd.update_centers(0, x, y, z)
+        upd.regrid()
+        upd.render_async(p, fb)
+        upd.sync()
+        old = fresh_frames(fresh, a, cam, reference=False)
+        assert fa.rays(0) == old[1] and fa.image(0).tobytes() == old[0].tobytes(), "frame A must see the old scene"
+        new = fresh_frames(fresh, edited(a, x, y, z), cam, reference=False)
+        assert fb.rays(0) == new[1] and fb.image(0).tobytes() == new[0].tobytes(), "frame B must see the moved scene"
+        assert old[0].tobytes() != new[0].tobytes()
+        device_equals_host(upd, cs, edited(a, x, y, z), (name, "after both frames"))
+    finally:
+        fa.close(), fb.close()
+
+
+# ---- block and scan edges -----------------------------------------------------------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("n", [LEVELS[0], LEVELS[1], LEVELS[1] + 1])
+def test_one_block_and_two(upd, fresh, n):
+    cs, arrs, mt = lattice_256(n)
+    a = edge_arrays(arrs, mt)
+    cam = edge_camera(64, 48)
+    shape = (64, 48, 2)
+    rng = np.random.default_rng(n)
+    x, z = ((arrs[k] + rng.uniform(-0.3, 0.3, n)).astype(F) for k in ("center_x", "center_z"))
+    y = arrs["center_y"].copy()
+    y[: n - 1] = rng.uniform(0.2, 1.5, n - 1).astype(F)
+    x[n - 1], z[n - 1] = arrs["center_x"][n - 1], arrs["center_z"][n - 1]
+    upd.set_scene_raw(cs, cam)
+    upd.regrid()
+    tables_equal(upd.grid_download(), binding.grid_describe(cs), (n, "unmoved"))
+    upd.update_centers(0, x, y, z)
+    upd.regrid()
+    e = edited(a, x, y, z)
+    want = device_equals_host(upd, cs, e, (n, "moved"))
+    assert want[0]["registrations"] > BLOCK       # several blocks of pairs
+    same(upd.render(frame(binding.VARIANT_GRID, shape=shape))[:2], fresh_frames(fresh, e, cam, shape), (n, "moved"))
+
+
+def test_the_second_level_of_every_prefix_sum(upd, fresh, scenes):
+    """66 004 spheres, more than 65 536 pairs, a capacity of 768 744 entries (asserted on the CPU in
+    test_the_cases_cover_the_block_and_scan_edges)."""
+    sc, a = scenes[BIG]
+    cs, cam = sc.spheres.contents, sc.camera.contents
+    upd.set_scene(sc)
+    upd.regrid()
+    tables_equal(upd.grid_download(), binding.grid_describe(cs), (BIG, "unmoved"))
+    act = a["inv_radius"] != 0
+    rng = np.random.default_rng(5)
+    for move in ("lift", "small jitter"):
+        if move == "lift":
+            x, y, z = moved_centres(a, move)
+        else:
+            x, y, z = (a[k].copy() for k in ("center_x", "center_y", "center_z"))
+            lat = lattice_of(a)
+            x[lat] = (x[lat] + rng.uniform(-0.02, 0.02, len(lat))).astype(F)
+            z[lat] = (z[lat] + rng.uniform(-0.02, 0.02, len(lat))).astype(F)
+        upd.update_centers(0, x, y, z)
+        upd.regrid()
+        e = edited(a, x, y, z)
+        want = device_equals_host(upd, cs, e, (BIG, move))
+        assert want[0]["registrations"] > 65536 and act.sum() + 1 > LEVELS[2]
+        same(upd.render(frame(binding.VARIANT_GRID, shape=BIG_FRAME))[:2], fresh_frames(fresh, e, cam, BIG_FRAME, reference=False), (BIG, move))

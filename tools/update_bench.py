@@ -22,9 +22,17 @@ The re-sort (r1_resort_spheres, §4.29; none of these is a pass / fail threshold
   (g.2) on config 5's scene, the frame after the refit alone, after the re-sort and after a fresh build of the same moved scene, for
         displacements of 0, 0.25, 1 and 4 spacings and for the lattice's centres permuted among its spheres — three contexts, alternating in
         one session, pixels and rays compared in every triple; and from it the displacement from which a re-sort pays for itself.
+The regrid (r1_regrid, §4.31; none of these is a pass / fail threshold either):
+  (h.1) the time of one regrid (enqueue to stream idle) on the large scene and on config 5's scene, beside r1_set_scene plus the first frame
+        through the grid (which builds and uploads it) with the same arrays;
+  (h.2) on the large scene, the frame through the grid after update + regrid, through the tree after the same update, and through the grid
+        of a fresh r1_set_scene, for `jitter` and `lift` of tests/test_refit_host.py and displacements of 0.25, 1 and 4 spacings — three
+        contexts, alternating in one session, pixels and rays compared in every triple; with the outliers, the registrations and the
+        launch's workgroups per CU before and after the scene's first regrid (which grows the small kernel's LDS tables to the capacity).
 Frames are r1_render_async into page-locked memory, timed from the enqueue to the stream idle by the host's clock.
-Writes its report to profiles/r20/update.txt (--out FILE: somewhere else) and section (g)'s to profiles/r22/resort.txt (--resort-out FILE).
-usage: tools/update_bench.py [--rounds N] [--frames N] [--out FILE] [--section all|a-f|g] [--resort-out FILE]"""
+Writes its report to profiles/r20/update.txt (--out FILE: somewhere else), section (g)'s to profiles/r22/resort.txt (--resort-out FILE) and
+section (h)'s to profiles/r24/regrid.txt (--regrid-out FILE).  --section all: (a)-(g), as before; (h) runs on its own.
+usage: tools/update_bench.py [--rounds N] [--frames N] [--out FILE] [--section all|a-f|g|h] [--resort-out FILE] [--regrid-out FILE]"""
 import argparse
 import ctypes as C
 import os
@@ -42,8 +50,9 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--frames", type=int, default=8, help="frames per timing of (b) and (c)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r20", "update.txt"), help="where the report is written")
-    ap.add_argument("--section", choices=("all", "a-f", "g"), default="all", help="g: the re-sort's section alone")
+    ap.add_argument("--section", choices=("all", "a-f", "g", "h"), default="all", help="g: the re-sort's section alone; h: the regrid's")
     ap.add_argument("--resort-out", default=os.path.join(ROOT, "profiles", "r22", "resort.txt"), help="where section (g)'s report is written")
+    ap.add_argument("--regrid-out", default=os.path.join(ROOT, "profiles", "r24", "regrid.txt"), help="where section (h)'s report is written")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -177,8 +186,121 @@ def main():
         with open(args.resort_out, "w") as f:
             f.write("\n".join(lines) + "\n")
 
-    if args.section == "g":
-        section_g()
+    def section_h():
+        """the regrid; its own report"""
+        del lines[:]
+        grid_p = r1.make_params(w, h, spp, seed, variant=binding.VARIANT_GRID)
+
+        def grid_frame(ctx):
+            ctx.render_async(grid_p, hf)
+            ctx.sync()
+
+        def frames_of(ctx, params, n):
+            def go():
+                ctx.render_async(params, hf)
+                ctx.sync()
+            go()  # workspaces
+            return [ms(go) for _ in range(n)]
+
+        large = r1.create_large_scene(w, h)
+        say(f"(h.1) one regrid against r1_set_scene plus the first frame through the grid, the same arrays ({args.rounds} rounds, alternating; enqueue to stream "
+            f"idle, host clock; the first frame is {w} x {h} x {spp} and builds and uploads the grid)")
+        for title, scene in (("the large scene", large), ("config 5's scene", r1.create_grid_scene(w, h, 400, 250))):
+            b = scene.arrays()
+            ctx = r1.Renderer(0)
+            ctx.set_scene(scene)
+            grid_frame(ctx)  # workspaces, the kernels' first launch
+            plain = frames_of(ctx, grid_p, 3)
+            t_grid, t_upd, t_set, t_first = [], [], [], []
+            for r in range(args.rounds + 1):
+                bx = (b["center_x"] + np.float32(0.01 * (r % 2))).astype(np.float32)
+                cs, keep = raw_from_arrays(b, bx, b["center_y"], b["center_z"])
+                ctx.regrid()  # (the plan of this r1_set_scene, the scene's first regrid: tables grown, scratch laid out)
+                ctx.sync()
+
+                def update():
+                    ctx.update_centers(0, bx, b["center_y"], b["center_z"])
+                    ctx.sync()
+
+                def regrid():
+                    ctx.regrid()
+                    ctx.sync()
+
+                tu, tg = ms(update), ms(regrid)
+                ts, tf = ms(lambda: ctx.set_scene_raw(cs, scene.camera.contents)), ms(lambda: grid_frame(ctx))
+                if r:  # (round 0: scratch, staging buffer, first launches)
+                    t_grid.append(tg), t_upd.append(tu), t_set.append(ts), t_first.append(tf)
+            info = binding.grid_describe(scene.spheres.contents)[0]
+            say(f"  {title}: {scene.count} spheres, grid of {int(info['cells'][0])} x {int(info['cells'][1])} x {int(info['cells'][2])} cells, "
+                f"{info['registrations']} registrations, {info['outliers']} outliers")
+            say(f"    r1_regrid                        {spread(t_grid)}")
+            say(f"    r1_update_centers                {spread(t_upd)}")
+            say(f"    r1_set_scene                     {spread(t_set)}")
+            say(f"    first frame through the grid     {spread(t_first)}")
+            say(f"    a later frame through the grid   {spread(plain)}")
+            first_cost = statistics.median(t_set) + statistics.median(t_first) - statistics.median(plain)
+            say(f"    (r1_set_scene + the grid's build) / (update + regrid): {first_cost / (statistics.median(t_upd) + statistics.median(t_grid)):.1f} x")
+            ctx.close()
+        say()
+        say(f"(h.2) the large scene, {w} x {h} x {spp}: the frame through the grid after update + regrid, through the tree after the same update, through the grid of a "
+            f"fresh r1_set_scene ({args.frames} frames per timing, {args.rounds} rounds, alternating)")
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        from test_refit_host import moved_centres
+        a = large.arrays()
+        lat = lattice_of(a)
+        spacing = float(binding.grid_describe(large.spheres.contents)[0]["cell"][0])  # (the grid's cells along x are the lattice's pitch)
+        ang = np.random.default_rng(5).uniform(0, 2 * np.pi, len(lat))
+
+        def moved(d):
+            if isinstance(d, str):
+                return moved_centres(a, d)
+            x, y, z = (a[k].copy() for k in ("center_x", "center_y", "center_z"))
+            x[lat] = (x[lat] + d * spacing * np.cos(ang)).astype(np.float32)
+            z[lat] = (z[lat] + d * spacing * np.sin(ang)).astype(np.float32)
+            return x, y, z
+
+        regridded, tree, fresh = r1.Renderer(0), r1.Renderer(0), r1.Renderer(0)
+        tree_p = r1.make_params(w, h, spp, seed)
+        regridded.set_scene(large), tree.set_scene(large)
+        grid_frame(regridded)
+        before = regridded.launch_info()
+        built = regridded.grid_download()[0]
+        regridded.regrid()
+        grid_frame(regridded)
+        after = regridded.launch_info()
+        say(f"  lattice spacing {spacing:.3f}; the build: {built['registrations']} registrations, {built['outliers']} outliers; workgroups per CU "
+            f"{before['blocks'] / before['compute_units']:.2f} ({before['blocks']} on {before['compute_units']} CUs) before the first regrid, "
+            f"{after['blocks'] / after['compute_units']:.2f} ({after['blocks']}) after it (kernel {after['kernel']})")
+        for d in ("jitter", "lift", 0.25, 1.0, 4.0):
+            x, y, z = moved(d)
+            cs, keep = raw_from_arrays(a, x, y, z)
+            for c in (regridded, tree):
+                c.update_centers(0, x, y, z)
+            regridded.regrid()
+            fresh.set_scene_raw(cs, large.camera.contents)
+            info = regridded.grid_download()[0]
+            t = {"regridded": [], "tree": [], "fresh": []}
+            same = True
+            for r in range(args.rounds):
+                out = []
+                for name, c, params in (("regridded", regridded, grid_p), ("tree", tree, tree_p), ("fresh", fresh, grid_p)):
+                    t[name] += frames_of(c, params, args.frames)
+                    out.append((hf.image(0).tobytes(), hf.rays(0)))
+                same = same and out[0] == out[1] == out[2]
+            m = {k: statistics.median(v) for k, v in t.items()}
+            fresh_info = fresh.grid_download()[0]
+            label = f"{d:<24s}" if isinstance(d, str) else f"displacement {d:4.2f} spacings"
+            regs = "overflow" if info["registrations"] < 0 else f"{info['registrations']:4d} registrations"
+            say(f"  {label}: regridded {m['regridded']:7.3f} ms ({regs}, {info['outliers']:3d} outliers), refitted tree {m['tree']:7.3f} ms, fresh grid "
+                f"{m['fresh']:7.3f} ms ({fresh_info['registrations']} registrations, {fresh_info['outliers']} outliers); regridded / tree "
+                f"{m['regridded'] / m['tree']:5.2f}, regridded / fresh {m['regridded'] / m['fresh']:5.2f}; pixels and rays {'equal' if same else 'DIFFER'}")
+        regridded.close(), tree.close(), fresh.close()
+        os.makedirs(os.path.dirname(os.path.abspath(args.regrid_out)), exist_ok=True)
+        with open(args.regrid_out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+    if args.section in ("g", "h"):
+        section_g() if args.section == "g" else section_h()
         hf.close()
         return
 
