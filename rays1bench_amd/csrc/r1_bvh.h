@@ -4,6 +4,7 @@
 #define R1_BVH_H
 
 #include <stdint.h>
+#include <string.h>
 
 #include <vector>
 
@@ -38,6 +39,16 @@ struct R1RefitTopo
     std::vector<uint32_t> height_off; // [heights + 1] by_height[height_off[h] .. height_off[h + 1]) are the nodes of height h
 };
 
+// R1RefitTopo's tables behind the scene -> active map in one array of words, as the device holds them (r1_context refit_tab); off[k]: where
+// scene_to_active, slot, leaf_ref, child_box, by_height begin
+inline void r1_refit_pack(const std::vector<uint32_t> &scene_to_active, const R1RefitTopo &t, std::vector<uint32_t> &tab, size_t off[5])
+{
+    const std::vector<uint32_t> *parts[5] = {&scene_to_active, &t.slot, &t.leaf_ref, &t.child_box, &t.by_height};
+    tab.clear();
+    for (int k = 0; k < 5; ++k)
+        off[k] = tab.size(), tab.insert(tab.end(), parts[k]->begin(), parts[k]->end());
+}
+
 // What a re-sort needs besides the tree and the refit's tables (r1_bvh_sort.h): topology too.  Positions 0 .. M are the movable
 // slots in ascending slot order; a splitting node is an inner node whose two children both hold movable slots.
 struct R1SortTopo
@@ -48,6 +59,20 @@ struct R1SortTopo
     std::vector<uint32_t> depth_off; // [depths + 1] seg[depth_off[d] .. depth_off[d + 1]) are depth d's
     std::vector<uint32_t> pos_seg;   // [depths][M] the index in `seg` of depth d's node that holds position p, or R1S_NONE
 };
+
+// R1SortTopo's tables in one array of words, as the device holds them (r1_context sort_tab); off[k]: where mov, mslot, seg (3 words each), pos_seg begin
+inline void r1_sort_pack(const R1SortTopo &s, std::vector<uint32_t> &tab, size_t off[4])
+{
+    const size_t m = s.mov.size();
+    off[0] = 0, off[1] = m, off[2] = 2 * m, off[3] = 2 * m + 3 * s.seg.size();
+    tab.assign(off[3] + s.pos_seg.size(), 0u);
+    if (m)
+        memcpy(&tab[off[0]], s.mov.data(), m * 4), memcpy(&tab[off[1]], s.mslot.data(), m * 4);
+    if (!s.seg.empty())
+        memcpy(&tab[off[2]], s.seg.data(), s.seg.size() * sizeof(R1SortSeg));
+    if (!s.pos_seg.empty())
+        memcpy(&tab[off[3]], s.pos_seg.data(), s.pos_seg.size() * 4);
+}
 
 void r1_build_bvh(uint32_t na, const float *cx, const float *cy, const float *cz, const float *rsq, const double *rbound, int leaf_max, R1Bvh &out);
 int r1_active_spheres(const r1_scene *s, std::vector<uint32_t> &active_to_scene); // inv_radius != 0, finite

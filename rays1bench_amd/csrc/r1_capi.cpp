@@ -1,6 +1,6 @@
 // r1_capi.cpp — the C-ABI of include/rays1.h on top of the HIP runtime: errors, the context's life, timing and what the last launch
-// left to read.  Host code only.  The scene upload is r1_scene.cpp, a frame's steps r1_frame.cpp, the render entry points r1_render.cpp,
-// the ray queries r1_queries.cpp (the trace kernel lives in r1_trace.hpp).
+// left to read.  Host code only.  The scene upload is r1_scene.cpp (its edits r1_scene_update.cpp, its grid r1_scene_grid.cpp), a frame's
+// steps r1_frame.cpp, the render entry points r1_render.cpp, the ray queries r1_queries.cpp (the trace kernel lives in r1_trace.hpp).
 //
 // There is no CPU fallback anywhere in these files: without a HIP device every compute entry point returns R1_ENODEVICE / R1_EHIP.
 

@@ -1,6 +1,7 @@
 // r1_context.h — what the files that implement the C-ABI on the HIP runtime share: the context, its device buffers, and the steps that
-// one of them defines and another calls.  Private to r1_capi.cpp (context, errors, timing), r1_scene.cpp (scene upload, moving spheres),
-// r1_frame.cpp (one frame, step by step), r1_render.cpp (the render entry points) and r1_queries.cpp (ray and path queries); C-linkage functions
+// one of them defines and another calls.  Private to r1_capi.cpp (context, errors, timing), r1_scene.cpp (scene upload),
+// r1_scene_update.cpp (moving spheres, sphere updates, re-sort), r1_scene_grid.cpp (the grid's upload, regrid), r1_frame.cpp (one frame,
+// step by step), r1_render.cpp (the render entry points) and r1_queries.cpp (ray and path queries); C-linkage functions
 // shared between files stay in r1_internal.h.
 #ifndef R1_CONTEXT_H
 #define R1_CONTEXT_H
@@ -230,6 +231,11 @@ int land_check(r1_context *c);
 
 // r1_scene.cpp
 R1DeviceCamera device_camera(const r1_camera &cam); // what the kernels read of a camera
+// R1_OK, or the refusal (error text set, in `who`'s name) of a null context, of a null `arg` where the call names one, of a context without a scene
+int need_scene(const char *who, const r1_context *c, const char *arg_name = nullptr, const void *arg = nullptr);
+void forget_occupancy(r1_context *c);               // the cached blocks per CU of the trace and query kernels: their LDS footprint has changed
+
+// r1_scene_grid.cpp
 int ensure_grid(r1_context *c);                     // R1_VARIANT_GRID: the grid of the context's scene, built and uploaded once per scene
 
 // r1_frame.cpp

@@ -1,4 +1,4 @@
-// r1_grid.h — the uniform grid of R1_VARIANT_GRID on the host (built by r1_grid.cpp, uploaded by r1_scene.cpp ensure_grid).
+// r1_grid.h — the uniform grid of R1_VARIANT_GRID on the host (built by r1_grid.cpp, uploaded by r1_scene_grid.cpp ensure_grid).
 #ifndef R1_GRID_H
 #define R1_GRID_H
 

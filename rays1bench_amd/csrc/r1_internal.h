@@ -15,6 +15,7 @@ struct R1RefitArgs; // r1_bvh_fill.h
 struct R1SetArgs;
 struct R1SortArgs; // r1_bvh_sort.h
 struct R1RegridArgs; // r1_grid_fill.h
+struct R1RadixArgs; // r1_device_sort.h
 
 // what r1_sweep_describe says of the sweep's tables besides the arrays
 struct r1_sweep_info
@@ -87,12 +88,15 @@ hipError_t r1_launch_refit(const R1RefitArgs *a, const uint32_t *height_off, uin
 
 // r1_resort.hip: the kernels of r1_resort_spheres
 hipError_t r1_launch_resort(const R1SortArgs *a, const uint32_t *depth_off, uint32_t depths, hipStream_t stream);
-size_t r1_sort_sums_words(size_t n); // words of block sums its prefix sum over n items needs
-void r1_scan_enqueue(uint32_t *data, uint32_t n, uint32_t *sums, hipStream_t stream); // exclusive prefix sum of data[0, n) in place, three launches per level
 
 // r1_regrid.hip: the kernels of r1_regrid
 hipError_t r1_launch_regrid(const R1RegridArgs *a, hipStream_t stream);
-size_t r1_regrid_blocks(size_t n); // workgroups of n items
+
+// r1_device_sort.hip: the prefix sum and the radix sort of both (r1_device_sort.h has the sizes of their scratch)
+// exclusive prefix sum of data[0, n) in place, three launches per level; sums: r1_scan_sums_words(n) words of scratch
+void r1_scan_enqueue(uint32_t *data, uint32_t n, uint32_t *sums, hipStream_t stream);
+// every list of *a sorted by its keys, 8 bits a pass for as long as top_key (no key is larger) has bits left; returns which of the two buffers holds the result
+int r1_radix_sort_enqueue(const R1RadixArgs *a, uint32_t top_key, hipStream_t stream);
 }
 
 #endif

@@ -9,19 +9,14 @@
 //   5. sort the pairs by cell: a stable LSD radix sort, as many 8-bit passes as the cell index needs — ids ascend within a cell;
 //   6. write back: a cell's start by binary search in the sorted keys, the ids, zeros behind them; 32-bit table and (small form) 16-bit.
 //
-// Every hand-over between workgroups is a KERNEL BOUNDARY, as in r1_refit.hip and r1_resort.hip and for their reason (§4.10): no look-back,
-// no arrival counter, no lane ever waits for another workgroup's store; no atomics.  The pair count lives in device memory only: every
-// kernel behind step 3 is launched for the capacity and reads the count (0 on overflow) — nothing is read back, nothing is written past
-// the capacity.  One lane per item, vector stores, plain HIP C++; nothing here is near a trace kernel.
+// Every hand-over between workgroups is a KERNEL BOUNDARY: the rule at the top of r1_device_sort.hip, whose prefix sum and radix sort these
+// steps use.  The pair count lives in device memory only: every kernel behind step 3 is launched for the capacity and reads the count (0 on
+// overflow) — nothing is read back, nothing is written past the capacity.  One lane per item, vector stores, plain HIP C++.
 #include <hip/hip_runtime.h>
 
+#include "r1_device_sort.h"
 #include "r1_grid_fill.h"
 #include "r1_internal.h"
-
-#define R1_REGRID_BLOCK 256 // lanes per workgroup = items per workgroup, in every kernel here: tests/test_gpu_regrid.py counts with it
-
-static inline unsigned regrid_blocks(size_t n) { return (unsigned)((n + R1_REGRID_BLOCK - 1) / R1_REGRID_BLOCK); }
-extern "C" size_t r1_regrid_blocks(size_t n) { return regrid_blocks(n); }
 
 // the workgroup's minimum (is_min) or maximum of one value per lane, in every lane
 __device__ inline double block_extreme(double v, bool is_min, double *sh)
@@ -29,7 +24,7 @@ __device__ inline double block_extreme(double v, bool is_min, double *sh)
     const uint32_t t = threadIdx.x;
     sh[t] = v;
     __syncthreads();
-    for (uint32_t off = R1_REGRID_BLOCK / 2; off > 0; off >>= 1)
+    for (uint32_t off = R1_SORT_BLOCK / 2; off > 0; off >>= 1)
     {
         if (t < off)
         {
@@ -57,10 +52,10 @@ __device__ inline void block_extent(R1GridExtent &e, double *sh)
 // ---- 1. classify ---------------------------------------------------------------------------------------------------------------------------
 
 // one lane per active sphere and one behind the last (entry na of span and oflag: 0, the prefix sums' total goes there)
-__global__ void __launch_bounds__(R1_REGRID_BLOCK) r1_regrid_classify_kernel(R1RegridArgs A)
+__global__ void __launch_bounds__(R1_SORT_BLOCK) r1_regrid_classify_kernel(R1RegridArgs A)
 {
-    __shared__ double sh[R1_REGRID_BLOCK];
-    const uint32_t i = blockIdx.x * R1_REGRID_BLOCK + threadIdx.x;
+    __shared__ double sh[R1_SORT_BLOCK];
+    const uint32_t i = blockIdx.x * R1_SORT_BLOCK + threadIdx.x;
     R1GridExtent e;
     e.clear();
     if (i <= A.na)
@@ -96,12 +91,12 @@ __device__ inline void put_geometry(R1GridArgs *g, const float lo[3], const floa
 }
 
 // one workgroup: the `blocks` extents of step 1 merged; lane 0 writes the geometry into both R1GridArgs
-__global__ void __launch_bounds__(R1_REGRID_BLOCK) r1_regrid_geometry_kernel(R1RegridArgs A, uint32_t blocks)
+__global__ void __launch_bounds__(R1_SORT_BLOCK) r1_regrid_geometry_kernel(R1RegridArgs A, uint32_t blocks)
 {
-    __shared__ double sh[R1_REGRID_BLOCK];
+    __shared__ double sh[R1_SORT_BLOCK];
     R1GridExtent e;
     e.clear();
-    for (uint32_t b = threadIdx.x; b < blocks; b += R1_REGRID_BLOCK)
+    for (uint32_t b = threadIdx.x; b < blocks; b += R1_SORT_BLOCK)
     {
         const double *p = A.part + (size_t)R1GF_EXTENT_WORDS * b;
         R1GridExtent o;
@@ -122,7 +117,7 @@ __global__ void __launch_bounds__(R1_REGRID_BLOCK) r1_regrid_geometry_kernel(R1R
 // ---- 3. the totals -----------------------------------------------------------------------------------------------------------------------------
 
 // one lane: behind the prefix sums.  The pair count every later kernel works with, n_out and v2
-__global__ void __launch_bounds__(R1_REGRID_BLOCK) r1_regrid_total_kernel(R1RegridArgs A)
+__global__ void __launch_bounds__(R1_SORT_BLOCK) r1_regrid_total_kernel(R1RegridArgs A)
 {
     if (blockIdx.x != 0 || threadIdx.x != 0)
         return;
@@ -142,9 +137,9 @@ __global__ void __launch_bounds__(R1_REGRID_BLOCK) r1_regrid_total_kernel(R1Regr
 // ---- 4. emit -----------------------------------------------------------------------------------------------------------------------------------
 
 // one lane per active sphere: its pairs at its offset (its cells again: the count is the first pass's), its place in the outlier list
-__global__ void __launch_bounds__(R1_REGRID_BLOCK) r1_regrid_emit_kernel(R1RegridArgs A)
+__global__ void __launch_bounds__(R1_SORT_BLOCK) r1_regrid_emit_kernel(R1RegridArgs A)
 {
-    const uint32_t i = blockIdx.x * R1_REGRID_BLOCK + threadIdx.x;
+    const uint32_t i = blockIdx.x * R1_SORT_BLOCK + threadIdx.x;
     if (i >= A.na)
         return;
     const uint32_t at = A.span[i], n = A.span[i + 1u] - at;
@@ -159,52 +154,13 @@ __global__ void __launch_bounds__(R1_REGRID_BLOCK) r1_regrid_emit_kernel(R1Regri
         A.outliers[o] = i;
 }
 
-// ---- 5. the sort ---------------------------------------------------------------------------------------------------------------------------------
-
-// hist[digit * blocks + block] = how many of the block's keys have that digit: lane t counts digit t (no atomics)
-__global__ void __launch_bounds__(R1_REGRID_BLOCK) r1_regrid_hist_kernel(R1RegridArgs A, int from, uint32_t shift)
-{
-    __shared__ uint32_t digit[R1_REGRID_BLOCK];
-    const uint32_t t = threadIdx.x, i = blockIdx.x * R1_REGRID_BLOCK + t, n = A.stat[R1GF_STAT_PAIRS];
-    digit[t] = i < n ? (A.key[from][i] >> shift) & 255u : 256u; // (256: a lane behind the last key, no digit)
-    __syncthreads();
-    uint32_t count = 0u;
-    for (uint32_t u = 0; u < R1_REGRID_BLOCK; ++u)
-        count += digit[u] == t ? 1u : 0u;
-    A.hist[t * gridDim.x + blockIdx.x] = count;
-}
-
-// hist holds its own exclusive prefix sum: where the block's first key of each digit goes; the keys of one digit keep their order within
-// the block (the lanes in front with the same digit are counted): a stable pass
-__global__ void __launch_bounds__(R1_REGRID_BLOCK) r1_regrid_scatter_kernel(R1RegridArgs A, int from, uint32_t shift)
-{
-    __shared__ uint32_t digit[R1_REGRID_BLOCK];
-    const uint32_t t = threadIdx.x, i = blockIdx.x * R1_REGRID_BLOCK + t, n = A.stat[R1GF_STAT_PAIRS];
-    uint32_t key = 0u, d = 256u;
-    if (i < n)
-        key = A.key[from][i], d = (key >> shift) & 255u;
-    digit[t] = d;
-    __syncthreads();
-    if (i >= n)
-        return;
-    uint32_t rank = 0u;
-    for (uint32_t u = 0; u < t; ++u)
-        rank += digit[u] == d ? 1u : 0u;
-    const uint32_t dest = A.hist[d * gridDim.x + blockIdx.x] + rank;
-    if (dest < A.cap) // (always: the counts sum to n <= cap)
-    {
-        A.key[1 - from][dest] = key;
-        A.val[1 - from][dest] = A.val[from][i];
-    }
-}
-
 // ---- 6. write-back -------------------------------------------------------------------------------------------------------------------------------
 
 // one lane per table entry: cell q's start = the first sorted pair whose cell is >= q (entry cells: the pair count); then the ids, zeros behind
 // them up to the capacity and (16-bit table) to the end of its last 16-byte row
-__global__ void __launch_bounds__(R1_REGRID_BLOCK) r1_regrid_write_kernel(R1RegridArgs A, int cur)
+__global__ void __launch_bounds__(R1_SORT_BLOCK) r1_regrid_write_kernel(R1RegridArgs A, int cur)
 {
-    const uint32_t idx = blockIdx.x * R1_REGRID_BLOCK + threadIdx.x, n = A.stat[R1GF_STAT_PAIRS], n_start = A.plan.n_start, words = n_start + A.cap;
+    const uint32_t idx = blockIdx.x * R1_SORT_BLOCK + threadIdx.x, n = A.stat[R1GF_STAT_PAIRS], n_start = A.plan.n_start, words = n_start + A.cap;
     uint32_t v = 0u;
     if (idx < n_start)
     {
@@ -234,22 +190,17 @@ __global__ void __launch_bounds__(R1_REGRID_BLOCK) r1_regrid_write_kernel(R1Regr
 // a->na > 0.  Everything on `stream`, nothing waited for.
 extern "C" hipError_t r1_launch_regrid(const R1RegridArgs *a, hipStream_t stream)
 {
-    const unsigned nb = regrid_blocks((size_t)a->na + 1u), nbc = regrid_blocks(a->cap);
-    hipLaunchKernelGGL(r1_regrid_classify_kernel, dim3(nb), dim3(R1_REGRID_BLOCK), 0, stream, *a);
-    hipLaunchKernelGGL(r1_regrid_geometry_kernel, dim3(1), dim3(R1_REGRID_BLOCK), 0, stream, *a, (uint32_t)nb);
+    const unsigned nb = r1_blocks((size_t)a->na + 1u);
+    hipLaunchKernelGGL(r1_regrid_classify_kernel, dim3(nb), dim3(R1_SORT_BLOCK), 0, stream, *a);
+    hipLaunchKernelGGL(r1_regrid_geometry_kernel, dim3(1), dim3(R1_SORT_BLOCK), 0, stream, *a, (uint32_t)nb);
     r1_scan_enqueue(a->span, a->na + 1u, a->sums, stream);
     r1_scan_enqueue(a->oflag, a->na + 1u, a->sums, stream);
-    hipLaunchKernelGGL(r1_regrid_total_kernel, dim3(1), dim3(R1_REGRID_BLOCK), 0, stream, *a);
-    hipLaunchKernelGGL(r1_regrid_emit_kernel, dim3(regrid_blocks(a->na)), dim3(R1_REGRID_BLOCK), 0, stream, *a);
-    int cur = 0;
-    const uint32_t top = a->plan.n_start - 2u; // the largest cell index (n_start = cells + 1 >= 2)
-    for (uint32_t shift = 0; shift == 0 || (shift < 32u && (top >> shift)); shift += 8u, cur ^= 1)
-    {
-        hipLaunchKernelGGL(r1_regrid_hist_kernel, dim3(nbc), dim3(R1_REGRID_BLOCK), 0, stream, *a, cur, shift);
-        r1_scan_enqueue(a->hist, 256u * nbc, a->sums, stream);
-        hipLaunchKernelGGL(r1_regrid_scatter_kernel, dim3(nbc), dim3(R1_REGRID_BLOCK), 0, stream, *a, cur, shift);
-    }
+    hipLaunchKernelGGL(r1_regrid_total_kernel, dim3(1), dim3(R1_SORT_BLOCK), 0, stream, *a);
+    hipLaunchKernelGGL(r1_regrid_emit_kernel, dim3(r1_blocks(a->na)), dim3(R1_SORT_BLOCK), 0, stream, *a);
+    // 5. the sort: the device's count of pairs, keys up to the largest cell index (n_start = cells + 1 >= 2)
+    const R1RadixArgs pairs = {{a->key[0], a->key[1]}, {a->val[0], a->val[1]}, a->hist, a->sums, a->cap, 1u, a->stat + R1GF_STAT_PAIRS};
+    const int cur = r1_radix_sort_enqueue(&pairs, a->plan.n_start - 2u, stream);
     const size_t entries = a->small && a->tab16_halves > a->plan.n_start + a->cap ? a->tab16_halves : (size_t)a->plan.n_start + a->cap;
-    hipLaunchKernelGGL(r1_regrid_write_kernel, dim3(regrid_blocks(entries)), dim3(R1_REGRID_BLOCK), 0, stream, *a, cur);
+    hipLaunchKernelGGL(r1_regrid_write_kernel, dim3(r1_blocks(entries)), dim3(R1_SORT_BLOCK), 0, stream, *a, cur);
     return hipGetLastError();
 }

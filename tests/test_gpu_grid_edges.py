@@ -39,7 +39,7 @@ def unit(v):
 
 
 def halves(cs):
-    """16-bit entries the small-scene grid kernel would keep in LDS: cell starts + registrations (r1_scene.cpp ensure_grid)."""
+    """16-bit entries the small-scene grid kernel would keep in LDS: cell starts + registrations (r1_scene_grid.cpp ensure_grid)."""
     info, start, ids, outl = binding.grid_describe(cs)
     return len(start) + info["registrations"]
 

@@ -13,15 +13,17 @@ from test_refit_host import MOVES, edge_scene, lattice_of, make_scene, moved_cen
 
 pytestmark = pytest.mark.gpu
 
-# The kernels of r1_regrid.hip work in blocks of 256 lanes, one item per lane (R1_REGRID_BLOCK), and their prefix sums are r1_resort.hip's
-# three-launch form, which recurses where the block sums exceed a block.  With N active spheres, a plan of R registrations, capacity
-# C = 2 R + 64 and P pairs:
+# The kernels of r1_regrid.hip work in blocks of 256 lanes, one item per lane (R1_SORT_BLOCK, r1_device_sort.h), and their prefix sums and
+# their radix sort are r1_device_sort.hip's: the three-launch prefix sum, which recurses where the block sums exceed a block, and one 8-bit
+# pass per byte of the largest cell index, the result in the buffer the parity of the passes picks.  With N active spheres, a plan of R
+# registrations, capacity C = 2 R + 64 and P pairs:
 #   classify and the two prefix sums run over N + 1 items:  one block while N <= 255, two from N = 256; emit runs over N: two from N = 257;
 #                                                           a second level of the prefix sum from N + 1 > 65 536;
 #   the radix sort's histogram has 256 x ceil(C / 256) entries: its prefix sum has a second level from C > 65 536;
-#   the sort's blocks of pairs: one while P <= 256.
+#   the sort's blocks of pairs: one while P <= 256;
+#   the sort's passes: one while the largest cell index is below 256, two below 65 536, three from there.
 # The cases: raw lattices of 255 / 256 / 257 spheres; small (N = 4), large (484) and grid40x30 (1204, the big form); grid300x220 (66 004
-# spheres, C = 768 744, P > 65 536: the second level of every prefix sum) — asserted in test_the_cases_cover_the_block_and_scan_edges.
+# spheres, C = 768 744, P > 65 536: the second level of every prefix sum; small, large and it: one, two and three passes) — asserted in test_the_cases_cover_the_block_and_scan_edges.
 BLOCK = 256
 LEVELS = (BLOCK - 1, BLOCK, BLOCK * BLOCK)  # N: one block of classify | two; of emit | two; items of one prefix-sum level
 FRAME = (96, 64, 4)
@@ -120,13 +122,18 @@ def test_the_cases_cover_the_block_and_scan_edges(scenes):
     assert n["grid40x30"] > 1023                                             # more than R1_MAX_ACTIVE_10BIT: the big form
     assert n["grid40x30"] + 1 <= LEVELS[2] < n[BIG] + 1                      # the spheres' prefix sums: the second level
     sc, a = scenes[BIG]
-    built = binding.grid_describe(sc.spheres.contents)[0]
-    assert 2 * built["registrations"] + 64 > LEVELS[2]                       # the histogram's prefix sum: the second level
+    built = {name: binding.grid_describe(s.spheres.contents) for name, (s, arrays) in scenes.items()}
+    assert 2 * built[BIG][0]["registrations"] + 64 > LEVELS[2]               # the histogram's prefix sum: the second level
     x, y, z = moved_centres(a, "lift")
     assert binding.regrid_describe(sc.spheres.contents, x, y, z)[0]["registrations"] > 65536
     for k in (LEVELS[0], LEVELS[1], LEVELS[1] + 1):
         cs, arrs, mt = lattice_256(k)
-        assert binding.grid_describe(cs)[0]["spheres"] == k
+        built[k] = binding.grid_describe(cs)
+        assert built[k][0]["spheres"] == k
+    top = {name: len(start) - 2 for name, (info, start, ids, outliers) in built.items()}    # the largest cell index: the sort's passes
+    assert min(top.values()) >= 0, top
+    for lo, hi in ((0, 256), (256, 65536), (65536, 1 << 32)):                # one pass, two, three: the result in buffer 1, 0, 1
+        assert any(lo <= t < hi for t in top.values()), (lo, hi, top)
 
 
 # ---- equals a fresh build; device equals host ---------------------------------------------------------------------------------------------

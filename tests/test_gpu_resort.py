@@ -15,8 +15,8 @@ from test_refit_host import edge_scene, lattice_of, moved_centres, raw_from_arra
 
 pytestmark = pytest.mark.gpu
 
-# The kernels of r1_resort.hip work in blocks of 256 lanes, one item per lane (R1_SORT_BLOCK), and their prefix sum is the three-launch form
-# that recurses where the block sums exceed a block.  With M movable spheres:
+# The kernels of r1_resort.hip work in blocks of 256 lanes, one item per lane (R1_SORT_BLOCK, r1_device_sort.h), and their prefix sum and
+# their radix sort are r1_device_sort.hip's: the three-launch form that recurses where the block sums exceed a block.  With M movable spheres:
 #   the flags' prefix sum runs over 3 M items:   one block alone while 3 M <= 256      (M <= 85),
 #                                                a second level from               M = 86,
 #                                                a third level from 3 M > 65 536:  M = 21 846;
