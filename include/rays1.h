@@ -287,9 +287,9 @@ int r1_tables_download(r1_context *ctx, float *exact, float *shade, uint32_t *ma
  *                shard's tiles are written, other bytes are left untouched.
  *   num_rays_out number of color() invocations (rayweek1.cpp:517) of this shard.
  *   device_seconds_out  (optional) GPU time of the kernels, from HIP events.
- * The frame is ONE launch: the trace kernel resolves each 32 x 32 tile as soon as its samples are complete
- * (rayweek1.cpp:762-775 resolves a pixel where it traced it).  If rgb_out is page-locked memory (r1_host_alloc) the
- * tiles are stored straight into it and nothing is copied; any other memory receives one copy of the finished image. */
+ * A trace launch that lands its tiles itself (from this call: the big-scene kernels) resolves each 32 x 32 tile as soon as its
+ * samples are complete and, where rgb_out is page-locked memory (r1_host_alloc), stores it straight into rgb_out.  Every other frame is trace +
+ * resolve + ONE copy of the finished image, which page-locked memory only makes faster. */
 int r1_render(r1_context *ctx, const r1_params *params, uint8_t *rgb_out, uint64_t *num_rays_out,
               double *device_seconds_out);
 

@@ -441,7 +441,7 @@ def test_one_device_multi_renderer_set_camera(renderer):
 # ---- the drop-in program --------------------------------------------------------------------------------------------------------------
 
 
-def test_program_orbit_option(tmp_path):
+def test_program_orbit_option(renderer, tmp_path):
     exe = os.path.join(ROOT, "rays1bench_amd", "lib", "rayweek1_hip")
     w, h, spp = 160, 96, 3
     out = subprocess.run([exe, "--orbit", "6", "--inflight", "2", "-n", "1", "-w", "--width", str(w), "--height", str(h), "--spp", str(spp)],
@@ -456,6 +456,12 @@ def test_program_orbit_option(tmp_path):
         assert first == (tmp_path / f"out_{name}.tga").read_bytes(), name  # angle 0 is the scene's own camera, bit for bit
         middle = (tmp_path / f"orbit_{name}_003.tga").read_bytes()
         assert len(middle) == len(first) and middle != first, name
+        sc = {"small": r1.create_small_scene, "medium": r1.create_medium_scene, "large": r1.create_large_scene}[name](w, h)
+        renderer.set_scene(sc)
+        renderer.set_camera(binding.orbit_cameras(sc, 6)[3])
+        want = tmp_path / f"want_{name}_003.tga"
+        binding.tga_write_rgb24(str(want), w, h, renderer.render(params(w, h, spp, 10001))[0])
+        assert middle == want.read_bytes(), (name, "frame 3 is the frame through orbit_cameras(scene, 6)[3]")
     assert sorted(f.name for f in tmp_path.iterdir() if f.name.startswith("orbit_")) == sorted(
         f"orbit_{n}_{k}.tga" for n in ("small", "medium", "large") for k in ("000", "003"))
     # without the flag the program prints no such line

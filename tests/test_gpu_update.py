@@ -2,6 +2,7 @@
 the box tree on the device.  The contract: every render and ray query afterwards gives, byte for byte and ray for ray, what a FRESH context
 gives after r1_set_scene with the moved arrays.  Nothing here has a tolerance."""
 import ctypes as C
+import math
 import os
 import re
 import subprocess
@@ -396,8 +397,35 @@ def test_state_rules(upd, fresh, scenes):
     assert info0["kernel"] == binding.VARIANT_BVH
 
 
-def test_rayweek1_hip_bounce(tmp_path):
-    """The drop-in program's --bounce: one `bounce:` line per scene, and with -w the first and the middle frame, which differ."""
+PROGRAM_SCENES = (("small", r1.create_small_scene), ("medium", r1.create_medium_scene), ("large", r1.create_large_scene))
+
+
+def program_lattice(a):
+    """The spheres rayweek1_hip's --bounce and --pulse animate, as the program picks them: the hittable spheres, stably sorted by radius_sq
+    descending, without the first four (Python's sort is stable, as std::stable_sort)."""
+    act = [i for i in range(len(a["inv_radius"])) if a["inv_radius"][i] != 0]
+    return sorted(act, key=lambda i: -float(a["radius_sq"][i]))[4:]
+
+
+def program_bounce_y(a, f, frames):
+    """center_y of frame f of --bounce FRAMES: the program's formula restated, fp64 rounded to fp32; math.sin is the C library's sin."""
+    y = a["center_y"].copy()
+    for i in program_lattice(a):
+        r = math.sqrt(float(a["radius_sq"][i]))
+        y[i] = F(float(a["center_y"][i]) + 0.5 * r * (1.0 + math.sin(2.0 * math.pi * (f / frames + (i % 8) / 8.0))))
+    return y
+
+
+def same_tga(path, w, h, img, what):
+    """The program's file at `path` equals, in bytes, `img` written by r1_tga_write_rgb24 (which swaps R and B in `img`)."""
+    want = path.with_name("want_" + path.name)
+    binding.tga_write_rgb24(str(want), w, h, img)
+    assert path.read_bytes() == want.read_bytes(), what
+
+
+def test_rayweek1_hip_bounce(upd, tmp_path):
+    """The drop-in program's --bounce: one `bounce:` line per scene, and with -w the first and the middle frame, which differ and are, in
+    bytes, what a context renders after r1_update_centers with the program's formula."""
     exe = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "rays1bench_amd", "lib", "rayweek1_hip")
     w, h, spp = 64, 48, 2
     out = subprocess.run([exe, "--bounce", "4", "-n", "1", "-w", "--width", str(w), "--height", str(h), "--spp", str(spp)], cwd=tmp_path,
@@ -411,3 +439,10 @@ def test_rayweek1_hip_bounce(tmp_path):
     assert "480 of" in lines[2]
     a, b = ((tmp_path / f"bounce_large_{f:03d}.tga").read_bytes() for f in (0, 2))
     assert len(a) == len(b) == 18 + w * h * 3 and a != b
+    for scene, make in PROGRAM_SCENES:
+        sc = make(w, h)
+        arr = sc.arrays()
+        upd.set_scene(sc)
+        for f in (0, 2):
+            upd.update_centers(0, arr["center_x"], program_bounce_y(arr, f, 4), arr["center_z"])
+            same_tga(tmp_path / f"bounce_{scene}_{f:03d}.tga", w, h, upd.render(r1.make_params(w, h, spp, 10001))[0], (scene, f))

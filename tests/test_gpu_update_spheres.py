@@ -2,6 +2,7 @@
 the box tree where a radius changed — on the device.  The contract is r1_update_centers': every render, ray query and path query afterwards
 gives, byte for byte and ray for ray, what a FRESH context gives after r1_set_scene with the edited arrays.  Nothing here has a tolerance."""
 import ctypes as C
+import math
 import os
 import re
 import subprocess
@@ -12,7 +13,8 @@ import pytest
 import rays1bench_amd as r1
 from rays1bench_amd import binding
 from test_bvh_host import F
-from test_gpu_update import CASES, MOVED_RULE, edge_arrays, edge_camera, expect_refusal, first_difference, params, same
+from test_gpu_update import (CASES, MOVED_RULE, PROGRAM_SCENES, edge_arrays, edge_camera, expect_refusal, first_difference, params, program_lattice, same,
+                             same_tga)
 from test_refit_host import edge_scene, lattice_of, raw_from_arrays
 from test_update_spheres_host import RADIUS_FAMILIES, radius_family
 
@@ -553,8 +555,28 @@ def test_state_rules(upd, fresh, scenes):
 # ---- 8: the drop-in program --------------------------------------------------------------------------------------------------------------------
 
 
-def test_rayweek1_hip_pulse(tmp_path):
-    """--pulse: one `pulse:` line per scene; with -w the first and the middle frame, which differ; the first is benchmark()'s own frame."""
+def program_pulse(a, f, frames):
+    """(radii, materials) of frame f of --pulse FRAMES for r1_update_spheres: the program's rule restated, the factors in fp64 and rounded to
+    fp32; math.sin and math.cos are the C library's.  A scale of exactly 1 keeps the scene's own radius_sq and inv_radius; otherwise the radius
+    is fp32(scale / fp64(inv_radius)), stored as r * r and 1 / r in fp32.  Material types and parameters stay."""
+    rsq, inv = a["radius_sq"].copy(), a["inv_radius"].copy()
+    alb = [a[k].copy() for k in ("albedo_r", "albedo_g", "albedo_b")]
+    t = f / frames
+    swing, mix = 0.3 * math.sin(2.0 * math.pi * t), 0.5 * (1.0 - math.cos(2.0 * math.pi * t))
+    for i in program_lattice(a):
+        scale = 1.0 + swing * math.cos(2.0 * math.pi * (i % 8) / 8.0)
+        if scale != 1.0:
+            r = F(scale / float(a["inv_radius"][i]))
+            rsq[i], inv[i] = r * r, F(1.0) / r
+        own = [float(a[k][i]) for k in ("albedo_r", "albedo_g", "albedo_b")]
+        for c in range(3):  # each channel towards the one before it: r -> g -> b -> r
+            alb[c][i] = F(own[c] + (own[(c + 2) % 3] - own[c]) * mix)
+    return (rsq, inv), (a["mat_type"], alb[0], alb[1], alb[2], a["mat_param"])
+
+
+def test_rayweek1_hip_pulse(upd, tmp_path):
+    """--pulse: one `pulse:` line per scene; with -w the first and the middle frame, which differ; the first is benchmark()'s own frame, the
+    middle one is, in bytes, what a context renders after r1_update_spheres with the program's rule."""
     exe = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "rays1bench_amd", "lib", "rayweek1_hip")
     w, h, spp = 64, 48, 2
     out = subprocess.run([exe, "--pulse", "3", "-n", "1", "-w", "--width", str(w), "--height", str(h), "--spp", str(spp)], cwd=tmp_path,
@@ -571,3 +593,9 @@ def test_rayweek1_hip_pulse(tmp_path):
         assert len(first) == len(middle) == 18 + w * h * 3
         assert (first != middle) == (scene != "small"), scene  # (the small scene has no lattice: its four spheres stay)
         assert first == (tmp_path / f"out_{scene}.tga").read_bytes(), (scene, "frame 0 of --pulse is the frame without it")
+    for scene, make in PROGRAM_SCENES:
+        sc = make(w, h)
+        radii, materials = program_pulse(sc.arrays(), 1, 3)
+        upd.set_scene(sc)
+        upd.update_spheres(0, radii=radii, materials=materials)
+        same_tga(tmp_path / f"pulse_{scene}_001.tga", w, h, upd.render(r1.make_params(w, h, spp, 10001))[0], scene)
