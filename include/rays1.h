@@ -380,6 +380,53 @@ int r1_adaptive_schedule(const r1_params *params, const r1_adaptive *opt, int32_
 int r1_render_adaptive(r1_context *ctx, const r1_params *params, const r1_adaptive *opt, uint8_t *rgb_out, uint64_t *num_rays_out,
                        r1_tile_report *tiles_out, r1_adaptive_result *result_out);
 
+/* ---- linear frames: fp32 radiance per pixel beside the 8-bit image ---- */
+
+/* The value.  For pixel (x, y), channel c and n samples: S = 0.0f, then S += radiance_c(sample s) for s = 0 .. n - 1 — plain fp32 adds
+ * in sample order, rayweek1.cpp:762, what the resolve launch does — and L = S * (float)(1.0f / n), one fp32 multiply, rayweek1.cpp:765.
+ * L is what the byte image is quantised from: (uint8)(int)(sqrtf(L) * 255.99f) equals r1_render's byte, for every pixel of every frame
+ * (r1_quantise_linear below does that step on the host).  A linear frame has the layout of rgb_out of r1_render with floats for bytes:
+ * row-major, row 0 = bottom row, three floats per pixel, width * height * 12 bytes.  Whole frames only: num_shards != 1 is R1_EINVAL in
+ * every call below.  No trace kernel differs: a frame runs the launches it always ran — its byte image goes into the context's device
+ * buffer — and one more launch sums the sample records they left (16 bytes per sample on the device, as for r1_render). */
+
+/* r1_render with a linear frame for the byte image: synchronous, every variant r1_render accepts, the same ray count, device_seconds_out
+ * with the extra launch in it.  Page-locked rgb_out (r1_host_alloc) is written by that launch itself, any other memory by one copy.
+ * Leaves a progressive accumulation alone, as r1_render does. */
+int r1_render_linear(r1_context *ctx, const r1_params *params, float *rgb_out, uint64_t *num_rays_out, double *device_seconds_out);
+
+/* r1_render_async with a linear frame: r1_render_async's rules — the throughput kernels, enqueued on `hip_stream` (NULL = the context's
+ * stream), nothing is waited for, one frame per context at a time, rgb_out and num_rays_out given together or both NULL (the frame then
+ * stays in the context's device buffers).  Page-locked memory (r1_host_alloc; num_rays_out 8-byte aligned) is written by the launches
+ * themselves, pageable memory by copies enqueued behind them; both are valid once the stream is idle.  PIXEL mode (r1_set_pixel_mode)
+ * keeps no sample records, so this call does not use it, whatever the switch says: the frame runs the record-keeping throughput kernels. */
+int r1_render_linear_async(r1_context *ctx, const r1_params *params, float *rgb_out, uint64_t *num_rays_out, void *hip_stream);
+
+/* The same frame into DEVICE memory, for a tensor that stays on the GPU: d_rgb_f32 receives width * height * 3 floats (4-byte aligned),
+ * d_num_rays one uint64 (8-byte aligned); R1_EINVAL otherwise, and nothing is enqueued.  Everything is enqueued on `hip_stream`, nothing
+ * is waited for.  PIXEL mode does not apply, as above. */
+int r1_render_linear_device(r1_context *ctx, const r1_params *params, void *d_rgb_f32, void *d_num_rays, void *hip_stream);
+
+/* The context's progressive accumulation (r1_render_pass) as a linear frame of the samples it holds; *samples_out (may be NULL) receives
+ * that count.  Synchronous.  R1_EINVAL while there is no valid accumulation (none started, or ended by r1_set_scene, r1_set_camera, an
+ * update or r1_render_adaptive).  It changes nothing: r1_render_pass(first_sample = that count) continues as before, r1_last_launch_info
+ * and r1_last_timing keep describing the last render. */
+int r1_pass_linear(r1_context *ctx, float *rgb_out, int32_t *samples_out);
+
+/* r1_render_adaptive with a linear frame: the same schedule, the same rule — which is defined on bytes —, the same reports, result and
+ * ray count; every tile's pixels equal r1_render_linear with spp = tiles_out[t].spp, cropped to the tile, bit for bit. */
+int r1_render_adaptive_linear(r1_context *ctx, const r1_params *params, const r1_adaptive *opt, float *rgb_out, uint64_t *num_rays_out,
+                              r1_tile_report *tiles_out, r1_adaptive_result *result_out);
+
+/* Host only, pure arithmetic: out[i] = (uint8_t)(int)(sqrtf(linear[i]) * 255.99f), rayweek1.cpp:766-775 for one channel, with the
+ * host's correctly rounded sqrtf.  A value whose (int) is undefined — negative (-0.0f counts as zero), NaN, infinite, or so large that
+ * the product is no int — is R1_EINVAL, and no byte is written then.  n_values == 0 is R1_OK. */
+int r1_quantise_linear(const float *linear, size_t n_values, uint8_t *out);
+
+/* The CPU form of r1_render_linear, no device: r1_camera_rays and r1_trace_rays_host for every sample, summed as above.  Slow (every ray
+ * against every sphere), meant for small frames: it is what lets the value be checked without a GPU.  num_rays_out may be NULL. */
+int r1_render_linear_host(const r1_scene *scene, const r1_camera *camera, const r1_params *params, float *rgb_out, uint64_t *num_rays_out);
+
 /* Pipelined form of r1_render — frames in flight whose results land on the HOST.  The reference times
  * dispatch -> pixels + ray count on the host (rayweek1.cpp:848 -> :891) for ONE frame and waits; a caller that
  * renders frame after frame (main's `-n` runs, rayweek1.cpp:969-984) can keep several in flight instead: the call
@@ -845,6 +892,11 @@ int r1_camera_look_at(const float lookfrom[3], const float lookat[3], const floa
  * leaves `pixels` with R and B swapped.  Returns R1_OK or R1_EINVAL if the file
  * cannot be opened. */
 int r1_tga_write_rgb24(const char *filename, int32_t width, int32_t height, uint8_t *pixels);
+
+/* Beside it, for a linear frame: a PFM file — the header "PF\n<width> <height>\n-1.0\n", then the rows from the bottom up as
+ * little-endian fp32 RGB, which is this library's row order: nothing is flipped, `pixels` is not changed.  R1_OK, or R1_EINVAL for a
+ * NULL or empty argument or a file that cannot be written. */
+int r1_pfm_write_rgb32f(const char *filename, int32_t width, int32_t height, const float *pixels);
 
 /* log_results (common.h:47-77): writes out_<scene>.txt as
  * `version|%.3fs|%llu|%0.3f mrays/s|` averaged over the runs. */

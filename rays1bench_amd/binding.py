@@ -230,6 +230,14 @@ SYMBOLS = [
     ("r1_trace_rays_device", C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     ("r1_trace_rays_host", C.c_int, [C.POINTER(CScene), C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("r1_camera_rays", C.c_int, [C.POINTER(CCamera), C.POINTER(Params), _i32p, _i32p, _i32p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    ("r1_render_linear", C.c_int, [_ctx, C.POINTER(Params), _f32p, _u64p, _dblp]),
+    ("r1_render_linear_async", C.c_int, [_ctx, C.POINTER(Params), _f32p, _u64p, C.c_void_p]),
+    ("r1_render_linear_device", C.c_int, [_ctx, C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("r1_pass_linear", C.c_int, [_ctx, _f32p, _i32p]),
+    ("r1_render_adaptive_linear", C.c_int, [_ctx, C.POINTER(Params), C.POINTER(Adaptive), _f32p, _u64p, C.POINTER(TileReport), C.POINTER(AdaptiveResult)]),
+    ("r1_quantise_linear", C.c_int, [_f32p, C.c_size_t, _u8p]),
+    ("r1_render_linear_host", C.c_int, [C.POINTER(CScene), C.POINTER(CCamera), C.POINTER(Params), _f32p, _u64p]),
+    ("r1_pfm_write_rgb32f", C.c_int, [C.c_char_p, C.c_int32, C.c_int32, _f32p]),
     ("r1_tga_write_rgb24", C.c_int, [C.c_char_p, C.c_int32, C.c_int32, _u8p]),
     ("r1_log_results", C.c_int, [C.c_char_p, C.c_char_p, _dblp, _u64p, C.c_int32]),
 ]
@@ -528,6 +536,46 @@ class Renderer:
         rays, res = C.c_uint64(), AdaptiveResult()
         _check(lib().r1_render_adaptive(self._c, C.byref(params), C.byref(opt), img.ctypes.data_as(_u8p), C.byref(rays),
                                         tiles.ctypes.data_as(C.POINTER(TileReport)), C.byref(res)))
+        return img, int(rays.value), tiles, {"samples": int(res.samples), "passes": int(res.passes), "tiles": int(res.tiles),
+                                            "tiles_settled": int(res.tiles_settled)}
+
+    def render_linear(self, params, out=None):
+        """r1_render_linear: the frame as fp32 radiance, float32 (height, width, 3) — the value r1_render's bytes are quantised from.
+        Returns (linear frame, ray count, device seconds).  `out`: a float32 array of that shape to render into."""
+        img = np.zeros((params.height, params.width, 3), np.float32) if out is None else out
+        rays, secs = C.c_uint64(), C.c_double()
+        _check(lib().r1_render_linear(self._c, C.byref(params), img.ctypes.data_as(_f32p), C.byref(rays), C.byref(secs)))
+        return img, int(rays.value), float(secs.value)
+
+    def render_linear_async(self, params, frame_ptr, rays_ptr, stream_ptr=None):
+        """r1_render_linear_async: enqueue one linear frame (throughput kernels); width * height * 3 floats land at `frame_ptr` and the
+        uint64 ray count at `rays_ptr` (host addresses: a LinearHostFrame's, or pageable memory) once the stream is idle.  Both None:
+        the frame stays on the device."""
+        _check(lib().r1_render_linear_async(self._c, C.byref(params), C.cast(frame_ptr, _f32p) if frame_ptr else None,
+                                            C.cast(rays_ptr, _u64p) if rays_ptr else None, _stream_arg(stream_ptr)))
+
+    def render_linear_device(self, params, d_rgb_f32_ptr, d_rays_ptr, stream_ptr=None):
+        """r1_render_linear_device: the linear frame into device memory (width * height * 3 floats, and one uint64); waits for nothing."""
+        _check(lib().r1_render_linear_device(self._c, C.byref(params), C.c_void_p(d_rgb_f32_ptr), C.c_void_p(d_rays_ptr), _stream_arg(stream_ptr)))
+
+    def pass_linear(self, params):
+        """r1_pass_linear: the progressive accumulation as a linear frame.  `params`: those of the accumulation's passes (the C call
+        keeps them; here they size the array).  Returns (float32 (height, width, 3), samples accumulated)."""
+        img = np.zeros((params.height, params.width, 3), np.float32)
+        n = C.c_int32()
+        _check(lib().r1_pass_linear(self._c, img.ctypes.data_as(_f32p), C.byref(n)))
+        return img, int(n.value)
+
+    def render_adaptive_linear(self, params, min_spp, pass_spp, max_delta, mean_delta_q8):
+        """r1_render_adaptive_linear: render_adaptive with a float32 (height, width, 3) linear frame for the byte image."""
+        img = np.zeros((params.height, params.width, 3), np.float32)
+        opt = Adaptive(min_spp, pass_spp, max_delta, mean_delta_q8)
+        total = C.c_int32()
+        _check(lib().r1_tile_count(C.byref(params), C.byref(total), None))
+        tiles = np.zeros(total.value, TILE_REPORT_DTYPE)
+        rays, res = C.c_uint64(), AdaptiveResult()
+        _check(lib().r1_render_adaptive_linear(self._c, C.byref(params), C.byref(opt), img.ctypes.data_as(_f32p), C.byref(rays),
+                                               tiles.ctypes.data_as(C.POINTER(TileReport)), C.byref(res)))
         return img, int(rays.value), tiles, {"samples": int(res.samples), "passes": int(res.passes), "tiles": int(res.tiles),
                                             "tiles_settled": int(res.tiles_settled)}
 
@@ -1038,6 +1086,69 @@ def camera_rays(ccamera, params, x, y, s):
     _check(lib().r1_camera_rays(C.byref(ccamera), C.byref(params), x.ctypes.data_as(_i32p), y.ctypes.data_as(_i32p), s.ctypes.data_as(_i32p),
                                 x.shape[0], rays.ctypes.data, seeds.ctypes.data))
     return rays, seeds
+
+
+def render_linear_host(cscene, ccamera, params):
+    """r1_render_linear_host: the linear frame on the CPU (camera_rays + trace_rays_host for every sample, summed in sample order; no
+    device; slow).  Returns (float32 (height, width, 3), ray count)."""
+    img = np.zeros((params.height, params.width, 3), np.float32)
+    rays = C.c_uint64()
+    _check(lib().r1_render_linear_host(C.byref(cscene), C.byref(ccamera), C.byref(params), img.ctypes.data_as(_f32p), C.byref(rays)))
+    return img, int(rays.value)
+
+
+def quantise_linear(linear):
+    """r1_quantise_linear: (uint8)(int)(sqrtf(v) * 255.99f) per value of a float32 array, on the host; a uint8 array of its shape."""
+    linear = np.ascontiguousarray(linear, np.float32)
+    out = np.zeros(linear.shape, np.uint8)
+    _check(lib().r1_quantise_linear(linear.ctypes.data_as(_f32p), linear.size, out.ctypes.data_as(_u8p)))
+    return out
+
+
+def pfm_write_rgb32f(filename, width, height, pixels):
+    """r1_pfm_write_rgb32f: a float32 (height, width, 3) linear frame as a PFM file (rows from the bottom up, little-endian)."""
+    pixels = np.ascontiguousarray(pixels, np.float32)
+    if pixels.size != width * height * 3:
+        raise R1Error(R1_EINVAL, "pfm_write_rgb32f: pixels must hold width * height * 3 floats")
+    _check(lib().r1_pfm_write_rgb32f(filename.encode(), width, height, pixels.ctypes.data_as(_f32p)))
+    return True
+
+
+class LinearHostFrame:
+    """Page-locked host memory (r1_host_alloc) for one linear frame: height x width x 3 floats followed by the uint64 ray count — a
+    target of Renderer.render_linear_async (frame_ptr = ptr, rays_ptr = ptr + rays_offset) that its launches write themselves."""
+
+    def __init__(self, width, height):
+        self.nbytes = width * height * 12
+        self.rays_offset = (self.nbytes + 7) & ~7
+        p = C.c_void_p()
+        _check(lib().r1_host_alloc(self.rays_offset + 8, C.byref(p)))
+        self.ptr = p.value
+        buf = (C.c_uint8 * (self.rays_offset + 8)).from_address(self.ptr)
+        self._all = np.frombuffer(buf, np.uint8)
+        self._all[:] = 0
+        self.image = self._all[:self.nbytes].view(np.float32).reshape(height, width, 3)
+        self._rays = self._all[self.rays_offset:].view(np.uint64)
+
+    @property
+    def rays_ptr(self):
+        return self.ptr + self.rays_offset
+
+    @property
+    def rays(self):
+        return int(self._rays[0])
+
+    def close(self):
+        if self.ptr:
+            self.image = self._rays = self._all = None
+            lib().r1_host_free(C.c_void_p(self.ptr))
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class RESULT:

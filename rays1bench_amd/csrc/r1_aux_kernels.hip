@@ -1,4 +1,4 @@
-// r1_aux_kernels.hip — the kernels around the trace kernel (wavefront variant, resolve, progressive accumulate, batch counts, assemble) and the launch
+// r1_aux_kernels.hip — the kernels around the trace kernel (wavefront variant, resolve, linear resolve and read-out, progressive accumulate, batch counts, assemble) and the launch
 // dispatch called from r1_frame.cpp and r1_render.cpp.  From the trace kernels' device functions it takes sweep_bvh (r1_hit_tree.hpp), start_sample,
 // path_store / path_load and quantise_pixel (r1_sample.hpp) and shade_level (r1_shade.hpp); the trace kernel itself: r1_trace.hpp.
 #include "r1_hit_tree.hpp"
@@ -180,6 +180,64 @@ __global__ void __launch_bounds__(256) r1_resolve_kernel(const R1ResolveArgs A)
             if (threadIdx.x == 0)
                 A.frame_rays[(size_t)lt_all * gridDim.x + blockIdx.x] = s_part[0] + s_part[1] + s_part[2] + s_part[3];
             __syncthreads();
+        }
+    }
+}
+
+// ============================================================================================
+// Linear frames (r1_render_linear*): one more launch behind a whole frame's trace and whatever closes it.  The resolve's
+// indexing and its sums — 0.0f plus the records' x, y, z in sample order — times inv_spp, the first line of quantise_pixel, stored as
+// three floats per pixel.  The w word is never read: a landing launch leaves its tag there.
+// ============================================================================================
+__global__ void __launch_bounds__(256) r1_resolve_linear_kernel(const R1LinearArgs A)
+{
+    const uint32_t tile_px = (uint32_t)(A.tile_w * A.tile_h);
+    for (uint32_t lt = blockIdx.y; lt < A.n_tiles; lt += gridDim.y)
+    {
+        const int x0 = (int)(lt % (uint32_t)A.tiles_x) * A.tile_w;
+        const int y0 = (int)(lt / (uint32_t)A.tiles_x) * A.tile_h;
+        const int tw = min(A.tile_w, A.width - x0);
+        const int th = min(A.tile_h, A.height - y0);
+        for (uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x; pix < tile_px; pix += gridDim.x * blockDim.x)
+        {
+            const int ly = (int)(pix / (uint32_t)A.tile_w);
+            const int lx = (int)(pix - (uint32_t)ly * (uint32_t)A.tile_w);
+            if (lx >= tw || ly >= th)
+                continue; // void slots of an edge tile
+            const float *s = (const float *)(A.samples + (size_t)lt * A.full + pix); // [tile][sample][pixel]
+            float cr = 0, cg = 0, cb = 0;
+            for (int i = 0; i < A.spp; ++i)
+            {
+                const float *v = s + (size_t)i * tile_px * 4;
+                cr += v[0], cg += v[1], cb += v[2]; // col += color(...) rayweek1.cpp:762
+            }
+            float *const o = A.out + ((size_t)(y0 + ly) * A.width + (x0 + lx)) * 3;
+            o[0] = cr * A.inv_spp, o[1] = cg * A.inv_spp, o[2] = cb * A.inv_spp; // col *= 1 / spp rayweek1.cpp:765
+        }
+    }
+}
+
+// The read-out of the accumulators (r1_pass_linear, r1_render_adaptive_linear): r1_accum_kernel's indexing over the padded [tile][pixel]
+// sums, each times (float)(1.0f / n) — n the same for every tile, or (A.report) the samples the tile's own report says it holds.
+__global__ void __launch_bounds__(256) r1_accum_linear_kernel(const R1ReadoutArgs A)
+{
+    const uint32_t tile_px = (uint32_t)(A.tile_w * A.tile_h);
+    for (uint32_t lt = blockIdx.y; lt < A.n_tiles; lt += gridDim.y)
+    {
+        const int x0 = (int)(lt % (uint32_t)A.tiles_x) * A.tile_w;
+        const int y0 = (int)(lt / (uint32_t)A.tiles_x) * A.tile_h;
+        const int tw = min(A.tile_w, A.width - x0);
+        const int th = min(A.tile_h, A.height - y0);
+        const float inv = A.report ? (float)(1.0f / A.report[lt].spp) : A.inv_n; // rayweek1.cpp:765 at the samples the sums hold
+        for (uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x; pix < tile_px; pix += gridDim.x * blockDim.x)
+        {
+            const int ly = (int)(pix / (uint32_t)A.tile_w);
+            const int lx = (int)(pix - (uint32_t)ly * (uint32_t)A.tile_w);
+            if (lx >= tw || ly >= th)
+                continue; // void slots of an edge tile
+            const float4 a = A.accum[(size_t)lt * tile_px + pix];
+            float *const o = A.out + ((size_t)(y0 + ly) * A.width + (x0 + lx)) * 3;
+            o[0] = a.x * inv, o[1] = a.y * inv, o[2] = a.z * inv;
         }
     }
 }
@@ -564,6 +622,25 @@ extern "C" hipError_t r1_launch_accum(const R1AccumArgs *args, hipStream_t strea
     const int bx = (args->tile_w * args->tile_h + 255) / 256;
     const int by = (int)(args->n_local_tiles < 65535u ? args->n_local_tiles : 65535u);
     hipLaunchKernelGGL(r1_accum_kernel, dim3(bx, by), dim3(256), 0, stream, *args);
+    return hipGetLastError();
+}
+
+// linear frames: one row of workgroups per tile (at most 65535 rows), as r1_launch_accum; a frame in flight takes the resolve's few rows
+extern "C" hipError_t r1_launch_resolve_linear(const R1LinearArgs *args, int max_rows, hipStream_t stream)
+{
+    const int bx = (args->tile_w * args->tile_h + 255) / 256;
+    int by = (int)(args->n_tiles < 65535u ? args->n_tiles : 65535u);
+    if (max_rows > 0 && by > max_rows)
+        by = max_rows;
+    hipLaunchKernelGGL(r1_resolve_linear_kernel, dim3(bx, by), dim3(256), 0, stream, *args);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t r1_launch_accum_linear(const R1ReadoutArgs *args, hipStream_t stream)
+{
+    const int bx = (args->tile_w * args->tile_h + 255) / 256;
+    const int by = (int)(args->n_tiles < 65535u ? args->n_tiles : 65535u);
+    hipLaunchKernelGGL(r1_accum_linear_kernel, dim3(bx, by), dim3(256), 0, stream, *args);
     return hipGetLastError();
 }
 

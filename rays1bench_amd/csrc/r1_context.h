@@ -158,6 +158,8 @@ struct r1_context
     DevBuf accum_even;         // [tile][pixel of the padded tile] the sums over the samples of even global index
     DevBuf adapt_list;         // two tile lists of a frame's tiles each (this pass's, the next one's), then the next one's length
     DevBuf adapt_report;       // [tile] R1TileReport
+    // linear frames (r1_render_linear*, r1_pass_linear, r1_render_adaptive_linear): `image` is sized for bytes
+    DevBuf linear;             // row-major width*height*3 floats, where the caller's memory is not the device's to write
     // ray queries (r1_cast_rays*): nothing here is read or written by a render
     DevBuf active_dev;         // active_to_scene on the device, uploaded once per r1_set_scene
     DevBuf cast_cursors;       // R1_CAST_CURSORS ray cursors, 128 bytes apart, taken in turn
@@ -224,6 +226,13 @@ struct Pass
     const r1_adaptive *rule = nullptr;
 };
 
+// A linear frame (r1_render_linear*): behind the frame's trace and whatever closes it, r1_resolve_linear_kernel sums the records
+// the trace left in the context's `samples` into `out`.  The launch keeps per-sample records: PIXEL mode is not chosen, whatever the switch says.
+struct Linear
+{
+    float *out = nullptr; // device address of width*height*3 floats, row-major (device memory, or page-locked host memory)
+};
+
 // ---- the steps that cross a file boundary ------------------------------------------------------------------------------------------------
 
 // r1_capi.cpp: a resolver of an earlier launch gave up waiting (the error of r1_sync and of the synchronous render)
@@ -243,7 +252,7 @@ bool big_scene(const r1_context *c, bool tree, bool grid, bool grid_pixel);
 void fill_scene(const r1_context *c, R1DeviceScene &s);
 void fill_walk(const r1_context *c, bool tree_lds, bool big, uint32_t top_nodes, R1TraceArgs &a);
 int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int block_layout, void *d_rays, hipStream_t st, bool throughput_mode,
-                  const Batch *batch = nullptr, Landing *landing = nullptr, const Pass *pass = nullptr);
+                  const Batch *batch = nullptr, Landing *landing = nullptr, const Pass *pass = nullptr, const Linear *linear = nullptr);
 
 #pragma GCC visibility pop
 

@@ -443,4 +443,30 @@ struct R1AdaptArgs
     uint32_t *reset;
 };
 
+// Linear frames.  r1_resolve_linear_kernel, one more launch behind a whole frame's trace and whatever closes it: the sums
+// r1_resolve_kernel takes over the records the trace left, times inv_spp, stored as fp32 — the value the byte is quantised from.
+struct R1LinearArgs
+{
+    const float4 *samples;       // [tile][sample][pixel of the padded tile]; x, y, z alone are read (a landing launch tags the w word)
+    float *out;                  // row-major width*height*3 floats
+    uint32_t full;               // tile_w * tile_h * spp
+    int32_t width, height, spp;
+    int32_t tile_w, tile_h, tiles_x;
+    uint32_t n_tiles;
+    float inv_spp;               // (float)(1.0f / spp)
+};
+
+// r1_accum_linear_kernel: the read-out of the accumulators of r1_render_pass and r1_render_adaptive, the padded [tile][pixel] layout to
+// row-major, times (float)(1.0f / n): n uniform (report == null, inv_n) or the tile's own (report[tile].spp).
+struct R1ReadoutArgs
+{
+    const float4 *accum;         // [tile][pixel of the padded tile] {r, g, b, 0}
+    const R1TileReport *report;  // [tile], or null
+    float *out;                  // row-major width*height*3 floats
+    int32_t width, height;
+    int32_t tile_w, tile_h, tiles_x;
+    uint32_t n_tiles;
+    float inv_n;                 // report == null: (float)(1.0f / n)
+};
+
 #endif

@@ -123,17 +123,19 @@ static int resolve_variant(const r1_context *c, int32_t wanted, bool throughput_
 // in latency mode, the throughput entry point with few long-lived waves per frame — per-sample records + r1_resolve_kernel either way,
 // unless r1_set_pixel_mode chose PIXEL mode for the throughput entry point (a lane owns a pixel: no sample records, no resolve launch,
 // ~10 % slower).  Refuses what is not built; changes nothing.
-static int choose_kernel(const r1_context *c, const r1_params *p, int variant, bool throughput_mode, const Batch *batch, const Pass *pass, Choice &k)
+// `records`: the caller reads the sample records afterwards (a linear frame), so PIXEL mode, which keeps none, is not chosen.
+static int choose_kernel(const r1_context *c, const r1_params *p, int variant, bool throughput_mode, const Batch *batch, const Pass *pass, bool records, Choice &k)
 {
     k.variant = variant;
     const bool wavefront = variant == R1_V_WAVEFRONT;
-    const bool big = big_scene(c, r1_is_tree(variant), r1_is_grid(variant), throughput_mode && c->pixel_mode);
+    const bool pixel_wish = throughput_mode && c->pixel_mode && !records;
+    const bool big = big_scene(c, r1_is_tree(variant), r1_is_grid(variant), pixel_wish);
     const bool frames = batch && batch->n_frames > 1; // (a batch or path of one frame: the single-frame kernel, a path's camera by value)
     static const int tp_mode_env = (int)r1_knob("R1_TP_MODE", -1); // tuning experiments: R1_MODE_TP, _LAT or _PIXEL for the throughput entry points
     int want = R1_MODE_LAT;
     if (pass)
         want = pass->list ? R1_MODE_LISTED : R1_MODE_PASS;
-    else if (throughput_mode && (c->pixel_mode || tp_mode_env == R1_MODE_PIXEL))
+    else if (pixel_wish || (throughput_mode && !records && tp_mode_env == R1_MODE_PIXEL))
         want = R1_MODE_PIXEL;
     else if (throughput_mode && !(tp_mode_env == R1_MODE_LAT && !big)) // (big scenes have no latency build: the knob leaves them alone)
         want = !frames ? R1_MODE_TP : batch->cameras ? R1_MODE_PATH : R1_MODE_BATCH;
@@ -635,10 +637,27 @@ static int close_frame(r1_context *c, const r1_params *p, const Choice &k, const
     return R1_OK;
 }
 
+// A linear frame's one more launch: the records the trace launch left, summed as the resolve sums them, into linear->out.
+// Whole single frames (the entry points see to it), so a tile of the launch is a tile of the frame.
+static int resolve_linear(const r1_context *c, const r1_params *p, int tiles_x, const Linear *linear, bool throughput_mode, hipStream_t st)
+{
+    if (!c->n_local_tiles || !c->total_samples)
+        return R1_OK;
+    R1LinearArgs l;
+    memset(&l, 0, sizeof(l));
+    l.samples = (const float4 *)c->samples.p, l.out = linear->out;
+    l.full = c->full, l.n_tiles = c->n_local_tiles;
+    l.width = p->width, l.height = p->height, l.spp = p->spp;
+    l.tile_w = p->tile_w, l.tile_h = p->tile_h, l.tiles_x = tiles_x;
+    l.inv_spp = (float)(1.0f / p->spp); // rayweek1.cpp:765
+    R1_HIP(r1_launch_resolve_linear(&l, throughput_mode ? R1_RESOLVE_ROWS_TP : 0, st));
+    return R1_OK;
+}
+
 // Enqueues the frame (trace + resolve) on `st`.  d_out / d_rays are device addresses; d_rays == NULL stands for the context's own
 // count word (R1_TAIL_RAYS of the counter allocation; the allocation may move in here, so callers take that address afterwards).
 int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int block_layout, void *d_rays, hipStream_t st,
-                         bool throughput_mode, const Batch *batch, Landing *landing, const Pass *pass)
+                         bool throughput_mode, const Batch *batch, Landing *landing, const Pass *pass, const Linear *linear)
 {
     if (!c->have_scene)
     {
@@ -663,7 +682,7 @@ int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int block_layo
     if (!d_rays) // (only now: the counter allocation may have moved)
         d_rays = counter_at(c, R1_TAIL_RAYS);
     Choice k;
-    if ((rc = choose_kernel(c, p, variant, throughput_mode, batch, pass, k)) || (rc = ensure_records(c, p, k, batch, st)))
+    if ((rc = choose_kernel(c, p, variant, throughput_mode, batch, pass, linear != nullptr, k)) || (rc = ensure_records(c, p, k, batch, st)))
         return rc;
 
     R1TraceArgs a;
@@ -696,6 +715,8 @@ int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int block_layo
     c->land_prev = k.land;
     if (k.land)
         c->land_parity = land_parity, c->land_armed = true;
+    if (linear && (rc = resolve_linear(c, p, a.tiles_x, linear, throughput_mode, st)))
+        return rc;
     R1_HIP(hipEventRecord(e[2], st));
     c->last0 = e[0], c->last1 = e[1], c->last2 = e[2];
     c->timing_valid = true;

@@ -62,6 +62,8 @@ hipError_t r1_trace_occupancy(R1Build b, size_t dyn_lds, int *blocks_per_cu);
 hipError_t r1_launch_resolve(const R1ResolveArgs *args, int max_rows, hipStream_t stream);
 hipError_t r1_launch_accum(const R1AccumArgs *args, hipStream_t stream);
 hipError_t r1_launch_adapt_accum(const R1AdaptArgs *args, hipStream_t stream);
+hipError_t r1_launch_resolve_linear(const R1LinearArgs *args, int max_rows, hipStream_t stream); // linear frames
+hipError_t r1_launch_accum_linear(const R1ReadoutArgs *args, hipStream_t stream);
 hipError_t r1_launch_adapt_compact(const uint32_t *cur, uint32_t n_cur, const R1TileReport *report, uint32_t at_cap, uint32_t *next, uint32_t *count_out,
                                    hipStream_t stream);
 hipError_t r1_launch_wavefront(R1WaveArgs *w, int blocks, hipStream_t stream);

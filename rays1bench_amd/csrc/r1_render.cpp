@@ -1,4 +1,4 @@
-// r1_render.cpp — the entry points that render: synchronous frames, progressive passes, adaptive sampling, frames in flight, batches and
+// r1_render.cpp — the entry points that render: synchronous frames, progressive passes, adaptive sampling, linear frames, frames in flight, batches and
 // camera paths, shards and their assembly.  Each checks its arguments, calls enqueue_frame (r1_frame.cpp) and brings the results home.
 
 #include <string.h>
@@ -318,12 +318,15 @@ extern "C" int r1_adaptive_schedule(const r1_params *p, const r1_adaptive *o, in
 
 static_assert(sizeof(r1_tile_report) == sizeof(R1TileReport) && sizeof(r1_tile_report) == 16 && sizeof(r1_adaptive_result) == 24, "public structs without padding; the device writes r1_tile_report's layout");
 
-extern "C" int r1_render_adaptive(r1_context *c, const r1_params *p, const r1_adaptive *opt, uint8_t *rgb_out, uint64_t *num_rays_out, r1_tile_report *tiles_out,
-                                  r1_adaptive_result *result_out)
+static int readout_linear(r1_context *c, const r1_params *p, int32_t tiles, int32_t n_uniform, bool per_tile, float *rgb_out);
+
+// r1_render_adaptive (rgb_out) and r1_render_adaptive_linear (linear_out): the passes are the same; what differs is which image goes home
+static int render_adaptive(const char *who, r1_context *c, const r1_params *p, const r1_adaptive *opt, uint8_t *rgb_out, float *linear_out, uint64_t *num_rays_out,
+                           r1_tile_report *tiles_out, r1_adaptive_result *result_out)
 {
-    if (!c || !p || !opt || !rgb_out)
+    if (!c || !p || !opt || (!rgb_out && !linear_out))
     {
-        r1_set_error("r1_render_adaptive: null argument");
+        r1_set_error("%s: null argument", who);
         return R1_EINVAL;
     }
     size_t n_pass = 0;
@@ -378,7 +381,7 @@ extern "C" int r1_render_adaptive(r1_context *c, const r1_params *p, const r1_ad
         ++passes;
         if (next > m)
         {
-            r1_set_error("r1_render_adaptive: a pass left %u active tiles of %u", next, m);
+            r1_set_error("%s: a pass left %u active tiles of %u", who, next, m);
             return R1_EHIP;
         }
         m = next;
@@ -391,7 +394,11 @@ extern "C" int r1_render_adaptive(r1_context *c, const r1_params *p, const r1_ad
         rep = local.data();
     }
     R1_HIP(hipMemcpyAsync(rep, c->adapt_report.p, (size_t)tiles * sizeof(R1TileReport), hipMemcpyDeviceToHost, c->stream));
-    R1_HIP(hipMemcpyAsync(rgb_out, c->image.p, img_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (rgb_out)
+        R1_HIP(hipMemcpyAsync(rgb_out, c->image.p, img_bytes, hipMemcpyDeviceToHost, c->stream));
+    // the linear frame: every tile's `all` sums, each scaled by the samples its own report says it holds
+    if (linear_out && (rc = readout_linear(c, p, tiles, 0, true, linear_out)))
+        return rc;
     R1_HIP(hipStreamSynchronize(c->stream));
     if (num_rays_out)
         *num_rays_out = rays_sum;
@@ -409,6 +416,195 @@ extern "C" int r1_render_adaptive(r1_context *c, const r1_params *p, const r1_ad
         result_out->passes = passes, result_out->tiles = tiles, result_out->tiles_settled = settled, result_out->reserved = 0;
     }
     return R1_OK;
+}
+
+extern "C" int r1_render_adaptive(r1_context *c, const r1_params *p, const r1_adaptive *opt, uint8_t *rgb_out, uint64_t *num_rays_out, r1_tile_report *tiles_out,
+                                  r1_adaptive_result *result_out)
+{
+    return render_adaptive("r1_render_adaptive", c, p, opt, rgb_out, nullptr, num_rays_out, tiles_out, result_out);
+}
+
+// ---- linear frames ------------------------------------------------------------------
+// The fp32 value every byte is quantised from: the pixel's sum in sample order times (float)(1.0f / n).  A whole frame is rendered as
+// always — same launches, the byte image into the context's `image` — and r1_resolve_linear_kernel follows on the records the trace left
+// (enqueue_frame's `linear`); the accumulators of a progressive or adaptive render are read out by r1_accum_linear_kernel.
+
+// what every linear render refuses before it changes or enqueues anything
+static int linear_check(const char *who, const r1_context *c, const r1_params *p)
+{
+    int rc = r1_params_check(p);
+    if (rc)
+        return rc;
+    if (p->num_shards != 1)
+    {
+        r1_set_error("%s renders whole frames (num_shards == 1, not %d)", who, p->num_shards);
+        return R1_EINVAL;
+    }
+    if (!c->have_scene)
+    {
+        r1_set_error("no scene set (call r1_set_scene first)");
+        return R1_EINVAL;
+    }
+    return R1_OK;
+}
+
+static size_t linear_bytes(const r1_params *p) { return (size_t)p->width * p->height * 3 * sizeof(float); }
+
+// Where a launch stores a linear frame meant for `rgb_out`: the caller's own memory if the device can write there (page-locked), else
+// the context's buffer, from which bring_linear enqueues the copy.
+static int linear_target(r1_context *c, const r1_params *p, float *rgb_out, Linear &lin)
+{
+    lin.out = (float *)mapped_host(rgb_out);
+    if (lin.out)
+        return R1_OK;
+    int rc = ensure(c->linear, linear_bytes(p));
+    lin.out = (float *)c->linear.p;
+    return rc;
+}
+static int bring_linear(r1_context *c, const r1_params *p, const Linear &lin, float *rgb_out, hipStream_t st)
+{
+    if (lin.out == (float *)c->linear.p)
+        R1_HIP(hipMemcpyAsync(rgb_out, c->linear.p, linear_bytes(p), hipMemcpyDeviceToHost, st));
+    return R1_OK;
+}
+
+extern "C" int r1_render_linear(r1_context *c, const r1_params *p, float *rgb_out, uint64_t *num_rays_out, double *device_seconds_out)
+{
+    if (!c || !p || !rgb_out)
+    {
+        r1_set_error("r1_render_linear: null argument");
+        return R1_EINVAL;
+    }
+    int rc = linear_check("r1_render_linear", c, p);
+    if (rc)
+        return rc;
+    R1_HIP(hipSetDevice(c->device));
+    Linear lin;
+    if ((rc = ensure(c->image, (size_t)p->width * p->height * 3 + 64)) || (rc = linear_target(c, p, rgb_out, lin)))
+        return rc;
+    const bool direct = !r1_is_stats(p->variant) && c->host_word_dev; // the ray count as r1_render brings it home
+    if ((rc = enqueue_frame(c, p, c->image.p, 0, rays_word(c, direct), c->stream, false, nullptr, nullptr, nullptr, &lin)) ||
+        (rc = bring_linear(c, p, lin, rgb_out, c->stream)))
+        return rc;
+    uint64_t rays = 0;
+    if ((rc = read_rays(c, direct, &rays)) || (rc = land_check(c)))
+        return rc;
+    if (num_rays_out)
+        *num_rays_out = rays;
+    if (device_seconds_out)
+    {
+        float ms = 0;
+        R1_HIP(hipEventElapsedTime(&ms, c->last0, c->last2)); // (the linear resolve included)
+        *device_seconds_out = ms * 1e-3;
+    }
+    return R1_OK;
+}
+
+// r1_render_async's rules.  The byte image stays in the context's device buffer; the landing of bytes into the caller's memory is not
+// used (the float frame is what the caller gave memory for), the ray count still goes straight into a page-locked word.
+extern "C" int r1_render_linear_async(r1_context *c, const r1_params *p, float *rgb_out, uint64_t *num_rays_out, void *hip_stream)
+{
+    if (!c || !p || ((rgb_out == nullptr) != (num_rays_out == nullptr)))
+    {
+        r1_set_error("r1_render_linear_async: null argument (rgb_out and num_rays_out are given together, or both NULL)");
+        return R1_EINVAL;
+    }
+    int rc = linear_check("r1_render_linear_async", c, p);
+    if (rc)
+        return rc;
+    R1_HIP(hipSetDevice(c->device));
+    Linear lin;
+    if ((rc = ensure(c->image, (size_t)p->width * p->height * 3 + 64)) || (rc = linear_target(c, p, rgb_out, lin)))
+        return rc;
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    void *d_rays = nullptr; // (the context's own count word, copied below)
+    if (num_rays_out && ((uintptr_t)num_rays_out & 7u) == 0 && !r1_is_stats(p->variant))
+        d_rays = mapped_host(num_rays_out);
+    if ((rc = enqueue_frame(c, p, c->image.p, 0, d_rays, st, true, nullptr, nullptr, nullptr, &lin)))
+        return rc;
+    if (rgb_out && (rc = bring_linear(c, p, lin, rgb_out, st)))
+        return rc;
+    if (num_rays_out && !d_rays)
+        R1_HIP(hipMemcpyAsync(num_rays_out, counter_at(c, R1_TAIL_RAYS), 8, hipMemcpyDeviceToHost, st));
+    return R1_OK;
+}
+
+extern "C" int r1_render_linear_device(r1_context *c, const r1_params *p, void *d_rgb_f32, void *d_num_rays, void *hip_stream)
+{
+    if (!c || !p || !d_rgb_f32 || !d_num_rays)
+    {
+        r1_set_error("r1_render_linear_device: null argument");
+        return R1_EINVAL;
+    }
+    if (((uintptr_t)d_rgb_f32 & 3u) || ((uintptr_t)d_num_rays & 7u))
+    {
+        r1_set_error("r1_render_linear_device: d_rgb_f32 must be 4-byte aligned and d_num_rays 8-byte aligned");
+        return R1_EINVAL;
+    }
+    int rc = linear_check("r1_render_linear_device", c, p);
+    if (rc)
+        return rc;
+    R1_HIP(hipSetDevice(c->device));
+    if ((rc = ensure(c->image, (size_t)p->width * p->height * 3 + 64)))
+        return rc;
+    Linear lin;
+    lin.out = (float *)d_rgb_f32;
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    return enqueue_frame(c, p, c->image.p, 0, d_num_rays, st, true, nullptr, nullptr, nullptr, &lin);
+}
+
+// The accumulators' read-out, then the frame on the host: `all` of r1_render_pass (n_uniform samples in every tile) or of an adaptive
+// render (per_tile: the samples of each tile's report).  Synchronous.
+static int readout_linear(r1_context *c, const r1_params *p, int32_t tiles, int32_t n_uniform, bool per_tile, float *rgb_out)
+{
+    Linear lin;
+    int rc = linear_target(c, p, rgb_out, lin);
+    if (rc)
+        return rc;
+    R1ReadoutArgs r;
+    memset(&r, 0, sizeof(r));
+    r.accum = (const float4 *)c->accum.p, r.report = per_tile ? (const R1TileReport *)c->adapt_report.p : nullptr;
+    r.out = lin.out;
+    r.width = p->width, r.height = p->height;
+    r.tile_w = p->tile_w, r.tile_h = p->tile_h, r.tiles_x = (p->width + p->tile_w - 1) / p->tile_w;
+    r.n_tiles = (uint32_t)tiles;
+    r.inv_n = per_tile ? 0.0f : (float)(1.0f / n_uniform); // rayweek1.cpp:765 at the accumulated spp
+    R1_HIP(r1_launch_accum_linear(&r, c->stream));
+    if ((rc = bring_linear(c, p, lin, rgb_out, c->stream)))
+        return rc;
+    R1_HIP(hipStreamSynchronize(c->stream));
+    return R1_OK;
+}
+
+extern "C" int r1_pass_linear(r1_context *c, float *rgb_out, int32_t *samples_out)
+{
+    if (!c || !rgb_out)
+    {
+        r1_set_error("r1_pass_linear: null argument");
+        return R1_EINVAL;
+    }
+    if (!c->pass_valid)
+    {
+        r1_set_error("r1_pass_linear: no accumulation to read (r1_render_pass starts one with first_sample 0; r1_set_scene, r1_set_camera and the updates end it)");
+        return R1_EINVAL;
+    }
+    const r1_params *p = &c->pass_key;
+    int32_t tiles = 0;
+    int rc = r1_tile_count(p, &tiles, nullptr);
+    if (rc)
+        return rc;
+    R1_HIP(hipSetDevice(c->device));
+    if ((rc = readout_linear(c, p, tiles, c->pass_samples, false, rgb_out)))
+        return rc;
+    if (samples_out)
+        *samples_out = c->pass_samples;
+    return R1_OK;
+}
+
+extern "C" int r1_render_adaptive_linear(r1_context *c, const r1_params *p, const r1_adaptive *opt, float *rgb_out, uint64_t *num_rays_out,
+                                         r1_tile_report *tiles_out, r1_adaptive_result *result_out)
+{
+    return render_adaptive("r1_render_adaptive_linear", c, p, opt, nullptr, rgb_out, num_rays_out, tiles_out, result_out);
 }
 
 // Pipelined form of r1_render (frames in flight, results on the HOST): the frame is enqueued with the throughput

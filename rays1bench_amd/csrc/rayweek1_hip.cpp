@@ -27,6 +27,8 @@
 // --adaptive MAXDELTA[,MEANQ8] [--min-spp N] [--pass-spp N] renders each frame through r1_render_adaptive: --spp is the cap, a tile stops
 // sampling once its pixels have settled (include/rays1.h); the report gains one "<scene> adaptive:" line.  MEANQ8 defaults to 65280 (no bound
 // on the mean), --min-spp and --pass-spp to 16.
+// --linear renders each frame through r1_render_linear: the fp32 frame comes home, the pixels of the TGA are r1_quantise_linear's — the bytes
+// r1_render returns — and -w also writes out_<scene>.pfm; the report gains one "<scene> linear:" line.
 // --backend hip (default) | cpu-step1 | cpu-step12: the reference's two single-thread CPU stages
 // (r1_cpu_backends.cpp) behind the same benchmark(), for the README-style table
 // (README.md:38-84).  Named backends of this program only — never a fallback: with --backend hip and no
@@ -70,6 +72,7 @@ static std::vector<r1_context *> g_ctx; // one per device in use (--gather host)
 static r1_multi *g_multi = nullptr;     // --gather rccl
 static std::vector<double> g_device_seconds; // per benchmark() call, for the JSON record
 static r1_launch_info g_last_info;
+static float *g_linear = nullptr; // --linear: the frame r1_render_linear fills (page-locked where the device allows it)
 
 r1_params frame_params()
 {
@@ -215,6 +218,13 @@ static Frame context_frame(const Scene *scene, Pix *pixels, const r1_params &p, 
                 rc = rc != R1_OK ? rc : rc2;
             }
         }
+        else if (rc == R1_OK && g_opt.linear)
+        {
+            // --linear (one device): the fp32 frame, then the bytes it quantises to
+            rc = r1_render_linear(g_ctx[i], &q, g_linear, &rays[i], &dev_s[i]);
+            if (rc == R1_OK)
+                rc = r1_quantise_linear(g_linear, (size_t)q.width * q.height * 3, &pixels[0].r);
+        }
         else if (rc == R1_OK)
             rc = r1_render(g_ctx[i], &q, &pixels[0].r, &rays[i], &dev_s[i]);
         rcs[i] = rc;
@@ -256,6 +266,16 @@ static Frame context_frame(const Scene *scene, Pix *pixels, const r1_params &p, 
         f.lines_after = line("%s adaptive: passes %d, tiles settled %d / %d, samples %llu (%.4f of cap x pixels), rays %llu (%.4f of cap x pixels)\n", scene_name,
                              adapt_res.passes, adapt_res.tiles_settled, adapt_res.tiles, (unsigned long long)adapt_res.samples,
                              (double)adapt_res.samples / (double)total_samples, (unsigned long long)f.rays, (double)f.rays / (double)total_samples);
+    if (g_opt.linear)
+    {
+        double sum = 0;
+        float top = 0;
+        const size_t n = (size_t)g_opt.width * g_opt.height * 3;
+        for (size_t k = 0; k < n; ++k)
+            sum += g_linear[k], top = g_linear[k] > top ? g_linear[k] : top;
+        f.lines_after = line("%s linear: %dx%dx3 fp32 (%.2f MB), mean %.6f, max %.6f, bytes from r1_quantise_linear\n", scene_name, g_opt.width, g_opt.height,
+                             (double)n * 4 / 1e6, sum / (double)n, (double)top);
+    }
     return f;
 }
 
@@ -296,6 +316,11 @@ RESULT benchmark(Scene *scene, Pix *pixels, bool write_tga, const char *scene_na
         char filename[128];
         snprintf(filename, sizeof(filename), "out_%s.tga", scene_name);
         r1_tga_write_rgb24(filename, g_opt.width, g_opt.height, &pixels[0].r); // swaps R/B in `pixels`, as the reference
+        if (g_opt.linear)
+        {
+            snprintf(filename, sizeof(filename), "out_%s.pfm", scene_name);
+            r1_pfm_write_rgb32f(filename, g_opt.width, g_opt.height, g_linear);
+        }
     }
     return result;
 }
@@ -373,6 +398,11 @@ int main(int argc, const char *argv[])
         if (strcmp(argv[i], "-w") == 0)
         {
             write_tga = true;
+            continue;
+        }
+        if (strcmp(argv[i], "--linear") == 0)
+        {
+            o.linear = true;
             continue;
         }
         if (i + 1 >= argc)
@@ -462,6 +492,12 @@ int main(int argc, const char *argv[])
         return 1;
     }
 
+    if (o.linear && (!one_pass || o.adaptive))
+    {
+        fprintf(stderr, "bad --linear: needs the hip backend, one device (no --gather rccl), no --passes and no --adaptive\n");
+        return 1;
+    }
+
     if ((o.pipeline > 0 || o.orbit > 0) && o.backend == 0)
     {
         // Frames in flight only overlap when their streams sit on different hardware queues; the ROCm default is 4.  One queue
@@ -516,6 +552,18 @@ int main(int argc, const char *argv[])
         pixels = new Pix[(size_t)o.width * o.height];
     memset(pixels, 0, (size_t)o.width * o.height * sizeof(pixels[0]));
 
+    bool linear_pinned = false;
+    if (o.linear)
+    {
+        void *mem = nullptr;
+        const size_t bytes = (size_t)o.width * o.height * 3 * sizeof(float);
+        if (r1_host_alloc(bytes, &mem) == R1_OK)
+            g_linear = (float *)mem, linear_pinned = true;
+        else
+            g_linear = new float[(size_t)o.width * o.height * 3];
+        memset(g_linear, 0, bytes);
+    }
+
     const char *version = o.backend == 0 ? "hip" : (o.backend == 12 ? "cpu-step12" : "cpu-step1");
     const struct
     {
@@ -548,6 +596,10 @@ int main(int argc, const char *argv[])
         r1_host_free(pixels);
     else
         delete[] pixels;
+    if (linear_pinned)
+        r1_host_free(g_linear);
+    else
+        delete[] g_linear;
     for (r1_context *c : g_ctx)
         r1_destroy(c);
     r1_multi_destroy(g_multi);

@@ -19,6 +19,7 @@ struct Options
     int passes = 0;  // --passes K: every frame in K progressive passes (r1_render_pass); 0 = one r1_render
     bool adaptive = false; // --adaptive: every frame through r1_render_adaptive
     r1_adaptive adapt = {16, 16, 0, 65280};
+    bool linear = false; // --linear: every frame through r1_render_linear, the pixels through r1_quantise_linear; -w also writes out_<scene>.pfm
     // the demos, each FRAMES frames per scene after the benchmark() runs; 0 = not asked for
     int pipeline = 0; // --pipeline: the same frame, --inflight of them in flight (r1_render_async)
     int inflight = 20;
