@@ -9,6 +9,7 @@
 
 #include "r1_device.h"
 #include "r1_grid_dda.h"
+#include "r1_offer.h"
 #include "r1_dev_math.hpp"
 #include "r1_hit_sweep.hpp"
 
@@ -39,7 +40,7 @@ __device__ __forceinline__ bool grid_trace(const R1TraceArgs &GA, R1GridCArgs *G
     {
         const uint32_t id = ((const __attribute__((address_space(4))) uint32_t *)G->outliers)[k];
         const float t = exact_offer(((cf4_ptr)GA.scene.exact)[id], o, d);
-        const bool upd = (t < FLT_MAX) & ((t < best) | ((t == best) & (id < best_id)));
+        const bool upd = (t < FLT_MAX) & r1_offer_better_form<R1_OFFER_FORM_GRID>(t, id, best, best_id); // (exact_offer: t > 0.001, or FLT_MAX)
         best = upd ? t : best;
         best_id = upd ? id : best_id;
     }
@@ -68,7 +69,7 @@ __device__ __forceinline__ bool grid_trace(const R1TraceArgs &GA, R1GridCArgs *G
         {
             const uint32_t id = SMALL ? (uint32_t)ltab[G->n_start + k] : gtab[G->n_start + k];
             const float t = exact_offer(tab[id], o, d);
-            const bool upd = (t < FLT_MAX) & ((t < best) | ((t == best) & (id < best_id)));
+            const bool upd = (t < FLT_MAX) & r1_offer_better_form<R1_OFFER_FORM_GRID>(t, id, best, best_id); // (exact_offer: t > 0.001, or FLT_MAX)
             best = upd ? t : best;
             best_id = upd ? id : best_id;
         }

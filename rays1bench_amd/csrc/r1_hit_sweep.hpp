@@ -10,6 +10,7 @@
 
 #include "r1_device.h"
 #include "r1_exact_math.h"
+#include "r1_offer.h"
 #include "r1_dev_math.hpp"
 
 #pragma clang fp contract(off)
@@ -169,7 +170,7 @@ __device__ __forceinline__ void exact_trips(const R1DeviceScene &S, const V3 o, 
         {
             const float t = exact_offer(sphere, ro, rd);
             if (t < FLT_MAX)
-                atomicMin(&best[owner], ((unsigned long long)__float_as_uint(t) << 32) | idx);
+                atomicMin(&best[owner], r1_offer_key(t, idx)); // (the rule of r1_offer_better, applied by the LDS atomic)
         }
     }
     __builtin_amdgcn_wave_barrier();
@@ -494,7 +495,7 @@ __device__ __forceinline__ void cooperative_sweep(const R1DeviceScene &S, unsign
             const float t = exact_offer(tab[i], ro, rd);
             if (t < FLT_MAX)
             {
-                const unsigned long long k = ((unsigned long long)__float_as_uint(t) << 32) | i; // t > 0: bit order = value order
+                const unsigned long long k = r1_offer_key(t, i); // t > 0: bit order = value order (r1_offer.h)
                 key = k < key ? k : key;
             }
         }

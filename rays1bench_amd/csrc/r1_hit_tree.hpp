@@ -9,6 +9,7 @@
 
 #include "r1_device.h"
 #include "r1_exact_math.h"
+#include "r1_offer.h"
 #include "r1_dev_math.hpp"
 
 #pragma clang fp contract(off)
@@ -61,6 +62,7 @@ __device__ __forceinline__ bool bvh_box(const float mx, const float my, const fl
 // the table — or, behind the last leaf, the sentinel pair r1_scene.cpp appends — and `mask` keeps those two slots from ever being flagged,
 // whatever their discriminants come out as (finite, inf, NaN).  The branch around the second fetch cost eight register copies (pair A
 // into pair B's registers), an exec-mask region and the compare in front of every leaf, on scenes whose leaves nearly all hold two pairs.
+template <int OFFER>
 __device__ __forceinline__ void leaf_quad(const float4 *__restrict__ prims, const uint32_t *__restrict__ ids, const uint32_t first,
                                           const uint32_t pairs, const V3 o, const V3 d, float &best, uint32_t &best_id)
 {
@@ -109,7 +111,7 @@ __device__ __forceinline__ void leaf_quad(const float4 *__restrict__ prims, cons
         const float t1 = n_ - root;
         const float t = (t1 > 0.001f) ? t1 : n_ + root;
         // (bitwise on purpose: && / || become nested exec-mask regions)
-        const bool upd = have & (t > 0.001f) & (t < FLT_MAX) & ((t < best) | ((t == best) & (id < best_id)));
+        const bool upd = have & r1_offer_update_form<OFFER>(t, id, best, best_id);
         best = upd ? t : best;
         best_id = upd ? id : best_id;
         flagged = __builtin_amdgcn_ballot_w64(mask != 0u);
@@ -124,6 +126,7 @@ __device__ __forceinline__ void leaf_quad(const float4 *__restrict__ prims, cons
 // against 120 + 52 t (t: the most flagged slots any lane holds) — DESIGN.md §4.26.  The offers are leaf_quad's operation for operation
 // and the slots come in index order, so the result is the same minimum offer with ties to the lowest index; an odd sphere's partner
 // (radius_sq = -inf: discriminant -inf) is never flagged, and a one-pair leaf fetches one pair.
+template <int OFFER>
 __device__ __forceinline__ void leaf_root(const float4 *__restrict__ prims, const uint32_t *__restrict__ ids, const uint32_t first,
                                           const uint32_t pairs, const V3 o, const V3 d, float &best, uint32_t &best_id)
 {
@@ -153,7 +156,7 @@ __device__ __forceinline__ void leaf_root(const float4 *__restrict__ prims, cons
                 const float root = r1_sqrt_exact_lanes(ds, any);
                 const float t1 = nb - root;
                 const float t = (t1 > 0.001f) ? t1 : nb + root;
-                const bool upd = flag & (t > 0.001f) & (t < FLT_MAX) & ((t < best) | ((t == best) & (id < best_id)));
+                const bool upd = flag & r1_offer_update_form<OFFER>(t, id, best, best_id);
                 best = upd ? t : best;
                 best_id = upd ? id : best_id;
             }
@@ -203,7 +206,8 @@ __device__ __forceinline__ void trav_start(Trav &t)
 // the vote costs ~20 VALU instructions per trip; removed in round 3)
 // LN: the node table is read from `lnodes`, the workgroup's copy in LDS (the trace kernel on small scenes), instead of S.bvh_nodes.
 // SLOTS: the root step tests its leaf with leaf_root instead of leaf_quad (r1_builds.h r1_root_by_slots: one choice per build).
-template <bool STATS, bool CARRY, bool LN, typename TS, bool SLOTS = false>
+// OFFER: the form of the closest-offer rule in the leaf tests (r1_offer.h r1_offer_better_form; the grid kernels' fallback walk passes the grid's).
+template <bool STATS, bool CARRY, bool LN, typename TS, bool SLOTS = false, int OFFER = R1_OFFER_FORM>
 __device__ __forceinline__ void bvh_advance(const R1DeviceScene &S, const V3 o, const V3 d, Trav &tv, TS *trav, const int tid,
                                             const uint32_t n_alive, unsigned long long *wstat, const float4 *lnodes /* LDS */, const uint32_t top = 0u /* !LN: nodes [0, top) are in lnodes */)
 {
@@ -352,9 +356,9 @@ __device__ __forceinline__ void bvh_advance(const R1DeviceScene &S, const V3 o, 
                 wstat[3] += 1;
         }
         if (SLOTS) // (the reference is the same LDS word for every lane: made a scalar, the compiler cannot know)
-            leaf_root(prims, ids, (uint32_t)__builtin_amdgcn_readfirstlane((int)(leaf & INDEX_MASK)), (uint32_t)__builtin_amdgcn_readfirstlane((int)lp), o, d, best, best_id);
+            leaf_root<OFFER>(prims, ids, (uint32_t)__builtin_amdgcn_readfirstlane((int)(leaf & INDEX_MASK)), (uint32_t)__builtin_amdgcn_readfirstlane((int)lp), o, d, best, best_id);
         else
-            leaf_quad(prims, ids, leaf & INDEX_MASK, lp, o, d, best, best_id);
+            leaf_quad<OFFER>(prims, ids, leaf & INDEX_MASK, lp, o, d, best, best_id);
         // (the other child's box is fetched only now: six more live registers across the leaf test spill in the 7-wave builds)
         V3 pa = pa_ray;
         if (!LN)
@@ -419,7 +423,7 @@ __device__ __forceinline__ void bvh_advance(const R1DeviceScene &S, const V3 o, 
                     if ((tid & 63) == __ffsll((long long)__ballot(1)) - 1)
                         wstat[3] += 1;
                 }
-                leaf_quad(prims, ids, first, cnt, o, d, best, best_id);
+                leaf_quad<OFFER>(prims, ids, first, cnt, o, d, best, best_id);
             }
             else
             for (uint32_t j = 0; j < cnt; j += 2u)
@@ -432,14 +436,14 @@ __device__ __forceinline__ void bvh_advance(const R1DeviceScene &S, const V3 o, 
                     if ((tid & 63) == __ffsll((long long)__ballot(1)) - 1)
                         wstat[3] += 1;
                 }
-                leaf_quad(prims, ids, first + j, take, o, d, best, best_id);
+                leaf_quad<OFFER>(prims, ids, first + j, take, o, d, best, best_id);
             }
             cur = sp > 0 ? trav_get(trav, --sp * R1_BLOCK + tid) : R1_BVH_DONE;
             if (LN && (__builtin_amdgcn_readfirstlane((int)__float_as_uint(lnodes[3].y)) & 4) != 0)
                 pa_ray.y = best < pa_ray.y ? best : pa_ray.y; // F = min(a_u + b_u, best): best has moved in the leaf, and only down
         }
     }
-    tv.cur = cur, tv.sp = sp, tv.best = best, tv.best_id = best_id;
+    tv.cur = cur, tv.sp = sp, tv.best = best, tv.best_id = r1_offer_settle_form<OFFER>(best, best_id); // (form 2: "none" again where the walk only held an offer of FLT_MAX, r1_offer.h)
 }
 
 // one complete walk (the wavefront kernels)

@@ -46,7 +46,8 @@ __device__ __forceinline__ bool query_finite(const float v) { return (__float_as
 // exact_offer), so the answer is the minimum offer, ties to the lowest index, IF it is < t_max.  The tree walk is seeded with best = t_max
 // so that it prunes what lies beyond; the walks' update rule (t < best) | (t == best & id < best_id) starts at best_id = 0xFFFFFFFF and
 // so admits an offer EQUAL to t_max — which is why every form ends in store's `best < t_max`: an admitted t == t_max is a miss, and
-// anything below it replaces it by the same rule.  The grid's walk starts at FLT_MAX and is filtered the same way; the reference form's
+// anything below it replaces it by the same rule (r1_offer.h: written as one compare of {t bits, index}; its form 2 admits a t of FLT_MAX
+// against a t_max of FLT_MAX in the same way, and bvh_advance settles that back to "none" before this store sees it).  The grid's walk starts at FLT_MAX and is filtered the same way; the reference form's
 // exact_test compares with the running t_max itself, strictly: seeded with the ray's t_max it IS rayweek1.cpp:284-314.
 // A ray with a non-finite origin or (normalised) direction, or a t_max that is NaN or <= 0.001, is a miss before any walk (load).
 struct R1CastJob
@@ -320,7 +321,7 @@ __global__ void __launch_bounds__(R1_BLOCK, JOB::waves(BIG)) r1_query_grid_kerne
                 fv.best = best, fv.best_id = best_id;
                 if (!fb)
                     fv.cur = R1_BVH_DONE;
-                bvh_advance<false, false, false, uint32_t>(A.t.scene, J.O(), J.D(), fv, s_trav, tid, 64u, nullptr, nullptr);
+                bvh_advance<false, false, false, uint32_t, false, R1_OFFER_FORM_GRID>(A.t.scene, J.O(), J.D(), fv, s_trav, tid, 64u, nullptr, nullptr);
                 best = fv.best, best_id = fv.best_id;
             }
             if ((JOB::BOUNCES ? alive : mine) && J.step(A, best_id, best, gtid, tid))

@@ -521,7 +521,7 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
                 if (!fb)
                     fv.cur = R1_BVH_DONE;
                 // (grid launches carry scene.bvh_root_leaf = 0: the walk starts at the root, which it reads from global memory)
-                bvh_advance<false, false, false, uint32_t>(HA.scene, p.o, p.d, fv, s_trav, tid, 64u, wstat, nullptr);
+                bvh_advance<false, false, false, uint32_t, false, R1_OFFER_FORM_GRID>(HA.scene, p.o, p.d, fv, s_trav, tid, 64u, wstat, nullptr);
                 best = fv.best, best_id = fv.best_id;
             }
             if (best_id != 0xFFFFFFFFu)
