@@ -738,6 +738,81 @@ int r1_trace_rays_host(const r1_scene *scene, int32_t max_bounces, const r1_ray 
 int r1_camera_rays(const r1_camera *camera, const r1_params *params, const int32_t *x, const int32_t *y, const int32_t *s, size_t n,
                    r1_ray *rays_out, r1_sample_seed *seeds_out);
 
+/* The same on the device, for a run of samples in r1_render_samples' order: for k in [first, first + n), sample s of pixel (x, y) with
+ * (y * width + x) * spp + s == k; d_rays[k - first] and d_seeds[k - first] receive, byte for byte, what r1_camera_rays writes for that
+ * sample.  camera NULL: the context's (r1_set_scene / r1_set_camera); a camera given travels by value in the launch's arguments.  Enqueues
+ * on `hip_stream` (NULL: the context's stream) and waits for nothing.  R1_EINVAL for a NULL ctx or params, an empty image, spp < 1,
+ * num_shards != 1, first + n beyond width * height * spp, no camera at all (camera NULL before the first r1_set_scene); then n == 0 is
+ * R1_OK; then R1_EINVAL for NULL or misaligned (16 bytes) d_rays / d_seeds. */
+int r1_camera_rays_device(r1_context *ctx, const r1_camera *camera, const r1_params *params, size_t first, size_t n, void *d_rays,
+                          void *d_seeds, void *hip_stream);
+
+/* ---- scatter queries: one color() level for caller-supplied rays --------------------------- */
+
+/* The level between a cast and a trace: ONE call of the reference's color() body (rayweek1.cpp:517-534) — the hit test, then
+ * Material::scatter — with the recursion left to the caller: another termination rule, per-bounce outputs, paths kept as data.  For ray i
+ * the three forms write, byte for byte alike, the record out[i], the scattered ray rays_out[i] and the advanced stream states seeds_out[i].
+ *   direction    without R1_SCATTER_UNIT_DIRECTIONS d is normalised as the Ray constructor does it (the trace forms' rule); with the flag d
+ *                is used as it is: a scattered direction IS normalised, and normalising it twice can change its last bit.  The flag is the
+ *                caller's promise that every d is a unit vector as a step wrote it (the rays_out of SCATTERED and ABSORBED records; the
+ *                zero bytes behind SKY and NONE are no ray).  For any other finite d the call still returns, but the walks are built for
+ *                unit directions and the variants need not agree.
+ *   non-finite   the ray queries' test on o and on the direction actually used.  A ray that fails it: R1_SCATTER_NONE, the record zero but
+ *                t = FLT_MAX, index = -1, mat_type = R1_MAT_NONE; rays_out[i] zero bytes; seeds_out[i] the guarded input; nothing drawn.
+ *   seeds        r1_trace_rays' rules: NULL = the seeding contract's states for (seed 0, pixel i, sample 0), i the index within the call;
+ *                r1_seed_guard on load in every form (a zero stream state never reaches random_in_unit_sphere).
+ *   walk         Hitable::hit(r, 0.001f, FLT_MAX); t_max and pad of the input are ignored.
+ *   miss         R1_SCATTER_SKY: weight = the sky's colour for the direction (rayweek1.cpp:532-534), nothing drawn, seeds_out[i] the
+ *                guarded input, rays_out[i] zero bytes.
+ *   hit          always scatters (the depth limit is the caller's): t, index (SCENE index, as r1_hit), mat_type of the sphere;
+ *                rays_out[i] = {hit point, FLT_MAX, scattered direction (unit), 0}; seeds_out[i] the states after the draws.
+ *                R1_SCATTER_ABSORBED: Metal whose scattered direction points below the surface (rayweek1.cpp:432): weight 0.
+ *                R1_SCATTER_SCATTERED: otherwise; weight = the albedo for Lambertian and Metal, exactly 1.0f for Dielectric.
+ * THE FOLD.  Run levels 0 .. B on the rays still alive: level 0 without the flag, every later level with it on the previous level's
+ * rays_out / seeds_out.  Count one ray per level whose event is not NONE.  SKY ends the path with col = weight, then col = w_e * col per
+ * channel over the SCATTERED weights of the path from the last to the first; ABSORBED ends it black; SCATTERED at level B ends it black.
+ * The result is r1_trace_rays(max_bounces = B)'s {r, g, b, rays}, bit for bit (a Dielectric's 1.0f multiplies exactly), and over
+ * r1_camera_rays' output r1_render_samples' records.
+ * Variants, refusals and argument order are the ray queries': R1_EINVAL for a NULL ctx, then for flags with unknown bits, then a variant
+ * that serves no rays, then before the first r1_set_scene and for GRID after an update until r1_regrid; then n == 0 is R1_OK; then NULL
+ * pointers.  A step changes no state another entry point sees and uses no per-context workspace but the launch's cursor: several scatter
+ * launches of one context may be in flight. */
+typedef struct r1_scatter
+{
+    float weight[3];   /* see the events */
+    int32_t event;     /* R1_SCATTER_* */
+    float t;           /* hit distance; FLT_MAX without a hit */
+    int32_t index;     /* SCENE index of the hit sphere, -1 without a hit */
+    uint32_t mat_type; /* R1_MAT_* of the hit sphere, R1_MAT_NONE without a hit */
+    uint32_t pad;      /* written as 0 */
+} r1_scatter; /* 32 bytes */
+
+enum
+{
+    R1_SCATTER_SCATTERED = 0,
+    R1_SCATTER_SKY = 1,
+    R1_SCATTER_ABSORBED = 2,
+    R1_SCATTER_NONE = 3
+};
+enum
+{
+    R1_SCATTER_UNIT_DIRECTIONS = 1 /* flags: the directions are unit vectors already (a previous step's rays_out) */
+};
+
+/* Host memory in and out, synchronous, R1_TRACE_CHUNK rays at a time (128 bytes per ray of a chunk in the cached workspace). */
+int r1_scatter_rays(r1_context *ctx, int32_t variant, int32_t flags, const r1_ray *rays, const r1_sample_seed *seeds, size_t n,
+                    r1_ray *rays_out, r1_sample_seed *seeds_out, r1_scatter *out);
+
+/* The same over DEVICE memory: enqueues on `hip_stream` (NULL = the context's stream) and waits for nothing.  Every pointer 16-byte
+ * aligned; d_seeds may be NULL.  d_rays_out == d_rays and d_seeds_out == d_seeds (in place) are allowed; any other overlap of an output
+ * with an input or with another output is R1_EINVAL, and nothing is enqueued. */
+int r1_scatter_rays_device(r1_context *ctx, int32_t variant, int32_t flags, const void *d_rays, const void *d_seeds, size_t n,
+                           void *d_rays_out, void *d_seeds_out, void *d_out, void *hip_stream);
+
+/* The same without a device, through the very level r1_trace_rays_host is the fold of.  The checker of the two forms above. */
+int r1_scatter_rays_host(const r1_scene *scene, int32_t flags, const r1_ray *rays, const r1_sample_seed *seeds, size_t n,
+                         r1_ray *rays_out, r1_sample_seed *seeds_out, r1_scatter *out);
+
 /* ---- host-side helpers of the drop-in (no GPU needed) ------------------------------ */
 
 /* Shape of the spatial index R1_VARIANT_BVH uses (r1_bvh.cpp; the reference has no such

@@ -110,6 +110,12 @@ CAST_CHUNK = 1 << 20  # R1_CAST_CHUNK: rays per launch of r1_cast_rays
 SEED_DTYPE = np.dtype([("scalar", np.uint32), ("lane0", np.uint32), ("lane1", np.uint32), ("lane2", np.uint32)])
 RADIANCE_DTYPE = np.dtype([("r", np.float32), ("g", np.float32), ("b", np.float32), ("rays", np.uint32)])
 TRACE_CHUNK = 1 << 20  # R1_TRACE_CHUNK: rays r1_trace_rays works through at a time
+# r1_scatter (32 bytes), the events and the flag of the scatter queries
+SCATTER_DTYPE = np.dtype([("weight", np.float32, 3), ("event", np.int32), ("t", np.float32), ("index", np.int32), ("mat_type", np.uint32),
+                          ("pad", np.uint32)])
+SCATTER_SCATTERED, SCATTER_SKY, SCATTER_ABSORBED, SCATTER_NONE = 0, 1, 2, 3
+SCATTER_UNIT_DIRECTIONS = 1
+MAT_LAMBERTIAN, MAT_METAL, MAT_DIELECTRIC, MAT_NONE = 0, 1, 2, 255
 
 
 def make_params(width, height, spp, seed=10001, max_bounces=50, tile_w=32, tile_h=32, shard=0, num_shards=1, variant=0):
@@ -230,6 +236,10 @@ SYMBOLS = [
     ("r1_trace_rays_device", C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     ("r1_trace_rays_host", C.c_int, [C.POINTER(CScene), C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("r1_camera_rays", C.c_int, [C.POINTER(CCamera), C.POINTER(Params), _i32p, _i32p, _i32p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    ("r1_camera_rays_device", C.c_int, [_ctx, C.POINTER(CCamera), C.POINTER(Params), C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("r1_scatter_rays", C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("r1_scatter_rays_device", C.c_int, [_ctx, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("r1_scatter_rays_host", C.c_int, [C.POINTER(CScene), C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("r1_render_linear", C.c_int, [_ctx, C.POINTER(Params), _f32p, _u64p, _dblp]),
     ("r1_render_linear_async", C.c_int, [_ctx, C.POINTER(Params), _f32p, _u64p, C.c_void_p]),
     ("r1_render_linear_device", C.c_int, [_ctx, C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -656,6 +666,31 @@ class Renderer:
         _check(lib().r1_trace_rays_device(self._c, variant, max_bounces, C.c_void_p(d_rays_ptr), C.c_void_p(d_seeds_ptr) if d_seeds_ptr else None, n,
                                           C.c_void_p(d_out_ptr), _stream_arg(stream)))
 
+    def scatter_rays(self, rays, seeds=None, flags=0, variant=0):
+        """r1_scatter_rays: one color() level — hit test, then Material::scatter — for caller-supplied rays, host memory in and out.  `rays`
+        and `seeds` as for trace_rays; flags: 0 or SCATTER_UNIT_DIRECTIONS (the directions are a previous step's: not normalised again).
+        Returns (Scatter records as a SCATTER_DTYPE array, the scattered rays as a RAY_DTYPE array, the advanced states as a SEED_DTYPE
+        array), in ray order."""
+        rays = _as_rays(rays)
+        seeds = _as_seeds(seeds, rays.shape[0])
+        out, rays_out, seeds_out = _scatter_out(rays.shape[0])
+        _check(lib().r1_scatter_rays(self._c, variant, flags, rays.ctypes.data, seeds.ctypes.data if seeds is not None else None, rays.shape[0],
+                                     rays_out.ctypes.data, seeds_out.ctypes.data, out.ctypes.data))
+        return Scatter(out, rays_out, seeds_out)
+
+    def scatter_rays_device(self, d_rays_ptr, d_seeds_ptr, n, d_rays_out_ptr, d_seeds_out_ptr, d_out_ptr, flags=0, variant=0, stream=None):
+        """r1_scatter_rays_device: the same over device memory (16-byte aligned: n r1_ray and n r1_sample_seed — or 0 / None — in; n r1_ray,
+        n r1_sample_seed and n r1_scatter out; d_rays_out_ptr == d_rays_ptr and d_seeds_out_ptr == d_seeds_ptr work in place); enqueues on
+        `stream` and waits for nothing."""
+        _check(lib().r1_scatter_rays_device(self._c, variant, flags, C.c_void_p(d_rays_ptr), C.c_void_p(d_seeds_ptr) if d_seeds_ptr else None, n,
+                                            C.c_void_p(d_rays_out_ptr), C.c_void_p(d_seeds_out_ptr), C.c_void_p(d_out_ptr), _stream_arg(stream)))
+
+    def camera_rays_device(self, params, first, n, d_rays_ptr, d_seeds_ptr, camera=None, stream=None):
+        """r1_camera_rays_device: the rays and stream states of samples [first, first + n) of the frame, in render_samples' order, written
+        to device memory as camera_rays writes them on the host; camera None: the context's.  Enqueues and waits for nothing."""
+        _check(lib().r1_camera_rays_device(self._c, C.byref(camera) if camera is not None else None, C.byref(params), first, n,
+                                           C.c_void_p(d_rays_ptr), C.c_void_p(d_seeds_ptr), _stream_arg(stream)))
+
     def set_pixel_mode(self, on):
         _check(lib().r1_set_pixel_mode(self._c, 1 if on else 0))
 
@@ -1074,6 +1109,33 @@ def trace_rays_host(cscene, rays, seeds=None, max_bounces=50):
     _check(lib().r1_trace_rays_host(C.byref(cscene), max_bounces, rays.ctypes.data, seeds.ctypes.data if seeds is not None else None,
                                     rays.shape[0], out.ctypes.data))
     return out
+
+
+class Scatter(tuple):
+    """What one step returns: (records, rays, seeds) — the SCATTER_DTYPE records, the scattered rays (RAY_DTYPE, unit directions: feed them
+    to the next step with SCATTER_UNIT_DIRECTIONS) and the advanced stream states (SEED_DTYPE).  Unpacks as a 3-tuple."""
+
+    def __new__(cls, records, rays, seeds):
+        return super().__new__(cls, (records, rays, seeds))
+
+    records = property(lambda self: self[0])
+    rays = property(lambda self: self[1])
+    seeds = property(lambda self: self[2])
+
+
+def _scatter_out(n):
+    return np.zeros(n, SCATTER_DTYPE), np.zeros(n, RAY_DTYPE), np.zeros(n, SEED_DTYPE)
+
+
+def scatter_rays_host(cscene, rays, seeds=None, flags=0):
+    """r1_scatter_rays_host: one color() level in scalar C++ on host threads (no device) — the level r1_trace_rays_host folds.  Same input
+    and output forms as Renderer.scatter_rays."""
+    rays = _as_rays(rays)
+    seeds = _as_seeds(seeds, rays.shape[0])
+    out, rays_out, seeds_out = _scatter_out(rays.shape[0])
+    _check(lib().r1_scatter_rays_host(C.byref(cscene), flags, rays.ctypes.data, seeds.ctypes.data if seeds is not None else None, rays.shape[0],
+                                      rays_out.ctypes.data, seeds_out.ctypes.data, out.ctypes.data))
+    return Scatter(out, rays_out, seeds_out)
 
 
 def camera_rays(ccamera, params, x, y, s):

@@ -242,6 +242,27 @@ __global__ void __launch_bounds__(256) r1_accum_linear_kernel(const R1ReadoutArg
     }
 }
 
+// r1_camera_rays_device: one lane per sample k of [first, first + n), k = (y * width + x) * spp + s as r1_render_samples
+// orders its records.  camera_ray (r1_sample.hpp) is start_ray without the Ray constructor: the record holds the direction un-normalised,
+// as the host's r1_camera_rays writes it, and the stream states after the camera's draws.  k runs to width * height * spp, which 64 bits hold.
+__global__ void __launch_bounds__(256) r1_camera_rays_kernel(const R1CameraRaysArgs A)
+{
+    const size_t stride = (size_t)gridDim.x * 256u;
+    for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < A.n; i += stride)
+    {
+        const size_t k = A.first + i;
+        const size_t pix = k / (uint32_t)A.spp;
+        const uint32_t s = (uint32_t)(k - pix * (uint32_t)A.spp);
+        const int y = (int)(pix / (uint32_t)A.width);
+        const int x = (int)(pix - (size_t)y * (uint32_t)A.width);
+        Path p;
+        const V3 dir = camera_ray(A.width, A.inv_w, A.inv_h, A.cam, p, x, y, s, A.seed);
+        A.rays[2 * i] = make_float4(p.o.x, p.o.y, p.o.z, FLT_MAX);
+        A.rays[2 * i + 1] = make_float4(dir.x, dir.y, dir.z, 0.0f);
+        A.seeds[i] = make_uint4(p.s_scalar, p.s0, p.s1, p.s2);
+    }
+}
+
 // ============================================================================================
 // Progressive passes (r1_render_pass): in place of the resolve launch.  One thread per pixel of a padded tile, as the resolve: the
 // accumulator (or 0.0f on the pass that starts the frame) plus the pass's records in sample order — the same sequence of fp32 adds the
@@ -641,6 +662,14 @@ extern "C" hipError_t r1_launch_accum_linear(const R1ReadoutArgs *args, hipStrea
     const int bx = (args->tile_w * args->tile_h + 255) / 256;
     const int by = (int)(args->n_tiles < 65535u ? args->n_tiles : 65535u);
     hipLaunchKernelGGL(r1_accum_linear_kernel, dim3(bx, by), dim3(256), 0, stream, *args);
+    return hipGetLastError();
+}
+
+// one lane per sample, grid-stride beyond 2^16 workgroups
+extern "C" hipError_t r1_launch_camera_rays(const R1CameraRaysArgs *args, hipStream_t stream)
+{
+    const unsigned long long blocks = (args->n + 255u) / 256u;
+    hipLaunchKernelGGL(r1_camera_rays_kernel, dim3((unsigned)(blocks < 65536u ? blocks : 65536u)), dim3(256), 0, stream, *args);
     return hipGetLastError();
 }
 

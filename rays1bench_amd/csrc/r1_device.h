@@ -335,7 +335,8 @@ enum
 {
     R1_JOB_CAST = 0, // ray queries: closest hit or occlusion
     R1_JOB_PATH = 1, // path queries: color()
-    R1_JOBS = 2
+    R1_JOB_SCATTER = 2, // scatter queries: one color() level
+    R1_JOBS = 3
 };
 
 // Ray queries (r1_cast_rays / r1_cast_rays_device, r1_query_kernels.hip): caller-supplied rays through the trace kernels' walks.
@@ -367,6 +368,36 @@ struct R1TraceRaysArgs
     uint32_t claim;         // rays per claim (a multiple of 64)
     uint32_t first;         // index within the call of the launch's ray 0 (seeds == null)
     uint32_t gstride;       // threads of the launch
+};
+
+// Scatter queries (r1_scatter_rays / r1_scatter_rays_device, r1_query_kernels.hip): one color() level for caller-supplied rays — the
+// path job's load, one walk, the hit arm of shade_level — with the scattered ray, the advanced stream states and a record as the result.
+struct R1ScatterArgs
+{
+    R1TraceArgs t;          // what the walks and the hit arm read: scene tables, bvh_lds_f4, bvh_depth, grid (everything else zero)
+    const float4 *rays;     // [n][2] {ox oy oz -} {dx dy dz -}: the public r1_ray
+    const uint4 *seeds;     // [n] the public r1_sample_seed; null: r1_seed_sample(0, first + i, 0)
+    float4 *rays_out;       // [n][2] {hit point, FLT_MAX} {scattered direction, 0}, or zero; may be `rays` itself
+    uint4 *seeds_out;       // [n] the states after the level's draws; may be `seeds` itself
+    float4 *out;            // [n][2] {weight rgb, event} {t, scene index, material type, 0}: the public r1_scatter
+    const uint32_t *active_to_scene; // [n_active] scene index of an active sphere
+    uint32_t *cursor;       // the launch's ray cursor (zero before the launch): the waves claim `claim` rays at a time
+    uint32_t n;             // <= R1_CAST_LAUNCH_MAX
+    uint32_t claim;         // rays per claim (a multiple of 64)
+    uint32_t first;         // index within the call of the launch's ray 0 (seeds == null)
+    uint32_t flags;         // R1_SCATTER_UNIT_DIRECTIONS: the directions are used as they are
+};
+
+// r1_camera_rays_kernel (r1_aux_kernels.hip): the primary rays and stream states of samples [first, first + n) of a frame, in r1_render_samples' order
+struct R1CameraRaysArgs
+{
+    R1DeviceCamera cam;     // by value
+    float4 *rays;           // [n][2] the public r1_ray: {origin, FLT_MAX} {un-normalised direction, 0}
+    uint4 *seeds;           // [n] the states after the camera's draws
+    unsigned long long first, n;
+    int32_t width, spp;
+    uint32_t seed;
+    float inv_w, inv_h;     // 1.0f / width, 1.0f / height (IEEE divisions done on the host)
 };
 
 struct R1ResolveArgs

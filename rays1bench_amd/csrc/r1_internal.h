@@ -83,6 +83,13 @@ hipError_t r1_cast_occupancy(int variant, int big, int plain, size_t dyn_lds, in
 hipError_t r1_launch_trace_rays(const R1TraceRaysArgs *args, int variant, int big, int blocks, size_t dyn_lds, hipStream_t stream);
 hipError_t r1_trace_rays_occupancy(int variant, int big, size_t dyn_lds, int *blocks_per_cu);
 
+// r1_query_kernels.hip, the scatter job; variant as for r1_launch_cast
+hipError_t r1_launch_scatter_rays(const R1ScatterArgs *args, int variant, int big, int blocks, size_t dyn_lds, hipStream_t stream);
+hipError_t r1_scatter_rays_occupancy(int variant, int big, size_t dyn_lds, int *blocks_per_cu);
+
+// r1_aux_kernels.hip: r1_camera_rays_device
+hipError_t r1_launch_camera_rays(const R1CameraRaysArgs *args, hipStream_t stream);
+
 // r1_refit.hip: the kernels of r1_update_centers* 
 hipError_t r1_launch_refit_move(const R1RefitArgs *a, uint32_t first, uint32_t count, const float *x, const float *y, const float *z, hipStream_t stream);
 hipError_t r1_launch_refit_set(const R1RefitArgs *a, const R1SetArgs *s, uint32_t first, uint32_t count, uint32_t groups, hipStream_t stream); // r1_update_spheres* (§4.27)

@@ -1,6 +1,7 @@
 // r1_queries.cpp — caller-supplied rays through the context's tree or grid: the ray queries (closest hit and occlusion; include/rays1.h
-// "ray queries") and the path queries (radiance; "path queries", §4.22).  Both are jobs of the kernels of
-// r1_query_kernels.hip and share the checks, the launch plan and the chunked loop of the host-memory forms below.
+// "ray queries"), the path queries (radiance; "path queries", §4.22) and the scatter queries (one color() level; "scatter
+// queries", §4.34).  All are jobs of the kernels of r1_query_kernels.hip and share the checks, the launch plan and the chunked loop of the
+// host-memory forms below.  r1_camera_rays_device, the generator of device-resident rays, stands at the end.
 
 #include <string.h>
 
@@ -10,10 +11,11 @@
 
 static_assert(sizeof(r1_ray) == 32 && sizeof(r1_hit) == 32, "the cast job reads and writes these layouts as two float4");
 static_assert(sizeof(r1_sample_seed) == 16 && sizeof(r1_radiance) == 16, "the path job reads and writes these layouts as one 16-byte word");
-static_assert(R1_TRACE_CHUNK == R1_CAST_CHUNK, "r1_trace_rays works in the ray queries' workspace, through the same loop: 64 bytes per ray of a chunk");
+static_assert(R1_TRACE_CHUNK == R1_CAST_CHUNK, "r1_trace_rays and r1_scatter_rays work in the ray queries' workspace, through the same loop: 64 / 128 bytes per ray of a chunk");
+static_assert(sizeof(r1_scatter) == 32, "the scatter job writes this layout as two float4");
 
-// The checks every entry point makes before it touches anything; `extra` is the cast's mode or the trace's max_bounces, tested where each
-// job has always tested it: the mode before the variant, the bounces after.  *structure: what the rays walk — R1_V_TREE, R1_V_GRID or
+// The checks every entry point makes before it touches anything; `extra` is the cast's mode, the trace's max_bounces or the step's flags, tested
+// where each job has always tested it: the mode and the flags before the variant, the bounces after.  *structure: what the rays walk — R1_V_TREE, R1_V_GRID or
 // R1_V_REFERENCE.
 static int query_check(const char *who, int job, r1_context *c, int32_t variant, int32_t extra, int *structure)
 {
@@ -27,6 +29,11 @@ static int query_check(const char *who, int job, r1_context *c, int32_t variant,
         r1_set_error("%s: mode %d is neither R1_CAST_CLOSEST nor R1_CAST_ANY", who, extra);
         return R1_EINVAL;
     }
+    if (job == R1_JOB_SCATTER && (extra & ~R1_SCATTER_UNIT_DIRECTIONS))
+    {
+        r1_set_error("%s: flags %d has bits other than R1_SCATTER_UNIT_DIRECTIONS", who, extra);
+        return R1_EINVAL;
+    }
     switch (variant)
     {
     case R1_VARIANT_DEFAULT:
@@ -34,7 +41,7 @@ static int query_check(const char *who, int job, r1_context *c, int32_t variant,
     case R1_VARIANT_GRID: *structure = R1_V_GRID; break;
     case R1_VARIANT_REFERENCE: *structure = R1_V_REFERENCE; break;
     default:
-        r1_set_error("%s: variant %d %s no rays (DEFAULT, BVH, GRID and REFERENCE do)", who, variant, job == R1_JOB_CAST ? "casts" : "traces");
+        r1_set_error("%s: variant %d %s no rays (DEFAULT, BVH, GRID and REFERENCE do)", who, variant, job == R1_JOB_CAST ? "casts" : job == R1_JOB_PATH ? "traces" : "scatters");
         return R1_EINVAL;
     }
     if (job == R1_JOB_PATH && (extra < 1 || extra > R1_MAX_BOUNCES_LIMIT))
@@ -76,7 +83,9 @@ struct QuerySlice
 
 static hipError_t query_occupancy(const QueryPlan &P, int *occ)
 {
-    return P.job == R1_JOB_CAST ? r1_cast_occupancy(P.structure, P.big, P.plain, P.dyn_lds, occ) : r1_trace_rays_occupancy(P.structure, P.big, P.dyn_lds, occ);
+    return P.job == R1_JOB_CAST   ? r1_cast_occupancy(P.structure, P.big, P.plain, P.dyn_lds, occ)
+           : P.job == R1_JOB_PATH ? r1_trace_rays_occupancy(P.structure, P.big, P.dyn_lds, occ)
+                                  : r1_scatter_rays_occupancy(P.structure, P.big, P.dyn_lds, occ);
 }
 
 // Waits for nothing (the first grid query after r1_set_scene builds the grid, as the first grid render does) and touches none of the
@@ -178,18 +187,61 @@ static int trace_enqueue(r1_context *c, int structure, int32_t max_bounces, cons
     return R1_OK;
 }
 
-// The host-memory forms: one chunk's rays, then (seed_each != 0) its seeds, then its records — 64 bytes per ray at the most — in the
-// cached workspace, so device memory stays bounded for any n.  enqueue(d_rays, d_seeds or null, at, m, d_out) launches one chunk on the
-// context's stream.
-template <class ENQUEUE>
-static int query_chunks(r1_context *c, const r1_ray *rays, const r1_sample_seed *seeds, size_t seed_each, size_t n, void *out, size_t out_each, ENQUEUE enqueue)
+// Enqueues one level for n rays (device memory; d_seeds may be null, as for a trace) on `st`.  No workspace but the launch's cursor:
+// any number of scatter launches of a context may be in flight.
+static int scatter_enqueue(r1_context *c, int structure, int32_t flags, const void *d_rays, const void *d_seeds, size_t first, size_t n, void *d_rays_out,
+                           void *d_seeds_out, void *d_out, hipStream_t st)
+{
+    QueryPlan P;
+    int rc = query_plan(c, R1_JOB_SCATTER, structure, P);
+    if (rc)
+        return rc;
+    R1ScatterArgs a;
+    memset(&a, 0, sizeof(a));
+    a.t = P.t;
+    a.active_to_scene = (const uint32_t *)c->active_dev.p;
+    a.flags = (uint32_t)flags;
+    for (QuerySlice s; query_slice(c, P, n, s);)
+    {
+        a.rays = (const float4 *)((const char *)d_rays + s.at * sizeof(r1_ray));
+        a.seeds = d_seeds ? (const uint4 *)((const char *)d_seeds + s.at * sizeof(r1_sample_seed)) : nullptr;
+        a.rays_out = (float4 *)((char *)d_rays_out + s.at * sizeof(r1_ray));
+        a.seeds_out = (uint4 *)((char *)d_seeds_out + s.at * sizeof(r1_sample_seed));
+        a.out = (float4 *)((char *)d_out + s.at * sizeof(r1_scatter));
+        a.n = s.n, a.claim = s.claim, a.cursor = s.cursor;
+        a.first = (uint32_t)(first + s.at);
+        R1_HIP(hipMemsetAsync(a.cursor, 0, 4, st));
+        R1_HIP(r1_launch_scatter_rays(&a, P.structure, P.big, (int)s.blocks, P.dyn_lds, st));
+    }
+    return R1_OK;
+}
+
+// one result array of a host-memory form: `each` bytes per ray
+struct ChunkOut
+{
+    void *host;
+    size_t each;
+};
+
+// The host-memory forms: one chunk's rays, then (seed_each != 0) its seeds, then its results — 64 bytes per ray at the most for a cast or a
+// trace, 128 for a step (32 + 16 in, 32 + 32 + 16 out) — in the cached workspace, so device memory stays bounded for any n.
+// enqueue(d_rays, d_seeds or null, at, m, d_out[]) launches one chunk on the context's stream; d_out[k] is the chunk's part of outs[k].
+template <size_t K, class ENQUEUE>
+static int query_chunks(r1_context *c, const r1_ray *rays, const r1_sample_seed *seeds, size_t seed_each, size_t n, const ChunkOut (&outs)[K], ENQUEUE enqueue)
 {
     int rc;
     R1_HIP(hipSetDevice(c->device));
     const size_t chunk = std::min<size_t>(n, R1_CAST_CHUNK);
-    if ((rc = ensure(c->cast_ws, chunk * 64)))
+    size_t each = sizeof(r1_ray) + seed_each;
+    for (const ChunkOut &o : outs)
+        each += (o.each + 15) & ~(size_t)15;
+    if ((rc = ensure(c->cast_ws, chunk * std::max<size_t>(each, 64))))
         return rc;
-    char *const d_rays = (char *)c->cast_ws.p, *const d_seeds = d_rays + chunk * sizeof(r1_ray), *const d_out = d_seeds + chunk * seed_each;
+    char *const d_rays = (char *)c->cast_ws.p, *const d_seeds = d_rays + chunk * sizeof(r1_ray);
+    char *d_out[K];
+    d_out[0] = d_seeds + chunk * seed_each;
+    for (size_t k = 1; k < K; ++k)
+        d_out[k] = d_out[k - 1] + chunk * ((outs[k - 1].each + 15) & ~(size_t)15);
     for (size_t at = 0; at < n; at += chunk)
     {
         const size_t m = std::min(chunk, n - at);
@@ -198,7 +250,8 @@ static int query_chunks(r1_context *c, const r1_ray *rays, const r1_sample_seed 
             R1_HIP(hipMemcpyAsync(d_seeds, seeds + at, m * seed_each, hipMemcpyHostToDevice, c->stream));
         if ((rc = enqueue(d_rays, seeds ? d_seeds : nullptr, at, m, d_out)))
             return rc;
-        R1_HIP(hipMemcpyAsync((char *)out + at * out_each, d_out, m * out_each, hipMemcpyDeviceToHost, c->stream));
+        for (size_t k = 0; k < K; ++k)
+            R1_HIP(hipMemcpyAsync((char *)outs[k].host + at * outs[k].each, d_out[k], m * outs[k].each, hipMemcpyDeviceToHost, c->stream));
         R1_HIP(hipStreamSynchronize(c->stream)); // (the next chunk reuses the workspace)
     }
     return R1_OK;
@@ -235,8 +288,9 @@ extern "C" int r1_cast_rays(r1_context *c, int32_t variant, int32_t mode, const 
         r1_set_error("r1_cast_rays: rays and out must not be NULL with n > 0");
         return R1_EINVAL;
     }
-    return query_chunks(c, rays, nullptr, 0, n, out, mode == R1_CAST_ANY ? 1 : sizeof(r1_hit), [=](const void *d_rays, const void *, size_t, size_t m, void *d_out) {
-        return cast_enqueue(c, structure, mode, d_rays, m, d_out, c->stream);
+    const ChunkOut outs[1] = {{out, mode == R1_CAST_ANY ? (size_t)1 : sizeof(r1_hit)}};
+    return query_chunks(c, rays, nullptr, 0, n, outs, [=](const void *d_rays, const void *, size_t, size_t m, char *const *d_out) {
+        return cast_enqueue(c, structure, mode, d_rays, m, d_out[0], c->stream);
     });
 }
 
@@ -272,7 +326,128 @@ extern "C" int r1_trace_rays(r1_context *c, int32_t variant, int32_t max_bounces
         r1_set_error("r1_trace_rays: rays and out must not be NULL with n > 0");
         return R1_EINVAL;
     }
-    return query_chunks(c, rays, seeds, sizeof(r1_sample_seed), n, out, sizeof(r1_radiance), [=](const void *d_rays, const void *d_seeds, size_t at, size_t m, void *d_out) {
-        return trace_enqueue(c, structure, max_bounces, d_rays, d_seeds, at, m, d_out, c->stream);
+    const ChunkOut outs[1] = {{out, sizeof(r1_radiance)}};
+    return query_chunks(c, rays, seeds, sizeof(r1_sample_seed), n, outs, [=](const void *d_rays, const void *d_seeds, size_t at, size_t m, char *const *d_out) {
+        return trace_enqueue(c, structure, max_bounces, d_rays, d_seeds, at, m, d_out[0], c->stream);
     });
+}
+
+// ---- scatter queries ---------------------------------------------------------------------------------------------------------------------
+
+// [a, a + na) and [b, b + nb) share a byte
+static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return a && b && pa < pb + nb && pb < pa + na;
+}
+
+extern "C" int r1_scatter_rays_device(r1_context *c, int32_t variant, int32_t flags, const void *d_rays, const void *d_seeds, size_t n, void *d_rays_out,
+                                      void *d_seeds_out, void *d_out, void *hip_stream)
+{
+    int structure = 0;
+    int rc = query_check("r1_scatter_rays_device", R1_JOB_SCATTER, c, variant, flags, &structure);
+    if (rc)
+        return rc;
+    if (n == 0)
+        return R1_OK;
+    if (!d_rays || !d_rays_out || !d_seeds_out || !d_out ||
+        (((uintptr_t)d_rays | (uintptr_t)d_seeds | (uintptr_t)d_rays_out | (uintptr_t)d_seeds_out | (uintptr_t)d_out) & 15u))
+    {
+        r1_set_error("r1_scatter_rays_device: d_rays, d_rays_out, d_seeds_out and d_out must be non-NULL device memory, and they and d_seeds 16-byte aligned");
+        return R1_EINVAL;
+    }
+    // in place is d_rays_out == d_rays and d_seeds_out == d_seeds, exactly: a lane reads ray i before it writes ray i.  Anything else that
+    // shares bytes lets one lane's result land in a ray another lane has yet to read.
+    const size_t nr = n * sizeof(r1_ray), ns = n * sizeof(r1_sample_seed), no = n * sizeof(r1_scatter);
+    const struct
+    {
+        const void *p;
+        size_t bytes;
+    } in[2] = {{d_rays, nr}, {d_seeds, ns}}, res[3] = {{d_rays_out, nr}, {d_seeds_out, ns}, {d_out, no}};
+    bool bad = false;
+    for (int o = 0; o < 3; ++o)
+    {
+        for (int i = 0; i < 2; ++i)
+            if (!(o == i && res[o].p == in[i].p) && ranges_overlap(res[o].p, res[o].bytes, in[i].p, in[i].bytes))
+                bad = true;
+        for (int q = o + 1; q < 3; ++q)
+            if (ranges_overlap(res[o].p, res[o].bytes, res[q].p, res[q].bytes))
+                bad = true;
+    }
+    if (bad)
+    {
+        r1_set_error("r1_scatter_rays_device: an output overlaps an input or another output (d_rays_out == d_rays and d_seeds_out == d_seeds alone are allowed)");
+        return R1_EINVAL;
+    }
+    return scatter_enqueue(c, structure, flags, d_rays, d_seeds, 0, n, d_rays_out, d_seeds_out, d_out, hip_stream ? (hipStream_t)hip_stream : c->stream);
+}
+
+extern "C" int r1_scatter_rays(r1_context *c, int32_t variant, int32_t flags, const r1_ray *rays, const r1_sample_seed *seeds, size_t n, r1_ray *rays_out,
+                               r1_sample_seed *seeds_out, r1_scatter *out)
+{
+    int structure = 0;
+    int rc = query_check("r1_scatter_rays", R1_JOB_SCATTER, c, variant, flags, &structure);
+    if (rc)
+        return rc;
+    if (n == 0)
+        return R1_OK;
+    if (!rays || !rays_out || !seeds_out || !out)
+    {
+        r1_set_error("r1_scatter_rays: rays, rays_out, seeds_out and out must not be NULL with n > 0");
+        return R1_EINVAL;
+    }
+    const ChunkOut outs[3] = {{out, sizeof(r1_scatter)}, {rays_out, sizeof(r1_ray)}, {seeds_out, sizeof(r1_sample_seed)}};
+    return query_chunks(c, rays, seeds, sizeof(r1_sample_seed), n, outs, [=](const void *d_rays, const void *d_seeds, size_t at, size_t m, char *const *d_out) {
+        return scatter_enqueue(c, structure, flags, d_rays, d_seeds, at, m, d_out[1], d_out[2], d_out[0], c->stream);
+    });
+}
+
+// ---- camera rays on the device -------------------------------------------------------------------------------------------------------------
+
+extern "C" int r1_camera_rays_device(r1_context *c, const r1_camera *camera, const r1_params *p, size_t first, size_t n, void *d_rays, void *d_seeds,
+                                     void *hip_stream)
+{
+    if (!c)
+    {
+        r1_set_error("r1_camera_rays_device: ctx is NULL");
+        return R1_EINVAL;
+    }
+    if (!p || p->width <= 0 || p->height <= 0 || p->spp < 1)
+    {
+        r1_set_error("r1_camera_rays_device: null params, an empty image or spp < 1");
+        return R1_EINVAL;
+    }
+    if (p->num_shards != 1)
+    {
+        r1_set_error("r1_camera_rays_device: whole frames only (num_shards %d)", p->num_shards);
+        return R1_EINVAL;
+    }
+    const size_t total = (size_t)p->width * (size_t)p->height * (size_t)p->spp;
+    if (first > total || n > total - first)
+    {
+        r1_set_error("r1_camera_rays_device: samples [%zu, %zu + %zu) reach beyond the frame's %zu", first, first, n, total);
+        return R1_EINVAL;
+    }
+    if (!camera && !c->have_scene)
+    {
+        r1_set_error("r1_camera_rays_device: no camera given and no scene set (call r1_set_scene first)");
+        return R1_EINVAL;
+    }
+    if (n == 0)
+        return R1_OK;
+    if (!d_rays || !d_seeds || (((uintptr_t)d_rays | (uintptr_t)d_seeds) & 15u))
+    {
+        r1_set_error("r1_camera_rays_device: d_rays and d_seeds must be non-NULL device memory, 16-byte aligned");
+        return R1_EINVAL;
+    }
+    R1_HIP(hipSetDevice(c->device));
+    R1CameraRaysArgs a;
+    memset(&a, 0, sizeof(a));
+    a.cam = camera ? device_camera(*camera) : c->cam;
+    a.rays = (float4 *)d_rays, a.seeds = (uint4 *)d_seeds;
+    a.first = first, a.n = n;
+    a.width = p->width, a.spp = p->spp, a.seed = p->seed;
+    a.inv_w = 1.0f / p->width, a.inv_h = 1.0f / p->height; // rayweek1.cpp:746
+    R1_HIP(r1_launch_camera_rays(&a, hip_stream ? (hipStream_t)hip_stream : c->stream));
+    return R1_OK;
 }

@@ -1,5 +1,5 @@
-// r1_queries_host.cpp — the ray and path queries on the host, no GPU: r1_cast_rays_host, r1_trace_rays_host and r1_camera_rays
-// (include/rays1.h).  Every ray against every active sphere in index order, in the reference's arithmetic — its
+// r1_queries_host.cpp — the ray, path and scatter queries on the host, no GPU: r1_cast_rays_host, r1_trace_rays_host, r1_scatter_rays_host
+// and r1_camera_rays (include/rays1.h).  Every ray against every active sphere in index order, in the reference's arithmetic — its
 // two FMA chains written with fmaf, everything else operation by operation (this file is compiled with -ffp-contract=off).
 
 #include "../../include/rays1.h"
@@ -17,7 +17,7 @@
 int r1_active_spheres(const r1_scene *s, std::vector<uint32_t> &active_to_scene); // inv_radius != 0, finite (r1_bvh.cpp)
 
 static_assert(sizeof(r1_ray) == 32 && sizeof(r1_hit) == 32, "the device reads and writes these layouts");
-static_assert(sizeof(r1_radiance) == 16 && sizeof(r1_sample_seed) == 16, "the device reads and writes these layouts");
+static_assert(sizeof(r1_radiance) == 16 && sizeof(r1_sample_seed) == 16 && sizeof(r1_scatter) == 32, "the device reads and writes these layouts");
 
 namespace
 {
@@ -180,11 +180,113 @@ struct TraceScene
     std::vector<float> shade;           // [active] {inv_radius, albedo rgb}
     std::vector<float> mat;             // [active] {param, 1 / ref_idx, ((1 - ref) / (1 + ref))^2}
     std::vector<uint8_t> type;
+    std::vector<uint32_t> scene_index;  // [active] index into the r1_scene arrays
 };
+
+// One color() level behind the Ray constructor (rayweek1.cpp:519-534) for the unit ray (o, d): the hit test, then the sky, or — where
+// may_scatter says that the depth limit allows it — the hit arm: hit record, draws, Material::scatter, the scattered ray in (o, d) and
+// the advanced stream states in sd.  r1_trace_rays_host is the fold of this function (trace_range), r1_scatter_rays_host one call of it
+// per ray (scatter_range): the two cannot drift apart.
+struct Level
+{
+    int event;    // R1_SCATTER_SCATTERED, _SKY, _ABSORBED; LEVEL_LIMIT: a hit at the depth limit (no scatter, no draws: black)
+    size_t hit;   // the active sphere, na without a hit
+    float t;      // the hit distance, FLT_MAX without a hit
+    V3 weight;    // SKY: the sky's colour; SCATTERED: the attenuation (albedo; 1 for a dielectric); else 0
+};
+enum { LEVEL_LIMIT = -1 };
+
+inline Level level(const TraceScene &T, V3 &o, V3 &d, r1_sample_seed &sd, const bool may_scatter)
+{
+    const size_t na = T.type.size();
+    Level L = {R1_SCATTER_SKY, na, FLT_MAX, {0, 0, 0}};
+    // Hitable::hit(r, 0.001f, FLT_MAX, rec), rayweek1.cpp:519
+    float best;
+    const size_t hit = closest(T.ex, na, o, d, best);
+    if (hit == na)
+    {
+        // sky (rayweek1.cpp:532-534), lerp = (1 - t) * a + t * b (mymath.h:212-216)
+        const float t = 0.5f * (d.y + 1.0f);
+        const float omt = 1.0f - t;
+        L.weight = {omt * 1.0f + t * 0.5f, omt * 1.0f + t * 0.7f, omt * 1.0f + t * 1.0f};
+        return L;
+    }
+    L.hit = hit, L.t = best;
+    if (!may_scatter)
+    {
+        L.event = LEVEL_LIMIT; // depth == MAX_BOUNCES: black (rayweek1.cpp:523-528)
+        return L;
+    }
+    // hit record (rayweek1.cpp:316-322)
+    const float *e = &T.ex[4 * hit], *sh = &T.shade[4 * hit], *mt = &T.mat[3 * hit];
+    const V3 hp = add(o, scale(d, best));
+    const V3 n = scale(sub(hp, {e[0], e[1], e[2]}), sh[0]);
+    const uint8_t type = T.type[hit];
+    V3 rius = {0, 0, 0};
+    if (type != R1_MAT_DIELECTRIC) // random_in_unit_sphere, mymath.h:224-235 (Lambertian and Metal both draw it, rayweek1.cpp:405, :430)
+        do
+        {
+            rius = {rand02_minus1(sd.lane0), rand02_minus1(sd.lane1), rand02_minus1(sd.lane2)};
+        } while (dot(rius, rius) >= 1);
+    V3 dir;
+    if (type == R1_MAT_LAMBERTIAN)
+    {
+        const V3 target = add(add(hp, n), rius); // rayweek1.cpp:403-409
+        dir = sub(target, hp);
+    }
+    else if (type == R1_MAT_METAL)
+    {
+        const V3 refl = sub(d, scale(n, 2.0f * dot(d, n))); // rayweek1.cpp:427-433, reflect :414-417
+        dir = add(refl, scale(rius, mt[0]));
+    }
+    else
+    {
+        // Dielectric::scatter rayweek1.cpp:470-511
+        const float ref_idx = mt[0];
+        const float ddn = dot(d, n);
+        const V3 reflected = sub(d, scale(n, 2.0f * ddn));
+        V3 outward;
+        float ni_over_nt, cosine;
+        if (ddn > 0)
+        {
+            outward = {-n.x, -n.y, -n.z};
+            ni_over_nt = ref_idx;
+            cosine = ref_idx * ddn;
+        }
+        else
+        {
+            outward = n;
+            ni_over_nt = mt[1];
+            cosine = -ddn;
+        }
+        // refract rayweek1.cpp:439-452
+        const float dt = dot(d, outward);
+        const float discriminant = 1.0f - ni_over_nt * ni_over_nt * (1.0f - dt * dt);
+        float reflect_prob = 1.0f;
+        V3 refracted = {0, 0, 0};
+        if (discriminant > 0)
+        {
+            refracted = sub(scale(sub(d, scale(outward, dt)), ni_over_nt), scale(outward, sqrtf(discriminant)));
+            // schlick rayweek1.cpp:454-459, x^5 exactly rounded (r1s_pow5 of r1_scatter.h)
+            const float r0 = mt[2];
+            const double x = (double)(1.0f - cosine), x2 = x * x;
+            reflect_prob = r0 + (1.0f - r0) * (float)(x2 * x2 * x);
+        }
+        dir = (rand01(sd.scalar) < reflect_prob) ? reflected : refracted;
+    }
+    const V3 nd = unit(dir);
+    o = hp, d = nd;
+    if (type == R1_MAT_DIELECTRIC)
+        L.event = R1_SCATTER_SCATTERED, L.weight = {1.0f, 1.0f, 1.0f}; // (attenuation 1, rayweek1.cpp:473)
+    else if (type == R1_MAT_LAMBERTIAN || dot(nd, n) > 0)
+        L.event = R1_SCATTER_SCATTERED, L.weight = {sh[1], sh[2], sh[3]};
+    else
+        L.event = R1_SCATTER_ABSORBED; // Metal::scatter() == false: black (rayweek1.cpp:432, :528)
+    return L;
+}
 
 void trace_range(const TraceScene &T, int32_t max_bounces, const r1_ray *rays, const r1_sample_seed *seeds, size_t i0, size_t i1, r1_radiance *out)
 {
-    const size_t na = T.type.size();
     std::vector<uint32_t> stack((size_t)max_bounces);
     for (size_t i = i0; i < i1; ++i)
     {
@@ -195,21 +297,16 @@ void trace_range(const TraceScene &T, int32_t max_bounces, const r1_ray *rays, c
             out[i] = rec; // no color()
             continue;
         }
-        const r1_sample_seed sd = r1_seed_guard(seeds ? seeds[i] : r1_seed_sample(0u, (uint32_t)i, 0u));
-        uint32_t s_scalar = sd.scalar, s0 = sd.lane0, s1 = sd.lane1, s2 = sd.lane2;
+        r1_sample_seed sd = r1_seed_guard(seeds ? seeds[i] : r1_seed_sample(0u, (uint32_t)i, 0u));
         int depth = 0, sp = 0;
         V3 col = {0, 0, 0};
         for (;;)
         {
-            // Hitable::hit(r, 0.001f, FLT_MAX, rec), rayweek1.cpp:519
-            float best;
-            const size_t hit = closest(T.ex, na, o, d, best);
-            if (hit == na)
+            const Level L = level(T, o, d, sd, depth < max_bounces);
+            if (L.event == R1_SCATTER_SKY)
             {
-                // sky (rayweek1.cpp:532-534), lerp = (1 - t) * a + t * b (mymath.h:212-216)
-                const float t = 0.5f * (d.y + 1.0f);
-                const float omt = 1.0f - t;
-                col = {omt * 1.0f + t * 0.5f, omt * 1.0f + t * 0.7f, omt * 1.0f + t * 1.0f};
+                // the attenuations innermost first: a0 * (a1 * (... * sky)), rayweek1.cpp:525
+                col = L.weight;
                 for (int e = sp - 1; e >= 0; --e)
                 {
                     const float *sh = &T.shade[4 * (size_t)stack[e]];
@@ -217,79 +314,87 @@ void trace_range(const TraceScene &T, int32_t max_bounces, const r1_ray *rays, c
                 }
                 break;
             }
-            if (depth >= max_bounces)
-                break; // depth == MAX_BOUNCES: black (rayweek1.cpp:523-528)
-            // hit record (rayweek1.cpp:316-322)
-            const float *e = &T.ex[4 * hit], *sh = &T.shade[4 * hit], *mt = &T.mat[3 * hit];
-            const V3 hp = add(o, scale(d, best));
-            const V3 n = scale(sub(hp, {e[0], e[1], e[2]}), sh[0]);
-            const uint8_t type = T.type[hit];
-            V3 rius = {0, 0, 0};
-            if (type != R1_MAT_DIELECTRIC) // random_in_unit_sphere, mymath.h:224-235 (Lambertian and Metal both draw it, rayweek1.cpp:405, :430)
-                do
-                {
-                    rius = {rand02_minus1(s0), rand02_minus1(s1), rand02_minus1(s2)};
-                } while (dot(rius, rius) >= 1);
-            V3 dir;
-            if (type == R1_MAT_LAMBERTIAN)
-            {
-                const V3 target = add(add(hp, n), rius); // rayweek1.cpp:403-409
-                dir = sub(target, hp);
-            }
-            else if (type == R1_MAT_METAL)
-            {
-                const V3 refl = sub(d, scale(n, 2.0f * dot(d, n))); // rayweek1.cpp:427-433, reflect :414-417
-                dir = add(refl, scale(rius, mt[0]));
-            }
-            else
-            {
-                // Dielectric::scatter rayweek1.cpp:470-511
-                const float ref_idx = mt[0];
-                const float ddn = dot(d, n);
-                const V3 reflected = sub(d, scale(n, 2.0f * ddn));
-                V3 outward;
-                float ni_over_nt, cosine;
-                if (ddn > 0)
-                {
-                    outward = {-n.x, -n.y, -n.z};
-                    ni_over_nt = ref_idx;
-                    cosine = ref_idx * ddn;
-                }
-                else
-                {
-                    outward = n;
-                    ni_over_nt = mt[1];
-                    cosine = -ddn;
-                }
-                // refract rayweek1.cpp:439-452
-                const float dt = dot(d, outward);
-                const float discriminant = 1.0f - ni_over_nt * ni_over_nt * (1.0f - dt * dt);
-                float reflect_prob = 1.0f;
-                V3 refracted = {0, 0, 0};
-                if (discriminant > 0)
-                {
-                    refracted = sub(scale(sub(d, scale(outward, dt)), ni_over_nt), scale(outward, sqrtf(discriminant)));
-                    // schlick rayweek1.cpp:454-459, x^5 exactly rounded (r1s_pow5 of r1_scatter.h)
-                    const float r0 = mt[2];
-                    const double x = (double)(1.0f - cosine), x2 = x * x;
-                    reflect_prob = r0 + (1.0f - r0) * (float)(x2 * x2 * x);
-                }
-                dir = (rand01(s_scalar) < reflect_prob) ? reflected : refracted;
-            }
-            const V3 nd = unit(dir);
-            o = hp, d = nd;
-            if (type == R1_MAT_DIELECTRIC || type == R1_MAT_LAMBERTIAN || dot(nd, n) > 0)
-            {
-                if (type != R1_MAT_DIELECTRIC)
-                    stack[sp++] = (uint32_t)hit;
-            }
-            else
-                break; // Metal::scatter() == false: black (rayweek1.cpp:432, :528)
+            if (L.event != R1_SCATTER_SCATTERED)
+                break; // the depth limit, or Metal::scatter() == false: black
+            if (T.type[L.hit] != R1_MAT_DIELECTRIC)
+                stack[sp++] = (uint32_t)L.hit;
             ++depth;
         }
         rec.r = col.x, rec.g = col.y, rec.b = col.z, rec.rays = (uint32_t)depth + 1u; // every level counts one ray (rayweek1.cpp:517)
         out[i] = rec;
     }
+}
+
+// ---- scatter queries: one level per ray (include/rays1.h "scatter queries") ---------------------------------------------
+void scatter_range(const TraceScene &T, int32_t flags, const r1_ray *rays, const r1_sample_seed *seeds, size_t i0, size_t i1, r1_ray *rays_out,
+                   r1_sample_seed *seeds_out, r1_scatter *out)
+{
+    for (size_t i = i0; i < i1; ++i)
+    {
+        const r1_ray in = rays[i]; // (read before anything of ray i is written: rays_out may be rays, seeds_out may be seeds)
+        r1_sample_seed sd = r1_seed_guard(seeds ? seeds[i] : r1_seed_sample(0u, (uint32_t)i, 0u));
+        V3 o, d;
+        bool valid;
+        if (flags & R1_SCATTER_UNIT_DIRECTIONS)
+        {
+            o = {in.o[0], in.o[1], in.o[2]}, d = {in.d[0], in.d[1], in.d[2]};
+            valid = finite_f(o.x) && finite_f(o.y) && finite_f(o.z) && finite_f(d.x) && finite_f(d.y) && finite_f(d.z);
+        }
+        else
+            valid = ray_start(in, o, d);
+        r1_scatter rec;
+        r1_ray next;
+        memset(&rec, 0, sizeof(rec)), memset(&next, 0, sizeof(next));
+        rec.event = R1_SCATTER_NONE, rec.t = FLT_MAX, rec.index = -1, rec.mat_type = R1_MAT_NONE;
+        if (valid)
+        {
+            const Level L = level(T, o, d, sd, true);
+            rec.event = L.event;
+            rec.weight[0] = L.weight.x, rec.weight[1] = L.weight.y, rec.weight[2] = L.weight.z;
+            if (L.event != R1_SCATTER_SKY)
+            {
+                rec.t = L.t, rec.index = (int32_t)T.scene_index[L.hit], rec.mat_type = T.type[L.hit];
+                next.o[0] = o.x, next.o[1] = o.y, next.o[2] = o.z, next.t_max = FLT_MAX;
+                next.d[0] = d.x, next.d[1] = d.y, next.d[2] = d.z;
+            }
+        }
+        out[i] = rec, rays_out[i] = next, seeds_out[i] = sd;
+    }
+}
+
+// the tables of a scene's active spheres as the levels read them; who: the entry point, for r1_last_error
+bool null_scene(const char *who, const r1_scene *s)
+{
+    if (s && (!s->count || (s->center_x && s->center_y && s->center_z && s->radius_sq && s->inv_radius && s->mat_type && s->albedo_r && s->albedo_g &&
+                            s->albedo_b && s->mat_param)))
+        return false;
+    r1_set_error("%s: null scene", who);
+    return true;
+}
+
+int trace_scene(const char *who, const r1_scene *s, TraceScene &T)
+{
+    if (exact_table(s, T.scene_index, T.ex) != R1_OK)
+        return R1_EINVAL;
+    const size_t na = T.scene_index.size();
+    T.shade.resize(4 * na + 4), T.mat.resize(3 * na + 3), T.type.resize(na);
+    for (size_t a = 0; a < na; ++a)
+    {
+        const uint32_t i = T.scene_index[a];
+        if (s->mat_type[i] > R1_MAT_DIELECTRIC)
+        {
+            r1_set_error("%s: sphere %u is hittable but has no material", who, i);
+            return R1_EINVAL;
+        }
+        T.shade[4 * a + 0] = s->inv_radius[i], T.shade[4 * a + 1] = s->albedo_r[i], T.shade[4 * a + 2] = s->albedo_g[i], T.shade[4 * a + 3] = s->albedo_b[i];
+        // the dielectric's constants as the device tables hold them (r1_sweep.cpp; rayweek1.cpp:489, :456-457): same IEEE operations, done once
+        const float ref_idx = s->mat_param[i];
+        float r0 = (1 - ref_idx) / (1 + ref_idx);
+        r0 = r0 * r0;
+        T.mat[3 * a + 0] = ref_idx, T.mat[3 * a + 1] = 1.0f / ref_idx, T.mat[3 * a + 2] = r0;
+        T.type[a] = s->mat_type[i];
+    }
+    return R1_OK;
 }
 
 } // namespace
@@ -328,12 +433,8 @@ extern "C" int r1_trace_rays_host(const r1_scene *s, int32_t max_bounces, const 
         r1_set_error("r1_trace_rays_host: max_bounces %d is not in 1..%d", max_bounces, R1_MAX_BOUNCES_LIMIT);
         return R1_EINVAL;
     }
-    if (!s || (s->count && (!s->center_x || !s->center_y || !s->center_z || !s->radius_sq || !s->inv_radius || !s->mat_type || !s->albedo_r ||
-                            !s->albedo_g || !s->albedo_b || !s->mat_param)))
-    {
-        r1_set_error("r1_trace_rays_host: null scene");
+    if (null_scene("r1_trace_rays_host", s))
         return R1_EINVAL;
-    }
     if (n == 0)
         return R1_OK;
     if (!rays || !out)
@@ -341,29 +442,34 @@ extern "C" int r1_trace_rays_host(const r1_scene *s, int32_t max_bounces, const 
         r1_set_error("r1_trace_rays_host: null rays or out with n > 0");
         return R1_EINVAL;
     }
-    std::vector<uint32_t> scene_index;
     TraceScene T;
-    if (exact_table(s, scene_index, T.ex) != R1_OK)
+    if (trace_scene("r1_trace_rays_host", s, T) != R1_OK)
         return R1_EINVAL;
-    const size_t na = scene_index.size();
-    T.shade.resize(4 * na + 4), T.mat.resize(3 * na + 3), T.type.resize(na);
-    for (size_t a = 0; a < na; ++a)
-    {
-        const uint32_t i = scene_index[a];
-        if (s->mat_type[i] > R1_MAT_DIELECTRIC)
-        {
-            r1_set_error("r1_trace_rays_host: sphere %u is hittable but has no material", i);
-            return R1_EINVAL;
-        }
-        T.shade[4 * a + 0] = s->inv_radius[i], T.shade[4 * a + 1] = s->albedo_r[i], T.shade[4 * a + 2] = s->albedo_g[i], T.shade[4 * a + 3] = s->albedo_b[i];
-        // the dielectric's constants as the device tables hold them (r1_sweep.cpp; rayweek1.cpp:489, :456-457): same IEEE operations, done once
-        const float ref_idx = s->mat_param[i];
-        float r0 = (1 - ref_idx) / (1 + ref_idx);
-        r0 = r0 * r0;
-        T.mat[3 * a + 0] = ref_idx, T.mat[3 * a + 1] = 1.0f / ref_idx, T.mat[3 * a + 2] = r0;
-        T.type[a] = s->mat_type[i];
-    }
     split_rays(n, [&](size_t i0, size_t i1) { trace_range(T, max_bounces, rays, seeds, i0, i1, out); });
+    return R1_OK;
+}
+
+extern "C" int r1_scatter_rays_host(const r1_scene *s, int32_t flags, const r1_ray *rays, const r1_sample_seed *seeds, size_t n, r1_ray *rays_out,
+                                    r1_sample_seed *seeds_out, r1_scatter *out)
+{
+    if (flags & ~R1_SCATTER_UNIT_DIRECTIONS)
+    {
+        r1_set_error("r1_scatter_rays_host: flags %d has bits other than R1_SCATTER_UNIT_DIRECTIONS", flags);
+        return R1_EINVAL;
+    }
+    if (null_scene("r1_scatter_rays_host", s))
+        return R1_EINVAL;
+    if (n == 0)
+        return R1_OK;
+    if (!rays || !rays_out || !seeds_out || !out)
+    {
+        r1_set_error("r1_scatter_rays_host: null rays, rays_out, seeds_out or out with n > 0");
+        return R1_EINVAL;
+    }
+    TraceScene T;
+    if (trace_scene("r1_scatter_rays_host", s, T) != R1_OK)
+        return R1_EINVAL;
+    split_rays(n, [&](size_t i0, size_t i1) { scatter_range(T, flags, rays, seeds, i0, i1, rays_out, seeds_out, out); });
     return R1_OK;
 }
 

@@ -1,4 +1,5 @@
-// r1_query_kernels.hip — the kernels of the ray queries (r1_cast_rays*) and of the path queries (r1_trace_rays*, §4.22):
+// r1_query_kernels.hip — the kernels of the ray queries (r1_cast_rays*), of the path queries (r1_trace_rays*, §4.22) and of the
+// scatter queries (r1_scatter_rays*, §4.34):
 // caller-supplied rays through the trace kernels' walks as they are — sweep_reference (r1_hit_sweep.hpp), bvh_advance (r1_hit_tree.hpp), grid_trace
 // (r1_hit_grid.hpp) — claimed with chunk_claim (r1_sample.hpp) and, the path jobs, shaded by shade_level (r1_shade.hpp).  There is
 // one loop per structure — box tree, uniform grid, reference form — and a JOB says what a lane does with a ray: how it is loaded and
@@ -158,6 +159,98 @@ struct R1PathJob
     __device__ __forceinline__ void finish(const Args &A, const uint32_t i, const bool walked) const
     {
         A.out[i] = walked ? make_float4(col.x, col.y, col.z, __uint_as_float(path_rays(p))) : make_float4(0.0f, 0.0f, 0.0f, 0.0f); // (no walk: no color())
+    }
+};
+
+// ---- the scatter job: one color() body (rayweek1.cpp:517-534) with the recursion left to the caller -------------------------
+// The path job's load — same r1_seed_guard in the same place — with R1_SCATTER_UNIT_DIRECTIONS deciding whether the direction is normalised
+// (wave-uniform: a flag of the launch), one walk, and then in finish() the sky's three lines of shade_level or its hit arm, scatter_hit
+// (r1_shade.hpp): the very function shade_level calls, so the level cannot drift from the trace kernels'.  No depth, no attenuation stack:
+// 80 bytes per ray — the record, the scattered ray, the advanced states — as five whole 16-byte stores.  rays_out may be rays and seeds_out
+// seeds: a lane has read ray i before it writes ray i, and no lane touches another lane's ray.
+// Registers (profiles/r29/scatter_kernel_meta.txt, beside the cast's r10 / r15 and the path's r14): the job carries the Path's ten words through
+// the walk where the cast carries seven, and scatter_hit's rejection loop and dielectric arm sit behind it.  Under the cast's bound of eight
+// waves the compiler parks 6 .. 15 SGPRs in VGPR lanes (12 .. 32 v_readlane / v_writelane), with or without the root step by slots; under
+// seven, 2 in three of the kernels; under the path job's six none, at 52 .. 60 VGPRs — so eight waves per SIMD fit all the same.  waves():
+// R1_PATHQ_WAVES.  root_by_slots(): true, as the path job — at six waves the big-scene tree kernel holds it without a spill (58 VGPRs, 96
+// SGPRs), which the cast's at eight does not.
+struct R1ScatterJob
+{
+    typedef R1ScatterArgs Args;
+    static constexpr bool BOUNCES = false;
+    static constexpr int waves(bool) { return R1_PATHQ_WAVES; }
+    static constexpr bool root_by_slots(bool) { return true; }
+
+    Path p;
+    uint32_t best_id; // the walk's answer (step)
+    float best;
+
+    __device__ __forceinline__ void idle()
+    {
+        p.o = mk(0, 0, 0), p.d = mk(0, 0, 1);
+        p.s_scalar = p.s0 = p.s1 = p.s2 = 1u, p.k = 0u, p.depth = 0, p.sp = 0;
+    }
+    __device__ __forceinline__ bool load(const Args &A, const uint32_t i)
+    {
+        const float4 a = A.rays[2 * (size_t)i], b = A.rays[2 * (size_t)i + 1];
+        p.o = mk(a.x, a.y, a.z);
+        p.d = mk(b.x, b.y, b.z);
+        if (!(A.flags & R1_SCATTER_UNIT_DIRECTIONS)) // (wave-uniform)
+            p.d = vunit(p.d); // Ray::Ray, rayweek1.cpp:107
+        r1_sample_seed sd;
+        if (A.seeds) // (wave-uniform)
+        {
+            const uint4 s = A.seeds[i];
+            sd.scalar = s.x, sd.lane0 = s.y, sd.lane1 = s.z, sd.lane2 = s.w;
+        }
+        else
+            sd = r1_seed_sample(0u, A.first + i, 0u);
+        sd = r1_seed_guard(sd);
+        p.s_scalar = sd.scalar, p.s0 = sd.lane0, p.s1 = sd.lane1, p.s2 = sd.lane2;
+        p.k = i, p.depth = 0, p.sp = 0;
+        return query_finite(p.o.x) && query_finite(p.o.y) && query_finite(p.o.z) && query_finite(p.d.x) && query_finite(p.d.y) && query_finite(p.d.z);
+    }
+    __device__ __forceinline__ void seed(float &) const {}
+    __device__ __forceinline__ V3 O() const { return p.o; }
+    __device__ __forceinline__ V3 D() const { return p.d; }
+    __device__ __forceinline__ bool step(const Args &, const uint32_t id, const float t, uint32_t, int)
+    {
+        best_id = id, best = t;
+        return true;
+    }
+    __device__ __forceinline__ void finish(const Args &A, const uint32_t i, const bool walked)
+    {
+        // no walk: R1_SCATTER_NONE {0 0 0 NONE} {FLT_MAX -1 R1_MAT_NONE 0}, a ray of zero bytes, the guarded states
+        float4 r0 = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(R1_SCATTER_NONE));
+        float4 r1 = make_float4(FLT_MAX, __int_as_float(-1), __uint_as_float((uint32_t)R1_MAT_NONE), 0.0f);
+        float4 n0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), n1 = n0;
+        if (walked)
+        {
+            if (best_id != 0xFFFFFFFFu)
+            {
+                uint32_t type;
+                f4 sh;
+                const bool on = scatter_hit(A.t.scene, p, (int)best_id, best, type, sh);
+                const uint32_t scene_index = ((const r1_gu32 *)A.active_to_scene)[best_id];
+                const bool glass = type == 2u;
+                r0 = on ? make_float4(glass ? 1.0f : sh.y, glass ? 1.0f : sh.z, glass ? 1.0f : sh.w, __int_as_float(R1_SCATTER_SCATTERED))
+                        : make_float4(0.0f, 0.0f, 0.0f, __int_as_float(R1_SCATTER_ABSORBED)); // Metal::scatter() == false, rayweek1.cpp:432
+                r1 = make_float4(best, __uint_as_float(scene_index), __uint_as_float(type), 0.0f);
+                n0 = make_float4(p.o.x, p.o.y, p.o.z, FLT_MAX);
+                n1 = make_float4(p.d.x, p.d.y, p.d.z, 0.0f);
+            }
+            else
+            {
+                // miss: sky (rayweek1.cpp:532-534), lerp = (1 - t) * a + t * b (mymath.h:212-216): shade_level's three lines
+                const float t = 0.5f * (p.d.y + 1.0f);
+                const float omt = 1.0f - t;
+                r0 = make_float4(omt * 1.0f + t * 0.5f, omt * 1.0f + t * 0.7f, omt * 1.0f + t * 1.0f, __int_as_float(R1_SCATTER_SKY));
+            }
+        }
+        float4 *rec = A.out + 2 * (size_t)i, *ray = A.rays_out + 2 * (size_t)i;
+        rec[0] = r0, rec[1] = r1;
+        ray[0] = n0, ray[1] = n1;
+        A.seeds_out[i] = make_uint4(p.s_scalar, p.s0, p.s1, p.s2);
     }
 };
 
@@ -410,7 +503,10 @@ static const void *query_kernel(const int job, const int variant, const int big,
 #endif
     if (plain)
         return nullptr;
-    return job == R1_JOB_CAST ? query_kernel<R1CastJob>(variant, big) : job == R1_JOB_PATH ? query_kernel<R1PathJob>(variant, big) : nullptr;
+    return job == R1_JOB_CAST      ? query_kernel<R1CastJob>(variant, big)
+           : job == R1_JOB_PATH    ? query_kernel<R1PathJob>(variant, big)
+           : job == R1_JOB_SCATTER ? query_kernel<R1ScatterJob>(variant, big)
+                                   : nullptr;
 }
 
 // One launcher and one occupancy query, keyed by job, structure and big; args: the job's argument struct.  The C names below are their
@@ -448,4 +544,12 @@ extern "C" hipError_t r1_launch_trace_rays(const R1TraceRaysArgs *args, int vari
 extern "C" hipError_t r1_trace_rays_occupancy(int variant, int big, size_t dyn_lds, int *blocks_per_cu)
 {
     return query_occupancy(R1_JOB_PATH, variant, big, 0, dyn_lds, blocks_per_cu);
+}
+extern "C" hipError_t r1_launch_scatter_rays(const R1ScatterArgs *args, int variant, int big, int blocks, size_t dyn_lds, hipStream_t stream)
+{
+    return query_launch(R1_JOB_SCATTER, args, variant, big, 0, blocks, dyn_lds, stream);
+}
+extern "C" hipError_t r1_scatter_rays_occupancy(int variant, int big, size_t dyn_lds, int *blocks_per_cu)
+{
+    return query_occupancy(R1_JOB_SCATTER, variant, big, 0, dyn_lds, blocks_per_cu);
 }

@@ -35,11 +35,13 @@ __device__ __forceinline__ uint32_t fastdiv(uint32_t n, const R1FastDiv dv)
     return dv.pow2 ? (n >> dv.shift) : (__umulhi(n, dv.mul) >> dv.shift);
 }
 
-// seeds + primary ray of sample s of pixel (x, y) (rayweek1.cpp:759-760)
-// C: the camera — the launch's own (A.cam), or the frame's of a camera path (start_sample)
-__device__ __forceinline__ void start_ray(const R1TraceArgs &A, const R1DeviceCamera &C, Path &p, const int x, const int y, const uint32_t s, const uint32_t seed)
+// seeds + primary ray of sample s of pixel (x, y) (rayweek1.cpp:759-760) up to the Ray constructor: the origin in p.o, the stream states
+// after the camera's draws in p, and the direction as getRay hands it to the constructor — UN-normalised — returned.  start_ray, and
+// r1_camera_rays_kernel (r1_aux_kernels.hip), which stores exactly this.
+__device__ __forceinline__ V3 camera_ray(const int width, const float inv_w, const float inv_h, const R1DeviceCamera &C, Path &p, const int x, const int y,
+                                         const uint32_t s, const uint32_t seed)
 {
-    const r1_sample_seed sd = r1_seed_sample(seed, (uint32_t)(y * A.width + x), s);
+    const r1_sample_seed sd = r1_seed_sample(seed, (uint32_t)(y * width + x), s);
     p.s_scalar = sd.scalar;
     p.s0 = sd.lane0;
     p.s1 = sd.lane1;
@@ -50,8 +52,8 @@ __device__ __forceinline__ void start_ray(const R1TraceArgs &A, const R1DeviceCa
     // uv = (myrand01_x4(state4) + (x, y)) * (1/W, 1/H): lanes 0,1 used, lane 2 advances too
     const float j0 = rand01(p.s0), j1 = rand01(p.s1);
     (void)xorshift32(p.s2);
-    const float u = (j0 + (float)x) * A.inv_w;
-    const float v = (j1 + (float)y) * A.inv_h;
+    const float u = (j0 + (float)x) * inv_w;
+    const float v = (j1 + (float)y) * inv_h;
 
     // random_in_unit_disk (rayweek1.cpp:353-362): g++ argument order => y gets the first draw
     V3 dk;
@@ -67,9 +69,14 @@ __device__ __forceinline__ void start_ray(const R1TraceArgs &A, const R1DeviceCa
     const V3 offset = vadd(vscale(ld3(C.u), rd.x), vscale(ld3(C.v), rd.y));
     const V3 org = ld3(C.origin);
     p.o = vadd(org, offset);
-    const V3 dir =
-        vsub(vsub(vadd(vadd(ld3(C.lower_left), vscale(ld3(C.horizontal), u)), vscale(ld3(C.vertical), v)), org), offset);
-    p.d = vunit(dir);
+    return vsub(vsub(vadd(vadd(ld3(C.lower_left), vscale(ld3(C.horizontal), u)), vscale(ld3(C.vertical), v)), org), offset);
+}
+
+// the same with the constructor's normalisation: the primary ray in p
+// C: the camera — the launch's own (A.cam), or the frame's of a camera path (start_sample)
+__device__ __forceinline__ void start_ray(const R1TraceArgs &A, const R1DeviceCamera &C, Path &p, const int x, const int y, const uint32_t s, const uint32_t seed)
+{
+    p.d = vunit(camera_ray(A.width, A.inv_w, A.inv_h, C, p, x, y, s, seed));
 }
 
 // (local tile j, pixel `pix` of the padded tile) -> image coordinates; false outside the image (edge tiles)

@@ -50,6 +50,58 @@ __device__ __forceinline__ uint32_t stack_get(const uint32_t *stack, const uint3
     return (stack[w * R1_BLOCK + tid] >> sh) & 0x3FFu;
 }
 
+// ---- the hit arm of a color() level: the hit record (rayweek1.cpp:316-322), the material's draws, Material::scatter (r1_scatter.h) and the
+// Ray constructor's normalisation.  The scattered ray replaces p.o, p.d and the stream states of p advance.  Returns whether the material
+// scattered: false is Metal::scatter() == false (rayweek1.cpp:432).  type: R1_MAT_* of the sphere; sh: its {inv_radius, albedo rgb}.
+// Shared by shade_level — every trace kernel and the path queries — and the scatter queries' job (r1_query_kernels.hip), which is this
+// arm and nothing else.
+__device__ __forceinline__ bool scatter_hit(const R1DeviceScene &S, Path &p, const int hit, const float t_hit, uint32_t &type, f4 &sh)
+{
+    // hit record (rayweek1.cpp:316-322)
+    const f4 e = ((const f4 *)S.exact)[hit];
+    sh = ((const f4 *)S.shade)[hit];
+    const f4 mt = ((const f4 *)S.mat)[hit];
+    const V3 hp = vadd(p.o, vscale(p.d, t_hit));
+    const V3 n = vscale(vsub(hp, mk(e.x, e.y, e.z)), sh.x);
+    type = __float_as_uint(mt.x);
+    // Lambertian and Metal both draw random_in_unit_sphere from the x4 stream
+    // (rayweek1.cpp:405, :430; Metal even with fuzz == 0): one shared loop
+    V3 rius = mk(0, 0, 0);
+    if (type != 2u)
+        rius = random_in_unit_sphere(p);
+    V3 dir; // un-normalised scattered direction; Ray::Ray normalises (rayweek1.cpp:107)
+    if (type == 0u)
+        dir = r1s_lambertian(hp, n, rius); // Lambertian::scatter rayweek1.cpp:403-409
+    else
+    {
+        // Metal and Dielectric both reflect (rayweek1.cpp:414-417): once, for whichever of the two arms the wave's lanes take
+        // (r1_scatter.h)
+        const float ddn = vdot(p.d, n);
+        const V3 refl = r1s_reflect(p.d, n, ddn);
+        if (type == 1u)
+            dir = r1s_metal(refl, rius, mt.y); // Metal::scatter rayweek1.cpp:427-433
+        else
+        {
+            // Dielectric::scatter rayweek1.cpp:470-511 (attenuation 1: nothing to push), without the outward normal;
+            // mt.z = 1.0f / _refIdx, divided on the host (same IEEE division)
+            const R1Dielectric k = r1s_dielectric(p.d, n, ddn, mt.y, mt.z);
+            // refract rayweek1.cpp:439-452
+            float reflect_prob = 1.0f;
+            V3 refracted = mk(0, 0, 0);
+            if (k.discriminant > 0)
+            {
+                refracted = r1s_refracted(p.d, n, ddn, k, r1_sqrt_exact(k.discriminant, true));
+                reflect_prob = r1s_schlick(mt.w, k.cosine); // rayweek1.cpp:454-459
+            }
+            dir = (rand01(p.s_scalar) < reflect_prob) ? refl : refracted;
+        }
+    }
+    const V3 nd = vunit_guarded(dir);
+    p.o = hp;
+    p.d = nd;
+    return type == 2u || type == 0u || vdot(nd, n) > 0;
+}
+
 // ---- one color() level after the hit test (rayweek1.cpp:517-534): count the ray, then either
 // scatter (new ray in p, hit index pushed on the attenuation stack) or finish the path: sky
 // colour times the stacked attenuations, or black.  Returns true when the path has ended, with
@@ -64,49 +116,9 @@ __device__ __forceinline__ bool shade_level(const R1TraceArgs &A, Path &p, const
     {
         if (p.depth < A.max_bounces)
         {
-            // hit record (rayweek1.cpp:316-322)
-            const f4 e = ((const f4 *)A.scene.exact)[hit];
-            const f4 sh = ((const f4 *)A.scene.shade)[hit];
-            const f4 mt = ((const f4 *)A.scene.mat)[hit];
-            const V3 hp = vadd(p.o, vscale(p.d, t_hit));
-            const V3 n = vscale(vsub(hp, mk(e.x, e.y, e.z)), sh.x);
-            const uint32_t type = __float_as_uint(mt.x);
-            // Lambertian and Metal both draw random_in_unit_sphere from the x4 stream
-            // (rayweek1.cpp:405, :430; Metal even with fuzz == 0): one shared loop
-            V3 rius = mk(0, 0, 0);
-            if (type != 2u)
-                rius = random_in_unit_sphere(p);
-            V3 dir; // un-normalised scattered direction; Ray::Ray normalises (rayweek1.cpp:107)
-            if (type == 0u)
-                dir = r1s_lambertian(hp, n, rius); // Lambertian::scatter rayweek1.cpp:403-409
-            else
-            {
-                // Metal and Dielectric both reflect (rayweek1.cpp:414-417): once, for whichever of the two arms the wave's lanes take
-                // (r1_scatter.h)
-                const float ddn = vdot(p.d, n);
-                const V3 refl = r1s_reflect(p.d, n, ddn);
-                if (type == 1u)
-                    dir = r1s_metal(refl, rius, mt.y); // Metal::scatter rayweek1.cpp:427-433
-                else
-                {
-                    // Dielectric::scatter rayweek1.cpp:470-511 (attenuation 1: nothing to push), without the outward normal;
-                    // mt.z = 1.0f / _refIdx, divided on the host (same IEEE division)
-                    const R1Dielectric k = r1s_dielectric(p.d, n, ddn, mt.y, mt.z);
-                    // refract rayweek1.cpp:439-452
-                    float reflect_prob = 1.0f;
-                    V3 refracted = mk(0, 0, 0);
-                    if (k.discriminant > 0)
-                    {
-                        refracted = r1s_refracted(p.d, n, ddn, k, r1_sqrt_exact(k.discriminant, true));
-                        reflect_prob = r1s_schlick(mt.w, k.cosine); // rayweek1.cpp:454-459
-                    }
-                    dir = (rand01(p.s_scalar) < reflect_prob) ? refl : refracted;
-                }
-            }
-            const V3 nd = vunit_guarded(dir);
-            p.o = hp;
-            p.d = nd;
-            if (type == 2u || type == 0u || vdot(nd, n) > 0)
+            uint32_t type;
+            f4 sh;
+            if (scatter_hit(A.scene, p, hit, t_hit, type, sh))
             {
                 if (type != 2u)
                 {
