@@ -1,6 +1,7 @@
-// r1_aux_kernels.hip — the kernels around the trace kernel (wavefront variant, resolve, linear resolve and read-out, progressive accumulate, batch counts, assemble) and the launch
-// dispatch called from r1_frame.cpp and r1_render.cpp.  From the trace kernels' device functions it takes sweep_bvh (r1_hit_tree.hpp), start_sample,
-// path_store / path_load and quantise_pixel (r1_sample.hpp) and shade_level (r1_shade.hpp); the trace kernel itself: r1_trace.hpp.
+// r1_aux_kernels.hip — the kernels in front of and beside the trace kernel (wavefront variant, camera rays, the put kernels) and the launch
+// dispatch called from r1_frame.cpp and r1_queries.cpp.  From the trace kernels' device functions it takes sweep_bvh (r1_hit_tree.hpp), start_sample,
+// camera_ray, path_store / path_load (r1_sample.hpp) and shade_level (r1_shade.hpp); the trace kernel itself: r1_trace.hpp; what closes a frame:
+// r1_close_kernels.hip.
 #include "r1_hit_tree.hpp"
 #include "r1_sample.hpp"
 #include "r1_shade.hpp"
@@ -112,136 +113,6 @@ __global__ void __launch_bounds__(R1_BLOCK) r1_wf_shade(const R1WaveArgs W)
         atomicAdd(W.t.num_rays, lane_rays);
 }
 
-// ============================================================================================
-// Resolve: one thread per pixel of this shard; sums the spp samples in sample order and
-// quantises exactly as rayweek1.cpp:765-775.
-// ============================================================================================
-__global__ void __launch_bounds__(256) r1_resolve_kernel(const R1ResolveArgs A)
-{
-    if (blockIdx.x == 0 && blockIdx.y == 0 && A.rays_src)
-    {
-        static_assert(R1_COUNTER_BYTES == 256 * 16, "one 16-byte store per thread zeroes the counter block");
-        if (threadIdx.x == 0)
-            *A.rays_dst = *A.rays_src;
-        __syncthreads();
-        if (A.reset)
-            ((uint4 *)A.reset)[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
-    }
-    const uint32_t tiles_stride = gridDim.y;
-    const uint32_t tiles_all = A.n_local_tiles * (A.n_frames ? A.n_frames : 1u);
-    for (uint32_t lt_all = blockIdx.y; lt_all < tiles_all; lt_all += tiles_stride)
-    {
-        const uint32_t f = lt_all / A.n_local_tiles, lt = lt_all - f * A.n_local_tiles; // frame of the batch, its local tile
-        uint8_t *const out = A.out + (size_t)f * A.out_stride;
-        const uint32_t tile = (uint32_t)A.shard + lt * (uint32_t)A.num_shards;
-        const int x0 = (int)(tile % (uint32_t)A.tiles_x) * A.tile_w;
-        const int y0 = (int)(tile / (uint32_t)A.tiles_x) * A.tile_h;
-        const int tw = min(A.tile_w, A.width - x0);
-        const int th = min(A.tile_h, A.height - y0);
-        const uint32_t base = lt_all * A.full;
-        unsigned long long rays = 0;
-        for (uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x; pix < (uint32_t)(A.tile_w * A.tile_h); pix += gridDim.x * blockDim.x)
-        {
-            const int ly = (int)(pix / (uint32_t)A.tile_w);
-            const int lx = (int)(pix - (uint32_t)ly * (uint32_t)A.tile_w);
-            if (lx >= tw || ly >= th)
-                continue; // void slots of an edge tile
-            const uint32_t tile_px = (uint32_t)(A.tile_w * A.tile_h);
-            const float4 *s = A.samples + base + pix; // [tile][sample][pixel]
-            float cr = 0, cg = 0, cb = 0;
-            for (int i = 0; i < A.spp; ++i)
-            {
-                const float4 v = s[(size_t)i * tile_px];
-                cr += v.x, cg += v.y, cb += v.z; // col += color(...) rayweek1.cpp:762
-                rays += __float_as_uint(v.w);
-            }
-            uint8_t r, g, b;
-            quantise_pixel(cr, cg, cb, A.inv_spp, r, g, b);
-            size_t o;
-            if (A.block_layout)
-                o = ((size_t)lt * A.tile_h * A.tile_w + (size_t)ly * A.tile_w + lx) * 3;
-            else
-                o = ((size_t)(y0 + ly) * A.width + (x0 + lx)) * 3;
-            out[o + 0] = r;
-            out[o + 1] = g;
-            out[o + 2] = b;
-        }
-        if (A.frame_rays) // frame batches: the frame's ray count is the sum over its samples (rayweek1.cpp:809-813)
-        {
-            // no atomics: 15 000 waves adding to one word per frame cost more than the whole resolve (a returning or
-            // non-returning atomic on ONE line sustains ~88 M/s on this chip, tools/ubench_atomic.hip).  Every workgroup
-            // stores ONE partial sum per tile it touches; r1_batch_counts_kernel adds them up per frame.
-            __shared__ unsigned long long s_part[4];
-            for (int off = 32; off > 0; off >>= 1)
-                rays += __shfl_down(rays, off, 64);
-            if ((threadIdx.x & 63u) == 0)
-                s_part[threadIdx.x >> 6] = rays;
-            __syncthreads();
-            if (threadIdx.x == 0)
-                A.frame_rays[(size_t)lt_all * gridDim.x + blockIdx.x] = s_part[0] + s_part[1] + s_part[2] + s_part[3];
-            __syncthreads();
-        }
-    }
-}
-
-// ============================================================================================
-// Linear frames (r1_render_linear*): one more launch behind a whole frame's trace and whatever closes it.  The resolve's
-// indexing and its sums — 0.0f plus the records' x, y, z in sample order — times inv_spp, the first line of quantise_pixel, stored as
-// three floats per pixel.  The w word is never read: a landing launch leaves its tag there.
-// ============================================================================================
-__global__ void __launch_bounds__(256) r1_resolve_linear_kernel(const R1LinearArgs A)
-{
-    const uint32_t tile_px = (uint32_t)(A.tile_w * A.tile_h);
-    for (uint32_t lt = blockIdx.y; lt < A.n_tiles; lt += gridDim.y)
-    {
-        const int x0 = (int)(lt % (uint32_t)A.tiles_x) * A.tile_w;
-        const int y0 = (int)(lt / (uint32_t)A.tiles_x) * A.tile_h;
-        const int tw = min(A.tile_w, A.width - x0);
-        const int th = min(A.tile_h, A.height - y0);
-        for (uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x; pix < tile_px; pix += gridDim.x * blockDim.x)
-        {
-            const int ly = (int)(pix / (uint32_t)A.tile_w);
-            const int lx = (int)(pix - (uint32_t)ly * (uint32_t)A.tile_w);
-            if (lx >= tw || ly >= th)
-                continue; // void slots of an edge tile
-            const float *s = (const float *)(A.samples + (size_t)lt * A.full + pix); // [tile][sample][pixel]
-            float cr = 0, cg = 0, cb = 0;
-            for (int i = 0; i < A.spp; ++i)
-            {
-                const float *v = s + (size_t)i * tile_px * 4;
-                cr += v[0], cg += v[1], cb += v[2]; // col += color(...) rayweek1.cpp:762
-            }
-            float *const o = A.out + ((size_t)(y0 + ly) * A.width + (x0 + lx)) * 3;
-            o[0] = cr * A.inv_spp, o[1] = cg * A.inv_spp, o[2] = cb * A.inv_spp; // col *= 1 / spp rayweek1.cpp:765
-        }
-    }
-}
-
-// The read-out of the accumulators (r1_pass_linear, r1_render_adaptive_linear): r1_accum_kernel's indexing over the padded [tile][pixel]
-// sums, each times (float)(1.0f / n) — n the same for every tile, or (A.report) the samples the tile's own report says it holds.
-__global__ void __launch_bounds__(256) r1_accum_linear_kernel(const R1ReadoutArgs A)
-{
-    const uint32_t tile_px = (uint32_t)(A.tile_w * A.tile_h);
-    for (uint32_t lt = blockIdx.y; lt < A.n_tiles; lt += gridDim.y)
-    {
-        const int x0 = (int)(lt % (uint32_t)A.tiles_x) * A.tile_w;
-        const int y0 = (int)(lt / (uint32_t)A.tiles_x) * A.tile_h;
-        const int tw = min(A.tile_w, A.width - x0);
-        const int th = min(A.tile_h, A.height - y0);
-        const float inv = A.report ? (float)(1.0f / A.report[lt].spp) : A.inv_n; // rayweek1.cpp:765 at the samples the sums hold
-        for (uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x; pix < tile_px; pix += gridDim.x * blockDim.x)
-        {
-            const int ly = (int)(pix / (uint32_t)A.tile_w);
-            const int lx = (int)(pix - (uint32_t)ly * (uint32_t)A.tile_w);
-            if (lx >= tw || ly >= th)
-                continue; // void slots of an edge tile
-            const float4 a = A.accum[(size_t)lt * tile_px + pix];
-            float *const o = A.out + ((size_t)(y0 + ly) * A.width + (x0 + lx)) * 3;
-            o[0] = a.x * inv, o[1] = a.y * inv, o[2] = a.z * inv;
-        }
-    }
-}
-
 // r1_camera_rays_device: one lane per sample k of [first, first + n), k = (y * width + x) * spp + s as r1_render_samples
 // orders its records.  camera_ray (r1_sample.hpp) is start_ray without the Ray constructor: the record holds the direction un-normalised,
 // as the host's r1_camera_rays writes it, and the stream states after the camera's draws.  k runs to width * height * spp, which 64 bits hold.
@@ -261,248 +132,6 @@ __global__ void __launch_bounds__(256) r1_camera_rays_kernel(const R1CameraRaysA
         A.rays[2 * i + 1] = make_float4(dir.x, dir.y, dir.z, 0.0f);
         A.seeds[i] = make_uint4(p.s_scalar, p.s0, p.s1, p.s2);
     }
-}
-
-// ============================================================================================
-// Progressive passes (r1_render_pass): in place of the resolve launch.  One thread per pixel of a padded tile, as the resolve: the
-// accumulator (or 0.0f on the pass that starts the frame) plus the pass's records in sample order — the same sequence of fp32 adds the
-// resolve of the whole frame makes — stored back, then quantised as the resolve does with n = first_sample + spp samples summed.
-// ============================================================================================
-__global__ void __launch_bounds__(256) r1_accum_kernel(const R1AccumArgs A)
-{
-    if (blockIdx.x == 0 && blockIdx.y == 0 && A.rays_src)
-    {
-        // the pass's ray count (the trace kernel's), then the counter block zeroed for the next launch: as r1_resolve_kernel
-        if (threadIdx.x == 0)
-            *A.rays_dst = *A.rays_src;
-        __syncthreads();
-        if (A.reset)
-            ((uint4 *)A.reset)[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
-    }
-    const uint32_t tile_px = (uint32_t)(A.tile_w * A.tile_h);
-    for (uint32_t lt = blockIdx.y; lt < A.n_local_tiles; lt += gridDim.y)
-    {
-        const int x0 = (int)(lt % (uint32_t)A.tiles_x) * A.tile_w;
-        const int y0 = (int)(lt / (uint32_t)A.tiles_x) * A.tile_h;
-        const int tw = min(A.tile_w, A.width - x0);
-        const int th = min(A.tile_h, A.height - y0);
-        for (uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x; pix < tile_px; pix += gridDim.x * blockDim.x)
-        {
-            const int ly = (int)(pix / (uint32_t)A.tile_w);
-            const int lx = (int)(pix - (uint32_t)ly * (uint32_t)A.tile_w);
-            if (lx >= tw || ly >= th)
-                continue; // void slots of an edge tile
-            float4 *const acc = A.accum + (size_t)lt * tile_px + pix;
-            float cr = 0, cg = 0, cb = 0;
-            if (!A.fresh)
-            {
-                const float4 a = *acc;
-                cr = a.x, cg = a.y, cb = a.z;
-            }
-            const float4 *s = A.samples + (size_t)lt * A.full + pix; // [tile][sample][pixel]
-            for (int i = 0; i < A.spp; ++i)
-            {
-                const float4 v = s[(size_t)i * tile_px];
-                cr += v.x, cg += v.y, cb += v.z; // col += color(...) rayweek1.cpp:762
-            }
-            *acc = make_float4(cr, cg, cb, 0.0f);
-            if (A.out)
-            {
-                uint8_t r, g, b;
-                quantise_pixel(cr, cg, cb, A.inv_n, r, g, b);
-                uint8_t *const o = A.out + ((size_t)(y0 + ly) * A.width + (x0 + lx)) * 3;
-                o[0] = r, o[1] = g, o[2] = b;
-            }
-        }
-    }
-}
-
-// ============================================================================================
-// Adaptive sampling (r1_render_adaptive): in place of r1_accum_kernel after a pass over listed tiles.  Workgroup j serves list position j,
-// i.e. tile list[j]: per pixel the `all` accumulator plus the pass's records in sample order, the `even` accumulator plus those of even
-// GLOBAL sample index, both stored back (indexed by tile, so that they survive the list shrinking) and quantised as the resolve does; the
-// `all` bytes go into the image; |byte_all - byte_even| over the tile's pixels inside the image and the three channels is reduced to its
-// maximum and its sum — integers, so the order of the reduction cannot matter — and one lane tests the rule and writes the tile's report.
-// ============================================================================================
-__global__ void __launch_bounds__(256) r1_adapt_accum_kernel(const R1AdaptArgs A)
-{
-    if (blockIdx.x == 0 && A.rays_src)
-    {
-        // the pass's ray count (the trace kernel's), then the counter block zeroed for the next launch: as r1_resolve_kernel
-        if (threadIdx.x == 0)
-            *A.rays_dst = *A.rays_src;
-        __syncthreads();
-        if (A.reset)
-            ((uint4 *)A.reset)[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
-    }
-    __shared__ uint32_t s_max[4], s_sum[4];
-    const uint32_t tile_px = (uint32_t)(A.tile_w * A.tile_h);
-    for (uint32_t j = blockIdx.x; j < A.n_listed; j += gridDim.x)
-    {
-        const uint32_t tile = A.list[j];
-        const int x0 = (int)(tile % (uint32_t)A.tiles_x) * A.tile_w;
-        const int y0 = (int)(tile / (uint32_t)A.tiles_x) * A.tile_h;
-        const int tw = min(A.tile_w, A.width - x0);
-        const int th = min(A.tile_h, A.height - y0);
-        uint32_t emax = 0, esum = 0;
-        for (uint32_t pix = threadIdx.x; pix < tile_px; pix += blockDim.x)
-        {
-            const int ly = (int)(pix / (uint32_t)A.tile_w);
-            const int lx = (int)(pix - (uint32_t)ly * (uint32_t)A.tile_w);
-            if (lx >= tw || ly >= th)
-                continue; // void slots of an edge tile
-            float4 *const pa = A.all + (size_t)tile * tile_px + pix, *const pe = A.even + (size_t)tile * tile_px + pix;
-            float ar = 0, ag = 0, ab = 0, er = 0, eg = 0, eb = 0;
-            if (A.first_sample)
-            {
-                const float4 a = *pa, e = *pe;
-                ar = a.x, ag = a.y, ab = a.z, er = e.x, eg = e.y, eb = e.z;
-            }
-            const float4 *s = A.samples + ((size_t)j * (uint32_t)A.spp) * tile_px + pix; // [list position][sample][pixel]
-            for (int i = 0; i < A.spp; ++i)
-            {
-                const float4 v = s[(size_t)i * tile_px];
-                ar += v.x, ag += v.y, ab += v.z; // col += color(...) rayweek1.cpp:762
-                if (((A.first_sample + (uint32_t)i) & 1u) == 0u)
-                    er += v.x, eg += v.y, eb += v.z;
-            }
-            *pa = make_float4(ar, ag, ab, 0.0f);
-            *pe = make_float4(er, eg, eb, 0.0f);
-            uint8_t r, g, b, r2, g2, b2;
-            quantise_pixel(ar, ag, ab, A.inv_all, r, g, b);
-            quantise_pixel(er, eg, eb, A.inv_even, r2, g2, b2);
-            uint8_t *const o = A.out + ((size_t)(y0 + ly) * A.width + (x0 + lx)) * 3;
-            o[0] = r, o[1] = g, o[2] = b;
-            const uint32_t dr = (uint32_t)abs((int)r - (int)r2), dg = (uint32_t)abs((int)g - (int)g2), db = (uint32_t)abs((int)b - (int)b2);
-            emax = max(emax, max(dr, max(dg, db)));
-            esum += dr + dg + db;
-        }
-        for (int off = 32; off > 0; off >>= 1)
-        {
-            emax = max(emax, (uint32_t)__shfl_down(emax, off, 64));
-            esum += __shfl_down(esum, off, 64);
-        }
-        if ((threadIdx.x & 63u) == 0)
-            s_max[threadIdx.x >> 6] = emax, s_sum[threadIdx.x >> 6] = esum;
-        __syncthreads();
-        if (threadIdx.x == 0)
-        {
-            emax = max(max(s_max[0], s_max[1]), max(s_max[2], s_max[3]));
-            esum = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
-            const bool settled = (int32_t)emax <= A.max_delta &&
-                                 (unsigned long long)esum * 256ull <= (unsigned long long)A.mean_delta_q8 * 3ull * (unsigned long long)(tw * th);
-            R1TileReport rp;
-            rp.spp = (int32_t)A.first_sample + A.spp, rp.settled = settled ? 1 : 0, rp.err_max = emax, rp.err_sum = esum;
-            A.report[tile] = rp;
-        }
-        __syncthreads();
-    }
-}
-
-// The next pass's list: the tiles of this pass's list that are still active — not settled, and (`at_cap` == 0) not at the cap — in the
-// order they had, which is ascending; their number goes to *count_out (a page-locked host word, or device memory).  One workgroup: a wave
-// places its tiles by ballot + prefix popcount, the four waves through LDS.  cur == null: every tile of the frame, in order (the first pass).
-__global__ void __launch_bounds__(256) r1_adapt_compact_kernel(const uint32_t *cur, uint32_t n_cur, const R1TileReport *report, uint32_t at_cap,
-                                                               uint32_t *next, uint32_t *count_out)
-{
-    __shared__ uint32_t s_cnt[4];
-    uint32_t base = 0;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    for (uint32_t i0 = 0; i0 < n_cur; i0 += 256u)
-    {
-        const uint32_t i = i0 + threadIdx.x;
-        uint32_t tile = 0;
-        bool keep = false;
-        if (i < n_cur)
-        {
-            tile = cur ? cur[i] : i;
-            keep = cur ? (!at_cap && report[tile].settled == 0) : true;
-        }
-        const unsigned long long m = __ballot(keep);
-        if (lane == 0)
-            s_cnt[wave] = (uint32_t)__popcll(m);
-        __syncthreads();
-        uint32_t before = 0;
-        for (uint32_t w = 0; w < wave; ++w)
-            before += s_cnt[w];
-        const uint32_t total = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-        if (keep)
-            next[base + before + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = tile;
-        base += total;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0)
-        *count_out = base;
-}
-
-// Frame batches: frame f's ray count = the sum of the partial sums the resolve launch left per (tile, workgroup column);
-// one workgroup per frame; the count goes next to the frame's pixels (out + f * out_stride + rays_offset).
-__global__ void __launch_bounds__(256)
-    r1_batch_counts_kernel(const unsigned long long *__restrict__ partial, uint32_t per_frame, uint8_t *__restrict__ out, size_t out_stride,
-                           size_t rays_offset)
-{
-    __shared__ unsigned long long s_part[4];
-    const unsigned long long *src = partial + (size_t)blockIdx.x * per_frame;
-    unsigned long long sum = 0;
-    for (uint32_t i = threadIdx.x; i < per_frame; i += blockDim.x)
-        sum += src[i];
-    for (int off = 32; off > 0; off >>= 1)
-        sum += __shfl_down(sum, off, 64);
-    if ((threadIdx.x & 63u) == 0)
-        s_part[threadIdx.x >> 6] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        *(unsigned long long *)(out + (size_t)blockIdx.x * out_stride + rays_offset) = s_part[0] + s_part[1] + s_part[2] + s_part[3];
-}
-
-// Scatter gathered dense tile blocks (shard-major) into a row-major image.  Frame batches: blockIdx.y = frame; the
-// frame's blocks start frame_in bytes after `blocks` (gathered layout [shard][frame][record]) and its image frame_out
-// bytes after `rgb`.
-__global__ void __launch_bounds__(256)
-    r1_assemble_kernel(const uint8_t *__restrict__ blocks_all, uint8_t *__restrict__ rgb_all, int width, int height, int tile_w, int tile_h,
-                       int tiles_x, int num_shards, size_t shard_stride, size_t frame_in, size_t frame_out, size_t total_offset, long long total_out,
-                       int want_total)
-{
-    const uint8_t *__restrict__ blocks = blocks_all + (size_t)blockIdx.y * frame_in;
-    uint8_t *__restrict__ rgb = rgb_all + (size_t)blockIdx.y * frame_out;
-    // gathered RECORDS (block + uint64 count at the end of every record): the frame's ray count is the sum of the
-    // shards' counts (rayweek1.cpp:809-813), written next to the image so that one copy brings both to the host
-    if (want_total && blockIdx.x == 0 && threadIdx.x == 0)
-    {
-        unsigned long long sum = 0;
-        for (int sh = 0; sh < num_shards; ++sh)
-            sum += *(const unsigned long long *)(blocks + (size_t)sh * shard_stride + total_offset);
-        *(unsigned long long *)(rgb + total_out) = sum;
-    }
-    const size_t n = (size_t)width * height;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-    {
-        const int y = (int)(i / (size_t)width), x = (int)(i - (size_t)y * width);
-        const int tile = (y / tile_h) * tiles_x + (x / tile_w);
-        const int shard = tile % num_shards, lt = tile / num_shards;
-        const size_t src = (size_t)shard * shard_stride + (((size_t)lt * tile_h + (size_t)(y % tile_h)) * tile_w + (x % tile_w)) * 3;
-        rgb[3 * i + 0] = blocks[src + 0];
-        rgb[3 * i + 1] = blocks[src + 1];
-        rgb[3 * i + 2] = blocks[src + 2];
-    }
-}
-
-// R1_LAND: the per-tile countdowns and per-frame accumulators of a context, set when its tiling changes (afterwards the resolvers
-// re-arm what they consume): tile t of the launch lacks (valid pixels of its tile) x spp samples.
-__global__ void __launch_bounds__(256) r1_land_arm_kernel(uint32_t *tile_cnt, unsigned long long *frame_rays, uint32_t *frame_left, uint32_t n_frames,
-                                                          uint32_t n_local_tiles, int width, int height, int spp, int tile_w, int tile_h, int tiles_x,
-                                                          int shard, int num_shards)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n_frames)
-        frame_rays[i] = 0ull, frame_left[i] = n_local_tiles;
-    if (i >= n_frames * n_local_tiles)
-        return;
-    const uint32_t lt = i % n_local_tiles;
-    const uint32_t tile = (uint32_t)shard + lt * (uint32_t)num_shards;
-    const int x0 = (int)(tile % (uint32_t)tiles_x) * tile_w, y0 = (int)(tile / (uint32_t)tiles_x) * tile_h;
-    const int tw = min(tile_w, width - x0), th = min(tile_h, height - y0);
-    tile_cnt[(size_t)i * R1_LAND_CNT_STRIDE] = (uint32_t)(tw * th * spp);
 }
 
 // six words into device memory, the values travelling in the kernel arguments (copied when the launch is enqueued: no host buffer
@@ -530,16 +159,7 @@ __global__ void r1_put_cameras_kernel(float4 *dst, const R1CameraRows rows, uint
         dst[threadIdx.x] = rows.row[threadIdx.x];
 }
 
-// ---- launchers (called from r1_frame.cpp, r1_render.cpp) -----------------------------------------------------
-
-extern "C" hipError_t r1_launch_land_arm(uint32_t *tile_cnt, unsigned long long *frame_rays, uint32_t *frame_left, uint32_t n_frames, uint32_t n_local_tiles,
-                                         int width, int height, int spp, int tile_w, int tile_h, int tiles_x, int shard, int num_shards, hipStream_t stream)
-{
-    const uint32_t n = n_frames * n_local_tiles > n_frames ? n_frames * n_local_tiles : n_frames;
-    hipLaunchKernelGGL(r1_land_arm_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, tile_cnt, frame_rays, frame_left, n_frames, n_local_tiles, width,
-                       height, spp, tile_w, tile_h, tiles_x, shard, num_shards);
-    return hipGetLastError();
-}
+// ---- launchers (called from r1_frame.cpp, r1_queries.cpp) ----------------------------------------------------
 
 extern "C" hipError_t r1_launch_put6(void *dst, const uint32_t *w, hipStream_t stream)
 {
@@ -619,87 +239,10 @@ extern "C" hipError_t r1_launch_wavefront(R1WaveArgs *w, int blocks, hipStream_t
     return hipGetLastError();
 }
 
-// max_rows: at most this many rows of workgroups (one row walks tiles row, row + rows, ...); 0 = one row per tile.  Frames in flight use
-// FEW, long-lived workgroups: a resolve launch shares the chip with persistent trace workgroups and gets a slot only when one of them
-// exits, so what it costs is the number of slot grants it needs, not its 26 us of work (profiles/r03/burst_timeline_20_frames.txt).
-extern "C" hipError_t r1_launch_resolve(const R1ResolveArgs *args, int max_rows, hipStream_t stream)
-{
-    const int tile_pix = args->tile_w * args->tile_h;
-    const int bx = (tile_pix + 255) / 256;
-    const uint32_t tiles_all = args->n_local_tiles * (args->n_frames ? args->n_frames : 1u);
-    int by = (int)(tiles_all < 65535u ? tiles_all : 65535u);
-    if (max_rows > 0 && by > max_rows)
-        by = max_rows;
-    hipLaunchKernelGGL(r1_resolve_kernel, dim3(bx, by), dim3(256), 0, stream, *args);
-    if (args->frame_rays) // frame batches: per-frame ray counts from the launch's partial sums ([tile of the batch][bx])
-        hipLaunchKernelGGL(r1_batch_counts_kernel, dim3(args->n_frames), dim3(256), 0, stream, args->frame_rays, args->n_local_tiles * (uint32_t)bx,
-                           args->out, args->out_stride, args->rays_offset);
-    return hipGetLastError();
-}
-
-// one row of workgroups per tile (at most 65535 rows), as the synchronous frame's resolve launch
-extern "C" hipError_t r1_launch_accum(const R1AccumArgs *args, hipStream_t stream)
-{
-    const int bx = (args->tile_w * args->tile_h + 255) / 256;
-    const int by = (int)(args->n_local_tiles < 65535u ? args->n_local_tiles : 65535u);
-    hipLaunchKernelGGL(r1_accum_kernel, dim3(bx, by), dim3(256), 0, stream, *args);
-    return hipGetLastError();
-}
-
-// linear frames: one row of workgroups per tile (at most 65535 rows), as r1_launch_accum; a frame in flight takes the resolve's few rows
-extern "C" hipError_t r1_launch_resolve_linear(const R1LinearArgs *args, int max_rows, hipStream_t stream)
-{
-    const int bx = (args->tile_w * args->tile_h + 255) / 256;
-    int by = (int)(args->n_tiles < 65535u ? args->n_tiles : 65535u);
-    if (max_rows > 0 && by > max_rows)
-        by = max_rows;
-    hipLaunchKernelGGL(r1_resolve_linear_kernel, dim3(bx, by), dim3(256), 0, stream, *args);
-    return hipGetLastError();
-}
-
-extern "C" hipError_t r1_launch_accum_linear(const R1ReadoutArgs *args, hipStream_t stream)
-{
-    const int bx = (args->tile_w * args->tile_h + 255) / 256;
-    const int by = (int)(args->n_tiles < 65535u ? args->n_tiles : 65535u);
-    hipLaunchKernelGGL(r1_accum_linear_kernel, dim3(bx, by), dim3(256), 0, stream, *args);
-    return hipGetLastError();
-}
-
 // one lane per sample, grid-stride beyond 2^16 workgroups
 extern "C" hipError_t r1_launch_camera_rays(const R1CameraRaysArgs *args, hipStream_t stream)
 {
     const unsigned long long blocks = (args->n + 255u) / 256u;
     hipLaunchKernelGGL(r1_camera_rays_kernel, dim3((unsigned)(blocks < 65536u ? blocks : 65536u)), dim3(256), 0, stream, *args);
-    return hipGetLastError();
-}
-
-// one workgroup per listed tile (at most 65535, each walking list positions a grid apart), then the next pass's list
-extern "C" hipError_t r1_launch_adapt_accum(const R1AdaptArgs *args, hipStream_t stream)
-{
-    const int bx = (int)(args->n_listed < 65535u ? args->n_listed : 65535u);
-    hipLaunchKernelGGL(r1_adapt_accum_kernel, dim3(bx), dim3(256), 0, stream, *args);
-    return hipGetLastError();
-}
-
-extern "C" hipError_t r1_launch_adapt_compact(const uint32_t *cur, uint32_t n_cur, const R1TileReport *report, uint32_t at_cap, uint32_t *next,
-                                              uint32_t *count_out, hipStream_t stream)
-{
-    hipLaunchKernelGGL(r1_adapt_compact_kernel, dim3(1), dim3(256), 0, stream, cur, n_cur, report, at_cap, next, count_out);
-    return hipGetLastError();
-}
-
-// blocks: gathered tile blocks or records; per frame f (0 .. n_frames - 1): shard sh's block at blocks + f * frame_in + sh * shard_stride,
-// image at rgb + f * frame_out.  want_total: the shards' uint64 counts at (block start + total_offset) are summed into the
-// uint64 at (the frame's image + total_out).
-extern "C" hipError_t r1_launch_assemble(const void *blocks, void *rgb, int width, int height, int tile_w, int tile_h, int tiles_x, int num_shards,
-                                         size_t shard_stride, int n_frames, size_t frame_in, size_t frame_out, size_t total_offset, long long total_out,
-                                         int want_total, hipStream_t stream)
-{
-    const size_t n = (size_t)width * height;
-    int grid = (int)((n + 255) / 256);
-    if (grid > 8192)
-        grid = 8192;
-    hipLaunchKernelGGL(r1_assemble_kernel, dim3(grid, n_frames > 0 ? n_frames : 1), dim3(256), 0, stream, (const uint8_t *)blocks, (uint8_t *)rgb, width,
-                       height, tile_w, tile_h, tiles_x, num_shards, shard_stride, frame_in, frame_out, total_offset, total_out, want_total);
     return hipGetLastError();
 }

@@ -214,7 +214,7 @@ struct Landing
 };
 
 // A progressive pass (r1_render_pass): samples [first_sample, first_sample + spp) traced by the R1_MODE_PASS kernels, then r1_accum_kernel instead of
-// the resolve launch.  d_out of enqueue_frame receives the preview unless `image` is false.
+// the resolve launch.  FrameJob::out receives the preview unless `image` is false.
 // A pass of r1_render_adaptive has a tile list: the launch's tiles are list[0, n_listed) of the frame's, traced by the R1_MODE_LISTED kernels and summed
 // and tested by r1_adapt_accum_kernel (accumulators and reports: the context's, indexed by tile of the frame).
 struct Pass
@@ -231,6 +231,20 @@ struct Pass
 struct Linear
 {
     float *out = nullptr; // device address of width*height*3 floats, row-major (device memory, or page-locked host memory)
+};
+
+// What an entry point asks enqueue_frame for: the call sites set the fields they need by name on a local.
+struct FrameJob
+{
+    void *out = nullptr;     // device address of the pixels: row-major image, dense tile block (block_layout 1), a batch's records
+    int block_layout = 0;
+    void *rays = nullptr;    // device address of the uint64 ray count; null: the context's own count word (R1_TAIL_RAYS)
+    hipStream_t st = nullptr;
+    bool throughput = false; // the throughput kernels (frames in flight), not the latency ones
+    const Batch *batch = nullptr;
+    Landing *landing = nullptr;
+    const Pass *pass = nullptr;
+    const Linear *linear = nullptr;
 };
 
 // ---- the steps that cross a file boundary ------------------------------------------------------------------------------------------------
@@ -251,8 +265,7 @@ int ensure_grid(r1_context *c);                     // R1_VARIANT_GRID: the grid
 bool big_scene(const r1_context *c, bool tree, bool grid, bool grid_pixel);
 void fill_scene(const r1_context *c, R1DeviceScene &s);
 void fill_walk(const r1_context *c, bool tree_lds, bool big, uint32_t top_nodes, R1TraceArgs &a);
-int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int block_layout, void *d_rays, hipStream_t st, bool throughput_mode,
-                  const Batch *batch = nullptr, Landing *landing = nullptr, const Pass *pass = nullptr, const Linear *linear = nullptr);
+int enqueue_frame(r1_context *c, const r1_params *p, FrameJob job); // (by value: the landing set-up redirects its copy's out and rays)
 
 #pragma GCC visibility pop
 

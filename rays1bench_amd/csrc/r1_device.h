@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "r1_grid_dda.h"
+#include "r1_tile.h"
 
 // Launch geometry of the trace kernel.
 #define R1_BLOCK 256        // threads per workgroup = 4 wave64
@@ -23,7 +24,7 @@
 #ifndef R1_STACK_LDS_WORDS_TP
 #define R1_STACK_LDS_WORDS_TP 10 // the same for the THROUGHPUT builds of that kernel (r1_mode_is_tp_family), kept apart for experiments: 6 words with the 32-bit
 #endif                           // traversal stack was the first way to seven workgroups (+3 % from the wave, -1.7 % from the deeper global overflow)
-#define R1_RESOLVE_ROWS_TP 256 // frames in flight: rows of workgroups of the resolve launch (0 = one per tile; 16 / 64 / 256 / one per tile: 29.4 / 30.6 / 31.3 / 30.7 Grays/s over 20 steps, 34.9 / 34.85 / 34.87 / 34.7 over 300), see r1_launch_resolve
+#define R1_RESOLVE_ROWS_TP 256 // frames in flight: rows of workgroups of the resolve launch (0 = one per tile; 16 / 64 / 256 / one per tile: 29.4 / 30.6 / 31.3 / 30.7 Grays/s over 20 steps, 34.9 / 34.85 / 34.87 / 34.7 over 300), see tile_row_grid (r1_close_kernels.hip)
 #define R1_NODES_LDS_MAX 256  // tree kernel: scenes whose tree has at most this many nodes (16 KB) run the small-scene kernels, which keep
                               // the node table in LDS; bigger trees run the big-scene kernels (node table through the vector L1)
 #define R1_CHUNK 256        // most samples a wave takes from the global queue per atomic (small frames) ...
@@ -400,12 +401,21 @@ struct R1CameraRaysArgs
     float inv_w, inv_h;     // 1.0f / width, 1.0f / height (IEEE divisions done on the host)
 };
 
+// What the launch that closes a frame does for the next one (R1ResolveArgs, R1AccumArgs, R1AdaptArgs), by its first workgroup, after the trace
+// kernel: publish the ray count the trace kernel accumulated in the context's counter block, then zero the block — two memset launches per frame less
+struct R1FrameClose
+{
+    const unsigned long long *rays_src; // null: the trace kernel counted into the caller's word itself, nothing to do
+    unsigned long long *rays_dst;
+    uint32_t *reset;             // R1_COUNTER_BYTES to zero, or null
+};
+
 struct R1ResolveArgs
 {
     const float4 *samples;
     uint32_t full;
-    int32_t width, height, spp;
-    int32_t tile_w, tile_h, tiles_x;
+    R1TileGeom geom;
+    int32_t spp;
     int32_t shard, num_shards;
     uint32_t n_local_tiles;      // per frame
     float inv_spp;               // (float)(1.0f / spp)
@@ -418,11 +428,7 @@ struct R1ResolveArgs
     uint32_t n_frames;
     size_t out_stride, rays_offset;
     unsigned long long *frame_rays; // null: single frame, the trace kernel counted
-    // end of the frame (block (0,0), after the trace kernel): publish the ray count the trace kernel accumulated in the
-    // context's counter block, then zero the block for the next frame — two memset launches per frame less
-    const unsigned long long *rays_src; // null: the trace kernel counted into the caller's word itself
-    unsigned long long *rays_dst;
-    uint32_t *reset;             // R1_COUNTER_BYTES to zero, or null
+    R1FrameClose close;
 };
 
 // Progressive passes (r1_accum_kernel, in place of the resolve launch): adds the pass's records, in sample order, to the context's per-pixel
@@ -433,15 +439,12 @@ struct R1AccumArgs
     float4 *accum;               // [local tile][pixel of the padded tile] {r, g, b, 0}
     uint8_t *out;                // row-major width*height*3 preview, or null: accumulate only
     uint32_t full;               // tile_w * tile_h * spp
-    int32_t width, height, spp;  // spp: the pass's samples
-    int32_t tile_w, tile_h, tiles_x;
+    R1TileGeom geom;
+    int32_t spp;                 // the pass's samples
     uint32_t n_local_tiles;
     uint32_t fresh;              // 1: the pass starts the accumulation (first_sample == 0): start from 0.0f
     float inv_n;                 // (float)(1.0f / n), n = first_sample + spp
-    // as R1ResolveArgs: publish the pass's ray count, zero the counter block for the next launch
-    const unsigned long long *rays_src;
-    unsigned long long *rays_dst;
-    uint32_t *reset;
+    R1FrameClose close;          // the pass's ray count
 };
 
 // Adaptive sampling (r1_render_adaptive): a tile's report on the device, in the layout of the public r1_tile_report
@@ -461,28 +464,25 @@ struct R1AdaptArgs
     float4 *all, *even;          // [tile of the frame][pixel of the padded tile] {r, g, b, 0}
     uint8_t *out;                // row-major width*height*3
     R1TileReport *report;        // [tile of the frame]
-    int32_t width, height, spp;  // spp: the pass's samples
-    int32_t tile_w, tile_h, tiles_x;
+    R1TileGeom geom;
+    int32_t spp;                 // the pass's samples
     uint32_t n_listed;
     uint32_t first_sample;       // global index of the pass's first sample (0: the accumulators start from 0.0f)
     float inv_all, inv_even;     // (float)(1.0f / n), (float)(1.0f / ((n + 1) / 2)), n = first_sample + spp
     int32_t max_delta;           // the rule: err_max <= max_delta (-1: never) ...
     uint32_t mean_delta_q8;      // ... and err_sum * 256 <= mean_delta_q8 * 3 * (pixels of the tile inside the image)
-    // as R1ResolveArgs: publish the pass's ray count, zero the counter block for the next launch
-    const unsigned long long *rays_src;
-    unsigned long long *rays_dst;
-    uint32_t *reset;
+    R1FrameClose close;          // the pass's ray count
 };
 
 // Linear frames.  r1_resolve_linear_kernel, one more launch behind a whole frame's trace and whatever closes it: the sums
 // r1_resolve_kernel takes over the records the trace left, times inv_spp, stored as fp32 — the value the byte is quantised from.
 struct R1LinearArgs
 {
-    const float4 *samples;       // [tile][sample][pixel of the padded tile]; x, y, z alone are read (a landing launch tags the w word)
+    const float4 *samples;       // [tile][sample][pixel of the padded tile]; x, y, z alone are used (a landing launch tags the w word)
     float *out;                  // row-major width*height*3 floats
     uint32_t full;               // tile_w * tile_h * spp
-    int32_t width, height, spp;
-    int32_t tile_w, tile_h, tiles_x;
+    R1TileGeom geom;
+    int32_t spp;
     uint32_t n_tiles;
     float inv_spp;               // (float)(1.0f / spp)
 };
@@ -494,10 +494,34 @@ struct R1ReadoutArgs
     const float4 *accum;         // [tile][pixel of the padded tile] {r, g, b, 0}
     const R1TileReport *report;  // [tile], or null
     float *out;                  // row-major width*height*3 floats
-    int32_t width, height;
-    int32_t tile_w, tile_h, tiles_x;
+    R1TileGeom geom;
     uint32_t n_tiles;
     float inv_n;                 // report == null: (float)(1.0f / n)
+};
+
+// r1_land_arm_kernel: the countdowns and per-frame accumulators of a landing launch of n_frames frames of n_local_tiles tiles (r1_land_area)
+struct R1LandArmArgs
+{
+    uint32_t *tile_cnt;
+    unsigned long long *frame_rays;
+    uint32_t *frame_left;
+    uint32_t n_frames, n_local_tiles;
+    R1TileGeom geom;
+    int32_t spp, shard, num_shards;
+};
+
+// r1_assemble_kernel.  blocks: gathered tile blocks or records; per frame f (0 .. n_frames - 1): shard sh's block at blocks + f * frame_in + sh *
+// shard_stride, image at rgb + f * frame_out.  want_total: the shards' uint64 counts at (block start + total_offset) are summed into the uint64 at
+// (the frame's image + total_out).
+struct R1AssembleArgs
+{
+    const uint8_t *blocks;
+    uint8_t *rgb;
+    R1TileGeom geom;
+    int32_t num_shards, n_frames;
+    size_t shard_stride, frame_in, frame_out, total_offset;
+    long long total_out;
+    int32_t want_total;
 };
 
 #endif

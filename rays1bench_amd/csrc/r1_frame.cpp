@@ -35,14 +35,12 @@ static R1FastDiv make_div(uint32_t d)
     return r;
 }
 
-static int prepare_tiles(r1_context *c, const r1_params *p, int n_frames)
+static int prepare_tiles(r1_context *c, const r1_params *p, const R1TileGeom &g, int n_frames)
 {
     if (c->tile_key_valid && same_tiling(c->tile_key, *p) && c->tile_frames == n_frames)
         return R1_OK;
-    const int tiles_x = (p->width + p->tile_w - 1) / p->tile_w;
-    const int tiles_y = (p->height + p->tile_h - 1) / p->tile_h;
-    const int total = tiles_x * tiles_y;
-    const uint32_t local = total > p->shard ? (uint32_t)((total - p->shard + p->num_shards - 1) / p->num_shards) : 0u;
+    const int total = r1_tiles(g);
+    const uint32_t local = r1_shard_tiles(total, p->shard, p->num_shards);
     const uint64_t full = (uint64_t)p->tile_w * p->tile_h * p->spp;
     if (full * local * (uint64_t)n_frames >= ((uint64_t)1 << 31) || (uint64_t)total * p->num_shards >= ((uint64_t)1 << 31))
     {
@@ -61,9 +59,9 @@ static int prepare_tiles(r1_context *c, const r1_params *p, int n_frames)
 
 // The context's counter allocation (its layout: r1_device.h R1_CNT_*, R1_TAIL_*, r1_land_area), sized for the launch's landing area.
 // Called by every entry point BEFORE it takes addresses inside the allocation (it may move when the launch needs more room).
-static int ensure_counters(r1_context *c, const r1_params *p, int n_frames)
+static int ensure_counters(r1_context *c, const r1_params *p, const R1TileGeom &g, int n_frames)
 {
-    int rc = prepare_tiles(c, p, n_frames);
+    int rc = prepare_tiles(c, p, g, n_frames);
     if (rc)
         return rc;
     const size_t F = (size_t)(n_frames > 0 ? n_frames : 1);
@@ -124,29 +122,30 @@ static int resolve_variant(const r1_context *c, int32_t wanted, bool throughput_
 // unless r1_set_pixel_mode chose PIXEL mode for the throughput entry point (a lane owns a pixel: no sample records, no resolve launch,
 // ~10 % slower).  Refuses what is not built; changes nothing.
 // `records`: the caller reads the sample records afterwards (a linear frame), so PIXEL mode, which keeps none, is not chosen.
-static int choose_kernel(const r1_context *c, const r1_params *p, int variant, bool throughput_mode, const Batch *batch, const Pass *pass, bool records, Choice &k)
+static int choose_kernel(const r1_context *c, const r1_params *p, const FrameJob &job, int variant, Choice &k)
 {
+    const bool throughput_mode = job.throughput, records = job.linear != nullptr;
     k.variant = variant;
     const bool wavefront = variant == R1_V_WAVEFRONT;
     const bool pixel_wish = throughput_mode && c->pixel_mode && !records;
     const bool big = big_scene(c, r1_is_tree(variant), r1_is_grid(variant), pixel_wish);
-    const bool frames = batch && batch->n_frames > 1; // (a batch or path of one frame: the single-frame kernel, a path's camera by value)
+    const bool frames = job.batch && job.batch->n_frames > 1; // (a batch or path of one frame: the single-frame kernel, a path's camera by value)
     static const int tp_mode_env = (int)r1_knob("R1_TP_MODE", -1); // tuning experiments: R1_MODE_TP, _LAT or _PIXEL for the throughput entry points
     int want = R1_MODE_LAT;
-    if (pass)
-        want = pass->list ? R1_MODE_LISTED : R1_MODE_PASS;
+    if (job.pass)
+        want = job.pass->list ? R1_MODE_LISTED : R1_MODE_PASS;
     else if (pixel_wish || (throughput_mode && !records && tp_mode_env == R1_MODE_PIXEL))
         want = R1_MODE_PIXEL;
     else if (throughput_mode && !(tp_mode_env == R1_MODE_LAT && !big)) // (big scenes have no latency build: the knob leaves them alone)
-        want = !frames ? R1_MODE_TP : batch->cameras ? R1_MODE_PATH : R1_MODE_BATCH;
+        want = !frames ? R1_MODE_TP : job.batch->cameras ? R1_MODE_PATH : R1_MODE_BATCH;
     // (the wavefront variant has kernels of its own; its grid is sized as the grouped sweep's frames in flight are)
     const bool built = wavefront ? r1_pick(R1_V_SWEEP, big, R1_MODE_TP, k.b) : r1_pick(variant, big, want, k.b);
-    if (!built && pass)
+    if (!built && job.pass)
     {
         r1_set_error("variant %d has no progressive-pass build", p->variant);
         return R1_EINVAL;
     }
-    if (batch && (!built || !r1_mode_is_tp_family(k.b.mode) || wavefront || r1_is_stats(variant) || variant == R1_V_REFERENCE))
+    if (job.batch && (!built || !r1_mode_is_tp_family(k.b.mode) || wavefront || r1_is_stats(variant) || variant == R1_V_REFERENCE))
     {
         r1_set_error("frame batches run through the throughput kernels only (no PIXEL mode, no diagnostic / reference-form / wavefront variant)");
         return R1_EINVAL;
@@ -167,31 +166,31 @@ static int choose_kernel(const r1_context *c, const r1_params *p, int variant, b
 // A listed pass has the list's length as its tile count — grid size, queue length and record buffer follow from it — so n_local_tiles and
 // total_samples are rewritten BEFORE anything is sized, and the cached tiling, which no longer describes the params it is kept under, is
 // dropped: the next call derives its own.  A pass of r1_render_pass gets its accumulator.
-static int size_tiles(r1_context *c, const r1_params *p, int n_frames, const Pass *pass)
+static int size_tiles(r1_context *c, const r1_params *p, const R1TileGeom &g, const FrameJob &job)
 {
-    int rc = ensure_counters(c, p, n_frames);
+    int rc = ensure_counters(c, p, g, job.batch ? job.batch->n_frames : 1);
     if (rc)
         return rc;
-    if (pass && pass->list)
+    if (job.pass && job.pass->list)
     {
-        c->n_local_tiles = pass->n_listed;
-        c->total_samples = c->full * pass->n_listed;
+        c->n_local_tiles = job.pass->n_listed;
+        c->total_samples = c->full * job.pass->n_listed;
         c->tile_key_valid = false;
     }
-    else if (pass)
-        return ensure(c->accum, (size_t)c->n_local_tiles * p->tile_w * p->tile_h * 16);
+    else if (job.pass)
+        return ensure(c->accum, (size_t)c->n_local_tiles * r1_tile_slots(g) * 16);
     return R1_OK;
 }
 
 // The launch's sample records (none in PIXEL mode), and a batch's partial ray counts where a resolve launch will follow
-static int ensure_records(r1_context *c, const r1_params *p, const Choice &k, const Batch *batch, hipStream_t st)
+static int ensure_records(r1_context *c, const R1TileGeom &g, const Choice &k, const FrameJob &job)
 {
     int rc;
-    if (batch && k.variant != R1_V_TREE)
+    if (job.batch && k.variant != R1_V_TREE)
     {
         // partial ray counts of the resolve launch: one uint64 per (tile of the batch, workgroup column)
-        const size_t cols = ((size_t)p->tile_w * p->tile_h + 255) / 256;
-        if ((rc = ensure(c->batch_rays, (size_t)batch->n_frames * (c->n_local_tiles ? c->n_local_tiles : 1) * cols * 8)))
+        const size_t cols = ((size_t)r1_tile_slots(g) + 255) / 256;
+        if ((rc = ensure(c->batch_rays, (size_t)job.batch->n_frames * (c->n_local_tiles ? c->n_local_tiles : 1) * cols * 8)))
             return rc;
     }
     if (k.b.mode == R1_MODE_PIXEL)
@@ -201,7 +200,7 @@ static int ensure_records(r1_context *c, const r1_params *p, const Choice &k, co
     if ((rc = ensure(c->samples, want)))
         return rc;
     if (fresh) // a record is recognised by its launch's tag: fresh memory must not carry one by accident
-        R1_HIP(hipMemsetAsync(c->samples.p, 0, c->samples.cap, st));
+        R1_HIP(hipMemsetAsync(c->samples.p, 0, c->samples.cap, job.st));
     return R1_OK;
 }
 
@@ -229,15 +228,15 @@ void fill_walk(const r1_context *c, bool tree_lds, bool big, uint32_t top_nodes,
 
 // Everything of R1TraceArgs that follows from the context, the params and the kernel choice; the batch block, the grid size and the
 // landing are the later steps'.  Takes addresses inside the counter allocation: after size_tiles.
-static void frame_args(const r1_context *c, const r1_params *p, const Choice &k, const Batch *batch, void *d_out, int block_layout, void *d_rays, R1TraceArgs &a)
+static void frame_args(const r1_context *c, const r1_params *p, const Choice &k, const FrameJob &job, const R1TileGeom &g, R1TraceArgs &a)
 {
     memset(&a, 0, sizeof(a));
     fill_scene(c, a.scene);
-    a.cam = batch && batch->cameras && batch->n_frames == 1 ? device_camera(batch->cameras[0]) : c->cam;
+    a.cam = job.batch && job.batch->cameras && job.batch->n_frames == 1 ? device_camera(job.batch->cameras[0]) : c->cam;
     a.width = p->width, a.height = p->height, a.spp = p->spp, a.max_bounces = p->max_bounces;
     a.seed = p->seed;
     a.inv_w = 1.0f / p->width, a.inv_h = 1.0f / p->height; // Vec3 inv_image_size(1.0f / td.image_w, 1.0f / td.image_h, 0) rayweek1.cpp:746
-    a.tile_w = p->tile_w, a.tile_h = p->tile_h, a.tiles_x = (p->width + p->tile_w - 1) / p->tile_w;
+    a.tile_w = g.tile_w, a.tile_h = g.tile_h, a.tiles_x = g.tiles_x;
     a.shard = p->shard, a.num_shards = p->num_shards;
     a.n_local_tiles = c->n_local_tiles, a.full = c->full, a.total_samples = c->total_samples;
     a.div_full = make_div(c->full), a.div_spp = make_div((uint32_t)p->spp), a.div_tw = make_div((uint32_t)p->tile_w), a.div_tx = make_div((uint32_t)a.tiles_x);
@@ -245,7 +244,7 @@ static void frame_args(const r1_context *c, const r1_params *p, const Choice &k,
     static const int coop_env = (int)r1_knob("R1_COOP_LANES", -1);
     a.coop_lanes = coop_env >= 0 ? (uint32_t)coop_env : R1_COOP_LANES;
     a.samples = (float4 *)c->samples.p;
-    a.num_rays = k.fused_clear ? (unsigned long long *)counter_at(c, R1_CNT_RAYS) : (unsigned long long *)d_rays;
+    a.num_rays = k.fused_clear ? (unsigned long long *)counter_at(c, R1_CNT_RAYS) : (unsigned long long *)job.rays;
     a.stats = r1_is_stats(k.variant) ? (unsigned long long *)counter_at(c, R1_CNT_STATS) : nullptr;
     if (r1_is_grid(k.variant))
         a.grid = (const R1GridArgs *)(k.b.big ? c->grid_dev32.p : c->grid_dev.p), a.scene.bvh_root_leaf = 0u; // (the grid kernels' fallback walks the tree from its root: no root step, r1_hit_tree.hpp bvh_advance)
@@ -254,9 +253,9 @@ static void frame_args(const r1_context *c, const r1_params *p, const Choice &k,
     if (k.b.mode == R1_MODE_PIXEL)
     {
         // the queue holds the padded pixels of the shard's tiles, and `samples` is the output the kernel resolves into
-        const uint32_t tp = (uint32_t)(p->tile_w * p->tile_h);
+        const uint32_t tp = r1_tile_slots(g);
         a.full = tp, a.div_full = make_div(tp), a.total_samples = c->n_local_tiles * tp;
-        a.samples = (float4 *)d_out, a.block_layout = block_layout;
+        a.samples = (float4 *)job.out, a.block_layout = job.block_layout;
         a.inv_spp = (float)(1.0f / p->spp); // rayweek1.cpp:765
     }
 }
@@ -310,7 +309,7 @@ static int put_path_cameras(r1_context *c, const Batch *batch, hipStream_t st, c
 
 // R1TraceArgs::batch (null in a single frame): a batch's numbers, behind them a path's camera table; or a pass's first sample and tile
 // list, which the R1_MODE_PASS / _LISTED kernels read where a sample is seeded.
-static int put_batch_block(r1_context *c, const Choice &k, const Batch *batch, const Pass *pass, hipStream_t st, R1TraceArgs &a)
+static int put_batch_block(r1_context *c, const Choice &k, const FrameJob &job, R1TraceArgs &a)
 {
     static_assert(sizeof(R1BatchArgs) == 24 && sizeof(R1PassArgs) == 24, "r1_launch_put6 writes the six words of R1BatchArgs / R1PassArgs");
     static_assert(sizeof(R1PathArgs) == 32 && __builtin_offsetof(R1PathArgs, cameras) == 24, "r1_launch_put8 writes the eight words of R1PathArgs into a 32-byte slot");
@@ -320,20 +319,20 @@ static int put_batch_block(r1_context *c, const Choice &k, const Batch *batch, c
         const bool path = k.b.mode == R1_MODE_PATH;
         R1PathArgs pa;
         memset(&pa, 0, sizeof(pa));
-        pa.batch.n_frames = (uint32_t)batch->n_frames, pa.batch.seed_stride = batch->seed_stride;
+        pa.batch.n_frames = (uint32_t)job.batch->n_frames, pa.batch.seed_stride = job.batch->seed_stride;
         pa.batch.div_tiles = make_div(c->n_local_tiles ? c->n_local_tiles : 1u), pa.batch.n_local_tiles = c->n_local_tiles;
-        if (path && (rc = put_path_cameras(c, batch, st, &pa.cameras)))
+        if (path && (rc = put_path_cameras(c, job.batch, job.st, &pa.cameras)))
             return rc;
-        if ((rc = put_batch_args(c, &pa, path ? 8 : 6, path ? nullptr : &pa.batch, st, &a.batch)))
+        if ((rc = put_batch_args(c, &pa, path ? 8 : 6, path ? nullptr : &pa.batch, job.st, &a.batch)))
             return rc;
     }
-    if (pass)
+    if (job.pass)
     {
         R1PassArgs pa;
         memset(&pa, 0, sizeof(pa));
-        pa.first_sample = (uint32_t)pass->first_sample;
-        pa.list = pass->list;
-        return put_batch_args(c, &pa, 6, nullptr, st, &a.batch);
+        pa.first_sample = (uint32_t)job.pass->first_sample;
+        pa.list = job.pass->list;
+        return put_batch_args(c, &pa, 6, nullptr, job.st, &a.batch);
     }
     return R1_OK;
 }
@@ -358,9 +357,12 @@ static int blocks_per_cu(r1_context *c, const Choice &k, const R1TraceArgs &a, i
 
 // The persistent grid and how its waves take work from the queue.  Changes nothing but its result.
 struct GridSize { long long blocks; uint32_t chunk_min, chunk_max, nq; };
-// total: sample slots of the launch; pixels: PIXEL mode — the padded pixels the queue holds instead — else 0; latency: r1_runs_as_latency of the build
-static GridSize size_grid(int cus, int per_cu, uint32_t total, uint32_t pixels, bool pixel_mode, bool latency, bool throughput_mode, int num_shards)
+// pixels: PIXEL mode — the padded pixels the queue holds instead of the launch's sample slots — else 0
+static GridSize size_grid(const r1_context *c, const Choice &k, const FrameJob &job, int per_cu, uint32_t pixels, int num_shards)
 {
+    const int cus = c->cus;
+    const uint32_t total = c->total_samples;
+    const bool pixel_mode = k.b.mode == R1_MODE_PIXEL, latency = r1_runs_as_latency(k.b.mode, k.b.big), throughput_mode = job.throughput;
     GridSize g;
     // Latency mode (the synchronous host entry points: one frame, the caller waits): as many waves as fit, every lane at least one
     // sample.  Throughput mode (the device-resident entry point, frames in flight on several streams): a wave's lanes run dry one by one
@@ -415,7 +417,8 @@ static GridSize size_grid(int cus, int per_cu, uint32_t total, uint32_t pixels, 
 }
 
 // Landing set-up (tiles resolved inside the trace kernel): the launch's set of queue heads, its record tag, the armed countdowns, where the
-// tiles land and the waves' tile lists.
+// tiles land — the caller's own memory where the device can write there, which redirects the job's out and rays for the steps behind this
+// one — and the waves' tile lists.
 // Launches alternate between two sets of queue heads and wave counts; workgroup 0 zeroes the set the launch before used, which nobody
 // touches any more (a workgroup that starts late still asks its own queue for work after the frame's last tile has been summed, so a
 // launch cannot clear its own).  After anything else has run through this context both sets (and the round-3 block) are cleared here.
@@ -423,10 +426,10 @@ static GridSize size_grid(int cus, int per_cu, uint32_t total, uint32_t pixels, 
 // the trace launch is enqueued: until then the context counts as neither, so a call refused from here on (tile lists too long, an
 // allocation, the launch) sends the next one through both memsets and the arming launch — it would otherwise take the set the last
 // launch that ran left exhausted, and no tile would be summed.
-static int land_setup(r1_context *c, const r1_params *p, const Batch *batch, Landing *landing, long long blocks, int block_layout, hipStream_t st,
-                      R1TraceArgs &a, void *&d_out, void *&d_rays, int &land_parity)
+static int land_setup(r1_context *c, const r1_params *p, FrameJob &job, long long blocks, R1TraceArgs &a, int &land_parity)
 {
-    const int n_frames = batch ? batch->n_frames : 1;
+    const int n_frames = job.batch ? job.batch->n_frames : 1;
+    const hipStream_t st = job.st;
     const bool prev = c->land_prev, armed = c->land_armed;
     c->land_prev = false, c->land_armed = false;
     land_parity = prev ? c->land_parity ^ 1 : 0;
@@ -456,21 +459,22 @@ static int land_setup(r1_context *c, const r1_params *p, const Batch *batch, Lan
     a.land_cnt = (uint32_t *)counter_at(c, area.tile_cnt); // (every countdown on a 128-byte line of its own)
     if (!armed || c->land_frames != n_frames || !same_tiling(c->land_key, *p))
     {
-        R1_HIP(r1_launch_land_arm(a.land_cnt, frame_rays, frame_left, (uint32_t)n_frames, c->n_local_tiles, p->width, p->height, p->spp, p->tile_w, p->tile_h,
-                                  a.tiles_x, p->shard, p->num_shards, st));
+        const R1TileGeom g = r1_tile_geom(p->width, p->height, p->tile_w, p->tile_h); // (only where the tiling changed: the arming launch)
+        const R1LandArmArgs arm = {a.land_cnt, frame_rays, frame_left, (uint32_t)n_frames, c->n_local_tiles, g, p->spp, p->shard, p->num_shards};
+        R1_HIP(r1_launch_land_arm(&arm, st));
         c->land_frames = n_frames, c->land_key = *p; // (land_armed: committed with the launch)
     }
-    if (landing && landing->out && (batch || landing->rays))
+    if (job.landing && job.landing->out && (job.batch || job.landing->rays))
     {
-        d_out = landing->out;
-        if (!batch)
-            d_rays = landing->rays;
-        landing->used = true;
+        job.out = job.landing->out;
+        if (!job.batch)
+            job.rays = job.landing->rays;
+        job.landing->used = true;
     }
-    a.land.out = (uint8_t *)d_out, a.land.rays_dst = (unsigned long long *)d_rays;
-    a.land.out_stride = batch ? batch->out_stride : 0, a.land.rays_offset = batch ? batch->rays_offset : 0, a.land.rays_in_out = batch ? 1u : 0u;
+    a.land.out = (uint8_t *)job.out, a.land.rays_dst = (unsigned long long *)job.rays;
+    a.land.out_stride = job.batch ? job.batch->out_stride : 0, a.land.rays_offset = job.batch ? job.batch->rays_offset : 0, a.land.rays_in_out = job.batch ? 1u : 0u;
     a.land.frame_rays = frame_rays, a.land.frame_left = frame_left;
-    a.land.n_frames = (uint32_t)n_frames, a.land.block_layout = (uint32_t)block_layout;
+    a.land.n_frames = (uint32_t)n_frames, a.land.block_layout = (uint32_t)job.block_layout;
     a.land.inv_spp = (float)(1.0f / p->spp); // rayweek1.cpp:765
     a.land.error = c->host_word_dev ? &c->host_word_dev->land_error : nullptr;
     // every wave's list of tiles: a row as long as the launch has tiles (the cursors only move forward: a wave meets a tile at
@@ -508,8 +512,9 @@ static void take_events(r1_context *c, hipEvent_t e[3])
 
 // What the trace launch finds in memory: the attenuation stack's global workspace, a clean counter block (the last frame's closing launch
 // left it so, or a memset does), the diagnostic builds' wave log, and a zero in the caller's count word where the kernel counts into it.
-static int prepare_memory(r1_context *c, const Choice &k, long long blocks, int per_cu, void *d_rays, hipStream_t st, R1TraceArgs &a)
+static int prepare_memory(r1_context *c, const Choice &k, const FrameJob &job, long long blocks, int per_cu, R1TraceArgs &a)
 {
+    const hipStream_t st = job.st;
     int rc;
     // (the small-scene tree kernels keep the first 3 * R1_STACK_LDS_WORDS stack entries in LDS and use the workspace beyond)
     if (k.b.big || (R1_STACK_LDS_WORDS < R1_STACK_WORDS && (r1_is_tree(k.variant) || r1_is_grid(k.variant))))
@@ -535,7 +540,7 @@ static int prepare_memory(r1_context *c, const Choice &k, long long blocks, int 
         R1_HIP(hipMemcpyAsync(counter_at(c, R1_CNT_WAVE_LOG), &c->wave_log_ptr, 8, hipMemcpyHostToDevice, st));
     }
     if (!k.fused_clear && !k.land)
-        R1_HIP(hipMemsetAsync(d_rays, 0, 8, st));
+        R1_HIP(hipMemsetAsync(job.rays, 0, 8, st));
     return R1_OK;
 }
 
@@ -570,94 +575,85 @@ static int launch_wavefront(r1_context *c, const R1TraceArgs &a, hipStream_t st,
 // fused_clear: that launch publishes the ray count and zeroes the counter block for the next frame, which saves the two memset launches
 // in front of every frame (they cost nothing to execute and ~10 us each to dispatch: a rank of an 8-GPU run renders its share of a frame
 // in 140 us).
-static int close_frame(r1_context *c, const r1_params *p, const Choice &k, const Batch *batch, const Pass *pass, int tiles_x, void *d_out, int block_layout,
-                       void *d_rays, bool throughput_mode, hipStream_t st)
+static int close_frame(r1_context *c, const r1_params *p, const Choice &k, const FrameJob &job, const R1TileGeom &g)
 {
-    const unsigned long long *rays_src = k.fused_clear ? (const unsigned long long *)counter_at(c, R1_CNT_RAYS) : nullptr;
-    unsigned long long *rays_dst = k.fused_clear ? (unsigned long long *)d_rays : nullptr;
-    uint32_t *reset = k.fused_clear ? (uint32_t *)c->counters.p : nullptr;
+    const hipStream_t st = job.st;
+    R1FrameClose close = {nullptr, nullptr, nullptr};
+    if (k.fused_clear)
+        close = {(const unsigned long long *)counter_at(c, R1_CNT_RAYS), (unsigned long long *)job.rays, (uint32_t *)c->counters.p};
     static const int resolve_rows = (int)r1_knob("R1_RESOLVE_ROWS", R1_RESOLVE_ROWS_TP); // tuning experiments
     if (k.b.mode == R1_MODE_LISTED && c->n_local_tiles)
     {
-        // adaptive sampling: the records go into the listed tiles' two accumulators, their `all` bytes into d_out, and every listed tile is tested
-        const int32_t n = pass->first_sample + p->spp;
-        R1AdaptArgs ad;
-        memset(&ad, 0, sizeof(ad));
-        ad.samples = (const float4 *)c->samples.p, ad.list = pass->list;
+        // adaptive sampling: the records go into the listed tiles' two accumulators, their `all` bytes into job.out, and every listed tile is tested
+        const int32_t n = job.pass->first_sample + p->spp;
+        R1AdaptArgs ad = {};
+        ad.samples = (const float4 *)c->samples.p, ad.list = job.pass->list;
         ad.all = (float4 *)c->accum.p, ad.even = (float4 *)c->accum_even.p;
-        ad.out = (uint8_t *)d_out, ad.report = (R1TileReport *)c->adapt_report.p;
-        ad.width = p->width, ad.height = p->height, ad.spp = p->spp;
-        ad.tile_w = p->tile_w, ad.tile_h = p->tile_h, ad.tiles_x = tiles_x;
-        ad.n_listed = pass->n_listed, ad.first_sample = (uint32_t)pass->first_sample;
+        ad.out = (uint8_t *)job.out, ad.report = (R1TileReport *)c->adapt_report.p;
+        ad.geom = g, ad.spp = p->spp;
+        ad.n_listed = job.pass->n_listed, ad.first_sample = (uint32_t)job.pass->first_sample;
         ad.inv_all = (float)(1.0f / n), ad.inv_even = (float)(1.0f / ((n + 1) / 2)); // rayweek1.cpp:765 at the samples each accumulator holds
-        ad.max_delta = pass->rule->max_delta, ad.mean_delta_q8 = (uint32_t)pass->rule->mean_delta_q8;
-        ad.rays_src = rays_src, ad.rays_dst = rays_dst, ad.reset = reset;
+        ad.max_delta = job.pass->rule->max_delta, ad.mean_delta_q8 = (uint32_t)job.pass->rule->mean_delta_q8;
+        ad.close = close;
         R1_HIP(r1_launch_adapt_accum(&ad, st));
     }
-    else if (pass && c->n_local_tiles)
+    else if (job.pass && c->n_local_tiles)
     {
-        // progressive pass: the records go into the accumulator, and the preview of samples [0, first_sample + spp) into d_out
-        R1AccumArgs ac;
-        memset(&ac, 0, sizeof(ac));
+        // progressive pass: the records go into the accumulator, and the preview of samples [0, first_sample + spp) into job.out
+        R1AccumArgs ac = {};
         ac.samples = (const float4 *)c->samples.p, ac.accum = (float4 *)c->accum.p;
-        ac.out = pass->image ? (uint8_t *)d_out : nullptr;
+        ac.out = job.pass->image ? (uint8_t *)job.out : nullptr;
         ac.full = c->full, ac.n_local_tiles = c->n_local_tiles;
-        ac.width = p->width, ac.height = p->height, ac.spp = p->spp;
-        ac.tile_w = p->tile_w, ac.tile_h = p->tile_h, ac.tiles_x = tiles_x;
-        ac.fresh = pass->first_sample == 0 ? 1u : 0u;
-        ac.inv_n = (float)(1.0f / (pass->first_sample + p->spp)); // rayweek1.cpp:765 at the accumulated spp
-        ac.rays_src = rays_src, ac.rays_dst = rays_dst, ac.reset = reset;
+        ac.geom = g, ac.spp = p->spp;
+        ac.fresh = job.pass->first_sample == 0 ? 1u : 0u;
+        ac.inv_n = (float)(1.0f / (job.pass->first_sample + p->spp)); // rayweek1.cpp:765 at the accumulated spp
+        ac.close = close;
         R1_HIP(r1_launch_accum(&ac, st));
     }
     else if (k.land)
         ; // the trace launch resolved its tiles itself
     else if (c->n_local_tiles && k.b.mode != R1_MODE_PIXEL)
     {
-        R1ResolveArgs r;
-        memset(&r, 0, sizeof(r));
+        R1ResolveArgs r = {};
         r.samples = (const float4 *)c->samples.p;
         r.full = c->full, r.n_local_tiles = c->n_local_tiles;
-        r.width = p->width, r.height = p->height, r.spp = p->spp;
-        r.tile_w = p->tile_w, r.tile_h = p->tile_h, r.tiles_x = tiles_x;
+        r.geom = g, r.spp = p->spp;
         r.shard = p->shard, r.num_shards = p->num_shards;
         r.inv_spp = (float)(1.0f / p->spp); // rayweek1.cpp:765
-        r.out = (uint8_t *)d_out, r.block_layout = block_layout;
-        r.n_frames = (uint32_t)(batch ? batch->n_frames : 1);
-        if (batch)
+        r.out = (uint8_t *)job.out, r.block_layout = job.block_layout;
+        r.n_frames = (uint32_t)(job.batch ? job.batch->n_frames : 1);
+        if (job.batch)
         {
-            r.out_stride = batch->out_stride, r.rays_offset = batch->rays_offset;
+            r.out_stride = job.batch->out_stride, r.rays_offset = job.batch->rays_offset;
             r.frame_rays = (unsigned long long *)c->batch_rays.p;
         }
-        r.rays_src = rays_src, r.rays_dst = rays_dst, r.reset = reset;
-        R1_HIP(r1_launch_resolve(&r, throughput_mode ? resolve_rows : 0, st));
+        r.close = close;
+        R1_HIP(r1_launch_resolve(&r, job.throughput ? resolve_rows : 0, st));
     }
-    else if (batch) // a shard without tiles: its frames' counts are zero
-        for (int f = 0; f < batch->n_frames; ++f)
-            R1_HIP(hipMemsetAsync((char *)d_out + (size_t)f * batch->out_stride + batch->rays_offset, 0, 8, st));
+    else if (job.batch) // a shard without tiles: its frames' counts are zero
+        for (int f = 0; f < job.batch->n_frames; ++f)
+            R1_HIP(hipMemsetAsync((char *)job.out + (size_t)f * job.batch->out_stride + job.batch->rays_offset, 0, 8, st));
     return R1_OK;
 }
 
 // A linear frame's one more launch: the records the trace launch left, summed as the resolve sums them, into linear->out.
 // Whole single frames (the entry points see to it), so a tile of the launch is a tile of the frame.
-static int resolve_linear(const r1_context *c, const r1_params *p, int tiles_x, const Linear *linear, bool throughput_mode, hipStream_t st)
+static int resolve_linear(const r1_context *c, const r1_params *p, const FrameJob &job, const R1TileGeom &g)
 {
     if (!c->n_local_tiles || !c->total_samples)
         return R1_OK;
-    R1LinearArgs l;
-    memset(&l, 0, sizeof(l));
-    l.samples = (const float4 *)c->samples.p, l.out = linear->out;
+    R1LinearArgs l = {};
+    l.samples = (const float4 *)c->samples.p, l.out = job.linear->out;
     l.full = c->full, l.n_tiles = c->n_local_tiles;
-    l.width = p->width, l.height = p->height, l.spp = p->spp;
-    l.tile_w = p->tile_w, l.tile_h = p->tile_h, l.tiles_x = tiles_x;
+    l.geom = g, l.spp = p->spp;
     l.inv_spp = (float)(1.0f / p->spp); // rayweek1.cpp:765
-    R1_HIP(r1_launch_resolve_linear(&l, throughput_mode ? R1_RESOLVE_ROWS_TP : 0, st));
+    R1_HIP(r1_launch_resolve_linear(&l, job.throughput ? R1_RESOLVE_ROWS_TP : 0, job.st));
     return R1_OK;
 }
 
-// Enqueues the frame (trace + resolve) on `st`.  d_out / d_rays are device addresses; d_rays == NULL stands for the context's own
-// count word (R1_TAIL_RAYS of the counter allocation; the allocation may move in here, so callers take that address afterwards).
-int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int block_layout, void *d_rays, hipStream_t st,
-                         bool throughput_mode, const Batch *batch, Landing *landing, const Pass *pass, const Linear *linear)
+// Enqueues the frame (trace + whatever closes it) on job.st.  job.out / job.rays are device addresses; job.rays == NULL stands for the context's
+// own count word (R1_TAIL_RAYS of the counter allocation; the allocation may move in here, so callers take that address afterwards).
+int enqueue_frame(r1_context *c, const r1_params *p, FrameJob job)
 {
     if (!c->have_scene)
     {
@@ -667,7 +663,8 @@ int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int block_layo
     int rc = r1_params_check(p);
     if (rc)
         return rc;
-    const int variant = resolve_variant(c, p->variant, throughput_mode);
+    const hipStream_t st = job.st;
+    const int variant = resolve_variant(c, p->variant, job.throughput);
     if (c->moved && variant != R1_V_REFERENCE && !r1_is_tree(variant) && !(r1_is_grid(variant) && c->grid_valid)) // (a grid r1_regrid re-registered serves)
     {
         r1_set_error("variant %d: the scene has moved (r1_update_centers) and only the box tree was refitted, not the sphere groups and the uniform grid; "
@@ -677,30 +674,30 @@ int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int block_layo
     R1_HIP(hipSetDevice(c->device));
     if (r1_is_grid(variant) && (rc = ensure_grid(c)))
         return rc;
-    if ((rc = size_tiles(c, p, batch ? batch->n_frames : 1, pass)))
+    const R1TileGeom g = r1_tile_geom(p->width, p->height, p->tile_w, p->tile_h); // the frame's geometry, for every step and closing launch
+    if ((rc = size_tiles(c, p, g, job)))
         return rc;
-    if (!d_rays) // (only now: the counter allocation may have moved)
-        d_rays = counter_at(c, R1_TAIL_RAYS);
+    if (!job.rays) // (only now: the counter allocation may have moved)
+        job.rays = counter_at(c, R1_TAIL_RAYS);
     Choice k;
-    if ((rc = choose_kernel(c, p, variant, throughput_mode, batch, pass, linear != nullptr, k)) || (rc = ensure_records(c, p, k, batch, st)))
+    if ((rc = choose_kernel(c, p, job, variant, k)) || (rc = ensure_records(c, g, k, job)))
         return rc;
 
     R1TraceArgs a;
-    frame_args(c, p, k, batch, d_out, block_layout, d_rays, a);
-    if ((rc = put_batch_block(c, k, batch, pass, st, a)))
+    frame_args(c, p, k, job, g, a);
+    if ((rc = put_batch_block(c, k, job, a)))
         return rc;
     int per_cu = 1, land_parity = 0;
     if ((rc = blocks_per_cu(c, k, a, &per_cu)))
         return rc;
-    const bool pixel_mode = k.b.mode == R1_MODE_PIXEL;
-    const GridSize g = size_grid(c->cus, per_cu, c->total_samples, pixel_mode ? a.total_samples : 0u, pixel_mode, r1_runs_as_latency(k.b.mode, k.b.big), throughput_mode, p->num_shards);
-    a.chunk_min = g.chunk_min, a.chunk_max = g.chunk_max, a.nq = g.nq;
-    long long blocks = g.blocks;
-    if (k.land && (rc = land_setup(c, p, batch, landing, blocks, block_layout, st, a, d_out, d_rays, land_parity)))
+    const GridSize gs = size_grid(c, k, job, per_cu, k.b.mode == R1_MODE_PIXEL ? a.total_samples : 0u, p->num_shards);
+    a.chunk_min = gs.chunk_min, a.chunk_max = gs.chunk_max, a.nq = gs.nq;
+    long long blocks = gs.blocks;
+    if (k.land && (rc = land_setup(c, p, job, blocks, a, land_parity)))
         return rc;
     hipEvent_t e[3];
     take_events(c, e);
-    if ((rc = prepare_memory(c, k, blocks, per_cu, d_rays, st, a)))
+    if ((rc = prepare_memory(c, k, job, blocks, per_cu, a)))
         return rc;
 
     R1_HIP(hipEventRecord(e[0], st));
@@ -709,13 +706,13 @@ int enqueue_frame(r1_context *c, const r1_params *p, void *d_out, int block_layo
     if (c->total_samples && variant == R1_V_WAVEFRONT && (rc = launch_wavefront(c, a, st, &blocks)))
         return rc;
     R1_HIP(hipEventRecord(e[1], st));
-    if ((rc = close_frame(c, p, k, batch, pass, a.tiles_x, d_out, block_layout, d_rays, throughput_mode, st)))
+    if ((rc = close_frame(c, p, k, job, g)))
         return rc;
     c->counters_clean = k.fused_clear;
     c->land_prev = k.land;
     if (k.land)
         c->land_parity = land_parity, c->land_armed = true;
-    if (linear && (rc = resolve_linear(c, p, a.tiles_x, linear, throughput_mode, st)))
+    if (job.linear && (rc = resolve_linear(c, p, job, g)))
         return rc;
     R1_HIP(hipEventRecord(e[2], st));
     c->last0 = e[0], c->last1 = e[1], c->last2 = e[2];

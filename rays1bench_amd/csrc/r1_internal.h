@@ -56,9 +56,15 @@ R1_TU_DECL(grid_small)
 R1_TU_DECL(grid_big)
 #undef R1_TU_DECL
 
-// r1_aux_kernels.hip
+// r1_aux_kernels.hip: the trace launch and occupancy dispatch, the wavefront variant, the put kernels
 hipError_t r1_launch_trace(const R1TraceArgs *args, R1Build b, int blocks, size_t grid_lds, hipStream_t stream);
 hipError_t r1_trace_occupancy(R1Build b, size_t dyn_lds, int *blocks_per_cu);
+hipError_t r1_launch_wavefront(R1WaveArgs *w, int blocks, hipStream_t stream);
+hipError_t r1_launch_put6(void *dst, const uint32_t *words, hipStream_t stream);
+hipError_t r1_launch_put8(void *dst, const uint32_t *words, hipStream_t stream);
+hipError_t r1_launch_put_cameras(void *dst, const float *cameras20, int n, hipStream_t stream); // n cameras of 20 floats each, host memory read during the call
+
+// r1_close_kernels.hip: what closes a frame.  max_rows: at most this many rows of workgroups (0: one per tile, up to 65535)
 hipError_t r1_launch_resolve(const R1ResolveArgs *args, int max_rows, hipStream_t stream);
 hipError_t r1_launch_accum(const R1AccumArgs *args, hipStream_t stream);
 hipError_t r1_launch_adapt_accum(const R1AdaptArgs *args, hipStream_t stream);
@@ -66,14 +72,8 @@ hipError_t r1_launch_resolve_linear(const R1LinearArgs *args, int max_rows, hipS
 hipError_t r1_launch_accum_linear(const R1ReadoutArgs *args, hipStream_t stream);
 hipError_t r1_launch_adapt_compact(const uint32_t *cur, uint32_t n_cur, const R1TileReport *report, uint32_t at_cap, uint32_t *next, uint32_t *count_out,
                                    hipStream_t stream);
-hipError_t r1_launch_wavefront(R1WaveArgs *w, int blocks, hipStream_t stream);
-hipError_t r1_launch_land_arm(uint32_t *tile_cnt, unsigned long long *frame_rays, uint32_t *frame_left, uint32_t n_frames, uint32_t n_local_tiles, int width,
-                              int height, int spp, int tile_w, int tile_h, int tiles_x, int shard, int num_shards, hipStream_t stream);
-hipError_t r1_launch_put6(void *dst, const uint32_t *words, hipStream_t stream);
-hipError_t r1_launch_put8(void *dst, const uint32_t *words, hipStream_t stream);
-hipError_t r1_launch_put_cameras(void *dst, const float *cameras20, int n, hipStream_t stream); // n cameras of 20 floats each, host memory read during the call
-hipError_t r1_launch_assemble(const void *blocks, void *rgb, int width, int height, int tile_w, int tile_h, int tiles_x, int num_shards, size_t shard_stride,
-                              int n_frames, size_t frame_in, size_t frame_out, size_t total_offset, long long total_out, int want_total, hipStream_t stream);
+hipError_t r1_launch_land_arm(const R1LandArmArgs *args, hipStream_t stream);
+hipError_t r1_launch_assemble(const R1AssembleArgs *args, hipStream_t stream);
 
 // r1_query_kernels.hip, the cast job; variant: R1_V_TREE, R1_V_GRID or R1_V_REFERENCE; plain: the tuning library's plain tree form
 hipError_t r1_launch_cast(const R1CastArgs *args, int variant, int big, int plain, int blocks, size_t dyn_lds, hipStream_t stream);

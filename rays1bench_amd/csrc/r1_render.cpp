@@ -25,14 +25,8 @@ static void *mapped_host(const void *ptr)
     return at.type == hipMemoryTypeHost ? at.devicePointer : nullptr;
 }
 
-// tile t of the frame: its corner and its size inside the image (the last column and row of tiles may be cut)
-struct TileRect { int x0, y0, tw, th; };
-static TileRect tile_rect(const r1_params *p, int t)
-{
-    const int tiles_x = (p->width + p->tile_w - 1) / p->tile_w;
-    const int x0 = (t % tiles_x) * p->tile_w, y0 = (t / tiles_x) * p->tile_h;
-    return {x0, y0, p->tile_w < p->width - x0 ? p->tile_w : p->width - x0, p->tile_h < p->height - y0 ? p->tile_h : p->height - y0};
-}
+// the frame's tile geometry (r1_tile.h), of params that r1_params_check has passed
+static R1TileGeom geom_of(const r1_params *p) { return r1_tile_geom(p->width, p->height, p->tile_w, p->tile_h); }
 
 // The ray count of a frame the caller waits for.  direct: the frame's last launch stores it straight into the context's page-locked word
 // (8 bytes over PCIe, no second copy to enqueue and wait for); else it is copied from behind the counter block.  rays_word: what
@@ -77,9 +71,12 @@ static int render_host(r1_context *c, const r1_params *p, uint8_t *rgb_out, uint
     Landing land_to;
     if (direct && !sharded)
         land_to.out = mapped_host(rgb_out), land_to.rays = &c->host_word_dev->rays;
-    if ((rc = enqueue_frame(c, p, c->image.p, sharded ? 1 : 0, rays_word(c, direct), c->stream, false, nullptr, &land_to)))
+    FrameJob job;
+    job.out = c->image.p, job.block_layout = sharded ? 1 : 0, job.rays = rays_word(c, direct), job.st = c->stream, job.landing = &land_to;
+    if ((rc = enqueue_frame(c, p, job)))
         return rc;
 
+    const R1TileGeom g = geom_of(p);
     uint64_t rays = 0;
     if (!sharded)
     {
@@ -96,10 +93,9 @@ static int render_host(r1_context *c, const r1_params *p, uint8_t *rgb_out, uint
             return rc;
         for (uint32_t lt = 0; lt < c->n_local_tiles; ++lt)
         {
-            const TileRect r = tile_rect(p, p->shard + (int)lt * p->num_shards);
-            for (int ly = 0; ly < r.th; ++ly)
-                memcpy(rgb_out + ((size_t)(r.y0 + ly) * p->width + r.x0) * 3,
-                       block.data() + ((size_t)lt * p->tile_h * p->tile_w + (size_t)ly * p->tile_w) * 3, (size_t)r.tw * 3);
+            const R1TileRect r = r1_tile_rect(g, r1_shard_tile(p->shard, lt, p->num_shards));
+            for (int ly = 0; ly < r.th; ++ly) // a row of the tile at a time
+                memcpy(rgb_out + r1_pixel_row_major(g, r, 0, ly) * 3, block.data() + r1_pixel_block(g, lt, 0, ly) * 3, (size_t)r.tw * 3);
         }
     }
     if ((rc = land_check(c)))
@@ -121,14 +117,14 @@ static int render_host(r1_context *c, const r1_params *p, uint8_t *rgb_out, uint
         R1_HIP(hipStreamSynchronize(c->stream));
         for (uint32_t lt = 0; lt < c->n_local_tiles; ++lt)
         {
-            const TileRect r = tile_rect(p, (int)lt); // (num_shards == 1: local tile = tile of the frame)
+            const R1TileRect r = r1_tile_rect(g, lt); // (num_shards == 1: local tile = tile of the frame)
             const float *src = tmp.data() + (size_t)lt * c->full * 4;
-            const size_t tile_px = (size_t)p->tile_w * p->tile_h;
+            const size_t tile_px = r1_tile_slots(g);
             for (int ly = 0; ly < r.th; ++ly)
                 for (int lx = 0; lx < r.tw; ++lx)
                     for (int sm = 0; sm < p->spp; ++sm)
                     {
-                        float *dst = samples_out + (((size_t)(r.y0 + ly) * p->width + (r.x0 + lx)) * p->spp + sm) * 4;
+                        float *dst = samples_out + (r1_pixel_row_major(g, r, lx, ly) * p->spp + sm) * 4;
                         memcpy(dst, src + ((size_t)sm * tile_px + (size_t)(ly * p->tile_w + lx)) * 4, 16);
                         if (c->land_prev) // the launch tagged its records' ray-count words (R1_LAND): the ABI's word is the count alone
                         {
@@ -225,7 +221,9 @@ extern "C" int r1_render_pass(r1_context *c, const r1_params *p, int32_t first_s
     Pass ps;
     ps.first_sample = first_sample;
     ps.image = rgb_out != nullptr;
-    if ((rc = enqueue_frame(c, p, c->image.p, 0, rays_word(c, direct), c->stream, false, nullptr, nullptr, &ps)))
+    FrameJob job;
+    job.out = c->image.p, job.rays = rays_word(c, direct), job.st = c->stream, job.pass = &ps;
+    if ((rc = enqueue_frame(c, p, job)))
         return rc;
     uint64_t rays = 0;
     if (rgb_out)
@@ -366,7 +364,9 @@ static int render_adaptive(const char *who, r1_context *c, const r1_params *p, c
         Pass ps;
         ps.first_sample = first;
         ps.list = lists[k & 1], ps.n_listed = m, ps.rule = opt;
-        if ((rc = enqueue_frame(c, &pp, c->image.p, 0, rays_word(c, direct), c->stream, false, nullptr, nullptr, &ps)))
+        FrameJob job;
+        job.out = c->image.p, job.rays = rays_word(c, direct), job.st = c->stream, job.pass = &ps;
+        if ((rc = enqueue_frame(c, &pp, job)))
             return rc;
         R1_HIP(r1_launch_adapt_compact(lists[k & 1], m, (const R1TileReport *)c->adapt_report.p, sched[k] == p->spp ? 1u : 0u, lists[(k & 1) ^ 1], d_count, c->stream));
         uint64_t rays = 0;
@@ -406,9 +406,10 @@ static int render_adaptive(const char *who, r1_context *c, const r1_params *p, c
     {
         uint64_t samples = 0;
         int32_t settled = 0;
+        const R1TileGeom g = geom_of(p);
         for (int32_t t = 0; t < tiles; ++t)
         {
-            const TileRect r = tile_rect(p, t);
+            const R1TileRect r = r1_tile_rect(g, (uint32_t)t);
             samples += (uint64_t)rep[t].spp * (uint64_t)(r.tw * r.th);
             settled += rep[t].settled ? 1 : 0;
         }
@@ -483,8 +484,9 @@ extern "C" int r1_render_linear(r1_context *c, const r1_params *p, float *rgb_ou
     if ((rc = ensure(c->image, (size_t)p->width * p->height * 3 + 64)) || (rc = linear_target(c, p, rgb_out, lin)))
         return rc;
     const bool direct = !r1_is_stats(p->variant) && c->host_word_dev; // the ray count as r1_render brings it home
-    if ((rc = enqueue_frame(c, p, c->image.p, 0, rays_word(c, direct), c->stream, false, nullptr, nullptr, nullptr, &lin)) ||
-        (rc = bring_linear(c, p, lin, rgb_out, c->stream)))
+    FrameJob job;
+    job.out = c->image.p, job.rays = rays_word(c, direct), job.st = c->stream, job.linear = &lin;
+    if ((rc = enqueue_frame(c, p, job)) || (rc = bring_linear(c, p, lin, rgb_out, c->stream)))
         return rc;
     uint64_t rays = 0;
     if ((rc = read_rays(c, direct, &rays)) || (rc = land_check(c)))
@@ -520,7 +522,9 @@ extern "C" int r1_render_linear_async(r1_context *c, const r1_params *p, float *
     void *d_rays = nullptr; // (the context's own count word, copied below)
     if (num_rays_out && ((uintptr_t)num_rays_out & 7u) == 0 && !r1_is_stats(p->variant))
         d_rays = mapped_host(num_rays_out);
-    if ((rc = enqueue_frame(c, p, c->image.p, 0, d_rays, st, true, nullptr, nullptr, nullptr, &lin)))
+    FrameJob job;
+    job.out = c->image.p, job.rays = d_rays, job.st = st, job.throughput = true, job.linear = &lin;
+    if ((rc = enqueue_frame(c, p, job)))
         return rc;
     if (rgb_out && (rc = bring_linear(c, p, lin, rgb_out, st)))
         return rc;
@@ -549,8 +553,9 @@ extern "C" int r1_render_linear_device(r1_context *c, const r1_params *p, void *
         return rc;
     Linear lin;
     lin.out = (float *)d_rgb_f32;
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    return enqueue_frame(c, p, c->image.p, 0, d_num_rays, st, true, nullptr, nullptr, nullptr, &lin);
+    FrameJob job;
+    job.out = c->image.p, job.rays = d_num_rays, job.st = hip_stream ? (hipStream_t)hip_stream : c->stream, job.throughput = true, job.linear = &lin;
+    return enqueue_frame(c, p, job);
 }
 
 // The accumulators' read-out, then the frame on the host: `all` of r1_render_pass (n_uniform samples in every tile) or of an adaptive
@@ -561,12 +566,10 @@ static int readout_linear(r1_context *c, const r1_params *p, int32_t tiles, int3
     int rc = linear_target(c, p, rgb_out, lin);
     if (rc)
         return rc;
-    R1ReadoutArgs r;
-    memset(&r, 0, sizeof(r));
+    R1ReadoutArgs r = {};
     r.accum = (const float4 *)c->accum.p, r.report = per_tile ? (const R1TileReport *)c->adapt_report.p : nullptr;
     r.out = lin.out;
-    r.width = p->width, r.height = p->height;
-    r.tile_w = p->tile_w, r.tile_h = p->tile_h, r.tiles_x = (p->width + p->tile_w - 1) / p->tile_w;
+    r.geom = geom_of(p);
     r.n_tiles = (uint32_t)tiles;
     r.inv_n = per_tile ? 0.0f : (float)(1.0f / n_uniform); // rayweek1.cpp:765 at the accumulated spp
     R1_HIP(r1_launch_accum_linear(&r, c->stream));
@@ -637,7 +640,9 @@ extern "C" int r1_render_async(r1_context *c, const r1_params *p, uint8_t *rgb_o
     Landing land_to;
     if (rgb_out && ((uintptr_t)num_rays_out & 7u) == 0)
         land_to.out = mapped_host(rgb_out), land_to.rays = mapped_host(num_rays_out);
-    if ((rc = enqueue_frame(c, p, c->image.p, 0, nullptr, st, true, nullptr, &land_to)))
+    FrameJob job;
+    job.out = c->image.p, job.st = st, job.throughput = true, job.landing = &land_to;
+    if ((rc = enqueue_frame(c, p, job)))
         return rc;
     if (rgb_out && !land_to.used) // (both NULL: the frame stays in the context's device buffers — a measurement aid, bench.py's value_device_resident)
     {
@@ -673,7 +678,9 @@ static int render_frames_async(const char *who, r1_context *c, const r1_params *
     Landing land_to;
     if (host_frames && ((uintptr_t)host_frames & 7u) == 0)
         land_to.out = mapped_host(host_frames);
-    if ((rc = enqueue_frame(c, p, c->image.p, 0, nullptr, st, true, &b, &land_to)))
+    FrameJob job;
+    job.out = c->image.p, job.st = st, job.throughput = true, job.batch = &b, job.landing = &land_to;
+    if ((rc = enqueue_frame(c, p, job)))
         return rc;
     if (host_frames && !land_to.used) // (NULL: the frames stay in the context's device buffer — a measurement aid)
         R1_HIP(hipMemcpyAsync(host_frames, c->image.p, frame * (size_t)n_frames, hipMemcpyDeviceToHost, st));
@@ -719,7 +726,9 @@ extern "C" int r1_render_shard_device_batch(r1_context *c, const r1_params *p, i
     const size_t record = r1_shard_record_bytes(p);
     Batch b;
     b.n_frames = n_frames, b.seed_stride = seed_stride, b.out_stride = record, b.rays_offset = record - 8;
-    return enqueue_frame(c, p, d_records, 1, nullptr, st, true, &b);
+    FrameJob job;
+    job.out = d_records, job.block_layout = 1, job.st = st, job.throughput = true, job.batch = &b;
+    return enqueue_frame(c, p, job);
 }
 
 extern "C" int r1_render_shard_device(r1_context *c, const r1_params *p, void *d_block, void *d_num_rays, void *hip_stream)
@@ -734,8 +743,9 @@ extern "C" int r1_render_shard_device(r1_context *c, const r1_params *p, void *d
         r1_set_error("r1_render_shard_device: d_num_rays must be 8-byte aligned (a uint64 the kernels store and add to atomically)");
         return R1_EINVAL;
     }
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    return enqueue_frame(c, p, d_block, 1, d_num_rays, st, true);
+    FrameJob job;
+    job.out = d_block, job.block_layout = 1, job.rays = d_num_rays, job.st = hip_stream ? (hipStream_t)hip_stream : c->stream, job.throughput = true;
+    return enqueue_frame(c, p, job);
 }
 
 extern "C" int r1_render_shard_device_once(r1_context *c, const r1_params *p, void *d_block, void *d_num_rays, void *hip_stream)
@@ -750,8 +760,9 @@ extern "C" int r1_render_shard_device_once(r1_context *c, const r1_params *p, vo
         r1_set_error("r1_render_shard_device_once: d_num_rays must be 8-byte aligned");
         return R1_EINVAL;
     }
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    return enqueue_frame(c, p, d_block, 1, d_num_rays, st, false);
+    FrameJob job;
+    job.out = d_block, job.block_layout = 1, job.rays = d_num_rays, job.st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    return enqueue_frame(c, p, job);
 }
 
 static int assemble_common(r1_context *c, const r1_params *p, const void *d_blocks, size_t shard_stride_bytes, void *d_rgb, void *d_total_rays,
@@ -781,10 +792,13 @@ static int assemble_common(r1_context *c, const r1_params *p, const void *d_bloc
     }
     R1_HIP(hipSetDevice(c->device));
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    const int tiles_x = (p->width + p->tile_w - 1) / p->tile_w;
-    const size_t record = r1_shard_record_bytes(p);
-    R1_HIP(r1_launch_assemble(d_blocks, d_rgb, p->width, p->height, p->tile_w, p->tile_h, tiles_x, p->num_shards, shard_stride_bytes, n_frames, frame_in,
-                              frame_out, record - 8, d_total_rays ? (long long)((char *)d_total_rays - (char *)d_rgb) : 0, d_total_rays ? 1 : 0, st));
+    R1AssembleArgs a = {};
+    a.blocks = (const uint8_t *)d_blocks, a.rgb = (uint8_t *)d_rgb;
+    a.geom = geom_of(p), a.num_shards = p->num_shards, a.n_frames = n_frames;
+    a.shard_stride = shard_stride_bytes, a.frame_in = frame_in, a.frame_out = frame_out;
+    a.total_offset = r1_shard_record_bytes(p) - 8; // (where a record keeps its shard's count)
+    a.total_out = d_total_rays ? (long long)((char *)d_total_rays - (char *)d_rgb) : 0, a.want_total = d_total_rays ? 1 : 0;
+    R1_HIP(r1_launch_assemble(&a, st));
     return R1_OK;
 }
 

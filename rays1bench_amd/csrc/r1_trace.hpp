@@ -11,8 +11,8 @@
 //   r1_land.hpp       tiles resolved inside the kernel: land_note ... land_exit
 // Included by the translation units that instantiate the kernel, one per family, through r1_trace_tu.inc (r1_trace_tree_small.hip,
 // r1_trace_tree_big.hip, r1_trace_sweep_small.hip, r1_trace_sweep_big.hip, r1_trace_grid_small.hip, r1_trace_grid_big.hip), so that an
-// experiment on one family rebuilds one file and `make -j` builds the families side by side.  r1_aux_kernels.hip (wavefront variant, resolve,
-// accumulate) and r1_query_kernels.hip (ray and path queries) include the subject headers they use, not this file.
+// experiment on one family rebuilds one file and `make -j` builds the families side by side.  r1_aux_kernels.hip (wavefront variant), r1_close_kernels.hip
+// (resolve, accumulate) and r1_query_kernels.hip (ray and path queries) include the subject headers they use, not this file.
 // The includes below stand in the order the definitions had in one file.
 //
 // What it replaces (all in the reference's src/step13/):

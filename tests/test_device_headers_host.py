@@ -10,8 +10,8 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "rays1bench_amd", "csrc")
-# every header that holds device code: r1_trace.hpp and the headers it is made of, and the three shared with host code
-HEADERS = sorted(os.path.basename(p) for p in glob.glob(os.path.join(CSRC, "*.hpp"))) + ["r1_scatter.h", "r1_exact_math.h", "r1_grid_dda.h"]
+# every header that holds device code: r1_trace.hpp and the headers it is made of, and the four shared with host code
+HEADERS = sorted(os.path.basename(p) for p in glob.glob(os.path.join(CSRC, "*.hpp"))) + ["r1_scatter.h", "r1_exact_math.h", "r1_grid_dda.h", "r1_tile.h"]
 
 
 def _makefile_var(name):
