@@ -97,6 +97,8 @@ static int spheres_enqueue(r1_context *c, uint32_t first, uint32_t count, const 
         s.shade = (float *)c->shade.p, s.mat = (float *)c->mat.p, s.radii = (double *)c->refit_radii.p;
         s.radius_sq = d->radius_sq, s.inv_radius = d->inv_radius, s.mat_type = d->mat_type;
         s.albedo_r = d->albedo_r, s.albedo_g = d->albedo_g, s.albedo_b = d->albedo_b, s.mat_param = d->mat_param;
+        // (the set kernel writes the rows of active spheres alone — active indices stop at R1_MAX_ACTIVE_10BIT - 1 in a small scene — so row
+        //  R1_MAX_ACTIVE_10BIT of the small-scene shade table, the identity row the attenuation words' pads point at (r1_sweep.cpp), stays)
         R1_HIP(r1_launch_refit_set(&c->refit, &s, first, count, (uint32_t)groups >> 1, st));
     }
     if (read_ev)

@@ -9,9 +9,19 @@
 #include "r1_device.h"
 #include "r1_exact_math.h"
 #include "r1_scatter.h"
+#include "r1_stack_words.h"
 #include "r1_dev_math.hpp"
 
 #pragma clang fp contract(off)
+
+// The shade phase's bookkeeping, trimmed, each step behind a macro so that the tuning build can measure it alone
+// (`make tuning EXTRA=-DR1_STACK_PAD=0`).
+#ifndef R1_STACK_PAD
+#define R1_STACK_PAD 1 // small scenes: attenuation words padded with the identity row (r1_stack_words.h); 0: the unwind selects 1.0f for the empty slots
+#endif
+#ifndef R1_HIT_OFFSET32
+#define R1_HIT_OFFSET32 1 // small scenes: the hit record's three rows through the tables' scalar bases and one 32-bit byte offset
+#endif
 
 namespace
 {
@@ -36,6 +46,14 @@ __device__ __forceinline__ void stack_push(uint32_t *stack, uint32_t *gstack, ui
         ((r1_gu32 *)gstack)[(uint32_t)(sp - 3 * LW) * gstride + g] = idx;
         return;
     }
+    if (R1_STACK_PAD)
+    {
+        // (sp is in [0, 51): an unsigned multiply-shift, not the signed division)
+        const uint32_t w = r1_stack_word((uint32_t)sp), sh = r1_stack_shift((uint32_t)sp, w);
+        uint32_t *const slot = stack + w * R1_BLOCK + tid;
+        *slot = r1_stack_push_word(*slot, sh, idx); // (sh == 0 opens the word: the pad in its upper slots, nothing of its old contents kept)
+        return;
+    }
     const int w = sp / 3, sh = (sp - 3 * w) * 10;
     uint32_t v = stack[w * R1_BLOCK + tid];
     v = (v & ~(0x3FFu << sh)) | (idx << sh);
@@ -55,12 +73,26 @@ __device__ __forceinline__ uint32_t stack_get(const uint32_t *stack, const uint3
 // scattered: false is Metal::scatter() == false (rayweek1.cpp:432).  type: R1_MAT_* of the sphere; sh: its {inv_radius, albedo rgb}.
 // Shared by shade_level — every trace kernel and the path queries — and the scatter queries' job (r1_query_kernels.hip), which is this
 // arm and nothing else.
+// SMALL: the caller knows 0 <= hit <= 1022 (a small scene) — the three rows are addressed by the tables' wave-uniform bases and one 32-bit
+// byte offset, as the unwind's gathers are, instead of three 64-bit per-lane addresses.
+template <bool SMALL = false>
 __device__ __forceinline__ bool scatter_hit(const R1DeviceScene &S, Path &p, const int hit, const float t_hit, uint32_t &type, f4 &sh)
 {
     // hit record (rayweek1.cpp:316-322)
-    const f4 e = ((const f4 *)S.exact)[hit];
-    sh = ((const f4 *)S.shade)[hit];
-    const f4 mt = ((const f4 *)S.mat)[hit];
+    f4 e, mt;
+    if (SMALL)
+    {
+        const uint32_t off = (uint32_t)hit * (uint32_t)sizeof(f4);
+        e = *(const f4 *)((const char *)S.exact + off);
+        sh = *(const f4 *)((const char *)S.shade + off);
+        mt = *(const f4 *)((const char *)S.mat + off);
+    }
+    else
+    {
+        e = ((const f4 *)S.exact)[hit];
+        sh = ((const f4 *)S.shade)[hit];
+        mt = ((const f4 *)S.mat)[hit];
+    }
     const V3 hp = vadd(p.o, vscale(p.d, t_hit));
     const V3 n = vscale(vsub(hp, mk(e.x, e.y, e.z)), sh.x);
     type = __float_as_uint(mt.x);
@@ -118,7 +150,7 @@ __device__ __forceinline__ bool shade_level(const R1TraceArgs &A, Path &p, const
         {
             uint32_t type;
             f4 sh;
-            if (scatter_hit(A.scene, p, hit, t_hit, type, sh))
+            if (scatter_hit<!BIG && R1_HIT_OFFSET32>(A.scene, p, hit, t_hit, type, sh))
             {
                 if (type != 2u)
                 {
@@ -168,17 +200,35 @@ __device__ __forceinline__ bool shade_level(const R1TraceArgs &A, Path &p, const
             // entry down.  The three albedos of a word are fetched together, whether the word is full or not (any 10-bit
             // index is inside the table, r1_sweep.cpp), and the slots above the top entry multiply by 1.0f, which changes
             // no bit: one round trip to the table per word instead of one per entry.
-            int w = (top - 1) / 3, j = (top - 1) - 3 * w;
             int t_ = tid;
             asm volatile("" : "+v"(t_)); // (the lane's LDS offset is formed here: hoisted out of the tracing loop, tid * 4 was a spilled register reloaded at every path's end)
-            for (; w >= 0; --w, j = 2)
+            if (R1_STACK_PAD)
             {
-                const uint32_t v = s_stack[w * R1_BLOCK + t_];
-                const float4 s2 = A.scene.shade[(v >> 20) & 0x3FFu], s1 = A.scene.shade[(v >> 10) & 0x3FFu], s0 = A.scene.shade[v & 0x3FFu];
-                const bool u2 = j >= 2, u1 = j >= 1;
-                col = mk((u2 ? s2.y : 1.0f) * col.x, (u2 ? s2.z : 1.0f) * col.y, (u2 ? s2.w : 1.0f) * col.z);
-                col = mk((u1 ? s1.y : 1.0f) * col.x, (u1 ? s1.z : 1.0f) * col.y, (u1 ? s1.w : 1.0f) * col.z);
-                col = mk(s0.y * col.x, s0.z * col.y, s0.w * col.z);
+                // every word the same way: the slots above the top entry hold the pad, whose row is {0, 1, 1, 1} (r1_stack_words.h)
+                // (not unrolled: a wave runs the longest of its lanes' trip counts, and a remainder loop in front of a four-word body adds its own)
+#pragma clang loop unroll(disable)
+                for (int w = (int)r1_stack_word((uint32_t)(top - 1)); w >= 0; --w)
+                {
+                    const uint32_t v = s_stack[w * R1_BLOCK + t_];
+                    const float4 s2 = A.scene.shade[(v >> 20) & 0x3FFu], s1 = A.scene.shade[(v >> 10) & 0x3FFu], s0 = A.scene.shade[v & 0x3FFu];
+                    float c[3] = {col.x, col.y, col.z};
+                    const float a2[3] = {s2.y, s2.z, s2.w}, a1[3] = {s1.y, s1.z, s1.w}, a0[3] = {s0.y, s0.z, s0.w};
+                    r1_stack_fold(c, a2, a1, a0);
+                    col = mk(c[0], c[1], c[2]);
+                }
+            }
+            else
+            {
+                int w = (top - 1) / 3, j = (top - 1) - 3 * w;
+                for (; w >= 0; --w, j = 2)
+                {
+                    const uint32_t v = s_stack[w * R1_BLOCK + t_];
+                    const float4 s2 = A.scene.shade[(v >> 20) & 0x3FFu], s1 = A.scene.shade[(v >> 10) & 0x3FFu], s0 = A.scene.shade[v & 0x3FFu];
+                    const bool u2 = j >= 2, u1 = j >= 1;
+                    col = mk((u2 ? s2.y : 1.0f) * col.x, (u2 ? s2.z : 1.0f) * col.y, (u2 ? s2.w : 1.0f) * col.z);
+                    col = mk((u1 ? s1.y : 1.0f) * col.x, (u1 ? s1.z : 1.0f) * col.y, (u1 ? s1.w : 1.0f) * col.z);
+                    col = mk(s0.y * col.x, s0.z * col.y, s0.w * col.z);
+                }
             }
         }
         done = true;

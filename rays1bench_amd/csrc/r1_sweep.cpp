@@ -188,6 +188,10 @@ void r1_build_sweep(const r1_scene *s, const std::vector<uint32_t> &active_to_sc
     std::vector<float> &sweep = out.sweep, &exact = out.exact, &shade = out.shade, &mat = out.mat;
     sweep.assign(4 * (size_t)ns_alloc, 0.0f), exact.assign(4 * (size_t)(na ? na : 1), 0.0f);
     shade.assign(4 * (size_t)(na > R1_MAX_ACTIVE_10BIT ? na : R1_MAX_ACTIVE_10BIT + 1), 0.0f); // small scenes: any 10-bit index may be read (unwind)
+    // small scenes: row R1_MAX_ACTIVE_10BIT — the one 10-bit index no sphere has — is the identity {0, 1, 1, 1}: what the empty slots of an
+    // attenuation word point at (r1_stack_words.h).  No update touches it: r1_update_spheres* write the rows of active spheres alone.
+    if (na <= R1_MAX_ACTIVE_10BIT)
+        shade[4 * (size_t)R1_MAX_ACTIVE_10BIT + 1] = shade[4 * (size_t)R1_MAX_ACTIVE_10BIT + 2] = shade[4 * (size_t)R1_MAX_ACTIVE_10BIT + 3] = 1.0f;
     mat.assign(4 * (size_t)(na ? na : 1), 0.0f);
     std::vector<uint32_t> &members = out.members;
     members.assign((size_t)R1_GROUP_MAX * ns_alloc, 0xFFFFFFFFu);

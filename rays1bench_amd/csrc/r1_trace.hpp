@@ -7,7 +7,7 @@
 //   r1_hit_tree.hpp   bvh_box, leaf_quad, leaf_root, Trav, bvh_advance, sweep_bvh
 //   r1_hit_grid.hpp   grid_trace
 //   r1_sample.hpp     chunk_claim, fastdiv, start_ray, start_sample, Pixel, quantise_pixel, path_store / path_load
-//   r1_shade.hpp      the attenuation stack, shade_level
+//   r1_shade.hpp      the attenuation stack (its words: r1_stack_words.h, shared with the host), shade_level
 //   r1_land.hpp       tiles resolved inside the kernel: land_note ... land_exit
 // Included by the translation units that instantiate the kernel, one per family, through r1_trace_tu.inc (r1_trace_tree_small.hip,
 // r1_trace_tree_big.hip, r1_trace_sweep_small.hip, r1_trace_sweep_big.hip, r1_trace_grid_small.hip, r1_trace_grid_big.hip), so that an
