@@ -573,6 +573,12 @@ typedef struct r1_launch_info
 } r1_launch_info;
 int r1_last_launch_info(r1_context *ctx, r1_launch_info *out);
 
+/* The form of the box-tree walk in the context's last trace launch: 1 — the kernel with the tree's flat axis compiled in (frames in flight
+ * and batches of R1_VARIANT_BVH on a small scene whose current tree is flat; decided per launch, so an update that changes the tree's
+ * flatness is followed), 0 — every other launch, and before the first.  Negative: ctx is NULL.  Diagnostic, for tests and reports;
+ * r1_launch_info keeps its layout and its `kernel`. */
+int r1_last_walk_form(r1_context *ctx);
+
 /* ---- one process, N GPUs: tile split + one RCCL all-gather per frame --------------------- */
 
 /* The multi-GPU form of benchmark()'s join (rayweek1.cpp:804-813, :773-775) behind ONE call, so that

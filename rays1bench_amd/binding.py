@@ -199,6 +199,7 @@ SYMBOLS = [
     ("r1_timing_end", C.c_int, [_ctx, _dblp, _dblp, _i32p]),
     ("r1_last_stats", C.c_int, [_ctx, _u64p]),
     ("r1_last_launch_info", C.c_int, [_ctx, C.POINTER(LaunchInfo)]),
+    ("r1_last_walk_form", C.c_int, [_ctx]),
     ("r1_last_wave_log", C.c_int, [_ctx, _u64p, C.c_size_t, C.POINTER(C.c_uint32)]),
     ("r1_host_scene_create", C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     ("r1_host_scene_destroy", None, [C.c_void_p]),
@@ -737,6 +738,13 @@ class Renderer:
         li = LaunchInfo()
         _check(lib().r1_last_launch_info(self._c, C.byref(li)))
         return {k: int(getattr(li, k)) for k, _ in LaunchInfo._fields_}
+
+    def walk_form(self):
+        """r1_last_walk_form: 1 where the last trace launch ran a flat twin of the tree kernel, else 0"""
+        form = lib().r1_last_walk_form(self._c)
+        if form < 0:
+            _check(form)
+        return int(form)
 
     def close(self):
         if self._c:

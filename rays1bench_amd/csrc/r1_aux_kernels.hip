@@ -198,8 +198,16 @@ extern "C" hipError_t r1_launch_put_cameras(void *dst, const float *cameras20, i
 
 // b: the build r1_pick chose (r1_frame.cpp choose_kernel); which builds exist is the lists' business, what is checked here is that the arguments are
 // those the build reads.  grid_lds: the grid kernels' 16-bit tables in LDS (small scenes; R1GridArgs::lds_bytes, which lives in device memory)
-extern "C" hipError_t r1_launch_trace(const R1TraceArgs *args, R1Build b, int blocks, size_t grid_lds, hipStream_t stream)
+// Flat trees: a landing launch of the small-scene frames-in-flight tree builds, (R1_V_TREE, false, false, TP / BATCH), whose tree
+// is flat — bvh_flat_e >= 0 in the arguments of THIS launch, so an update that changes the tree's flatness is followed — runs the build's
+// flat twin, the same body with the answer compiled in; same arguments, grid, LDS and registers per wave.  r1_pick and its table know
+// nothing of it.  *walk_form: 1 where the twin ran, else 0 (r1_last_walk_form).
+#ifndef R1_FLAT_TWINS
+#define R1_FLAT_TWINS 1 // 0: the generic kernels serve every tree (`make tuning EXTRA=-DR1_FLAT_TWINS=0`)
+#endif
+extern "C" hipError_t r1_launch_trace(const R1TraceArgs *args, R1Build b, int blocks, size_t grid_lds, hipStream_t stream, int *walk_form)
 {
+    *walk_form = 0;
     // (a batch's or path's numbers, a pass's first sample and a listed pass's tile list are read through args->batch; the single-frame builds take none)
     if ((r1_mode_is_batch(b.mode) || r1_mode_is_pass(b.mode)) != (args->batch != nullptr))
         return hipErrorInvalidValue;
@@ -207,6 +215,13 @@ extern "C" hipError_t r1_launch_trace(const R1TraceArgs *args, R1Build b, int bl
     if (r1_build_lands(b.variant, b.stats, b.mode) != (args->land_res > 0u))
         return hipErrorInvalidValue;
     const size_t walk_lds = r1_walk_lds(b.variant, b.big, args->bvh_depth, args->bvh_lds_f4, grid_lds);
+    const bool twin = R1_FLAT_TWINS && (r1_same_build(b, R1_V_TREE, false, false, R1_MODE_TP) || r1_same_build(b, R1_V_TREE, false, false, R1_MODE_BATCH)) &&
+                      args->land_res > 0u && args->scene.bvh_flat_e >= 0.0f;
+    if (twin)
+    {
+        *walk_form = 1;
+        return r1_tu_tree_small_launch_flat(args, b, blocks, walk_lds, stream);
+    }
     if (r1_is_tree(b.variant))
         return b.big ? r1_tu_tree_big_launch(args, b, blocks, walk_lds, stream) : r1_tu_tree_small_launch(args, b, blocks, walk_lds, stream);
     if (r1_is_grid(b.variant) && args->grid == nullptr)

@@ -292,6 +292,8 @@ extern "C" int r1_last_launch_info(r1_context *c, r1_launch_info *out)
     return R1_OK;
 }
 
+extern "C" int r1_last_walk_form(r1_context *c) { return c ? c->walk_form : R1_EINVAL; }
+
 // internal (tools/land_debug.py): the context's counter allocation as it is after the stream has drained
 extern "C" int r1_debug_dump_counters(r1_context *c, void *out, size_t bytes, size_t *have)
 {

@@ -189,6 +189,7 @@ struct r1_context
     bool stage_busy = false;
 
     r1_launch_info info;
+    int walk_form = 0; // r1_last_walk_form: what r1_launch_trace said of the last trace launch (1: a flat twin ran)
 };
 
 // an address inside the context's counter allocation, by its offset in the layout of r1_device.h (R1_CNT_*, R1_TAIL_*, r1_land_area)

@@ -701,8 +701,9 @@ int enqueue_frame(r1_context *c, const r1_params *p, FrameJob job)
         return rc;
 
     R1_HIP(hipEventRecord(e[0], st));
+    c->walk_form = 0;
     if (c->total_samples && variant != R1_V_WAVEFRONT)
-        R1_HIP(r1_launch_trace(&a, k.b, (int)blocks, r1_is_grid(variant) && !k.b.big ? c->grid_args.lds_bytes : 0u, st));
+        R1_HIP(r1_launch_trace(&a, k.b, (int)blocks, r1_is_grid(variant) && !k.b.big ? c->grid_args.lds_bytes : 0u, st, &c->walk_form));
     if (c->total_samples && variant == R1_V_WAVEFRONT && (rc = launch_wavefront(c, a, st, &blocks)))
         return rc;
     R1_HIP(hipEventRecord(e[1], st));

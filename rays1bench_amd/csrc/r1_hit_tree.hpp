@@ -207,10 +207,30 @@ __device__ __forceinline__ void trav_start(Trav &t)
 // LN: the node table is read from `lnodes`, the workgroup's copy in LDS (the trace kernel on small scenes), instead of S.bvh_nodes.
 // SLOTS: the root step tests its leaf with leaf_root instead of leaf_quad (r1_builds.h r1_root_by_slots: one choice per build).
 // OFFER: the form of the closest-offer rule in the leaf tests (r1_offer.h r1_offer_better_form; the grid kernels' fallback walk passes the grid's).
-template <bool STATS, bool CARRY, bool LN, typename TS, bool SLOTS = false, int OFFER = R1_OFFER_FORM>
+// FLAT: is the tree flat (visit_flat below)?  R1_FLAT_ASK: the table says — bit 2 of the code in the LDS copy of node 0, read where it is
+// needed; every kernel r1_pick reaches.  R1_FLAT_YES / R1_FLAT_NO: the launch knows (LN walks only): one node loop is instantiated, and the
+// slab, the choice of the node loop and the F update after a leaf read no flag (r1_flatwalk_kernel).
+#define R1_FLAT_ASK (-1)
+#define R1_FLAT_NO 0
+#define R1_FLAT_YES 1
+#ifndef R1_ROOT_SCALAR
+// FLAT = R1_FLAT_YES: the root step's wave-uniform words by scalar loads (1) or from the LDS copy, as every other walk (0).  Left at 0: with
+// the words in scalar registers across the root leaf's test hipcc parks the kernel-argument pointer in a lane of the spill register and fetches
+// it back twice per iteration — 32 lane moves in the main loop against the generic kernel's 30 (28 at 0), profiles/r32/flat_walk_counts.txt —
+// and the library with it ran at the generic kernel's rate (profiles/r32/flat_walk_ab.txt).  `make tuning EXTRA=-DR1_ROOT_SCALAR=1` builds it.
+#define R1_ROOT_SCALAR 0
+#endif
+template <bool STATS, bool CARRY, bool LN, typename TS, bool SLOTS = false, int OFFER = R1_OFFER_FORM, int FLAT = R1_FLAT_ASK>
 __device__ __forceinline__ void bvh_advance(const R1DeviceScene &S, const V3 o, const V3 d, Trav &tv, TS *trav, const int tid,
                                             const uint32_t n_alive, unsigned long long *wstat, const float4 *lnodes /* LDS */, const uint32_t top = 0u /* !LN: nodes [0, top) are in lnodes */)
 {
+    static_assert(FLAT == R1_FLAT_ASK || LN, "a walk that knows its tree's flatness reads the table from LDS");
+    // The root step's words are the same for every lane.  A walk that knows its tree is flat fetches them by scalar loads — node 0 from the
+    // table in global memory through a constant-address-space pointer, the root-leaf code and the slab from the arguments, which is where the
+    // staging code takes them from — instead of a v_mov of an LDS address and a per-lane ds_read each.  Same words, same operations.
+    constexpr bool ROOT_S = FLAT == R1_FLAT_YES && R1_ROOT_SCALAR != 0;
+    typedef const float __attribute__((address_space(4))) *cf_ptr;
+    const cf_ptr sf = (cf_ptr)(const float *)S.bvh_nodes; // (used where ROOT_S)
     const float4 *__restrict__ nodes = S.bvh_nodes;
     const float4 *__restrict__ prims = S.bvh_prims;
     const uint32_t *__restrict__ ids = S.bvh_ids;
@@ -224,7 +244,7 @@ __device__ __forceinline__ void bvh_advance(const R1DeviceScene &S, const V3 o, 
     V3 pa_ray = mk(0.0f, 0.0f, 0.0f);
     if (LN)
     {
-        const float pad_ray = lnodes[3].x * r2; // the tree's A (every node carries it)
+        const float pad_ray = (ROOT_S ? sf[12] : lnodes[3].x) * r2; // the tree's A (every node carries it)
         pa_ray = mk(pad_ray * ainv.x, pad_ray * ainv.y, pad_ray * ainv.z);
     }
     float best = tv.best;
@@ -341,13 +361,16 @@ __device__ __forceinline__ void bvh_advance(const R1DeviceScene &S, const V3 o, 
     // pruning rule as a visit of node 0 followed by the leaf; one node trip and one leaf trip fewer per ray in the divergent loops below.
     // (the small-scene kernels find the code in the K slot of their LDS copy of node 0 — the trace kernel puts it there, K itself is folded
     //  into the half extents for their trees — instead of holding a scalar register for it through the whole kernel)
-    const uint32_t root_leaf = LN ? __float_as_uint(lnodes[3].y) & 3u : S.bvh_root_leaf; // (bit 2 of the LDS copy's code: a flat tree, see r1_trace_kernel)
+    const uint32_t root_leaf = LN && !ROOT_S ? __float_as_uint(lnodes[3].y) & 3u : S.bvh_root_leaf; // (bit 2 of the LDS copy's code: a flat tree, see r1_trace_kernel)
     if (root_leaf != 0u && cur == 0u) // (the first condition is wave-uniform)
     {
-        const int k = root_leaf == 1u ? 1 : 0; // column of the OTHER child in the node's rows
+        // column of the OTHER child in the node's rows (ROOT_S: an index of scalar loads — written as selects between the two columns, hipcc
+        // makes two v_mov and a v_cndmask of every word)
+        const int k = ROOT_S ? __builtin_amdgcn_readfirstlane(root_leaf == 1u ? 1 : 0) : (root_leaf == 1u ? 1 : 0);
         const float *nf = (const float *)lnodes; // node 0: always in the workgroup's LDS copy (big scenes keep the top of the tree there: at least node 0, r1_frame.cpp fill_walk)
-        const uint32_t leaf = __float_as_uint(nf[14 + (1 - k)]);
-        const uint32_t other = __float_as_uint(nf[14 + k]);
+        // (ROOT_S: the table's 32-bit references, converted on the scalar pipe to the 16-bit form the LDS copy holds)
+        const uint32_t leaf = ROOT_S ? r1_ref16(__float_as_uint(sf[14 + (1 - k)])) : __float_as_uint(nf[14 + (1 - k)]);
+        const uint32_t other = ROOT_S ? r1_ref16(__float_as_uint(sf[14 + k])) : __float_as_uint(nf[14 + k]);
         const uint32_t lp = (leaf >> COUNT_SHIFT) & 7u;
         if (STATS)
         {
@@ -373,7 +396,8 @@ __device__ __forceinline__ void bvh_advance(const R1DeviceScene &S, const V3 o, 
             pa = mk(pad * ainv.x, pad * ainv.y, pad * ainv.z);
         }
         float tn;
-        const bool h = bvh_box(nf[0 + k], nf[2 + k], nf[4 + k], nf[6 + k], nf[8 + k], nf[10 + k], pa, oi, inv, ainv, best, tn);
+        const bool h = ROOT_S ? bvh_box(sf[0 + k], sf[2 + k], sf[4 + k], sf[6 + k], sf[8 + k], sf[10 + k], pa, oi, inv, ainv, best, tn)
+                              : bvh_box(nf[0 + k], nf[2 + k], nf[4 + k], nf[6 + k], nf[8 + k], nf[10 + k], pa, oi, inv, ainv, best, tn);
         cur = h ? other : R1_BVH_DONE;
         // (the sibling's own visit taken into this step as well — `if (cur < LEAF_BIT) visit_node();` here — measured 35.5 against 36.2
         //  Grays/s: a generic visit runs at 0.54 lane utilisation inside the loop and at the ~0.34 of the starting lanes out here)
@@ -384,9 +408,16 @@ __device__ __forceinline__ void bvh_advance(const R1DeviceScene &S, const V3 o, 
     // carried over from an earlier call.
     // (the flag is made a scalar: the compiler cannot know that a value from LDS is wave-uniform, and a branch it takes for divergent runs
     //  both node loops one after the other)
-    if (LN && (__builtin_amdgcn_readfirstlane((int)__float_as_uint(lnodes[3].y)) & 4) != 0)
+    // (FLAT = R1_FLAT_YES: the slab stays behind a condition on a scalar the compiler cannot see through, one s_cmp.  With the slab in
+    //  straight-line code hipcc keeps -oi in registers of its own and forms them with three v_xor on either side of the root step: six
+    //  more VALU instructions per call than the flag's branch costs the generic kernel)
+    int slab_known = 1;
+    if (FLAT == R1_FLAT_YES)
+        asm volatile("" : "+s"(slab_known));
+    if ((FLAT == R1_FLAT_YES && slab_known != 0) || (FLAT == R1_FLAT_ASK && LN && (__builtin_amdgcn_readfirstlane((int)__float_as_uint(lnodes[3].y)) & 4) != 0))
     {
-        const float a_u = __fmaf_rn(lnodes[7].x, inv.y, -oi.y), b_u = __fmaf_rn(lnodes[7].y, ainv.y, pa_ray.y);
+        const float m_u = ROOT_S ? S.bvh_flat_m : lnodes[7].x, e_u = ROOT_S ? S.bvh_flat_e : lnodes[7].y;
+        const float a_u = __fmaf_rn(m_u, inv.y, -oi.y), b_u = __fmaf_rn(e_u, ainv.y, pa_ray.y);
         const float tyf = a_u + b_u;
         oi.y = fmaxf(a_u - b_u, 0.0f);
         // (a compare instead of fminf: the compiler canonicalises both operands of an fminf; a NaN sum — a ray that does not move along y — leaves `best`)
@@ -401,7 +432,13 @@ __device__ __forceinline__ void bvh_advance(const R1DeviceScene &S, const V3 o, 
         if (CARRY && R1_CARRY_DIV * (uint32_t)__popcll(walking) <= n_alive)
             break; // (n_alive <= 3: never true while a lane walks, so the last walks of a wave run to their end)
         // inner nodes: descend to the nearer child, remember the farther one
-        if (LN && (__builtin_amdgcn_readfirstlane((int)__float_as_uint(lnodes[3].y)) & 4) != 0)
+        if (FLAT == R1_FLAT_YES)
+            while (cur < LEAF_BIT)
+                visit_flat();
+        else if (FLAT == R1_FLAT_NO)
+            while (cur < LEAF_BIT)
+                visit_node();
+        else if (LN && (__builtin_amdgcn_readfirstlane((int)__float_as_uint(lnodes[3].y)) & 4) != 0)
             while (cur < LEAF_BIT)
                 visit_flat();
         else
@@ -439,7 +476,7 @@ __device__ __forceinline__ void bvh_advance(const R1DeviceScene &S, const V3 o, 
                 leaf_quad<OFFER>(prims, ids, first + j, take, o, d, best, best_id);
             }
             cur = sp > 0 ? trav_get(trav, --sp * R1_BLOCK + tid) : R1_BVH_DONE;
-            if (LN && (__builtin_amdgcn_readfirstlane((int)__float_as_uint(lnodes[3].y)) & 4) != 0)
+            if (FLAT == R1_FLAT_YES || (FLAT == R1_FLAT_ASK && LN && (__builtin_amdgcn_readfirstlane((int)__float_as_uint(lnodes[3].y)) & 4) != 0))
                 pa_ray.y = best < pa_ray.y ? best : pa_ray.y; // F = min(a_u + b_u, best): best has moved in the leaf, and only down
         }
     }

@@ -55,9 +55,11 @@ R1_TU_DECL(sweep_big)
 R1_TU_DECL(grid_small)
 R1_TU_DECL(grid_big)
 #undef R1_TU_DECL
+// r1_trace_tree_small.hip: the flat twin of build b (r1_flatwalk_kernel); hipErrorInvalidValue: b has none
+hipError_t r1_tu_tree_small_launch_flat(const R1TraceArgs *args, R1Build b, int blocks, size_t dyn_lds, hipStream_t stream);
 
 // r1_aux_kernels.hip: the trace launch and occupancy dispatch, the wavefront variant, the put kernels
-hipError_t r1_launch_trace(const R1TraceArgs *args, R1Build b, int blocks, size_t grid_lds, hipStream_t stream);
+hipError_t r1_launch_trace(const R1TraceArgs *args, R1Build b, int blocks, size_t grid_lds, hipStream_t stream, int *walk_form);
 hipError_t r1_trace_occupancy(R1Build b, size_t dyn_lds, int *blocks_per_cu);
 hipError_t r1_launch_wavefront(R1WaveArgs *w, int blocks, hipStream_t stream);
 hipError_t r1_launch_put6(void *dst, const uint32_t *words, hipStream_t stream);

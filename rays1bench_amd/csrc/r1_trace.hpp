@@ -101,7 +101,8 @@ struct TraceWaves
 // bring them nothing.  A pass on a big scene runs as R1_MODE_TP without landing; r1_accum_kernel / r1_adapt_accum_kernel sum a pass's records.
 // (the body of the kernel; r1_trace_kernel and, for the uniform grid, r1_grid_kernel below are its __global__ instances; r1_pass_kernel,
 // r1_path_kernel and r1_adaptive_kernel those of R1_MODE_PASS, _PATH and _LISTED)
-template <int VARIANT, bool STATS, bool BIG, int MODE>
+// FLAT: what the walk knows of the tree's flat axis before it looks (r1_hit_tree.hpp bvh_advance; R1_FLAT_ASK: nothing, every kernel r1_pick reaches)
+template <int VARIANT, bool STATS, bool BIG, int MODE, int FLAT = R1_FLAT_ASK>
 __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
 {
     constexpr bool LISTED = MODE == R1_MODE_LISTED, PASS = r1_mode_is_pass(MODE);
@@ -498,7 +499,7 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
         {
             // while-while with carry-over
             R1_FRESH_ARGS(HA) // (table pointers, the tree's centre: fetched for the walk, free again after it)
-            bvh_advance<STATS, true, LN, TS, r1_root_by_slots(STATS, BIG, MODE)>(HA.scene, p.o, p.d, tv, (TS *)s_trav, tid, (uint32_t)__popcll(live_now), wstat, lnodes, top);
+            bvh_advance<STATS, true, LN, TS, r1_root_by_slots(STATS, BIG, MODE), R1_OFFER_FORM, FLAT>(HA.scene, p.o, p.d, tv, (TS *)s_trav, tid, (uint32_t)__popcll(live_now), wstat, lnodes, top);
             ready = alive && tv.cur == R1_BVH_DONE;
             if (tv.best_id != 0xFFFFFFFFu)
                 t_hit = tv.best, hit = (int)tv.best_id;
@@ -660,6 +661,14 @@ template <bool STATS, bool BIG, int MODE>
 __global__ void __launch_bounds__(R1_BLOCK, (TraceWaves<R1_V_GRID, STATS, BIG, MODE>::value)) r1_grid_kernel(const R1TraceArgs A)
 {
     r1_trace_body<R1_V_GRID, STATS, BIG, MODE>(A);
+}
+
+// Flat box trees: the frames-in-flight tree kernels of small scenes, <R1_V_TREE, false, false, R1_MODE_TP / _BATCH>, with the
+// walk's flat axis compiled in.  No build of r1_pick's: r1_launch_trace launches one in its sibling's place when the launch's tree is flat.
+template <int MODE>
+__global__ void __launch_bounds__(R1_BLOCK, (TraceWaves<R1_V_TREE, false, false, MODE>::value)) r1_flatwalk_kernel(const R1TraceArgs A)
+{
+    r1_trace_body<R1_V_TREE, false, false, MODE, R1_FLAT_YES>(A);
 }
 
 // Progressive passes (R1_MODE_PASS): the same body under a name of its own, for the tree, the exhaustive sweeps (grouped and reference form) and the grid
