@@ -427,6 +427,61 @@ int r1_quantise_linear(const float *linear, size_t n_values, uint8_t *out);
  * against every sphere), meant for small frames: it is what lets the value be checked without a GPU.  num_rays_out may be NULL. */
 int r1_render_linear_host(const r1_scene *scene, const r1_camera *camera, const r1_params *params, float *rgb_out, uint64_t *num_rays_out);
 
+/* ---- region renders: a window of the frame, bit for bit its crop ---- */
+
+/* A window of the frame `params` describes.  params keeps the meaning it has in r1_render: its width and height fix the pixel index
+ * y * width + x of the seeds (rays1_seed.h) and the camera's 1/W, 1/H, so a sample's streams depend on (seed, pixel of the FRAME, sample
+ * index) alone and the window's pixels are the frame's, whatever else the launch traces. */
+typedef struct r1_region
+{
+    int32_t x0, y0;        /* lower-left pixel of the window in the frame (row 0 = bottom row, as everywhere) */
+    int32_t width, height; /* its size in pixels, >= 1; x0 + width <= params->width, y0 + height <= params->height */
+    int32_t out_stride;    /* pixels between the starts of two rows of the OUTPUT image; 0 = width, else >= width */
+} r1_region;
+
+/* Results, with stride = out_stride ? out_stride : width:
+ *   bytes    pixel (x, y) of the region at out + ((size_t)y * stride + x) * 3 equals pixel (x0 + x, y0 + y) of r1_render(params), byte for byte;
+ *   linear   floats at out + ((size_t)y * stride + x) * 3 equal r1_render_linear's value of that pixel, bit for bit;
+ *   records  equal r1_render_samples' records of those pixels, in the region's own order ((y * region.width + x) * spp + s), dense;
+ *   count    the color() calls of exactly the region's samples = the sum of those records' count words;
+ *   with out_stride > width the bytes between the rows are not written: out_stride = params->width and out = frame + (y0 * W + x0) * 3
+ *   patch a window into a caller's whole frame.
+ * Limits: params must pass every check of r1_params_check except the sample total; the frame has width * height < 2^31 (the pixel index
+ * stays an int) and need not fit one launch; the region is bounded as a frame of its own size is: region.width * region.height * spp
+ * < 2^31 and the padded sample slots of its tiles < 2^31, else R1_ELIMIT.  So a 40 000 x 40 000 x 2 frame, which r1_render refuses, is
+ * rendered window by window.  Whole-frame sharding is not combined with regions (num_shards != 1: R1_EINVAL); the variants are those
+ * r1_render_pass accepts (DEFAULT, REFERENCE, PREFILTER, BVH, GRID; the diagnostic variants and WAVEFRONT: R1_EINVAL).  After an update
+ * regions are served and refused as frames are.  PIXEL mode does not apply.  One region render per context at a time, as for any frame.
+ * The region's tiles (params->tile_w x tile_h) are cut from the region's own corner. */
+
+/* Pure arithmetic, no device: the one place the rules above are checked; every call below uses it.  R1_EINVAL names the offending
+ * field in r1_last_error; R1_ELIMIT as above. */
+int r1_region_check(const r1_params *params, const r1_region *region);
+
+/* Synchronous; r1_render's rules otherwise: it leaves a progressive accumulation alone, and r1_last_launch_info / r1_last_timing
+ * describe it.  num_rays_out and device_seconds_out may be NULL. */
+int r1_render_region(r1_context *ctx, const r1_params *params, const r1_region *region, uint8_t *rgb_out, uint64_t *num_rays_out,
+                     double *device_seconds_out);
+
+/* The same, plus the records: samples_out receives region.width * region.height * spp records of 4 floats (r1_render_samples' record). */
+int r1_render_region_samples(r1_context *ctx, const r1_params *params, const r1_region *region, uint8_t *rgb_out, uint64_t *num_rays_out,
+                             float *samples_out);
+
+/* The linear form: three floats per pixel (r1_render_linear's value). */
+int r1_render_region_linear(r1_context *ctx, const r1_params *params, const r1_region *region, float *rgb_out, uint64_t *num_rays_out,
+                            double *device_seconds_out);
+
+/* Into DEVICE memory: d_rgb_u8 (bytes) and d_rgb_f32 (floats, 4-byte aligned) — either or both, R1_EINVAL if neither — and d_num_rays
+ * (one uint64, 8-byte aligned, not NULL).  Everything is enqueued on `hip_stream` (NULL = the context's stream) and nothing is waited
+ * for, as with r1_render_linear_device.  A refused call enqueues nothing. */
+int r1_render_region_device(r1_context *ctx, const r1_params *params, const r1_region *region, void *d_rgb_u8, void *d_rgb_f32,
+                            void *d_num_rays, void *hip_stream);
+
+/* The CPU form, no device: r1_camera_rays + r1_trace_rays_host per sample, summed as r1_render_linear_host sums; honours out_stride
+ * (nothing between the rows is written).  Bytes come from r1_quantise_linear.  num_rays_out may be NULL. */
+int r1_render_region_host(const r1_scene *scene, const r1_camera *camera, const r1_params *params, const r1_region *region, float *linear_out,
+                          uint64_t *num_rays_out);
+
 /* Pipelined form of r1_render — frames in flight whose results land on the HOST.  The reference times
  * dispatch -> pixels + ray count on the host (rayweek1.cpp:848 -> :891) for ONE frame and waits; a caller that
  * renders frame after frame (main's `-n` runs, rayweek1.cpp:969-984) can keep several in flight instead: the call

@@ -92,6 +92,11 @@ class Adaptive(C.Structure):
     _fields_ = [("min_spp", C.c_int32), ("pass_spp", C.c_int32), ("max_delta", C.c_int32), ("mean_delta_q8", C.c_int32)]
 
 
+class Region(C.Structure):
+    """r1_region: a window of the frame (x0, y0: its lower-left pixel; out_stride: pixels between two rows of the output, 0 = width)."""
+    _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("out_stride", C.c_int32)]
+
+
 class TileReport(C.Structure):
     _fields_ = [("spp", C.c_int32), ("settled", C.c_int32), ("err_max", C.c_uint32), ("err_sum", C.c_uint32)]
 
@@ -248,6 +253,12 @@ SYMBOLS = [
     ("r1_render_adaptive_linear", C.c_int, [_ctx, C.POINTER(Params), C.POINTER(Adaptive), _f32p, _u64p, C.POINTER(TileReport), C.POINTER(AdaptiveResult)]),
     ("r1_quantise_linear", C.c_int, [_f32p, C.c_size_t, _u8p]),
     ("r1_render_linear_host", C.c_int, [C.POINTER(CScene), C.POINTER(CCamera), C.POINTER(Params), _f32p, _u64p]),
+    ("r1_region_check", C.c_int, [C.POINTER(Params), C.POINTER(Region)]),
+    ("r1_render_region", C.c_int, [_ctx, C.POINTER(Params), C.POINTER(Region), C.c_void_p, _u64p, _dblp]),
+    ("r1_render_region_samples", C.c_int, [_ctx, C.POINTER(Params), C.POINTER(Region), C.c_void_p, _u64p, _f32p]),
+    ("r1_render_region_linear", C.c_int, [_ctx, C.POINTER(Params), C.POINTER(Region), C.c_void_p, _u64p, _dblp]),
+    ("r1_render_region_device", C.c_int, [_ctx, C.POINTER(Params), C.POINTER(Region), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("r1_render_region_host", C.c_int, [C.POINTER(CScene), C.POINTER(CCamera), C.POINTER(Params), C.POINTER(Region), C.c_void_p, _u64p]),
     ("r1_pfm_write_rgb32f", C.c_int, [C.c_char_p, C.c_int32, C.c_int32, _f32p]),
     ("r1_tga_write_rgb24", C.c_int, [C.c_char_p, C.c_int32, C.c_int32, _u8p]),
     ("r1_log_results", C.c_int, [C.c_char_p, C.c_char_p, _dblp, _u64p, C.c_int32]),
@@ -557,6 +568,40 @@ class Renderer:
         rays, secs = C.c_uint64(), C.c_double()
         _check(lib().r1_render_linear(self._c, C.byref(params), img.ctypes.data_as(_f32p), C.byref(rays), C.byref(secs)))
         return img, int(rays.value), float(secs.value)
+
+    def render_region(self, params, region, out=None):
+        """r1_render_region: window `region` = (x0, y0, width, height) of the frame `params` describes, byte for byte the crop of
+        render(params).  Returns (uint8 (height, width, 3) of the region, ray count of the region's samples, device seconds).  `out`: a
+        uint8 array of that shape to render into; it may be a view into a larger image (rows a multiple of three bytes apart), whose
+        row pitch becomes the region's out_stride — out=frame[y0:y0 + h, x0:x0 + w] patches the window into a whole frame."""
+        rg, img = _region_target(region, out, np.uint8)
+        rays, secs = C.c_uint64(), C.c_double()
+        _check(lib().r1_render_region(self._c, C.byref(params), C.byref(rg), C.c_void_p(img.ctypes.data), C.byref(rays), C.byref(secs)))
+        return img, int(rays.value), float(secs.value)
+
+    def render_region_samples(self, params, region, out=None):
+        """r1_render_region_samples: render_region plus the records of the region's samples, float32 (height * width * spp, 4) in the
+        region's own order ((y * width + x) * spp + s).  Returns (image, ray count, records)."""
+        rg, img = _region_target(region, out, np.uint8)
+        samples = np.zeros((max(rg.height, 0) * max(rg.width, 0) * max(params.spp, 0), 4), np.float32)
+        rays = C.c_uint64()
+        _check(lib().r1_render_region_samples(self._c, C.byref(params), C.byref(rg), C.c_void_p(img.ctypes.data), C.byref(rays), samples.ctypes.data_as(_f32p)))
+        return img, int(rays.value), samples
+
+    def render_region_linear(self, params, region, out=None):
+        """r1_render_region_linear: the region as fp32 radiance, bit for bit the crop of render_linear(params).  Returns (float32
+        (height, width, 3), ray count, device seconds).  `out`: as for render_region, a float32 array or view."""
+        rg, img = _region_target(region, out, np.float32)
+        rays, secs = C.c_uint64(), C.c_double()
+        _check(lib().r1_render_region_linear(self._c, C.byref(params), C.byref(rg), C.c_void_p(img.ctypes.data), C.byref(rays), C.byref(secs)))
+        return img, int(rays.value), float(secs.value)
+
+    def render_region_device(self, params, region, d_rgb_u8_ptr, d_rgb_f32_ptr, d_rays_ptr, out_stride=0, stream_ptr=None):
+        """r1_render_region_device: the region into device memory — bytes at d_rgb_u8_ptr, floats at d_rgb_f32_ptr (either may be None / 0),
+        rows out_stride pixels apart (0 = the region's width), and one uint64 at d_rays_ptr; waits for nothing."""
+        rg = Region(*[int(v) for v in region], int(out_stride))
+        _check(lib().r1_render_region_device(self._c, C.byref(params), C.byref(rg), C.c_void_p(d_rgb_u8_ptr or None), C.c_void_p(d_rgb_f32_ptr or None),
+                                             C.c_void_p(d_rays_ptr or None), _stream_arg(stream_ptr)))
 
     def render_linear_async(self, params, frame_ptr, rays_ptr, stream_ptr=None):
         """r1_render_linear_async: enqueue one linear frame (throughput kernels); width * height * 3 floats land at `frame_ptr` and the
@@ -1164,6 +1209,38 @@ def render_linear_host(cscene, ccamera, params):
     img = np.zeros((params.height, params.width, 3), np.float32)
     rays = C.c_uint64()
     _check(lib().r1_render_linear_host(C.byref(cscene), C.byref(ccamera), C.byref(params), img.ctypes.data_as(_f32p), C.byref(rays)))
+    return img, int(rays.value)
+
+
+def _region_target(region, out, dtype):
+    """(Region, array) of a host-memory region render: a new dense (height, width, 3) array, or the caller's `out` — an array or a view of that
+    shape whose pixels are contiguous and whose rows lie a whole number of pixels apart: that pitch is the region's out_stride."""
+    x0, y0, w, h = (int(v) for v in region)
+    if out is None:
+        if w < 1 or h < 1:  # (no array of that shape: let the library name the field)
+            return Region(x0, y0, w, h, 0), np.zeros((1, 1, 3), dtype)
+        return Region(x0, y0, w, h, 0), np.zeros((h, w, 3), dtype)
+    item = np.dtype(dtype).itemsize
+    if not (isinstance(out, np.ndarray) and out.dtype == np.dtype(dtype) and out.shape == (h, w, 3) and out.strides[1:] == (3 * item, item)
+            and out.strides[0] % (3 * item) == 0 and out.strides[0] >= 3 * item * w and out.flags.writeable):
+        raise R1Error(R1_EINVAL, f"region render: out must be a writeable {np.dtype(dtype).name} array or view of shape ({h}, {w}, 3) with whole pixels between its rows")
+    return Region(x0, y0, w, h, out.strides[0] // (3 * item)), out
+
+
+def region_check(params, region, out_stride=0):
+    """r1_region_check: raises R1Error (code R1_EINVAL or R1_ELIMIT, the text names the field) unless `region` = (x0, y0, width, height) with
+    out_stride is a window of the frame `params` describes that a region render accepts.  Pure arithmetic."""
+    rg = Region(*[int(v) for v in region], int(out_stride))
+    _check(lib().r1_region_check(C.byref(params), C.byref(rg)))
+    return True
+
+
+def render_region_host(cscene, ccamera, params, region, out=None):
+    """r1_render_region_host: the region's linear values on the CPU (camera_rays + trace_rays_host per sample; no device; slow).  Returns
+    (float32 (height, width, 3), ray count); `out` as for Renderer.render_region_linear.  Bytes: quantise_linear of the result."""
+    rg, img = _region_target(region, out, np.float32)
+    rays = C.c_uint64()
+    _check(lib().r1_render_region_host(C.byref(cscene), C.byref(ccamera), C.byref(params), C.byref(rg), C.c_void_p(img.ctypes.data), C.byref(rays)))
     return img, int(rays.value)
 
 

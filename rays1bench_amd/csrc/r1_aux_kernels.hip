@@ -205,9 +205,13 @@ extern "C" hipError_t r1_launch_put_cameras(void *dst, const float *cameras20, i
 #ifndef R1_FLAT_TWINS
 #define R1_FLAT_TWINS 1 // 0: the generic kernels serve every tree (`make tuning EXTRA=-DR1_FLAT_TWINS=0`)
 #endif
-extern "C" hipError_t r1_launch_trace(const R1TraceArgs *args, R1Build b, int blocks, size_t grid_lds, hipStream_t stream, int *walk_form)
+// Region renders: `region` != 0 — the pass behind args->batch carries a region's corner — runs the region twin of the R1_MODE_PASS
+// build b, r1_region_kernel, chosen here as the flat twins are; any other build is refused.
+extern "C" hipError_t r1_launch_trace(const R1TraceArgs *args, R1Build b, int blocks, size_t grid_lds, hipStream_t stream, int *walk_form, int region)
 {
     *walk_form = 0;
+    if (region && (b.mode != R1_MODE_PASS || b.stats))
+        return hipErrorInvalidValue;
     // (a batch's or path's numbers, a pass's first sample and a listed pass's tile list are read through args->batch; the single-frame builds take none)
     if ((r1_mode_is_batch(b.mode) || r1_mode_is_pass(b.mode)) != (args->batch != nullptr))
         return hipErrorInvalidValue;
@@ -222,10 +226,18 @@ extern "C" hipError_t r1_launch_trace(const R1TraceArgs *args, R1Build b, int bl
         *walk_form = 1;
         return r1_tu_tree_small_launch_flat(args, b, blocks, walk_lds, stream);
     }
-    if (r1_is_tree(b.variant))
-        return b.big ? r1_tu_tree_big_launch(args, b, blocks, walk_lds, stream) : r1_tu_tree_small_launch(args, b, blocks, walk_lds, stream);
     if (r1_is_grid(b.variant) && args->grid == nullptr)
         return hipErrorInvalidValue; // (the grid kernels read their tables through this pointer)
+    if (region)
+    {
+        if (r1_is_tree(b.variant))
+            return b.big ? r1_tu_tree_big_launch_region(args, b, blocks, walk_lds, stream) : r1_tu_tree_small_launch_region(args, b, blocks, walk_lds, stream);
+        if (r1_is_grid(b.variant))
+            return b.big ? r1_tu_grid_big_launch_region(args, b, blocks, walk_lds, stream) : r1_tu_grid_small_launch_region(args, b, blocks, walk_lds, stream);
+        return b.big ? r1_tu_sweep_big_launch_region(args, b, blocks, walk_lds, stream) : r1_tu_sweep_small_launch_region(args, b, blocks, walk_lds, stream);
+    }
+    if (r1_is_tree(b.variant))
+        return b.big ? r1_tu_tree_big_launch(args, b, blocks, walk_lds, stream) : r1_tu_tree_small_launch(args, b, blocks, walk_lds, stream);
     if (r1_is_grid(b.variant))
         return b.big ? r1_tu_grid_big_launch(args, b, blocks, walk_lds, stream) : r1_tu_grid_small_launch(args, b, blocks, walk_lds, stream);
     return b.big ? r1_tu_sweep_big_launch(args, b, blocks, walk_lds, stream) : r1_tu_sweep_small_launch(args, b, blocks, walk_lds, stream);

@@ -1,4 +1,4 @@
-// r1_close_kernels.hip — the kernels that close a frame behind the trace launch (resolve, linear resolve and read-out, progressive accumulate, adaptive
+// r1_close_kernels.hip — the kernels that close a frame behind the trace launch (resolve, region resolve, linear resolve and read-out, progressive accumulate, adaptive
 // accumulate and compact, batch counts, assemble, landing arm) and their launchers, called from r1_frame.cpp and r1_render.cpp.  The tile geometry is
 // r1_tile.h's; quantise_pixel is the trace kernels' (r1_sample.hpp).  The trace kernel's own resolver: r1_land.hpp.
 #include "r1_sample.hpp"
@@ -110,6 +110,38 @@ __global__ void __launch_bounds__(256) r1_resolve_linear_kernel(const R1LinearAr
             sum_records(A.samples + (size_t)lt * A.full + pix, tile_px, A.spp, cr, cg, cb);
             float *const o = A.out + r1_pixel_row_major(A.geom, rect, lx, ly) * 3;
             o[0] = cr * A.inv_spp, o[1] = cg * A.inv_spp, o[2] = cb * A.inv_spp; // col *= 1 / spp rayweek1.cpp:765
+        }
+    }
+}
+
+// Region renders (r1_render_region*): in place of the resolve launch behind a launch of r1_region_kernel.  The resolve's walk over
+// [tile][sample][pixel] records with the region's own tile geometry — void slots of its edge tiles skipped — and the resolve's sums; the pixel goes
+// to (y * stride + x) of the caller's window as bytes (quantise_pixel), as floats (its first line: the sum times inv_spp), or both.  Nothing
+// between the rows is written.  The w word is not read: the trace launch counted its rays itself, and the prologue publishes that count.
+__global__ void __launch_bounds__(256) r1_resolve_region_kernel(const R1RegionArgs A)
+{
+    if (blockIdx.x == 0 && blockIdx.y == 0 && A.close.rays_src)
+        close_prologue(A.close);
+    const uint32_t tile_px = r1_tile_slots(A.geom);
+    for (uint32_t lt = blockIdx.y; lt < A.n_tiles; lt += gridDim.y)
+    {
+        const R1TileRect rect = r1_tile_rect(A.geom, lt);
+        for (uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x; pix < tile_px; pix += gridDim.x * blockDim.x)
+        {
+            int lx, ly;
+            if (!r1_tile_pixel(A.geom, rect, pix, &lx, &ly))
+                continue; // void slots of an edge tile
+            float cr = 0, cg = 0, cb = 0;
+            sum_records(A.samples + (size_t)lt * A.full + pix, tile_px, A.spp, cr, cg, cb);
+            const size_t o = ((size_t)(rect.y0 + ly) * A.stride + (size_t)(rect.x0 + lx)) * 3;
+            if (A.out_f32)
+                A.out_f32[o + 0] = cr * A.inv_spp, A.out_f32[o + 1] = cg * A.inv_spp, A.out_f32[o + 2] = cb * A.inv_spp; // col *= 1 / spp rayweek1.cpp:765
+            if (A.out_u8)
+            {
+                uint8_t r, g, b;
+                quantise_pixel(cr, cg, cb, A.inv_spp, r, g, b);
+                A.out_u8[o + 0] = r, A.out_u8[o + 1] = g, A.out_u8[o + 2] = b;
+            }
         }
     }
 }
@@ -369,6 +401,13 @@ extern "C" hipError_t r1_launch_accum(const R1AccumArgs *args, hipStream_t strea
 extern "C" hipError_t r1_launch_resolve_linear(const R1LinearArgs *args, int max_rows, hipStream_t stream)
 {
     hipLaunchKernelGGL(r1_resolve_linear_kernel, tile_row_grid(args->geom, args->n_tiles, max_rows), dim3(256), 0, stream, *args);
+    return hipGetLastError();
+}
+
+// region renders: one row of workgroups per tile of the region, as r1_launch_accum
+extern "C" hipError_t r1_launch_resolve_region(const R1RegionArgs *args, hipStream_t stream)
+{
+    hipLaunchKernelGGL(r1_resolve_region_kernel, tile_row_grid(args->geom, args->n_tiles, 0), dim3(256), 0, stream, *args);
     return hipGetLastError();
 }
 

@@ -218,6 +218,10 @@ struct Landing
 // the resolve launch.  FrameJob::out receives the preview unless `image` is false.
 // A pass of r1_render_adaptive has a tile list: the launch's tiles are list[0, n_listed) of the frame's, traced by the R1_MODE_LISTED kernels and summed
 // and tested by r1_adapt_accum_kernel (accumulators and reports: the context's, indexed by tile of the frame).
+// A region render (r1_render_region*) is a pass with a region: first_sample 0, the launch's tiles cut from the region's own corner
+// (enqueue_frame takes its tile geometry from the region's size), traced by the region twins of the R1_MODE_PASS kernels and closed by
+// r1_resolve_region_kernel, which stores FrameJob::out (bytes; may be null), region_linear (floats; may be null) or both with the region's row
+// stride.  No accumulator is touched: a progressive accumulation of the context stays as it is.
 struct Pass
 {
     int32_t first_sample = 0;
@@ -225,6 +229,8 @@ struct Pass
     const uint32_t *list = nullptr; // device memory
     uint32_t n_listed = 0;
     const r1_adaptive *rule = nullptr;
+    const r1_region *region = nullptr; // r1_region_check has passed it
+    float *region_linear = nullptr;    // device address
 };
 
 // A linear frame (r1_render_linear*): behind the frame's trace and whatever closes it, r1_resolve_linear_kernel sums the records

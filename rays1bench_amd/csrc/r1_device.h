@@ -169,12 +169,14 @@ struct R1PathArgs
 // (null in every single-frame launch).  Six words: written by r1_launch_put6 into a batch-argument slot.
 // Adaptive sampling (r1_render_adaptive, the R1_MODE_LISTED builds): behind it the pass's tile list — the launch's local tile j is tile list[j] of
 // the frame — device memory; null in a pass of r1_render_pass, whose kernels never read it.
+// Region renders (r1_render_region*, r1_region_kernel): the region's corner in the frame and the frame's width, which the lanes add and
+// seed with once a sample has passed the bound test of the region's own tiles; zero in every other pass, whose kernels never read them.
 struct R1PassArgs
 {
     uint32_t first_sample;
-    uint32_t unused0;
+    uint32_t x0;
     const uint32_t *list;
-    uint32_t unused[2];
+    uint32_t y0, frame_w;
 };
 
 // What the waves that sum finished tiles need (R1_LAND); by value in the kernel arguments, read when a wave has run out of samples.
@@ -485,6 +487,22 @@ struct R1LinearArgs
     int32_t spp;
     uint32_t n_tiles;
     float inv_spp;               // (float)(1.0f / spp)
+};
+
+// Region renders (r1_resolve_region_kernel): the records of a launch over the REGION's tiles (geom: a frame of the region's size),
+// summed as the resolve sums them, into a window whose rows lie `stride` pixels apart: bytes, floats or both.
+struct R1RegionArgs
+{
+    const float4 *samples;       // [tile of the region][sample][pixel of the padded tile]; x, y, z alone are used
+    uint8_t *out_u8;             // pixel (x, y) of the region at out_u8 + (y * stride + x) * 3, or null
+    float *out_f32;              // ... at out_f32 + (y * stride + x) * 3, or null
+    uint32_t full;               // tile_w * tile_h * spp
+    R1TileGeom geom;             // the region's own tiling: width and height are the region's
+    int32_t spp;
+    uint32_t n_tiles;
+    uint32_t stride;             // pixels between the starts of two rows of the output, >= geom.width
+    float inv_spp;               // (float)(1.0f / spp)
+    R1FrameClose close;
 };
 
 // r1_accum_linear_kernel: the read-out of the accumulators of r1_render_pass and r1_render_adaptive, the padded [tile][pixel] layout to

@@ -44,7 +44,7 @@ static int prepare_tiles(r1_context *c, const r1_params *p, const R1TileGeom &g,
     const uint64_t full = (uint64_t)p->tile_w * p->tile_h * p->spp;
     if (full * local * (uint64_t)n_frames >= ((uint64_t)1 << 31) || (uint64_t)total * p->num_shards >= ((uint64_t)1 << 31))
     {
-        r1_set_error("%d frame(s) of %dx%dx%d with %dx%d tiles exceed 2^31 sample slots per launch", n_frames, p->width, p->height, p->spp, p->tile_w,
+        r1_set_error("%d frame(s) of %dx%dx%d with %dx%d tiles exceed 2^31 sample slots per launch", n_frames, g.width, g.height, p->spp, p->tile_w,
                      p->tile_h);
         return R1_ELIMIT;
     }
@@ -166,11 +166,20 @@ static int choose_kernel(const r1_context *c, const r1_params *p, const FrameJob
 // A listed pass has the list's length as its tile count — grid size, queue length and record buffer follow from it — so n_local_tiles and
 // total_samples are rewritten BEFORE anything is sized, and the cached tiling, which no longer describes the params it is kept under, is
 // dropped: the next call derives its own.  A pass of r1_render_pass gets its accumulator.
+// A region's tiles are those of a frame of the region's size (g is that frame's geometry): derived afresh, and the cached tiling is dropped
+// as for a listed pass — the key would describe the params' frame, not the region.  A region has no accumulator.
 static int size_tiles(r1_context *c, const r1_params *p, const R1TileGeom &g, const FrameJob &job)
 {
+    const bool region = job.pass && job.pass->region;
+    if (region)
+        c->tile_key_valid = false;
     int rc = ensure_counters(c, p, g, job.batch ? job.batch->n_frames : 1);
+    if (region)
+        c->tile_key_valid = false;
     if (rc)
         return rc;
+    if (region)
+        return R1_OK;
     if (job.pass && job.pass->list)
     {
         c->n_local_tiles = job.pass->n_listed;
@@ -233,7 +242,9 @@ static void frame_args(const r1_context *c, const r1_params *p, const Choice &k,
     memset(&a, 0, sizeof(a));
     fill_scene(c, a.scene);
     a.cam = job.batch && job.batch->cameras && job.batch->n_frames == 1 ? device_camera(job.batch->cameras[0]) : c->cam;
-    a.width = p->width, a.height = p->height, a.spp = p->spp, a.max_bounces = p->max_bounces;
+    // (g: the frame's geometry — a region's: the launch's bound test and record places see a frame of the region's size, while 1/W and 1/H stay the
+    //  whole frame's, with which the region's lanes aim their samples, r1_sample.hpp start_sample)
+    a.width = g.width, a.height = g.height, a.spp = p->spp, a.max_bounces = p->max_bounces;
     a.seed = p->seed;
     a.inv_w = 1.0f / p->width, a.inv_h = 1.0f / p->height; // Vec3 inv_image_size(1.0f / td.image_w, 1.0f / td.image_h, 0) rayweek1.cpp:746
     a.tile_w = g.tile_w, a.tile_h = g.tile_h, a.tiles_x = g.tiles_x;
@@ -309,7 +320,7 @@ static int put_path_cameras(r1_context *c, const Batch *batch, hipStream_t st, c
 
 // R1TraceArgs::batch (null in a single frame): a batch's numbers, behind them a path's camera table; or a pass's first sample and tile
 // list, which the R1_MODE_PASS / _LISTED kernels read where a sample is seeded.
-static int put_batch_block(r1_context *c, const Choice &k, const FrameJob &job, R1TraceArgs &a)
+static int put_batch_block(r1_context *c, const r1_params *p, const Choice &k, const FrameJob &job, R1TraceArgs &a)
 {
     static_assert(sizeof(R1BatchArgs) == 24 && sizeof(R1PassArgs) == 24, "r1_launch_put6 writes the six words of R1BatchArgs / R1PassArgs");
     static_assert(sizeof(R1PathArgs) == 32 && __builtin_offsetof(R1PathArgs, cameras) == 24, "r1_launch_put8 writes the eight words of R1PathArgs into a 32-byte slot");
@@ -332,6 +343,8 @@ static int put_batch_block(r1_context *c, const Choice &k, const FrameJob &job, 
         memset(&pa, 0, sizeof(pa));
         pa.first_sample = (uint32_t)job.pass->first_sample;
         pa.list = job.pass->list;
+        if (job.pass->region) // (the corner the lanes add, and the frame's width they seed with)
+            pa.x0 = (uint32_t)job.pass->region->x0, pa.y0 = (uint32_t)job.pass->region->y0, pa.frame_w = (uint32_t)p->width;
         return put_batch_args(c, &pa, 6, nullptr, job.st, &a.batch);
     }
     return R1_OK;
@@ -597,6 +610,20 @@ static int close_frame(r1_context *c, const r1_params *p, const Choice &k, const
         ad.close = close;
         R1_HIP(r1_launch_adapt_accum(&ad, st));
     }
+    else if (job.pass && job.pass->region && c->n_local_tiles)
+    {
+        // region render: the records of the region's tiles, resolved into the caller's window (bytes, floats or both)
+        const r1_region *const rg = job.pass->region;
+        R1RegionArgs r = {};
+        r.samples = (const float4 *)c->samples.p;
+        r.out_u8 = (uint8_t *)job.out, r.out_f32 = job.pass->region_linear;
+        r.full = c->full, r.n_tiles = c->n_local_tiles;
+        r.geom = g, r.spp = p->spp;
+        r.stride = (uint32_t)(rg->out_stride ? rg->out_stride : rg->width);
+        r.inv_spp = (float)(1.0f / p->spp); // rayweek1.cpp:765
+        r.close = close;
+        R1_HIP(r1_launch_resolve_region(&r, st));
+    }
     else if (job.pass && c->n_local_tiles)
     {
         // progressive pass: the records go into the accumulator, and the preview of samples [0, first_sample + spp) into job.out
@@ -660,7 +687,8 @@ int enqueue_frame(r1_context *c, const r1_params *p, FrameJob job)
         r1_set_error("no scene set (call r1_set_scene first)");
         return R1_EINVAL;
     }
-    int rc = r1_params_check(p);
+    const r1_region *const region = job.pass ? job.pass->region : nullptr;
+    int rc = region ? r1_region_check(p, region) : r1_params_check(p); // (a region's frame need not fit one launch)
     if (rc)
         return rc;
     const hipStream_t st = job.st;
@@ -674,7 +702,8 @@ int enqueue_frame(r1_context *c, const r1_params *p, FrameJob job)
     R1_HIP(hipSetDevice(c->device));
     if (r1_is_grid(variant) && (rc = ensure_grid(c)))
         return rc;
-    const R1TileGeom g = r1_tile_geom(p->width, p->height, p->tile_w, p->tile_h); // the frame's geometry, for every step and closing launch
+    // the frame's geometry, for every step and closing launch; a region's: that of a frame of the region's size, tiles cut from its own corner
+    const R1TileGeom g = region ? r1_tile_geom(region->width, region->height, p->tile_w, p->tile_h) : r1_tile_geom(p->width, p->height, p->tile_w, p->tile_h);
     if ((rc = size_tiles(c, p, g, job)))
         return rc;
     if (!job.rays) // (only now: the counter allocation may have moved)
@@ -685,7 +714,7 @@ int enqueue_frame(r1_context *c, const r1_params *p, FrameJob job)
 
     R1TraceArgs a;
     frame_args(c, p, k, job, g, a);
-    if ((rc = put_batch_block(c, k, job, a)))
+    if ((rc = put_batch_block(c, p, k, job, a)))
         return rc;
     int per_cu = 1, land_parity = 0;
     if ((rc = blocks_per_cu(c, k, a, &per_cu)))
@@ -703,7 +732,7 @@ int enqueue_frame(r1_context *c, const r1_params *p, FrameJob job)
     R1_HIP(hipEventRecord(e[0], st));
     c->walk_form = 0;
     if (c->total_samples && variant != R1_V_WAVEFRONT)
-        R1_HIP(r1_launch_trace(&a, k.b, (int)blocks, r1_is_grid(variant) && !k.b.big ? c->grid_args.lds_bytes : 0u, st, &c->walk_form));
+        R1_HIP(r1_launch_trace(&a, k.b, (int)blocks, r1_is_grid(variant) && !k.b.big ? c->grid_args.lds_bytes : 0u, st, &c->walk_form, region ? 1 : 0));
     if (c->total_samples && variant == R1_V_WAVEFRONT && (rc = launch_wavefront(c, a, st, &blocks)))
         return rc;
     R1_HIP(hipEventRecord(e[1], st));

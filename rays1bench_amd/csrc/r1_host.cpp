@@ -294,7 +294,8 @@ static int tiles_required(int tile, int size) // rayweek1.cpp:61-68
     return n;
 }
 
-extern "C" int r1_params_check(const r1_params *p)
+// every check of r1_params_check but the frame's sample total (r1_region_check: a frame rendered window by window need not fit one launch)
+static int params_fields_check(const r1_params *p)
 {
     if (!p || p->width <= 0 || p->height <= 0 || p->spp <= 0 || p->tile_w <= 0 || p->tile_h <= 0 || p->num_shards < 1 ||
         p->shard < 0 || p->shard >= p->num_shards || p->max_bounces < 1 || p->max_bounces > R1_MAX_BOUNCES_LIMIT ||
@@ -305,9 +306,73 @@ extern "C" int r1_params_check(const r1_params *p)
                      p ? p->max_bounces : 0, p ? p->variant : 0);
         return R1_EINVAL;
     }
-    if ((int64_t)p->width * p->height * p->spp >= (int64_t)1 << 31 || p->width > 65535 || p->height > 65535)
+    if (p->width > 65535 || p->height > 65535)
     {
         r1_set_error("image %dx%dx%d exceeds 2^31 samples", p->width, p->height, p->spp);
+        return R1_ELIMIT;
+    }
+    return R1_OK;
+}
+
+extern "C" int r1_params_check(const r1_params *p)
+{
+    int rc = params_fields_check(p);
+    if (rc)
+        return rc;
+    if ((int64_t)p->width * p->height * p->spp >= (int64_t)1 << 31)
+    {
+        r1_set_error("image %dx%dx%d exceeds 2^31 samples", p->width, p->height, p->spp);
+        return R1_ELIMIT;
+    }
+    return R1_OK;
+}
+
+// Region renders (include/rays1.h): the one place a region's rules are checked.  Pure arithmetic.
+extern "C" int r1_region_check(const r1_params *p, const r1_region *r)
+{
+    if (!p || !r)
+    {
+        r1_set_error("r1_region_check: %s is NULL", !p ? "params" : "region");
+        return R1_EINVAL;
+    }
+    int rc = params_fields_check(p);
+    if (rc)
+        return rc;
+    if (p->num_shards != 1)
+    {
+        r1_set_error("region renders are not combined with whole-frame sharding (num_shards == 1, not %d)", p->num_shards);
+        return R1_EINVAL;
+    }
+    if (p->variant == R1_VARIANT_STATS || p->variant == R1_VARIANT_BVH_STATS || p->variant == R1_VARIANT_GRID_STATS || p->variant == R1_VARIANT_WAVEFRONT)
+    {
+        r1_set_error("region renders: variant %d (a diagnostic build or the wavefront variant) has no region build", p->variant);
+        return R1_EINVAL;
+    }
+    if ((int64_t)p->width * p->height >= (int64_t)1 << 31)
+    {
+        r1_set_error("region renders: a frame of %dx%d pixels exceeds 2^31 (the pixel index of the seeds is an int)", p->width, p->height);
+        return R1_ELIMIT;
+    }
+    const char *bad = r->x0 < 0                                      ? "x0 is negative"
+                      : r->y0 < 0                                    ? "y0 is negative"
+                      : r->width < 1                                 ? "width is not >= 1"
+                      : r->height < 1                                ? "height is not >= 1"
+                      : (int64_t)r->x0 + r->width > p->width         ? "x0 + width exceeds the frame's width"
+                      : (int64_t)r->y0 + r->height > p->height       ? "y0 + height exceeds the frame's height"
+                      : r->out_stride != 0 && r->out_stride < r->width ? "out_stride is neither 0 nor >= width"
+                                                                     : nullptr;
+    if (bad)
+    {
+        r1_set_error("r1_region: %s (region %d,%d %dx%d stride %d in a frame of %dx%d)", bad, r->x0, r->y0, r->width, r->height, r->out_stride, p->width, p->height);
+        return R1_EINVAL;
+    }
+    // what bounds a frame of the region's size: its samples, and the padded sample slots of its tiles (r1_frame.cpp prepare_tiles)
+    const int64_t tiles = (int64_t)tiles_required(p->tile_w, r->width) * tiles_required(p->tile_h, r->height);
+    // (128 bits: tile_w * tile_h * spp * tiles of int32 fields does not fit 64)
+    const unsigned __int128 slots = (unsigned __int128)((uint64_t)p->tile_w * (uint64_t)p->tile_h) * (uint64_t)p->spp * (uint64_t)tiles;
+    if ((int64_t)r->width * r->height * p->spp >= (int64_t)1 << 31 || slots >= ((unsigned __int128)1 << 31))
+    {
+        r1_set_error("a region of %dx%dx%d with %dx%d tiles exceeds 2^31 samples or sample slots per launch", r->width, r->height, p->spp, p->tile_w, p->tile_h);
         return R1_ELIMIT;
     }
     return R1_OK;

@@ -45,8 +45,10 @@ int r1_grid_plan_describe(const r1_scene *built, double *doubles4, int32_t *flat
 int r1_params_check(const r1_params *p);
 
 // r1_trace_<family>.hip (r1_trace_tu.inc): the family's builds, by walking its list; hipErrorInvalidValue: not one of them
+// (_launch_region: the region twin of a R1_MODE_PASS build, r1_region_kernel)
 #define R1_TU_DECL(NAME)                                                                                                       \
     hipError_t r1_tu_##NAME##_launch(const R1TraceArgs *args, R1Build b, int blocks, size_t dyn_lds, hipStream_t stream);     \
+    hipError_t r1_tu_##NAME##_launch_region(const R1TraceArgs *args, R1Build b, int blocks, size_t dyn_lds, hipStream_t stream); \
     hipError_t r1_tu_##NAME##_occupancy(R1Build b, size_t dyn_lds, int *blocks_per_cu);
 R1_TU_DECL(tree_small)
 R1_TU_DECL(tree_big)
@@ -59,7 +61,7 @@ R1_TU_DECL(grid_big)
 hipError_t r1_tu_tree_small_launch_flat(const R1TraceArgs *args, R1Build b, int blocks, size_t dyn_lds, hipStream_t stream);
 
 // r1_aux_kernels.hip: the trace launch and occupancy dispatch, the wavefront variant, the put kernels
-hipError_t r1_launch_trace(const R1TraceArgs *args, R1Build b, int blocks, size_t grid_lds, hipStream_t stream, int *walk_form);
+hipError_t r1_launch_trace(const R1TraceArgs *args, R1Build b, int blocks, size_t grid_lds, hipStream_t stream, int *walk_form, int region);
 hipError_t r1_trace_occupancy(R1Build b, size_t dyn_lds, int *blocks_per_cu);
 hipError_t r1_launch_wavefront(R1WaveArgs *w, int blocks, hipStream_t stream);
 hipError_t r1_launch_put6(void *dst, const uint32_t *words, hipStream_t stream);
@@ -71,6 +73,7 @@ hipError_t r1_launch_resolve(const R1ResolveArgs *args, int max_rows, hipStream_
 hipError_t r1_launch_accum(const R1AccumArgs *args, hipStream_t stream);
 hipError_t r1_launch_adapt_accum(const R1AdaptArgs *args, hipStream_t stream);
 hipError_t r1_launch_resolve_linear(const R1LinearArgs *args, int max_rows, hipStream_t stream); // linear frames
+hipError_t r1_launch_resolve_region(const R1RegionArgs *args, hipStream_t stream); // region renders
 hipError_t r1_launch_accum_linear(const R1ReadoutArgs *args, hipStream_t stream);
 hipError_t r1_launch_adapt_compact(const uint32_t *cur, uint32_t n_cur, const R1TileReport *report, uint32_t at_cap, uint32_t *next, uint32_t *count_out,
                                    hipStream_t stream);

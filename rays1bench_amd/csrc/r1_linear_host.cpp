@@ -12,7 +12,52 @@
 
 #include <vector>
 
-// rayweek1.cpp:757-765 for every pixel: S = 0.0f; S += color(sample s) for s = 0 .. spp - 1; L = S * (float)(1.0f / spp)
+// rayweek1.cpp:757-765 for every pixel of window `win` of the frame: S = 0.0f; S += color(sample s) for s = 0 .. spp - 1; L = S * (float)(1.0f / spp),
+// stored at rgb_out + (y * stride + x) * 3 for pixel (x, y) of the window.  The whole frame is the window (0, 0, width, height) with stride width.
+static int render_window_host(const r1_scene *scene, const r1_camera *camera, const r1_params *p, const r1_region &win, float *rgb_out, uint64_t *num_rays_out)
+{
+    int rc;
+    // a few rows of pixels at a time: the rays, seeds and records of their samples (64 bytes a sample) stay small for any frame
+    const size_t spp = (size_t)p->spp, n_pixels = (size_t)win.width * win.height;
+    const size_t stride = win.out_stride ? (size_t)win.out_stride : (size_t)win.width;
+    const size_t chunk = (((size_t)1 << 16) + spp - 1) / spp; // pixels
+    std::vector<int32_t> x, y, s;
+    std::vector<r1_ray> rays;
+    std::vector<r1_sample_seed> seeds;
+    std::vector<r1_radiance> rec;
+    const float inv = (float)(1.0f / p->spp); // rayweek1.cpp:765
+    uint64_t total = 0;
+    for (size_t p0 = 0; p0 < n_pixels; p0 += chunk)
+    {
+        const size_t np = n_pixels - p0 < chunk ? n_pixels - p0 : chunk, n = np * spp;
+        x.resize(n), y.resize(n), s.resize(n), rays.resize(n), seeds.resize(n), rec.resize(n);
+        for (size_t i = 0; i < np; ++i)
+            for (size_t k = 0; k < spp; ++k)
+            {
+                x[i * spp + k] = win.x0 + (int32_t)((p0 + i) % (size_t)win.width), y[i * spp + k] = win.y0 + (int32_t)((p0 + i) / (size_t)win.width);
+                s[i * spp + k] = (int32_t)k;
+            }
+        if ((rc = r1_camera_rays(camera, p, x.data(), y.data(), s.data(), n, rays.data(), seeds.data())) ||
+            (rc = r1_trace_rays_host(scene, p->max_bounces, rays.data(), seeds.data(), n, rec.data())))
+            return rc;
+        for (size_t i = 0; i < np; ++i)
+        {
+            float cr = 0.0f, cg = 0.0f, cb = 0.0f;
+            for (size_t k = 0; k < spp; ++k)
+            {
+                const r1_radiance &v = rec[i * spp + k];
+                cr += v.r, cg += v.g, cb += v.b; // col += color(...) rayweek1.cpp:762
+                total += v.rays;
+            }
+            float *const o = rgb_out + ((p0 + i) / (size_t)win.width * stride + (p0 + i) % (size_t)win.width) * 3;
+            o[0] = cr * inv, o[1] = cg * inv, o[2] = cb * inv;
+        }
+    }
+    if (num_rays_out)
+        *num_rays_out = total;
+    return R1_OK;
+}
+
 extern "C" int r1_render_linear_host(const r1_scene *scene, const r1_camera *camera, const r1_params *p, float *rgb_out, uint64_t *num_rays_out)
 {
     if (!scene || !camera || !p || !rgb_out)
@@ -28,44 +73,24 @@ extern "C" int r1_render_linear_host(const r1_scene *scene, const r1_camera *cam
         r1_set_error("r1_render_linear_host renders whole frames (num_shards == 1, not %d)", p->num_shards);
         return R1_EINVAL;
     }
-    // a few rows of pixels at a time: the rays, seeds and records of their samples (64 bytes a sample) stay small for any frame
-    const size_t spp = (size_t)p->spp, n_pixels = (size_t)p->width * p->height;
-    const size_t chunk = (((size_t)1 << 16) + spp - 1) / spp; // pixels
-    std::vector<int32_t> x, y, s;
-    std::vector<r1_ray> rays;
-    std::vector<r1_sample_seed> seeds;
-    std::vector<r1_radiance> rec;
-    const float inv = (float)(1.0f / p->spp); // rayweek1.cpp:765
-    uint64_t total = 0;
-    for (size_t p0 = 0; p0 < n_pixels; p0 += chunk)
+    const r1_region whole = {0, 0, p->width, p->height, 0};
+    return render_window_host(scene, camera, p, whole, rgb_out, num_rays_out);
+}
+
+// The CPU form of r1_render_region_linear: the window's pixels of the FRAME — r1_camera_rays seeds and aims with params' width
+// and height — summed as above, rows out_stride pixels apart.
+extern "C" int r1_render_region_host(const r1_scene *scene, const r1_camera *camera, const r1_params *p, const r1_region *region, float *linear_out,
+                                     uint64_t *num_rays_out)
+{
+    if (!scene || !camera || !p || !region || !linear_out)
     {
-        const size_t np = n_pixels - p0 < chunk ? n_pixels - p0 : chunk, n = np * spp;
-        x.resize(n), y.resize(n), s.resize(n), rays.resize(n), seeds.resize(n), rec.resize(n);
-        for (size_t i = 0; i < np; ++i)
-            for (size_t k = 0; k < spp; ++k)
-            {
-                x[i * spp + k] = (int32_t)((p0 + i) % (size_t)p->width), y[i * spp + k] = (int32_t)((p0 + i) / (size_t)p->width);
-                s[i * spp + k] = (int32_t)k;
-            }
-        if ((rc = r1_camera_rays(camera, p, x.data(), y.data(), s.data(), n, rays.data(), seeds.data())) ||
-            (rc = r1_trace_rays_host(scene, p->max_bounces, rays.data(), seeds.data(), n, rec.data())))
-            return rc;
-        for (size_t i = 0; i < np; ++i)
-        {
-            float cr = 0.0f, cg = 0.0f, cb = 0.0f;
-            for (size_t k = 0; k < spp; ++k)
-            {
-                const r1_radiance &v = rec[i * spp + k];
-                cr += v.r, cg += v.g, cb += v.b; // col += color(...) rayweek1.cpp:762
-                total += v.rays;
-            }
-            float *const o = rgb_out + (p0 + i) * 3;
-            o[0] = cr * inv, o[1] = cg * inv, o[2] = cb * inv;
-        }
+        r1_set_error("r1_render_region_host: null argument");
+        return R1_EINVAL;
     }
-    if (num_rays_out)
-        *num_rays_out = total;
-    return R1_OK;
+    int rc = r1_region_check(p, region);
+    if (rc)
+        return rc;
+    return render_window_host(scene, camera, p, *region, linear_out, num_rays_out);
 }
 
 // rayweek1.cpp:766-775 for one channel: (uint8)(int)(sqrtf(v) * 255.99f).  Refused before a byte is written: a value whose (int) is

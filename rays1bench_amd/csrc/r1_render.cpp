@@ -42,6 +42,37 @@ static int read_rays(r1_context *c, bool direct, uint64_t *rays)
     return R1_OK;
 }
 
+// The records the last launch left (whole frames, num_shards == 1: local tile = tile of g's frame), brought home in the ABI's order: device order
+// is [padded tile][sample][pixel in tile], the ABI's ((y * width + x) * spp + s) over g's frame — the params' frame, or a region's own.
+// Waits for the context's stream.
+static int gather_records(r1_context *c, const R1TileGeom &g, const int32_t spp, float *samples_out)
+{
+    std::vector<float> tmp((size_t)c->total_samples * 4);
+    R1_HIP(hipMemcpyAsync(tmp.data(), c->samples.p, tmp.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    R1_HIP(hipStreamSynchronize(c->stream));
+    for (uint32_t lt = 0; lt < c->n_local_tiles; ++lt)
+    {
+        const R1TileRect r = r1_tile_rect(g, lt);
+        const float *src = tmp.data() + (size_t)lt * c->full * 4;
+        const size_t tile_px = r1_tile_slots(g);
+        for (int ly = 0; ly < r.th; ++ly)
+            for (int lx = 0; lx < r.tw; ++lx)
+                for (int sm = 0; sm < spp; ++sm)
+                {
+                    float *dst = samples_out + (r1_pixel_row_major(g, r, lx, ly) * spp + sm) * 4;
+                    memcpy(dst, src + ((size_t)sm * tile_px + (size_t)(ly * g.tile_w + lx)) * 4, 16);
+                    if (c->land_prev) // the launch tagged its records' ray-count words (R1_LAND): the ABI's word is the count alone
+                    {
+                        uint32_t wv;
+                        memcpy(&wv, dst + 3, 4);
+                        wv &= 255u;
+                        memcpy(dst + 3, &wv, 4);
+                    }
+                }
+    }
+    return R1_OK;
+}
+
 static int render_host(r1_context *c, const r1_params *p, uint8_t *rgb_out, uint64_t *num_rays_out, double *device_seconds_out,
                        float *samples_out)
 {
@@ -109,33 +140,7 @@ static int render_host(r1_context *c, const r1_params *p, uint8_t *rgb_out, uint
         *device_seconds_out = ms * 1e-3;
     }
     if (samples_out)
-    {
-        // device order is [padded tile][sample][pixel in tile]; the ABI order is
-        // ((y*width + x)*spp + s)
-        std::vector<float> tmp((size_t)c->total_samples * 4);
-        R1_HIP(hipMemcpyAsync(tmp.data(), c->samples.p, tmp.size() * 4, hipMemcpyDeviceToHost, c->stream));
-        R1_HIP(hipStreamSynchronize(c->stream));
-        for (uint32_t lt = 0; lt < c->n_local_tiles; ++lt)
-        {
-            const R1TileRect r = r1_tile_rect(g, lt); // (num_shards == 1: local tile = tile of the frame)
-            const float *src = tmp.data() + (size_t)lt * c->full * 4;
-            const size_t tile_px = r1_tile_slots(g);
-            for (int ly = 0; ly < r.th; ++ly)
-                for (int lx = 0; lx < r.tw; ++lx)
-                    for (int sm = 0; sm < p->spp; ++sm)
-                    {
-                        float *dst = samples_out + (r1_pixel_row_major(g, r, lx, ly) * p->spp + sm) * 4;
-                        memcpy(dst, src + ((size_t)sm * tile_px + (size_t)(ly * p->tile_w + lx)) * 4, 16);
-                        if (c->land_prev) // the launch tagged its records' ray-count words (R1_LAND): the ABI's word is the count alone
-                        {
-                            uint32_t wv;
-                            memcpy(&wv, dst + 3, 4);
-                            wv &= 255u;
-                            memcpy(dst + 3, &wv, 4);
-                        }
-                    }
-        }
-    }
+        return gather_records(c, g, p->spp, samples_out);
     return R1_OK;
 }
 
@@ -608,6 +613,113 @@ extern "C" int r1_render_adaptive_linear(r1_context *c, const r1_params *p, cons
                                          r1_tile_report *tiles_out, r1_adaptive_result *result_out)
 {
     return render_adaptive("r1_render_adaptive_linear", c, p, opt, nullptr, rgb_out, num_rays_out, tiles_out, result_out);
+}
+
+// ---- region renders -----------------------------------------------------------------
+// A window of the frame: a pass with a region (r1_context.h Pass), so the launch path is enqueue_frame's and the state rules — moved scenes, the
+// grid's validity, the landing state, a progressive accumulation left alone — are those of every frame.  The launch works on a dense image of
+// the region's size in the context's buffers; the caller's row stride is applied by the copies home (host forms) or by the closing kernel
+// itself (device form).
+
+// the synchronous forms: bytes (rgb_out), floats (linear_out), records (samples_out)
+static int render_region_host_out(const char *who, r1_context *c, const r1_params *p, const r1_region *rg, uint8_t *rgb_out, float *linear_out,
+                                  uint64_t *num_rays_out, double *device_seconds_out, float *samples_out)
+{
+    if (!c || !p || !rg || (!rgb_out && !linear_out))
+    {
+        r1_set_error("%s: null argument", who);
+        return R1_EINVAL;
+    }
+    int rc = r1_region_check(p, rg);
+    if (rc)
+        return rc;
+    if (!c->have_scene)
+    {
+        r1_set_error("no scene set (call r1_set_scene first)");
+        return R1_EINVAL;
+    }
+    R1_HIP(hipSetDevice(c->device));
+    const size_t n_px = (size_t)rg->width * rg->height;
+    if ((rgb_out && (rc = ensure(c->image, n_px * 3 + 64))) || (linear_out && (rc = ensure(c->linear, n_px * 3 * sizeof(float)))))
+        return rc;
+    const bool direct = c->host_word_dev != nullptr; // the ray count straight into the page-locked word, as r1_render_pass
+    r1_region dense = *rg;
+    dense.out_stride = 0; // (the context's buffers hold the window densely)
+    Pass ps;
+    ps.region = &dense;
+    ps.region_linear = linear_out ? (float *)c->linear.p : nullptr;
+    FrameJob job;
+    job.out = rgb_out ? c->image.p : nullptr, job.rays = rays_word(c, direct), job.st = c->stream, job.pass = &ps;
+    if ((rc = enqueue_frame(c, p, job)))
+        return rc;
+    const size_t stride = rg->out_stride ? (size_t)rg->out_stride : (size_t)rg->width;
+    if (rgb_out)
+        R1_HIP(hipMemcpy2DAsync(rgb_out, stride * 3, c->image.p, (size_t)rg->width * 3, (size_t)rg->width * 3, (size_t)rg->height, hipMemcpyDeviceToHost, c->stream));
+    if (linear_out)
+        R1_HIP(hipMemcpy2DAsync(linear_out, stride * 12, c->linear.p, (size_t)rg->width * 12, (size_t)rg->width * 12, (size_t)rg->height, hipMemcpyDeviceToHost, c->stream));
+    uint64_t rays = 0;
+    if ((rc = read_rays(c, direct, &rays)) || (rc = land_check(c)))
+        return rc;
+    if (num_rays_out)
+        *num_rays_out = rays;
+    if (device_seconds_out)
+    {
+        float ms = 0;
+        R1_HIP(hipEventElapsedTime(&ms, c->last0, c->last2));
+        *device_seconds_out = ms * 1e-3;
+    }
+    if (samples_out) // dense in the region's own geometry: the gather of r1_render_samples
+        return gather_records(c, r1_tile_geom(rg->width, rg->height, p->tile_w, p->tile_h), p->spp, samples_out);
+    return R1_OK;
+}
+
+extern "C" int r1_render_region(r1_context *c, const r1_params *p, const r1_region *region, uint8_t *rgb_out, uint64_t *num_rays_out, double *device_seconds_out)
+{
+    return render_region_host_out("r1_render_region", c, p, region, rgb_out, nullptr, num_rays_out, device_seconds_out, nullptr);
+}
+
+extern "C" int r1_render_region_samples(r1_context *c, const r1_params *p, const r1_region *region, uint8_t *rgb_out, uint64_t *num_rays_out, float *samples_out)
+{
+    if (!samples_out)
+    {
+        r1_set_error("r1_render_region_samples: null samples_out");
+        return R1_EINVAL;
+    }
+    return render_region_host_out("r1_render_region_samples", c, p, region, rgb_out, nullptr, num_rays_out, nullptr, samples_out);
+}
+
+extern "C" int r1_render_region_linear(r1_context *c, const r1_params *p, const r1_region *region, float *rgb_out, uint64_t *num_rays_out, double *device_seconds_out)
+{
+    return render_region_host_out("r1_render_region_linear", c, p, region, nullptr, rgb_out, num_rays_out, device_seconds_out, nullptr);
+}
+
+extern "C" int r1_render_region_device(r1_context *c, const r1_params *p, const r1_region *region, void *d_rgb_u8, void *d_rgb_f32, void *d_num_rays, void *hip_stream)
+{
+    if (!c || !p || !region || (!d_rgb_u8 && !d_rgb_f32) || !d_num_rays)
+    {
+        r1_set_error("r1_render_region_device: null argument (an image — d_rgb_u8, d_rgb_f32 or both — and d_num_rays are needed)");
+        return R1_EINVAL;
+    }
+    if (((uintptr_t)d_rgb_f32 & 3u) || ((uintptr_t)d_num_rays & 7u))
+    {
+        r1_set_error("r1_render_region_device: d_rgb_f32 must be 4-byte aligned and d_num_rays 8-byte aligned");
+        return R1_EINVAL;
+    }
+    int rc = r1_region_check(p, region);
+    if (rc)
+        return rc;
+    if (!c->have_scene)
+    {
+        r1_set_error("no scene set (call r1_set_scene first)");
+        return R1_EINVAL;
+    }
+    R1_HIP(hipSetDevice(c->device));
+    Pass ps;
+    ps.region = region; // (the closing kernel applies the caller's row stride)
+    ps.region_linear = (float *)d_rgb_f32;
+    FrameJob job;
+    job.out = d_rgb_u8, job.rays = d_num_rays, job.st = hip_stream ? (hipStream_t)hip_stream : c->stream, job.pass = &ps;
+    return enqueue_frame(c, p, job);
 }
 
 // Pipelined form of r1_render (frames in flight, results on the HOST): the frame is enqueued with the throughput

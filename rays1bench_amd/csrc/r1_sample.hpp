@@ -38,10 +38,11 @@ __device__ __forceinline__ uint32_t fastdiv(uint32_t n, const R1FastDiv dv)
 // seeds + primary ray of sample s of pixel (x, y) (rayweek1.cpp:759-760) up to the Ray constructor: the origin in p.o, the stream states
 // after the camera's draws in p, and the direction as getRay hands it to the constructor — UN-normalised — returned.  start_ray, and
 // r1_camera_rays_kernel (r1_aux_kernels.hip), which stores exactly this.
-__device__ __forceinline__ V3 camera_ray(const int width, const float inv_w, const float inv_h, const R1DeviceCamera &C, Path &p, const int x, const int y,
-                                         const uint32_t s, const uint32_t seed)
+// camera_ray_at: the same for a caller that has the pixel's index in the frame, `pixel` = y * width + x (a region's lanes, start_sample)
+__device__ __forceinline__ V3 camera_ray_at(const uint32_t pixel, const float inv_w, const float inv_h, const R1DeviceCamera &C, Path &p, const int x, const int y,
+                                            const uint32_t s, const uint32_t seed)
 {
-    const r1_sample_seed sd = r1_seed_sample(seed, (uint32_t)(y * width + x), s);
+    const r1_sample_seed sd = r1_seed_sample(seed, pixel, s);
     p.s_scalar = sd.scalar;
     p.s0 = sd.lane0;
     p.s1 = sd.lane1;
@@ -70,6 +71,11 @@ __device__ __forceinline__ V3 camera_ray(const int width, const float inv_w, con
     const V3 org = ld3(C.origin);
     p.o = vadd(org, offset);
     return vsub(vsub(vadd(vadd(ld3(C.lower_left), vscale(ld3(C.horizontal), u)), vscale(ld3(C.vertical), v)), org), offset);
+}
+__device__ __forceinline__ V3 camera_ray(const int width, const float inv_w, const float inv_h, const R1DeviceCamera &C, Path &p, const int x, const int y,
+                                         const uint32_t s, const uint32_t seed)
+{
+    return camera_ray_at((uint32_t)(y * width + x), inv_w, inv_h, C, p, x, y, s, seed);
 }
 
 // the same with the constructor's normalisation: the primary ray in p
@@ -104,11 +110,17 @@ __device__ __forceinline__ bool tile_pixel(const R1TraceArgs &A, const uint32_t 
 // start_ray out of the loop, i.e. emits these very loads behind a loop that only builds the address.
 // LIST (adaptive sampling, R1_MODE_LISTED): a PASS whose local tile j is tile list[j] of the frame (R1PassArgs::list); the record keeps the list
 // position.  j is a per-lane value (a wave's chunk may straddle tiles), so every lane loads its own entry, as a camera path's lanes do.
-template <bool BATCH = false, bool PASS = false, bool PATH = false, bool LIST = false>
+// REGION (region renders, r1_region_kernel): a PASS whose arguments describe a frame of the REGION's size, cut into tiles from
+// the region's own corner — the bound test, the record's place and everything behind them see that frame — and whose lanes, once the bound
+// test is over, move the pixel by the region's corner (x0, y0) and seed and aim the sample with the WHOLE frame's width, 1/W and 1/H: A.inv_w
+// and A.inv_h are the frame's, and x0, y0 and the frame's width are the three words of R1PassArgs behind first_sample (which is 0), read by
+// scalar loads where that one is.  The pixel's index in the frame is a uint32 (width * height < 2^31, r1_region_check).
+template <bool BATCH = false, bool PASS = false, bool PATH = false, bool LIST = false, bool REGION = false>
 __device__ __forceinline__ bool start_sample(const R1TraceArgs &A, Path &p, uint32_t k)
 {
     static_assert(!PATH || BATCH, "a camera path is a batch");
     static_assert(!LIST || (PASS && !BATCH), "a listed pass is a pass");
+    static_assert(!REGION || (PASS && !BATCH && !LIST), "a region is a pass over tiles of its own");
     const uint32_t j = fastdiv(k, A.div_full); // padded tile, frame-major over the frames of the launch
     const uint32_t r = k - j * A.full;
     const uint32_t pix = fastdiv(r, A.div_spp);
@@ -155,6 +167,15 @@ __device__ __forceinline__ bool start_sample(const R1TraceArgs &A, Path &p, uint
         const f3 c4 = *(gf3_ptr)(t + 4); // (the row's 20th word is padding: a loaded register nobody reads is the first one hipcc reuses, and it waits for all five loads to do so)
         const R1DeviceCamera C = {{c0.x, c0.y, c0.z}, {c0.w, c1.x, c1.y}, {c1.z, c1.w, c2.x}, {c2.y, c2.z, c2.w}, {c3.x, c3.y, c3.z}, {c3.w, c4.x, c4.y}, c4.z};
         start_ray(A, C, p, x, y, s_global, seed);
+        return true;
+    }
+    if (REGION)
+    {
+        typedef const uint32_t __attribute__((address_space(4))) *cu32_ptr;
+        const cu32_ptr b = (cu32_ptr)A.batch;
+        static_assert(__builtin_offsetof(R1PassArgs, x0) == 4 && __builtin_offsetof(R1PassArgs, y0) == 16 && __builtin_offsetof(R1PassArgs, frame_w) == 20, "the words read here");
+        const uint32_t fx = (uint32_t)x + b[1], fy = (uint32_t)y + b[4]; // the pixel in the frame
+        p.d = vunit(camera_ray_at(fy * b[5] + fx, A.inv_w, A.inv_h, A.cam, p, (int)fx, (int)fy, s_global, seed));
         return true;
     }
     start_ray(A, A.cam, p, x, y, s_global, seed);

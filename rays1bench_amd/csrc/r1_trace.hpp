@@ -1,5 +1,5 @@
 // r1_trace.hpp — hand-written HIP for gfx950 (MI355X, wave64): the per-pixel/per-sample path-tracing hot path of rays1bench step13.
-// This file: the persistent trace kernel (TraceWaves, r1_trace_body and its five __global__ templates).  The device functions it is made
+// This file: the persistent trace kernel (TraceWaves, r1_trace_body and its __global__ templates).  The device functions it is made
 // of live in headers by subject, each of which compiles alone (tests/test_device_headers_host.py) and has internal linkage:
 //   r1_dev_math.hpp   address-space typedefs, V3 and its operations, the xorshift32 streams, Path
 //   r1_kargs.hpp      fresh_args / R1_FRESH_ARGS: the kernel's arguments read again where they are used
@@ -102,9 +102,11 @@ struct TraceWaves
 // (the body of the kernel; r1_trace_kernel and, for the uniform grid, r1_grid_kernel below are its __global__ instances; r1_pass_kernel,
 // r1_path_kernel and r1_adaptive_kernel those of R1_MODE_PASS, _PATH and _LISTED)
 // FLAT: what the walk knows of the tree's flat axis before it looks (r1_hit_tree.hpp bvh_advance; R1_FLAT_ASK: nothing, every kernel r1_pick reaches)
-template <int VARIANT, bool STATS, bool BIG, int MODE, int FLAT = R1_FLAT_ASK>
+// REGION: a pass over a window of the frame (r1_sample.hpp start_sample, the one place that reads it; r1_region_kernel below)
+template <int VARIANT, bool STATS, bool BIG, int MODE, int FLAT = R1_FLAT_ASK, bool REGION = false>
 __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
 {
+    static_assert(!REGION || MODE == R1_MODE_PASS, "a region is traced as a pass");
     constexpr bool LISTED = MODE == R1_MODE_LISTED, PASS = r1_mode_is_pass(MODE);
     constexpr bool CPATH = MODE == R1_MODE_PATH, BATCH = r1_mode_is_batch(MODE); // (a path's frames each have a camera of their own, start_sample)
     constexpr bool LAT = r1_runs_as_latency(MODE, BIG), PIX = MODE == R1_MODE_PIXEL;
@@ -403,7 +405,7 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
             if (SPARE)
             {
                 if (!has_spare && rank < avail)
-                    has_spare = start_sample<BATCH, PASS, CPATH, LISTED>(FA, spare, q_next + rank); // false: void slot, ask again
+                    has_spare = start_sample<BATCH, PASS, CPATH, LISTED, REGION>(FA, spare, q_next + rank); // false: void slot, ask again
             }
             else if (!alive && rank < avail)
             {
@@ -414,7 +416,7 @@ __device__ __forceinline__ void r1_trace_body(const R1TraceArgs A)
                         start_ray(A, A.cam, p, (int)(px.xy & 0xFFFFu), (int)(px.xy >> 16), 0u, A.seed);
                 }
                 else
-                    alive = start_sample<BATCH, PASS, CPATH, LISTED>(FA, p, q_next + rank); // false: void slot, ask again
+                    alive = start_sample<BATCH, PASS, CPATH, LISTED, REGION>(FA, p, q_next + rank); // false: void slot, ask again
                 if (VARIANT == R1_V_TREE && alive)
                     trav_start(tv);
             }
@@ -676,6 +678,14 @@ template <int VARIANT, bool BIG>
 __global__ void __launch_bounds__(R1_BLOCK, (TraceWaves<VARIANT, false, BIG, R1_MODE_PASS>::value)) r1_pass_kernel(const R1TraceArgs A)
 {
     r1_trace_body<VARIANT, false, BIG, R1_MODE_PASS>(A);
+}
+
+// Region renders (r1_render_region*): the twin of every r1_pass_kernel, built for its sibling's waves.  No build of r1_pick's:
+// r1_launch_trace launches one in its sibling's place when the pass carries a region.
+template <int VARIANT, bool BIG>
+__global__ void __launch_bounds__(R1_BLOCK, (TraceWaves<VARIANT, false, BIG, R1_MODE_PASS>::value)) r1_region_kernel(const R1TraceArgs A)
+{
+    r1_trace_body<VARIANT, false, BIG, R1_MODE_PASS, R1_FLAT_ASK, true>(A);
 }
 
 // Adaptive sampling (R1_MODE_LISTED): the same body under a name of its own, for the tree, the grouped sweep and the grid; built for the

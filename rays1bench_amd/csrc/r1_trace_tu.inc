@@ -37,6 +37,30 @@ extern "C" hipError_t R1_CAT(r1_tu_, R1_TU_NAME, _launch)(const R1TraceArgs *arg
     return hipErrorInvalidValue;
 }
 
+// The region twin of build b (r1_trace.hpp r1_region_kernel; DESIGN.md §4.37): every R1_MODE_PASS build of the family has one, which takes the
+// arguments, the grid and the LDS of that build.  hipErrorInvalidValue: b has no twin.
+template <int V, bool S, bool BIG, int M>
+static hipError_t r1_region_launch(const R1TraceArgs *args, int blocks, size_t dyn_lds, hipStream_t stream)
+{
+    if constexpr (M == R1_MODE_PASS)
+    {
+        hipLaunchKernelGGL((r1_region_kernel<V, BIG>), dim3(blocks), dim3(R1_BLOCK), dyn_lds, stream, *args);
+        return hipGetLastError();
+    }
+    else
+        return hipErrorInvalidValue;
+}
+
+extern "C" hipError_t R1_CAT(r1_tu_, R1_TU_NAME, _launch_region)(const R1TraceArgs *args, R1Build b, int blocks, size_t dyn_lds, hipStream_t stream)
+{
+#define R1_X(V, S, BIG, M)                                                                                                                 \
+    if (r1_same_build(b, V, S, BIG, M))                                                                                                    \
+        return r1_region_launch<V, S, BIG, M>(args, blocks, dyn_lds, stream);
+    R1_TU_BUILDS(R1_X)
+#undef R1_X
+    return hipErrorInvalidValue;
+}
+
 extern "C" hipError_t R1_CAT(r1_tu_, R1_TU_NAME, _occupancy)(R1Build b, size_t dyn_lds, int *blocks_per_cu)
 {
 #define R1_X(V, S, BIG, M)                                                                                                                 \

@@ -29,6 +29,9 @@
 // on the mean), --min-spp and --pass-spp to 16.
 // --linear renders each frame through r1_render_linear: the fp32 frame comes home, the pixels of the TGA are r1_quantise_linear's — the bytes
 // r1_render returns — and -w also writes out_<scene>.pfm; the report gains one "<scene> linear:" line.
+// --region X,Y,W,H renders each frame through r1_render_region: window (X, Y, W, H) of the --width x --height frame (row 0 = bottom row), the
+// crop of the whole frame byte for byte; the pixels, the TGA and the counts of the report and of out_<scene>.txt are the window's, and the report
+// gains one "<scene> region:" line.
 // --backend hip (default) | cpu-step1 | cpu-step12: the reference's two single-thread CPU stages
 // (r1_cpu_backends.cpp) behind the same benchmark(), for the README-style table
 // (README.md:38-84).  Named backends of this program only — never a fallback: with --backend hip and no
@@ -225,6 +228,8 @@ static Frame context_frame(const Scene *scene, Pix *pixels, const r1_params &p, 
             if (rc == R1_OK)
                 rc = r1_quantise_linear(g_linear, (size_t)q.width * q.height * 3, &pixels[0].r);
         }
+        else if (rc == R1_OK && g_opt.region) // --region (one device): the window's pixels, dense at the start of the buffer
+            rc = r1_render_region(g_ctx[i], &q, &g_opt.window, &pixels[0].r, &rays[i], &dev_s[i]);
         else if (rc == R1_OK)
             rc = r1_render(g_ctx[i], &q, &pixels[0].r, &rays[i], &dev_s[i]);
         rcs[i] = rc;
@@ -276,6 +281,11 @@ static Frame context_frame(const Scene *scene, Pix *pixels, const r1_params &p, 
         f.lines_after = line("%s linear: %dx%dx3 fp32 (%.2f MB), mean %.6f, max %.6f, bytes from r1_quantise_linear\n", scene_name, g_opt.width, g_opt.height,
                              (double)n * 4 / 1e6, sum / (double)n, (double)top);
     }
+    if (g_opt.region)
+        f.lines_after = line("%s region: %d,%d %dx%d of %dx%d (%.4f of the frame's pixels), samples %llu, rays %llu\n", scene_name, g_opt.window.x0, g_opt.window.y0,
+                             g_opt.window.width, g_opt.window.height, g_opt.width, g_opt.height,
+                             (double)g_opt.window.width * g_opt.window.height / ((double)g_opt.width * g_opt.height),
+                             (unsigned long long)((uint64_t)g_opt.window.width * g_opt.window.height * g_opt.spp), (unsigned long long)f.rays);
     return f;
 }
 
@@ -300,7 +310,9 @@ RESULT benchmark(Scene *scene, Pix *pixels, bool write_tga, const char *scene_na
 
     printf("%s\n", scene_name);
     printf("elapsed time:   %.3fs\n", result.elapsed_seconds);
-    printf("total samples:  %llu\n", (unsigned long long)((uint64_t)g_opt.width * g_opt.height * g_opt.spp));
+    // (the image benchmark() hands back: the frame, or --region's window)
+    const int out_w = g_opt.region ? g_opt.window.width : g_opt.width, out_h = g_opt.region ? g_opt.window.height : g_opt.height;
+    printf("total samples:  %llu\n", (unsigned long long)((uint64_t)out_w * out_h * g_opt.spp));
     printf("total rays:     %llu\n", (unsigned long long)result.num_rays);
     printf("mrays/s:        %0.2f\n", result.get_mrays_per_sec());
     fputs(f.lines.c_str(), stdout);
@@ -315,7 +327,7 @@ RESULT benchmark(Scene *scene, Pix *pixels, bool write_tga, const char *scene_na
     {
         char filename[128];
         snprintf(filename, sizeof(filename), "out_%s.tga", scene_name);
-        r1_tga_write_rgb24(filename, g_opt.width, g_opt.height, &pixels[0].r); // swaps R/B in `pixels`, as the reference
+        r1_tga_write_rgb24(filename, out_w, out_h, &pixels[0].r); // swaps R/B in `pixels`, as the reference
         if (g_opt.linear)
         {
             snprintf(filename, sizeof(filename), "out_%s.pfm", scene_name);
@@ -374,7 +386,7 @@ int main(int argc, const char *argv[])
 {
     Options &o = g_opt;
     bool write_tga = false;
-    bool passes_given = false, orbit_given = false, bounce_given = false, pulse_given = false, adapt_fields_ok = true, adapt_sub_given = false;
+    bool passes_given = false, orbit_given = false, bounce_given = false, pulse_given = false, adapt_fields_ok = true, adapt_sub_given = false, region_fields_ok = true;
     int num_runs = 1;
     const static int MAX_NUMS = 32;
     RESULT results[MAX_NUMS];
@@ -406,7 +418,11 @@ int main(int argc, const char *argv[])
             continue;
         }
         if (i + 1 >= argc)
+        {
+            if (strcmp(argv[i], "--region") == 0) // (ignored, it would render the whole frame)
+                o.region = true, region_fields_ok = false;
             break; // every other option takes a value: as the last argument it is ignored
+        }
         const char *const value = argv[i + 1];
         const IntOption *row = nullptr;
         for (const IntOption &r : int_options)
@@ -442,6 +458,13 @@ int main(int argc, const char *argv[])
                 adapt_fields_ok = end != w;
             }
             adapt_fields_ok = adapt_fields_ok && *end == 0;
+        }
+        else if (strcmp(argv[i], "--region") == 0)
+        {
+            // X,Y,W,H
+            o.region = true;
+            int n_read = 0;
+            region_fields_ok = sscanf(value, "%d,%d,%d,%d%n", &o.window.x0, &o.window.y0, &o.window.width, &o.window.height, &n_read) == 4 && value[n_read] == 0;
         }
         else if (strcmp(argv[i], "--backend") == 0)
             o.backend = strcmp(value, "hip") == 0 ? 0 : (strcmp(value, "cpu-step1") == 0 ? 1 : (strcmp(value, "cpu-step12") == 0 ? 12 : -1));
@@ -498,6 +521,22 @@ int main(int argc, const char *argv[])
         return 1;
     }
 
+    if (o.region)
+    {
+        // what r1_render_region cannot serve is refused here, before a device is touched, as --linear's is; the window itself by r1_region_check
+        if (!region_fields_ok || !one_pass || o.adaptive || o.linear)
+        {
+            fprintf(stderr, "bad --region X,Y,W,H: needs four integers, the hip backend, one device (no --gather rccl), no --passes, no --adaptive and no --linear\n");
+            return 1;
+        }
+        const r1_params fp = frame_params();
+        if (r1_region_check(&fp, &o.window) != R1_OK)
+        {
+            fprintf(stderr, "bad --region %d,%d,%d,%d: %s\n", o.window.x0, o.window.y0, o.window.width, o.window.height, r1_last_error());
+            return 1;
+        }
+    }
+
     if ((o.pipeline > 0 || o.orbit > 0) && o.backend == 0)
     {
         // Frames in flight only overlap when their streams sit on different hardware queues; the ROCm default is 4.  One queue
@@ -542,15 +581,16 @@ int main(int argc, const char *argv[])
     // image, which page-locked memory only makes faster (any other memory works too).
     Pix *pixels = nullptr;
     bool pixels_pinned = false;
+    const size_t n_pixels = o.region ? (size_t)o.window.width * o.window.height : (size_t)o.width * o.height; // (--region: the window's, whatever the frame's size)
     if (o.backend == 0)
     {
         void *mem = nullptr;
-        if (r1_host_alloc((size_t)o.width * o.height * sizeof(Pix), &mem) == R1_OK)
+        if (r1_host_alloc(n_pixels * sizeof(Pix), &mem) == R1_OK)
             pixels = (Pix *)mem, pixels_pinned = true;
     }
     if (!pixels)
-        pixels = new Pix[(size_t)o.width * o.height];
-    memset(pixels, 0, (size_t)o.width * o.height * sizeof(pixels[0]));
+        pixels = new Pix[n_pixels];
+    memset(pixels, 0, n_pixels * sizeof(pixels[0]));
 
     bool linear_pinned = false;
     if (o.linear)
