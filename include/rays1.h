@@ -482,6 +482,50 @@ int r1_render_region_device(r1_context *ctx, const r1_params *params, const r1_r
 int r1_render_region_host(const r1_scene *scene, const r1_camera *camera, const r1_params *params, const r1_region *region, float *linear_out,
                           uint64_t *num_rays_out);
 
+/* ---- feature frames: first-hit albedo, normal and depth per pixel ---- */
+
+/* The guide images a denoiser, an upscaler or a compositor wants beside a noisy frame, aligned with it pixel for pixel.  For pixel (x, y)
+ * of the frame `params` describes (width, height, spp, seed) and the context's camera, the samples s = 0 .. spp - 1 in that order:
+ *   ray      what r1_camera_rays returns for (x, y, s) — the same draws, the pixel index y * width + x of the FRAME — normalised once, as the
+ *            Ray constructor does: the primary ray r1_render traces for that sample;
+ *   hit      Hitable::hit(ray, 0.001f, FLT_MAX): R1_CAST_CLOSEST's record;
+ *   a sample with a hit adds the sphere's albedo_r / _g / _b as the scene arrays hold them (a dielectric: 1, 1, 1, the weight of its
+ *            scatter) to albedo, the record's n to normal, its t to depth and 1 to hits;
+ *   a sample without one adds the sky's colour for its ray to albedo — u = 0.5f * (d.y + 1.0f), (1 - u) * 1.0f + u * {0.5f, 0.7f, 1.0f} — and
+ *            nothing else;
+ *   a sample whose origin or normalised direction is not finite adds nothing and is not tested.
+ * Each of the seven sums starts at 0.0f and takes plain fp32 adds in sample order; then one fp32 multiply by (float)(1.0f / spp) each —
+ * r1_render_linear's arithmetic.  Normals are not re-normalised; depth * spp / hits is the mean distance over the hits, hits / spp the
+ * coverage.  A pixel with hits == 0 has albedo equal to r1_render_linear's value of that pixel, bit for bit: every sample's radiance is the
+ * sky of its primary ray. */
+typedef struct r1_feature
+{
+    float albedo[3];
+    float depth;
+    float normal[3];
+    uint32_t hits; /* samples of the pixel with a hit, 0 .. spp */
+} r1_feature;
+
+/* A feature frame has r1_render's layout with records for pixels: row-major, row 0 = bottom row.  `region` is r1_region's window, out_stride
+ * (in pixels, here records) included — nothing between the rows is written, the window's records are the frame's — and NULL means the
+ * whole frame, {0, 0, width, height, 0}.  The rules are r1_region_check's, applied to that region (so num_shards != 1 is R1_EINVAL, and
+ * max_bounces and the tile fields are checked and otherwise unused).  params->variant follows the queries' rule: DEFAULT and BVH walk the
+ * box tree, GRID the uniform grid (built on first use; far origins take the tree), REFERENCE tests every sphere; any other variant is
+ * R1_EINVAL.  The call is a query: a progressive accumulation survives it, r1_last_launch_info and r1_last_timing keep describing the
+ * last render, after an update it sees the moved scene (GRID: R1_EINVAL, "the scene has moved", until r1_regrid), and the camera is the
+ * context's, as r1_set_scene or r1_set_camera left it.  Refusals, in this order: ctx NULL; params, region or variant; no scene yet; out
+ * NULL (device form: or not 16-byte aligned).  A refused call enqueues nothing.
+ * Synchronous; `out` is host memory; device_seconds_out may be NULL. */
+int r1_render_features(r1_context *ctx, const r1_params *params, const r1_region *region, r1_feature *out, double *device_seconds_out);
+
+/* The same into DEVICE memory (16-byte aligned): everything is enqueued on `hip_stream` (NULL = the context's stream), nothing is waited
+ * for.  No workspace but the launch's cursor: any number of these launches of a context may be in flight. */
+int r1_render_features_device(r1_context *ctx, const r1_params *params, const r1_region *region, void *d_out, void *hip_stream);
+
+/* The CPU form, no device: r1_camera_rays + r1_cast_rays_host per sample and the sums above.  Slow (every ray against every sphere); it
+ * is what the other two are checked against.  params->variant is checked as r1_region_check checks it and otherwise unused. */
+int r1_render_features_host(const r1_scene *scene, const r1_camera *camera, const r1_params *params, const r1_region *region, r1_feature *out);
+
 /* Pipelined form of r1_render — frames in flight whose results land on the HOST.  The reference times
  * dispatch -> pixels + ray count on the host (rayweek1.cpp:848 -> :891) for ONE frame and waits; a caller that
  * renders frame after frame (main's `-n` runs, rayweek1.cpp:969-984) can keep several in flight instead: the call

@@ -121,6 +121,8 @@ SCATTER_DTYPE = np.dtype([("weight", np.float32, 3), ("event", np.int32), ("t", 
 SCATTER_SCATTERED, SCATTER_SKY, SCATTER_ABSORBED, SCATTER_NONE = 0, 1, 2, 3
 SCATTER_UNIT_DIRECTIONS = 1
 MAT_LAMBERTIAN, MAT_METAL, MAT_DIELECTRIC, MAT_NONE = 0, 1, 2, 255
+# r1_feature (32 bytes): a pixel of a feature frame
+FEATURE_DTYPE = np.dtype([("albedo", np.float32, 3), ("depth", np.float32), ("normal", np.float32, 3), ("hits", np.uint32)])
 
 
 def make_params(width, height, spp, seed=10001, max_bounces=50, tile_w=32, tile_h=32, shard=0, num_shards=1, variant=0):
@@ -259,6 +261,9 @@ SYMBOLS = [
     ("r1_render_region_linear", C.c_int, [_ctx, C.POINTER(Params), C.POINTER(Region), C.c_void_p, _u64p, _dblp]),
     ("r1_render_region_device", C.c_int, [_ctx, C.POINTER(Params), C.POINTER(Region), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("r1_render_region_host", C.c_int, [C.POINTER(CScene), C.POINTER(CCamera), C.POINTER(Params), C.POINTER(Region), C.c_void_p, _u64p]),
+    ("r1_render_features", C.c_int, [_ctx, C.POINTER(Params), C.POINTER(Region), C.c_void_p, _dblp]),
+    ("r1_render_features_device", C.c_int, [_ctx, C.POINTER(Params), C.POINTER(Region), C.c_void_p, C.c_void_p]),
+    ("r1_render_features_host", C.c_int, [C.POINTER(CScene), C.POINTER(CCamera), C.POINTER(Params), C.POINTER(Region), C.c_void_p]),
     ("r1_pfm_write_rgb32f", C.c_int, [C.c_char_p, C.c_int32, C.c_int32, _f32p]),
     ("r1_tga_write_rgb24", C.c_int, [C.c_char_p, C.c_int32, C.c_int32, _u8p]),
     ("r1_log_results", C.c_int, [C.c_char_p, C.c_char_p, _dblp, _u64p, C.c_int32]),
@@ -602,6 +607,27 @@ class Renderer:
         rg = Region(*[int(v) for v in region], int(out_stride))
         _check(lib().r1_render_region_device(self._c, C.byref(params), C.byref(rg), C.c_void_p(d_rgb_u8_ptr or None), C.c_void_p(d_rgb_f32_ptr or None),
                                              C.c_void_p(d_rays_ptr or None), _stream_arg(stream_ptr)))
+
+    def render_features(self, params, region=None, out=None):
+        """r1_render_features: first-hit albedo, normal, depth and hit count per pixel of the frame `params` describes, or of its window
+        `region` = (x0, y0, width, height); params.variant chooses tree, grid or reference form.  Returns (FEATURE_DTYPE array (height,
+        width), device seconds).  `out`: a FEATURE_DTYPE array or view of that shape whose rows lie whole records apart — that pitch
+        becomes the region's out_stride, and nothing between the rows is written."""
+        rg, img = _feature_target(params, region, out)
+        secs = C.c_double()
+        _check(lib().r1_render_features(self._c, C.byref(params), C.byref(rg) if rg is not None else None, C.c_void_p(img.ctypes.data), C.byref(secs)))
+        return img, secs.value
+
+    def render_features_device(self, params, d_out_ptr, region=None, stream_ptr=None, out_stride=0):
+        """r1_render_features_device: the same into device memory at d_out_ptr (16-byte aligned), rows out_stride records apart (0 = the
+        window's width); enqueued on stream_ptr, waits for nothing."""
+        if region is None and not out_stride:
+            rg = None
+        else:
+            x0, y0, w, h = (int(v) for v in region) if region is not None else (0, 0, params.width, params.height)
+            rg = Region(x0, y0, w, h, int(out_stride))
+        _check(lib().r1_render_features_device(self._c, C.byref(params), C.byref(rg) if rg is not None else None, C.c_void_p(d_out_ptr or None),
+                                               _stream_arg(stream_ptr)))
 
     def render_linear_async(self, params, frame_ptr, rays_ptr, stream_ptr=None):
         """r1_render_linear_async: enqueue one linear frame (throughput kernels); width * height * 3 floats land at `frame_ptr` and the
@@ -1242,6 +1268,30 @@ def render_region_host(cscene, ccamera, params, region, out=None):
     rays = C.c_uint64()
     _check(lib().r1_render_region_host(C.byref(cscene), C.byref(ccamera), C.byref(params), C.byref(rg), C.c_void_p(img.ctypes.data), C.byref(rays)))
     return img, int(rays.value)
+
+
+def _feature_target(params, region, out):
+    """(Region or None, array) of a host-memory feature frame: a new dense (height, width) FEATURE_DTYPE array, or the caller's `out` — an array
+    or a view of that shape whose rows lie a whole number of records apart: that pitch is the region's out_stride.  None: the call's NULL
+    region, the whole frame."""
+    x0, y0, w, h = (int(v) for v in region) if region is not None else (0, 0, params.width, params.height)
+    if out is None:
+        img = np.zeros((max(h, 1), max(w, 1)), FEATURE_DTYPE)  # (a size no array has: the library names the field)
+        return (Region(x0, y0, w, h, 0) if region is not None else None), img
+    item = FEATURE_DTYPE.itemsize
+    if not (isinstance(out, np.ndarray) and out.dtype == FEATURE_DTYPE and out.shape == (h, w) and out.strides[1] == item
+            and out.strides[0] % item == 0 and out.strides[0] >= item * w and out.flags.writeable):
+        raise R1Error(R1_EINVAL, f"feature frame: out must be a writeable FEATURE_DTYPE array or view of shape ({h}, {w}) with whole records between its rows")
+    return Region(x0, y0, w, h, out.strides[0] // item), out
+
+
+def render_features_host(cscene, ccamera, params, region=None, out=None):
+    """r1_render_features_host: the feature frame on the CPU (camera_rays + cast_rays_host per sample, summed in sample order; no device;
+    slow) — what Renderer.render_features is checked against.  Returns a FEATURE_DTYPE array (height, width); `region` and `out` as there."""
+    rg, img = _feature_target(params, region, out)
+    _check(lib().r1_render_features_host(C.byref(cscene), C.byref(ccamera), C.byref(params), C.byref(rg) if rg is not None else None,
+                                         C.c_void_p(img.ctypes.data)))
+    return img
 
 
 def quantise_linear(linear):

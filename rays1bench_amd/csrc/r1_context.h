@@ -269,6 +269,7 @@ void forget_occupancy(r1_context *c);               // the cached blocks per CU 
 int ensure_grid(r1_context *c);                     // R1_VARIANT_GRID: the grid of the context's scene, built and uploaded once per scene
 
 // r1_frame.cpp
+R1FastDiv make_div(uint32_t d);                     // the launch constant by which the kernels' fastdiv divides (r1_device.h R1FastDiv)
 bool big_scene(const r1_context *c, bool tree, bool grid, bool grid_pixel);
 void fill_scene(const r1_context *c, R1DeviceScene &s);
 void fill_walk(const r1_context *c, bool tree_lds, bool big, uint32_t top_nodes, R1TraceArgs &a);

@@ -339,7 +339,8 @@ enum
     R1_JOB_CAST = 0, // ray queries: closest hit or occlusion
     R1_JOB_PATH = 1, // path queries: color()
     R1_JOB_SCATTER = 2, // scatter queries: one color() level
-    R1_JOBS = 3
+    R1_JOB_FEATURES = 3, // feature frames: the camera's own rays, first-hit albedo, normal and depth summed per pixel
+    R1_JOBS = 4
 };
 
 // Ray queries (r1_cast_rays / r1_cast_rays_device, r1_query_kernels.hip): caller-supplied rays through the trace kernels' walks.
@@ -389,6 +390,24 @@ struct R1ScatterArgs
     uint32_t claim;         // rays per claim (a multiple of 64)
     uint32_t first;         // index within the call of the launch's ray 0 (seeds == null)
     uint32_t flags;         // R1_SCATTER_UNIT_DIRECTIONS: the directions are used as they are
+};
+
+// Feature frames (r1_render_features / r1_render_features_device, r1_query_kernels.hip): an item of the launch is a PIXEL of a
+// window of the frame; its lane makes the pixel's samples one after the other with camera_ray (r1_sample.hpp), walks each and sums the first
+// hit's albedo, normal and depth in registers.  Nothing is read but the scene tables: the frame is in the arguments.
+struct R1FeatureArgs
+{
+    R1TraceArgs t;          // what the walks read (scene tables, bvh_lds_f4, bvh_depth, grid) and the frame camera_ray reads where a sample starts:
+                            // cam, width, spp, seed, inv_w, inv_h, and inv_spp = (float)(1.0f / spp) (everything else zero)
+    float4 *out;            // pixel (x, y) of the frame at out + ((y - y0) * stride + (x - x0)) * 2: {albedo rgb, depth} {normal xyz, hits}, the public r1_feature
+    uint32_t *cursor;       // the launch's pixel cursor (zero before the launch): the waves claim `claim` pixels at a time
+    uint32_t n;             // pixels of the launch, <= R1_CAST_LAUNCH_MAX
+    uint32_t claim;         // pixels per claim (a multiple of 64)
+    uint32_t first;         // index within the window, row-major, of the launch's pixel 0
+    uint32_t x0, y0;        // the window's corner in the frame
+    uint32_t win_w;         // the window's width ...
+    R1FastDiv div_win_w;    // ... and the division by it (window index < 2^31)
+    uint32_t stride;        // pixels between the starts of two rows of the output, >= win_w
 };
 
 // r1_camera_rays_kernel (r1_aux_kernels.hip): the primary rays and stream states of samples [first, first + n) of a frame, in r1_render_samples' order

@@ -17,7 +17,7 @@ static bool same_tiling(const r1_params &a, const r1_params &b)
            a.shard == b.shard && a.num_shards == b.num_shards;
 }
 
-static R1FastDiv make_div(uint32_t d)
+R1FastDiv make_div(uint32_t d)
 {
     R1FastDiv r;
     uint32_t sh = 0;

@@ -92,6 +92,10 @@ hipError_t r1_trace_rays_occupancy(int variant, int big, size_t dyn_lds, int *bl
 hipError_t r1_launch_scatter_rays(const R1ScatterArgs *args, int variant, int big, int blocks, size_t dyn_lds, hipStream_t stream);
 hipError_t r1_scatter_rays_occupancy(int variant, int big, size_t dyn_lds, int *blocks_per_cu);
 
+// r1_query_kernels.hip, the feature job (an item is a pixel); variant as for r1_launch_cast
+hipError_t r1_launch_features(const R1FeatureArgs *args, int variant, int big, int blocks, size_t dyn_lds, hipStream_t stream);
+hipError_t r1_features_occupancy(int variant, int big, size_t dyn_lds, int *blocks_per_cu);
+
 // r1_aux_kernels.hip: r1_camera_rays_device
 hipError_t r1_launch_camera_rays(const R1CameraRaysArgs *args, hipStream_t stream);
 

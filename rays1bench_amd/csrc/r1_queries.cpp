@@ -1,7 +1,8 @@
 // r1_queries.cpp — caller-supplied rays through the context's tree or grid: the ray queries (closest hit and occlusion; include/rays1.h
 // "ray queries"), the path queries (radiance; "path queries", §4.22) and the scatter queries (one color() level; "scatter
 // queries", §4.34).  All are jobs of the kernels of r1_query_kernels.hip and share the checks, the launch plan and the chunked loop of the
-// host-memory forms below.  r1_camera_rays_device, the generator of device-resident rays, stands at the end.
+// host-memory forms below.  Feature frames ("feature frames", §4.38) are a fourth job through the same checks and plan: a query whose rays
+// are the frame's own.  r1_camera_rays_device, the generator of device-resident rays, stands at the end.
 
 #include <string.h>
 
@@ -13,6 +14,7 @@ static_assert(sizeof(r1_ray) == 32 && sizeof(r1_hit) == 32, "the cast job reads 
 static_assert(sizeof(r1_sample_seed) == 16 && sizeof(r1_radiance) == 16, "the path job reads and writes these layouts as one 16-byte word");
 static_assert(R1_TRACE_CHUNK == R1_CAST_CHUNK, "r1_trace_rays and r1_scatter_rays work in the ray queries' workspace, through the same loop: 64 / 128 bytes per ray of a chunk");
 static_assert(sizeof(r1_scatter) == 32, "the scatter job writes this layout as two float4");
+static_assert(sizeof(r1_feature) == 32, "the feature job writes this layout as two float4");
 
 // The checks every entry point makes before it touches anything; `extra` is the cast's mode, the trace's max_bounces or the step's flags, tested
 // where each job has always tested it: the mode and the flags before the variant, the bounces after.  *structure: what the rays walk — R1_V_TREE, R1_V_GRID or
@@ -41,7 +43,8 @@ static int query_check(const char *who, int job, r1_context *c, int32_t variant,
     case R1_VARIANT_GRID: *structure = R1_V_GRID; break;
     case R1_VARIANT_REFERENCE: *structure = R1_V_REFERENCE; break;
     default:
-        r1_set_error("%s: variant %d %s no rays (DEFAULT, BVH, GRID and REFERENCE do)", who, variant, job == R1_JOB_CAST ? "casts" : job == R1_JOB_PATH ? "traces" : "scatters");
+        r1_set_error("%s: variant %d %s no rays (DEFAULT, BVH, GRID and REFERENCE do)", who, variant,
+                     job == R1_JOB_CAST ? "casts" : job == R1_JOB_PATH ? "traces" : job == R1_JOB_SCATTER ? "scatters" : "walks");
         return R1_EINVAL;
     }
     if (job == R1_JOB_PATH && (extra < 1 || extra > R1_MAX_BOUNCES_LIMIT))
@@ -83,9 +86,10 @@ struct QuerySlice
 
 static hipError_t query_occupancy(const QueryPlan &P, int *occ)
 {
-    return P.job == R1_JOB_CAST   ? r1_cast_occupancy(P.structure, P.big, P.plain, P.dyn_lds, occ)
-           : P.job == R1_JOB_PATH ? r1_trace_rays_occupancy(P.structure, P.big, P.dyn_lds, occ)
-                                  : r1_scatter_rays_occupancy(P.structure, P.big, P.dyn_lds, occ);
+    return P.job == R1_JOB_CAST       ? r1_cast_occupancy(P.structure, P.big, P.plain, P.dyn_lds, occ)
+           : P.job == R1_JOB_PATH     ? r1_trace_rays_occupancy(P.structure, P.big, P.dyn_lds, occ)
+           : P.job == R1_JOB_FEATURES ? r1_features_occupancy(P.structure, P.big, P.dyn_lds, occ)
+                                      : r1_scatter_rays_occupancy(P.structure, P.big, P.dyn_lds, occ);
 }
 
 // Waits for nothing (the first grid query after r1_set_scene builds the grid, as the first grid render does) and touches none of the
@@ -122,15 +126,27 @@ static int query_plan(r1_context *c, int job, int structure, QueryPlan &P)
 // The next launch of n rays; false: none left.  Persistent: as many workgroups as the chip holds, fewer where the rays run out; a wave
 // claims 64 .. 256 rays at a time, about an eighth of its share (the waves that finish first take the rest).  The cursors are taken in
 // turn, so that launches in flight on different streams do not share one.
-static bool query_slice(r1_context *c, const QueryPlan &P, size_t n, QuerySlice &s)
+// walks: what one item of the launch costs in walks — 1 for a ray; a feature frame's item is a pixel of spp walks, and the eighth of a wave's
+// share is counted in walks, so that the tail of a launch — its slowest claim — stays what it is for rays: from spp 4 on that is the
+// minimum, one wave-full of 64 pixels.  The minimum is two wave-fulls once the launch fills the chip (more pixels than lanes; below that a
+// larger claim would only leave waves without one): a frame of a million pixels is 15 000 claims of 64 on ONE cursor, which sustains ~88 M
+// returning atomics a second (tools/ubench_atomic.hip), and the walks of a claim are short.  Measured with R1_FEATURE_CLAIM of the tuning library
+// (profiles/r34/features.txt), claims of 64 / 128 / 256 pixels, ms per frame: the large scene at 1200 x 800 x 10 0.349 / 0.331 / 0.415 (tree)
+// and 0.289 / 0.260 / 0.302 (grid); config 5's scene at 1920 x 1080 x 4 0.747 / 0.734 / 0.810 (tree) and 0.530 / 0.457 / 0.429 (grid).
+static bool query_slice(r1_context *c, const QueryPlan &P, size_t n, QuerySlice &s, uint32_t walks = 1)
 {
     s.at += s.n;
     if (s.at >= n)
         return false;
     s.n = (uint32_t)std::min<size_t>(n - s.at, R1_CAST_LAUNCH_MAX);
     s.blocks = (uint32_t)std::min<size_t>((size_t)c->cus * P.per_cu, ((size_t)s.n + R1_BLOCK - 1) / R1_BLOCK);
-    const uint32_t share = s.n / (s.blocks * (R1_BLOCK / 64) * 8u);
-    s.claim = std::min(256u, std::max(64u, (share + 63u) & ~63u));
+    const uint32_t waves = s.blocks * (R1_BLOCK / 64);
+    const uint32_t share = s.n / (waves * 8u) / walks;
+    const uint32_t least = P.job == R1_JOB_FEATURES && s.n / 64u > waves ? 128u : 64u;
+    s.claim = std::min(256u, std::max(least, (share + 63u) & ~63u));
+    static const uint32_t feature_claim = (uint32_t)r1_knob("R1_FEATURE_CLAIM", 0); // tuning library only
+    if (P.job == R1_JOB_FEATURES && feature_claim)
+        s.claim = (feature_claim + 63u) & ~63u;
     s.cursor = (uint32_t *)((char *)c->cast_cursors.p + 128 * (c->cast_cursor_next++ % R1_CAST_CURSORS));
     return true;
 }
@@ -400,6 +416,144 @@ extern "C" int r1_scatter_rays(r1_context *c, int32_t variant, int32_t flags, co
     return query_chunks(c, rays, seeds, sizeof(r1_sample_seed), n, outs, [=](const void *d_rays, const void *d_seeds, size_t at, size_t m, char *const *d_out) {
         return scatter_enqueue(c, structure, flags, d_rays, d_seeds, at, m, d_out[1], d_out[2], d_out[0], c->stream);
     });
+}
+
+// ---- feature frames ----------------------------------------------------------------------------------------------------
+// A query whose rays are the frame's own: the checks, the plan, the slices and the cursors are the queries', an item of a launch is a pixel
+// of the window.  Like every query it touches none of the state a render reads.
+
+// The refusals of both forms, in the documented order (NULL ctx; params, region, variant; no scene; then the caller tests `out`).  *win: the
+// region the call renders — the caller's, or the whole frame.
+static int features_check(const char *who, r1_context *c, const r1_params *p, const r1_region *region, r1_region *win, int *structure)
+{
+    if (!c)
+    {
+        r1_set_error("%s: ctx is NULL", who);
+        return R1_EINVAL;
+    }
+    if (!p)
+    {
+        r1_set_error("%s: params is NULL", who);
+        return R1_EINVAL;
+    }
+    const r1_region whole = {0, 0, p->width, p->height, 0};
+    *win = region ? *region : whole;
+    int rc = r1_region_check(p, win);
+    if (rc)
+        return rc;
+    return query_check(who, R1_JOB_FEATURES, c, p->variant, 0, structure);
+}
+
+// Enqueues window `win` of the frame (r1_region_check has passed it) on `st`: pixel (x, y) of the window at d_out + (y * stride + x) records.
+static int features_enqueue(r1_context *c, int structure, const r1_params *p, const r1_region &win, void *d_out, hipStream_t st)
+{
+    QueryPlan P;
+    int rc = query_plan(c, R1_JOB_FEATURES, structure, P);
+    if (rc)
+        return rc;
+    R1FeatureArgs a;
+    memset(&a, 0, sizeof(a));
+    a.t = P.t;
+    a.t.cam = c->cam;
+    a.t.width = p->width, a.t.height = p->height, a.t.spp = p->spp, a.t.seed = p->seed;
+    a.t.inv_w = 1.0f / p->width, a.t.inv_h = 1.0f / p->height; // rayweek1.cpp:746
+    a.t.inv_spp = (float)(1.0f / p->spp);                        // rayweek1.cpp:765
+    a.out = (float4 *)d_out;
+    a.x0 = (uint32_t)win.x0, a.y0 = (uint32_t)win.y0;
+    a.win_w = (uint32_t)win.width, a.div_win_w = make_div(a.win_w);
+    a.stride = (uint32_t)(win.out_stride ? win.out_stride : win.width);
+    const size_t n = (size_t)win.width * (size_t)win.height;
+    for (QuerySlice s; query_slice(c, P, n, s, (uint32_t)p->spp);)
+    {
+        a.first = (uint32_t)s.at;
+        a.n = s.n, a.claim = s.claim, a.cursor = s.cursor;
+        R1_HIP(hipMemsetAsync(a.cursor, 0, 4, st));
+        R1_HIP(r1_launch_features(&a, P.structure, P.big, (int)s.blocks, P.dyn_lds, st));
+    }
+    return R1_OK;
+}
+
+extern "C" int r1_render_features_device(r1_context *c, const r1_params *p, const r1_region *region, void *d_out, void *hip_stream)
+{
+    r1_region win;
+    int structure = 0;
+    int rc = features_check("r1_render_features_device", c, p, region, &win, &structure);
+    if (rc)
+        return rc;
+    if (!d_out || ((uintptr_t)d_out & 15u))
+    {
+        r1_set_error("r1_render_features_device: d_out must be non-NULL device memory, 16-byte aligned");
+        return R1_EINVAL;
+    }
+    return features_enqueue(c, structure, p, win, d_out, hip_stream ? (hipStream_t)hip_stream : c->stream);
+}
+
+// The host-memory form: bands of whole rows of the window, R1_CAST_CHUNK pixels at the most, densely in the queries' workspace (32 bytes a
+// pixel: device memory stays bounded for any frame), each copied home with the caller's row stride before the next reuses the workspace.
+// The device time is taken with events of the call's own: the context's describe the last render.
+extern "C" int r1_render_features(r1_context *c, const r1_params *p, const r1_region *region, r1_feature *out, double *device_seconds_out)
+{
+    r1_region win;
+    int structure = 0;
+    int rc = features_check("r1_render_features", c, p, region, &win, &structure);
+    if (rc)
+        return rc;
+    if (!out)
+    {
+        r1_set_error("r1_render_features: out is NULL");
+        return R1_EINVAL;
+    }
+    R1_HIP(hipSetDevice(c->device));
+    const size_t stride = win.out_stride ? (size_t)win.out_stride : (size_t)win.width;
+    const int32_t band_rows = (int32_t)std::max<size_t>(1, std::min<size_t>((size_t)win.height, R1_CAST_CHUNK / (size_t)win.width));
+    if ((rc = ensure(c->cast_ws, (size_t)band_rows * win.width * sizeof(r1_feature))))
+        return rc;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    if (device_seconds_out)
+    {
+        R1_HIP(hipEventCreate(&ev[0]));
+        if (hipEventCreate(&ev[1]) != hipSuccess)
+        {
+            (void)hipEventDestroy(ev[0]);
+            r1_set_error("r1_render_features: hipEventCreate failed");
+            return R1_EHIP;
+        }
+    }
+    // (from here on nothing returns before the events are destroyed: a failed step ends the loop)
+    double seconds = 0.0;
+    hipError_t e = hipSuccess;
+    for (int32_t y = 0; y < win.height && rc == R1_OK && e == hipSuccess; y += band_rows)
+    {
+        const int32_t rows = std::min(band_rows, win.height - y);
+        const r1_region band = {win.x0, win.y0 + y, win.width, rows, 0};
+        if (ev[0])
+            e = hipEventRecord(ev[0], c->stream);
+        if (e == hipSuccess)
+            rc = features_enqueue(c, structure, p, band, c->cast_ws.p, c->stream);
+        if (rc == R1_OK && e == hipSuccess && ev[1])
+            e = hipEventRecord(ev[1], c->stream);
+        if (rc == R1_OK && e == hipSuccess)
+            e = hipMemcpy2DAsync(out + (size_t)y * stride, stride * sizeof(r1_feature), c->cast_ws.p, (size_t)win.width * sizeof(r1_feature),
+                                 (size_t)win.width * sizeof(r1_feature), (size_t)rows, hipMemcpyDeviceToHost, c->stream);
+        if (rc == R1_OK && e == hipSuccess)
+            e = hipStreamSynchronize(c->stream); // (the next band reuses the workspace)
+        if (rc == R1_OK && e == hipSuccess && ev[0])
+        {
+            float ms = 0;
+            e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+            seconds += ms * 1e-3;
+        }
+    }
+    if (ev[0])
+        (void)hipEventDestroy(ev[0]), (void)hipEventDestroy(ev[1]);
+    if (rc == R1_OK && e != hipSuccess)
+    {
+        r1_set_error("r1_render_features: %s", hipGetErrorString(e));
+        rc = R1_EHIP;
+    }
+    if (rc == R1_OK && device_seconds_out)
+        *device_seconds_out = seconds;
+    return rc;
 }
 
 // ---- camera rays on the device -------------------------------------------------------------------------------------------------------------

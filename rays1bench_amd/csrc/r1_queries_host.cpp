@@ -1,5 +1,5 @@
 // r1_queries_host.cpp — the ray, path and scatter queries on the host, no GPU: r1_cast_rays_host, r1_trace_rays_host, r1_scatter_rays_host
-// and r1_camera_rays (include/rays1.h).  Every ray against every active sphere in index order, in the reference's arithmetic — its
+// and r1_camera_rays (include/rays1.h), and r1_render_features_host, their fold into a feature frame (§4.38).  Every ray against every active sphere in index order, in the reference's arithmetic — its
 // two FMA chains written with fmaf, everything else operation by operation (this file is compiled with -ffp-contract=off).
 
 #include "../../include/rays1.h"
@@ -11,6 +11,7 @@
 #include <math.h>
 #include <string.h>
 
+#include <atomic>
 #include <thread>
 #include <vector>
 
@@ -471,6 +472,89 @@ extern "C" int r1_scatter_rays_host(const r1_scene *s, int32_t flags, const r1_r
         return R1_EINVAL;
     split_rays(n, [&](size_t i0, size_t i1) { scatter_range(T, flags, rays, seeds, i0, i1, rays_out, seeds_out, out); });
     return R1_OK;
+}
+
+// ---- feature frames (include/rays1.h "feature frames") --------------------------------------------------------------------
+// The checker of r1_render_features*: per pixel of the window r1_camera_rays for its spp samples, cast_range — r1_cast_rays_host's loop — for
+// their R1_CAST_CLOSEST records, and the seven sums as plain fp32 adds in sample order, times (float)(1.0f / spp).
+extern "C" int r1_render_features_host(const r1_scene *s, const r1_camera *cam, const r1_params *p, const r1_region *region, r1_feature *out)
+{
+    if (!s || !cam || !p || !out)
+    {
+        r1_set_error("r1_render_features_host: null scene, camera, params or out");
+        return R1_EINVAL;
+    }
+    const r1_region whole = {0, 0, p->width, p->height, 0};
+    const r1_region win = region ? *region : whole;
+    int rc = r1_region_check(p, &win);
+    if (rc)
+        return rc;
+    if (s->count && (!s->center_x || !s->center_y || !s->center_z || !s->radius_sq || !s->inv_radius || !s->mat_type || !s->albedo_r || !s->albedo_g || !s->albedo_b))
+    {
+        r1_set_error("r1_render_features_host: null scene");
+        return R1_EINVAL;
+    }
+    std::vector<uint32_t> scene_index;
+    std::vector<float> ex;
+    if (exact_table(s, scene_index, ex) != R1_OK)
+        return R1_EINVAL;
+    const size_t spp = (size_t)p->spp, stride = win.out_stride ? (size_t)win.out_stride : (size_t)win.width;
+    const float inv = (float)(1.0f / p->spp); // rayweek1.cpp:765
+    std::atomic<int> failed(R1_OK); // (r1_camera_rays cannot fail on a checked window; kept for the day it can)
+    // (pixels of the window, row-major, on host threads: they are independent)
+    split_rays((size_t)win.width * (size_t)win.height, [&](size_t i0, size_t i1) {
+        std::vector<int32_t> xs(spp), ys(spp), ss(spp);
+        std::vector<r1_ray> rays(spp);
+        std::vector<r1_sample_seed> seeds(spp);
+        std::vector<r1_hit> hits(spp);
+        for (size_t k = 0; k < spp; ++k)
+            ss[k] = (int32_t)k;
+        for (size_t i = i0; i < i1; ++i)
+        {
+            const size_t wy = i / (size_t)win.width, wx = i % (size_t)win.width;
+            for (size_t k = 0; k < spp; ++k)
+                xs[k] = win.x0 + (int32_t)wx, ys[k] = win.y0 + (int32_t)wy;
+            if (r1_camera_rays(cam, p, xs.data(), ys.data(), ss.data(), spp, rays.data(), seeds.data()) != R1_OK)
+            {
+                failed = R1_EINVAL;
+                return;
+            }
+            cast_range(ex, scene_index, s, R1_CAST_CLOSEST, rays.data(), 0, spp, hits.data());
+            r1_feature f;
+            memset(&f, 0, sizeof(f));
+            for (size_t k = 0; k < spp; ++k)
+            {
+                V3 o, d;
+                if (!ray_start(rays[k], o, d))
+                    continue; // a non-finite ray: nothing is added
+                const r1_hit &h = hits[k];
+                if (h.index >= 0)
+                {
+                    const bool glass = s->mat_type[h.index] == R1_MAT_DIELECTRIC; // (attenuation 1, rayweek1.cpp:473)
+                    f.albedo[0] += glass ? 1.0f : s->albedo_r[h.index];
+                    f.albedo[1] += glass ? 1.0f : s->albedo_g[h.index];
+                    f.albedo[2] += glass ? 1.0f : s->albedo_b[h.index];
+                    f.normal[0] += h.n[0], f.normal[1] += h.n[1], f.normal[2] += h.n[2];
+                    f.depth += h.t;
+                    f.hits += 1u;
+                }
+                else
+                {
+                    // sky (rayweek1.cpp:532-534), lerp = (1 - t) * a + t * b (mymath.h:212-216)
+                    const float t = 0.5f * (d.y + 1.0f);
+                    const float omt = 1.0f - t;
+                    f.albedo[0] += omt * 1.0f + t * 0.5f, f.albedo[1] += omt * 1.0f + t * 0.7f, f.albedo[2] += omt * 1.0f + t * 1.0f;
+                }
+            }
+            for (int k = 0; k < 3; ++k)
+                f.albedo[k] *= inv, f.normal[k] *= inv;
+            f.depth *= inv;
+            out[wy * stride + wx] = f;
+        }
+    });
+    if (failed != R1_OK)
+        r1_set_error("r1_render_features_host: r1_camera_rays refused a sample of the window");
+    return failed;
 }
 
 // rayweek1.cpp:757-760 under the seeding contract — start_ray of r1_sample.hpp on the host, without the Ray constructor's normalisation

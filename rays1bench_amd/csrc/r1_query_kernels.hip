@@ -1,13 +1,13 @@
 // r1_query_kernels.hip — the kernels of the ray queries (r1_cast_rays*), of the path queries (r1_trace_rays*, §4.22) and of the
-// scatter queries (r1_scatter_rays*, §4.34):
+// scatter queries (r1_scatter_rays*, §4.34), and of the feature frames (r1_render_features*, §4.38), whose rays are the camera's own:
 // caller-supplied rays through the trace kernels' walks as they are — sweep_reference (r1_hit_sweep.hpp), bvh_advance (r1_hit_tree.hpp), grid_trace
 // (r1_hit_grid.hpp) — claimed with chunk_claim (r1_sample.hpp) and, the path jobs, shaded by shade_level (r1_shade.hpp).  There is
 // one loop per structure — box tree, uniform grid, reference form — and a JOB says what a lane does with a ray: how it is loaded and
 // when it is no ray at all, how its walk is seeded, what a complete walk leads to and which record is written.
-//   Args                     the kernel's argument struct; every job's has t, rays, cursor, n and claim
+//   Args                     the kernel's argument struct; every job's has t, cursor, n and claim
 //   waves(big)               the occupancy bound given to the compiler
 //   idle()                   the state of a lane without a ray (the walks are called by all 64 lanes)
-//   load(A, i)               ray i of the launch; false: the ray takes no walk
+//   load(A, i)               ray i of the launch (the feature job: pixel i, and its first sample's ray); false: it takes no walk
 //   seed(best)               where a walk's closest offer starts, if not at FLT_MAX
 //   O(), D()                 what the walk follows
 //   step(A, id, t, ..)       a walk is complete (id 0xFFFFFFFF: nothing hit); true: the ray's answer is known, false: O(), D() are the job's next walk
@@ -251,6 +251,111 @@ struct R1ScatterJob
         rec[0] = r0, rec[1] = r1;
         ray[0] = n0, ray[1] = n1;
         A.seeds_out[i] = make_uint4(p.s_scalar, p.s0, p.s1, p.s2);
+    }
+};
+
+// ---- the feature job: first-hit albedo, normal and depth of a frame's own primary rays, summed per pixel ------------------
+// An item is a PIXEL of a window of the frame, not a ray: load() makes sample 0's ray with camera_ray — the function r1_camera_rays_kernel
+// and start_sample call, so the ray is the render's — and step() adds what the walk found and makes the next sample's ray; the job
+// BOUNCES until the pixel's spp samples are through.  The camera and the frame's numbers are read from the kernel arguments where a sample
+// starts, and camera_ray's stream states die with it: nothing but the sums, the ray, the pixel and the sample index crosses a walk.
+//   hit      albedo += the sphere's (1, 1, 1 for a dielectric: Material::scatter's weight, the scatter job's rule), normal += (p - centre) *
+//            inv_radius (the cast job's n), depth += t, hits += 1
+//   miss     albedo += the sky of the ray (shade_level's three lines); normal, depth and hits stay
+//   a sample whose origin or normalised direction is not finite (the cast job's load rule) adds nothing and takes no walk
+// Plain fp32 adds in sample order, then one multiply by (float)(1.0f / spp) each: r1_render_linear's arithmetic, so a pixel without a
+// hit has that call's value.  One 32-byte record per pixel as two 16-byte stores; no atomics, no LDS of its own, no sample records.
+// Registers (profiles/r34/features_kernel_meta.txt, beside the cast's r10 / r15, the path's r14 and the scatter's r29): the job carries 16 words
+// across a walk — seven sums, hits, the ray, the pixel, the sample — where the cast carries seven and the scatter job ten.  Under the bounds
+// 4, 5 and 6 waves the compiler gives one and the same code: 57 VGPRs (tree) and 61 (grid), so eight waves per SIMD fit all the same, with
+// the SGPR file at its limit of 106 and 2 .. 11 SGPRs parked in VGPR lanes (4 .. 33 v_readlane / v_writelane): the camera's 19 words beside
+// the walk's table bases.  Under eight it keeps 78 SGPRs and parks 27 .. 48 (81 .. 152 lane moves, 100 .. 150 instructions more) for 54 .. 60
+// VGPRs.  Without the root step by slots the small-scene tree kernel parks none and is 152 instructions shorter; the others do not change.
+// On the device (profiles/r34/features.txt) eight waves and the plain root step both stay inside the run-to-run spread of six waves with
+// the step: waves() R1_PATHQ_WAVES' value, root_by_slots() true, as the path and scatter jobs.
+#ifndef R1_FEATURE_WAVES
+#define R1_FEATURE_WAVES 6
+#endif
+#ifndef R1_FEATURE_ROOT_BY_SLOTS
+#define R1_FEATURE_ROOT_BY_SLOTS true
+#endif
+struct R1FeatureJob
+{
+    typedef R1FeatureArgs Args;
+    static constexpr bool BOUNCES = true;
+    static constexpr int waves(bool) { return R1_FEATURE_WAVES; }
+    static constexpr bool root_by_slots(bool) { return R1_FEATURE_ROOT_BY_SLOTS; }
+
+    V3 o, d;        // the sample's ray
+    V3 albedo, normal;
+    float depth;
+    uint32_t hits;
+    uint32_t xy;    // x | y << 16: the pixel in the frame (width, height <= 65535)
+    uint32_t s;     // the sample the ray belongs to
+
+    __device__ __forceinline__ void idle()
+    {
+        o = mk(0, 0, 0), d = mk(0, 0, 1);
+        albedo = normal = mk(0, 0, 0), depth = 0.0f, hits = 0u, xy = 0u, s = 0u;
+    }
+    // the ray of the first finite sample from s on; false: the pixel has none left
+    __device__ __forceinline__ bool aim(const Args &A)
+    {
+        for (; s < (uint32_t)A.t.spp; ++s)
+        {
+            Path p;
+            const int x = (int)(xy & 0xFFFFu), y = (int)(xy >> 16);
+            d = vunit(camera_ray(A.t.width, A.t.inv_w, A.t.inv_h, A.t.cam, p, x, y, s, A.t.seed)); // Ray::Ray, rayweek1.cpp:107
+            o = p.o;
+            if (query_finite(o.x) && query_finite(o.y) && query_finite(o.z) && query_finite(d.x) && query_finite(d.y) && query_finite(d.z))
+                return true;
+        }
+        return false;
+    }
+    __device__ __forceinline__ bool load(const Args &A, const uint32_t i)
+    {
+        const uint32_t w = A.first + i; // the pixel's index in the window
+        const uint32_t wy = fastdiv(w, A.div_win_w), wx = w - wy * A.win_w;
+        xy = (A.x0 + wx) | ((A.y0 + wy) << 16);
+        albedo = normal = mk(0, 0, 0), depth = 0.0f, hits = 0u, s = 0u;
+        return aim(A);
+    }
+    __device__ __forceinline__ void seed(float &) const {}
+    __device__ __forceinline__ V3 O() const { return o; }
+    __device__ __forceinline__ V3 D() const { return d; }
+    __device__ __forceinline__ bool step(const Args &A, const uint32_t id, const float t, uint32_t, int)
+    {
+        if (id != 0xFFFFFFFFu)
+        {
+            // the hit record of rayweek1.cpp:316-322 as the cast job stores it; the rows as scatter_hit reads them
+            const f4 e = ((const f4 *)A.t.scene.exact)[id];
+            const f4 sh = ((const f4 *)A.t.scene.shade)[id];
+            const bool glass = __float_as_uint(((const f4 *)A.t.scene.mat)[id].x) == 2u;
+            const V3 hp = vadd(o, vscale(d, t));
+            const V3 n = vscale(vsub(hp, mk(e.x, e.y, e.z)), sh.x);
+            albedo = vadd(albedo, mk(glass ? 1.0f : sh.y, glass ? 1.0f : sh.z, glass ? 1.0f : sh.w));
+            normal = vadd(normal, n);
+            depth += t;
+            ++hits;
+        }
+        else
+        {
+            // miss: sky (rayweek1.cpp:532-534), lerp = (1 - t) * a + t * b (mymath.h:212-216): shade_level's three lines
+            const float k = 0.5f * (d.y + 1.0f);
+            const float omk = 1.0f - k;
+            albedo = vadd(albedo, mk(omk * 1.0f + k * 0.5f, omk * 1.0f + k * 0.7f, omk * 1.0f + k * 1.0f));
+        }
+        ++s;
+        return !aim(A); // false: the next sample's ray is in o, d
+    }
+    // (walked false: every sample was non-finite — the sums are the zeros load() left)
+    __device__ __forceinline__ void finish(const Args &A, const uint32_t, const bool) const
+    {
+        const float inv = A.t.inv_spp;
+        const uint32_t wx = (xy & 0xFFFFu) - A.x0, wy = (xy >> 16) - A.y0;
+        float4 *dst = A.out + 2 * ((size_t)wy * A.stride + wx);
+        dst[0] = make_float4(albedo.x * inv, albedo.y * inv, albedo.z * inv, depth * inv);
+        dst[1] = make_float4(normal.x * inv, normal.y * inv, normal.z * inv, __uint_as_float(hits));
     }
 };
 
@@ -503,10 +608,11 @@ static const void *query_kernel(const int job, const int variant, const int big,
 #endif
     if (plain)
         return nullptr;
-    return job == R1_JOB_CAST      ? query_kernel<R1CastJob>(variant, big)
-           : job == R1_JOB_PATH    ? query_kernel<R1PathJob>(variant, big)
-           : job == R1_JOB_SCATTER ? query_kernel<R1ScatterJob>(variant, big)
-                                   : nullptr;
+    return job == R1_JOB_CAST       ? query_kernel<R1CastJob>(variant, big)
+           : job == R1_JOB_PATH     ? query_kernel<R1PathJob>(variant, big)
+           : job == R1_JOB_SCATTER  ? query_kernel<R1ScatterJob>(variant, big)
+           : job == R1_JOB_FEATURES ? query_kernel<R1FeatureJob>(variant, big)
+                                    : nullptr;
 }
 
 // One launcher and one occupancy query, keyed by job, structure and big; args: the job's argument struct.  The C names below are their
@@ -552,4 +658,12 @@ extern "C" hipError_t r1_launch_scatter_rays(const R1ScatterArgs *args, int vari
 extern "C" hipError_t r1_scatter_rays_occupancy(int variant, int big, size_t dyn_lds, int *blocks_per_cu)
 {
     return query_occupancy(R1_JOB_SCATTER, variant, big, 0, dyn_lds, blocks_per_cu);
+}
+extern "C" hipError_t r1_launch_features(const R1FeatureArgs *args, int variant, int big, int blocks, size_t dyn_lds, hipStream_t stream)
+{
+    return query_launch(R1_JOB_FEATURES, args, variant, big, 0, blocks, dyn_lds, stream);
+}
+extern "C" hipError_t r1_features_occupancy(int variant, int big, size_t dyn_lds, int *blocks_per_cu)
+{
+    return query_occupancy(R1_JOB_FEATURES, variant, big, 0, dyn_lds, blocks_per_cu);
 }

@@ -32,6 +32,9 @@
 // --region X,Y,W,H renders each frame through r1_render_region: window (X, Y, W, H) of the --width x --height frame (row 0 = bottom row), the
 // crop of the whole frame byte for byte; the pixels, the TGA and the counts of the report and of out_<scene>.txt are the window's, and the report
 // gains one "<scene> region:" line.
+// --features also renders each frame's feature frame through r1_render_features (the window's, with --region): first-hit albedo, normal and
+// depth per pixel, aligned with the frame; -w also writes out_<scene>_albedo.pfm, _normal.pfm and _depth.pfm (depth in all three channels),
+// and the report gains one "<scene> features:" line with the device time.
 // --backend hip (default) | cpu-step1 | cpu-step12: the reference's two single-thread CPU stages
 // (r1_cpu_backends.cpp) behind the same benchmark(), for the README-style table
 // (README.md:38-84).  Named backends of this program only — never a fallback: with --backend hip and no
@@ -76,6 +79,7 @@ static r1_multi *g_multi = nullptr;     // --gather rccl
 static std::vector<double> g_device_seconds; // per benchmark() call, for the JSON record
 static r1_launch_info g_last_info;
 static float *g_linear = nullptr; // --linear: the frame r1_render_linear fills (page-locked where the device allows it)
+static std::vector<r1_feature> g_features; // --features: the feature frame of the last benchmark() call
 
 r1_params frame_params()
 {
@@ -186,6 +190,7 @@ static Frame context_frame(const Scene *scene, Pix *pixels, const r1_params &p, 
     std::vector<std::string> errs(nd);
     r1_adaptive_result adapt_res;
     memset(&adapt_res, 0, sizeof(adapt_res));
+    double features_s = 0.0;
     auto worker = [&](int i) {
         r1_params q = p;
         q.shard = i, q.num_shards = nd;
@@ -232,6 +237,12 @@ static Frame context_frame(const Scene *scene, Pix *pixels, const r1_params &p, 
             rc = r1_render_region(g_ctx[i], &q, &g_opt.window, &pixels[0].r, &rays[i], &dev_s[i]);
         else if (rc == R1_OK)
             rc = r1_render(g_ctx[i], &q, &pixels[0].r, &rays[i], &dev_s[i]);
+        if (rc == R1_OK && g_opt.features) // --features (one device): the feature frame of what was just rendered — the frame, or --region's window
+        {
+            const r1_region *const win = g_opt.region ? &g_opt.window : nullptr;
+            g_features.assign(win ? (size_t)win->width * win->height : (size_t)q.width * q.height, r1_feature());
+            rc = r1_render_features(g_ctx[i], &q, win, g_features.data(), &features_s);
+        }
         rcs[i] = rc;
         if (rc != R1_OK)
             errs[i] = r1_last_error(); // thread-local in the library
@@ -286,6 +297,14 @@ static Frame context_frame(const Scene *scene, Pix *pixels, const r1_params &p, 
                              g_opt.window.width, g_opt.window.height, g_opt.width, g_opt.height,
                              (double)g_opt.window.width * g_opt.window.height / ((double)g_opt.width * g_opt.height),
                              (unsigned long long)((uint64_t)g_opt.window.width * g_opt.window.height * g_opt.spp), (unsigned long long)f.rays);
+    if (g_opt.features)
+    {
+        uint64_t hits = 0, covered = 0;
+        for (const r1_feature &v : g_features)
+            hits += v.hits, covered += v.hits ? 1 : 0;
+        f.lines_after += line("%s features: %zu pixels, %llu with a hit, coverage %.4f of the samples, device time %.3fms\n", scene_name, g_features.size(),
+                              (unsigned long long)covered, (double)hits / ((double)g_features.size() * g_opt.spp), features_s * 1e3);
+    }
     return f;
 }
 
@@ -332,6 +351,20 @@ RESULT benchmark(Scene *scene, Pix *pixels, bool write_tga, const char *scene_na
         {
             snprintf(filename, sizeof(filename), "out_%s.pfm", scene_name);
             r1_pfm_write_rgb32f(filename, g_opt.width, g_opt.height, g_linear);
+        }
+        if (g_opt.features)
+        {
+            // three planes of the feature frame, each as RGB fp32: albedo, normal, depth (in all three channels)
+            std::vector<float> plane(g_features.size() * 3);
+            static const char *const names[3] = {"albedo", "normal", "depth"};
+            for (int k = 0; k < 3; ++k)
+            {
+                for (size_t i = 0; i < g_features.size(); ++i)
+                    for (int ch = 0; ch < 3; ++ch)
+                        plane[3 * i + ch] = k == 0 ? g_features[i].albedo[ch] : k == 1 ? g_features[i].normal[ch] : g_features[i].depth;
+                snprintf(filename, sizeof(filename), "out_%s_%s.pfm", scene_name, names[k]);
+                r1_pfm_write_rgb32f(filename, out_w, out_h, plane.data());
+            }
         }
     }
     return result;
@@ -415,6 +448,11 @@ int main(int argc, const char *argv[])
         if (strcmp(argv[i], "--linear") == 0)
         {
             o.linear = true;
+            continue;
+        }
+        if (strcmp(argv[i], "--features") == 0)
+        {
+            o.features = true;
             continue;
         }
         if (i + 1 >= argc)
@@ -518,6 +556,12 @@ int main(int argc, const char *argv[])
     if (o.linear && (!one_pass || o.adaptive))
     {
         fprintf(stderr, "bad --linear: needs the hip backend, one device (no --gather rccl), no --passes and no --adaptive\n");
+        return 1;
+    }
+
+    if (o.features && (!one_pass || o.adaptive || !(tree_variant || o.variant == R1_VARIANT_GRID || o.variant == R1_VARIANT_REFERENCE)))
+    {
+        fprintf(stderr, "bad --features: needs the hip backend, one device (no --gather rccl), --variant 0, 1, 4 or 7, no --passes and no --adaptive\n");
         return 1;
     }
 

@@ -20,6 +20,7 @@ struct Options
     bool adaptive = false; // --adaptive: every frame through r1_render_adaptive
     r1_adaptive adapt = {16, 16, 0, 65280};
     bool linear = false; // --linear: every frame through r1_render_linear, the pixels through r1_quantise_linear; -w also writes out_<scene>.pfm
+    bool features = false; // --features: each frame's feature frame too (r1_render_features); -w also writes out_<scene>_albedo.pfm, _normal.pfm, _depth.pfm
     bool region = false; // --region X,Y,W,H: every frame through r1_render_region; the pixels, the TGA and the counts are the window's
     r1_region window = {0, 0, 0, 0, 0};
     // the demos, each FRAMES frames per scene after the benchmark() runs; 0 = not asked for
