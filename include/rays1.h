@@ -526,6 +526,86 @@ int r1_render_features_device(r1_context *ctx, const r1_params *params, const r1
  * is what the other two are checked against.  params->variant is checked as r1_region_check checks it and otherwise unused. */
 int r1_render_features_host(const r1_scene *scene, const r1_camera *camera, const r1_params *params, const r1_region *region, r1_feature *out);
 
+/* ---- denoised frames: an edge-avoiding a-trous filter over the feature guides ---- */
+
+/* The filter of a noisy linear frame L (r1_render_linear's layout: three floats per pixel, row 0 = bottom row) guided by the feature frame f
+ * of the same frame (r1_render_features): a 5 x 5 B3-spline kernel applied `iterations` times with its taps 1, 2, 4, ... pixels apart, every
+ * tap weighted by how well its normal, its depth and its current colour agree with the centre's.  The arithmetic is one contract, and the
+ * device forms equal r1_denoise_host bit for bit.  Plain fp32; every * + - / and sqrtf below is one correctly rounded operation in the order
+ * written, nothing is fused, min / max / clamp are selects, the weights are rational (no exp), subnormal values are kept.
+ *   prepare, per pixel p:
+ *     surf = hits > 0;  a_c = DEMODULATE ? (albedo_c < 1/256 ? 1/256 : albedo_c) : 1;  e_c = L_c / a_c
+ *     nn = (nx*nx + ny*ny) + nz*nz;  l = sqrtf(nn);  nh = l > 0 ? n / l : 0 (one division per component)
+ *     m = surf ? depth / (float)hits : 0      (the mean distance of the pixel's hits, up to the factor spp both sides of a ratio share)
+ *   iteration i = 0 .. iterations - 1, cur = e at first:
+ *     step = 1 << i;  sc = sigma_color * 2^-i;  sc2 = sc * sc
+ *     a pixel that is not surf keeps its value; for a surf pixel p: S_c = 0, W = 0, then the taps q = p + step * (dx, dy), dy = -2 .. 2 in
+ *     the outer loop and dx = -2 .. 2 in the inner one; a tap off the image or not surf is skipped
+ *       h = H[dy + 2] * H[dx + 2], H = {1/16, 1/4, 3/8, 1/4, 1/16} (exact products); the centre tap has w = h; any other tap
+ *       c = (nh_p.x*nh_q.x + nh_p.y*nh_q.y) + nh_p.z*nh_q.z;  c = c < 0 ? 0 : c;  c = c > 1 ? 1 : c;  c = c * c, normal_power_log2 times
+ *       mx = m_p < m_q ? m_q : m_p;  den = sigma_depth * mx;  rz = den > 0 ? (m_p - m_q) / den : 0;  xz = rz * rz
+ *       d = cur_p - cur_q;  dc = (d.r*d.r + d.g*d.g) + d.b*d.b;  xc = dc / sc2
+ *       w = (h * c) / ((1 + xz) * (1 + xc))
+ *       S_c = S_c + w * cur_q,c (multiply, then add);  W = W + w
+ *     next_c = S_c / W  (W is at least 9/64, the centre's)
+ *   end: out_c = cur_c * a_c for surf pixels; every other pixel of out has L's bits — all of its samples saw the sky of their primary rays,
+ *   the pixel is free of noise.
+ * No address depends on pixel data; non-finite input propagates by IEEE rules and cannot fault.
+ * What to choose: the filter removes noise and detail alike, and the fewer samples a frame has the better the trade.  At 1-4 spp three
+ * iterations with normal_power_log2 6, sigma_color 1, sigma_depth 0.1 and DEMODULATE cut the error against a converged frame to 0.4-0.85 of
+ * the noisy frame's; at 16 spp three or more iterations gain little or make the frame WORSE and one iteration is what still helps
+ * (DESIGN.md 4.39 has the figures).  A scene whose spheres are a few pixels each wants a lower normal_power_log2 (4). */
+#define R1_DENOISE_DEMODULATE 1u       /* divide by the first-hit albedo before the filter, multiply after it: texture edges survive */
+#define R1_DENOISE_MAX_ITERATIONS 8
+#define R1_DENOISE_MAX_POWER_LOG2 10
+typedef struct r1_denoise_opt
+{
+    int32_t iterations;        /* 1 .. 8: the taps of the last one are 2^(iterations - 1) pixels apart */
+    int32_t normal_power_log2; /* k in 0 .. 10: the normals' cosine is raised to 2^k */
+    float sigma_color;         /* > 0, finite */
+    float sigma_depth;         /* > 0, finite: relative to the larger of the two mean distances */
+    uint32_t flags;            /* R1_DENOISE_DEMODULATE or 0 */
+} r1_denoise_opt;
+
+/* The three images of a call: width x height pixels each, rows `*_stride` PIXELS apart (three floats of L and out, one record of f); a
+ * stride of 0 means width.  Nothing between the rows is read or written. */
+typedef struct r1_denoise_frame
+{
+    int32_t width, height;
+    int32_t linear_stride, feature_stride, out_stride;
+} r1_denoise_frame;
+
+/* The rules of both structs, pure arithmetic, the one place they are checked: R1_EINVAL names the offending field (width, height, a stride
+ * that is neither 0 nor >= width, iterations, normal_power_log2, sigma_color, sigma_depth, flags), R1_ELIMIT at width * height >= 2^31. */
+int r1_denoise_check(const r1_denoise_frame *frame, const r1_denoise_opt *opt);
+
+/* The definition: the contract above on the CPU, no device.  `out` may be L (L is consumed before out is written); f must not overlap out. */
+int r1_denoise_host(const r1_denoise_frame *frame, const r1_denoise_opt *opt, const float *L, const r1_feature *f, float *out);
+
+/* The same on DEVICE memory: d_L and d_out 4-byte aligned, d_f 16-byte aligned, d_out may be d_L.  Everything is enqueued on `hip_stream`
+ * (NULL = the context's stream), nothing is waited for.  The filter's records (48 bytes a pixel) live in a workspace of the context that
+ * grows on first use, as the queries' does: ONE denoise per context may be in flight, ordered by the stream.  Like the queries it changes no
+ * state a render reads: a progressive accumulation survives it, r1_last_launch_info and r1_last_timing keep describing the last render.
+ * Needs no scene.  Refusals, in this order: ctx NULL; frame or options (r1_denoise_check); then pointers and alignment.  A refused call
+ * enqueues nothing. */
+int r1_denoise_device(r1_context *ctx, const r1_denoise_frame *frame, const r1_denoise_opt *opt, const void *d_L, const void *d_f, void *d_out, void *hip_stream);
+
+/* The same on HOST memory, synchronous: L and f go up, out comes home; device_seconds_out (may be NULL) is the filter's time alone. */
+int r1_denoise(r1_context *ctx, const r1_denoise_frame *frame, const r1_denoise_opt *opt, const float *L, const r1_feature *f, float *out,
+               double *device_seconds_out);
+
+/* A frame rendered and denoised: r1_render_linear_device + r1_render_features_device + r1_denoise_device of the whole frame `params`
+ * describes, on one stream, the feature frame in the context's workspace; rgb_out is r1_render_linear's layout, the ray count is
+ * r1_render_linear's.  params->variant must be one both parts accept — DEFAULT, BVH, GRID or REFERENCE — else R1_EINVAL; for the rest the
+ * rules are r1_render_linear's, and so is the state the call leaves (launch info, timing).  Refusals, in
+ * this order: ctx NULL; params or options NULL, the options, the variant; then pointers and alignment; then what r1_render_linear refuses.
+ * A refused call enqueues nothing.  Synchronous; device_seconds_out (may be NULL): render, features and filter together. */
+int r1_render_denoised(r1_context *ctx, const r1_params *params, const r1_denoise_opt *opt, float *rgb_out, uint64_t *num_rays_out,
+                       double *device_seconds_out);
+
+/* The same into DEVICE memory (d_rgb_f32 4-byte aligned, d_num_rays 8-byte aligned), enqueued on `hip_stream`, waits for nothing. */
+int r1_render_denoised_device(r1_context *ctx, const r1_params *params, const r1_denoise_opt *opt, void *d_rgb_f32, void *d_num_rays, void *hip_stream);
+
 /* Pipelined form of r1_render — frames in flight whose results land on the HOST.  The reference times
  * dispatch -> pixels + ray count on the host (rayweek1.cpp:848 -> :891) for ONE frame and waits; a caller that
  * renders frame after frame (main's `-n` runs, rayweek1.cpp:969-984) can keep several in flight instead: the call

@@ -97,6 +97,26 @@ class Region(C.Structure):
     _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("out_stride", C.c_int32)]
 
 
+# denoised frames (r1_denoise*): the flag, the limits of the options
+DENOISE_DEMODULATE = 1
+DENOISE_MAX_ITERATIONS, DENOISE_MAX_POWER_LOG2 = 8, 10
+
+
+class DenoiseOpt(C.Structure):
+    """r1_denoise_opt: iterations 1..8, normal_power_log2 0..10, sigma_color and sigma_depth > 0 and finite, flags DENOISE_DEMODULATE or 0."""
+    _fields_ = [("iterations", C.c_int32), ("normal_power_log2", C.c_int32), ("sigma_color", C.c_float), ("sigma_depth", C.c_float), ("flags", C.c_uint32)]
+
+
+class DenoiseFrame(C.Structure):
+    """r1_denoise_frame: the size of the three images and the pixels between two rows of each (0 = width)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("linear_stride", C.c_int32), ("feature_stride", C.c_int32), ("out_stride", C.c_int32)]
+
+
+def make_denoise_opt(iterations=3, normal_power_log2=6, sigma_color=1.0, sigma_depth=0.1, flags=DENOISE_DEMODULATE):
+    """The options DESIGN.md §4.39 measured at 1-4 spp; at 16 spp and more, iterations=1."""
+    return DenoiseOpt(int(iterations), int(normal_power_log2), float(sigma_color), float(sigma_depth), int(flags))
+
+
 class TileReport(C.Structure):
     _fields_ = [("spp", C.c_int32), ("settled", C.c_int32), ("err_max", C.c_uint32), ("err_sum", C.c_uint32)]
 
@@ -264,6 +284,12 @@ SYMBOLS = [
     ("r1_render_features", C.c_int, [_ctx, C.POINTER(Params), C.POINTER(Region), C.c_void_p, _dblp]),
     ("r1_render_features_device", C.c_int, [_ctx, C.POINTER(Params), C.POINTER(Region), C.c_void_p, C.c_void_p]),
     ("r1_render_features_host", C.c_int, [C.POINTER(CScene), C.POINTER(CCamera), C.POINTER(Params), C.POINTER(Region), C.c_void_p]),
+    ("r1_denoise_check", C.c_int, [C.POINTER(DenoiseFrame), C.POINTER(DenoiseOpt)]),
+    ("r1_denoise_host", C.c_int, [C.POINTER(DenoiseFrame), C.POINTER(DenoiseOpt), C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("r1_denoise_device", C.c_int, [_ctx, C.POINTER(DenoiseFrame), C.POINTER(DenoiseOpt), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("r1_denoise", C.c_int, [_ctx, C.POINTER(DenoiseFrame), C.POINTER(DenoiseOpt), C.c_void_p, C.c_void_p, C.c_void_p, _dblp]),
+    ("r1_render_denoised", C.c_int, [_ctx, C.POINTER(Params), C.POINTER(DenoiseOpt), C.c_void_p, _u64p, _dblp]),
+    ("r1_render_denoised_device", C.c_int, [_ctx, C.POINTER(Params), C.POINTER(DenoiseOpt), C.c_void_p, C.c_void_p, C.c_void_p]),
     ("r1_pfm_write_rgb32f", C.c_int, [C.c_char_p, C.c_int32, C.c_int32, _f32p]),
     ("r1_tga_write_rgb24", C.c_int, [C.c_char_p, C.c_int32, C.c_int32, _u8p]),
     ("r1_log_results", C.c_int, [C.c_char_p, C.c_char_p, _dblp, _u64p, C.c_int32]),
@@ -627,6 +653,35 @@ class Renderer:
             x0, y0, w, h = (int(v) for v in region) if region is not None else (0, 0, params.width, params.height)
             rg = Region(x0, y0, w, h, int(out_stride))
         _check(lib().r1_render_features_device(self._c, C.byref(params), C.byref(rg) if rg is not None else None, C.c_void_p(d_out_ptr or None),
+                                               _stream_arg(stream_ptr)))
+
+    def denoise(self, L, f, opt, out=None):
+        """r1_denoise: the a-trous filter of the linear frame L (float32 (height, width, 3)) guided by the feature frame f (FEATURE_DTYPE
+        (height, width)), host memory, synchronous.  Arrays or views whose rows lie whole pixels apart: the pitches become the frame's
+        strides.  `out`: None (a new dense array), or such an array — L itself for in place.  Returns (out, device seconds of the filter)."""
+        fr, L, f, out = _denoise_target(L, f, out)
+        secs = C.c_double()
+        _check(lib().r1_denoise(self._c, C.byref(fr), C.byref(opt), C.c_void_p(L.ctypes.data), C.c_void_p(f.ctypes.data), C.c_void_p(out.ctypes.data), C.byref(secs)))
+        return out, secs.value
+
+    def denoise_device(self, width, height, opt, d_L_ptr, d_f_ptr, d_out_ptr, stream_ptr=None, linear_stride=0, feature_stride=0, out_stride=0):
+        """r1_denoise_device: the same on device memory (d_L and d_out 4-byte aligned, d_f 16-byte aligned, d_out may be d_L; strides in
+        pixels, 0 = width); enqueued on stream_ptr, waits for nothing.  One denoise per context in flight."""
+        fr = DenoiseFrame(int(width), int(height), int(linear_stride), int(feature_stride), int(out_stride))
+        _check(lib().r1_denoise_device(self._c, C.byref(fr), C.byref(opt), C.c_void_p(d_L_ptr or None), C.c_void_p(d_f_ptr or None), C.c_void_p(d_out_ptr or None),
+                                       _stream_arg(stream_ptr)))
+
+    def render_denoised(self, params, opt):
+        """r1_render_denoised: the frame rendered (r1_render_linear), its feature frame and the filter, on the device.  Returns (float32
+        (height, width, 3), ray count, device seconds of all three)."""
+        img = np.zeros((max(params.height, 1), max(params.width, 1), 3), np.float32)
+        rays, secs = C.c_uint64(), C.c_double()
+        _check(lib().r1_render_denoised(self._c, C.byref(params), C.byref(opt), C.c_void_p(img.ctypes.data), C.byref(rays), C.byref(secs)))
+        return img, int(rays.value), secs.value
+
+    def render_denoised_device(self, params, opt, d_rgb_f32_ptr, d_rays_ptr, stream_ptr=None):
+        """r1_render_denoised_device: the same into device memory (width * height * 3 floats, and one uint64); waits for nothing."""
+        _check(lib().r1_render_denoised_device(self._c, C.byref(params), C.byref(opt), C.c_void_p(d_rgb_f32_ptr or None), C.c_void_p(d_rays_ptr or None),
                                                _stream_arg(stream_ptr)))
 
     def render_linear_async(self, params, frame_ptr, rays_ptr, stream_ptr=None):
@@ -1292,6 +1347,41 @@ def render_features_host(cscene, ccamera, params, region=None, out=None):
     _check(lib().r1_render_features_host(C.byref(cscene), C.byref(ccamera), C.byref(params), C.byref(rg) if rg is not None else None,
                                          C.c_void_p(img.ctypes.data)))
     return img
+
+
+def _pixel_pitch(a, what, dtype, tail, item):
+    """pixels between two rows of `a`, an array or view of shape (h, w) + tail whose pixels are contiguous and whose rows lie whole pixels apart"""
+    ok = isinstance(a, np.ndarray) and a.dtype == dtype and a.ndim == 2 + len(tail) and a.shape[2:] == tail and a.shape[0] > 0 and a.shape[1] > 0
+    ok = ok and a.strides[1] == item and (not tail or a.strides[2] == 4) and a.strides[0] % item == 0 and a.strides[0] >= item * a.shape[1]
+    if not ok:
+        raise R1Error(R1_EINVAL, f"denoise: {what} must be a {np.dtype(dtype).name} array or view (height, width{', 3' if tail else ''}) with whole pixels between its rows")
+    return a.strides[0] // item
+
+
+def _denoise_target(L, f, out):
+    """(DenoiseFrame, L, f, out) of a host-memory denoise: the pitches of the three arrays become the frame's strides; out None: a new dense array"""
+    ls, fs = _pixel_pitch(L, "L", np.float32, (3,), 12), _pixel_pitch(f, "f", FEATURE_DTYPE, (), FEATURE_DTYPE.itemsize)
+    h, w = L.shape[:2]
+    if out is None:
+        out = np.zeros((h, w, 3), np.float32)
+    os_ = _pixel_pitch(out, "out", np.float32, (3,), 12)
+    if f.shape != (h, w) or out.shape != (h, w, 3) or not out.flags.writeable:
+        raise R1Error(R1_EINVAL, f"denoise: L {L.shape}, f {f.shape} and out {out.shape} are not one frame, or out is read-only")
+    return DenoiseFrame(w, h, ls, fs, os_), L, f, out
+
+
+def denoise_check(frame, opt):
+    """r1_denoise_check: raises R1Error (R1_EINVAL naming the field, R1_ELIMIT at width * height >= 2^31) unless the DenoiseFrame and the
+    DenoiseOpt are ones a denoise accepts.  Pure arithmetic."""
+    _check(lib().r1_denoise_check(C.byref(frame), C.byref(opt)))
+    return True
+
+
+def denoise_host(L, f, opt, out=None):
+    """r1_denoise_host: the filter on the CPU, no device: the definition Renderer.denoise is checked against.  Arguments as there; returns out."""
+    fr, L, f, out = _denoise_target(L, f, out)
+    _check(lib().r1_denoise_host(C.byref(fr), C.byref(opt), C.c_void_p(L.ctypes.data), C.c_void_p(f.ctypes.data), C.c_void_p(out.ctypes.data)))
+    return out
 
 
 def quantise_linear(linear):

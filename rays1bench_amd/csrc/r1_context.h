@@ -1,7 +1,7 @@
 // r1_context.h — what the files that implement the C-ABI on the HIP runtime share: the context, its device buffers, and the steps that
 // one of them defines and another calls.  Private to r1_capi.cpp (context, errors, timing), r1_scene.cpp (scene upload),
 // r1_scene_update.cpp (moving spheres, sphere updates, re-sort), r1_scene_grid.cpp (the grid's upload, regrid), r1_frame.cpp (one frame,
-// step by step), r1_render.cpp (the render entry points) and r1_queries.cpp (ray and path queries); C-linkage functions
+// step by step), r1_render.cpp (the render entry points), r1_queries.cpp (ray and path queries) and r1_denoise.cpp (denoised frames); C-linkage functions
 // shared between files stay in r1_internal.h.
 #ifndef R1_CONTEXT_H
 #define R1_CONTEXT_H
@@ -166,6 +166,8 @@ struct r1_context
     uint32_t cast_cursor_next = 0;
     DevBuf cast_ws;            // r1_cast_rays, r1_trace_rays: one chunk's rays, seeds and records (R1_CAST_CHUNK x 64 bytes)
     int query_occupancy[R1_JOBS][8] = {{0}}; // blocks per CU of the query kernels, [job][structure slot * 2 + big]; follows the tree as `occupancy` does
+    // denoised frames (r1_denoise*, r1_render_denoised*): the filter's records, then what the composed forms keep beside them
+    DevBuf denoise_ws;         // r1_denoise.cpp denoise_layout; nothing here is read or written by a render
     // path queries (r1_trace_rays*): one launch in flight per context
     DevBuf trace_stack;        // the paths' attenuation stack, [max_bounces][threads of the launch] hit indices
     // moving spheres (r1_update_centers*): the refit's tables — topology, uploaded once per r1_set_scene — and its scratch

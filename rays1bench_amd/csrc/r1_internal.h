@@ -16,6 +16,7 @@ struct R1SetArgs;
 struct R1SortArgs; // r1_bvh_sort.h
 struct R1RegridArgs; // r1_grid_fill.h
 struct R1RadixArgs; // r1_device_sort.h
+struct R1DenoiseArgs; // r1_denoise.h
 
 // what r1_sweep_describe says of the sweep's tables besides the arrays
 struct r1_sweep_info
@@ -95,6 +96,11 @@ hipError_t r1_scatter_rays_occupancy(int variant, int big, size_t dyn_lds, int *
 // r1_query_kernels.hip, the feature job (an item is a pixel); variant as for r1_launch_cast
 hipError_t r1_launch_features(const R1FeatureArgs *args, int variant, int big, int blocks, size_t dyn_lds, hipStream_t stream);
 hipError_t r1_features_occupancy(int variant, int big, size_t dyn_lds, int *blocks_per_cu);
+
+// r1_denoise_kernels.hip: the kernels of denoised frames.  staged: tile and halo through LDS (steps <= R1D_STAGE_MAX_STEP, else
+// hipErrorInvalidValue); last: the pass that re-modulates and writes `out`
+hipError_t r1_launch_denoise_prepare(const R1DenoiseArgs *args, hipStream_t stream);
+hipError_t r1_launch_denoise_pass(const R1DenoiseArgs *args, int staged, int last, hipStream_t stream);
 
 // r1_aux_kernels.hip: r1_camera_rays_device
 hipError_t r1_launch_camera_rays(const R1CameraRaysArgs *args, hipStream_t stream);

@@ -35,6 +35,9 @@
 // --features also renders each frame's feature frame through r1_render_features (the window's, with --region): first-hit albedo, normal and
 // depth per pixel, aligned with the frame; -w also writes out_<scene>_albedo.pfm, _normal.pfm and _depth.pfm (depth in all three channels),
 // and the report gains one "<scene> features:" line with the device time.
+// --denoise [ITERATIONS] is --linear, and each frame is also rendered through r1_render_denoised (ITERATIONS a-trous iterations, 3 if not given;
+// normal_power_log2 6, sigma_color 1, sigma_depth 0.1, demodulated): -w also writes out_<scene>_denoised.pfm next to the noisy out_<scene>.pfm,
+// and the report gains one "<scene> denoise:" line with the device time.
 // --backend hip (default) | cpu-step1 | cpu-step12: the reference's two single-thread CPU stages
 // (r1_cpu_backends.cpp) behind the same benchmark(), for the README-style table
 // (README.md:38-84).  Named backends of this program only — never a fallback: with --backend hip and no
@@ -79,6 +82,7 @@ static r1_multi *g_multi = nullptr;     // --gather rccl
 static std::vector<double> g_device_seconds; // per benchmark() call, for the JSON record
 static r1_launch_info g_last_info;
 static float *g_linear = nullptr; // --linear: the frame r1_render_linear fills (page-locked where the device allows it)
+static std::vector<float> g_denoised;       // --denoise: the denoised frame of the last benchmark() call
 static std::vector<r1_feature> g_features; // --features: the feature frame of the last benchmark() call
 
 r1_params frame_params()
@@ -190,7 +194,7 @@ static Frame context_frame(const Scene *scene, Pix *pixels, const r1_params &p, 
     std::vector<std::string> errs(nd);
     r1_adaptive_result adapt_res;
     memset(&adapt_res, 0, sizeof(adapt_res));
-    double features_s = 0.0;
+    double features_s = 0.0, denoise_s = 0.0;
     auto worker = [&](int i) {
         r1_params q = p;
         q.shard = i, q.num_shards = nd;
@@ -237,6 +241,12 @@ static Frame context_frame(const Scene *scene, Pix *pixels, const r1_params &p, 
             rc = r1_render_region(g_ctx[i], &q, &g_opt.window, &pixels[0].r, &rays[i], &dev_s[i]);
         else if (rc == R1_OK)
             rc = r1_render(g_ctx[i], &q, &pixels[0].r, &rays[i], &dev_s[i]);
+        if (rc == R1_OK && g_opt.denoise) // --denoise (one device): the same frame again, rendered, guided and filtered on the device
+        {
+            uint64_t again = 0;
+            g_denoised.assign((size_t)q.width * q.height * 3, 0.0f);
+            rc = r1_render_denoised(g_ctx[i], &q, &g_opt.denoise_opt, g_denoised.data(), &again, &denoise_s);
+        }
         if (rc == R1_OK && g_opt.features) // --features (one device): the feature frame of what was just rendered — the frame, or --region's window
         {
             const r1_region *const win = g_opt.region ? &g_opt.window : nullptr;
@@ -297,6 +307,16 @@ static Frame context_frame(const Scene *scene, Pix *pixels, const r1_params &p, 
                              g_opt.window.width, g_opt.window.height, g_opt.width, g_opt.height,
                              (double)g_opt.window.width * g_opt.window.height / ((double)g_opt.width * g_opt.height),
                              (unsigned long long)((uint64_t)g_opt.window.width * g_opt.window.height * g_opt.spp), (unsigned long long)f.rays);
+    if (g_opt.denoise)
+    {
+        double sum = 0;
+        for (const float v : g_denoised)
+            sum += v;
+        f.lines_after += line("%s denoise: %d iterations, normal power 2^%d, sigma colour %g, sigma depth %g, %s, mean %.6f, device time %.3fms (render, features, filter)\n",
+                              scene_name, g_opt.denoise_opt.iterations, g_opt.denoise_opt.normal_power_log2, (double)g_opt.denoise_opt.sigma_color,
+                              (double)g_opt.denoise_opt.sigma_depth, (g_opt.denoise_opt.flags & R1_DENOISE_DEMODULATE) ? "demodulated" : "not demodulated",
+                              sum / (double)g_denoised.size(), denoise_s * 1e3);
+    }
     if (g_opt.features)
     {
         uint64_t hits = 0, covered = 0;
@@ -351,6 +371,11 @@ RESULT benchmark(Scene *scene, Pix *pixels, bool write_tga, const char *scene_na
         {
             snprintf(filename, sizeof(filename), "out_%s.pfm", scene_name);
             r1_pfm_write_rgb32f(filename, g_opt.width, g_opt.height, g_linear);
+        }
+        if (g_opt.denoise)
+        {
+            snprintf(filename, sizeof(filename), "out_%s_denoised.pfm", scene_name);
+            r1_pfm_write_rgb32f(filename, g_opt.width, g_opt.height, g_denoised.data());
         }
         if (g_opt.features)
         {
@@ -455,6 +480,13 @@ int main(int argc, const char *argv[])
             o.features = true;
             continue;
         }
+        if (strcmp(argv[i], "--denoise") == 0) // (its value is optional: taken where the next argument is a number)
+        {
+            o.denoise = o.linear = true;
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9')
+                o.denoise_opt.iterations = atoi(argv[++i]);
+            continue;
+        }
         if (i + 1 >= argc)
         {
             if (strcmp(argv[i], "--region") == 0) // (ignored, it would render the whole frame)
@@ -550,6 +582,14 @@ int main(int argc, const char *argv[])
     {
         fprintf(stderr, "bad --adaptive MAXDELTA[,MEANQ8] / --min-spp / --pass-spp: needs -1 <= MAXDELTA <= 255, 0 <= MEANQ8 <= 65280, --min-spp and --pass-spp >= 1 "
                         "(both only with --adaptive), the hip backend, one device (no --gather rccl), --variant 0, 2, 4 or 7, and no --passes, --pipeline or --orbit\n");
+        return 1;
+    }
+
+    if (o.denoise && (!one_pass || o.adaptive || o.region || !(tree_variant || o.variant == R1_VARIANT_GRID || o.variant == R1_VARIANT_REFERENCE) ||
+                      o.denoise_opt.iterations < 1 || o.denoise_opt.iterations > R1_DENOISE_MAX_ITERATIONS))
+    {
+        fprintf(stderr, "bad --denoise [ITERATIONS]: needs 1..%d iterations, the hip backend, one device (no --gather rccl), --variant 0, 1, 4 or 7, no --passes, "
+                        "no --adaptive and no --region\n", R1_DENOISE_MAX_ITERATIONS);
         return 1;
     }
 

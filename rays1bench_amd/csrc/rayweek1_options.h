@@ -21,6 +21,9 @@ struct Options
     r1_adaptive adapt = {16, 16, 0, 65280};
     bool linear = false; // --linear: every frame through r1_render_linear, the pixels through r1_quantise_linear; -w also writes out_<scene>.pfm
     bool features = false; // --features: each frame's feature frame too (r1_render_features); -w also writes out_<scene>_albedo.pfm, _normal.pfm, _depth.pfm
+    // --denoise [ITERATIONS]: --linear, and each frame also through r1_render_denoised; -w also writes out_<scene>_denoised.pfm next to out_<scene>.pfm
+    bool denoise = false;
+    r1_denoise_opt denoise_opt = {3, 6, 1.0f, 0.1f, R1_DENOISE_DEMODULATE};
     bool region = false; // --region X,Y,W,H: every frame through r1_render_region; the pixels, the TGA and the counts are the window's
     r1_region window = {0, 0, 0, 0, 0};
     // the demos, each FRAMES frames per scene after the benchmark() runs; 0 = not asked for

@@ -1,0 +1,260 @@
+"""CPU tests of denoised frames (include/rays1.h): the names are declared, exported and bound; r1_denoise_host equals the
+contract re-stated in numpy (tests/denoise_cases.py) bit for bit on rendered and synthetic frames whose classes of input are asserted; pixels
+without a hit keep L's bits; in place; strides with sentinels; both flag values and the ends of every option's range; every refusal with its
+text; the quality bound on the medium scene; the drop-in program's refusals; the census of the new kernels; tools/check_denoise_host.cpp
+under the address and undefined-behaviour sanitizers.  What the device computes is checked in tests/test_gpu_denoise.py.  Every comparison
+of frames is tobytes() equality."""
+import ctypes as C
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import rays1bench_amd as r1
+from rays1bench_amd import binding
+
+import denoise_cases as dc
+import feature_cases as fc
+import linear_cases as lc
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = ("r1_denoise_check", "r1_denoise_host", "r1_denoise_device", "r1_denoise", "r1_render_denoised", "r1_render_denoised_device")
+
+
+def test_every_new_name_is_declared_exported_and_bound():
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "rays1.h")).read(), flags=re.S)
+    names = {s[0] for s in binding.SYMBOLS}
+    for name in NEW:
+        assert re.search(r"\bint\s+" + name + r"\s*\(", hdr), name
+        assert hasattr(r1.lib(), name) and name in names, name
+    assert re.search(r"typedef\s+struct\s+r1_denoise_opt\s*\{\s*int32_t\s+iterations\s*;\s*int32_t\s+normal_power_log2\s*;\s*float\s+sigma_color\s*;\s*float\s+sigma_depth\s*;"
+                     r"\s*uint32_t\s+flags\s*;\s*\}\s*r1_denoise_opt\s*;", hdr)
+    assert re.search(r"typedef\s+struct\s+r1_denoise_frame\s*\{\s*int32_t\s+width\s*,\s*height\s*;\s*int32_t\s+linear_stride\s*,\s*feature_stride\s*,\s*out_stride\s*;\s*\}"
+                     r"\s*r1_denoise_frame\s*;", hdr)
+    assert re.search(r"#define R1_DENOISE_DEMODULATE 1u", hdr) and binding.DENOISE_DEMODULATE == 1
+    assert re.search(r"#define R1_ABI_VERSION 4\b", hdr) and r1.lib().r1_abi_version() == 4
+    assert C.sizeof(binding.DenoiseOpt) == 20 and C.sizeof(binding.DenoiseFrame) == 20
+    for m in ("denoise", "denoise_device", "render_denoised", "render_denoised_device"):
+        assert callable(getattr(binding.Renderer, m, None)), m
+    assert callable(getattr(binding, "denoise_host", None)) and callable(getattr(binding, "denoise_check", None))
+
+
+# ---- the host form against the numpy form -----------------------------------------------------------------------------------------------------
+
+# every case with the measured options, without demodulation, and at both ends of every option's range
+OPTION_SETS = {"measured": {}, "plain": dict(flags=0), "lowest": dict(iterations=1, normal_power_log2=0, sigma_color=1e-30, sigma_depth=1e-30),
+               "highest": dict(iterations=8, normal_power_log2=10, sigma_color=3e38, sigma_depth=3e38, flags=0), "sharp": dict(normal_power_log2=10, sigma_color=1e-3),
+               "flat": dict(normal_power_log2=0, sigma_depth=1e3)}
+
+
+@pytest.mark.parametrize("options", list(OPTION_SETS))
+@pytest.mark.parametrize("name", list(dc.RENDERED) + list(dc.SYNTHETIC))
+def test_host_form_equals_the_numpy_form(name, options):
+    L, f, it = dc.inputs(name)
+    kw = dict(OPTION_SETS[options])
+    kw.setdefault("iterations", it)
+    got = binding.denoise_host(L, f, dc.opt(**kw))
+    want = dc.numpy_denoise(L, f, dc.opt(**kw))
+    assert got.dtype == np.float32 and got.shape == L.shape
+    assert got.tobytes() == want.tobytes()
+    sky = f["hits"] == 0
+    assert got[sky].tobytes() == L[sky].tobytes()  # every pixel without a hit has L's bits
+    if name != "1x1" and options in ("measured", "plain"):
+        assert (got[~sky] != L[~sky]).any(axis=-1).mean() > 0.5  # (and the filter is no identity)
+
+
+@pytest.mark.parametrize("name", ["37x21", "70x40"])
+def test_synthetic_frames_hold_every_class_of_input(name):
+    L, f, _ = dc.inputs(name)
+    cls = dc.classes(L, f, k=6)
+    print(name, cls)
+    for what, least in (("no-hit 3x3 blocks", 2), ("hit pixels with a zero normal", 3), ("albedo 0", 10), ("albedo in (0, 1/256)", 10), ("equal depths", 10),
+                        ("depths 1000x apart", 10), ("colour steps >= 1e4", 10), ("c^(2^k) subnormal", 5), ("c^(2^k) zero from c > 0", 5)):
+        assert cls[what] >= least, (what, cls)
+
+
+def test_a_5x3_frame_with_4_iterations_has_every_non_centre_tap_of_the_last_pass_off_the_image():
+    """step 8 on 5 x 3: only the centre tap is on the image, next = (h * cur) / h with h = 9/64"""
+    L, f, it = dc.inputs("5x3")
+    assert it == 4 and (1 << (it - 1)) > max(f.shape) - 1
+    for flags in (0, binding.DENOISE_DEMODULATE):
+        assert binding.denoise_host(L, f, dc.opt(iterations=4, flags=flags)).tobytes() == dc.numpy_denoise(L, f, dc.opt(iterations=4, flags=flags)).tobytes()
+
+
+def test_the_rendered_cases_have_both_kinds_of_pixel():
+    for name in dc.RENDERED:
+        L, f, _ = dc.inputs(name)
+        sky = f["hits"] == 0
+        assert sky.sum() >= 10 and (~sky).sum() >= 10
+        assert L[sky].tobytes() == f["albedo"][sky].tobytes()  # (the link §4.38 gives: the two frames are of one render)
+
+
+@pytest.mark.parametrize("name", ["large", "70x40"])
+def test_out_aliased_to_L_equals_the_result_without_aliasing(name):
+    L, f, _ = dc.inputs(name)
+    for flags in (0, binding.DENOISE_DEMODULATE):
+        buf = L.copy()
+        got = binding.denoise_host(buf, f, dc.opt(flags=flags), out=buf)
+        assert got is buf and buf.tobytes() == dc.host_result(name, iterations=3, flags=flags).tobytes()
+
+
+@pytest.mark.parametrize("name", ["medium", "37x21"])
+def test_strides_with_sentinel_bytes_between_the_rows_stay_untouched(name):
+    L, f, _ = dc.inputs(name)
+    h, w = f.shape
+    Lv, Lbuf = dc.strided(L, w + 3)
+    fv, fbuf = dc.strided(f, w + 1)
+    ov, obuf = dc.strided(np.zeros_like(L), w + 5)
+    before_L, before_f = Lbuf.tobytes(), fbuf.tobytes()
+    got = binding.denoise_host(Lv, fv, dc.opt(), out=ov)
+    assert got.tobytes() == dc.host_result(name, iterations=3).tobytes()
+    assert (obuf[:, w:].view(np.uint8) == dc.PREFILL).all()
+    assert Lbuf.tobytes() == before_L and fbuf.tobytes() == before_f
+    # in place through a strided view: the bytes between L's rows stay
+    binding.denoise_host(Lv, fv, dc.opt(), out=Lv)
+    assert Lv.tobytes() == got.tobytes() and (Lbuf[:, w:].view(np.uint8) == dc.PREFILL).all()
+
+
+# ---- refusals -----------------------------------------------------------------------------------------------------------------------------------
+
+W, H = 37, 21
+BAD_FRAMES = [((0, H, 0, 0, 0), binding.R1_EINVAL, "width"), ((W, 0, 0, 0, 0), binding.R1_EINVAL, "height"), ((-3, H, 0, 0, 0), binding.R1_EINVAL, "width"),
+              ((65536, 32768, 0, 0, 0), binding.R1_ELIMIT, "2^31"), ((W, H, W - 1, 0, 0), binding.R1_EINVAL, "linear_stride"),
+              ((W, H, 0, W - 1, 0), binding.R1_EINVAL, "feature_stride"), ((W, H, 0, 0, -1), binding.R1_EINVAL, "out_stride")]
+BAD_OPTIONS = [(dict(iterations=0), "iterations"), (dict(iterations=9), "iterations"), (dict(normal_power_log2=-1), "normal_power_log2"),
+               (dict(normal_power_log2=11), "normal_power_log2"), (dict(sigma_color=0.0), "sigma_color"), (dict(sigma_color=-1.0), "sigma_color"),
+               (dict(sigma_color=float("inf")), "sigma_color"), (dict(sigma_color=float("nan")), "sigma_color"), (dict(sigma_depth=0.0), "sigma_depth"),
+               (dict(sigma_depth=float("inf")), "sigma_depth"), (dict(sigma_depth=float("nan")), "sigma_depth"), (dict(flags=2), "flags"), (dict(flags=3), "flags")]
+
+
+def test_every_refusal_with_its_text_and_nothing_written():
+    Lb = r1.lib()
+    L, f, _ = dc.inputs("37x21")
+    out = np.frombuffer(bytes([dc.PREFILL]) * (W * H * 12), np.float32).copy()
+    pL, pf, po = C.c_void_p(L.ctypes.data), C.c_void_p(f.ctypes.data), C.c_void_p(out.ctypes.data)
+    good_fr, good_o = binding.DenoiseFrame(W, H, 0, 0, 0), dc.opt()
+    assert binding.denoise_check(good_fr, good_o) is True
+    for fields, code, says in BAD_FRAMES:
+        fr = binding.DenoiseFrame(*fields)
+        for rc in (Lb.r1_denoise_check(C.byref(fr), C.byref(good_o)), Lb.r1_denoise_host(C.byref(fr), C.byref(good_o), pL, pf, po)):
+            assert rc == code and says in Lb.r1_last_error().decode(), (fields, rc, Lb.r1_last_error())
+        with pytest.raises(binding.R1Error) as e:
+            binding.denoise_check(fr, good_o)
+        assert e.value.code == code
+    for kw, says in BAD_OPTIONS:
+        o = dc.opt(**kw)
+        for rc in (Lb.r1_denoise_check(C.byref(good_fr), C.byref(o)), Lb.r1_denoise_host(C.byref(good_fr), C.byref(o), pL, pf, po)):
+            assert rc == binding.R1_EINVAL and says in Lb.r1_last_error().decode(), (kw, rc, Lb.r1_last_error())
+    assert Lb.r1_denoise_check(None, C.byref(good_o)) == binding.R1_EINVAL and "frame is NULL" in Lb.r1_last_error().decode()
+    assert Lb.r1_denoise_check(C.byref(good_fr), None) == binding.R1_EINVAL and "options is NULL" in Lb.r1_last_error().decode()
+    for args, says in (((None, pf, po), "L is NULL"), ((pL, None, po), "f is NULL"), ((pL, pf, None), "out is NULL")):
+        assert Lb.r1_denoise_host(C.byref(good_fr), C.byref(good_o), *args) == binding.R1_EINVAL and says in Lb.r1_last_error().decode()
+    assert (out.view(np.uint8) == dc.PREFILL).all()
+    # the ends of the ranges are accepted
+    for kw in (dict(iterations=1), dict(iterations=8), dict(normal_power_log2=0), dict(normal_power_log2=10), dict(sigma_color=1e-45), dict(sigma_depth=3.4e38), dict(flags=0)):
+        assert binding.denoise_check(good_fr, dc.opt(**kw))
+    assert binding.denoise_check(binding.DenoiseFrame(46340, 46340, 46340, 50000, 0), good_o)  # 2 147 395 600 pixels: below 2^31
+
+
+def test_the_python_layer_refuses_arrays_that_are_not_one_frame():
+    L, f, _ = dc.inputs("37x21")
+    for bad in ((L.astype(np.float64), f, None), (L[:, :, :2], f, None), (L, f[:, 1:], None), (L, f, np.zeros((H, W + 1, 3), np.float32)), (L[:, ::2], f[:, ::2], None)):
+        with pytest.raises(binding.R1Error):
+            binding.denoise_host(*bad[:2], dc.opt(), out=bad[2])
+
+
+def test_device_forms_refuse_a_null_context_first_without_a_device():
+    Lb = r1.lib()
+    p = fc.params("medium")
+    for call in (lambda: Lb.r1_denoise_device(None, None, None, None, None, None, None), lambda: Lb.r1_denoise(None, None, None, None, None, None, None),
+                 lambda: Lb.r1_render_denoised(None, C.byref(p), None, None, None, None), lambda: Lb.r1_render_denoised_device(None, None, None, None, None, None)):
+        assert call() == binding.R1_EINVAL and "ctx is NULL" in Lb.r1_last_error().decode()
+
+
+# ---- quality ------------------------------------------------------------------------------------------------------------------------------------
+
+
+@pytest.fixture(scope="module")
+def medium_reference():
+    sa = lc.scene_arrays("medium", 160, 100)
+    ref, _ = binding.render_linear_host(lc.cscene(sa), lc.ccamera(sa), r1.make_params(160, 100, 512, 777))
+    return sa, ref
+
+
+@pytest.mark.parametrize("spp", [1, 4])
+def test_three_iterations_cut_the_error_of_a_noisy_medium_frame_to_three_quarters(medium_reference, spp):
+    """RMSE(out) <= 0.75 * RMSE(noisy) against 512 spp at seed 777; measured here 0.4234 (1 spp) and 0.5615 (4 spp), as the numpy prototype of the
+    contract did (0.42, 0.56)."""
+    sa, ref = medium_reference
+    p = r1.make_params(160, 100, spp, 4242)
+    L, _ = binding.render_linear_host(lc.cscene(sa), lc.ccamera(sa), p)
+    f = binding.render_features_host(lc.cscene(sa), lc.ccamera(sa), p)
+    out = binding.denoise_host(L, f, dc.opt(iterations=3, normal_power_log2=6, sigma_color=1.0, sigma_depth=0.1, flags=binding.DENOISE_DEMODULATE))
+    noisy, clean = dc.rmse(L, ref), dc.rmse(out, ref)
+    print(f"medium 160x100x{spp}: RMSE noisy {noisy:.5f}, denoised {clean:.5f}, ratio {clean / noisy:.4f}")
+    assert clean <= 0.75 * noisy
+
+
+# ---- the drop-in program --------------------------------------------------------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("args", [["--denoise", "--passes", "2"], ["--denoise", "--adaptive", "24"], ["--denoise", "--devices", "2"], ["--denoise", "0"], ["--denoise", "9"],
+                                  ["--denoise", "--backend", "cpu-step12"], ["--denoise", "3", "--gather", "rccl"], ["--variant", "2", "--denoise"],
+                                  ["--variant", "6", "--denoise", "2"], ["--denoise", "--region", "0,0,4,4"]], ids=lambda a: "_".join(a).replace("--", ""))
+def test_program_refuses_denoise_with_what_it_cannot_serve_before_touching_a_device(tmp_path, args):
+    exe = os.path.join(ROOT, "rays1bench_amd", "lib", "rayweek1_hip")
+    out = subprocess.run([exe, "--width", "32", "--height", "16", "--spp", "8", *args], cwd=tmp_path, capture_output=True, timeout=120)
+    assert out.returncode == 1, (out.returncode, out.stderr)
+    assert b"--denoise" in out.stderr
+    assert b"cannot create HIP context" not in out.stderr
+    assert not any(tmp_path.iterdir())  # (nothing rendered, nothing written)
+
+
+# ---- the built library ------------------------------------------------------------------------------------------------------------------------
+
+
+def test_census_of_the_denoise_kernels():
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import kernel_meta
+    lib = os.path.join(ROOT, "rays1bench_amd", "lib", "librays1.so")
+    if not (os.path.exists(lib) and os.path.exists(kernel_meta.LLVM + "/llvm-objdump")):
+        pytest.skip("no library / no LLVM tools")
+    k = kernel_meta.collect(lib)
+    own = sorted(n for n in k if "r1_denoise" in n)
+    assert len(own) == 5, own
+    assert sum("r1_denoise_pass_kernel" in n for n in own) == 4 and sum("r1_denoise_prepare_kernel" in n for n in own) == 1
+    for name in own:
+        a = k[name]
+        print(name, {x: a[x] for x in ("vgpr", "sgpr", "sgpr_spill", "lane_moves", "insts", "lds")})  # (recorded in DESIGN.md §4.39)
+        assert a["v_mfma"] == 0 and a["flat_load"] == 0 and a["flat_store"] == 0, (name, a)
+        assert int(a["scratch"]) == 0 and a["scratch_insts"] == 0 and int(a["vgpr_spill"]) == 0 and int(a["sgpr_spill"]) == 0, (name, a)
+        assert int(a["vgpr"]) <= 64, (name, a["vgpr"])  # eight waves per SIMD fit
+        staged = "kernelILb1E" in name or "kernel<true" in name  # (mangled or demangled)
+        assert int(a["lds"]) == (20480 if staged else 0), (name, a["lds"])  # (32 + 8) x (8 + 8) records of 32 bytes: eight workgroups a CU
+
+
+# ---- the stand-alone program ------------------------------------------------------------------------------------------------------------------
+
+
+@pytest.fixture(scope="module")
+def check_program(tmp_path_factory):
+    """tools/check_denoise_host.cpp built with the host source it drives, under the address and undefined-behaviour sanitizers: a stand-alone
+    program of its own, no GPU, nothing loaded into another process."""
+    out = str(tmp_path_factory.mktemp("denoise_host") / "check_denoise_host")
+    src = [os.path.join(ROOT, "tools", "check_denoise_host.cpp"), os.path.join(ROOT, "rays1bench_amd", "csrc", "r1_denoise_host.cpp")]
+    inc = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include")
+    assert os.path.isdir(inc), "the HIP headers are needed to compile the library's host sources"
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off",
+                           "-D__HIP_PLATFORM_AMD__", "-I" + inc] + src + ["-o", out])
+    return out
+
+
+def test_stand_alone_program_under_the_sanitizers(check_program):
+    out = subprocess.run([check_program], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    assert "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr
+    for says in ("every value the contract's under 5 sets of options", "strides 40, 38, 42", "refusals wrote nothing"):
+        assert says in out.stdout
