@@ -606,6 +606,103 @@ int r1_render_denoised(r1_context *ctx, const r1_params *params, const r1_denois
 /* The same into DEVICE memory (d_rgb_f32 4-byte aligned, d_num_rays 8-byte aligned), enqueued on `hip_stream`, waits for nothing. */
 int r1_render_denoised_device(r1_context *ctx, const r1_params *params, const r1_denoise_opt *opt, void *d_rgb_f32, void *d_num_rays, void *hip_stream);
 
+/* ---- variance frames: the variance of every pixel's mean beside its linear value ---- */
+
+/* What a variance-guided filter, an error-driven sampling rule or a confidence display wants beside a linear frame: how far each pixel's
+ * mean can be trusted.  The contract — plain fp32, every operation correctly rounded, in the order written, nothing fused.  For pixel
+ * (x, y), channel c, n = spp and the pixel's sample records x_s (r1_render_samples' records):
+ *   L_c    exactly r1_render_linear's value: S = 0.0f; S += x_s,c for s = 0 .. n - 1; L = S * (float)(1.0f / n)
+ *   D_c    D = 0.0f; then for s = 0 .. n - 1: d = x_s,c - L_c; D = D + d * d — a second walk over the same records, in sample order
+ *   var_c  n > 1 ? D_c * (1.0f / ((float)n * (float)(n - 1))) : 0.0f
+ * var is the unbiased estimate of the variance of the pixel's MEAN (the sample variance over n).  It is never negative; for n = 1 it is
+ * +0.0f, bits 0, whatever the records hold — one sample carries no variance.  A record that is not finite makes its pixel's var NaN or
+ * infinite by IEEE rules and touches no other pixel. */
+typedef struct r1_moment
+{
+    float var[3];
+    uint32_t samples; /* n: the samples behind L and var */
+} r1_moment;
+
+/* A variance frame has r1_render's layout with 16-byte records for pixels, as a feature frame has: row-major, row 0 = bottom row, dense,
+ * width * height * 16 bytes.  The three forms below follow r1_render_linear, r1_render_linear_device and r1_render_linear_host in every
+ * rule: whole frames only (num_shards != 1: R1_EINVAL), every variant r1_render_linear accepts, the same ray count, PIXEL mode does not
+ * apply, a progressive accumulation is left alone, r1_last_launch_info and r1_last_timing describe the frame.  rgb_out is r1_render_linear's
+ * frame bit for bit.  The cost is no further launch: the one that closes a linear frame is replaced by one that walks the records twice and
+ * stores both outputs, inside the timed span.  A refused call enqueues nothing.
+ * Not provided: variance from a progressive or adaptive accumulation, of a region, of a frame in flight (r1_render_linear_async), of a
+ * batch, a shard or an r1_multi frame — their accumulators hold sums only, and a second moment wants the records of all samples at once. */
+
+/* Synchronous; rgb_out and moments_out are host memory (page-locked memory, moments_out 16-byte aligned, is written by the launch itself);
+ * num_rays_out and device_seconds_out may be NULL. */
+int r1_render_moments(r1_context *ctx, const r1_params *params, float *rgb_out, r1_moment *moments_out, uint64_t *num_rays_out,
+                      double *device_seconds_out);
+
+/* Into DEVICE memory: d_rgb_f32 (width * height * 3 floats, 4-byte aligned), d_moments (width * height records, 16-byte aligned),
+ * d_num_rays (one uint64, 8-byte aligned); R1_EINVAL otherwise.  Everything is enqueued on `hip_stream` (NULL = the context's stream),
+ * nothing is waited for. */
+int r1_render_moments_device(r1_context *ctx, const r1_params *params, void *d_rgb_f32, void *d_moments, void *d_num_rays, void *hip_stream);
+
+/* The CPU form, no device: r1_render_linear_host's frame and ray count and the records above.  Slow; it is what the other two are checked
+ * against.  num_rays_out may be NULL. */
+int r1_render_moments_host(const r1_scene *scene, const r1_camera *camera, const r1_params *params, float *rgb_out, r1_moment *moments_out,
+                           uint64_t *num_rays_out);
+
+/* ---- variance-guided denoised frames: the a-trous filter with a colour tolerance that follows each pixel's noise ---- */
+
+/* The "denoised frames" contract above with these changes and no others.  V is the variance frame of L (r1_render_moments: var of the
+ * pixel's mean), a_c the prepare step's albedo divisor, K3 = {1/4, 1/2, 1/4}.  Plain fp32, one correctly rounded operation per step, in
+ * the order written.
+ *   prepare     v = surf ? (V_r / (a_r * a_r) + V_g / (a_g * a_g)) + V_b / (a_b * a_b) : 0 — the variance of the demodulated value in the
+ *               metric dc uses.  V of a pixel without a hit is never read into any result.
+ *   iteration i, surf pixel p, before the taps: G = 0, K = 0; dy = -1 .. 1 in the outer loop, dx = -1 .. 1 in the inner one, q = p + (dx, dy)
+ *               — one pixel apart at every step —, a tap off the image or not surf is skipped; k = K3[dy + 1] * K3[dx + 1];
+ *               G = G + k * v_q; K = K + k; then g = G / K (K is at least 1/4, the centre's)
+ *   colour term sc2 = sigma_color * sigma_color in every iteration (no 2^-i: the variance shrinks through the passes by itself);
+ *               den = sc2 * g + variance_floor; xc = dc / den
+ *   the sums    also T = T + (w * w) * v_q for every tap taken, the centre included with w = h; next_c = S_c / W; v_next = T / (W * W)
+ * The end step, the normal and depth terms, the tap order and what a pixel without a hit keeps are unchanged.
+ * What to choose: normal_power_log2 6, sigma_depth 0.1 and DEMODULATE as above, sigma_color 2 and variance_floor 1e-4, three iterations.
+ * On the medium scene that cuts the error against a converged frame to 0.52 / 0.53 / 0.61 of the noisy frame's at 2 / 4 / 16 spp where the
+ * fixed tolerance reaches 0.47 / 0.56 / 0.89, and five iterations no longer make a 16-spp frame worse (0.64 against 1.07); at 1 spp there
+ * is no variance: use r1_denoise there (DESIGN.md 4.40 has the table). */
+typedef struct r1_denoise_guided_opt
+{
+    r1_denoise_opt base;
+    float variance_floor; /* > 0, finite */
+    uint32_t reserved;    /* 0 */
+} r1_denoise_guided_opt;
+
+/* The four images of a call; strides in PIXELS (three floats of L and out, one record of f and of V), 0 means width. */
+typedef struct r1_denoise_guided_frame
+{
+    int32_t width, height;
+    int32_t linear_stride, feature_stride, moment_stride, out_stride;
+} r1_denoise_guided_frame;
+
+/* Pure arithmetic: r1_denoise_check's rules for the fields the structs share, then moment_stride, variance_floor and reserved; R1_EINVAL
+ * names the field. */
+int r1_denoise_guided_check(const r1_denoise_guided_frame *frame, const r1_denoise_guided_opt *opt);
+
+/* The definition, on the CPU.  `out` may be L; f and V must not overlap out. */
+int r1_denoise_guided_host(const r1_denoise_guided_frame *frame, const r1_denoise_guided_opt *opt, const float *L, const r1_feature *f,
+                           const r1_moment *V, float *out);
+
+/* On DEVICE memory: r1_denoise_device's rules (d_V 16-byte aligned as d_f; 56 bytes a pixel of the context's workspace; one denoise per
+ * context in flight; no state a render reads changes).  Refusals: ctx NULL; the check; pointers and alignment.  Nothing is enqueued then. */
+int r1_denoise_guided_device(r1_context *ctx, const r1_denoise_guided_frame *frame, const r1_denoise_guided_opt *opt, const void *d_L,
+                             const void *d_f, const void *d_V, void *d_out, void *hip_stream);
+
+/* On HOST memory, synchronous; device_seconds_out (may be NULL): the filter alone. */
+int r1_denoise_guided(r1_context *ctx, const r1_denoise_guided_frame *frame, const r1_denoise_guided_opt *opt, const float *L,
+                      const r1_feature *f, const r1_moment *V, float *out, double *device_seconds_out);
+
+/* r1_render_moments_device + r1_render_features_device + the guided filter on one stream: r1_render_denoised's rules, and params->spp < 2
+ * is R1_EINVAL naming spp — one sample carries no variance; use r1_render_denoised at 1 spp. */
+int r1_render_denoised_guided(r1_context *ctx, const r1_params *params, const r1_denoise_guided_opt *opt, float *rgb_out,
+                              uint64_t *num_rays_out, double *device_seconds_out);
+int r1_render_denoised_guided_device(r1_context *ctx, const r1_params *params, const r1_denoise_guided_opt *opt, void *d_rgb_f32,
+                                     void *d_num_rays, void *hip_stream);
+
 /* Pipelined form of r1_render — frames in flight whose results land on the HOST.  The reference times
  * dispatch -> pixels + ray count on the host (rayweek1.cpp:848 -> :891) for ONE frame and waits; a caller that
  * renders frame after frame (main's `-n` runs, rayweek1.cpp:969-984) can keep several in flight instead: the call

@@ -112,6 +112,22 @@ class DenoiseFrame(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("linear_stride", C.c_int32), ("feature_stride", C.c_int32), ("out_stride", C.c_int32)]
 
 
+class DenoiseGuidedOpt(C.Structure):
+    """r1_denoise_guided_opt: a DenoiseOpt, variance_floor > 0 and finite, reserved 0."""
+    _fields_ = [("base", DenoiseOpt), ("variance_floor", C.c_float), ("reserved", C.c_uint32)]
+
+
+class DenoiseGuidedFrame(C.Structure):
+    """r1_denoise_guided_frame: the size of the four images and the pixels between two rows of each (0 = width)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("linear_stride", C.c_int32), ("feature_stride", C.c_int32), ("moment_stride", C.c_int32),
+                ("out_stride", C.c_int32)]
+
+
+def make_denoise_guided_opt(iterations=3, normal_power_log2=6, sigma_color=2.0, sigma_depth=0.1, flags=DENOISE_DEMODULATE, variance_floor=1e-4, reserved=0):
+    """The options of the variance-guided filter; the defaults are the ones DESIGN.md §4.40 chose on the medium scene."""
+    return DenoiseGuidedOpt(DenoiseOpt(int(iterations), int(normal_power_log2), float(sigma_color), float(sigma_depth), int(flags)), float(variance_floor), int(reserved))
+
+
 def make_denoise_opt(iterations=3, normal_power_log2=6, sigma_color=1.0, sigma_depth=0.1, flags=DENOISE_DEMODULATE):
     """The options DESIGN.md §4.39 measured at 1-4 spp; at 16 spp and more, iterations=1."""
     return DenoiseOpt(int(iterations), int(normal_power_log2), float(sigma_color), float(sigma_depth), int(flags))
@@ -143,6 +159,8 @@ SCATTER_UNIT_DIRECTIONS = 1
 MAT_LAMBERTIAN, MAT_METAL, MAT_DIELECTRIC, MAT_NONE = 0, 1, 2, 255
 # r1_feature (32 bytes): a pixel of a feature frame
 FEATURE_DTYPE = np.dtype([("albedo", np.float32, 3), ("depth", np.float32), ("normal", np.float32, 3), ("hits", np.uint32)])
+# r1_moment (16 bytes): a pixel of a variance frame
+MOMENT_DTYPE = np.dtype([("var", np.float32, 3), ("samples", np.uint32)])
 
 
 def make_params(width, height, spp, seed=10001, max_bounces=50, tile_w=32, tile_h=32, shard=0, num_shards=1, variant=0):
@@ -275,6 +293,9 @@ SYMBOLS = [
     ("r1_render_adaptive_linear", C.c_int, [_ctx, C.POINTER(Params), C.POINTER(Adaptive), _f32p, _u64p, C.POINTER(TileReport), C.POINTER(AdaptiveResult)]),
     ("r1_quantise_linear", C.c_int, [_f32p, C.c_size_t, _u8p]),
     ("r1_render_linear_host", C.c_int, [C.POINTER(CScene), C.POINTER(CCamera), C.POINTER(Params), _f32p, _u64p]),
+    ("r1_render_moments", C.c_int, [_ctx, C.POINTER(Params), _f32p, C.c_void_p, _u64p, _dblp]),
+    ("r1_render_moments_device", C.c_int, [_ctx, C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("r1_render_moments_host", C.c_int, [C.POINTER(CScene), C.POINTER(CCamera), C.POINTER(Params), _f32p, C.c_void_p, _u64p]),
     ("r1_region_check", C.c_int, [C.POINTER(Params), C.POINTER(Region)]),
     ("r1_render_region", C.c_int, [_ctx, C.POINTER(Params), C.POINTER(Region), C.c_void_p, _u64p, _dblp]),
     ("r1_render_region_samples", C.c_int, [_ctx, C.POINTER(Params), C.POINTER(Region), C.c_void_p, _u64p, _f32p]),
@@ -290,6 +311,12 @@ SYMBOLS = [
     ("r1_denoise", C.c_int, [_ctx, C.POINTER(DenoiseFrame), C.POINTER(DenoiseOpt), C.c_void_p, C.c_void_p, C.c_void_p, _dblp]),
     ("r1_render_denoised", C.c_int, [_ctx, C.POINTER(Params), C.POINTER(DenoiseOpt), C.c_void_p, _u64p, _dblp]),
     ("r1_render_denoised_device", C.c_int, [_ctx, C.POINTER(Params), C.POINTER(DenoiseOpt), C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("r1_denoise_guided_check", C.c_int, [C.POINTER(DenoiseGuidedFrame), C.POINTER(DenoiseGuidedOpt)]),
+    ("r1_denoise_guided_host", C.c_int, [C.POINTER(DenoiseGuidedFrame), C.POINTER(DenoiseGuidedOpt), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("r1_denoise_guided_device", C.c_int, [_ctx, C.POINTER(DenoiseGuidedFrame), C.POINTER(DenoiseGuidedOpt), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("r1_denoise_guided", C.c_int, [_ctx, C.POINTER(DenoiseGuidedFrame), C.POINTER(DenoiseGuidedOpt), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _dblp]),
+    ("r1_render_denoised_guided", C.c_int, [_ctx, C.POINTER(Params), C.POINTER(DenoiseGuidedOpt), C.c_void_p, _u64p, _dblp]),
+    ("r1_render_denoised_guided_device", C.c_int, [_ctx, C.POINTER(Params), C.POINTER(DenoiseGuidedOpt), C.c_void_p, C.c_void_p, C.c_void_p]),
     ("r1_pfm_write_rgb32f", C.c_int, [C.c_char_p, C.c_int32, C.c_int32, _f32p]),
     ("r1_tga_write_rgb24", C.c_int, [C.c_char_p, C.c_int32, C.c_int32, _u8p]),
     ("r1_log_results", C.c_int, [C.c_char_p, C.c_char_p, _dblp, _u64p, C.c_int32]),
@@ -600,6 +627,21 @@ class Renderer:
         _check(lib().r1_render_linear(self._c, C.byref(params), img.ctypes.data_as(_f32p), C.byref(rays), C.byref(secs)))
         return img, int(rays.value), float(secs.value)
 
+    def render_moments(self, params):
+        """r1_render_moments: the linear frame and the variance of every pixel's mean.  Returns (float32 (height, width, 3) — render_linear's
+        frame bit for bit —, MOMENT_DTYPE array (height, width), ray count, device seconds)."""
+        img = np.zeros((params.height, params.width, 3), np.float32)
+        mom = np.zeros((params.height, params.width), MOMENT_DTYPE)
+        rays, secs = C.c_uint64(), C.c_double()
+        _check(lib().r1_render_moments(self._c, C.byref(params), img.ctypes.data_as(_f32p), C.c_void_p(mom.ctypes.data), C.byref(rays), C.byref(secs)))
+        return img, mom, int(rays.value), float(secs.value)
+
+    def render_moments_device(self, params, d_rgb_f32_ptr, d_moments_ptr, d_rays_ptr, stream_ptr=None):
+        """r1_render_moments_device: the same into device memory (width * height * 3 floats; width * height 16-byte records, 16-byte
+        aligned; one uint64); enqueued on stream_ptr, waits for nothing."""
+        _check(lib().r1_render_moments_device(self._c, C.byref(params), C.c_void_p(d_rgb_f32_ptr or None), C.c_void_p(d_moments_ptr or None),
+                                              C.c_void_p(d_rays_ptr or None), _stream_arg(stream_ptr)))
+
     def render_region(self, params, region, out=None):
         """r1_render_region: window `region` = (x0, y0, width, height) of the frame `params` describes, byte for byte the crop of
         render(params).  Returns (uint8 (height, width, 3) of the region, ray count of the region's samples, device seconds).  `out`: a
@@ -683,6 +725,36 @@ class Renderer:
         """r1_render_denoised_device: the same into device memory (width * height * 3 floats, and one uint64); waits for nothing."""
         _check(lib().r1_render_denoised_device(self._c, C.byref(params), C.byref(opt), C.c_void_p(d_rgb_f32_ptr or None), C.c_void_p(d_rays_ptr or None),
                                                _stream_arg(stream_ptr)))
+
+    def denoise_guided(self, L, f, V, opt, out=None):
+        """r1_denoise_guided: the variance-guided filter of L guided by f and the variance frame V (MOMENT_DTYPE (height, width)), host memory,
+        synchronous; arrays and `out` as for denoise.  Returns (out, device seconds of the filter)."""
+        fr, L, f, V, out = _denoise_guided_target(L, f, V, out)
+        secs = C.c_double()
+        _check(lib().r1_denoise_guided(self._c, C.byref(fr), C.byref(opt), C.c_void_p(L.ctypes.data), C.c_void_p(f.ctypes.data), C.c_void_p(V.ctypes.data),
+                                       C.c_void_p(out.ctypes.data), C.byref(secs)))
+        return out, secs.value
+
+    def denoise_guided_device(self, width, height, opt, d_L_ptr, d_f_ptr, d_V_ptr, d_out_ptr, stream_ptr=None, linear_stride=0, feature_stride=0, moment_stride=0,
+                              out_stride=0):
+        """r1_denoise_guided_device: the same on device memory (d_L and d_out 4-byte aligned, d_f and d_V 16-byte aligned, d_out may be d_L;
+        strides in pixels, 0 = width); enqueued on stream_ptr, waits for nothing.  One denoise per context in flight."""
+        fr = DenoiseGuidedFrame(int(width), int(height), int(linear_stride), int(feature_stride), int(moment_stride), int(out_stride))
+        _check(lib().r1_denoise_guided_device(self._c, C.byref(fr), C.byref(opt), C.c_void_p(d_L_ptr or None), C.c_void_p(d_f_ptr or None), C.c_void_p(d_V_ptr or None),
+                                              C.c_void_p(d_out_ptr or None), _stream_arg(stream_ptr)))
+
+    def render_denoised_guided(self, params, opt):
+        """r1_render_denoised_guided: the frame rendered with its variance frame, its feature frame and the guided filter, on the device.
+        Returns (float32 (height, width, 3), ray count, device seconds of all three).  spp >= 2."""
+        img = np.zeros((max(params.height, 1), max(params.width, 1), 3), np.float32)
+        rays, secs = C.c_uint64(), C.c_double()
+        _check(lib().r1_render_denoised_guided(self._c, C.byref(params), C.byref(opt), C.c_void_p(img.ctypes.data), C.byref(rays), C.byref(secs)))
+        return img, int(rays.value), secs.value
+
+    def render_denoised_guided_device(self, params, opt, d_rgb_f32_ptr, d_rays_ptr, stream_ptr=None):
+        """r1_render_denoised_guided_device: the same into device memory (width * height * 3 floats, and one uint64); waits for nothing."""
+        _check(lib().r1_render_denoised_guided_device(self._c, C.byref(params), C.byref(opt), C.c_void_p(d_rgb_f32_ptr or None), C.c_void_p(d_rays_ptr or None),
+                                                      _stream_arg(stream_ptr)))
 
     def render_linear_async(self, params, frame_ptr, rays_ptr, stream_ptr=None):
         """r1_render_linear_async: enqueue one linear frame (throughput kernels); width * height * 3 floats land at `frame_ptr` and the
@@ -1293,6 +1365,16 @@ def render_linear_host(cscene, ccamera, params):
     return img, int(rays.value)
 
 
+def render_moments_host(cscene, ccamera, params):
+    """r1_render_moments_host: the linear frame and its variance frame on the CPU (no device; slow) — what Renderer.render_moments is checked
+    against.  Returns (float32 (height, width, 3), MOMENT_DTYPE array (height, width), ray count)."""
+    img = np.zeros((params.height, params.width, 3), np.float32)
+    mom = np.zeros((params.height, params.width), MOMENT_DTYPE)
+    rays = C.c_uint64()
+    _check(lib().r1_render_moments_host(C.byref(cscene), C.byref(ccamera), C.byref(params), img.ctypes.data_as(_f32p), C.c_void_p(mom.ctypes.data), C.byref(rays)))
+    return img, mom, int(rays.value)
+
+
 def _region_target(region, out, dtype):
     """(Region, array) of a host-memory region render: a new dense (height, width, 3) array, or the caller's `out` — an array or a view of that
     shape whose pixels are contiguous and whose rows lie a whole number of pixels apart: that pitch is the region's out_stride."""
@@ -1381,6 +1463,30 @@ def denoise_host(L, f, opt, out=None):
     """r1_denoise_host: the filter on the CPU, no device: the definition Renderer.denoise is checked against.  Arguments as there; returns out."""
     fr, L, f, out = _denoise_target(L, f, out)
     _check(lib().r1_denoise_host(C.byref(fr), C.byref(opt), C.c_void_p(L.ctypes.data), C.c_void_p(f.ctypes.data), C.c_void_p(out.ctypes.data)))
+    return out
+
+
+def _denoise_guided_target(L, f, V, out):
+    """(DenoiseGuidedFrame, L, f, V, out) of a host-memory guided denoise: _denoise_target's rules, and V's pitch"""
+    fr, L, f, out = _denoise_target(L, f, out)
+    ms = _pixel_pitch(V, "V", MOMENT_DTYPE, (), MOMENT_DTYPE.itemsize)
+    if V.shape != f.shape:
+        raise R1Error(R1_EINVAL, f"denoise: V {V.shape} is not the frame of f {f.shape}")
+    return DenoiseGuidedFrame(fr.width, fr.height, fr.linear_stride, fr.feature_stride, ms, fr.out_stride), L, f, V, out
+
+
+def denoise_guided_check(frame, opt):
+    """r1_denoise_guided_check: raises R1Error naming the field unless the DenoiseGuidedFrame and the DenoiseGuidedOpt are ones a guided
+    denoise accepts.  Pure arithmetic."""
+    _check(lib().r1_denoise_guided_check(C.byref(frame), C.byref(opt)))
+    return True
+
+
+def denoise_guided_host(L, f, V, opt, out=None):
+    """r1_denoise_guided_host: the variance-guided filter on the CPU, no device: the definition Renderer.denoise_guided is checked against."""
+    fr, L, f, V, out = _denoise_guided_target(L, f, V, out)
+    _check(lib().r1_denoise_guided_host(C.byref(fr), C.byref(opt), C.c_void_p(L.ctypes.data), C.c_void_p(f.ctypes.data), C.c_void_p(V.ctypes.data),
+                                        C.c_void_p(out.ctypes.data)))
     return out
 
 

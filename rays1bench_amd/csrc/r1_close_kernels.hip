@@ -1,5 +1,5 @@
 // r1_close_kernels.hip — the kernels that close a frame behind the trace launch (resolve, region resolve, linear resolve and read-out, progressive accumulate, adaptive
-// accumulate and compact, batch counts, assemble, landing arm) and their launchers, called from r1_frame.cpp and r1_render.cpp.  The tile geometry is
+// accumulate and compact, batch counts, assemble, landing arm, variance resolve) and their launchers, called from r1_frame.cpp and r1_render.cpp.  The tile geometry is
 // r1_tile.h's; quantise_pixel is the trace kernels' (r1_sample.hpp).  The trace kernel's own resolver: r1_land.hpp.
 #include "r1_sample.hpp"
 #include "r1_internal.h"
@@ -358,6 +358,42 @@ __global__ void __launch_bounds__(256) r1_land_arm_kernel(const R1LandArmArgs A)
     A.tile_cnt[(size_t)i * R1_LAND_CNT_STRIDE] = (uint32_t)(rect.tw * rect.th * A.spp);
 }
 
+// Variance frames (r1_render_moments*): in place of r1_resolve_linear_kernel, with its indexing, tile walk and sums, so L has
+// its bits.  Then the pixel's records once more in sample order (they come from cache): d = x - L; D = D + d * d, plain fp32, nothing fused
+// (-ffp-contract=off); var = D * inv_nn, the unbiased variance of the pixel's MEAN, and +0.0f for one sample whatever the records hold.
+// One 16-byte store of {var r, var g, var b, spp} per pixel.
+__global__ void __launch_bounds__(256) r1_resolve_moments_kernel(const R1MomentsArgs A)
+{
+    const uint32_t tile_px = r1_tile_slots(A.geom);
+    for (uint32_t lt = blockIdx.y; lt < A.n_tiles; lt += gridDim.y)
+    {
+        const R1TileRect rect = r1_tile_rect(A.geom, lt);
+        for (uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x; pix < tile_px; pix += gridDim.x * blockDim.x)
+        {
+            int lx, ly;
+            if (!r1_tile_pixel(A.geom, rect, pix, &lx, &ly))
+                continue; // void slots of an edge tile
+            const float4 *const s = A.samples + (size_t)lt * A.full + pix;
+            float cr = 0, cg = 0, cb = 0;
+            sum_records(s, tile_px, A.spp, cr, cg, cb);
+            const float lr = cr * A.inv_spp, lg = cg * A.inv_spp, lb = cb * A.inv_spp; // col *= 1 / spp rayweek1.cpp:765
+            float dr = 0, dg = 0, db = 0;
+            for (int i = 0; i < A.spp; ++i)
+            {
+                const float4 v = s[(size_t)i * tile_px];
+                const float er = v.x - lr, eg = v.y - lg, eb = v.z - lb;
+                dr = dr + er * er, dg = dg + eg * eg, db = db + eb * eb;
+            }
+            const size_t px = r1_pixel_row_major(A.geom, rect, lx, ly);
+            float *const o = A.out + px * 3;
+            o[0] = lr, o[1] = lg, o[2] = lb;
+            const bool many = A.spp > 1;
+            A.moments[px] = make_uint4(many ? __float_as_uint(dr * A.inv_nn) : 0u, many ? __float_as_uint(dg * A.inv_nn) : 0u,
+                                       many ? __float_as_uint(db * A.inv_nn) : 0u, (uint32_t)A.spp);
+        }
+    }
+}
+
 // ---- launchers (called from r1_frame.cpp, r1_render.cpp) -----------------------------------------------------
 
 // The grid of a tile-row launch: workgroups of 256 threads across a padded tile's slots, one row of them per tile (at most 65535 rows; a row walks
@@ -401,6 +437,13 @@ extern "C" hipError_t r1_launch_accum(const R1AccumArgs *args, hipStream_t strea
 extern "C" hipError_t r1_launch_resolve_linear(const R1LinearArgs *args, int max_rows, hipStream_t stream)
 {
     hipLaunchKernelGGL(r1_resolve_linear_kernel, tile_row_grid(args->geom, args->n_tiles, max_rows), dim3(256), 0, stream, *args);
+    return hipGetLastError();
+}
+
+// variance frames: r1_launch_resolve_linear's grid
+extern "C" hipError_t r1_launch_resolve_moments(const R1MomentsArgs *args, int max_rows, hipStream_t stream)
+{
+    hipLaunchKernelGGL(r1_resolve_moments_kernel, tile_row_grid(args->geom, args->n_tiles, max_rows), dim3(256), 0, stream, *args);
     return hipGetLastError();
 }
 

@@ -160,6 +160,7 @@ struct r1_context
     DevBuf adapt_report;       // [tile] R1TileReport
     // linear frames (r1_render_linear*, r1_pass_linear, r1_render_adaptive_linear): `image` is sized for bytes
     DevBuf linear;             // row-major width*height*3 floats, where the caller's memory is not the device's to write
+    DevBuf moments;            // variance frames (r1_render_moments): row-major width*height r1_moment records, on the same terms
     // ray queries (r1_cast_rays*): nothing here is read or written by a render
     DevBuf active_dev;         // active_to_scene on the device, uploaded once per r1_set_scene
     DevBuf cast_cursors;       // R1_CAST_CURSORS ray cursors, 128 bytes apart, taken in turn
@@ -237,9 +238,12 @@ struct Pass
 
 // A linear frame (r1_render_linear*): behind the frame's trace and whatever closes it, r1_resolve_linear_kernel sums the records
 // the trace left in the context's `samples` into `out`.  The launch keeps per-sample records: PIXEL mode is not chosen, whatever the switch says.
+// A variance frame (r1_render_moments*) is a linear frame with `moments` set: r1_resolve_moments_kernel takes the launch's
+// place and stores both.
 struct Linear
 {
-    float *out = nullptr; // device address of width*height*3 floats, row-major (device memory, or page-locked host memory)
+    float *out = nullptr;    // device address of width*height*3 floats, row-major (device memory, or page-locked host memory)
+    void *moments = nullptr; // device address of width*height r1_moment records, row-major, 16-byte aligned; null: a linear frame alone
 };
 
 // What an entry point asks enqueue_frame for: the call sites set the fields they need by name on a local.

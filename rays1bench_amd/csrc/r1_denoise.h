@@ -88,6 +88,33 @@ R1D_HD float r1d_sc2(float sigma_color, int i)
     return sc * sc;
 }
 
+// ---- the variance-guided form (include/rays1.h "variance-guided denoised frames"): what it adds to the lines above ----
+// The records stay as they are; the variance v of a pixel's demodulated value is one more float a pixel, ping and pong.  r1d_weight serves
+// unchanged with r1d_den's value for sc2: xc = dc / den.
+
+// Prepare: v = surf ? (V_r / (a_r * a_r) + V_g / (a_g * a_g)) + V_b / (a_b * a_b) : 0; V of a pixel without a hit is not used
+R1D_HD float r1d_prepare_v(const float V[3], const float albedo[3], uint32_t hits, uint32_t flags)
+{
+    if (hits == 0u)
+        return 0.0f;
+    const float ar = r1d_albedo(albedo[0], flags), ag = r1d_albedo(albedo[1], flags), ab = r1d_albedo(albedo[2], flags);
+    return (V[0] / (ar * ar) + V[1] / (ag * ag)) + V[2] / (ab * ab);
+}
+
+// The 3-tap table {1/4, 1/2, 1/4} at offset d = -1 .. 1, and one tap of the 3 x 3 prefilter of v: G = G + k * v_q, K = K + k
+R1D_HD float r1d_k3(int d) { return d == 0 ? 0.5f : 0.25f; }
+R1D_HD void r1d_prefilter_tap(float k, float vq, float &G, float &K)
+{
+    G = G + k * vq;
+    K = K + k;
+}
+
+// The colour term's denominator of a pixel: sc2 * g + variance_floor, sc2 = sigma_color * sigma_color in every iteration
+R1D_HD float r1d_den(float sc2, float g, float variance_floor) { return sc2 * g + variance_floor; }
+
+// One tap into the variance sum: T = T + (w * w) * v_q
+R1D_HD void r1d_accumulate_v(float w, float vq, float &T) { T = T + (w * w) * vq; }
+
 // ---- what the kernels read and write (r1_denoise_kernels.hip), device memory; by value in their arguments ----
 // A workgroup of 256 threads owns one 32 x 8 tile of the frame (r1_tile.h's geometry: tiles numbered row by row, slot = ly * 32 + lx, edge
 // tiles cut by the image); a thread owns one pixel.  The records are dense, width apart; only L, f and out have the caller's strides.
@@ -110,6 +137,17 @@ struct R1DenoiseArgs
     uint32_t flags, k;
     float sigma_depth, sc2;
     int32_t step;
+};
+
+// The guided kernels (r1_vfilter_kernels.hip): the same records and fields (d.sc2: sigma_color squared), and the variance beside them
+struct R1VFilterArgs
+{
+    R1DenoiseArgs d;
+    const float *V;             // prepare: the variance frame, 4 words a pixel {var r, g, b, samples}, rows moment_stride pixels apart (16-byte aligned)
+    const float *v_cur;         // a pass: one float a pixel, dense ...
+    float *v_next;              // ... and what it writes (prepare: the first pass's v_cur); unused by the last pass
+    uint32_t moment_stride;
+    float variance_floor;
 };
 
 #endif

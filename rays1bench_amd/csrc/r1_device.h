@@ -508,6 +508,22 @@ struct R1LinearArgs
     float inv_spp;               // (float)(1.0f / spp)
 };
 
+// Variance frames.  r1_resolve_moments_kernel, launched INSTEAD of r1_resolve_linear_kernel: the same walk and the same
+// sums, then a second walk over the pixel's records for the squared deviations from the stored mean; it stores the linear value and the
+// pixel's r1_moment record.
+struct R1MomentsArgs
+{
+    const float4 *samples;       // as R1LinearArgs::samples
+    float *out;                  // row-major width*height*3 floats: r1_resolve_linear_kernel's values
+    uint4 *moments;              // row-major width*height records {var r, var g, var b as fp32 bits, spp}, 16-byte aligned
+    uint32_t full;               // tile_w * tile_h * spp
+    R1TileGeom geom;
+    int32_t spp;
+    uint32_t n_tiles;
+    float inv_spp;               // (float)(1.0f / spp)
+    float inv_nn;                // spp > 1: 1.0f / ((float)spp * (float)(spp - 1)); unused at spp == 1, where every var is +0.0f
+};
+
 // Region renders (r1_resolve_region_kernel): the records of a launch over the REGION's tiles (geom: a frame of the region's size),
 // summed as the resolve sums them, into a window whose rows lie `stride` pixels apart: bytes, floats or both.
 struct R1RegionArgs

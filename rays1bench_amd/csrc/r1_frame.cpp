@@ -669,6 +669,17 @@ static int resolve_linear(const r1_context *c, const r1_params *p, const FrameJo
 {
     if (!c->n_local_tiles || !c->total_samples)
         return R1_OK;
+    if (job.linear->moments) // a variance frame: one launch in the linear one's place stores both
+    {
+        R1MomentsArgs m = {};
+        m.samples = (const float4 *)c->samples.p, m.out = job.linear->out, m.moments = (uint4 *)job.linear->moments;
+        m.full = c->full, m.n_tiles = c->n_local_tiles;
+        m.geom = g, m.spp = p->spp;
+        m.inv_spp = (float)(1.0f / p->spp); // rayweek1.cpp:765
+        m.inv_nn = p->spp > 1 ? 1.0f / ((float)p->spp * (float)(p->spp - 1)) : 0.0f;
+        R1_HIP(r1_launch_resolve_moments(&m, job.throughput ? R1_RESOLVE_ROWS_TP : 0, job.st));
+        return R1_OK;
+    }
     R1LinearArgs l = {};
     l.samples = (const float4 *)c->samples.p, l.out = job.linear->out;
     l.full = c->full, l.n_tiles = c->n_local_tiles;

@@ -17,6 +17,7 @@ struct R1SortArgs; // r1_bvh_sort.h
 struct R1RegridArgs; // r1_grid_fill.h
 struct R1RadixArgs; // r1_device_sort.h
 struct R1DenoiseArgs; // r1_denoise.h
+struct R1VFilterArgs; // r1_denoise.h
 
 // what r1_sweep_describe says of the sweep's tables besides the arrays
 struct r1_sweep_info
@@ -74,6 +75,7 @@ hipError_t r1_launch_resolve(const R1ResolveArgs *args, int max_rows, hipStream_
 hipError_t r1_launch_accum(const R1AccumArgs *args, hipStream_t stream);
 hipError_t r1_launch_adapt_accum(const R1AdaptArgs *args, hipStream_t stream);
 hipError_t r1_launch_resolve_linear(const R1LinearArgs *args, int max_rows, hipStream_t stream); // linear frames
+hipError_t r1_launch_resolve_moments(const R1MomentsArgs *args, int max_rows, hipStream_t stream); // variance frames
 hipError_t r1_launch_resolve_region(const R1RegionArgs *args, hipStream_t stream); // region renders
 hipError_t r1_launch_accum_linear(const R1ReadoutArgs *args, hipStream_t stream);
 hipError_t r1_launch_adapt_compact(const uint32_t *cur, uint32_t n_cur, const R1TileReport *report, uint32_t at_cap, uint32_t *next, uint32_t *count_out,
@@ -101,6 +103,9 @@ hipError_t r1_features_occupancy(int variant, int big, size_t dyn_lds, int *bloc
 // hipErrorInvalidValue); last: the pass that re-modulates and writes `out`
 hipError_t r1_launch_denoise_prepare(const R1DenoiseArgs *args, hipStream_t stream);
 hipError_t r1_launch_denoise_pass(const R1DenoiseArgs *args, int staged, int last, hipStream_t stream);
+// r1_vfilter_kernels.hip: their variance-guided twins, on the same terms
+hipError_t r1_launch_vfilter_prepare(const R1VFilterArgs *args, hipStream_t stream);
+hipError_t r1_launch_vfilter_pass(const R1VFilterArgs *args, int staged, int last, hipStream_t stream);
 
 // r1_aux_kernels.hip: r1_camera_rays_device
 hipError_t r1_launch_camera_rays(const R1CameraRaysArgs *args, hipStream_t stream);

@@ -1,5 +1,5 @@
 // r1_linear_host.cpp — linear frames without a GPU (include/rays1.h): r1_render_linear_host, the CPU form of
-// r1_render_linear built from r1_camera_rays and r1_trace_rays_host; r1_quantise_linear, the step from a linear value to the byte; and
+// r1_render_linear built from r1_camera_rays and r1_trace_rays_host, and r1_render_moments_host beside it (§4.40); r1_quantise_linear, the step from a linear value to the byte; and
 // r1_pfm_write_rgb32f.  Compiled as every host file is, with -ffp-contract=off and without -ffast-math: the sums below are plain fp32
 // adds in sample order, and sqrtf is the host's correctly rounded one.
 
@@ -14,7 +14,9 @@
 
 // rayweek1.cpp:757-765 for every pixel of window `win` of the frame: S = 0.0f; S += color(sample s) for s = 0 .. spp - 1; L = S * (float)(1.0f / spp),
 // stored at rgb_out + (y * stride + x) * 3 for pixel (x, y) of the window.  The whole frame is the window (0, 0, width, height) with stride width.
-static int render_window_host(const r1_scene *scene, const r1_camera *camera, const r1_params *p, const r1_region &win, float *rgb_out, uint64_t *num_rays_out)
+// moments_out (may be null; dense, win.width records a row): the pixel's r1_moment record, DESIGN.md §4.40 — a second walk over the same records.
+static int render_window_host(const r1_scene *scene, const r1_camera *camera, const r1_params *p, const r1_region &win, float *rgb_out, uint64_t *num_rays_out,
+                              r1_moment *moments_out = nullptr)
 {
     int rc;
     // a few rows of pixels at a time: the rays, seeds and records of their samples (64 bytes a sample) stay small for any frame
@@ -26,6 +28,7 @@ static int render_window_host(const r1_scene *scene, const r1_camera *camera, co
     std::vector<r1_sample_seed> seeds;
     std::vector<r1_radiance> rec;
     const float inv = (float)(1.0f / p->spp); // rayweek1.cpp:765
+    const float inv_nn = p->spp > 1 ? 1.0f / ((float)p->spp * (float)(p->spp - 1)) : 0.0f;
     uint64_t total = 0;
     for (size_t p0 = 0; p0 < n_pixels; p0 += chunk)
     {
@@ -51,6 +54,19 @@ static int render_window_host(const r1_scene *scene, const r1_camera *camera, co
             }
             float *const o = rgb_out + ((p0 + i) / (size_t)win.width * stride + (p0 + i) % (size_t)win.width) * 3;
             o[0] = cr * inv, o[1] = cg * inv, o[2] = cb * inv;
+            if (!moments_out)
+                continue;
+            const float lr = o[0], lg = o[1], lb = o[2];
+            float dr = 0.0f, dg = 0.0f, db = 0.0f;
+            for (size_t k = 0; k < spp; ++k)
+            {
+                const r1_radiance &v = rec[i * spp + k];
+                const float er = v.r - lr, eg = v.g - lg, eb = v.b - lb;
+                dr = dr + er * er, dg = dg + eg * eg, db = db + eb * eb;
+            }
+            r1_moment &m = moments_out[p0 + i];
+            m.var[0] = p->spp > 1 ? dr * inv_nn : 0.0f, m.var[1] = p->spp > 1 ? dg * inv_nn : 0.0f, m.var[2] = p->spp > 1 ? db * inv_nn : 0.0f;
+            m.samples = (uint32_t)p->spp;
         }
     }
     if (num_rays_out)
@@ -75,6 +91,26 @@ extern "C" int r1_render_linear_host(const r1_scene *scene, const r1_camera *cam
     }
     const r1_region whole = {0, 0, p->width, p->height, 0};
     return render_window_host(scene, camera, p, whole, rgb_out, num_rays_out);
+}
+
+// The CPU form of r1_render_moments: r1_render_linear_host's frame and ray count, and the moment records beside it
+extern "C" int r1_render_moments_host(const r1_scene *scene, const r1_camera *camera, const r1_params *p, float *rgb_out, r1_moment *moments_out, uint64_t *num_rays_out)
+{
+    if (!scene || !camera || !p || !rgb_out || !moments_out)
+    {
+        r1_set_error("r1_render_moments_host: null argument");
+        return R1_EINVAL;
+    }
+    int rc = r1_params_check(p);
+    if (rc)
+        return rc;
+    if (p->num_shards != 1)
+    {
+        r1_set_error("r1_render_moments_host renders whole frames (num_shards == 1, not %d)", p->num_shards);
+        return R1_EINVAL;
+    }
+    const r1_region whole = {0, 0, p->width, p->height, 0};
+    return render_window_host(scene, camera, p, whole, rgb_out, num_rays_out, moments_out);
 }
 
 // The CPU form of r1_render_region_linear: the window's pixels of the FRAME — r1_camera_rays seeds and aims with params' width

@@ -474,24 +474,47 @@ static int bring_linear(r1_context *c, const r1_params *p, const Linear &lin, fl
     return R1_OK;
 }
 
-extern "C" int r1_render_linear(r1_context *c, const r1_params *p, float *rgb_out, uint64_t *num_rays_out, double *device_seconds_out)
+// The same for a variance frame's records: page-locked memory is written by the launch itself if it is 16-byte aligned
+static size_t moments_bytes(const r1_params *p) { return (size_t)p->width * p->height * sizeof(r1_moment); }
+static int moments_target(r1_context *c, const r1_params *p, r1_moment *moments_out, Linear &lin)
 {
+    lin.moments = mapped_host(moments_out);
+    if (lin.moments && !((uintptr_t)lin.moments & 15u)) // (the kernel stores whole records)
+        return R1_OK;
+    int rc = ensure(c->moments, moments_bytes(p));
+    lin.moments = c->moments.p;
+    return rc;
+}
+static int bring_moments(r1_context *c, const r1_params *p, const Linear &lin, r1_moment *moments_out, hipStream_t st)
+{
+    if (lin.moments == c->moments.p)
+        R1_HIP(hipMemcpyAsync(moments_out, c->moments.p, moments_bytes(p), hipMemcpyDeviceToHost, st));
+    return R1_OK;
+}
+
+// r1_render_linear (moments_out null) and r1_render_moments: the same frame; a variance frame's resolve launch stores the moment records too
+static int render_linear_sync(const char *who, r1_context *c, const r1_params *p, float *rgb_out, r1_moment *moments_out, uint64_t *num_rays_out,
+                              double *device_seconds_out)
+{
+    const bool want_moments = moments_out != nullptr;
     if (!c || !p || !rgb_out)
     {
-        r1_set_error("r1_render_linear: null argument");
+        r1_set_error("%s: null argument", who);
         return R1_EINVAL;
     }
-    int rc = linear_check("r1_render_linear", c, p);
+    int rc = linear_check(who, c, p);
     if (rc)
         return rc;
     R1_HIP(hipSetDevice(c->device));
     Linear lin;
-    if ((rc = ensure(c->image, (size_t)p->width * p->height * 3 + 64)) || (rc = linear_target(c, p, rgb_out, lin)))
+    if ((rc = ensure(c->image, (size_t)p->width * p->height * 3 + 64)) || (rc = linear_target(c, p, rgb_out, lin)) ||
+        (want_moments && (rc = moments_target(c, p, moments_out, lin))))
         return rc;
     const bool direct = !r1_is_stats(p->variant) && c->host_word_dev; // the ray count as r1_render brings it home
     FrameJob job;
     job.out = c->image.p, job.rays = rays_word(c, direct), job.st = c->stream, job.linear = &lin;
-    if ((rc = enqueue_frame(c, p, job)) || (rc = bring_linear(c, p, lin, rgb_out, c->stream)))
+    if ((rc = enqueue_frame(c, p, job)) || (rc = bring_linear(c, p, lin, rgb_out, c->stream)) ||
+        (want_moments && (rc = bring_moments(c, p, lin, moments_out, c->stream))))
         return rc;
     uint64_t rays = 0;
     if ((rc = read_rays(c, direct, &rays)) || (rc = land_check(c)))
@@ -505,6 +528,11 @@ extern "C" int r1_render_linear(r1_context *c, const r1_params *p, float *rgb_ou
         *device_seconds_out = ms * 1e-3;
     }
     return R1_OK;
+}
+
+extern "C" int r1_render_linear(r1_context *c, const r1_params *p, float *rgb_out, uint64_t *num_rays_out, double *device_seconds_out)
+{
+    return render_linear_sync("r1_render_linear", c, p, rgb_out, nullptr, num_rays_out, device_seconds_out);
 }
 
 // r1_render_async's rules.  The byte image stays in the context's device buffer; the landing of bytes into the caller's memory is not
@@ -538,29 +566,64 @@ extern "C" int r1_render_linear_async(r1_context *c, const r1_params *p, float *
     return R1_OK;
 }
 
-extern "C" int r1_render_linear_device(r1_context *c, const r1_params *p, void *d_rgb_f32, void *d_num_rays, void *hip_stream)
+// r1_render_linear_device (no moments) and r1_render_moments_device
+static int render_linear_to_device(const char *who, r1_context *c, const r1_params *p, void *d_rgb_f32, void *d_moments, void *d_num_rays, void *hip_stream)
 {
     if (!c || !p || !d_rgb_f32 || !d_num_rays)
     {
-        r1_set_error("r1_render_linear_device: null argument");
+        r1_set_error("%s: null argument", who);
         return R1_EINVAL;
     }
     if (((uintptr_t)d_rgb_f32 & 3u) || ((uintptr_t)d_num_rays & 7u))
     {
-        r1_set_error("r1_render_linear_device: d_rgb_f32 must be 4-byte aligned and d_num_rays 8-byte aligned");
+        r1_set_error("%s: d_rgb_f32 must be 4-byte aligned and d_num_rays 8-byte aligned", who);
         return R1_EINVAL;
     }
-    int rc = linear_check("r1_render_linear_device", c, p);
+    int rc = linear_check(who, c, p);
     if (rc)
         return rc;
     R1_HIP(hipSetDevice(c->device));
     if ((rc = ensure(c->image, (size_t)p->width * p->height * 3 + 64)))
         return rc;
     Linear lin;
-    lin.out = (float *)d_rgb_f32;
+    lin.out = (float *)d_rgb_f32, lin.moments = d_moments;
     FrameJob job;
     job.out = c->image.p, job.rays = d_num_rays, job.st = hip_stream ? (hipStream_t)hip_stream : c->stream, job.throughput = true, job.linear = &lin;
     return enqueue_frame(c, p, job);
+}
+
+extern "C" int r1_render_linear_device(r1_context *c, const r1_params *p, void *d_rgb_f32, void *d_num_rays, void *hip_stream)
+{
+    return render_linear_to_device("r1_render_linear_device", c, p, d_rgb_f32, nullptr, d_num_rays, hip_stream);
+}
+
+// ---- variance frames ----------------------------------------------------------------
+// A linear frame whose closing launch is r1_resolve_moments_kernel: the linear value and, from a second walk over the same records, the
+// unbiased variance of each pixel's mean.  Everything else — checks, launches, state, timing — is the linear frame's.
+
+extern "C" int r1_render_moments(r1_context *c, const r1_params *p, float *rgb_out, r1_moment *moments_out, uint64_t *num_rays_out, double *device_seconds_out)
+{
+    if (!moments_out) // (the shared body takes a null target for "a linear frame alone")
+    {
+        r1_set_error("r1_render_moments: null argument");
+        return R1_EINVAL;
+    }
+    return render_linear_sync("r1_render_moments", c, p, rgb_out, moments_out, num_rays_out, device_seconds_out);
+}
+
+extern "C" int r1_render_moments_device(r1_context *c, const r1_params *p, void *d_rgb_f32, void *d_moments, void *d_num_rays, void *hip_stream)
+{
+    if (!c || !p || !d_rgb_f32 || !d_moments || !d_num_rays)
+    {
+        r1_set_error("r1_render_moments_device: null argument");
+        return R1_EINVAL;
+    }
+    if ((uintptr_t)d_moments & 15u)
+    {
+        r1_set_error("r1_render_moments_device: d_moments must be 16-byte aligned");
+        return R1_EINVAL;
+    }
+    return render_linear_to_device("r1_render_moments_device", c, p, d_rgb_f32, d_moments, d_num_rays, hip_stream);
 }
 
 // The accumulators' read-out, then the frame on the host: `all` of r1_render_pass (n_uniform samples in every tile) or of an adaptive

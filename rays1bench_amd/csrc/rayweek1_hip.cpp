@@ -38,6 +38,8 @@
 // --denoise [ITERATIONS] is --linear, and each frame is also rendered through r1_render_denoised (ITERATIONS a-trous iterations, 3 if not given;
 // normal_power_log2 6, sigma_color 1, sigma_depth 0.1, demodulated): -w also writes out_<scene>_denoised.pfm next to the noisy out_<scene>.pfm,
 // and the report gains one "<scene> denoise:" line with the device time.
+// --denoise-guided [ITERATIONS] is the same through r1_render_denoised_guided (the variance-guided filter: sigma_color 2, variance_floor 1e-4): the same
+// file, one "<scene> denoise-guided:" line; not with --denoise, and not with --spp 1, which carries no variance.
 // --backend hip (default) | cpu-step1 | cpu-step12: the reference's two single-thread CPU stages
 // (r1_cpu_backends.cpp) behind the same benchmark(), for the README-style table
 // (README.md:38-84).  Named backends of this program only — never a fallback: with --backend hip and no
@@ -247,6 +249,12 @@ static Frame context_frame(const Scene *scene, Pix *pixels, const r1_params &p, 
             g_denoised.assign((size_t)q.width * q.height * 3, 0.0f);
             rc = r1_render_denoised(g_ctx[i], &q, &g_opt.denoise_opt, g_denoised.data(), &again, &denoise_s);
         }
+        if (rc == R1_OK && g_opt.denoise_guided) // --denoise-guided (one device): the same frame again with its variance frame, guided and filtered
+        {
+            uint64_t again = 0;
+            g_denoised.assign((size_t)q.width * q.height * 3, 0.0f);
+            rc = r1_render_denoised_guided(g_ctx[i], &q, &g_opt.guided_opt, g_denoised.data(), &again, &denoise_s);
+        }
         if (rc == R1_OK && g_opt.features) // --features (one device): the feature frame of what was just rendered — the frame, or --region's window
         {
             const r1_region *const win = g_opt.region ? &g_opt.window : nullptr;
@@ -317,6 +325,17 @@ static Frame context_frame(const Scene *scene, Pix *pixels, const r1_params &p, 
                               (double)g_opt.denoise_opt.sigma_depth, (g_opt.denoise_opt.flags & R1_DENOISE_DEMODULATE) ? "demodulated" : "not demodulated",
                               sum / (double)g_denoised.size(), denoise_s * 1e3);
     }
+    if (g_opt.denoise_guided)
+    {
+        double sum = 0;
+        for (const float v : g_denoised)
+            sum += v;
+        const r1_denoise_opt &b = g_opt.guided_opt.base;
+        f.lines_after += line("%s denoise-guided: %d iterations, normal power 2^%d, sigma colour %g, sigma depth %g, variance floor %g, %s, mean %.6f, device time %.3fms "
+                              "(render with moments, features, filter)\n",
+                              scene_name, b.iterations, b.normal_power_log2, (double)b.sigma_color, (double)b.sigma_depth, (double)g_opt.guided_opt.variance_floor,
+                              (b.flags & R1_DENOISE_DEMODULATE) ? "demodulated" : "not demodulated", sum / (double)g_denoised.size(), denoise_s * 1e3);
+    }
     if (g_opt.features)
     {
         uint64_t hits = 0, covered = 0;
@@ -372,7 +391,7 @@ RESULT benchmark(Scene *scene, Pix *pixels, bool write_tga, const char *scene_na
             snprintf(filename, sizeof(filename), "out_%s.pfm", scene_name);
             r1_pfm_write_rgb32f(filename, g_opt.width, g_opt.height, g_linear);
         }
-        if (g_opt.denoise)
+        if (g_opt.denoise || g_opt.denoise_guided)
         {
             snprintf(filename, sizeof(filename), "out_%s_denoised.pfm", scene_name);
             r1_pfm_write_rgb32f(filename, g_opt.width, g_opt.height, g_denoised.data());
@@ -478,6 +497,13 @@ int main(int argc, const char *argv[])
         if (strcmp(argv[i], "--features") == 0)
         {
             o.features = true;
+            continue;
+        }
+        if (strcmp(argv[i], "--denoise-guided") == 0) // (its value is optional, as --denoise's)
+        {
+            o.denoise_guided = o.linear = true;
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9')
+                o.guided_opt.base.iterations = atoi(argv[++i]);
             continue;
         }
         if (strcmp(argv[i], "--denoise") == 0) // (its value is optional: taken where the next argument is a number)
@@ -590,6 +616,15 @@ int main(int argc, const char *argv[])
     {
         fprintf(stderr, "bad --denoise [ITERATIONS]: needs 1..%d iterations, the hip backend, one device (no --gather rccl), --variant 0, 1, 4 or 7, no --passes, "
                         "no --adaptive and no --region\n", R1_DENOISE_MAX_ITERATIONS);
+        return 1;
+    }
+
+    if (o.denoise_guided && (o.denoise || o.spp < 2 || !one_pass || o.adaptive || o.region ||
+                             !(tree_variant || o.variant == R1_VARIANT_GRID || o.variant == R1_VARIANT_REFERENCE) || o.guided_opt.base.iterations < 1 ||
+                             o.guided_opt.base.iterations > R1_DENOISE_MAX_ITERATIONS))
+    {
+        fprintf(stderr, "bad --denoise-guided [ITERATIONS]: needs 1..%d iterations, --spp 2 or more, the hip backend, one device (no --gather rccl), --variant 0, 1, 4 or 7, "
+                        "no --denoise, no --passes, no --adaptive and no --region\n", R1_DENOISE_MAX_ITERATIONS);
         return 1;
     }
 

@@ -24,6 +24,9 @@ struct Options
     // --denoise [ITERATIONS]: --linear, and each frame also through r1_render_denoised; -w also writes out_<scene>_denoised.pfm next to out_<scene>.pfm
     bool denoise = false;
     r1_denoise_opt denoise_opt = {3, 6, 1.0f, 0.1f, R1_DENOISE_DEMODULATE};
+    // --denoise-guided [ITERATIONS]: --linear, and each frame also through r1_render_denoised_guided (sigma colour 2, variance floor 1e-4); the same file
+    bool denoise_guided = false;
+    r1_denoise_guided_opt guided_opt = {{3, 6, 2.0f, 0.1f, R1_DENOISE_DEMODULATE}, 1e-4f, 0u};
     bool region = false; // --region X,Y,W,H: every frame through r1_render_region; the pixels, the TGA and the counts are the window's
     r1_region window = {0, 0, 0, 0, 0};
     // the demos, each FRAMES frames per scene after the benchmark() runs; 0 = not asked for

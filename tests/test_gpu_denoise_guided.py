@@ -1,0 +1,215 @@
+"""GPU tests of variance-guided denoised frames (include/rays1.h): r1_denoise_guided_device and r1_denoise_guided return
+r1_denoise_guided_host's frame — which tests/test_denoise_guided_host.py pins to the contract restated in numpy — byte for byte, and
+r1_render_denoised_guided* the host composition's.  Nothing here has a tolerance."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import rays1bench_amd as r1
+from rays1bench_amd import binding
+
+import denoise_cases as dc
+import guided_cases as gc
+import linear_cases as lc
+
+pytestmark = pytest.mark.gpu
+
+ALL = list(dc.RENDERED) + list(dc.SYNTHETIC) + list(dc.DEVICE_ONLY)
+
+
+@pytest.fixture()
+def renderer():
+    assert r1.device_count() >= 1, "no HIP device: the product has no CPU fallback"
+    r = r1.Renderer(0)
+    yield r
+    r.close()
+
+
+def bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def differing(a, b):
+    return int((bits(a) != bits(b)).sum())
+
+
+def device_result(renderer, L, f, V, o, in_place=False, times=1):
+    """r1_denoise_guided_device on tensors holding the three frames; the output tensor is prefilled with NaN"""
+    h, w = L.shape[:2]
+    dL = torch.from_numpy(np.ascontiguousarray(L)).cuda()
+    df = torch.from_numpy(np.ascontiguousarray(f).view(np.uint32).reshape(h, w, 8).view(np.int32)).cuda()
+    dV = torch.from_numpy(np.ascontiguousarray(V).view(np.uint32).reshape(h, w, 4).view(np.int32)).cuda()
+    dout = dL if in_place else torch.full((h, w, 3), float("nan"), dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    for _ in range(times):
+        renderer.denoise_guided_device(w, h, o, dL.data_ptr(), df.data_ptr(), dV.data_ptr(), dout.data_ptr())
+    renderer.sync()
+    return dout.cpu().numpy()
+
+
+@pytest.mark.parametrize("name", ALL)
+def test_both_device_forms_are_the_host_form(renderer, name):
+    L, f, V, it = gc.inputs(name)
+    it = 5 if name in dc.DEVICE_ONLY else it  # (tiles crossed in x and y, halos clipped on four edges, whole step-16 kernels)
+    want = gc.host_result(name, iterations=it)
+    o = gc.opt(iterations=it)
+    got = device_result(renderer, L, f, V, o)
+    assert differing(got, want) == 0, (name, differing(got, want))
+    out, secs = renderer.denoise_guided(np.array(L), f, V, o)
+    assert differing(out, want) == 0 and secs > 0
+    none = f["hits"] == 0
+    assert bits(got)[none].tobytes() == bits(L)[none].tobytes()
+
+
+@pytest.mark.parametrize("iterations", [1, 2, 3, 4, 5, 6])
+def test_every_pass_kernel_also_runs_as_the_last_pass(renderer, iterations):
+    name = "70x40"
+    L, f, V, _ = gc.inputs(name)
+    got = device_result(renderer, L, f, V, gc.opt(iterations=iterations))
+    assert differing(got, gc.host_result(name, iterations=iterations)) == 0
+
+
+@pytest.mark.parametrize("options", sorted(gc.OPTION_SETS))
+def test_option_sets_and_k_0_6_10(renderer, options):
+    name = "37x21"
+    L, f, V, it = gc.inputs(name)
+    kw = dict(gc.OPTION_SETS[options])
+    kw.setdefault("iterations", it)
+    got = device_result(renderer, L, f, V, gc.opt(**kw))
+    assert differing(got, gc.host_result(name, **kw)) == 0
+    for k in (0, 6, 10):
+        got = device_result(renderer, L, f, V, gc.opt(iterations=it, normal_power_log2=k))
+        assert differing(got, gc.host_result(name, iterations=it, normal_power_log2=k)) == 0, k
+
+
+def test_in_place_twice_in_a_row(renderer):
+    name = "65x33"
+    L, f, V, it = gc.inputs(name)
+    o = gc.opt(iterations=it)
+    once = gc.host_result(name, iterations=it)
+    twice = binding.denoise_guided_host(np.array(once), f, V, o)
+    assert differing(device_result(renderer, L, f, V, o, in_place=True), once) == 0
+    assert differing(device_result(renderer, L, f, V, o, in_place=True, times=2), twice) == 0
+
+
+def test_strides_with_nan_between_the_rows(renderer):
+    name = "37x21"
+    L, f, V, it = gc.inputs(name)
+    h, w = L.shape[:2]
+    pl, pf, pv, po = w + 3, w + 1, w + 2, w + 5
+    dL = torch.full((h, pl, 3), float("nan"), dtype=torch.float32, device="cuda")
+    df = torch.full((h, pf, 8), -1, dtype=torch.int32, device="cuda")  # (0xFFFFFFFF: a NaN, and hits of 2^32 - 1)
+    dV = torch.full((h, pv, 4), -1, dtype=torch.int32, device="cuda")
+    dout = torch.full((h, po, 3), 7.0, dtype=torch.float32, device="cuda")
+    dL[:, :w] = torch.from_numpy(np.ascontiguousarray(L)).cuda()
+    df[:, :w] = torch.from_numpy(np.ascontiguousarray(f).view(np.uint32).reshape(h, w, 8).view(np.int32)).cuda()
+    dV[:, :w] = torch.from_numpy(np.ascontiguousarray(V).view(np.uint32).reshape(h, w, 4).view(np.int32)).cuda()
+    torch.cuda.synchronize()
+    renderer.denoise_guided_device(w, h, gc.opt(iterations=it), dL.data_ptr(), df.data_ptr(), dV.data_ptr(), dout.data_ptr(), None, pl, pf, pv, po)
+    renderer.sync()
+    got = dout.cpu().numpy()
+    assert differing(got[:, :w], gc.host_result(name)) == 0 and (got[:, w:] == 7.0).all()
+    # host memory with strides
+    Lv, _ = dc.strided(L, pl)
+    fv, _ = dc.strided(f, pf)
+    Vv, _ = dc.strided(V, pv)
+    ov, ob = dc.strided(np.zeros_like(L), po)
+    out, _ = renderer.denoise_guided(Lv, fv, Vv, gc.opt(iterations=it), out=ov)
+    assert differing(out, gc.host_result(name)) == 0 and (ob[:, w:].view(np.uint8) == dc.PREFILL).all()
+
+
+@pytest.mark.parametrize("name,w,h,spp", [("medium", 77, 45, 3), ("large", 64, 48, 4)], ids=lambda v: str(v))
+def test_render_denoised_guided_is_the_host_composition(renderer, name, w, h, spp):
+    sc = lc.SCENES[name](w, h)
+    renderer.set_scene(sc)
+    p = r1.make_params(w, h, spp, lc.SEED)
+    L, V, want_rays = binding.render_moments_host(sc.spheres.contents, sc.camera.contents, p)
+    f = binding.render_features_host(sc.spheres.contents, sc.camera.contents, p)
+    o = gc.opt()
+    want = binding.denoise_guided_host(L, f, V, o)
+    for variant in (binding.VARIANT_DEFAULT, binding.VARIANT_BVH, binding.VARIANT_GRID, binding.VARIANT_REFERENCE):
+        pv = r1.make_params(w, h, spp, lc.SEED, variant=variant)
+        img, rays, secs = renderer.render_denoised_guided(pv, o)
+        assert rays == want_rays and secs > 0 and differing(img, want) == 0, (variant, differing(img, want))
+    frame = torch.full((h, w, 3), float("nan"), dtype=torch.float32, device="cuda")
+    count = torch.zeros(1, dtype=torch.int64, device="cuda")
+    stream = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    renderer.render_denoised_guided_device(p, o, frame.data_ptr(), count.data_ptr(), stream.cuda_stream)
+    stream.synchronize()
+    assert differing(frame.cpu().numpy(), want) == 0 and int(count.item()) == want_rays
+    # the state rules: the launch info is the render's; the unguided filter still serves on the same workspace
+    assert renderer.launch_info()["samples"] > 0
+    plain, plain_rays, _ = renderer.render_denoised(p, dc.opt())
+    assert plain_rays == want_rays and differing(plain, binding.denoise_host(L, f, dc.opt())) == 0
+
+
+def test_refusals_enqueue_nothing_and_a_progressive_accumulation_survives(renderer):
+    name, w, h = "small", 64, 48
+    Lb = r1.lib()
+    renderer.set_scene(lc.SCENES[name](w, h))
+    p = r1.make_params(w, h, 2, lc.SEED)
+    renderer.render_pass(p, 0, image=False)
+    info = renderer.launch_info()
+    o = gc.opt()
+    with pytest.raises(binding.R1Error) as e:
+        renderer.render_denoised_guided(r1.make_params(w, h, 1, lc.SEED), o)
+    assert e.value.code == binding.R1_EINVAL and "spp" in str(e.value)
+    with pytest.raises(binding.R1Error) as e:
+        renderer.render_denoised_guided(r1.make_params(w, h, 2, lc.SEED, variant=binding.VARIANT_PREFILTER), o)
+    assert "variant" in str(e.value)
+    with pytest.raises(binding.R1Error) as e:
+        renderer.render_denoised_guided(p, gc.opt(variance_floor=0.0))
+    assert "variance_floor" in str(e.value)
+    dev = torch.full((w * h * 3 + 4,), 0.5, dtype=torch.float32, device="cuda")
+    rec = torch.full((w * h * 8 + 8,), 3, dtype=torch.int32, device="cuda")
+    cnt = torch.full((2,), 5, dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+    fr = binding.DenoiseGuidedFrame(w, h, 0, 0, 0, 0)
+    c = renderer._c
+    calls = [lambda: Lb.r1_render_denoised_guided_device(c, C.byref(p), C.byref(o), None, cnt.data_ptr(), None),
+             lambda: Lb.r1_render_denoised_guided_device(c, C.byref(p), C.byref(o), dev.data_ptr() + 2, cnt.data_ptr(), None),
+             lambda: Lb.r1_render_denoised_guided_device(c, C.byref(p), C.byref(o), dev.data_ptr(), cnt.data_ptr() + 4, None),
+             lambda: Lb.r1_render_denoised_guided_device(c, C.byref(p), None, dev.data_ptr(), cnt.data_ptr(), None),
+             lambda: Lb.r1_denoise_guided_device(c, C.byref(fr), C.byref(o), dev.data_ptr(), rec.data_ptr(), rec.data_ptr() + 8, dev.data_ptr(), None),
+             lambda: Lb.r1_denoise_guided_device(c, C.byref(fr), C.byref(o), dev.data_ptr(), rec.data_ptr() + 4, rec.data_ptr(), dev.data_ptr(), None),
+             lambda: Lb.r1_denoise_guided_device(c, C.byref(fr), C.byref(o), dev.data_ptr(), rec.data_ptr(), None, dev.data_ptr(), None),
+             lambda: Lb.r1_denoise_guided_device(c, C.byref(fr), None, dev.data_ptr(), rec.data_ptr(), rec.data_ptr(), dev.data_ptr(), None)]
+    for k, call in enumerate(calls):
+        assert call() == binding.R1_EINVAL, k
+        assert renderer.launch_info() == info, k
+    torch.cuda.synchronize()
+    assert bool((dev == 0.5).all()) and bool((rec == 3).all()) and bool((cnt == 5).all())
+    # a filter call is a query: the accumulation continues at 2 and ends as the 5-sample frame
+    L, f, V, it = gc.inputs("37x21")
+    assert differing(device_result(renderer, L, f, V, gc.opt(iterations=it)), gc.host_result("37x21")) == 0
+    assert renderer.launch_info() == info
+    img, total = renderer.render_pass(r1.make_params(w, h, 3, lc.SEED), 2)
+    want = renderer.render(r1.make_params(w, h, 5, lc.SEED))
+    assert total == want[1] and img.tobytes() == want[0].tobytes()
+
+
+def test_program_denoise_guided_writes_the_filtered_frame(tmp_path):
+    """rayweek1_hip --denoise-guided -w: out_<scene>_denoised.pfm is the host composition's frame of the program's params, and the report has one
+    `denoise-guided:` line per scene."""
+    import os
+    import subprocess
+    exe = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "rays1bench_amd", "lib", "rayweek1_hip")
+    w, h, spp = 48, 32, 3
+    out = subprocess.run([exe, "--denoise-guided", "2", "-w", "--width", str(w), "--height", str(h), "--spp", str(spp)], cwd=tmp_path, capture_output=True, text=True,
+                         timeout=120)
+    assert out.returncode == 0, out.stderr[-2000:]
+    head = f"PF\n{w} {h}\n-1.0\n".encode()
+    for name in ("small", "medium"):
+        assert out.stdout.count(f"{name} denoise-guided: 2 iterations") == 1, out.stdout
+        sc = lc.SCENES[name](w, h)
+        p = r1.make_params(w, h, spp)
+        L, V, _ = binding.render_moments_host(sc.spheres.contents, sc.camera.contents, p)
+        f = binding.render_features_host(sc.spheres.contents, sc.camera.contents, p)
+        want = binding.denoise_guided_host(L, f, V, gc.opt(iterations=2))
+        data = (tmp_path / f"out_{name}_denoised.pfm").read_bytes()
+        assert data.startswith(head) and differing(np.frombuffer(data[len(head):], "<f4").reshape(h, w, 3), want) == 0, name
+        noisy = (tmp_path / f"out_{name}.pfm").read_bytes()
+        assert differing(np.frombuffer(noisy[len(head):], "<f4").reshape(h, w, 3), L) == 0, name

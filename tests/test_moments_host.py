@@ -1,0 +1,187 @@
+"""CPU tests of variance frames (include/rays1.h): every new name is declared, exported and bound; r1_render_moments_host equals
+the contract restated in numpy (tests/moment_cases.py) on the ORACLE's per-sample records, bit for bit, and its linear frame is
+r1_render_linear_host's; the restatement's inputs are the REFERENCE's own records where a fixture holds them at 64 samples a pixel; the
+refusals; the census of the new kernel.  What the device computes is checked in tests/test_gpu_moments.py.  Nothing here has a tolerance."""
+import ctypes as C
+import os
+import re
+import sys
+from fractions import Fraction
+
+import numpy as np
+import pytest
+
+import rays1bench_amd as r1
+from rays1bench_amd import binding
+import r1o
+
+import linear_cases as lc
+import moment_cases as mc
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLD = os.path.join(ROOT, "tests", "golden")
+
+NEW = ("r1_render_moments", "r1_render_moments_device", "r1_render_moments_host")
+
+
+def test_every_new_name_is_declared_exported_and_bound():
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "rays1.h")).read(), flags=re.S)
+    names = {s[0] for s in binding.SYMBOLS}
+    for name in NEW:
+        assert re.search(r"\bint\s+" + name + r"\s*\(", hdr), name
+        assert hasattr(r1.lib(), name) and name in names, name
+    assert re.search(r"typedef\s+struct\s+r1_moment\s*\{\s*float\s+var\[3\];\s*uint32_t\s+samples;\s*\}\s*r1_moment;", hdr)
+    assert re.search(r"\bint\s+r1_render_moments\s*\(\s*r1_context\s*\*\s*\w+\s*,\s*const\s+r1_params\s*\*\s*\w+\s*,\s*float\s*\*\s*\w+\s*,\s*r1_moment\s*\*\s*\w+\s*,"
+                     r"\s*uint64_t\s*\*\s*\w+\s*,\s*double\s*\*\s*\w+\s*\)\s*;", hdr)
+    assert re.search(r"#define R1_ABI_VERSION 4\b", hdr)
+    assert binding.MOMENT_DTYPE.itemsize == 16 and binding.MOMENT_DTYPE.fields["samples"][1] == 12
+    for m in ("render_moments", "render_moments_device"):
+        assert callable(getattr(binding.Renderer, m, None)), m
+    assert callable(getattr(binding, "render_moments_host", None))
+
+
+def test_the_restatement_on_records_whose_arithmetic_is_exact():
+    """Small integers: every operation of the contract is exact but the last multiply, so var is the correctly rounded product of D and the
+    rounded 1 / (n (n - 1)) — and within an ulp of the unbiased variance of the mean, D / (n (n - 1)), computed in rationals."""
+    rec = np.zeros((1, 2, 4, 4), np.float32)
+    rec[0, 0, :, 0] = [0, 1, 2, 5]     # mean 2, D = 4 + 1 + 0 + 9
+    rec[0, 0, :, 1] = [3, 3, 3, 3]     # no variance
+    rec[0, 0, :, 2] = [8, 0, 0, 0]     # mean 2, D = 36 + 4 + 4 + 4
+    rec[0, 1, :, :3] = 7
+    L, mom = mc.moments_of(rec)
+    assert L[0, 0].tolist() == [2.0, 3.0, 2.0] and mom["samples"].tolist() == [[4, 4]]
+    scale = np.float32(1) / np.float32(12)
+    assert mom["var"][0, 0].tolist() == [float(np.float32(14) * scale), 0.0, float(np.float32(48) * scale)]
+    for got, D in zip(mom["var"][0, 0].tolist(), (14, 0, 48)):
+        assert abs(Fraction(got) - Fraction(D, 12)) <= Fraction(float(np.spacing(np.float32(got))))
+    assert mom["var"][0, 1].view(np.uint32).tolist() == [0, 0, 0]
+    # one sample: +0.0f bits whatever the record holds
+    for value in (0.25, np.inf, np.nan, -3.0):
+        one = np.full((1, 1, 1, 4), value, np.float32)
+        assert mc.moments_of(one)[1]["var"].view(np.uint32).tolist() == [[[0, 0, 0]]]
+
+
+@pytest.mark.parametrize("name,w,h,spp", lc.FRAMES, ids=lambda v: str(v))
+def test_host_form_is_the_restatement_on_the_oracles_records(name, w, h, spp):
+    rec, rays = lc.oracle_records(name, w, h, spp)
+    want_L, want = mc.moments_of(rec)
+    lin, mom, got_rays = mc.host_frame(name, w, h, spp)
+    assert mom.dtype == binding.MOMENT_DTYPE and mom.shape == (h, w) and lin.shape == (h, w, 3)
+    assert got_rays == rays
+    assert lc.same_bits(lin, want_L), mc.differing(lin, want_L)
+    assert mc.same_records(mom, want), mc.differing(mom["var"], want["var"])
+    assert (mom["samples"] == spp).all()
+    assert (mom["var"] >= 0).all()  # (so none is NaN either)
+    if spp == 1:
+        assert not mom["var"].view(np.uint32).any()  # +0.0f bits
+    else:
+        assert (mom["var"] > 0).any() and np.isfinite(mom["var"]).all()
+    # the linear frame is r1_render_linear_host's, and the tile fields change nothing
+    sa = lc.scene_arrays(name, w, h)
+    host_lin, host_rays = binding.render_linear_host(lc.cscene(sa), lc.ccamera(sa), r1.make_params(w, h, spp, lc.SEED))
+    assert host_rays == got_rays and lc.same_bits(lin, host_lin)
+    if (w, h) != (200, 100):
+        lin2, mom2, rays2 = binding.render_moments_host(lc.cscene(sa), lc.ccamera(sa), r1.make_params(w, h, spp, lc.SEED, tile_w=16, tile_h=8))
+        assert rays2 == got_rays and lc.same_bits(lin2, lin) and mc.same_records(mom2, mom)
+
+
+def test_the_restatement_at_64_samples_rests_on_the_references_own_records():
+    """samples_large_320x200x64.bin holds records the REFERENCE computed for scattered (pixel, sample) pairs of a 64-sample frame.  For a
+    number of its pixels: the oracle's 64 records contain the reference's own, bit for bit, at the sample indices the file holds; the
+    library's host path (r1_camera_rays + r1_trace_rays_host, what r1_render_moments_host walks) returns the oracle's records; so the
+    restatement at n = 64 is the same on either, and its variances are finite and not negative."""
+    g = r1o.read_golden(os.path.join(GOLD, "samples_large_320x200x64.bin"))
+    w, h, spp, seed, _ = g["hdr"].tolist()
+    assert spp == 64
+    sa = r1o.SceneArrays.from_golden(r1o.read_golden(os.path.join(GOLD, "scene_large_320x200.bin")))
+    pix = g["y"].astype(np.int64) * w + g["x"]
+    order = np.argsort(pix, kind="stable")
+    counts = np.bincount(pix)
+    chosen = list(np.nonzero(counts >= 2)[0][:24]) + list(np.unique(pix)[:40])  # pixels with several held samples, and the first few
+    chosen = sorted(set(int(v) for v in chosen))
+    xs = np.repeat(np.array([v % w for v in chosen], np.int32), spp)
+    ys = np.repeat(np.array([v // w for v in chosen], np.int32), spp)
+    ss = np.tile(np.arange(spp, dtype=np.int32), len(chosen))
+    rgb, rays = r1o.trace_samples(sa, w, h, seed, xs, ys, ss)
+    rec = np.zeros((1, len(chosen), spp, 4), np.float32)
+    rec[0, :, :, :3] = rgb.reshape(len(chosen), spp, 3)
+    held = 0
+    fixture_rgb = g["rgb"].reshape(-1, 3)
+    for i in order:
+        if int(pix[i]) in chosen:
+            k = chosen.index(int(pix[i]))
+            assert rec[0, k, int(g["s"][i]), :3].tobytes() == fixture_rgb[i].tobytes(), (k, int(g["s"][i]))
+            assert int(rays.reshape(len(chosen), spp)[k, int(g["s"][i])]) == int(g["rays"][i])
+            held += 1
+    assert held >= len(chosen) + 24
+    p = r1.make_params(w, h, spp, seed)
+    cam_rays, seeds = binding.camera_rays(lc.ccamera(sa), p, xs, ys, ss)
+    own = binding.trace_rays_host(lc.cscene(sa), cam_rays, seeds, p.max_bounces)
+    own_rec = np.zeros_like(rec)
+    for c, field in enumerate(("r", "g", "b")):
+        own_rec[0, :, :, c] = own[field].reshape(len(chosen), spp)
+    assert own_rec.tobytes() == rec.tobytes()
+    L, mom = mc.moments_of(rec)
+    L2, mom2 = mc.moments_of(own_rec)
+    assert lc.same_bits(L, L2) and mc.same_records(mom, mom2)
+    assert (mom["samples"] == 64).all() and (mom["var"] >= 0).all() and np.isfinite(mom["var"]).all() and (mom["var"] > 0).any()
+
+
+def test_host_form_at_64_samples_is_the_restatement_on_the_oracles_records():
+    """r1_render_moments_host itself at n = 64, on a frame small enough for the CPU"""
+    name, w, h, spp = "large", 24, 15, 64
+    rec, rays = lc.oracle_records(name, w, h, spp)
+    want_L, want = mc.moments_of(rec)
+    lin, mom, got_rays = mc.host_frame(name, w, h, spp)
+    assert got_rays == rays and lc.same_bits(lin, want_L) and mc.same_records(mom, want)
+    assert (mom["samples"] == 64).all() and (mom["var"] >= 0).all() and (mom["var"] > 0).any()
+
+
+def test_host_form_refusals_with_their_texts():
+    L = r1.lib()
+    sa = lc.scene_arrays("small", 16, 8)
+    out = np.full((8, 16, 3), 7, np.float32)
+    mom = np.full((8, 16), 7, binding.MOMENT_DTYPE)
+    rays = C.c_uint64()
+    sc, cam = C.byref(lc.cscene(sa)), C.byref(lc.ccamera(sa))
+    fp, mp = out.ctypes.data_as(C.POINTER(C.c_float)), C.c_void_p(mom.ctypes.data)
+    p = r1.make_params(16, 8, 2)
+    err = lambda: L.r1_last_error().decode()  # noqa: E731
+    for args in ((None, cam, C.byref(p), fp, mp, C.byref(rays)), (sc, None, C.byref(p), fp, mp, C.byref(rays)), (sc, cam, None, fp, mp, C.byref(rays)),
+                 (sc, cam, C.byref(p), None, mp, C.byref(rays)), (sc, cam, C.byref(p), fp, None, C.byref(rays))):
+        assert L.r1_render_moments_host(*args) == binding.R1_EINVAL
+        assert err() == "r1_render_moments_host: null argument"
+    two = r1.make_params(16, 8, 2, shard=0, num_shards=2)
+    assert L.r1_render_moments_host(sc, cam, C.byref(two), fp, mp, C.byref(rays)) == binding.R1_EINVAL
+    assert err() == "r1_render_moments_host renders whole frames (num_shards == 1, not 2)"
+    for bad in (r1.make_params(16, 8, 0), r1.make_params(0, 8, 2), r1.make_params(16, 8, 2, tile_w=0)):  # (r1_params_check's refusal)
+        assert L.r1_render_moments_host(sc, cam, C.byref(bad), fp, mp, C.byref(rays)) == binding.R1_EINVAL
+        assert err().startswith("bad r1_params"), err()
+    assert (out == 7).all() and mom.tobytes() == np.full((8, 16), 7, binding.MOMENT_DTYPE).tobytes()  # nothing written
+    assert L.r1_render_moments_host(sc, cam, C.byref(p), fp, mp, None) == binding.R1_OK  # (the count may be left out)
+    assert (mom["samples"] == 2).all()
+
+
+def test_device_forms_refuse_null_arguments_first_without_a_device():
+    L = r1.lib()
+    p = r1.make_params(16, 8, 2)
+    assert L.r1_render_moments(None, C.byref(p), None, None, None, None) == binding.R1_EINVAL
+    assert L.r1_last_error().decode() == "r1_render_moments: null argument"
+    assert L.r1_render_moments_device(None, C.byref(p), None, None, None, None) == binding.R1_EINVAL
+    assert L.r1_last_error().decode() == "r1_render_moments_device: null argument"
+
+
+def test_census_of_the_moments_kernel():
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import kernel_meta
+    lib = os.path.join(ROOT, "rays1bench_amd", "lib", "librays1.so")
+    if not (os.path.exists(lib) and os.path.exists(kernel_meta.LLVM + "/llvm-objdump")):
+        pytest.skip("no library / no LLVM tools")
+    k = kernel_meta.collect(lib)
+    own = [n for n in k if "r1_resolve_moments_kernel" in n]
+    assert len(own) == 1, own
+    a = k[own[0]]
+    print(own[0], {x: a[x] for x in ("vgpr", "sgpr", "sgpr_spill", "lane_moves", "insts", "lds")})  # (recorded in DESIGN.md §4.40)
+    assert a["v_mfma"] == 0 and a["flat_load"] == 0 and a["flat_store"] == 0, a
+    assert int(a["scratch"]) == 0 and a["scratch_insts"] == 0 and int(a["vgpr_spill"]) == 0 and int(a["sgpr_spill"]) == 0, a
+    assert int(a["vgpr"]) <= 128 and int(a["lds"]) == 0, a  # four waves a SIMD fit

@@ -1,0 +1,245 @@
+// tools/check_denoise_guided_host.cpp — r1_denoise_guided_host (rays1bench_amd/csrc/r1_denoise_guided_host.cpp with r1_denoise_host.cpp, whose
+// check it shares) driven stand-alone: the contract of include/rays1.h "variance-guided denoised frames" once more in plain C loops over
+// dense arrays, with nothing of r1_denoise.h, compared bit for bit on a seeded frame under several sets of options; in place; rows with
+// strides in buffers sized to the last pixel, so a sanitizer sees any access between or behind the rows; the refusals.  Built by
+// tests/test_denoise_guided_host.py with -fsanitize=address,undefined and -ffp-contract=off.  No GPU, no HIP runtime call.
+#include <math.h>
+#include <stdarg.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <vector>
+
+#include "../include/rays1.h"
+#include "../rays1bench_amd/csrc/r1_internal.h"
+
+// (the library's error text lives in r1_capi.cpp, next to the HIP runtime: this program links the host sources only)
+static char g_error[512];
+void r1_set_error(const char *fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_error, sizeof(g_error), fmt, ap);
+    va_end(ap);
+}
+
+#define NEED(c)                                                \
+    do                                                         \
+    {                                                          \
+        if (!(c))                                              \
+        {                                                      \
+            fprintf(stderr, "line %d: %s\n", __LINE__, #c);    \
+            return 1;                                          \
+        }                                                      \
+    } while (0)
+
+// splitmix64: the frame's values
+static uint64_t g_state = 0x9E3779B97F4A7C15ull;
+static uint64_t next_u64()
+{
+    uint64_t z = (g_state += 0x9E3779B97F4A7C15ull);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+static float uniform(float lo, float hi) { return lo + (hi - lo) * (float)((next_u64() >> 40) * (1.0 / 16777216.0)); }
+static bool chance(double p) { return (next_u64() >> 11) * (1.0 / 9007199254740992.0) < p; }
+
+// The contract, dense arrays: L [n][3], f [n], V [n] -> out [n][3]
+static void contract(int w, int h, const r1_denoise_guided_opt &go, const float *L, const r1_feature *f, const r1_moment *V, float *out)
+{
+    const r1_denoise_opt &o = go.base;
+    const size_t n = (size_t)w * h;
+    static const float H[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f}, K3[3] = {0.25f, 0.5f, 0.25f};
+    std::vector<float> a(n * 3), cur(n * 3), nxt(n * 3), nh(n * 3), m(n), v(n), vn(n);
+    std::vector<char> surf(n);
+    for (size_t i = 0; i < n; ++i)
+    {
+        surf[i] = f[i].hits > 0;
+        for (int c = 0; c < 3; ++c)
+        {
+            a[i * 3 + c] = (o.flags & R1_DENOISE_DEMODULATE) ? (f[i].albedo[c] < 1.0f / 256.0f ? 1.0f / 256.0f : f[i].albedo[c]) : 1.0f;
+            cur[i * 3 + c] = surf[i] ? L[i * 3 + c] / a[i * 3 + c] : L[i * 3 + c];
+        }
+        const float nn = (f[i].normal[0] * f[i].normal[0] + f[i].normal[1] * f[i].normal[1]) + f[i].normal[2] * f[i].normal[2];
+        const float l = sqrtf(nn);
+        for (int c = 0; c < 3; ++c)
+            nh[i * 3 + c] = l > 0.0f ? f[i].normal[c] / l : 0.0f;
+        m[i] = surf[i] ? f[i].depth / (float)f[i].hits : 0.0f;
+        v[i] = 0.0f;
+        if (surf[i])
+            v[i] = (V[i].var[0] / (a[i * 3] * a[i * 3]) + V[i].var[1] / (a[i * 3 + 1] * a[i * 3 + 1])) + V[i].var[2] / (a[i * 3 + 2] * a[i * 3 + 2]);
+    }
+    const float sc2 = o.sigma_color * o.sigma_color;
+    for (int it = 0; it < o.iterations; ++it)
+    {
+        const int step = 1 << it;
+        for (int y = 0; y < h; ++y)
+            for (int x = 0; x < w; ++x)
+            {
+                const size_t p = (size_t)y * w + x;
+                for (int c = 0; c < 3; ++c)
+                    nxt[p * 3 + c] = cur[p * 3 + c];
+                vn[p] = v[p];
+                if (!surf[p])
+                    continue;
+                float G = 0.0f, K = 0.0f;
+                for (int dy = -1; dy <= 1; ++dy)
+                    for (int dx = -1; dx <= 1; ++dx)
+                    {
+                        const int qx = x + dx, qy = y + dy;
+                        if (qx < 0 || qx >= w || qy < 0 || qy >= h || !surf[(size_t)qy * w + qx])
+                            continue;
+                        const float k = K3[dy + 1] * K3[dx + 1];
+                        G = G + k * v[(size_t)qy * w + qx];
+                        K = K + k;
+                    }
+                const float g = G / K;
+                const float denc = sc2 * g + go.variance_floor;
+                float S[3] = {0.0f, 0.0f, 0.0f}, W = 0.0f, T = 0.0f;
+                for (int dy = -2; dy <= 2; ++dy)
+                    for (int dx = -2; dx <= 2; ++dx)
+                    {
+                        const int qx = x + dx * step, qy = y + dy * step;
+                        if (qx < 0 || qx >= w || qy < 0 || qy >= h)
+                            continue;
+                        const size_t q = (size_t)qy * w + qx;
+                        if (!surf[q])
+                            continue;
+                        const float hh = H[dy + 2] * H[dx + 2];
+                        float wt = hh;
+                        if (dx != 0 || dy != 0)
+                        {
+                            float c = (nh[p * 3] * nh[q * 3] + nh[p * 3 + 1] * nh[q * 3 + 1]) + nh[p * 3 + 2] * nh[q * 3 + 2];
+                            c = c < 0.0f ? 0.0f : c;
+                            c = c > 1.0f ? 1.0f : c;
+                            for (int j = 0; j < o.normal_power_log2; ++j)
+                                c = c * c;
+                            const float mx = m[p] < m[q] ? m[q] : m[p];
+                            const float den = o.sigma_depth * mx;
+                            const float rz = den > 0.0f ? (m[p] - m[q]) / den : 0.0f;
+                            const float xz = rz * rz;
+                            const float dr = cur[p * 3] - cur[q * 3], dg = cur[p * 3 + 1] - cur[q * 3 + 1], db = cur[p * 3 + 2] - cur[q * 3 + 2];
+                            const float dc = (dr * dr + dg * dg) + db * db;
+                            const float xc = dc / denc;
+                            wt = (hh * c) / ((1.0f + xz) * (1.0f + xc));
+                        }
+                        for (int c = 0; c < 3; ++c)
+                            S[c] = S[c] + wt * cur[q * 3 + c];
+                        W = W + wt;
+                        T = T + (wt * wt) * v[q];
+                    }
+                for (int c = 0; c < 3; ++c)
+                    nxt[p * 3 + c] = S[c] / W;
+                vn[p] = T / (W * W);
+            }
+        cur.swap(nxt), v.swap(vn);
+    }
+    for (size_t i = 0; i < n; ++i)
+        for (int c = 0; c < 3; ++c)
+            out[i * 3 + c] = surf[i] ? cur[i * 3 + c] * a[i * 3 + c] : cur[i * 3 + c];
+}
+
+static bool same_bits(const float *a, const float *b, size_t n) { return memcmp(a, b, n * sizeof(float)) == 0; }
+
+int main()
+{
+    const int w = 37, h = 21;
+    const size_t n = (size_t)w * h;
+    std::vector<float> L(n * 3);
+    std::vector<r1_feature> f(n);
+    std::vector<r1_moment> V(n);
+    for (size_t i = 0; i < n; ++i)
+    {
+        r1_feature &r = f[i];
+        memset(&r, 0, sizeof(r));
+        r.hits = chance(0.08) ? 0u : 1u + (uint32_t)(next_u64() % 4);
+        for (int c = 0; c < 3; ++c)
+        {
+            r.albedo[c] = chance(0.05) ? 0.0f : chance(0.05) ? 1.0f / 1024.0f : uniform(0.05f, 1.0f);
+            L[i * 3 + c] = r.albedo[c] * uniform(0.0f, 2.0f) + uniform(0.0f, 0.05f);
+            r.normal[c] = r.hits ? uniform(-1.0f, 1.0f) * (float)r.hits : 0.0f;
+            const float s = uniform(0.0f, 0.05f);
+            V[i].var[c] = r.hits == 0 ? NAN : chance(0.1) ? 0.0f : chance(0.03) ? 1e30f : chance(0.05) ? 1e-41f : s * s;
+        }
+        r.depth = r.hits ? (chance(0.5) ? 2.5f : uniform(0.5f, 20.0f)) * (float)r.hits : 0.0f;
+        V[i].samples = 4;
+    }
+    // a hit pixel whose eight neighbours have none
+    for (int dy = -1; dy <= 1; ++dy)
+        for (int dx = -1; dx <= 1; ++dx)
+            if (dx || dy)
+            {
+                const size_t q = (size_t)(10 + dy) * w + 20 + dx;
+                f[q].hits = 0, V[q].var[0] = V[q].var[1] = V[q].var[2] = NAN;
+            }
+    f[(size_t)10 * w + 20].hits = 2, f[(size_t)10 * w + 20].depth = 5.0f, f[(size_t)10 * w + 20].normal[2] = 2.0f;
+    for (int c = 0; c < 3; ++c)
+        V[(size_t)10 * w + 20].var[c] = 1e-4f;
+
+    const r1_denoise_guided_frame dense = {w, h, 0, 0, 0, 0};
+    const r1_denoise_guided_opt sets[5] = {{{3, 6, 2.0f, 0.1f, R1_DENOISE_DEMODULATE}, 1e-4f, 0u},
+                                           {{1, 0, 1e-3f, 1e-3f, 0u}, 1e-30f, 0u},
+                                           {{8, 10, 1e3f, 1e3f, R1_DENOISE_DEMODULATE}, 1e30f, 0u},
+                                           {{5, 4, 1.0f, 0.5f, 0u}, 1e-6f, 0u},
+                                           {{4, 6, 4.0f, 0.1f, R1_DENOISE_DEMODULATE}, 1e-6f, 0u}};
+    std::vector<float> want(n * 3), got(n * 3);
+    for (const r1_denoise_guided_opt &o : sets)
+    {
+        contract(w, h, o, L.data(), f.data(), V.data(), want.data());
+        NEED(r1_denoise_guided_host(&dense, &o, L.data(), f.data(), V.data(), got.data()) == R1_OK);
+        NEED(same_bits(got.data(), want.data(), n * 3));
+        for (size_t i = 0; i < n; ++i)
+            if (f[i].hits == 0)
+                NEED(same_bits(&got[i * 3], &L[i * 3], 3));
+        std::vector<float> work(L); // in place
+        NEED(r1_denoise_guided_host(&dense, &o, work.data(), f.data(), V.data(), work.data()) == R1_OK);
+        NEED(same_bits(work.data(), want.data(), n * 3));
+    }
+    printf("every value the contract's under 5 sets of options, also in place\n");
+
+    // strides, in buffers that end with the last pixel of the last row
+    const r1_denoise_guided_frame st = {w, h, 40, 38, 41, 42};
+    const r1_denoise_guided_opt &o = sets[0];
+    contract(w, h, o, L.data(), f.data(), V.data(), want.data());
+    std::vector<float> Ls((size_t)(h - 1) * st.linear_stride * 3 + (size_t)w * 3, -7.0f), outs((size_t)(h - 1) * st.out_stride * 3 + (size_t)w * 3, -7.0f);
+    std::vector<r1_feature> fs((size_t)(h - 1) * st.feature_stride + w);
+    std::vector<r1_moment> Vs((size_t)(h - 1) * st.moment_stride + w);
+    memset(fs.data(), 0xA5, fs.size() * sizeof(r1_feature));
+    memset(Vs.data(), 0xA5, Vs.size() * sizeof(r1_moment));
+    for (int y = 0; y < h; ++y)
+    {
+        memcpy(&Ls[(size_t)y * st.linear_stride * 3], &L[(size_t)y * w * 3], (size_t)w * 12);
+        memcpy(&fs[(size_t)y * st.feature_stride], &f[(size_t)y * w], (size_t)w * sizeof(r1_feature));
+        memcpy(&Vs[(size_t)y * st.moment_stride], &V[(size_t)y * w], (size_t)w * sizeof(r1_moment));
+    }
+    NEED(r1_denoise_guided_host(&st, &o, Ls.data(), fs.data(), Vs.data(), outs.data()) == R1_OK);
+    for (int y = 0; y < h; ++y)
+    {
+        NEED(same_bits(&outs[(size_t)y * st.out_stride * 3], &want[(size_t)y * w * 3], (size_t)w * 3));
+        if (y + 1 < h)
+            for (int x = w * 3; x < st.out_stride * 3; ++x)
+                NEED(outs[(size_t)y * st.out_stride * 3 + x] == -7.0f);
+    }
+    printf("strides 40, 38, 41, 42: the rows' values, nothing between them\n");
+
+    // refusals: the check first, then the pointers; nothing written
+    std::vector<float> sentinel(n * 3, 3.0f);
+    r1_denoise_guided_opt bad = o;
+    bad.variance_floor = 0.0f;
+    NEED(r1_denoise_guided_host(&dense, &bad, L.data(), f.data(), V.data(), sentinel.data()) == R1_EINVAL && strstr(g_error, "variance_floor"));
+    bad = o, bad.reserved = 1u;
+    NEED(r1_denoise_guided_host(&dense, &bad, L.data(), f.data(), V.data(), sentinel.data()) == R1_EINVAL && strstr(g_error, "reserved"));
+    bad = o, bad.base.flags = 2u;
+    NEED(r1_denoise_guided_host(&dense, &bad, L.data(), f.data(), V.data(), sentinel.data()) == R1_EINVAL && strstr(g_error, "flags"));
+    r1_denoise_guided_frame badf = dense;
+    badf.moment_stride = w - 1;
+    NEED(r1_denoise_guided_host(&badf, &o, L.data(), f.data(), V.data(), sentinel.data()) == R1_EINVAL && strstr(g_error, "moment_stride"));
+    NEED(r1_denoise_guided_host(&dense, &o, L.data(), f.data(), nullptr, sentinel.data()) == R1_EINVAL && strstr(g_error, "V is NULL"));
+    NEED(r1_denoise_guided_host(nullptr, &o, L.data(), f.data(), V.data(), sentinel.data()) == R1_EINVAL);
+    for (const float s : sentinel)
+        NEED(s == 3.0f);
+    printf("refusals wrote nothing\n");
+    return 0;
+}

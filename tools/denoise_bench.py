@@ -74,12 +74,56 @@ def composition(L, f, o):
     return torch.where(surf[..., None], cur * a, L)
 
 
+def guided_section(args, rend, st, say, timed, seed, spp):
+    """r1_denoise_guided_device beside r1_denoise_device at 3 and 5 iterations, then its passes one by one; 56 bytes a pixel a pass: two
+    16-byte records and v read once, a record and v written."""
+    say()
+    say(f"variance-guided filter (sigma_color 2, variance_floor 1e-4) beside the unguided one; R1_VFILTER_STAGE_MAX_STEP={os.environ.get('R1_VFILTER_STAGE_MAX_STEP', '-')}")
+    for w, h in ((1200, 800), (1920, 1080)):
+        rend.set_scene(r1.create_large_scene(w, h))
+        p = r1.make_params(w, h, spp, seed, variant=binding.VARIANT_BVH)
+        L = torch.zeros((h, w, 3), dtype=torch.float32, device="cuda")
+        f = torch.zeros((h, w, 8), dtype=torch.float32, device="cuda")
+        V = torch.zeros((h, w, 4), dtype=torch.float32, device="cuda")
+        out = torch.zeros((h, w, 3), dtype=torch.float32, device="cuda")
+        cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()
+        rend.render_moments_device(p, L.data_ptr(), V.data_ptr(), cnt.data_ptr(), stream_ptr=st.cuda_stream)
+        rend.render_features_device(p, f.data_ptr(), stream_ptr=st.cuda_stream)
+        st.synchronize()
+        say(f"{w}x{h}")
+
+        def guided(i):
+            return lambda: rend.denoise_guided_device(w, h, binding.make_denoise_guided_opt(iterations=i), L.data_ptr(), f.data_ptr(), V.data_ptr(), out.data_ptr(),
+                                                      stream_ptr=st.cuda_stream)
+
+        def plain(i):
+            return lambda: rend.denoise_device(w, h, binding.make_denoise_opt(iterations=i), L.data_ptr(), f.data_ptr(), out.data_ptr(), stream_ptr=st.cuda_stream)
+
+        for it in (3, 5):
+            forms = [(f"r1_denoise_device, {it} iterations", plain(it)), (f"r1_denoise_guided_device, {it} iterations", guided(it))]
+            res = timed(forms, st)
+            for name, _ in forms:
+                v = res[name]
+                say(f"  {name:<44} {statistics.median(v) * 1e3:9.3f} ({min(v) * 1e3:.3f} .. {max(v) * 1e3:.3f}) ms")
+        forms = [(i, guided(i)) for i in range(1, 7)]
+        res = timed(forms, st)
+        med = {i: statistics.median(res[i]) for i, _ in forms}
+        say(f"  guided passes: prepare + pass of step 1 {med[1] * 1e3:.3f} ms (one iteration); 56 bytes a pixel = {56 * w * h / 1e6:.1f} MB a pass")
+        for i in range(1, 6):
+            dt = med[i + 1] - med[i]
+            say(f"    pass of step {1 << i:<2} {dt * 1e3:8.3f} ms  {56 * w * h / dt / 1e12 if dt > 0 else float('nan'):6.3f} TB/s of the 56-byte floor"
+                f"   ({i + 1} iterations {med[i + 1] * 1e3:.3f} ms, {min(res[i + 1]) * 1e3:.3f} .. {max(res[i + 1]) * 1e3:.3f})")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--out", default=None, help="also write the report to this file")
     ap.add_argument("--lib", default=None)
     ap.add_argument("--only-denoise", action="store_true", help="form (a) and its passes alone (for comparing builds and R1_DENOISE_STAGE_MAX_STEP)")
+    ap.add_argument("--guided", action="store_true", help="also the variance-guided filter beside the unguided one (DESIGN.md §4.40); with --lib "
+                    "librays1_tuning.so R1_VFILTER_STAGE_MAX_STEP says up to which step its passes stage their taps in LDS (0: never)")
     args = ap.parse_args()
     if args.lib:
         binding.set_lib_path(os.path.abspath(args.lib))
@@ -156,6 +200,8 @@ def main():
             dt = med[i + 1] - med[i]
             say(f"    pass of step {1 << i:<2} {dt * 1e3:8.3f} ms  {48 * w * h / dt / 1e12 if dt > 0 else float('nan'):6.3f} TB/s of the 48-byte floor"
                 f"   ({i + 1} iterations {med[i + 1] * 1e3:.3f} ms, {min(res[i + 1]) * 1e3:.3f} .. {max(res[i + 1]) * 1e3:.3f})")
+    if args.guided:
+        guided_section(args, rend, st, say, timed, seed, spp)
     rend.close()
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
