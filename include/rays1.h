@@ -703,6 +703,151 @@ int r1_render_denoised_guided(r1_context *ctx, const r1_params *params, const r1
 int r1_render_denoised_guided_device(r1_context *ctx, const r1_params *params, const r1_denoise_guided_opt *opt, void *d_rgb_f32,
                                      void *d_num_rays, void *hip_stream);
 
+/* ---- accumulated frames: history reprojected along a camera path ---- */
+
+/* Temporal accumulation, the stage in front of the filters above: each pixel of the current frame looks up where its surface point was on
+ * the PREVIOUS frame's screen, fetches the history there if the surfaces agree, and blends.  No new record type: a history is a previous
+ * call's outputs (A: three floats a pixel, M: r1_moment with `samples` = the history's length) plus that frame's feature frame and camera.
+ * One fp32 contract; r1_accumulate_host defines it and the device forms equal it bit for bit.  Plain fp32; every + - * / and sqrtf below is
+ * one correctly rounded operation in the order written, nothing is fused, min / max / abs / clamp are selects, subnormal values are kept,
+ * and floorf (exact) is the only library call.  a . b is (a.x*b.x + a.y*b.y) + a.z*b.z.
+ *   inputs    the current frame: L and V (r1_render_moments) and f (r1_render_features) and the camera `cam` they were rendered through;
+ *             the history: A_prev, f_prev, M_prev and the camera `prev` of that frame; spp of the current render and spp_prev of the render
+ *             that made f_prev — they scale `depth` back to a distance, and nothing else.
+ *   plan      r1_reproject_plan, once per call, on the host, shared by both forms.  From prev, with dl = lower_left - origin:
+ *             pu = dl . u;  pv = dl . v;  pw = dl . w;  hu = horizontal . u;  vv = vertical . v;
+ *             inv_w = 1.0f / (float)width;  inv_h = 1.0f / (float)height (as the renders form them).
+ *             pw, hu or vv zero or not finite: R1_EINVAL naming camera_prev.
+ *   pixel (x, y):  n = V.samples
+ *     no surface   f.hits == 0 or n == 0: A_out has L's bits and M_out has V's bits.  (hits == 0: every sample saw the sky of its primary
+ *                  ray, the pixel is free of noise, as for the filters.)
+ *     world point  s = ((float)x + 0.5f) * inv_w;  t = ((float)y + 0.5f) * inv_h
+ *                  d = ((cam.lower_left + cam.horizontal * s) + cam.vertical * t) - cam.origin     (camera_ray_at's order, no lens offset)
+ *                  dh = d / sqrtf(d . d)  (one division per component);  m = (f.depth / (float)f.hits) * (float)spp;  P = cam.origin + dh * m
+ *                  A PINHOLE reconstruction: the lens offsets of the samples are ignored, so with an aperture P is the point in focus
+ *                  only to first order, and the depth test below is what forgives it.
+ *     previous     q = P - prev.origin;  a = q . prev.u;  b = q . prev.v;  c = q . prev.w
+ *     screen       the point is in front of the previous camera iff c * pw > 0 (a NaN fails)
+ *     position     k = pw / c;  sx = (a * k - pu) / hu;  sy = (b * k - pv) / vv
+ *                  px = sx * (float)width - 0.5f;  py = sy * (float)height - 0.5f
+ *                  history exists only if px > -1 && px < (float)width && py > -1 && py < (float)height — comparisons of floats: NaN and
+ *                  +-inf fail BEFORE any conversion to an integer
+ *                  x0 = (int)floorf(px);  fx = px - floorf(px);  y0 and fy likewise
+ *     expected     e = sqrtf(q . q)
+ *     taps         B = 0, C = 0, U = 0, N = 2^32 - 1; (j, i) in {0, 1}^2, j in the outer loop, the tap at (x0 + i, y0 + j) with the bilinear
+ *                  weight b = (i ? fx : 1 - fx) * (j ? fy : 1 - fy).  A tap is skipped if it is off the image (tested on the integers,
+ *                  first); or b is not > 0; or f_prev.hits == 0; or M_prev.samples == 0; or, with
+ *                  m_q = (f_prev.depth / (float)f_prev.hits) * (float)spp_prev, t = e - m_q, t = t < 0 ? -t : t, mx = e < m_q ? m_q : e,
+ *                  not t <= depth_tolerance * mx (a NaN skips); or nh . nh_q < normal_min_cos, nh the unit normal by the filters' prepare
+ *                  rule (zero where the normals cancel).  A tap taken: B = B + b;  C_c = C_c + b * A_prev_c;  U_c = U_c + b * M_prev.var_c;
+ *                  N = M_prev.samples < N ? M_prev.samples : N
+ *     blend        if B > 0: hist = C / B;  vh = U / B;  N_new = max(n, min(N + n, max_samples)) in 64 bits (N near 2^32 cannot wrap);
+ *                  alpha = n >= N_new ? 1.0f : (float)n / (float)N_new;  A_out = hist + (L - hist) * alpha;
+ *                  var_out = ((1 - alpha) * (1 - alpha)) * vh + (alpha * alpha) * V.var;  samples_out = N_new.
+ *                  Otherwise the pixel is as for "no surface".
+ * The b-weighted mean of the four history variances is a deliberate approximation: the four pixels share samples of earlier frames, so
+ * they are correlated and the true variance of the mean is not the mean of the variances; it errs towards a larger variance.
+ * Addresses DO depend on pixel data here, which the filters' contracts rule out.  The guard order above is what keeps them on the image:
+ * the float comparisons on px and py come first and fail for NaN and infinities, floorf's results are then integers in -1 .. width - 1 and
+ * -1 .. height - 1, and each tap's (x0 + i, y0 + j) is tested against the image before an address is formed from it.  Every tap address is
+ * formed from integers already tested to lie on the image; non-finite or absurd input loses its history and cannot fault.
+ * Aliasing: the call is a gather, so A_out / M_out must not overlap A_prev / M_prev / f_prev — equal pointers are refused (R1_EINVAL).
+ * A_out may be L and M_out may be V: a pixel's own records are consumed before its outputs are written.
+ * Moving spheres need no motion vectors in this contract: a point on a sphere that moved re-projects to where the sphere was not, and
+ * the depth and normal tests drop that history — the pixel starts again from its own samples.  Per-sphere motion vectors, which would keep
+ * it, are out of scope.
+ * What to choose (tools/accumulate_prototype.py on the medium scene): max_samples 32, depth_tolerance 0.05,
+ * normal_min_cos 0.9. */
+typedef struct r1_accumulate_opt
+{
+    uint32_t max_samples;  /* >= 1: the cap of the history length; it turns the running mean into an exponential one */
+    float depth_tolerance; /* > 0, finite: relative to the larger of the two distances */
+    float normal_min_cos;  /* finite, -1 .. 1 */
+    uint32_t flags;        /* 0 */
+} r1_accumulate_opt;
+
+/* The eight images of a call: width x height pixels each, rows `*_stride` PIXELS apart (three floats of L, A_prev and A_out, one record of
+ * the others); a stride of 0 means width.  Nothing between the rows is read or written. */
+typedef struct r1_accumulate_frame
+{
+    int32_t width, height;
+    int32_t linear_stride, moment_stride, feature_stride;                /* L, V, f */
+    int32_t prev_stride, prev_feature_stride, prev_moment_stride;        /* A_prev, f_prev, M_prev */
+    int32_t out_stride, out_moment_stride;                               /* A_out, M_out */
+} r1_accumulate_frame;
+
+/* Through what the two frames were rendered */
+typedef struct r1_accumulate_view
+{
+    r1_camera camera;      /* of L, V and f */
+    r1_camera camera_prev; /* of the history */
+    int32_t spp;           /* >= 1: of the render that made f */
+    int32_t spp_prev;      /* >= 1: of the render that made f_prev */
+} r1_accumulate_view;
+
+/* The images: host memory for r1_accumulate_host and r1_accumulate, device memory for r1_accumulate_device */
+typedef struct r1_accumulate_images
+{
+    const void *L;      /* float[3] a pixel */
+    const void *V;      /* r1_moment */
+    const void *f;      /* r1_feature */
+    const void *A_prev; /* float[3] a pixel */
+    const void *f_prev; /* r1_feature */
+    const void *M_prev; /* r1_moment */
+    void *A_out;        /* float[3] a pixel; may be L */
+    void *M_out;        /* r1_moment; may be V */
+} r1_accumulate_images;
+
+/* What one call computes once for all of its pixels (the "plan" above) */
+typedef struct r1_reproject_plan
+{
+    float pu, pv, pw, hu, vv, inv_w, inv_h;
+} r1_reproject_plan;
+
+/* The rules of the three structs, pure arithmetic, the one place they are checked: R1_EINVAL names the offending field (width, height, a
+ * stride that is neither 0 nor >= width, max_samples, depth_tolerance, normal_min_cos, flags, spp, spp_prev, camera_prev when the plan is
+ * unusable), R1_ELIMIT at width * height >= 2^31.  plan_out (may be NULL) receives the plan. */
+int r1_accumulate_check(const r1_accumulate_frame *frame, const r1_accumulate_opt *opt, const r1_accumulate_view *view, r1_reproject_plan *plan_out);
+
+/* The definition: the contract above on the CPU, no device.  Refusals: the check; then a NULL image; then an output equal to a history
+ * image. */
+int r1_accumulate_host(const r1_accumulate_frame *frame, const r1_accumulate_opt *opt, const r1_accumulate_view *view, const r1_accumulate_images *images);
+
+/* The same on DEVICE memory: L, A_prev and A_out 4-byte aligned, the feature and moment images 16-byte aligned.  One launch, enqueued on
+ * `hip_stream` (NULL = the context's stream), nothing is waited for.  It needs no workspace: any number of calls may be in flight.  Like
+ * the filters it changes no state a render reads and needs no scene.  Refusals, in this order: ctx NULL; the check; then pointers,
+ * alignment and aliasing.  A refused call enqueues nothing. */
+int r1_accumulate_device(r1_context *ctx, const r1_accumulate_frame *frame, const r1_accumulate_opt *opt, const r1_accumulate_view *view,
+                         const r1_accumulate_images *d_images, void *hip_stream);
+
+/* The same on HOST memory, synchronous: the six inputs go up, the two outputs come home; device_seconds_out (may be NULL) is the kernel's
+ * time alone. */
+int r1_accumulate(r1_context *ctx, const r1_accumulate_frame *frame, const r1_accumulate_opt *opt, const r1_accumulate_view *view,
+                  const r1_accumulate_images *images, double *device_seconds_out);
+
+/* The composed, stateful form: on one stream r1_render_moments_device, then r1_render_features_device, then the accumulation against the
+ * CONTEXT'S history, which the call then replaces by its own unfiltered result, feature frame, camera and spp.  guided_opt NULL: rgb_out is
+ * the accumulated frame.  Otherwise r1_denoise_guided_device filters the ACCUMULATED frame with the accumulated variance and the current
+ * features into rgb_out (the history keeps the unfiltered accumulation), and params->spp < 2 is R1_EINVAL as in r1_render_denoised_guided;
+ * without the filter any spp is served.  "Previous camera" is the context's camera at the previous accumulated call, "current" the
+ * context's camera now, as r1_set_scene or r1_set_camera left it.  The history is empty — the frame passes through unchanged, rgb_out is
+ * r1_render_moments' frame — on the first call, after r1_accumulate_reset, after r1_set_scene, and when width or height differ from the
+ * history's; r1_update_*, r1_resort_spheres and r1_regrid keep it.  A previous camera through which nothing can be projected also passes
+ * the frame through.  The history (60 bytes a pixel, twice) lives in a workspace of the context that grows on first use; the calls of a
+ * context are ordered by one stream, or by the caller.  Variants and refusal order are r1_render_denoised_guided's: ctx NULL; params or
+ * acc_opt NULL, the params, the options, the variant, spp with a filter; pointers and alignment; then what r1_render_moments refuses.  A
+ * refused call enqueues nothing and keeps the history.  The state left is r1_render_moments': launch info and timing describe the frame,
+ * a progressive accumulation survives.  Synchronous; device_seconds_out (may be NULL): everything enqueued. */
+int r1_render_accumulated(r1_context *ctx, const r1_params *params, const r1_accumulate_opt *acc_opt, const r1_denoise_guided_opt *guided_opt,
+                          float *rgb_out, uint64_t *num_rays_out, double *device_seconds_out);
+
+/* The same into DEVICE memory (d_rgb_f32 4-byte aligned, d_num_rays 8-byte aligned), enqueued on `hip_stream`, waits for nothing. */
+int r1_render_accumulated_device(r1_context *ctx, const r1_params *params, const r1_accumulate_opt *acc_opt, const r1_denoise_guided_opt *guided_opt,
+                                 void *d_rgb_f32, void *d_num_rays, void *hip_stream);
+
+/* Forgets the context's history: the next accumulated frame passes through.  Waits for nothing, frees nothing. */
+int r1_accumulate_reset(r1_context *ctx);
+
 /* Pipelined form of r1_render — frames in flight whose results land on the HOST.  The reference times
  * dispatch -> pixels + ray count on the host (rayweek1.cpp:848 -> :891) for ONE frame and waits; a caller that
  * renders frame after frame (main's `-n` runs, rayweek1.cpp:969-984) can keep several in flight instead: the call

@@ -128,6 +128,46 @@ def make_denoise_guided_opt(iterations=3, normal_power_log2=6, sigma_color=2.0, 
     return DenoiseGuidedOpt(DenoiseOpt(int(iterations), int(normal_power_log2), float(sigma_color), float(sigma_depth), int(flags)), float(variance_floor), int(reserved))
 
 
+class AccumulateOpt(C.Structure):
+    """r1_accumulate_opt: max_samples >= 1, depth_tolerance > 0 and finite, normal_min_cos in -1 .. 1, flags 0."""
+    _fields_ = [("max_samples", C.c_uint32), ("depth_tolerance", C.c_float), ("normal_min_cos", C.c_float), ("flags", C.c_uint32)]
+
+
+class AccumulateFrame(C.Structure):
+    """r1_accumulate_frame: the size of the eight images and the pixels between two rows of each (0 = width)."""
+    _fields_ = [(n, C.c_int32) for n in ("width", "height", "linear_stride", "moment_stride", "feature_stride", "prev_stride", "prev_feature_stride",
+                                         "prev_moment_stride", "out_stride", "out_moment_stride")]
+
+
+class AccumulateView(C.Structure):
+    """r1_accumulate_view: the cameras and the spp of the current frame and of the history."""
+    _fields_ = [("camera", CCamera), ("camera_prev", CCamera), ("spp", C.c_int32), ("spp_prev", C.c_int32)]
+
+
+class AccumulateImages(C.Structure):
+    """r1_accumulate_images: L, V, f, A_prev, f_prev, M_prev, A_out, M_out — host or device addresses."""
+    _fields_ = [(n, C.c_void_p) for n in ("L", "V", "f", "A_prev", "f_prev", "M_prev", "A_out", "M_out")]
+
+
+class ReprojectPlan(C.Structure):
+    """r1_reproject_plan: what one accumulation computes once for all of its pixels."""
+    _fields_ = [(n, C.c_float) for n in ("pu", "pv", "pw", "hu", "vv", "inv_w", "inv_h")]
+
+
+def make_accumulate_opt(max_samples=32, depth_tolerance=0.05, normal_min_cos=0.9, flags=0):
+    """The options of an accumulation; the defaults are the ones DESIGN.md §4.41 chose on the medium scene."""
+    return AccumulateOpt(int(max_samples), float(depth_tolerance), float(normal_min_cos), int(flags))
+
+
+def make_accumulate_view(camera, camera_prev, spp, spp_prev):
+    """r1_accumulate_view of two CCamera (copied) and the spp of the two renders."""
+    v = AccumulateView()
+    C.memmove(C.byref(v.camera), C.byref(camera), C.sizeof(CCamera))
+    C.memmove(C.byref(v.camera_prev), C.byref(camera_prev), C.sizeof(CCamera))
+    v.spp, v.spp_prev = int(spp), int(spp_prev)
+    return v
+
+
 def make_denoise_opt(iterations=3, normal_power_log2=6, sigma_color=1.0, sigma_depth=0.1, flags=DENOISE_DEMODULATE):
     """The options DESIGN.md §4.39 measured at 1-4 spp; at 16 spp and more, iterations=1."""
     return DenoiseOpt(int(iterations), int(normal_power_log2), float(sigma_color), float(sigma_depth), int(flags))
@@ -317,6 +357,13 @@ SYMBOLS = [
     ("r1_denoise_guided", C.c_int, [_ctx, C.POINTER(DenoiseGuidedFrame), C.POINTER(DenoiseGuidedOpt), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _dblp]),
     ("r1_render_denoised_guided", C.c_int, [_ctx, C.POINTER(Params), C.POINTER(DenoiseGuidedOpt), C.c_void_p, _u64p, _dblp]),
     ("r1_render_denoised_guided_device", C.c_int, [_ctx, C.POINTER(Params), C.POINTER(DenoiseGuidedOpt), C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("r1_accumulate_check", C.c_int, [C.POINTER(AccumulateFrame), C.POINTER(AccumulateOpt), C.POINTER(AccumulateView), C.POINTER(ReprojectPlan)]),
+    ("r1_accumulate_host", C.c_int, [C.POINTER(AccumulateFrame), C.POINTER(AccumulateOpt), C.POINTER(AccumulateView), C.POINTER(AccumulateImages)]),
+    ("r1_accumulate_device", C.c_int, [_ctx, C.POINTER(AccumulateFrame), C.POINTER(AccumulateOpt), C.POINTER(AccumulateView), C.POINTER(AccumulateImages), C.c_void_p]),
+    ("r1_accumulate", C.c_int, [_ctx, C.POINTER(AccumulateFrame), C.POINTER(AccumulateOpt), C.POINTER(AccumulateView), C.POINTER(AccumulateImages), _dblp]),
+    ("r1_render_accumulated", C.c_int, [_ctx, C.POINTER(Params), C.POINTER(AccumulateOpt), C.POINTER(DenoiseGuidedOpt), C.c_void_p, _u64p, _dblp]),
+    ("r1_render_accumulated_device", C.c_int, [_ctx, C.POINTER(Params), C.POINTER(AccumulateOpt), C.POINTER(DenoiseGuidedOpt), C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("r1_accumulate_reset", C.c_int, [_ctx]),
     ("r1_pfm_write_rgb32f", C.c_int, [C.c_char_p, C.c_int32, C.c_int32, _f32p]),
     ("r1_tga_write_rgb24", C.c_int, [C.c_char_p, C.c_int32, C.c_int32, _u8p]),
     ("r1_log_results", C.c_int, [C.c_char_p, C.c_char_p, _dblp, _u64p, C.c_int32]),
@@ -755,6 +802,41 @@ class Renderer:
         """r1_render_denoised_guided_device: the same into device memory (width * height * 3 floats, and one uint64); waits for nothing."""
         _check(lib().r1_render_denoised_guided_device(self._c, C.byref(params), C.byref(opt), C.c_void_p(d_rgb_f32_ptr or None), C.c_void_p(d_rays_ptr or None),
                                                       _stream_arg(stream_ptr)))
+
+    def accumulate(self, L, V, f, A_prev, f_prev, M_prev, view, opt, A_out=None, M_out=None):
+        """r1_accumulate: the accumulation of the frame (L, V, f) against the history (A_prev, f_prev, M_prev), host memory, synchronous;
+        arrays and outputs as for accumulate_host.  Returns (A_out, M_out, device seconds of the kernel)."""
+        fr, im, A_out, M_out, keep = _accumulate_target(L, V, f, A_prev, f_prev, M_prev, A_out, M_out)
+        secs = C.c_double()
+        _check(lib().r1_accumulate(self._c, C.byref(fr), C.byref(opt), C.byref(view), C.byref(im), C.byref(secs)))
+        return A_out, M_out, secs.value
+
+    def accumulate_device(self, width, height, view, opt, d_L_ptr, d_V_ptr, d_f_ptr, d_A_prev_ptr, d_f_prev_ptr, d_M_prev_ptr, d_A_out_ptr, d_M_out_ptr,
+                          stream_ptr=None, strides=None):
+        """r1_accumulate_device: the same on device memory (L, A_prev, A_out 4-byte aligned, the feature and moment images 16-byte aligned;
+        A_out may be L, M_out may be V); `strides`: eight pixel pitches in the order of the pointers (0 = width); enqueued on stream_ptr,
+        waits for nothing."""
+        fr = AccumulateFrame(int(width), int(height), *[int(v) for v in (strides or (0,) * 8)])
+        im = AccumulateImages(*[p or None for p in (d_L_ptr, d_V_ptr, d_f_ptr, d_A_prev_ptr, d_f_prev_ptr, d_M_prev_ptr, d_A_out_ptr, d_M_out_ptr)])
+        _check(lib().r1_accumulate_device(self._c, C.byref(fr), C.byref(opt), C.byref(view), C.byref(im), _stream_arg(stream_ptr)))
+
+    def render_accumulated(self, params, acc_opt, guided_opt=None):
+        """r1_render_accumulated: the frame rendered with its variance and feature frames, accumulated against the context's history and,
+        with guided_opt, filtered.  Returns (float32 (height, width, 3), ray count, device seconds of everything)."""
+        img = np.zeros((max(params.height, 1), max(params.width, 1), 3), np.float32)
+        rays, secs = C.c_uint64(), C.c_double()
+        _check(lib().r1_render_accumulated(self._c, C.byref(params), C.byref(acc_opt), C.byref(guided_opt) if guided_opt is not None else None,
+                                           C.c_void_p(img.ctypes.data), C.byref(rays), C.byref(secs)))
+        return img, int(rays.value), secs.value
+
+    def render_accumulated_device(self, params, acc_opt, guided_opt, d_rgb_f32_ptr, d_rays_ptr, stream_ptr=None):
+        """r1_render_accumulated_device: the same into device memory (width * height * 3 floats, and one uint64); waits for nothing."""
+        _check(lib().r1_render_accumulated_device(self._c, C.byref(params), C.byref(acc_opt), C.byref(guided_opt) if guided_opt is not None else None,
+                                                  C.c_void_p(d_rgb_f32_ptr or None), C.c_void_p(d_rays_ptr or None), _stream_arg(stream_ptr)))
+
+    def accumulate_reset(self):
+        """r1_accumulate_reset: the context's history is forgotten; the next accumulated frame passes through."""
+        _check(lib().r1_accumulate_reset(self._c))
 
     def render_linear_async(self, params, frame_ptr, rays_ptr, stream_ptr=None):
         """r1_render_linear_async: enqueue one linear frame (throughput kernels); width * height * 3 floats land at `frame_ptr` and the
@@ -1488,6 +1570,41 @@ def denoise_guided_host(L, f, V, opt, out=None):
     _check(lib().r1_denoise_guided_host(C.byref(fr), C.byref(opt), C.c_void_p(L.ctypes.data), C.c_void_p(f.ctypes.data), C.c_void_p(V.ctypes.data),
                                         C.c_void_p(out.ctypes.data)))
     return out
+
+
+def _accumulate_target(L, V, f, A_prev, f_prev, M_prev, A_out, M_out):
+    """(AccumulateFrame, AccumulateImages, A_out, M_out, the arrays kept alive) of a host-memory accumulation: the pitches of the eight arrays
+    become the frame's strides; an output that is None: a new dense array"""
+    h, w = L.shape[:2]
+    if A_out is None:
+        A_out = np.zeros((h, w, 3), np.float32)
+    if M_out is None:
+        M_out = np.zeros((h, w), MOMENT_DTYPE)
+    spec = (("L", L, np.float32, (3,), 12), ("V", V, MOMENT_DTYPE, (), 16), ("f", f, FEATURE_DTYPE, (), 32), ("A_prev", A_prev, np.float32, (3,), 12),
+            ("f_prev", f_prev, FEATURE_DTYPE, (), 32), ("M_prev", M_prev, MOMENT_DTYPE, (), 16), ("A_out", A_out, np.float32, (3,), 12),
+            ("M_out", M_out, MOMENT_DTYPE, (), 16))
+    pitches = [_pixel_pitch(a, name, dt, tail, item) for name, a, dt, tail, item in spec]
+    if any(a.shape[:2] != (h, w) for _, a, _, _, _ in spec) or not (A_out.flags.writeable and M_out.flags.writeable):
+        raise R1Error(R1_EINVAL, "accumulate: the eight arrays are not one frame, or an output is read-only")
+    keep = [a for _, a, _, _, _ in spec]
+    return AccumulateFrame(w, h, *pitches), AccumulateImages(*[a.ctypes.data for a in keep]), A_out, M_out, keep
+
+
+def accumulate_check(frame, opt, view):
+    """r1_accumulate_check: raises R1Error (R1_EINVAL naming the field, R1_ELIMIT at width * height >= 2^31) unless the AccumulateFrame, the
+    AccumulateOpt and the AccumulateView are ones an accumulation accepts; returns the call's ReprojectPlan.  Pure arithmetic."""
+    plan = ReprojectPlan()
+    _check(lib().r1_accumulate_check(C.byref(frame), C.byref(opt), C.byref(view), C.byref(plan)))
+    return plan
+
+
+def accumulate_host(L, V, f, A_prev, f_prev, M_prev, view, opt, A_out=None, M_out=None):
+    """r1_accumulate_host: the accumulation on the CPU, no device: the definition Renderer.accumulate is checked against.  L, A_prev float32
+    (height, width, 3); V, M_prev MOMENT_DTYPE and f, f_prev FEATURE_DTYPE (height, width); arrays or views whose rows lie whole pixels
+    apart.  A_out / M_out: None (new dense arrays) or such arrays — L and V themselves for in place.  Returns (A_out, M_out)."""
+    fr, im, A_out, M_out, keep = _accumulate_target(L, V, f, A_prev, f_prev, M_prev, A_out, M_out)
+    _check(lib().r1_accumulate_host(C.byref(fr), C.byref(opt), C.byref(view), C.byref(im)))
+    return A_out, M_out
 
 
 def quantise_linear(linear):

@@ -1,7 +1,7 @@
 // r1_context.h — what the files that implement the C-ABI on the HIP runtime share: the context, its device buffers, and the steps that
 // one of them defines and another calls.  Private to r1_capi.cpp (context, errors, timing), r1_scene.cpp (scene upload),
 // r1_scene_update.cpp (moving spheres, sphere updates, re-sort), r1_scene_grid.cpp (the grid's upload, regrid), r1_frame.cpp (one frame,
-// step by step), r1_render.cpp (the render entry points), r1_queries.cpp (ray and path queries) and r1_denoise.cpp (denoised frames); C-linkage functions
+// step by step), r1_render.cpp (the render entry points), r1_queries.cpp (ray and path queries), r1_denoise.cpp (denoised frames) and r1_accumulate.cpp (accumulated frames); C-linkage functions
 // shared between files stay in r1_internal.h.
 #ifndef R1_CONTEXT_H
 #define R1_CONTEXT_H
@@ -169,6 +169,12 @@ struct r1_context
     int query_occupancy[R1_JOBS][8] = {{0}}; // blocks per CU of the query kernels, [job][structure slot * 2 + big]; follows the tree as `occupancy` does
     // denoised frames (r1_denoise*, r1_render_denoised*): the filter's records, then what the composed forms keep beside them
     DevBuf denoise_ws;         // r1_denoise.cpp denoise_layout; nothing here is read or written by a render
+    // accumulated frames (r1_accumulate*, r1_render_accumulated*; r1_accumulate.cpp)
+    DevBuf history_ws;         // a 256-byte head (a composed frame's ray count), two history slots {f, M, A} and a dense output frame
+    DevBuf accumulate_io;      // r1_accumulate: the eight images of a call on host memory, dense
+    int history_slot = -1;     // the slot that holds the last accumulated frame; -1: the history is empty
+    int32_t history_w = 0, history_h = 0, history_spp = 0;
+    r1_camera history_cam;     // the context's camera at that call
     // path queries (r1_trace_rays*): one launch in flight per context
     DevBuf trace_stack;        // the paths' attenuation stack, [max_bounces][threads of the launch] hit indices
     // moving spheres (r1_update_centers*): the refit's tables — topology, uploaded once per r1_set_scene — and its scratch
@@ -280,6 +286,43 @@ bool big_scene(const r1_context *c, bool tree, bool grid, bool grid_pixel);
 void fill_scene(const r1_context *c, R1DeviceScene &s);
 void fill_walk(const r1_context *c, bool tree_lds, bool big, uint32_t top_nodes, R1TraceArgs &a);
 int enqueue_frame(r1_context *c, const r1_params *p, FrameJob job); // (by value: the landing set-up redirects its copy's out and rays)
+
+// Two events of the call's own around `work` on the context's stream, then the stream is waited for: the context's events describe the last
+// render.  What the synchronous forms of the filters and of the accumulation time their device work with.
+template <class F> static int timed_sync(r1_context *c, const char *who, double *seconds_out, F work)
+{
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    if (seconds_out)
+    {
+        R1_HIP(hipEventCreate(&ev[0]));
+        if (hipEventCreate(&ev[1]) != hipSuccess)
+        {
+            (void)hipEventDestroy(ev[0]);
+            r1_set_error("%s: hipEventCreate failed", who);
+            return R1_EHIP;
+        }
+    }
+    // (from here on nothing returns before the events are destroyed)
+    hipError_t e = ev[0] ? hipEventRecord(ev[0], c->stream) : hipSuccess;
+    int rc = e == hipSuccess ? work() : R1_OK;
+    if (rc == R1_OK && e == hipSuccess && ev[1])
+        e = hipEventRecord(ev[1], c->stream);
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(c->stream); // (also behind a failed step: nothing of this call is left in flight)
+    float ms = 0;
+    if (rc == R1_OK && e == hipSuccess && ev[0])
+        e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+    if (ev[0])
+        (void)hipEventDestroy(ev[0]), (void)hipEventDestroy(ev[1]);
+    if (rc == R1_OK && e != hipSuccess)
+    {
+        r1_set_error("%s: %s", who, hipGetErrorString(e));
+        rc = R1_EHIP;
+    }
+    if (rc == R1_OK && seconds_out)
+        *seconds_out = ms * 1e-3;
+    return rc;
+}
 
 #pragma GCC visibility pop
 

@@ -81,42 +81,7 @@ extern "C" int r1_denoise_device(r1_context *c, const r1_denoise_frame *fr, cons
     return denoise_enqueue(c, fr, o, d_L, d_f, d_out, hip_stream ? (hipStream_t)hip_stream : c->stream);
 }
 
-// Two events of the call's own around `work` on the context's stream, then the stream is waited for: the context's events describe the last render.
-template <class F> static int timed_sync(r1_context *c, const char *who, double *seconds_out, F work)
-{
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    if (seconds_out)
-    {
-        R1_HIP(hipEventCreate(&ev[0]));
-        if (hipEventCreate(&ev[1]) != hipSuccess)
-        {
-            (void)hipEventDestroy(ev[0]);
-            r1_set_error("%s: hipEventCreate failed", who);
-            return R1_EHIP;
-        }
-    }
-    // (from here on nothing returns before the events are destroyed)
-    hipError_t e = ev[0] ? hipEventRecord(ev[0], c->stream) : hipSuccess;
-    int rc = e == hipSuccess ? work() : R1_OK;
-    if (rc == R1_OK && e == hipSuccess && ev[1])
-        e = hipEventRecord(ev[1], c->stream);
-    if (e == hipSuccess)
-        e = hipStreamSynchronize(c->stream); // (also behind a failed step: nothing of this call is left in flight)
-    float ms = 0;
-    if (rc == R1_OK && e == hipSuccess && ev[0])
-        e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-    if (ev[0])
-        (void)hipEventDestroy(ev[0]), (void)hipEventDestroy(ev[1]);
-    if (rc == R1_OK && e != hipSuccess)
-    {
-        r1_set_error("%s: %s", who, hipGetErrorString(e));
-        rc = R1_EHIP;
-    }
-    if (rc == R1_OK && seconds_out)
-        *seconds_out = ms * 1e-3;
-    return rc;
-}
-
+// (timed_sync, the two events around a call's device work: r1_context.h)
 extern "C" int r1_denoise(r1_context *c, const r1_denoise_frame *fr, const r1_denoise_opt *o, const float *L, const r1_feature *f, float *out,
                           double *device_seconds_out)
 {

@@ -18,6 +18,7 @@ struct R1RegridArgs; // r1_grid_fill.h
 struct R1RadixArgs; // r1_device_sort.h
 struct R1DenoiseArgs; // r1_denoise.h
 struct R1VFilterArgs; // r1_denoise.h
+struct R1ReprojectArgs; // r1_reproject.h
 
 // what r1_sweep_describe says of the sweep's tables besides the arrays
 struct r1_sweep_info
@@ -106,6 +107,14 @@ hipError_t r1_launch_denoise_pass(const R1DenoiseArgs *args, int staged, int las
 // r1_vfilter_kernels.hip: their variance-guided twins, on the same terms
 hipError_t r1_launch_vfilter_prepare(const R1VFilterArgs *args, hipStream_t stream);
 hipError_t r1_launch_vfilter_pass(const R1VFilterArgs *args, int staged, int last, hipStream_t stream);
+
+// r1_reproject_kernels.hip: the kernel of accumulated frames
+hipError_t r1_launch_reproject(const R1ReprojectArgs *args, hipStream_t stream);
+// r1_accumulate_host.cpp: the kernel's arguments from the public structs (the check has passed and left `plan`); what every form refuses of
+// the images behind the check — a NULL pointer, an output that is a history image
+void r1_accumulate_args(const r1_accumulate_frame *fr, const r1_accumulate_opt *o, const r1_accumulate_view *v, const r1_reproject_plan *plan,
+                        const r1_accumulate_images *im, R1ReprojectArgs *a);
+int r1_accumulate_images_check(const char *who, const r1_accumulate_images *im);
 
 // r1_aux_kernels.hip: r1_camera_rays_device
 hipError_t r1_launch_camera_rays(const R1CameraRaysArgs *args, hipStream_t stream);

@@ -68,6 +68,7 @@ extern "C" int r1_set_scene(r1_context *c, const r1_scene *s, const r1_camera *c
         return R1_EINVAL;
     }
     c->pass_valid = false; // (a progressive frame does not continue across a scene upload, even of the same arrays)
+    c->history_slot = -1;  // (nor does the history of accumulated frames)
     R1_HIP(hipSetDevice(c->device));
 
     const float *const src[9] = {s->center_x, s->center_y, s->center_z, s->radius_sq, s->inv_radius, s->albedo_r, s->albedo_g, s->albedo_b, s->mat_param};
