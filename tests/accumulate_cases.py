@@ -27,6 +27,7 @@ OPTION_SETS = {"defaults": {}, "max_samples 1": dict(max_samples=1), "max_sample
 SYNTHETIC = {"1x1": (1, 1), "5x3": (5, 3), "37x21": (37, 21), "70x40": (70, 40)}
 DEVICE_ONLY = {"65x33": (65, 33), "257x17": (257, 17), "150x141": (150, 141)}
 PAIRS = ("identical", "left", "right", "down", "up", "zoom", "turned")  # (i), (ii) x 4, (iii), (v); (iv) is "identical": the camera is axis-aligned
+ROTATED_PAIR, ROTATED_AT = "general", "37x21"  # reproject_truth_cases' two cameras, neither axis-aligned: run at that one size
 RENDERED = {"medium": (33, 17, 3), "large": (64, 48, 4)}
 SPP, SPP_PREV = 4, 3  # of the synthetic pairs: dc.synthetic's hits are 1 .. 4
 
@@ -54,7 +55,11 @@ def make_camera(origin, u, v, w, half_w, half_h):
 
 
 def camera_pair(pair, w, h):
-    """(current, previous) of a synthetic frame: the current camera sits at the origin and looks along -z, axis-aligned"""
+    """(current, previous) of a synthetic frame: the current camera sits at the origin and looks along -z, axis-aligned — but for
+    ROTATED_PAIR, where both cameras are turned about all three axes"""
+    if pair == ROTATED_PAIR:
+        import reproject_truth_cases as rt  # (it imports this module)
+        return rt.cameras("general", w, h)
     hw, hh = 1.0, float(F(h) / F(w))
     X, Y, Z = (1, 0, 0), (0, 1, 0), (0, 0, 1)
     cur = make_camera((0, 0, 0), X, Y, Z, hw, hh)

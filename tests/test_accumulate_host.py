@@ -2,8 +2,9 @@
 the contract restated in numpy (tests/accumulate_cases.py) bit for bit on rendered pairs and on synthetic pairs asserted to hold every block
 the contract names, under seven camera pairs and option sets that cover both ends of every range; a pixel without history carries L's and V's
 bits; the sample count's cap; variances stay non-negative; strides with sentinel bytes; in place; every refusal with its text; the quality of
-an orbit and of a static camera on the medium scene; the census of the new kernel; the stand-alone program under the sanitizers.  What the
-device computes: tests/test_gpu_accumulate.py.  Only the quality test has bounds."""
+an orbit and of a static camera on the medium scene; the census of the new kernel; the stand-alone program under the sanitizers; and both CPU
+forms against the reprojection computed in float64 (tests/reproject_truth_cases.py) under cameras that are not axis-aligned.  What the
+device computes: tests/test_gpu_accumulate.py.  Only the quality tests and the float64 comparison have bounds."""
 import ctypes as C
 import os
 import re
@@ -18,6 +19,7 @@ from rays1bench_amd import binding
 import accumulate_cases as ac
 import denoise_cases as dc
 import guided_cases as gc
+import reproject_truth_cases as rt
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("r1_accumulate_check", "r1_accumulate_host", "r1_accumulate_device", "r1_accumulate", "r1_render_accumulated", "r1_render_accumulated_device",
@@ -106,6 +108,65 @@ def test_synthetic_pairs_hold_every_block_and_the_camera_pairs_do_what_they_are_
     A, M = ac.host_result("synthetic", name, "identical", "high ends")
     lifted = (M["samples"] >= ac.WRAP)
     assert lifted.sum() > 0 and (M["samples"][lifted] == ac.WRAP + ac.SPP).all()
+
+
+def test_synthetic_frames_under_two_rotated_cameras():
+    """the six guard classes of the synthetic frames (NaN depth, the wrap, ...) through a previous camera that is not axis-aligned"""
+    name, pair = ac.ROTATED_AT, ac.ROTATED_PAIR
+    frames, view = ac.synthetic_inputs(name, pair)
+    assert all(abs(x) > 0.01 for k in ("u", "v") for x in ac.cam_fields(view.camera_prev)[k])  # (no component of the basis is 0)
+    for options in sorted(ac.OPTION_SETS):
+        o = ac.opt(**ac.OPTION_SETS[options])
+        *want, stats = ac.numpy_accumulate(*frames, view, o, want_stats=True)
+        got = binding.accumulate_host(*frames, view, o)
+        assert ac.same(got, want), options
+        check_properties(frames, got, o, stats["mask"])
+        if options == "defaults":
+            s = stats
+    assert s["blended"] > 0 and s["surface without history"] > 0 and s["fx exactly 0"] == 0, s
+    for why in ("off the image", "hits", "samples", "depth", "normal"):
+        assert s["skipped"][why] > 0, s["skipped"]
+
+
+# ---- against the geometry in float64 ------------------------------------------------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("size,prev", rt.CASES, ids=lambda v: str(v).replace(" ", "_"))
+def test_both_cpu_forms_look_where_float64_geometry_says(size, prev):
+    """tests/reproject_truth_cases.py: the history is the ramp (x, y, 1), so A_out is the reprojected screen position; the truth is the
+    plane's point projected through the previous camera in float64.  Bound: 32 * 2^-24 * max(w, h) pixels; measured (printed here, table
+    in reproject_truth_cases.py and DESIGN.md §4.41) at most 6.53 of those units."""
+    c = rt.case(size, prev)
+    *want, stats = ac.numpy_accumulate(*c["frames"], c["view"], c["opt"], want_stats=True)
+    got = binding.accumulate_host(*c["frames"], c["view"], c["opt"])
+    print(f"{size} {prev}: compared {c['compared'].mean():.3f} of the frame, numpy {rt.error_in_units(c, want[0]):.2f}, host {rt.error_in_units(c, got[0]):.2f} "
+          f"x 2^-24 max(w, h) px")
+    assert stats["skipped"]["depth"] == 0 and stats["skipped"]["normal"] == 0 and stats["skipped"]["hits"] == 0 and stats["skipped"]["samples"] == 0
+    assert (stats["mask"] | ~c["compared"]).all()  # every compared pixel is blended
+    rt.check_against_truth(c, want, (size, prev, "numpy"))
+    rt.check_against_truth(c, got, (size, prev, "host"))
+    assert ac.same(got, want), (size, prev)  # ... and the two stay bit-equal on camera pairs neither has seen
+
+
+def test_the_truth_cases_tell_the_mistakes_apart():
+    """the float64 truth moves by half a pixel or more under each mistake it is there to catch — a self-check of the cases, in float64
+    alone: nothing of the code under test runs here"""
+    c = rt.case("70x40", "general")
+    w, h = c["size"]
+    m = c["compared"]
+    cur, was = rt.cameras("general", w, h)
+    o, dh, dist = rt.plane_distance(cur, w, h)
+    good = c["truth"][..., :2] / (1.0 - rt.ALPHA)
+
+    def moved(P, cam=was):
+        px, py, _ = rt.screen_position(P, cam, w, h)
+        return float(np.abs(np.stack([px, py], -1) - good)[m].max())
+
+    assert moved(o + dh * dist[..., None]) == 0.0
+    assert moved(o + dh * (dist * rt.SPP_PREV / rt.SPP)[..., None]) >= 0.5       # spp_prev where spp belongs
+    assert moved(o + dh[::-1] * dist[::-1][..., None]) >= 0.5                    # t from the other edge
+    assert moved(o + dh * dist[..., None], cur) >= 0.5                            # the current camera for the previous one
+    assert rt.tolerance(w, h) < 1e-3
 
 
 @pytest.mark.parametrize("name,pair", [("37x21", "left"), ("70x40", "zoom")])

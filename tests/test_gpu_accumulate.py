@@ -1,7 +1,10 @@
 """GPU tests of accumulated frames (include/rays1.h): r1_accumulate_device and r1_accumulate return r1_accumulate_host's two
 images — which tests/test_accumulate_host.py pins to the contract restated in numpy — byte for byte, and r1_render_accumulated* the host
-composition's frames along a camera path, under the history rules.  Nothing here has a tolerance."""
+composition's frames along a camera path, under the history rules: every sentence of the composed form's paragraph in the header has a test
+here.  One bound: the device forms against the reprojection computed in float64 (tests/reproject_truth_cases.py), the tolerance worked
+out there; everything else is bit for bit."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -11,9 +14,14 @@ import rays1bench_amd as r1
 from rays1bench_amd import binding
 
 import accumulate_cases as ac
+import denoise_cases as dc
 import guided_cases as gc
 import linear_cases as lc
+import reproject_truth_cases as rt
+from test_gpu_update import MOVED_RULE
+from test_gpu_update_spheres import edited, material_family
 from test_refit_host import moved_centres, raw_from_arrays
+from test_update_spheres_host import radius_family
 
 pytestmark = pytest.mark.gpu
 
@@ -95,6 +103,45 @@ def test_tiles_crossed_in_x_and_y(renderer, name):
     for pair in ("identical", "left", "zoom"):
         frames, view = ac.synthetic_inputs(name, pair)
         check_both_forms(renderer, frames, view, ac.host_result("synthetic", name, pair), tag=(name, pair))
+
+
+def test_synthetic_frames_under_two_rotated_cameras(renderer):
+    """the guard classes of the synthetic frames through a previous camera that is not axis-aligned: host form, numpy and both device forms"""
+    name, pair = ac.ROTATED_AT, ac.ROTATED_PAIR
+    frames, view = ac.synthetic_inputs(name, pair)
+    for options in sorted(ac.OPTION_SETS):
+        o = ac.opt(**ac.OPTION_SETS[options])
+        want = ac.host_result("synthetic", name, pair, options)
+        assert ac.same(ac.numpy_accumulate(*frames, view, o), want), options
+        check_both_forms(renderer, frames, view, want, o, tag=(name, pair, options))
+        assert ac.same(fetch(renderer, device_result(renderer, frames, view, o, in_place=True), frames[0].shape[1]), want), (options, "in place")
+
+
+@functools.lru_cache(maxsize=None)
+def truth_host_result(size, prev):
+    """r1_accumulate_host of a case of reproject_truth_cases, read-only"""
+    c = rt.case(size, prev)
+    A, M = binding.accumulate_host(*c["frames"], c["view"], c["opt"])
+    A.setflags(write=False), M.setflags(write=False)
+    return A, M
+
+
+@pytest.mark.parametrize("size,prev", rt.CASES, ids=lambda v: str(v).replace(" ", "_"))
+def test_every_device_form_looks_where_float64_geometry_says(renderer, size, prev):
+    """tests/reproject_truth_cases.py: the history is the ramp (x, y, 1), so A_out is where the kernel looked; against the plane's point
+    projected through the previous camera in float64, within 32 * 2^-24 * max(w, h) pixels (the fp32 restatement measures at most 6.53 of
+    those units), and bit for bit the host form."""
+    c = rt.case(size, prev)
+    frames, view, o, w = c["frames"], c["view"], c["opt"], c["size"][0]
+    want = truth_host_result(size, prev)
+    for in_place in (False, True):
+        got = fetch(renderer, device_result(renderer, frames, view, o, in_place=in_place), w)
+        err = rt.check_against_truth(c, got, (size, prev, "device", in_place))
+        assert ac.same(got, want), (size, prev, "device", in_place)
+    A, M, _ = renderer.accumulate(*frames, view, o)
+    rt.check_against_truth(c, (A, M), (size, prev, "host memory"))
+    print(f"{size} {prev}: {err:.2f} x 2^-24 max(w, h) px over {c['compared'].mean():.3f} of the frame")
+    check_both_forms(renderer, frames, view, want, o, tag=(size, prev))
 
 
 @pytest.mark.parametrize("options", sorted(ac.OPTION_SETS))
@@ -195,19 +242,44 @@ def test_refusals_enqueue_nothing_and_leave_the_launch_info_as_it_was(renderer):
 def host_path(cs, cams, w, h, spp, seeds, go=None, o=None):
     """[(frame that goes out, ray count)] of the host composition along `cams`: r1_render_moments_host + r1_render_features_host +
     r1_accumulate_host against the frame before (+ r1_denoise_guided_host of the accumulated frame)"""
+    return [(s["out"], s["rays"]) for s in host_steps(cs, cams, w, h, spp, seeds, go, o)]
+
+
+def per_frame(v, n):
+    """v for each of n frames: a list or tuple holds one value a frame, anything else is every frame's"""
+    if isinstance(v, (list, tuple)):
+        assert len(v) == n
+        return list(v)
+    return [v] * n
+
+
+def host_steps(cs, cams, w, h, spp, seeds, go=None, o=None):
+    """host_path with its parts: one dict a frame — out (what goes out), rays, L, V, f (the frame's own renders), A, M (the history it
+    leaves), passed (True where the frame passed through).  cs, w, h, spp and go may be lists with one value a frame.  The rules of the
+    composed form as the header states them: the history is empty at the first frame and where the size changed; a previous camera the
+    plan refuses passes the frame through; spp_prev is the spp of the frame before; the history is the unfiltered accumulation."""
     o = o or ac.opt()
-    out, A, M, fp, cam_p = [], None, None, None, None
-    for cam, seed in zip(cams, seeds):
-        p = r1.make_params(w, h, spp, seed)
-        L, V, rays = binding.render_moments_host(cs, cam, p)
-        f = binding.render_features_host(cs, cam, p)
-        if A is None:
+    n = len(cams)
+    steps, A, M, fp, cam_p, spp_p, size_p = [], None, None, None, None, None, None
+    for cam, seed, cs_k, w_k, h_k, spp_k, go_k in zip(cams, seeds, per_frame(cs, n), per_frame(w, n), per_frame(h, n), per_frame(spp, n), per_frame(go, n)):
+        p = r1.make_params(w_k, h_k, spp_k, seed)
+        L, V, rays = binding.render_moments_host(cs_k, cam, p)
+        f = binding.render_features_host(cs_k, cam, p)
+        passed = A is None or size_p != (w_k, h_k)
+        if not passed:
+            view = ac.view_of(cam, cam_p, spp_k, spp_p)
+            try:
+                binding.accumulate_check(binding.AccumulateFrame(w_k, h_k, 0, 0, 0, 0, 0, 0, 0, 0), o, view)
+            except binding.R1Error:
+                passed = True
+        if passed:
             A, M = L, V
         else:
-            A, M = binding.accumulate_host(L, V, f, A, fp, M, ac.view_of(cam, cam_p, spp, spp), o)
-        fp, cam_p = f, cam
-        out.append((binding.denoise_guided_host(A, f, M, go) if go is not None else A, rays))
-    return out
+            A, M = binding.accumulate_host(L, V, f, A, fp, M, view, o)
+        fp, cam_p, spp_p, size_p = f, cam, spp_k, (w_k, h_k)
+        steps.append({"out": binding.denoise_guided_host(A, f, M, go_k) if go_k is not None else A, "rays": rays, "L": L, "V": V, "f": f, "A": A, "M": M,
+                      "passed": passed})
+    return steps
 
 
 def differing(a, b):
@@ -302,3 +374,269 @@ def test_a_progressive_accumulation_survives_accumulated_frames(renderer):
     img, total = renderer.render_pass(r1.make_params(w, h, 3, lc.SEED), 2)
     want = renderer.render(r1.make_params(w, h, 5, lc.SEED))
     assert total == want[1] and img.tobytes() == want[0].tobytes()
+
+
+# ---- the history rules, sentence by sentence ------------------------------------------------------------------------------------------------------
+
+NAME, W, H = "medium", 33, 17
+ALL_VARIANTS = (binding.VARIANT_DEFAULT, binding.VARIANT_BVH, binding.VARIANT_GRID, binding.VARIANT_REFERENCE)
+
+
+@functools.lru_cache(maxsize=None)
+def medium():
+    """(scene, four cameras of its orbit): built once, never changed"""
+    sc = lc.SCENES[NAME](W, H)
+    return sc, tuple(binding.orbit_cameras(sc, 64)[:4])
+
+
+def seeds_of(n):
+    return [lc.SEED + k for k in range(n)]
+
+
+def run_path(renderer, cams, seeds, w=W, h=H, spp=2, go=None, variant=binding.VARIANT_DEFAULT, o=None):
+    """[(frame, rays)] of r1_render_accumulated along `cams` on the context as it stands; w, h, spp, go and variant may be lists"""
+    n = len(cams)
+    out = []
+    for cam, seed, w_k, h_k, spp_k, go_k, variant_k in zip(cams, seeds, per_frame(w, n), per_frame(h, n), per_frame(spp, n), per_frame(go, n), per_frame(variant, n)):
+        renderer.set_camera(cam)
+        img, rays, _ = renderer.render_accumulated(r1.make_params(w_k, h_k, spp_k, seed, variant=variant_k), o or ac.opt(), go_k)
+        out.append((img, rays))
+    return out
+
+
+def assert_path(got, want, tag):
+    assert len(got) == len(want)
+    for k, (g, s) in enumerate(zip(got, want)):
+        assert g[1] == s["rays"] and differing(g[0], s["out"]) == 0, (tag, k, differing(g[0], s["out"]))
+
+
+def assert_accumulates(steps, tag=None):
+    """a self-check of a case: these frames are not their own pass-through frames, so a lost history would show"""
+    for k, s in enumerate(steps):
+        assert not s["passed"] and differing(s["A"], s["L"]) > 0, (tag, k)
+
+
+@pytest.mark.parametrize("filtered", [False, True], ids=["accumulated", "accumulated_and_filtered"])
+def test_spp_changes_along_the_path(renderer, filtered):
+    """"... which the call then replaces by its own unfiltered result, feature frame, camera and SPP": spp_prev is the spp of the frame before"""
+    sc, cams = medium()
+    spp, seeds = [2, 4, 3, 2], seeds_of(4)
+    go = gc.opt() if filtered else None
+    want = host_steps(sc.spheres.contents, cams, W, H, spp, seeds, go)
+    assert_accumulates(want[1:])
+    for k in (1, 2, 3):  # the case tells the two apart: with the frame's own spp for spp_prev the composition is another frame
+        s, b = want[k], want[k - 1]
+        wrong, _ = binding.accumulate_host(s["L"], s["V"], s["f"], b["A"], b["f"], b["M"], ac.view_of(cams[k], cams[k - 1], spp[k], spp[k]), ac.opt())
+        assert differing(wrong, s["A"]) > 0, k
+    renderer.set_scene(sc)
+    assert_path(run_path(renderer, cams, seeds, spp=spp, go=go), want, "spp 2, 4, 3, 2")
+
+
+def test_the_variant_switched_between_frames(renderer):
+    sc, cams = medium()
+    seeds = seeds_of(4)
+    want = host_steps(sc.spheres.contents, cams, W, H, 2, seeds)
+    assert_accumulates(want[1:])
+    renderer.set_scene(sc)
+    assert_path(run_path(renderer, cams, seeds, variant=list(ALL_VARIANTS)), want, "DEFAULT, BVH, GRID, REFERENCE")
+
+
+def test_the_filter_switched_on_off_on(renderer):
+    """"(the history keeps the unfiltered accumulation)" whatever went out: a frame behind a filtered one is the unfiltered path's"""
+    sc, cams = medium()
+    seeds = seeds_of(4)
+    go = [gc.opt(), None, gc.opt(), None]
+    want = host_steps(sc.spheres.contents, cams, W, H, 2, seeds, go)
+    assert_accumulates(want[1:])
+    assert differing(want[0]["out"], want[0]["A"]) > 0  # (the filter changes the frame, so a history of filtered frames would show)
+    renderer.set_scene(sc)
+    assert_path(run_path(renderer, cams, seeds, go=go), want, "on, off, on, off")
+
+
+@pytest.mark.parametrize("how", ["update_spheres", "resort_spheres", "regrid"])
+def test_updates_resort_and_regrid_keep_the_history(renderer, how):
+    """"r1_update_*, r1_resort_spheres and r1_regrid keep it": the next frame is the host composition on the updated arrays against the
+    history of the arrays as they were"""
+    sc, cams = medium()
+    a = sc.arrays()
+    variant = binding.VARIANT_GRID if how == "regrid" else binding.VARIANT_DEFAULT
+    renderer.set_scene(sc)
+    first = run_path(renderer, cams[:1], seeds_of(1), variant=variant)  # (through the grid where it is to be re-registered: that builds it)
+    if how == "update_spheres":
+        x, y, z, rsq, inv = radius_family(a, "lattice_x0.25")
+        mats = material_family(a, "permute")
+        renderer.update_spheres(0, radii=(rsq, inv), materials=mats)
+        after = edited(a, None, (rsq, inv), mats)
+    else:
+        x, y, z = moved_centres(a, "jitter")
+        renderer.update_centers(0, x, y, z)
+        renderer.resort_spheres() if how == "resort_spheres" else renderer.regrid()
+        after = edited(a, (x, y, z))
+    moved, keep = raw_from_arrays(after)  # (keep: the arrays `moved` points to)
+    want = host_steps([sc.spheres.contents, moved], cams[:2], W, H, 2, seeds_of(2))
+    assert_accumulates(want[1:], how)
+    renderer.set_camera(cams[1])
+    img, rays, _ = renderer.render_accumulated(r1.make_params(W, H, 2, lc.SEED + 1, variant=variant), ac.opt())
+    assert_path(first + [(img, rays)], want, how)
+    del keep
+
+
+def test_a_refused_call_keeps_the_history(renderer):
+    """"A refused call enqueues nothing and keeps the history": one refusal of each kind in the documented order, down to what
+    r1_render_moments refuses, between two frames; the second is the host path's, not a pass-through"""
+    sc, cams = medium()
+    a = sc.arrays()
+    x, y, z = moved_centres(a, "jitter")
+    moved, keep = raw_from_arrays(edited(a, (x, y, z)))
+    want = host_steps([sc.spheres.contents, moved], cams[:2], W, H, 2, seeds_of(2))
+    assert_accumulates(want[1:])
+    Lb, c, o, go = r1.lib(), renderer._c, ac.opt(), gc.opt()
+    renderer.set_scene(sc)
+    first = run_path(renderer, cams[:1], seeds_of(1))
+    renderer.update_centers(0, x, y, z)  # (keeps the history; the grid is stale from here on)
+    renderer.set_camera(cams[1])
+    frame = torch.full((H, W, 3), 5.0, dtype=torch.float32, device="cuda")
+    cnt = torch.full((2,), 5, dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+    info = renderer.launch_info()
+
+    def p(spp=2, **kw):
+        return r1.make_params(W, H, spp, lc.SEED + 1, **kw)
+
+    refused = [(lambda: renderer.render_accumulated(p(), ac.opt(flags=1)), "flags"),
+               (lambda: renderer.render_accumulated(p(), ac.opt(max_samples=0)), "max_samples"),
+               (lambda: renderer.render_accumulated(p(), o, gc.opt(variance_floor=0.0)), "variance_floor"),
+               (lambda: renderer.render_accumulated(p(variant=binding.VARIANT_PREFILTER), o), "variant"),
+               (lambda: renderer.render_accumulated(p(spp=1), o, go), "spp"),
+               (lambda: renderer.render_accumulated_device(p(), o, None, frame.data_ptr() + 2, cnt.data_ptr()), "aligned"),
+               (lambda: renderer.render_accumulated_device(p(), o, None, frame.data_ptr(), cnt.data_ptr() + 4), "aligned"),
+               (lambda: renderer.render_accumulated(p(shard=0, num_shards=2), o), "num_shards"),                    # r1_render_moments' own
+               (lambda: renderer.render_accumulated(p(variant=binding.VARIANT_GRID), o), MOVED_RULE),                # ... the stale grid
+               (lambda: renderer.render_accumulated_device(p(variant=binding.VARIANT_GRID), o, go, frame.data_ptr(), cnt.data_ptr()), MOVED_RULE)]
+    for k, (call, text) in enumerate(refused):
+        with pytest.raises(binding.R1Error) as e:
+            call()
+        assert e.value.code == binding.R1_EINVAL and text in str(e.value), (k, e.value)
+        assert renderer.launch_info() == info, k
+    assert Lb.r1_render_accumulated(c, None, C.byref(o), None, None, None, None) == binding.R1_EINVAL
+    torch.cuda.synchronize()
+    assert bool((frame == 5).all()) and bool((cnt == 5).all())  # nothing was enqueued
+    img, rays, _ = renderer.render_accumulated(p(), o)
+    assert_path(first + [(img, rays)], want, "after the refusals")
+    del keep
+
+
+def without_w(cam):
+    """a copy of `cam` with w = 0: it renders as before — the kernels read origin, lower_left, horizontal, vertical, u, v and the lens
+    radius — but as a PREVIOUS camera its plan has pw = 0, through which nothing can be projected"""
+    out = binding.CCamera()
+    C.memmove(C.byref(out), C.byref(cam), C.sizeof(out))
+    out.w = (C.c_float * 3)(0, 0, 0)
+    return out
+
+
+def test_a_previous_camera_through_which_nothing_projects(renderer):
+    """"A previous camera through which nothing can be projected also passes the frame through" — and the frame behind it accumulates again"""
+    sc, cams = medium()
+    flat = without_w(cams[1])
+    with pytest.raises(binding.R1Error) as e:
+        binding.accumulate_check(binding.AccumulateFrame(W, H, 0, 0, 0, 0, 0, 0, 0, 0), ac.opt(), ac.view_of(cams[2], flat, 2, 2))
+    assert e.value.code == binding.R1_EINVAL and "camera_prev" in str(e.value)
+    path, seeds = [cams[0], flat, cams[2], cams[3]], seeds_of(4)
+    want = host_steps(sc.spheres.contents, path, W, H, 2, seeds)
+    assert [s["passed"] for s in want] == [True, False, True, False]
+    usual = host_steps(sc.spheres.contents, [cams[0], cams[1]], W, H, 2, seeds[:2])
+    assert differing(want[1]["out"], usual[1]["out"]) == 0  # as the CURRENT camera it is cams[1]: w is not read
+    assert_accumulates([want[1], want[3]])
+    renderer.set_scene(sc)
+    got = run_path(renderer, path, seeds)
+    assert_path(got, want, "c0, flat, c2, c3")
+    renderer.set_camera(cams[2])
+    L, _, rays, _ = renderer.render_moments(r1.make_params(W, H, 2, seeds[2]))
+    assert differing(got[2][0], L) == 0 and got[2][1] == rays  # the frame behind the flat camera is r1_render_moments' frame
+    # ... and as the first frame of a path it is the render itself
+    renderer.accumulate_reset()
+    assert_path(run_path(renderer, [flat, cams[2]], seeds[1:3]), host_steps(sc.spheres.contents, [flat, cams[2]], W, H, 2, seeds[1:3]), "flat first")
+
+
+def test_a_changed_size_that_does_not_grow_the_workspace(renderer):
+    """"... and when width or height differ from the history's": smaller, and the same pixel count with width and height swapped"""
+    sc, cams = medium()
+    w, h = [40, 33, 33, 17, 17], [24, 17, 17, 33, 33]
+    path, seeds = [cams[0], cams[1], cams[2], cams[3], cams[0]], seeds_of(5)
+    want = host_steps(sc.spheres.contents, path, w, h, 2, seeds)
+    assert [s["passed"] for s in want] == [True, True, False, True, False]
+    assert_accumulates([want[2], want[4]])
+    renderer.set_scene(sc)
+    got = run_path(renderer, path, seeds, w=w, h=h)
+    assert_path(got, want, "40x24, 33x17, 33x17, 17x33, 17x33")
+    for k in (1, 3):  # exactly where the size changed: r1_render_moments' frame
+        renderer.set_camera(path[k])
+        L, _, rays, _ = renderer.render_moments(r1.make_params(w[k], h[k], 2, seeds[k]))
+        assert differing(got[k][0], L) == 0 and got[k][1] == rays, k
+
+
+def query_rays(cam, n=64):
+    """n rays from the camera's origin through its screen"""
+    c = ac.cam_fields(cam)
+    rays = np.zeros(n, binding.RAY_DTYPE)
+    s = (np.arange(n, dtype=np.float32) + np.float32(0.5)) / np.float32(n)
+    rays["o"] = c["origin"]
+    rays["d"] = (c["lower_left"] + c["horizontal"] * s[:, None] + c["vertical"] * s[::-1, None]) - c["origin"]
+    rays["t_max"] = np.float32(1e30)
+    return rays
+
+
+def test_the_history_survives_the_other_calls_of_the_context(renderer):
+    """between two accumulated frames every other kind of call runs once at the same size; the second frame is still the host path's"""
+    sc, cams = medium()
+    seeds = seeds_of(2)
+    want = host_steps(sc.spheres.contents, cams[:2], W, H, 2, seeds, [None, gc.opt()])
+    assert_accumulates(want[1:])
+    renderer.set_scene(sc)
+    first = run_path(renderer, cams[:1], seeds[:1])
+    p = r1.make_params(W, H, 2, 99)
+    renderer.render(p)
+    renderer.render_pass(p, 0)
+    renderer.render_adaptive(r1.make_params(W, H, 4, 99), 1, 1, -1, 0)
+    renderer.render_region(p, (3, 2, 20, 9))
+    renderer.render_linear(p)
+    renderer.render_moments(p)
+    renderer.render_features(p)
+    renderer.render_denoised(p, dc.opt())
+    renderer.render_denoised_guided(p, gc.opt())
+    frames, view = ac.synthetic_inputs("37x21", "identical")
+    check_both_forms(renderer, frames, view, ac.host_result("synthetic", "37x21", "identical"))
+    rays = query_rays(cams[0])
+    assert len(renderer.cast_rays(rays)) == len(rays) and len(renderer.trace_rays(rays)) == len(rays)
+    hf = binding.HostFrame(W, H)
+    try:
+        renderer.render_async(p, hf)
+        renderer.sync()
+        assert hf.rays > 0
+    finally:
+        hf.close()
+    assert_path(first + run_path(renderer, cams[1:2], seeds[1:], go=gc.opt()), want, "after the other calls")
+
+
+def test_two_streams_ordered_by_the_caller(renderer):
+    """"the calls of a context are ordered by one stream, or by the caller": frame k on stream A, frame k + 1 on stream B behind an event
+    of A, frame k + 2 through the synchronous form once both are idle"""
+    sc, cams = medium()
+    seeds = seeds_of(3)
+    want = host_steps(sc.spheres.contents, cams[:3], W, H, 2, seeds)
+    assert_accumulates(want[1:])
+    renderer.set_scene(sc)
+    out = [torch.full((H, W, 3), float("nan"), dtype=torch.float32, device="cuda") for _ in range(2)]
+    count = torch.zeros(2, dtype=torch.int64, device="cuda")
+    A, B = torch.cuda.Stream(), torch.cuda.Stream()
+    torch.cuda.synchronize()
+    renderer.set_camera(cams[0])
+    renderer.render_accumulated_device(r1.make_params(W, H, 2, seeds[0]), ac.opt(), None, out[0].data_ptr(), count[0:].data_ptr(), A.cuda_stream)
+    B.wait_stream(A)
+    renderer.set_camera(cams[1])
+    renderer.render_accumulated_device(r1.make_params(W, H, 2, seeds[1]), ac.opt(), None, out[1].data_ptr(), count[1:].data_ptr(), B.cuda_stream)
+    A.synchronize()
+    B.synchronize()
+    got = [(out[k].cpu().numpy(), int(count[k].item())) for k in range(2)]
+    assert_path(got + run_path(renderer, cams[2:3], seeds[2:]), want, "stream A, stream B, synchronous")
