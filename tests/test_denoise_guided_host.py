@@ -2,8 +2,10 @@
 r1_denoise_guided_host equals the contract restated in numpy (tests/guided_cases.py) bit for bit on rendered and synthetic frames whose
 variance frames hold every class of value the contract names, under option sets that cover both flag values and both ends of every range;
 pixels without a hit keep L's bits and no NaN of theirs reaches an output; out == L; strides with sentinel bytes; every refusal of the check;
-the quality test on the medium scene; the census of the new kernels.  What the device computes: tests/test_gpu_denoise_guided.py.  Only the
-quality test has a bound."""
+the quality test on the medium scene; the census of the new kernels; and, against float64 (tests/filter_truth_cases.py), the
+restatement and the host form within a derived rounding bound of the contract's prose, and the cases shown to tell each named mistake of
+the guided filter apart.  What the device computes: tests/test_gpu_denoise_guided.py.  Only the quality test and the float64 tests have a
+bound."""
 import ctypes as C
 import os
 import re
@@ -16,6 +18,7 @@ import rays1bench_amd as r1
 from rays1bench_amd import binding
 
 import denoise_cases as dc
+import filter_truth_cases as tc
 import guided_cases as gc
 import linear_cases as lc
 
@@ -70,6 +73,34 @@ def test_synthetic_variance_frames_hold_every_class_of_input(name):
     V0 = V.copy()
     V0["var"][f["hits"] == 0] = 0
     assert bits(binding.denoise_guided_host(L, f, V0, gc.opt(iterations=gc.inputs(name)[3]))).tobytes() == bits(out).tobytes()
+
+
+# ---- against the float64 truth ------------------------------------------------------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("flags", tc.FLAGS)
+@pytest.mark.parametrize("name", list(tc.CASES))
+def test_restatement_and_host_form_are_the_float64_truth_within_the_bound(name, flags):
+    """max |out - truth| <= (32 + 2^k / 4) n u max |truth|, and pixels without a hit carry L's bits (their variance is NaN: never read)"""
+    L, f, V = tc.inputs(name)
+    o = tc.options(name, flags, guided=True)
+    a = tc.check_against_truth(gc.numpy_guided(L, f, V, o), name, flags, True, "numpy_denoise_guided")
+    b = tc.check_against_truth(binding.denoise_guided_host(L, f, V, o), name, flags, True, "r1_denoise_guided_host")
+    assert a == b  # (the two are one frame bit for bit)
+
+
+@pytest.mark.parametrize("mistake", tc.GUIDED_MISTAKES + tc.SHARED_MISTAKES)
+def test_the_truth_cases_tell_the_mistakes_apart(mistake):
+    """float64 only: each named mistake, made in truth_filter, moves the guided truth of some case by at least 100 times that case's bound"""
+    ratios = {}
+    for name in ("general 41x23", "general 7x5"):
+        o = tc.options(name, 0, True).base
+        for flags in tc.FLAGS:
+            ratios[name, flags] = tc.shift_in_units(name, flags, True, mistake) / tc.bound_in_units(o.iterations, o.normal_power_log2)
+    print(mistake, {k: f"{v:.3g}" for k, v in ratios.items()})
+    assert max(ratios.values()) >= 100, (mistake, ratios)
+    if mistake == "v over a, not a^2":  # a mistake of demodulation alone
+        assert ratios["general 41x23", 0] == 0 and ratios["general 41x23", binding.DENOISE_DEMODULATE] >= 100
 
 
 @pytest.mark.parametrize("name", ["medium", "37x21"])

@@ -2,8 +2,10 @@
 contract re-stated in numpy (tests/denoise_cases.py) bit for bit on rendered and synthetic frames whose classes of input are asserted; pixels
 without a hit keep L's bits; in place; strides with sentinels; both flag values and the ends of every option's range; every refusal with its
 text; the quality bound on the medium scene; the drop-in program's refusals; the census of the new kernels; tools/check_denoise_host.cpp
-under the address and undefined-behaviour sanitizers.  What the device computes is checked in tests/test_gpu_denoise.py.  Every comparison
-of frames is tobytes() equality."""
+under the address and undefined-behaviour sanitizers; and, against float64 (tests/filter_truth_cases.py), the restatement
+and the host form within a derived rounding bound of the contract's prose computed as a per-pixel gather, that truth against a closed form
+where the filter is the iterated B3 spline, and the cases shown to tell each named mistake apart.  What the device computes is checked in
+tests/test_gpu_denoise.py.  Every comparison of fp32 frames with each other is tobytes() equality; only the float64 tests have a bound."""
 import ctypes as C
 import os
 import re
@@ -18,6 +20,7 @@ from rays1bench_amd import binding
 
 import denoise_cases as dc
 import feature_cases as fc
+import filter_truth_cases as tc
 import linear_cases as lc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -116,6 +119,56 @@ def test_strides_with_sentinel_bytes_between_the_rows_stay_untouched(name):
     # in place through a strided view: the bytes between L's rows stay
     binding.denoise_host(Lv, fv, dc.opt(), out=Lv)
     assert Lv.tobytes() == got.tobytes() and (Lbuf[:, w:].view(np.uint8) == dc.PREFILL).all()
+
+
+# ---- against the float64 truth ------------------------------------------------------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("flags", tc.FLAGS)
+@pytest.mark.parametrize("name", list(tc.CASES))
+def test_restatement_and_host_form_are_the_float64_truth_within_the_bound(name, flags):
+    """max |out - truth| <= (32 + 2^k / 4) n u max |truth|, and pixels without a hit carry L's bits"""
+    L, f, _ = tc.inputs(name)
+    o = tc.options(name, flags, guided=False)
+    a = tc.check_against_truth(dc.numpy_denoise(L, f, o), name, flags, False, "numpy_denoise")
+    b = tc.check_against_truth(binding.denoise_host(L, f, o), name, flags, False, "r1_denoise_host")
+    assert a == b  # (the two are one frame bit for bit)
+
+
+@pytest.mark.parametrize("name", tc.NEUTRAL_FULL)
+def test_the_truth_is_the_iterated_b3_spline_where_every_weight_is_h(name):
+    """a (A_y (L / a) A_x^T) by matrix products against truth_filter's gather, to 1e-12 relative: both filters, both flags"""
+    L, f, _ = tc.inputs(name)
+    for flags in tc.FLAGS:
+        for guided in (False, True):
+            o = tc.options(name, flags, guided)
+            want = tc.closed_form(L, f, o.base if guided else o)
+            got = tc.truth(name, flags, guided)
+            assert np.abs(got - want).max() <= 1e-12 * np.abs(want).max(), (name, flags, guided)
+    if name != "neutral_full 1x1":
+        assert np.abs(tc.truth(name, 0, False) - L).max() > 0.01 * np.abs(L).max()  # (and the spline is no identity)
+
+
+@pytest.mark.parametrize("mistake", tc.UNGUIDED_MISTAKES + tc.SHARED_MISTAKES)
+def test_the_truth_cases_tell_the_mistakes_apart(mistake):
+    """float64 only: each named mistake, made in truth_filter, moves some case by at least 100 times that case's bound"""
+    ratios = {}
+    for name in ("general 41x23", "neutral_full 41x23", "neutral_holes 41x23"):
+        o = tc.options(name, 0, False)
+        for flags in tc.FLAGS:
+            ratios[name, flags] = tc.shift_in_units(name, flags, False, mistake) / tc.bound_in_units(o.iterations, o.normal_power_log2)
+    print(mistake, {k: f"{v:.3g}" for k, v in ratios.items()})
+    assert max(ratios.values()) >= 100, (mistake, ratios)
+    if mistake in ("H all fifths", "step = i + 1", "bounds transposed"):  # what the neutral cases are there for
+        assert ratios["neutral_full 41x23", 0] >= 100 and ratios["neutral_holes 41x23", 0] >= 100, (mistake, ratios)
+
+
+def test_transposing_the_tap_address_alone_is_no_mistake():
+    """H[dy + 2] * H[dx + 2] is symmetric: p + step * (dy, dx) for p + step * (dx, dy) is the same sum in another order.  Only its rounding
+    differs, which the bit-for-bit chain pins; the transposition that is a mistake is the bounds', above."""
+    for name in ("general 41x23", "neutral_holes 41x23"):
+        for guided in (False, True):
+            assert tc.shift_in_units(name, binding.DENOISE_DEMODULATE, guided, "tap address transposed") < 1e-6, (name, guided)
 
 
 # ---- refusals -----------------------------------------------------------------------------------------------------------------------------------

@@ -3,7 +3,8 @@
 workgroup tiles with clipped halos on all four edges, and large enough for whole step-16 kernels; every iteration count through the
 LDS-staged and the direct passes; the ends of normal_power_log2; both flags; a torch tensor on a stream of its own; in place; strides and
 sentinels; refusals; r1_render_denoised against the host composition for every variant; the context's state before and after; a moved
-scene; and the drop-in program's PFM file."""
+scene; the drop-in program's PFM file; and all three device forms, in place too, against the float64 truth of the contract's prose within
+its derived bound (tests/filter_truth_cases.py) — the only test here with a bound."""
 import ctypes as C
 import os
 import subprocess
@@ -17,6 +18,7 @@ from rays1bench_amd import binding
 
 import denoise_cases as dc
 import feature_cases as fc
+import filter_truth_cases as tc
 import linear_cases as lc
 from test_refit_host import moved_centres, raw_from_arrays
 
@@ -84,6 +86,25 @@ def test_both_device_forms_equal_the_host_form(renderer, name):
     got, secs = renderer.denoise(L, f, dc.opt(iterations=it))
     assert got.tobytes() == want.tobytes(), (name, "host memory", mismatch(got, want))
     assert secs > 0
+
+
+@pytest.mark.parametrize("name", tc.DEVICE_CASES)
+def test_the_device_forms_are_the_float64_truth_within_the_bound(renderer, name):
+    """r1_denoise_device out of place and with d_out == d_L, and r1_denoise, both flag values: max |out - truth| <= (32 + 2^k / 4) n u
+    max |truth|, pixels without a hit carry L's bits, and the error is the host form's to the digit"""
+    L, f, _ = tc.inputs(name)
+    h, w = f.shape
+    for flags in tc.FLAGS:
+        o = tc.options(name, flags, guided=False)
+        host = tc.check_against_truth(binding.denoise_host(L, f, o), name, flags, False, "r1_denoise_host")
+        errs = {"r1_denoise_device": tc.check_against_truth(device_denoise(renderer, L, f, o), name, flags, False, "r1_denoise_device")}
+        dL, df = on_device(L), on_device(f)
+        torch.cuda.synchronize()
+        renderer.denoise_device(w, h, o, dL.data_ptr(), df.data_ptr(), dL.data_ptr())
+        renderer.sync()
+        errs["in place"] = tc.check_against_truth(dL.cpu().numpy(), name, flags, False, "r1_denoise_device, d_out == d_L")
+        errs["r1_denoise"] = tc.check_against_truth(renderer.denoise(L, f, o)[0], name, flags, False, "r1_denoise")
+        assert all(e == host for e in errs.values()), (name, flags, host, errs)
 
 
 @pytest.mark.parametrize("iterations", [1, 2, 3, 4, 5, 6])

@@ -1,6 +1,7 @@
 """GPU tests of variance-guided denoised frames (include/rays1.h): r1_denoise_guided_device and r1_denoise_guided return
 r1_denoise_guided_host's frame — which tests/test_denoise_guided_host.py pins to the contract restated in numpy — byte for byte, and
-r1_render_denoised_guided* the host composition's.  Nothing here has a tolerance."""
+r1_render_denoised_guided* the host composition's; and all three device forms, in place too, lie within the derived bound of the float64
+truth of the contract's prose (tests/filter_truth_cases.py) — the only test here with a bound."""
 import ctypes as C
 
 import numpy as np
@@ -11,6 +12,7 @@ import rays1bench_amd as r1
 from rays1bench_amd import binding
 
 import denoise_cases as dc
+import filter_truth_cases as tc
 import guided_cases as gc
 import linear_cases as lc
 
@@ -61,6 +63,20 @@ def test_both_device_forms_are_the_host_form(renderer, name):
     assert differing(out, want) == 0 and secs > 0
     none = f["hits"] == 0
     assert bits(got)[none].tobytes() == bits(L)[none].tobytes()
+
+
+@pytest.mark.parametrize("name", tc.DEVICE_CASES)
+def test_the_device_forms_are_the_float64_truth_within_the_bound(renderer, name):
+    """r1_denoise_guided_device out of place and in place, and r1_denoise_guided, both flag values: max |out - truth| <= (32 + 2^k / 4) n u
+    max |truth|, pixels without a hit carry L's bits (their variance is NaN), and the error is the host form's to the digit"""
+    L, f, V = tc.inputs(name)
+    for flags in tc.FLAGS:
+        o = tc.options(name, flags, guided=True)
+        host = tc.check_against_truth(binding.denoise_guided_host(L, f, V, o), name, flags, True, "r1_denoise_guided_host")
+        errs = {"out of place": tc.check_against_truth(device_result(renderer, L, f, V, o), name, flags, True, "r1_denoise_guided_device"),
+                "in place": tc.check_against_truth(device_result(renderer, L, f, V, o, in_place=True), name, flags, True, "r1_denoise_guided_device, in place"),
+                "host memory": tc.check_against_truth(renderer.denoise_guided(np.array(L), f, V, o)[0], name, flags, True, "r1_denoise_guided")}
+        assert all(e == host for e in errs.values()), (name, flags, host, errs)
 
 
 @pytest.mark.parametrize("iterations", [1, 2, 3, 4, 5, 6])

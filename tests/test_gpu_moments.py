@@ -1,6 +1,8 @@
 """GPU tests of variance frames (include/rays1.h): r1_render_moments and r1_render_moments_device return r1_render_linear's
 frame and ray count and, per pixel, the record r1_render_moments_host returns — which tests/test_moments_host.py pins to the contract
-restated on the oracle's records.  Every expectation is BYTE FOR BYTE; nothing here has a tolerance."""
+restated on the oracle's records.  Every such expectation is BYTE FOR BYTE.  Against float64 (tests/moment_cases.py): the
+device's variances within the derived bound of the plain statistic on the records r1_render_samples returns for the same params, and the
+ratio over 48 seeds that says the estimate is unbiased and of the mean — the only two tests here with a bound."""
 import ctypes as C
 
 import numpy as np
@@ -63,6 +65,34 @@ def test_both_device_forms_are_the_host_form_whatever_the_tiles(renderer, name, 
         assert lc.same_bits(lin_d, want_L) and mc.same_records(mom_d, want), (tw, th, mc.differing(mom_d["var"], want["var"]))
     plain, plain_rays, _ = renderer.render_linear(r1.make_params(w, h, spp, lc.SEED))
     assert plain_rays == want_rays and lc.same_bits(plain, want_L)
+
+
+@pytest.mark.parametrize("name,w,h,spp", [fr for fr in lc.FRAMES if fr[3] > 1] + [("large", 24, 15, 64), ("medium", 24, 15, 2)], ids=lambda v: str(v))
+def test_both_device_forms_are_the_float64_variance_of_the_mean_of_the_devices_own_records(renderer, name, w, h, spp):
+    """var against x.var(ddof=1) / n in float64 of the records r1_render_samples returns for the same params:
+    |var - truth| <= (2n + 8) u truth + n^2 / (n - 1) u^2 L64^2"""
+    renderer.set_scene(lc.SCENES[name](w, h))
+    p = r1.make_params(w, h, spp, lc.SEED)
+    _, rays, samples = renderer.render_samples(p)
+    rec = samples.reshape(h, w, spp, 4)
+    lin, mom, got_rays, _ = renderer.render_moments(p)
+    assert got_rays == rays
+    assert np.abs(lin.astype(np.float64) - mc.truth_variance(rec)[1]).max() <= (spp + 1) * 2.0 ** -24 * np.abs(rec[..., :3]).max()  # (the records are this frame's)
+    a = mc.check_variance(mom, rec, f"r1_render_moments {name} {w}x{h}")
+    _, mom_d, _ = device_frame(renderer, p)
+    b = mc.check_variance(mom_d, rec, f"r1_render_moments_device {name} {w}x{h}")
+    assert a == b
+
+
+@pytest.mark.parametrize("n", mc.SEEDS_SPP)
+def test_the_estimate_is_unbiased_and_of_the_mean_over_48_seeds(renderer, n):
+    """R = sum var_over_seeds(L) / sum mean_over_seeds(var) from r1_render_moments' frames: nearer to 1 than to n / (n - 1)"""
+    name, w, h = mc.SEEDS_FRAME
+    renderer.set_scene(lc.SCENES[name](w, h))
+    frames = [renderer.render_moments(r1.make_params(w, h, n, seed))[:2] for seed in mc.SEEDS]
+    R = mc.seeds_ratio(frames)
+    print(f"{name} {w}x{h}x{n}, {len(mc.SEEDS)} seeds: R = {R:.4f}, band {np.exp(mc.seeds_band(n)):.4f}")
+    assert abs(np.log(R)) < mc.seeds_band(n)
 
 
 @pytest.mark.parametrize("vname", sorted(VARIANTS))

@@ -1,7 +1,9 @@
 """CPU tests of variance frames (include/rays1.h): every new name is declared, exported and bound; r1_render_moments_host equals
 the contract restated in numpy (tests/moment_cases.py) on the ORACLE's per-sample records, bit for bit, and its linear frame is
 r1_render_linear_host's; the restatement's inputs are the REFERENCE's own records where a fixture holds them at 64 samples a pixel; the
-refusals; the census of the new kernel.  What the device computes is checked in tests/test_gpu_moments.py.  Nothing here has a tolerance."""
+refusals; the census of the new kernel; and, against float64, both the restatement and the host form within a derived
+rounding bound of the plain statistic on the same records, and the ratio over 48 seeds that says the estimate is unbiased and of the MEAN.
+What the device computes is checked in tests/test_gpu_moments.py.  Only the two float64 tests have a bound; both are tests/moment_cases.py's."""
 import ctypes as C
 import os
 import re
@@ -135,6 +137,47 @@ def test_host_form_at_64_samples_is_the_restatement_on_the_oracles_records():
     lin, mom, got_rays = mc.host_frame(name, w, h, spp)
     assert got_rays == rays and lc.same_bits(lin, want_L) and mc.same_records(mom, want)
     assert (mom["samples"] == 64).all() and (mom["var"] >= 0).all() and (mom["var"] > 0).any()
+
+
+# ---- against float64 (tests/moment_cases.py has the bounds and what was measured) ----------------------------------------------------------------
+
+TRUTH_FRAMES = [fr for fr in lc.FRAMES if fr[3] > 1] + [("large", 24, 15, 64), ("medium", 24, 15, 2)]
+
+
+@pytest.mark.parametrize("name,w,h,spp", TRUTH_FRAMES, ids=lambda v: str(v))
+def test_restatement_and_host_form_are_the_float64_variance_of_the_mean_within_the_bound(name, w, h, spp):
+    """var against x.var(ddof=1) / n of the oracle's records in float64: |var - truth| <= (2n + 8) u truth + n^2 / (n - 1) u^2 L64^2"""
+    rec, _ = lc.oracle_records(name, w, h, spp)
+    _, restated = mc.moments_of(rec)
+    _, mom, _ = mc.host_frame(name, w, h, spp)
+    for tag, got in (("numpy restatement", restated), ("r1_render_moments_host", mom)):
+        mc.check_variance(got, rec, f"{tag} {name} {w}x{h}")
+
+
+def test_the_bounds_second_term_is_needed_equal_samples_whose_fp32_mean_is_not_the_sample():
+    """three equal samples: the float64 variance is 0, the fp32 mean of some values is off by an ulp and var is not 0 — within the bound
+    only by its second term"""
+    x = np.float32(0.1)
+    rec = np.full((1, 1, 3, 4), x, np.float32)
+    L, mom = mc.moments_of(rec)
+    assert L[0, 0, 0] != x and mom["var"][0, 0, 0] > 0  # (0.1f + 0.1f + 0.1f) * (1 / 3.0f) is not 0.1f
+    want, _ = mc.truth_variance(rec)
+    assert not want.any()
+    mc.check_variance(mom, rec, "three equal samples")
+
+
+@pytest.mark.parametrize("n", mc.SEEDS_SPP)
+def test_the_estimate_is_unbiased_and_of_the_mean_over_48_seeds(n):
+    """R = sum var_over_seeds(L) / sum mean_over_seeds(var) is nearer to 1 than to n / (n - 1); here within a third of that band"""
+    name, w, h = mc.SEEDS_FRAME
+    sc = lc.SCENES[name](w, h)
+    frames = [binding.render_moments_host(sc.spheres.contents, sc.camera.contents, r1.make_params(w, h, n, seed))[:2] for seed in mc.SEEDS]
+    R = mc.seeds_ratio(frames)
+    print(f"{name} {w}x{h}x{n}, {len(mc.SEEDS)} seeds: R = {R:.4f}, band {np.exp(mc.seeds_band(n)):.4f}")
+    assert abs(np.log(R)) < mc.seeds_band(n)
+    assert abs(np.log(R)) < mc.seeds_band(n) / 3  # (else: more seeds, not a wider band)
+    # what the two mistakes of the scale would give lies outside: var * (n - 1) / n for 1 / n^2, var * n for a forgotten / n
+    assert abs(np.log(R * n / (n - 1))) > mc.seeds_band(n) and abs(np.log(R / n)) > mc.seeds_band(n)
 
 
 def test_host_form_refusals_with_their_texts():
