@@ -218,18 +218,8 @@ extern "C" int r1_render_accumulated_device(r1_context *c, const r1_params *p, c
                                             void *d_num_rays, void *hip_stream)
 {
     int rc = composed_check("r1_render_accumulated_device", c, p, o, go);
-    if (rc)
+    if (rc || (rc = device_outputs_check("r1_render_accumulated_device", c, d_rgb_f32, d_num_rays)))
         return rc;
-    if (!d_rgb_f32 || !d_num_rays || ((uintptr_t)d_rgb_f32 & 3u) || ((uintptr_t)d_num_rays & 7u))
-    {
-        r1_set_error("r1_render_accumulated_device: d_rgb_f32 must be non-NULL and 4-byte aligned, d_num_rays non-NULL and 8-byte aligned");
-        return R1_EINVAL;
-    }
-    if (!c->have_scene) // (before a workspace is grown: a refused call changes nothing)
-    {
-        r1_set_error("no scene set (call r1_set_scene first)");
-        return R1_EINVAL;
-    }
     R1_HIP(hipSetDevice(c->device));
     if ((rc = history_ensure(c, p)))
         return rc;
@@ -258,15 +248,6 @@ extern "C" int r1_render_accumulated(r1_context *c, const r1_params *p, const r1
     const size_t n = (size_t)p->width * p->height;
     const HistoryLayout l = history_layout(n);
     char *const ws = (char *)c->history_ws.p;
-    if ((rc = timed_sync(c, "r1_render_accumulated", device_seconds_out, [&] { return composed_enqueue(c, p, o, go, ws + l.out, ws, c->stream); })))
-        return rc;
-    uint64_t rays = 0;
-    R1_HIP(hipMemcpyAsync(rgb_out, ws + l.out, n * 12, hipMemcpyDeviceToHost, c->stream));
-    R1_HIP(hipMemcpyAsync(&rays, ws, 8, hipMemcpyDeviceToHost, c->stream));
-    R1_HIP(hipStreamSynchronize(c->stream));
-    if ((rc = land_check(c)))
-        return rc;
-    if (num_rays_out)
-        *num_rays_out = rays;
-    return R1_OK;
+    return timed_render_home(c, "r1_render_accumulated", device_seconds_out, ws + l.out, ws, n, rgb_out, num_rays_out,
+                             [&] { return composed_enqueue(c, p, o, go, ws + l.out, ws, c->stream); });
 }

@@ -324,6 +324,43 @@ template <class F> static int timed_sync(r1_context *c, const char *who, double 
     return rc;
 }
 
+// The end of a composed synchronous render (r1_render_denoised, r1_render_denoised_guided, r1_render_accumulated): `enqueue` under timed_sync,
+// then the frame of n pixels at d_rgb and the 8-byte ray word at d_rays come home, and a resolver that gave up is reported.
+template <class F>
+static int timed_render_home(r1_context *c, const char *who, double *seconds_out, const void *d_rgb, const void *d_rays, size_t n, float *rgb_out,
+                             uint64_t *num_rays_out, F enqueue)
+{
+    int rc = timed_sync(c, who, seconds_out, enqueue);
+    if (rc)
+        return rc;
+    uint64_t rays = 0;
+    R1_HIP(hipMemcpyAsync(rgb_out, d_rgb, n * 12, hipMemcpyDeviceToHost, c->stream));
+    R1_HIP(hipMemcpyAsync(&rays, d_rays, 8, hipMemcpyDeviceToHost, c->stream));
+    R1_HIP(hipStreamSynchronize(c->stream));
+    if ((rc = land_check(c)))
+        return rc;
+    if (num_rays_out)
+        *num_rays_out = rays;
+    return R1_OK;
+}
+
+// What their device siblings refuse behind their own checks: the two outputs, then a context without a scene (before a workspace is grown:
+// a refused call changes nothing)
+inline int device_outputs_check(const char *who, const r1_context *c, const void *d_rgb_f32, const void *d_num_rays)
+{
+    if (!d_rgb_f32 || !d_num_rays || ((uintptr_t)d_rgb_f32 & 3u) || ((uintptr_t)d_num_rays & 7u))
+    {
+        r1_set_error("%s: d_rgb_f32 must be non-NULL and 4-byte aligned, d_num_rays non-NULL and 8-byte aligned", who);
+        return R1_EINVAL;
+    }
+    if (!c->have_scene)
+    {
+        r1_set_error("no scene set (call r1_set_scene first)");
+        return R1_EINVAL;
+    }
+    return R1_OK;
+}
+
 #pragma GCC visibility pop
 
 #endif

@@ -139,7 +139,7 @@ struct R1DenoiseArgs
     int32_t step;
 };
 
-// The guided kernels (r1_vfilter_kernels.hip): the same records and fields (d.sc2: sigma_color squared), and the variance beside them
+// The guided kernels (r1_vfilter_*): the same records and fields (d.sc2: sigma_color squared), and the variance beside them
 struct R1VFilterArgs
 {
     R1DenoiseArgs d;

@@ -16,7 +16,6 @@ struct R1SetArgs;
 struct R1SortArgs; // r1_bvh_sort.h
 struct R1RegridArgs; // r1_grid_fill.h
 struct R1RadixArgs; // r1_device_sort.h
-struct R1DenoiseArgs; // r1_denoise.h
 struct R1VFilterArgs; // r1_denoise.h
 struct R1ReprojectArgs; // r1_reproject.h
 
@@ -100,13 +99,11 @@ hipError_t r1_scatter_rays_occupancy(int variant, int big, size_t dyn_lds, int *
 hipError_t r1_launch_features(const R1FeatureArgs *args, int variant, int big, int blocks, size_t dyn_lds, hipStream_t stream);
 hipError_t r1_features_occupancy(int variant, int big, size_t dyn_lds, int *blocks_per_cu);
 
-// r1_denoise_kernels.hip: the kernels of denoised frames.  staged: tile and halo through LDS (steps <= R1D_STAGE_MAX_STEP, else
-// hipErrorInvalidValue); last: the pass that re-modulates and writes `out`
-hipError_t r1_launch_denoise_prepare(const R1DenoiseArgs *args, hipStream_t stream);
-hipError_t r1_launch_denoise_pass(const R1DenoiseArgs *args, int staged, int last, hipStream_t stream);
-// r1_vfilter_kernels.hip: their variance-guided twins, on the same terms
-hipError_t r1_launch_vfilter_prepare(const R1VFilterArgs *args, hipStream_t stream);
-hipError_t r1_launch_vfilter_pass(const R1VFilterArgs *args, int staged, int last, hipStream_t stream);
+// r1_denoise_kernels.hip: the kernels of denoised frames and of their variance-guided form (§4.40).  guided: the r1_vfilter
+// kernels, which read all of *args; otherwise the r1_denoise kernels, which read args->d alone.  staged: tile and halo through LDS (steps <=
+// R1D_STAGE_MAX_STEP, else hipErrorInvalidValue); last: the pass that re-modulates and writes `out`
+hipError_t r1_launch_denoise_prepare(const R1VFilterArgs *args, int guided, hipStream_t stream);
+hipError_t r1_launch_denoise_pass(const R1VFilterArgs *args, int guided, int staged, int last, hipStream_t stream);
 
 // r1_reproject_kernels.hip: the kernel of accumulated frames
 hipError_t r1_launch_reproject(const R1ReprojectArgs *args, hipStream_t stream);

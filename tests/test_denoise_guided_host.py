@@ -248,7 +248,7 @@ def check_program(tmp_path_factory):
     import subprocess
     out = str(tmp_path_factory.mktemp("denoise_guided_host") / "check_denoise_guided_host")
     src = [os.path.join(ROOT, "tools", "check_denoise_guided_host.cpp")] + [os.path.join(ROOT, "rays1bench_amd", "csrc", f) for f in
-                                                                          ("r1_denoise_guided_host.cpp", "r1_denoise_host.cpp")]
+                                                                          ("r1_denoise_host.cpp",)]
     inc = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include")
     assert os.path.isdir(inc), "the HIP headers are needed to compile the library's host sources"
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off",

@@ -1,4 +1,4 @@
-// tools/check_denoise_guided_host.cpp — r1_denoise_guided_host (rays1bench_amd/csrc/r1_denoise_guided_host.cpp with r1_denoise_host.cpp, whose
+// tools/check_denoise_guided_host.cpp — r1_denoise_guided_host (rays1bench_amd/csrc/r1_denoise_host.cpp, beside the unguided form whose
 // check it shares) driven stand-alone: the contract of include/rays1.h "variance-guided denoised frames" once more in plain C loops over
 // dense arrays, with nothing of r1_denoise.h, compared bit for bit on a seeded frame under several sets of options; in place; rows with
 // strides in buffers sized to the last pixel, so a sanitizer sees any access between or behind the rows; the refusals.  Built by
